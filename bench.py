@@ -4,8 +4,10 @@
 Metric (BASELINE.json): Msplats rasterized/s, forward+backward, plus train-step ms and the HBM-roofline fraction.
 A "step" is one gradient-exchange batch: `--views-per-step` (default 8) independent views per rank through the per-view
 hot path, their curve-parameter gradients summed and (N > 1) all-reduced once -- the unit BASELINE's "train-step" implies.
-The timed region is the K-step region repeated until it lasts >= --min-seconds (3 s; `repeats`, `views_timed` in the output; `steps`
-and `warmup` are echoed unchanged), so the driver's small K still measures a steady state.  One view is:
+The timed region is exactly `--steps` K steps after `--warmup` W untimed ones; `ms_per_step` in the output is its length / K, so
+K for a steady-state measurement (a region of seconds, not the default's tens of ms) can be chosen from a short run.
+`--dump-outputs DIR` writes what the last timed step computed (the step's summed curve-parameter gradients and the last view's
+outputs) as DIR/<name>.npy.  One view is:
     rasterizer forward  (preprocess -> tile binning + per-tile depth sort -> alpha-composite)
   + rasterizer backward (dL/d{mean2D,conic,opacity,colour,all_map} -> dL/d{mean3D,scale,rotation})
 with inputs already resident in HBM (SURVEY.md section 8d "raster-only benchmark": dL_dcolor ~ N(0,1)*1e-3,
@@ -181,11 +183,13 @@ def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=32,
-                    help="timed steps; one step = one gradient-exchange batch of --views-per-step views per rank "
-                         "(raster mode: one view)")
+                    help="timed steps, exactly; one step = one gradient-exchange batch of --views-per-step views per rank "
+                         "(raster mode: one view).  The default region is short (~60 ms on cfg3): for a steady-state "
+                         "number choose K from a short run's ms_per_step so that the region lasts seconds")
     ap.add_argument("--warmup", type=int, default=4)
     ap.add_argument("--min-seconds", type=float, default=3.0,
-                    help="the K-step region is repeated (inside one barrier-bracketed timing) until it lasts this long")
+                    help="multi-rank runs: the single-GPU diagnostic (`own_n1`) repeats the K-step region until it lasts "
+                         "min(1 s, this); the timed region itself is always exactly K steps")
     ap.add_argument("--config", default="cfg3")
     ap.add_argument("--mode", default="view", choices=["view", "raster"],
                     help="view: full per-view hot path (curve sampling -> splat attrs -> raster fwd+bwd -> curve grads "
@@ -224,7 +228,13 @@ def parse_args(argv=None):
     ap.add_argument("--fused-sort", type=int, default=-1, choices=[-1, 0, 1],
                     help="A/B: tile sort inside the forward compositor (sets CGS_FUSED_TILE_SORT, which the library reads once); "
                          "-1 = library default")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32; "
+                         "at most 64 MB in all, larger arrays as a fixed seeded sample)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error(f"--steps {args.steps}: need at least one timed step")
+    return args
 
 
 def start_rank(args):
@@ -336,6 +346,56 @@ class Workload:
             self.empty, self.empty, 0, cam.camera_center, gB, R, bB, iB, False, True, False)
 
 
+# the gradient tuple of _C.rasterize_gaussians_backward, in its order
+RASTER_GRAD_NAMES = ("dL_dmeans2D", "dL_dcolors", "dL_dopacity", "dL_dmeans3D", "dL_dcov3D", "dL_dsh", "dL_dscales",
+                     "dL_drotations", "dL_dall_map")
+DUMP_MAX_BYTES = 64 * 2 ** 20
+DUMP_SEED = 0
+
+
+def direct_outputs(d):
+    """The per-view outputs among the buffers of a fused direct body (make_direct_view)."""
+    return dict(color=d["color"], invdepth=d["invd"], all_map=d["omap"], radii=d["radii"])
+
+
+def dump_outputs(pipe, out_dir):
+    """--dump-outputs: what the last timed step computed, as out_dir/<name>.npy in float32.  View mode: the step's summed
+    curve-parameter gradients (what the step hands to the optimizer) and the outputs of its last view; raster mode: the
+    forward outputs and gradients of the step's one view.  The arrays share a budget of DUMP_MAX_BYTES: smallest first, each
+    takes at most an equal share of what is left, and an array over its share is written as the elements at a fixed seeded
+    sample of flat indices (np.random.default_rng(DUMP_SEED).choice(numel, share, replace=False), sorted).
+    -> manifest for the JSON line"""
+    import numpy as np
+    w = pipe.w
+    torch.cuda.synchronize()
+    arrays = {}
+    if w.args.mode == "view":
+        B, flat = w.B, pipe.last_step_gradient()
+        arrays["grad_curve_points"] = flat[0:12 * B].view(B, 4, 3)
+        arrays["grad_width"] = flat[12 * B:13 * B].view(B, 1)
+        arrays["grad_opacity"] = flat[13 * B:14 * B].view(B, 1)
+        arrays.update({"last_view_" + k: v for k, v in pipe.last_outputs.items()})
+    else:
+        arrays.update(pipe.last_outputs)
+    os.makedirs(out_dir, exist_ok=True)
+    left, manifest = (DUMP_MAX_BYTES - 4096) // 4, {}   # (4 KiB for the .npy headers)
+    by_size = sorted(arrays.items(), key=lambda kv: (kv[1].numel(), kv[0]))
+    for i, (name, t) in enumerate(by_size):
+        a = t.detach().float().cpu().numpy()
+        share = left // (len(by_size) - i)
+        entry = {"shape": list(a.shape)}
+        if a.size > share:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, share, replace=False))
+            a = a.reshape(-1)[idx]
+            entry["sampled"] = int(share)
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+        left -= a.size
+        manifest[name] = entry
+    return {"dir": out_dir, "arrays": manifest,
+            "sample": f"arrays with a 'sampled' count hold the elements at np.sort(np.random.default_rng({DUMP_SEED})"
+                      ".choice(numel, sampled, replace=False)) of the flattened array"}
+
+
 class ViewPipeline:
     """The schedule the headline times, and nothing else: `views_per_step` independent views per step and rank, up to `streams` of
     them in flight (one captured hipGraph per stream, replayed after a 140-byte camera copy), their curve-parameter gradients
@@ -377,6 +437,7 @@ class ViewPipeline:
         self.cap = 0
         self.eager_direct = None   # [set][stream] -> body: the fused direct body launched eagerly (--no-graph without --autograd-view)
         self.packs = {}
+        self.last_outputs = None   # what the most recently dispatched view (raster mode: step) returns to its caller
         longest = 1
         if args.mode == "view":
             with torch.no_grad():   # longest tile list over this rank's views (eager, exact path) -> bucket capacity
@@ -398,7 +459,7 @@ class ViewPipeline:
                 if not cap:
                     raise RuntimeError(f'tile lists of {longest} entries exceed the bucket limit')
                 self.packs = {id(c): StaticCamera.packed(c) for c in w.my_cams}
-                view_graphs = []      # [set][stream] -> (graph, its static camera, its stream)
+                view_graphs = []      # [set][stream] -> (graph, its static camera, its stream, its outputs)
                 for q in range(self.n_sets):
                     view_graphs.append([])
                     for si in range(self.vstreams.n):
@@ -409,18 +470,20 @@ class ViewPipeline:
 
                             def body(scam=scam, leaves=self.leaf_sets[q][si], sink=sink):
                                 del sink[:]
-                                self.step_view(scam, leaves, False, cap, sink)
+                                outs = self.step_view(scam, leaves, False, cap, sink)
                                 self.overflow_acc.add_(sink[0][2:3])   # sticky bucket-overflow flag, checked after the timed region
+                                return outs
                         else:
                             direct, dbufs = self.make_direct_view(self.flat_sets[q][si], cap)
                             self.direct_bufs.append(dbufs)
 
-                            def body(scam=scam, direct=direct):
+                            def body(scam=scam, direct=direct, dbufs=dbufs):
                                 direct(scam)
+                                return direct_outputs(dbufs)
 
                         st = self.vstreams.streams[si] if self.vstreams.streams else torch.cuda.Stream()
-                        graph, _ = capture_graph(body, st)
-                        view_graphs[q].append((graph, scam, st))
+                        graph, outs = capture_graph(body, st)   # outs: the graph's static output tensors
+                        view_graphs[q].append((graph, scam, st, outs))
                 self.zero_gradients()
                 self.overflow_acc.zero_()
                 for dbufs in self.direct_bufs:
@@ -447,6 +510,9 @@ class ViewPipeline:
         if collect:
             self.stats["R"] += R
             self.stats["visible"] += int((radii > 0).sum())
+        else:
+            self.last_outputs = dict(color=color, invdepth=invd, all_map=om, radii=radii,
+                                     **{n: g for n, g in zip(RASTER_GRAD_NAMES, grads) if g is not None and g.numel()})
         return grads
 
     def make_leaves(self, flat):
@@ -478,6 +544,7 @@ class ViewPipeline:
         color.backward(w.dL_dcolor)   # synthetic upstream gradient; grads accumulate into the flat buffer's views
         if collect:
             self.stats["visible"] += int((radii > 0).sum())
+        return dict(color=color.detach(), invdepth=invd, all_map=om, radii=radii)
 
     def make_direct_view(self, flat, cap):
         """The autograd-free per-view body on the fused entry points (cgs_view_forward / cgs_view_backward): what the hipGraph
@@ -520,7 +587,7 @@ class ViewPipeline:
 
     # ------------------------------------------------------------------------------------------------ the schedule
     def _replay_view(self, vs, j, cam, q=0):
-        graph, scam, st = self.view_graphs[q][j % min(len(self.view_graphs[q]), vs.n)]
+        graph, scam, st, self.last_outputs = self.view_graphs[q][j % min(len(self.view_graphs[q]), vs.n)]
         if vs.streams:
             with torch.cuda.stream(st):
                 scam.load(self.packs[id(cam)])
@@ -571,9 +638,13 @@ class ViewPipeline:
                     self.prof_direct[0](cam)
                     self.stats["visible"] += int((self.prof_direct[1]["radii"] > 0).sum())
                 elif self.eager_direct is not None and not collect:
-                    vs.run(j, self.eager_direct[q][j % vs.n][0], cam)
+                    body, dbufs = self.eager_direct[q][j % vs.n]
+                    vs.run(j, body, cam)
+                    self.last_outputs = direct_outputs(dbufs)
                 else:
-                    vs.run(j, self.step_view, cam, leaves[j % vs.n], collect)
+                    outs = vs.run(j, self.step_view, cam, leaves[j % vs.n], collect)
+                    if not collect:
+                        self.last_outputs = outs
             vs.join()     # (events only: the main stream waits, the view streams run on into the next step)
             for f in flats[1:vs.n]:
                 flats[0].add_(f)
@@ -618,9 +689,10 @@ class ViewPipeline:
 
 # ------------------------------------------------------------------------------------------------ the timed region
 def time_headline(pipe):
-    """THE measurement: Wm untimed warm-up steps, then exactly K steps (repeated back to back until the region lasts --min-seconds)
-    between barrier + synchronize brackets, max over ranks.  Everything else bench.py reports is measured after this returns.
-    -> {"elapsed": seconds of the timed region (max over ranks), "reps": K-step regions inside it, "own_n1", "rank_diag"}"""
+    """THE measurement: Wm untimed warm-up steps, then exactly K steps between barrier + synchronize brackets, max over ranks.
+    Everything else bench.py reports is measured after this returns.
+    -> {"elapsed": seconds of the timed region (max over ranks), "own_n1", "rank_diag",
+        "dumped": the --dump-outputs manifest (rank 0) or None}"""
     w = pipe.w
     args, dev, K, Wm, G, my_cams = w.args, w.dev, w.K, w.Wm, pipe.G, w.my_cams
     distributed = w.world > 1 or bool(os.environ.get("CGS_BENCH_FORCE_DIST"))   # (the env switch exercises RCCL with a single rank)
@@ -647,28 +719,16 @@ def time_headline(pipe):
         pipe.form_process_group()
     dist = pipe.dist
 
-    def timed(reps):
-        """Wm warm-up steps, then the K-step region `reps` times back to back inside ONE barrier + synchronize bracket."""
+    def timed():
+        """Wm warm-up steps, then the K-step region inside ONE barrier + synchronize bracket."""
         pipe.run_views(my_cams[:Wm * G])
         pipe.barrier()
         t0 = time.perf_counter()
-        for _ in range(reps):
-            pipe.run_views(my_cams[Wm * G:(Wm + K) * G])
+        pipe.run_views(my_cams[Wm * G:(Wm + K) * G])
         pipe.barrier()
         return time.perf_counter() - t0
 
-    def timed_long():
-        """A pilot K-step region sizes the repeat count (max over ranks, so every rank repeats equally), then the
-        measurement proper."""
-        pilot = timed(1)
-        if dist is not None:
-            tp = torch.tensor([pilot], device=dev, dtype=torch.float64)
-            dist.all_reduce(tp, op=dist.ReduceOp.MAX)
-            pilot = float(tp.item())
-        reps = max(1, min(10000, int(math.ceil(1.1 * args.min_seconds / max(pilot, 1e-6)))))   # (the pilot runs colder, hence slower)
-        return (timed(reps) if reps > 1 else pilot), reps
-
-    elapsed, reps = timed_long()
+    elapsed = timed()
     for dbufs in pipe.direct_bufs:   # sticky overflow counters of the direct bodies
         pipe.overflow_acc.add_(dbufs["sticky"])
     if dist is not None:   # every rank takes the same decision (the re-timing below contains collectives)
@@ -676,7 +736,9 @@ def time_headline(pipe):
     if int(pipe.overflow_acc.item()) != 0:   # a tile list outgrew its bucket on some rank: graph results invalid
         print("bench: bucket overflow in graph mode, re-timing with eager launches", file=sys.stderr)
         pipe.use_graphs = False
-        elapsed, reps = timed_long()
+        elapsed = timed()
+    # the dump reads the last timed step's buffers: before the diagnostics below all-reduce and zero a gradient buffer
+    dumped = dump_outputs(pipe, args.dump_outputs) if args.dump_outputs and w.rank == 0 else None
     rank_diag = None
     if dist is not None:
         # per-rank times of the timed region (the headline takes the MAX), each rank's own N = 1 rate, and the all-reduce of the
@@ -706,7 +768,7 @@ def time_headline(pipe):
         rank_diag = {"per_rank_elapsed_s": per_rank, "own_n1": [(float(t[1].item()), float(t[2].item())) for t in every],
                      "all_reduce_ms": ar_ms}
         elapsed = max(per_rank)
-    return {"elapsed": elapsed, "reps": reps, "own_n1": own_n1, "rank_diag": rank_diag}
+    return {"elapsed": elapsed, "own_n1": own_n1, "rank_diag": rank_diag, "dumped": dumped}
 
 
 # ------------------------------------------------------------------------------------------------ after the timed region
@@ -866,16 +928,15 @@ def headline_fields(pipe, head, R_mean, vis_mean):
     """metric / value / config of the contract, from the timed region alone."""
     w, args = pipe.w, pipe.w.args
     K, Wm, G, world, P, B, m, W, H = w.K, w.Wm, pipe.G, w.world, w.P, w.B, w.m, w.W, w.H
-    elapsed, reps = head["elapsed"], head["reps"]
-    steps_timed = K * reps
-    views_timed = steps_timed * G            # per rank
-    ms_per_step = elapsed / steps_timed * 1e3
+    elapsed = head["elapsed"]
+    views_timed = K * G            # per rank
+    ms_per_step = elapsed / K * 1e3
     ms_per_view = elapsed / views_timed * 1e3   # per rank
     value = P * world * views_timed / elapsed / 1e6
     out = {
         "metric": "Msplats rasterized/s (fwd+bwd)", "value": round(value, 3), "unit": "Msplats/s",
         "n_gpus": world, "steps": K, "warmup": Wm, "ms_per_step": round(ms_per_step, 4),
-        "repeats": reps, "views_timed": views_timed * world, "timed_seconds": round(elapsed, 4),
+        "views_timed": views_timed * world, "timed_seconds": round(elapsed, 4),
         "ms_per_view": round(ms_per_view, 5),
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
         "config": {"workload": f"{args.config}: synthetic curve-Gaussians, {B} curves x {m} = {P} splats, "
@@ -921,8 +982,7 @@ def scaling_fields(out, pipe, head):
                         "NCCL_MAX_NCHANNELS=4 (RCCL channels starving the compositors of CUs)"}
     if rank_diag is not None:
         # measured, beside the prediction above: a bad first multi-GPU run says WHERE it lost
-        n_steps = K * head["reps"]
-        per = [t / n_steps * 1e3 for t in rank_diag["per_rank_elapsed_s"]]
+        per = [t / K * 1e3 for t in rank_diag["per_rank_elapsed_s"]]
         slow = max(range(len(per)), key=per.__getitem__)
         out["all_reduce_ms"] = None if rank_diag["all_reduce_ms"] is None else round(rank_diag["all_reduce_ms"], 4)
         out["all_reduce_note"] = ("one all-reduce of the flat gradient buffer (38 floats / curve) timed alone, max over ranks; "
@@ -1365,8 +1425,8 @@ def cpu_baseline_fields(out, w):
 
 def child_line(cfg, extra=()):
     import subprocess
-    cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--config", cfg, "--steps", "8", "--warmup", "2",
-           "--min-seconds", "1.0", "--no-cpu-baseline", "--no-general-route", "--no-realistic-size"] + list(extra)
+    cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--config", cfg, "--steps", "128", "--warmup", "8",
+           "--no-cpu-baseline", "--no-general-route", "--no-realistic-size"] + list(extra)
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=900)
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -1452,6 +1512,8 @@ def main():
         realistic_size_fields(out)
     if args.all_configs and w.world == 1:
         all_configs_fields(out)
+    if head["dumped"] is not None:
+        out["dump_outputs"] = head["dumped"]
     if dist is not None:
         dist.destroy_process_group()
     try:   # RCCL writes its banner through C stdio: flush that buffer so the JSON line is the LAST line on stdout

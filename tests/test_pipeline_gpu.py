@@ -1206,6 +1206,113 @@ def test_bench_other_schedules(flags, launch):
         assert out["step_boundary"] == "join per step"
 
 
+def test_bench_dump_outputs_reproduce_across_runs_and_schedules():
+    """--dump-outputs DIR writes what the last timed step computed, float32, within 64 MB, and the line says what it wrote.
+    Two runs with the same arguments see the same inputs, so their dumps agree (gradients up to the order of float atomics,
+    radii exactly).  So does a run over a one-rank RCCL group on one stream: there the all-reduce diagnostic after the
+    timed region reuses the very buffer the last step reduced into, and the dump must be taken before it.  Raster mode dumps
+    the rasterizer's outputs and gradients.  --steps K is echoed and is the number of timed steps."""
+    import json
+    import subprocess
+    import sys
+    import tempfile
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "CGS_BENCH_FORCE_DIST")}
+    base = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "1", "--config", "cfg1",
+            "--no-cpu-baseline", "--no-train-step", "--no-kernel-times", "--no-general-route"]
+    runs = (([], {}), ([], {}), (["--streams", "1"], {"CGS_BENCH_FORCE_DIST": "1", "MASTER_PORT": "29553"}),
+            (["--mode", "raster"], {}))
+    with tempfile.TemporaryDirectory() as tmp:
+        dumps = []
+        for i, (extra, extra_env) in enumerate(runs):
+            d = os.path.join(tmp, str(i))
+            r = subprocess.run(base + extra + ["--dump-outputs", d], cwd=root, env=dict(env, **extra_env), capture_output=True,
+                               text=True, timeout=600)
+            assert r.returncode == 0, r.stderr[-2000:]
+            out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+            assert out["steps"] == 5 and "repeats" not in out
+            assert out["views_timed"] == 5 * out["config"]["views_per_step_per_rank"]
+            man = out["dump_outputs"]["arrays"]
+            assert sorted(f[:-4] for f in os.listdir(d)) == sorted(man)
+            arrs = {n: np.load(os.path.join(d, n + ".npy")) for n in man}
+            assert sum(os.path.getsize(os.path.join(d, n + ".npy")) for n in man) <= 64 * 2 ** 20
+            for n, a in arrs.items():
+                assert a.dtype == np.float32 and np.isfinite(a).all(), n
+                assert "sampled" in man[n] or list(a.shape) == man[n]["shape"], n
+            dumps.append(arrs)
+        a, b, dist1, ras = dumps
+        assert out["config"]["mode"] == "raster"
+        B = 417
+        assert a["grad_curve_points"].shape == (B, 4, 3) and a["grad_width"].shape == (B, 1)
+        assert a["last_view_color"].shape == (1, 800, 800) and a["last_view_all_map"].shape == (4, 800, 800)
+        assert np.abs(a["grad_curve_points"]).max() > 0 and (a["last_view_radii"] > 0).any()
+        for other in (b, dist1):
+            assert sorted(a) == sorted(other)
+            np.testing.assert_array_equal(a["last_view_radii"], other["last_view_radii"])
+            for n in a:
+                rel = np.linalg.norm(a[n] - other[n]) / max(np.linalg.norm(a[n]), 1e-30)
+                assert rel < 1e-4, (n, rel)
+        assert {"color", "radii", "all_map", "dL_dmeans3D", "dL_dscales", "dL_drotations", "dL_dopacity"} <= set(ras)
+
+
+def test_bench_times_k_steps_and_dumps_the_last_one(tmp_path, monkeypatch):
+    """In process, on the default schedule (graph replay, three streams, double-buffered gradient sets): the timed region
+    dispatches exactly the K steps of views my_cams[Wm G:(Wm + K) G], and the dump holds the LAST of them -- its summed
+    gradient and its last view's outputs equal the same views run again one at a time, eagerly, through the drop-in API,
+    while the step before it gives a clearly different gradient."""
+    monkeypatch.setenv("HSA_ENABLE_IPC_MODE_LEGACY", os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "CGS_BENCH_FORCE_DIST", "CGS_BENCH_REHEARSAL"):
+        monkeypatch.delenv(k, raising=False)
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    if root not in sys.path:
+        sys.path.insert(0, root)
+    import bench
+    K, Wm = 5, 2
+    args = bench.parse_args(["--gpus", "1", "--steps", str(K), "--warmup", str(Wm), "--config", "cfg1",
+                             "--dump-outputs", str(tmp_path / "d")])
+    w = bench.Workload(args, bench.start_rank(args))
+    pipe = bench.ViewPipeline(w)
+    G = pipe.G
+    assert pipe.use_graphs and pipe.vstreams.n == 3 and pipe.n_sets == 2 and G == 8
+    calls = []
+    run_views = pipe.run_views
+
+    def spy(view_list, *a, **kw):
+        s0 = pipe.step_no
+        run_views(view_list, *a, **kw)
+        calls.append((list(view_list), pipe.step_no - s0))
+    monkeypatch.setattr(pipe, "run_views", spy)
+    head = bench.time_headline(pipe)
+    assert pipe.use_graphs and int(pipe.overflow_acc.item()) == 0     # no eager re-timing
+    assert [n for _, n in calls] == [Wm, K]
+    assert [id(c) for c in calls[1][0]] == [id(c) for c in w.my_cams[Wm * G:(Wm + K) * G]]
+    dumped = head["dumped"]["arrays"]
+    got = {n: np.load(tmp_path / "d" / (n + ".npy")) for n in dumped}
+    assert not any("sampled" in e for e in dumped.values())
+
+    def serial_step(cams):
+        pipe.run_views(cams, serial=True, graphs=False)
+        pipe.barrier()
+        flat = pipe.last_step_gradient(serial=True)
+        B = w.B
+        return np.concatenate([flat[:12 * B].cpu().numpy(), flat[12 * B:14 * B].cpu().numpy()])
+
+    rel = lambda x, y: float(np.linalg.norm(x - y) / max(np.linalg.norm(y), 1e-30))
+    dumped_grad = np.concatenate([got[n].reshape(-1) for n in ("grad_curve_points", "grad_width", "grad_opacity")])
+    last = serial_step(w.my_cams[(Wm + K - 1) * G:(Wm + K) * G])
+    outs = {k: v.detach().float().cpu().numpy() for k, v in pipe.last_outputs.items()}
+    assert rel(dumped_grad, last) < 1e-3        # the bench's own tolerance for schedule vs serial eager
+    # (the drop-in path samples and projects in other kernels than the fused one: a last-ulp ceil may flip a radius by 1)
+    dr = np.abs(got["last_view_radii"] - outs["radii"])
+    assert dr.max() <= 1 and np.mean(dr > 0) < 1e-3
+    for n in ("color", "invdepth", "all_map"):
+        assert rel(got["last_view_" + n], outs[n]) < 1e-4, n
+    before = serial_step(w.my_cams[(Wm + K - 2) * G:(Wm + K - 1) * G])
+    assert rel(dumped_grad, before) > 1e-2
+    del pipe, w
+    torch.cuda.synchronize()
+
+
 def test_connection_loss_matches_the_reference_block():
     """cgs_endpoint_connection_loss (O(B) memory, one sweep) against train.py:133-146 written out with torch.cdist:
     value, gradient w.r.t. the control points (only first and last points receive one), the no-pair case, and end points
