@@ -80,6 +80,8 @@ SIGNATURES = {
     "cgs_adam_step_flat": (_i, [_i64, _vp, _vp, _vp, _vp, C.c_char_p, _i, _f, _f, _f, _i, _i, _vp]),
     "cgs_knn_workspace_bytes": (C.c_size_t, [_i]),
     "cgs_knn_mean_dist2": (_i, [_i, _vp, _vp, _vp, _vp]),
+    "cgs_nn1_workspace_bytes": (C.c_size_t, [_i]),
+    "cgs_nn1": (_i, [_i, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "cgs_sample_curves_forward": (_i, [_i, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp]),
     "cgs_sample_curves_backward": (_i, [_i, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "cgs_splat_attrs_forward": (_i, [_i, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

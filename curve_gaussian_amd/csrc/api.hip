@@ -1412,4 +1412,22 @@ int cgs_knn_mean_dist2(int P, const float* points, float* mean_dist2, void* work
     return CGS_OK;
 }
 
+size_t cgs_nn1_workspace_bytes(int n_query) { return nn1_workspace_bytes(n_query); }
+
+int cgs_nn1(int n_query, const float* query, int n_ref, const float* ref, float* dist, int* index, void* workspace,
+            void* stream_) {
+    if (n_query < 0 || n_ref < 0 || n_query > (1 << 30) || n_ref > (1 << 30)) {
+        set_error("cgs_nn1: invalid argument (n_query=%d, n_ref=%d)", n_query, n_ref);
+        return CGS_ERR_INVALID_ARGUMENT;
+    }
+    if (n_query == 0) return CGS_OK;
+    if (n_ref == 0 || !query || !ref || !dist || !index || !workspace) {
+        set_error("cgs_nn1: invalid argument (NULL pointer or an empty reference set, n_ref=%d)", n_ref);
+        return CGS_ERR_INVALID_ARGUMENT;
+    }
+    launch_nn1((hipStream_t)stream_, n_query, query, n_ref, ref, dist, index, workspace);
+    if (!check_launch("nn1", false, (hipStream_t)stream_)) return CGS_ERR_HIP;
+    return CGS_OK;
+}
+
 }  // extern "C"

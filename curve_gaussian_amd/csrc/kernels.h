@@ -146,4 +146,9 @@ void launch_adam_flat(hipStream_t s, long long n, float* p, float* g, float* m, 
 size_t knn_workspace_bytes(int P);
 void launch_knn(hipStream_t s, int P, const float* pts, float* dists, void* workspace);
 
+// nn.hip
+size_t nn1_workspace_bytes(int n_query);
+void launch_nn1(hipStream_t s, int n_query, const float* query, int n_ref, const float* ref, float* dist, int* index,
+                void* workspace);
+
 }  // namespace cgs

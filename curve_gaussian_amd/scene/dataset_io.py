@@ -11,7 +11,8 @@
   ``get_parametric_edge(visible_checking=False)`` -> ``process_geometry_data``
   (edge_extraction/extract_para_edge.py:60-129, 252-256): curves as 4x3 control points, lines as 6 floats, and the
   edge point cloud sampled every 5 mm of Simpson-rule arc length (edge_extraction/extract_uitl.py:291-330).
-  ``merge_endpoints`` (opt.merge_endpoints_flag) and the visibility check are not reproduced.
+  ``merge_endpoints`` (opt.merge_endpoints_flag, train.py:257-265) is reproduced as an option
+  (edge_extraction.merge_endpoints; off by default here, on by default in the reference); the visibility check is not.
 * ``point_cloud.ply`` splat snapshot -- ``save_ply`` (scene/gaussian_model.py:267-280, 383-400; scene/__init__.py:96).
 
 Parity: the camera arithmetic is pinned by tests/golden/emap_camera.npz (reference graphics_utils imported by
@@ -209,20 +210,28 @@ def sample_edge_points(curves_ctl_pts, lines_end_pts, sample_resolution=0.005):
     return np.array(pts, dtype=np.float32).reshape(-1, 3)
 
 
-def extract_curves(gaussians):
-    """train.py:252-256,266-273: Bezier curves as [n,12], line segments as [n,6] (first and last control point)."""
+def extract_curves(gaussians, merge_endpoints=False, distance_threshold=0.015):
+    """train.py:252-256,266-273: Bezier curves as [n,12], line segments as [n,6] (first and last control point).
+    merge_endpoints=True also merges nearby endpoints (train.py:257-265, edge_extraction.merge_endpoints, on the
+    control points' device) -- the reference's default (merge_endpoints_flag = True); False keeps the output as it was."""
     cp = gaussians.get_curve_points.detach()
     isb = gaussians.is_bezier.bool()
-    bez = cp[isb].reshape(-1, 12).cpu().numpy()
-    lines = cp[~isb][:, [0, -1], :].reshape(-1, 6).cpu().numpy()
+    bez = cp[isb].reshape(-1, 12)
+    lines = cp[~isb][:, [0, -1], :].reshape(-1, 6)
+    if merge_endpoints:
+        from ..edge_extraction.ops import merge_endpoints as _merge
+        lines, bez = _merge(lines, bez, distance_threshold)
+    bez = bez.cpu().numpy()
+    lines = lines.cpu().numpy()
     return {"lines_end_pts": lines.tolist() if len(lines) > 0 else [],
             "curves_ctl_pts": bez.tolist() if len(bez) > 0 else []}
 
 
-def write_parametric_edges(gaussians, model_path):
-    """Writes parametric_edges.json (the evaluation input, train.py:287-293) and edge_points.ply (ASCII, :277-285)."""
+def write_parametric_edges(gaussians, model_path, merge_endpoints=False, distance_threshold=0.015):
+    """Writes parametric_edges.json (the evaluation input, train.py:287-293) and edge_points.ply (ASCII, :277-285).
+    merge_endpoints / distance_threshold: see extract_curves (the reference's default is merge_endpoints=True)."""
     os.makedirs(model_path, exist_ok=True)
-    merged = extract_curves(gaussians)
+    merged = extract_curves(gaussians, merge_endpoints, distance_threshold)
     curves = np.array(merged["curves_ctl_pts"]).reshape(-1, 12).reshape(-1, 4, 3)
     lines = np.array(merged["lines_end_pts"]).reshape(-1, 6)
     edge_dict = {"curves_ctl_pts": curves.tolist(), "lines_end_pts": lines.tolist()}

@@ -406,6 +406,20 @@ size_t cgs_knn_workspace_bytes(int P);
 int cgs_knn_mean_dist2(int P, const float* points /*[P,3]*/, float* mean_dist2 /*[P]*/, void* workspace, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Exact 1-nearest-neighbour (edge evaluation).  Replaces the point_cloud_utils.k_nearest_neighbors(x, y, k=1) KD-tree
+ * queries of the reference's evaluator (edge_extraction/eval_utils.py:77-115, 195-249) and its scipy cKDTree query
+ * (eval_ABC.py:27-38): for every query point q[i], dist[i] = min_j |q[i] - ref[j]| and index[i] = the argmin.
+ * Squared distances are the fp32 value of (dx*dx + dy*dy) + dz*dz (no FMA contraction, no GEMM expansion), brute force.
+ * Ties: the LOWEST index among reference points at the same fp32 distance (duplicates are normal in ABC ground truth);
+ * the result is deterministic, bit for bit.  n_query = 0 is a no-op; n_ref = 0 with n_query > 0, negative sizes, sizes
+ * above 2^30 and NULL pointers are CGS_ERR_INVALID_ARGUMENT, rejected before anything is launched.
+ * workspace: cgs_nn1_workspace_bytes(n_query) bytes of device scratch.
+ * ------------------------------------------------------------------------------------------------ */
+size_t cgs_nn1_workspace_bytes(int n_query);
+int cgs_nn1(int n_query, const float* query /*[n_query,3]*/, int n_ref, const float* ref /*[n_ref,3]*/,
+            float* dist /*[n_query]*/, int* index /*[n_query]*/, void* workspace, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Per-call options of the operator API.  The `debug` argument of cgs_rasterize_forward / cgs_rasterize_backward is a bit
  * set: bit 0 is the reference's debug flag (rasterize_points.cu:53: synchronise and check after every kernel), the bits
  * below select measurement / parity variants FOR THAT CALL ONLY -- nothing process-wide, nothing another thread's call
