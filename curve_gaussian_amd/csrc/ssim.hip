@@ -356,18 +356,20 @@ void launch_ssim_bwd(hipStream_t s, int planes, int H, int W, const float* img1,
                        img1, img2, dL_dmap, dm_dmu1, dm_dsigma1_sq, dm_dsigma12, dL_dimg1, PhotoArgs{});
 }
 
-// workspace: [3 * H*W floats: dm_dmu1, dm_dsigma1_sq, dm_dsigma12][2 * PHOTO_SLOTS doubles, zero on first use]
-size_t photometric_workspace_bytes(int H, int W) {
-    return (((size_t)3 * H * W * sizeof(float) + 127) & ~(size_t)127) + 2 * PHOTO_SLOTS * sizeof(double);
-}
+// workspace: [2 * PHOTO_SLOTS doubles, zero on first use][3 * H*W floats: dm_dmu1, dm_dsigma1_sq, dm_dsigma12].  The slots
+// come first, at an offset that does not depend on H x W, so one zeroed workspace serves images of any size up to its own
+// (k_photo_finish leaves the slots zero again).
+constexpr size_t PHOTO_SLOT_BYTES = 2 * PHOTO_SLOTS * sizeof(double);
+static_assert(PHOTO_SLOT_BYTES % 128 == 0, "derivative maps stay 128-byte aligned");
+size_t photometric_workspace_bytes(int H, int W) { return PHOTO_SLOT_BYTES + (size_t)3 * H * W * sizeof(float); }
 void launch_photometric_loss(hipStream_t s, int H, int W, const float* image, const float* gt, const int* view_index,
                              float thr, const unsigned int* n_pos, float lambda_a, float lambda_b, int clamp,
                              void* workspace, float* grad, float* loss) {
     const size_t N = (size_t)H * W;
-    float* dm1 = reinterpret_cast<float*>(workspace);
+    double* slots = reinterpret_cast<double*>(workspace);
+    float* dm1 = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + PHOTO_SLOT_BYTES);
     float* dm2 = dm1 + N;
     float* dm3 = dm2 + N;
-    double* slots = reinterpret_cast<double*>(reinterpret_cast<char*>(workspace) + ((3 * N * sizeof(float) + 127) & ~(size_t)127));
     PhotoArgs pa;
     pa.clamp = clamp;
     pa.dmap_const = -lambda_b / (float)N;

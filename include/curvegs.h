@@ -328,7 +328,8 @@ int cgs_edge_aware_loss(int channels, int height, int width, const float* image,
  *   x = clamp_input ? clamp(image, 0, 1) : image          (render()'s clamp, gaussian_renderer/__init__.py:138)
  * with lambda_edge = lambda_mse (1 - lambda_dssim), lambda_ssim = lambda_mse lambda_dssim in train.py's notation.
  * n_pos: device u32 = #{gt > threshold}, from cgs_edge_count (depends on gt only: compute once per gt image).
- * workspace: cgs_photometric_workspace_bytes(H, W) bytes, zero-filled before its FIRST use, then reusable as is.
+ * workspace: cgs_photometric_workspace_bytes(H, W) bytes, zero-filled before its FIRST use, then reusable as is, also
+ * for any other H' x W' whose workspace size is not larger.
  * Outputs: dL_dimage [H*W] = d loss / d image (0 where the clamp is active), loss [1]. */
 size_t cgs_photometric_workspace_bytes(int height, int width);
 int cgs_edge_count(int channels, int height, int width, const float* gt, float threshold, uint32_t* n_pos, void* stream);
@@ -347,7 +348,9 @@ int cgs_photometric_loss_indexed(int height, int width, const float* image, cons
  * curves closer than distance_threshold (0.05 in the reference); 0 when there is no such pair.  The reference builds the
  * (2B)^2 cdist matrix; this is a neighbour search on a hashed uniform grid, O(B) memory and time.  curve_points [B,4,3].
  * dL_dcurve_points [B,4,3]: accumulate != 0 adds the gradient to the rows 0 and 3 (the other rows are untouched),
- * accumulate == 0 writes the whole tensor (rows 1, 2 zero).  workspace: cgs_endpoint_connection_workspace_bytes(B). */
+ * accumulate == 0 writes the whole tensor (rows 1, 2 zero).  workspace: cgs_endpoint_connection_workspace_bytes(B).
+ * Coordinate range: grid cells are indexed with (int)floorf(x / (1.0001 distance_threshold)), so every end-point
+ * coordinate must satisfy |x| < 2^30 distance_threshold; beyond that the cell index overflows and pairs are missed. */
 size_t cgs_endpoint_connection_workspace_bytes(int B);
 int cgs_endpoint_connection_loss(int B, const float* curve_points, float distance_threshold, float weight, void* workspace,
                                  float* loss, float* dL_dcurve_points, int accumulate, void* stream);
