@@ -201,8 +201,8 @@ Tensor mark_visible(const Tensor& means3D, const Tensor& viewmatrix, const Tenso
 }
 
 // ------------------------------------------------------------------------------------------------ fused per-view path
-// Forward half of ops/view_render.py::_ViewRender: detached float32 copies of the parameters, every buffer of the view, the
-// begin half of the checked forward (or the sync-free forward when static_cap > 0) and render()'s epilogue, in one call.
+// Forward half of ViewRenderFn (and of TrainStep's direct path): detached float32 copies of the parameters, every buffer of the
+// view and ONE cgs_view_forward_render -- the checked forward, or the sync-free one when sync_free -- with render()'s epilogue.
 // -> (color, invdepth, all_map, radii, rend_dir | empty, color_raw | None, saved tensors..., handle, cap)
 struct ViewFwd {
     Tensor color_out, invd, amap, radii, rend_dir, color_raw;                               // color_raw: undefined unless clamp
@@ -281,7 +281,7 @@ std::pair<int64_t, int64_t> view_wait(int64_t handle) {
 }
 void view_abandon(int64_t handle) { cgs_view_forward_abandon((int)handle); }
 
-// Backward half: clamp gradient + cgs_view_backward.  -> (g_cp, g_w, g_ol, g_mk | None, g_m2d)
+// Backward half: cgs_view_backward_render, the clamp gradient folded in.  -> (g_cp, g_w, g_ol, g_mk | None, g_m2d)
 struct ViewBwd { Tensor g_cp, g_w, g_ol, g_mk, g_m2d; };   // undefined = None (sinks took it / no mask)
 ViewBwd view_backward_core(const Tensor& cp, const Tensor& w, const Tensor& ol, const c10::optional<Tensor>& mk,
                            const c10::optional<Tensor>& is_bezier_u8, const Tensor& coef, const Tensor& geom, const Tensor& binb,
@@ -380,12 +380,12 @@ py::tuple view_backward(const Tensor& cp, const Tensor& w, const Tensor& ol, con
 // The fused view route and the photometric loss as torch::autograd::Function: their backward runs on the autograd engine's
 // device thread WITHOUT the GIL and without the Python custom-Function machinery (ctx object, argument tuple checks, a
 // Python frame per node) -- what `render()` + `loss.backward()` of the literal drop-in loop (train.py:95-148) pays per
-// iteration beside the kernels themselves.  Same kernels, same saved state as ops/view_render.py::_ViewRender, which stays
-// as the ctypes-bindings form (CGS_TORCH_SHIM=0).
+// iteration beside the kernels themselves.  ops/view_render.py::_ViewRender is the same node over the ctypes bindings
+// (CGS_TORCH_SHIM=0): same arguments, same outputs, same two library calls.
 using torch::autograd::AutogradContext;
 using torch::autograd::variable_list;
 
-// Python: ops/view_render.py::_general_backward_cpp (re-render through the general route).  A leaked pointer on purpose: a
+// Python: ops/view_render.py::_general_backward (re-render through the general route).  A leaked pointer on purpose: a
 // static py::object would be destroyed after the interpreter has been finalised.
 py::object* g_general_backward = nullptr;
 
@@ -446,10 +446,11 @@ struct ViewRenderFn : public torch::autograd::Function<ViewRenderFn> {
         }
         if (ctx->saved_data["ran"].toBool()) {
             // a second backward over this forward (retain_graph): the sampling backward's two grid-wide sums were cleared by the
-            // forward's norm pass once -- clear them again
+            // forward's norm pass once -- clear them again, through variable_data() so that the saved tensor's version (checked
+            // at every unpack) stays that of the forward
             int first = 0, count = 0;
             cgs_view_norms_backward_range(&first, &count);
-            norms.narrow(0, first, count).zero_();
+            norms.variable_data().narrow(0, first, count).zero_();
         }
         c10::optional<std::vector<Tensor>> sinks;
         if (ctx->saved_data.count("sinks")) {

@@ -220,20 +220,91 @@ def test_fused_route_and_loss_are_cpp_autograd_nodes_under_the_shim():
     assert float(gm._curve_points.grad.abs().max()) > 0 and pkg["viewspace_points"].grad is not None
 
 
-def test_fused_route_backward_twice_over_one_forward():
-    """retain_graph + two backwards through one fused render(): the second one gives the same gradients again (the grid-wide
-    sums of the sampling backward are cleared by the forward once and by the node before any further backward)."""
+def _use_binding(monkeypatch, shim):
+    """Select the fused node's binding: the compiled shim (ViewRenderFn, the default) or the ctypes bindings (_ViewRender,
+    CGS_TORCH_SHIM=0).  The general route resolves its own binding once, so that choice is reset too."""
+    from curve_gaussian_amd import diff_cur_rasterization as D
+    if shim:
+        monkeypatch.delenv("CGS_TORCH_SHIM", raising=False)
+    else:
+        monkeypatch.setenv("CGS_TORCH_SHIM", "0")
+    monkeypatch.setattr(D._ExtProxy, "_impl", None)
+
+
+def test_fused_route_backward_twice_over_one_forward(monkeypatch):
+    """retain_graph + repeated backwards through one fused render(), under both bindings: the second and the third give the
+    same gradients again (the grid-wide sums of the sampling backward are cleared by the forward once and by the node before
+    any further backward -- without bumping the version of the saved buffer, which autograd checks at every unpack)."""
     from curve_gaussian_amd.gaussian_renderer import PipelineParams, render
     c, mask, cam = _small()
     cam = cam.to(DEV)
-    gm = _model(c, mask)
     dimg = torch.randn(1, cam.image_height, cam.image_width, generator=torch.Generator().manual_seed(5)).to(DEV)
-    pkg = render(cam, gm, PipelineParams(), torch.zeros(3, device=DEV))
-    first = torch.autograd.grad(pkg["render"], [gm._curve_points, gm._width, gm._opacity], dimg, retain_graph=True)
-    second = torch.autograd.grad(pkg["render"], [gm._curve_points, gm._width, gm._opacity], dimg, retain_graph=True)
-    for a, b, n in zip(first, second, ("curve_points", "width", "opacity")):
-        assert float(a.abs().max()) > 0
-        assert_close(n, b.cpu(), a.cpu(), rel=2e-4)
+    for shim in (True, False):
+        _use_binding(monkeypatch, shim)
+        gm = _model(c, mask)
+        pkg = render(cam, gm, PipelineParams(), torch.zeros(3, device=DEV))
+        wrt = [gm._curve_points, gm._width, gm._opacity]
+        first = torch.autograd.grad(pkg["render"], wrt, dimg, retain_graph=True)
+        for _ in range(2):
+            again = torch.autograd.grad(pkg["render"], wrt, dimg, retain_graph=True)
+            for a, b, n in zip(first, again, ("curve_points", "width", "opacity")):
+                assert float(a.abs().max()) > 0
+                assert_close(n, b.cpu(), a.cpu(), rel=2e-4)
+
+
+def test_both_bindings_of_the_fused_node_agree(monkeypatch):
+    """ViewRenderFn (compiled shim) and _ViewRender (ctypes bindings) make the same cgs_view_forward_render /
+    cgs_view_backward_render calls: identical forward outputs and gradients equal to the rounding of the backward's atomics,
+    for every switch the node takes (mask, clamp, direction map, eager / sync-free) and for a depth loss, which reaches the
+    general backward."""
+    from curve_gaussian_amd import _lib as L
+    from curve_gaussian_amd.gaussian_renderer import PipelineParams, render
+    from curve_gaussian_amd.ops import view_render as VR
+    _use_binding(monkeypatch, True)
+    if not L.use_shim():
+        pytest.skip("CGS_LIB names an experiment build: the ctypes bindings are the only binding")
+    c, mask, cam = _small()
+    cam = cam.to(DEV)
+    H, W = cam.image_height, cam.image_width
+    bg = torch.zeros(3, device=DEV)
+    gen = torch.Generator().manual_seed(7)
+    dimg, ddepth = (torch.randn(1, H, W, generator=gen).to(DEV) for _ in range(2))
+    render(cam, _model(c, mask), PipelineParams(), bg)              # (sizes the buckets of this shape)
+    lib = L.load()
+    cap = min(2 * VR._capacity(lib, torch.device(DEV), c["curve_points"].shape[0] * 12, W, H), int(lib.cgs_bucket_capacity_limit()))
+    cases = [(use_mask, clamp, rend_dir, static, False) for use_mask in (False, True) for clamp in (False, True)
+             for rend_dir in (False, True) for static in (False, True)]
+    cases.append((True, True, True, False, True))
+    for use_mask, clamp, rend_dir, static, depth_loss in cases:
+        case = f"mask={use_mask} clamp={clamp} rend_dir={rend_dir} static={static} depth_loss={depth_loss}"
+        got = {}
+        for shim in (True, False):
+            _use_binding(monkeypatch, shim)
+            gm = _model(c, mask)
+            sink = []
+            pkg = render(cam, gm, PipelineParams(), bg, use_mask=use_mask, mask_thr=0.3, clamp=clamp, compute_rend_dir=rend_dir,
+                         static_bucket_cap=cap if static else 0, status_sink=sink if static else None)
+            node = pkg["render"].grad_fn.name()
+            assert ("ViewRenderFn" in node) == shim and ("_ViewRender" in node) != shim, (case, node)
+            if static:
+                assert len(sink) == 1 and int(sink[0][2]) == 0, case        # (status word 2: a bucket overflowed)
+            loss = (pkg["render"] * dimg).sum()
+            if depth_loss:
+                loss = loss + (pkg["depth"] * ddepth).sum()
+            loss.backward()
+            grads = {n: getattr(gm, n).grad for n in ("_curve_points", "_width", "_opacity", "_mask")}
+            grads["viewspace_points"] = pkg["viewspace_points"].grad
+            got[shim] = pkg, grads
+        (ps, gs), (pc, gc) = got[True], got[False]
+        for k in ("render", "depth", "rend_alpha", "rend_dir", "radii", "visibility_filter"):
+            assert (ps[k] is None) == (pc[k] is None), (case, k)
+            assert ps[k] is None or torch.equal(ps[k], pc[k]), (case, k)
+        for n, a in gs.items():
+            b = gc[n]
+            assert (a is None) == (b is None), (case, n)
+            if a is not None:
+                assert float(a.abs().max()) > 0, (case, n)
+                assert_close(f"{case} {n}", b.cpu(), a.cpu(), rel=2e-4)
 
 
 def test_fused_route_resamples_with_the_eps_of_prepare_scaling_rot(monkeypatch):
