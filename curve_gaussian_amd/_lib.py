@@ -82,6 +82,7 @@ SIGNATURES = {
     "cgs_knn_mean_dist2": (_i, [_i, _vp, _vp, _vp, _vp]),
     "cgs_nn1_workspace_bytes": (C.c_size_t, [_i]),
     "cgs_nn1": (_i, [_i, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "cgs_edge_visibility": (_i, [_i, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _vp, _i, _vp, _vp]),
     "cgs_sample_curves_forward": (_i, [_i, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp]),
     "cgs_sample_curves_backward": (_i, [_i, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "cgs_splat_attrs_forward": (_i, [_i, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

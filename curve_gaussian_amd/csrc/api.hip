@@ -1430,4 +1430,28 @@ int cgs_nn1(int n_query, const float* query, int n_ref, const float* ref, float*
     return CGS_OK;
 }
 
+int cgs_edge_visibility(int n_curves, const double* curves, int n_lines, const double* lines, int n_frames,
+                        const double* K, const double* w2c, int height, int width, const unsigned char* maps,
+                        int invert, int* counts, void* stream_) {
+    if (n_curves < 0 || n_lines < 0 || n_frames < 0 || (long long)n_curves + n_lines > (1 << 30)) {
+        set_error("cgs_edge_visibility: invalid argument (n_curves=%d, n_lines=%d, n_frames=%d)", n_curves, n_lines,
+                  n_frames);
+        return CGS_ERR_INVALID_ARGUMENT;
+    }
+    if (n_curves + n_lines == 0) return CGS_OK;
+    if (n_frames > 0 && (height <= 0 || width <= 0)) {
+        set_error("cgs_edge_visibility: invalid argument (height=%d, width=%d)", height, width);
+        return CGS_ERR_INVALID_ARGUMENT;
+    }
+    if ((n_curves > 0 && !curves) || (n_lines > 0 && !lines) || !counts ||
+        (n_frames > 0 && (!K || !w2c || !maps))) {
+        set_error("cgs_edge_visibility: invalid argument (NULL pointer)");
+        return CGS_ERR_INVALID_ARGUMENT;
+    }
+    launch_edge_visibility((hipStream_t)stream_, n_curves, curves, n_lines, lines, n_frames, K, w2c, height, width,
+                           maps, invert, counts);
+    if (!check_launch("edge_visibility", false, (hipStream_t)stream_)) return CGS_ERR_HIP;
+    return CGS_OK;
+}
+
 }  // extern "C"

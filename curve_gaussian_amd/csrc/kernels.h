@@ -151,4 +151,9 @@ size_t nn1_workspace_bytes(int n_query);
 void launch_nn1(hipStream_t s, int n_query, const float* query, int n_ref, const float* ref, float* dist, int* index,
                 void* workspace);
 
+// visibility.hip
+void launch_edge_visibility(hipStream_t s, int n_curves, const double* curves, int n_lines, const double* lines,
+                            int n_frames, const double* K, const double* w2c, int height, int width,
+                            const unsigned char* maps, int invert, int* counts);
+
 }  // namespace cgs

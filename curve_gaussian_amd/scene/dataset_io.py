@@ -12,12 +12,15 @@
   (edge_extraction/extract_para_edge.py:60-129, 252-256): curves as 4x3 control points, lines as 6 floats, and the
   edge point cloud sampled every 5 mm of Simpson-rule arc length (edge_extraction/extract_uitl.py:291-330).
   ``merge_endpoints`` (opt.merge_endpoints_flag, train.py:257-265) is reproduced as an option
-  (edge_extraction.merge_endpoints; off by default here, on by default in the reference); the visibility check is not.
+  (edge_extraction.merge_endpoints; off by default here, on by default in the reference), and so is
+  ``get_parametric_edge(visible_checking=True)`` (visible_checking=True, scan_dir, detector: the edge-map
+  visibility check, edge_extraction.get_parametric_edge, on the GPU; off by default, as in the reference).
 * ``point_cloud.ply`` splat snapshot -- ``save_ply`` (scene/gaussian_model.py:267-280, 383-400; scene/__init__.py:96).
 
 Parity: the camera arithmetic is pinned by tests/golden/emap_camera.npz (reference graphics_utils imported by
-tests/golden/make_golden.py); the edge_extraction modules cannot be imported here (cv2 / point_cloud_utils missing), so
-the sampling is restated and unpinned."""
+tests/golden/make_golden.py); the edge sampling and the visibility check by tests/golden/visibility/visibility.npz
+(edge_extraction/extract_para_edge.py imported by tests/golden/make_visibility_golden.py, cv2 / point_cloud_utils
+replaced by placeholders)."""
 import json
 import math
 import os
@@ -227,15 +230,25 @@ def extract_curves(gaussians, merge_endpoints=False, distance_threshold=0.015):
             "curves_ctl_pts": bez.tolist() if len(bez) > 0 else []}
 
 
-def write_parametric_edges(gaussians, model_path, merge_endpoints=False, distance_threshold=0.015):
+def write_parametric_edges(gaussians, model_path, merge_endpoints=False, distance_threshold=0.015,
+                           visible_checking=False, scan_dir=None, detector="DexiNed"):
     """Writes parametric_edges.json (the evaluation input, train.py:287-293) and edge_points.ply (ASCII, :277-285).
-    merge_endpoints / distance_threshold: see extract_curves (the reference's default is merge_endpoints=True)."""
-    os.makedirs(model_path, exist_ok=True)
+    merge_endpoints / distance_threshold: see extract_curves (the reference's default is merge_endpoints=True).
+    visible_checking=True keeps only the edges that `detector`'s edge maps of the scan at `scan_dir` show
+    (get_parametric_edge(True, ...), edge_extraction.get_parametric_edge; the check runs on the GPU)."""
+    if visible_checking and scan_dir is None:
+        raise ValueError("write_parametric_edges(visible_checking=True) needs scan_dir, the scan holding "
+                         "meta_data.json and the edge maps")
+    from ..edge_extraction.para_edge import get_parametric_edge
     merged = extract_curves(gaussians, merge_endpoints, distance_threshold)
-    curves = np.array(merged["curves_ctl_pts"]).reshape(-1, 12).reshape(-1, 4, 3)
-    lines = np.array(merged["lines_end_pts"]).reshape(-1, 6)
-    edge_dict = {"curves_ctl_pts": curves.tolist(), "lines_end_pts": lines.tolist()}
-    pts = sample_edge_points(curves, lines)
+    pts, edge_dict = get_parametric_edge(visible_checking, merged, scan_dir, detector)
+    write_edge_files(model_path, edge_dict, pts)
+    return edge_dict, pts
+
+
+def write_edge_files(model_path, edge_dict, pts):
+    """parametric_edges.json (`edge_dict`) and edge_points.ply (ASCII, `pts` [N,3]) into `model_path`."""
+    os.makedirs(model_path, exist_ok=True)
     with open(os.path.join(model_path, "parametric_edges.json"), "w") as f:
         json.dump(edge_dict, f)
     with open(os.path.join(model_path, "edge_points.ply"), "w") as f:
@@ -243,7 +256,6 @@ def write_parametric_edges(gaussians, model_path, merge_endpoints=False, distanc
                 "end_header\n" % len(pts))
         for p in pts:
             f.write("%.10g %.10g %.10g\n" % (p[0], p[1], p[2]))
-    return edge_dict, pts
 
 
 # ------------------------------------------------------------------------------------------ splat snapshot (PLY)

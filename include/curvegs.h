@@ -423,6 +423,29 @@ int cgs_nn1(int n_query, const float* query /*[n_query,3]*/, int n_ref, const fl
             float* dist /*[n_query]*/, int* index /*[n_query]*/, void* workspace, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Edge-map visibility check (extraction).  Replaces the (edge, frame) loop of the reference's compute_visibility
+ * (edge_extraction/extract_para_edge.py:145-197, called by get_parametric_edge(visible_checking=True) :200-249):
+ * counts[e] = the number of frames f in which edge e is seen by the 2D edge detector.  Edges are the curves (4 control
+ * points each) followed by the lines (2 end points each); only these points are projected, never sampled points.
+ * Per frame: K[f] (row-major 3x3) and w2c[f] = inv(camtoworld)[:3,:4] (row-major 3x4, inverted on the host); each point
+ * is projected in float64 as x = K (R X + T), every dot product ((a0*b0 + a1*b1) + a2*b2) + t without FMA contraction,
+ * then divided by x[2] with IEEE division.  Quirks kept: no z > 0 test (a point behind the camera projects mirrored and
+ * counts if it lands in the image); z = 0 gives inf / NaN and drops the point; coordinates round half to even (np.round)
+ * and a point is kept if 0 <= u < width and 0 <= v < height.  The cell is 0 with no kept point, else
+ * mean(values) > 0.1 && max(values) > 0.5 with the mean summed left to right in control-point order (np.mean over <= 4
+ * values); values are maps[f][v][u] / 255.0, or 1 - maps[f][v][u] / 255.0 when invert = 1 (DexiNed).
+ * maps: uint8 [n_frames, height, width], one byte per pixel (offsets are 64-bit: the buffer may exceed 2^31 bytes).
+ * The caller applies the reference's mask, counts > ceil(0.05 * n_frames).  Counts are deterministic (integer sums).
+ * n_curves + n_lines = 0 is a no-op; negative sizes, more than 2^30 edges, height or width <= 0 with n_frames > 0 and
+ * NULL pointers with a non-zero size are CGS_ERR_INVALID_ARGUMENT, rejected before anything is launched.
+ * ------------------------------------------------------------------------------------------------ */
+int cgs_edge_visibility(int n_curves, const double* curves /*[n_curves,4,3]*/, int n_lines,
+                        const double* lines /*[n_lines,2,3]*/, int n_frames, const double* K /*[n_frames,3,3]*/,
+                        const double* w2c /*[n_frames,3,4]*/, int height, int width,
+                        const unsigned char* maps /*[n_frames,height,width]*/, int invert, int* counts /*[E]*/,
+                        void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Per-call options of the operator API.  The `debug` argument of cgs_rasterize_forward / cgs_rasterize_backward is a bit
  * set: bit 0 is the reference's debug flag (rasterize_points.cu:53: synchronise and check after every kernel), the bits
  * below select measurement / parity variants FOR THAT CALL ONLY -- nothing process-wide, nothing another thread's call
