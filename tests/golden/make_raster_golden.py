@@ -1,11 +1,12 @@
 #!/usr/bin/env python
 """Freezes the rasterizer ORACLE (oracle/raster_ref.c) on four small scenes -> tests/golden/raster_{small,ties,opaque,room}.npz.
 
-What these files are, and what they are not.  The reference rasterizer ships no tests or vectors and cannot be built here
-(nvcc / cub / GLM absent), so nothing can pin the oracle to the reference's binary output: these fixtures do NOT change the
-"parity unpinned" status of K1-K10.  They pin the oracle AND the kernels to a point in time: the oracle is
-rebuilt from source on every box, so without a frozen copy the two could drift together unnoticed.  `-m "not gpu"` tests compare
-today's oracle build with the file, `-m gpu` tests compare the HIP path with the file.
+What these files are.  The oracle is rebuilt from source on every box, so without a frozen copy it and the kernels could drift
+together unnoticed; the files pin both to a point in time.  Since the reference rasterizer itself is built as an oracle
+(oracle/ref_raster/) the files are also held to the REFERENCE's binary on the GPU
+(tests/test_ref_raster_gpu.py::test_reference_binary_reproduces_the_frozen_fixtures): radii, num_rendered, tile ranges and
+per-tile lists bit-exact, forward images within 2.7e-7 of the maximum, gradients within the 1e-4 parity budget.
+`-m "not gpu"` tests compare today's oracle build with the file, `-m gpu` tests compare the HIP path with the file.
 
     python tests/golden/make_raster_golden.py          # rewrites the four files (do this ONLY for a deliberate oracle change)
 

@@ -1,6 +1,6 @@
 """CPU: today's build of the rasterizer oracle (oracle/raster_ref.c, compiled on this box) against the FROZEN copy of its
 outputs in tests/golden/raster_*.npz (tests/golden/make_raster_golden.py).  Guards against oracle / kernel co-drift: the GPU
-suite holds the HIP path to the same files.  It does not pin the oracle to the reference (nothing can here)."""
+suite holds the HIP path to the same files.  The GPU suite holds the reference's own binary to them too (tests/test_ref_raster_gpu.py)."""
 import os
 import sys
 
