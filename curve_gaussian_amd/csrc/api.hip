@@ -287,6 +287,182 @@ __global__ void __launch_bounds__(256) k_clamp_backward(size_t n, const float* _
         g_out[i] = (x >= 0.f && x <= 1.f) ? g_in[i] : 0.f;   // torch.clamp's backward: the gradient passes where min <= x <= max
     }
 }
+
+// ---------------------------------------------------------------------------------------------- shared sequencing
+// Tile grid and focal lengths of one W x H frame (rasterizer_impl.cu:227-228)
+struct Frame {
+    int W, H, gx, gy, tiles;
+    size_t npix;
+    float focal_x, focal_y;
+    Frame(int width, int height, float tan_fovx = 1.f, float tan_fovy = 1.f)
+        : W(width), H(height), gx((width + TILE - 1) / TILE), gy((height + TILE - 1) / TILE), tiles(gx * gy),
+          npix((size_t)width * height), focal_x(width / (2.0f * tan_fovx)), focal_y(height / (2.0f * tan_fovy)) {}
+};
+// The states carved from the three buffers (a NULL binning buffer is skipped: the operator forward sizes it later).
+// clear_bytes: tile_count, tile_cursor and the status words are adjacent 128B-aligned carve-outs, cleared by one launch.
+struct States { GeomState geom; BinState bin; ImageState img; size_t clear_bytes; };
+static States carve_states(const Frame& f, int P, const void* geometry, const void* binning, size_t bin_slots, const void* image) {
+    char *gchunk = (char*)geometry, *bchunk = (char*)binning, *ichunk = (char*)image;
+    States b{};
+    b.geom = geom_from_chunk(gchunk, (size_t)P);
+    if (bchunk) b.bin = bin_from_chunk(bchunk, bin_slots);
+    b.img = image_from_chunk(ichunk, f.npix, (size_t)f.tiles);
+    b.clear_bytes = (size_t)((char*)(b.img.total + TOTAL_WORDS) - (char*)b.img.tile_count);
+    return b;
+}
+
+// Splat inputs of the two operator forwards: exactly one of shs / colors_precomp and one of (scales, rotations) /
+// cov3D_precomp, all_map with render_geo, cam_pos with shs, rotations and all_map 16-byte aligned
+static bool splat_inputs_ok(const char* fn, int M, const float* means3D, const float* shs, const float* colors_precomp,
+                            const float* opacities, const float* scales, const float* rotations, const float* cov3D_precomp,
+                            const float* all_map, const float* cam_pos, int render_geo, const int* radii) {
+    if (!means3D || !opacities || !radii || (!shs == !colors_precomp) ||
+        (cov3D_precomp ? (scales || rotations) : (!scales || !rotations)) || (render_geo && !all_map) ||
+        (shs && (!cam_pos || M <= 0))) {
+        set_error("%s: inconsistent inputs (need exactly one of shs/colors_precomp and one of "
+                  "(scales,rotations)/cov3D_precomp; all_map is required with render_geo)", fn);
+        return false;
+    }
+    if (!aligned16(rotations) || !aligned16(all_map)) {
+        set_error("%s: rotations/all_map must be 16-byte aligned", fn);
+        return false;
+    }
+    return true;
+}
+// A caller-chosen bucket capacity and the binning buffer it needs
+static bool bucket_cap_ok(const char* fn, uint32_t bucket_capacity, int tiles, size_t binning_bytes) {
+    const uint64_t slots = (uint64_t)bucket_capacity * (uint64_t)tiles;
+    if (bucket_capacity > bucket_cap_limit() || slots >= (1ull << 31) || binning_bytes < cgs_binning_bytes((int64_t)slots)) {
+        set_error("%s: bucket capacity %u needs %zu binning bytes (got %zu; limit %u per tile)", fn, bucket_capacity,
+                  cgs_binning_bytes((int64_t)slots), binning_bytes, bucket_cap_limit());
+        return false;
+    }
+    return true;
+}
+// Bucket capacity for the longest tile list seen recently: 1.25 x + 64, rounded up to 64
+static inline uint64_t bucket_cap_for(int64_t longest) { return (((uint64_t)longest * 5 / 4 + 64) + 63) & ~63ull; }
+
+// Status readback of the forwards that wait for one: a pool of slots (pinned 16-byte buffer + event, created on first use).
+// cgs_rasterize_forward holds a slot for the length of its call; a checked view forward hands its slot out as the HANDLE that
+// cgs_view_forward_wait releases, so forwards of different threads, devices, streams or models are independent (a handle
+// dropped between begin and wait holds its slot until cgs_view_forward_abandon).  An event records only on streams of the
+// device it was created on: a forward takes an idle slot of the current device, else a fresh one, else an idle slot of
+// another device, whose event it re-creates.
+struct StatSlot {
+    uint32_t* h = nullptr;
+    hipEvent_t ev = nullptr;
+    int dev = -1, P = 0, W = 0, H = 0;
+    uint64_t cap = 0;
+    bool busy = false, in_flight = false;   // in_flight: a copy queued and not yet waited for
+};
+constexpr int STAT_SLOTS = 64;
+static StatSlot g_slots[STAT_SLOTS];
+static std::mutex g_slot_mu;
+static int slot_acquire() {   // -> slot index, or a negative status
+    const int dev = current_device();
+    std::lock_guard<std::mutex> lk(g_slot_mu);
+    int fresh = -1, other = -1;
+    for (int i = 0; i < STAT_SLOTS; i++) {
+        StatSlot& v = g_slots[i];
+        if (v.busy) continue;
+        if (v.dev == dev) { v.busy = true; return i; }
+        if (!v.h && fresh < 0) fresh = i;
+        if (v.h && other < 0) other = i;
+    }
+    const int i = fresh >= 0 ? fresh : other;
+    if (i < 0) {
+        set_error("cgs_view_forward_begin: no free status slot for device %d (%d slots; every begin needs its cgs_view_forward_wait)",
+                  dev, STAT_SLOTS);
+        return CGS_ERR_INVALID_ARGUMENT;
+    }
+    StatSlot& v = g_slots[i];
+    if (v.ev) (void)hipEventDestroy(v.ev);
+    v.ev = nullptr;
+    v.dev = -1;
+    hipError_t e = v.h ? hipSuccess : hipHostMalloc((void**)&v.h, 4 * sizeof(uint32_t), hipHostMallocDefault);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&v.ev, hipEventDisableTiming);
+    if (e != hipSuccess) {
+        set_error("pinned readback buffer / event creation failed");
+        return CGS_ERR_HIP;
+    }
+    v.dev = dev;
+    v.busy = true;
+    return i;
+}
+static bool slot_held(int i) {   // (a handle of an outstanding forward)
+    std::lock_guard<std::mutex> lk(g_slot_mu);
+    return i >= 0 && i < STAT_SLOTS && g_slots[i].busy;
+}
+static void slot_release(int i) {
+    std::lock_guard<std::mutex> lk(g_slot_mu);
+    g_slots[i].busy = false;
+}
+// a copy still in flight lands before the pinned words can go to another forward
+static void slot_abandon(int i) {
+    if (g_slots[i].in_flight) (void)hipEventSynchronize(g_slots[i].ev);
+    g_slots[i].in_flight = false;
+    slot_release(i);
+}
+static bool slot_read(int i, const uint32_t* words, hipStream_t s, const char* what) {   // 4 status words + the event behind them
+    hipError_t e = hipMemcpyAsync(g_slots[i].h, words, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipEventRecord(g_slots[i].ev, s);
+    g_slots[i].in_flight = true;
+    if (e != hipSuccess) set_error("%s: status readback failed: %s", what, hipGetErrorString(e));
+    return e == hipSuccess;
+}
+static bool slot_sync(int i, const char* what) {
+    const hipError_t e = hipEventSynchronize(g_slots[i].ev);
+    g_slots[i].in_flight = e != hipSuccess;
+    if (e != hipSuccess) set_error("%s: status readback failed: %s", what, hipGetErrorString(e));
+    return e == hipSuccess;
+}
+// A bucket forward's readback (num_rendered, longest list, visible splats, oversized rects) taken in: the shape's binning
+// hints (num_rendered only when no bucket overflowed), cgs_last_forward_stats and cgs_last_forward_visible
+static bool slot_wait(int i, const char* what) {
+    if (!slot_sync(i, what)) return false;
+    const StatSlot& v = g_slots[i];
+    const uint32_t longest = v.h[1];
+    hints_update(v.P, v.W, v.H, (uint64_t)longest <= v.cap ? (int64_t)v.h[0] : -1, longest, (int64_t)v.h[3], v.dev);
+    g_last_stats[0] = (int64_t)v.h[0]; g_last_stats[1] = (int64_t)longest; g_last_stats[2] = 1;
+    g_last_visible = (int64_t)v.h[2];
+    return true;
+}
+
+// Bucket binning and compositing behind the preprocess of every bucket forward: scatter into buckets of `cap` slots per tile;
+// with a readback slot (>= 0), the status words reduced and copied to it right behind the SCATTER, so that the host's wait
+// overlaps the compositor; the tile sort (inside the compositor when `cap` allows) and the compositor.  `tag` matters only
+// without `unit` (the unit-colour compositors always tag).  The epilogue outputs (either may be NULL) are written by the
+// sorting compositor, else by one launch behind the other one.
+static bool bucket_tail(hipStream_t s, const char* what, const Frame& f, const States& b, uint64_t cap, int P, const int* radii,
+                        const BinHints& hints, int cull, uint32_t* nonunit, bool geo, bool unit, bool tag,
+                        const float* background, float* out_color, float* out_invdepth, float* out_all_map,
+                        float* color_clamped, float* dir_out, const float* wv, int slot) {
+    launch_scatter_bucket(s, P, radii, b.geom.rec, f.gx, f.gy, b.img.tile_count, b.bin.keys, (uint32_t)cap, cull, b.img.total + 3,
+                          hints.big > 0 ? b.img.tile_cursor : nullptr, (uint32_t)f.tiles, nonunit, scatter_spw(hints));
+    if (slot >= 0) {
+        uint32_t* const stat = b.img.work + 4;   // four words of the (cleared) work block
+        hipLaunchKernelGGL(k_count_stats, dim3(STAT_BLOCKS), dim3(256), 0, s, b.img.tile_count, f.tiles, radii, P, b.img.total + 3,
+                           stat, b.img.work + VIS_COUNT_WORD);
+        if (!slot_read(slot, stat, s, what)) return false;
+        StatSlot& v = g_slots[slot];
+        v.P = P; v.W = f.W; v.H = f.H; v.cap = cap;
+    }
+    if (render_fwd_can_sort((uint32_t)cap) && fuse_sort()) {
+        launch_render_fwd_sorting(s, geo, f.tiles, b.img.tile_count, b.bin.keys, (uint32_t)cap, b.img.ranges, b.img.total,
+                                  b.bin.point_list, f.W, f.H, f.gx, b.geom.rec, b.img.final_T, b.img.n_contrib, background,
+                                  out_color, out_invdepth, out_all_map, unit, tag, color_clamped, dir_out, wv);
+    } else {
+        launch_tile_sort_bucket(s, f.tiles, b.img.tile_count, b.img.ranges, b.img.total, b.bin.keys, b.bin.point_list,
+                                (uint32_t)cap);
+        launch_render_fwd(s, geo, f.tiles, b.img.ranges, b.bin.point_list, f.W, f.H, f.gx, b.geom.rec, b.img.final_T,
+                          b.img.n_contrib, background, out_color, out_invdepth, out_all_map, unit, tag);
+        if (color_clamped || dir_out)   // (long-list buckets: the non-sorting forward has no epilogue of its own)
+            hipLaunchKernelGGL(k_render_epilogue, dim3((unsigned)std::min<size_t>((f.npix + 255) / 256, 4096)), dim3(256), 0, s,
+                               f.npix, out_color, out_all_map, wv, 1, color_clamped, dir_out);
+    }
+    return check_launch(what, false, s);
+}
+
 extern "C" {
 
 const char* cgs_last_error(void) { return g_err; }
@@ -300,8 +476,8 @@ size_t cgs_geometry_bytes(int P) {
 }
 size_t cgs_image_bytes(int width, int height) {
     char* c = nullptr;
-    const size_t tiles = (size_t)((width + TILE - 1) / TILE) * ((height + TILE - 1) / TILE);
-    image_from_chunk(c, (size_t)width * height, tiles);
+    const Frame f(width, height);
+    image_from_chunk(c, f.npix, (size_t)f.tiles);
     return (size_t)c + 128;
 }
 size_t cgs_binning_bytes(int64_t R) {
@@ -366,162 +542,78 @@ int64_t cgs_rasterize_forward(cgs_alloc_fn geometry_alloc, void* geometry_user, 
         set_error("cgs_rasterize_forward: invalid argument (P=%d W=%d H=%d or NULL output/camera pointer)", P, width, height);
         return CGS_ERR_INVALID_ARGUMENT;
     }
-    const size_t npix = (size_t)width * height;
+    const Frame f(width, height, tan_fovx, tan_fovy);
     if (P == 0) {  // rasterize_points.cu:91: outputs stay zero-filled, nothing is rendered (not even background)
-        if (zero_async(out_color, npix * 4, s) != hipSuccess || zero_async(out_invdepth, npix * 4, s) != hipSuccess ||
-            zero_async(out_all_map, npix * 16, s) != hipSuccess) {
+        if (zero_async(out_color, f.npix * 4, s) != hipSuccess || zero_async(out_invdepth, f.npix * 4, s) != hipSuccess ||
+            zero_async(out_all_map, f.npix * 16, s) != hipSuccess) {
             set_error("zero_async failed");
             return CGS_ERR_HIP;
         }
         return 0;
     }
-    if (!means3D || !opacities || !radii || (!shs == !colors_precomp) ||
-        (cov3D_precomp ? (scales || rotations) : (!scales || !rotations)) || (render_geo && !all_map) ||
-        (shs && (!cam_pos || M <= 0))) {
-        set_error("cgs_rasterize_forward: inconsistent inputs (need exactly one of shs/colors_precomp and one of "
-                  "(scales,rotations)/cov3D_precomp; all_map is required with render_geo)");
+    if (!splat_inputs_ok("cgs_rasterize_forward", M, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
+                         all_map, cam_pos, render_geo, radii))
         return CGS_ERR_INVALID_ARGUMENT;
-    }
-    if (!aligned16(rotations) || !aligned16(all_map)) {
-        set_error("cgs_rasterize_forward: rotations/all_map must be 16-byte aligned");
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
-    const int gx = (width + TILE - 1) / TILE, gy = (height + TILE - 1) / TILE;
-    const int tiles = gx * gy;
-    const float focal_y = height / (2.0f * tan_fovy);  // rasterizer_impl.cu:227-228
-    const float focal_x = width / (2.0f * tan_fovx);
-
     char* gchunk = (char*)geometry_alloc(geometry_user, cgs_geometry_bytes(P));
     char* ichunk = (char*)image_alloc(image_user, cgs_image_bytes(width, height));
     if (!gchunk || !ichunk) {
         set_error("cgs_rasterize_forward: geometry/image allocation callback returned NULL");
         return CGS_ERR_ALLOC;
     }
-    GeomState geom = geom_from_chunk(gchunk, (size_t)P);
-    ImageState img = image_from_chunk(ichunk, npix, (size_t)tiles);
-
-    // tile_count and tile_cursor are adjacent 128B-aligned carve-outs: clear both (+total) with one memset
-    const size_t clear_bytes = (size_t)((char*)(img.total + TOTAL_WORDS) - (char*)img.tile_count);
+    States b = carve_states(f, P, gchunk, nullptr, 0, ichunk);
     const int cull = (debug & CGS_OPT_NO_TILE_CULLING) ? 0 : 1;   // per call (include/curvegs.h)
     debug &= CGS_OPT_DEBUG;
-    // pinned copy of img.total + the event behind it: per calling thread AND per device (an event only records on streams of
-    // the device it was created on)
-    constexpr int MAX_DEV = 16;
-    static thread_local uint32_t* h_tot_dev[MAX_DEV] = {};
-    static thread_local hipEvent_t ev_dev[MAX_DEV] = {};
-    const int dev_ix = current_device();
-    if (dev_ix < 0 || dev_ix >= MAX_DEV) {
-        set_error("cgs_rasterize_forward: device index %d out of range", dev_ix);
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
-    if (!h_tot_dev[dev_ix]) {
-        if (hipHostMalloc((void**)&h_tot_dev[dev_ix], TOTAL_WORDS * sizeof(uint32_t), hipHostMallocDefault) != hipSuccess ||
-            hipEventCreateWithFlags(&ev_dev[dev_ix], hipEventDisableTiming) != hipSuccess) {
-            set_error("pinned readback buffer / event creation failed");
-            if (h_tot_dev[dev_ix]) (void)hipHostFree(h_tot_dev[dev_ix]);
-            h_tot_dev[dev_ix] = nullptr;
-            return CGS_ERR_HIP;
-        }
-    }
-    uint32_t* const h_tot = h_tot_dev[dev_ix];
-    const hipEvent_t ev = ev_dev[dev_ix];
-    auto read_totals = [&]() -> bool {  // async copy of img.total + event; the caller waits on the event later
-        hipError_t e = hipMemcpyAsync(h_tot, img.total, TOTAL_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipEventRecord(ev, s);
-        if (e != hipSuccess) set_error("reading num_rendered failed: %s", hipGetErrorString(e));
-        return e == hipSuccess;
-    };
-    auto wait_totals = [&]() -> bool {
-        const hipError_t e = hipEventSynchronize(ev);
-        if (e != hipSuccess) set_error("reading num_rendered failed: %s", hipGetErrorString(e));
-        return e == hipSuccess;
-    };
+    // the status readback of this (blocking) call: a slot of the pool, given back (after its copy landed) when the call returns
+    struct Lease { int i; ~Lease() { slot_abandon(i); } };
+    const int slot = slot_acquire();
+    if (slot < 0) return slot;
+    const Lease lease{slot};
+    const uint32_t* const h_tot = g_slots[slot].h;
     // tile_count == NULL (bucket binning): the kernel does not count, so it can clear the histogram/cursors/status words
     // itself; with counting, they are cleared by a separate launch first.  Either way it zeroes the gradient accumulators.
     auto preprocess = [&](uint32_t* tile_count) -> bool {
-        launch_preprocess_fwd(s, P, D, M, means3D, scales, scale_modifier, rotations, opacities, shs, geom.clamped,
+        launch_preprocess_fwd(s, P, D, M, means3D, scales, scale_modifier, rotations, opacities, shs, b.geom.clamped,
                               cov3D_precomp, colors_precomp, render_geo ? all_map : nullptr, viewmatrix, projmatrix,
-                              cam_pos, width, height, tan_fovx, tan_fovy, focal_x, focal_y, radii, geom.rec, geom.rgb,
-                              gx, gy, tile_count, antialiasing, cull, geom.grad_acc, img.tile_count,
-                              tile_count ? 0 : clear_bytes / sizeof(uint32_t));
+                              cam_pos, width, height, tan_fovx, tan_fovy, f.focal_x, f.focal_y, radii, b.geom.rec, b.geom.rgb,
+                              f.gx, f.gy, tile_count, antialiasing, cull, b.geom.grad_acc, b.img.tile_count,
+                              tile_count ? 0 : b.clear_bytes / sizeof(uint32_t));
         return check_launch("preprocess_fwd", debug, s);
     };
     const bool tag = list_tags_fit(P);
-    uint32_t* const nonunit = img.work + NONUNIT_WORD;
-    auto render = [&](const uint32_t* point_list) -> bool {
-        launch_render_fwd(s, render_geo != 0, tiles, img.ranges, point_list, width, height, gx, geom.rec, img.final_T,
-                          img.n_contrib, background, out_color, out_invdepth, out_all_map, false, tag);
-        return check_launch("render_fwd", debug, s);
-    };
+    uint32_t* const nonunit = b.img.work + NONUNIT_WORD;
 
     // ---- path B: single-pass bucket binning (default once a previous forward has told us how long tile lists get).
-    // Every tile owns a fixed-capacity bucket, so neither the per-tile count pass, nor the scan, nor num_rendered is
-    // needed before the compositor can be queued: the whole forward is enqueued back to back and the host only waits
-    // for the 16-byte readback (num_rendered is part of the reference's API) while the compositor is already running.
-    // A tile that outgrows its bucket raises the overflow flag and the call falls through to the exact path below.
-    bool preprocessed = false;
+    // The whole forward is enqueued back to back and the host only waits for the 16-byte readback (num_rendered is part of
+    // the reference's API) while the compositor is already running.  A tile that outgrows its bucket raises the overflow
+    // flag and the call falls through to the exact path below.
     const BinHints hints = hints_load(P, width, height);
-    const int64_t max_hint = hints.max;
-    if (cull && !debug && max_hint > 0) {
-        const uint64_t cap = (((uint64_t)max_hint * 5 / 4 + 64) + 63) & ~63ull;
-        if (cap <= bucket_cap_limit() && cap * (uint64_t)tiles < (1ull << 31)) {
+    if (cull && !debug && hints.max > 0) {
+        const uint64_t cap = bucket_cap_for(hints.max);
+        if (cap <= bucket_cap_limit() && cap * (uint64_t)f.tiles < (1ull << 31)) {
             if (!preprocess(nullptr)) return CGS_ERR_HIP;
-            preprocessed = true;
-            char* bchunk = (char*)binning_alloc(binning_user, cgs_binning_bytes((int64_t)(cap * tiles)));
+            char* bchunk = (char*)binning_alloc(binning_user, cgs_binning_bytes((int64_t)(cap * f.tiles)));
             if (!bchunk) {
                 set_error("cgs_rasterize_forward: binning allocation callback returned NULL");
                 return CGS_ERR_ALLOC;
             }
-            BinState bin = bin_from_chunk(bchunk, (size_t)(cap * tiles));
-            const bool defer_big = hints.big > 0;
-            launch_scatter_bucket(s, P, radii, geom.rec, gx, gy, img.tile_count, bin.keys, (uint32_t)cap, cull, img.total + 3,
-                                  defer_big ? img.tile_cursor : nullptr, (uint32_t)tiles, nonunit, scatter_spw(hints));   // (cursors: unused here)
-            // num_rendered (part of the reference's return value) and the longest tile list are known once the SCATTER is done:
-            // one small launch reduces the tile histogram, 16 bytes travel to the host, and the forward compositor -- which
-            // sorts every tile's bucket itself, like the sync-free forward's -- is queued behind them before the host waits.
-            // (Round 4 ran a separate sort launch here so that the readback could follow it: 30 us of kernel per view.)
-            uint32_t* const stat = img.work + 4;   // four words of the (cleared) work block
-            hipLaunchKernelGGL(k_count_stats, dim3(STAT_BLOCKS), dim3(256), 0, s, img.tile_count, tiles, radii, P, img.total + 3, stat,
-                               img.work + VIS_COUNT_WORD);
-            {
-                hipError_t e = hipMemcpyAsync(h_tot, stat, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, s);
-                if (e == hipSuccess) e = hipEventRecord(ev, s);
-                if (e != hipSuccess) {
-                    set_error("reading num_rendered failed: %s", hipGetErrorString(e));
-                    return CGS_ERR_HIP;
-                }
-            }
-            if (fuse_sort() && render_fwd_can_sort((uint32_t)cap)) {
-                launch_render_fwd_sorting(s, render_geo != 0, tiles, img.tile_count, bin.keys, (uint32_t)cap, img.ranges, img.total,
-                                          bin.point_list, width, height, gx, geom.rec, img.final_T, img.n_contrib, background,
-                                          out_color, out_invdepth, out_all_map, false, tag);
-                if (!check_launch("render_fwd", debug, s)) return CGS_ERR_HIP;
-            } else {
-                launch_tile_sort_bucket(s, tiles, img.tile_count, img.ranges, img.total, bin.keys, bin.point_list, (uint32_t)cap);
-                if (!render(bin.point_list)) return CGS_ERR_HIP;
-            }
-            if (!wait_totals()) return CGS_ERR_HIP;
-            const uint32_t longest = h_tot[1];
-            const int64_t Rb = (int64_t)h_tot[0];   // (= the sum of the list lengths whenever no bucket overflowed)
-            g_last_visible = (int64_t)h_tot[2];
-            hints_update(P, width, height, (uint64_t)longest <= cap ? Rb : -1, longest, (int64_t)h_tot[3]);
-            if ((uint64_t)longest <= cap) {
-                g_last_stats[0] = Rb; g_last_stats[1] = (int64_t)longest; g_last_stats[2] = 1;
-                return Rb;
-            }
+            b.bin = bin_from_chunk(bchunk, (size_t)(cap * f.tiles));
+            if (!bucket_tail(s, "render_fwd", f, b, cap, P, radii, hints, cull, nonunit, render_geo != 0, false, tag, background,
+                             out_color, out_invdepth, out_all_map, nullptr, nullptr, nullptr, slot) ||
+                !slot_wait(slot, "cgs_rasterize_forward"))
+                return CGS_ERR_HIP;
+            if ((uint64_t)h_tot[1] <= cap) return (int64_t)h_tot[0];
             // overflow: the image just rendered is incomplete -- redo the binning with exact sizes
         }
     }
 
     // ---- path A: exact layout (count -> scan -> scatter -> sort); bit-identical to the reference's binning when
     // tile culling is off.  Used for the first forward, in debug mode, with culling off and after a bucket overflow.
-    if (zero_async(img.tile_count, clear_bytes, s) != hipSuccess) {
+    if (zero_async(b.img.tile_count, b.clear_bytes, s) != hipSuccess) {
         set_error("zero_async(tile histogram) failed");
         return CGS_ERR_HIP;
     }
-    if (!preprocess(img.tile_count)) return CGS_ERR_HIP;
-    (void)preprocessed;
-    launch_scan_tiles(s, tiles, img.tile_count, img.ranges, img.total);
+    if (!preprocess(b.img.tile_count)) return CGS_ERR_HIP;
+    launch_scan_tiles(s, f.tiles, b.img.tile_count, b.img.ranges, b.img.total);
     if (!check_launch("scan_tiles", debug, s)) return CGS_ERR_HIP;
 
     // num_rendered has to reach the host (it sizes the binning buffer and is part of the reference's API).  Instead of
@@ -529,7 +621,7 @@ int64_t cgs_rasterize_forward(cgs_alloc_fn geometry_alloc, void* geometry_user, 
     // binning kernels are launched SPECULATIVELY into a buffer sized from the previous call's R (+25 %) while an event
     // marks the readback; the host then waits on the event only.  If the guess was too small (scene changed a lot)
     // the kernels skipped every tile that would not fit and are re-run on an exact-size buffer.
-    if (!read_totals()) return CGS_ERR_HIP;
+    if (!slot_read(slot, b.img.total, s, "cgs_rasterize_forward")) return CGS_ERR_HIP;
     const int64_t hint = hints.R;
     int64_t cap = 0;
     char* bchunk = nullptr;
@@ -542,15 +634,15 @@ int64_t cgs_rasterize_forward(cgs_alloc_fn geometry_alloc, void* geometry_user, 
             return CGS_ERR_ALLOC;
         }
         bin = bin_from_chunk(bchunk, (size_t)cap);
-        launch_scatter(s, P, radii, geom.rec, gx, gy, img.ranges, img.tile_cursor, bin.keys, (uint32_t)cap, cull, nonunit);
-        launch_tile_sort_small(s, tiles, img.ranges, bin.keys, bin.point_list, (uint32_t)cap);
+        launch_scatter(s, P, radii, b.geom.rec, f.gx, f.gy, b.img.ranges, b.img.tile_cursor, bin.keys, (uint32_t)cap, cull, nonunit);
+        launch_tile_sort_small(s, f.tiles, b.img.ranges, bin.keys, bin.point_list, (uint32_t)cap);
     }
-    if (!wait_totals()) return CGS_ERR_HIP;
+    if (!slot_sync(slot, "cgs_rasterize_forward")) return CGS_ERR_HIP;
     const int64_t R = (int64_t)h_tot[0];
     const uint32_t max_count = h_tot[1];
     hints_update(P, width, height, R, max_count, -1);
     if (!bchunk || R > cap) {  // first call, debug mode, or the speculative buffer was too small: exact-size (re)run
-        if (cap > 0 && zero_async(img.tile_cursor, (size_t)tiles * sizeof(uint32_t), s) != hipSuccess) {
+        if (cap > 0 && zero_async(b.img.tile_cursor, (size_t)f.tiles * sizeof(uint32_t), s) != hipSuccess) {
             set_error("zero_async(tile cursors) failed");
             return CGS_ERR_HIP;
         }
@@ -562,17 +654,20 @@ int64_t cgs_rasterize_forward(cgs_alloc_fn geometry_alloc, void* geometry_user, 
         }
         bin = bin_from_chunk(bchunk, (size_t)(R > 0 ? R : 1));
         if (R > 0) {
-            launch_scatter(s, P, radii, geom.rec, gx, gy, img.ranges, img.tile_cursor, bin.keys, (uint32_t)cap, cull, nonunit);
+            launch_scatter(s, P, radii, b.geom.rec, f.gx, f.gy, b.img.ranges, b.img.tile_cursor, bin.keys, (uint32_t)cap, cull,
+                           nonunit);
             if (!check_launch("scatter", debug, s)) return CGS_ERR_HIP;
-            launch_tile_sort_small(s, tiles, img.ranges, bin.keys, bin.point_list, (uint32_t)cap);
+            launch_tile_sort_small(s, f.tiles, b.img.ranges, bin.keys, bin.point_list, (uint32_t)cap);
             if (!check_launch("tile_sort", debug, s)) return CGS_ERR_HIP;
         }
     }
     if (R > 0) {
-        launch_tile_sort_big(s, tiles, img.ranges, bin.keys, bin.point_list, max_count);  // no-op unless a list > 1024
+        launch_tile_sort_big(s, f.tiles, b.img.ranges, bin.keys, bin.point_list, max_count);  // no-op unless a list > 1024
         if (!check_launch("tile_sort", debug, s)) return CGS_ERR_HIP;
     }
-    if (!render(bin.point_list)) return CGS_ERR_HIP;
+    launch_render_fwd(s, render_geo != 0, f.tiles, b.img.ranges, bin.point_list, width, height, f.gx, b.geom.rec, b.img.final_T,
+                      b.img.n_contrib, background, out_color, out_invdepth, out_all_map, false, tag);
+    if (!check_launch("render_fwd", debug, s)) return CGS_ERR_HIP;
     g_last_stats[0] = R; g_last_stats[1] = (int64_t)max_count; g_last_stats[2] = 0;
     return R;
 }
@@ -593,57 +688,28 @@ int cgs_rasterize_forward_static(void* geometry_buffer, void* binning_buffer, si
         set_error("cgs_rasterize_forward_static: invalid argument (P=%d W=%d H=%d, NULL pointer or zero capacity)", P, width, height);
         return CGS_ERR_INVALID_ARGUMENT;
     }
-    if (!means3D || !opacities || !radii || (!shs == !colors_precomp) ||
-        (cov3D_precomp ? (scales || rotations) : (!scales || !rotations)) || (render_geo && !all_map) ||
-        (shs && (!cam_pos || M <= 0)) || !aligned16(rotations) || !aligned16(all_map)) {
-        set_error("cgs_rasterize_forward_static: inconsistent or misaligned inputs");
+    const Frame f(width, height, tan_fovx, tan_fovy);
+    if (!splat_inputs_ok("cgs_rasterize_forward_static", M, means3D, shs, colors_precomp, opacities, scales, rotations,
+                         cov3D_precomp, all_map, cam_pos, render_geo, radii) ||
+        !bucket_cap_ok("cgs_rasterize_forward_static", bucket_capacity, f.tiles, binning_bytes))
         return CGS_ERR_INVALID_ARGUMENT;
-    }
-    const int gx = (width + TILE - 1) / TILE, gy = (height + TILE - 1) / TILE;
-    const int tiles = gx * gy;
     const uint64_t cap = bucket_capacity;
-    if (cap > bucket_cap_limit() || cap * (uint64_t)tiles >= (1ull << 31) ||
-        binning_bytes < cgs_binning_bytes((int64_t)(cap * tiles))) {
-        set_error("cgs_rasterize_forward_static: bucket capacity %u needs %zu binning bytes (got %zu; limit %u per tile)",
-                  bucket_capacity, cgs_binning_bytes((int64_t)(cap * tiles)), binning_bytes, bucket_cap_limit());
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
-    const size_t npix = (size_t)width * height;
-    const float focal_y = height / (2.0f * tan_fovy);
-    const float focal_x = width / (2.0f * tan_fovx);
-    char* gchunk = (char*)geometry_buffer;
-    char* bchunk = (char*)binning_buffer;
-    char* ichunk = (char*)image_buffer;
-    GeomState geom = geom_from_chunk(gchunk, (size_t)P);
-    BinState bin = bin_from_chunk(bchunk, (size_t)(cap * tiles));
-    ImageState img = image_from_chunk(ichunk, npix, (size_t)tiles);
-    const size_t clear_bytes = (size_t)((char*)(img.total + TOTAL_WORDS) - (char*)img.tile_count);
-    launch_preprocess_fwd(s, P, D, M, means3D, scales, scale_modifier, rotations, opacities, shs, geom.clamped,
+    const States b = carve_states(f, P, geometry_buffer, binning_buffer, (size_t)(cap * f.tiles), image_buffer);
+    launch_preprocess_fwd(s, P, D, M, means3D, scales, scale_modifier, rotations, opacities, shs, b.geom.clamped,
                           cov3D_precomp, colors_precomp, render_geo ? all_map : nullptr, viewmatrix, projmatrix, cam_pos,
-                          width, height, tan_fovx, tan_fovy, focal_x, focal_y, radii, geom.rec, geom.rgb, gx, gy, nullptr,
-                          antialiasing, 1, geom.grad_acc, img.tile_count, clear_bytes / sizeof(uint32_t));
+                          width, height, tan_fovx, tan_fovy, f.focal_x, f.focal_y, radii, b.geom.rec, b.geom.rgb, f.gx, f.gy,
+                          nullptr, antialiasing, 1, b.geom.grad_acc, b.img.tile_count, b.clear_bytes / sizeof(uint32_t));
     const BinHints hints = hints_load(P, width, height);   // (from the caller's probing forwards of this shape)
-    const bool defer_big = hints.big > 0;
-    const bool tag = list_tags_fit(P);
-    launch_scatter_bucket(s, P, radii, geom.rec, gx, gy, img.tile_count, bin.keys, (uint32_t)cap, 1, img.total + 3,
-                          defer_big ? img.tile_cursor : nullptr, (uint32_t)tiles, img.work + NONUNIT_WORD, scatter_spw(hints));
-    if (render_fwd_can_sort((uint32_t)cap) && fuse_sort()) {
-        launch_render_fwd_sorting(s, render_geo != 0, tiles, img.tile_count, bin.keys, (uint32_t)cap, img.ranges, img.total,
-                                  bin.point_list, width, height, gx, geom.rec, img.final_T, img.n_contrib, background,
-                                  out_color, out_invdepth, out_all_map, false, tag);
-    } else {
-        launch_tile_sort_bucket(s, tiles, img.tile_count, img.ranges, img.total, bin.keys, bin.point_list, (uint32_t)cap);
-        launch_render_fwd(s, render_geo != 0, tiles, img.ranges, bin.point_list, width, height, gx, geom.rec, img.final_T,
-                          img.n_contrib, background, out_color, out_invdepth, out_all_map, false, tag);
-    }
-    if (!check_launch("rasterize_forward_static", false, s)) return CGS_ERR_HIP;
+    if (!bucket_tail(s, "rasterize_forward_static", f, b, cap, P, radii, hints, 1, b.img.work + NONUNIT_WORD, render_geo != 0,
+                     false, list_tags_fit(P), background, out_color, out_invdepth, out_all_map, nullptr, nullptr, nullptr, -1))
+        return CGS_ERR_HIP;
     return CGS_OK;
 }
 
 size_t cgs_image_status_offset(int width, int height) {
     char* c = nullptr;
-    const size_t tiles = (size_t)((width + TILE - 1) / TILE) * ((height + TILE - 1) / TILE);
-    ImageState img = image_from_chunk(c, (size_t)width * height, tiles);
+    const Frame f(width, height);
+    ImageState img = image_from_chunk(c, f.npix, (size_t)f.tiles);
     return (size_t)((char*)img.total - (char*)nullptr);
 }
 int cgs_status_words(void) { return TOTAL_WORDS; }
@@ -687,17 +753,8 @@ int cgs_rasterize_backward(int P, int D, int M, int64_t R, const float* backgrou
         set_error("cgs_rasterize_backward: rotations/dL_dconic/dL_drot must be 16-byte aligned");
         return CGS_ERR_INVALID_ARGUMENT;
     }
-    const int gx = (width + TILE - 1) / TILE, gy = (height + TILE - 1) / TILE;
-    const int tiles = gx * gy;
-    const size_t npix = (size_t)width * height;
-    const float focal_y = height / (2.0f * tan_fovy);
-    const float focal_x = width / (2.0f * tan_fovx);
-    char* gchunk = (char*)geometry_buffer;
-    char* bchunk = (char*)binning_buffer;
-    char* ichunk = (char*)image_buffer;
-    GeomState geom = geom_from_chunk(gchunk, (size_t)P);
-    BinState bin = bin_from_chunk(bchunk, (size_t)(R > 0 ? R : 1));
-    ImageState img = image_from_chunk(ichunk, npix, (size_t)tiles);
+    const Frame f(width, height, tan_fovx, tan_fovy);
+    const States b = carve_states(f, P, geometry_buffer, binning_buffer, (size_t)(R > 0 ? R : 1), image_buffer);
 
     // geom.grad_acc is zero here: the forward's preprocess kernel cleared it and k_preprocess_bwd clears it after use
     if (R > 0) {
@@ -711,18 +768,18 @@ int cgs_rasterize_backward(int P, int D, int M, int64_t R, const float* backgrou
         // forward raised img.work[NONUNIT_WORD] if any visible splat deviates, and the two kernels test that word on entry.
         const uint32_t* gate = nullptr;
         if (tagged && !geo && !invd && !colg && !general_only) {
-            gate = img.work + NONUNIT_WORD;
-            launch_render_bwd_unit(s, tiles, img.ranges, bin.point_list, width, height, gx, background, geom.rec, img.final_T,
-                                   img.n_contrib, dL_dout_color, geom.grad_acc, ACC_STRIDE, gate);
+            gate = b.img.work + NONUNIT_WORD;
+            launch_render_bwd_unit(s, f.tiles, b.img.ranges, b.bin.point_list, width, height, f.gx, background, b.geom.rec,
+                                   b.img.final_T, b.img.n_contrib, dL_dout_color, b.geom.grad_acc, ACC_STRIDE, gate);
         }
-        launch_render_bwd(s, geo, invd, colg, tiles, img.ranges, bin.point_list, width, height, gx, background, geom.rec,
-                          img.final_T, img.n_contrib, dL_dout_color, dL_dout_invdepth, dL_dout_all_map, geom.grad_acc,
-                          ACC_STRIDE, id_mask, gate);
+        launch_render_bwd(s, geo, invd, colg, f.tiles, b.img.ranges, b.bin.point_list, width, height, f.gx, background,
+                          b.geom.rec, b.img.final_T, b.img.n_contrib, dL_dout_color, dL_dout_invdepth, dL_dout_all_map,
+                          b.geom.grad_acc, ACC_STRIDE, id_mask, gate);
         if (!check_launch("render_bwd", debug, s)) return CGS_ERR_HIP;
     }
-    launch_preprocess_bwd(s, P, D, M, means3D, radii, shs, geom.clamped, opacities, scales, rotations, scale_modifier,
-                          cov3D_precomp, viewmatrix, projmatrix, cam_pos, focal_x, focal_y, tan_fovx, tan_fovy, width,
-                          height, geom.rec, geom.grad_acc, dL_dmean2D, dL_dconic, dL_dinvdepth, dL_dopacity, dL_dmean3D,
+    launch_preprocess_bwd(s, P, D, M, means3D, radii, shs, b.geom.clamped, opacities, scales, rotations, scale_modifier,
+                          cov3D_precomp, viewmatrix, projmatrix, cam_pos, f.focal_x, f.focal_y, tan_fovx, tan_fovy, width,
+                          height, b.geom.rec, b.geom.grad_acc, dL_dmean2D, dL_dconic, dL_dinvdepth, dL_dopacity, dL_dmean3D,
                           dL_dcolor, dL_dall_map, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, antialiasing);
     if (!check_launch("preprocess_bwd", debug, s)) return CGS_ERR_HIP;
     return CGS_OK;
@@ -761,73 +818,16 @@ int cgs_sample_curves_forward(int B, int m, const float* curve_points, const flo
 // ---------------------------------------------------------------------------------------------- fused per-view path
 // One view of the training configuration, curve parameters in, image out (and back): the per-splat chains are fused
 // (view.hip), the rasterizer is the sync-free single-pass bucket pipeline of cgs_rasterize_forward_static.
-// Status readback of the checked view forward.  Every cgs_view_forward_begin takes a slot of a small pool (pinned 16-byte
-// buffer + event, created on first use) and returns its handle; cgs_view_forward_wait(handle) blocks on that slot's event and
-// releases it.  Forwards begun by different threads, on different devices or streams, or for different models are
-// independent; a caller that drops a handle (an exception between begin and wait) leaks nothing but the slot until
-// cgs_view_forward_abandon(handle).
-// A slot belongs to the device its event was created on (hipEventRecord rejects an event / stream pair of different devices):
-// a forward only takes slots of the current device.
-struct ViewStat { uint32_t* h = nullptr; hipEvent_t ev = nullptr; int dev = -1, P = 0, W = 0, H = 0; uint64_t cap = 0; bool busy = false; };
-constexpr int VIEW_SLOTS = 64;
-static ViewStat g_view_slots[VIEW_SLOTS];
-static std::mutex g_view_mu;
-static int view_slot_acquire() {   // -> slot index, or a negative status
-    const int dev = current_device();
-    std::lock_guard<std::mutex> lk(g_view_mu);
-    int fresh = -1;
-    for (int i = 0; i < VIEW_SLOTS; i++) {
-        ViewStat& v = g_view_slots[i];
-        if (v.busy) continue;
-        if (!v.h) { if (fresh < 0) fresh = i; continue; }   // never used: taken only when no idle slot of this device exists
-        if (v.dev != dev) continue;
-        v.busy = true;
-        return i;
-    }
-    if (fresh >= 0) {
-        ViewStat& v = g_view_slots[fresh];
-        if (hipHostMalloc((void**)&v.h, 4 * sizeof(uint32_t), hipHostMallocDefault) != hipSuccess ||
-            hipEventCreateWithFlags(&v.ev, hipEventDisableTiming) != hipSuccess) {
-            set_error("pinned readback buffer / event creation failed");
-            if (v.h) (void)hipHostFree(v.h);
-            v.h = nullptr;
-            return CGS_ERR_HIP;
-        }
-        v.dev = dev;
-        v.busy = true;
-        return fresh;
-    }
-    set_error("cgs_view_forward_begin: no free status slot for device %d (%d slots; every begin needs its cgs_view_forward_wait)", dev,
-              VIEW_SLOTS);
-    return CGS_ERR_INVALID_ARGUMENT;
-}
-static bool view_slot_busy(int i) {
-    std::lock_guard<std::mutex> lk(g_view_mu);
-    return g_view_slots[i].busy;
-}
-static void view_slot_release(int i) {
-    std::lock_guard<std::mutex> lk(g_view_mu);
-    g_view_slots[i].busy = false;
-}
 static int64_t view_forward_wait(int handle, int64_t* n_visible) {
-    if (handle < 0 || handle >= VIEW_SLOTS || !view_slot_busy(handle)) {
+    if (!slot_held(handle)) {
         set_error("cgs_view_forward_wait: handle %d is not an outstanding checked forward", handle);
         return CGS_ERR_INVALID_ARGUMENT;
     }
-    ViewStat& v = g_view_slots[handle];
-    const hipError_t e = hipEventSynchronize(v.ev);
-    if (e != hipSuccess) {
-        view_slot_release(handle);
-        set_error("cgs_view_forward_checked: status readback failed: %s", hipGetErrorString(e));
-        return CGS_ERR_HIP;
-    }
-    const uint32_t longest = v.h[1];
-    hints_update(v.P, v.W, v.H, (uint64_t)longest <= v.cap ? (int64_t)v.h[0] : -1, longest, (int64_t)v.h[3], v.dev);
-    g_last_stats[0] = (int64_t)v.h[0]; g_last_stats[1] = (int64_t)longest; g_last_stats[2] = 1;
-    g_last_visible = (int64_t)v.h[2];
-    if (n_visible) *n_visible = (int64_t)v.h[2];
-    view_slot_release(handle);
-    return (int64_t)longest;
+    const bool ok = slot_wait(handle, "cgs_view_forward_wait");
+    const int64_t longest = (int64_t)g_slots[handle].h[1];
+    if (ok && n_visible) *n_visible = g_last_visible;
+    slot_release(handle);
+    return ok ? longest : CGS_ERR_HIP;
 }
 
 static int64_t view_forward_impl(int mode, int B, int m, const float* curve_points, const float* width, const uint8_t* is_bezier, const float* coef,
@@ -852,75 +852,30 @@ static int64_t view_forward_impl(int mode, int B, int m, const float* curve_poin
                   width_px, height_px);
         return CGS_ERR_INVALID_ARGUMENT;
     }
-    const int gx = (width_px + TILE - 1) / TILE, gy = (height_px + TILE - 1) / TILE;
-    const int tiles = gx * gy;
+    const Frame f(width_px, height_px, tan_fovx, tan_fovy);
+    if (!bucket_cap_ok("cgs_view_forward", bucket_capacity, f.tiles, binning_bytes)) return CGS_ERR_INVALID_ARGUMENT;
     const uint64_t cap = bucket_capacity;
-    if (cap > bucket_cap_limit() || cap * (uint64_t)tiles >= (1ull << 31) ||
-        binning_bytes < cgs_binning_bytes((int64_t)(cap * tiles))) {
-        set_error("cgs_view_forward: bucket capacity %u needs %zu binning bytes (got %zu; limit %u per tile)", bucket_capacity,
-                  cgs_binning_bytes((int64_t)(cap * tiles)), binning_bytes, bucket_cap_limit());
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
-    const size_t npix = (size_t)width_px * height_px;
-    const float focal_y = height_px / (2.0f * tan_fovy);
-    const float focal_x = width_px / (2.0f * tan_fovx);
-    char* gchunk = (char*)geometry_buffer;
-    char* bchunk = (char*)binning_buffer;
-    char* ichunk = (char*)image_buffer;
-    GeomState geom = geom_from_chunk(gchunk, (size_t)P);
-    BinState bin = bin_from_chunk(bchunk, (size_t)(cap * tiles));
-    ImageState img = image_from_chunk(ichunk, npix, (size_t)tiles);
-    const size_t clear_bytes = (size_t)((char*)(img.total + TOTAL_WORDS) - (char*)img.tile_count);
+    const States b = carve_states(f, P, geometry_buffer, binning_buffer, (size_t)(cap * f.tiles), image_buffer);
     const bool shared = (mode & VIEW_MODE_SHARED) != 0;
     mode &= VIEW_MODE_MASK;
-    // the norm pass writes the three forward sums and clears the backward's two: no zero-fill launch
-    if (!shared) launch_sample_norms(s, B, m, curve_points, is_bezier, coef, norms);
-    launch_view_forward(s, B, m, curve_points, width, is_bezier, coef, eps, norms, opacity_logit, mask_logit, mask_thr,
-                        colors_precomp, cam_pos, viewmatrix, projmatrix, tan_fovx, tan_fovy, focal_x, focal_y, width_px,
-                        height_px, gx, gy, xyz, rotation, scaling, radii, geom.rec, geom.grad_acc, img.tile_count,
-                        clear_bytes / sizeof(uint32_t));
-    // k_view_fwd writes unit colours (no colors_precomp) and all_map[3] = 1 itself: the compositor derives both sums from T
-    const bool unit = colors_precomp == nullptr;
-    const bool aux = out_all_map != nullptr;   // image-only forward (unit colours required) when the caller passes neither map
-    const BinHints hints = hints_load(P, width_px, height_px);
-    const bool defer_big = hints.big > 0;
-    launch_scatter_bucket(s, P, radii, geom.rec, gx, gy, img.tile_count, bin.keys, (uint32_t)cap, 1, img.total + 3,
-                          defer_big ? img.tile_cursor : nullptr, (uint32_t)tiles, nullptr, scatter_spw(hints));
     // checked: the longest tile list (and the instance count, oversized-rect count) travel to the host right behind the
     // scatter; the compositor is queued before the host waits, so the wait overlaps it
     const bool checked = mode != 0;
-    int slot = -1;
-    if (checked) {
-        slot = view_slot_acquire();
-        if (slot < 0) return slot;
-        ViewStat& vs = g_view_slots[slot];
-        // four words of the (cleared) work block
-        uint32_t* const stat = img.work + 4;
-        hipLaunchKernelGGL(k_count_stats, dim3(STAT_BLOCKS), dim3(256), 0, s, img.tile_count, tiles, radii, P, img.total + 3, stat,
-                               img.work + VIS_COUNT_WORD);
-        hipError_t e = hipMemcpyAsync(vs.h, stat, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipEventRecord(vs.ev, s);
-        if (e != hipSuccess) {
-            view_slot_release(slot);
-            set_error("cgs_view_forward_checked: status readback failed: %s", hipGetErrorString(e));
-            return CGS_ERR_HIP;
-        }
-        vs.P = P; vs.W = width_px; vs.H = height_px; vs.cap = cap;
-    }
-    if (render_fwd_can_sort((uint32_t)cap) && fuse_sort()) {
-        launch_render_fwd_sorting(s, aux, tiles, img.tile_count, bin.keys, (uint32_t)cap, img.ranges, img.total,
-                                  bin.point_list, width_px, height_px, gx, geom.rec, img.final_T, img.n_contrib, background,
-                                  out_color, out_invdepth, out_all_map, unit, unit, out_color_clamped, out_rend_dir, viewmatrix);
-    } else {
-        launch_tile_sort_bucket(s, tiles, img.tile_count, img.ranges, img.total, bin.keys, bin.point_list, (uint32_t)cap);
-        launch_render_fwd(s, aux, tiles, img.ranges, bin.point_list, width_px, height_px, gx, geom.rec, img.final_T,
-                          img.n_contrib, background, out_color, out_invdepth, out_all_map, unit);
-        if (out_color_clamped || out_rend_dir)   // (long-list buckets: the non-sorting forward has no epilogue of its own)
-            hipLaunchKernelGGL(k_render_epilogue, dim3((unsigned)std::min<size_t>((npix + 255) / 256, 4096)), dim3(256), 0, s, npix,
-                               out_color, out_all_map, viewmatrix, 1, out_color_clamped, out_rend_dir);
-    }
-    if (!check_launch("view_forward", false, s)) {
-        if (checked) view_slot_release(slot);
+    const int slot = checked ? slot_acquire() : -1;
+    if (checked && slot < 0) return slot;
+    // the norm pass writes the three forward sums and clears the backward's two: no zero-fill launch
+    if (!shared) launch_sample_norms(s, B, m, curve_points, is_bezier, coef, norms);
+    launch_view_forward(s, B, m, curve_points, width, is_bezier, coef, eps, norms, opacity_logit, mask_logit, mask_thr,
+                        colors_precomp, cam_pos, viewmatrix, projmatrix, tan_fovx, tan_fovy, f.focal_x, f.focal_y, width_px,
+                        height_px, f.gx, f.gy, xyz, rotation, scaling, radii, b.geom.rec, b.geom.grad_acc, b.img.tile_count,
+                        b.clear_bytes / sizeof(uint32_t));
+    // k_view_fwd writes unit colours (no colors_precomp) and all_map[3] = 1 itself: the compositor derives both sums from T.
+    // Image-only forward (unit colours required) when the caller passes neither map.
+    const bool unit = colors_precomp == nullptr;
+    if (!bucket_tail(s, "view_forward", f, b, cap, P, radii, hints_load(P, width_px, height_px), 1, nullptr, out_all_map != nullptr,
+                     unit, unit, background, out_color, out_invdepth, out_all_map, out_color_clamped, out_rend_dir, viewmatrix,
+                     slot)) {
+        if (checked) slot_abandon(slot);
         return CGS_ERR_HIP;
     }
     if (checked) return mode == 1 ? view_forward_wait(slot, nullptr) : (int64_t)slot;
@@ -981,11 +936,7 @@ int cgs_view_forward_render(int checked, int B, int m, const float* curve_points
 }
 int64_t cgs_view_forward_wait(int handle, int64_t* n_visible) { return view_forward_wait(handle, n_visible); }
 void cgs_view_forward_abandon(int handle) {
-    if (handle < 0 || handle >= VIEW_SLOTS || !view_slot_busy(handle)) return;
-    // the slot's readback may still be in flight: let it land before the pinned words can be handed to another forward (a
-    // later forward on ANOTHER stream would otherwise race with it)
-    (void)hipEventSynchronize(g_view_slots[handle].ev);
-    view_slot_release(handle);
+    if (slot_held(handle)) slot_abandon(handle);
 }
 int cgs_view_forward_shared(int B, int m, const float* curve_points, const float* width, const uint8_t* is_bezier, const float* coef,
                      float eps, double* norms, const float* opacity_logit, const float* mask_logit, float mask_thr,
@@ -1005,9 +956,9 @@ int cgs_visible_indices(int P, const int* radii, const void* image_buffer, int w
         set_error("cgs_visible_indices: invalid argument");
         return CGS_ERR_INVALID_ARGUMENT;
     }
-    const size_t tiles = (size_t)((width + TILE - 1) / TILE) * ((height + TILE - 1) / TILE);
+    const Frame f(width, height);
     char* ichunk = (char*)const_cast<void*>(image_buffer);
-    ImageState img = image_from_chunk(ichunk, (size_t)width * height, tiles);
+    ImageState img = image_from_chunk(ichunk, f.npix, (size_t)f.tiles);
     hipLaunchKernelGGL(k_visible_compact, dim3(STAT_BLOCKS), dim3(256), 0, (hipStream_t)stream_, radii, P, img.work + VIS_COUNT_WORD,
                        (long long*)out_indices);
     if (!check_launch("visible_indices", false, (hipStream_t)stream_)) return CGS_ERR_HIP;
@@ -1016,8 +967,7 @@ int cgs_visible_indices(int P, const int* radii, const void* image_buffer, int w
 uint32_t cgs_bucket_capacity_hint(int P, int width, int height) {
     const int64_t mx = hints_load(P, width, height).max;
     if (mx <= 0) return 0u;
-    const uint64_t cap = (((uint64_t)mx * 5 / 4 + 64) + 63) & ~63ull;
-    return (uint32_t)std::min<uint64_t>(cap, bucket_cap_limit());
+    return (uint32_t)std::min<uint64_t>(bucket_cap_for(mx), bucket_cap_limit());
 }
 
 int cgs_view_norms_backward_range(int* first, int* count) {
@@ -1051,30 +1001,22 @@ static int view_backward_impl(int B, int m, const float* curve_points, const flo
         set_error("cgs_view_backward: invalid argument");
         return CGS_ERR_INVALID_ARGUMENT;
     }
-    const int gx = (width_px + TILE - 1) / TILE, gy = (height_px + TILE - 1) / TILE;
-    const int tiles = gx * gy;
-    const size_t npix = (size_t)width_px * height_px;
-    const float focal_y = height_px / (2.0f * tan_fovy);
-    const float focal_x = width_px / (2.0f * tan_fovx);
-    char* gchunk = (char*)geometry_buffer;
-    char* bchunk = (char*)binning_buffer;
-    char* ichunk = (char*)image_buffer;
-    GeomState geom = geom_from_chunk(gchunk, (size_t)P);
-    BinState bin = bin_from_chunk(bchunk, 1);
-    ImageState img = image_from_chunk(ichunk, npix, (size_t)tiles);
+    const Frame f(width_px, height_px, tan_fovx, tan_fovy);
+    const States b = carve_states(f, P, geometry_buffer, binning_buffer, 1, image_buffer);
     // scratch: [B,13] per-curve partials of dL/d{curve_points, width} (k_view_bwd -> k_sample_bwd_close; curve_math.h,
     // sample_backward_tail).  Rounds 2-5 sent 15 floats per SPLAT through here.
     // training configuration: only dL/dcolour flows in, the colours themselves need no gradient; the forward wrote unit
     // colours unless it was given colors_precomp (same argument here): closed-form dL/dalpha, no recurrences (render.hip, UNIT)
     if (colors_precomp == nullptr)
-        launch_render_bwd_unit(s, tiles, img.ranges, bin.point_list, width_px, height_px, gx, background, geom.rec, img.final_T,
-                               img.n_contrib, dL_dout_color, geom.grad_acc, ACC_STRIDE_VIEW, nullptr, clamp_raw);
+        launch_render_bwd_unit(s, f.tiles, b.img.ranges, b.bin.point_list, width_px, height_px, f.gx, background, b.geom.rec,
+                               b.img.final_T, b.img.n_contrib, dL_dout_color, b.geom.grad_acc, ACC_STRIDE_VIEW, nullptr, clamp_raw);
     else   // arbitrary colours: the general training instance (the forward did not tag the lists)
-        launch_render_bwd(s, false, false, false, tiles, img.ranges, bin.point_list, width_px, height_px, gx, background, geom.rec,
-                          img.final_T, img.n_contrib, dL_dout_color, nullptr, nullptr, geom.grad_acc, ACC_STRIDE_VIEW);
+        launch_render_bwd(s, false, false, false, f.tiles, b.img.ranges, b.bin.point_list, width_px, height_px, f.gx, background,
+                          b.geom.rec, b.img.final_T, b.img.n_contrib, dL_dout_color, nullptr, nullptr, b.geom.grad_acc,
+                          ACC_STRIDE_VIEW);
     launch_view_backward(s, B, m, curve_points, width, is_bezier, coef, eps, norms, opacity_logit, mask_logit, mask_thr,
-                         cam_pos, viewmatrix, projmatrix, tan_fovx, tan_fovy, focal_x, focal_y, width_px, height_px, radii,
-                         geom.rec, geom.grad_acc, dL_drotation_extra, dL_dmeans2D, dL_dopacity_logit, dL_dmask_logit, scratch,
+                         cam_pos, viewmatrix, projmatrix, tan_fovx, tan_fovy, f.focal_x, f.focal_y, width_px, height_px, radii,
+                         b.geom.rec, b.geom.grad_acc, dL_drotation_extra, dL_dmeans2D, dL_dopacity_logit, dL_dmask_logit, scratch,
                          ((flags & CGS_VIEW_ACCUMULATE) ? 1 : 0) | ((flags & CGS_VIEW_SHARED) ? 2 : 0));
     if (!(flags & CGS_VIEW_SHARED))
         launch_sample_backward_close(s, B, m, curve_points, width, is_bezier, coef, eps, norms, scratch, dL_dcurve_points,

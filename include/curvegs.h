@@ -56,7 +56,9 @@ const char* cgs_target_arch(void);
  *   out_color [1,H,W], out_invdepth [1,H,W], out_all_map [4,H,W] f32, radii [P] i32 are fully written
  *   (no pre-zeroing required).  Returns num_rendered (#(splat,tile) instances binned) >= 0, which the
  *   caller passes back as R.  Performs one stream synchronisation (to size the binning buffer), like
- *   the reference's blocking 4-byte D2H copy (rasterizer_impl.cu:287).
+ *   the reference's blocking 4-byte D2H copy (rasterizer_impl.cu:287).  The readback goes through a slot of the
+ *   status-slot pool of the checked view forwards (below), held for the length of the call: the call fails like
+ *   cgs_view_forward_begin when all 64 slots are held by outstanding forwards.
  * ------------------------------------------------------------------------------------------------ */
 int64_t cgs_rasterize_forward(
     cgs_alloc_fn geometry_alloc, void* geometry_user,
@@ -177,7 +179,8 @@ int64_t cgs_view_forward_checked(int B, int m, const float* curve_points, const 
  * returns a HANDLE (>= 0; negative: status code); cgs_view_forward_wait(handle, &n_visible) blocks on that readback, releases
  * the handle and returns what cgs_view_forward_checked returns (n_visible, optional: splats with radii > 0 -- sizes render()'s
  * visibility_filter = (radii > 0).nonzero(), gaussian_renderer/__init__.py:150, without a device-wide sync).  Any number of
- * forwards (threads, devices, streams, models) may be outstanding up to a pool of 64; a handle that will never be waited on
+ * forwards (threads, devices, streams, models) may be outstanding up to a pool of 64 status slots, which cgs_rasterize_forward
+ * shares (one slot per call in progress); a slot idle on one device serves another.  A handle that will never be waited on
  * (an exception between the two halves) is returned with cgs_view_forward_abandon. */
 int cgs_view_forward_begin(int B, int m, const float* curve_points, const float* width, const uint8_t* is_bezier, const float* coef,
                      float eps, double* norms, const float* opacity_logit, const float* mask_logit, float mask_thr,

@@ -380,6 +380,61 @@ def test_two_models_interleave_their_fused_forwards():
     assert VR.finish(p2b)[0] and torch.equal(img2b, ref2)
 
 
+def _begin_view(gm, cam, bg):
+    """A checked fused forward left outstanding: (image, Pending) -- its status slot is held until VR.finish()."""
+    from curve_gaussian_amd.ops import view_render as VR
+    pend = []
+    z = torch.zeros_like(gm.get_xyz, requires_grad=True)
+    out = VR.view_render(gm._curve_points, gm._width, gm._opacity, None, z, gm.is_bezier, gm.n_gaussians, 0.01, bg, cam,
+                         *tanfov(cam), 0, None, True, False, pend)
+    return out[0], pend[0]
+
+
+def test_operator_forward_between_begin_and_wait_of_view_forwards():
+    """The operator API (the general route) and the checked view forwards read their status back through one slot pool: an
+    operator forward run while view forwards are outstanding takes a slot of its own and gives it back, and every image
+    equals the one rendered alone."""
+    from curve_gaussian_amd.gaussian_renderer import PipelineParams, render
+    from curve_gaussian_amd.ops import view_render as VR
+    c1, mask1, cam1 = _small(B=150, seed=5)
+    c2, mask2, cam2 = _small(B=260, seed=6, H=64, W=80)
+    gm1, gm2 = _model(c1, mask1), _model(c2, mask2)
+    cam1, cam2 = cam1.to(DEV), cam2.to(DEV)
+    bg = torch.zeros(3, device=DEV)
+    ref1 = render(cam1, gm1, PipelineParams(), bg)["render"].clone()
+    ref2 = render(cam2, gm2, PipelineParams(), bg)["render"].clone()
+    for _ in range(2):   # (the first general forward takes the exact binning path, the second the bucket path)
+        ref_op = render(cam1, gm1, PipelineParams(), bg, fused=False)["render"].clone()
+    pending = [_begin_view(gm, cam, bg) for gm, cam in ((gm1, cam1), (gm2, cam2), (gm1, cam1))]
+    op = render(cam1, gm1, PipelineParams(), bg, fused=False)["render"]
+    assert [VR.finish(p)[0] for _img, p in pending] == [True] * 3
+    assert torch.equal(op, ref_op)
+    for (img, _p), ref in zip(pending, (ref1, ref2, ref1)):
+        assert torch.equal(img, ref)
+
+
+@pytest.mark.skipif(torch.cuda.device_count() < 2, reason="needs two GPUs")
+def test_status_slots_move_to_another_device_once_idle():
+    """Every slot of the pool bound to cuda:0 (64 checked forwards outstanding at once, then finished): a checked view
+    forward and an operator-API forward on cuda:1 rebind idle slots and render what they render alone."""
+    from curve_gaussian_amd.gaussian_renderer import PipelineParams, render
+    from curve_gaussian_amd.ops import view_render as VR
+    c1, mask1, cam1 = _small(B=150, seed=5)
+    gm0, cam0 = _model(c1, mask1), cam1.to(DEV)
+    bg0 = torch.zeros(3, device=DEV)
+    pending = [_begin_view(gm0, cam0, bg0) for _ in range(64)]
+    assert all(VR.finish(p)[0] for _img, p in pending)
+    del pending
+    dev = "cuda:1"
+    with torch.cuda.device(dev):
+        gm, cam, bg = _model(c1, mask1, device=dev), cam1.to(dev), torch.zeros(3, device=dev)
+        view = render(cam, gm, PipelineParams(), bg)["render"].clone()
+        op = render(cam, gm, PipelineParams(), bg, fused=False)["render"].clone()
+        torch.cuda.synchronize()
+        assert torch.equal(render(cam, gm, PipelineParams(), bg)["render"], view)
+        assert torch.equal(render(cam, gm, PipelineParams(), bg, fused=False)["render"], op)
+
+
 def _render_loop(gm, cam, bg, n, out, key):
     from curve_gaussian_amd.gaussian_renderer import PipelineParams, render
     try:
