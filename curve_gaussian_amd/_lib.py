@@ -83,12 +83,20 @@ SIGNATURES = {
     "cgs_nn1_workspace_bytes": (C.c_size_t, [_i]),
     "cgs_nn1": (_i, [_i, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "cgs_edge_visibility": (_i, [_i, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _vp, _i, _vp, _vp]),
+    "cgs_view_metrics_workspace_bytes": (C.c_size_t, [_i]),
+    "cgs_view_metrics": (_i, [_i, _vp, _vp, _vp, _vp, _vp]),
     "cgs_sample_curves_forward": (_i, [_i, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp]),
     "cgs_sample_curves_backward": (_i, [_i, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "cgs_splat_attrs_forward": (_i, [_i, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "cgs_splat_attrs_backward": (_i, [_i, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                       _vp, _vp, _vp]),
 }
+
+
+class MetricView(C.Structure):
+    """cgs_metric_view (include/curvegs.h)."""
+    _fields_ = [("image", _vp), ("gt", _vp), ("channels", _i), ("height", _i), ("width", _i), ("x0", _i)]
+
 
 _lib = None
 

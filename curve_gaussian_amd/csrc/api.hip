@@ -1396,4 +1396,37 @@ int cgs_edge_visibility(int n_curves, const double* curves, int n_lines, const d
     return CGS_OK;
 }
 
+size_t cgs_view_metrics_workspace_bytes(int n_views) { return view_metrics_workspace_bytes(n_views); }
+
+int cgs_view_metrics(int n_views, const cgs_metric_view* views, void* workspace, double* sums, double* means,
+                     void* stream_) {
+    if (n_views < 0 || n_views > 65535) {
+        set_error("cgs_view_metrics: invalid argument (n_views=%d)", n_views);
+        return CGS_ERR_INVALID_ARGUMENT;
+    }
+    if (n_views == 0) return CGS_OK;
+    if (!views || !workspace || !sums) {
+        set_error("cgs_view_metrics: invalid argument (NULL pointer)");
+        return CGS_ERR_INVALID_ARGUMENT;
+    }
+    for (int v = 0; v < n_views; v++) {
+        const cgs_metric_view& d = views[v];
+        if (!d.image || !d.gt) {
+            set_error("cgs_view_metrics: invalid argument (view %d: NULL pointer)", v);
+            return CGS_ERR_INVALID_ARGUMENT;
+        }
+        if (d.channels <= 0 || d.height <= 0 || d.width <= 0 || d.x0 < 0 || d.x0 >= d.width) {
+            set_error("cgs_view_metrics: invalid argument (view %d: channels=%d, height=%d, width=%d, x0=%d)", v,
+                      d.channels, d.height, d.width, d.x0);
+            return CGS_ERR_INVALID_ARGUMENT;
+        }
+    }
+    if (launch_view_metrics((hipStream_t)stream_, n_views, views, workspace, sums, means) != hipSuccess) {
+        set_error("cgs_view_metrics: descriptor copy failed");
+        return CGS_ERR_HIP;
+    }
+    if (!check_launch("view_metrics", false, (hipStream_t)stream_)) return CGS_ERR_HIP;
+    return CGS_OK;
+}
+
 }  // extern "C"

@@ -156,4 +156,9 @@ void launch_edge_visibility(hipStream_t s, int n_curves, const double* curves, i
                             int n_frames, const double* K, const double* w2c, int height, int width,
                             const unsigned char* maps, int invert, int* counts);
 
+// metrics.hip
+size_t view_metrics_workspace_bytes(int n_views);
+hipError_t launch_view_metrics(hipStream_t s, int n_views, const cgs_metric_view* views_host, void* workspace,
+                               double* sums, double* means);
+
 }  // namespace cgs

@@ -294,6 +294,59 @@ def save_ply(gaussians, path):
     return names
 
 
+_PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2",
+              "uint16": "u2", "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4",
+              "double": "f8", "float64": "f8"}
+
+
+def read_ply_table(path):
+    """The vertex table of a PLY file -> dict name -> [N] array, for the layouts point-cloud tools write: ``ascii``,
+    ``binary_little_endian`` or ``binary_big_endian``, scalar properties of any PLY type (float / double positions,
+    ``uchar`` colours).  Elements written before ``vertex`` must have scalar properties only; those after it are ignored."""
+    with open(path, "rb") as f:
+        blob = f.read()
+    head, body = blob.split(b"end_header", 1)
+    body = body[body.index(b"\n") + 1:]
+    lines = head.decode("ascii").splitlines()
+    if not lines or lines[0].strip() != "ply":
+        raise ValueError(f"{path}: not a PLY file")
+    fmt, elements = None, []
+    for ln in lines[1:]:
+        tok = ln.split()
+        if not tok:
+            continue
+        if tok[0] == "format":
+            fmt = tok[1]
+        elif tok[0] == "element":
+            elements.append((tok[1], int(tok[2]), []))
+        elif tok[0] == "property":
+            if tok[1] == "list":
+                elements[-1][2].append((tok[-1], None))
+            else:
+                elements[-1][2].append((tok[2], _PLY_TYPES[tok[1]]))
+    if fmt not in ("ascii", "binary_little_endian", "binary_big_endian"):
+        raise ValueError(f"{path}: unsupported PLY format {fmt}")
+    offset = 0
+    text_rows = body.decode("ascii").split("\n") if fmt == "ascii" else None
+    for name, count, props in elements:
+        if any(t is None for _, t in props):
+            raise ValueError(f"{path}: list properties in element {name} are not supported")
+        if fmt == "ascii":
+            rows = text_rows[offset:offset + count]
+            offset += count
+            if name == "vertex":
+                table = [r.split() for r in rows]
+                return {p: np.array([float(r[i]) for r in table]).astype(t) for i, (p, t) in enumerate(props)}
+        else:
+            end = "<" if fmt == "binary_little_endian" else ">"
+            dt = np.dtype([(p, end + t) for p, t in props])
+            if name == "vertex":
+                tab = np.frombuffer(body, dtype=dt, count=count, offset=offset)
+                return {p: tab[p].astype(np.dtype(t)) for p, t in props}
+            offset += dt.itemsize * count
+    raise ValueError(f"{path}: no vertex element")
+
+
 def read_ply_vertices(path):
     """Minimal reader of the float32 binary little-endian vertex table save_ply writes -> dict name -> [P] array."""
     with open(path, "rb") as f:

@@ -421,26 +421,47 @@ class GaussianCurveModel:
 
 
 class Scene:
-    """What the reference's ``Scene(args, gaussians)`` (scene/__init__.py:27-92) does for an EMAP scan, minus the file
-    copies: read the cameras (dataset_io.read_emap = readEMAP + loadCam), build the seed cloud of rendemapInfo
-    (dataset_readers.py:404-441: the 15^3 grid when ``init_random_init``) and call ``gaussians.create_from_pcd``."""
+    """What the reference's ``Scene(args, gaussians)`` (scene/__init__.py:27-92) does, minus the file copies and the
+    shuffle.  Dispatch as the reference's (:45-56): a scan with a ``sparse/`` folder is COLMAP (colmap_io.read_colmap =
+    readColmapSceneInfo + loadCam; the model is built from its point cloud); otherwise it is EMAP: read the cameras
+    (dataset_io.read_emap = readEMAP + loadCam), build the seed cloud of rendemapInfo (dataset_readers.py:404-441: the
+    15^3 grid when ``init_random_init``) and call ``gaussians.create_from_pcd``.
+
+    ``eval`` / ``llffhold``: the held-out split.  COLMAP: see read_colmap (the train list keeps every camera).  EMAP:
+    ``eval=True`` makes the test list the same frames again (rendemapInfo :385-399); with ``eval=False`` the test list is
+    empty and the train list is the frames once (the reference's list holds them twice).
+    ``images`` / ``resolution`` (COLMAP only): ``--images`` and ``-r`` of the reference."""
 
     def __init__(self, source_path, gaussians, detector="DexiNed", num_pts_per_axis=15, cameras_extent=None, rng=None,
-                 device=None):
+                 device=None, eval=False, llffhold=8, images=None, resolution=-1):
+        import os
         from . import dataset_io
         self.gaussians = gaussians
-        self.train_cameras = dataset_io.read_emap(source_path, detector=detector)
-        self.point_cloud = dataset_io.grid_point_cloud(num_pts_per_axis, rng)
-        if cameras_extent is None:   # getNerfppNorm (dataset_readers.py:46-67): 1.1 x the largest distance to the mean centre
-            centres = torch.stack([c.camera_center for c in self.train_cameras]).double()
-            cameras_extent = float((centres - centres.mean(0)).norm(dim=1).max() * 1.1)
+        if os.path.exists(os.path.join(source_path, "sparse")):
+            from . import colmap_io
+            self.train_cameras, self.test_cameras, self.point_cloud, extent = colmap_io.read_colmap(
+                source_path, images=images, eval=eval, llffhold=llffhold, detector=detector, resolution=resolution)
+            if cameras_extent is None:
+                cameras_extent = extent
+        else:
+            self.train_cameras = dataset_io.read_emap(source_path, detector=detector)
+            self.test_cameras = list(self.train_cameras) if eval else []
+            self.point_cloud = dataset_io.grid_point_cloud(num_pts_per_axis, rng)
+            if cameras_extent is None:   # getNerfppNorm (dataset_readers.py:46-67): 1.1 x the largest distance to the mean centre
+                centres = torch.stack([c.camera_center for c in self.train_cameras]).double()
+                cameras_extent = float((centres - centres.mean(0)).norm(dim=1).max() * 1.1)
         self.cameras_extent = cameras_extent
         if device is not None:
-            self.train_cameras = [c.to(device) for c in self.train_cameras]
+            moved = {id(c): c.to(device) for c in self.train_cameras + self.test_cameras}
+            self.train_cameras = [moved[id(c)] for c in self.train_cameras]
+            self.test_cameras = [moved[id(c)] for c in self.test_cameras]
         gaussians.create_from_pcd(self.point_cloud, self.train_cameras, self.cameras_extent)
 
     def getTrainCameras(self, scale=1.0):
         return self.train_cameras
+
+    def getTestCameras(self, scale=1.0):
+        return self.test_cameras
 
 
 def _install_topology():

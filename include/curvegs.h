@@ -526,6 +526,30 @@ void cgs_prof_reset(void);
 /* Fills up to `cap` entries; returns the number of distinct kernels seen.  names[i] points to static storage. */
 int cgs_prof_collect(const char** names, double* total_ms, int64_t* launches, int cap);
 
+/* ------------------------------------------------------------------------------------------------
+ * Held-out image metrics (training_report, reference train.py:321-376): for each of n_views views, in one launch,
+ *   sums[v] = (sum |d|, sum d^2) in float64 over c < channels, y < height, x0 <= x < width,
+ *   d = clamp(image[y,x], 0, 1) - clamp(gt[c,y,x], 0, 1) computed in float32 (NaN propagates as in torch.clamp),
+ * and, when `means` is not NULL, means[v] = sums[v] / (channels * height * (width - x0)).  `image` is [1,height,width]
+ * (broadcast over the gt's channels), `gt` [channels,height,width], both contiguous float32; views may differ in size.
+ * Deterministic: fixed slices per view, partial sums added in index order by the view's last workgroup; the bits of view
+ * v depend only on view v.  No host synchronisation: the descriptor table travels with one stream-ordered copy into
+ * `workspace` (cgs_view_metrics_workspace_bytes(n_views) bytes of device memory; no initialisation needed).
+ * n_views = 0 is a no-op; n_views < 0 or > 65535, NULL pointers, channels / height / width <= 0 and x0 outside
+ * [0, width) are CGS_ERR_INVALID_ARGUMENT, rejected before anything is launched.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct cgs_metric_view {
+    const float* image; /* [1,height,width] */
+    const float* gt;    /* [channels,height,width] */
+    int channels;
+    int height;
+    int width;
+    int x0;             /* first column (train_test_exp: width / 2) */
+} cgs_metric_view;
+size_t cgs_view_metrics_workspace_bytes(int n_views);
+int cgs_view_metrics(int n_views, const cgs_metric_view* views /*host, [n_views]*/, void* workspace,
+                     double* sums /*[n_views,2]*/, double* means /*[n_views,2] or NULL*/, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
