@@ -85,6 +85,7 @@ SIGNATURES = {
     "cgs_edge_visibility": (_i, [_i, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _vp, _i, _vp, _vp]),
     "cgs_view_metrics_workspace_bytes": (C.c_size_t, [_i]),
     "cgs_view_metrics": (_i, [_i, _vp, _vp, _vp, _vp, _vp]),
+    "cgs_densification_stats": (_i, [_i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "cgs_sample_curves_forward": (_i, [_i, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp]),
     "cgs_sample_curves_backward": (_i, [_i, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "cgs_splat_attrs_forward": (_i, [_i, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

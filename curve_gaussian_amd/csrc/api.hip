@@ -1396,6 +1396,23 @@ int cgs_edge_visibility(int n_curves, const double* curves, int n_lines, const d
     return CGS_OK;
 }
 
+int cgs_densification_stats(int64_t P, const int* radii, const float* dL_dmeans2D, int64_t grad_stride, float* max_radii2D,
+                            float* xyz_gradient_accum, float* denom, const uint32_t* skip_flag, void* stream_) {
+    if (P < 0 || grad_stride < 2) {
+        set_error("cgs_densification_stats: invalid argument (P=%lld, grad_stride=%lld)", (long long)P, (long long)grad_stride);
+        return CGS_ERR_INVALID_ARGUMENT;
+    }
+    if (P == 0) return CGS_OK;
+    if (!radii || !dL_dmeans2D || !max_radii2D || !xyz_gradient_accum || !denom) {
+        set_error("cgs_densification_stats: invalid argument (NULL pointer)");
+        return CGS_ERR_INVALID_ARGUMENT;
+    }
+    launch_densification_stats((hipStream_t)stream_, (long long)P, radii, dL_dmeans2D, (long long)grad_stride, max_radii2D,
+                               xyz_gradient_accum, denom, skip_flag);
+    if (!check_launch("densification_stats", false, (hipStream_t)stream_)) return CGS_ERR_HIP;
+    return CGS_OK;
+}
+
 size_t cgs_view_metrics_workspace_bytes(int n_views) { return view_metrics_workspace_bytes(n_views); }
 
 int cgs_view_metrics(int n_views, const cgs_metric_view* views, void* workspace, double* sums, double* means,

@@ -161,4 +161,8 @@ size_t view_metrics_workspace_bytes(int n_views);
 hipError_t launch_view_metrics(hipStream_t s, int n_views, const cgs_metric_view* views_host, void* workspace,
                                double* sums, double* means);
 
+// densify.hip
+void launch_densification_stats(hipStream_t s, long long P, const int* radii, const float* grad, long long stride,
+                                float* max_radii, float* accum, float* denom, const unsigned int* skip_flag);
+
 }  // namespace cgs

@@ -419,6 +419,40 @@ class GaussianCurveModel:
                                                              keepdim=True)
         self.denom[update_filter] += 1
 
+    def densification_buffers(self):
+        """(max_radii2D [P], xyz_gradient_accum [P,1], denom [P,1]), zero-filled at n_splats where missing or stale (a
+        topology edit that did not resize them), as add_densification_stats allocates them."""
+        dev, P = self._curve_points.device, self.n_splats
+        if getattr(self, "max_radii2D", None) is None or self.max_radii2D.shape[0] != P:
+            self.max_radii2D = torch.zeros(P, device=dev)
+        if getattr(self, "xyz_gradient_accum", None) is None or self.xyz_gradient_accum.shape[0] != P:
+            self.xyz_gradient_accum = torch.zeros((P, 1), device=dev)
+            self.denom = torch.zeros((P, 1), device=dev)
+        return self.max_radii2D, self.xyz_gradient_accum, self.denom
+
+    def accumulate_densification_stats(self, radii, dL_dmeans2D, skip_flag=None):
+        """train.py:184-187 in one launch on the current stream (csrc/densify.hip): for the splats with radii > 0,
+        max_radii2D = max(max_radii2D, radii), xyz_gradient_accum += |dL_dmeans2D[:, :2]|, denom += 1 -- no visible-index
+        list, so no device-to-host sync.  dL_dmeans2D: [P, >=2] float32 (the `viewspace_points` gradient; its rows may be
+        wider than 2).  skip_flag: optional device uint32 scalar, non-zero writes nothing (a replay that overflowed)."""
+        import ctypes as C
+        from .. import _lib as L
+        mr, acc, den = self.densification_buffers()
+        P = mr.shape[0]
+        if radii.shape[0] != P or dL_dmeans2D.shape[0] != P:
+            raise ValueError(f"accumulate_densification_stats: radii {tuple(radii.shape)} / dL_dmeans2D "
+                             f"{tuple(dL_dmeans2D.shape)} do not cover the model's {P} splats")
+        for name, t, dt in (("radii", radii, torch.int32), ("dL_dmeans2D", dL_dmeans2D, torch.float32)):
+            L.require_gpu_tensor(t, name)
+            if t.dtype != dt or not t.is_contiguous():
+                raise ValueError(f"accumulate_densification_stats: {name} must be a contiguous {dt} tensor")
+        stride = dL_dmeans2D.shape[1] if dL_dmeans2D.dim() == 2 else 0
+        lib = L.load()
+        with L.device_guard(mr.device):
+            rc = lib.cgs_densification_stats(P, L.ptr(radii), L.ptr(dL_dmeans2D), stride, L.ptr(mr), L.ptr(acc), L.ptr(den),
+                                             L.ptr(skip_flag) if skip_flag is not None else None, L.raw_stream(mr.device))
+        L.check(rc, "cgs_densification_stats")
+
 
 class Scene:
     """What the reference's ``Scene(args, gaussians)`` (scene/__init__.py:27-92) does, minus the file copies and the

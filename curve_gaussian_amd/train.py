@@ -1,0 +1,326 @@
+"""The reference's training driver (train.py:38-248, ``__main__`` :378-416) on this package's parts: scan -> trained curves ->
+``parametric_edges.json``.
+
+    python -m curve_gaussian_amd.train -s SCAN -m OUT [--iterations N] [--backend graphed|direct|autograd|torch]
+
+The loop keeps the reference's order.  Per iteration: learning rate, SH degree every 1000 iterations, a random view without
+replacement, render + losses + every regulariser + backward (one ``TrainStep`` call), densification statistics before
+``densify_until_iter``, the held-out report, the topology edits, the snapshot, the optimizer step, the checkpoint.
+
+The topology edits run between the backward and the optimizer step (:183-236), so those iterations are run with
+``step(update=False)`` and finished with ``apply_update()``; they are known in advance from the iteration number.  So are
+the report and snapshot iterations, which read the model before its update (:176-229).  Every other iteration runs
+straight through, and with ``backend="graphed"`` it is one graph replay.  An edit that replaced a curve parameter leaves
+that group without gradient, and torch.optim.Adam then skips it; the flat one-launch Adam skips the whole step then
+(``TrainStep.apply_update``).
+
+Out of scope: tensorboard, draw_curve / draw_ellipsoids, the network GUI, view-parallel runs, sparse_adam."""
+import argparse
+import os
+import sys
+
+import torch
+
+
+class ModelParams:
+    """The fields of the reference's ModelParams (arguments/__init__.py:47-66) this driver reads."""
+
+    def __init__(self, source_path="", model_path="", sh_degree=0, n_gaussians=12, detector="DexiNed", resolution=-1,
+                 white_background=False, eval=False):
+        self.source_path, self.model_path = source_path, model_path
+        self.sh_degree, self.n_gaussians, self.detector = sh_degree, n_gaussians, detector
+        self.resolution, self.white_background, self.eval = resolution, white_background, eval
+
+
+class OptimizationParams:
+    """arguments/__init__.py:77-124, the reference's defaults."""
+
+    def __init__(self, **overrides):
+        self.iterations = 10_000
+        self.position_lr_delay_mult = 0.01
+        self.position_lr_max_steps = 30_000
+        self.lr_curve_points_init = 0.0005
+        self.lr_curve_points_final = 0.000005
+        self.feature_lr = 0.0025
+        self.opacity_lr = 0.025
+        self.scaling_lr = 0.005
+        self.rotation_lr = 0.001
+        self.mask_lr = 0.01
+        self.exposure_lr_init = 0.01
+        self.exposure_lr_final = 0.001
+        self.exposure_lr_delay_steps = 0
+        self.exposure_lr_delay_mult = 0.0
+        self.percent_dense = 0.01
+        self.lambda_dssim = 0.1
+        self.opacity_cull = 0.01
+        self.opacity_cull_second = 0.05
+        self.opacity_loss_weight = 0.01
+        self.lambda_mse = 10.
+        self.lambda_curve_smo = 0.1
+        self.lambda_points_conn = 0.1
+        self.lambda_width = 0.01
+        self.lambda_mask = 0.0005
+        self.mask_threshold = 0.01
+        self.merge_endpoints_flag = True
+        self.visible_checking = False
+        self.densification_interval = 2000
+        self.opacity_reset_interval = 3000
+        self.prune_interval = 1500
+        self.densify_from_iter = 500
+        self.densify_until_iter = 7000
+        self.conn_from_iter = 7000
+        self.densify_grad_threshold = 2000
+        self.random_background = False
+        self.optimizer_type = "default"
+        self.threshold_line = 0.0015
+        self.threshold_max_line = 0.005
+        self.threshold_angle = 20
+        self.threshold_angle_skip = 30
+        self.distance_threshold = 0.02
+        self.similarity_threshold = 0.97
+        self._variant()
+        for k, v in overrides.items():
+            if not hasattr(self, k):
+                raise TypeError(f"OptimizationParams: unknown option {k!r}")
+            setattr(self, k, v)
+
+    def _variant(self):
+        pass
+
+
+class OptimizationParamsPidinet(OptimizationParams):
+    """arguments/__init__.py:127-135"""
+
+    def _variant(self):
+        self.lambda_mse = 2.0
+        self.lambda_width = 0.0
+        self.threshold_line = 0.002
+        self.threshold_max_line = 0.006
+        self.distance_threshold = 0.03
+        self.similarity_threshold = 0.95
+
+
+class OptimizationParamsReplica(OptimizationParams):
+    """arguments/__init__.py:138-147"""
+
+    def _variant(self):
+        self.opacity_cull = 0.05
+        self.lambda_mse = 1.0
+        self.lambda_width = 0.0
+        self.threshold_line = 0.0002
+        self.threshold_max_line = 0.001
+        self.similarity_threshold = 0.95
+
+
+BACKENDS = ("graphed", "direct", "autograd", "torch")
+
+
+def edit_iteration(it, opt):
+    """True on the iterations where train.py:189-211 edits the topology (after the backward, before the optimizer step)."""
+    return ((it < opt.densify_until_iter and it > opt.densify_from_iter and it % opt.densification_interval == 0)
+            or it == opt.densify_until_iter
+            or (it % 1000 == 500 and it > opt.densify_until_iter)                      # :202
+            or (it % 1000 == 0 and it > 3000 and it != opt.iterations)                 # :206
+            or (it % 1000 == 0 and it > opt.densify_until_iter) or it == opt.iterations)   # :209
+
+
+def make_scene(dataset, opt, device):
+    """train.py:45-48: the model, the scan, the optimizer groups."""
+    from .scene import GaussianCurveModel, Scene
+    gaussians = GaussianCurveModel(dataset.sh_degree, dataset.n_gaussians, opt.optimizer_type, device=device)
+    scene = Scene(dataset.source_path, gaussians, detector=dataset.detector, eval=dataset.eval,
+                  resolution=dataset.resolution, device=device)
+    scene.model_path = dataset.model_path
+    gaussians.training_setup(opt)
+    return scene, gaussians
+
+
+def make_step(backend, gaussians, cameras, opt, seed=0):
+    """The per-iteration object of `backend` with train.py's loss weights, every regulariser and the statistics on."""
+    from .train_step import GraphedTrainStep, TrainStep
+    if backend not in BACKENDS:
+        raise ValueError(f"training: unknown backend {backend!r} (one of {BACKENDS})")
+    gts = [c.original_image[:1].contiguous() for c in cameras]
+    kw = dict(lambda_mse=opt.lambda_mse, lambda_dssim=opt.lambda_dssim, lambda_mask=opt.lambda_mask,
+              densify_until_iter=opt.densify_until_iter, mask_threshold=opt.mask_threshold, seed=seed, regularisers=True,
+              opacity_loss_weight=opt.opacity_loss_weight, lambda_curve_smo=opt.lambda_curve_smo,
+              lambda_width=opt.lambda_width, lambda_points_conn=opt.lambda_points_conn, conn_from_iter=opt.conn_from_iter,
+              densification_stats=True)
+    if backend == "graphed":
+        return GraphedTrainStep(gaussians, cameras, gts, **kw)
+    return TrainStep(gaussians, cameras, gts, fused=backend != "torch", direct=backend == "direct", **kw)
+
+
+def _report(iteration, testing_iterations, scene, bg):
+    from . import evaluation as E
+    from .gaussian_renderer import PipelineParams, render
+    return E.training_report(None, iteration, None, None, None, 0.0, testing_iterations, scene, render,
+                             (PipelineParams(), bg), False)
+
+
+def _save_ply(gaussians, model_path, iteration):
+    """scene/__init__.py:94-96 (Scene.save)."""
+    from .scene.dataset_io import save_ply
+    save_ply(gaussians, os.path.join(model_path, "point_cloud", f"iteration_{iteration}", "point_cloud.ply"))
+
+
+def _export(gaussians, dataset, opt):
+    """train.py:250-293 (extract_curves)."""
+    from .scene.dataset_io import write_parametric_edges
+    return write_parametric_edges(gaussians, dataset.model_path, merge_endpoints=opt.merge_endpoints_flag,
+                                  distance_threshold=0.015, visible_checking=opt.visible_checking,   # :264
+                                  scan_dir=dataset.source_path, detector=dataset.detector)
+
+
+def training(dataset, opt, testing_iterations, saving_iterations, checkpoint_iterations, checkpoint=None, backend="graphed",
+             seed=0, device="cuda", quiet=False, scene=None, step=None, report=None, save_ply=None, save_checkpoint=None,
+             export=None):
+    """train.py:38-248.  Returns {"events": [(iteration, event, n_curves_after)] for every edit, report, save, checkpoint and
+    the export, "losses": {iteration: loss} (the first iteration and every iteration run with a deferred update),
+    "first_iter", "scene", "gaussians"}.
+
+    Collaborators (defaults in brackets), injectable so that the loop itself can be run by a CPU test: ``scene`` = (scene,
+    gaussians) [make_scene], ``step`` = the per-iteration object [make_step(backend, ...)], ``report(iteration,
+    testing_iterations, scene, bg)`` [evaluation.training_report], ``save_ply(gaussians, model_path, iteration)``,
+    ``save_checkpoint(obj, path)`` [torch.save], ``export(gaussians, dataset, opt)`` [write_parametric_edges]."""
+    say = (lambda *a: None) if quiet else print
+    os.makedirs(dataset.model_path, exist_ok=True)
+    scene, gaussians = scene if scene is not None else make_scene(dataset, opt, device)
+    first_iter = 0
+    if checkpoint:                                                                  # :49-51
+        model_params, first_iter = torch.load(checkpoint, weights_only=False)
+        gaussians.restore(model_params, opt)
+    step = step if step is not None else make_step(backend, gaussians, scene.getTrainCameras(), opt, seed)
+    step.start_at(first_iter)
+    bg = torch.tensor([1, 1, 1] if dataset.white_background else [0, 0, 0], dtype=torch.float32,
+                      device=gaussians._curve_points.device)                        # :53-54
+    step.bg = bg
+    report = report or _report
+    save_ply = save_ply or _save_ply
+    save_checkpoint = save_checkpoint or torch.save
+    export = export or _export
+    events, losses = [], {}
+    finish = getattr(step, "finish", lambda: None)
+    n_curves = lambda: int(gaussians._curve_points.shape[0])
+
+    def log(it, name):
+        events.append((it, name, n_curves()))
+
+    for iteration in range(first_iter + 1, opt.iterations + 1):
+        if iteration % 1000 == 0:                                                   # :81-82
+            gaussians.oneupSHdegree()
+        deferred = (edit_iteration(iteration, opt) or iteration in testing_iterations or iteration in saving_iterations
+                    or iteration == opt.iterations)
+        loss, pkg = step.step(update=not deferred)
+        if iteration == first_iter + 1 or deferred:
+            losses[iteration] = float(loss)
+        if not deferred:
+            if iteration in checkpoint_iterations:
+                finish()
+                save_checkpoint((gaussians.capture(), iteration), os.path.join(dataset.model_path, f"chkpnt{iteration}.pth"))
+                log(iteration, "checkpoint")
+            continue
+        if iteration in testing_iterations:                                         # :176-179
+            report(iteration, testing_iterations, scene, bg)
+            log(iteration, "report")
+        if iteration < opt.densify_until_iter:                                      # :182-191 (statistics: in the step)
+            if iteration > opt.densify_from_iter and iteration % opt.densification_interval == 0:
+                size_threshold = 20 if iteration > opt.opacity_reset_interval else None   # :190
+                gaussians.densify_and_prune(opt.densify_grad_threshold, opt.opacity_cull, scene.cameras_extent,
+                                            size_threshold, pkg["radii"])
+                log(iteration, "densify_and_prune")
+        if iteration == opt.densify_until_iter:                                     # :195-199
+            gaussians.prune_curves((gaussians.get_curve_opacity <= opt.opacity_cull_second).squeeze())
+            log(iteration, "prune_curves")
+            gaussians.fix_opacity()
+            log(iteration, "fix_opacity")
+        if iteration % 1000 == 500 and iteration > opt.densify_until_iter:          # :202-204
+            gaussians.only_prune(opt.opacity_cull, opt.mask_threshold)
+            log(iteration, "only_prune")
+            gaussians.mask_trim_split(opt.mask_threshold)
+            log(iteration, "mask_trim_split")
+        if iteration % 1000 == 0 and iteration > 3000 and iteration != opt.iterations:   # :206-207
+            gaussians.curve_split_curvature(opt.threshold_angle, opt.threshold_angle_skip)
+            log(iteration, "curve_split_curvature")
+        if (iteration % 1000 == 0 and iteration > opt.densify_until_iter) or iteration == opt.iterations:   # :209-211
+            gaussians.fit_curve_to_line(opt.threshold_line, opt.threshold_max_line)
+            log(iteration, "fit_curve_to_line")
+            gaussians.merge_curves(opt.distance_threshold, opt.similarity_threshold)
+            log(iteration, "merge_curves")
+        if iteration in saving_iterations:                                          # :213-229
+            say(f"\n[ITER {iteration}] Saving Gaussians")
+            save_ply(gaussians, dataset.model_path, iteration)
+            log(iteration, "save")
+        if iteration < opt.iterations:                                              # :227-236
+            step.apply_update()
+        else:
+            step.drop_update()
+        if iteration in checkpoint_iterations:                                      # :238-240
+            say(f"\n[ITER {iteration}] Saving Checkpoint")
+            finish()
+            save_checkpoint((gaussians.capture(), iteration), os.path.join(dataset.model_path, f"chkpnt{iteration}.pth"))
+            log(iteration, "checkpoint")
+    finish()
+    export(gaussians, dataset, opt)                                                 # :248
+    log(opt.iterations, "export")
+    return {"events": events, "losses": losses, "first_iter": first_iter, "scene": scene, "gaussians": gaussians}
+
+
+def select_options(source_path, detector):
+    """train.py:396-402: 'ABC' scans with the Pidinet detector and 'Replica' scans take their option variants.  (The
+    reference tests the ModelParams object's class default, never 'Pidinet', and builds the variant after parsing, so its
+    own run keeps the base values; here the variant's values are the defaults of the parsed options -- DESIGN section 6.)"""
+    cls = OptimizationParams
+    if "ABC" in source_path and detector == "Pidinet":
+        cls = OptimizationParamsPidinet
+    if "Replica" in source_path:
+        cls = OptimizationParamsReplica
+    return cls
+
+
+def build_parser():
+    p = argparse.ArgumentParser(description="Training script parameters")
+    p.add_argument("--source_path", "-s", default="")
+    p.add_argument("--model_path", "-m", default="")
+    p.add_argument("--sh_degree", type=int, default=0)
+    p.add_argument("--n_gaussians", type=int, default=12)
+    p.add_argument("--detector", default="DexiNed")
+    p.add_argument("--resolution", "-r", type=int, default=-1)
+    p.add_argument("--white_background", "-w", action="store_true")
+    p.add_argument("--eval", action="store_true")
+    p.add_argument("--iterations", type=int, default=None)
+    p.add_argument("--test_iterations", nargs="+", type=int, default=[3_000, 10_000])        # :386-391
+    p.add_argument("--save_iterations", nargs="+", type=int, default=[3_000, 10_000])
+    p.add_argument("--quiet", action="store_true")
+    p.add_argument("--checkpoint_iterations", nargs="+", type=int, default=[10000])
+    p.add_argument("--start_checkpoint", type=str, default=None)
+    p.add_argument("--backend", choices=BACKENDS, default="graphed")
+    p.add_argument("--seed", type=int, default=0)
+    return p
+
+
+def parse_args(argv):
+    """(ModelParams, OptimizationParams, args) of a command line, as :378-404 derives them."""
+    args = build_parser().parse_args(argv)
+    source_path = os.path.abspath(args.source_path)                                 # ModelParams.extract (:63-66)
+    opt = select_options(source_path, args.detector)()
+    if args.iterations is not None:
+        opt.iterations = args.iterations
+    args.save_iterations.append(opt.iterations)                                     # :404
+    dataset = ModelParams(source_path, args.model_path, args.sh_degree, args.n_gaussians, args.detector, args.resolution,
+                          args.white_background, args.eval)
+    return dataset, opt, args
+
+
+def main(argv=None):
+    dataset, opt, args = parse_args(sys.argv[1:] if argv is None else argv)
+    if not dataset.model_path:
+        raise SystemExit("train: -m / --model_path is required")
+    print("Optimizing " + dataset.model_path)
+    training(dataset, opt, args.test_iterations, args.save_iterations, args.checkpoint_iterations, args.start_checkpoint,
+             backend=args.backend, seed=args.seed, quiet=args.quiet)
+    print("\nTraining complete.")
+
+
+if __name__ == "__main__":
+    main()

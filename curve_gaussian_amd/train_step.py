@@ -21,8 +21,13 @@ class TrainStep:
     def __init__(self, gaussians, cameras, gt_images, lambda_mse=10.0, lambda_dssim=0.1, lambda_mask=0.0005,
                  densify_until_iter=7000, mask_threshold=0.01, seed=0, rank=0, world=1, fused=True,
                  regularisers=False, opacity_loss_weight=0.01, lambda_curve_smo=0.1, lambda_width=0.01,
-                 lambda_points_conn=0.1, conn_from_iter=7000, direct=False):
+                 lambda_points_conn=0.1, conn_from_iter=7000, direct=False, densification_stats=False):
         self.g = gaussians
+        # densification_stats=True: every iteration before densify_until_iter adds the view's statistics (train.py:184-187:
+        # max_radii2D, xyz_gradient_accum, denom) after the backward, in one launch without a host sync
+        # (GaussianCurveModel.accumulate_densification_stats, csrc/densify.hip)
+        self.densification_stats = bool(densification_stats)
+        self._deferred = None      # step(update=False): the parameters of the iteration whose update is pending
         # direct=True (fused only, compiled host shim): the iteration without autograd -- the checked view forward, the
         # photometric loss kernels, the view backward (adding into the flat gradient buffer), Adam and prepare_scaling_rot
         # called one after the other.  Same kernels and numbers as the autograd form; a third of its host time.  Unlike
@@ -111,8 +116,30 @@ class TrainStep:
                 mine = v
         return mine
 
-    def step(self, view_index=None):
+    def start_at(self, iteration):
+        """Continue a resumed run: the next step() is iteration + 1 (train.py:49-51, 73)."""
+        self.iteration = int(iteration)
+
+    def _stats_active(self, iteration):
+        """train.py:184: the statistics are gathered while `iteration < opt.densify_until_iter`."""
+        return self.densification_stats and iteration < self.densify_until_iter
+
+    def _params(self):
         g = self.g
+        return {"curve_points": g._curve_points, "width": g._width, "opacity": g._opacity, "mask": g._mask,
+                "f_dc": g._features_dc, "f_rest": g._features_rest}
+
+    def step(self, view_index=None, update=True):
+        """One iteration.  update=False stops after the backward and the densification statistics: the gradients wait in
+        the gradient buffer until ``apply_update()`` (or ``drop_update()``) -- train.py runs its topology edits between
+        ``loss.backward()`` and ``optimizer.step()`` (:183-236)."""
+        return self._eager_step(view_index, update, self._eager_direct and self.fused)
+
+    def _eager_step(self, view_index, update, direct):
+        g = self.g
+        if self._deferred is not None:
+            raise RuntimeError("TrainStep.step: the update of the previous step(update=False) is still pending "
+                               "(call apply_update() or drop_update())")
         self.iteration += 1
         self.reset_timestep += 1                   # train.py:76
         it = self.iteration
@@ -120,8 +147,8 @@ class TrainStep:
         vi = self._next_view() if view_index is None else view_index
         cam, gt = self.cams[vi], self.gts[vi]
         use_mask = it >= self.densify_until_iter
-        if self._eager_direct and self.fused:
-            return self._step_direct(cam, gt, use_mask)
+        if direct:
+            return self._step_direct(cam, gt, use_mask, update)
         pkg = render(cam, g, self.pipe, self.bg, use_mask=use_mask, mask_thr=self.mask_threshold,
                      compute_visibility=not self.fused, clamp=not self.fused, compute_rend_dir=not self.fused,
                      grad_sinks=self.fused)   # (fused: the backward kernels add into the flat gradient buffer themselves)
@@ -138,17 +165,78 @@ class TrainStep:
             loss = loss + self._regulariser_terms(pkg["radii"], 1.0 if self.reset_timestep > 0 else 0.0,
                                                   with_conn=self._conn_active(self.iteration))
         loss.backward(gradient=unit_grad(loss.device) if self.fused else None)
+        if self._stats_active(it):                 # train.py:184-187
+            g.accumulate_densification_stats(pkg["radii"], pkg["viewspace_points"].grad)
         self.flat.all_reduce()
+        self._finish(update)
+        return loss.detach(), pkg
+
+    def _finish(self, update):
+        if update:
+            self._optimizer_step()
+        else:
+            self._deferred = self._params()
+
+    def _optimizer_step(self):
+        g = self.g
         if self.fused:
             g.optimizer.step(zero_grad=True)       # Adam + zero_grad in one launch
         else:
             g.optimizer.step()
             self.flat.zero_()                      # grads are views of the flat buffer: keep them, zero in place
         g.prepare_scaling_rot()                    # train.py:242-243
-        return loss.detach(), pkg
+
+    def replaced_groups(self):
+        """Names of the parameter groups whose tensor was replaced since the pending step(update=False) (topology edits)."""
+        if self._deferred is None:
+            return []
+        now = self._params()
+        return [n for n, p in self._deferred.items() if now[n] is not p]
+
+    def apply_update(self):
+        """The optimizer step of the pending step(update=False), as train.py:226-236 takes it after the topology edits.
+        An edit that replaced a group's nn.Parameter left it with grad = None, and torch.optim.Adam skips such a group
+        (moments and step count included).  fused=False steps torch.optim.Adam with grad None on the replaced groups.  The
+        flat one-launch Adam keeps one step count for all groups: when any group was replaced the whole step is skipped and
+        the gradients dropped.  Both are exact when every group was replaced (prune_curves replaces all six); scene/topology.py
+        installs new parameter objects for all six groups on every edit, so an edit of one group (fit_curve_to_line alone)
+        skips the whole step on both.  Returns True when the step was applied."""
+        if self._deferred is None:
+            raise RuntimeError("TrainStep.apply_update: no step(update=False) is pending")
+        replaced = self.replaced_groups()
+        if self.fused:
+            if replaced:
+                self.drop_update()
+                return False
+            self._deferred = None
+            self._optimizer_step()
+            return True
+        g = self.g
+        stale = [p for n, p in self._params().items() if n in replaced]
+        kept = [p.grad for p in stale]
+        for p in stale:
+            p.grad = None
+        self._deferred = None
+        try:
+            g.optimizer.step()
+        finally:
+            for p, gr in zip(stale, kept):
+                p.grad = gr
+        self.flat.zero_()
+        g.prepare_scaling_rot()
+        return True
+
+    def drop_update(self):
+        """Discard the pending step(update=False): gradients cleared, parameters, moments and step count unchanged
+        (train.py:227 takes no optimizer step on the last iteration)."""
+        if self._deferred is None:
+            raise RuntimeError("TrainStep.drop_update: no step(update=False) is pending")
+        self._deferred = None
+        self.flat.zero_()
+        self.g.prepare_scaling_rot()
 
 
-    def _step_direct(self, cam, gt, use_mask):
+    def _step_direct(self, cam, gt, use_mask, update=True):
         """TrainStep.step() from the render on, without autograd (TrainStep(direct=True)): train.py:95-107, :110-146, :235,
         :242-243 as eight library calls.  The forward is the checked one (exact binning: a bucket overflow re-renders with the
         raised capacity before anything reached the gradient buffer)."""
@@ -235,9 +323,10 @@ class TrainStep:
                 sg = torch.sigmoid(mask)
                 loss = loss + self.lambda_mask * sg.mean()
                 sinks[3].add_(sg * (1 - sg), alpha=self.lambda_mask / mask.numel())
+            if self._stats_active(self.iteration):   # train.py:184-187 (the checked forward resolved any overflow)
+                g.accumulate_densification_stats(radii, g_m2d)
         self.flat.all_reduce()
-        g.optimizer.step(zero_grad=True)
-        g.prepare_scaling_rot()
+        self._finish(update)
         pkg = {"render": color, "viewspace_points": _GradHolder(g_m2d), "visibility_filter": None, "radii": radii, "depth": invd,
                "rend_dir": None, "rend_alpha": amap[3:4]}
         return loss, pkg
@@ -336,6 +425,8 @@ class GraphedTrainStep(TrainStep):
         self._status = None
         self._use_mask = False
         self._use_conn = False      # graph constant like _use_mask: the switch at conn_from_iter re-captures
+        self._use_stats = False     # likewise: the statistics stop at densify_until_iter
+        self._stats_ptrs = None     # the statistics buffers the graph writes (restore() replaces them: re-capture)
         self._flag_host = torch.zeros(64, dtype=torch.int32).pin_memory()
         # single-GPU replays: the captured Adam kernel reports "this iteration was skipped" straight into that pinned ring
         # (entry = its own execution count, kept in device memory, modulo 64) -- no device-to-host copy queued between one
@@ -365,6 +456,8 @@ class GraphedTrainStep(TrainStep):
             loss = loss + self._regulariser_terms(pkg["radii"], self._opa_gate, with_conn=self._use_conn)
         loss.backward(gradient=unit_grad(loss.device))
         status = sink[0]
+        if self._use_stats:     # gated like the Adam below: an overflowed replay adds nothing, its eager redo does
+            g.accumulate_densification_stats(pkg["radii"], pkg["viewspace_points"].grad, skip_flag=status[2:3])
         g.optimizer.step_dev(zero_grad=True, skip_flag=status[2:3], report=self._report())
         return loss.detach(), status
 
@@ -490,6 +583,8 @@ class GraphedTrainStep(TrainStep):
             loss = loss + self.lambda_mask * sg.mean()
             grads.view("mask").add_(sg * (1 - sg), alpha=self.lambda_mask / mask.numel())
         status = b["status"]
+        if self._use_stats:     # gated like the Adam below: an overflowed replay adds nothing, its eager redo does
+            g.accumulate_densification_stats(b["radii"], b["g_m2d"], skip_flag=status[2:3])
         if self._capture_coll:
             import torch.distributed as dist
             dist.all_reduce(g.optimizer.grads.flat)
@@ -545,6 +640,8 @@ class GraphedTrainStep(TrainStep):
             loss = loss + self.lambda_mask * sg.mean()
             grads.view("mask").add_(sg * (1 - sg), alpha=self.lambda_mask / mask.numel())
         status = b["status"]
+        if self._use_stats:     # gated like the Adam below: an overflowed replay adds nothing, its eager redo does
+            g.accumulate_densification_stats(b["radii"], b["g_m2d"], skip_flag=status[2:3])
         if self._capture_coll:
             import torch.distributed as dist
             dist.all_reduce(g.optimizer.grads.flat)
@@ -615,6 +712,8 @@ class GraphedTrainStep(TrainStep):
             self._bind_inputs()
         # warm-up replicas of the body must not change the model: snapshot, run on a side stream, restore
         snap = (opt.flat.clone(), opt.exp_avg.clone(), opt.exp_avg_sq.clone(), opt.step_count)
+        stats = self.g.densification_buffers() if self._use_stats else ()
+        stats_snap = [t.clone() for t in stats]
         # The gradient accumulators of the parameters live as long as an autograd graph references them, and they keep
         # the stream they were created on.  Eager steps create them on the default stream, and a captured backward
         # that has to synchronise with the default stream cannot be captured: drop the old graph (the derived splat
@@ -637,6 +736,9 @@ class GraphedTrainStep(TrainStep):
             self._loss, self._status = self._body()
         opt.flat.copy_(snap[0]); opt.exp_avg.copy_(snap[1]); opt.exp_avg_sq.copy_(snap[2])
         opt.step_count = snap[3]
+        for t, v in zip(stats, stats_snap):
+            t.copy_(v)
+        self._stats_ptrs = tuple(t.data_ptr() for t in stats) or None
         opt.grads.zero_()
         self.g.prepare_scaling_rot()
         self._report_seq.fill_(self._report_next)   # (the warm-up executions of the body counted too)
@@ -675,13 +777,32 @@ class GraphedTrainStep(TrainStep):
             self._bufs = None
         return len(redo)
 
-    def step(self, view_index=None):
+    def _stats_moved(self):
+        """The statistics buffers are not the ones the graph was captured with (restore(), or any other replacement)."""
+        if not self._use_stats or self._graph is None:
+            return False
         g = self.g
+        return tuple(t.data_ptr() for t in (g.max_radii2D, g.xyz_gradient_accum, g.denom)) != self._stats_ptrs
+
+    def step(self, view_index=None, update=True):
+        """One replayed iteration.  update=False (iterations with topology edits, train.py:183-236) drains the replays in
+        flight and runs the iteration eagerly -- the direct body for the direct graph -- up to and including the backward
+        and the statistics; ``apply_update()`` / ``drop_update()`` then decide the optimizer step."""
+        g = self.g
+        if not update:
+            from . import _lib as L
+            self.finish()
+            return self._eager_step(view_index, False, self.direct and L.use_shim())
+        if self._deferred is not None:
+            raise RuntimeError("GraphedTrainStep.step: the update of the previous step(update=False) is still pending "
+                               "(call apply_update() or drop_update())")
         use_mask = self.iteration + 1 >= self.densify_until_iter
         use_conn = self._conn_active(self.iteration + 1)
-        if use_mask != self._use_mask or use_conn != self._use_conn:   # a phase of train.py starts: re-capture
+        use_stats = self._stats_active(self.iteration + 1)
+        if (use_mask != self._use_mask or use_conn != self._use_conn or use_stats != self._use_stats
+                or self._stats_moved()):   # a phase of train.py starts (or the captured buffers moved): re-capture
             self.finish()
-            self._use_mask, self._use_conn = use_mask, use_conn
+            self._use_mask, self._use_conn, self._use_stats = use_mask, use_conn, use_stats
             self._graph = None
         self._check_overflow()
         self.iteration += 1
@@ -718,6 +839,15 @@ class GraphedTrainStep(TrainStep):
         self._bufs = None
         self._loss = self._status = None
         self._derived_stale = False
+
+    def start_at(self, iteration):
+        self.finish()
+        TrainStep.start_at(self, iteration)
+        self._t0 = self.g.optimizer.step_count - self.iteration
+
+    def drop_update(self):
+        TrainStep.drop_update(self)
+        self._t0 -= 1           # no Adam step for this iteration: step number = _t0 + iteration stays true
 
     def _refresh_derived(self):
         if getattr(self, "_derived_stale", False):

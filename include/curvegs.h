@@ -550,6 +550,23 @@ size_t cgs_view_metrics_workspace_bytes(int n_views);
 int cgs_view_metrics(int n_views, const cgs_metric_view* views /*host, [n_views]*/, void* workspace,
                      double* sums /*[n_views,2]*/, double* means /*[n_views,2] or NULL*/, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Densification statistics (reference train.py:184-187, GaussianModel.add_densification_stats): for every splat i < P
+ * with radii[i] > 0, in one launch,
+ *   max_radii2D[i] = max(max_radii2D[i], (float)radii[i]);
+ *   xyz_gradient_accum[i] += sqrt(gx*gx + gy*gy);   gx, gy = dL_dmeans2D[i * grad_stride + 0 / 1]
+ *   denom[i] += 1;
+ * splats with radii[i] <= 0 are not touched.  The reference indexes with the list of visible splats (a device-to-host
+ * sync); here every splat is decided on the device.  One thread per splat, no atomics: deterministic, bit for bit.
+ * skip_flag != NULL and *skip_flag != 0 (the convention of cgs_adam_step_flat_dev: status word [2] of a replayed
+ * forward that overflowed its buckets) writes nothing.  max_radii2D [P], xyz_gradient_accum [P,1], denom [P,1] float32.
+ * P = 0 is a no-op; P < 0, grad_stride < 2 and NULL pointers with P > 0 are CGS_ERR_INVALID_ARGUMENT, rejected before
+ * anything is launched.
+ * ------------------------------------------------------------------------------------------------ */
+int cgs_densification_stats(int64_t P, const int* radii /*[P]*/, const float* dL_dmeans2D /*[P,grad_stride]*/,
+                            int64_t grad_stride, float* max_radii2D /*[P]*/, float* xyz_gradient_accum /*[P]*/,
+                            float* denom /*[P]*/, const uint32_t* skip_flag /*device, may be NULL*/, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
