@@ -8,6 +8,7 @@ import torch
 
 from .. import _lib as L
 
+EDGE_THRESHOLD = 0.1   # loss_utils.py:100-103: gt pixels above it are edge pixels
 
 _UNIT = {}
 
@@ -55,7 +56,7 @@ class _EdgeAwareLoss(torch.autograd.Function):
         return grad * g, None, None
 
 
-def edge_aware_loss(image, gt_image, threshold=0.1):
+def edge_aware_loss(image, gt_image, threshold=EDGE_THRESHOLD):
     """image, gt_image: [C,H,W] (the reference passes the 1-channel render and gt[:1])."""
     return _EdgeAwareLoss.apply(image, gt_image, threshold)
 
@@ -80,16 +81,51 @@ class _EdgeCountCache:
         return hit[0]
 
 
+_photo_workspaces = {}
+
+
+def photometric_workspace(dev, H, W, stream):
+    """The zero-initialised workspace of cgs_photometric_loss for (device, H, W, stream), cached.  Bounded: every hipGraph
+    capture runs on a fresh stream and would otherwise pin one workspace (3 maps) per capture forever.  Dropping an entry
+    is safe: a captured graph keeps using the block inside its own memory pool, eager callers simply allocate a new one."""
+    key = (str(dev), H, W, stream)
+    ws = _photo_workspaces.get(key)
+    if ws is None:
+        while len(_photo_workspaces) >= 6:
+            _photo_workspaces.pop(next(iter(_photo_workspaces)))
+        ws = _photo_workspaces[key] = torch.zeros(int(L.load().cgs_photometric_workspace_bytes(H, W)), dtype=torch.uint8,
+                                                  device=dev)
+    return ws
+
+
+def photometric_weights(lambda_mse, lambda_dssim):
+    """(a, b) of cgs_photometric_loss: loss = a * edge_aware_loss + b * (1 - ssim) (train.py:107)."""
+    return lambda_mse * (1.0 - lambda_dssim), lambda_mse * lambda_dssim
+
+
+def launch_photometric_loss(H, W, image, gt, n_pos, a, b, clamp, ws, grad, loss, stream, view_idx=None,
+                            threshold=EDGE_THRESHOLD):
+    """cgs_photometric_loss on `stream` into the caller's `grad` [1,H,W] and `loss` (0-dim); allocates nothing.
+    view_idx (device int32 scalar): cgs_photometric_loss_indexed instead -- `gt` is a [V,H,W] stack, `n_pos` the [V] table
+    of edge-pixel counts, and the kernels pick the view on the device."""
+    lib, p, cf = L.load(), L.ptr, C.c_float
+    if view_idx is None:
+        rc = lib.cgs_photometric_loss(H, W, p(image), p(gt), cf(threshold), p(n_pos), cf(a), cf(b), 1 if clamp else 0, p(ws),
+                                      p(grad), p(loss), stream)
+    else:
+        rc = lib.cgs_photometric_loss_indexed(H, W, p(image), p(gt), p(view_idx), cf(threshold), p(n_pos), cf(a), cf(b),
+                                              1 if clamp else 0, p(ws), p(grad), p(loss), stream)
+    L.check(rc, "cgs_photometric_loss" if view_idx is None else "cgs_photometric_loss_indexed")
+
+
 class _PhotometricLoss(torch.autograd.Function):
     """loss = lambda_mse * ((1 - lambda_dssim) * edge_aware_loss(x, gt) + lambda_dssim * (1 - fused_ssim(x, gt))),
     x = clamp(image, 0, 1) if clamp else image (train.py:101-107 + render()'s clamp), value and d loss / d image from
     cgs_photometric_loss: three kernels instead of ~30 elementwise / reduction launches and their autograd graph."""
-    _workspaces = {}
 
     @staticmethod
     def forward(ctx, image, gt_image, lambda_mse, lambda_dssim, threshold, clamp, n_pos):
         L.require_gpu_tensor(image, "image")
-        lib = L.load()
         dev = image.device
         with L.device_guard(dev):
             img = image.detach().float().contiguous()
@@ -100,23 +136,11 @@ class _PhotometricLoss(torch.autograd.Function):
             stream = L.raw_stream(dev)
             if n_pos is None:
                 n_pos = _EdgeCountCache.get(gt, threshold, stream)
-            key = (str(dev), H, W, stream)
-            ws = _PhotometricLoss._workspaces.get(key)
-            if ws is None:
-                # bounded: every hipGraph capture runs on a fresh stream and would otherwise pin one workspace (3 maps)
-                # per capture forever.  Dropping an entry is safe: a captured graph keeps using the block inside its
-                # own memory pool, eager callers simply allocate a new one.
-                while len(_PhotometricLoss._workspaces) >= 6:
-                    _PhotometricLoss._workspaces.pop(next(iter(_PhotometricLoss._workspaces)))
-                ws = _PhotometricLoss._workspaces[key] = torch.zeros(
-                    int(lib.cgs_photometric_workspace_bytes(H, W)), dtype=torch.uint8, device=dev)
+            ws = photometric_workspace(dev, H, W, stream)
             grad = torch.empty_like(img)
             loss = torch.empty((), dtype=torch.float32, device=dev)
-            a = lambda_mse * (1.0 - lambda_dssim)
-            b = lambda_mse * lambda_dssim
-            rc = lib.cgs_photometric_loss(H, W, L.ptr(img), L.ptr(gt), C.c_float(threshold), L.ptr(n_pos), C.c_float(a),
-                                          C.c_float(b), 1 if clamp else 0, L.ptr(ws), L.ptr(grad), L.ptr(loss), stream)
-            L.check(rc, "cgs_photometric_loss")
+            a, b = photometric_weights(lambda_mse, lambda_dssim)
+            launch_photometric_loss(H, W, img, gt, n_pos, a, b, clamp, ws, grad, loss, stream, threshold=threshold)
         ctx.save_for_backward(grad)
         return loss
 
@@ -126,14 +150,14 @@ class _PhotometricLoss(torch.autograd.Function):
         return scale_by_upstream(grad, g), None, None, None, None, None, None
 
 
-def edge_pixel_count(gt_image, threshold=0.1):
+def edge_pixel_count(gt_image, threshold=EDGE_THRESHOLD):
     """Device int32 scalar #{mean_c gt > threshold} (loss_utils.py:100-103), cached per gt tensor."""
     gt = gt_image.detach().float().contiguous()
     with L.device_guard(gt.device):
         return _EdgeCountCache.get(gt, threshold, L.raw_stream(gt.device))
 
 
-def photometric_loss(image, gt_image, lambda_mse=10.0, lambda_dssim=0.1, threshold=0.1, clamp=False, n_pos=None):
+def photometric_loss(image, gt_image, lambda_mse=10.0, lambda_dssim=0.1, threshold=EDGE_THRESHOLD, clamp=False, n_pos=None):
     """image, gt_image: [1,H,W].  Same value/gradient as composing (clamp,) edge_aware_loss and fused_ssim (tested).
     clamp=True takes the UNclamped rasterizer output and applies render()'s clamp(0,1) inside the kernels.
     n_pos: optional device int32 scalar from ``edge_pixel_count`` (graph-captured steps feed it through a static buffer)."""
@@ -141,7 +165,6 @@ def photometric_loss(image, gt_image, lambda_mse=10.0, lambda_dssim=0.1, thresho
         # the C++ autograd node of the compiled shim (csrc/torch_shim.cpp::PhotometricLossFn): same kernels, no Python frame in
         # the backward.  float32 only: the node hands on a float32 gradient, a half-precision render goes through
         # _PhotometricLoss, whose gradient autograd casts to the input's dtype.
-        lib = L.load()
         dev = image.device
         with L.device_guard(dev):
             gt = gt_image.detach().float().contiguous()
@@ -149,13 +172,7 @@ def photometric_loss(image, gt_image, lambda_mse=10.0, lambda_dssim=0.1, thresho
             stream = L.raw_stream(dev)
             if n_pos is None:
                 n_pos = _EdgeCountCache.get(gt, threshold, stream)
-            key = (str(dev), H, W, stream)
-            ws = _PhotometricLoss._workspaces.get(key)
-            if ws is None:
-                while len(_PhotometricLoss._workspaces) >= 6:
-                    _PhotometricLoss._workspaces.pop(next(iter(_PhotometricLoss._workspaces)))
-                ws = _PhotometricLoss._workspaces[key] = torch.zeros(int(lib.cgs_photometric_workspace_bytes(H, W)),
-                                                                      dtype=torch.uint8, device=dev)
-            return L.shim().photometric_loss(image, gt, n_pos, ws, float(threshold), lambda_mse * (1.0 - lambda_dssim),
-                                             lambda_mse * lambda_dssim, bool(clamp), unit_grad(dev))
+            ws = photometric_workspace(dev, H, W, stream)
+            a, b = photometric_weights(lambda_mse, lambda_dssim)
+            return L.shim().photometric_loss(image, gt, n_pos, ws, float(threshold), a, b, bool(clamp), unit_grad(dev))
     return _PhotometricLoss.apply(image, gt_image, lambda_mse, lambda_dssim, threshold, clamp, n_pos)

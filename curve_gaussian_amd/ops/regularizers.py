@@ -18,6 +18,9 @@ fused ops replace them in the training step."""
 import torch
 import torch.nn.functional as F
 
+WIDTH_THRESHOLD = 0.005       # train.py:126-131: the width term counts curves at or above it
+CONNECTION_DISTANCE = 0.05    # train.py:133-146: end points closer than this are pulled together
+
 
 def mask_loss(gaussians, lambda_mask=0.0005):
     return lambda_mask * torch.mean(torch.sigmoid(gaussians._mask))
@@ -39,7 +42,7 @@ def curve_smoothness_loss(gaussians, radii, weight=0.1):
     return weight * cos_sim.mean() * any_visible
 
 
-def width_loss(gaussians, weight=0.01, width_thr=0.005):
+def width_loss(gaussians, weight=0.01, width_thr=WIDTH_THRESHOLD):
     """train.py:126-131: mean excess over the curves at or above the threshold, 0 if there is none."""
     w = gaussians.get_curve_width
     sel = (w >= width_thr).to(w.dtype)
@@ -52,45 +55,58 @@ import ctypes as _C
 from .. import _lib as _L
 
 
+_reg_workspaces = {}
+
+
+def regularizer_workspace(dev, stream):
+    """The zero-initialised workspace of cgs_curve_regularizers for (device, stream), cached (the kernels leave it zeroed
+    again for the next launch on the same stream)."""
+    key = (str(dev), stream)
+    ws = _reg_workspaces.get(key)
+    if ws is None:
+        while len(_reg_workspaces) >= 8:
+            _reg_workspaces.pop(next(iter(_reg_workspaces)))
+        ws = _reg_workspaces[key] = torch.zeros(int(_L.load().cgs_curve_regularizers_workspace_bytes()), dtype=torch.uint8,
+                                                device=dev)
+    return ws
+
+
+def launch_curve_regularizers(m, rotation, opacity_logit, width_log, radii, w_opacity, opacity_gate, w_smooth, w_width, ws,
+                              loss, g_rot, g_op, g_w, stream, width_thr=WIDTH_THRESHOLD):
+    """cgs_curve_regularizers on `stream` into the caller's loss (0-dim) and gradients (shaped like rotation [P,4],
+    opacity_logit and width_log [B,1]); allocates nothing.  opacity_gate: a float (folded into the weight) or a float32
+    device scalar the kernels read."""
+    gate = opacity_gate if torch.is_tensor(opacity_gate) else None
+    w_op = float(w_opacity) if gate is not None else float(w_opacity) * float(opacity_gate)
+    p, cf = _L.ptr, _C.c_float
+    rc = _L.load().cgs_curve_regularizers(rotation.shape[0] // m, int(m), p(rotation), p(opacity_logit), p(width_log), p(radii),
+                                          cf(w_op), p(gate), cf(w_smooth), cf(w_width), cf(width_thr), p(ws), p(loss), p(g_rot),
+                                          p(g_op), p(g_w), stream)
+    _L.check(rc, "cgs_curve_regularizers")
+
+
 class _CurveRegularizers(torch.autograd.Function):
     """opacity + smoothness + width terms above from cgs_curve_regularizers: value and gradients in three launches
     (the torch-op versions cost ~60 launches and 0.8 ms at P = 200 k)."""
-    _workspaces = {}
 
     @staticmethod
     def forward(ctx, rotation_raw, opacity_logit, width_log, radii, m, w_opacity, opacity_gate, w_smooth, w_width, width_thr):
         _L.require_gpu_tensor(rotation_raw, "rotation")
-        lib = _L.load()
         dev = rotation_raw.device
         rot = rotation_raw.detach().float().contiguous()
         op = opacity_logit.detach().float().contiguous()
         wl = width_log.detach().float().contiguous()
         rad = radii.detach().to(torch.int32).contiguous()
-        P = rot.shape[0]
-        B = P // m
         stream = _L.raw_stream(dev)
-        key = (str(dev), stream)
-        ws = _CurveRegularizers._workspaces.get(key)
-        if ws is None:
-            while len(_CurveRegularizers._workspaces) >= 8:
-                _CurveRegularizers._workspaces.pop(next(iter(_CurveRegularizers._workspaces)))
-            ws = _CurveRegularizers._workspaces[key] = torch.zeros(
-                int(lib.cgs_curve_regularizers_workspace_bytes()), dtype=torch.uint8, device=dev)
+        ws = regularizer_workspace(dev, stream)
         loss = torch.empty((), dtype=torch.float32, device=dev)
         g_rot = torch.empty_like(rot)
         g_op = torch.empty_like(op)
         g_w = torch.empty_like(wl)
-        gate = None
         if torch.is_tensor(opacity_gate):
-            gate = opacity_gate.detach().float().contiguous()
-            w_op = float(w_opacity)
-        else:
-            w_op = float(w_opacity) * float(opacity_gate)
-        rc = lib.cgs_curve_regularizers(B, int(m), _L.ptr(rot), _L.ptr(op), _L.ptr(wl), _L.ptr(rad), _C.c_float(w_op),
-                                        _L.ptr(gate) if gate is not None else None, _C.c_float(w_smooth),
-                                        _C.c_float(w_width), _C.c_float(width_thr), _L.ptr(ws), _L.ptr(loss),
-                                        _L.ptr(g_rot), _L.ptr(g_op), _L.ptr(g_w), stream)
-        _L.check(rc, "cgs_curve_regularizers")
+            opacity_gate = opacity_gate.detach().float().contiguous()
+        launch_curve_regularizers(m, rot, op, wl, rad, w_opacity, opacity_gate, w_smooth, w_width, ws, loss, g_rot, g_op, g_w,
+                                  stream, width_thr)
         ctx.save_for_backward(g_rot, g_op, g_w)
         ctx.shapes = (rotation_raw.shape, opacity_logit.shape, width_log.shape)
         return loss
@@ -104,7 +120,8 @@ class _CurveRegularizers(torch.autograd.Function):
                 None, None)
 
 
-def curve_regularizers(gaussians, radii, w_opacity=0.01, opacity_gate=1.0, w_smooth=0.1, w_width=0.01, width_thr=0.005):
+def curve_regularizers(gaussians, radii, w_opacity=0.01, opacity_gate=1.0, w_smooth=0.1, w_width=0.01,
+                       width_thr=WIDTH_THRESHOLD):
     """opacity_loss * gate + curve_smoothness_loss + width_loss (the three functions above), fused.
     opacity_gate: float or 0-dim device tensor (train.py:114's ``reset_timestep > 0``; the counter is incremented at the
     top of every iteration, train.py:76, so the gate is 1 from the first iteration on)."""
@@ -112,7 +129,7 @@ def curve_regularizers(gaussians, radii, w_opacity=0.01, opacity_gate=1.0, w_smo
                                     w_opacity, opacity_gate, w_smooth, w_width, width_thr)
 
 
-def connection_loss_reference(gaussians, weight=0.1, dis_thr=0.05):
+def connection_loss_reference(gaussians, weight=0.1, dis_thr=CONNECTION_DISTANCE):
     """train.py:133-146 as written (torch.cdist over all 2B end points; exact differences instead of the matmul
     expansion cdist may pick for large inputs).  O(B^2) memory: the test reference of ``connection_loss``."""
     curve_points = gaussians.get_curve_points
@@ -128,6 +145,15 @@ def connection_loss_reference(gaussians, weight=0.1, dis_thr=0.05):
     return dist.sum() * 0.0
 
 
+def launch_connection_loss(curve_points, weight, ws, loss, grad, accumulate, stream, dis_thr=CONNECTION_DISTANCE):
+    """cgs_endpoint_connection_loss on `stream` into the caller's loss (0-dim) and gradient [B,K,3] (added to it when
+    `accumulate`); allocates nothing.  ws: cgs_endpoint_connection_workspace_bytes(B) bytes, initialised by the launch."""
+    p, cf = _L.ptr, _C.c_float
+    rc = _L.load().cgs_endpoint_connection_loss(curve_points.shape[0], p(curve_points), cf(dis_thr), cf(weight), p(ws), p(loss),
+                                                p(grad), 1 if accumulate else 0, stream)
+    _L.check(rc, "cgs_endpoint_connection_loss")
+
+
 class _ConnectionLoss(torch.autograd.Function):
     """cgs_endpoint_connection_loss: value and gradient in one sweep, O(B) memory."""
 
@@ -137,14 +163,11 @@ class _ConnectionLoss(torch.autograd.Function):
         lib = _L.load()
         dev = curve_points.device
         cp = curve_points.detach().float().contiguous()
-        B = cp.shape[0]
         with _L.device_guard(dev):
-            ws = torch.empty(int(lib.cgs_endpoint_connection_workspace_bytes(B)), dtype=torch.uint8, device=dev)
+            ws = torch.empty(int(lib.cgs_endpoint_connection_workspace_bytes(cp.shape[0])), dtype=torch.uint8, device=dev)
             loss = torch.empty((), dtype=torch.float32, device=dev)
             grad = torch.empty_like(cp)
-            rc = lib.cgs_endpoint_connection_loss(B, _L.ptr(cp), _C.c_float(dis_thr), _C.c_float(weight), _L.ptr(ws),
-                                                  _L.ptr(loss), _L.ptr(grad), 0, _L.raw_stream(dev))
-            _L.check(rc, "cgs_endpoint_connection_loss")
+            launch_connection_loss(cp, weight, ws, loss, grad, False, _L.raw_stream(dev), dis_thr)
         ctx.save_for_backward(grad)
         ctx.shape = curve_points.shape
         return loss
@@ -156,6 +179,6 @@ class _ConnectionLoss(torch.autograd.Function):
         return sc(grad, g).view(ctx.shape), None, None
 
 
-def connection_loss(gaussians, weight=0.1, dis_thr=0.05):
+def connection_loss(gaussians, weight=0.1, dis_thr=CONNECTION_DISTANCE):
     """lambda_points_conn * mean distance between end points of different curves closer than `dis_thr` (train.py:133-146)."""
     return _ConnectionLoss.apply(gaussians._curve_points, float(weight), float(dis_thr))

@@ -5,14 +5,20 @@
 
 Only the photometric terms and (from ``densify_until_iter``) the mask regulariser are included; the O(B^2) connection
 loss and the topology edits are out of scope."""
+import ctypes as C
+import math
 import os
 import random
 
 import torch
 
+from . import _lib as L
 from .fused_ssim import fused_ssim
-from .gaussian_renderer import PipelineParams, render
-from .ops.losses import edge_aware_loss, photometric_loss, unit_grad
+from .gaussian_renderer import PipelineParams, _fused_route_ok, render
+from .ops import regularizers as RG, view_render as VR
+from .ops.curve_sampling import _bezier_mask, sample_coefficients
+from .ops.losses import (edge_aware_loss, edge_pixel_count, launch_photometric_loss, photometric_loss, photometric_weights,
+                         photometric_workspace, unit_grad)
 from .ops.optim import FlatAdam
 from .view_parallel import FlatGrads, StaticCamera as _StaticCamera, no_gc
 
@@ -33,7 +39,6 @@ class TrainStep:
         # called one after the other.  Same kernels and numbers as the autograd form; a third of its host time.  Unlike
         # GraphedTrainStep nothing is captured: cameras may differ in size and field of view, binning stays exact.
         self._eager_direct = bool(direct)
-        self._direct_ws = {}
         self.cams = cameras
         self.gts = gt_images                      # list of [1,H,W] edge maps on the device
         self.lambda_mse, self.lambda_dssim, self.lambda_mask = lambda_mse, lambda_dssim, lambda_mask
@@ -53,8 +58,7 @@ class TrainStep:
         self.rank, self.world = rank, world
         if gaussians.optimizer is None:
             gaussians.training_setup()
-        named = {"curve_points": gaussians._curve_points, "width": gaussians._width, "opacity": gaussians._opacity,
-                 "mask": gaussians._mask, "f_dc": gaussians._features_dc, "f_rest": gaussians._features_rest}
+        named = self._params()
         self.flat = FlatGrads(named)
         self.fused = fused
         if fused:   # one-launch Adam with the reference's per-group learning rates (training_setup :203-213)
@@ -75,13 +79,10 @@ class TrainStep:
 
     def _on_topology_change(self):
         """The per-curve tensors were resized (scene/topology.py): rebind the flat gradient buffer."""
-        g = self.g
-        named = {"curve_points": g._curve_points, "width": g._width, "opacity": g._opacity, "mask": g._mask,
-                 "f_dc": g._features_dc, "f_rest": g._features_rest}
         if self.fused:
-            self.flat = g.optimizer.grads          # FlatAdam.rebuild made new flat buffers and views
+            self.flat = self.g.optimizer.grads     # FlatAdam.rebuild made new flat buffers and views
         else:
-            self.flat = FlatGrads(named)
+            self.flat = FlatGrads(self._params())
 
     def _conn_active(self, iteration):
         """train.py:133: `opt.lambda_points_conn > 0 and iteration > opt.conn_from_iter`."""
@@ -89,7 +90,6 @@ class TrainStep:
 
     def _regulariser_terms(self, radii, opacity_gate, with_conn=False):
         """train.py:113-146; opacity_gate (float or device scalar) switches the opacity term (reset_timestep > 0)."""
-        from .ops import regularizers as RG
         g = self.g
         if self.fused:   # one HIP op (three launches)
             reg = RG.curve_regularizers(g, radii, self.opacity_loss_weight, opacity_gate, self.lambda_curve_smo,
@@ -147,29 +147,76 @@ class TrainStep:
         vi = self._next_view() if view_index is None else view_index
         cam, gt = self.cams[vi], self.gts[vi]
         use_mask = it >= self.densify_until_iter
+        gate = 1.0 if self.reset_timestep > 0 else 0.0
         if direct:
-            return self._step_direct(cam, gt, use_mask, update)
-        pkg = render(cam, g, self.pipe, self.bg, use_mask=use_mask, mask_thr=self.mask_threshold,
-                     compute_visibility=not self.fused, clamp=not self.fused, compute_rend_dir=not self.fused,
-                     grad_sinks=self.fused)   # (fused: the backward kernels add into the flat gradient buffer themselves)
-        image = pkg["render"]
-        if self.fused:   # raw composite in, render()'s clamp applied inside the loss kernels
-            loss = photometric_loss(image, gt[:1], self.lambda_mse, self.lambda_dssim, clamp=True)
+            loss, pkg = self._step_direct(cam, gt, gate, use_mask, self._conn_active(it), self._stats_active(it))
         else:
-            Ll1 = edge_aware_loss(image, gt[:1])
-            ssim_value = fused_ssim(image.unsqueeze(0), gt[:1].unsqueeze(0))
-            loss = self.lambda_mse * ((1.0 - self.lambda_dssim) * Ll1 + self.lambda_dssim * (1.0 - ssim_value))
-        if use_mask:
-            loss = loss + self.lambda_mask * torch.mean(torch.sigmoid(g._mask))
-        if self.regularisers:
-            loss = loss + self._regulariser_terms(pkg["radii"], 1.0 if self.reset_timestep > 0 else 0.0,
-                                                  with_conn=self._conn_active(self.iteration))
-        loss.backward(gradient=unit_grad(loss.device) if self.fused else None)
-        if self._stats_active(it):                 # train.py:184-187
-            g.accumulate_densification_stats(pkg["radii"], pkg["viewspace_points"].grad)
+            pkg = render(cam, g, self.pipe, self.bg, use_mask=use_mask, mask_thr=self.mask_threshold,
+                         compute_visibility=not self.fused, clamp=not self.fused, compute_rend_dir=not self.fused,
+                         grad_sinks=self.fused)   # (fused: the backward kernels add into the flat gradient buffer themselves)
+            loss = self._autograd_loss(pkg, gt[:1], None, gate, use_mask, self._conn_active(it), self._stats_active(it))
         self.flat.all_reduce()
         self._finish(update)
-        return loss.detach(), pkg
+        return loss, pkg
+
+    def _autograd_loss(self, pkg, gt, n_pos, gate, use_mask, use_conn, use_stats, skip_flag=None):
+        """train.py:98-146 and :184-187 through autograd: the photometric loss of pkg["render"] against gt (n_pos: its
+        edge-pixel count as a device scalar, or None), the mask term, the regularisers (gate: the opacity term's switch,
+        float or device scalar), the backward and the densification statistics (skip_flag as in
+        accumulate_densification_stats).  Returns the detached loss."""
+        g = self.g
+        image = pkg["render"]
+        if self.fused:   # raw composite in, render()'s clamp applied inside the loss kernels
+            loss = photometric_loss(image, gt, self.lambda_mse, self.lambda_dssim, clamp=True, n_pos=n_pos)
+        else:
+            Ll1 = edge_aware_loss(image, gt)
+            ssim_value = fused_ssim(image.unsqueeze(0), gt.unsqueeze(0))
+            loss = self.lambda_mse * ((1.0 - self.lambda_dssim) * Ll1 + self.lambda_dssim * (1.0 - ssim_value))
+        if use_mask:            # train.py:110-111
+            loss = loss + self.lambda_mask * torch.mean(torch.sigmoid(g._mask))
+        if self.regularisers:
+            loss = loss + self._regulariser_terms(pkg["radii"], gate, with_conn=use_conn)
+        loss.backward(gradient=unit_grad(loss.device) if self.fused else None)
+        if use_stats:           # train.py:184-187
+            g.accumulate_densification_stats(pkg["radii"], pkg["viewspace_points"].grad, skip_flag=skip_flag)
+        return loss.detach()
+
+    def _direct_regularisers(self, loss, rotation, radii, gate, b):
+        """train.py:113-131 without autograd, from forward quantities only: launched before the view backward, which takes the
+        returned dL/drotation_raw (None without regularisers).  b: the buffers reg_ws, reg_loss, r_rot, r_op, r_w."""
+        if not self.regularisers:
+            return loss, None
+        g = self.g
+        RG.launch_curve_regularizers(g.n_gaussians, rotation, g._opacity.detach(), g._width.detach(), radii,
+                                     self.opacity_loss_weight, gate, self.lambda_curve_smo, self.lambda_width, b["reg_ws"],
+                                     b["reg_loss"], b["r_rot"], b["r_op"], b["r_w"], L.raw_stream(g._curve_points.device))
+        return loss + b["reg_loss"], b["r_rot"]
+
+    def _direct_tail(self, loss, radii, g_m2d, grads, b, use_mask, use_conn, use_stats, skip_flag=None):
+        """The iteration without autograd after the view backward wrote the flat gradient buffer `grads`: the regularisers'
+        per-curve gradients, the connection loss (train.py:133-146), the mask term (:110-111) and the densification
+        statistics (:184-187; skip_flag as in accumulate_densification_stats).  Returns the loss."""
+        g = self.g
+        if self.regularisers:
+            grads.view("opacity").add_(b["r_op"])
+            grads.view("width").add_(b["r_w"])
+            if use_conn:        # adds to the curve-point gradient the backward wrote
+                cp = g._curve_points.detach()
+                if "conn_ws" not in b:   # the eager step: sized by the curve count, which topology edits change
+                    b["conn_ws"] = torch.empty(int(L.load().cgs_endpoint_connection_workspace_bytes(cp.shape[0])),
+                                               dtype=torch.uint8, device=cp.device)
+                    b["conn_loss"] = torch.zeros((), dtype=torch.float32, device=cp.device)
+                RG.launch_connection_loss(cp, self.lambda_points_conn, b["conn_ws"], b["conn_loss"], grads.view("curve_points"),
+                                          True, L.raw_stream(cp.device))
+                loss = loss + b["conn_loss"]
+        if use_mask:            # train.py:110-111: lambda_mask * mean(sigmoid(mask)), gradient added by hand
+            mask = g._mask.detach()
+            sg = torch.sigmoid(mask)
+            loss = loss + self.lambda_mask * sg.mean()
+            grads.view("mask").add_(sg * (1 - sg), alpha=self.lambda_mask / mask.numel())
+        if use_stats:
+            g.accumulate_densification_stats(radii, g_m2d, skip_flag=skip_flag)
+        return loss
 
     def _finish(self, update):
         if update:
@@ -236,21 +283,14 @@ class TrainStep:
         self.g.prepare_scaling_rot()
 
 
-    def _step_direct(self, cam, gt, use_mask, update=True):
-        """TrainStep.step() from the render on, without autograd (TrainStep(direct=True)): train.py:95-107, :110-146, :235,
-        :242-243 as eight library calls.  The forward is the checked one (exact binning: a bucket overflow re-renders with the
+    def _step_direct(self, cam, gt, gate, use_mask, use_conn, use_stats):
+        """TrainStep.step() from the render to the statistics, without autograd (TrainStep(direct=True)): train.py:95-146,
+        :184-187 as library calls.  The forward is the checked one (exact binning: a bucket overflow re-renders with the
         raised capacity before anything reached the gradient buffer)."""
-        import ctypes as C
-        import math
-        from . import _lib as L
-        from .ops import view_render as VR
-        from .ops.curve_sampling import _bezier_mask, sample_coefficients
-        from .ops.losses import edge_pixel_count
         g = self.g
         lib = L.load()
         if not L.use_shim():
             raise L.CurveGSError("TrainStep(direct=True) needs the compiled host shim (curve_gaussian_amd/_cgs_torch.so)")
-        from .gaussian_renderer import _fused_route_ok
         if not _fused_route_ok(g, self.pipe, 1.0, None):
             # a parameter tensor was replaced since the last prepare_scaling_rot (reset_opacity, a topology edit made outside
             # the loop): train.py refreshes the derived tensors at the end of every iteration (:242-243), so they are
@@ -266,21 +306,12 @@ class TrainStep:
         tanx, tany = math.tan(cam.FoVx * 0.5), math.tan(cam.FoVy * 0.5)
         isb, coef = _bezier_mask(g.is_bezier, dev), sample_coefficients(m, dev)
         eps = getattr(g, "_derived_eps", 1e-8)
-        p, cf = L.ptr, C.c_float
         gt1 = gt[:1].detach().float().contiguous()
         n_pos = edge_pixel_count(gt1)
+        a, bb = photometric_weights(self.lambda_mse, self.lambda_dssim)
         with L.device_guard(dev):
             st = L.raw_stream(dev)
-            key = (str(dev), H, W, st)
-            ws = self._direct_ws.get(key)
-            if ws is None:
-                if len(self._direct_ws) >= 8:
-                    self._direct_ws.pop(next(iter(self._direct_ws)))
-                ws = self._direct_ws[key] = dict(
-                    photo=torch.zeros(int(lib.cgs_photometric_workspace_bytes(H, W)), dtype=torch.uint8, device=dev),
-                    reg=torch.zeros(int(lib.cgs_curve_regularizers_workspace_bytes()), dtype=torch.uint8, device=dev),
-                    gate={v: torch.full((1,), v, dtype=torch.float32, device=dev) for v in (0.0, 1.0)})
-            a, bb = self.lambda_mse * (1.0 - self.lambda_dssim), self.lambda_mse * self.lambda_dssim
+            ws = photometric_workspace(dev, H, W, st)
             while True:
                 cap = VR._capacity(lib, dev, P, W, H)
                 color, invd, amap, radii, _dir, _raw, saved, handle = L.shim().view_forward(
@@ -291,42 +322,22 @@ class TrainStep:
                 # the forward's 16-byte status readback -- the compositor and the loss are already queued behind it
                 g_img = torch.empty_like(color)
                 loss = torch.empty((), dtype=torch.float32, device=dev)
-                L.check(lib.cgs_photometric_loss(H, W, p(color), p(gt1), cf(0.1), p(n_pos), cf(a), cf(bb), 1, p(ws["photo"]), p(g_img),
-                                                 p(loss), st), "cgs_photometric_loss")
+                launch_photometric_loss(H, W, color, gt1, n_pos, a, bb, True, ws, g_img, loss, st)
                 ok, _nvis = VR.finish(pend)
                 if ok:
                     break
+            b = {}
+            if self.regularisers:
+                f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
+                b = dict(reg_ws=RG.regularizer_workspace(dev, st), reg_loss=f32(()), r_rot=f32(P, 4), r_op=f32(B, 1), r_w=f32(B, 1))
+            rot = g._rotation.detach() if self.regularisers else None   # (derived lazily: read only when needed)
+            loss, r_rot = self._direct_regularisers(loss, rot, radii, gate, b)
             grads = self.flat
             sinks = [grads.view("curve_points"), grads.view("width"), grads.view("opacity")] + ([grads.view("mask")] if use_mask else [])
-            extra = None
-            if self.regularisers:   # (train.py:113-131) forward quantities only: queued before the backward, which takes dL/drotation
-                f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
-                r_rot, r_op, r_w, reg_loss = f32(P, 4), f32(B, 1), f32(B, 1), f32(())
-                gate = ws["gate"][1.0 if self.reset_timestep > 0 else 0.0]
-                L.check(lib.cgs_curve_regularizers(B, m, p(g._rotation.detach()), p(ol), p(wl), p(radii), cf(self.opacity_loss_weight),
-                                                   p(gate), cf(self.lambda_curve_smo), cf(self.lambda_width), cf(0.005), p(ws["reg"]),
-                                                   p(reg_loss), p(r_rot), p(r_op), p(r_w), st), "cgs_curve_regularizers")
-                extra = r_rot
-                loss = loss + reg_loss
-            _n, _n, _n, _n, g_m2d = L.shim().view_backward(*saved[:4], isb, coef, *saved[4:], m, self.mask_threshold, tanx, tany, H, W,
-                                                           eps, g_img, None, sinks, extra)
-            if self.regularisers:
-                sinks[2].add_(r_op)
-                sinks[1].add_(r_w)
-                if self._conn_active(self.iteration):
-                    conn_ws = torch.zeros(int(lib.cgs_endpoint_connection_workspace_bytes(B)), dtype=torch.uint8, device=dev)
-                    conn_loss = torch.zeros((), dtype=torch.float32, device=dev)
-                    L.check(lib.cgs_endpoint_connection_loss(B, p(cp), cf(0.05), cf(self.lambda_points_conn), p(conn_ws), p(conn_loss),
-                                                             p(sinks[0]), 1, st), "cgs_endpoint_connection_loss")
-                    loss = loss + conn_loss
-            if use_mask:            # train.py:110-111: lambda_mask * mean(sigmoid(mask)), gradient added by hand
-                sg = torch.sigmoid(mask)
-                loss = loss + self.lambda_mask * sg.mean()
-                sinks[3].add_(sg * (1 - sg), alpha=self.lambda_mask / mask.numel())
-            if self._stats_active(self.iteration):   # train.py:184-187 (the checked forward resolved any overflow)
-                g.accumulate_densification_stats(radii, g_m2d)
-        self.flat.all_reduce()
-        self._finish(update)
+            g_m2d = L.shim().view_backward(*saved[:4], isb, coef, *saved[4:], m, self.mask_threshold, tanx, tany, H, W, eps, g_img,
+                                           None, sinks, r_rot)[4]
+            # (the checked forward resolved any overflow: the statistics need no skip flag)
+            loss = self._direct_tail(loss, radii, g_m2d, grads, b, use_mask, use_conn, use_stats)
         pkg = {"render": color, "viewspace_points": _GradHolder(g_m2d), "visibility_filter": None, "radii": radii, "depth": invd,
                "rend_dir": None, "rend_alpha": amap[3:4]}
         return loss, pkg
@@ -404,7 +415,6 @@ class GraphedTrainStep(TrainStep):
         # captured kernels read.  The gt edge maps live in one [V,H,W] stack and the direct body picks the step's map
         # on the device (cgs_photometric_loss_indexed): no per-step 4*H*W-byte copy.
         import struct
-        from .ops.losses import edge_pixel_count
         self._cam = _StaticCamera(c0, dev)
         H, W = int(c0.image_height), int(c0.image_width)
         self._gt_stack = torch.stack([g[:1].reshape(H, W).float() for g in self.gts]).contiguous()
@@ -449,26 +459,30 @@ class GraphedTrainStep(TrainStep):
         pkg = render(self._cam, g, self.pipe, self.bg, use_mask=self._use_mask, mask_thr=self.mask_threshold,
                      compute_visibility=False, clamp=False, compute_rend_dir=False,
                      static_bucket_cap=self._cap, status_sink=sink)
-        loss = photometric_loss(pkg["render"], self._gt, self.lambda_mse, self.lambda_dssim, clamp=True, n_pos=self._npos)
-        if self._use_mask:      # train.py:110-111 (a graph constant: the switch at densify_until_iter re-captures)
-            loss = loss + self.lambda_mask * torch.mean(torch.sigmoid(g._mask))
-        if self.regularisers:   # sync-free torch ops; the opacity term is gated by a device scalar refreshed per step
-            loss = loss + self._regulariser_terms(pkg["radii"], self._opa_gate, with_conn=self._use_conn)
-        loss.backward(gradient=unit_grad(loss.device))
         status = sink[0]
-        if self._use_stats:     # gated like the Adam below: an overflowed replay adds nothing, its eager redo does
-            g.accumulate_densification_stats(pkg["radii"], pkg["viewspace_points"].grad, skip_flag=status[2:3])
-        g.optimizer.step_dev(zero_grad=True, skip_flag=status[2:3], report=self._report())
-        return loss.detach(), status
+        # sync-free: the phase switches are graph constants (a switch re-captures), the opacity term is gated by a device
+        # scalar refreshed per step, and the statistics are gated like the Adam step (an overflowed replay adds nothing)
+        loss = self._autograd_loss(pkg, self._gt, self._npos, self._opa_gate, self._use_mask, self._use_conn, self._use_stats,
+                                   skip_flag=status[2:3])
+        self._captured_update(status[2:3])
+        return loss, status
+
+    def _captured_update(self, skip):
+        """The Adam step of the replayed sequence, skipped on the device when `skip` is set (a bucket overflow: the host redoes
+        the iteration eagerly).  View-parallel runs all-reduce the gradients and the flag first: captured here with
+        capture_collectives, otherwise the host does it and the Adam step after the replay (step())."""
+        if self._capture_coll:
+            import torch.distributed as dist
+            dist.all_reduce(self.g.optimizer.grads.flat)
+            dist.all_reduce(skip, op=dist.ReduceOp.MAX)   # any rank overflowed -> every rank skips
+        if not self._collective or self._capture_coll:
+            self.g.optimizer.step_dev(zero_grad=True, skip_flag=skip, report=self._report())
 
     # -- the same sequence without autograd: every kernel of the iteration called through the C ABI on preallocated
     # buffers, gradients written straight into the flat gradient buffer.  Inside a graph the autograd bookkeeping
     # costs nothing on the host, but it does cost GPU launches (gradient accumulation adds, ones/zeros fills,
     # grad * 1 multiplies: ~10 of 41 launches, ~45 us at cfg3).
     def _alloc_direct(self):
-        import ctypes as C
-        from . import _lib as L
-        from .ops.curve_sampling import sample_coefficients, _bezier_mask
         lib = L.load()
         g = self.g
         dev = g.device
@@ -512,144 +526,74 @@ class GraphedTrainStep(TrainStep):
         return b
 
     def _body_direct(self):
-        import ctypes as C
-        import math
-        from . import _lib as L
         lib = L.load()
         g = self.g
         b = self._bufs if self._bufs is not None else self._alloc_direct()
         B, P, m, H, W = b["B"], b["P"], b["m"], b["H"], b["W"]
-        p, cf, s = L.ptr, C.c_float, L.raw_stream(g.device)
+        p, cf, s, chk = L.ptr, C.c_float, L.raw_stream(g.device), L.check
         grads = g.optimizer.grads                       # FlatGrads: .view(name) are the parameters' .grad
         cp, wl, ol = g._curve_points.detach(), g._width.detach(), g._opacity.detach()
         mask = g._mask.detach() if self._use_mask else None
         cam = self._cam
         tanx, tany = math.tan(cam.FoVx * 0.5), math.tan(cam.FoVy * 0.5)
-        chk = L.check
-        if self.fused_view:
-            return self._body_direct_fused(lib, b, cam, cp, wl, ol, mask, grads, tanx, tany, s)
+        aux = self.aux_outputs or not self.fused_view
         # ---- forward: curves -> splats -> per-view attributes -> rasterizer (sync-free) -> loss
-        chk(lib.cgs_sample_curves_forward(B, m, p(cp), p(wl), p(b["isb"]), p(b["coef"]), cf(1e-8), p(b["norms"]),
-                                          p(b["xyz"]), p(b["rot"]), p(b["scl"]), s), "sample_curves_forward")
-        chk(lib.cgs_splat_attrs_forward(B, m, p(b["rot"]), p(b["xyz"]), p(ol), p(mask), cf(self.mask_threshold),
-                                        p(b["scl"]), p(cam.camera_center), p(cam.world_view_transform), p(b["rot_n"]),
-                                        p(b["opac"]), p(b["scl_m"]) if mask is not None else None, p(b["amap"]), s),
-            "splat_attrs_forward")
-        scales = b["scl_m"] if mask is not None else b["scl"]
-        chk(lib.cgs_rasterize_forward_static(
-            p(b["geom"]), p(b["bin"]), b["nbin"], p(b["img"]), self._cap, P, 0, 0, p(b["bg"]), W, H, p(b["xyz"]), None,
-            p(b["colors"]), p(b["opac"]), p(scales), 1.0, p(b["rot_n"]), None, p(b["amap"]),
-            p(cam.world_view_transform), p(cam.full_proj_transform), p(cam.camera_center), tanx, tany, p(b["color"]),
-            p(b["invd"]), p(b["omap"]), 0, 1, p(b["radii"]), s), "rasterize_forward_static")
-        a = self.lambda_mse * (1.0 - self.lambda_dssim)
-        bb = self.lambda_mse * self.lambda_dssim
-        chk(lib.cgs_photometric_loss_indexed(H, W, p(b["color"]), p(self._gt_stack), p(self._view_idx), cf(0.1),
-                                             p(self._npos_table), cf(a), cf(bb), 1, p(b["photo_ws"]), p(b["g_img"]),
-                                             p(b["loss"]), s), "photometric_loss_indexed")
+        if self.fused_view:     # the fused per-view entry points: 8 launches for render + its backward instead of 13
+            chk(lib.cgs_view_forward(
+                B, m, p(cp), p(wl), p(b["isb"]), p(b["coef"]), cf(1e-8), p(b["norms"]), p(ol), p(mask), cf(self.mask_threshold),
+                None, p(b["geom"]), p(b["bin"]), b["nbin"], p(b["img"]), self._cap, p(b["bg"]), W, H,
+                p(cam.world_view_transform), p(cam.full_proj_transform), p(cam.camera_center), tanx, tany, p(b["color"]),
+                p(b["invd"]) if aux else None, p(b["omap"]) if aux else None, p(b["radii"]),
+                p(b["xyz"]), p(b["rot"]), p(b["scl"]), s), "view_forward")
+        else:
+            chk(lib.cgs_sample_curves_forward(B, m, p(cp), p(wl), p(b["isb"]), p(b["coef"]), cf(1e-8), p(b["norms"]),
+                                              p(b["xyz"]), p(b["rot"]), p(b["scl"]), s), "sample_curves_forward")
+            chk(lib.cgs_splat_attrs_forward(B, m, p(b["rot"]), p(b["xyz"]), p(ol), p(mask), cf(self.mask_threshold),
+                                            p(b["scl"]), p(cam.camera_center), p(cam.world_view_transform), p(b["rot_n"]),
+                                            p(b["opac"]), p(b["scl_m"]) if mask is not None else None, p(b["amap"]), s),
+                "splat_attrs_forward")
+            scales = b["scl_m"] if mask is not None else b["scl"]
+            chk(lib.cgs_rasterize_forward_static(
+                p(b["geom"]), p(b["bin"]), b["nbin"], p(b["img"]), self._cap, P, 0, 0, p(b["bg"]), W, H, p(b["xyz"]), None,
+                p(b["colors"]), p(b["opac"]), p(scales), 1.0, p(b["rot_n"]), None, p(b["amap"]),
+                p(cam.world_view_transform), p(cam.full_proj_transform), p(cam.camera_center), tanx, tany, p(b["color"]),
+                p(b["invd"]), p(b["omap"]), 0, 1, p(b["radii"]), s), "rasterize_forward_static")
+        a, bb = photometric_weights(self.lambda_mse, self.lambda_dssim)
+        launch_photometric_loss(H, W, b["color"], self._gt_stack, self._npos_table, a, bb, True, b["photo_ws"], b["g_img"],
+                                b["loss"], s, view_idx=self._view_idx)
+        loss, r_rot = self._direct_regularisers(b["loss"], b["rot"], b["radii"], self._opa_gate, b)
         # ---- backward: rasterizer -> attributes -> sampling, straight into the flat gradient views
-        chk(lib.cgs_rasterize_backward(
-            P, 0, 0, 1, p(b["bg"]), W, H, p(b["xyz"]), None, p(b["colors"]), p(b["amap"]), p(b["opac"]), p(scales), 1.0,
-            p(b["rot_n"]), None, p(cam.world_view_transform), p(cam.full_proj_transform), p(cam.camera_center), tanx,
-            tany, p(b["radii"]), p(b["geom"]), p(b["bin"]), p(b["img"]), p(b["g_img"]), None, None, p(b["g_m2d"]),
-            p(b["g_conic"]), p(b["g_opac"]), None, None, p(b["g_m3d"]), p(b["g_cov"]), None, p(b["g_scl"]),
-            p(b["g_rotn"]), p(b["g_amap"]), 0, 1, 0, s), "rasterize_backward")
-        chk(lib.cgs_splat_attrs_backward(
-            B, m, p(b["rot"]), p(b["xyz"]), p(ol), p(mask), cf(self.mask_threshold), p(b["scl"]), p(cam.camera_center),
-            p(cam.world_view_transform), p(b["g_rotn"]), p(b["g_opac"]), p(b["g_scl"]) if mask is not None else None,
-            p(b["g_amap"]), p(b["g_rot_raw"]), p(grads.view("opacity")), p(grads.view("mask")) if mask is not None else None,
-            p(b["g_scaling"]) if mask is not None else None, s), "splat_attrs_backward")
-        g_scaling = b["g_scaling"] if mask is not None else b["g_scl"]
-        loss = b["loss"]
-        if self.regularisers:
-            chk(lib.cgs_curve_regularizers(B, m, p(b["rot"]), p(ol), p(wl), p(b["radii"]), cf(self.opacity_loss_weight),
-                                           p(self._opa_gate), cf(self.lambda_curve_smo), cf(self.lambda_width), cf(0.005),
-                                           p(b["reg_ws"]), p(b["reg_loss"]), p(b["r_rot"]), p(b["r_op"]), p(b["r_w"]), s),
-                "curve_regularizers")
-            b["g_rot_raw"].add_(b["r_rot"])
-            grads.view("opacity").add_(b["r_op"])
-            loss = loss + b["reg_loss"]
-        chk(lib.cgs_sample_curves_backward(B, m, p(cp), p(wl), p(b["isb"]), p(b["coef"]), cf(1e-8), p(b["norms"]),
-                                           p(b["g_m3d"]), p(b["g_rot_raw"]), p(g_scaling), p(grads.view("curve_points")),
-                                           p(grads.view("width")), p(b["gv"]), s), "sample_curves_backward")
-        if self.regularisers:
-            grads.view("width").add_(b["r_w"])
-            if self._use_conn:   # adds to the curve-point gradient the sampling backward just wrote
-                chk(lib.cgs_endpoint_connection_loss(B, p(cp), cf(0.05), cf(self.lambda_points_conn), p(b["conn_ws"]),
-                                                     p(b["conn_loss"]), p(grads.view("curve_points")), 1, s),
-                    "endpoint_connection_loss")
-                loss = loss + b["conn_loss"]
-        if self._use_mask:      # train.py:110-111: lambda_mask * mean(sigmoid(mask)), gradient added by hand
-            sg = torch.sigmoid(mask)
-            loss = loss + self.lambda_mask * sg.mean()
-            grads.view("mask").add_(sg * (1 - sg), alpha=self.lambda_mask / mask.numel())
+        if self.fused_view:
+            chk(lib.cgs_view_backward(
+                B, m, p(cp), p(wl), p(b["isb"]), p(b["coef"]), cf(1e-8), p(b["norms"]), p(ol), p(mask), cf(self.mask_threshold),
+                None, p(b["geom"]), p(b["bin"]), p(b["img"]), p(b["bg"]), W, H, p(cam.world_view_transform),
+                p(cam.full_proj_transform), p(cam.camera_center), tanx, tany, p(b["radii"]), p(b["g_img"]), p(r_rot),
+                p(b["g_m2d"]), p(grads.view("curve_points")), p(grads.view("width")), p(grads.view("opacity")),
+                p(grads.view("mask")) if mask is not None else None, p(b["view_scratch"]), 0, s), "view_backward")
+        else:
+            chk(lib.cgs_rasterize_backward(
+                P, 0, 0, 1, p(b["bg"]), W, H, p(b["xyz"]), None, p(b["colors"]), p(b["amap"]), p(b["opac"]), p(scales), 1.0,
+                p(b["rot_n"]), None, p(cam.world_view_transform), p(cam.full_proj_transform), p(cam.camera_center), tanx,
+                tany, p(b["radii"]), p(b["geom"]), p(b["bin"]), p(b["img"]), p(b["g_img"]), None, None, p(b["g_m2d"]),
+                p(b["g_conic"]), p(b["g_opac"]), None, None, p(b["g_m3d"]), p(b["g_cov"]), None, p(b["g_scl"]),
+                p(b["g_rotn"]), p(b["g_amap"]), 0, 1, 0, s), "rasterize_backward")
+            chk(lib.cgs_splat_attrs_backward(
+                B, m, p(b["rot"]), p(b["xyz"]), p(ol), p(mask), cf(self.mask_threshold), p(b["scl"]), p(cam.camera_center),
+                p(cam.world_view_transform), p(b["g_rotn"]), p(b["g_opac"]), p(b["g_scl"]) if mask is not None else None,
+                p(b["g_amap"]), p(b["g_rot_raw"]), p(grads.view("opacity")), p(grads.view("mask")) if mask is not None else None,
+                p(b["g_scaling"]) if mask is not None else None, s), "splat_attrs_backward")
+            if r_rot is not None:
+                b["g_rot_raw"].add_(r_rot)
+            g_scaling = b["g_scaling"] if mask is not None else b["g_scl"]
+            chk(lib.cgs_sample_curves_backward(B, m, p(cp), p(wl), p(b["isb"]), p(b["coef"]), cf(1e-8), p(b["norms"]),
+                                               p(b["g_m3d"]), p(b["g_rot_raw"]), p(g_scaling), p(grads.view("curve_points")),
+                                               p(grads.view("width")), p(b["gv"]), s), "sample_curves_backward")
         status = b["status"]
-        if self._use_stats:     # gated like the Adam below: an overflowed replay adds nothing, its eager redo does
-            g.accumulate_densification_stats(b["radii"], b["g_m2d"], skip_flag=status[2:3])
-        if self._capture_coll:
-            import torch.distributed as dist
-            dist.all_reduce(g.optimizer.grads.flat)
-            dist.all_reduce(status[2:3], op=dist.ReduceOp.MAX)   # any rank overflowed -> every rank skips
-        if not self._collective or self._capture_coll:   # view-parallel: the all-reduce sits between backward and optimizer
-            g.optimizer.step_dev(zero_grad=True, skip_flag=status[2:3], report=self._report())
-        self.last = dict(radii=b["radii"], dL_dmeans2D=b["g_m2d"], render=b["color"], depth=b["invd"], all_map=b["omap"])
-        return loss, status
-
-    def _body_direct_fused(self, lib, b, cam, cp, wl, ol, mask, grads, tanx, tany, s):
-        """The direct body on the fused per-view entry points: 8 launches for render + its backward instead of 13."""
-        import ctypes as C
-        from . import _lib as L
-        g = self.g
-        B, P, m, H, W = b["B"], b["P"], b["m"], b["H"], b["W"]
-        p, cf, chk = L.ptr, C.c_float, L.check
-        chk(lib.cgs_view_forward(
-            B, m, p(cp), p(wl), p(b["isb"]), p(b["coef"]), cf(1e-8), p(b["norms"]), p(ol), p(mask), cf(self.mask_threshold),
-            None, p(b["geom"]), p(b["bin"]), b["nbin"], p(b["img"]), self._cap, p(b["bg"]), W, H,
-            p(cam.world_view_transform), p(cam.full_proj_transform), p(cam.camera_center), tanx, tany, p(b["color"]),
-            p(b["invd"]) if self.aux_outputs else None, p(b["omap"]) if self.aux_outputs else None, p(b["radii"]),
-            p(b["xyz"]), p(b["rot"]), p(b["scl"]), s), "view_forward")
-        a = self.lambda_mse * (1.0 - self.lambda_dssim)
-        bb = self.lambda_mse * self.lambda_dssim
-        chk(lib.cgs_photometric_loss_indexed(H, W, p(b["color"]), p(self._gt_stack), p(self._view_idx), cf(0.1),
-                                             p(self._npos_table), cf(a), cf(bb), 1, p(b["photo_ws"]), p(b["g_img"]),
-                                             p(b["loss"]), s), "photometric_loss_indexed")
-        loss = b["loss"]
-        extra = None
-        if self.regularisers:   # needs only forward quantities: runs before the backward and hands it dL/drotation_raw
-            chk(lib.cgs_curve_regularizers(B, m, p(b["rot"]), p(ol), p(wl), p(b["radii"]), cf(self.opacity_loss_weight),
-                                           p(self._opa_gate), cf(self.lambda_curve_smo), cf(self.lambda_width), cf(0.005),
-                                           p(b["reg_ws"]), p(b["reg_loss"]), p(b["r_rot"]), p(b["r_op"]), p(b["r_w"]), s),
-                "curve_regularizers")
-            extra = b["r_rot"]
-            loss = loss + b["reg_loss"]
-        chk(lib.cgs_view_backward(
-            B, m, p(cp), p(wl), p(b["isb"]), p(b["coef"]), cf(1e-8), p(b["norms"]), p(ol), p(mask), cf(self.mask_threshold),
-            None, p(b["geom"]), p(b["bin"]), p(b["img"]), p(b["bg"]), W, H, p(cam.world_view_transform),
-            p(cam.full_proj_transform), p(cam.camera_center), tanx, tany, p(b["radii"]), p(b["g_img"]), p(extra),
-            p(b["g_m2d"]), p(grads.view("curve_points")), p(grads.view("width")), p(grads.view("opacity")),
-            p(grads.view("mask")) if mask is not None else None, p(b["view_scratch"]), 0, s), "view_backward")
-        if self.regularisers:
-            grads.view("opacity").add_(b["r_op"])
-            grads.view("width").add_(b["r_w"])
-            if self._use_conn:
-                chk(lib.cgs_endpoint_connection_loss(B, p(cp), cf(0.05), cf(self.lambda_points_conn), p(b["conn_ws"]),
-                                                     p(b["conn_loss"]), p(grads.view("curve_points")), 1, s),
-                    "endpoint_connection_loss")
-                loss = loss + b["conn_loss"]
-        if self._use_mask:      # train.py:110-111: lambda_mask * mean(sigmoid(mask)), gradient added by hand
-            sg = torch.sigmoid(mask)
-            loss = loss + self.lambda_mask * sg.mean()
-            grads.view("mask").add_(sg * (1 - sg), alpha=self.lambda_mask / mask.numel())
-        status = b["status"]
-        if self._use_stats:     # gated like the Adam below: an overflowed replay adds nothing, its eager redo does
-            g.accumulate_densification_stats(b["radii"], b["g_m2d"], skip_flag=status[2:3])
-        if self._capture_coll:
-            import torch.distributed as dist
-            dist.all_reduce(g.optimizer.grads.flat)
-            dist.all_reduce(status[2:3], op=dist.ReduceOp.MAX)   # any rank overflowed -> every rank skips
-        if not self._collective or self._capture_coll:
-            g.optimizer.step_dev(zero_grad=True, skip_flag=status[2:3], report=self._report())
-        self.last = dict(radii=b["radii"], dL_dmeans2D=b["g_m2d"], render=b["color"],
-                         depth=b["invd"] if self.aux_outputs else None, all_map=b["omap"] if self.aux_outputs else None)
+        loss = self._direct_tail(loss, b["radii"], b["g_m2d"], grads, b, self._use_mask, self._use_conn, self._use_stats,
+                                 skip_flag=status[2:3])
+        self._captured_update(status[2:3])
+        self.last = dict(radii=b["radii"], dL_dmeans2D=b["g_m2d"], render=b["color"], depth=b["invd"] if aux else None,
+                         all_map=b["omap"] if aux else None)
         return loss, status
 
     def _report(self):
@@ -661,15 +605,13 @@ class GraphedTrainStep(TrainStep):
 
     def _probe_capacity(self):
         """Longest tile list over a few eager (exact-path) renders -> bucket capacity."""
-        from . import _lib as L
-        import ctypes
         lib = L.load()
         longest = 1
         with torch.no_grad():
             for cam in self.cams[:min(8, len(self.cams))]:
                 render(cam, self.g, self.pipe, self.bg, compute_visibility=False, clamp=False, compute_rend_dir=False)
-                m = ctypes.c_int64()
-                lib.cgs_last_forward_stats(None, ctypes.byref(m), None)
+                m = C.c_int64()
+                lib.cgs_last_forward_stats(None, C.byref(m), None)
                 longest = max(longest, int(m.value))
         limit = int(lib.cgs_bucket_capacity_limit())
         cap = (int(longest * self.cap_margin) + 64 + 63) // 64 * 64
@@ -790,7 +732,6 @@ class GraphedTrainStep(TrainStep):
         and the statistics; ``apply_update()`` / ``drop_update()`` then decide the optimizer step."""
         g = self.g
         if not update:
-            from . import _lib as L
             self.finish()
             return self._eager_step(view_index, False, self.direct and L.use_shim())
         if self._deferred is not None:
@@ -813,7 +754,7 @@ class GraphedTrainStep(TrainStep):
             self._capture(vi)
         self._stage(vi)
         self._graph.replay()
-        if self._collective and not self._capture_coll:
+        if self._collective and not self._capture_coll:   # the all-reduce between the replayed backward and Adam
             import torch.distributed as dist
             dist.all_reduce(g.optimizer.grads.flat)
             dist.all_reduce(self._status[2:3], op=dist.ReduceOp.MAX)   # any rank overflowed -> every rank skips
