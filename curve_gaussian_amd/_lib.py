@@ -86,6 +86,9 @@ SIGNATURES = {
     "cgs_view_metrics_workspace_bytes": (C.c_size_t, [_i]),
     "cgs_view_metrics": (_i, [_i, _vp, _vp, _vp, _vp, _vp]),
     "cgs_densification_stats": (_i, [_i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "cgs_project_points": (_i, [_i, _vp, _i, _vp, _vp, _i, _i, _vp, _vp]),
+    "cgs_render_points_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i]),
+    "cgs_render_points": (_i, [_i, _vp, _vp, _i, _vp, _vp, _i, _i, C.c_double, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "cgs_sample_curves_forward": (_i, [_i, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp]),
     "cgs_sample_curves_backward": (_i, [_i, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "cgs_splat_attrs_forward": (_i, [_i, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -1446,4 +1446,56 @@ int cgs_view_metrics(int n_views, const cgs_metric_view* views, void* workspace,
     return CGS_OK;
 }
 
+int cgs_project_points(int P, const float* points, int V, const double* intr, const double* w2c, int height, int width,
+                       double* uv_out, void* stream_) {
+    if (P < 0 || V < 0 || (long long)P * V > (1LL << 40)) {
+        set_error("cgs_project_points: invalid argument (P=%d, V=%d)", P, V);
+        return CGS_ERR_INVALID_ARGUMENT;
+    }
+    if (P == 0 || V == 0) return CGS_OK;
+    if (height <= 0 || width <= 0) {
+        set_error("cgs_project_points: invalid argument (height=%d, width=%d)", height, width);
+        return CGS_ERR_INVALID_ARGUMENT;
+    }
+    if (!points || !intr || !w2c || !uv_out) {
+        set_error("cgs_project_points: invalid argument (NULL pointer)");
+        return CGS_ERR_INVALID_ARGUMENT;
+    }
+    launch_project_points((hipStream_t)stream_, P, points, V, intr, w2c, height, width, uv_out);
+    if (!check_launch("project_points", false, (hipStream_t)stream_)) return CGS_ERR_HIP;
+    return CGS_OK;
+}
+
+size_t cgs_render_points_workspace_bytes(int P, int V, int height, int width) {
+    return render_points_workspace_bytes(P, V, height, width);
+}
+
+int cgs_render_points(int P, const float* points, const float* colors, int V, const double* intr, const double* w2c,
+                      int height, int width, double alpha, const double* background, float* out, int* kept,
+                      void* workspace, size_t workspace_bytes, void* stream_) {
+    if (P < 0 || V < 0 || height <= 0 || width <= 0 || (long long)height * width > (1LL << 31)) {
+        set_error("cgs_render_points: invalid argument (P=%d, V=%d, height=%d, width=%d)", P, V, height, width);
+        return CGS_ERR_INVALID_ARGUMENT;
+    }
+    if (!(alpha >= 0.0 && alpha <= 1.0)) {
+        set_error("cgs_render_points: invalid argument (alpha=%g, need 0 <= alpha <= 1)", alpha);
+        return CGS_ERR_INVALID_ARGUMENT;
+    }
+    if (V == 0) return CGS_OK;
+    if (!intr || !w2c || !background || !out || !workspace || (P > 0 && (!points || !colors))) {
+        set_error("cgs_render_points: invalid argument (NULL pointer)");
+        return CGS_ERR_INVALID_ARGUMENT;
+    }
+    const int per = render_points_views_per_chunk(P, V, height, width, workspace_bytes);
+    if (per <= 0) {
+        set_error("cgs_render_points: invalid argument (workspace of %zu bytes holds no view; one view needs %zu)",
+                  workspace_bytes, render_points_workspace_bytes(P, 1, height, width));
+        return CGS_ERR_INVALID_ARGUMENT;
+    }
+    launch_render_points((hipStream_t)stream_, P, points, colors, V, intr, w2c, height, width, alpha, background, out,
+                         kept, workspace, per);
+    if (!check_launch("render_points", false, (hipStream_t)stream_)) return CGS_ERR_HIP;
+    return CGS_OK;
+}
+
 }  // extern "C"

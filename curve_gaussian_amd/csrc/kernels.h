@@ -161,6 +161,16 @@ size_t view_metrics_workspace_bytes(int n_views);
 hipError_t launch_view_metrics(hipStream_t s, int n_views, const cgs_metric_view* views_host, void* workspace,
                                double* sums, double* means);
 
+// novel_view.hip
+void launch_project_points(hipStream_t s, int P, const float* points, int V, const double* intr, const double* w2c,
+                           int height, int width, double* uv);
+size_t render_points_workspace_bytes(int P, int V, int H, int W);
+int render_points_views_per_chunk(int P, int V, int H, int W, size_t ws_bytes);
+int render_points_keep(double alpha);
+void launch_render_points(hipStream_t s, int P, const float* points, const float* colors, int V, const double* intr,
+                          const double* w2c, int height, int width, double alpha, const double* bg, float* out,
+                          int* kept, void* ws, int views_per_chunk);
+
 // densify.hip
 void launch_densification_stats(hipStream_t s, long long P, const int* radii, const float* grad, long long stride,
                                 float* max_radii, float* accum, float* denom, const unsigned int* skip_flag);

@@ -1,0 +1,319 @@
+"""Multi-view projection of the extracted edges (the reference's eval_ABC.py --render_mv, :66-138 and :180-185, and
+eval_replica.py process_scan, :100-212): the ``parametric_edges.json`` edges, sampled densely and coloured per edge, are
+projected into every camera of a scan and drawn one pixel per point, one image per view.
+
+``project_points`` and ``render_points`` run in the HIP kernels ``cgs_project_points`` / ``cgs_render_points`` (there is
+no CPU path: CPU tensors raise).  The camera loaders and the per-edge colours are host-side float64 numpy, computed as
+the reference computes them.  Deviations: the output is the camera's pixel grid (a kept point covers pixel
+(floor(u), floor(v)), alpha-composited in point order) rather than a matplotlib figure; the colour permutation is seeded;
+SIMPLE_PINHOLE cameras are read as (f, f, cx, cy)."""
+import colorsys
+import json
+import logging
+import os
+import time
+from concurrent.futures import ThreadPoolExecutor
+from pathlib import Path
+from typing import NamedTuple
+
+import numpy as np
+import torch
+
+from .. import _lib as L
+from ..scene import colmap_io
+from ..scene.dataset_io import focal2fov, fov2focal
+from .abc import pred_points_and_directions
+
+log = logging.getLogger(__name__)
+
+ALPHA = 0.5                        # plt.scatter(..., alpha=0.5)
+BACKGROUND = (1.0, 1.0, 1.0)       # matplotlib's white figure
+REPLICA_SAMPLE_RESOLUTION = 0.0005  # eval_replica.py:113
+WORKSPACE_BUDGET = 1 << 30          # bytes of kernel scratch per render_points call (views are chunked to fit)
+OUTPUT_BUDGET = 1 << 30             # bytes of float32 images per driver batch
+MAX_WRITERS = 16                    # image-encoding threads
+
+
+class NovelViewCamera(NamedTuple):
+    name: str          # output file name (ABC: the frame's stem; Replica: the COLMAP image name)
+    R: np.ndarray      # [3,3] float64 world -> camera rotation, applied as R @ X
+    T: np.ndarray      # [3] float64
+    fx: float
+    fy: float
+    cx: float
+    cy: float
+    width: int
+    height: int
+
+
+# ------------------------------------------------------------------------------------------------ camera loaders
+def transforms_video_cameras(scan_dir, detector="DexiNed"):
+    """The cameras of ``<scan_dir>/transforms_video.json`` as readCamerasFromTransforms (scene/dataset_readers.py:251-287)
+    builds them and project_points_to_camera (eval_ABC.py:66-81) turns them into intrinsics: c2w[:3,1:3] flipped, w2c =
+    inv(c2w), fx = W / (2 tan(FovX / 2)), FovY = focal2fov(fov2focal(FovX, W), H), fy = H / (2 tan(FovY / 2)),
+    (cx, cy) = (W / 2, H / 2).  W and H are the size of the edge map the reference opens, found by its path rule
+    (``<scan_dir>/<file_path>.png`` with 'ABC-NEF/' -> 'ABC-NEF_Edge/data/' and 'train' -> 'edge_<detector>'); a missing
+    file raises FileNotFoundError naming the path."""
+    from PIL import Image
+    path = os.path.abspath(scan_dir)
+    with open(os.path.join(path, "transforms_video.json")) as f:
+        contents = json.load(f)
+    fovx = contents["camera_angle_x"]
+    cams = []
+    for frame in contents["frames"]:
+        cam_name = os.path.join(path, frame["file_path"] + ".png")
+        c2w = np.array(frame["transform_matrix"])
+        c2w[:3, 1:3] *= -1
+        w2c = np.linalg.inv(c2w)
+        image_path = os.path.join(path, cam_name)
+        edge_path = image_path.replace("ABC-NEF/", "ABC-NEF_Edge/data/").replace("train", "edge_" + detector)
+        if not os.path.isfile(edge_path):
+            raise FileNotFoundError(f"edge map not found: {edge_path}")
+        with Image.open(edge_path) as img:
+            W, H = img.size
+        fovy = focal2fov(fov2focal(fovx, W), H)
+        cams.append(NovelViewCamera(Path(cam_name).stem, np.ascontiguousarray(w2c[:3, :3]), w2c[:3, 3].copy(),
+                                    W / (2 * np.tan(fovx / 2)), H / (2 * np.tan(fovy / 2)), W / 2, H / 2, W, H))
+    return cams
+
+
+def colmap_cameras(scan_dir):
+    """Every image of ``<scan_dir>/sparse/0/{images,cameras}.bin``, in file order, as eval_replica.py:136-157 reads them:
+    R = qvec2rotmat(qvec), T = tvec, PINHOLE (fx, fy, cx, cy) = params[0:4].  SIMPLE_PINHOLE is read as (f, f, cx, cy)
+    (the reference would index past its 3 parameters); any other model raises ValueError."""
+    sparse = os.path.join(scan_dir, "sparse", "0")
+    imgs = colmap_io.read_images_binary(os.path.join(sparse, "images.bin"))
+    intr = colmap_io.read_cameras_binary(os.path.join(sparse, "cameras.bin"))
+    cams = []
+    for _, im in imgs.items():
+        c = intr[im.camera_id]
+        if c.model == "PINHOLE":
+            fx, fy, cx, cy = (float(v) for v in c.params[:4])
+        elif c.model == "SIMPLE_PINHOLE":
+            fx, cx, cy = (float(v) for v in c.params[:3])
+            fy = fx
+        else:
+            raise ValueError(f"{sparse}: camera {c.id} has model {c.model}; novel views need PINHOLE or SIMPLE_PINHOLE")
+        cams.append(NovelViewCamera(im.name, colmap_io.qvec2rotmat(im.qvec), np.asarray(im.tvec, np.float64), fx, fy, cx,
+                                    cy, int(c.width), int(c.height)))
+    return cams
+
+
+def camera_arrays(cams):
+    """(intrinsics [V,4] = (fx, fy, cx, cy), w2c [V,3,4] = [R | T]) float64 host arrays of a list of cameras."""
+    intr = np.array([[c.fx, c.fy, c.cx, c.cy] for c in cams], np.float64).reshape(-1, 4)
+    w2c = np.array([np.concatenate([c.R, c.T[:, None]], 1) for c in cams], np.float64).reshape(-1, 3, 4)
+    return intr, w2c
+
+
+# ------------------------------------------------------------------------------------------------ per-edge colours
+def _hls_palette(n, h=0.01, l=0.6, s=0.65):
+    """seaborn.color_palette('hls', n)."""
+    hues = np.linspace(0, 1, int(n) + 1)[:-1]
+    hues += h
+    hues %= 1
+    hues -= hues.astype(int)
+    return [colorsys.hls_to_rgb(h_i, l, s) for h_i in hues]
+
+
+def fancy_cmap_lut(N=256):
+    """The [N,3] float64 lookup table of utils/vis_utils.get_fancy_cmap: gold, then the 'hls' palette of 100 colours
+    rotated by 3, through LinearSegmentedColormap.from_list (N = 256 entries, linear interpolation, gamma 1)."""
+    pal = _hls_palette(100)
+    colors = np.array([(1.0, 215 / 255, 0.0)] + pal[3:] + pal[:2], np.float64)   # 'gold' = #FFD700
+    x = np.linspace(0, 1, len(colors)) * (N - 1)
+    xind = (N - 1) * np.linspace(0, 1, N) ** 1.0
+    ind = np.searchsorted(x, xind)[1:-1]
+    distance = (xind[1:-1] - x[ind - 1]) / (x[ind] - x[ind - 1])
+    lut = np.concatenate([colors[:1], distance[:, None] * (colors[ind] - colors[ind - 1]) + colors[ind - 1],
+                          colors[-1:]])
+    return np.clip(lut, 0.0, 1.0)
+
+
+def fancy_colors(num):
+    """utils/vis_utils.get_fancy_color(num): float32 [num,3], the colour map at linspace(0, 1, num + 1)[1:]."""
+    lut = fancy_cmap_lut()
+    N = lut.shape[0]
+    xa = torch.linspace(0, 1, num + 1)[1:].numpy().copy()
+    xa *= N
+    xa[xa == N] = N - 1
+    return torch.from_numpy(lut[xa.astype(int)]).float()
+
+
+def edge_point_colors(pred, seed=0):
+    """Per-point colours of get_pred_points_and_directions (eval_utils.py:387-388, 414, 482): edge e (curves, then lines)
+    gets fancy_colors(n + 1)[perm][e], perm = torch.randperm(n) drawn from a generator seeded with `seed` (the reference's
+    permutation is unseeded), repeated over the edge's samples.  float32 [N,3] in the order of pred.points."""
+    n = int(pred.num_curves) + int(pred.num_lines)
+    g = torch.Generator().manual_seed(int(seed))
+    cols = fancy_colors(n + 1)[torch.randperm(n, generator=g)].numpy()
+    counts = np.concatenate([np.asarray(pred.curve_counts, np.int64), np.asarray(pred.line_counts, np.int64)])
+    return np.repeat(cols, counts, axis=0).reshape(-1, 3).astype(np.float32)
+
+
+# ------------------------------------------------------------------------------------------------ GPU ops
+def _cameras_on(dev, intrinsics, w2c):
+    def host(x):
+        if isinstance(x, torch.Tensor):
+            x = x.detach().cpu().numpy()
+        return np.asarray(x, dtype=np.float64)
+    K, M = host(intrinsics), host(w2c)
+    V = K.shape[0] if K.ndim == 2 else -1
+    if K.shape != (V, 4) or M.size != 12 * V:
+        raise L.CurveGSError(f"intrinsics must be [V,4] and w2c [V,3,4] (got {K.shape}, {M.shape})")
+    return (V, torch.from_numpy(np.ascontiguousarray(K)).to(dev),
+            torch.from_numpy(np.ascontiguousarray(M.reshape(V, 12))).to(dev))
+
+
+def _points(points, name="points"):
+    L.require_gpu_tensor(points, name)
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise L.CurveGSError(f"{name} must be [P,3] (got {tuple(points.shape)})")
+    return points.to(torch.float32).contiguous()
+
+
+def project_points(points, intrinsics, w2c, height, width):
+    """(u, v) of every point in every view, float64 [V,P,2] on the points' device, NaN for a dropped point (behind the
+    camera, c2 <= 0, or outside 0 <= u < width, 0 <= v < height).  points: float32 [P,3] GPU tensor; intrinsics [V,4]
+    (fx, fy, cx, cy) and w2c [V,3,4] float64 host arrays or tensors (``cgs_project_points``)."""
+    pts = _points(points)
+    dev = pts.device
+    with L.device_guard(dev):
+        V, K, M = _cameras_on(dev, intrinsics, w2c)
+        P = pts.shape[0]
+        uv = torch.empty((V, P, 2), dtype=torch.float64, device=dev)
+        rc = L.load().cgs_project_points(P, L.ptr(pts), V, L.ptr(K), L.ptr(M), int(height), int(width), L.ptr(uv),
+                                         L.raw_stream(dev))
+        L.check(rc, "cgs_project_points")
+    return uv
+
+
+def render_points(points, colors, intrinsics, w2c, height, width, alpha=ALPHA, background=BACKGROUND,
+                  workspace_bytes=None, return_kept=False):
+    """float32 [V,height,width,3] images of the points (``cgs_render_points``): a kept point covers pixel
+    (floor(u), floor(v)), the points of a pixel are composited in ascending index with constant `alpha` over
+    `background`.  points / colors float32 [P,3] GPU tensors on one device; cameras as project_points.  The views are
+    processed in chunks that fit `workspace_bytes` of scratch (default: WORKSPACE_BUDGET; the result does not depend on
+    it).  With return_kept, also the int32 [V] number of kept points per view."""
+    pts = _points(points)
+    col = _points(colors, "colors")
+    dev = pts.device
+    if col.device != dev or col.shape[0] != pts.shape[0]:
+        raise L.CurveGSError(f"colors must be [P,3] on {dev} (got {tuple(col.shape)} on {col.device})")
+    bg = np.ascontiguousarray(np.asarray(background, np.float64).reshape(3))
+    lib = L.load()
+    with L.device_guard(dev):
+        V, K, M = _cameras_on(dev, intrinsics, w2c)
+        P, H, W = pts.shape[0], int(height), int(width)
+        out = torch.empty((V, max(H, 0), max(W, 0), 3), dtype=torch.float32, device=dev)
+        kept = torch.zeros((V,), dtype=torch.int32, device=dev)
+        if V > 0:
+            need = lib.cgs_render_points_workspace_bytes(P, V, H, W)
+            one = lib.cgs_render_points_workspace_bytes(P, 1, H, W)
+            budget = WORKSPACE_BUDGET if workspace_bytes is None else int(workspace_bytes)
+            nbytes = max(min(need, budget), one)
+            ws = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=dev)
+            rc = lib.cgs_render_points(P, L.ptr(pts), L.ptr(col), V, L.ptr(K), L.ptr(M), H, W, float(alpha),
+                                       bg.ctypes.data_as(L.C.c_void_p), L.ptr(out), L.ptr(kept), L.ptr(ws), nbytes,
+                                       L.raw_stream(dev))
+            L.check(rc, "cgs_render_points")
+    return (out, kept) if return_kept else out
+
+
+# ------------------------------------------------------------------------------------------------ drivers
+def _write_images(jobs, pool):
+    """jobs: (path, uint8 [H,W,3]); PIL picks the format from the extension, as savefig does."""
+    from PIL import Image
+
+    def one(job):
+        path, img = job
+        Image.fromarray(img, "RGB").save(path)
+    list(pool.map(one, jobs))
+
+
+def render_views(points, colors, cams, out_dir, file_names, device=None, alpha=ALPHA, background=BACKGROUND):
+    """Renders `points` into every camera and writes <out_dir>/<file_names[v]> for each view with at least one kept
+    point (the reference saves nothing for an empty view): round(255 * image) as uint8 RGB.  Views of one size are
+    rendered together, OUTPUT_BUDGET bytes of images at a time.  Returns {"views", "written", "gpu_s", "write_s"}: the
+    GPU time (render, conversion and copy to the host, synchronised) and the encoding time, in seconds."""
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    pts = torch.from_numpy(np.ascontiguousarray(points, np.float32).reshape(-1, 3)).to(dev)
+    col = torch.from_numpy(np.ascontiguousarray(colors, np.float32).reshape(-1, 3)).to(dev)
+    stats = {"views": len(cams), "written": 0, "gpu_s": 0.0, "write_s": 0.0}
+    by_size = {}
+    for v, c in enumerate(cams):
+        by_size.setdefault((c.height, c.width), []).append(v)
+    os.makedirs(out_dir, exist_ok=True)
+    with ThreadPoolExecutor(max_workers=MAX_WRITERS) as pool:
+        for (H, W), idx in by_size.items():
+            per = max(1, OUTPUT_BUDGET // (H * W * 12))
+            for b in range(0, len(idx), per):
+                sel = idx[b:b + per]
+                intr, w2c = camera_arrays([cams[v] for v in sel])
+                t0 = time.perf_counter()
+                img, kept = render_points(pts, col, intr, w2c, H, W, alpha, background, return_kept=True)
+                u8 = torch.round(img * 255.0).clamp_(0, 255).to(torch.uint8).cpu().numpy()
+                kept = kept.cpu().numpy()
+                t1 = time.perf_counter()
+                jobs = [(os.path.join(out_dir, file_names[v]), u8[k]) for k, v in enumerate(sel) if kept[k] > 0]
+                _write_images(jobs, pool)
+                stats["gpu_s"] += t1 - t0
+                stats["write_s"] += time.perf_counter() - t1
+                stats["written"] += len(jobs)
+    return stats
+
+
+def _scan_points(base_dir, scan, sample_resolution, seed):
+    path = os.path.join(base_dir, scan, "parametric_edges.json")
+    if not os.path.exists(path):
+        log.info(f"Invalid prediction at {scan}")
+        return None
+    pred = pred_points_and_directions(path, sample_resolution)
+    pts = pred.points
+    if len(pts) == 0:
+        log.info(f"Invalid prediction at {scan}")
+        return None
+    return pts, edge_point_colors(pred, seed)
+
+
+def render_abc_novel_views(base_dir, dataset_dir, detector="DexiNed", seed=0, device=None):
+    """eval_ABC.py main with --render_mv (:180-185): for every scan directory of `dataset_dir` (sorted) with a
+    <base_dir>/<scan>/parametric_edges.json, the edges sampled every 0.005 are drawn into every camera of
+    <dataset_dir>/<scan>/transforms_video.json and written to <base_dir>/<scan>/novel_view/<frame stem>.png.
+    Returns {scan: stats of render_views}."""
+    out = {}
+    for scan in sorted(f.name for f in os.scandir(dataset_dir) if f.is_dir()):
+        log.info(f"Processing: {scan}")
+        got = _scan_points(base_dir, scan, 0.005, seed)
+        if got is None:
+            continue
+        cams = transforms_video_cameras(os.path.join(dataset_dir, scan), detector)
+        out[scan] = render_views(*got, cams, os.path.join(base_dir, scan, "novel_view"),
+                                 [c.name + ".png" for c in cams], device)
+    return out
+
+
+def replica_scans(dataset_dir, scans_file=None):
+    """The scan names of a Replica run: the lines of `scans_file` (the reference reads edge_extraction/Replica_scans.txt),
+    or every directory of `dataset_dir` holding sparse/0, sorted."""
+    if scans_file is not None:
+        with open(scans_file) as f:
+            return [ln.strip() for ln in f if ln.strip()]
+    return sorted(f.name for f in os.scandir(dataset_dir)
+                  if f.is_dir() and os.path.isdir(os.path.join(f.path, "sparse", "0")))
+
+
+def render_replica_novel_views(base_dir, dataset_dir, scans=None, seed=0, device=None):
+    """eval_replica.py process_scan (:100-212) for every scan in `scans` (default: replica_scans(dataset_dir)): the edges
+    sampled every 0.0005 are drawn into every COLMAP camera of <dataset_dir>/<scan>/sparse/0 and written to
+    <base_dir>/<scan>/novel_view/<image name> (format from the extension).  The comparison video is not made.
+    Returns {scan: stats of render_views}."""
+    out = {}
+    for scan in (replica_scans(dataset_dir) if scans is None else scans):
+        print(f"Processing: {scan}")
+        got = _scan_points(base_dir, scan, REPLICA_SAMPLE_RESOLUTION, seed)
+        if got is None:
+            continue
+        cams = colmap_cameras(os.path.join(dataset_dir, scan))
+        out[scan] = render_views(*got, cams, os.path.join(base_dir, scan, "novel_view"), [c.name for c in cams], device)
+    return out

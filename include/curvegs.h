@@ -567,6 +567,38 @@ int cgs_densification_stats(int64_t P, const int* radii /*[P]*/, const float* dL
                             int64_t grad_stride, float* max_radii2D /*[P]*/, float* xyz_gradient_accum /*[P]*/,
                             float* denom /*[P]*/, const uint32_t* skip_flag /*device, may be NULL*/, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Multi-view projection of extracted edges (novel views).  Replaces the per-point, per-view Python loops of the
+ * reference's eval_ABC.py --render_mv (project_points_to_camera / visualize_projection :66-138) and eval_replica.py
+ * (process_scan :100-212).  Cameras: intr[v] = (fx, fy, cx, cy) and w2c[v] = [R | T] (row-major 3x4), float64.
+ * Projection, in float64 with the reference's operation order: X = (double)points[i], c = R X + T with every row
+ * ((r0*X + r1*Y) + r2*Z) + t (no FMA contraction), dropped if c2 <= 0, u = fx * (c0 / c2) + cx, v = fy * (c1 / c2) + cy
+ * (IEEE division), kept if 0 <= u < width and 0 <= v < height.
+ *
+ * cgs_project_points writes uv_out[v][i] = (u, v) of every kept point and (NaN, NaN) for a dropped one.  P = 0 or V = 0
+ * is a no-op; negative sizes, height or width <= 0 and NULL pointers are CGS_ERR_INVALID_ARGUMENT.
+ *
+ * cgs_render_points draws the kept points into float32 images out[V,height,width,3]: a kept point covers pixel
+ * (floor(u), floor(v)); the n points of a pixel are composited in ascending point index with constant `alpha` over
+ * `background` (host, 3 values): out = bg (1-alpha)^n + sum_j alpha c_j (1-alpha)^r_j, r_j = the number of later points
+ * in that pixel, in float64, rounded to float32 once.  Only the newest K points of a pixel enter the sum, K the smallest
+ * k with (1-alpha)^k <= 2^-25 (25 at alpha = 0.5, 1 at alpha = 1): the terms left out add up to at most 2^-25 max|c|.
+ * Deterministic (integer atomics only; the result depends only on the set of points in each pixel).  kept (device,
+ * [V], may be NULL) receives the number of kept points of each view.  `workspace` is device scratch of
+ * `workspace_bytes` bytes: cgs_render_points_workspace_bytes(P, V, height, width) processes every view in one pass
+ * (capped at 2^31 (view, point) pairs and 65535 views per pass); less processes the views in chunks, down to
+ * cgs_render_points_workspace_bytes(P, 1, height, width).  P = 0 writes the background; V = 0 is a no-op; negative
+ * sizes, height or width <= 0, height * width > 2^31, alpha outside [0, 1], a workspace too small for one view and NULL
+ * pointers are CGS_ERR_INVALID_ARGUMENT, rejected before anything is launched.
+ * ------------------------------------------------------------------------------------------------ */
+int cgs_project_points(int P, const float* points /*[P,3]*/, int V, const double* intr /*[V,4]*/,
+                       const double* w2c /*[V,12]*/, int height, int width, double* uv_out /*[V,P,2]*/, void* stream);
+size_t cgs_render_points_workspace_bytes(int P, int V, int height, int width);
+int cgs_render_points(int P, const float* points /*[P,3]*/, const float* colors /*[P,3]*/, int V,
+                      const double* intr /*[V,4]*/, const double* w2c /*[V,12]*/, int height, int width, double alpha,
+                      const double* background /*host [3]*/, float* out /*[V,height,width,3]*/, int* kept /*[V]*/,
+                      void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
