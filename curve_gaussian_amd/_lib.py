@@ -89,6 +89,9 @@ SIGNATURES = {
     "cgs_project_points": (_i, [_i, _vp, _i, _vp, _vp, _i, _i, _vp, _vp]),
     "cgs_render_points_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i]),
     "cgs_render_points": (_i, [_i, _vp, _vp, _i, _vp, _vp, _i, _i, C.c_double, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "cgs_ellipsoid_mesh_body_bytes": (_i64, [_i, _i, C.POINTER(_i64), C.POINTER(_i64)]),
+    "cgs_ellipsoid_mesh_vertices": (_i, [_i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
+    "cgs_ellipsoid_mesh_faces": (_i, [_i, _i, _i, _i, _vp, _vp, _vp]),
     "cgs_sample_curves_forward": (_i, [_i, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp]),
     "cgs_sample_curves_backward": (_i, [_i, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "cgs_splat_attrs_forward": (_i, [_i, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

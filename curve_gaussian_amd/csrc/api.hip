@@ -1498,4 +1498,65 @@ int cgs_render_points(int P, const float* points, const float* colors, int V, co
     return CGS_OK;
 }
 
+int64_t cgs_ellipsoid_mesh_body_bytes(int P, int resolution, int64_t* vertex_bytes, int64_t* face_bytes) {
+    if (P < 0 || resolution < 2 || resolution > 1024) {
+        set_error("cgs_ellipsoid_mesh_body_bytes: invalid argument (P=%d, resolution=%d)", P, resolution);
+        return -1;
+    }
+    const long long V0 = 2 + 2LL * resolution * (resolution - 1), F0 = 4LL * resolution * (resolution - 1);
+    if ((long long)P * V0 > (1LL << 31)) {
+        set_error("cgs_ellipsoid_mesh_body_bytes: %d splats of %lld vertices: a vertex index would not fit in an int", P,
+                  V0);
+        return -1;
+    }
+    const int64_t vb = (int64_t)P * V0 * 27, fb = (int64_t)P * F0 * 13;
+    if (vertex_bytes) *vertex_bytes = vb;
+    if (face_bytes) *face_bytes = fb;
+    return vb + fb;
+}
+
+int cgs_ellipsoid_mesh_vertices(int first, int count, const float* xyz, const float* rot, const float* scale,
+                                const float* rgb, int V0, const double* unit_vertices, void* out, void* stream_) {
+    if (first < 0 || count < 0 || V0 <= 0 || (long long)(first + (long long)count) * V0 > (1LL << 31)) {
+        set_error("cgs_ellipsoid_mesh_vertices: invalid argument (first=%d, count=%d, V0=%d)", first, count, V0);
+        return CGS_ERR_INVALID_ARGUMENT;
+    }
+    if (count == 0) return CGS_OK;
+    if (!xyz || !rot || !scale || !rgb || !unit_vertices || !out) {
+        set_error("cgs_ellipsoid_mesh_vertices: invalid argument (NULL pointer)");
+        return CGS_ERR_INVALID_ARGUMENT;
+    }
+    if ((uintptr_t)out % 16) {
+        set_error("cgs_ellipsoid_mesh_vertices: out must be 16-byte aligned");
+        return CGS_ERR_INVALID_ARGUMENT;
+    }
+    launch_ellipsoid_vertices((hipStream_t)stream_, first, count, xyz, rot, scale, rgb, V0, unit_vertices, out);
+    if (!check_launch("ellipsoid_mesh_vertices", false, (hipStream_t)stream_)) return CGS_ERR_HIP;
+    return CGS_OK;
+}
+
+int cgs_ellipsoid_mesh_faces(int first, int count, int V0, int F0, const int* template_faces, void* out, void* stream_) {
+    if (first < 0 || count < 0 || V0 <= 0 || F0 <= 0) {
+        set_error("cgs_ellipsoid_mesh_faces: invalid argument (first=%d, count=%d, V0=%d, F0=%d)", first, count, V0, F0);
+        return CGS_ERR_INVALID_ARGUMENT;
+    }
+    if ((long long)(first + (long long)count) * V0 > (1LL << 31)) {
+        set_error("cgs_ellipsoid_mesh_faces: splats [%d, %d) of %d vertices: a vertex index would not fit in an int",
+                  first, first + count, V0);
+        return CGS_ERR_INVALID_ARGUMENT;
+    }
+    if (count == 0) return CGS_OK;
+    if (!template_faces || !out) {
+        set_error("cgs_ellipsoid_mesh_faces: invalid argument (NULL pointer)");
+        return CGS_ERR_INVALID_ARGUMENT;
+    }
+    if ((uintptr_t)out % 16) {
+        set_error("cgs_ellipsoid_mesh_faces: out must be 16-byte aligned");
+        return CGS_ERR_INVALID_ARGUMENT;
+    }
+    launch_ellipsoid_faces((hipStream_t)stream_, first, count, V0, F0, template_faces, out);
+    if (!check_launch("ellipsoid_mesh_faces", false, (hipStream_t)stream_)) return CGS_ERR_HIP;
+    return CGS_OK;
+}
+
 }  // extern "C"

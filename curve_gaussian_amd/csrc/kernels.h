@@ -171,6 +171,11 @@ void launch_render_points(hipStream_t s, int P, const float* points, const float
                           const double* w2c, int height, int width, double alpha, const double* bg, float* out,
                           int* kept, void* ws, int views_per_chunk);
 
+// mesh.hip
+void launch_ellipsoid_vertices(hipStream_t s, int first, int count, const float* xyz, const float* rot, const float* scale,
+                               const float* rgb, int V0, const double* template_vertices, void* out);
+void launch_ellipsoid_faces(hipStream_t s, int first, int count, int V0, int F0, const int* template_faces, void* out);
+
 // densify.hip
 void launch_densification_stats(hipStream_t s, long long P, const int* radii, const float* grad, long long stride,
                                 float* max_radii, float* accum, float* denom, const unsigned int* skip_flag);

@@ -394,6 +394,17 @@ class GaussianCurveModel:
         cov = Lm @ Lm.transpose(1, 2)
         return torch.stack((cov[:, 0, 0], cov[:, 0, 1], cov[:, 0, 2], cov[:, 1, 1], cov[:, 1, 2], cov[:, 2, 2]), -1)
 
+    # ------------------------------------------------------------------ inspection files (:634-727, scene/snapshot_viz.py)
+    def draw_curve(self, path, step, num_sample=200, seed=0):
+        """``{path}/curve_step{step}.ply``: num_sample points of every curve, coloured per curve (ASCII PLY)."""
+        from . import snapshot_viz
+        return snapshot_viz.draw_curve(self, path, step, num_sample, seed)
+
+    def draw_ellipsoids(self, path, step, radius=1.2, seed=0):
+        """``{path}/ellipsoids_step{step}.ply``: every splat as a scaled, rotated sphere (binary PLY, built on the GPU)."""
+        from . import snapshot_viz
+        return snapshot_viz.draw_ellipsoids(self, path, step, radius, seed)
+
     @property
     def get_features(self):
         return torch.cat((self._features_dc.flatten(0, 1), self._features_rest.flatten(0, 1)), dim=1)

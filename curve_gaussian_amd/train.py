@@ -2,6 +2,7 @@
 ``parametric_edges.json``.
 
     python -m curve_gaussian_amd.train -s SCAN -m OUT [--iterations N] [--backend graphed|direct|autograd|torch]
+                                       [--draw_snapshots]
 
 The loop keeps the reference's order.  Per iteration: learning rate, SH degree every 1000 iterations, a random view without
 replacement, render + losses + every regulariser + backward (one ``TrainStep`` call), densification statistics before
@@ -9,12 +10,14 @@ replacement, render + losses + every regulariser + backward (one ``TrainStep`` c
 
 The topology edits run between the backward and the optimizer step (:183-236), so those iterations are run with
 ``step(update=False)`` and finished with ``apply_update()``; they are known in advance from the iteration number.  So are
-the report and snapshot iterations, which read the model before its update (:176-229).  Every other iteration runs
+the report and snapshot iterations, which read the model before its update (:176-229).  With ``draw`` (``--draw_snapshots``)
+every snapshot is followed by the reference's two inspection files, ``curve_step{N}.ply`` and ``ellipsoids_step{N}.ply``
+(``draw_curve`` / ``draw_ellipsoids``, :215-220; scene/snapshot_viz.py); it is off by default.  Every other iteration runs
 straight through, and with ``backend="graphed"`` it is one graph replay.  An edit that replaced a curve parameter leaves
 that group without gradient, and torch.optim.Adam then skips it; the flat one-launch Adam skips the whole step then
 (``TrainStep.apply_update``).
 
-Out of scope: tensorboard, draw_curve / draw_ellipsoids, the network GUI, view-parallel runs, sparse_adam."""
+Out of scope: tensorboard, the network GUI, view-parallel runs, sparse_adam."""
 import argparse
 import os
 import sys
@@ -174,7 +177,7 @@ def _export(gaussians, dataset, opt):
 
 def training(dataset, opt, testing_iterations, saving_iterations, checkpoint_iterations, checkpoint=None, backend="graphed",
              seed=0, device="cuda", quiet=False, scene=None, step=None, report=None, save_ply=None, save_checkpoint=None,
-             export=None):
+             export=None, draw=False):
     """train.py:38-248.  Returns {"events": [(iteration, event, n_curves_after)] for every edit, report, save, checkpoint and
     the export, "losses": {iteration: loss} (the first iteration and every iteration run with a deferred update),
     "first_iter", "scene", "gaussians"}.
@@ -182,7 +185,9 @@ def training(dataset, opt, testing_iterations, saving_iterations, checkpoint_ite
     Collaborators (defaults in brackets), injectable so that the loop itself can be run by a CPU test: ``scene`` = (scene,
     gaussians) [make_scene], ``step`` = the per-iteration object [make_step(backend, ...)], ``report(iteration,
     testing_iterations, scene, bg)`` [evaluation.training_report], ``save_ply(gaussians, model_path, iteration)``,
-    ``save_checkpoint(obj, path)`` [torch.save], ``export(gaussians, dataset, opt)`` [write_parametric_edges]."""
+    ``save_checkpoint(obj, path)`` [torch.save], ``export(gaussians, dataset, opt)`` [write_parametric_edges].  ``draw``: after
+    every snapshot, ``gaussians.draw_curve(dir, iteration)`` and ``gaussians.draw_ellipsoids(dir, iteration)`` into the
+    snapshot's directory (train.py:215-220); no event is logged for them."""
     say = (lambda *a: None) if quiet else print
     os.makedirs(dataset.model_path, exist_ok=True)
     scene, gaussians = scene if scene is not None else make_scene(dataset, opt, device)
@@ -251,6 +256,10 @@ def training(dataset, opt, testing_iterations, saving_iterations, checkpoint_ite
             say(f"\n[ITER {iteration}] Saving Gaussians")
             save_ply(gaussians, dataset.model_path, iteration)
             log(iteration, "save")
+            if draw:                                                                # :215-220
+                snap = os.path.join(dataset.model_path, "point_cloud", f"iteration_{iteration}")
+                gaussians.draw_curve(snap, iteration)
+                gaussians.draw_ellipsoids(snap, iteration)
         if iteration < opt.iterations:                                              # :227-236
             step.apply_update()
         else:
@@ -296,6 +305,8 @@ def build_parser():
     p.add_argument("--start_checkpoint", type=str, default=None)
     p.add_argument("--backend", choices=BACKENDS, default="graphed")
     p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--draw_snapshots", action="store_true",
+                   help="write curve_step{N}.ply and ellipsoids_step{N}.ply next to every snapshot")
     return p
 
 
@@ -318,7 +329,7 @@ def main(argv=None):
         raise SystemExit("train: -m / --model_path is required")
     print("Optimizing " + dataset.model_path)
     training(dataset, opt, args.test_iterations, args.save_iterations, args.checkpoint_iterations, args.start_checkpoint,
-             backend=args.backend, seed=args.seed, quiet=args.quiet)
+             backend=args.backend, seed=args.seed, quiet=args.quiet, draw=args.draw_snapshots)
     print("\nTraining complete.")
 
 

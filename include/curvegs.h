@@ -599,6 +599,38 @@ int cgs_render_points(int P, const float* points /*[P,3]*/, const float* colors 
                       const double* background /*host [3]*/, float* out /*[V,height,width,3]*/, int* kept /*[V]*/,
                       void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Ellipsoid mesh of the splats (GaussianCurveModel.draw_ellipsoids, the reference's scene/gaussian_curve_model.py:634-709:
+ * one Open3D sphere per splat, scaled, rotated, moved, painted, merged and written with write_triangle_mesh).  The kernels
+ * write the binary little-endian body of the PLY file: every splat contributes V0 vertex records of 27 bytes (double x,
+ * y, z; uchar red, green, blue) and F0 face records of 13 bytes (uchar 3; int a, b, c).  At resolution r the sphere has
+ * V0 = 2 + 2 r (r - 1) vertices and F0 = 4 r (r - 1) triangles (182 and 360 at r = 10).
+ *
+ * cgs_ellipsoid_mesh_body_bytes returns the body size of P splats (vertex_bytes + face_bytes, each stored if not NULL),
+ * or -1 for P < 0, resolution outside [2, 1024], or P * V0 > 2^31 (a vertex index would not fit in an int).
+ *
+ * cgs_ellipsoid_mesh_vertices writes the vertex records of splats [first, first + count) to `out`: xyz [P,3], rot [P,4]
+ * (w, x, y, z, used as given), scale [P,3] and rgb [P,3] are float32 device arrays indexed by the absolute splat
+ * number; unit_vertices [V0,3] is the float64 sphere template with its radius applied.  Vertex k of splat i, in float64
+ * without FMA contraction: p_j = unit_vertices[k][j] * (double)scale[i][j]; R = Eigen's toRotationMatrix of the quaternion;
+ * every row ((r0*p0 + r1*p1) + r2*p2) + (double)xyz[i][j].  Colour: uint8(round(min(1, max(0, c)) * 255)) (half away
+ * from zero; NaN gives 0).  Record r of the chunk (r = (i - first) * V0 + k) starts at byte 27 r of `out`.
+ *
+ * cgs_ellipsoid_mesh_faces writes the face records of splats [first, first + count): record (i - first) * F0 + k holds
+ * template_faces[k] + i * V0, at byte 13 ((i - first) * F0 + k).
+ *
+ * Both: `out` is 16-byte aligned device memory of the chunk size rounded up to a multiple of 16 bytes; every 16-byte
+ * word of it is written, the padding after the last record with zeros.  The bytes do not depend on the chunking.
+ * count = 0 is a no-op; negative sizes, (first + count) * V0 > 2^31, a misaligned `out` and NULL pointers are
+ * CGS_ERR_INVALID_ARGUMENT, rejected before anything is launched.
+ * ------------------------------------------------------------------------------------------------ */
+int64_t cgs_ellipsoid_mesh_body_bytes(int P, int resolution, int64_t* vertex_bytes, int64_t* face_bytes);
+int cgs_ellipsoid_mesh_vertices(int first, int count, const float* xyz /*[P,3]*/, const float* rot /*[P,4] wxyz*/,
+                                const float* scale /*[P,3]*/, const float* rgb /*[P,3]*/, int V0,
+                                const double* unit_vertices /*[V0,3]*/, void* out, void* stream);
+int cgs_ellipsoid_mesh_faces(int first, int count, int V0, int F0, const int* template_faces /*[F0,3]*/, void* out,
+                             void* stream);
+
 #ifdef __cplusplus
 }
 #endif
