@@ -92,6 +92,10 @@ SIGNATURES = {
     "cgs_ellipsoid_mesh_body_bytes": (_i64, [_i, _i, C.POINTER(_i64), C.POINTER(_i64)]),
     "cgs_ellipsoid_mesh_vertices": (_i, [_i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
     "cgs_ellipsoid_mesh_faces": (_i, [_i, _i, _i, _i, _vp, _vp, _vp]),
+    "cgs_curve_straightness": (_i, [_i, _vp, _vp, _i, C.c_double, C.c_double, _vp, _vp, _vp, _vp]),
+    "cgs_segment_merge_workspace_bytes": (C.c_size_t, [_i]),
+    "cgs_segment_merge_labels": (_i, [_i, _vp, C.c_double, C.c_double, _vp, _vp, _vp, _vp]),
+    "cgs_pair_consensus_fit": (_i, [_i, _vp, _i, _vp, _i, C.c_double, C.c_double, _vp, _vp, _vp, _vp, _vp]),
     "cgs_sample_curves_forward": (_i, [_i, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp]),
     "cgs_sample_curves_backward": (_i, [_i, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "cgs_splat_attrs_forward": (_i, [_i, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -1559,4 +1559,77 @@ int cgs_ellipsoid_mesh_faces(int first, int count, int V0, int F0, const int* te
     return CGS_OK;
 }
 
+int cgs_curve_straightness(int B, const float* curve_points, const uint8_t* is_bezier, int sample_num, double threshold,
+                           double threshold_max, double* mean_dist, double* max_dist, uint8_t* straight, void* stream_) {
+    if (B < 0 || B > (1 << 24) || sample_num < 2 || sample_num > CGS_CURVE_FIT_MAX_SAMPLES) {
+        set_error("cgs_curve_straightness: invalid argument (B=%d, sample_num=%d, need 2 <= sample_num <= %d)", B, sample_num,
+                  CGS_CURVE_FIT_MAX_SAMPLES);
+        return CGS_ERR_INVALID_ARGUMENT;
+    }
+    if (threshold != threshold || threshold_max != threshold_max) {
+        set_error("cgs_curve_straightness: invalid argument (a threshold is NaN)");
+        return CGS_ERR_INVALID_ARGUMENT;
+    }
+    if (B == 0) return CGS_OK;
+    if (!curve_points || !is_bezier || !mean_dist || !max_dist || !straight) {
+        set_error("cgs_curve_straightness: invalid argument (NULL pointer)");
+        return CGS_ERR_INVALID_ARGUMENT;
+    }
+    launch_curve_straightness((hipStream_t)stream_, B, curve_points, is_bezier, sample_num, threshold, threshold_max,
+                              mean_dist, max_dist, straight);
+    if (!check_launch("curve_straightness", false, (hipStream_t)stream_)) return CGS_ERR_HIP;
+    return CGS_OK;
+}
+
+size_t cgs_segment_merge_workspace_bytes(int n) { return segment_merge_workspace_bytes(n); }
+
+int cgs_segment_merge_labels(int n, const float* seg, double distance_threshold, double similarity_threshold,
+                             void* workspace, int* labels, int* n_components, void* stream_) {
+    if (n < 0 || n > CGS_SEGMENT_MERGE_MAX) {
+        set_error("cgs_segment_merge_labels: invalid argument (n=%d, need 0 <= n <= %d)", n, CGS_SEGMENT_MERGE_MAX);
+        return CGS_ERR_INVALID_ARGUMENT;
+    }
+    if (distance_threshold != distance_threshold || similarity_threshold != similarity_threshold) {
+        set_error("cgs_segment_merge_labels: invalid argument (a threshold is NaN)");
+        return CGS_ERR_INVALID_ARGUMENT;
+    }
+    if (!n_components || (n > 0 && (!seg || !workspace || !labels))) {
+        set_error("cgs_segment_merge_labels: invalid argument (NULL pointer)");
+        return CGS_ERR_INVALID_ARGUMENT;
+    }
+    if (n == 0) {
+        if (hipMemsetAsync(n_components, 0, sizeof(int), (hipStream_t)stream_) != hipSuccess) {
+            set_error("cgs_segment_merge_labels: hipMemsetAsync failed");
+            return CGS_ERR_HIP;
+        }
+        return CGS_OK;
+    }
+    launch_segment_merge_labels((hipStream_t)stream_, n, seg, distance_threshold, similarity_threshold, workspace, labels,
+                                n_components);
+    if (!check_launch("segment_merge_labels", false, (hipStream_t)stream_)) return CGS_ERR_HIP;
+    return CGS_OK;
+}
+
+int cgs_pair_consensus_fit(int B, const float* curve_points, int K, const int* pairs, int sample_num, double ransac_thresh,
+                           double error_threshold, float* ctrl, double* rmse, int* inliers, uint8_t* ok, void* stream_) {
+    if (B < 0 || K < 0 || B > (1 << 24) || K > (1 << 24) || sample_num < 2 || sample_num > CGS_CURVE_FIT_MAX_SAMPLES) {
+        set_error("cgs_pair_consensus_fit: invalid argument (B=%d, K=%d, sample_num=%d, need 2 <= sample_num <= %d)", B, K,
+                  sample_num, CGS_CURVE_FIT_MAX_SAMPLES);
+        return CGS_ERR_INVALID_ARGUMENT;
+    }
+    if (ransac_thresh != ransac_thresh || error_threshold != error_threshold) {
+        set_error("cgs_pair_consensus_fit: invalid argument (a threshold is NaN)");
+        return CGS_ERR_INVALID_ARGUMENT;
+    }
+    if (K == 0) return CGS_OK;
+    if (B == 0 || !curve_points || !pairs || !ctrl || !rmse || !inliers || !ok) {
+        set_error("cgs_pair_consensus_fit: invalid argument (NULL pointer or pairs without curves, B=%d)", B);
+        return CGS_ERR_INVALID_ARGUMENT;
+    }
+    launch_pair_consensus_fit((hipStream_t)stream_, K, curve_points, pairs, sample_num, ransac_thresh, error_threshold, ctrl,
+                              rmse, inliers, ok);
+    if (!check_launch("pair_consensus_fit", false, (hipStream_t)stream_)) return CGS_ERR_HIP;
+    return CGS_OK;
+}
+
 }  // extern "C"

@@ -180,4 +180,13 @@ void launch_ellipsoid_faces(hipStream_t s, int first, int count, int V0, int F0,
 void launch_densification_stats(hipStream_t s, long long P, const int* radii, const float* grad, long long stride,
                                 float* max_radii, float* accum, float* denom, const unsigned int* skip_flag);
 
+// curve_fit.hip
+void launch_curve_straightness(hipStream_t s, int B, const float* cp, const uint8_t* is_bezier, int sample_num,
+                               double thr, double thr_max, double* mean_dist, double* max_dist, uint8_t* straight);
+size_t segment_merge_workspace_bytes(int n);
+void launch_segment_merge_labels(hipStream_t s, int n, const float* seg, double dist_thr, double sim_thr, void* workspace,
+                                 int* labels, int* n_components);
+void launch_pair_consensus_fit(hipStream_t s, int K, const float* cp, const int* pairs, int sample_num, double ransac_thr,
+                               double err_thr, float* ctrl, double* rmse, int* inliers, uint8_t* ok);
+
 }  // namespace cgs

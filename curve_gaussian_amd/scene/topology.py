@@ -313,6 +313,18 @@ def mask_trim_split(g, mask_threshold):
 # Two third-party pieces of the reference are absent from this image and restated: skimage's ransac(LineModelND) (the reference
 # calls it unseeded: its result is random; here a SEEDED sampler with the same model, residual and trial count) and
 # scipy.optimize.curve_fit on a model that is linear in its 12 parameters (= its linear least-squares solution).
+# backend="gpu" runs the three data-parallel parts (the per-curve straightness test, the pairwise segment predicate with its
+# connected components, the per-pair line consensus and Bezier fit) in the kernels of ops/curve_fit.py, in float64; the greedy
+# pairing, the per-component end points and the model surgery are the same code for both back ends.  Its line consensus is
+# exhaustive over all two-point lines instead of 1000 random trials, so it needs no seed.
+TOPOLOGY_BACKENDS = ("host", "gpu")
+
+
+def _check_backend(backend):
+    if backend not in TOPOLOGY_BACKENDS:
+        raise ValueError(f"unknown topology backend {backend!r}: expected one of {TOPOLOGY_BACKENDS}")
+
+
 def get_curve_gaussians(g, t):
     """:70-79 -- curve points at parameters t ([n,1,1]) -> [n,B,3]; straight segments on their chord."""
     cp = g._curve_points
@@ -348,11 +360,8 @@ def is_curve_straight(g, sample_points, threshold=0.002, threshold_max=0.004):
     return bool((np.mean(d) < threshold) & (d.max() < threshold_max)), start, end
 
 
-def fit_curve_to_line(g, threshold=0.002, threshold_max=0.004, sample_num=100):
-    """:597-621 -- Bezier curves whose 100 samples lie on a segment become straight segments (is_bezier = False).  Like the
-    reference the control points themselves are NOT moved (its `new_curve_points[selected_mask][:, 0] = ...` assigns into a
-    copy made by the boolean index): the segment is the chord P0-P3 from then on, and the curve-point group's Adam moments
-    restart from zero (replace_tensor_to_optimizer)."""
+def _straight_curves_host(g, threshold, threshold_max, sample_num):
+    """is_curve_straight on the samples of every Bezier curve, one curve at a time -> bool [B] (CPU)."""
     dev = g._curve_points.device
     t = torch.linspace(0, 1, sample_num, device=dev)[:, None, None]
     with torch.no_grad():
@@ -364,6 +373,22 @@ def fit_curve_to_line(g, threshold=0.002, threshold_max=0.004, sample_num=100):
             continue
         ok, _start, _end = is_curve_straight(g, samples[i], threshold, threshold_max)
         selected[i] = ok
+    return selected
+
+
+def fit_curve_to_line(g, threshold=0.002, threshold_max=0.004, sample_num=100, backend="host"):
+    """:597-621 -- Bezier curves whose 100 samples lie on a segment become straight segments (is_bezier = False).  Like the
+    reference the control points themselves are NOT moved (its `new_curve_points[selected_mask][:, 0] = ...` assigns into a
+    copy made by the boolean index): the segment is the chord P0-P3 from then on, and the curve-point group's Adam moments
+    restart from zero (replace_tensor_to_optimizer).  backend "gpu": the test of every curve in one kernel launch
+    (ops.curve_fit.curve_straightness) instead of the per-curve loop."""
+    _check_backend(backend)
+    dev = g._curve_points.device
+    if backend == "gpu":
+        from ..ops.curve_fit import curve_straightness
+        selected = curve_straightness(g._curve_points.detach(), g.is_bezier, threshold, threshold_max, sample_num)[2]
+    else:
+        selected = _straight_curves_host(g, threshold, threshold_max, sample_num)
     if bool(selected.any()):
         new_is_bezier = g.is_bezier.clone()
         new_is_bezier[selected.to(dev)] = False
@@ -458,13 +483,43 @@ def _bezier_fit(xyz, error_threshold=0.02):
     return None if rmse > error_threshold else P.reshape(-1)
 
 
-def merge_curves(g, distance_threshold=0.02, similarity_threshold=0.97, sample_num=100, ransac_thresh=0.005, seed=0):
+def _fit_pair_host(pts, distance_threshold, ransac_thresh, rng):
+    """The 200 samples of a pair of curves -> the 12 control-point coordinates of the one Bezier through them, or None."""
+    import numpy as np
+    try:
+        inl = _ransac_line(pts, ransac_thresh, 1000, rng)
+        line_eps = _line_fitting(pts[inl])
+    except Exception:   # noqa: BLE001 -- like the reference: a pair without a line is left alone
+        return None
+    main = line_eps[3:] - line_eps[:3]
+    main = main / np.linalg.norm(main)
+    mean_pt = (line_eps[3:] + line_eps[:3]) / 2
+    pts = pts[np.argsort((pts - mean_pt) @ main)]
+    return _bezier_fit(pts, error_threshold=distance_threshold)
+
+
+def _segment_labels_host(seg, distance_threshold, similarity_threshold):
+    """Component label of every straight segment [n,6] (numpy)."""
+    import numpy as np
+    from scipy.sparse.csgraph import connected_components
+    dmat = _pairwise_segment_distances(seg)
+    sim = np.abs(_pairwise_cosine_similarity(seg))     # (:557)
+    return connected_components((dmat <= distance_threshold) & (sim >= similarity_threshold))[1]
+
+
+def merge_curves(g, distance_threshold=0.02, similarity_threshold=0.97, sample_num=100, ransac_thresh=0.005, seed=0,
+                 backend="host"):
     """:459-595 -- (1) Bezier curves whose end points lie within 2 * distance_threshold and whose end tangents are parallel
     (|cos| > similarity_threshold) are paired greedily (most parallel partner first), their 200 samples ordered along the RANSAC
     line of the pair and refitted by ONE cubic Bezier if its RMSE stays below distance_threshold; (2) straight segments that are
     close and parallel are merged per connected component into the segment spanning their samples.  Merged curves are pruned, the
-    new ones appended with the mean opacity / width of their sources.  -> number of curves removed."""
+    new ones appended with the mean opacity / width of their sources.  -> number of curves removed.
+    backend "gpu": the fit of all pairs in one launch (ops.curve_fit.pair_consensus_fit: the line with the most samples within
+    ransac_thresh among ALL two-point lines, `seed` unused) and the segment predicate with its components in
+    ops.curve_fit.segment_merge_labels; the pairing, the per-component end points (linear in the number of merged lines) and the
+    model surgery are shared with "host"."""
     import numpy as np
+    _check_backend(backend)
     dev = g._curve_points.device
     rng = np.random.default_rng(seed)
     with torch.no_grad():
@@ -495,33 +550,37 @@ def merge_curves(g, distance_threshold=0.02, similarity_threshold=0.97, sample_n
             best_j = max(nb, key=lambda j: confidence[i, j])
             merged.update((i, best_j))
             pairs.append([i, best_j])
-        for comp in pairs:
-            pts = np.concatenate([samples_h[i] for i in comp], axis=0)
-            try:
-                inl = _ransac_line(pts, ransac_thresh, 1000, rng)
-                line_eps = _line_fitting(pts[inl])
-            except Exception:   # noqa: BLE001 -- like the reference: a pair without a line is left alone
-                continue
-            main = line_eps[3:] - line_eps[:3]
-            main = main / np.linalg.norm(main)
-            mean_pt = (line_eps[3:] + line_eps[:3]) / 2
-            pts = pts[np.argsort((pts - mean_pt) @ main)]
-            out = _bezier_fit(pts, error_threshold=distance_threshold)
-            if out is not None:
+        if backend == "gpu" and pairs:
+            from ..ops.curve_fit import pair_consensus_fit
+            ctrl, _rmse, _inl, ok = pair_consensus_fit(cp, torch.tensor(pairs, dtype=torch.int32, device=dev), sample_num,
+                                                       ransac_thresh, distance_threshold)
+            ctrl, ok = ctrl.cpu(), ok.cpu().numpy()
+            fits = [ctrl[k] if ok[k] else None for k in range(len(pairs))]
+        else:
+            fits = []
+            for comp in pairs:
+                out = _fit_pair_host(np.concatenate([samples_h[i] for i in comp], axis=0), distance_threshold, ransac_thresh, rng)
+                fits.append(None if out is None else torch.from_numpy(out.reshape(4, 3)).float())
+        for comp, fit in zip(pairs, fits):
+            if fit is not None:
                 merge_mask[comp] = True
-                new["cp"].append(torch.from_numpy(out.reshape(4, 3)).float())
+                new["cp"].append(fit)
                 new["op"].append(g._opacity.detach()[comp].mean(dim=0, keepdim=True))
                 new["w"].append(g._width.detach()[comp].mean(dim=0, keepdim=True))
                 new["bez"].append(True)
         line_idx = np.nonzero(~is_bez)[0]
         if len(line_idx) > 0:
-            from scipy.sparse.csgraph import connected_components
-            seg = cp.cpu().numpy()[line_idx][:, [0, -1], :].reshape(len(line_idx), 6)
-            dmat = _pairwise_segment_distances(seg)
-            sim = np.abs(_pairwise_cosine_similarity(seg))     # (:557)
-            ncomp, labels = connected_components((dmat <= distance_threshold) & (sim >= similarity_threshold))
-            for c in range(ncomp):
-                members = np.nonzero(labels == c)[0]
+            if backend == "gpu":
+                from ..ops.curve_fit import segment_merge_labels
+                seg_d = cp[torch.from_numpy(line_idx).to(dev)][:, [0, -1], :].reshape(len(line_idx), 6)
+                labels = segment_merge_labels(seg_d, distance_threshold, similarity_threshold)[0].cpu().numpy()
+            else:
+                seg = cp.cpu().numpy()[line_idx][:, [0, -1], :].reshape(len(line_idx), 6)
+                labels = _segment_labels_host(seg, distance_threshold, similarity_threshold)
+            # components in the order of their first member (scipy numbers them so; the kernel's label IS the first member)
+            order = np.argsort(labels, kind="stable")
+            bounds = np.nonzero(np.diff(labels[order]))[0] + 1
+            for members in np.split(order, bounds):
                 if len(members) == 1:
                     continue
                 comp = line_idx[members]

@@ -2,7 +2,7 @@
 ``parametric_edges.json``.
 
     python -m curve_gaussian_amd.train -s SCAN -m OUT [--iterations N] [--backend graphed|direct|autograd|torch]
-                                       [--draw_snapshots]
+                                       [--draw_snapshots] [--topology_backend host|gpu]
 
 The loop keeps the reference's order.  Per iteration: learning rate, SH degree every 1000 iterations, a random view without
 replacement, render + losses + every regulariser + backward (one ``TrainStep`` call), densification statistics before
@@ -177,7 +177,7 @@ def _export(gaussians, dataset, opt):
 
 def training(dataset, opt, testing_iterations, saving_iterations, checkpoint_iterations, checkpoint=None, backend="graphed",
              seed=0, device="cuda", quiet=False, scene=None, step=None, report=None, save_ply=None, save_checkpoint=None,
-             export=None, draw=False):
+             export=None, draw=False, topology_backend="host"):
     """train.py:38-248.  Returns {"events": [(iteration, event, n_curves_after)] for every edit, report, save, checkpoint and
     the export, "losses": {iteration: loss} (the first iteration and every iteration run with a deferred update),
     "first_iter", "scene", "gaussians"}.
@@ -187,7 +187,12 @@ def training(dataset, opt, testing_iterations, saving_iterations, checkpoint_ite
     testing_iterations, scene, bg)`` [evaluation.training_report], ``save_ply(gaussians, model_path, iteration)``,
     ``save_checkpoint(obj, path)`` [torch.save], ``export(gaussians, dataset, opt)`` [write_parametric_edges].  ``draw``: after
     every snapshot, ``gaussians.draw_curve(dir, iteration)`` and ``gaussians.draw_ellipsoids(dir, iteration)`` into the
-    snapshot's directory (train.py:215-220); no event is logged for them."""
+    snapshot's directory (train.py:215-220); no event is logged for them.  ``topology_backend``: "host" runs fit_curve_to_line
+    and merge_curves in numpy like the reference, "gpu" in the kernels of ops/curve_fit.py (scene/topology.py); the schedule and
+    the event log are the same."""
+    from .scene.topology import _check_backend
+    _check_backend(topology_backend)
+    topo = {} if topology_backend == "host" else {"backend": topology_backend}
     say = (lambda *a: None) if quiet else print
     os.makedirs(dataset.model_path, exist_ok=True)
     scene, gaussians = scene if scene is not None else make_scene(dataset, opt, device)
@@ -248,9 +253,9 @@ def training(dataset, opt, testing_iterations, saving_iterations, checkpoint_ite
             gaussians.curve_split_curvature(opt.threshold_angle, opt.threshold_angle_skip)
             log(iteration, "curve_split_curvature")
         if (iteration % 1000 == 0 and iteration > opt.densify_until_iter) or iteration == opt.iterations:   # :209-211
-            gaussians.fit_curve_to_line(opt.threshold_line, opt.threshold_max_line)
+            gaussians.fit_curve_to_line(opt.threshold_line, opt.threshold_max_line, **topo)
             log(iteration, "fit_curve_to_line")
-            gaussians.merge_curves(opt.distance_threshold, opt.similarity_threshold)
+            gaussians.merge_curves(opt.distance_threshold, opt.similarity_threshold, **topo)
             log(iteration, "merge_curves")
         if iteration in saving_iterations:                                          # :213-229
             say(f"\n[ITER {iteration}] Saving Gaussians")
@@ -305,6 +310,8 @@ def build_parser():
     p.add_argument("--start_checkpoint", type=str, default=None)
     p.add_argument("--backend", choices=BACKENDS, default="graphed")
     p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--topology_backend", choices=("host", "gpu"), default="host",
+                   help="where fit_curve_to_line / merge_curves compute: numpy on the host like the reference, or HIP kernels")
     p.add_argument("--draw_snapshots", action="store_true",
                    help="write curve_step{N}.ply and ellipsoids_step{N}.ply next to every snapshot")
     return p
@@ -329,7 +336,8 @@ def main(argv=None):
         raise SystemExit("train: -m / --model_path is required")
     print("Optimizing " + dataset.model_path)
     training(dataset, opt, args.test_iterations, args.save_iterations, args.checkpoint_iterations, args.start_checkpoint,
-             backend=args.backend, seed=args.seed, quiet=args.quiet, draw=args.draw_snapshots)
+             backend=args.backend, seed=args.seed, quiet=args.quiet, draw=args.draw_snapshots,
+             topology_backend=args.topology_backend)
     print("\nTraining complete.")
 
 

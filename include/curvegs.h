@@ -631,6 +631,49 @@ int cgs_ellipsoid_mesh_vertices(int first, int count, const float* xyz /*[P,3]*/
 int cgs_ellipsoid_mesh_faces(int first, int count, int V0, int F0, const int* template_faces /*[F0,3]*/, void* out,
                              void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Line fitting and merging (GaussianCurveModel.fit_curve_to_line / merge_curves, the reference's
+ * scene/gaussian_curve_model.py:459-632 over edge_extraction/fitting.py and merging.py): the data-parallel parts of the
+ * two edits.  Inputs are the model's float32 tensors, all arithmetic is float64, every result is deterministic (no
+ * floating-point atomics, reductions in a fixed order).  Sizes of 0 are no-ops; negative sizes, sizes above the limits
+ * below, thresholds that are NaN and NULL pointers are CGS_ERR_INVALID_ARGUMENT, rejected before anything is launched.
+ *
+ * cgs_curve_straightness (is_curve_straight for every curve): the sample_num cubic Bernstein samples of curve b at
+ * t = i / (sample_num - 1), their mean and 3x3 covariance, the unit eigenvector of its largest eigenvalue, the
+ * projections t_i on it; mean_dist[b] / max_dist[b] = mean / maximum distance of the samples to the foot
+ * mean + clip(t_i, min t, max t) * direction; straight[b] = is_bezier[b] && mean_dist < threshold && max_dist <
+ * threshold_max.  Samples that all coincide give distances 0.  2 <= sample_num <= CGS_CURVE_FIT_MAX_SAMPLES.
+ *
+ * cgs_segment_merge_labels (merge_curves, straight segments): segments a < b are joined when
+ * |cos(dir a, dir b)| >= similarity_threshold and min(dist(b.start, a), dist(b.end, a)) <= distance_threshold, the
+ * distance of a point to segment a with its foot clipped to the segment; a segment of zero length is joined to nothing.
+ * labels[i] = the smallest segment index of i's connected component, *n_components (device) = the number of components.
+ * n <= CGS_SEGMENT_MERGE_MAX.  workspace: cgs_segment_merge_workspace_bytes(n) bytes of device memory (an n x
+ * ceil(n / 64) bit matrix; no initialisation needed).
+ *
+ * cgs_pair_consensus_fit (merge_curves, Bezier pairs): for pair k the N = 2 sample_num samples of curves pairs[k][0] and
+ * pairs[k][1] (in that order) are (1) searched exhaustively for the two-point line with the most points closer than
+ * ransac_thresh (then the smallest sum of squared residuals, then the smallest (i, j); point pairs at distance 0 are no
+ * candidates), (2) the inliers fitted by their centroid, principal direction and the extent of their projections, (3) all
+ * N points ordered by their projection on that segment's direction about its midpoint (ties by index), (4) fitted by the
+ * least-squares cubic Bezier at t = linspace(0, 1, N): ctrl[k] its control points, rmse[k] its root-mean-square error,
+ * inliers[k] the winning count, ok[k] = rmse <= error_threshold.  A pair without a line (best count < 2) gets ok = 0,
+ * rmse = 0 and zero control points.  Curve indices must lie in [0, B) (not checked: they are device data).
+ * 2 <= sample_num <= CGS_CURVE_FIT_MAX_SAMPLES.
+ * ------------------------------------------------------------------------------------------------ */
+#define CGS_CURVE_FIT_MAX_SAMPLES 256
+#define CGS_SEGMENT_MERGE_MAX 12288
+int cgs_curve_straightness(int B, const float* curve_points /*[B,4,3]*/, const uint8_t* is_bezier /*[B]*/, int sample_num,
+                           double threshold, double threshold_max, double* mean_dist /*[B]*/, double* max_dist /*[B]*/,
+                           uint8_t* straight /*[B]*/, void* stream);
+size_t cgs_segment_merge_workspace_bytes(int n);
+int cgs_segment_merge_labels(int n, const float* seg /*[n,6]: start, end*/, double distance_threshold,
+                             double similarity_threshold, void* workspace, int* labels /*[n]*/,
+                             int* n_components /*device, [1]*/, void* stream);
+int cgs_pair_consensus_fit(int B, const float* curve_points /*[B,4,3]*/, int K, const int* pairs /*[K,2]*/, int sample_num,
+                           double ransac_thresh, double error_threshold, float* ctrl /*[K,4,3]*/, double* rmse /*[K]*/,
+                           int* inliers /*[K]*/, uint8_t* ok /*[K]*/, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
