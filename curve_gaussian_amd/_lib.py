@@ -85,6 +85,8 @@ SIGNATURES = {
     "cgs_edge_visibility": (_i, [_i, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _vp, _i, _vp, _vp]),
     "cgs_view_metrics_workspace_bytes": (C.c_size_t, [_i]),
     "cgs_view_metrics": (_i, [_i, _vp, _vp, _vp, _vp, _vp]),
+    "cgs_report_panels_workspace_bytes": (C.c_size_t, [_i]),
+    "cgs_report_panels": (_i, [_i, _vp, _vp, _vp, _vp]),
     "cgs_densification_stats": (_i, [_i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "cgs_project_points": (_i, [_i, _vp, _i, _vp, _vp, _i, _i, _vp, _vp]),
     "cgs_render_points_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i]),
@@ -108,6 +110,15 @@ class MetricView(C.Structure):
     """cgs_metric_view (include/curvegs.h)."""
     _fields_ = [("image", _vp), ("gt", _vp), ("channels", _i), ("height", _i), ("width", _i), ("x0", _i)]
 
+
+class ReportView(C.Structure):
+    """cgs_report_view (include/curvegs.h)."""
+    _fields_ = [("render", _vp), ("gt", _vp), ("depth", _vp), ("rend_dir", _vp), ("rend_alpha", _vp), ("gt_channels", _i),
+                ("height", _i), ("width", _i), ("written", C.c_uint), ("out_offset", C.c_size_t)]
+
+
+REPORT_MAX_VIEWS = 32   # CGS_REPORT_MAX_VIEWS
+REPORT_PANELS = ("render", "ground_truth", "depth", "rend_dir", "rend_alpha")   # panel order of cgs_report_panels
 
 _lib = None
 

@@ -1446,6 +1446,44 @@ int cgs_view_metrics(int n_views, const cgs_metric_view* views, void* workspace,
     return CGS_OK;
 }
 
+size_t cgs_report_panels_workspace_bytes(int n_views) { return report_panels_workspace_bytes(n_views); }
+
+int cgs_report_panels(int n_views, cgs_report_view* views, void* workspace, unsigned char* out, void* stream_) {
+    if (n_views < 0 || n_views > CGS_REPORT_MAX_VIEWS) {
+        set_error("cgs_report_panels: invalid argument (n_views=%d, at most %d per call)", n_views, CGS_REPORT_MAX_VIEWS);
+        return CGS_ERR_INVALID_ARGUMENT;
+    }
+    if (n_views == 0) return CGS_OK;
+    if (!views || !workspace || !out) {
+        set_error("cgs_report_panels: invalid argument (NULL pointer)");
+        return CGS_ERR_INVALID_ARGUMENT;
+    }
+    for (int v = 0; v < n_views; v++) {
+        const cgs_report_view& d = views[v];
+        if (d.height <= 0 || d.width <= 0 || (d.gt && d.gt_channels != 1 && d.gt_channels != 3)) {
+            set_error("cgs_report_panels: invalid argument (view %d: gt_channels=%d, height=%d, width=%d)", v, d.gt_channels,
+                      d.height, d.width);
+            return CGS_ERR_INVALID_ARGUMENT;
+        }
+        const size_t bytes = (size_t)CGS_REPORT_PANELS * 3 * (size_t)d.height * (size_t)d.width;
+        for (int u = 0; u < v; u++) {
+            const size_t other = (size_t)CGS_REPORT_PANELS * 3 * (size_t)views[u].height * (size_t)views[u].width;
+            if (d.out_offset < views[u].out_offset + other && views[u].out_offset < d.out_offset + bytes) {
+                set_error("cgs_report_panels: invalid argument (the output ranges of views %d and %d overlap)", u, v);
+                return CGS_ERR_INVALID_ARGUMENT;
+            }
+        }
+    }
+    for (int v = 0; v < n_views; v++) {
+        cgs_report_view& d = views[v];
+        d.written = (d.render ? 1u : 0u) | (d.gt ? 2u : 0u) | (d.depth ? 4u : 0u) | (d.rend_dir ? 8u : 0u) |
+                    (d.rend_alpha ? 16u : 0u);
+    }
+    launch_report_panels((hipStream_t)stream_, n_views, views, workspace, out);
+    if (!check_launch("report_panels", false, (hipStream_t)stream_)) return CGS_ERR_HIP;
+    return CGS_OK;
+}
+
 int cgs_project_points(int P, const float* points, int V, const double* intr, const double* w2c, int height, int width,
                        double* uv_out, void* stream_) {
     if (P < 0 || V < 0 || (long long)P * V > (1LL << 40)) {

@@ -161,6 +161,11 @@ size_t view_metrics_workspace_bytes(int n_views);
 hipError_t launch_view_metrics(hipStream_t s, int n_views, const cgs_metric_view* views_host, void* workspace,
                                double* sums, double* means);
 
+// report.hip
+size_t report_panels_workspace_bytes(int n_views);
+void launch_report_panels(hipStream_t s, int n_views, const cgs_report_view* views_host, void* workspace,
+                          unsigned char* out);
+
 // novel_view.hip
 void launch_project_points(hipStream_t s, int P, const float* points, int V, const double* intr, const double* w2c,
                            int height, int width, double* uv);

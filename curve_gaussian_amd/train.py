@@ -2,7 +2,7 @@
 ``parametric_edges.json``.
 
     python -m curve_gaussian_amd.train -s SCAN -m OUT [--iterations N] [--backend graphed|direct|autograd|torch]
-                                       [--draw_snapshots] [--topology_backend host|gpu]
+                                       [--draw_snapshots] [--topology_backend host|gpu] [--report_dir DIR]
 
 The loop keeps the reference's order.  Per iteration: learning rate, SH degree every 1000 iterations, a random view without
 replacement, render + losses + every regulariser + backward (one ``TrainStep`` call), densification statistics before
@@ -17,7 +17,12 @@ straight through, and with ``backend="graphed"`` it is one graph replay.  An edi
 that group without gradient, and torch.optim.Adam then skips it; the flat one-launch Adam skips the whole step then
 (``TrainStep.apply_update``).
 
-Out of scope: tensorboard, the network GUI, view-parallel runs, sparse_adam."""
+With ``report_writer`` (``--report_dir DIR``: an ``evaluation.ReportDirWriter``) the held-out report also writes the
+reference's tensorboard summaries (:323-373) -- the report's scalars and, for the first five views of each config, the
+render, ground truth, depth, direction and alpha panels -- as ``DIR/scalars.jsonl`` and
+``DIR/images/iter_{N:06d}/{config}_view_{name}__{panel}.png``.  Without it nothing is written and the run is what it was.
+
+Out of scope: the network GUI, view-parallel runs, sparse_adam."""
 import argparse
 import os
 import sys
@@ -154,10 +159,10 @@ def make_step(backend, gaussians, cameras, opt, seed=0):
     return TrainStep(gaussians, cameras, gts, fused=backend != "torch", direct=backend == "direct", **kw)
 
 
-def _report(iteration, testing_iterations, scene, bg):
+def _report(iteration, testing_iterations, scene, bg, writer=None):
     from . import evaluation as E
     from .gaussian_renderer import PipelineParams, render
-    return E.training_report(None, iteration, None, None, None, 0.0, testing_iterations, scene, render,
+    return E.training_report(writer, iteration, None, None, None, None, testing_iterations, scene, render,
                              (PipelineParams(), bg), False)
 
 
@@ -177,7 +182,7 @@ def _export(gaussians, dataset, opt):
 
 def training(dataset, opt, testing_iterations, saving_iterations, checkpoint_iterations, checkpoint=None, backend="graphed",
              seed=0, device="cuda", quiet=False, scene=None, step=None, report=None, save_ply=None, save_checkpoint=None,
-             export=None, draw=False, topology_backend="host"):
+             export=None, draw=False, topology_backend="host", report_writer=None):
     """train.py:38-248.  Returns {"events": [(iteration, event, n_curves_after)] for every edit, report, save, checkpoint and
     the export, "losses": {iteration: loss} (the first iteration and every iteration run with a deferred update),
     "first_iter", "scene", "gaussians"}.
@@ -189,7 +194,9 @@ def training(dataset, opt, testing_iterations, saving_iterations, checkpoint_ite
     every snapshot, ``gaussians.draw_curve(dir, iteration)`` and ``gaussians.draw_ellipsoids(dir, iteration)`` into the
     snapshot's directory (train.py:215-220); no event is logged for them.  ``topology_backend``: "host" runs fit_curve_to_line
     and merge_curves in numpy like the reference, "gpu" in the kernels of ops/curve_fit.py (scene/topology.py); the schedule and
-    the event log are the same."""
+    the event log are the same.  ``report_writer``: a summary writer (``evaluation.ReportDirWriter``, a tensorboard
+    ``SummaryWriter``) handed to the default ``report``, which then writes the reference's scalar and image summaries at the
+    test iterations; None writes nothing.  An injected ``report`` is called as before and never sees it."""
     from .scene.topology import _check_backend
     _check_backend(topology_backend)
     topo = {} if topology_backend == "host" else {"backend": topology_backend}
@@ -205,7 +212,8 @@ def training(dataset, opt, testing_iterations, saving_iterations, checkpoint_ite
     bg = torch.tensor([1, 1, 1] if dataset.white_background else [0, 0, 0], dtype=torch.float32,
                       device=gaussians._curve_points.device)                        # :53-54
     step.bg = bg
-    report = report or _report
+    if report is None:
+        report = _report if report_writer is None else (lambda *a: _report(*a, writer=report_writer))
     save_ply = save_ply or _save_ply
     save_checkpoint = save_checkpoint or torch.save
     export = export or _export
@@ -314,6 +322,9 @@ def build_parser():
                    help="where fit_curve_to_line / merge_curves compute: numpy on the host like the reference, or HIP kernels")
     p.add_argument("--draw_snapshots", action="store_true",
                    help="write curve_step{N}.ply and ellipsoids_step{N}.ply next to every snapshot")
+    p.add_argument("--report_dir", default=None,
+                   help="write the report's summaries here at every test iteration: scalars.jsonl and, per view, the render, "
+                        "ground-truth, depth, direction and alpha panels as images/iter_{N}/*.png")
     return p
 
 
@@ -335,9 +346,13 @@ def main(argv=None):
     if not dataset.model_path:
         raise SystemExit("train: -m / --model_path is required")
     print("Optimizing " + dataset.model_path)
+    writer = None
+    if args.report_dir:
+        from .evaluation import ReportDirWriter
+        writer = ReportDirWriter(args.report_dir)
     training(dataset, opt, args.test_iterations, args.save_iterations, args.checkpoint_iterations, args.start_checkpoint,
              backend=args.backend, seed=args.seed, quiet=args.quiet, draw=args.draw_snapshots,
-             topology_backend=args.topology_backend)
+             topology_backend=args.topology_backend, report_writer=writer)
     print("\nTraining complete.")
 
 

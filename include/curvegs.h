@@ -551,6 +551,53 @@ int cgs_view_metrics(int n_views, const cgs_metric_view* views /*host, [n_views]
                      double* sums /*[n_views,2]*/, double* means /*[n_views,2] or NULL*/, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Image summaries of the training report (reference train.py:346-364): for each of n_views views, five 8-bit RGB panels
+ * packed as uint8 [5, height, width, 3] at out + out_offset, in the order
+ *   0 render, 1 ground_truth, 2 depth, 3 rend_dir, 4 rend_alpha.
+ * Per pixel, in float32 and in this order of operations (no fused multiply-add):
+ *   q(x)          = (uint8) clip(x * 255, 0, 255), truncated; q(NaN) = 0      (what a tensorboard image summary does to a
+ *                   float image)
+ *   render, rend_alpha, ground_truth:  q(clamp(x, 0, 1)), a one-channel value replicated to R, G, B; a gt with
+ *                   gt_channels = 3 gives its channels as R, G, B
+ *   depth:          m = max(0, largest non-NaN pixel of the view),  s = depth / m * 256,
+ *                   i = s >= 255 ? 255 : (s > 0 ? (int)s : 0),  colour = q(turbo[i]) (csrc/turbo_table.h); a view with
+ *                   m = 0 and every pixel whose s is NaN are (0, 0, 0).  PRECONDITION: depth >= 0, which is what the
+ *                   rasterizer's depth map is (a blend of positive view depths over a zero background); a negative pixel
+ *                   is not an error, it takes table entry 0
+ *   rend_dir:       n = v / max(|v|, 1e-12) over the three channels (F.normalize(dim=0)), q(n * 0.5 + 0.5) per channel
+ * Inputs are contiguous float32: render, depth, rend_alpha [1,height,width], rend_dir [3,height,width], gt
+ * [gt_channels,height,width] with gt_channels 1 or 3.  Any of the five may be NULL: that panel's bytes are left untouched
+ * and its bit in `written` stays clear (bit p = panel p; `written` is filled in the caller's host table before the call
+ * returns).  Views may differ in size; their output ranges must not overlap.  16-byte aligned planes are read with
+ * 16-byte loads and 4-byte aligned panels written 12 bytes (four pixels) per lane; anything else takes the element path,
+ * with the same results.
+ * Two launches for all views, nothing else: (1) every view's depth maximum as cgs_report_panels_workspace_bytes(n_views)
+ * bytes of per-workgroup partial maxima in `workspace` -- every slot is rewritten by every call, so the workspace needs
+ * no initialisation, and no atomics are involved; (2) the panels.  The table travels as a kernel argument: no copy, no
+ * host synchronisation, and a stream capture of the call holds everything it needs.  That argument bounds n_views by
+ * CGS_REPORT_MAX_VIEWS per call.  n_views = 0 is a no-op; n_views outside [0, CGS_REPORT_MAX_VIEWS], NULL table /
+ * workspace / out, height or width <= 0, gt_channels other than 1 or 3 with a gt, and overlapping output ranges are
+ * CGS_ERR_INVALID_ARGUMENT, rejected before anything is launched.
+ * ------------------------------------------------------------------------------------------------ */
+#define CGS_REPORT_MAX_VIEWS 32
+#define CGS_REPORT_PANELS 5
+typedef struct cgs_report_view {
+    const float* render;     /* [1,height,width] or NULL */
+    const float* gt;         /* [gt_channels,height,width] or NULL */
+    const float* depth;      /* [1,height,width] or NULL */
+    const float* rend_dir;   /* [3,height,width] or NULL */
+    const float* rend_alpha; /* [1,height,width] or NULL */
+    int gt_channels;         /* 1 or 3 (read only when gt is not NULL) */
+    int height;
+    int width;
+    unsigned int written;    /* out: bit p set when panel p was written */
+    size_t out_offset;       /* byte offset of this view's [5,height,width,3] block in `out` */
+} cgs_report_view;
+size_t cgs_report_panels_workspace_bytes(int n_views);
+int cgs_report_panels(int n_views, cgs_report_view* views /*host, [n_views]*/, void* workspace, unsigned char* out,
+                      void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Densification statistics (reference train.py:184-187, GaussianModel.add_densification_stats): for every splat i < P
  * with radii[i] > 0, in one launch,
  *   max_radii2D[i] = max(max_radii2D[i], (float)radii[i]);
