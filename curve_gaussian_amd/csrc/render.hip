@@ -72,14 +72,6 @@ struct ViewEpilogue {
 // (the kernel is bound by exactly those two: VALU issue and LDS return traffic).  Each wave compacts the staged entries
 // its quadrant accepted into a private list and walks it in groups of 16.
 constexpr int GROUP = 16;
-// What-if builds (profiles/probes/kernel_times.py, profiles/r06_experiments.md): the forward with ONE cost removed -- wrong
-// images on purpose, only the times mean something.  Bits: 1 no pair walk (operands + MFMAs stay), 2 no groups at all (sort,
-// staging and lists stay), 4 walk without the per-pair LDS read of the splat's channels, 8 walk without v_exp, 16 walk without the
-// termination test, 32 fused rank + stage path without the ranking loop, 64 no per-pixel output stores, 128 staging without the
-// quadrant reach test (every mask 15), 256 staging without the record gather, 512 no list building.  0 in every product build.
-#ifndef CGS_WHATIF
-#define CGS_WHATIF 0
-#endif
 // 6 waves per SIMD (80 VGPRs, a dozen spills): 136 us at the natural 104 VGPRs / 4 waves, 124 at 5, 122 at 6, 128 at 7
 #ifndef CGS_FWD3_WAVES
 #define CGS_FWD3_WAVES 6
@@ -97,11 +89,6 @@ constexpr int GROUP = 16;
 // (176 us); with three views in flight the matching footprints let forward and backward workgroups of neighbouring views
 // share CUs evenly: 567 -> 597 Msplats/s.  (A branch-free walk -- eight pairs' exp2 / rcp / colour reads in flight before
 // the sequential recurrence -- was 8 us faster at 5 waves, but needs 32 more live registers: 589 at 6 waves with spills.)
-// What-if builds of the general backward (profiles/r06_experiments.md section 8; 0 in product builds): 1 = no flush (the
-// splat-parallel moment passes), 2 = no recurrences in the walk (exp2 + tests + the store stay), 4 = no combining pass
-#ifndef CGS_BWD3_WHATIF
-#define CGS_BWD3_WHATIF 0
-#endif
 #ifndef CGS_BWD3_WAVES
 #define CGS_BWD3_WAVES 6
 #endif
@@ -186,7 +173,7 @@ __global__ void __launch_bounds__(256, UNIT ? CGS_FWD3_WAVES : CGS_FWD3_WAVES_GE
             const SplatRec* r = rec + id;
             float4 ra = make_float4(0.f, 0.f, 1.f, 0.f), rb = make_float4(1.f, 0.f, 0.f, 0.f), rc = ra;
             float tau2 = -1.f;
-            if (has && !(CGS_WHATIF & 256)) {
+            if (has) {
                 ra = r->a;
                 rb = r->b;
                 if (GEO) rc = r->c;
@@ -199,7 +186,7 @@ __global__ void __launch_bounds__(256, UNIT ? CGS_FWD3_WAVES : CGS_FWD3_WAVES_GE
             uint32_t lost = 0u;
             if (((uint32_t)__builtin_amdgcn_readfirstlane((int)tid) & ~63u) < n) {   // wave-uniform
                 // (depths are positive finite floats -- view-space z > 0.2 -- whose order is the order of their bit patterns)
-                const uint32_t rk[1] = {(CGS_WHATIF & 32) ? tid : rank_loop_f32(reinterpret_cast<const float*>(s_ord), n, __uint_as_float(depth))};
+                const uint32_t rk[1] = {rank_loop_f32(reinterpret_cast<const float*>(s_ord), n, __uint_as_float(depth))};
                 if (has) {
                     float4 sa, sb;
                     stage_splat(ra, rb, sa, sb);
@@ -207,7 +194,7 @@ __global__ void __launch_bounds__(256, UNIT ? CGS_FWD3_WAVES : CGS_FWD3_WAVES_GE
                     s_geo[slot] = sa;
                     s_at[slot] = make_float4(sb.z, sb.w, sb.x, __builtin_amdgcn_logf(sb.y));
                     if (GEO) s_c[GEO ? slot : 0] = UNIT ? make_float4(rc.x, rc.y, rc.z, sb.w) : rc;
-                    const uint32_t qm = (CGS_WHATIF & 128) ? 15u : quadrant_mask(ra, rb, tau2, X0, Y0);
+                    const uint32_t qm = quadrant_mask(ra, rb, tau2, X0, Y0);
                     lost = atomicExch(&s_si[rk[0]], 0x100u | qm);
                     bs.point_list[base + rk[0]] = TAG ? (id | (qm << LIST_TAG_SHIFT)) : id;
                 }
@@ -255,33 +242,33 @@ __global__ void __launch_bounds__(256, UNIT ? CGS_FWD3_WAVES : CGS_FWD3_WAVES_GE
 
     for (int i = 0; i < rounds; i++) {
         if (!prestaged) {   // block-uniform (prestaged: one round, staged above)
-        if (!__syncthreads_or(!wave_done)) break;
-        const int progress = i * BATCH + threadIdx.x;
-        uint32_t qm = 0;
-        if (progress < total) {
-            const uint32_t id = SORT ? s_ord[progress] : point_list[range.x + progress];
-            const SplatRec* r = rec + id;
-            const float4 a = r->a, b = r->b;
-            float4 sa, sb;
-            stage_splat(a, b, sa, sb);
-            s_geo[threadIdx.x + 1] = sa;
-            s_at[threadIdx.x + 1] = make_float4(sb.z, sb.w, sb.x, __builtin_amdgcn_logf(sb.y));   // v_log_f32 = log2
-            // UNIT: all_map[3] == 1 is not read back, its slot carries 1/depth -- one 16-byte read per pair instead of two reads
-            if (GEO) s_c[threadIdx.x + 1] = UNIT ? make_float4(r->c.x, r->c.y, r->c.z, sb.w) : r->c;
-            qm = quadrant_mask(a, b, r->d.z, X0, Y0);   // (0 unless opacity >= 1/255: the log is finite for every listed entry)
-            // UNIT (view entry points): the list entry carries the quadrant mask in its top four bits for the backward of the
-            // same view (LIST_ID_MASK / LIST_TAG_SHIFT, composite.h) -- its staging then needs no reach test.  Entries of
-            // batches this workgroup never stages (every pixel terminated before) lie behind every pixel's cut.
-            if (TAG) const_cast<uint32_t*>(SORT ? bs.point_list : point_list)[range.x + progress] = id | (qm << LIST_TAG_SHIFT);
-        }
+            if (!__syncthreads_or(!wave_done)) break;
+            const int progress = i * BATCH + threadIdx.x;
+            uint32_t qm = 0;
+            if (progress < total) {
+                const uint32_t id = SORT ? s_ord[progress] : point_list[range.x + progress];
+                const SplatRec* r = rec + id;
+                const float4 a = r->a, b = r->b;
+                float4 sa, sb;
+                stage_splat(a, b, sa, sb);
+                s_geo[threadIdx.x + 1] = sa;
+                s_at[threadIdx.x + 1] = make_float4(sb.z, sb.w, sb.x, __builtin_amdgcn_logf(sb.y));   // v_log_f32 = log2
+                // UNIT: all_map[3] == 1 is not read back, its slot carries 1/depth -- one 16-byte read per pair instead of two reads
+                if (GEO) s_c[threadIdx.x + 1] = UNIT ? make_float4(r->c.x, r->c.y, r->c.z, sb.w) : r->c;
+                qm = quadrant_mask(a, b, r->d.z, X0, Y0);   // (0 unless opacity >= 1/255: the log is finite for every listed entry)
+                // UNIT (view entry points): the list entry carries the quadrant mask in its top four bits for the backward of the
+                // same view (LIST_ID_MASK / LIST_TAG_SHIFT, composite.h) -- its staging then needs no reach test.  Entries of
+                // batches this workgroup never stages (every pixel terminated before) lie behind every pixel's cut.
+                if (TAG) const_cast<uint32_t*>(SORT ? bs.point_list : point_list)[range.x + progress] = id | (qm << LIST_TAG_SHIFT);
+            }
 #pragma unroll
-        for (int q = 0; q < 4; q++) {
-            const uint64_t bal = ballot64((qm >> q) & 1u);
-            if (lane == 0) s_qmask[q][g.wave] = bal;
+            for (int q = 0; q < 4; q++) {
+                const uint64_t bal = ballot64((qm >> q) & 1u);
+                if (lane == 0) s_qmask[q][g.wave] = bal;
+            }
+            __syncthreads();
         }
-        __syncthreads();
-        }
-        if (wave_done || (CGS_WHATIF & 512)) continue;
+        if (wave_done) continue;
         // ---- this wave's list: the staged entries its quadrant accepted, in list order, padded to a multiple of 16
         int n = 0;
 #pragma unroll
@@ -298,7 +285,7 @@ __global__ void __launch_bounds__(256, UNIT ? CGS_FWD3_WAVES : CGS_FWD3_WAVES_GE
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         uint32_t last_off = 0;   // byte offset (16 * (staged index + 1)) of the last splat this pixel blended in this batch
-        for (int g0 = 0; g0 < ((CGS_WHATIF & 2) ? 0 : n); g0 += GROUP) {
+        for (int g0 = 0; g0 < n; g0 += GROUP) {
             // exponents of the group's 16 splats at this wave's 64 pixels.  (Issuing the NEXT group's MFMAs before this
             // group's blends was tried: 16 more live registers, 122 -> 135 us.)
             f32x16 P;
@@ -308,8 +295,7 @@ __global__ void __launch_bounds__(256, UNIT ? CGS_FWD3_WAVES : CGS_FWD3_WAVES_GE
                 const float2 cl = *reinterpret_cast<const float2*>(at_bytes + joff + 8);
                 P = p2_mfma(p2_splat_operand(lane, ge.x, ge.y, ge.z, ge.w, cl.x, cl.y, hx, hy), pix);
             }
-            const int cnt = (CGS_WHATIF & 1) ? 0 : min(GROUP, n - g0);
-            if (CGS_WHATIF & 1) Dacc += P[0] + P[15];
+            const int cnt = min(GROUP, n - g0);
             uint4 w4 = make_uint4(0u, 0u, 0u, 0u);   // four list offsets at a time, same in every lane
 #pragma unroll
             for (int s = 0; s < GROUP; s += 2) {
@@ -322,16 +308,13 @@ __global__ void __launch_bounds__(256, UNIT ? CGS_FWD3_WAVES : CGS_FWD3_WAVES_GE
                     t1 = *reinterpret_cast<const float2*>(at_bytes + j1);
                 }
                 float4 c0 = make_float4(0.f, 0.f, 0.f, 0.f), c1 = c0;
-                if (GEO && !(CGS_WHATIF & 4)) {
+                if (GEO) {
                     c0 = *reinterpret_cast<const float4*>(c_bytes + j0);
                     c1 = *reinterpret_cast<const float4*>(c_bytes + j1);
-                } else if (GEO) {
-                    c0 = make_float4(hx, hy, k.big, k.cA);
-                    c1 = make_float4(hy, hx, k.cA, k.big);
                 }
                 // alpha = min(0.99, opacity * G) = min(0.99, exp2(P)); reference: alpha < 1/255 -> skip
-                const float al0 = fminf(0.99f, (CGS_WHATIF & 8) ? P[s] : __builtin_amdgcn_exp2f(P[s]));
-                const float al1 = fminf(0.99f, (CGS_WHATIF & 8) ? P[s + 1] : __builtin_amdgcn_exp2f(P[s + 1]));
+                const float al0 = fminf(0.99f, __builtin_amdgcn_exp2f(P[s]));
+                const float al1 = fminf(0.99f, __builtin_amdgcn_exp2f(P[s + 1]));
                 const float a0 = al0 * sat01(fmaf(al0, k.big, cA));
                 const float a1 = al1 * sat01(fmaf(al1, k.big, cA));
                 // two splats blended together, one termination test (see k_render_fwd)
@@ -339,7 +322,7 @@ __global__ void __launch_bounds__(256, UNIT ? CGS_FWD3_WAVES : CGS_FWD3_WAVES_GE
                 float T1 = fmaf(-Tw, a0, Tw);
                 float wb = a1 * T1;
                 float T2 = fmaf(-T1, a1, T1);
-                if (!(CGS_WHATIF & 16) && __builtin_expect(ballot64(T2 < 0.0001f) != 0ull, 0)) {
+                if (__builtin_expect(ballot64(T2 < 0.0001f) != 0ull, 0)) {
                     const bool d0 = T1 < 0.0001f;
                     T_dead = d0 ? Tw : T_dead;
                     wa = d0 ? 0.f : wa;
@@ -382,7 +365,7 @@ __global__ void __launch_bounds__(256, UNIT ? CGS_FWD3_WAVES : CGS_FWD3_WAVES_GE
     }
     const bool terminated = !(cA > -0x1p120f);
     if (UNIT && !terminated) last_contributor = (uint32_t)total;   // never terminated: no cut
-    if ((CGS_WHATIF & 64) ? (g.inside && Tw + Dacc + A0 + A1 + A2 == 12345.f) : g.inside) {
+    if (g.inside) {
         const size_t HW = (size_t)H * W;
         const float T = terminated ? T_dead : Tw;
         final_T[g.pix_id] = T;
@@ -679,11 +662,6 @@ __global__ void __launch_bounds__(256, GEO ? CGS_BWD3_WAVES_GEO : (INVD || COLG)
                         const float m = sat01(fmaf(e, k.big, k.cA)) * sat01((float)wv[u] - jmin_f);
                         const float alpha_u = e * m;
                         const float alpha = fminf(0.99f, alpha_u);
-                        if (CGS_BWD3_WHATIF & 2) {
-                            sg[u * SSTRIDE + pix_off] = alpha;
-                            if (EXTRA) sw[u * SSTRIDE + pix_off] = alpha_u;
-                            continue;
-                        }
                         // The reference keeps (last_alpha, last_colour) and folds them into the "colour behind" accumulator at
                         // the start of the next step (backward.cu:605,620,631); folding right after use is the same
                         // recurrence -- acc' = acc + alpha (c - acc) -- with one fma per channel.
@@ -713,7 +691,6 @@ __global__ void __launch_bounds__(256, GEO ? CGS_BWD3_WAVES_GEO : (INVD || COLG)
                         if (EXTRA) sw[u * SSTRIDE + pix_off] = v_w;
                     }
                     // ---- flush the eight slots
-                    if (!(CGS_BWD3_WHATIF & 1)) {
                     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                     __builtin_amdgcn_wave_barrier();
                     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -805,44 +782,41 @@ __global__ void __launch_bounds__(256, GEO ? CGS_BWD3_WAVES_GEO : (INVD || COLG)
                     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                     __builtin_amdgcn_wave_barrier();   // the slot buffers may be overwritten from here on
                     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                    }
                 }
             }
         }
         // ---- the batch's per-splat sums leave the workgroup: lane (entry, field) -> consecutive floats of the splat's
         // 64-byte accumulator record = one L2 request per entry
-        if (!(CGS_BWD3_WHATIF & 4)) {
-            __syncthreads();
-            const int nb = min(BB, total - i * BB);
-            uint64_t tm[4][NC];
-            int base[4][NC];
+        __syncthreads();
+        const int nb = min(BB, total - i * BB);
+        uint64_t tm[4][NC];
+        int base[4][NC];
 #pragma unroll
-            for (int w = 0; w < 4; w++) {
-                int acc = 0;
+        for (int w = 0; w < 4; w++) {
+            int acc = 0;
 #pragma unroll
-                for (int c = 0; c < NC; c++) { tm[w][c] = s_tmask[w][c]; base[w][c] = acc; acc += __builtin_popcountll(tm[w][c]); }
-            }
-            constexpr int FL = NF > 8 ? 16 : 8;     // lanes per entry
-            constexpr int EPP = 256 / FL;           // entries per pass of the workgroup
-            const int f = (int)(threadIdx.x & (FL - 1));
+            for (int c = 0; c < NC; c++) { tm[w][c] = s_tmask[w][c]; base[w][c] = acc; acc += __builtin_popcountll(tm[w][c]); }
+        }
+        constexpr int FL = NF > 8 ? 16 : 8;     // lanes per entry
+        constexpr int EPP = 256 / FL;           // entries per pass of the workgroup
+        const int f = (int)(threadIdx.x & (FL - 1));
 #pragma unroll
-            for (int c = 0; c < NC; c++) {
+        for (int c = 0; c < NC; c++) {
 #pragma unroll
-                for (int h = 0; h < 64 / EPP; h++) {
-                    const int bit = h * EPP + (int)(threadIdx.x / FL), e = c * 64 + bit;
-                    if (e < nb && f < NF) {
-                        float v = 0.f;
-                        bool any = false;
+            for (int h = 0; h < 64 / EPP; h++) {
+                const int bit = h * EPP + (int)(threadIdx.x / FL), e = c * 64 + bit;
+                if (e < nb && f < NF) {
+                    float v = 0.f;
+                    bool any = false;
 #pragma unroll
-                        for (int w = 0; w < 4; w++) {
-                            const uint64_t m = tm[w][c];
-                            const int pos = base[w][c] + __builtin_popcountll(m & ((1ull << bit) - 1ull));
-                            if (((m >> bit) & 1ull) && pos < CAP) { v += s_res[w][pos * NF + f]; any = true; }
-                        }
-                        if (any && v != 0.f) {
-                            const uint32_t id = INVD ? s_id[e + 1] : __float_as_uint(s_at[e + 1].y);
-                            atomicAdd(grad_acc + (size_t)id * acc_stride + f, v);
-                        }
+                    for (int w = 0; w < 4; w++) {
+                        const uint64_t m = tm[w][c];
+                        const int pos = base[w][c] + __builtin_popcountll(m & ((1ull << bit) - 1ull));
+                        if (((m >> bit) & 1ull) && pos < CAP) { v += s_res[w][pos * NF + f]; any = true; }
+                    }
+                    if (any && v != 0.f) {
+                        const uint32_t id = INVD ? s_id[e + 1] : __float_as_uint(s_at[e + 1].y);
+                        atomicAdd(grad_acc + (size_t)id * acc_stride + f, v);
                     }
                 }
             }
