@@ -11,13 +11,13 @@ namespace cgs {
 // workgroups: no atomics, no zero-fill launch, the same bits on every run), which also clears the slots of the
 // backward's two; those are accumulated with one fire-and-forget f64 atomic per workgroup (same-address f64 atomics
 // serialise at ~20 ns each: 782 blocks on one address cost more than the kernels themselves, 49 per slot do not).
-// (Round 5 tried to let the last workgroup of k_sample_bwd<3> hand the backward's slots back cleared, by an arrival
+// (Round 5 tried to let the last workgroup of k_sample_bwd_curves hand the backward's slots back cleared, by an arrival
 // ticket: a RETURNING device-scope atomic per workgroup -- one address or 64 -- took that kernel from 8.3 to 12.7 -
 // 17.1 us at 794 workgroups; on this multi-XCD part the answer comes from beyond the XCD's L2.  Not kept.)
 constexpr int NORM_SLOTS = 64;
 // norms[q * NORM_SLOTS + slot].  Forward (k_sample_f12, ONE pass): q0 = S1 = sum |c1v|^2, q1 = S2 = sum |cross(tan,c1v)|^2,
 // q2 = BS = sum dot(cross(cross(tan,c1v), tan), c1v), from which N1 = sqrt(S1), N2 = sqrt(S2) / N1 (c2v = cross(tan,
-// c1v / N1)).  Backward (k_sample_bwd<1>, ONE pass): q3 = D2 = sum dot(g_v2, c2v), q4 = A = sum dot(g_v1 +
+// c1v / N1)).  Backward (k_sample_bwd_sums, ONE pass): q3 = D2 = sum dot(g_v2, c2v), q4 = A = sum dot(g_v1 +
 // cross(g_v2, tan) / N2, c1v); the second global term follows in closed form, D1 = A - D2 / N2^3 * BS / N1 (it is
 // linear in D2), so neither direction needs a second grid-wide pass.
 constexpr int NQ_FWD = 3, NQ_ALL = 5;
@@ -85,6 +85,25 @@ __device__ __forceinline__ void stage_consts(const SampleCoef* __restrict__ coef
 }
 constexpr int SAMPLE_BLOCK = 256;   // threads per block of the kernels whose blocks hold whole curves
 constexpr int MAX_M = 32;  // samples per curve supported by the LDS table (reference default 12)
+
+// "Blocks hold whole curves": SAMPLE_BLOCK / m curves per block, so cpb * m threads of a block are active.  Host side: the
+// curves per block and the grid that covers B curves.
+struct CurveLaunch { int cpb; dim3 grid; };
+inline CurveLaunch curve_launch(int B, int m) {
+    const int cpb = SAMPLE_BLOCK / m;
+    return {cpb, dim3((B + cpb - 1) / cpb)};
+}
+// Device side: this thread is sample i of curve b; the idle threads of the block and the curves past B are not valid (they
+// still take part in the block's barriers and sums).
+struct CurveSlot { int i, b; bool valid; };
+__device__ __forceinline__ CurveSlot curve_slot(int B, int m, int curves_per_block) {
+    const int lc = threadIdx.x / m;
+    CurveSlot t;
+    t.i = threadIdx.x - lc * m;
+    t.b = blockIdx.x * curves_per_block + lc;
+    t.valid = lc < curves_per_block && t.b < B;
+    return t;
+}
 
 // block-wide sums of N quantities -> one f64 atomic each on this block's slot of quantities q0, q0+1, ...
 template <int N>
@@ -207,6 +226,15 @@ __device__ __forceinline__ void rot_matrix(const SampleFwd& s, float M[3][3]) { 
     M[2][0] = s.v0.z; M[2][1] = s.v1.z; M[2][2] = s.v2.z;
 }
 
+// One sample's terms of the backward's two grid-wide sums (q3 = D2 and q4 = A of the norms layout above)
+struct NormTerms { double d2, a; };
+__device__ __forceinline__ NormTerms norm_sum_terms(const SampleFwd& s, float N2, V3 g_v1, V3 g_v2) {
+    NormTerms t;
+    t.d2 = (double)dot(g_v2, s.c2v);
+    t.a = (double)dot(g_v1, s.c1v) + (double)((1.f / N2) * dot(cross(g_v2, s.tan), s.c1v));
+    return t;
+}
+
 // Tail of the sampling backward for ONE sample: from dL/d{v0, v1, v2} (columns of the rotation), dL/dxyz and dL/dscaling to
 // this sample's contribution to dL/d{p0..p3} and dL/dwidth (reference: autograd of scene/gaussian_curve_model.py:180-198).
 // D2 = sum_all <g_v2, c2v> and D1 (stage_consts) are the two grid-wide sums the global Frobenius norms bring in.  The map is
@@ -261,9 +289,9 @@ __device__ __forceinline__ CurveGrad sample_backward_tail(const CurveCP& c, cons
 }
 constexpr int CURVE_PART = 13;   // per-curve partial of the fused view backward: dL/d{p0..p3} (12) + dL/dwidth
 // Sum the 13 per-sample values of every curve of the block over its m samples (sample order: deterministic) and hand each
-// (curve, field) sum to fn(local curve, field, sum).  s_part: [13][SAMPLE_BLOCK + 1] floats of LDS.
+// (curve, field) sum to fn(curve, field, sum), curve < B.  s_part: [13][SAMPLE_BLOCK + 1] floats of LDS.
 template <typename F>
-__device__ __forceinline__ void curve_reduce(const CurveGrad& g, float (*s_part)[256 + 1], int m, int curves_per_block, F fn) {
+__device__ __forceinline__ void curve_reduce(const CurveGrad& g, float (*s_part)[256 + 1], int B, int m, int curves_per_block, F fn) {
     const int t = threadIdx.x;
     s_part[0][t] = g.gp0.x; s_part[1][t] = g.gp0.y; s_part[2][t] = g.gp0.z;
     s_part[3][t] = g.gp1.x; s_part[4][t] = g.gp1.y; s_part[5][t] = g.gp1.z;
@@ -275,8 +303,15 @@ __device__ __forceinline__ void curve_reduce(const CurveGrad& g, float (*s_part)
         const int c2 = o / CURVE_PART, f = o - c2 * CURVE_PART;
         float sum = 0.f;
         for (int q = 0; q < m; q++) sum += s_part[f][c2 * m + q];
-        fn(c2, f, sum);
+        const int bb = blockIdx.x * curves_per_block + c2;
+        if (bb < B) fn(bb, f, sum);
     }
+}
+// Store v, the finished sum of (curve bb, field f), to dL/dcurve_points [B][12] or dL/dwidth [B]
+__device__ __forceinline__ void store_curve_grad(float* __restrict__ g_cp, float* __restrict__ g_width, int bb, int f, float v,
+                                                 int accumulate) {
+    float* dst = f < 12 ? g_cp + (size_t)bb * 12 + f : g_width + bb;
+    *dst = accumulate ? *dst + v : v;
 }
 
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }

@@ -3,12 +3,12 @@
 //
 //   forward   k_sample_f3 -> k_attrs_fwd -> k_preprocess_fwd          = k_view_fwd
 //             (xyz / rot / scaling -> rot_n / opacity / all_map -> SplatRec + radii: 100 B/splat written and re-read twice)
-//   backward  k_preprocess_bwd -> k_attrs_bwd -> k_sample_bwd<1>      = k_view_bwd
+//   backward  k_preprocess_bwd -> k_attrs_bwd -> k_sample_bwd_sums   = k_view_bwd
 //             (dL/d{mean3D, scale, rot_n, opacity, all_map} -> dL/d{rot_raw, scaling} -> dL/d{v0,v1,v2} + global sums)
 //
 // Same device functions as the separate kernels (curve_math.h, splat_math.h), so the results are the same; the global
 // Frobenius norms still need their own pass before (k_sample_f12) and the per-curve reduction its own pass after
-// (k_sample_bwd<3>).  Training configuration only: scales + rotations (no precomputed covariance), precomputed colours
+// (k_sample_bwd_close).  Training configuration only: scales + rotations (no precomputed covariance), precomputed colours
 // (no SH), no antialiasing -- everything else goes through the general kernels.
 #include "curve_math.h"
 #include "splat_math.h"
@@ -63,7 +63,7 @@ __global__ void __launch_bounds__(256) k_view_fwd(
     radii[p] = out_radius;
 }
 
-// Blocks hold whole curves (curves_per_block * m active threads), as k_attrs_bwd / k_sample_bwd<3> do: the per-curve
+// Blocks hold whole curves (curves_per_block * m active threads), as k_attrs_bwd / k_sample_bwd_curves do: the per-curve
 // opacity-logit gradient is the sample-ordered sum of its m per-splat terms.
 // 6 waves per SIMD = 80 VGPRs, the allocation of the compositors this kernel shares the GPU with when several views are
 // in flight: at its natural 115 VGPRs its waves only fit a SIMD once several compositor waves have drained, and the
@@ -98,11 +98,11 @@ __global__ void __launch_bounds__(SAMPLE_BLOCK, WAVES) k_view_bwd(
     __shared__ BlockConst s_bc;
     __shared__ float s_go[SAMPLE_BLOCK];
     stage_consts(coef, m, norms, s_coef, &s_bc);
-    const int lc = threadIdx.x / m, i = threadIdx.x - lc * m;
-    const int b = blockIdx.x * curves_per_block + lc;
-    const bool valid = lc < curves_per_block && b < B;
+    const CurveSlot t = curve_slot(B, m, curves_per_block);
+    const int i = t.i, b = t.b;
+    const bool valid = t.valid;
     float g_op_term = 0.f;
-    double acc_d2 = 0, acc_a = 0;
+    NormTerms nt = {0, 0};
     CurveGrad cg;
     cg.gp0 = cg.gp1 = cg.gp2 = cg.gp3 = V3{0.f, 0.f, 0.f};
     cg.gw = 0.f;
@@ -162,17 +162,14 @@ __global__ void __launch_bounds__(SAMPLE_BLOCK, WAVES) k_view_bwd(
         const V3 g_v0 = {gM[0][0], gM[1][0], gM[2][0]};
         const V3 g_v1 = {gM[0][1], gM[1][1], gM[2][1]};
         const V3 g_v2 = {gM[0][2], gM[1][2], gM[2][2]};
-        acc_d2 = (double)dot(g_v2, s.c2v);
-        acc_a = (double)dot(g_v1, s.c1v) + (double)((1.f / N2) * dot(cross(g_v2, s.tan), s.c1v));
+        nt = norm_sum_terms(s, N2, g_v1, g_v2);
         const V3 g_x = {o.dmean.x, o.dmean.y, o.dmean.z}, g_s = {gs.x * ab.mk, gs.y * ab.mk, gs.z * ab.mk};
         cg = sample_backward_tail(c, s_coef[i], s, w, eps, N1, N2, 0.f, 0.f, g_v0, g_v1, g_v2, g_x, true, g_s);
     }
     s_go[threadIdx.x] = g_op_term;
-    const double acc2v[2] = {acc_d2, acc_a};
+    const double acc2v[2] = {nt.d2, nt.a};
     block_accumulate<2>(acc2v, norms, 3);     // (contains the barrier that publishes s_go)
-    curve_reduce(cg, s_part, m, curves_per_block, [&](int c2, int f, float sum) {
-        const int bb = blockIdx.x * curves_per_block + c2;
-        if (bb >= B) return;
+    curve_reduce(cg, s_part, B, m, curves_per_block, [&](int bb, int f, float sum) {
         float* dst = curve_part + (size_t)bb * CURVE_PART + f;
         *dst = acc_scr ? *dst + sum : sum;
     });
@@ -203,18 +200,15 @@ void launch_view_backward(hipStream_t s, int B, int m, const float* cp, const fl
                           const SplatRec* rec, float* grad_acc, const float* g_rot_raw_extra, float* dL_dmean2D,
                           float* g_opacity_logit, float* g_mask_logit, float* curve_part, int accumulate) {
     ProfScope p("view_bwd", s);
-    const int cpb = SAMPLE_BLOCK / m;
+    const CurveLaunch cl = curve_launch(B, m);
     const ViewParams vp{viewmatrix, projmatrix, tan_fovx, tan_fovy, focal_x, focal_y, W, H, 0, 0};
-    if ((long long)B * m >= VIEW_BWD_LARGE_P)
-        hipLaunchKernelGGL(k_view_bwd<CGS_VIEW_BWD_WAVES_LARGE>, dim3((B + cpb - 1) / cpb), dim3(SAMPLE_BLOCK), 0, s, B, m, cpb, cp,
-                           width, is_bezier, reinterpret_cast<const SampleCoef*>(coef), eps, norms, opacity_logit, mask_logit,
-                           mask_thr, campos, vp, radii, rec, grad_acc, g_rot_raw_extra, dL_dmean2D, g_opacity_logit, g_mask_logit,
-                           curve_part, accumulate);
-    else
-        hipLaunchKernelGGL(k_view_bwd<CGS_VIEW_BWD_WAVES>, dim3((B + cpb - 1) / cpb), dim3(SAMPLE_BLOCK), 0, s, B, m, cpb, cp, width,
-                           is_bezier, reinterpret_cast<const SampleCoef*>(coef), eps, norms, opacity_logit, mask_logit, mask_thr,
-                           campos, vp, radii, rec, grad_acc, g_rot_raw_extra, dL_dmean2D, g_opacity_logit, g_mask_logit, curve_part,
-                           accumulate);
+    const auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, cl.grid, dim3(SAMPLE_BLOCK), 0, s, B, m, cl.cpb, cp, width, is_bezier,
+                           reinterpret_cast<const SampleCoef*>(coef), eps, norms, opacity_logit, mask_logit, mask_thr, campos, vp,
+                           radii, rec, grad_acc, g_rot_raw_extra, dL_dmean2D, g_opacity_logit, g_mask_logit, curve_part, accumulate);
+    };
+    if ((long long)B * m >= VIEW_BWD_LARGE_P) launch(k_view_bwd<CGS_VIEW_BWD_WAVES_LARGE>);
+    else launch(k_view_bwd<CGS_VIEW_BWD_WAVES>);
 }
 
 }  // namespace cgs
