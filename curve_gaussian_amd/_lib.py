@@ -103,6 +103,7 @@ SIGNATURES = {
     "cgs_splat_attrs_forward": (_i, [_i, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "cgs_splat_attrs_backward": (_i, [_i, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                       _vp, _vp, _vp]),
+    "cgs_undistort_images": (_i, [_i, _vp, _f, _vp, _vp]),
 }
 
 
@@ -117,7 +118,16 @@ class ReportView(C.Structure):
                 ("height", _i), ("width", _i), ("written", C.c_uint), ("out_offset", C.c_size_t)]
 
 
+class UndistortView(C.Structure):
+    """cgs_undistort_view (include/curvegs.h)."""
+    _fields_ = [("src", _vp), ("dst", _vp), ("channels", _i), ("height", _i), ("width", _i), ("model", _i),
+                ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
+                ("out_fx", C.c_double), ("out_fy", C.c_double), ("k", C.c_double * 8)]
+
+
 REPORT_MAX_VIEWS = 32   # CGS_REPORT_MAX_VIEWS
+UNDISTORT_MAX_VIEWS = 24   # CGS_UNDISTORT_MAX_VIEWS
+UNDISTORT_MAX_CHANNELS = 4   # CGS_UNDISTORT_MAX_CHANNELS
 REPORT_PANELS = ("render", "ground_truth", "depth", "rend_dir", "rend_alpha")   # panel order of cgs_report_panels
 
 _lib = None

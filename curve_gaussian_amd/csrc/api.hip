@@ -1670,4 +1670,54 @@ int cgs_pair_consensus_fit(int B, const float* curve_points, int K, const int* p
     return CGS_OK;
 }
 
+int cgs_undistort_images(int n_views, const cgs_undistort_view* views, float fill, int* blank_counts, void* stream_) {
+    if (n_views < 0 || n_views > CGS_UNDISTORT_MAX_VIEWS) {
+        set_error("cgs_undistort_images: invalid argument (n_views=%d, at most %d per call)", n_views, CGS_UNDISTORT_MAX_VIEWS);
+        return CGS_ERR_INVALID_ARGUMENT;
+    }
+    if (n_views == 0) return CGS_OK;
+    if (!views || !blank_counts) {
+        set_error("cgs_undistort_images: invalid argument (NULL pointer)");
+        return CGS_ERR_INVALID_ARGUMENT;
+    }
+    if (!std::isfinite(fill)) {
+        set_error("cgs_undistort_images: invalid argument (fill is not finite)");
+        return CGS_ERR_INVALID_ARGUMENT;
+    }
+    for (int v = 0; v < n_views; v++) {
+        const cgs_undistort_view& d = views[v];
+        if (!d.src || !d.dst || d.src == d.dst) {
+            set_error("cgs_undistort_images: invalid argument (view %d: NULL pointer or dst == src)", v);
+            return CGS_ERR_INVALID_ARGUMENT;
+        }
+        if (d.channels < 1 || d.channels > CGS_UNDISTORT_MAX_CHANNELS || d.height <= 0 || d.width <= 0) {
+            set_error("cgs_undistort_images: invalid argument (view %d: channels=%d (1..%d), height=%d, width=%d)", v, d.channels,
+                      CGS_UNDISTORT_MAX_CHANNELS, d.height, d.width);
+            return CGS_ERR_INVALID_ARGUMENT;
+        }
+        if (d.model != 0 && d.model != 1 && d.model != 2 && d.model != 3 && d.model != 4 && d.model != 6) {
+            set_error("cgs_undistort_images: invalid argument (view %d: camera model id %d is not supported: SIMPLE_PINHOLE 0, "
+                      "PINHOLE 1, SIMPLE_RADIAL 2, RADIAL 3, OPENCV 4 and FULL_OPENCV 6 are)", v, d.model);
+            return CGS_ERR_INVALID_ARGUMENT;
+        }
+        const double focals[4] = {d.fx, d.fy, d.out_fx, d.out_fy};
+        for (double f : focals) {
+            if (!(f > 0.0) || !std::isfinite(f)) {
+                set_error("cgs_undistort_images: invalid argument (view %d: focal lengths fx=%g, fy=%g, out_fx=%g, out_fy=%g must "
+                          "be positive and finite)", v, d.fx, d.fy, d.out_fx, d.out_fy);
+                return CGS_ERR_INVALID_ARGUMENT;
+            }
+        }
+        bool finite = std::isfinite(d.cx) && std::isfinite(d.cy);
+        for (double k : d.k) finite = finite && std::isfinite(k);
+        if (!finite) {
+            set_error("cgs_undistort_images: invalid argument (view %d: a principal point or coefficient is not finite)", v);
+            return CGS_ERR_INVALID_ARGUMENT;
+        }
+    }
+    launch_undistort_images((hipStream_t)stream_, n_views, views, fill, blank_counts);
+    if (!check_launch("undistort_images", false, (hipStream_t)stream_)) return CGS_ERR_HIP;
+    return CGS_OK;
+}
+
 }  // extern "C"

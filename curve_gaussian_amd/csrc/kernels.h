@@ -194,4 +194,9 @@ void launch_segment_merge_labels(hipStream_t s, int n, const float* seg, double 
 void launch_pair_consensus_fit(hipStream_t s, int K, const float* cp, const int* pairs, int sample_num, double ransac_thr,
                                double err_thr, float* ctrl, double* rmse, int* inliers, uint8_t* ok);
 
+
+// undistort.hip
+void launch_undistort_images(hipStream_t s, int n_views, const cgs_undistort_view* views_host, float fill,
+                             int* blank_counts);
+
 }  // namespace cgs

@@ -16,6 +16,7 @@ from typing import NamedTuple
 import numpy as np
 import torch
 
+from ..ops.undistort import distortion_of, undistort_images
 from ..synthetic import projection_matrix, world2view
 from .dataset_io import BasicPointCloud, EdgeCamera, _pil_to_chw, focal2fov, fov2focal, read_ply_table
 
@@ -335,7 +336,25 @@ def test_image_names(path, cam_extrinsics, llffhold):
         return [line.strip() for line in f]
 
 
-def read_colmap(path, images=None, eval=False, llffhold=8, detector="DexiNed", resolution=-1):
+def _undistorted_maps(path, images, detector, resolution, extrs, intrs, backend):
+    """The edge maps of read_colmap(undistort=True): loaded as ever, then resampled in as few calls as the op's chunks allow."""
+    import warnings
+    maps = [load_edge_image(edge_map_path(path, images, extr.name, detector), resolution) for extr in extrs]
+    args = [distortion_of(intr, int(m.shape[2]), int(m.shape[1])) for intr, m in zip(intrs, maps)]
+    maps, blank = undistort_images(maps, [a[0] for a in args], [a[1] for a in args], [a[3] for a in args],
+                                   [a[2] for a in args], fill=0.0, backend=backend)
+    for extr, m, n_blank in zip(extrs, maps, blank.tolist()):
+        if n_blank > BLANK_WARN_FRACTION * m.shape[1] * m.shape[2]:
+            warnings.warn(f"read_colmap: {n_blank} of the {m.shape[1] * m.shape[2]} pixels of {extr.name} are blank after "
+                          "undistortion (no source pixel reaches them)")
+    return maps
+
+
+BLANK_WARN_FRACTION = 0.25   # read_colmap(undistort=True) warns about an image with more blank pixels than this
+
+
+def read_colmap(path, images=None, eval=False, llffhold=8, detector="DexiNed", resolution=-1, undistort=False,
+                undistort_backend="gpu"):
     """readColmapSceneInfo + loadCam for a COLMAP scan -> (train_cameras, test_cameras, point_cloud, cameras_extent).
 
     Reference behaviours kept exactly: R = qvec2rotmat(qvec)^T and T = tvec; FoV from the focal lengths (SIMPLE_PINHOLE
@@ -350,14 +369,30 @@ def read_colmap(path, images=None, eval=False, llffhold=8, detector="DexiNed", r
     1600 px wide, otherwise a target width); the extent is getNerfppNorm's over the train list.
 
     K of a SIMPLE_PINHOLE camera uses f for both axes (the reference reuses the fy of the camera read before it, or fails
-    on the first).  Mask images and depth parameters are not read."""
+    on the first).  Mask images and depth parameters are not read.
+
+    ``undistort=True`` (not in the reference, which reads undistorted scans only) accepts SIMPLE_RADIAL, RADIAL and
+    FULL_OPENCV cameras too and honours the file's distortion coefficients and principal point: the edge maps are loaded
+    as above, resize included, and then resampled by ``ops.undistort.undistort_images`` (``undistort_backend``: "gpu",
+    HIP, the images stay on the device; "host", numpy) into the camera that is built here anyway -- the file's focal
+    lengths, principal point at the centre.  Every EdgeCamera field except ``original_image`` is what a PINHOLE camera
+    with the same focal lengths gives without the flag.  An image of which more than a quarter comes out blank (no source
+    pixel reaches it) is reported with ``warnings.warn``."""
     sparse = os.path.join(path, "sparse/0")
     cam_intrinsics, cam_extrinsics = read_model(sparse)
     test_names = test_image_names(path, cam_extrinsics, llffhold) if eval else []
+    extrs = list(cam_extrinsics.values())
+    intrs = [cam_intrinsics[extr.camera_id] for extr in extrs]
+    maps = _undistorted_maps(path, images, detector, resolution, extrs, intrs, undistort_backend) if undistort else None
     cams, is_test = [], []
-    for extr in cam_extrinsics.values():
-        intr = cam_intrinsics[extr.camera_id]
-        image = load_edge_image(edge_map_path(path, images, extr.name, detector), resolution)
+    for k, (extr, intr) in enumerate(zip(extrs, intrs)):
+        if undistort:
+            # the camera of the resampled map: the output focal lengths distortion_of gives at the file's own size
+            _, _, (fx, fy), _ = distortion_of(intr, intr.width, intr.height)
+            intr = intr._replace(model="PINHOLE", params=np.array([fx, fy, intr.width / 2.0, intr.height / 2.0]))
+            image = maps[k]
+        else:
+            image = load_edge_image(edge_map_path(path, images, extr.name, detector), resolution)
         cam = camera_from_colmap(intr, extr, image)
         cams.append(cam)
         is_test.append(cam.image_name in test_names)

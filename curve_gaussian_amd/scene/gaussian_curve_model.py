@@ -475,17 +475,21 @@ class Scene:
     ``eval`` / ``llffhold``: the held-out split.  COLMAP: see read_colmap (the train list keeps every camera).  EMAP:
     ``eval=True`` makes the test list the same frames again (rendemapInfo :385-399); with ``eval=False`` the test list is
     empty and the train list is the frames once (the reference's list holds them twice).
-    ``images`` / ``resolution`` (COLMAP only): ``--images`` and ``-r`` of the reference."""
+    ``images`` / ``resolution`` (COLMAP only): ``--images`` and ``-r`` of the reference.  ``undistort`` (COLMAP only; not in
+    the reference): resample the edge maps through the cameras' lens models, see read_colmap; on the GPU when `device` is
+    one, on the host otherwise."""
 
     def __init__(self, source_path, gaussians, detector="DexiNed", num_pts_per_axis=15, cameras_extent=None, rng=None,
-                 device=None, eval=False, llffhold=8, images=None, resolution=-1):
+                 device=None, eval=False, llffhold=8, images=None, resolution=-1, undistort=False):
         import os
         from . import dataset_io
         self.gaussians = gaussians
         if os.path.exists(os.path.join(source_path, "sparse")):
             from . import colmap_io
             self.train_cameras, self.test_cameras, self.point_cloud, extent = colmap_io.read_colmap(
-                source_path, images=images, eval=eval, llffhold=llffhold, detector=detector, resolution=resolution)
+                source_path, images=images, eval=eval, llffhold=llffhold, detector=detector, resolution=resolution,
+                undistort=undistort,
+                undistort_backend="gpu" if device is not None and torch.device(device).type == "cuda" else "host")
             if cameras_extent is None:
                 cameras_extent = extent
         else:

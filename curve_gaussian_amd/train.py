@@ -2,7 +2,7 @@
 ``parametric_edges.json``.
 
     python -m curve_gaussian_amd.train -s SCAN -m OUT [--iterations N] [--backend graphed|direct|autograd|torch]
-                                       [--draw_snapshots] [--topology_backend host|gpu] [--report_dir DIR]
+                                       [--draw_snapshots] [--topology_backend host|gpu] [--report_dir DIR] [--undistort]
 
 The loop keeps the reference's order.  Per iteration: learning rate, SH degree every 1000 iterations, a random view without
 replacement, render + losses + every regulariser + backward (one ``TrainStep`` call), densification statistics before
@@ -34,10 +34,11 @@ class ModelParams:
     """The fields of the reference's ModelParams (arguments/__init__.py:47-66) this driver reads."""
 
     def __init__(self, source_path="", model_path="", sh_degree=0, n_gaussians=12, detector="DexiNed", resolution=-1,
-                 white_background=False, eval=False):
+                 white_background=False, eval=False, undistort=False):
         self.source_path, self.model_path = source_path, model_path
         self.sh_degree, self.n_gaussians, self.detector = sh_degree, n_gaussians, detector
         self.resolution, self.white_background, self.eval = resolution, white_background, eval
+        self.undistort = undistort   # not in the reference: COLMAP scans with lens distortion (scene/colmap_io.py)
 
 
 class OptimizationParams:
@@ -137,7 +138,7 @@ def make_scene(dataset, opt, device):
     from .scene import GaussianCurveModel, Scene
     gaussians = GaussianCurveModel(dataset.sh_degree, dataset.n_gaussians, opt.optimizer_type, device=device)
     scene = Scene(dataset.source_path, gaussians, detector=dataset.detector, eval=dataset.eval,
-                  resolution=dataset.resolution, device=device)
+                  resolution=dataset.resolution, device=device, undistort=dataset.undistort)
     scene.model_path = dataset.model_path
     gaussians.training_setup(opt)
     return scene, gaussians
@@ -310,6 +311,9 @@ def build_parser():
     p.add_argument("--resolution", "-r", type=int, default=-1)
     p.add_argument("--white_background", "-w", action="store_true")
     p.add_argument("--eval", action="store_true")
+    p.add_argument("--undistort", action="store_true",
+                   help="COLMAP scans: resample the edge maps through each camera's lens model and principal point (accepts "
+                        "SIMPLE_RADIAL, RADIAL and FULL_OPENCV cameras too); without it distortion is ignored, as in the reference")
     p.add_argument("--iterations", type=int, default=None)
     p.add_argument("--test_iterations", nargs="+", type=int, default=[3_000, 10_000])        # :386-391
     p.add_argument("--save_iterations", nargs="+", type=int, default=[3_000, 10_000])
@@ -337,7 +341,7 @@ def parse_args(argv):
         opt.iterations = args.iterations
     args.save_iterations.append(opt.iterations)                                     # :404
     dataset = ModelParams(source_path, args.model_path, args.sh_degree, args.n_gaussians, args.detector, args.resolution,
-                          args.white_background, args.eval)
+                          args.white_background, args.eval, args.undistort)
     return dataset, opt, args
 
 

@@ -721,6 +721,50 @@ int cgs_pair_consensus_fit(int B, const float* curve_points /*[B,4,3]*/, int K, 
                            double ransac_thresh, double error_threshold, float* ctrl /*[K,4,3]*/, double* rmse /*[K]*/,
                            int* inliers /*[K]*/, uint8_t* ok /*[K]*/, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Undistortion of the edge maps of a COLMAP scan (no counterpart in the reference, which reads undistorted scans only):
+ * every view's [channels,height,width] float32 image `src`, detected in a camera with lens distortion and any principal
+ * point, is resampled into `dst`, the same pixel grid seen by the ideal pinhole camera with focal lengths out_fx, out_fy
+ * and its principal point at (width / 2, height / 2).  One launch for all views; views may differ in size.
+ * Per output pixel (i, j), coordinates in float64 in this order of operations (no fused multiply-add):
+ *   x = (i + 0.5 - width / 2) / out_fx,  y = (j + 0.5 - height / 2) / out_fy,  r2 = x x + y y
+ *   (xd, yd) by `model`, a COLMAP camera model id with its coefficients k[] in COLMAP's parameter order:
+ *     0 SIMPLE_PINHOLE, 1 PINHOLE   xd = x, yd = y
+ *     2 SIMPLE_RADIAL (k)           xd = x s, yd = y s,  s = 1 + k r2
+ *     3 RADIAL (k1, k2)             xd = x s, yd = y s,  s = 1 + k1 r2 + k2 r2^2
+ *     4 OPENCV (k1, k2, p1, p2)     xd = x s + 2 p1 x y + p2 (r2 + 2 x^2),  yd = y s + p1 (r2 + 2 y^2) + 2 p2 x y,  s as RADIAL
+ *     6 FULL_OPENCV (k1, k2, p1, p2, k3, k4, k5, k6)   as OPENCV with
+ *                                   s = (1 + k1 r2 + k2 r2^2 + k3 r2^3) / (1 + k4 r2 + k5 r2^2 + k6 r2^3)
+ *   u = fx xd + cx - 0.5,  v = fy yd + cy - 0.5      (fx, fy, cx, cy: the source camera at the resolution of `src`)
+ *   x0 = floor(u), y0 = floor(v), a = u - x0, b = v - y0; the four taps (x0 | x0 + 1, y0 | y0 + 1) carry the weights
+ *   (1-a)(1-b), a(1-b), (1-a) b, a b, rounded to float32; a tap outside [0, width-1] x [0, height-1] reads `fill`;
+ *   dst = ((w00 t00 + w01 t01) + w10 t10) + w11 t11 in float32, per channel.
+ * An integer position therefore copies its pixel bit for bit.  A pixel is BLANK, and holds `fill`, unless -1 < u < width
+ * and -1 < v < height: outside that range, or with a position that is not finite, no tap of non-zero weight lies inside
+ * the source.  Every view's number of blank pixels is ADDED to blank_counts[v] (device, [n_views];
+ * the caller zeroes it) with integer atomics, at most one per workgroup: the result does not depend on their order.
+ * The table travels as a kernel argument, which bounds n_views by CGS_UNDISTORT_MAX_VIEWS per call; no copy, no host
+ * synchronisation.  n_views = 0 is a no-op; n_views outside [0, CGS_UNDISTORT_MAX_VIEWS], a NULL table / blank_counts /
+ * src / dst, dst == src, channels outside [1, CGS_UNDISTORT_MAX_CHANNELS], height or width <= 0, focal lengths that are
+ * not positive and finite, a `fill`, principal point or coefficient that is not finite and any other model id are
+ * CGS_ERR_INVALID_ARGUMENT, rejected before anything is launched.
+ * ------------------------------------------------------------------------------------------------ */
+#define CGS_UNDISTORT_MAX_VIEWS 24
+#define CGS_UNDISTORT_MAX_CHANNELS 4
+typedef struct cgs_undistort_view {
+    const float* src;   /* [channels,height,width] */
+    float* dst;         /* [channels,height,width], no overlap with any src */
+    int channels;
+    int height;
+    int width;
+    int model;          /* COLMAP camera model id */
+    double fx, fy, cx, cy;   /* the source camera, in pixels of `src` */
+    double out_fx, out_fy;   /* the pinhole camera of `dst` */
+    double k[8];        /* distortion coefficients in COLMAP's order; the unused ones are ignored */
+} cgs_undistort_view;
+int cgs_undistort_images(int n_views, const cgs_undistort_view* views /*host, [n_views]*/, float fill,
+                         int* blank_counts /*device, [n_views]*/, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
