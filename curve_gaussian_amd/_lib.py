@@ -104,6 +104,8 @@ SIGNATURES = {
     "cgs_splat_attrs_backward": (_i, [_i, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                       _vp, _vp, _vp]),
     "cgs_undistort_images": (_i, [_i, _vp, _f, _vp, _vp]),
+    "cgs_edge_gradients": (_i, [_i, _vp, _vp, _i, _vp]),
+    "cgs_edge_trace": (_i, [_i, _vp, _f, _f, _i, _vp, _vp]),
 }
 
 
@@ -125,9 +127,22 @@ class UndistortView(C.Structure):
                 ("out_fx", C.c_double), ("out_fy", C.c_double), ("k", C.c_double * 8)]
 
 
+class EdgeGradientView(C.Structure):
+    """cgs_edge_gradient_view (include/curvegs.h)."""
+    _fields_ = [("pixels", _vp), ("gx", _vp), ("gy", _vp), ("m", _vp), ("height", _i), ("width", _i), ("channels", _i),
+                ("reserved", _i)]
+
+
+class EdgeTraceView(C.Structure):
+    """cgs_edge_trace_view (include/curvegs.h)."""
+    _fields_ = [("gx", _vp), ("gy", _vp), ("m", _vp), ("e", _vp), ("state", _vp), ("height", _i), ("width", _i)]
+
+
 REPORT_MAX_VIEWS = 32   # CGS_REPORT_MAX_VIEWS
 UNDISTORT_MAX_VIEWS = 24   # CGS_UNDISTORT_MAX_VIEWS
 UNDISTORT_MAX_CHANNELS = 4   # CGS_UNDISTORT_MAX_CHANNELS
+EDGE_MAX_VIEWS = 24   # CGS_EDGE_MAX_VIEWS
+EDGE_MAX_RADIUS = 12   # CGS_EDGE_MAX_RADIUS
 REPORT_PANELS = ("render", "ground_truth", "depth", "rend_dir", "rend_alpha")   # panel order of cgs_report_panels
 
 _lib = None

@@ -1720,4 +1720,69 @@ int cgs_undistort_images(int n_views, const cgs_undistort_view* views, float fil
     return CGS_OK;
 }
 
+int cgs_edge_gradients(int n_views, const cgs_edge_gradient_view* views, const float* taps, int radius, void* stream_) {
+    if (n_views < 1 || n_views > CGS_EDGE_MAX_VIEWS) {
+        set_error("cgs_edge_gradients: invalid argument (n_views=%d, 1..%d per call)", n_views, CGS_EDGE_MAX_VIEWS);
+        return CGS_ERR_INVALID_ARGUMENT;
+    }
+    if (!views || !taps) {
+        set_error("cgs_edge_gradients: invalid argument (NULL pointer)");
+        return CGS_ERR_INVALID_ARGUMENT;
+    }
+    if (radius < 0 || radius > CGS_EDGE_MAX_RADIUS) {
+        set_error("cgs_edge_gradients: invalid argument (radius=%d, 0..%d)", radius, CGS_EDGE_MAX_RADIUS);
+        return CGS_ERR_INVALID_ARGUMENT;
+    }
+    for (int v = 0; v < n_views; v++) {
+        const cgs_edge_gradient_view& d = views[v];
+        if (!d.pixels || !d.gx || !d.gy || !d.m) {
+            set_error("cgs_edge_gradients: invalid argument (view %d: NULL pointer)", v);
+            return CGS_ERR_INVALID_ARGUMENT;
+        }
+        if (d.height <= 0 || d.width <= 0 || (d.channels != 1 && d.channels != 3 && d.channels != 4)) {
+            set_error("cgs_edge_gradients: invalid argument (view %d: height=%d, width=%d, channels=%d (1, 3 or 4))", v, d.height,
+                      d.width, d.channels);
+            return CGS_ERR_INVALID_ARGUMENT;
+        }
+    }
+    launch_edge_gradients((hipStream_t)stream_, n_views, views, taps, radius);
+    if (!check_launch("edge_gradients", false, (hipStream_t)stream_)) return CGS_ERR_HIP;
+    return CGS_OK;
+}
+
+int cgs_edge_trace(int n_views, const cgs_edge_trace_view* views, float low, float high, int thin, int* changed_flag,
+                   void* stream_) {
+    if (n_views < 1 || n_views > CGS_EDGE_MAX_VIEWS) {
+        set_error("cgs_edge_trace: invalid argument (n_views=%d, 1..%d per call)", n_views, CGS_EDGE_MAX_VIEWS);
+        return CGS_ERR_INVALID_ARGUMENT;
+    }
+    if (!views || !changed_flag) {
+        set_error("cgs_edge_trace: invalid argument (NULL pointer)");
+        return CGS_ERR_INVALID_ARGUMENT;
+    }
+    if (!(low > 0.0f) || !(low <= high) || !std::isfinite(high)) {   // (a NaN compares false)
+        set_error("cgs_edge_trace: invalid argument (low=%g, high=%g: need 0 < low <= high, finite)", low, high);
+        return CGS_ERR_INVALID_ARGUMENT;
+    }
+    for (int v = 0; v < n_views; v++) {
+        const cgs_edge_trace_view& d = views[v];
+        if (!d.gx || !d.gy || !d.m || !d.e || !d.state) {
+            set_error("cgs_edge_trace: invalid argument (view %d: NULL pointer)", v);
+            return CGS_ERR_INVALID_ARGUMENT;
+        }
+        if (d.height <= 0 || d.width <= 0) {
+            set_error("cgs_edge_trace: invalid argument (view %d: height=%d, width=%d)", v, d.height, d.width);
+            return CGS_ERR_INVALID_ARGUMENT;
+        }
+    }
+    hipError_t err = hipSuccess;
+    const int rounds = launch_edge_trace((hipStream_t)stream_, n_views, views, low, high, thin, changed_flag, &err);
+    if (rounds < 0) {
+        set_error("edge_trace failed: %s", hipGetErrorString(err));
+        return CGS_ERR_HIP;
+    }
+    if (!check_launch("edge_trace", false, (hipStream_t)stream_)) return CGS_ERR_HIP;
+    return rounds;
+}
+
 }  // extern "C"

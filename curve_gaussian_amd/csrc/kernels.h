@@ -199,4 +199,10 @@ void launch_pair_consensus_fit(hipStream_t s, int K, const float* cp, const int*
 void launch_undistort_images(hipStream_t s, int n_views, const cgs_undistort_view* views_host, float fill,
                              int* blank_counts);
 
+// edge_detect.hip
+void launch_edge_gradients(hipStream_t s, int n_views, const cgs_edge_gradient_view* views_host, const float* taps,
+                           int radius);
+int launch_edge_trace(hipStream_t s, int n_views, const cgs_edge_trace_view* views_host, float low, float high, int thin,
+                      int* changed_flag, hipError_t* err);
+
 }  // namespace cgs

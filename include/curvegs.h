@@ -765,6 +765,65 @@ typedef struct cgs_undistort_view {
 int cgs_undistort_images(int n_views, const cgs_undistort_view* views /*host, [n_views]*/, float fill,
                          int* blank_counts /*device, [n_views]*/, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Edge maps from photographs: a classical (Canny) detector with a soft response.  No counterpart in the reference, whose
+ * edge maps come from a learned detector outside it; this is not one.  Two calls per batch of views, views may differ in
+ * size, every table travels as a kernel argument (at most CGS_EDGE_MAX_VIEWS views per call, no host -> device copy).
+ *
+ * cgs_edge_gradients: pixels (uint8, [height,width,channels] interleaved, channels 1, 3 or 4; a fourth channel is ignored)
+ * -> gx, gy, m, float32 [height,width] each.  All arithmetic float32, no fused multiply-add, correctly rounded divide
+ * and square root:
+ *   Y = ((0.299f R + 0.587f G) + 0.114f B) / 255f, or value / 255f for one channel
+ *   smoothing with the 2 radius + 1 taps (host, [2 radius + 1], offset -radius first; radius 0 with the tap 1 is none):
+ *     rows first, then columns, coordinates outside the image clamped, each sum accumulated from the lowest offset
+ *     to the highest, starting from the first product
+ *   gx = ((S(x+1,y-1) + 2 S(x+1,y)) + S(x+1,y+1)) - ((S(x-1,y-1) + 2 S(x-1,y)) + S(x-1,y+1)), times 0.25f
+ *   gy = ((S(x-1,y+1) + 2 S(x,y+1)) + S(x+1,y+1)) - ((S(x-1,y-1) + 2 S(x,y-1)) + S(x+1,y-1)), times 0.25f
+ *     (S: the smoothed image, coordinates clamped), m = sqrtf(gx gx + gy gy).
+ * One launch for all views.  No host synchronisation.
+ *
+ * cgs_edge_trace: gx, gy, m (finite) -> e, float32 [height,width] in [0,1].  With ax = |gx|, ay = |gy|, T = 0.41421357f:
+ *   thin != 0: the neighbour pair of a pixel is (x-1,y),(x+1,y) when ay <= T ax, else (x,y-1),(x,y+1) when ax <= T ay,
+ *     else (x-1,y-1),(x+1,y+1) when gx gy > 0, else (x+1,y-1),(x-1,y+1); a neighbour outside the image has magnitude 0;
+ *     m' = m iff m > m(first) and m >= m(second), else 0.  thin == 0: m' = m.
+ *   candidates: m' >= low; strong: m' >= high; a candidate is kept iff its 8-connected component of candidates holds a
+ *     strong pixel; e = min(m' / high, 1) for kept pixels, 0 elsewhere.
+ * Launches: one classification (m' into `e`, a state byte per pixel into `state`: 0 none, 1 candidate, 2 kept), then
+ * propagation rounds, each one launch that settles every 64x16 tile against its 1-pixel halo and sets *changed_flag
+ * (device, one int) when a tile changed, followed by a 4-byte readback and a stream synchronisation; rounds repeat until
+ * one leaves the flag 0; then one launch turns m' into e.  The set of kept pixels does not depend on the order of
+ * propagation.  RETURNS the number of propagation rounds (>= 1) on success.  Not capturable into a graph.
+ *
+ * Both: n_views outside [1, CGS_EDGE_MAX_VIEWS], a NULL table / taps / changed_flag / image pointer, height or width
+ * <= 0, channels other than 1, 3, 4, radius outside [0, CGS_EDGE_MAX_RADIUS], low <= 0, low > high or a threshold that
+ * is NaN are CGS_ERR_INVALID_ARGUMENT, rejected before anything is launched.
+ * ------------------------------------------------------------------------------------------------ */
+#define CGS_EDGE_MAX_VIEWS 24
+#define CGS_EDGE_MAX_RADIUS 12
+typedef struct cgs_edge_gradient_view {
+    const uint8_t* pixels;   /* [height,width,channels] */
+    float* gx;               /* [height,width] */
+    float* gy;
+    float* m;
+    int height;
+    int width;
+    int channels;
+    int reserved;
+} cgs_edge_gradient_view;
+typedef struct cgs_edge_trace_view {
+    const float* gx;   /* [height,width] */
+    const float* gy;
+    const float* m;
+    float* e;          /* [height,width]; holds m' between the launches */
+    uint8_t* state;    /* [height,width] bytes of scratch; no initialisation needed */
+    int height;
+    int width;
+} cgs_edge_trace_view;
+int cgs_edge_gradients(int n_views, const cgs_edge_gradient_view* views /*host, [n_views]*/,
+                       const float* taps /*host, [2 radius + 1]*/, int radius, void* stream);
+int cgs_edge_trace(int n_views, const cgs_edge_trace_view* views /*host, [n_views]*/, float low, float high, int thin,
+                   int* changed_flag /*device, [1]*/, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
