@@ -106,6 +106,11 @@ SIGNATURES = {
     "cgs_undistort_images": (_i, [_i, _vp, _f, _vp, _vp]),
     "cgs_edge_gradients": (_i, [_i, _vp, _vp, _i, _vp]),
     "cgs_edge_trace": (_i, [_i, _vp, _f, _f, _i, _vp, _vp]),
+    "cgs_point_mask": (_i, [_i, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp]),
+    "cgs_edt_workspace_bytes": (C.c_size_t, [_i, _i, _i]),
+    "cgs_edt_squared": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp]),
+    "cgs_edge_score_workspace_bytes": (C.c_size_t, [_i]),
+    "cgs_edge_score_reduce": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 
@@ -143,6 +148,9 @@ UNDISTORT_MAX_VIEWS = 24   # CGS_UNDISTORT_MAX_VIEWS
 UNDISTORT_MAX_CHANNELS = 4   # CGS_UNDISTORT_MAX_CHANNELS
 EDGE_MAX_VIEWS = 24   # CGS_EDGE_MAX_VIEWS
 EDGE_MAX_RADIUS = 12   # CGS_EDGE_MAX_RADIUS
+EDT_INF = 2147483647   # CGS_EDT_INF
+EDT_MAX_SIZE = 16384   # CGS_EDT_MAX_SIZE
+EDGE_SCORE_MAX_TOL = 8   # CGS_EDGE_SCORE_MAX_TOL
 REPORT_PANELS = ("render", "ground_truth", "depth", "rend_dir", "rend_alpha")   # panel order of cgs_report_panels
 
 _lib = None

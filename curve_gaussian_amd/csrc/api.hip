@@ -1785,4 +1785,84 @@ int cgs_edge_trace(int n_views, const cgs_edge_trace_view* views, float low, flo
     return rounds;
 }
 
+int cgs_point_mask(int P, const float* points, int V, const double* intr, const double* w2c, int height, int width,
+                   uint8_t* mask_out, int* kept, void* stream_) {
+    if (P < 0 || V < 0) {
+        set_error("cgs_point_mask: invalid argument (P=%d, V=%d)", P, V);
+        return CGS_ERR_INVALID_ARGUMENT;
+    }
+    if (V == 0) return CGS_OK;
+    if (height <= 0 || width <= 0) {
+        set_error("cgs_point_mask: invalid argument (height=%d, width=%d)", height, width);
+        return CGS_ERR_INVALID_ARGUMENT;
+    }
+    if (!intr || !w2c || !mask_out || (P > 0 && !points)) {
+        set_error("cgs_point_mask: invalid argument (NULL pointer)");
+        return CGS_ERR_INVALID_ARGUMENT;
+    }
+    if (launch_point_mask((hipStream_t)stream_, P, points, V, intr, w2c, height, width, mask_out, kept) != hipSuccess) {
+        set_error("cgs_point_mask: clearing the mask failed");
+        return CGS_ERR_HIP;
+    }
+    if (!check_launch("point_mask", false, (hipStream_t)stream_)) return CGS_ERR_HIP;
+    return CGS_OK;
+}
+
+static bool edt_size_ok(int height, int width) {
+    return height >= 1 && height <= CGS_EDT_MAX_SIZE && width >= 1 && width <= CGS_EDT_MAX_SIZE;
+}
+
+size_t cgs_edt_workspace_bytes(int V, int height, int width) {
+    if (V < 0 || !edt_size_ok(height, width)) return 0;
+    return edt_workspace_bytes(V, height, width);
+}
+
+int cgs_edt_squared(int V, int height, int width, const uint8_t* mask, void* workspace, int32_t* dist2_out, void* stream_) {
+    if (V < 0 || !edt_size_ok(height, width)) {
+        set_error("cgs_edt_squared: invalid argument (V=%d, height=%d, width=%d; sizes lie in [1, %d])", V, height, width,
+                  CGS_EDT_MAX_SIZE);
+        return CGS_ERR_INVALID_ARGUMENT;
+    }
+    if (V == 0) return CGS_OK;
+    if (!mask || !workspace || !dist2_out) {
+        set_error("cgs_edt_squared: invalid argument (NULL pointer)");
+        return CGS_ERR_INVALID_ARGUMENT;
+    }
+    launch_edt_squared((hipStream_t)stream_, V, height, width, mask, workspace, dist2_out);
+    if (!check_launch("edt_squared", false, (hipStream_t)stream_)) return CGS_ERR_HIP;
+    return CGS_OK;
+}
+
+size_t cgs_edge_score_workspace_bytes(int V) { return edge_score_workspace_bytes(V); }
+
+int cgs_edge_score_reduce(int V, int height, int width, const uint8_t* pred_mask, const uint8_t* det_mask,
+                          const int32_t* pred_dist2, const int32_t* det_dist2, int n_tol, const int* tol2, void* workspace,
+                          int64_t* counts, double* sums, uint8_t* both_nonempty, void* stream_) {
+    if (V < 0 || !edt_size_ok(height, width) || n_tol < 0 || n_tol > CGS_EDGE_SCORE_MAX_TOL) {
+        set_error("cgs_edge_score_reduce: invalid argument (V=%d, height=%d, width=%d, n_tol=%d)", V, height, width, n_tol);
+        return CGS_ERR_INVALID_ARGUMENT;
+    }
+    if (n_tol > 0 && !tol2) {
+        set_error("cgs_edge_score_reduce: invalid argument (NULL pointer)");
+        return CGS_ERR_INVALID_ARGUMENT;
+    }
+    for (int t = 0; t < n_tol; t++)
+        if (tol2[t] < 0) {
+            set_error("cgs_edge_score_reduce: invalid argument (tol2[%d]=%d)", t, tol2[t]);
+            return CGS_ERR_INVALID_ARGUMENT;
+        }
+    if (V == 0) return CGS_OK;
+    if (!pred_mask || !det_mask || !pred_dist2 || !det_dist2 || !workspace || !counts || !sums || !both_nonempty) {
+        set_error("cgs_edge_score_reduce: invalid argument (NULL pointer)");
+        return CGS_ERR_INVALID_ARGUMENT;
+    }
+    if (launch_edge_score_reduce((hipStream_t)stream_, V, height, width, pred_mask, det_mask, pred_dist2, det_dist2, n_tol,
+                                 tol2, workspace, counts, sums, both_nonempty) != hipSuccess) {
+        set_error("cgs_edge_score_reduce: clearing the counters failed");
+        return CGS_ERR_HIP;
+    }
+    if (!check_launch("edge_score_reduce", false, (hipStream_t)stream_)) return CGS_ERR_HIP;
+    return CGS_OK;
+}
+
 }  // extern "C"

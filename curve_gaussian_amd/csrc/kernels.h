@@ -205,4 +205,15 @@ void launch_edge_gradients(hipStream_t s, int n_views, const cgs_edge_gradient_v
 int launch_edge_trace(hipStream_t s, int n_views, const cgs_edge_trace_view* views_host, float low, float high, int thin,
                       int* changed_flag, hipError_t* err);
 
+// edge_score.hip
+hipError_t launch_point_mask(hipStream_t s, int P, const float* points, int V, const double* intr, const double* w2c,
+                             int height, int width, uint8_t* mask, int* kept);
+size_t edt_workspace_bytes(int V, int height, int width);
+void launch_edt_squared(hipStream_t s, int V, int height, int width, const uint8_t* mask, void* workspace, int* dist2);
+size_t edge_score_workspace_bytes(int V);
+hipError_t launch_edge_score_reduce(hipStream_t s, int V, int height, int width, const uint8_t* pred_mask,
+                                    const uint8_t* det_mask, const int* pred_dist2, const int* det_dist2, int n_tol,
+                                    const int* tol2, void* workspace, int64_t* counts, double* sums,
+                                    uint8_t* both_nonempty);
+
 }  // namespace cgs

@@ -22,6 +22,7 @@
 // reaches the result: the output depends only on the set of points in each pixel, so two runs are bit-identical.  Pixel
 // offsets are 64-bit; list offsets are 32-bit because a chunk holds at most 2^31 (view, point) pairs.
 #include "kernels.h"
+#include "point_projection.h"
 
 #include <math.h>
 
@@ -36,33 +37,7 @@ constexpr int NV_POINT_BLOCKS_MAX = 1024;      // grid.x of the projection passe
 constexpr long long NV_MAX_PAIRS = 1LL << 31;  // (view, point) pairs per chunk: 32-bit list offsets
 constexpr int NV_MAX_VIEWS = 65535;            // views per launch: grid.y
 
-struct NvCam {
-    double m[12];   // [R | T], row-major 3x4
-    double f[4];    // fx, fy, cx, cy
-};
-
-__device__ inline void nv_load_cam(NvCam& c, const double* __restrict__ intr, const double* __restrict__ w2c, int v) {
-#pragma unroll
-    for (int k = 0; k < 12; k++) c.m[k] = w2c[12 * (size_t)v + k];
-#pragma unroll
-    for (int k = 0; k < 4; k++) c.f[k] = intr[4 * (size_t)v + k];
-}
-
-// True if the point is kept; (u, v) as the reference computes them.
-__device__ inline bool nv_project(const NvCam& c, const float* __restrict__ pts, long long i, double wd, double hd,
-                                  double& u, double& v) {
-#pragma clang fp contract(off)
-    const double X = (double)pts[3 * i + 0], Y = (double)pts[3 * i + 1], Z = (double)pts[3 * i + 2];
-    const double c0 = ((c.m[0] * X + c.m[1] * Y) + c.m[2] * Z) + c.m[3];
-    const double c1 = ((c.m[4] * X + c.m[5] * Y) + c.m[6] * Z) + c.m[7];
-    const double c2 = ((c.m[8] * X + c.m[9] * Y) + c.m[10] * Z) + c.m[11];
-    if (c2 <= 0.0) return false;
-    const double x = c0 / c2;
-    const double y = c1 / c2;
-    u = c.f[0] * x + c.f[2];
-    v = c.f[1] * y + c.f[3];
-    return u >= 0.0 && u < wd && v >= 0.0 && v < hd;   // NaN fails every comparison
-}
+// NvCam, nv_load_cam, nv_project: point_projection.h (shared with edge_score.hip)
 
 // uv[v][i] = (u, v) of a kept point, (NaN, NaN) for a dropped one.
 __global__ void __launch_bounds__(NV_BLOCK) k_nv_project(int P, const float* __restrict__ pts,

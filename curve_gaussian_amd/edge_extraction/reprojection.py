@@ -1,0 +1,283 @@
+"""Reprojection score of the extracted edges: ``parametric_edges.json`` projected into every camera of a scan and compared,
+in pixels, with that camera's edge map -- precision, recall and F-score at pixel tolerances, 2D accuracy / completeness
+(Chamfer) in pixels.  It needs no 3D ground truth, so it also scores Replica, COLMAP and photograph-only scans, and it
+scores the product's output (after merging, line fitting, endpoint merging and the visibility check), not the Gaussian
+render.  The reference has no counterpart: its eval_replica.py stops at pictures.
+
+The edges are sampled as the novel-view code samples them (``abc.pred_points_and_directions``), every point the projection
+rule of ``cgs_project_points`` keeps marks its pixel (``ops.edge_score.point_masks``), a pixel of the edge map is detected
+when e > edge_threshold with e = 1 - u/255 (DexiNed) or u/255 (PidiNet) -- the conversions of ``para_edge`` -- and
+``ops.edge_score.score_masks`` compares the two masks; its docstring freezes the aggregate.
+
+KNOWN LIMIT: there is no depth.  An edge hidden behind a surface still projects into the view, finds no detected pixel
+there and counts against precision and accuracy.
+
+``python -m curve_gaussian_amd.edge_extraction.reprojection --base_dir <predictions> --dataset_dir <scans>`` scores every
+scan, writes ``<base_dir>/<scan>/reprojection_score.json`` and prints one line per scan and their mean."""
+import argparse
+import json
+import logging
+import math
+import os
+import sys
+
+import numpy as np
+import torch
+
+from ..ops import edge_score as ES
+from ..scene.dataset_io import fov2focal
+from .abc import pred_points_and_directions
+from .novel_view import NovelViewCamera, camera_arrays, replica_scans
+from .para_edge import EDGE_MAX_THRESHOLD, edge_map_paths, get_edge_maps
+
+log = logging.getLogger(__name__)
+
+SAMPLE_RESOLUTION = 0.0005   # the novel views' Replica value (eval_replica.py:113)
+LAYOUTS = ("emap", "colmap")
+SCORE_FILE = "reprojection_score.json"
+
+
+def detected_lut(detector, edge_threshold):
+    """bool [256]: is a stored byte u a detected edge pixel?  e > edge_threshold with e = 1 - u/255.0 (DexiNed) or u/255.0
+    (PidiNet) in float64, the conversions of para_edge / cgs_edge_visibility."""
+    u = np.arange(256, dtype=np.float64)
+    if detector == "DexiNed":
+        e = 1 - u / 255.0
+    elif detector == "PidiNet":
+        e = u / 255.0
+    else:
+        raise ValueError(f"Unknown detector: {detector}")
+    return e > float(edge_threshold)
+
+
+def _pred_points(pred, sample_resolution):
+    return np.ascontiguousarray(pred_points_and_directions(pred, sample_resolution).points, np.float32).reshape(-1, 3)
+
+
+def _json_number(x):
+    x = float(x)
+    return x if math.isfinite(x) else None
+
+
+def score_edges(pred, cameras, edge_maps_u8, detector, tolerances_px=(1, 2, 4), edge_threshold=EDGE_MAX_THRESHOLD,
+                sample_resolution=SAMPLE_RESOLUTION, device=None, backend="gpu", budget_bytes=None):
+    """pred: a ``parametric_edges.json`` path or its dict.  cameras: ``NovelViewCamera`` s (R, T world -> camera; fx, fy, cx,
+    cy; size).  edge_maps_u8: one uint8 [H,W] map per camera (a list, or an [V,H,W] array), the stored bytes of the
+    detector's maps, each of its camera's size.  Returns {"aggregate": ops.edge_score's aggregate over all views,
+    "views": one row per camera in order (name, width, height, kept_points, n_pred, n_det, pred_hits, det_hits,
+    accuracy_px, completeness_px, both_nonempty), "settings"}.  Views of one size are scored together, ``budget_bytes``
+    (default ops.edge_score.BYTE_BUDGET) of masks and distance transforms at a time.  ``backend``: "gpu" (HIP; ``device``)
+    or "host" (numpy)."""
+    ES._check_backend(backend)
+    tolerances_px = [float(t) for t in tolerances_px]
+    ES.tolerances_squared(tolerances_px)
+    lut = detected_lut(detector, edge_threshold)
+    cameras = list(cameras)
+    maps = [np.asarray(m) for m in edge_maps_u8]
+    if len(maps) != len(cameras):
+        raise ValueError(f"score_edges: {len(cameras)} cameras and {len(maps)} edge maps")
+    for c, m in zip(cameras, maps):
+        if m.dtype != np.uint8 or m.shape != (c.height, c.width):
+            raise ValueError(f"score_edges: the edge map of {c.name} must be uint8 [{c.height},{c.width}] (got {m.dtype} "
+                             f"{m.shape})")
+    pts = _pred_points(pred, sample_resolution)
+    if backend == "gpu":
+        device = ES._device_for([], "score_edges", device)
+        pts_b = torch.from_numpy(pts).to(device)
+    else:
+        pts_b = pts
+    budget = ES.BYTE_BUDGET if budget_bytes is None else int(budget_bytes)
+    by_size = {}
+    for v, c in enumerate(cameras):
+        by_size.setdefault((c.height, c.width), []).append(v)
+    V, n_tol = len(cameras), len(tolerances_px)
+    per_view = {"n_pred": np.zeros(V, np.int64), "n_det": np.zeros(V, np.int64), "pred_hits": np.zeros((V, n_tol), np.int64),
+                "det_hits": np.zeros((V, n_tol), np.int64), "sum_pred_to_det": np.zeros(V, np.float64),
+                "sum_det_to_pred": np.zeros(V, np.float64), "both_nonempty": np.zeros(V, bool)}
+    kept = np.zeros(V, np.int64)
+    for (H, W), idx in by_size.items():
+        per = max(1, budget // (ES.BYTES_PER_PIXEL * H * W))
+        for b in range(0, len(idx), per):
+            sel = idx[b:b + per]
+            intr, w2c = camera_arrays([cameras[v] for v in sel])
+            pm, k = ES.point_masks(pts_b, intr, w2c, H, W, backend=backend, device=device, return_kept=True)
+            dm = torch.from_numpy(lut[np.stack([maps[v] for v in sel])].astype(np.uint8))
+            res = ES.score_masks(pm, dm, tolerances_px, backend=backend, device=device, budget_bytes=budget)
+            kept[sel] = k.cpu().numpy()
+            for name, a in per_view.items():
+                a[sel] = res[name].numpy()
+    agg = ES.aggregate_scores(tolerances_px, **per_view)
+    rows = []
+    for v, c in enumerate(cameras):
+        both = bool(per_view["both_nonempty"][v])
+        rows.append({"name": c.name, "width": int(c.width), "height": int(c.height), "kept_points": int(kept[v]),
+                     "n_pred": int(per_view["n_pred"][v]), "n_det": int(per_view["n_det"][v]),
+                     "pred_hits": [int(h) for h in per_view["pred_hits"][v]],
+                     "det_hits": [int(h) for h in per_view["det_hits"][v]],
+                     "accuracy_px": float(per_view["sum_pred_to_det"][v] / per_view["n_pred"][v]) if both else float("nan"),
+                     "completeness_px": float(per_view["sum_det_to_pred"][v] / per_view["n_det"][v]) if both else float("nan"),
+                     "both_nonempty": both})
+    settings = {"detector": detector, "tolerances_px": tolerances_px, "edge_threshold": float(edge_threshold),
+                "sample_resolution": float(sample_resolution), "backend": backend, "points": int(pts.shape[0])}
+    return {"aggregate": agg, "views": rows, "settings": settings}
+
+
+# ------------------------------------------------------------------------------------------------ cameras and maps of a scan
+def scene_cameras(cams):
+    """(NovelViewCamera s, uint8 maps) of the cameras a Scene trains on (``EdgeCamera``: read_emap, read_colmap): R is stored
+    transposed there, the focal lengths are those of the field of view at the map's size and the principal point is the
+    centre -- the camera the rasterizer uses; the map is channel 0 of ``original_image`` (a stored byte / 255), back as a
+    byte."""
+    out, maps = [], []
+    for c in cams:
+        H, W = int(c.image_height), int(c.image_width)
+        out.append(NovelViewCamera(c.image_name, np.ascontiguousarray(np.asarray(c.R, np.float64).T),
+                                   np.asarray(c.T, np.float64), fov2focal(c.FoVx, W), fov2focal(c.FoVy, H), W / 2.0, H / 2.0,
+                                   W, H))
+        maps.append(torch.round(c.original_image[0].detach().float().cpu() * 255.0).clamp_(0, 255).to(torch.uint8).numpy())
+    return out, maps
+
+
+def emap_cameras(scan_dir, detector):
+    """(NovelViewCamera s, uint8 [F,H,W] maps) of an EMAP scan through ``get_edge_maps``: K = intrinsics[:3,:3] and
+    w2c = inv(camtoworld), as the visibility check forms them; a view is named by its frame's ``rgb_path``."""
+    maps, intrinsics, camtoworld, h, w = get_edge_maps(scan_dir, detector)
+    meta, _ = edge_map_paths(scan_dir, detector)
+    cams = []
+    for fr, K, c2w in zip(meta["frames"], intrinsics, camtoworld):
+        w2c = np.linalg.inv(np.asarray(c2w, np.float64))
+        cams.append(NovelViewCamera(os.path.basename(fr["rgb_path"]), np.ascontiguousarray(w2c[:3, :3]), w2c[:3, 3].copy(),
+                                    float(K[0][0]), float(K[1][1]), float(K[0][2]), float(K[1][2]), w, h))
+    return cams, maps
+
+
+def colmap_scan_cameras(scan_dir, detector, undistort=False, backend="gpu", resolution=-1):
+    """(NovelViewCamera s, uint8 maps) of a COLMAP or Replica scan through ``read_colmap`` (every image; with ``undistort``
+    the maps are resampled through each camera's lens model first, on ``backend``)."""
+    from ..scene.colmap_io import read_colmap
+    train, _, _, _ = read_colmap(scan_dir, detector=detector, resolution=resolution, undistort=undistort,
+                                 undistort_backend=backend)
+    return scene_cameras(train)
+
+
+def write_score(path, result):
+    """The result of score_edges (or a dict of them) as JSON; NaN is written as null."""
+    def clean(x):
+        if isinstance(x, dict):
+            return {k: clean(v) for k, v in x.items()}
+        if isinstance(x, (list, tuple)):
+            return [clean(v) for v in x]
+        if isinstance(x, float):
+            return _json_number(x)
+        return x
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w") as f:
+        json.dump(clean(result), f, indent=1)
+
+
+def score_scan(base_dir, dataset_dir, scan, layout="emap", detector="DexiNed", undistort=False, tolerances_px=(1, 2, 4),
+               edge_threshold=EDGE_MAX_THRESHOLD, sample_resolution=SAMPLE_RESOLUTION, device=None, backend="gpu",
+               resolution=-1):
+    """Scores ``<base_dir>/<scan>/parametric_edges.json`` against the ``detector`` edge maps of ``<dataset_dir>/<scan>`` and
+    writes ``<base_dir>/<scan>/reprojection_score.json`` = {"scan", "aggregate", "views", "settings"}.  ``layout``: "emap"
+    (meta_data.json; cameras and maps through get_edge_maps) or "colmap" (sparse/0, also Replica; through read_colmap, with
+    ``undistort`` and ``resolution`` as there).  Returns the dict, or None -- after reporting it -- for a scan without a
+    prediction, as the reference's tools skip one."""
+    ES._check_backend(backend)
+    if layout not in LAYOUTS:
+        raise ValueError(f"unknown layout {layout!r}: expected one of {LAYOUTS}")
+    path = os.path.join(base_dir, scan, "parametric_edges.json")
+    if not os.path.exists(path):
+        log.info(f"Invalid prediction at {scan}")
+        return None
+    scan_dir = os.path.join(dataset_dir, scan)
+    if layout == "emap":
+        if undistort:
+            raise ValueError("undistort applies to the colmap layout only")
+        cams, maps = emap_cameras(scan_dir, detector)
+    else:
+        cams, maps = colmap_scan_cameras(scan_dir, detector, undistort, backend, resolution)
+    res = score_edges(path, cams, maps, detector, tolerances_px, edge_threshold, sample_resolution, device, backend)
+    res["settings"].update({"layout": layout, "undistort": bool(undistort)})
+    out = {"scan": scan, **res}
+    write_score(os.path.join(base_dir, scan, SCORE_FILE), out)
+    return out
+
+
+def score_scene(model_path, scene, detector, **kw):
+    """The driver's ``--reprojection_score``: ``<model_path>/parametric_edges.json`` against the cameras the scene trained
+    on and, separately, its test cameras (the held-out ones under ``--eval``; "test" is null when there are none).
+    Writes ``<model_path>/reprojection_score.json`` = {"train": ..., "test": ...} and returns it."""
+    pred = os.path.join(model_path, "parametric_edges.json")
+    out = {}
+    for split, cams in (("train", scene.getTrainCameras()), ("test", scene.getTestCameras())):
+        out[split] = score_edges(pred, *scene_cameras(cams), detector, **kw) if len(cams) else None
+    write_score(os.path.join(model_path, SCORE_FILE), out)
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ command line
+def scan_line(scan, agg):
+    parts = [f"{scan}: views {agg['views']}"]
+    for t, p, r, f in zip(agg["tolerances_px"], agg["precision"], agg["recall"], agg["fscore"]):
+        parts.append(f"P/R/F @ {t:g} px: {p:.4f} {r:.4f} {f:.4f}")
+    parts.append(f"Accuracy: {agg['accuracy_px']:.4f} px")
+    parts.append(f"Completeness: {agg['completeness_px']:.4f} px")
+    parts.append(f"Chamfer: {agg['chamfer_px']:.4f} px ({agg['chamfer_views']} views)")
+    return ", ".join(parts)
+
+
+def summary_lines(aggregates):
+    """The mean over the scored scans of every aggregate figure (NaN figures are left out of their mean)."""
+    if not aggregates:
+        return ["Summary: no scan scored."]
+    mean = lambda xs: float(np.nanmean(xs)) if np.isfinite(xs).any() else float("nan")
+    out = [f"Summary (mean over {len(aggregates)} scans):"]
+    for k, t in enumerate(aggregates[0]["tolerances_px"]):
+        for name, key in (("Precision", "precision"), ("Recall", "recall"), ("F-Score", "fscore")):
+            out.append(f"  {name} @ {t:g} px: {mean(np.array([a[key][k] for a in aggregates], np.float64)):.4f}")
+    for name, key in (("Accuracy", "accuracy_px"), ("Completeness", "completeness_px"), ("Chamfer", "chamfer_px")):
+        out.append(f"  {name}: {mean(np.array([a[key] for a in aggregates], np.float64)):.4f} px")
+    return out
+
+
+def dataset_scans(dataset_dir, layout, scans_file=None):
+    """The lines of `scans_file`, or every scan directory of `dataset_dir` of that layout, sorted."""
+    if scans_file is not None or layout == "colmap":
+        return replica_scans(dataset_dir, scans_file)
+    return sorted(f.name for f in os.scandir(dataset_dir)
+                  if f.is_dir() and os.path.isfile(os.path.join(f.path, "meta_data.json")))
+
+
+def parser():
+    ap = argparse.ArgumentParser(description="Score parametric edges in 2D against a scan's edge maps.")
+    ap.add_argument("--base_dir", default="./output", help="directory holding <scan>/parametric_edges.json")
+    ap.add_argument("--dataset_dir", required=True, help="directory holding the scans")
+    ap.add_argument("--scans", default=None, help="file with one scan name per line (default: every scan of --dataset_dir)")
+    ap.add_argument("--layout", choices=LAYOUTS, default="emap")
+    ap.add_argument("--detector", default="DexiNed")
+    ap.add_argument("--tolerances", nargs="+", type=float, default=[1, 2, 4], help="pixel tolerances")
+    ap.add_argument("--edge_threshold", type=float, default=EDGE_MAX_THRESHOLD)
+    ap.add_argument("--undistort", action="store_true", help="colmap layout: resample the edge maps through the lens model")
+    ap.add_argument("--backend", choices=ES.SCORE_BACKENDS, default="gpu")
+    return ap
+
+
+def main(argv=None):
+    args = parser().parse_args(argv)
+    aggregates = []
+    for scan in dataset_scans(args.dataset_dir, args.layout, args.scans):
+        res = score_scan(args.base_dir, args.dataset_dir, scan, args.layout, args.detector, args.undistort, args.tolerances,
+                         args.edge_threshold, backend=args.backend)
+        if res is None:
+            print(f"Invalid prediction at {scan}")
+            continue
+        aggregates.append(res["aggregate"])
+        print(scan_line(scan, res["aggregate"]))
+    for line in summary_lines(aggregates):
+        print(line)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -329,6 +329,10 @@ def build_parser():
     p.add_argument("--report_dir", default=None,
                    help="write the report's summaries here at every test iteration: scalars.jsonl and, per view, the render, "
                         "ground-truth, depth, direction and alpha panels as images/iter_{N}/*.png")
+    p.add_argument("--reprojection_score", action="store_true",
+                   help="after the export, score parametric_edges.json in 2D against the edge maps of the train cameras and, "
+                        "separately, of the test cameras (the held-out ones under --eval): reprojection_score.json in the "
+                        "model directory")
     return p
 
 
@@ -354,9 +358,15 @@ def main(argv=None):
     if args.report_dir:
         from .evaluation import ReportDirWriter
         writer = ReportDirWriter(args.report_dir)
-    training(dataset, opt, args.test_iterations, args.save_iterations, args.checkpoint_iterations, args.start_checkpoint,
-             backend=args.backend, seed=args.seed, quiet=args.quiet, draw=args.draw_snapshots,
-             topology_backend=args.topology_backend, report_writer=writer)
+    out = training(dataset, opt, args.test_iterations, args.save_iterations, args.checkpoint_iterations, args.start_checkpoint,
+                   backend=args.backend, seed=args.seed, quiet=args.quiet, draw=args.draw_snapshots,
+                   topology_backend=args.topology_backend, report_writer=writer)
+    if args.reprojection_score:
+        from .edge_extraction.reprojection import scan_line, score_scene
+        scores = score_scene(dataset.model_path, out["scene"], dataset.detector)
+        for split, res in scores.items():
+            if res is not None:
+                print(scan_line(split, res["aggregate"]))
     print("\nTraining complete.")
 
 

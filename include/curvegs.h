@@ -824,6 +824,59 @@ int cgs_edge_gradients(int n_views, const cgs_edge_gradient_view* views /*host, 
 int cgs_edge_trace(int n_views, const cgs_edge_trace_view* views /*host, [n_views]*/, float low, float high, int thin,
                    int* changed_flag /*device, [1]*/, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Reprojection score of extracted edges: the edges projected into every camera against that camera's edge map, in pixels
+ * (precision / recall / F-score at pixel tolerances, 2D accuracy / completeness).  No ground truth in 3D is needed.  The
+ * reference has no counterpart.  Three entry points; masks are uint8 [V,height,width], nonzero = set, all views of a call
+ * share one size.  All of them: caller's stream, no allocation, no host synchronisation.
+ *
+ * cgs_point_mask builds the prediction mask: mask_out[v][floor(v_px)][floor(u_px)] = 1 for every point that
+ * cgs_project_points keeps in view v (the same device function: float64, the same operation order, no FMA contraction),
+ * 0 elsewhere; the call zeroes the mask itself.  Points that share a pixel store the same byte: plain stores, no atomics
+ * on the mask.  kept (device, [V], may be NULL) receives the number of kept points of each view (integer atomics).
+ * V = 0 is a no-op, P = 0 leaves zero masks; negative sizes, height or width <= 0 and NULL pointers are
+ * CGS_ERR_INVALID_ARGUMENT, rejected before anything is launched.
+ *
+ * cgs_edt_squared is the exact squared Euclidean distance transform: dist2_out[v][y][x] = the minimum over the set pixels
+ * (x', y') of view v of (x - x')^2 + (y - y')^2, CGS_EDT_INF everywhere in a view without a set pixel.  Integer
+ * arithmetic: the result is bit-identical to a brute-force minimum and does not depend on the launch geometry.  Two
+ * passes: per column, the distance g to the nearest set pixel of that column (uint16, in `workspace`,
+ * cgs_edt_workspace_bytes(V, height, width) bytes of device memory, no initialisation needed); per pixel, the minimum of
+ * d^2 + g[x -+ d]^2 outward over d while d^2 is below the best so far.  Cost per pixel: its true distance, O(width) in a
+ * view with (almost) no set pixel.  height and width lie in [1, CGS_EDT_MAX_SIZE], so a finite result is below 2^30.
+ * V = 0 is a no-op; V < 0, a size outside that range and NULL pointers are CGS_ERR_INVALID_ARGUMENT, rejected before
+ * anything is launched.
+ *
+ * cgs_edge_score_reduce reduces every view to its counts and sums.  pred_dist2 is the transform of pred_mask (the distance
+ * to the nearest predicted pixel), det_dist2 that of det_mask.  tol2 (host, n_tol <= CGS_EDGE_SCORE_MAX_TOL values >= 0)
+ * are squared tolerances.  Per view v:
+ *   counts[v] = (n_pred, n_det, pred_hits[0 .. n_tol), det_hits[0 .. n_tol))        int64, 2 + 2 n_tol values
+ *     pred_hits[t] = #{p in pred : det_dist2(p) <= tol2[t]},  det_hits[t] = #{q in det : pred_dist2(q) <= tol2[t]}
+ *   sums[v]   = (sum over p in pred of sqrt((double)det_dist2(p)), sum over q in det of sqrt((double)pred_dist2(q)))
+ *   both_nonempty[v] = 1 when n_pred > 0 and n_det > 0, else 0; such a view keeps n_pred and n_det and gets zero hits
+ *     and zero sums.
+ * Deterministic: integer counts; the float64 sums are partial sums over fixed slices of the view, added in index order by
+ * the view's last workgroup (an integer counter decides which), as cgs_view_metrics does: the bits of view v depend on
+ * view v's size and content only.  `workspace`: cgs_edge_score_workspace_bytes(V) bytes of device memory, no
+ * initialisation needed.  V = 0 is a no-op; V < 0, a size outside [1, CGS_EDT_MAX_SIZE], n_tol outside
+ * [0, CGS_EDGE_SCORE_MAX_TOL], a negative tolerance and NULL pointers are CGS_ERR_INVALID_ARGUMENT, rejected before
+ * anything is launched.
+ * ------------------------------------------------------------------------------------------------ */
+#define CGS_EDT_INF 2147483647 /* INT32_MAX */
+#define CGS_EDT_MAX_SIZE 16384
+#define CGS_EDGE_SCORE_MAX_TOL 8
+int cgs_point_mask(int P, const float* points /*[P,3]*/, int V, const double* intr /*[V,4]*/,
+                   const double* w2c /*[V,12]*/, int height, int width, uint8_t* mask_out /*[V,height,width]*/,
+                   int* kept /*[V] or NULL*/, void* stream);
+size_t cgs_edt_workspace_bytes(int V, int height, int width);
+int cgs_edt_squared(int V, int height, int width, const uint8_t* mask /*[V,height,width]*/, void* workspace,
+                    int32_t* dist2_out /*[V,height,width]*/, void* stream);
+size_t cgs_edge_score_workspace_bytes(int V);
+int cgs_edge_score_reduce(int V, int height, int width, const uint8_t* pred_mask, const uint8_t* det_mask,
+                          const int32_t* pred_dist2, const int32_t* det_dist2, int n_tol, const int* tol2 /*host*/,
+                          void* workspace, int64_t* counts /*[V, 2 + 2 n_tol]*/, double* sums /*[V,2]*/,
+                          uint8_t* both_nonempty /*[V]*/, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
