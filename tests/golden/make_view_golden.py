@@ -57,29 +57,43 @@ def scenes():
     return out
 
 
-def chain(curves, mask_logit, cam, bg, dimg):
-    """The oracle chain -> dict(color, invdepth, all_map, radii, final_T, g_curve_points, g_width, g_opacity[, g_mask], g_means2D)."""
-    leaves = [curves[k].clone().float().requires_grad_(True) for k in ("curve_points", "width", "opacity")]
-    ml = mask_logit.clone().float().requires_grad_(True) if mask_logit is not None else None
-    xyz, rot, scl = TR.prepare_scaling_rot(leaves[0], leaves[1], curves["is_bezier"], M)
+def chain(curves, mask_logit, cam, bg, dimg, m=M, mask_thr=MASK_THR, pull=torch.float32, opac_scale=1.0, decisions=False):
+    """The oracle chain -> dict(color, invdepth, all_map, radii, final_T, g_curve_points, g_width, g_opacity[, g_mask], g_means2D).
+
+    The frozen files are this function under its defaults.  tests/view_ref64.py calls it at other sample counts `m` and with
+    `pull=torch.float64`: the compositor still gets the float32 splat tensors, and its per-splat gradients are pulled back
+    through a float64 copy of the same torch graph (the mask's on / off decisions are those of the float32 forward).
+    `opac_scale` multiplies the splat opacities handed to the compositor and `decisions` adds its per-pixel decisions
+    (n_contrib: the last contributor's list position; n_blended: how many list entries were blended) -- both for
+    tests/test_view_ref64_cpu.py."""
+    def graph(dt, on=None):
+        leaves = [curves[k].clone().to(dt).requires_grad_(True) for k in ("curve_points", "width", "opacity")]
+        ml = mask_logit.clone().to(dt).requires_grad_(True) if mask_logit is not None else None
+        xyz, rot, scl = TR.prepare_scaling_rot(leaves[0], leaves[1], curves["is_bezier"], m)
+        rotn = torch.nn.functional.normalize(rot)
+        opac = torch.sigmoid(leaves[2]).unsqueeze(1).expand(-1, m, -1).reshape(-1, 1)
+        scales = scl
+        if ml is not None:   # gaussian_renderer/__init__.py:72-76 (straight-through estimator)
+            sg = torch.sigmoid(ml)
+            on = (sg > mask_thr) if on is None else on
+            mk = (on.to(dt) - sg).detach() + sg
+            scales = scl * mk.view(-1, 1)
+            opac = opac * mk.view(-1, 1)
+        return leaves, ml, xyz, rot, rotn, opac, scales, on
+    leaves, ml, xyz, rot, rotn, opac, scales, on = graph(torch.float32)
     P = xyz.shape[0]
-    rotn = torch.nn.functional.normalize(rot)
-    opac = torch.sigmoid(leaves[2]).unsqueeze(1).expand(-1, M, -1).reshape(-1, 1)
-    scales = scl
-    if ml is not None:   # gaussian_renderer/__init__.py:72-76 (straight-through estimator)
-        sg = torch.sigmoid(ml)
-        mk = ((sg > MASK_THR).float() - sg).detach() + sg
-        scales = scl * mk.view(-1, 1)
-        opac = opac * mk.view(-1, 1)
     amap = TR.build_all_map(rot.detach(), xyz.detach(), cam.camera_center, cam.world_view_transform).float().contiguous()
     tfx, tfy = tanfov(cam)
     H, W = cam.image_height, cam.image_width
     n = lambda t: np.ascontiguousarray(t.detach().numpy().astype(np.float32))
-    fw = ORA.forward(np.full(3, bg, np.float32), n(xyz), np.ones((P, 1), np.float32), n(opac), n(scales), n(rotn), 1.0, None,
+    opac_in = n(opac) if opac_scale == 1.0 else (n(opac).astype(np.float64) * opac_scale).astype(np.float32)
+    fw = ORA.forward(np.full(3, bg, np.float32), n(xyz), np.ones((P, 1), np.float32), opac_in, n(scales), n(rotn), 1.0, None,
                      n(amap), n(cam.world_view_transform), n(cam.full_proj_transform), tfx, tfy, H, W, None, 0,
                      n(cam.camera_center))
     gr = ORA.backward(fw, np.ascontiguousarray(dimg, np.float32), None, None)
-    t = lambda a: torch.from_numpy(np.asarray(a, np.float32))
+    if pull != torch.float32:
+        leaves, ml, xyz, rot, rotn, opac, scales, on = graph(pull, on)
+    t = lambda a: torch.from_numpy(np.asarray(a, np.float32)).to(pull)
     ((xyz * t(gr["dL_dmeans3D"])).sum() + (scales * t(gr["dL_dscales"])).sum() + (rotn * t(gr["dL_drotations"])).sum()
      + (opac * t(gr["dL_dopacity"])).sum()).backward()
     out = dict(color=fw.color.copy(), invdepth=fw.invdepth.copy(), out_all_map=fw.out_all_map.copy(),
@@ -88,6 +102,12 @@ def chain(curves, mask_logit, cam, bg, dimg):
                g_means2D=np.asarray(gr["dL_dmeans2D"], np.float32))
     if ml is not None:
         out["g_mask"] = ml.grad.numpy()
+    if decisions:
+        from util import near_threshold_pairs, pixel_decisions, radius_margin
+        out["n_contrib"] = fw.n_contrib.copy()
+        out["n_blended"] = pixel_decisions(fw)
+        out["near_pairs"] = near_threshold_pairs(fw)
+        out["radius_margin"] = radius_margin(fw)
     fw.free()
     return out
 

@@ -466,14 +466,14 @@ class _ViewCalls:
     """cgs_view_forward / cgs_view_backward through ctypes on caller-owned buffers, the way bench.py and GraphedTrainStep
     call them (no autograd)."""
 
-    def __init__(self, cp, width, opacity, is_bezier, cam, cap, colors=None, bg=0.0, mask=None):
+    def __init__(self, cp, width, opacity, is_bezier, cam, cap, colors=None, bg=0.0, mask=None, m=12):
         import ctypes as C
         from curve_gaussian_amd import _lib as L
         from curve_gaussian_amd.ops import curve_sampling
         self.L, self.C, self.lib = L, C, L.load()
         lib = self.lib
         self.cam = cam.to(DEV)
-        self.B, self.m = cp.shape[0], 12
+        self.B, self.m = cp.shape[0], m
         self.P = self.B * self.m
         self.H, self.W = cam.image_height, cam.image_width
         tiles = ((self.W + 15) // 16) * ((self.H + 15) // 16)

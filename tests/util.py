@@ -147,6 +147,46 @@ def near_threshold_pairs(fw, window=1e-5):
     return near
 
 
+def pixel_decisions(fw):
+    """[H,W] number of list entries an oracle forward blended into each pixel (alpha >= 1/255 taken, T >= 1e-4 kept); the
+    oracle itself keeps only the last contributor's position (fw.n_contrib).  Same numpy walk as near_threshold_pairs."""
+    H, W = fw.H, fw.W
+    tiles_x = (W + 15) // 16
+    m2, co, pl, ranges = fw.means2D.astype(np.float32), fw.conic_opacity.astype(np.float32), fw.point_list, fw.ranges
+    out = np.zeros((H, W), np.int64)
+    for t, (r0, r1) in enumerate(ranges):
+        if r1 <= r0:
+            continue
+        ty, tx = divmod(t, tiles_x)
+        ys, xs = np.arange(ty * 16, min(H, ty * 16 + 16), dtype=np.float32), np.arange(tx * 16, min(W, tx * 16 + 16), dtype=np.float32)
+        px, py = np.meshgrid(xs, ys)
+        ids = pl[r0:r1]
+        dx = m2[ids, 0][:, None] - px.reshape(1, -1)
+        dy = m2[ids, 1][:, None] - py.reshape(1, -1)
+        c = co[ids]
+        power = np.float32(-0.5) * (c[:, 0:1] * dx * dx + c[:, 2:3] * dy * dy) - c[:, 1:2] * dx * dy
+        alpha = np.minimum(np.float32(0.99), c[:, 3:4] * np.exp(power))
+        blends = (power <= 0) & (alpha >= np.float32(1.0 / 255.0))
+        Tn = np.cumprod(np.where(blends, np.float32(1.0) - alpha, np.float32(1.0)), axis=0, dtype=np.float32)
+        alive = np.logical_and.accumulate(~blends | (Tn >= np.float32(1e-4)), axis=0)     # (the terminating entry is not blended)
+        out[int(ys[0]):int(ys[-1]) + 1, int(xs[0]):int(xs[-1]) + 1] = (blends & alive).sum(0).reshape(len(ys), len(xs))
+    return out
+
+
+def radius_margin(fw):
+    """Smallest relative distance of a visible splat's 3 sigma extent from the integer its radius = ceil(3 sqrt(lambda_max))
+    rounds to (forward.cu:219-221), recomputed in float64 from the conics an oracle forward saved: a splat closer than the
+    arithmetic difference of two implementations may legally get another radius."""
+    co = fw.conic_opacity.astype(np.float64)[fw.radii > 0]
+    if co.shape[0] == 0:
+        return 1.0
+    det_c = co[:, 0] * co[:, 2] - co[:, 1] ** 2          # conic = inverse of the dilated 2D covariance
+    a, b, c = co[:, 2] / det_c, -co[:, 1] / det_c, co[:, 0] / det_c
+    mid = 0.5 * (a + c)
+    r = 3.0 * np.sqrt(mid + np.sqrt(np.maximum(0.1, mid * mid - (a * c - b * b))))
+    return float((np.minimum(np.ceil(r) - r, r - np.floor(r)) / r).min())
+
+
 def carve_offsets(base_ptr_mod, counts_and_sizes):
     """Replicates csrc/common.h::carve (128-byte aligned carve-outs) for tests that decode the scratch buffers."""
     offs = []
