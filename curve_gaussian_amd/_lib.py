@@ -111,6 +111,8 @@ SIGNATURES = {
     "cgs_edt_squared": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp]),
     "cgs_edge_score_workspace_bytes": (C.c_size_t, [_i]),
     "cgs_edge_score_reduce": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cgs_pack_near_bits": (_i, [_i, _i, _i, _vp, _i, _vp, _vp]),
+    "cgs_voxel_votes": (_i, [_i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp]),
 }
 
 
@@ -151,6 +153,7 @@ EDGE_MAX_RADIUS = 12   # CGS_EDGE_MAX_RADIUS
 EDT_INF = 2147483647   # CGS_EDT_INF
 EDT_MAX_SIZE = 16384   # CGS_EDT_MAX_SIZE
 EDGE_SCORE_MAX_TOL = 8   # CGS_EDGE_SCORE_MAX_TOL
+SEED_MAX_VIEWS = 65535   # CGS_SEED_MAX_VIEWS
 REPORT_PANELS = ("render", "ground_truth", "depth", "rend_dir", "rend_alpha")   # panel order of cgs_report_panels
 
 _lib = None

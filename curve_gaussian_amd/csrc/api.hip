@@ -7,6 +7,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cmath>
 #include <map>
 #include <mutex>
 #include <string>
@@ -1862,6 +1863,48 @@ int cgs_edge_score_reduce(int V, int height, int width, const uint8_t* pred_mask
         return CGS_ERR_HIP;
     }
     if (!check_launch("edge_score_reduce", false, (hipStream_t)stream_)) return CGS_ERR_HIP;
+    return CGS_OK;
+}
+
+int cgs_pack_near_bits(int V, int height, int width, const int32_t* dist2, int tol2, uint32_t* bits_out, void* stream_) {
+    if (V < 0 || !edt_size_ok(height, width) || tol2 < 0) {
+        set_error("cgs_pack_near_bits: invalid argument (V=%d, height=%d, width=%d, tol2=%d; sizes lie in [1, %d])", V,
+                  height, width, tol2, CGS_EDT_MAX_SIZE);
+        return CGS_ERR_INVALID_ARGUMENT;
+    }
+    if (V == 0) return CGS_OK;
+    if (!dist2 || !bits_out) {
+        set_error("cgs_pack_near_bits: invalid argument (NULL pointer)");
+        return CGS_ERR_INVALID_ARGUMENT;
+    }
+    launch_pack_near_bits((hipStream_t)stream_, V, height, width, dist2, tol2, bits_out);
+    if (!check_launch("pack_near_bits", false, (hipStream_t)stream_)) return CGS_ERR_HIP;
+    return CGS_OK;
+}
+
+int cgs_voxel_votes(int nx, int ny, int nz, const double* lo, const double* step, int V, const double* intr,
+                    const double* w2c, int height, int width, const uint32_t* bits, int accumulate, uint16_t* seen,
+                    uint16_t* hit, void* stream_) {
+    if (V < 0 || V > CGS_SEED_MAX_VIEWS || nx <= 0 || ny <= 0 || nz <= 0 || !edt_size_ok(height, width)) {
+        set_error("cgs_voxel_votes: invalid argument (dims=%dx%dx%d, V=%d, height=%d, width=%d)", nx, ny, nz, V, height, width);
+        return CGS_ERR_INVALID_ARGUMENT;
+    }
+    if ((long long)nx * ny > INT32_MAX || (long long)nx * ny * nz > INT32_MAX) {   // the first product is below 2^62
+        set_error("cgs_voxel_votes: invalid argument (%dx%dx%d voxels: at most 2^31 - 1)", nx, ny, nz);
+        return CGS_ERR_INVALID_ARGUMENT;
+    }
+    if (!lo || !step || !seen || !hit || (V > 0 && (!intr || !w2c || !bits))) {
+        set_error("cgs_voxel_votes: invalid argument (NULL pointer)");
+        return CGS_ERR_INVALID_ARGUMENT;
+    }
+    for (int a = 0; a < 3; a++)
+        if (!std::isfinite(lo[a]) || !std::isfinite(step[a]) || !(step[a] > 0.0)) {
+            set_error("cgs_voxel_votes: invalid argument (axis %d: lo=%g, step=%g)", a, lo[a], step[a]);
+            return CGS_ERR_INVALID_ARGUMENT;
+        }
+    if (V == 0 && accumulate) return CGS_OK;
+    launch_voxel_votes((hipStream_t)stream_, nx, ny, nz, lo, step, V, intr, w2c, height, width, bits, accumulate, seen, hit);
+    if (!check_launch("voxel_votes", false, (hipStream_t)stream_)) return CGS_ERR_HIP;
     return CGS_OK;
 }
 

@@ -1,0 +1,119 @@
+// Multi-view voxel vote: where do the edge maps of a scan say the edges are?  (include/curvegs.h, cgs_pack_near_bits /
+// cgs_voxel_votes.)  Every voxel centre of a regular grid is projected into every view and counts the views that see it
+// and the views in which it lands within a tolerance of a detected edge pixel.  Two kernels:
+//   k_pack_near_bits   one thread per pixel of the PADDED row (32 * stride pixels, stride = ceil(W / 32) words): the bit is
+//                      dist2 <= tol2 inside the image and 0 in the padding, one wave ballot gives two words, lanes 0 and 32
+//                      store them.  A padded plane is a whole number of words, so the linear pixel index / 32 is the word
+//                      index and a wave may straddle two rows.  Every word is written, padding included: no memset.
+//   k_voxel_votes      one thread per voxel, linear index with x fastest, so the lanes of a wave are neighbours along x and
+//                      gather neighbouring pixels.  The centre is lo + (i + 0.5) * step in float64 without contraction,
+//                      rounded to float32: the point that is projected, by nv_project_xyz (point_projection.h), the device
+//                      function of cgs_project_points / cgs_point_mask.  The thread loops over the views; the camera index
+//                      is wave-uniform, so the 16 doubles of a camera are scalar loads, as in visibility.hip.  Both counts
+//                      stay in registers; one plain 16-bit store each at the end (a read-add-store of the thread's own
+//                      voxel with `accumulate`).  No atomics, no LDS: the result does not depend on the launch geometry.
+//                      The packed masks are the only gathered data: 1600x1200 is 240 KB a view, 24 MB for 100 views.
+// Voxel and map offsets are 64-bit.
+#include <algorithm>
+
+#include "kernels.h"
+#include "point_projection.h"
+
+namespace cgs {
+
+constexpr int SEED_THREADS = 256;        // 4 waves
+constexpr int SEED_MAX_VIEWS = 65535;    // grid.y of the packing launch
+
+struct SeedGrid {  // passed by value
+    double lo[3];
+    double step[3];
+    int nx, ny, nz;
+};
+
+__global__ void __launch_bounds__(SEED_THREADS) k_pack_near_bits(int height, int width, int stride,
+                                                                const int* __restrict__ dist2, int tol2,
+                                                                unsigned int* __restrict__ bits) {
+    const long long padded = (long long)height * stride * 32;   // <= 16384 * 16384: a multiple of 32
+    const long long p = (long long)blockIdx.x * SEED_THREADS + threadIdx.x;
+    const int view = blockIdx.y;
+    bool near = false;
+    if (p < padded) {
+        const int y = (int)(p / (32 * stride)), x = (int)(p - (long long)y * (32 * stride));
+        if (x < width) near = dist2[((size_t)view * (size_t)height + (size_t)y) * (size_t)width + (size_t)x] <= tol2;
+    }
+    const unsigned long long b = __ballot(near);   // every lane of the wave arrives here
+    const int lane = threadIdx.x & 63;
+    if ((lane & 31) == 0 && p < padded)            // p is a multiple of 32 here: p / 32 is this half wave's word
+        bits[(size_t)view * (size_t)height * (size_t)stride + (size_t)(p >> 5)] = (unsigned int)(lane ? b >> 32 : b);
+}
+
+__global__ void __launch_bounds__(SEED_THREADS) k_voxel_votes(const SeedGrid g, int V, const double* __restrict__ intr,
+                                                             const double* __restrict__ w2c, int height, int width,
+                                                             int stride, const unsigned int* __restrict__ bits,
+                                                             int accumulate, unsigned short* __restrict__ seen,
+                                                             unsigned short* __restrict__ hit) {
+#pragma clang fp contract(off)
+    const long long n = (long long)g.nx * g.ny * g.nz;   // <= 2^31 - 1
+    const long long id = (long long)blockIdx.x * SEED_THREADS + threadIdx.x;
+    if (id >= n) return;
+    const int i = (int)(id % g.nx);
+    const long long r = id / g.nx;
+    const int j = (int)(r % g.ny), k = (int)(r / g.ny);
+    // the centre in float64, then the float32 point that the projection contract is written for
+    const double X = (double)(float)(g.lo[0] + ((double)i + 0.5) * g.step[0]);
+    const double Y = (double)(float)(g.lo[1] + ((double)j + 0.5) * g.step[1]);
+    const double Z = (double)(float)(g.lo[2] + ((double)k + 0.5) * g.step[2]);
+    const double wd = (double)width, hd = (double)height;
+    const size_t plane = (size_t)height * (size_t)stride;
+    int n_seen = 0, n_hit = 0;
+    for (int v = 0; v < V; v++) {   // v is uniform: scalar loads of the camera
+        NvCam c;
+        nv_load_cam(c, intr, w2c, v);
+        double pu, pv;
+        if (!nv_project_xyz(c, X, Y, Z, wd, hd, pu, pv)) continue;
+        n_seen++;
+        // 0 <= pu < W and 0 <= pv < H: the pixel is inside the view, its word inside the view's plane
+        const unsigned int px = (unsigned int)floor(pu), py = (unsigned int)floor(pv);
+        const unsigned int w = bits[(size_t)v * plane + (size_t)py * (size_t)stride + (size_t)(px >> 5)];
+        n_hit += (int)((w >> (px & 31u)) & 1u);
+    }
+    if (accumulate) {
+        n_seen += seen[id];
+        n_hit += hit[id];
+    }
+    seen[id] = (unsigned short)n_seen;
+    hit[id] = (unsigned short)n_hit;
+}
+
+void launch_pack_near_bits(hipStream_t s, int V, int height, int width, const int* dist2, int tol2, unsigned int* bits) {
+    const int stride = (width + 31) / 32;
+    const long long padded = (long long)height * stride * 32;
+    const unsigned blocks = (unsigned)((padded + SEED_THREADS - 1) / SEED_THREADS);   // <= 2^28 / 256 + 1
+    const size_t plane = (size_t)height * (size_t)width;
+    ProfScope p("pack_near_bits", s);
+    for (int v0 = 0; v0 < V; v0 += SEED_MAX_VIEWS) {
+        const int nv = std::min(SEED_MAX_VIEWS, V - v0);
+        hipLaunchKernelGGL(k_pack_near_bits, dim3(blocks, nv), dim3(SEED_THREADS), 0, s, height, width, stride,
+                           dist2 + (size_t)v0 * plane, tol2, bits + (size_t)v0 * (size_t)height * (size_t)stride);
+    }
+}
+
+void launch_voxel_votes(hipStream_t s, int nx, int ny, int nz, const double* lo, const double* step, int V,
+                        const double* intr, const double* w2c, int height, int width, const unsigned int* bits,
+                        int accumulate, unsigned short* seen, unsigned short* hit) {
+    SeedGrid g;
+    for (int a = 0; a < 3; a++) {
+        g.lo[a] = lo[a];
+        g.step[a] = step[a];
+    }
+    g.nx = nx;
+    g.ny = ny;
+    g.nz = nz;
+    const long long n = (long long)nx * ny * nz;
+    const unsigned blocks = (unsigned)((n + SEED_THREADS - 1) / SEED_THREADS);   // <= 2^23
+    ProfScope p("voxel_votes", s);
+    hipLaunchKernelGGL(k_voxel_votes, dim3(blocks), dim3(SEED_THREADS), 0, s, g, V, intr, w2c, height, width,
+                       (width + 31) / 32, bits, accumulate, seen, hit);
+}
+
+}  // namespace cgs

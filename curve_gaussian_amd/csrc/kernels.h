@@ -215,5 +215,10 @@ hipError_t launch_edge_score_reduce(hipStream_t s, int V, int height, int width,
                                     const uint8_t* det_mask, const int* pred_dist2, const int* det_dist2, int n_tol,
                                     const int* tol2, void* workspace, int64_t* counts, double* sums,
                                     uint8_t* both_nonempty);
+// edge_seed.hip
+void launch_pack_near_bits(hipStream_t s, int V, int height, int width, const int* dist2, int tol2, unsigned int* bits);
+void launch_voxel_votes(hipStream_t s, int nx, int ny, int nz, const double* lo, const double* step, int V,
+                        const double* intr, const double* w2c, int height, int width, const unsigned int* bits,
+                        int accumulate, unsigned short* seen, unsigned short* hit);
 
 }  // namespace cgs

@@ -1,5 +1,6 @@
 // The pinhole projection of a world point into a camera, shared by every kernel that must agree on which points a view
-// keeps (novel_view.hip: cgs_project_points / cgs_render_points; edge_score.hip: cgs_point_mask).
+// keeps (novel_view.hip: cgs_project_points / cgs_render_points; edge_score.hip: cgs_point_mask; edge_seed.hip:
+// cgs_voxel_votes).
 //
 // Exact, the reference's operation order (eval_ABC.py project_points_to_camera :66-81): X float32 widened to float64,
 // c = R X + T with every row ((r0*X + r1*Y) + r2*Z) + t, dropped if c2 <= 0 (a NaN depth is dropped too: it fails the
@@ -22,11 +23,10 @@ __device__ inline void nv_load_cam(NvCam& c, const double* __restrict__ intr, co
     for (int k = 0; k < 4; k++) c.f[k] = intr[4 * (size_t)v + k];
 }
 
-// True if the point is kept; (u, v) as the reference computes them.
-__device__ inline bool nv_project(const NvCam& c, const float* __restrict__ pts, long long i, double wd, double hd,
-                                  double& u, double& v) {
+// True if the point is kept; (u, v) as the reference computes them.  (X, Y, Z): a float32 point widened to float64.
+__device__ inline bool nv_project_xyz(const NvCam& c, double X, double Y, double Z, double wd, double hd, double& u,
+                                      double& v) {
 #pragma clang fp contract(off)
-    const double X = (double)pts[3 * i + 0], Y = (double)pts[3 * i + 1], Z = (double)pts[3 * i + 2];
     const double c0 = ((c.m[0] * X + c.m[1] * Y) + c.m[2] * Z) + c.m[3];
     const double c1 = ((c.m[4] * X + c.m[5] * Y) + c.m[6] * Z) + c.m[7];
     const double c2 = ((c.m[8] * X + c.m[9] * Y) + c.m[10] * Z) + c.m[11];
@@ -36,6 +36,12 @@ __device__ inline bool nv_project(const NvCam& c, const float* __restrict__ pts,
     u = c.f[0] * x + c.f[2];
     v = c.f[1] * y + c.f[3];
     return u >= 0.0 && u < wd && v >= 0.0 && v < hd;   // NaN fails every comparison
+}
+
+// Point i of a float32 [P,3] array.
+__device__ inline bool nv_project(const NvCam& c, const float* __restrict__ pts, long long i, double wd, double hd,
+                                  double& u, double& v) {
+    return nv_project_xyz(c, (double)pts[3 * i + 0], (double)pts[3 * i + 1], (double)pts[3 * i + 2], wd, hd, u, v);
 }
 
 }  // namespace cgs

@@ -1,0 +1,74 @@
+"""Seed points of a scan from its edge maps, without training: the multi-view voxel vote of ``ops.edge_seed`` as a tool.
+
+    python -m curve_gaussian_amd.edge_seed_cli --scan DIR [--layout emap|colmap] [--backend gpu|host] --out seeds.ply
+
+The cameras and maps are those ``edge_extraction.reprojection`` scores against: ``emap_cameras`` (meta_data.json) or
+``read_colmap`` (sparse/0; ``--undistort`` as there).  The box is ``--bounds``, or ``scene.default_seed_bounds``.  The seeds
+are written as the ASCII PLY of ``edge_points.ply``; the counts are printed.  The defaults are untuned and there is no
+occlusion reasoning (ops/edge_seed.py)."""
+import argparse
+import sys
+
+import numpy as np
+
+from .edge_extraction import reprojection as RP
+from .ops import edge_seed as SD
+from .scene import dataset_io as IO
+
+
+def parser():
+    ap = argparse.ArgumentParser(description="Seed points from a scan's edge maps by a multi-view voxel vote.")
+    ap.add_argument("--scan", required=True, help="the scan directory")
+    ap.add_argument("--layout", choices=RP.LAYOUTS, default="emap")
+    ap.add_argument("--detector", default="DexiNed")
+    ap.add_argument("--backend", choices=SD.SEED_BACKENDS, default="gpu")
+    ap.add_argument("--undistort", action="store_true", help="colmap layout: resample the edge maps through the lens model")
+    ap.add_argument("--out", required=True, help="the PLY file to write")
+    ap.add_argument("--bounds", nargs=6, type=float, default=None, metavar=("X0", "Y0", "Z0", "X1", "Y1", "Z1"))
+    ap.add_argument("--grid", type=int, default=128)
+    ap.add_argument("--tol_px", type=float, default=2.0)
+    ap.add_argument("--min_views", type=int, default=3)
+    ap.add_argument("--min_ratio", type=float, default=0.8)
+    ap.add_argument("--cell", type=int, default=4)
+    ap.add_argument("--max_seeds", type=int, default=20000)
+    ap.add_argument("--edge_threshold", type=float, default=SD.EDGE_MAX_THRESHOLD)
+    return ap
+
+
+def seed_scan(scan_dir, layout="emap", detector="DexiNed", undistort=False, bounds=None, backend="gpu", **options):
+    """(seeds float64 [N,3], info) of the scan at ``scan_dir``; ``options``: seed_points' keywords."""
+    if layout not in RP.LAYOUTS:
+        raise ValueError(f"unknown layout {layout!r}: expected one of {RP.LAYOUTS}")
+    points = None
+    if layout == "emap":
+        if undistort:
+            raise ValueError("undistort applies to the colmap layout only")
+        cams, maps = RP.emap_cameras(scan_dir, detector)
+    else:
+        from .scene.colmap_io import read_colmap
+        train, _, pcd, _ = read_colmap(scan_dir, detector=detector, undistort=undistort, undistort_backend=backend)
+        cams, maps = RP.scene_cameras(train)
+        points = pcd.points
+    if bounds is None:
+        bounds = IO.default_seed_bounds(layout, points)
+    seeds, info = SD.seed_points(cams, maps, detector, bounds, backend=backend, **options)
+    info["bounds"] = [np.asarray(b, np.float64).tolist() for b in bounds]
+    return seeds, info
+
+
+def main(argv=None):
+    args = parser().parse_args(argv)
+    bounds = (args.bounds[:3], args.bounds[3:]) if args.bounds is not None else None
+    seeds, info = seed_scan(args.scan, args.layout, args.detector, args.undistort, bounds, args.backend, grid=args.grid,
+                            tol_px=args.tol_px, min_views=args.min_views, min_ratio=args.min_ratio, cell=args.cell,
+                            max_seeds=args.max_seeds, edge_threshold=args.edge_threshold)
+    IO.write_points_ply(args.out, seeds)
+    print(f"views {info['views']}, grid {info['dims'][0]}x{info['dims'][1]}x{info['dims'][2]}, kept voxels "
+          f"{info['kept_voxels']}, cells {info['cells']}, seeds {info['seeds']}{' (capped)' if info['capped'] else ''}, "
+          f"bounds {info['bounds']}")
+    print(f"Wrote {args.out}")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -1,0 +1,310 @@
+"""Seed points for the curves from a scan's own edge maps: a multi-view voxel vote (cgs_pack_near_bits / cgs_voxel_votes,
+include/curvegs.h; csrc/edge_seed.hip).  The reference has no counterpart: it seeds a fixed 15^3 grid or the SfM cloud.
+
+Definitions (frozen), the same on both back ends bit for bit:
+  grid       ``bounds`` = (lo, hi) float64 [3] each and ``dims`` = (nx, ny, nz) >= 1; step = (hi - lo) / dims in float64;
+             voxel (i, j, k) has the linear index (k ny + j) nx + i and the centre lo + (i + 0.5) step per axis, computed in
+             float64 and rounded to float32 -- the float32 point is what ``project_points`` (ops.edge_score) projects
+  near mask  near[y][x] = (d2[y][x] <= tol2), d2 the ``edt_squared`` transform of the view's detected mask, tol2 =
+             ``tolerances_squared``; one bit per pixel in uint32 words, word w of row y = pixels 32 w .. 32 w + 31, bit b =
+             pixel 32 w + b, row stride ceil(W / 32) words, padding bits 0 (tensors hold the words as int32)
+  votes      seen[g] = the views in which the projection keeps the centre of voxel g; hit[g] = those whose near bit at
+             (floor(v), floor(u)) is set; uint16, at most 65535 views in total
+  selection  kept iff seen >= min_views and hit >= need[seen], need[s] = ceil(min_ratio * s) built in float64
+  thinning   cells of ``cell`` voxels per axis; a cell with kept voxels gives one seed, the mean of their integer
+             coordinates (int64 sums over a count), at lo + (mean + 0.5) step in float64; seeds ordered by cell index;
+             above ``max_seeds`` the cells with the largest summed hit are kept (ties: the lower cell index)
+
+There is NO occlusion reasoning: a voxel behind a surface is seen by the views that look at it through the surface, and
+with few views the back-projections of unrelated edge pixels intersect in empty space ("ghosts"); min_views / min_ratio
+are the only defence.  The curve direction is not seeded.  The defaults of ``seed_points`` are untuned.
+
+Two back ends: ``"gpu"``, HIP, and ``"host"``, numpy -- the same rules, for a machine without a GPU and what the tests hold
+the kernels against.  Selection and thinning are integer numpy on both."""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from .. import _lib as L
+from ..edge_extraction.para_edge import EDGE_MAX_THRESHOLD
+from . import edge_score as ES
+
+SEED_BACKENDS = ES.SCORE_BACKENDS
+MAX_VIEWS = L.SEED_MAX_VIEWS
+MAX_VOXELS = 2 ** 31 - 1
+BYTE_BUDGET = 1 << 30     # bytes of masks, transforms, scratch and bits per chunk of views in seed_points
+BYTES_PER_PIXEL = 8       # uint8 mask, uint16 column pass, int32 transform, one bit (rounded up)
+HOST_SLAB = 1 << 18       # voxels per numpy slab of the host back end
+
+
+def _check_backend(backend):
+    if backend not in SEED_BACKENDS:
+        raise ValueError(f"unknown edge seed backend {backend!r}: expected one of {SEED_BACKENDS}")
+
+
+def bits_stride(width):
+    return (int(width) + 31) // 32
+
+
+# ------------------------------------------------------------------------------------------------ near bits
+def near_bits(dist2, tol_px, backend="gpu", device=None):
+    """dist2: int32 [V,H,W] (tensor or array), the ``edt_squared`` transform of the detected masks.  Returns the packed
+    near masks, int32 [V,H,ceil(W/32)] holding the uint32 words of the module docstring: bit = dist2 <= floor(tol_px^2).
+    ``backend="gpu"``: ``cgs_pack_near_bits``, the result stays on the device; ``backend="host"``: numpy, a CPU tensor."""
+    _check_backend(backend)
+    tol2 = ES.tolerances_squared([tol_px])[0]
+    if isinstance(dist2, np.ndarray):
+        dist2 = torch.from_numpy(np.ascontiguousarray(dist2))
+    if not torch.is_tensor(dist2) or dist2.dtype != torch.int32 or dist2.dim() != 3:
+        raise ValueError("near_bits: dist2 must be an int32 [V,H,W] stack of squared distance transforms")
+    V, H, W = (int(s) for s in dist2.shape)
+    if V > 0:
+        ES._check_size("near_bits", H, W)
+    stride = bits_stride(W)
+    if backend == "host":
+        near = dist2.detach().cpu().numpy() <= tol2
+        padded = np.zeros((V, H, stride * 32), bool)
+        padded[:, :, :W] = near
+        words = np.packbits(padded, axis=-1, bitorder="little").view("<u4")
+        return torch.from_numpy(np.ascontiguousarray(words).view(np.int32).reshape(V, H, stride))
+    dev = ES._device_for([dist2], "near_bits", device)
+    with L.device_guard(dev):
+        dist2 = dist2.to(dev).contiguous()
+        bits = torch.empty((V, H, stride), dtype=torch.int32, device=dev)
+        if V > 0:
+            rc = L.load().cgs_pack_near_bits(V, H, W, L.ptr(dist2), tol2, L.ptr(bits), L.raw_stream(dev))
+            L.check(rc, "cgs_pack_near_bits")
+    return bits
+
+
+def unpack_bits(bits, width):
+    """The inverse of the packing: int32 [V,H,ceil(width/32)] words -> (near bool [V,H,width], padding bool
+    [V,H,32 ceil(width/32) - width]) numpy arrays."""
+    words = bits.detach().cpu().numpy() if torch.is_tensor(bits) else np.asarray(bits)
+    words = np.ascontiguousarray(words).view(np.uint32).astype("<u4")
+    flat = np.unpackbits(words.view(np.uint8), axis=-1, bitorder="little").astype(bool)
+    return flat[..., :int(width)], flat[..., int(width):]
+
+
+# ------------------------------------------------------------------------------------------------ grid and votes
+def _grid(bounds, dims):
+    lo, hi = (np.asarray(b, np.float64).reshape(-1) for b in bounds)
+    if lo.shape != (3,) or hi.shape != (3,):
+        raise ValueError("bounds must be (lo [3], hi [3])")
+    dims = tuple(int(d) for d in dims)
+    if len(dims) != 3 or min(dims) < 1:
+        raise ValueError(f"dims must be three positive integers (got {dims})")
+    if not (np.isfinite(lo).all() and np.isfinite(hi).all() and (hi > lo).all()):
+        raise ValueError(f"bounds must be finite with hi > lo on every axis (got lo={lo.tolist()}, hi={hi.tolist()})")
+    if dims[0] * dims[1] * dims[2] > MAX_VOXELS:
+        raise ValueError(f"a grid holds at most 2^31 - 1 voxels (got {dims})")
+    step = (hi - lo) / np.array(dims, np.float64)
+    if not (np.isfinite(step).all() and (step > 0.0).all()):
+        raise ValueError(f"the voxel size must be finite and positive (got {step.tolist()})")
+    return lo, hi, dims, step
+
+
+def _centres(lo, dims, step, start, stop):
+    g = np.arange(start, stop, dtype=np.int64)
+    ijk = np.stack([g % dims[0], (g // dims[0]) % dims[1], g // (dims[0] * dims[1])], 1).astype(np.float64)
+    return (lo[None, :] + (ijk + 0.5) * step[None, :]).astype(np.float32)   # one rounded operation per ufunc: no FMA
+
+
+def voxel_centres(bounds, dims, start=0, stop=None):
+    """float32 [n,3]: the projected centres of the voxels with linear index in [start, stop), the rule of the docstring."""
+    lo, _, dims, step = _grid(bounds, dims)
+    return _centres(lo, dims, step, start, dims[0] * dims[1] * dims[2] if stop is None else stop)
+
+
+def _votes_host(lo, dims, step, K, M, words, H, W, seen, hit):
+    n = dims[0] * dims[1] * dims[2]
+    words = words.view(np.uint32)
+    for s0 in range(0, n, HOST_SLAB):
+        s1 = min(n, s0 + HOST_SLAB)
+        pts = _centres(lo, dims, step, s0, s1)
+        for v in range(K.shape[0]):   # one view at a time: [slab] temporaries
+            pu, pv, keep = ES.project_points_host(pts, K[v:v + 1], M[v:v + 1], H, W)
+            idx = np.nonzero(keep[0])[0]
+            px, py = np.floor(pu[0][idx]).astype(np.int64), np.floor(pv[0][idx]).astype(np.int64)
+            bit = (words[v, py, px >> 5] >> (px & 31).astype(np.uint32)) & np.uint32(1)
+            seen[s0 + idx] += np.uint16(1)
+            hit[s0 + idx] += bit.astype(np.uint16)
+
+
+def voxel_votes(bounds, dims, intrinsics, w2c, bits, height, width, counts=None, backend="gpu", device=None):
+    """(seen, hit): uint16 [nx ny nz] tensors, the votes of the module docstring over the views of this call.
+    intrinsics [V,4] = (fx, fy, cx, cy) and w2c [V,3,4] float64 (arrays or tensors); ``bits``: ``near_bits`` of the same
+    views, int32 [V,height,ceil(width/32)].  ``counts``: a (seen, hit) pair of an earlier call over the same grid -- the
+    votes are added to it in place and it is returned; the views of all accumulating calls number at most 65535 (the
+    caller's to keep: ``seed_points`` checks it).  ``backend="gpu"``: ``cgs_voxel_votes``, device tensors;
+    ``backend="host"``: numpy, CPU tensors."""
+    _check_backend(backend)
+    lo, _, dims, step = _grid(bounds, dims)
+    height, width = ES._check_size("voxel_votes", height, width)
+    V, K, M = ES._cameras(intrinsics, w2c)
+    if V > MAX_VIEWS:
+        raise ValueError(f"voxel_votes: at most {MAX_VIEWS} views (got {V})")
+    if not torch.is_tensor(bits):
+        bits = torch.from_numpy(np.ascontiguousarray(bits))
+    if bits.dtype != torch.int32 or tuple(bits.shape) != (V, height, bits_stride(width)):
+        raise ValueError(f"voxel_votes: bits must be int32 [{V},{height},{bits_stride(width)}] (got {bits.dtype} "
+                         f"{tuple(bits.shape)})")
+    n = dims[0] * dims[1] * dims[2]
+    if counts is not None:
+        for c in counts:
+            if not torch.is_tensor(c) or c.dtype != torch.uint16 or tuple(c.shape) != (n,) or not c.is_contiguous():
+                raise ValueError(f"voxel_votes: counts must be a pair of contiguous uint16 [{n}] tensors")
+    if backend == "host":
+        seen, hit = counts if counts is not None else (torch.zeros(n, dtype=torch.uint16), torch.zeros(n, dtype=torch.uint16))
+        if seen.is_cuda or hit.is_cuda:
+            raise ValueError("voxel_votes: backend='host' accumulates into CPU tensors")
+        _votes_host(lo, dims, step, K, M, bits.detach().cpu().numpy(), height, width, seen.numpy(), hit.numpy())
+        return seen, hit
+    dev = ES._device_for([bits] + list(counts or []), "voxel_votes", device)
+    with L.device_guard(dev):
+        if counts is not None:
+            seen, hit = counts
+            if seen.device != dev or hit.device != dev:
+                raise ValueError(f"voxel_votes: counts must be on {dev}")
+        else:
+            seen = torch.empty(n, dtype=torch.uint16, device=dev)
+            hit = torch.empty(n, dtype=torch.uint16, device=dev)
+        bits = bits.to(dev).contiguous()
+        Kd, Md = torch.from_numpy(K).to(dev), torch.from_numpy(M).to(dev)
+        lo_c, step_c = (C.c_double * 3)(*lo), (C.c_double * 3)(*step)
+        rc = L.load().cgs_voxel_votes(dims[0], dims[1], dims[2], C.cast(lo_c, C.c_void_p), C.cast(step_c, C.c_void_p), V,
+                                      L.ptr(Kd), L.ptr(Md), height, width, L.ptr(bits), 1 if counts is not None else 0,
+                                      L.ptr(seen), L.ptr(hit), L.raw_stream(dev))
+        L.check(rc, "cgs_voxel_votes")
+    return seen, hit
+
+
+# ------------------------------------------------------------------------------------------------ selection and thinning
+def need_table(min_ratio, views):
+    """int64 [views + 1]: need[s] = ceil(min_ratio * s), in float64."""
+    min_ratio = float(min_ratio)
+    if not (0.0 <= min_ratio <= 1.0):
+        raise ValueError(f"min_ratio must lie in [0, 1] (got {min_ratio})")
+    return np.ceil(min_ratio * np.arange(int(views) + 1, dtype=np.float64)).astype(np.int64)
+
+
+def _counts_host(x):
+    return (x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)).astype(np.int64).reshape(-1)
+
+
+def select_voxels(seen, hit, min_views, min_ratio):
+    """bool [n] (numpy): seen >= min_views and hit >= need[seen] -- integer comparisons against the ``need_table``."""
+    seen, hit = _counts_host(seen), _counts_host(hit)
+    if seen.shape != hit.shape:
+        raise ValueError("select_voxels: seen and hit differ in shape")
+    need = need_table(min_ratio, int(seen.max()) if seen.size else 0)
+    return (seen >= int(min_views)) & (hit >= need[seen])
+
+
+def thin_to_seeds(keep, hit, bounds, dims, cell, max_seeds):
+    """One seed per cell of ``cell``^3 voxels that holds a kept voxel (module docstring).  Returns (seeds float64 [N,3],
+    info): info = {"cells": the cells with a kept voxel, "capped": whether max_seeds cut them, "cell_index": int64 [N],
+    "hit_sum": int64 [N]}."""
+    lo, _, (nx, ny, nz), step = _grid(bounds, dims)
+    cell, max_seeds = int(cell), int(max_seeds)
+    if cell < 1 or max_seeds < 1:
+        raise ValueError(f"cell and max_seeds must be positive (got {cell}, {max_seeds})")
+    keep = np.asarray(keep.detach().cpu().numpy() if torch.is_tensor(keep) else keep).reshape(-1).astype(bool)
+    hit = _counts_host(hit)
+    if keep.size != nx * ny * nz or hit.size != keep.size:
+        raise ValueError(f"thin_to_seeds: keep and hit must hold {nx * ny * nz} voxels")
+    g = np.nonzero(keep)[0].astype(np.int64)
+    ijk = np.stack([g % nx, (g // nx) % ny, g // (nx * ny)], 1)
+    cx, cy = -(-nx // cell), -(-ny // cell)
+    cidx = ((ijk[:, 2] // cell) * cy + ijk[:, 1] // cell) * cx + ijk[:, 0] // cell
+    order = np.argsort(cidx, kind="stable")
+    cells, first, count = np.unique(cidx[order], return_index=True, return_counts=True)
+    if cells.size == 0:
+        return np.zeros((0, 3), np.float64), {"cells": 0, "capped": False, "cell_index": cells, "hit_sum": cells.copy()}
+    sums = np.add.reduceat(ijk[order], first, axis=0)          # int64
+    hit_sum = np.add.reduceat(hit[g][order], first)
+    capped = cells.size > max_seeds
+    if capped:
+        best = np.lexsort((cells, -hit_sum))[:max_seeds]       # the largest hit sums, ties to the lower cell index
+        sel = np.sort(best)                                    # cells is ascending: back in cell order
+        cells, sums, count, hit_sum = cells[sel], sums[sel], count[sel], hit_sum[sel]
+    mean = sums.astype(np.float64) / count.astype(np.float64)[:, None]
+    seeds = lo[None, :] + (mean + 0.5) * step[None, :]
+    return seeds, {"cells": int(first.size), "capped": bool(capped), "cell_index": cells, "hit_sum": hit_sum}
+
+
+# ------------------------------------------------------------------------------------------------ a scan
+def grid_dims(bounds, grid):
+    """``grid`` voxels along the longest side of the box, the other axes rounded so that the voxels are near-cubic."""
+    lo, hi = (np.asarray(b, np.float64).reshape(-1) for b in bounds)
+    grid = int(grid)
+    if grid < 1:
+        raise ValueError(f"grid must be positive (got {grid})")
+    if lo.shape != (3,) or hi.shape != (3,) or not (np.isfinite(lo).all() and np.isfinite(hi).all() and (hi > lo).all()):
+        raise ValueError(f"bounds must be finite with hi > lo on every axis (got lo={lo.tolist()}, hi={hi.tolist()})")
+    ext = hi - lo
+    voxel = ext.max() / grid
+    return tuple(int(max(1, min(grid, round(e / voxel)))) for e in ext)
+
+
+def seed_points(cameras, edge_maps_u8, detector, bounds, grid=128, tol_px=2, min_views=3, min_ratio=0.8, cell=4,
+                max_seeds=20000, edge_threshold=EDGE_MAX_THRESHOLD, backend="gpu", device=None, budget_bytes=None):
+    """cameras: ``NovelViewCamera`` s; edge_maps_u8: one uint8 [H,W] map per camera (a list or an [V,H,W] array), the
+    stored bytes of the detector's maps, as ``score_edges`` takes them.  bounds = (lo, hi) of the box to search.
+
+    A pixel is detected when ``reprojection.detected_lut(detector, edge_threshold)`` says so; every view's detected mask
+    goes through ``edt_squared`` and ``near_bits(tol_px)``; the views vote on a grid of ``grid`` voxels along the longest
+    side (``grid_dims``); ``select_voxels(min_views, min_ratio)`` and ``thin_to_seeds(cell, max_seeds)`` give the seeds.
+    Views are grouped by size and processed ``budget_bytes`` (default BYTE_BUDGET; 8 bytes per pixel, at least one view)
+    at a time; the votes accumulate across the chunks, so the result does not depend on the chunking.
+
+    Returns (seeds float64 [N,3], info) with info = {"dims", "voxels", "views", "kept_voxels", "cells", "seeds", "capped",
+    "backend"}.  THE DEFAULTS ARE UNTUNED (no scan has been measured against them), there is no occlusion reasoning, and
+    the curve direction is not seeded.  ``backend``: "gpu" (HIP; ``device``) or "host" (numpy)."""
+    from ..edge_extraction.novel_view import camera_arrays
+    from ..edge_extraction.reprojection import detected_lut
+    _check_backend(backend)
+    lut = detected_lut(detector, edge_threshold)
+    cameras = list(cameras)
+    maps = [np.asarray(m) for m in edge_maps_u8]
+    if len(maps) != len(cameras):
+        raise ValueError(f"seed_points: {len(cameras)} cameras and {len(maps)} edge maps")
+    if len(cameras) > MAX_VIEWS:
+        raise ValueError(f"seed_points: at most {MAX_VIEWS} views (got {len(cameras)})")
+    for c, m in zip(cameras, maps):
+        if m.dtype != np.uint8 or m.shape != (c.height, c.width):
+            raise ValueError(f"seed_points: the edge map of {c.name} must be uint8 [{c.height},{c.width}] (got {m.dtype} "
+                             f"{m.shape})")
+    ES.tolerances_squared([tol_px])
+    dims = grid_dims(bounds, grid)
+    _grid(bounds, dims)
+    need_table(min_ratio, 0)
+    budget = BYTE_BUDGET if budget_bytes is None else int(budget_bytes)
+    if budget <= 0:
+        raise ValueError(f"seed_points: budget_bytes must be positive (got {budget})")
+    if backend == "gpu":
+        device = ES._device_for([], "seed_points", device)
+    n = dims[0] * dims[1] * dims[2]
+    by_size = {}
+    for v, c in enumerate(cameras):
+        by_size.setdefault((c.height, c.width), []).append(v)
+    counts = None
+    for (H, W), idx in by_size.items():
+        per = max(1, budget // (BYTES_PER_PIXEL * H * W))
+        for b in range(0, len(idx), per):
+            sel = idx[b:b + per]
+            intr, w2c = camera_arrays([cameras[v] for v in sel])
+            det = torch.from_numpy(lut[np.stack([maps[v] for v in sel])].astype(np.uint8))
+            d2 = ES.edt_squared(det, backend=backend, device=device)
+            bits = near_bits(d2, tol_px, backend=backend, device=device)
+            del d2
+            counts = voxel_votes(bounds, dims, intr, w2c, bits, H, W, counts=counts, backend=backend, device=device)
+    if counts is None:   # no view: nothing is seen
+        counts = (torch.zeros(n, dtype=torch.uint16), torch.zeros(n, dtype=torch.uint16))
+    seen, hit = (c.cpu().numpy() for c in counts)
+    keep = select_voxels(seen, hit, min_views, min_ratio)
+    seeds, thin = thin_to_seeds(keep, hit, bounds, dims, cell, max_seeds)
+    info = {"dims": dims, "voxels": n, "views": len(cameras), "kept_voxels": int(np.count_nonzero(keep)),
+            "cells": thin["cells"], "seeds": int(seeds.shape[0]), "capped": thin["capped"], "backend": backend}
+    return seeds, info

@@ -155,6 +155,44 @@ def grid_point_cloud(num_pts_per_axis: int = 15, rng=None) -> BasicPointCloud:
     return BasicPointCloud(points=xyz, colors=SH2RGB(rnd / 255.0), normals=np.zeros((xyz.shape[0], 3)))
 
 
+EMAP_SEED_BOUNDS = ((-0.05, -0.05, -0.05), (1.05, 1.05, 1.05))   # the box of grid_point_cloud
+INIT_MODES = ("reference", "edge_votes")
+
+
+def default_seed_bounds(layout, points=None):
+    """The box the edge vote searches when none is given, (lo, hi) float64 [3] each.  ``"emap"``: the reference's box
+    [-0.05, 1.05]^3 (grid_point_cloud).  ``"colmap"``: per axis the 2nd to 98th percentile of the SfM ``points`` [N,3],
+    padded by 10 % of that side on both ends."""
+    if layout == "emap":
+        return np.array(EMAP_SEED_BOUNDS[0], np.float64), np.array(EMAP_SEED_BOUNDS[1], np.float64)
+    if layout != "colmap":
+        raise ValueError(f"unknown layout {layout!r}: expected 'emap' or 'colmap'")
+    pts = np.asarray(points if points is not None else np.zeros((0, 3)), np.float64).reshape(-1, 3)
+    if pts.shape[0] == 0:
+        raise ValueError("default_seed_bounds: the colmap layout needs the scan's SfM points")
+    lo, hi = np.percentile(pts, 2.0, axis=0), np.percentile(pts, 98.0, axis=0)
+    pad = 0.1 * (hi - lo)
+    return lo - pad, hi + pad
+
+
+def edge_vote_point_cloud(cameras, detector, bounds, rng=None, **options) -> BasicPointCloud:
+    """A seed cloud from the edge maps of the cameras a Scene trains on (``EdgeCamera`` s): the multi-view voxel vote of
+    ``ops.edge_seed.seed_points`` over ``bounds`` = (lo, hi), every view voting with the camera it is trained with
+    (``reprojection.scene_cameras``).  ``options``: seed_points' keywords (grid, tol_px, min_views, min_ratio, cell,
+    max_seeds, edge_threshold, backend, device, budget_bytes).  Colours as grid_point_cloud's.  No seed is a ValueError
+    that names the bounds and the counts: there is no fallback to another cloud."""
+    from ..edge_extraction.reprojection import scene_cameras
+    from ..ops.edge_seed import seed_points
+    cams, maps = scene_cameras(cameras)
+    seeds, info = seed_points(cams, maps, detector, bounds, **options)
+    if seeds.shape[0] == 0:
+        lo, hi = (np.asarray(b, np.float64).tolist() for b in bounds)
+        raise ValueError(f"edge_vote_point_cloud: no seed in the box lo={lo}, hi={hi}: {info['views']} views voted on "
+                         f"{info['dims']} voxels, {info['kept_voxels']} passed the selection, {info['cells']} cells hold one")
+    rnd = (rng.random if rng is not None else np.random.random)((seeds.shape[0], 3))
+    return BasicPointCloud(points=seeds, colors=SH2RGB(rnd / 255.0), normals=np.zeros((seeds.shape[0], 3)))
+
+
 def write_emap(path, cameras, edge_maps, detector="DexiNed"):
     """Writes a scan in the EMAP layout (meta_data.json + <detector dir>/<i>_colors.png) from cameras that carry
     world_view_transform / FoVx / FoVy (e.g. curve_gaussian_amd.synthetic cameras) and [1,H,W] or [H,W] edge maps in
@@ -251,7 +289,12 @@ def write_edge_files(model_path, edge_dict, pts):
     os.makedirs(model_path, exist_ok=True)
     with open(os.path.join(model_path, "parametric_edges.json"), "w") as f:
         json.dump(edge_dict, f)
-    with open(os.path.join(model_path, "edge_points.ply"), "w") as f:
+    write_points_ply(os.path.join(model_path, "edge_points.ply"), pts)
+
+
+def write_points_ply(path, pts):
+    """`pts` [N,3] as an ASCII PLY of double x y z (train.py:277-285)."""
+    with open(path, "w") as f:
         f.write("ply\nformat ascii 1.0\nelement vertex %d\nproperty double x\nproperty double y\nproperty double z\n"
                 "end_header\n" % len(pts))
         for p in pts:

@@ -477,12 +477,22 @@ class Scene:
     empty and the train list is the frames once (the reference's list holds them twice).
     ``images`` / ``resolution`` (COLMAP only): ``--images`` and ``-r`` of the reference.  ``undistort`` (COLMAP only; not in
     the reference): resample the edge maps through the cameras' lens models, see read_colmap; on the GPU when `device` is
-    one, on the host otherwise."""
+    one, on the host otherwise.
+
+    ``init`` (not in the reference): ``"reference"`` seeds the model as above; ``"edge_votes"`` seeds it from the edge maps
+    of the training cameras by a multi-view voxel vote (dataset_io.edge_vote_point_cloud; every view votes with the camera
+    it is trained with, ``undistort`` included).  ``init_options``: the keywords of ops.edge_seed.seed_points, and
+    ``bounds`` = (lo, hi) (default: dataset_io.default_seed_bounds -- the reference's box for EMAP, the trimmed extent of
+    the SfM cloud for COLMAP); the vote runs on the GPU when `device` is one, on the host otherwise, unless ``backend``
+    says so.  No seed, or an unknown ``init``, is a ValueError: there is no fallback."""
 
     def __init__(self, source_path, gaussians, detector="DexiNed", num_pts_per_axis=15, cameras_extent=None, rng=None,
-                 device=None, eval=False, llffhold=8, images=None, resolution=-1, undistort=False):
+                 device=None, eval=False, llffhold=8, images=None, resolution=-1, undistort=False, init="reference",
+                 init_options=None):
         import os
         from . import dataset_io
+        if init not in dataset_io.INIT_MODES:
+            raise ValueError(f"unknown init {init!r}: expected one of {dataset_io.INIT_MODES}")
         self.gaussians = gaussians
         if os.path.exists(os.path.join(source_path, "sparse")):
             from . import colmap_io
@@ -500,6 +510,17 @@ class Scene:
                 centres = torch.stack([c.camera_center for c in self.train_cameras]).double()
                 cameras_extent = float((centres - centres.mean(0)).norm(dim=1).max() * 1.1)
         self.cameras_extent = cameras_extent
+        if init == "edge_votes":
+            opts = dict(init_options or {})
+            layout = "colmap" if os.path.exists(os.path.join(source_path, "sparse")) else "emap"
+            bounds = opts.pop("bounds", None)
+            if bounds is None:
+                bounds = dataset_io.default_seed_bounds(layout, self.point_cloud.points)
+            on_gpu = device is not None and torch.device(device).type == "cuda"
+            opts.setdefault("backend", "gpu" if on_gpu else "host")
+            if opts["backend"] == "gpu" and on_gpu:
+                opts.setdefault("device", device)
+            self.point_cloud = dataset_io.edge_vote_point_cloud(self.train_cameras, detector, bounds, rng, **opts)
         if device is not None:
             moved = {id(c): c.to(device) for c in self.train_cameras + self.test_cameras}
             self.train_cameras = [moved[id(c)] for c in self.train_cameras]

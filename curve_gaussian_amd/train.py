@@ -3,6 +3,7 @@
 
     python -m curve_gaussian_amd.train -s SCAN -m OUT [--iterations N] [--backend graphed|direct|autograd|torch]
                                        [--draw_snapshots] [--topology_backend host|gpu] [--report_dir DIR] [--undistort]
+                                       [--init reference|edge_votes]
 
 The loop keeps the reference's order.  Per iteration: learning rate, SH degree every 1000 iterations, a random view without
 replacement, render + losses + every regulariser + backward (one ``TrainStep`` call), densification statistics before
@@ -34,11 +35,13 @@ class ModelParams:
     """The fields of the reference's ModelParams (arguments/__init__.py:47-66) this driver reads."""
 
     def __init__(self, source_path="", model_path="", sh_degree=0, n_gaussians=12, detector="DexiNed", resolution=-1,
-                 white_background=False, eval=False, undistort=False):
+                 white_background=False, eval=False, undistort=False, init="reference", init_options=None):
         self.source_path, self.model_path = source_path, model_path
         self.sh_degree, self.n_gaussians, self.detector = sh_degree, n_gaussians, detector
         self.resolution, self.white_background, self.eval = resolution, white_background, eval
         self.undistort = undistort   # not in the reference: COLMAP scans with lens distortion (scene/colmap_io.py)
+        # not in the reference: "edge_votes" seeds the curves from the edge maps (Scene; ops/edge_seed.py)
+        self.init, self.init_options = init, dict(init_options or {})
 
 
 class OptimizationParams:
@@ -138,7 +141,8 @@ def make_scene(dataset, opt, device):
     from .scene import GaussianCurveModel, Scene
     gaussians = GaussianCurveModel(dataset.sh_degree, dataset.n_gaussians, opt.optimizer_type, device=device)
     scene = Scene(dataset.source_path, gaussians, detector=dataset.detector, eval=dataset.eval,
-                  resolution=dataset.resolution, device=device, undistort=dataset.undistort)
+                  resolution=dataset.resolution, device=device, undistort=dataset.undistort, init=dataset.init,
+                  init_options=dataset.init_options)
     scene.model_path = dataset.model_path
     gaussians.training_setup(opt)
     return scene, gaussians
@@ -314,6 +318,16 @@ def build_parser():
     p.add_argument("--undistort", action="store_true",
                    help="COLMAP scans: resample the edge maps through each camera's lens model and principal point (accepts "
                         "SIMPLE_RADIAL, RADIAL and FULL_OPENCV cameras too); without it distortion is ignored, as in the reference")
+    p.add_argument("--init", choices=("reference", "edge_votes"), default="reference",
+                   help="the seed of the curves: the reference's (the 15^3 grid, or the SfM cloud of a COLMAP scan) or a "
+                        "multi-view voxel vote of the training views' edge maps (untuned defaults; no occlusion reasoning)")
+    p.add_argument("--init_grid", type=int, default=None, help="edge_votes: voxels along the longest side of the box")
+    p.add_argument("--init_tol_px", type=float, default=None, help="edge_votes: pixel distance to a detected edge that votes")
+    p.add_argument("--init_min_views", type=int, default=None, help="edge_votes: views that must see a voxel")
+    p.add_argument("--init_min_ratio", type=float, default=None, help="edge_votes: share of the seeing views that must vote")
+    p.add_argument("--init_cell", type=int, default=None, help="edge_votes: voxels per axis thinned to one seed")
+    p.add_argument("--init_bounds", nargs=6, type=float, default=None, metavar=("X0", "Y0", "Z0", "X1", "Y1", "Z1"),
+                   help="edge_votes: the box to search (default: the reference's box, or the trimmed extent of the SfM cloud)")
     p.add_argument("--iterations", type=int, default=None)
     p.add_argument("--test_iterations", nargs="+", type=int, default=[3_000, 10_000])        # :386-391
     p.add_argument("--save_iterations", nargs="+", type=int, default=[3_000, 10_000])
@@ -344,8 +358,12 @@ def parse_args(argv):
     if args.iterations is not None:
         opt.iterations = args.iterations
     args.save_iterations.append(opt.iterations)                                     # :404
+    init_options = {k: v for k, v in (("grid", args.init_grid), ("tol_px", args.init_tol_px), ("min_views", args.init_min_views),
+                                      ("min_ratio", args.init_min_ratio), ("cell", args.init_cell)) if v is not None}
+    if args.init_bounds is not None:
+        init_options["bounds"] = (args.init_bounds[:3], args.init_bounds[3:])
     dataset = ModelParams(source_path, args.model_path, args.sh_degree, args.n_gaussians, args.detector, args.resolution,
-                          args.white_background, args.eval, args.undistort)
+                          args.white_background, args.eval, args.undistort, args.init, init_options)
     return dataset, opt, args
 
 

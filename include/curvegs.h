@@ -877,6 +877,44 @@ int cgs_edge_score_reduce(int V, int height, int width, const uint8_t* pred_mask
                           void* workspace, int64_t* counts /*[V, 2 + 2 n_tol]*/, double* sums /*[V,2]*/,
                           uint8_t* both_nonempty /*[V]*/, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Multi-view voxel vote: a seed for the curves from the scan's own edge maps.  Every voxel centre of a regular grid is
+ * projected into every view; a voxel records in how many views it lies inside the image and in how many of those it lands
+ * within a tolerance of a detected edge pixel.  The reference has no counterpart (it seeds a fixed 15^3 grid, or the SfM
+ * cloud).  There is no occlusion reasoning.  Both entry points: caller's stream, no allocation, no host synchronisation,
+ * no atomics, results independent of the launch geometry.
+ *
+ * Grid: lo, step (host, float64 [3]; step = (hi - lo) / dims, formed by the caller) and dims (nx, ny, nz), each >= 1.
+ * Voxel (i, j, k) has the linear index (k ny + j) nx + i (x fastest) and the centre lo + (i + 0.5) step per axis, computed
+ * in float64 without FMA contraction and rounded to float32; that float32 point is projected.
+ *
+ * cgs_pack_near_bits: near[v][y][x] = (dist2[v][y][x] <= tol2), dist2 the cgs_edt_squared transform of a view's detected
+ * mask, packed one bit per pixel into uint32 words: word w of row y holds pixels 32 w .. 32 w + 31, bit b is pixel
+ * 32 w + b; the row stride is ceil(width / 32) words, padding bits are 0.  bits_out is [V, height, ceil(width / 32)]; the
+ * kernel writes every word (no memset).  A view without a feature (all CGS_EDT_INF) packs to zero.  V = 0 is a no-op;
+ * V < 0, tol2 < 0, a size outside [1, CGS_EDT_MAX_SIZE] and NULL pointers are CGS_ERR_INVALID_ARGUMENT, rejected before
+ * anything is launched.
+ *
+ * cgs_voxel_votes, for voxel g over the V views of the call (intr [V,4] = (fx, fy, cx, cy), w2c [V,12] = [R | T] row-major,
+ * device, float64; all views of a call share one size):
+ *   seen[g] = the number of views in which the projection rule of cgs_project_points keeps the centre (the same device
+ *             function, the same operation order: c2 > 0, 0 <= u < width, 0 <= v < height)
+ *   hit[g]  = the number of those views whose near bit at (floor(v), floor(u)) is set
+ * accumulate == 0 stores the counts, accumulate != 0 adds them to what seen / hit hold (a plain read-add-store of the
+ * thread's own voxel), so a scan is voted chunk of views by chunk of views.  Counts are uint16: the caller keeps the total
+ * number of views over the accumulating calls at or below CGS_SEED_MAX_VIEWS.  V = 0 with accumulate == 0 zeroes the
+ * counts (intr, w2c and bits may then be NULL); V = 0 with accumulate != 0 is a no-op.  V outside [0, CGS_SEED_MAX_VIEWS],
+ * a non-positive dim, more than 2^31 - 1 voxels, a size outside [1, CGS_EDT_MAX_SIZE], a non-finite lo, a non-finite or
+ * non-positive step and NULL pointers are CGS_ERR_INVALID_ARGUMENT, rejected before anything is launched.
+ * ------------------------------------------------------------------------------------------------ */
+#define CGS_SEED_MAX_VIEWS 65535
+int cgs_pack_near_bits(int V, int height, int width, const int32_t* dist2 /*[V,height,width]*/, int tol2,
+                       uint32_t* bits_out /*[V,height,ceil(width/32)]*/, void* stream);
+int cgs_voxel_votes(int nx, int ny, int nz, const double* lo /*host, [3]*/, const double* step /*host, [3]*/, int V,
+                    const double* intr /*[V,4]*/, const double* w2c /*[V,12]*/, int height, int width,
+                    const uint32_t* bits /*[V,height,ceil(width/32)]*/, int accumulate, uint16_t* seen /*[nx ny nz]*/,
+                    uint16_t* hit /*[nx ny nz]*/, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
