@@ -113,6 +113,7 @@ SIGNATURES = {
     "cgs_edge_score_reduce": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "cgs_pack_near_bits": (_i, [_i, _i, _i, _vp, _i, _vp, _vp]),
     "cgs_voxel_votes": (_i, [_i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp]),
+    "cgs_voxel_moments": (_i, [_i, _i, _i, _vp, _i, _vp, _i, _vp, _vp]),
 }
 
 
@@ -154,6 +155,7 @@ EDT_INF = 2147483647   # CGS_EDT_INF
 EDT_MAX_SIZE = 16384   # CGS_EDT_MAX_SIZE
 EDGE_SCORE_MAX_TOL = 8   # CGS_EDGE_SCORE_MAX_TOL
 SEED_MAX_VIEWS = 65535   # CGS_SEED_MAX_VIEWS
+SEED_MAX_RADIUS = 15   # CGS_SEED_MAX_RADIUS
 REPORT_PANELS = ("render", "ground_truth", "depth", "rend_dir", "rend_alpha")   # panel order of cgs_report_panels
 
 _lib = None

@@ -1908,4 +1908,26 @@ int cgs_voxel_votes(int nx, int ny, int nz, const double* lo, const double* step
     return CGS_OK;
 }
 
+int cgs_voxel_moments(int nx, int ny, int nz, const void* keep_bits, int N, const void* centres, int radius, void* moments,
+                      void* stream_) {
+    if (N < 0 || nx <= 0 || ny <= 0 || nz <= 0 || radius < 1 || radius > CGS_SEED_MAX_RADIUS) {
+        set_error("cgs_voxel_moments: invalid argument (dims=%dx%dx%d, N=%d, radius=%d; the radius lies in [1, %d])", nx, ny,
+                  nz, N, radius, CGS_SEED_MAX_RADIUS);
+        return CGS_ERR_INVALID_ARGUMENT;
+    }
+    if ((long long)nx * ny > INT32_MAX || (long long)nx * ny * nz > INT32_MAX) {   // the first product is below 2^62
+        set_error("cgs_voxel_moments: invalid argument (%dx%dx%d voxels: at most 2^31 - 1)", nx, ny, nz);
+        return CGS_ERR_INVALID_ARGUMENT;
+    }
+    if (!keep_bits || !centres || !moments) {
+        set_error("cgs_voxel_moments: invalid argument (NULL pointer)");
+        return CGS_ERR_INVALID_ARGUMENT;
+    }
+    if (N == 0) return CGS_OK;
+    launch_voxel_moments((hipStream_t)stream_, nx, ny, nz, (const unsigned int*)keep_bits, N, (const int*)centres, radius,
+                         (int*)moments);
+    if (!check_launch("voxel_moments", false, (hipStream_t)stream_)) return CGS_ERR_HIP;
+    return CGS_OK;
+}
+
 }  // extern "C"

@@ -1,6 +1,7 @@
 // Multi-view voxel vote: where do the edge maps of a scan say the edges are?  (include/curvegs.h, cgs_pack_near_bits /
-// cgs_voxel_votes.)  Every voxel centre of a regular grid is projected into every view and counts the views that see it
-// and the views in which it lands within a tolerance of a detected edge pixel.  Two kernels:
+// cgs_voxel_votes / cgs_voxel_moments.)  Every voxel centre of a regular grid is projected into every view and counts the
+// views that see it and the views in which it lands within a tolerance of a detected edge pixel; the kept voxels around a
+// seed then give the seed's direction through their integer second moments.  Three kernels:
 //   k_pack_near_bits   one thread per pixel of the PADDED row (32 * stride pixels, stride = ceil(W / 32) words): the bit is
 //                      dist2 <= tol2 inside the image and 0 in the padding, one wave ballot gives two words, lanes 0 and 32
 //                      store them.  A padded plane is a whole number of words, so the linear pixel index / 32 is the word
@@ -13,7 +14,14 @@
 //                      stay in registers; one plain 16-bit store each at the end (a read-add-store of the thread's own
 //                      voxel with `accumulate`).  No atomics, no LDS: the result does not depend on the launch geometry.
 //                      The packed masks are the only gathered data: 1600x1200 is 240 KB a view, 24 MB for 100 views.
-// Voxel and map offsets are 64-bit.
+//   k_voxel_moments    one wave per seed, four seeds per block.  The lanes walk the (dy, dz) rows of the seed's window, at
+//                      most 31 x 31 of them; a row inside the grid whose half span h = isqrt(r^2 - dy^2 - dz^2) exists
+//                      covers x = cx - h .. cx + h clipped to the grid, at most 31 voxels in at most two words: plain
+//                      loads, a 64-bit shift and a mask leave the row's kept voxels, and the ten integers are summed from
+//                      the set bits in registers.  One shuffle reduction per wave, lane 0 stores the ten values: every
+//                      output word is written, no memset.  Integers only, no atomics, no LDS, no barrier (a wave without a
+//                      seed leaves at once): the result does not depend on the launch geometry.
+// Voxel, map and keep-bit offsets are 64-bit.
 #include <algorithm>
 
 #include "kernels.h"
@@ -23,6 +31,8 @@ namespace cgs {
 
 constexpr int SEED_THREADS = 256;        // 4 waves
 constexpr int SEED_MAX_VIEWS = 65535;    // grid.y of the packing launch
+constexpr int MOMENT_WAVES = SEED_THREADS / 64;   // seeds per block of k_voxel_moments
+constexpr int MOMENT_VALUES = 10;        // m, the three first and the six second moments
 
 struct SeedGrid {  // passed by value
     double lo[3];
@@ -85,6 +95,53 @@ __global__ void __launch_bounds__(SEED_THREADS) k_voxel_votes(const SeedGrid g, 
     hit[id] = (unsigned short)n_hit;
 }
 
+__global__ void __launch_bounds__(SEED_THREADS) k_voxel_moments(int nx, int ny, int nz, int stride,
+                                                               const unsigned int* __restrict__ keep, int N,
+                                                               const int* __restrict__ centres, int radius,
+                                                               int* __restrict__ moments) {
+    const int lane = threadIdx.x & 63;
+    const long long seed = (long long)blockIdx.x * MOMENT_WAVES + (threadIdx.x >> 6);
+    if (seed >= N) return;   // wave-uniform; the kernel has no barrier
+    const int cx = centres[3 * seed], cy = centres[3 * seed + 1], cz = centres[3 * seed + 2];
+    const int side = 2 * radius + 1, r2 = radius * radius;
+    int acc[MOMENT_VALUES];
+#pragma unroll
+    for (int k = 0; k < MOMENT_VALUES; k++) acc[k] = 0;
+    // a centre outside the grid (the caller's error) reads nothing and gives a zero row
+    const bool inside = cx >= 0 && cx < nx && cy >= 0 && cy < ny && cz >= 0 && cz < nz;
+    for (int row = lane; inside && row < side * side; row += 64) {
+        const int dz = row / side - radius, dy = row % side - radius;
+        const int y = cy + dy, z = cz + dz;
+        const int rem = r2 - dy * dy - dz * dz;
+        if (y < 0 || y >= ny || z < 0 || z >= nz || rem < 0) continue;
+        int h = 0;   // isqrt(rem), at most 15
+        while ((h + 1) * (h + 1) <= rem) h++;
+        const int x0 = max(cx - h, 0), x1 = min(cx + h, nx - 1);   // x0 <= cx <= x1, x1 - x0 <= 30
+        const unsigned int* line = keep + ((size_t)z * (size_t)ny + (size_t)y) * (size_t)stride;
+        const int w0 = x0 >> 5, w1 = x1 >> 5;                      // w1 - w0 <= 1, w1 < stride
+        unsigned long long span = line[w0];
+        if (w1 != w0) span |= (unsigned long long)line[w1] << 32;
+        // bit b of `bitsx` = voxel x0 + b; (x0 & 31) + (x1 - x0 + 1) <= 62 bits of `span` are in use
+        unsigned int bitsx = (unsigned int)(span >> (x0 & 31)) & ((1u << (x1 - x0 + 1)) - 1u);
+        while (bitsx) {
+            const int dx = x0 + (__ffs(bitsx) - 1) - cx;
+            bitsx &= bitsx - 1u;
+            acc[0] += 1;
+            acc[1] += dx; acc[2] += dy; acc[3] += dz;
+            acc[4] += dx * dx; acc[5] += dy * dy; acc[6] += dz * dz;
+            acc[7] += dx * dy; acc[8] += dx * dz; acc[9] += dy * dz;
+        }
+    }
+    for (int off = 32; off >= 1; off >>= 1) {
+#pragma unroll
+        for (int k = 0; k < MOMENT_VALUES; k++) acc[k] += __shfl_xor(acc[k], off, 64);
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < MOMENT_VALUES; k++) moments[(size_t)seed * MOMENT_VALUES + k] = acc[k];
+    }
+}
+
 void launch_pack_near_bits(hipStream_t s, int V, int height, int width, const int* dist2, int tol2, unsigned int* bits) {
     const int stride = (width + 31) / 32;
     const long long padded = (long long)height * stride * 32;
@@ -114,6 +171,14 @@ void launch_voxel_votes(hipStream_t s, int nx, int ny, int nz, const double* lo,
     ProfScope p("voxel_votes", s);
     hipLaunchKernelGGL(k_voxel_votes, dim3(blocks), dim3(SEED_THREADS), 0, s, g, V, intr, w2c, height, width,
                        (width + 31) / 32, bits, accumulate, seen, hit);
+}
+
+void launch_voxel_moments(hipStream_t s, int nx, int ny, int nz, const unsigned int* keep, int N, const int* centres,
+                          int radius, int* moments) {
+    const unsigned blocks = (unsigned)(((long long)N + MOMENT_WAVES - 1) / MOMENT_WAVES);
+    ProfScope p("voxel_moments", s);
+    hipLaunchKernelGGL(k_voxel_moments, dim3(blocks), dim3(SEED_THREADS), 0, s, nx, ny, nz, (nx + 31) / 32, keep, N, centres,
+                       radius, moments);
 }
 
 }  // namespace cgs

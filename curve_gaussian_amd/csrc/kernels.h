@@ -220,5 +220,7 @@ void launch_pack_near_bits(hipStream_t s, int V, int height, int width, const in
 void launch_voxel_votes(hipStream_t s, int nx, int ny, int nz, const double* lo, const double* step, int V,
                         const double* intr, const double* w2c, int height, int width, const unsigned int* bits,
                         int accumulate, unsigned short* seen, unsigned short* hit);
+void launch_voxel_moments(hipStream_t s, int nx, int ny, int nz, const unsigned int* keep, int N, const int* centres,
+                          int radius, int* moments);
 
 }  // namespace cgs

@@ -1,11 +1,13 @@
 """Seed points of a scan from its edge maps, without training: the multi-view voxel vote of ``ops.edge_seed`` as a tool.
 
-    python -m curve_gaussian_amd.edge_seed_cli --scan DIR [--layout emap|colmap] [--backend gpu|host] --out seeds.ply
+    python -m curve_gaussian_amd.edge_seed_cli --scan DIR [--layout emap|colmap] [--backend gpu|host] [--directions]
+                                               --out seeds.ply
 
 The cameras and maps are those ``edge_extraction.reprojection`` scores against: ``emap_cameras`` (meta_data.json) or
 ``read_colmap`` (sparse/0; ``--undistort`` as there).  The box is ``--bounds``, or ``scene.default_seed_bounds``.  The seeds
-are written as the ASCII PLY of ``edge_points.ply``; the counts are printed.  The defaults are untuned and there is no
-occlusion reasoning (ops/edge_seed.py)."""
+are written as the ASCII PLY of ``edge_points.ply``; the counts are printed.  ``--directions`` also seeds the curves'
+directions: they are written as the PLY's normals (zero for an undirected seed) and the directed count is printed.  The
+defaults are untuned and there is no occlusion reasoning (ops/edge_seed.py)."""
 import argparse
 import sys
 
@@ -32,6 +34,10 @@ def parser():
     ap.add_argument("--cell", type=int, default=4)
     ap.add_argument("--max_seeds", type=int, default=20000)
     ap.add_argument("--edge_threshold", type=float, default=SD.EDGE_MAX_THRESHOLD)
+    ap.add_argument("--directions", action="store_true", help="seed the curves' directions too (the PLY's normals)")
+    ap.add_argument("--dir_radius", type=int, default=SD.DIR_RADIUS)
+    ap.add_argument("--dir_min_support", type=int, default=SD.DIR_MIN_SUPPORT)
+    ap.add_argument("--dir_min_linearity", type=float, default=SD.DIR_MIN_LINEARITY)
     return ap
 
 
@@ -61,11 +67,13 @@ def main(argv=None):
     bounds = (args.bounds[:3], args.bounds[3:]) if args.bounds is not None else None
     seeds, info = seed_scan(args.scan, args.layout, args.detector, args.undistort, bounds, args.backend, grid=args.grid,
                             tol_px=args.tol_px, min_views=args.min_views, min_ratio=args.min_ratio, cell=args.cell,
-                            max_seeds=args.max_seeds, edge_threshold=args.edge_threshold)
-    IO.write_points_ply(args.out, seeds)
+                            max_seeds=args.max_seeds, edge_threshold=args.edge_threshold, directions=args.directions,
+                            dir_radius=args.dir_radius, dir_min_support=args.dir_min_support,
+                            dir_min_linearity=args.dir_min_linearity)
+    IO.write_points_ply(args.out, seeds, info["directions"] if args.directions else None)
     print(f"views {info['views']}, grid {info['dims'][0]}x{info['dims'][1]}x{info['dims'][2]}, kept voxels "
           f"{info['kept_voxels']}, cells {info['cells']}, seeds {info['seeds']}{' (capped)' if info['capped'] else ''}, "
-          f"bounds {info['bounds']}")
+          f"bounds {info['bounds']}" + (f", directed {info['directed']}" if args.directions else ""))
     print(f"Wrote {args.out}")
     return 0
 

@@ -1,5 +1,6 @@
 """Seed points for the curves from a scan's own edge maps: a multi-view voxel vote (cgs_pack_near_bits / cgs_voxel_votes,
-include/curvegs.h; csrc/edge_seed.hip).  The reference has no counterpart: it seeds a fixed 15^3 grid or the SfM cloud.
+include/curvegs.h; csrc/edge_seed.hip), and on request their directions from the vote's kept voxels (cgs_voxel_moments).
+The reference has no counterpart: it seeds a fixed 15^3 grid or the SfM cloud, every curve along +-Y.
 
 Definitions (frozen), the same on both back ends bit for bit:
   grid       ``bounds`` = (lo, hi) float64 [3] each and ``dims`` = (nx, ny, nz) >= 1; step = (hi - lo) / dims in float64;
@@ -15,12 +16,32 @@ Definitions (frozen), the same on both back ends bit for bit:
              coordinates (int64 sums over a count), at lo + (mean + 0.5) step in float64; seeds ordered by cell index;
              above ``max_seeds`` the cells with the largest summed hit are kept (ties: the lower cell index)
 
+Directions (``directions=True``; frozen), the same on both back ends bit for bit:
+  keep bits  the selection mask packed exactly like the near masks with x fastest: word w of row (j, k) = voxels
+             i = 32 w .. 32 w + 31, bit b = voxel 32 w + b, row stride ceil(nx / 32) words, rows ordered (k ny + j), padding
+             bits 0, the words held as int32 [nz, ny, ceil(nx / 32)]; made on the host by ``keep_bits`` for both back ends
+  centre     the centre voxel of a seed, from the thinning's own integer sums: c_a = (2 sum_a + count) // (2 count) per
+             axis, floor(mean + 0.5) in integers (``thin_to_seeds(return_centres=True)``)
+  window     every voxel q of the grid with its keep bit set and |q - c|^2 <= r^2 -- an integer comparison over a ball
+             clipped to the grid, not a cube; r = ``dir_radius``, 1 <= r <= 15 (SEED_MAX_RADIUS), so a row of the window
+             spans at most 31 voxels and at most two words
+  moments    with d = q - c over the window, int32 [N,10] = [m, sum dx, sum dy, sum dz, sum dx^2, sum dy^2, sum dz^2,
+             sum dx dy, sum dx dz, sum dy dz]; every value is bounded by (2 r + 1)^3 r^2 <= 6.8e6: int32 is exact and the
+             order of the summation cannot matter
+  direction  host float64 code, the same for both back ends (``seed_directions``): the integer matrix
+             m sum(d d^T) - (sum d)(sum d)^T in int64, converted to float64, ``np.linalg.eigh`` with eigenvalues
+             l0 <= l1 <= l2; the direction is the eigenvector of l2 with its sign fixed so that its component of largest
+             magnitude is positive (ties: the lowest axis); linearity = (l2 - l1) / l2, or 0 when l2 = 0; a seed is
+             directed iff m >= dir_min_support and linearity >= dir_min_linearity; an undirected seed (a junction, a
+             blob, a lone voxel) gets the zero vector and its curve is laid along +-Y
+
 There is NO occlusion reasoning: a voxel behind a surface is seen by the views that look at it through the surface, and
 with few views the back-projections of unrelated edge pixels intersect in empty space ("ghosts"); min_views / min_ratio
-are the only defence.  The curve direction is not seeded.  The defaults of ``seed_points`` are untuned.
+are the only defence.  The curve direction is not seeded unless ``directions=True``.  The defaults of ``seed_points``
+are untuned, those of the directions (DIR_RADIUS, DIR_MIN_SUPPORT, DIR_MIN_LINEARITY) included.
 
 Two back ends: ``"gpu"``, HIP, and ``"host"``, numpy -- the same rules, for a machine without a GPU and what the tests hold
-the kernels against.  Selection and thinning are integer numpy on both."""
+the kernels against.  Selection, thinning, the keep bits and the eigen-decomposition are numpy on both."""
 import ctypes as C
 
 import numpy as np
@@ -36,6 +57,10 @@ MAX_VOXELS = 2 ** 31 - 1
 BYTE_BUDGET = 1 << 30     # bytes of masks, transforms, scratch and bits per chunk of views in seed_points
 BYTES_PER_PIXEL = 8       # uint8 mask, uint16 column pass, int32 transform, one bit (rounded up)
 HOST_SLAB = 1 << 18       # voxels per numpy slab of the host back end
+SEED_MAX_RADIUS = L.SEED_MAX_RADIUS
+MOMENT_VALUES = 10        # m, sum d [3], sum d^2 [3], sum dx dy, sum dx dz, sum dy dz
+# UNTUNED, like the other defaults of this module: no scan has been trained against them beyond the drawn test scan
+DIR_RADIUS, DIR_MIN_SUPPORT, DIR_MIN_LINEARITY = 6, 6, 0.5
 
 
 def _check_backend(backend):
@@ -202,10 +227,11 @@ def select_voxels(seen, hit, min_views, min_ratio):
     return (seen >= int(min_views)) & (hit >= need[seen])
 
 
-def thin_to_seeds(keep, hit, bounds, dims, cell, max_seeds):
+def thin_to_seeds(keep, hit, bounds, dims, cell, max_seeds, return_centres=False):
     """One seed per cell of ``cell``^3 voxels that holds a kept voxel (module docstring).  Returns (seeds float64 [N,3],
     info): info = {"cells": the cells with a kept voxel, "capped": whether max_seeds cut them, "cell_index": int64 [N],
-    "hit_sum": int64 [N]}."""
+    "hit_sum": int64 [N]}, and with ``return_centres`` also "centre_voxel": int64 [N,3], the centre voxel of every seed
+    (module docstring), cut by max_seeds along with the rest."""
     lo, _, (nx, ny, nz), step = _grid(bounds, dims)
     cell, max_seeds = int(cell), int(max_seeds)
     if cell < 1 or max_seeds < 1:
@@ -221,7 +247,10 @@ def thin_to_seeds(keep, hit, bounds, dims, cell, max_seeds):
     order = np.argsort(cidx, kind="stable")
     cells, first, count = np.unique(cidx[order], return_index=True, return_counts=True)
     if cells.size == 0:
-        return np.zeros((0, 3), np.float64), {"cells": 0, "capped": False, "cell_index": cells, "hit_sum": cells.copy()}
+        info = {"cells": 0, "capped": False, "cell_index": cells, "hit_sum": cells.copy()}
+        if return_centres:
+            info["centre_voxel"] = np.zeros((0, 3), np.int64)
+        return np.zeros((0, 3), np.float64), info
     sums = np.add.reduceat(ijk[order], first, axis=0)          # int64
     hit_sum = np.add.reduceat(hit[g][order], first)
     capped = cells.size > max_seeds
@@ -231,7 +260,121 @@ def thin_to_seeds(keep, hit, bounds, dims, cell, max_seeds):
         cells, sums, count, hit_sum = cells[sel], sums[sel], count[sel], hit_sum[sel]
     mean = sums.astype(np.float64) / count.astype(np.float64)[:, None]
     seeds = lo[None, :] + (mean + 0.5) * step[None, :]
-    return seeds, {"cells": int(first.size), "capped": bool(capped), "cell_index": cells, "hit_sum": hit_sum}
+    info = {"cells": int(first.size), "capped": bool(capped), "cell_index": cells, "hit_sum": hit_sum}
+    if return_centres:
+        info["centre_voxel"] = (2 * sums + count[:, None]) // (2 * count[:, None])   # int64: floor(mean + 0.5)
+    return seeds, info
+
+
+# ------------------------------------------------------------------------------------------------ directions
+def keep_bits(keep, dims):
+    """The selection mask ``keep`` (bool [nx ny nz], x fastest, as ``select_voxels`` returns it) packed into the keep bits
+    of the module docstring: an int32 [nz, ny, ceil(nx / 32)] CPU tensor.  numpy on both back ends: n / 8 bytes."""
+    nx, ny, nz = (int(d) for d in dims)
+    if min(nx, ny, nz) < 1:
+        raise ValueError(f"dims must be three positive integers (got {(nx, ny, nz)})")
+    keep = np.asarray(keep.detach().cpu().numpy() if torch.is_tensor(keep) else keep).reshape(-1).astype(bool)
+    if keep.size != nx * ny * nz:
+        raise ValueError(f"keep_bits: keep must hold {nx * ny * nz} voxels (got {keep.size})")
+    stride = bits_stride(nx)
+    padded = np.zeros((nz, ny, stride * 32), bool)
+    padded[:, :, :nx] = keep.reshape(nz, ny, nx)
+    words = np.packbits(padded, axis=-1, bitorder="little").view("<u4")
+    return torch.from_numpy(np.ascontiguousarray(words).view(np.int32).reshape(nz, ny, stride))
+
+
+def _ball_offsets(radius):
+    """int64 [K,3]: the offsets (dx, dy, dz) with dx^2 + dy^2 + dz^2 <= radius^2."""
+    a = np.arange(-radius, radius + 1, dtype=np.int64)
+    dz, dy, dx = np.meshgrid(a, a, a, indexing="ij")
+    d = np.stack([dx.ravel(), dy.ravel(), dz.ravel()], 1)
+    return d[(d * d).sum(1) <= radius * radius]
+
+
+def _moments_host(words, dims, centres, radius):
+    nx, ny, nz = dims
+    words = words.view(np.uint32)
+    d = _ball_offsets(radius)
+    feat = np.stack([np.ones(len(d), np.int64), d[:, 0], d[:, 1], d[:, 2], d[:, 0] ** 2, d[:, 1] ** 2, d[:, 2] ** 2,
+                     d[:, 0] * d[:, 1], d[:, 0] * d[:, 2], d[:, 1] * d[:, 2]], 1)
+    out = np.zeros((centres.shape[0], MOMENT_VALUES), np.int64)
+    per = max(1, HOST_SLAB // len(d))   # seeds per slab: [slab, K] temporaries
+    for s0 in range(0, centres.shape[0], per):
+        q = centres[s0:s0 + per, None, :] + d[None, :, :]
+        x, y, z = q[..., 0], q[..., 1], q[..., 2]
+        inside = (x >= 0) & (x < nx) & (y >= 0) & (y < ny) & (z >= 0) & (z < nz)
+        xi, yi, zi = np.where(inside, x, 0), np.where(inside, y, 0), np.where(inside, z, 0)
+        bit = (words[zi, yi, xi >> 5] >> (xi & 31).astype(np.uint32)) & np.uint32(1)
+        out[s0:s0 + per] = (inside & (bit != 0)).astype(np.int64) @ feat
+    return out.astype(np.int32)
+
+
+def voxel_moments(bits, dims, centres, radius, backend="gpu", device=None):
+    """int32 [N,10] tensor: the moments of the module docstring of the kept voxels within ``radius`` voxels of every
+    centre.  bits: ``keep_bits``, int32 [nz, ny, ceil(nx / 32)] (tensor or array); centres: integer [N,3] voxel
+    coordinates inside the grid.  ``backend="gpu"``: ``cgs_voxel_moments``, a device tensor; ``backend="host"``: numpy, a
+    CPU tensor.  A centre outside the grid, a radius outside [1, SEED_MAX_RADIUS] and bits of another shape or dtype are
+    ValueErrors."""
+    _check_backend(backend)
+    dims = tuple(int(v) for v in dims)
+    if len(dims) != 3 or min(dims) < 1:
+        raise ValueError(f"dims must be three positive integers (got {dims})")
+    if dims[0] * dims[1] * dims[2] > MAX_VOXELS:
+        raise ValueError(f"a grid holds at most 2^31 - 1 voxels (got {dims})")
+    if int(radius) != radius or not (1 <= int(radius) <= SEED_MAX_RADIUS):
+        raise ValueError(f"voxel_moments: the radius must be an integer in [1, {SEED_MAX_RADIUS}] (got {radius})")
+    radius = int(radius)
+    if not torch.is_tensor(bits):
+        bits = torch.from_numpy(np.ascontiguousarray(bits))
+    want = (dims[2], dims[1], bits_stride(dims[0]))
+    if bits.dtype != torch.int32 or tuple(bits.shape) != want:
+        raise ValueError(f"voxel_moments: bits must be int32 {list(want)} (got {bits.dtype} {tuple(bits.shape)})")
+    cen = centres.detach().cpu().numpy() if torch.is_tensor(centres) else np.asarray(centres)
+    if cen.size == 0:
+        cen = cen.reshape(0, 3)
+    if cen.ndim != 2 or cen.shape[1] != 3 or cen.dtype.kind not in "iu":
+        raise ValueError("voxel_moments: centres must be integer [N,3] voxel coordinates")
+    cen = np.ascontiguousarray(cen.astype(np.int64))
+    if cen.shape[0] and ((cen < 0).any() or (cen >= np.array(dims, np.int64)[None, :]).any()):
+        raise ValueError(f"voxel_moments: a centre lies outside the {dims} grid")
+    N = cen.shape[0]
+    if backend == "host":
+        return torch.from_numpy(_moments_host(np.ascontiguousarray(bits.detach().cpu().numpy()), dims, cen, radius))
+    dev = ES._device_for([bits], "voxel_moments", device)
+    with L.device_guard(dev):
+        bits = bits.to(dev).contiguous()
+        cen_d = torch.from_numpy(cen.astype(np.int32)).to(dev)
+        out = torch.empty((N, MOMENT_VALUES), dtype=torch.int32, device=dev)
+        if N > 0:
+            rc = L.load().cgs_voxel_moments(dims[0], dims[1], dims[2], L.ptr(bits), N, L.ptr(cen_d), radius, L.ptr(out),
+                                            L.raw_stream(dev))
+            L.check(rc, "cgs_voxel_moments")
+    return out
+
+
+def seed_directions(moments, min_support=DIR_MIN_SUPPORT, min_linearity=DIR_MIN_LINEARITY):
+    """moments: int32 [N,10] (``voxel_moments``; tensor or array).  Returns (directions float64 [N,3] -- unit rows, zero
+    rows for undirected seeds --, directed bool [N], linearity float64 [N]) by the direction rule of the module docstring.
+    Host float64 code on both back ends."""
+    mom = (moments.detach().cpu().numpy() if torch.is_tensor(moments) else np.asarray(moments)).astype(np.int64)
+    if mom.ndim != 2 or mom.shape[1] != MOMENT_VALUES:
+        raise ValueError(f"seed_directions: moments must be [N,{MOMENT_VALUES}]")
+    N = mom.shape[0]
+    if N == 0:
+        return np.zeros((0, 3), np.float64), np.zeros(0, bool), np.zeros(0, np.float64)
+    m, s = mom[:, 0], mom[:, 1:4]
+    second = np.empty((N, 3, 3), np.int64)
+    for (a, b), col in (((0, 0), 4), ((1, 1), 5), ((2, 2), 6), ((0, 1), 7), ((0, 2), 8), ((1, 2), 9)):
+        second[:, a, b] = second[:, b, a] = mom[:, col]
+    scatter = m[:, None, None] * second - s[:, :, None] * s[:, None, :]   # int64: below 2^63 by the bound on the moments
+    lam, vec = np.linalg.eigh(scatter.astype(np.float64))
+    top = vec[:, :, 2]
+    lead = np.argmax(np.abs(top), axis=1)                                  # the first of equal magnitudes: the lowest axis
+    top = np.where(top[np.arange(N), lead][:, None] < 0.0, -top, top)
+    positive = lam[:, 2] > 0.0
+    linearity = np.where(positive, (lam[:, 2] - lam[:, 1]) / np.where(positive, lam[:, 2], 1.0), 0.0)
+    directed = (m >= int(min_support)) & (linearity >= float(min_linearity))
+    return np.where(directed[:, None], top, 0.0), directed, linearity
 
 
 # ------------------------------------------------------------------------------------------------ a scan
@@ -249,7 +392,9 @@ def grid_dims(bounds, grid):
 
 
 def seed_points(cameras, edge_maps_u8, detector, bounds, grid=128, tol_px=2, min_views=3, min_ratio=0.8, cell=4,
-                max_seeds=20000, edge_threshold=EDGE_MAX_THRESHOLD, backend="gpu", device=None, budget_bytes=None):
+                max_seeds=20000, edge_threshold=EDGE_MAX_THRESHOLD, backend="gpu", device=None, budget_bytes=None,
+                directions=False, dir_radius=DIR_RADIUS, dir_min_support=DIR_MIN_SUPPORT,
+                dir_min_linearity=DIR_MIN_LINEARITY):
     """cameras: ``NovelViewCamera`` s; edge_maps_u8: one uint8 [H,W] map per camera (a list or an [V,H,W] array), the
     stored bytes of the detector's maps, as ``score_edges`` takes them.  bounds = (lo, hi) of the box to search.
 
@@ -261,7 +406,12 @@ def seed_points(cameras, edge_maps_u8, detector, bounds, grid=128, tol_px=2, min
 
     Returns (seeds float64 [N,3], info) with info = {"dims", "voxels", "views", "kept_voxels", "cells", "seeds", "capped",
     "backend"}.  THE DEFAULTS ARE UNTUNED (no scan has been measured against them), there is no occlusion reasoning, and
-    the curve direction is not seeded.  ``backend``: "gpu" (HIP; ``device``) or "host" (numpy)."""
+    the curve direction is not seeded unless ``directions=True``.  ``backend``: "gpu" (HIP; ``device``) or "host" (numpy).
+
+    ``directions=True``: the kept voxels within ``dir_radius`` voxels of every seed's centre voxel give its direction
+    (``keep_bits``, ``voxel_moments`` on ``backend``, ``seed_directions(dir_min_support, dir_min_linearity)``; module
+    docstring); info additionally holds "directions" (float64 [N,3]: unit rows, zero rows for undirected seeds) and
+    "directed" (their count).  These three defaults are untuned too."""
     from ..edge_extraction.novel_view import camera_arrays
     from ..edge_extraction.reprojection import detected_lut
     _check_backend(backend)
@@ -277,6 +427,8 @@ def seed_points(cameras, edge_maps_u8, detector, bounds, grid=128, tol_px=2, min
             raise ValueError(f"seed_points: the edge map of {c.name} must be uint8 [{c.height},{c.width}] (got {m.dtype} "
                              f"{m.shape})")
     ES.tolerances_squared([tol_px])
+    if directions and (int(dir_radius) != dir_radius or not (1 <= int(dir_radius) <= SEED_MAX_RADIUS)):
+        raise ValueError(f"seed_points: dir_radius must be an integer in [1, {SEED_MAX_RADIUS}] (got {dir_radius})")
     dims = grid_dims(bounds, grid)
     _grid(bounds, dims)
     need_table(min_ratio, 0)
@@ -304,7 +456,11 @@ def seed_points(cameras, edge_maps_u8, detector, bounds, grid=128, tol_px=2, min
         counts = (torch.zeros(n, dtype=torch.uint16), torch.zeros(n, dtype=torch.uint16))
     seen, hit = (c.cpu().numpy() for c in counts)
     keep = select_voxels(seen, hit, min_views, min_ratio)
-    seeds, thin = thin_to_seeds(keep, hit, bounds, dims, cell, max_seeds)
+    seeds, thin = thin_to_seeds(keep, hit, bounds, dims, cell, max_seeds, return_centres=bool(directions))
     info = {"dims": dims, "voxels": n, "views": len(cameras), "kept_voxels": int(np.count_nonzero(keep)),
             "cells": thin["cells"], "seeds": int(seeds.shape[0]), "capped": thin["capped"], "backend": backend}
+    if directions:
+        moments = voxel_moments(keep_bits(keep, dims), dims, thin["centre_voxel"], dir_radius, backend=backend, device=device)
+        vectors, directed, _ = seed_directions(moments, dir_min_support, dir_min_linearity)
+        info["directions"], info["directed"] = vectors, int(np.count_nonzero(directed))
     return seeds, info

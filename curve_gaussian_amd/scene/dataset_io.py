@@ -179,8 +179,10 @@ def edge_vote_point_cloud(cameras, detector, bounds, rng=None, **options) -> Bas
     """A seed cloud from the edge maps of the cameras a Scene trains on (``EdgeCamera`` s): the multi-view voxel vote of
     ``ops.edge_seed.seed_points`` over ``bounds`` = (lo, hi), every view voting with the camera it is trained with
     (``reprojection.scene_cameras``).  ``options``: seed_points' keywords (grid, tol_px, min_views, min_ratio, cell,
-    max_seeds, edge_threshold, backend, device, budget_bytes).  Colours as grid_point_cloud's.  No seed is a ValueError
-    that names the bounds and the counts: there is no fallback to another cloud."""
+    max_seeds, edge_threshold, backend, device, budget_bytes, directions, dir_radius, dir_min_support,
+    dir_min_linearity).  Colours as grid_point_cloud's.  The normals are zeros, or with ``directions=True`` the seeded
+    directions (unit rows, zero rows for undirected seeds).  No seed is a ValueError that names the bounds and the
+    counts: there is no fallback to another cloud."""
     from ..edge_extraction.reprojection import scene_cameras
     from ..ops.edge_seed import seed_points
     cams, maps = scene_cameras(cameras)
@@ -190,7 +192,8 @@ def edge_vote_point_cloud(cameras, detector, bounds, rng=None, **options) -> Bas
         raise ValueError(f"edge_vote_point_cloud: no seed in the box lo={lo}, hi={hi}: {info['views']} views voted on "
                          f"{info['dims']} voxels, {info['kept_voxels']} passed the selection, {info['cells']} cells hold one")
     rnd = (rng.random if rng is not None else np.random.random)((seeds.shape[0], 3))
-    return BasicPointCloud(points=seeds, colors=SH2RGB(rnd / 255.0), normals=np.zeros((seeds.shape[0], 3)))
+    normals = info["directions"] if options.get("directions", False) else np.zeros((seeds.shape[0], 3))
+    return BasicPointCloud(points=seeds, colors=SH2RGB(rnd / 255.0), normals=normals)
 
 
 def write_emap(path, cameras, edge_maps, detector="DexiNed"):
@@ -292,13 +295,17 @@ def write_edge_files(model_path, edge_dict, pts):
     write_points_ply(os.path.join(model_path, "edge_points.ply"), pts)
 
 
-def write_points_ply(path, pts):
-    """`pts` [N,3] as an ASCII PLY of double x y z (train.py:277-285)."""
+def write_points_ply(path, pts, normals=None):
+    """`pts` [N,3] as an ASCII PLY of double x y z (train.py:277-285); with `normals` [N,3], of double x y z nx ny nz."""
+    extra = "property double nx\nproperty double ny\nproperty double nz\n" if normals is not None else ""
     with open(path, "w") as f:
         f.write("ply\nformat ascii 1.0\nelement vertex %d\nproperty double x\nproperty double y\nproperty double z\n"
-                "end_header\n" % len(pts))
-        for p in pts:
-            f.write("%.10g %.10g %.10g\n" % (p[0], p[1], p[2]))
+                "%send_header\n" % (len(pts), extra))
+        for k, p in enumerate(pts):
+            if normals is None:
+                f.write("%.10g %.10g %.10g\n" % (p[0], p[1], p[2]))
+            else:
+                f.write("%.10g %.10g %.10g %.10g %.10g %.10g\n" % (p[0], p[1], p[2], *normals[k]))
 
 
 # ------------------------------------------------------------------------------------------ splat snapshot (PLY)

@@ -30,11 +30,20 @@ def get_expon_lr_func(lr_init, lr_final, lr_delay_steps=0, lr_delay_mult=1.0, ma
     return helper
 
 
-def initialize_bezier_curves(points, bound, n_control_points=4):
+def initialize_bezier_curves(points, bound, n_control_points=4, directions=None):
     """One cubic Bezier per seed point, laid along +-Y (reference :27-51): P0 = p - (0, bound, 0), P3 = p + (0, bound, 0),
-    P1 / P2 at half that distance.  points [B,3], bound [B,1] -> [B,4,3]."""
+    P1 / P2 at half that distance.  points [B,3], bound [B,1] -> [B,4,3].  ``directions`` (not in the reference): [B,3]
+    with unit or zero rows; the curve of a unit row d is laid along +-d (the offset is bound * d), that of a zero row
+    along +-Y."""
     assert n_control_points == 4
-    direction = torch.cat([torch.zeros_like(bound), bound, torch.zeros_like(bound)], dim=1)
+    if directions is None:
+        direction = torch.cat([torch.zeros_like(bound), bound, torch.zeros_like(bound)], dim=1)
+    else:
+        directions = directions.to(device=points.device, dtype=points.dtype)
+        if directions.shape != points.shape:
+            raise ValueError(f"directions must be {tuple(points.shape)} (got {tuple(directions.shape)})")
+        y_axis = torch.tensor([0.0, 1.0, 0.0], device=points.device, dtype=points.dtype)
+        direction = bound * torch.where((directions == 0).all(dim=1, keepdim=True), y_axis, directions)
     return torch.stack([points - direction, points - 0.5 * direction, points + 0.5 * direction, points + direction], dim=1)
 
 
@@ -139,11 +148,13 @@ class GaussianCurveModel:
         self.prepare_scaling_rot()
         return self
 
-    def create_from_pcd(self, pcd, cam_infos, spatial_lr_scale: float, init_size: float = 0.5, n_control_points: int = 4):
+    def create_from_pcd(self, pcd, cam_infos, spatial_lr_scale: float, init_size: float = 0.5, n_control_points: int = 4,
+                        directions=None):
         """Reference :142-178: one curve per point of the seed cloud.  bound = init_size * sqrt(mean squared distance to
         the 3 nearest neighbours) from the HIP ``simple_knn.distCUDA2``; control points along +-Y; opacity 0.6, width
         5e-3; DC feature = RGB2SH of the red channel, replicated over the curve's m samples; mask = 1; all curves Bezier;
-        one 3x4 identity exposure per camera.  `pcd`: anything with ``.points`` / ``.colors`` ([N,3] arrays)."""
+        one 3x4 identity exposure per camera.  `pcd`: anything with ``.points`` / ``.colors`` ([N,3] arrays).
+        ``directions`` (not in the reference): [N,3] unit or zero rows, see initialize_bezier_curves."""
         from ..simple_knn import distCUDA2
         from .dataset_io import RGB2SH
         dev = self.device
@@ -153,7 +164,9 @@ class GaussianCurveModel:
         dist2 = torch.clamp_min(distCUDA2(torch.from_numpy(np.asarray(pcd.points)).float().to(dev)), 0.0000001)
         self.dist = torch.sqrt(dist2).mean()
         bound = init_size * torch.sqrt(dist2).unsqueeze(1)
-        points_per_curve = initialize_bezier_curves(fused_point_cloud, bound, n_control_points)
+        if directions is not None:
+            directions = (directions if torch.is_tensor(directions) else torch.tensor(np.asarray(directions))).float().to(dev)
+        points_per_curve = initialize_bezier_curves(fused_point_cloud, bound, n_control_points, directions)
         B = fused_point_cloud.shape[0]
         opacities = torch.logit(0.6 * torch.ones((B, 1), dtype=torch.float, device=dev))   # inverse_sigmoid
         widths = self.scaling_inverse_activation(5e-3 * torch.ones((B, 1), dtype=torch.float, device=dev))
@@ -484,7 +497,8 @@ class Scene:
     it is trained with, ``undistort`` included).  ``init_options``: the keywords of ops.edge_seed.seed_points, and
     ``bounds`` = (lo, hi) (default: dataset_io.default_seed_bounds -- the reference's box for EMAP, the trimmed extent of
     the SfM cloud for COLMAP); the vote runs on the GPU when `device` is one, on the host otherwise, unless ``backend``
-    says so.  No seed, or an unknown ``init``, is a ValueError: there is no fallback."""
+    says so.  With ``"directions": True`` among them the vote also seeds the curves' directions: the cloud's normals hold
+    them and are handed to ``create_from_pcd``.  No seed, or an unknown ``init``, is a ValueError: there is no fallback."""
 
     def __init__(self, source_path, gaussians, detector="DexiNed", num_pts_per_axis=15, cameras_extent=None, rng=None,
                  device=None, eval=False, llffhold=8, images=None, resolution=-1, undistort=False, init="reference",
@@ -510,6 +524,7 @@ class Scene:
                 centres = torch.stack([c.camera_center for c in self.train_cameras]).double()
                 cameras_extent = float((centres - centres.mean(0)).norm(dim=1).max() * 1.1)
         self.cameras_extent = cameras_extent
+        directed = False
         if init == "edge_votes":
             opts = dict(init_options or {})
             layout = "colmap" if os.path.exists(os.path.join(source_path, "sparse")) else "emap"
@@ -520,12 +535,17 @@ class Scene:
             opts.setdefault("backend", "gpu" if on_gpu else "host")
             if opts["backend"] == "gpu" and on_gpu:
                 opts.setdefault("device", device)
+            directed = bool(opts.get("directions", False))
             self.point_cloud = dataset_io.edge_vote_point_cloud(self.train_cameras, detector, bounds, rng, **opts)
         if device is not None:
             moved = {id(c): c.to(device) for c in self.train_cameras + self.test_cameras}
             self.train_cameras = [moved[id(c)] for c in self.train_cameras]
             self.test_cameras = [moved[id(c)] for c in self.test_cameras]
-        gaussians.create_from_pcd(self.point_cloud, self.train_cameras, self.cameras_extent)
+        if directed:
+            gaussians.create_from_pcd(self.point_cloud, self.train_cameras, self.cameras_extent,
+                                      directions=self.point_cloud.normals)
+        else:
+            gaussians.create_from_pcd(self.point_cloud, self.train_cameras, self.cameras_extent)
 
     def getTrainCameras(self, scale=1.0):
         return self.train_cameras

@@ -3,7 +3,7 @@
 
     python -m curve_gaussian_amd.train -s SCAN -m OUT [--iterations N] [--backend graphed|direct|autograd|torch]
                                        [--draw_snapshots] [--topology_backend host|gpu] [--report_dir DIR] [--undistort]
-                                       [--init reference|edge_votes]
+                                       [--init reference|edge_votes] [--init_directions]
 
 The loop keeps the reference's order.  Per iteration: learning rate, SH degree every 1000 iterations, a random view without
 replacement, render + losses + every regulariser + backward (one ``TrainStep`` call), densification statistics before
@@ -326,6 +326,14 @@ def build_parser():
     p.add_argument("--init_min_views", type=int, default=None, help="edge_votes: views that must see a voxel")
     p.add_argument("--init_min_ratio", type=float, default=None, help="edge_votes: share of the seeing views that must vote")
     p.add_argument("--init_cell", type=int, default=None, help="edge_votes: voxels per axis thinned to one seed")
+    p.add_argument("--init_directions", action="store_true",
+                   help="edge_votes: lay every curve along the principal axis of the kept voxels around its seed instead of "
+                        "+-Y (untuned defaults)")
+    p.add_argument("--init_dir_radius", type=int, default=None, help="edge_votes: voxels around a seed that give its direction")
+    p.add_argument("--init_dir_min_support", type=int, default=None,
+                   help="edge_votes: kept voxels a seed needs around it to be given a direction")
+    p.add_argument("--init_dir_min_linearity", type=float, default=None,
+                   help="edge_votes: (l2 - l1) / l2 of the voxels' scatter a seed needs to be given a direction")
     p.add_argument("--init_bounds", nargs=6, type=float, default=None, metavar=("X0", "Y0", "Z0", "X1", "Y1", "Z1"),
                    help="edge_votes: the box to search (default: the reference's box, or the trimmed extent of the SfM cloud)")
     p.add_argument("--iterations", type=int, default=None)
@@ -359,7 +367,11 @@ def parse_args(argv):
         opt.iterations = args.iterations
     args.save_iterations.append(opt.iterations)                                     # :404
     init_options = {k: v for k, v in (("grid", args.init_grid), ("tol_px", args.init_tol_px), ("min_views", args.init_min_views),
-                                      ("min_ratio", args.init_min_ratio), ("cell", args.init_cell)) if v is not None}
+                                      ("min_ratio", args.init_min_ratio), ("cell", args.init_cell),
+                                      ("dir_radius", args.init_dir_radius), ("dir_min_support", args.init_dir_min_support),
+                                      ("dir_min_linearity", args.init_dir_min_linearity)) if v is not None}
+    if args.init_directions:
+        init_options["directions"] = True
     if args.init_bounds is not None:
         init_options["bounds"] = (args.init_bounds[:3], args.init_bounds[3:])
     dataset = ModelParams(source_path, args.model_path, args.sh_degree, args.n_gaussians, args.detector, args.resolution,

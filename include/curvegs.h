@@ -915,6 +915,23 @@ int cgs_voxel_votes(int nx, int ny, int nz, const double* lo /*host, [3]*/, cons
                     const uint32_t* bits /*[V,height,ceil(width/32)]*/, int accumulate, uint16_t* seen /*[nx ny nz]*/,
                     uint16_t* hit /*[nx ny nz]*/, void* stream);
 
+/* cgs_voxel_moments: the direction of a seed from the kept voxels around it.  keep_bits is the selection mask of the grid
+ * packed like the near masks with x fastest: word w of row (j, k) holds voxels i = 32 w .. 32 w + 31, bit b is voxel
+ * 32 w + b; the row stride is ceil(nx / 32) words, rows are ordered (k ny + j), padding bits are 0 -- [nz, ny, ceil(nx / 32)]
+ * uint32, device.  centres is int32 [N,3], device: the centre voxel (cx, cy, cz) of every seed, inside the grid (a centre
+ * outside it reads nothing and gives a zero row).  The window of a seed is every voxel q of the grid with its keep bit set
+ * and |q - c|^2 <= radius^2 (an integer comparison: a ball clipped to the grid, not a cube).  With d = q - c over the
+ * window, moments[s] = (m, sum dx, sum dy, sum dz, sum dx^2, sum dy^2, sum dz^2, sum dx dy, sum dx dz, sum dy dz), int32
+ * [N,10]: every value is bounded by (2 radius + 1)^3 radius^2 <= 6.8e6, so the sums are exact and their order cannot
+ * matter.  One wave per seed; no atomics, no float, the kernel writes every output word (no memset), the caller's stream,
+ * no allocation, no host synchronisation; the result does not depend on the launch geometry.  N = 0 is a no-op.  N < 0, a
+ * non-positive dim, more than 2^31 - 1 voxels, a radius outside [1, CGS_SEED_MAX_RADIUS] and NULL pointers are
+ * CGS_ERR_INVALID_ARGUMENT, rejected before anything is launched. */
+#define CGS_SEED_MAX_RADIUS 15
+int cgs_voxel_moments(int nx, int ny, int nz, const void* keep_bits /*[nz,ny,ceil(nx/32)] uint32*/, int N,
+                      const void* centres /*int32 [N,3], inside the grid*/, int radius, void* moments /*int32 [N,10]*/,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif
