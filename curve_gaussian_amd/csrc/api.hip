@@ -1930,4 +1930,67 @@ int cgs_voxel_moments(int nx, int ny, int nz, const void* keep_bits, int N, cons
     return CGS_OK;
 }
 
+// The checks that cgs_ray_claims and cgs_ray_wins share with cgs_voxel_votes: dims, sizes, the list, lo and step.
+static bool ray_args_ok(const char* name, int nx, int ny, int nz, const double* lo, const double* step, int M, int V,
+                        int height, int width) {
+    if (M < 0 || V < 0 || V > CGS_SEED_MAX_VIEWS || nx <= 0 || ny <= 0 || nz <= 0 || !edt_size_ok(height, width)) {
+        set_error("%s: invalid argument (dims=%dx%dx%d, M=%d, V=%d, height=%d, width=%d)", name, nx, ny, nz, M, V, height,
+                  width);
+        return false;
+    }
+    if ((long long)nx * ny > INT32_MAX || (long long)nx * ny * nz > INT32_MAX) {   // the first product is below 2^62
+        set_error("%s: invalid argument (%dx%dx%d voxels: at most 2^31 - 1)", name, nx, ny, nz);
+        return false;
+    }
+    if (!lo || !step) {
+        set_error("%s: invalid argument (NULL pointer)", name);
+        return false;
+    }
+    for (int a = 0; a < 3; a++)
+        if (!std::isfinite(lo[a]) || !std::isfinite(step[a]) || !(step[a] > 0.0)) {
+            set_error("%s: invalid argument (axis %d: lo=%g, step=%g)", name, a, lo[a], step[a]);
+            return false;
+        }
+    return true;
+}
+
+int cgs_ray_claims(int nx, int ny, int nz, const double* lo, const double* step, int M, const int32_t* index,
+                   const uint16_t* support, int V, const double* intr, const double* w2c, int height, int width,
+                   const uint32_t* bits, int clear, uint32_t* best, void* stream_) {
+    if (!ray_args_ok("cgs_ray_claims", nx, ny, nz, lo, step, M, V, height, width)) return CGS_ERR_INVALID_ARGUMENT;
+    if ((V > 0 && !best) || (M > 0 && V > 0 && (!index || !support || !intr || !w2c || !bits))) {
+        set_error("cgs_ray_claims: invalid argument (NULL pointer)");
+        return CGS_ERR_INVALID_ARGUMENT;
+    }
+    if (launch_ray_claims((hipStream_t)stream_, nx, ny, nz, lo, step, M, index, support, V, intr, w2c, height, width, bits,
+                          clear, best) != hipSuccess) {
+        set_error("cgs_ray_claims: clearing the claims failed");
+        return CGS_ERR_HIP;
+    }
+    if (M == 0 || V == 0) return CGS_OK;
+    if (!check_launch("ray_claims", false, (hipStream_t)stream_)) return CGS_ERR_HIP;
+    return CGS_OK;
+}
+
+int cgs_ray_wins(int nx, int ny, int nz, const double* lo, const double* step, int M, const int32_t* index,
+                 const uint16_t* support, int V, const double* intr, const double* w2c, int height, int width,
+                 const uint32_t* bits, const uint32_t* best, int window, int margin, int accumulate, uint16_t* wins,
+                 void* stream_) {
+    if (!ray_args_ok("cgs_ray_wins", nx, ny, nz, lo, step, M, V, height, width)) return CGS_ERR_INVALID_ARGUMENT;
+    if (window < 0 || window > CGS_SEED_MAX_WINDOW || margin < 0 || margin > 65535) {
+        set_error("cgs_ray_wins: invalid argument (window=%d, margin=%d; the window lies in [0, %d], the margin in [0, 65535])",
+                  window, margin, CGS_SEED_MAX_WINDOW);
+        return CGS_ERR_INVALID_ARGUMENT;
+    }
+    if (M > 0 && V > 0 && (!index || !support || !intr || !w2c || !bits || !best || !wins)) {
+        set_error("cgs_ray_wins: invalid argument (NULL pointer)");
+        return CGS_ERR_INVALID_ARGUMENT;
+    }
+    if (M == 0 || V == 0) return CGS_OK;
+    launch_ray_wins((hipStream_t)stream_, nx, ny, nz, lo, step, M, index, support, V, intr, w2c, height, width, bits, best,
+                    window, margin, accumulate, wins);
+    if (!check_launch("ray_wins", false, (hipStream_t)stream_)) return CGS_ERR_HIP;
+    return CGS_OK;
+}
+
 }  // extern "C"

@@ -1,7 +1,8 @@
 // Multi-view voxel vote: where do the edge maps of a scan say the edges are?  (include/curvegs.h, cgs_pack_near_bits /
-// cgs_voxel_votes / cgs_voxel_moments.)  Every voxel centre of a regular grid is projected into every view and counts the
-// views that see it and the views in which it lands within a tolerance of a detected edge pixel; the kept voxels around a
-// seed then give the seed's direction through their integer second moments.  Three kernels:
+// cgs_voxel_votes / cgs_voxel_moments / cgs_ray_claims / cgs_ray_wins.)  Every voxel centre of a regular grid is projected
+// into every view and counts the views that see it and the views in which it lands within a tolerance of a detected edge
+// pixel; the kept voxels around a seed then give the seed's direction through their integer second moments; on request the
+// kept voxels first claim the pixels they land on and only those that win their claims stay.  Five kernels:
 //   k_pack_near_bits   one thread per pixel of the PADDED row (32 * stride pixels, stride = ceil(W / 32) words): the bit is
 //                      dist2 <= tol2 inside the image and 0 in the padding, one wave ballot gives two words, lanes 0 and 32
 //                      store them.  A padded plane is a whole number of words, so the linear pixel index / 32 is the word
@@ -21,7 +22,18 @@
 //                      the set bits in registers.  One shuffle reduction per wave, lane 0 stores the ten values: every
 //                      output word is written, no memset.  Integers only, no atomics, no LDS, no barrier (a wave without a
 //                      seed leaves at once): the result does not depend on the launch geometry.
-// Voxel, map and keep-bit offsets are 64-bit.
+//   k_ray_claims       one thread per LISTED voxel (the kept voxels, ascending linear indices).  The same centre, the same
+//                      projection and the same near bit as k_voxel_votes, through the same device functions (seed_centre,
+//                      seed_pixel): a pixel that differs between the vote and the claim would be a bug that no tolerance
+//                      hides.  Where the voxel hits, its support goes into best[v][y][x] by atomicMax on unsigned int: the
+//                      one atomic of this file, and an integer maximum does not depend on the order, so the result still
+//                      does not depend on the launch geometry.
+//   k_ray_wins         one thread per listed voxel, the same walk.  Where the voxel hits, the maximum of best over the
+//                      (2 w + 1)^2 window around its pixel, clipped to the image, by plain loads; the view is won when
+//                      support + margin (32 bits) reaches it.  The count stays in a register; one plain 16-bit store at the
+//                      end (a read-add-store of the thread's own word with `accumulate`).  No atomics, no LDS, no barrier.
+//                      An index outside the grid (the caller's error) reads nothing, claims nothing and wins nothing.
+// Voxel, map, keep-bit and pixel offsets are 64-bit.
 #include <algorithm>
 
 #include "kernels.h"
@@ -57,6 +69,33 @@ __global__ void __launch_bounds__(SEED_THREADS) k_pack_near_bits(int height, int
         bits[(size_t)view * (size_t)height * (size_t)stride + (size_t)(p >> 5)] = (unsigned int)(lane ? b >> 32 : b);
 }
 
+// The centre of the voxel with linear index `id` (x fastest): float64, then the float32 point that the projection contract
+// is written for, widened again.
+__device__ inline void seed_centre(const SeedGrid& g, long long id, double& X, double& Y, double& Z) {
+#pragma clang fp contract(off)
+    const int i = (int)(id % g.nx);
+    const long long r = id / g.nx;
+    const int j = (int)(r % g.ny), k = (int)(r / g.ny);
+    X = (double)(float)(g.lo[0] + ((double)i + 0.5) * g.step[0]);
+    Y = (double)(float)(g.lo[1] + ((double)j + 0.5) * g.step[1]);
+    Z = (double)(float)(g.lo[2] + ((double)k + 0.5) * g.step[2]);
+}
+
+// True if view `c` keeps the centre; then (px, py) is its pixel and `near` the pixel's bit in the view's packed mask.
+__device__ inline bool seed_pixel(const NvCam& c, double X, double Y, double Z, double wd, double hd,
+                                  const unsigned int* __restrict__ view_bits, int stride, unsigned int& px, unsigned int& py,
+                                  bool& near) {
+#pragma clang fp contract(off)
+    double pu, pv;
+    if (!nv_project_xyz(c, X, Y, Z, wd, hd, pu, pv)) return false;
+    // 0 <= pu < W and 0 <= pv < H: the pixel is inside the view, its word inside the view's plane
+    px = (unsigned int)floor(pu);
+    py = (unsigned int)floor(pv);
+    const unsigned int w = view_bits[(size_t)py * (size_t)stride + (size_t)(px >> 5)];
+    near = ((w >> (px & 31u)) & 1u) != 0u;
+    return true;
+}
+
 __global__ void __launch_bounds__(SEED_THREADS) k_voxel_votes(const SeedGrid g, int V, const double* __restrict__ intr,
                                                              const double* __restrict__ w2c, int height, int width,
                                                              int stride, const unsigned int* __restrict__ bits,
@@ -66,26 +105,19 @@ __global__ void __launch_bounds__(SEED_THREADS) k_voxel_votes(const SeedGrid g, 
     const long long n = (long long)g.nx * g.ny * g.nz;   // <= 2^31 - 1
     const long long id = (long long)blockIdx.x * SEED_THREADS + threadIdx.x;
     if (id >= n) return;
-    const int i = (int)(id % g.nx);
-    const long long r = id / g.nx;
-    const int j = (int)(r % g.ny), k = (int)(r / g.ny);
-    // the centre in float64, then the float32 point that the projection contract is written for
-    const double X = (double)(float)(g.lo[0] + ((double)i + 0.5) * g.step[0]);
-    const double Y = (double)(float)(g.lo[1] + ((double)j + 0.5) * g.step[1]);
-    const double Z = (double)(float)(g.lo[2] + ((double)k + 0.5) * g.step[2]);
+    double X, Y, Z;
+    seed_centre(g, id, X, Y, Z);
     const double wd = (double)width, hd = (double)height;
     const size_t plane = (size_t)height * (size_t)stride;
     int n_seen = 0, n_hit = 0;
     for (int v = 0; v < V; v++) {   // v is uniform: scalar loads of the camera
         NvCam c;
         nv_load_cam(c, intr, w2c, v);
-        double pu, pv;
-        if (!nv_project_xyz(c, X, Y, Z, wd, hd, pu, pv)) continue;
+        unsigned int px, py;
+        bool near;
+        if (!seed_pixel(c, X, Y, Z, wd, hd, bits + (size_t)v * plane, stride, px, py, near)) continue;
         n_seen++;
-        // 0 <= pu < W and 0 <= pv < H: the pixel is inside the view, its word inside the view's plane
-        const unsigned int px = (unsigned int)floor(pu), py = (unsigned int)floor(pv);
-        const unsigned int w = bits[(size_t)v * plane + (size_t)py * (size_t)stride + (size_t)(px >> 5)];
-        n_hit += (int)((w >> (px & 31u)) & 1u);
+        n_hit += (int)near;
     }
     if (accumulate) {
         n_seen += seen[id];
@@ -142,6 +174,73 @@ __global__ void __launch_bounds__(SEED_THREADS) k_voxel_moments(int nx, int ny, 
     }
 }
 
+__global__ void __launch_bounds__(SEED_THREADS) k_ray_claims(const SeedGrid g, int M, const int* __restrict__ index,
+                                                            const unsigned short* __restrict__ support, int V,
+                                                            const double* __restrict__ intr, const double* __restrict__ w2c,
+                                                            int height, int width, int stride,
+                                                            const unsigned int* __restrict__ bits, unsigned int* best) {
+#pragma clang fp contract(off)
+    const long long n = (long long)g.nx * g.ny * g.nz;   // <= 2^31 - 1
+    const long long m = (long long)blockIdx.x * SEED_THREADS + threadIdx.x;
+    if (m >= M) return;
+    const long long id = index[m];
+    if (id < 0 || id >= n) return;   // the caller's error: claims nothing
+    const unsigned int s = support[m];
+    double X, Y, Z;
+    seed_centre(g, id, X, Y, Z);
+    const double wd = (double)width, hd = (double)height;
+    const size_t plane = (size_t)height * (size_t)stride, image = (size_t)height * (size_t)width;
+    for (int v = 0; v < V; v++) {   // v is uniform: scalar loads of the camera
+        NvCam c;
+        nv_load_cam(c, intr, w2c, v);
+        unsigned int px, py;
+        bool near;
+        if (!seed_pixel(c, X, Y, Z, wd, hd, bits + (size_t)v * plane, stride, px, py, near) || !near) continue;
+        unsigned int* p = best + (size_t)v * image + (size_t)py * (size_t)width + (size_t)px;
+        // no look before the atomic: a plain load that skips it where best already holds as much measured slower
+        // (profiles/edge_seed_exclusive.md)
+        atomicMax(p, s);
+    }
+}
+
+__global__ void __launch_bounds__(SEED_THREADS) k_ray_wins(const SeedGrid g, int M, const int* __restrict__ index,
+                                                          const unsigned short* __restrict__ support, int V,
+                                                          const double* __restrict__ intr, const double* __restrict__ w2c,
+                                                          int height, int width, int stride,
+                                                          const unsigned int* __restrict__ bits,
+                                                          const unsigned int* __restrict__ best, int window, int margin,
+                                                          int accumulate, unsigned short* __restrict__ wins) {
+#pragma clang fp contract(off)
+    const long long n = (long long)g.nx * g.ny * g.nz;   // <= 2^31 - 1
+    const long long m = (long long)blockIdx.x * SEED_THREADS + threadIdx.x;
+    if (m >= M) return;
+    const long long id = index[m];
+    int n_wins = 0;
+    if (id >= 0 && id < n) {   // an index outside the grid is the caller's error: it wins nothing
+        const unsigned int s = (unsigned int)support[m] + (unsigned int)margin;   // <= 131070: 32 bits do not wrap
+        double X, Y, Z;
+        seed_centre(g, id, X, Y, Z);
+        const double wd = (double)width, hd = (double)height;
+        const size_t plane = (size_t)height * (size_t)stride, image = (size_t)height * (size_t)width;
+        for (int v = 0; v < V; v++) {   // v is uniform: scalar loads of the camera
+            NvCam c;
+            nv_load_cam(c, intr, w2c, v);
+            unsigned int px, py;
+            bool near;
+            if (!seed_pixel(c, X, Y, Z, wd, hd, bits + (size_t)v * plane, stride, px, py, near) || !near) continue;
+            const int x0 = max((int)px - window, 0), x1 = min((int)px + window, width - 1);
+            const int y0 = max((int)py - window, 0), y1 = min((int)py + window, height - 1);
+            const unsigned int* view = best + (size_t)v * image;
+            unsigned int top = 0;
+            for (int y = y0; y <= y1; y++)
+                for (int x = x0; x <= x1; x++) top = max(top, view[(size_t)y * (size_t)width + (size_t)x]);
+            n_wins += (int)(s >= top);
+        }
+    }
+    if (accumulate) n_wins += wins[m];
+    wins[m] = (unsigned short)n_wins;
+}
+
 void launch_pack_near_bits(hipStream_t s, int V, int height, int width, const int* dist2, int tol2, unsigned int* bits) {
     const int stride = (width + 31) / 32;
     const long long padded = (long long)height * stride * 32;
@@ -155,9 +254,7 @@ void launch_pack_near_bits(hipStream_t s, int V, int height, int width, const in
     }
 }
 
-void launch_voxel_votes(hipStream_t s, int nx, int ny, int nz, const double* lo, const double* step, int V,
-                        const double* intr, const double* w2c, int height, int width, const unsigned int* bits,
-                        int accumulate, unsigned short* seen, unsigned short* hit) {
+static SeedGrid seed_grid(int nx, int ny, int nz, const double* lo, const double* step) {
     SeedGrid g;
     for (int a = 0; a < 3; a++) {
         g.lo[a] = lo[a];
@@ -166,6 +263,13 @@ void launch_voxel_votes(hipStream_t s, int nx, int ny, int nz, const double* lo,
     g.nx = nx;
     g.ny = ny;
     g.nz = nz;
+    return g;
+}
+
+void launch_voxel_votes(hipStream_t s, int nx, int ny, int nz, const double* lo, const double* step, int V,
+                        const double* intr, const double* w2c, int height, int width, const unsigned int* bits,
+                        int accumulate, unsigned short* seen, unsigned short* hit) {
+    const SeedGrid g = seed_grid(nx, ny, nz, lo, step);
     const long long n = (long long)nx * ny * nz;
     const unsigned blocks = (unsigned)((n + SEED_THREADS - 1) / SEED_THREADS);   // <= 2^23
     ProfScope p("voxel_votes", s);
@@ -179,6 +283,31 @@ void launch_voxel_moments(hipStream_t s, int nx, int ny, int nz, const unsigned 
     ProfScope p("voxel_moments", s);
     hipLaunchKernelGGL(k_voxel_moments, dim3(blocks), dim3(SEED_THREADS), 0, s, nx, ny, nz, (nx + 31) / 32, keep, N, centres,
                        radius, moments);
+}
+
+hipError_t launch_ray_claims(hipStream_t s, int nx, int ny, int nz, const double* lo, const double* step, int M,
+                             const int* index, const unsigned short* support, int V, const double* intr, const double* w2c,
+                             int height, int width, const unsigned int* bits, int clear, unsigned int* best) {
+    if (clear && V > 0) {
+        const hipError_t e = hipMemsetAsync(best, 0, (size_t)V * (size_t)height * (size_t)width * sizeof(unsigned int), s);
+        if (e != hipSuccess) return e;
+    }
+    if (M == 0 || V == 0) return hipSuccess;
+    const unsigned blocks = (unsigned)(((long long)M + SEED_THREADS - 1) / SEED_THREADS);   // <= 2^23
+    ProfScope p("ray_claims", s);
+    hipLaunchKernelGGL(k_ray_claims, dim3(blocks), dim3(SEED_THREADS), 0, s, seed_grid(nx, ny, nz, lo, step), M, index,
+                       support, V, intr, w2c, height, width, (width + 31) / 32, bits, best);
+    return hipSuccess;
+}
+
+void launch_ray_wins(hipStream_t s, int nx, int ny, int nz, const double* lo, const double* step, int M, const int* index,
+                     const unsigned short* support, int V, const double* intr, const double* w2c, int height, int width,
+                     const unsigned int* bits, const unsigned int* best, int window, int margin, int accumulate,
+                     unsigned short* wins) {
+    const unsigned blocks = (unsigned)(((long long)M + SEED_THREADS - 1) / SEED_THREADS);   // <= 2^23
+    ProfScope p("ray_wins", s);
+    hipLaunchKernelGGL(k_ray_wins, dim3(blocks), dim3(SEED_THREADS), 0, s, seed_grid(nx, ny, nz, lo, step), M, index, support,
+                       V, intr, w2c, height, width, (width + 31) / 32, bits, best, window, margin, accumulate, wins);
 }
 
 }  // namespace cgs

@@ -222,5 +222,12 @@ void launch_voxel_votes(hipStream_t s, int nx, int ny, int nz, const double* lo,
                         int accumulate, unsigned short* seen, unsigned short* hit);
 void launch_voxel_moments(hipStream_t s, int nx, int ny, int nz, const unsigned int* keep, int N, const int* centres,
                           int radius, int* moments);
+hipError_t launch_ray_claims(hipStream_t s, int nx, int ny, int nz, const double* lo, const double* step, int M,
+                             const int* index, const unsigned short* support, int V, const double* intr, const double* w2c,
+                             int height, int width, const unsigned int* bits, int clear, unsigned int* best);
+void launch_ray_wins(hipStream_t s, int nx, int ny, int nz, const double* lo, const double* step, int M, const int* index,
+                     const unsigned short* support, int V, const double* intr, const double* w2c, int height, int width,
+                     const unsigned int* bits, const unsigned int* best, int window, int margin, int accumulate,
+                     unsigned short* wins);
 
 }  // namespace cgs

@@ -1,13 +1,15 @@
 """Seed points of a scan from its edge maps, without training: the multi-view voxel vote of ``ops.edge_seed`` as a tool.
 
     python -m curve_gaussian_amd.edge_seed_cli --scan DIR [--layout emap|colmap] [--backend gpu|host] [--directions]
-                                               --out seeds.ply
+                                               [--exclusive] --out seeds.ply
 
 The cameras and maps are those ``edge_extraction.reprojection`` scores against: ``emap_cameras`` (meta_data.json) or
 ``read_colmap`` (sparse/0; ``--undistort`` as there).  The box is ``--bounds``, or ``scene.default_seed_bounds``.  The seeds
 are written as the ASCII PLY of ``edge_points.ply``; the counts are printed.  ``--directions`` also seeds the curves'
-directions: they are written as the PLY's normals (zero for an undirected seed) and the directed count is printed.  The
-defaults are untuned and there is no occlusion reasoning (ops/edge_seed.py)."""
+directions: they are written as the PLY's normals (zero for an undirected seed) and the directed count is printed.
+``--exclusive`` keeps only the voted voxels that win the pixels they claim (``--excl_window``, ``--excl_margin``,
+``--excl_win_ratio``), which suppresses the ghosts of a scan with few views; the voxels that remain are printed.  The
+defaults are untuned and there is no occlusion reasoning, with or without ``--exclusive`` (ops/edge_seed.py)."""
 import argparse
 import sys
 
@@ -38,7 +40,20 @@ def parser():
     ap.add_argument("--dir_radius", type=int, default=SD.DIR_RADIUS)
     ap.add_argument("--dir_min_support", type=int, default=SD.DIR_MIN_SUPPORT)
     ap.add_argument("--dir_min_linearity", type=float, default=SD.DIR_MIN_LINEARITY)
+    ap.add_argument("--exclusive", action="store_true", help="keep only the voted voxels that win the pixels they claim")
+    ap.add_argument("--excl_window", type=int, default=SD.EXCL_WINDOW)
+    ap.add_argument("--excl_margin", type=int, default=SD.EXCL_MARGIN)
+    ap.add_argument("--excl_win_ratio", type=float, default=SD.EXCL_WIN_RATIO)
     return ap
+
+
+def seed_options(args):
+    """seed_points' keywords of a parsed command line."""
+    return dict(grid=args.grid, tol_px=args.tol_px, min_views=args.min_views, min_ratio=args.min_ratio, cell=args.cell,
+                max_seeds=args.max_seeds, edge_threshold=args.edge_threshold, directions=args.directions,
+                dir_radius=args.dir_radius, dir_min_support=args.dir_min_support, dir_min_linearity=args.dir_min_linearity,
+                exclusive=args.exclusive, excl_window=args.excl_window, excl_margin=args.excl_margin,
+                excl_win_ratio=args.excl_win_ratio)
 
 
 def seed_scan(scan_dir, layout="emap", detector="DexiNed", undistort=False, bounds=None, backend="gpu", **options):
@@ -65,15 +80,12 @@ def seed_scan(scan_dir, layout="emap", detector="DexiNed", undistort=False, boun
 def main(argv=None):
     args = parser().parse_args(argv)
     bounds = (args.bounds[:3], args.bounds[3:]) if args.bounds is not None else None
-    seeds, info = seed_scan(args.scan, args.layout, args.detector, args.undistort, bounds, args.backend, grid=args.grid,
-                            tol_px=args.tol_px, min_views=args.min_views, min_ratio=args.min_ratio, cell=args.cell,
-                            max_seeds=args.max_seeds, edge_threshold=args.edge_threshold, directions=args.directions,
-                            dir_radius=args.dir_radius, dir_min_support=args.dir_min_support,
-                            dir_min_linearity=args.dir_min_linearity)
+    seeds, info = seed_scan(args.scan, args.layout, args.detector, args.undistort, bounds, args.backend, **seed_options(args))
     IO.write_points_ply(args.out, seeds, info["directions"] if args.directions else None)
     print(f"views {info['views']}, grid {info['dims'][0]}x{info['dims'][1]}x{info['dims'][2]}, kept voxels "
           f"{info['kept_voxels']}, cells {info['cells']}, seeds {info['seeds']}{' (capped)' if info['capped'] else ''}, "
-          f"bounds {info['bounds']}" + (f", directed {info['directed']}" if args.directions else ""))
+          f"bounds {info['bounds']}" + (f", after the claims {info['exclusive_voxels']} voxels" if args.exclusive else "")
+          + (f", directed {info['directed']}" if args.directions else ""))
     print(f"Wrote {args.out}")
     return 0
 

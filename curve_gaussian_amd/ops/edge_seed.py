@@ -1,5 +1,6 @@
 """Seed points for the curves from a scan's own edge maps: a multi-view voxel vote (cgs_pack_near_bits / cgs_voxel_votes,
-include/curvegs.h; csrc/edge_seed.hip), and on request their directions from the vote's kept voxels (cgs_voxel_moments).
+include/curvegs.h; csrc/edge_seed.hip), on request a ray-exclusive refinement of its selection (cgs_ray_claims /
+cgs_ray_wins), and on request the seeds' directions from the kept voxels (cgs_voxel_moments).
 The reference has no counterpart: it seeds a fixed 15^3 grid or the SfM cloud, every curve along +-Y.
 
 Definitions (frozen), the same on both back ends bit for bit:
@@ -35,13 +36,35 @@ Directions (``directions=True``; frozen), the same on both back 
              directed iff m >= dir_min_support and linearity >= dir_min_linearity; an undirected seed (a junction, a
              blob, a lone voxel) gets the zero vector and its curve is laid along +-Y
 
-There is NO occlusion reasoning: a voxel behind a surface is seen by the views that look at it through the surface, and
-with few views the back-projections of unrelated edge pixels intersect in empty space ("ghosts"); min_views / min_ratio
-are the only defence.  The curve direction is not seeded unless ``directions=True``.  The defaults of ``seed_points``
-are untuned, those of the directions (DIR_RADIUS, DIR_MIN_SUPPORT, DIR_MIN_LINEARITY) included.
+Ray-exclusive claims (``exclusive=True``; frozen), the same on both back ends bit for bit:
+  list       ``index`` int32 [M]: the linear indices of the voxels that ``select_voxels`` kept, ascending (``np.nonzero`` on
+             the host for both back ends); an index outside [0, n) is a ValueError (the kernels read nothing for it and
+             give 0)
+  support    support[m] = (hit * 65535) // seen of that voxel, in int64 on the host for both back ends
+             (``voxel_support``): an integer in [1, 65535] for a voxel with a hit, uint16 [M]; 0 where seen = 0
+  claim      listed voxel m HITS in view v when the rule of the votes keeps its centre and finds its near bit set: the same
+             float32 centre, the same projection (c2 > 0, 0 <= u < W, 0 <= v < H), the bit at (floor(v), floor(u)).
+             best[v][y][x] = the largest support over the listed voxels that hit at pixel (x, y) of view v, 0 where there
+             is none; uint32 [V,H,W] (tensors hold the words as int32)
+  wins       wins[m] = the number of views in which m hits and support[m] + margin >= max(best[v]) over the window
+             |dx| <= w, |dy| <= w around m's pixel, clipped to the image; w = ``excl_window`` in [0, SEED_MAX_WINDOW],
+             margin = ``excl_margin``, an integer in [0, 65535]; the sum is formed in 32 bits; uint16 [M]
+  selection  voxel m stays iff wins[m] >= need_table(excl_win_ratio)[hit[m]]; the surviving mask is what the thinning,
+             the keep bits and the moments then see
+
+There is NO occlusion reasoning in the vote: a voxel behind a surface is seen by the views that look at it through the
+surface, and with few views the back-projections of unrelated edge pixels intersect in empty space ("ghosts");
+min_views / min_ratio are its only defence.  ``exclusive=True`` adds a winner-take-all pass without depth: a voxel stays
+only if, in enough of the views in which it hits, no listed voxel near the same ray is better supported.  That removes
+most ghosts of a scan with few views (each of their pixels is explained better by a true voxel) and thins a true tube to
+its best-supported ridge; it does NOT recover occlusion -- a voxel behind a surface still votes through it --, and a true
+edge that is weakly supported everywhere and runs next to a strong one in the images loses.  The curve direction is not
+seeded unless ``directions=True``.  The defaults of ``seed_points`` are untuned, those of the directions (DIR_RADIUS,
+DIR_MIN_SUPPORT, DIR_MIN_LINEARITY) and of the claims (EXCL_WINDOW, EXCL_MARGIN, EXCL_WIN_RATIO) included.
 
 Two back ends: ``"gpu"``, HIP, and ``"host"``, numpy -- the same rules, for a machine without a GPU and what the tests hold
-the kernels against.  Selection, thinning, the keep bits and the eigen-decomposition are numpy on both."""
+the kernels against.  Selection, thinning, the list and its support, the keep bits and the eigen-decomposition are numpy
+on both."""
 import ctypes as C
 
 import numpy as np
@@ -56,11 +79,16 @@ MAX_VIEWS = L.SEED_MAX_VIEWS
 MAX_VOXELS = 2 ** 31 - 1
 BYTE_BUDGET = 1 << 30     # bytes of masks, transforms, scratch and bits per chunk of views in seed_points
 BYTES_PER_PIXEL = 8       # uint8 mask, uint16 column pass, int32 transform, one bit (rounded up)
+EXCL_BYTES_PER_PIXEL = 4  # the second sweep of ``exclusive``: uint32 best (the near bits stay from the first sweep)
 HOST_SLAB = 1 << 18       # voxels per numpy slab of the host back end
 SEED_MAX_RADIUS = L.SEED_MAX_RADIUS
 MOMENT_VALUES = 10        # m, sum d [3], sum d^2 [3], sum dx dy, sum dx dz, sum dy dz
 # UNTUNED, like the other defaults of this module: no scan has been trained against them beyond the drawn test scan
 DIR_RADIUS, DIR_MIN_SUPPORT, DIR_MIN_LINEARITY = 6, 6, 0.5
+SEED_MAX_WINDOW = L.SEED_MAX_WINDOW
+MAX_SUPPORT = 65535
+# UNTUNED as well: one prototype run on the two drawn test scans, no real scan
+EXCL_WINDOW, EXCL_MARGIN, EXCL_WIN_RATIO = 1, 0, 0.5
 
 
 def _check_backend(backend):
@@ -131,7 +159,10 @@ def _grid(bounds, dims):
 
 
 def _centres(lo, dims, step, start, stop):
-    g = np.arange(start, stop, dtype=np.int64)
+    return _centres_of(lo, dims, step, np.arange(start, stop, dtype=np.int64))
+
+
+def _centres_of(lo, dims, step, g):
     ijk = np.stack([g % dims[0], (g // dims[0]) % dims[1], g // (dims[0] * dims[1])], 1).astype(np.float64)
     return (lo[None, :] + (ijk + 0.5) * step[None, :]).astype(np.float32)   # one rounded operation per ufunc: no FMA
 
@@ -266,6 +297,186 @@ def thin_to_seeds(keep, hit, bounds, dims, cell, max_seeds, return_centres=False
     return seeds, info
 
 
+# ------------------------------------------------------------------------------------------------ ray-exclusive claims
+def _list_index(name, index, n):
+    idx = index.detach().cpu().numpy() if torch.is_tensor(index) else np.asarray(index)
+    if idx.size == 0:
+        return np.zeros(0, np.int32)
+    if idx.ndim != 1 or idx.dtype.kind not in "iu":
+        raise ValueError(f"{name}: index must be an integer [M] list of linear voxel indices")
+    idx = idx.astype(np.int64)
+    if (idx < 0).any() or (idx >= n).any():
+        raise ValueError(f"{name}: an index lies outside [0, {n})")
+    return np.ascontiguousarray(idx.astype(np.int32))
+
+
+def voxel_support(seen, hit, index):
+    """uint16 [M] CPU tensor: support[m] = (hit * 65535) // seen of voxel index[m] in int64 (module docstring); 0 where
+    seen = 0.  seen, hit: the votes (uint16 [n] tensors or integer arrays); index: integer [M] inside [0, n).  Host code on
+    both back ends.  A hit above seen, counts of different shapes and an index outside the grid are ValueErrors."""
+    seen, hit = _counts_host(seen), _counts_host(hit)
+    if seen.shape != hit.shape:
+        raise ValueError("voxel_support: seen and hit differ in shape")
+    idx = _list_index("voxel_support", index, seen.size).astype(np.int64)
+    s, h = seen[idx], hit[idx]
+    if (h > s).any() or (h < 0).any():
+        raise ValueError("voxel_support: hit must lie in [0, seen]")
+    support = np.where(s > 0, (h * MAX_SUPPORT) // np.maximum(s, 1), 0)
+    return torch.from_numpy(support.astype(np.uint16))
+
+
+def _ray_args(name, bounds, dims, index, support, intrinsics, w2c, bits, height, width):
+    lo, _, dims, step = _grid(bounds, dims)
+    height, width = ES._check_size(name, height, width)
+    V, K, M = ES._cameras(intrinsics, w2c)
+    if V > MAX_VIEWS:
+        raise ValueError(f"{name}: at most {MAX_VIEWS} views (got {V})")
+    if not torch.is_tensor(bits):
+        bits = torch.from_numpy(np.ascontiguousarray(bits))
+    if bits.dtype != torch.int32 or tuple(bits.shape) != (V, height, bits_stride(width)):
+        raise ValueError(f"{name}: bits must be int32 [{V},{height},{bits_stride(width)}] (got {bits.dtype} "
+                         f"{tuple(bits.shape)})")
+    idx = _list_index(name, index, dims[0] * dims[1] * dims[2])
+    sup = support.detach().cpu().numpy() if torch.is_tensor(support) else np.asarray(support)
+    if sup.size == 0:
+        sup = np.zeros(0, np.uint16)
+    if sup.ndim != 1 or sup.dtype.kind not in "iu" or sup.shape != idx.shape:
+        raise ValueError(f"{name}: support must be an integer [{idx.size}] list, one value per listed voxel")
+    sup = sup.astype(np.int64)
+    if (sup < 0).any() or (sup > MAX_SUPPORT).any():
+        raise ValueError(f"{name}: a support lies outside [0, {MAX_SUPPORT}]")
+    return lo, dims, step, height, width, V, K, M, bits, idx, np.ascontiguousarray(sup.astype(np.uint16))
+
+
+def _hits_host(pts, K, M, words, H, W, v):
+    """(the positions among the centres ``pts`` that hit in view v, their px, their py): the rule of ``_votes_host``."""
+    pu, pv, keep = ES.project_points_host(pts, K[v:v + 1], M[v:v + 1], H, W)
+    at = np.nonzero(keep[0])[0]
+    px, py = np.floor(pu[0][at]).astype(np.int64), np.floor(pv[0][at]).astype(np.int64)
+    bit = (words[v, py, px >> 5] >> (px & 31).astype(np.uint32)) & np.uint32(1)
+    near = bit != 0
+    return at[near], px[near], py[near]
+
+
+def ray_claims(bounds, dims, index, support, intrinsics, w2c, bits, height, width, best=None, backend="gpu", device=None):
+    """best: int32 [V,height,width] tensor holding the uint32 claims of the module docstring (values <= 65535) over the
+    views of this call.  index: integer [M] linear indices inside the grid; support: integer [M] in [0, 65535]
+    (``voxel_support``); cameras and ``bits`` as for ``voxel_votes``.  ``best``: the claims of an earlier call over the
+    same views -- this list's claims are raised into it in place (a list claimed piece by piece) and it is returned;
+    without it the claims start from 0.  ``backend="gpu"``: ``cgs_ray_claims``, a device tensor; ``backend="host"``:
+    ``np.maximum.at``, a CPU tensor."""
+    _check_backend(backend)
+    lo, dims, step, height, width, V, K, M, bits, idx, sup = _ray_args("ray_claims", bounds, dims, index, support,
+                                                                       intrinsics, w2c, bits, height, width)
+    if best is not None and (not torch.is_tensor(best) or best.dtype != torch.int32
+                             or tuple(best.shape) != (V, height, width) or not best.is_contiguous()):
+        raise ValueError(f"ray_claims: best must be a contiguous int32 [{V},{height},{width}] tensor")
+    if backend == "host":
+        if best is None:
+            best = torch.zeros((V, height, width), dtype=torch.int32)
+        if best.is_cuda:
+            raise ValueError("ray_claims: backend='host' claims into a CPU tensor")
+        out, words = best.numpy(), bits.detach().cpu().numpy().view(np.uint32)
+        for s0 in range(0, idx.size, HOST_SLAB):
+            pts = _centres_of(lo, dims, step, idx[s0:s0 + HOST_SLAB].astype(np.int64))
+            for v in range(V):   # one view at a time: [slab] temporaries
+                at, px, py = _hits_host(pts, K, M, words, height, width, v)
+                np.maximum.at(out[v], (py, px), sup[s0 + at].astype(np.int32))
+        return best
+    dev = ES._device_for([bits] + ([best] if best is not None else []), "ray_claims", device)
+    with L.device_guard(dev):
+        clear = best is None
+        if clear:
+            best = torch.empty((V, height, width), dtype=torch.int32, device=dev)
+        elif best.device != dev:
+            raise ValueError(f"ray_claims: best must be on {dev}")
+        bits = bits.to(dev).contiguous()
+        Kd, Md = torch.from_numpy(K).to(dev), torch.from_numpy(M).to(dev)
+        idx_d, sup_d = torch.from_numpy(idx).to(dev), torch.from_numpy(sup).to(dev)
+        lo_c, step_c = (C.c_double * 3)(*lo), (C.c_double * 3)(*step)
+        rc = L.load().cgs_ray_claims(dims[0], dims[1], dims[2], C.cast(lo_c, C.c_void_p), C.cast(step_c, C.c_void_p),
+                                     idx.size, L.ptr(idx_d), L.ptr(sup_d), V, L.ptr(Kd), L.ptr(Md), height, width, L.ptr(bits),
+                                     1 if clear else 0, L.ptr(best), L.raw_stream(dev))
+        L.check(rc, "cgs_ray_claims")
+    return best
+
+
+def ray_wins(bounds, dims, index, support, intrinsics, w2c, bits, best, height, width, window=EXCL_WINDOW,
+             margin=EXCL_MARGIN, counts=None, backend="gpu", device=None):
+    """wins: uint16 [M] tensor, the wins of the module docstring over the views of this call.  ``best``: ``ray_claims`` of
+    ALL listed voxels over the same views, int32 [V,height,width]; ``window`` an integer in [0, SEED_MAX_WINDOW],
+    ``margin`` an integer in [0, 65535].  ``counts``: the wins of an earlier call over the same list -- this call's are
+    added to it in place and it is returned (the views of all accumulating calls number at most 65535).
+    ``backend="gpu"``: ``cgs_ray_wins``, a device tensor; ``backend="host"``: numpy, a CPU tensor."""
+    _check_backend(backend)
+    lo, dims, step, height, width, V, K, M, bits, idx, sup = _ray_args("ray_wins", bounds, dims, index, support, intrinsics,
+                                                                       w2c, bits, height, width)
+    if int(window) != window or not (0 <= int(window) <= SEED_MAX_WINDOW):
+        raise ValueError(f"ray_wins: the window must be an integer in [0, {SEED_MAX_WINDOW}] (got {window})")
+    if int(margin) != margin or not (0 <= int(margin) <= MAX_SUPPORT):
+        raise ValueError(f"ray_wins: the margin must be an integer in [0, {MAX_SUPPORT}] (got {margin})")
+    window, margin = int(window), int(margin)
+    if not torch.is_tensor(best):
+        best = torch.from_numpy(np.ascontiguousarray(best))
+    if best.dtype != torch.int32 or tuple(best.shape) != (V, height, width):
+        raise ValueError(f"ray_wins: best must be int32 [{V},{height},{width}] (got {best.dtype} {tuple(best.shape)})")
+    if counts is not None and (not torch.is_tensor(counts) or counts.dtype != torch.uint16
+                               or tuple(counts.shape) != (idx.size,) or not counts.is_contiguous()):
+        raise ValueError(f"ray_wins: counts must be a contiguous uint16 [{idx.size}] tensor")
+    if backend == "host":
+        wins = counts if counts is not None else torch.zeros(idx.size, dtype=torch.uint16)
+        if wins.is_cuda:
+            raise ValueError("ray_wins: backend='host' accumulates into a CPU tensor")
+        out, words = wins.numpy(), bits.detach().cpu().numpy().view(np.uint32)
+        claims = best.detach().cpu().numpy().view(np.uint32)
+        for s0 in range(0, idx.size, HOST_SLAB):
+            pts = _centres_of(lo, dims, step, idx[s0:s0 + HOST_SLAB].astype(np.int64))
+            for v in range(V):   # one view at a time: [slab] temporaries
+                at, px, py = _hits_host(pts, K, M, words, height, width, v)
+                x0, x1 = np.maximum(px - window, 0), np.minimum(px + window, width - 1)
+                y0, y1 = np.maximum(py - window, 0), np.minimum(py + window, height - 1)
+                top = np.zeros(at.size, np.int64)
+                for dy in range(-window, window + 1):       # the shifted maximum of the clipped window
+                    for dx in range(-window, window + 1):
+                        top = np.maximum(top, claims[v, np.clip(py + dy, y0, y1), np.clip(px + dx, x0, x1)])
+                out[s0 + at] += (sup[s0 + at].astype(np.int64) + margin >= top).astype(np.uint16)
+        return wins
+    dev = ES._device_for([bits, best] + ([counts] if counts is not None else []), "ray_wins", device)
+    with L.device_guard(dev):
+        if counts is not None:
+            wins = counts
+            if wins.device != dev:
+                raise ValueError(f"ray_wins: counts must be on {dev}")
+        elif V == 0:   # no view: the call is a no-op and nothing is won
+            wins = torch.zeros(idx.size, dtype=torch.uint16, device=dev)
+        else:
+            wins = torch.empty(idx.size, dtype=torch.uint16, device=dev)
+        bits, best = bits.to(dev).contiguous(), best.to(dev).contiguous()
+        Kd, Md = torch.from_numpy(K).to(dev), torch.from_numpy(M).to(dev)
+        idx_d, sup_d = torch.from_numpy(idx).to(dev), torch.from_numpy(sup).to(dev)
+        lo_c, step_c = (C.c_double * 3)(*lo), (C.c_double * 3)(*step)
+        rc = L.load().cgs_ray_wins(dims[0], dims[1], dims[2], C.cast(lo_c, C.c_void_p), C.cast(step_c, C.c_void_p), idx.size,
+                                   L.ptr(idx_d), L.ptr(sup_d), V, L.ptr(Kd), L.ptr(Md), height, width, L.ptr(bits),
+                                   L.ptr(best), window, margin, 1 if counts is not None else 0, L.ptr(wins),
+                                   L.raw_stream(dev))
+        L.check(rc, "cgs_ray_wins")
+    return wins
+
+
+def select_exclusive(wins, hit, win_ratio):
+    """bool [M] (numpy): wins >= need[hit] -- an integer comparison against ``need_table(win_ratio)``.  wins, hit: one value
+    per listed voxel (hit = the vote's hit of that voxel)."""
+    wins, hit = _counts_host(wins), _counts_host(hit)
+    if wins.shape != hit.shape:
+        raise ValueError("select_exclusive: wins and hit differ in shape")
+    if (wins < 0).any() or (hit < 0).any():
+        raise ValueError("select_exclusive: wins and hit must not be negative")
+    if not (0.0 <= float(win_ratio) <= 1.0):
+        raise ValueError(f"select_exclusive: win_ratio must lie in [0, 1] (got {win_ratio})")
+    need = need_table(win_ratio, int(hit.max()) if hit.size else 0)
+    return wins >= need[hit]
+
+
 # ------------------------------------------------------------------------------------------------ directions
 def keep_bits(keep, dims):
     """The selection mask ``keep`` (bool [nx ny nz], x fastest, as ``select_voxels`` returns it) packed into the keep bits
@@ -394,7 +605,8 @@ def grid_dims(bounds, grid):
 def seed_points(cameras, edge_maps_u8, detector, bounds, grid=128, tol_px=2, min_views=3, min_ratio=0.8, cell=4,
                 max_seeds=20000, edge_threshold=EDGE_MAX_THRESHOLD, backend="gpu", device=None, budget_bytes=None,
                 directions=False, dir_radius=DIR_RADIUS, dir_min_support=DIR_MIN_SUPPORT,
-                dir_min_linearity=DIR_MIN_LINEARITY):
+                dir_min_linearity=DIR_MIN_LINEARITY, exclusive=False, excl_window=EXCL_WINDOW, excl_margin=EXCL_MARGIN,
+                excl_win_ratio=EXCL_WIN_RATIO):
     """cameras: ``NovelViewCamera`` s; edge_maps_u8: one uint8 [H,W] map per camera (a list or an [V,H,W] array), the
     stored bytes of the detector's maps, as ``score_edges`` takes them.  bounds = (lo, hi) of the box to search.
 
@@ -405,13 +617,23 @@ def seed_points(cameras, edge_maps_u8, detector, bounds, grid=128, tol_px=2, min
     at a time; the votes accumulate across the chunks, so the result does not depend on the chunking.
 
     Returns (seeds float64 [N,3], info) with info = {"dims", "voxels", "views", "kept_voxels", "cells", "seeds", "capped",
-    "backend"}.  THE DEFAULTS ARE UNTUNED (no scan has been measured against them), there is no occlusion reasoning, and
-    the curve direction is not seeded unless ``directions=True``.  ``backend``: "gpu" (HIP; ``device``) or "host" (numpy).
+    "backend"}.  THE DEFAULTS ARE UNTUNED (no scan has been measured against them), the vote has no occlusion reasoning
+    (``exclusive=True`` suppresses ghosts without depth, see below), and the curve direction is not seeded unless
+    ``directions=True``.  ``backend``: "gpu" (HIP; ``device``) or "host" (numpy).
 
     ``directions=True``: the kept voxels within ``dir_radius`` voxels of every seed's centre voxel give its direction
     (``keep_bits``, ``voxel_moments`` on ``backend``, ``seed_directions(dir_min_support, dir_min_linearity)``; module
     docstring); info additionally holds "directions" (float64 [N,3]: unit rows, zero rows for undirected seeds) and
-    "directed" (their count).  These three defaults are untuned too."""
+    "directed" (their count).  These three defaults are untuned too.
+
+    ``exclusive=True``: between the selection and the thinning the kept voxels claim the pixels they hit and only those
+    that win their claims stay (``voxel_support``, ``ray_claims``, ``ray_wins(excl_window, excl_margin)``,
+    ``select_exclusive(excl_win_ratio)``; module docstring).  A second sweep over the views does it chunk by chunk: the
+    packed near bits of the first sweep stay where they were made (one bit per pixel), ``best`` costs
+    EXCL_BYTES_PER_PIXEL bytes per pixel of ``budget_bytes``, and the wins accumulate across the chunks, so the result
+    does not depend on the chunking.  The thinning, the keep bits and the moments see the surviving mask; info
+    additionally holds "exclusive_voxels", the voxels that remain ("kept_voxels" keeps its meaning).  These three
+    defaults are untuned too; there is still no depth."""
     from ..edge_extraction.novel_view import camera_arrays
     from ..edge_extraction.reprojection import detected_lut
     _check_backend(backend)
@@ -429,6 +651,13 @@ def seed_points(cameras, edge_maps_u8, detector, bounds, grid=128, tol_px=2, min
     ES.tolerances_squared([tol_px])
     if directions and (int(dir_radius) != dir_radius or not (1 <= int(dir_radius) <= SEED_MAX_RADIUS)):
         raise ValueError(f"seed_points: dir_radius must be an integer in [1, {SEED_MAX_RADIUS}] (got {dir_radius})")
+    if exclusive:
+        if int(excl_window) != excl_window or not (0 <= int(excl_window) <= SEED_MAX_WINDOW):
+            raise ValueError(f"seed_points: excl_window must be an integer in [0, {SEED_MAX_WINDOW}] (got {excl_window})")
+        if int(excl_margin) != excl_margin or not (0 <= int(excl_margin) <= MAX_SUPPORT):
+            raise ValueError(f"seed_points: excl_margin must be an integer in [0, {MAX_SUPPORT}] (got {excl_margin})")
+        if not (0.0 <= float(excl_win_ratio) <= 1.0):
+            raise ValueError(f"seed_points: excl_win_ratio must lie in [0, 1] (got {excl_win_ratio})")
     dims = grid_dims(bounds, grid)
     _grid(bounds, dims)
     need_table(min_ratio, 0)
@@ -441,7 +670,7 @@ def seed_points(cameras, edge_maps_u8, detector, bounds, grid=128, tol_px=2, min
     by_size = {}
     for v, c in enumerate(cameras):
         by_size.setdefault((c.height, c.width), []).append(v)
-    counts = None
+    counts, chunks = None, []   # chunks: (H, W, intrinsics, w2c, near bits) of the first sweep, for the second
     for (H, W), idx in by_size.items():
         per = max(1, budget // (BYTES_PER_PIXEL * H * W))
         for b in range(0, len(idx), per):
@@ -452,13 +681,35 @@ def seed_points(cameras, edge_maps_u8, detector, bounds, grid=128, tol_px=2, min
             bits = near_bits(d2, tol_px, backend=backend, device=device)
             del d2
             counts = voxel_votes(bounds, dims, intr, w2c, bits, H, W, counts=counts, backend=backend, device=device)
+            if exclusive:
+                chunks.append((H, W, intr, w2c, bits))
     if counts is None:   # no view: nothing is seen
         counts = (torch.zeros(n, dtype=torch.uint16), torch.zeros(n, dtype=torch.uint16))
     seen, hit = (c.cpu().numpy() for c in counts)
     keep = select_voxels(seen, hit, min_views, min_ratio)
+    kept_voxels = int(np.count_nonzero(keep))
+    if exclusive:   # the second sweep: the kept voxels claim their pixels, chunk of views by chunk of views
+        index = np.nonzero(keep)[0].astype(np.int32)
+        support = voxel_support(seen, hit, index)
+        wins = None
+        for H, W, intr, w2c, bits in chunks:
+            per = max(1, budget // (EXCL_BYTES_PER_PIXEL * H * W))
+            for b in range(0, bits.shape[0], per):
+                args = (bounds, dims, index, support, intr[b:b + per], w2c[b:b + per], bits[b:b + per])
+                best = ray_claims(*args, H, W, backend=backend, device=device)
+                wins = ray_wins(*args, best, H, W, window=excl_window, margin=excl_margin, counts=wins, backend=backend,
+                                device=device)
+                del best
+        del chunks
+        if wins is None:   # no view
+            wins = torch.zeros(index.size, dtype=torch.uint16)
+        keep = np.zeros(n, bool)
+        keep[index[select_exclusive(wins, hit[index], excl_win_ratio)]] = True
     seeds, thin = thin_to_seeds(keep, hit, bounds, dims, cell, max_seeds, return_centres=bool(directions))
-    info = {"dims": dims, "voxels": n, "views": len(cameras), "kept_voxels": int(np.count_nonzero(keep)),
+    info = {"dims": dims, "voxels": n, "views": len(cameras), "kept_voxels": kept_voxels,
             "cells": thin["cells"], "seeds": int(seeds.shape[0]), "capped": thin["capped"], "backend": backend}
+    if exclusive:
+        info["exclusive_voxels"] = int(np.count_nonzero(keep))
     if directions:
         moments = voxel_moments(keep_bits(keep, dims), dims, thin["centre_voxel"], dir_radius, backend=backend, device=device)
         vectors, directed, _ = seed_directions(moments, dir_min_support, dir_min_linearity)

@@ -498,7 +498,9 @@ class Scene:
     ``bounds`` = (lo, hi) (default: dataset_io.default_seed_bounds -- the reference's box for EMAP, the trimmed extent of
     the SfM cloud for COLMAP); the vote runs on the GPU when `device` is one, on the host otherwise, unless ``backend``
     says so.  With ``"directions": True`` among them the vote also seeds the curves' directions: the cloud's normals hold
-    them and are handed to ``create_from_pcd``.  No seed, or an unknown ``init``, is a ValueError: there is no fallback."""
+    them and are handed to ``create_from_pcd``.  With ``"exclusive": True`` only the voted voxels that win the pixels they
+    claim give seeds (fewer ghosts from few views; still no depth).  No seed, or an unknown ``init``, is a ValueError:
+    there is no fallback."""
 
     def __init__(self, source_path, gaussians, detector="DexiNed", num_pts_per_axis=15, cameras_extent=None, rng=None,
                  device=None, eval=False, llffhold=8, images=None, resolution=-1, undistort=False, init="reference",

@@ -3,7 +3,7 @@
 
     python -m curve_gaussian_amd.train -s SCAN -m OUT [--iterations N] [--backend graphed|direct|autograd|torch]
                                        [--draw_snapshots] [--topology_backend host|gpu] [--report_dir DIR] [--undistort]
-                                       [--init reference|edge_votes] [--init_directions]
+                                       [--init reference|edge_votes] [--init_directions] [--init_exclusive]
 
 The loop keeps the reference's order.  Per iteration: learning rate, SH degree every 1000 iterations, a random view without
 replacement, render + losses + every regulariser + backward (one ``TrainStep`` call), densification statistics before
@@ -320,7 +320,8 @@ def build_parser():
                         "SIMPLE_RADIAL, RADIAL and FULL_OPENCV cameras too); without it distortion is ignored, as in the reference")
     p.add_argument("--init", choices=("reference", "edge_votes"), default="reference",
                    help="the seed of the curves: the reference's (the 15^3 grid, or the SfM cloud of a COLMAP scan) or a "
-                        "multi-view voxel vote of the training views' edge maps (untuned defaults; no occlusion reasoning)")
+                        "multi-view voxel vote of the training views' edge maps (untuned defaults; no occlusion reasoning, "
+                        "see --init_exclusive)")
     p.add_argument("--init_grid", type=int, default=None, help="edge_votes: voxels along the longest side of the box")
     p.add_argument("--init_tol_px", type=float, default=None, help="edge_votes: pixel distance to a detected edge that votes")
     p.add_argument("--init_min_views", type=int, default=None, help="edge_votes: views that must see a voxel")
@@ -334,6 +335,15 @@ def build_parser():
                    help="edge_votes: kept voxels a seed needs around it to be given a direction")
     p.add_argument("--init_dir_min_linearity", type=float, default=None,
                    help="edge_votes: (l2 - l1) / l2 of the voxels' scatter a seed needs to be given a direction")
+    p.add_argument("--init_exclusive", action="store_true",
+                   help="edge_votes: keep only the voted voxels that win the pixels they claim -- suppresses the ghosts of a "
+                        "scan with few views (untuned defaults; still no depth)")
+    p.add_argument("--init_excl_window", type=int, default=None,
+                   help="edge_votes: pixels around a voxel's pixel in which a better supported voxel beats it")
+    p.add_argument("--init_excl_margin", type=int, default=None,
+                   help="edge_votes: support (of 65535) by which a voxel may fall short of the best claim and still win")
+    p.add_argument("--init_excl_win_ratio", type=float, default=None,
+                   help="edge_votes: share of the views a voxel hits in that it must win")
     p.add_argument("--init_bounds", nargs=6, type=float, default=None, metavar=("X0", "Y0", "Z0", "X1", "Y1", "Z1"),
                    help="edge_votes: the box to search (default: the reference's box, or the trimmed extent of the SfM cloud)")
     p.add_argument("--iterations", type=int, default=None)
@@ -369,9 +379,13 @@ def parse_args(argv):
     init_options = {k: v for k, v in (("grid", args.init_grid), ("tol_px", args.init_tol_px), ("min_views", args.init_min_views),
                                       ("min_ratio", args.init_min_ratio), ("cell", args.init_cell),
                                       ("dir_radius", args.init_dir_radius), ("dir_min_support", args.init_dir_min_support),
-                                      ("dir_min_linearity", args.init_dir_min_linearity)) if v is not None}
+                                      ("dir_min_linearity", args.init_dir_min_linearity),
+                                      ("excl_window", args.init_excl_window), ("excl_margin", args.init_excl_margin),
+                                      ("excl_win_ratio", args.init_excl_win_ratio)) if v is not None}
     if args.init_directions:
         init_options["directions"] = True
+    if args.init_exclusive:
+        init_options["exclusive"] = True
     if args.init_bounds is not None:
         init_options["bounds"] = (args.init_bounds[:3], args.init_bounds[3:])
     dataset = ModelParams(source_path, args.model_path, args.sh_degree, args.n_gaussians, args.detector, args.resolution,

@@ -881,8 +881,9 @@ int cgs_edge_score_reduce(int V, int height, int width, const uint8_t* pred_mask
  * Multi-view voxel vote: a seed for the curves from the scan's own edge maps.  Every voxel centre of a regular grid is
  * projected into every view; a voxel records in how many views it lies inside the image and in how many of those it lands
  * within a tolerance of a detected edge pixel.  The reference has no counterpart (it seeds a fixed 15^3 grid, or the SfM
- * cloud).  There is no occlusion reasoning.  Both entry points: caller's stream, no allocation, no host synchronisation,
- * no atomics, results independent of the launch geometry.
+ * cloud).  There is no occlusion reasoning in the vote (cgs_ray_claims / cgs_ray_wins below refine its selection without
+ * depth).  Both entry points: caller's stream, no allocation, no host synchronisation, no atomics, results independent of
+ * the launch geometry.
  *
  * Grid: lo, step (host, float64 [3]; step = (hi - lo) / dims, formed by the caller) and dims (nx, ny, nz), each >= 1.
  * Voxel (i, j, k) has the linear index (k ny + j) nx + i (x fastest) and the centre lo + (i + 0.5) step per axis, computed
@@ -931,6 +932,44 @@ int cgs_voxel_votes(int nx, int ny, int nz, const double* lo /*host, [3]*/, cons
 int cgs_voxel_moments(int nx, int ny, int nz, const void* keep_bits /*[nz,ny,ceil(nx/32)] uint32*/, int N,
                       const void* centres /*int32 [N,3], inside the grid*/, int radius, void* moments /*int32 [N,10]*/,
                       void* stream);
+
+/* cgs_ray_claims / cgs_ray_wins: a ray-exclusive refinement of the vote's selection (winner take all, no depth).  The
+ * voxels that the selection kept are LISTED: index is int32 [M], device, their linear indices (ascending when the caller
+ * is ops/edge_seed.py; the kernels do not need an order), and support is uint16 [M], device,
+ * support[m] = (hit * 65535) / seen of that voxel in integers, formed by the caller.  Grid, cameras, sizes and bits as for
+ * cgs_voxel_votes.  Listed voxel m HITS in view v when the rule of cgs_voxel_votes keeps its centre and finds its near bit
+ * set: the same float32 centre, the same projection (c2 > 0, 0 <= u < width, 0 <= v < height), the bit at
+ * (floor(v), floor(u)) -- the same device functions, so a vote and a claim cannot land on different pixels.
+ *
+ * cgs_ray_claims: best[v][y][x] (uint32 [V,height,width], device) becomes the maximum of what it held and of support[m]
+ * over the listed voxels that hit at pixel (x, y) of view v, by an integer atomic maximum: the result does not depend on
+ * the order or on the launch geometry.  clear != 0 first zeroes best (an asynchronous memset on the caller's stream), so
+ * best is 0 where no voxel hits; clear == 0 claims into what best holds (a list claimed piece by piece).
+ *
+ * cgs_ray_wins: wins[m] (uint16 [M], device) = the number of views in which m hits and
+ * support[m] + margin >= max(best[v][y][x] over |x - px| <= window, |y - py| <= window clipped to the image), (px, py)
+ * being m's pixel; the sum is formed in 32 bits.  At most (2 window + 1)^2 plain loads per hit; no atomics.
+ * accumulate == 0 stores the count (every listed voxel's word is written), accumulate != 0 adds it to what wins[m] holds
+ * (a plain read-add-store of the thread's own word), so a scan is refined chunk of views by chunk of views; the caller keeps
+ * the views of the accumulating calls at or below CGS_SEED_MAX_VIEWS.  best must hold the claims of ALL listed voxels for
+ * the views of the call.
+ *
+ * Both: one thread per listed voxel, the caller's stream, no allocation, no host synchronisation.  An index outside
+ * [0, nx ny nz) is the caller's error: the kernels read nothing for it, it claims nothing and its wins are 0.  M = 0 or
+ * V = 0 is a no-op apart from the requested clear (pointers that the call does not touch may then be NULL).  M < 0, V
+ * outside [0, CGS_SEED_MAX_VIEWS], a window outside [0, CGS_SEED_MAX_WINDOW], a margin outside [0, 65535], a non-positive
+ * dim, more than 2^31 - 1 voxels, a size outside [1, CGS_EDT_MAX_SIZE], a non-finite lo, a non-finite or non-positive step
+ * and NULL pointers are CGS_ERR_INVALID_ARGUMENT, rejected before anything is launched or cleared. */
+#define CGS_SEED_MAX_WINDOW 4
+int cgs_ray_claims(int nx, int ny, int nz, const double* lo /*host, [3]*/, const double* step /*host, [3]*/, int M,
+                   const int32_t* index /*[M]*/, const uint16_t* support /*[M]*/, int V, const double* intr /*[V,4]*/,
+                   const double* w2c /*[V,12]*/, int height, int width, const uint32_t* bits /*[V,height,ceil(width/32)]*/,
+                   int clear, uint32_t* best /*[V,height,width]*/, void* stream);
+int cgs_ray_wins(int nx, int ny, int nz, const double* lo /*host, [3]*/, const double* step /*host, [3]*/, int M,
+                 const int32_t* index /*[M]*/, const uint16_t* support /*[M]*/, int V, const double* intr /*[V,4]*/,
+                 const double* w2c /*[V,12]*/, int height, int width, const uint32_t* bits /*[V,height,ceil(width/32)]*/,
+                 const uint32_t* best /*[V,height,width]*/, int window, int margin, int accumulate, uint16_t* wins /*[M]*/,
+                 void* stream);
 
 #ifdef __cplusplus
 }
