@@ -116,6 +116,7 @@ SIGNATURES = {
     "cgs_voxel_moments": (_i, [_i, _i, _i, _vp, _i, _vp, _i, _vp, _vp]),
     "cgs_ray_claims": (_i, [_i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _i, _vp, _vp]),
     "cgs_ray_wins": (_i, [_i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp]),
+    "cgs_edge_support": (_i, [_i, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp]),
 }
 
 
@@ -159,6 +160,7 @@ EDGE_SCORE_MAX_TOL = 8   # CGS_EDGE_SCORE_MAX_TOL
 SEED_MAX_VIEWS = 65535   # CGS_SEED_MAX_VIEWS
 SEED_MAX_RADIUS = 15   # CGS_SEED_MAX_RADIUS
 SEED_MAX_WINDOW = 4   # CGS_SEED_MAX_WINDOW
+EDGE_SUPPORT_MAX_TOL = 4   # CGS_EDGE_SUPPORT_MAX_TOL
 REPORT_PANELS = ("render", "ground_truth", "depth", "rend_dir", "rend_alpha")   # panel order of cgs_report_panels
 
 _lib = None

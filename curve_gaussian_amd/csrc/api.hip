@@ -1993,4 +1993,27 @@ int cgs_ray_wins(int nx, int ny, int nz, const double* lo, const double* step, i
     return CGS_OK;
 }
 
+int cgs_edge_support(int E, int P, const float* points, const int32_t* offsets, int V, const double* intr,
+                     const double* w2c, int height, int width, const int32_t* d2, int T, const int32_t* tol2,
+                     int32_t* counts, void* stream_) {
+    if (E < 0 || P < 0 || V < 0 || T < 1 || T > CGS_EDGE_SUPPORT_MAX_TOL) {
+        set_error("cgs_edge_support: invalid argument (E=%d, P=%d, V=%d, T=%d; T lies in [1, %d])", E, P, V, T,
+                  CGS_EDGE_SUPPORT_MAX_TOL);
+        return CGS_ERR_INVALID_ARGUMENT;
+    }
+    if (E == 0 || V == 0) return CGS_OK;
+    if (!edt_size_ok(height, width)) {   // d2 is a cgs_edt_squared transform
+        set_error("cgs_edge_support: invalid argument (height=%d, width=%d; sizes lie in [1, %d])", height, width,
+                  CGS_EDT_MAX_SIZE);
+        return CGS_ERR_INVALID_ARGUMENT;
+    }
+    if (!offsets || !intr || !w2c || !d2 || !tol2 || !counts || (P > 0 && !points)) {
+        set_error("cgs_edge_support: invalid argument (NULL pointer)");
+        return CGS_ERR_INVALID_ARGUMENT;
+    }
+    launch_edge_support((hipStream_t)stream_, E, P, points, offsets, V, intr, w2c, height, width, d2, T, tol2, counts);
+    if (!check_launch("edge_support", false, (hipStream_t)stream_)) return CGS_ERR_HIP;
+    return CGS_OK;
+}
+
 }  // extern "C"

@@ -230,4 +230,8 @@ void launch_ray_wins(hipStream_t s, int nx, int ny, int nz, const double* lo, co
                      const unsigned int* bits, const unsigned int* best, int window, int margin, int accumulate,
                      unsigned short* wins);
 
+// edge_support.hip
+void launch_edge_support(hipStream_t s, int E, int P, const float* points, const int* offsets, int V, const double* intr,
+                         const double* w2c, int height, int width, const int* d2, int T, const int* tol2, int* counts);
+
 }  // namespace cgs

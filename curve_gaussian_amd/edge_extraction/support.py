@@ -1,0 +1,156 @@
+"""Per-edge 2D support of the extracted edges: every edge of ``parametric_edges.json`` sampled along its length, projected
+into every camera of a scan and compared with that camera's detected edge pixels (``ops.edge_support``; its docstring
+freezes the verdict).  Unlike the reference's visibility check, which looks at a curve's four control points or a line's
+two end points, this says WHICH edge the images do not show along its length; unlike the reprojection score it is one
+record per edge.  The reference has no counterpart.
+
+KNOWN LIMITS: there is no depth -- an edge hidden behind a surface in most views loses its support there, which is why the
+rule counts supporting frames and does not pool; a thick detector response inflates support; THE DEFAULTS ARE UNTUNED.
+
+``python -m curve_gaussian_amd.edge_extraction.support --base_dir <predictions> --dataset_dir <scans>`` checks every scan,
+writes ``<base_dir>/<scan>/edge_support.json`` -- one record per edge -- and, with ``--write_filtered``,
+``parametric_edges_supported.json`` with the kept edges.  ``parametric_edges.json`` is never written."""
+import argparse
+import json
+import logging
+import os
+import sys
+
+import numpy as np
+
+from ..ops import edge_support as SP
+from .para_edge import EDGE_MAX_THRESHOLD, EDGE_VISIBILITY_FRAMES_RATIO
+from .reprojection import (LAYOUTS, SAMPLE_RESOLUTION, _json_number, colmap_scan_cameras, dataset_scans, emap_cameras,
+                           scene_cameras, write_score)
+
+log = logging.getLogger(__name__)
+
+SUPPORT_FILE = "edge_support.json"
+FILTERED_FILE = "parametric_edges_supported.json"
+
+
+def filter_edge_dict(edge_dict, kept):
+    """The edges of ``edge_dict`` whose entry of ``kept`` (bool [Nc + Nl], curves first, then lines) is set, as a new dict of
+    lists in the layout of ``get_parametric_edge``: curves [n,4,3], lines [n,6]."""
+    curves = np.asarray(edge_dict["curves_ctl_pts"], np.float64).reshape(-1, 4, 3)
+    lines = np.asarray(edge_dict["lines_end_pts"], np.float64).reshape(-1, 6)
+    kept = np.asarray(kept).reshape(-1)
+    if kept.dtype != bool or kept.size != len(curves) + len(lines):
+        raise ValueError(f"filter_edge_dict: kept must be bool [{len(curves) + len(lines)}] (got {kept.dtype} {kept.shape})")
+    return {"curves_ctl_pts": curves[kept[:len(curves)]].tolist(), "lines_end_pts": lines[kept[len(curves):]].tolist()}
+
+
+def edge_records(result):
+    """One record per edge of an ``edge_support`` result: kind ("curve" / "line"), index within its kind, samples, seeing
+    views, supporting views and pooled share per tolerance (NaN as None), kept."""
+    nc = result["curves"]
+    rows = []
+    for e in range(len(result["n_points"])):
+        rows.append({"kind": "curve" if e < nc else "line", "index": int(e if e < nc else e - nc),
+                     "samples": int(result["n_points"][e]), "seeing_views": int(result["seeing_views"][e]),
+                     "supporting_views": [int(s) for s in result["supporting_views"][e]],
+                     "share": [_json_number(s) for s in result["share"][e]], "kept": bool(result["kept"][e])})
+    return rows
+
+
+def write_support(model_dir, edge_dict, result, write_filtered=False, extra=None):
+    """``<model_dir>/edge_support.json`` = {"edges": edge_records, "kept", "total", "settings", **extra} and, with
+    ``write_filtered``, ``<model_dir>/parametric_edges_supported.json``.  Returns the dict written."""
+    out = {**(extra or {}), "edges": edge_records(result), "kept": int(np.count_nonzero(result["kept"])),
+           "total": int(len(result["kept"])), "settings": dict(result["settings"])}
+    write_score(os.path.join(model_dir, SUPPORT_FILE), out)
+    if write_filtered:
+        with open(os.path.join(model_dir, FILTERED_FILE), "w") as f:
+            json.dump(filter_edge_dict(edge_dict, result["kept"]), f)
+    return out
+
+
+def score_scan(base_dir, dataset_dir, scan, layout="emap", detector="DexiNed", undistort=False, write_filtered=False,
+               device=None, backend="gpu", resolution=-1, **options):
+    """Checks ``<base_dir>/<scan>/parametric_edges.json`` against the ``detector`` edge maps of ``<dataset_dir>/<scan>`` and
+    writes ``<base_dir>/<scan>/edge_support.json`` (``write_support``).  ``layout``, ``undistort`` and ``resolution`` (of the
+    images) as ``reprojection.score_scan``, the same camera loaders; ``options`` go to ``ops.edge_support.edge_support``
+    (sampling ``resolution`` as ``sample_resolution``).  Returns the dict written, or None -- after reporting it -- for a
+    scan without a prediction."""
+    SP._check_backend(backend)
+    if layout not in LAYOUTS:
+        raise ValueError(f"unknown layout {layout!r}: expected one of {LAYOUTS}")
+    path = os.path.join(base_dir, scan, "parametric_edges.json")
+    if not os.path.exists(path):
+        log.info(f"Invalid prediction at {scan}")
+        return None
+    with open(path) as f:
+        edge_dict = json.load(f)
+    scan_dir = os.path.join(dataset_dir, scan)
+    if layout == "emap":
+        if undistort:
+            raise ValueError("undistort applies to the colmap layout only")
+        cams, maps = emap_cameras(scan_dir, detector)
+    else:
+        cams, maps = colmap_scan_cameras(scan_dir, detector, undistort, backend, resolution)
+    if "sample_resolution" in options:
+        options["resolution"] = options.pop("sample_resolution")
+    res = SP.edge_support(edge_dict, cams, maps, detector, device=device, backend=backend, **options)
+    res["settings"].update({"layout": layout, "undistort": bool(undistort)})
+    return write_support(os.path.join(base_dir, scan), edge_dict, res, write_filtered, extra={"scan": scan})
+
+
+def support_scene(model_path, edge_dict, cameras, edge_maps, detector, **options):
+    """The export's ``support_checking``: ``edge_dict`` against the given cameras (``NovelViewCamera`` s and uint8 maps, or a
+    Scene's ``EdgeCamera`` s when ``edge_maps`` is None: ``reprojection.scene_cameras``).  Writes ``edge_support.json`` and
+    ``parametric_edges_supported.json`` into ``model_path``, prints the counts before and after, and returns
+    (the filtered dict, the ``edge_support`` result)."""
+    if edge_maps is None:
+        cameras, edge_maps = scene_cameras(cameras)
+    res = SP.edge_support(edge_dict, cameras, edge_maps, detector, **options)
+    os.makedirs(model_path, exist_ok=True)
+    out = write_support(model_path, edge_dict, res, write_filtered=True)
+    print("before support checking: ", out["total"], "after support checking: ", out["kept"])
+    return filter_edge_dict(edge_dict, res["kept"]), res
+
+
+# ------------------------------------------------------------------------------------------------ command line
+def scan_line(scan, out):
+    return f"{scan}: views {out['settings']['views']}, edges {out['total']}, kept {out['kept']}"
+
+
+def parser():
+    ap = argparse.ArgumentParser(description="Check every parametric edge along its length against a scan's edge maps.")
+    ap.add_argument("--base_dir", default="./output", help="directory holding <scan>/parametric_edges.json")
+    ap.add_argument("--dataset_dir", required=True, help="directory holding the scans")
+    ap.add_argument("--scans", default=None, help="file with one scan name per line (default: every scan of --dataset_dir)")
+    ap.add_argument("--layout", choices=LAYOUTS, default="emap")
+    ap.add_argument("--detector", default="DexiNed")
+    ap.add_argument("--undistort", action="store_true", help="colmap layout: resample the edge maps through the lens model")
+    ap.add_argument("--tolerances", nargs="+", type=float, default=list(SP.TOLERANCES_PX), help="pixel tolerances (1 to 4)")
+    ap.add_argument("--keep_tolerance", type=float, default=SP.KEEP_TOLERANCE_PX, help="the tolerance that decides 'kept'")
+    ap.add_argument("--min_visible", type=float, default=SP.MIN_VISIBLE,
+                    help="share of an edge's samples a view must see (untuned)")
+    ap.add_argument("--min_near", type=float, default=SP.MIN_NEAR,
+                    help="share of the seen samples that must lie near a detected pixel (untuned)")
+    ap.add_argument("--frames_ratio", type=float, default=EDGE_VISIBILITY_FRAMES_RATIO,
+                    help="an edge is kept when more than ceil(ratio * views) views support it")
+    ap.add_argument("--sample_resolution", type=float, default=SAMPLE_RESOLUTION)
+    ap.add_argument("--edge_threshold", type=float, default=EDGE_MAX_THRESHOLD)
+    ap.add_argument("--write_filtered", action="store_true", help=f"also write {FILTERED_FILE} with the kept edges")
+    ap.add_argument("--backend", choices=SP.SUPPORT_BACKENDS, default="gpu")
+    return ap
+
+
+def main(argv=None):
+    args = parser().parse_args(argv)
+    for scan in dataset_scans(args.dataset_dir, args.layout, args.scans):
+        out = score_scan(args.base_dir, args.dataset_dir, scan, args.layout, args.detector, args.undistort,
+                         args.write_filtered, backend=args.backend, tolerances_px=args.tolerances,
+                         keep_tolerance_px=args.keep_tolerance, min_visible=args.min_visible, min_near=args.min_near,
+                         frames_ratio=args.frames_ratio, sample_resolution=args.sample_resolution,
+                         edge_threshold=args.edge_threshold)
+        if out is None:
+            print(f"Invalid prediction at {scan}")
+            continue
+        print(scan_line(scan, out))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

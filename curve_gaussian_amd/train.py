@@ -365,7 +365,29 @@ def build_parser():
                    help="after the export, score parametric_edges.json in 2D against the edge maps of the train cameras and, "
                         "separately, of the test cameras (the held-out ones under --eval): reprojection_score.json in the "
                         "model directory")
+    p.add_argument("--support_check", action="store_true",
+                   help="after the export, check every edge of parametric_edges.json along its length against the edge "
+                        "maps of the train cameras: edge_support.json and parametric_edges_supported.json in the model "
+                        "directory; parametric_edges.json stays as it is (untuned defaults; no depth)")
+    p.add_argument("--support_tol_px", type=float, default=None,
+                   help="support check: pixel distance to a detected edge within which a sample counts as near")
+    p.add_argument("--support_min_near", type=float, default=None,
+                   help="support check: share of the samples a view sees that must be near")
+    p.add_argument("--support_min_visible", type=float, default=None,
+                   help="support check: share of an edge's samples that a view must see")
+    p.add_argument("--support_frames_ratio", type=float, default=None,
+                   help="support check: an edge is kept when more than ceil(ratio * views) views support it")
     return p
+
+
+def support_options(args):
+    """The options of ops.edge_support.edge_support that the command line sets; the rest keep their defaults."""
+    opts = {k: v for k, v in (("min_near", args.support_min_near), ("min_visible", args.support_min_visible),
+                              ("frames_ratio", args.support_frames_ratio)) if v is not None}
+    if args.support_tol_px is not None:
+        opts["tolerances_px"] = (args.support_tol_px,)
+        opts["keep_tolerance_px"] = args.support_tol_px
+    return opts
 
 
 def parse_args(argv):
@@ -411,6 +433,13 @@ def main(argv=None):
         for split, res in scores.items():
             if res is not None:
                 print(scan_line(split, res["aggregate"]))
+    if args.support_check:
+        import json
+        from .edge_extraction.support import support_scene
+        with open(os.path.join(dataset.model_path, "parametric_edges.json")) as f:
+            edge_dict = json.load(f)
+        support_scene(dataset.model_path, edge_dict, out["scene"].getTrainCameras(), None, dataset.detector,
+                      **support_options(args))
     print("\nTraining complete.")
 
 

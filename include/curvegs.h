@@ -971,6 +971,35 @@ int cgs_ray_wins(int nx, int ny, int nz, const double* lo /*host, [3]*/, const d
                  const uint32_t* best /*[V,height,width]*/, int window, int margin, int accumulate, uint16_t* wins /*[M]*/,
                  void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Per-edge 2D support: every extracted edge checked along its length against every view's detected edge pixels.  The
+ * reference's visibility check (cgs_edge_visibility) looks at a curve's four control points or a line's two end points;
+ * this counts the edge's own samples.  The reference has no counterpart.
+ *
+ * points is float32 [P,3], device: the samples of all edges, edge after edge.  offsets is int32 [E+1], device,
+ * non-decreasing with offsets[0] = 0 and offsets[E] = P: edge e owns the points offsets[e] .. offsets[e+1] - 1 (the kernel
+ * clips both ends to [0, P], so offsets that break the contract read nothing out of bounds).  Cameras as for
+ * cgs_point_mask: intr [V,4] = (fx, fy, cx, cy) and w2c [V,12] = [R | T] row-major, device, float64; all views of a call
+ * share one size.  d2 is int32 [V,height,width], device: the cgs_edt_squared transform of every view's detected mask.
+ * tol2 is int32 [T], device, 1 <= T <= CGS_EDGE_SUPPORT_MAX_TOL: squared tolerances.
+ *
+ * counts is int32 [E,V,1+T], device.  A point is SEEN in view v when the projection rule of cgs_project_points keeps it
+ * (the same device function, the same operation order, no FMA contraction, IEEE division: c2 > 0, 0 <= u < width,
+ * 0 <= v < height).
+ *   counts[e][v][0]     = the number of seen points of edge e
+ *   counts[e][v][1 + t] = the number of seen points with d2[v][floor(v)][floor(u)] <= tol2[t]
+ * One wave per (edge, view); integers only, no atomics, no LDS, no barrier: the result does not depend on the launch
+ * geometry.  The kernel writes every output word (no memset); an edge without points gives a zero row.  The caller's
+ * stream, no allocation, no host synchronisation.  E = 0 or V = 0 is a no-op (nothing to write).  E, P or V < 0, T outside
+ * [1, CGS_EDGE_SUPPORT_MAX_TOL], a size outside [1, CGS_EDT_MAX_SIZE] and NULL pointers (points only when P > 0) are
+ * CGS_ERR_INVALID_ARGUMENT, rejected before anything is launched.
+ * ------------------------------------------------------------------------------------------------ */
+#define CGS_EDGE_SUPPORT_MAX_TOL 4
+int cgs_edge_support(int E, int P, const float* points /*[P,3]*/, const int32_t* offsets /*[E+1]*/, int V,
+                     const double* intr /*[V,4]*/, const double* w2c /*[V,12]*/, int height, int width,
+                     const int32_t* d2 /*[V,height,width]*/, int T, const int32_t* tol2 /*[T]*/,
+                     int32_t* counts /*[E,V,1+T]*/, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
