@@ -1485,6 +1485,11 @@ int cgs_report_panels(int n_views, cgs_report_view* views, void* workspace, unsi
     return CGS_OK;
 }
 
+// The tail of an entry whose launches are queued: the launch check on the entry's stream.
+static int finish(const char* what, void* stream_) {
+    return check_launch(what, false, (hipStream_t)stream_) ? CGS_OK : CGS_ERR_HIP;
+}
+
 int cgs_project_points(int P, const float* points, int V, const double* intr, const double* w2c, int height, int width,
                        double* uv_out, void* stream_) {
     if (P < 0 || V < 0 || (long long)P * V > (1LL << 40)) {
@@ -1501,8 +1506,7 @@ int cgs_project_points(int P, const float* points, int V, const double* intr, co
         return CGS_ERR_INVALID_ARGUMENT;
     }
     launch_project_points((hipStream_t)stream_, P, points, V, intr, w2c, height, width, uv_out);
-    if (!check_launch("project_points", false, (hipStream_t)stream_)) return CGS_ERR_HIP;
-    return CGS_OK;
+    return finish("project_points", stream_);
 }
 
 size_t cgs_render_points_workspace_bytes(int P, int V, int height, int width) {
@@ -1533,8 +1537,7 @@ int cgs_render_points(int P, const float* points, const float* colors, int V, co
     }
     launch_render_points((hipStream_t)stream_, P, points, colors, V, intr, w2c, height, width, alpha, background, out,
                          kept, workspace, per);
-    if (!check_launch("render_points", false, (hipStream_t)stream_)) return CGS_ERR_HIP;
-    return CGS_OK;
+    return finish("render_points", stream_);
 }
 
 int64_t cgs_ellipsoid_mesh_body_bytes(int P, int resolution, int64_t* vertex_bytes, int64_t* face_bytes) {
@@ -1570,8 +1573,7 @@ int cgs_ellipsoid_mesh_vertices(int first, int count, const float* xyz, const fl
         return CGS_ERR_INVALID_ARGUMENT;
     }
     launch_ellipsoid_vertices((hipStream_t)stream_, first, count, xyz, rot, scale, rgb, V0, unit_vertices, out);
-    if (!check_launch("ellipsoid_mesh_vertices", false, (hipStream_t)stream_)) return CGS_ERR_HIP;
-    return CGS_OK;
+    return finish("ellipsoid_mesh_vertices", stream_);
 }
 
 int cgs_ellipsoid_mesh_faces(int first, int count, int V0, int F0, const int* template_faces, void* out, void* stream_) {
@@ -1594,8 +1596,7 @@ int cgs_ellipsoid_mesh_faces(int first, int count, int V0, int F0, const int* te
         return CGS_ERR_INVALID_ARGUMENT;
     }
     launch_ellipsoid_faces((hipStream_t)stream_, first, count, V0, F0, template_faces, out);
-    if (!check_launch("ellipsoid_mesh_faces", false, (hipStream_t)stream_)) return CGS_ERR_HIP;
-    return CGS_OK;
+    return finish("ellipsoid_mesh_faces", stream_);
 }
 
 int cgs_curve_straightness(int B, const float* curve_points, const uint8_t* is_bezier, int sample_num, double threshold,
@@ -1616,8 +1617,7 @@ int cgs_curve_straightness(int B, const float* curve_points, const uint8_t* is_b
     }
     launch_curve_straightness((hipStream_t)stream_, B, curve_points, is_bezier, sample_num, threshold, threshold_max,
                               mean_dist, max_dist, straight);
-    if (!check_launch("curve_straightness", false, (hipStream_t)stream_)) return CGS_ERR_HIP;
-    return CGS_OK;
+    return finish("curve_straightness", stream_);
 }
 
 size_t cgs_segment_merge_workspace_bytes(int n) { return segment_merge_workspace_bytes(n); }
@@ -1645,8 +1645,7 @@ int cgs_segment_merge_labels(int n, const float* seg, double distance_threshold,
     }
     launch_segment_merge_labels((hipStream_t)stream_, n, seg, distance_threshold, similarity_threshold, workspace, labels,
                                 n_components);
-    if (!check_launch("segment_merge_labels", false, (hipStream_t)stream_)) return CGS_ERR_HIP;
-    return CGS_OK;
+    return finish("segment_merge_labels", stream_);
 }
 
 int cgs_pair_consensus_fit(int B, const float* curve_points, int K, const int* pairs, int sample_num, double ransac_thresh,
@@ -1667,8 +1666,7 @@ int cgs_pair_consensus_fit(int B, const float* curve_points, int K, const int* p
     }
     launch_pair_consensus_fit((hipStream_t)stream_, K, curve_points, pairs, sample_num, ransac_thresh, error_threshold, ctrl,
                               rmse, inliers, ok);
-    if (!check_launch("pair_consensus_fit", false, (hipStream_t)stream_)) return CGS_ERR_HIP;
-    return CGS_OK;
+    return finish("pair_consensus_fit", stream_);
 }
 
 int cgs_undistort_images(int n_views, const cgs_undistort_view* views, float fill, int* blank_counts, void* stream_) {
@@ -1717,8 +1715,7 @@ int cgs_undistort_images(int n_views, const cgs_undistort_view* views, float fil
         }
     }
     launch_undistort_images((hipStream_t)stream_, n_views, views, fill, blank_counts);
-    if (!check_launch("undistort_images", false, (hipStream_t)stream_)) return CGS_ERR_HIP;
-    return CGS_OK;
+    return finish("undistort_images", stream_);
 }
 
 int cgs_edge_gradients(int n_views, const cgs_edge_gradient_view* views, const float* taps, int radius, void* stream_) {
@@ -1747,8 +1744,7 @@ int cgs_edge_gradients(int n_views, const cgs_edge_gradient_view* views, const f
         }
     }
     launch_edge_gradients((hipStream_t)stream_, n_views, views, taps, radius);
-    if (!check_launch("edge_gradients", false, (hipStream_t)stream_)) return CGS_ERR_HIP;
-    return CGS_OK;
+    return finish("edge_gradients", stream_);
 }
 
 int cgs_edge_trace(int n_views, const cgs_edge_trace_view* views, float low, float high, int thin, int* changed_flag,
@@ -1805,8 +1801,7 @@ int cgs_point_mask(int P, const float* points, int V, const double* intr, const 
         set_error("cgs_point_mask: clearing the mask failed");
         return CGS_ERR_HIP;
     }
-    if (!check_launch("point_mask", false, (hipStream_t)stream_)) return CGS_ERR_HIP;
-    return CGS_OK;
+    return finish("point_mask", stream_);
 }
 
 static bool edt_size_ok(int height, int width) {
@@ -1830,8 +1825,7 @@ int cgs_edt_squared(int V, int height, int width, const uint8_t* mask, void* wor
         return CGS_ERR_INVALID_ARGUMENT;
     }
     launch_edt_squared((hipStream_t)stream_, V, height, width, mask, workspace, dist2_out);
-    if (!check_launch("edt_squared", false, (hipStream_t)stream_)) return CGS_ERR_HIP;
-    return CGS_OK;
+    return finish("edt_squared", stream_);
 }
 
 size_t cgs_edge_score_workspace_bytes(int V) { return edge_score_workspace_bytes(V); }
@@ -1862,8 +1856,7 @@ int cgs_edge_score_reduce(int V, int height, int width, const uint8_t* pred_mask
         set_error("cgs_edge_score_reduce: clearing the counters failed");
         return CGS_ERR_HIP;
     }
-    if (!check_launch("edge_score_reduce", false, (hipStream_t)stream_)) return CGS_ERR_HIP;
-    return CGS_OK;
+    return finish("edge_score_reduce", stream_);
 }
 
 int cgs_pack_near_bits(int V, int height, int width, const int32_t* dist2, int tol2, uint32_t* bits_out, void* stream_) {
@@ -1878,75 +1871,21 @@ int cgs_pack_near_bits(int V, int height, int width, const int32_t* dist2, int t
         return CGS_ERR_INVALID_ARGUMENT;
     }
     launch_pack_near_bits((hipStream_t)stream_, V, height, width, dist2, tol2, bits_out);
-    if (!check_launch("pack_near_bits", false, (hipStream_t)stream_)) return CGS_ERR_HIP;
-    return CGS_OK;
+    return finish("pack_near_bits", stream_);
 }
 
-int cgs_voxel_votes(int nx, int ny, int nz, const double* lo, const double* step, int V, const double* intr,
-                    const double* w2c, int height, int width, const uint32_t* bits, int accumulate, uint16_t* seen,
-                    uint16_t* hit, void* stream_) {
-    if (V < 0 || V > CGS_SEED_MAX_VIEWS || nx <= 0 || ny <= 0 || nz <= 0 || !edt_size_ok(height, width)) {
-        set_error("cgs_voxel_votes: invalid argument (dims=%dx%dx%d, V=%d, height=%d, width=%d)", nx, ny, nz, V, height, width);
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
-    if ((long long)nx * ny > INT32_MAX || (long long)nx * ny * nz > INT32_MAX) {   // the first product is below 2^62
-        set_error("cgs_voxel_votes: invalid argument (%dx%dx%d voxels: at most 2^31 - 1)", nx, ny, nz);
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
-    if (!lo || !step || !seen || !hit || (V > 0 && (!intr || !w2c || !bits))) {
-        set_error("cgs_voxel_votes: invalid argument (NULL pointer)");
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
-    for (int a = 0; a < 3; a++)
-        if (!std::isfinite(lo[a]) || !std::isfinite(step[a]) || !(step[a] > 0.0)) {
-            set_error("cgs_voxel_votes: invalid argument (axis %d: lo=%g, step=%g)", a, lo[a], step[a]);
-            return CGS_ERR_INVALID_ARGUMENT;
-        }
-    if (V == 0 && accumulate) return CGS_OK;
-    launch_voxel_votes((hipStream_t)stream_, nx, ny, nz, lo, step, V, intr, w2c, height, width, bits, accumulate, seen, hit);
-    if (!check_launch("voxel_votes", false, (hipStream_t)stream_)) return CGS_ERR_HIP;
-    return CGS_OK;
-}
-
-int cgs_voxel_moments(int nx, int ny, int nz, const void* keep_bits, int N, const void* centres, int radius, void* moments,
-                      void* stream_) {
-    if (N < 0 || nx <= 0 || ny <= 0 || nz <= 0 || radius < 1 || radius > CGS_SEED_MAX_RADIUS) {
-        set_error("cgs_voxel_moments: invalid argument (dims=%dx%dx%d, N=%d, radius=%d; the radius lies in [1, %d])", nx, ny,
-                  nz, N, radius, CGS_SEED_MAX_RADIUS);
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
-    if ((long long)nx * ny > INT32_MAX || (long long)nx * ny * nz > INT32_MAX) {   // the first product is below 2^62
-        set_error("cgs_voxel_moments: invalid argument (%dx%dx%d voxels: at most 2^31 - 1)", nx, ny, nz);
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
-    if (!keep_bits || !centres || !moments) {
-        set_error("cgs_voxel_moments: invalid argument (NULL pointer)");
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
-    if (N == 0) return CGS_OK;
-    launch_voxel_moments((hipStream_t)stream_, nx, ny, nz, (const unsigned int*)keep_bits, N, (const int*)centres, radius,
-                         (int*)moments);
-    if (!check_launch("voxel_moments", false, (hipStream_t)stream_)) return CGS_ERR_HIP;
-    return CGS_OK;
-}
-
-// The checks that cgs_ray_claims and cgs_ray_wins share with cgs_voxel_votes: dims, sizes, the list, lo and step.
-static bool ray_args_ok(const char* name, int nx, int ny, int nz, const double* lo, const double* step, int M, int V,
-                        int height, int width) {
-    if (M < 0 || V < 0 || V > CGS_SEED_MAX_VIEWS || nx <= 0 || ny <= 0 || nz <= 0 || !edt_size_ok(height, width)) {
-        set_error("%s: invalid argument (dims=%dx%dx%d, M=%d, V=%d, height=%d, width=%d)", name, nx, ny, nz, M, V, height,
-                  width);
+// The checks that the seed entries share.  A grid: positive dims, nx ny and nx ny nz at most 2^31 - 1 and, where lo and step
+// are given (cgs_voxel_moments has neither; a NULL one is the entry's to report), finite with step > 0.
+static bool seed_grid_ok(const char* name, int nx, int ny, int nz, const double* lo, const double* step) {
+    if (nx <= 0 || ny <= 0 || nz <= 0) {
+        set_error("%s: invalid argument (dims=%dx%dx%d)", name, nx, ny, nz);
         return false;
     }
     if ((long long)nx * ny > INT32_MAX || (long long)nx * ny * nz > INT32_MAX) {   // the first product is below 2^62
         set_error("%s: invalid argument (%dx%dx%d voxels: at most 2^31 - 1)", name, nx, ny, nz);
         return false;
     }
-    if (!lo || !step) {
-        set_error("%s: invalid argument (NULL pointer)", name);
-        return false;
-    }
-    for (int a = 0; a < 3; a++)
+    for (int a = 0; lo && step && a < 3; a++)
         if (!std::isfinite(lo[a]) || !std::isfinite(step[a]) || !(step[a] > 0.0)) {
             set_error("%s: invalid argument (axis %d: lo=%g, step=%g)", name, a, lo[a], step[a]);
             return false;
@@ -1954,29 +1893,89 @@ static bool ray_args_ok(const char* name, int nx, int ny, int nz, const double* 
     return true;
 }
 
+// The views of a seed entry: their number and the size of their maps.
+static bool seed_views_ok(const char* name, int V, int height, int width) {
+    if (V < 0 || V > CGS_SEED_MAX_VIEWS || !edt_size_ok(height, width)) {
+        set_error("%s: invalid argument (V=%d, height=%d, width=%d; sizes lie in [1, %d])", name, V, height, width,
+                  CGS_EDT_MAX_SIZE);
+        return false;
+    }
+    return true;
+}
+
+int cgs_voxel_votes(int nx, int ny, int nz, const double* lo, const double* step, int V, const double* intr,
+                    const double* w2c, int height, int width, const uint32_t* bits, int accumulate, uint16_t* seen,
+                    uint16_t* hit, void* stream_) {
+    // a NULL pointer is reported after the dims and before a bad lo or step, as it always was
+    const bool ptrs = lo && step && seen && hit && (V == 0 || (intr && w2c && bits));
+    if (!seed_views_ok("cgs_voxel_votes", V, height, width) ||
+        !seed_grid_ok("cgs_voxel_votes", nx, ny, nz, ptrs ? lo : nullptr, ptrs ? step : nullptr))
+        return CGS_ERR_INVALID_ARGUMENT;
+    if (!ptrs) {
+        set_error("cgs_voxel_votes: invalid argument (NULL pointer)");
+        return CGS_ERR_INVALID_ARGUMENT;
+    }
+    if (V == 0 && accumulate) return CGS_OK;
+    launch_voxel_votes((hipStream_t)stream_, SeedGrid{{lo[0], lo[1], lo[2]}, {step[0], step[1], step[2]}, nx, ny, nz},
+                       SeedViews{V, height, width, (width + 31) / 32, intr, w2c, bits}, accumulate, seen, hit);
+    return finish("voxel_votes", stream_);
+}
+
+int cgs_voxel_moments(int nx, int ny, int nz, const void* keep_bits, int N, const void* centres, int radius, void* moments,
+                      void* stream_) {
+    if (N < 0 || radius < 1 || radius > CGS_SEED_MAX_RADIUS) {
+        set_error("cgs_voxel_moments: invalid argument (N=%d, radius=%d; the radius lies in [1, %d])", N, radius,
+                  CGS_SEED_MAX_RADIUS);
+        return CGS_ERR_INVALID_ARGUMENT;
+    }
+    if (!seed_grid_ok("cgs_voxel_moments", nx, ny, nz, nullptr, nullptr)) return CGS_ERR_INVALID_ARGUMENT;
+    if (!keep_bits || !centres || !moments) {
+        set_error("cgs_voxel_moments: invalid argument (NULL pointer)");
+        return CGS_ERR_INVALID_ARGUMENT;
+    }
+    if (N == 0) return CGS_OK;
+    launch_voxel_moments((hipStream_t)stream_, nx, ny, nz, (const unsigned int*)keep_bits, N, (const int*)centres, radius,
+                         (int*)moments);
+    return finish("voxel_moments", stream_);
+}
+
 int cgs_ray_claims(int nx, int ny, int nz, const double* lo, const double* step, int M, const int32_t* index,
                    const uint16_t* support, int V, const double* intr, const double* w2c, int height, int width,
                    const uint32_t* bits, int clear, uint32_t* best, void* stream_) {
-    if (!ray_args_ok("cgs_ray_claims", nx, ny, nz, lo, step, M, V, height, width)) return CGS_ERR_INVALID_ARGUMENT;
-    if ((V > 0 && !best) || (M > 0 && V > 0 && (!index || !support || !intr || !w2c || !bits))) {
+    if (M < 0) {
+        set_error("cgs_ray_claims: invalid argument (M=%d)", M);
+        return CGS_ERR_INVALID_ARGUMENT;
+    }
+    if (!seed_views_ok("cgs_ray_claims", V, height, width) || !seed_grid_ok("cgs_ray_claims", nx, ny, nz, lo, step))
+        return CGS_ERR_INVALID_ARGUMENT;
+    if (!lo || !step || (V > 0 && !best) || (M > 0 && V > 0 && (!index || !support || !intr || !w2c || !bits))) {
         set_error("cgs_ray_claims: invalid argument (NULL pointer)");
         return CGS_ERR_INVALID_ARGUMENT;
     }
-    if (launch_ray_claims((hipStream_t)stream_, nx, ny, nz, lo, step, M, index, support, V, intr, w2c, height, width, bits,
-                          clear, best) != hipSuccess) {
+    const SeedGrid g{{lo[0], lo[1], lo[2]}, {step[0], step[1], step[2]}, nx, ny, nz};
+    const SeedViews views{V, height, width, (width + 31) / 32, intr, w2c, bits};
+    if (launch_ray_claims((hipStream_t)stream_, g, views, M, index, support, clear, best) != hipSuccess) {
         set_error("cgs_ray_claims: clearing the claims failed");
         return CGS_ERR_HIP;
     }
     if (M == 0 || V == 0) return CGS_OK;
-    if (!check_launch("ray_claims", false, (hipStream_t)stream_)) return CGS_ERR_HIP;
-    return CGS_OK;
+    return finish("ray_claims", stream_);
 }
 
 int cgs_ray_wins(int nx, int ny, int nz, const double* lo, const double* step, int M, const int32_t* index,
                  const uint16_t* support, int V, const double* intr, const double* w2c, int height, int width,
                  const uint32_t* bits, const uint32_t* best, int window, int margin, int accumulate, uint16_t* wins,
                  void* stream_) {
-    if (!ray_args_ok("cgs_ray_wins", nx, ny, nz, lo, step, M, V, height, width)) return CGS_ERR_INVALID_ARGUMENT;
+    if (M < 0) {
+        set_error("cgs_ray_wins: invalid argument (M=%d)", M);
+        return CGS_ERR_INVALID_ARGUMENT;
+    }
+    if (!seed_views_ok("cgs_ray_wins", V, height, width) || !seed_grid_ok("cgs_ray_wins", nx, ny, nz, lo, step))
+        return CGS_ERR_INVALID_ARGUMENT;
+    if (!lo || !step) {   // before the window and the margin, as it always was
+        set_error("cgs_ray_wins: invalid argument (NULL pointer)");
+        return CGS_ERR_INVALID_ARGUMENT;
+    }
     if (window < 0 || window > CGS_SEED_MAX_WINDOW || margin < 0 || margin > 65535) {
         set_error("cgs_ray_wins: invalid argument (window=%d, margin=%d; the window lies in [0, %d], the margin in [0, 65535])",
                   window, margin, CGS_SEED_MAX_WINDOW);
@@ -1987,10 +1986,10 @@ int cgs_ray_wins(int nx, int ny, int nz, const double* lo, const double* step, i
         return CGS_ERR_INVALID_ARGUMENT;
     }
     if (M == 0 || V == 0) return CGS_OK;
-    launch_ray_wins((hipStream_t)stream_, nx, ny, nz, lo, step, M, index, support, V, intr, w2c, height, width, bits, best,
-                    window, margin, accumulate, wins);
-    if (!check_launch("ray_wins", false, (hipStream_t)stream_)) return CGS_ERR_HIP;
-    return CGS_OK;
+    launch_ray_wins((hipStream_t)stream_, SeedGrid{{lo[0], lo[1], lo[2]}, {step[0], step[1], step[2]}, nx, ny, nz},
+                    SeedViews{V, height, width, (width + 31) / 32, intr, w2c, bits}, M, index, support, best, window, margin,
+                    accumulate, wins);
+    return finish("ray_wins", stream_);
 }
 
 int cgs_edge_support(int E, int P, const float* points, const int32_t* offsets, int V, const double* intr,
@@ -2012,8 +2011,7 @@ int cgs_edge_support(int E, int P, const float* points, const int32_t* offsets, 
         return CGS_ERR_INVALID_ARGUMENT;
     }
     launch_edge_support((hipStream_t)stream_, E, P, points, offsets, V, intr, w2c, height, width, d2, T, tol2, counts);
-    if (!check_launch("edge_support", false, (hipStream_t)stream_)) return CGS_ERR_HIP;
-    return CGS_OK;
+    return finish("edge_support", stream_);
 }
 
 }  // extern "C"

@@ -7,14 +7,20 @@
 //                      dist2 <= tol2 inside the image and 0 in the padding, one wave ballot gives two words, lanes 0 and 32
 //                      store them.  A padded plane is a whole number of words, so the linear pixel index / 32 is the word
 //                      index and a wave may straddle two rows.  Every word is written, padding included: no memset.
+//   seed_walk          the walk that the three kernels below share, written once: the centre of a voxel is
+//                      lo + (i + 0.5) * step in float64 without contraction, rounded to float32 (seed_centre): the point
+//                      that is projected, by nv_project_xyz (point_projection.h), the device function of
+//                      cgs_project_points / cgs_point_mask.  The thread loops over the views; the camera index is
+//                      wave-uniform, so the 16 doubles of a camera are scalar loads, as in visibility.hip.  For every view
+//                      that keeps the centre, seed_pixel gives its pixel and the pixel's near bit, and the kernel's own
+//                      lambda gets (v, px, py, near).  A pixel that differed between the vote and the claim would be a bug
+//                      that no tolerance hides: there is one walk for it to differ in.
 //   k_voxel_votes      one thread per voxel, linear index with x fastest, so the lanes of a wave are neighbours along x and
-//                      gather neighbouring pixels.  The centre is lo + (i + 0.5) * step in float64 without contraction,
-//                      rounded to float32: the point that is projected, by nv_project_xyz (point_projection.h), the device
-//                      function of cgs_project_points / cgs_point_mask.  The thread loops over the views; the camera index
-//                      is wave-uniform, so the 16 doubles of a camera are scalar loads, as in visibility.hip.  Both counts
-//                      stay in registers; one plain 16-bit store each at the end (a read-add-store of the thread's own
-//                      voxel with `accumulate`).  No atomics, no LDS: the result does not depend on the launch geometry.
-//                      The packed masks are the only gathered data: 1600x1200 is 240 KB a view, 24 MB for 100 views.
+//                      gather neighbouring pixels.  The walk counts the views that keep the centre and those whose bit is
+//                      set.  Both counts stay in registers; one plain 16-bit store each at the end (a read-add-store of the
+//                      thread's own voxel with `accumulate`).  No atomics, no LDS: the result does not depend on the launch
+//                      geometry.  The packed masks are the only gathered data: 1600x1200 is 240 KB a view, 24 MB for 100
+//                      views.
 //   k_voxel_moments    one wave per seed, four seeds per block.  The lanes walk the (dy, dz) rows of the seed's window, at
 //                      most 31 x 31 of them; a row inside the grid whose half span h = isqrt(r^2 - dy^2 - dz^2) exists
 //                      covers x = cx - h .. cx + h clipped to the grid, at most 31 voxels in at most two words: plain
@@ -22,12 +28,10 @@
 //                      the set bits in registers.  One shuffle reduction per wave, lane 0 stores the ten values: every
 //                      output word is written, no memset.  Integers only, no atomics, no LDS, no barrier (a wave without a
 //                      seed leaves at once): the result does not depend on the launch geometry.
-//   k_ray_claims       one thread per LISTED voxel (the kept voxels, ascending linear indices).  The same centre, the same
-//                      projection and the same near bit as k_voxel_votes, through the same device functions (seed_centre,
-//                      seed_pixel): a pixel that differs between the vote and the claim would be a bug that no tolerance
-//                      hides.  Where the voxel hits, its support goes into best[v][y][x] by atomicMax on unsigned int: the
-//                      one atomic of this file, and an integer maximum does not depend on the order, so the result still
-//                      does not depend on the launch geometry.
+//   k_ray_claims       one thread per LISTED voxel (the kept voxels, ascending linear indices), the same walk.  Where the
+//                      voxel hits, its support goes into best[v][y][x] by atomicMax on unsigned int: the one atomic of
+//                      this file, and an integer maximum does not depend on the order, so the result still does not depend
+//                      on the launch geometry.
 //   k_ray_wins         one thread per listed voxel, the same walk.  Where the voxel hits, the maximum of best over the
 //                      (2 w + 1)^2 window around its pixel, clipped to the image, by plain loads; the view is won when
 //                      support + margin (32 bits) reaches it.  The count stays in a register; one plain 16-bit store at the
@@ -45,12 +49,6 @@ constexpr int SEED_THREADS = 256;        // 4 waves
 constexpr int SEED_MAX_VIEWS = 65535;    // grid.y of the packing launch
 constexpr int MOMENT_WAVES = SEED_THREADS / 64;   // seeds per block of k_voxel_moments
 constexpr int MOMENT_VALUES = 10;        // m, the three first and the six second moments
-
-struct SeedGrid {  // passed by value
-    double lo[3];
-    double step[3];
-    int nx, ny, nz;
-};
 
 __global__ void __launch_bounds__(SEED_THREADS) k_pack_near_bits(int height, int width, int stride,
                                                                 const int* __restrict__ dist2, int tol2,
@@ -96,29 +94,34 @@ __device__ inline bool seed_pixel(const NvCam& c, double X, double Y, double Z, 
     return true;
 }
 
-__global__ void __launch_bounds__(SEED_THREADS) k_voxel_votes(const SeedGrid g, int V, const double* __restrict__ intr,
-                                                             const double* __restrict__ w2c, int height, int width,
-                                                             int stride, const unsigned int* __restrict__ bits,
-                                                             int accumulate, unsigned short* __restrict__ seen,
-                                                             unsigned short* __restrict__ hit) {
+// The walk of the file header: f(v, px, py, near) for every view v that keeps the centre of the voxel with linear index `id`.
+template <class F>
+__device__ inline void seed_walk(const SeedGrid& g, const SeedViews& s, long long id, F&& f) {
 #pragma clang fp contract(off)
+    double X, Y, Z;
+    seed_centre(g, id, X, Y, Z);
+    const double wd = (double)s.width, hd = (double)s.height;
+    const size_t plane = (size_t)s.height * (size_t)s.stride;
+    for (int v = 0; v < s.V; v++) {   // v is uniform: scalar loads of the camera
+        NvCam c;
+        nv_load_cam(c, s.intr, s.w2c, v);
+        unsigned int px, py;
+        bool near;
+        if (seed_pixel(c, X, Y, Z, wd, hd, s.bits + (size_t)v * plane, s.stride, px, py, near)) f(v, px, py, near);
+    }
+}
+
+__global__ void __launch_bounds__(SEED_THREADS) k_voxel_votes(const SeedGrid g, const SeedViews s, int accumulate,
+                                                             unsigned short* __restrict__ seen,
+                                                             unsigned short* __restrict__ hit) {
     const long long n = (long long)g.nx * g.ny * g.nz;   // <= 2^31 - 1
     const long long id = (long long)blockIdx.x * SEED_THREADS + threadIdx.x;
     if (id >= n) return;
-    double X, Y, Z;
-    seed_centre(g, id, X, Y, Z);
-    const double wd = (double)width, hd = (double)height;
-    const size_t plane = (size_t)height * (size_t)stride;
     int n_seen = 0, n_hit = 0;
-    for (int v = 0; v < V; v++) {   // v is uniform: scalar loads of the camera
-        NvCam c;
-        nv_load_cam(c, intr, w2c, v);
-        unsigned int px, py;
-        bool near;
-        if (!seed_pixel(c, X, Y, Z, wd, hd, bits + (size_t)v * plane, stride, px, py, near)) continue;
+    seed_walk(g, s, id, [&](int, unsigned int, unsigned int, bool near) {
         n_seen++;
         n_hit += (int)near;
-    }
+    });
     if (accumulate) {
         n_seen += seen[id];
         n_hit += hit[id];
@@ -174,68 +177,49 @@ __global__ void __launch_bounds__(SEED_THREADS) k_voxel_moments(int nx, int ny, 
     }
 }
 
-__global__ void __launch_bounds__(SEED_THREADS) k_ray_claims(const SeedGrid g, int M, const int* __restrict__ index,
-                                                            const unsigned short* __restrict__ support, int V,
-                                                            const double* __restrict__ intr, const double* __restrict__ w2c,
-                                                            int height, int width, int stride,
-                                                            const unsigned int* __restrict__ bits, unsigned int* best) {
-#pragma clang fp contract(off)
+__global__ void __launch_bounds__(SEED_THREADS) k_ray_claims(const SeedGrid g, const SeedViews s, int M,
+                                                            const int* __restrict__ index,
+                                                            const unsigned short* __restrict__ support,
+                                                            unsigned int* __restrict__ best) {
     const long long n = (long long)g.nx * g.ny * g.nz;   // <= 2^31 - 1
     const long long m = (long long)blockIdx.x * SEED_THREADS + threadIdx.x;
     if (m >= M) return;
     const long long id = index[m];
     if (id < 0 || id >= n) return;   // the caller's error: claims nothing
-    const unsigned int s = support[m];
-    double X, Y, Z;
-    seed_centre(g, id, X, Y, Z);
-    const double wd = (double)width, hd = (double)height;
-    const size_t plane = (size_t)height * (size_t)stride, image = (size_t)height * (size_t)width;
-    for (int v = 0; v < V; v++) {   // v is uniform: scalar loads of the camera
-        NvCam c;
-        nv_load_cam(c, intr, w2c, v);
-        unsigned int px, py;
-        bool near;
-        if (!seed_pixel(c, X, Y, Z, wd, hd, bits + (size_t)v * plane, stride, px, py, near) || !near) continue;
-        unsigned int* p = best + (size_t)v * image + (size_t)py * (size_t)width + (size_t)px;
+    const unsigned int sup = support[m];
+    const size_t image = (size_t)s.height * (size_t)s.width;
+    seed_walk(g, s, id, [&](int v, unsigned int px, unsigned int py, bool near) {
+        if (!near) return;
+        unsigned int* p = best + (size_t)v * image + (size_t)py * (size_t)s.width + (size_t)px;
         // no look before the atomic: a plain load that skips it where best already holds as much measured slower
         // (profiles/edge_seed_exclusive.md)
-        atomicMax(p, s);
-    }
+        atomicMax(p, sup);
+    });
 }
 
-__global__ void __launch_bounds__(SEED_THREADS) k_ray_wins(const SeedGrid g, int M, const int* __restrict__ index,
-                                                          const unsigned short* __restrict__ support, int V,
-                                                          const double* __restrict__ intr, const double* __restrict__ w2c,
-                                                          int height, int width, int stride,
-                                                          const unsigned int* __restrict__ bits,
+__global__ void __launch_bounds__(SEED_THREADS) k_ray_wins(const SeedGrid g, const SeedViews s, int M,
+                                                          const int* __restrict__ index,
+                                                          const unsigned short* __restrict__ support,
                                                           const unsigned int* __restrict__ best, int window, int margin,
                                                           int accumulate, unsigned short* __restrict__ wins) {
-#pragma clang fp contract(off)
     const long long n = (long long)g.nx * g.ny * g.nz;   // <= 2^31 - 1
     const long long m = (long long)blockIdx.x * SEED_THREADS + threadIdx.x;
     if (m >= M) return;
     const long long id = index[m];
     int n_wins = 0;
     if (id >= 0 && id < n) {   // an index outside the grid is the caller's error: it wins nothing
-        const unsigned int s = (unsigned int)support[m] + (unsigned int)margin;   // <= 131070: 32 bits do not wrap
-        double X, Y, Z;
-        seed_centre(g, id, X, Y, Z);
-        const double wd = (double)width, hd = (double)height;
-        const size_t plane = (size_t)height * (size_t)stride, image = (size_t)height * (size_t)width;
-        for (int v = 0; v < V; v++) {   // v is uniform: scalar loads of the camera
-            NvCam c;
-            nv_load_cam(c, intr, w2c, v);
-            unsigned int px, py;
-            bool near;
-            if (!seed_pixel(c, X, Y, Z, wd, hd, bits + (size_t)v * plane, stride, px, py, near) || !near) continue;
-            const int x0 = max((int)px - window, 0), x1 = min((int)px + window, width - 1);
-            const int y0 = max((int)py - window, 0), y1 = min((int)py + window, height - 1);
+        const unsigned int sup = (unsigned int)support[m] + (unsigned int)margin;   // <= 131070: 32 bits do not wrap
+        const size_t image = (size_t)s.height * (size_t)s.width;
+        seed_walk(g, s, id, [&](int v, unsigned int px, unsigned int py, bool near) {
+            if (!near) return;
+            const int x0 = max((int)px - window, 0), x1 = min((int)px + window, s.width - 1);
+            const int y0 = max((int)py - window, 0), y1 = min((int)py + window, s.height - 1);
             const unsigned int* view = best + (size_t)v * image;
             unsigned int top = 0;
             for (int y = y0; y <= y1; y++)
-                for (int x = x0; x <= x1; x++) top = max(top, view[(size_t)y * (size_t)width + (size_t)x]);
-            n_wins += (int)(s >= top);
-        }
+                for (int x = x0; x <= x1; x++) top = max(top, view[(size_t)y * (size_t)s.width + (size_t)x]);
+            n_wins += (int)(sup >= top);
+        });
     }
     if (accumulate) n_wins += wins[m];
     wins[m] = (unsigned short)n_wins;
@@ -254,27 +238,12 @@ void launch_pack_near_bits(hipStream_t s, int V, int height, int width, const in
     }
 }
 
-static SeedGrid seed_grid(int nx, int ny, int nz, const double* lo, const double* step) {
-    SeedGrid g;
-    for (int a = 0; a < 3; a++) {
-        g.lo[a] = lo[a];
-        g.step[a] = step[a];
-    }
-    g.nx = nx;
-    g.ny = ny;
-    g.nz = nz;
-    return g;
-}
-
-void launch_voxel_votes(hipStream_t s, int nx, int ny, int nz, const double* lo, const double* step, int V,
-                        const double* intr, const double* w2c, int height, int width, const unsigned int* bits,
-                        int accumulate, unsigned short* seen, unsigned short* hit) {
-    const SeedGrid g = seed_grid(nx, ny, nz, lo, step);
-    const long long n = (long long)nx * ny * nz;
+void launch_voxel_votes(hipStream_t s, SeedGrid g, SeedViews views, int accumulate, unsigned short* seen,
+                        unsigned short* hit) {
+    const long long n = (long long)g.nx * g.ny * g.nz;
     const unsigned blocks = (unsigned)((n + SEED_THREADS - 1) / SEED_THREADS);   // <= 2^23
     ProfScope p("voxel_votes", s);
-    hipLaunchKernelGGL(k_voxel_votes, dim3(blocks), dim3(SEED_THREADS), 0, s, g, V, intr, w2c, height, width,
-                       (width + 31) / 32, bits, accumulate, seen, hit);
+    hipLaunchKernelGGL(k_voxel_votes, dim3(blocks), dim3(SEED_THREADS), 0, s, g, views, accumulate, seen, hit);
 }
 
 void launch_voxel_moments(hipStream_t s, int nx, int ny, int nz, const unsigned int* keep, int N, const int* centres,
@@ -285,29 +254,26 @@ void launch_voxel_moments(hipStream_t s, int nx, int ny, int nz, const unsigned 
                        radius, moments);
 }
 
-hipError_t launch_ray_claims(hipStream_t s, int nx, int ny, int nz, const double* lo, const double* step, int M,
-                             const int* index, const unsigned short* support, int V, const double* intr, const double* w2c,
-                             int height, int width, const unsigned int* bits, int clear, unsigned int* best) {
-    if (clear && V > 0) {
-        const hipError_t e = hipMemsetAsync(best, 0, (size_t)V * (size_t)height * (size_t)width * sizeof(unsigned int), s);
+hipError_t launch_ray_claims(hipStream_t s, SeedGrid g, SeedViews views, int M, const int* index,
+                             const unsigned short* support, int clear, unsigned int* best) {
+    if (clear && views.V > 0) {
+        const size_t bytes = (size_t)views.V * (size_t)views.height * (size_t)views.width * sizeof(unsigned int);
+        const hipError_t e = hipMemsetAsync(best, 0, bytes, s);
         if (e != hipSuccess) return e;
     }
-    if (M == 0 || V == 0) return hipSuccess;
+    if (M == 0 || views.V == 0) return hipSuccess;
     const unsigned blocks = (unsigned)(((long long)M + SEED_THREADS - 1) / SEED_THREADS);   // <= 2^23
     ProfScope p("ray_claims", s);
-    hipLaunchKernelGGL(k_ray_claims, dim3(blocks), dim3(SEED_THREADS), 0, s, seed_grid(nx, ny, nz, lo, step), M, index,
-                       support, V, intr, w2c, height, width, (width + 31) / 32, bits, best);
+    hipLaunchKernelGGL(k_ray_claims, dim3(blocks), dim3(SEED_THREADS), 0, s, g, views, M, index, support, best);
     return hipSuccess;
 }
 
-void launch_ray_wins(hipStream_t s, int nx, int ny, int nz, const double* lo, const double* step, int M, const int* index,
-                     const unsigned short* support, int V, const double* intr, const double* w2c, int height, int width,
-                     const unsigned int* bits, const unsigned int* best, int window, int margin, int accumulate,
-                     unsigned short* wins) {
+void launch_ray_wins(hipStream_t s, SeedGrid g, SeedViews views, int M, const int* index, const unsigned short* support,
+                     const unsigned int* best, int window, int margin, int accumulate, unsigned short* wins) {
     const unsigned blocks = (unsigned)(((long long)M + SEED_THREADS - 1) / SEED_THREADS);   // <= 2^23
     ProfScope p("ray_wins", s);
-    hipLaunchKernelGGL(k_ray_wins, dim3(blocks), dim3(SEED_THREADS), 0, s, seed_grid(nx, ny, nz, lo, step), M, index, support,
-                       V, intr, w2c, height, width, (width + 31) / 32, bits, best, window, margin, accumulate, wins);
+    hipLaunchKernelGGL(k_ray_wins, dim3(blocks), dim3(SEED_THREADS), 0, s, g, views, M, index, support, best, window, margin,
+                       accumulate, wins);
 }
 
 }  // namespace cgs

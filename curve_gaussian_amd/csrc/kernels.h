@@ -217,18 +217,25 @@ hipError_t launch_edge_score_reduce(hipStream_t s, int V, int height, int width,
                                     uint8_t* both_nonempty);
 // edge_seed.hip
 void launch_pack_near_bits(hipStream_t s, int V, int height, int width, const int* dist2, int tol2, unsigned int* bits);
-void launch_voxel_votes(hipStream_t s, int nx, int ny, int nz, const double* lo, const double* step, int V,
-                        const double* intr, const double* w2c, int height, int width, const unsigned int* bits,
-                        int accumulate, unsigned short* seen, unsigned short* hit);
+struct SeedGrid {   // the voxel grid of a vote; passed by value
+    double lo[3];
+    double step[3];
+    int nx, ny, nz;
+};
+struct SeedViews {  // the views of one call: cameras and packed near masks, stride = ceil(width / 32) words; passed by value
+    int V, height, width, stride;
+    const double* intr;
+    const double* w2c;
+    const unsigned int* bits;
+};
+void launch_voxel_votes(hipStream_t s, SeedGrid g, SeedViews views, int accumulate, unsigned short* seen,
+                        unsigned short* hit);
 void launch_voxel_moments(hipStream_t s, int nx, int ny, int nz, const unsigned int* keep, int N, const int* centres,
                           int radius, int* moments);
-hipError_t launch_ray_claims(hipStream_t s, int nx, int ny, int nz, const double* lo, const double* step, int M,
-                             const int* index, const unsigned short* support, int V, const double* intr, const double* w2c,
-                             int height, int width, const unsigned int* bits, int clear, unsigned int* best);
-void launch_ray_wins(hipStream_t s, int nx, int ny, int nz, const double* lo, const double* step, int M, const int* index,
-                     const unsigned short* support, int V, const double* intr, const double* w2c, int height, int width,
-                     const unsigned int* bits, const unsigned int* best, int window, int margin, int accumulate,
-                     unsigned short* wins);
+hipError_t launch_ray_claims(hipStream_t s, SeedGrid g, SeedViews views, int M, const int* index,
+                             const unsigned short* support, int clear, unsigned int* best);
+void launch_ray_wins(hipStream_t s, SeedGrid g, SeedViews views, int M, const int* index, const unsigned short* support,
+                     const unsigned int* best, int window, int margin, int accumulate, unsigned short* wins);
 
 // edge_support.hip
 void launch_edge_support(hipStream_t s, int E, int P, const float* points, const int* offsets, int V, const double* intr,

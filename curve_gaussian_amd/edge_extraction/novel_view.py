@@ -20,6 +20,8 @@ import numpy as np
 import torch
 
 from .. import _lib as L
+from ..ops.edge_score import _cameras, cameras_on
+from ..ops.view_chunks import camera_arrays, view_chunks
 from ..scene import colmap_io
 from ..scene.dataset_io import focal2fov, fov2focal
 from .abc import pred_points_and_directions
@@ -99,13 +101,6 @@ def colmap_cameras(scan_dir):
     return cams
 
 
-def camera_arrays(cams):
-    """(intrinsics [V,4] = (fx, fy, cx, cy), w2c [V,3,4] = [R | T]) float64 host arrays of a list of cameras."""
-    intr = np.array([[c.fx, c.fy, c.cx, c.cy] for c in cams], np.float64).reshape(-1, 4)
-    w2c = np.array([np.concatenate([c.R, c.T[:, None]], 1) for c in cams], np.float64).reshape(-1, 3, 4)
-    return intr, w2c
-
-
 # ------------------------------------------------------------------------------------------------ per-edge colours
 def _hls_palette(n, h=0.01, l=0.6, s=0.65):
     """seaborn.color_palette('hls', n)."""
@@ -152,19 +147,6 @@ def edge_point_colors(pred, seed=0):
 
 
 # ------------------------------------------------------------------------------------------------ GPU ops
-def _cameras_on(dev, intrinsics, w2c):
-    def host(x):
-        if isinstance(x, torch.Tensor):
-            x = x.detach().cpu().numpy()
-        return np.asarray(x, dtype=np.float64)
-    K, M = host(intrinsics), host(w2c)
-    V = K.shape[0] if K.ndim == 2 else -1
-    if K.shape != (V, 4) or M.size != 12 * V:
-        raise L.CurveGSError(f"intrinsics must be [V,4] and w2c [V,3,4] (got {K.shape}, {M.shape})")
-    return (V, torch.from_numpy(np.ascontiguousarray(K)).to(dev),
-            torch.from_numpy(np.ascontiguousarray(M.reshape(V, 12))).to(dev))
-
-
 def _points(points, name="points"):
     L.require_gpu_tensor(points, name)
     if points.dim() != 2 or points.shape[1] != 3:
@@ -178,8 +160,9 @@ def project_points(points, intrinsics, w2c, height, width):
     (fx, fy, cx, cy) and w2c [V,3,4] float64 host arrays or tensors (``cgs_project_points``)."""
     pts = _points(points)
     dev = pts.device
+    V, K, M = _cameras(intrinsics, w2c, L.CurveGSError)
     with L.device_guard(dev):
-        V, K, M = _cameras_on(dev, intrinsics, w2c)
+        K, M = cameras_on(dev, K, M)
         P = pts.shape[0]
         uv = torch.empty((V, P, 2), dtype=torch.float64, device=dev)
         rc = L.load().cgs_project_points(P, L.ptr(pts), V, L.ptr(K), L.ptr(M), int(height), int(width), L.ptr(uv),
@@ -202,8 +185,9 @@ def render_points(points, colors, intrinsics, w2c, height, width, alpha=ALPHA, b
         raise L.CurveGSError(f"colors must be [P,3] on {dev} (got {tuple(col.shape)} on {col.device})")
     bg = np.ascontiguousarray(np.asarray(background, np.float64).reshape(3))
     lib = L.load()
+    V, K, M = _cameras(intrinsics, w2c, L.CurveGSError)
     with L.device_guard(dev):
-        V, K, M = _cameras_on(dev, intrinsics, w2c)
+        K, M = cameras_on(dev, K, M)
         P, H, W = pts.shape[0], int(height), int(width)
         out = torch.empty((V, max(H, 0), max(W, 0), 3), dtype=torch.float32, device=dev)
         kept = torch.zeros((V,), dtype=torch.int32, device=dev)
@@ -240,26 +224,19 @@ def render_views(points, colors, cams, out_dir, file_names, device=None, alpha=A
     pts = torch.from_numpy(np.ascontiguousarray(points, np.float32).reshape(-1, 3)).to(dev)
     col = torch.from_numpy(np.ascontiguousarray(colors, np.float32).reshape(-1, 3)).to(dev)
     stats = {"views": len(cams), "written": 0, "gpu_s": 0.0, "write_s": 0.0}
-    by_size = {}
-    for v, c in enumerate(cams):
-        by_size.setdefault((c.height, c.width), []).append(v)
     os.makedirs(out_dir, exist_ok=True)
     with ThreadPoolExecutor(max_workers=MAX_WRITERS) as pool:
-        for (H, W), idx in by_size.items():
-            per = max(1, OUTPUT_BUDGET // (H * W * 12))
-            for b in range(0, len(idx), per):
-                sel = idx[b:b + per]
-                intr, w2c = camera_arrays([cams[v] for v in sel])
-                t0 = time.perf_counter()
-                img, kept = render_points(pts, col, intr, w2c, H, W, alpha, background, return_kept=True)
-                u8 = torch.round(img * 255.0).clamp_(0, 255).to(torch.uint8).cpu().numpy()
-                kept = kept.cpu().numpy()
-                t1 = time.perf_counter()
-                jobs = [(os.path.join(out_dir, file_names[v]), u8[k]) for k, v in enumerate(sel) if kept[k] > 0]
-                _write_images(jobs, pool)
-                stats["gpu_s"] += t1 - t0
-                stats["write_s"] += time.perf_counter() - t1
-                stats["written"] += len(jobs)
+        for H, W, sel, intr, w2c in view_chunks(cams, 12, OUTPUT_BUDGET):   # 12 bytes: a float32 RGB pixel
+            t0 = time.perf_counter()
+            img, kept = render_points(pts, col, intr, w2c, H, W, alpha, background, return_kept=True)
+            u8 = torch.round(img * 255.0).clamp_(0, 255).to(torch.uint8).cpu().numpy()
+            kept = kept.cpu().numpy()
+            t1 = time.perf_counter()
+            jobs = [(os.path.join(out_dir, file_names[v]), u8[k]) for k, v in enumerate(sel) if kept[k] > 0]
+            _write_images(jobs, pool)
+            stats["gpu_s"] += t1 - t0
+            stats["write_s"] += time.perf_counter() - t1
+            stats["written"] += len(jobs)
     return stats
 
 

@@ -25,9 +25,10 @@ import numpy as np
 import torch
 
 from ..ops import edge_score as ES
+from ..ops.view_chunks import check_edge_maps, detected_lut, detected_masks, view_chunks
 from ..scene.dataset_io import fov2focal
 from .abc import pred_points_and_directions
-from .novel_view import NovelViewCamera, camera_arrays, replica_scans
+from .novel_view import NovelViewCamera, replica_scans
 from .para_edge import EDGE_MAX_THRESHOLD, edge_map_paths, get_edge_maps
 
 log = logging.getLogger(__name__)
@@ -35,19 +36,6 @@ log = logging.getLogger(__name__)
 SAMPLE_RESOLUTION = 0.0005   # the novel views' Replica value (eval_replica.py:113)
 LAYOUTS = ("emap", "colmap")
 SCORE_FILE = "reprojection_score.json"
-
-
-def detected_lut(detector, edge_threshold):
-    """bool [256]: is a stored byte u a detected edge pixel?  e > edge_threshold with e = 1 - u/255.0 (DexiNed) or u/255.0
-    (PidiNet) in float64, the conversions of para_edge / cgs_edge_visibility."""
-    u = np.arange(256, dtype=np.float64)
-    if detector == "DexiNed":
-        e = 1 - u / 255.0
-    elif detector == "PidiNet":
-        e = u / 255.0
-    else:
-        raise ValueError(f"Unknown detector: {detector}")
-    return e > float(edge_threshold)
 
 
 def _pred_points(pred, sample_resolution):
@@ -72,14 +60,7 @@ def score_edges(pred, cameras, edge_maps_u8, detector, tolerances_px=(1, 2, 4), 
     tolerances_px = [float(t) for t in tolerances_px]
     ES.tolerances_squared(tolerances_px)
     lut = detected_lut(detector, edge_threshold)
-    cameras = list(cameras)
-    maps = [np.asarray(m) for m in edge_maps_u8]
-    if len(maps) != len(cameras):
-        raise ValueError(f"score_edges: {len(cameras)} cameras and {len(maps)} edge maps")
-    for c, m in zip(cameras, maps):
-        if m.dtype != np.uint8 or m.shape != (c.height, c.width):
-            raise ValueError(f"score_edges: the edge map of {c.name} must be uint8 [{c.height},{c.width}] (got {m.dtype} "
-                             f"{m.shape})")
+    cameras, maps = check_edge_maps("score_edges", cameras, edge_maps_u8)
     pts = _pred_points(pred, sample_resolution)
     if backend == "gpu":
         device = ES._device_for([], "score_edges", device)
@@ -87,25 +68,18 @@ def score_edges(pred, cameras, edge_maps_u8, detector, tolerances_px=(1, 2, 4), 
     else:
         pts_b = pts
     budget = ES.BYTE_BUDGET if budget_bytes is None else int(budget_bytes)
-    by_size = {}
-    for v, c in enumerate(cameras):
-        by_size.setdefault((c.height, c.width), []).append(v)
     V, n_tol = len(cameras), len(tolerances_px)
     per_view = {"n_pred": np.zeros(V, np.int64), "n_det": np.zeros(V, np.int64), "pred_hits": np.zeros((V, n_tol), np.int64),
                 "det_hits": np.zeros((V, n_tol), np.int64), "sum_pred_to_det": np.zeros(V, np.float64),
                 "sum_det_to_pred": np.zeros(V, np.float64), "both_nonempty": np.zeros(V, bool)}
     kept = np.zeros(V, np.int64)
-    for (H, W), idx in by_size.items():
-        per = max(1, budget // (ES.BYTES_PER_PIXEL * H * W))
-        for b in range(0, len(idx), per):
-            sel = idx[b:b + per]
-            intr, w2c = camera_arrays([cameras[v] for v in sel])
-            pm, k = ES.point_masks(pts_b, intr, w2c, H, W, backend=backend, device=device, return_kept=True)
-            dm = torch.from_numpy(lut[np.stack([maps[v] for v in sel])].astype(np.uint8))
-            res = ES.score_masks(pm, dm, tolerances_px, backend=backend, device=device, budget_bytes=budget)
-            kept[sel] = k.cpu().numpy()
-            for name, a in per_view.items():
-                a[sel] = res[name].numpy()
+    for H, W, sel, intr, w2c in view_chunks(cameras, ES.BYTES_PER_PIXEL, budget):
+        pm, k = ES.point_masks(pts_b, intr, w2c, H, W, backend=backend, device=device, return_kept=True)
+        res = ES.score_masks(pm, detected_masks(lut, maps, sel), tolerances_px, backend=backend, device=device,
+                             budget_bytes=budget)
+        kept[sel] = k.cpu().numpy()
+        for name, a in per_view.items():
+            a[sel] = res[name].numpy()
     agg = ES.aggregate_scores(tolerances_px, **per_view)
     rows = []
     for v, c in enumerate(cameras):

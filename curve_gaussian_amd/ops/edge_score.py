@@ -32,6 +32,7 @@ import numpy as np
 import torch
 
 from .. import _lib as L
+from .view_chunks import check_budget
 
 SCORE_BACKENDS = ("gpu", "host")
 EDT_INF = L.EDT_INF
@@ -87,18 +88,23 @@ def tolerances_squared(tolerances_px):
 
 
 # ------------------------------------------------------------------------------------------------ point masks
-def _host64(x):
-    if torch.is_tensor(x):
-        x = x.detach().cpu().numpy()
-    return np.asarray(x, dtype=np.float64)
+def _host(x):
+    """A tensor (any device) or an array as a numpy array."""
+    return x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)
 
 
-def _cameras(intrinsics, w2c):
-    K, M = _host64(intrinsics), _host64(w2c)
+def _cameras(intrinsics, w2c, error=ValueError):
+    """(V, K [V,4], M [V,12]) contiguous float64 host arrays of a camera stack, checked; ``error``: what a bad shape raises."""
+    K, M = (np.asarray(_host(x), dtype=np.float64) for x in (intrinsics, w2c))
     V = K.shape[0] if K.ndim == 2 else -1
     if K.shape != (V, 4) or M.size != 12 * V:
-        raise ValueError(f"intrinsics must be [V,4] and w2c [V,3,4] (got {K.shape}, {M.shape})")
+        raise error(f"intrinsics must be [V,4] and w2c [V,3,4] (got {K.shape}, {M.shape})")
     return V, np.ascontiguousarray(K), np.ascontiguousarray(M.reshape(V, 12))
+
+
+def cameras_on(dev, K, M):
+    """The checked host arrays of ``_cameras`` as tensors on ``dev``."""
+    return torch.from_numpy(K).to(dev), torch.from_numpy(M).to(dev)
 
 
 def project_points_host(points, K, M, height, width):
@@ -147,7 +153,7 @@ def point_masks(points, intrinsics, w2c, height, width, backend="gpu", device=No
         mask = torch.empty((V, height, width), dtype=torch.uint8, device=dev)
         kept = torch.empty((V,), dtype=torch.int32, device=dev)
         if V > 0:
-            Kd, Md = torch.from_numpy(K).to(dev), torch.from_numpy(M).to(dev)
+            Kd, Md = cameras_on(dev, K, M)
             rc = L.load().cgs_point_mask(int(pts.shape[0]), L.ptr(pts), V, L.ptr(Kd), L.ptr(Md), height, width, L.ptr(mask),
                                          L.ptr(kept), L.raw_stream(dev))
             L.check(rc, "cgs_point_mask")
@@ -203,7 +209,7 @@ def edt_squared(masks, backend="gpu", device=None):
     masks = _as_masks(masks, "edt_squared: masks")
     V, H, W = (int(s) for s in masks.shape)
     if backend == "host":
-        m = masks.detach().cpu().numpy()
+        m = _host(masks)
         out = np.empty((V, H, W), np.int32)
         for v in range(V):
             out[v] = edt_squared_host(m[v])
@@ -294,9 +300,7 @@ def score_masks(pred_masks, det_masks, tolerances_px=(1, 2, 4), backend="gpu", d
     det = _as_masks(det_masks, "score_masks: det_masks")
     if pred.shape != det.shape:
         raise ValueError(f"score_masks: pred_masks {tuple(pred.shape)} and det_masks {tuple(det.shape)} differ in shape")
-    budget = BYTE_BUDGET if budget_bytes is None else int(budget_bytes)
-    if budget <= 0:
-        raise ValueError(f"score_masks: budget_bytes must be positive (got {budget})")
+    budget = check_budget("score_masks", budget_bytes, BYTE_BUDGET)
     V, H, W = (int(s) for s in pred.shape)
     per = max(1, budget // (BYTES_PER_PIXEL * H * W)) if V else 1
     dev = _device_for([pred, det], "score_masks", device) if backend == "gpu" else None
@@ -304,7 +308,7 @@ def score_masks(pred_masks, det_masks, tolerances_px=(1, 2, 4), backend="gpu", d
     for v0 in range(0, V, per):
         p, q = pred[v0:v0 + per], det[v0:v0 + per]
         if backend == "host":
-            p, q = p.detach().cpu().numpy(), q.detach().cpu().numpy()
+            p, q = _host(p), _host(q)
             pd2, qd2 = edt_squared(p, "host").numpy(), edt_squared(q, "host").numpy()
             parts.append(_reduce_host(p, q, pd2, qd2, tol2))
         else:

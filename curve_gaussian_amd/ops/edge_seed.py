@@ -73,6 +73,7 @@ import torch
 from .. import _lib as L
 from ..edge_extraction.para_edge import EDGE_MAX_THRESHOLD
 from . import edge_score as ES
+from .view_chunks import check_budget, check_edge_maps, detected_lut, detected_masks, view_chunks
 
 SEED_BACKENDS = ES.SCORE_BACKENDS
 MAX_VIEWS = L.SEED_MAX_VIEWS
@@ -98,6 +99,34 @@ def _check_backend(backend):
 
 def bits_stride(width):
     return (int(width) + 31) // 32
+
+
+def _check_bits(name, bits, V, height, width):
+    """The packed masks of V views as a tensor: int32 [V,height,ceil(width/32)]."""
+    if not torch.is_tensor(bits):
+        bits = torch.from_numpy(np.ascontiguousarray(bits))
+    if bits.dtype != torch.int32 or tuple(bits.shape) != (V, height, bits_stride(width)):
+        raise ValueError(f"{name}: bits must be int32 [{V},{height},{bits_stride(width)}] (got {bits.dtype} "
+                         f"{tuple(bits.shape)})")
+    return bits
+
+
+def _check_window(name, window):
+    if int(window) != window or not (0 <= int(window) <= SEED_MAX_WINDOW):
+        raise ValueError(f"{name} must be an integer in [0, {SEED_MAX_WINDOW}] (got {window})")
+    return int(window)
+
+
+def _check_margin(name, margin):
+    if int(margin) != margin or not (0 <= int(margin) <= MAX_SUPPORT):
+        raise ValueError(f"{name} must be an integer in [0, {MAX_SUPPORT}] (got {margin})")
+    return int(margin)
+
+
+def _check_ratio(name, ratio):
+    if not (0.0 <= float(ratio) <= 1.0):
+        raise ValueError(f"{name} must lie in [0, 1] (got {ratio})")
+    return float(ratio)
 
 
 # ------------------------------------------------------------------------------------------------ near bits
@@ -134,8 +163,7 @@ def near_bits(dist2, tol_px, backend="gpu", device=None):
 def unpack_bits(bits, width):
     """The inverse of the packing: int32 [V,H,ceil(width/32)] words -> (near bool [V,H,width], padding bool
     [V,H,32 ceil(width/32) - width]) numpy arrays."""
-    words = bits.detach().cpu().numpy() if torch.is_tensor(bits) else np.asarray(bits)
-    words = np.ascontiguousarray(words).view(np.uint32).astype("<u4")
+    words = np.ascontiguousarray(ES._host(bits)).view(np.uint32).astype("<u4")
     flat = np.unpackbits(words.view(np.uint8), axis=-1, bitorder="little").astype(bool)
     return flat[..., :int(width)], flat[..., int(width):]
 
@@ -158,6 +186,10 @@ def _grid(bounds, dims):
     return lo, hi, dims, step
 
 
+def _grid_c(lo, step):
+    return (C.c_double * 3)(*lo), (C.c_double * 3)(*step)
+
+
 def _centres(lo, dims, step, start, stop):
     return _centres_of(lo, dims, step, np.arange(start, stop, dtype=np.int64))
 
@@ -173,19 +205,24 @@ def voxel_centres(bounds, dims, start=0, stop=None):
     return _centres(lo, dims, step, start, dims[0] * dims[1] * dims[2] if stop is None else stop)
 
 
+def _pixels_host(pts, K, M, words, H, W, v):
+    """(at, px, py, bit): the positions among the centres ``pts`` that view v keeps, their pixels and the pixels' near bits
+    in the packed uint32 ``words``."""
+    pu, pv, keep = ES.project_points_host(pts, K[v:v + 1], M[v:v + 1], H, W)
+    at = np.nonzero(keep[0])[0]
+    px, py = np.floor(pu[0][at]).astype(np.int64), np.floor(pv[0][at]).astype(np.int64)
+    return at, px, py, (words[v, py, px >> 5] >> (px & 31).astype(np.uint32)) & np.uint32(1)
+
+
 def _votes_host(lo, dims, step, K, M, words, H, W, seen, hit):
     n = dims[0] * dims[1] * dims[2]
     words = words.view(np.uint32)
     for s0 in range(0, n, HOST_SLAB):
-        s1 = min(n, s0 + HOST_SLAB)
-        pts = _centres(lo, dims, step, s0, s1)
+        pts = _centres(lo, dims, step, s0, min(n, s0 + HOST_SLAB))
         for v in range(K.shape[0]):   # one view at a time: [slab] temporaries
-            pu, pv, keep = ES.project_points_host(pts, K[v:v + 1], M[v:v + 1], H, W)
-            idx = np.nonzero(keep[0])[0]
-            px, py = np.floor(pu[0][idx]).astype(np.int64), np.floor(pv[0][idx]).astype(np.int64)
-            bit = (words[v, py, px >> 5] >> (px & 31).astype(np.uint32)) & np.uint32(1)
-            seen[s0 + idx] += np.uint16(1)
-            hit[s0 + idx] += bit.astype(np.uint16)
+            at, _, _, bit = _pixels_host(pts, K, M, words, H, W, v)
+            seen[s0 + at] += np.uint16(1)
+            hit[s0 + at] += bit.astype(np.uint16)
 
 
 def voxel_votes(bounds, dims, intrinsics, w2c, bits, height, width, counts=None, backend="gpu", device=None):
@@ -201,11 +238,7 @@ def voxel_votes(bounds, dims, intrinsics, w2c, bits, height, width, counts=None,
     V, K, M = ES._cameras(intrinsics, w2c)
     if V > MAX_VIEWS:
         raise ValueError(f"voxel_votes: at most {MAX_VIEWS} views (got {V})")
-    if not torch.is_tensor(bits):
-        bits = torch.from_numpy(np.ascontiguousarray(bits))
-    if bits.dtype != torch.int32 or tuple(bits.shape) != (V, height, bits_stride(width)):
-        raise ValueError(f"voxel_votes: bits must be int32 [{V},{height},{bits_stride(width)}] (got {bits.dtype} "
-                         f"{tuple(bits.shape)})")
+    bits = _check_bits("voxel_votes", bits, V, height, width)
     n = dims[0] * dims[1] * dims[2]
     if counts is not None:
         for c in counts:
@@ -227,11 +260,9 @@ def voxel_votes(bounds, dims, intrinsics, w2c, bits, height, width, counts=None,
             seen = torch.empty(n, dtype=torch.uint16, device=dev)
             hit = torch.empty(n, dtype=torch.uint16, device=dev)
         bits = bits.to(dev).contiguous()
-        Kd, Md = torch.from_numpy(K).to(dev), torch.from_numpy(M).to(dev)
-        lo_c, step_c = (C.c_double * 3)(*lo), (C.c_double * 3)(*step)
-        rc = L.load().cgs_voxel_votes(dims[0], dims[1], dims[2], C.cast(lo_c, C.c_void_p), C.cast(step_c, C.c_void_p), V,
-                                      L.ptr(Kd), L.ptr(Md), height, width, L.ptr(bits), 1 if counts is not None else 0,
-                                      L.ptr(seen), L.ptr(hit), L.raw_stream(dev))
+        (Kd, Md), (lo_c, step_c) = ES.cameras_on(dev, K, M), _grid_c(lo, step)
+        rc = L.load().cgs_voxel_votes(*dims, lo_c, step_c, V, L.ptr(Kd), L.ptr(Md), height, width, L.ptr(bits),
+                                      1 if counts is not None else 0, L.ptr(seen), L.ptr(hit), L.raw_stream(dev))
         L.check(rc, "cgs_voxel_votes")
     return seen, hit
 
@@ -239,14 +270,11 @@ def voxel_votes(bounds, dims, intrinsics, w2c, bits, height, width, counts=None,
 # ------------------------------------------------------------------------------------------------ selection and thinning
 def need_table(min_ratio, views):
     """int64 [views + 1]: need[s] = ceil(min_ratio * s), in float64."""
-    min_ratio = float(min_ratio)
-    if not (0.0 <= min_ratio <= 1.0):
-        raise ValueError(f"min_ratio must lie in [0, 1] (got {min_ratio})")
-    return np.ceil(min_ratio * np.arange(int(views) + 1, dtype=np.float64)).astype(np.int64)
+    return np.ceil(_check_ratio("min_ratio", min_ratio) * np.arange(int(views) + 1, dtype=np.float64)).astype(np.int64)
 
 
 def _counts_host(x):
-    return (x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)).astype(np.int64).reshape(-1)
+    return ES._host(x).astype(np.int64).reshape(-1)
 
 
 def select_voxels(seen, hit, min_views, min_ratio):
@@ -267,7 +295,7 @@ def thin_to_seeds(keep, hit, bounds, dims, cell, max_seeds, return_centres=False
     cell, max_seeds = int(cell), int(max_seeds)
     if cell < 1 or max_seeds < 1:
         raise ValueError(f"cell and max_seeds must be positive (got {cell}, {max_seeds})")
-    keep = np.asarray(keep.detach().cpu().numpy() if torch.is_tensor(keep) else keep).reshape(-1).astype(bool)
+    keep = ES._host(keep).reshape(-1).astype(bool)
     hit = _counts_host(hit)
     if keep.size != nx * ny * nz or hit.size != keep.size:
         raise ValueError(f"thin_to_seeds: keep and hit must hold {nx * ny * nz} voxels")
@@ -299,7 +327,7 @@ def thin_to_seeds(keep, hit, bounds, dims, cell, max_seeds, return_centres=False
 
 # ------------------------------------------------------------------------------------------------ ray-exclusive claims
 def _list_index(name, index, n):
-    idx = index.detach().cpu().numpy() if torch.is_tensor(index) else np.asarray(index)
+    idx = ES._host(index)
     if idx.size == 0:
         return np.zeros(0, np.int32)
     if idx.ndim != 1 or idx.dtype.kind not in "iu":
@@ -331,13 +359,9 @@ def _ray_args(name, bounds, dims, index, support, intrinsics, w2c, bits, height,
     V, K, M = ES._cameras(intrinsics, w2c)
     if V > MAX_VIEWS:
         raise ValueError(f"{name}: at most {MAX_VIEWS} views (got {V})")
-    if not torch.is_tensor(bits):
-        bits = torch.from_numpy(np.ascontiguousarray(bits))
-    if bits.dtype != torch.int32 or tuple(bits.shape) != (V, height, bits_stride(width)):
-        raise ValueError(f"{name}: bits must be int32 [{V},{height},{bits_stride(width)}] (got {bits.dtype} "
-                         f"{tuple(bits.shape)})")
+    bits = _check_bits(name, bits, V, height, width)
     idx = _list_index(name, index, dims[0] * dims[1] * dims[2])
-    sup = support.detach().cpu().numpy() if torch.is_tensor(support) else np.asarray(support)
+    sup = ES._host(support)
     if sup.size == 0:
         sup = np.zeros(0, np.uint16)
     if sup.ndim != 1 or sup.dtype.kind not in "iu" or sup.shape != idx.shape:
@@ -350,10 +374,7 @@ def _ray_args(name, bounds, dims, index, support, intrinsics, w2c, bits, height,
 
 def _hits_host(pts, K, M, words, H, W, v):
     """(the positions among the centres ``pts`` that hit in view v, their px, their py): the rule of ``_votes_host``."""
-    pu, pv, keep = ES.project_points_host(pts, K[v:v + 1], M[v:v + 1], H, W)
-    at = np.nonzero(keep[0])[0]
-    px, py = np.floor(pu[0][at]).astype(np.int64), np.floor(pv[0][at]).astype(np.int64)
-    bit = (words[v, py, px >> 5] >> (px & 31).astype(np.uint32)) & np.uint32(1)
+    at, px, py, bit = _pixels_host(pts, K, M, words, H, W, v)
     near = bit != 0
     return at[near], px[near], py[near]
 
@@ -391,12 +412,10 @@ def ray_claims(bounds, dims, index, support, intrinsics, w2c, bits, height, widt
         elif best.device != dev:
             raise ValueError(f"ray_claims: best must be on {dev}")
         bits = bits.to(dev).contiguous()
-        Kd, Md = torch.from_numpy(K).to(dev), torch.from_numpy(M).to(dev)
+        (Kd, Md), (lo_c, step_c) = ES.cameras_on(dev, K, M), _grid_c(lo, step)
         idx_d, sup_d = torch.from_numpy(idx).to(dev), torch.from_numpy(sup).to(dev)
-        lo_c, step_c = (C.c_double * 3)(*lo), (C.c_double * 3)(*step)
-        rc = L.load().cgs_ray_claims(dims[0], dims[1], dims[2], C.cast(lo_c, C.c_void_p), C.cast(step_c, C.c_void_p),
-                                     idx.size, L.ptr(idx_d), L.ptr(sup_d), V, L.ptr(Kd), L.ptr(Md), height, width, L.ptr(bits),
-                                     1 if clear else 0, L.ptr(best), L.raw_stream(dev))
+        rc = L.load().cgs_ray_claims(*dims, lo_c, step_c, idx.size, L.ptr(idx_d), L.ptr(sup_d), V, L.ptr(Kd), L.ptr(Md),
+                                     height, width, L.ptr(bits), 1 if clear else 0, L.ptr(best), L.raw_stream(dev))
         L.check(rc, "cgs_ray_claims")
     return best
 
@@ -411,11 +430,7 @@ def ray_wins(bounds, dims, index, support, intrinsics, w2c, bits, best, height, 
     _check_backend(backend)
     lo, dims, step, height, width, V, K, M, bits, idx, sup = _ray_args("ray_wins", bounds, dims, index, support, intrinsics,
                                                                        w2c, bits, height, width)
-    if int(window) != window or not (0 <= int(window) <= SEED_MAX_WINDOW):
-        raise ValueError(f"ray_wins: the window must be an integer in [0, {SEED_MAX_WINDOW}] (got {window})")
-    if int(margin) != margin or not (0 <= int(margin) <= MAX_SUPPORT):
-        raise ValueError(f"ray_wins: the margin must be an integer in [0, {MAX_SUPPORT}] (got {margin})")
-    window, margin = int(window), int(margin)
+    window, margin = _check_window("ray_wins: the window", window), _check_margin("ray_wins: the margin", margin)
     if not torch.is_tensor(best):
         best = torch.from_numpy(np.ascontiguousarray(best))
     if best.dtype != torch.int32 or tuple(best.shape) != (V, height, width):
@@ -452,13 +467,11 @@ def ray_wins(bounds, dims, index, support, intrinsics, w2c, bits, best, height, 
         else:
             wins = torch.empty(idx.size, dtype=torch.uint16, device=dev)
         bits, best = bits.to(dev).contiguous(), best.to(dev).contiguous()
-        Kd, Md = torch.from_numpy(K).to(dev), torch.from_numpy(M).to(dev)
+        (Kd, Md), (lo_c, step_c) = ES.cameras_on(dev, K, M), _grid_c(lo, step)
         idx_d, sup_d = torch.from_numpy(idx).to(dev), torch.from_numpy(sup).to(dev)
-        lo_c, step_c = (C.c_double * 3)(*lo), (C.c_double * 3)(*step)
-        rc = L.load().cgs_ray_wins(dims[0], dims[1], dims[2], C.cast(lo_c, C.c_void_p), C.cast(step_c, C.c_void_p), idx.size,
-                                   L.ptr(idx_d), L.ptr(sup_d), V, L.ptr(Kd), L.ptr(Md), height, width, L.ptr(bits),
-                                   L.ptr(best), window, margin, 1 if counts is not None else 0, L.ptr(wins),
-                                   L.raw_stream(dev))
+        rc = L.load().cgs_ray_wins(*dims, lo_c, step_c, idx.size, L.ptr(idx_d), L.ptr(sup_d), V, L.ptr(Kd), L.ptr(Md),
+                                   height, width, L.ptr(bits), L.ptr(best), window, margin, 1 if counts is not None else 0,
+                                   L.ptr(wins), L.raw_stream(dev))
         L.check(rc, "cgs_ray_wins")
     return wins
 
@@ -471,8 +484,7 @@ def select_exclusive(wins, hit, win_ratio):
         raise ValueError("select_exclusive: wins and hit differ in shape")
     if (wins < 0).any() or (hit < 0).any():
         raise ValueError("select_exclusive: wins and hit must not be negative")
-    if not (0.0 <= float(win_ratio) <= 1.0):
-        raise ValueError(f"select_exclusive: win_ratio must lie in [0, 1] (got {win_ratio})")
+    _check_ratio("select_exclusive: win_ratio", win_ratio)
     need = need_table(win_ratio, int(hit.max()) if hit.size else 0)
     return wins >= need[hit]
 
@@ -484,7 +496,7 @@ def keep_bits(keep, dims):
     nx, ny, nz = (int(d) for d in dims)
     if min(nx, ny, nz) < 1:
         raise ValueError(f"dims must be three positive integers (got {(nx, ny, nz)})")
-    keep = np.asarray(keep.detach().cpu().numpy() if torch.is_tensor(keep) else keep).reshape(-1).astype(bool)
+    keep = ES._host(keep).reshape(-1).astype(bool)
     if keep.size != nx * ny * nz:
         raise ValueError(f"keep_bits: keep must hold {nx * ny * nz} voxels (got {keep.size})")
     stride = bits_stride(nx)
@@ -540,7 +552,7 @@ def voxel_moments(bits, dims, centres, radius, backend="gpu", device=None):
     want = (dims[2], dims[1], bits_stride(dims[0]))
     if bits.dtype != torch.int32 or tuple(bits.shape) != want:
         raise ValueError(f"voxel_moments: bits must be int32 {list(want)} (got {bits.dtype} {tuple(bits.shape)})")
-    cen = centres.detach().cpu().numpy() if torch.is_tensor(centres) else np.asarray(centres)
+    cen = ES._host(centres)
     if cen.size == 0:
         cen = cen.reshape(0, 3)
     if cen.ndim != 2 or cen.shape[1] != 3 or cen.dtype.kind not in "iu":
@@ -567,7 +579,7 @@ def seed_directions(moments, min_support=DIR_MIN_SUPPORT, min_linearity=DIR_MIN_
     """moments: int32 [N,10] (``voxel_moments``; tensor or array).  Returns (directions float64 [N,3] -- unit rows, zero
     rows for undirected seeds --, directed bool [N], linearity float64 [N]) by the direction rule of the module docstring.
     Host float64 code on both back ends."""
-    mom = (moments.detach().cpu().numpy() if torch.is_tensor(moments) else np.asarray(moments)).astype(np.int64)
+    mom = ES._host(moments).astype(np.int64)
     if mom.ndim != 2 or mom.shape[1] != MOMENT_VALUES:
         raise ValueError(f"seed_directions: moments must be [N,{MOMENT_VALUES}]")
     N = mom.shape[0]
@@ -629,60 +641,39 @@ def seed_points(cameras, edge_maps_u8, detector, bounds, grid=128, tol_px=2, min
     ``exclusive=True``: between the selection and the thinning the kept voxels claim the pixels they hit and only those
     that win their claims stay (``voxel_support``, ``ray_claims``, ``ray_wins(excl_window, excl_margin)``,
     ``select_exclusive(excl_win_ratio)``; module docstring).  A second sweep over the views does it chunk by chunk: the
-    packed near bits of the first sweep stay where they were made (one bit per pixel), ``best`` costs
+    packed near bits of the first sweep are kept, view by view (one bit per pixel), ``best`` costs
     EXCL_BYTES_PER_PIXEL bytes per pixel of ``budget_bytes``, and the wins accumulate across the chunks, so the result
     does not depend on the chunking.  The thinning, the keep bits and the moments see the surviving mask; info
     additionally holds "exclusive_voxels", the voxels that remain ("kept_voxels" keeps its meaning).  These three
     defaults are untuned too; there is still no depth."""
-    from ..edge_extraction.novel_view import camera_arrays
-    from ..edge_extraction.reprojection import detected_lut
     _check_backend(backend)
     lut = detected_lut(detector, edge_threshold)
-    cameras = list(cameras)
-    maps = [np.asarray(m) for m in edge_maps_u8]
-    if len(maps) != len(cameras):
-        raise ValueError(f"seed_points: {len(cameras)} cameras and {len(maps)} edge maps")
+    cameras, maps = check_edge_maps("seed_points", cameras, edge_maps_u8)
     if len(cameras) > MAX_VIEWS:
         raise ValueError(f"seed_points: at most {MAX_VIEWS} views (got {len(cameras)})")
-    for c, m in zip(cameras, maps):
-        if m.dtype != np.uint8 or m.shape != (c.height, c.width):
-            raise ValueError(f"seed_points: the edge map of {c.name} must be uint8 [{c.height},{c.width}] (got {m.dtype} "
-                             f"{m.shape})")
     ES.tolerances_squared([tol_px])
     if directions and (int(dir_radius) != dir_radius or not (1 <= int(dir_radius) <= SEED_MAX_RADIUS)):
         raise ValueError(f"seed_points: dir_radius must be an integer in [1, {SEED_MAX_RADIUS}] (got {dir_radius})")
     if exclusive:
-        if int(excl_window) != excl_window or not (0 <= int(excl_window) <= SEED_MAX_WINDOW):
-            raise ValueError(f"seed_points: excl_window must be an integer in [0, {SEED_MAX_WINDOW}] (got {excl_window})")
-        if int(excl_margin) != excl_margin or not (0 <= int(excl_margin) <= MAX_SUPPORT):
-            raise ValueError(f"seed_points: excl_margin must be an integer in [0, {MAX_SUPPORT}] (got {excl_margin})")
-        if not (0.0 <= float(excl_win_ratio) <= 1.0):
-            raise ValueError(f"seed_points: excl_win_ratio must lie in [0, 1] (got {excl_win_ratio})")
+        _check_window("seed_points: excl_window", excl_window)
+        _check_margin("seed_points: excl_margin", excl_margin)
+        _check_ratio("seed_points: excl_win_ratio", excl_win_ratio)
     dims = grid_dims(bounds, grid)
     _grid(bounds, dims)
     need_table(min_ratio, 0)
-    budget = BYTE_BUDGET if budget_bytes is None else int(budget_bytes)
-    if budget <= 0:
-        raise ValueError(f"seed_points: budget_bytes must be positive (got {budget})")
+    budget = check_budget("seed_points", budget_bytes, BYTE_BUDGET)
     if backend == "gpu":
         device = ES._device_for([], "seed_points", device)
     n = dims[0] * dims[1] * dims[2]
-    by_size = {}
-    for v, c in enumerate(cameras):
-        by_size.setdefault((c.height, c.width), []).append(v)
-    counts, chunks = None, []   # chunks: (H, W, intrinsics, w2c, near bits) of the first sweep, for the second
-    for (H, W), idx in by_size.items():
-        per = max(1, budget // (BYTES_PER_PIXEL * H * W))
-        for b in range(0, len(idx), per):
-            sel = idx[b:b + per]
-            intr, w2c = camera_arrays([cameras[v] for v in sel])
-            det = torch.from_numpy(lut[np.stack([maps[v] for v in sel])].astype(np.uint8))
-            d2 = ES.edt_squared(det, backend=backend, device=device)
-            bits = near_bits(d2, tol_px, backend=backend, device=device)
-            del d2
-            counts = voxel_votes(bounds, dims, intr, w2c, bits, H, W, counts=counts, backend=backend, device=device)
-            if exclusive:
-                chunks.append((H, W, intr, w2c, bits))
+    on = {"backend": backend, "device": device}
+    counts, near = None, {}   # near: every view's near bits of the first sweep, for the second
+    for H, W, sel, intr, w2c in view_chunks(cameras, BYTES_PER_PIXEL, budget):
+        d2 = ES.edt_squared(detected_masks(lut, maps, sel), **on)
+        bits = near_bits(d2, tol_px, **on)
+        del d2
+        counts = voxel_votes(bounds, dims, intr, w2c, bits, H, W, counts=counts, **on)
+        if exclusive:
+            near.update(zip(sel, bits))
     if counts is None:   # no view: nothing is seen
         counts = (torch.zeros(n, dtype=torch.uint16), torch.zeros(n, dtype=torch.uint16))
     seen, hit = (c.cpu().numpy() for c in counts)
@@ -692,15 +683,12 @@ def seed_points(cameras, edge_maps_u8, detector, bounds, grid=128, tol_px=2, min
         index = np.nonzero(keep)[0].astype(np.int32)
         support = voxel_support(seen, hit, index)
         wins = None
-        for H, W, intr, w2c, bits in chunks:
-            per = max(1, budget // (EXCL_BYTES_PER_PIXEL * H * W))
-            for b in range(0, bits.shape[0], per):
-                args = (bounds, dims, index, support, intr[b:b + per], w2c[b:b + per], bits[b:b + per])
-                best = ray_claims(*args, H, W, backend=backend, device=device)
-                wins = ray_wins(*args, best, H, W, window=excl_window, margin=excl_margin, counts=wins, backend=backend,
-                                device=device)
-                del best
-        del chunks
+        for H, W, sel, intr, w2c in view_chunks(cameras, EXCL_BYTES_PER_PIXEL, budget):
+            args = (bounds, dims, index, support, intr, w2c, torch.stack([near[v] for v in sel]))
+            best = ray_claims(*args, H, W, **on)
+            wins = ray_wins(*args, best, H, W, window=excl_window, margin=excl_margin, counts=wins, **on)
+            del best
+        del near
         if wins is None:   # no view
             wins = torch.zeros(index.size, dtype=torch.uint16)
         keep = np.zeros(n, bool)
@@ -711,7 +699,7 @@ def seed_points(cameras, edge_maps_u8, detector, bounds, grid=128, tol_px=2, min
     if exclusive:
         info["exclusive_voxels"] = int(np.count_nonzero(keep))
     if directions:
-        moments = voxel_moments(keep_bits(keep, dims), dims, thin["centre_voxel"], dir_radius, backend=backend, device=device)
+        moments = voxel_moments(keep_bits(keep, dims), dims, thin["centre_voxel"], dir_radius, **on)
         vectors, directed, _ = seed_directions(moments, dir_min_support, dir_min_linearity)
         info["directions"], info["directed"] = vectors, int(np.count_nonzero(directed))
     return seeds, info

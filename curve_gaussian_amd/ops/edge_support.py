@@ -33,11 +33,11 @@ import numpy as np
 import torch
 
 from .. import _lib as L
-from ..edge_extraction.novel_view import camera_arrays
 from ..edge_extraction.para_edge import EDGE_MAX_THRESHOLD, EDGE_VISIBILITY_FRAMES_RATIO
-from ..edge_extraction.reprojection import SAMPLE_RESOLUTION, detected_lut
+from ..edge_extraction.reprojection import SAMPLE_RESOLUTION
 from ..scene.dataset_io import bezier_curve_length
 from . import edge_score as ES
+from .view_chunks import check_budget, check_edge_maps, detected_lut, detected_masks, view_chunks
 
 SUPPORT_BACKENDS = ES.SCORE_BACKENDS
 MAX_TOL = L.EDGE_SUPPORT_MAX_TOL
@@ -111,7 +111,7 @@ def _points(points):
 
 def _offsets(offsets, P):
     """int32 [E+1] on the host, checked: integers, non-decreasing, offsets[0] = 0, offsets[E] = P."""
-    off = offsets.detach().cpu().numpy() if torch.is_tensor(offsets) else np.asarray(offsets)
+    off = ES._host(offsets)
     if off.ndim != 1 or off.size < 1 or not np.issubdtype(off.dtype, np.integer):
         raise ValueError(f"offsets must be an integer [E+1] array (got {off.dtype} {off.shape})")
     off = off.astype(np.int64)
@@ -186,7 +186,7 @@ def support_counts(points, offsets, intrinsics, w2c, d2, tolerances_px, backend=
         if E > 0 and V > 0:
             off_d = torch.from_numpy(off).to(dev)
             tol_d = torch.tensor(tol2, dtype=torch.int32).to(dev)
-            Kd, Md = torch.from_numpy(K).to(dev), torch.from_numpy(M).to(dev)
+            Kd, Md = ES.cameras_on(dev, K, M)
             rc = L.load().cgs_edge_support(E, int(pts.shape[0]), L.ptr(pts), L.ptr(off_d), V, L.ptr(Kd), L.ptr(Md),
                                            int(d2.shape[1]), int(d2.shape[2]), L.ptr(d2), T, L.ptr(tol_d), L.ptr(out),
                                            L.raw_stream(dev))
@@ -209,8 +209,7 @@ def support_verdict(counts, n_points, frames, min_visible=MIN_VISIBLE, min_near=
     the thresholds ceil(min_visible * n) and ceil(min_near * seen) are formed in float64.  Returns numpy arrays:
     "seeing_views" int64 [E], "supporting_views" int64 [E,T], "share" float64 [E,T] (NaN where no view sees a sample) and
     "kept" bool [E], the verdict at tolerance ``keep_index``."""
-    c = (counts.detach().cpu().numpy() if torch.is_tensor(counts) else np.asarray(counts)).astype(np.int64)
-    n = (n_points.detach().cpu().numpy() if torch.is_tensor(n_points) else np.asarray(n_points)).astype(np.int64).reshape(-1)
+    c, n = ES._host(counts).astype(np.int64), ES._host(n_points).astype(np.int64).reshape(-1)
     if c.ndim != 3 or c.shape[2] < 2 or c.shape[0] != n.size:
         raise ValueError(f"counts must be [E,V,1+T] and n_points [E] (got {c.shape}, {n.shape})")
     min_visible, min_near = _ratio01("min_visible", min_visible), _ratio01("min_near", min_near)
@@ -259,17 +258,8 @@ def edge_support(edge_dict, cameras, edge_maps_u8, detector, resolution=SAMPLE_R
         raise ValueError(f"edge_support: keep_tolerance_px {keep_tolerance_px} is not one of tolerances_px {tolerances_px}")
     keep_index = tolerances_px.index(float(keep_tolerance_px))
     lut = detected_lut(detector, edge_threshold)
-    cameras = list(cameras)
-    maps = [np.asarray(m) for m in edge_maps_u8]
-    if len(maps) != len(cameras):
-        raise ValueError(f"edge_support: {len(cameras)} cameras and {len(maps)} edge maps")
-    for c, m in zip(cameras, maps):
-        if m.dtype != np.uint8 or m.shape != (c.height, c.width):
-            raise ValueError(f"edge_support: the edge map of {c.name} must be uint8 [{c.height},{c.width}] (got {m.dtype} "
-                             f"{m.shape})")
-    budget = BYTE_BUDGET if budget_bytes is None else int(budget_bytes)
-    if budget <= 0:
-        raise ValueError(f"edge_support: budget_bytes must be positive (got {budget})")
+    cameras, maps = check_edge_maps("edge_support", cameras, edge_maps_u8)
+    budget = check_budget("edge_support", budget_bytes, BYTE_BUDGET)
     curves, lines = _edge_arrays(edge_dict["curves_ctl_pts"], edge_dict["lines_end_pts"])
     pts, off = sample_edges(curves, lines, resolution)
     E, V, T = off.size - 1, len(cameras), len(tol2)
@@ -279,18 +269,10 @@ def edge_support(edge_dict, cameras, edge_maps_u8, detector, resolution=SAMPLE_R
     else:
         pts_b = pts
     counts = np.zeros((E, V, 1 + T), np.int32)
-    by_size = {}
-    for v, c in enumerate(cameras):
-        by_size.setdefault((c.height, c.width), []).append(v)
-    for (H, W), idx in by_size.items():
-        per = max(1, budget // (BYTES_PER_PIXEL * H * W))
-        for b in range(0, len(idx), per):
-            sel = idx[b:b + per]
-            intr, w2c = camera_arrays([cameras[v] for v in sel])
-            det = torch.from_numpy(lut[np.stack([maps[v] for v in sel])].astype(np.uint8))
-            d2 = ES.edt_squared(det, backend=backend, device=device)
-            counts[:, sel, :] = support_counts(pts_b, off, intr, w2c, d2, tolerances_px, backend=backend).cpu().numpy()
-            del d2
+    for _, _, sel, intr, w2c in view_chunks(cameras, BYTES_PER_PIXEL, budget):
+        d2 = ES.edt_squared(detected_masks(lut, maps, sel), backend=backend, device=device)
+        counts[:, sel, :] = support_counts(pts_b, off, intr, w2c, d2, tolerances_px, backend=backend).cpu().numpy()
+        del d2
     n_points = np.diff(off.astype(np.int64))
     out = {"counts": torch.from_numpy(counts), "n_points": n_points, "curves": int(len(curves)), "lines": int(len(lines))}
     out.update(support_verdict(counts, n_points, V, min_visible, min_near, frames_ratio, keep_index))

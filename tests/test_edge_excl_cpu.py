@@ -208,6 +208,11 @@ def test_chunking_the_second_sweep_changes_nothing():
     one, info_1 = SD.seed_points(cams, maps, "PidiNet", SC.SEED_BOUNDS, backend="host", exclusive=True, budget_bytes=1,
                                  **SC.SEED_OPTIONS)
     assert np.array_equal(one, whole) and info_1 == info, "one view at a time"
+    kw = dict(backend="host", exclusive=True, directions=True, **SC.SEED_OPTIONS)   # and with the directions on top
+    whole_d, info_d = SD.seed_points(cams, maps, "PidiNet", SC.SEED_BOUNDS, **kw)
+    one_d, info_1d = SD.seed_points(cams, maps, "PidiNet", SC.SEED_BOUNDS, budget_bytes=1, **kw)
+    assert np.array_equal(whole_d, whole) and np.array_equal(one_d, whole) and XC.same_info(info_1d, info_d)
+    assert info_d["directions"].shape == (len(whole), 3) and {k: info_d[k] for k in info} == info
     assert SD.EXCL_BYTES_PER_PIXEL == 4 and SD.BYTES_PER_PIXEL == 8
 
 

@@ -86,6 +86,20 @@ def test_chunking_changes_nothing():
     assert len(whole) > 0 and np.array_equal(whole, parts) and info == info_p
 
 
+def test_one_view_per_chunk_with_claims_and_directions_equals_host():
+    """budget_bytes=1: both sweeps of seed_points go one view at a time -- six uploads of one camera, six SeedViews of one
+    view, the votes and the wins accumulated across them.  Seeds, directions and every integer of info equal the host's."""
+    cams, maps = SC.seed_novel_cameras()
+    kw = dict(exclusive=True, directions=True, **SC.SEED_OPTIONS)
+    want, want_info = SD.seed_points(cams, maps, "PidiNet", SC.SEED_BOUNDS, backend="host", **kw)
+    got, info = SD.seed_points(cams, maps, "PidiNet", SC.SEED_BOUNDS, backend="gpu", device=DEV, budget_bytes=1, **kw)
+    assert len(got) > 0 and got.dtype == np.float64 and np.array_equal(got, want)
+    assert np.array_equal(info["directions"], want_info["directions"]) and info["backend"] == "gpu"
+    keys = set(want_info) - {"backend", "directions"}
+    assert keys == set(info) - {"backend", "directions"} and all(info[k] == want_info[k] for k in keys)
+    assert 0 < info["exclusive_voxels"] < info["kept_voxels"] and info["directed"] > 0 and info["views"] == 6
+
+
 def test_seed_points_gpu_equals_host():
     cams, maps = SC.seed_novel_cameras()
     want, want_info = _host_seeds()
