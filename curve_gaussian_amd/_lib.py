@@ -117,6 +117,7 @@ SIGNATURES = {
     "cgs_ray_claims": (_i, [_i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _i, _vp, _vp]),
     "cgs_ray_wins": (_i, [_i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "cgs_edge_support": (_i, [_i, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp]),
+    "cgs_thin_masks": (_i, [_i, _i, _i, _vp, _vp, _vp, _i, C.POINTER(_i), _vp]),
 }
 
 
@@ -161,6 +162,9 @@ SEED_MAX_VIEWS = 65535   # CGS_SEED_MAX_VIEWS
 SEED_MAX_RADIUS = 15   # CGS_SEED_MAX_RADIUS
 SEED_MAX_WINDOW = 4   # CGS_SEED_MAX_WINDOW
 EDGE_SUPPORT_MAX_TOL = 4   # CGS_EDGE_SUPPORT_MAX_TOL
+THIN_PASS_ITERATIONS = 4   # CGS_THIN_PASS_ITERATIONS
+THIN_TILE_WIDTH = 48   # CGS_THIN_TILE_WIDTH
+THIN_TILE_HEIGHT = 240   # CGS_THIN_TILE_HEIGHT
 REPORT_PANELS = ("render", "ground_truth", "depth", "rend_dir", "rend_alpha")   # panel order of cgs_report_panels
 
 _lib = None

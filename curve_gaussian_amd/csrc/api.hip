@@ -2014,4 +2014,32 @@ int cgs_edge_support(int E, int P, const float* points, const int32_t* offsets, 
     return finish("edge_support", stream_);
 }
 
+int cgs_thin_masks(int V, int height, int width, uint8_t* masks, uint8_t* scratch, int* changed_flag, int max_iterations,
+                   int* iterations_out, void* stream_) {
+    if (V < 0 || !edt_size_ok(height, width) || max_iterations < 0) {
+        set_error("cgs_thin_masks: invalid argument (V=%d, height=%d, width=%d, max_iterations=%d; sizes lie in [1, %d])", V,
+                  height, width, max_iterations, CGS_EDT_MAX_SIZE);
+        return CGS_ERR_INVALID_ARGUMENT;
+    }
+    if (V == 0) {
+        if (iterations_out) *iterations_out = 0;
+        return CGS_OK;
+    }
+    if (!masks || !scratch || !changed_flag) {
+        set_error("cgs_thin_masks: invalid argument (NULL pointer)");
+        return CGS_ERR_INVALID_ARGUMENT;
+    }
+    hipError_t err = hipSuccess;
+    int iterations = 0;
+    const int passes = launch_thin_masks((hipStream_t)stream_, V, height, width, masks, scratch, changed_flag, max_iterations,
+                                         &iterations, &err);
+    if (passes < 0) {
+        set_error("thin_masks failed: %s", hipGetErrorString(err));
+        return CGS_ERR_HIP;
+    }
+    if (!check_launch("thin_masks", false, (hipStream_t)stream_)) return CGS_ERR_HIP;
+    if (iterations_out) *iterations_out = iterations;
+    return passes;
+}
+
 }  // extern "C"

@@ -25,6 +25,7 @@ import numpy as np
 import torch
 
 from ..ops import edge_score as ES
+from ..ops.edge_thin import thin_masks
 from ..ops.view_chunks import check_edge_maps, detected_lut, detected_masks, view_chunks
 from ..scene.dataset_io import fov2focal
 from .abc import pred_points_and_directions
@@ -48,14 +49,16 @@ def _json_number(x):
 
 
 def score_edges(pred, cameras, edge_maps_u8, detector, tolerances_px=(1, 2, 4), edge_threshold=EDGE_MAX_THRESHOLD,
-                sample_resolution=SAMPLE_RESOLUTION, device=None, backend="gpu", budget_bytes=None):
+                sample_resolution=SAMPLE_RESOLUTION, device=None, backend="gpu", budget_bytes=None, thin=False):
     """pred: a ``parametric_edges.json`` path or its dict.  cameras: ``NovelViewCamera`` s (R, T world -> camera; fx, fy, cx,
     cy; size).  edge_maps_u8: one uint8 [H,W] map per camera (a list, or an [V,H,W] array), the stored bytes of the
     detector's maps, each of its camera's size.  Returns {"aggregate": ops.edge_score's aggregate over all views,
     "views": one row per camera in order (name, width, height, kept_points, n_pred, n_det, pred_hits, det_hits,
     accuracy_px, completeness_px, both_nonempty), "settings"}.  Views of one size are scored together, ``budget_bytes``
     (default ops.edge_score.BYTE_BUDGET) of masks and distance transforms at a time.  ``backend``: "gpu" (HIP; ``device``)
-    or "host" (numpy)."""
+    or "host" (numpy).  ``thin``: every chunk's detected masks go through ``ops.edge_thin.thin_masks`` on the same back end
+    first (a detector's response several pixels wide makes the recall measure its line width; untuned, limits in
+    ops/edge_thin.py); "settings" then holds "thin": true, and nothing otherwise."""
     ES._check_backend(backend)
     tolerances_px = [float(t) for t in tolerances_px]
     ES.tolerances_squared(tolerances_px)
@@ -75,8 +78,10 @@ def score_edges(pred, cameras, edge_maps_u8, detector, tolerances_px=(1, 2, 4), 
     kept = np.zeros(V, np.int64)
     for H, W, sel, intr, w2c in view_chunks(cameras, ES.BYTES_PER_PIXEL, budget):
         pm, k = ES.point_masks(pts_b, intr, w2c, H, W, backend=backend, device=device, return_kept=True)
-        res = ES.score_masks(pm, detected_masks(lut, maps, sel), tolerances_px, backend=backend, device=device,
-                             budget_bytes=budget)
+        det = detected_masks(lut, maps, sel)
+        if thin:
+            det = thin_masks(det, backend=backend, device=device)
+        res = ES.score_masks(pm, det, tolerances_px, backend=backend, device=device, budget_bytes=budget)
         kept[sel] = k.cpu().numpy()
         for name, a in per_view.items():
             a[sel] = res[name].numpy()
@@ -93,6 +98,8 @@ def score_edges(pred, cameras, edge_maps_u8, detector, tolerances_px=(1, 2, 4), 
                      "both_nonempty": both})
     settings = {"detector": detector, "tolerances_px": tolerances_px, "edge_threshold": float(edge_threshold),
                 "sample_resolution": float(sample_resolution), "backend": backend, "points": int(pts.shape[0])}
+    if thin:
+        settings["thin"] = True
     return {"aggregate": agg, "views": rows, "settings": settings}
 
 
@@ -151,11 +158,11 @@ def write_score(path, result):
 
 def score_scan(base_dir, dataset_dir, scan, layout="emap", detector="DexiNed", undistort=False, tolerances_px=(1, 2, 4),
                edge_threshold=EDGE_MAX_THRESHOLD, sample_resolution=SAMPLE_RESOLUTION, device=None, backend="gpu",
-               resolution=-1):
+               resolution=-1, thin=False):
     """Scores ``<base_dir>/<scan>/parametric_edges.json`` against the ``detector`` edge maps of ``<dataset_dir>/<scan>`` and
     writes ``<base_dir>/<scan>/reprojection_score.json`` = {"scan", "aggregate", "views", "settings"}.  ``layout``: "emap"
     (meta_data.json; cameras and maps through get_edge_maps) or "colmap" (sparse/0, also Replica; through read_colmap, with
-    ``undistort`` and ``resolution`` as there).  Returns the dict, or None -- after reporting it -- for a scan without a
+    ``undistort`` and ``resolution`` as there); ``thin`` as ``score_edges``.  Returns the dict, or None -- after reporting it -- for a scan without a
     prediction, as the reference's tools skip one."""
     ES._check_backend(backend)
     if layout not in LAYOUTS:
@@ -171,7 +178,8 @@ def score_scan(base_dir, dataset_dir, scan, layout="emap", detector="DexiNed", u
         cams, maps = emap_cameras(scan_dir, detector)
     else:
         cams, maps = colmap_scan_cameras(scan_dir, detector, undistort, backend, resolution)
-    res = score_edges(path, cams, maps, detector, tolerances_px, edge_threshold, sample_resolution, device, backend)
+    res = score_edges(path, cams, maps, detector, tolerances_px, edge_threshold, sample_resolution, device, backend,
+                      thin=thin)
     res["settings"].update({"layout": layout, "undistort": bool(undistort)})
     out = {"scan": scan, **res}
     write_score(os.path.join(base_dir, scan, SCORE_FILE), out)
@@ -234,6 +242,7 @@ def parser():
     ap.add_argument("--edge_threshold", type=float, default=EDGE_MAX_THRESHOLD)
     ap.add_argument("--undistort", action="store_true", help="colmap layout: resample the edge maps through the lens model")
     ap.add_argument("--backend", choices=ES.SCORE_BACKENDS, default="gpu")
+    ap.add_argument("--thin", action="store_true", help="thin the detected masks first (a thick detector response; untuned)")
     return ap
 
 
@@ -242,7 +251,7 @@ def main(argv=None):
     aggregates = []
     for scan in dataset_scans(args.dataset_dir, args.layout, args.scans):
         res = score_scan(args.base_dir, args.dataset_dir, scan, args.layout, args.detector, args.undistort, args.tolerances,
-                         args.edge_threshold, backend=args.backend)
+                         args.edge_threshold, backend=args.backend, thin=args.thin)
         if res is None:
             print(f"Invalid prediction at {scan}")
             continue

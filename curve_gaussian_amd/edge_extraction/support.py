@@ -134,6 +134,7 @@ def parser():
     ap.add_argument("--edge_threshold", type=float, default=EDGE_MAX_THRESHOLD)
     ap.add_argument("--write_filtered", action="store_true", help=f"also write {FILTERED_FILE} with the kept edges")
     ap.add_argument("--backend", choices=SP.SUPPORT_BACKENDS, default="gpu")
+    ap.add_argument("--thin", action="store_true", help="thin the detected masks first (a thick detector response; untuned)")
     return ap
 
 
@@ -144,7 +145,7 @@ def main(argv=None):
                          args.write_filtered, backend=args.backend, tolerances_px=args.tolerances,
                          keep_tolerance_px=args.keep_tolerance, min_visible=args.min_visible, min_near=args.min_near,
                          frames_ratio=args.frames_ratio, sample_resolution=args.sample_resolution,
-                         edge_threshold=args.edge_threshold)
+                         edge_threshold=args.edge_threshold, **({"thin": True} if args.thin else {}))
         if out is None:
             print(f"Invalid prediction at {scan}")
             continue

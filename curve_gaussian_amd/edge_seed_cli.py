@@ -44,16 +44,20 @@ def parser():
     ap.add_argument("--excl_window", type=int, default=SD.EXCL_WINDOW)
     ap.add_argument("--excl_margin", type=int, default=SD.EXCL_MARGIN)
     ap.add_argument("--excl_win_ratio", type=float, default=SD.EXCL_WIN_RATIO)
+    ap.add_argument("--thin", action="store_true", help="thin the detected masks first (a thick detector response; untuned)")
     return ap
 
 
 def seed_options(args):
     """seed_points' keywords of a parsed command line."""
-    return dict(grid=args.grid, tol_px=args.tol_px, min_views=args.min_views, min_ratio=args.min_ratio, cell=args.cell,
+    opts = dict(grid=args.grid, tol_px=args.tol_px, min_views=args.min_views, min_ratio=args.min_ratio, cell=args.cell,
                 max_seeds=args.max_seeds, edge_threshold=args.edge_threshold, directions=args.directions,
                 dir_radius=args.dir_radius, dir_min_support=args.dir_min_support, dir_min_linearity=args.dir_min_linearity,
                 exclusive=args.exclusive, excl_window=args.excl_window, excl_margin=args.excl_margin,
                 excl_win_ratio=args.excl_win_ratio)
+    if args.thin:
+        opts["thin"] = True
+    return opts
 
 
 def seed_scan(scan_dir, layout="emap", detector="DexiNed", undistort=False, bounds=None, backend="gpu", **options):
@@ -85,7 +89,7 @@ def main(argv=None):
     print(f"views {info['views']}, grid {info['dims'][0]}x{info['dims'][1]}x{info['dims'][2]}, kept voxels "
           f"{info['kept_voxels']}, cells {info['cells']}, seeds {info['seeds']}{' (capped)' if info['capped'] else ''}, "
           f"bounds {info['bounds']}" + (f", after the claims {info['exclusive_voxels']} voxels" if args.exclusive else "")
-          + (f", directed {info['directed']}" if args.directions else ""))
+          + (f", directed {info['directed']}" if args.directions else "") + (", detected masks thinned" if args.thin else ""))
     print(f"Wrote {args.out}")
     return 0
 

@@ -73,6 +73,7 @@ import torch
 from .. import _lib as L
 from ..edge_extraction.para_edge import EDGE_MAX_THRESHOLD
 from . import edge_score as ES
+from .edge_thin import thin_masks
 from .view_chunks import check_budget, check_edge_maps, detected_lut, detected_masks, view_chunks
 
 SEED_BACKENDS = ES.SCORE_BACKENDS
@@ -618,7 +619,7 @@ def seed_points(cameras, edge_maps_u8, detector, bounds, grid=128, tol_px=2, min
                 max_seeds=20000, edge_threshold=EDGE_MAX_THRESHOLD, backend="gpu", device=None, budget_bytes=None,
                 directions=False, dir_radius=DIR_RADIUS, dir_min_support=DIR_MIN_SUPPORT,
                 dir_min_linearity=DIR_MIN_LINEARITY, exclusive=False, excl_window=EXCL_WINDOW, excl_margin=EXCL_MARGIN,
-                excl_win_ratio=EXCL_WIN_RATIO):
+                excl_win_ratio=EXCL_WIN_RATIO, thin=False):
     """cameras: ``NovelViewCamera`` s; edge_maps_u8: one uint8 [H,W] map per camera (a list or an [V,H,W] array), the
     stored bytes of the detector's maps, as ``score_edges`` takes them.  bounds = (lo, hi) of the box to search.
 
@@ -645,7 +646,12 @@ def seed_points(cameras, edge_maps_u8, detector, bounds, grid=128, tol_px=2, min
     EXCL_BYTES_PER_PIXEL bytes per pixel of ``budget_bytes``, and the wins accumulate across the chunks, so the result
     does not depend on the chunking.  The thinning, the keep bits and the moments see the surviving mask; info
     additionally holds "exclusive_voxels", the voxels that remain ("kept_voxels" keeps its meaning).  These three
-    defaults are untuned too; there is still no depth."""
+    defaults are untuned too; there is still no depth.
+
+    ``thin=True``: every chunk's detected masks go through ``edge_thin.thin_masks`` on the same back end before the
+    transform (a detector's response several pixels wide widens the near band by half its width; 2 bytes per pixel,
+    released before the transform is allocated; untuned, limits in ops/edge_thin.py); info then holds "thin": True, and
+    nothing otherwise."""
     _check_backend(backend)
     lut = detected_lut(detector, edge_threshold)
     cameras, maps = check_edge_maps("seed_points", cameras, edge_maps_u8)
@@ -668,7 +674,11 @@ def seed_points(cameras, edge_maps_u8, detector, bounds, grid=128, tol_px=2, min
     on = {"backend": backend, "device": device}
     counts, near = None, {}   # near: every view's near bits of the first sweep, for the second
     for H, W, sel, intr, w2c in view_chunks(cameras, BYTES_PER_PIXEL, budget):
-        d2 = ES.edt_squared(detected_masks(lut, maps, sel), **on)
+        det = detected_masks(lut, maps, sel)
+        if thin:
+            det = thin_masks(det, **on)
+        d2 = ES.edt_squared(det, **on)
+        del det
         bits = near_bits(d2, tol_px, **on)
         del d2
         counts = voxel_votes(bounds, dims, intr, w2c, bits, H, W, counts=counts, **on)
@@ -693,13 +703,15 @@ def seed_points(cameras, edge_maps_u8, detector, bounds, grid=128, tol_px=2, min
             wins = torch.zeros(index.size, dtype=torch.uint16)
         keep = np.zeros(n, bool)
         keep[index[select_exclusive(wins, hit[index], excl_win_ratio)]] = True
-    seeds, thin = thin_to_seeds(keep, hit, bounds, dims, cell, max_seeds, return_centres=bool(directions))
+    seeds, cells = thin_to_seeds(keep, hit, bounds, dims, cell, max_seeds, return_centres=bool(directions))
     info = {"dims": dims, "voxels": n, "views": len(cameras), "kept_voxels": kept_voxels,
-            "cells": thin["cells"], "seeds": int(seeds.shape[0]), "capped": thin["capped"], "backend": backend}
+            "cells": cells["cells"], "seeds": int(seeds.shape[0]), "capped": cells["capped"], "backend": backend}
+    if thin:
+        info["thin"] = True
     if exclusive:
         info["exclusive_voxels"] = int(np.count_nonzero(keep))
     if directions:
-        moments = voxel_moments(keep_bits(keep, dims), dims, thin["centre_voxel"], dir_radius, **on)
+        moments = voxel_moments(keep_bits(keep, dims), dims, cells["centre_voxel"], dir_radius, **on)
         vectors, directed, _ = seed_directions(moments, dir_min_support, dir_min_linearity)
         info["directions"], info["directed"] = vectors, int(np.count_nonzero(directed))
     return seeds, info

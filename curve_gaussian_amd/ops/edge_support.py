@@ -23,7 +23,8 @@ The thresholds are built in float64 on the host, as ``edge_seed.need_table`` bui
 
 KNOWN LIMITS.  There is no depth: an edge hidden behind a surface in most views loses its support there, which is why the
 rule counts supporting FRAMES and does not pool the samples of all views.  A thick detector response inflates support: a
-chord across a wide response lies "on" it.  THE DEFAULTS OF ``edge_support`` ARE UNTUNED: one run on the drawn test scan
+chord across a wide response lies "on" it (``thin=True`` thins the detected masks first: ops/edge_thin.py, DESIGN.md 4.8n;
+untuned, checked on dilated drawn maps only).  THE DEFAULTS OF ``edge_support`` ARE UNTUNED: one run on the drawn test scan
 (tests/edge_support_cases.py), no real scan.
 
 Two back ends: ``"gpu"``, HIP, and ``"host"``, numpy -- the same rules in integers, so the counts agree exactly."""
@@ -37,6 +38,7 @@ from ..edge_extraction.para_edge import EDGE_MAX_THRESHOLD, EDGE_VISIBILITY_FRAM
 from ..edge_extraction.reprojection import SAMPLE_RESOLUTION
 from ..scene.dataset_io import bezier_curve_length
 from . import edge_score as ES
+from .edge_thin import thin_masks
 from .view_chunks import check_budget, check_edge_maps, detected_lut, detected_masks, view_chunks
 
 SUPPORT_BACKENDS = ES.SCORE_BACKENDS
@@ -235,7 +237,7 @@ def support_verdict(counts, n_points, frames, min_visible=MIN_VISIBLE, min_near=
 def edge_support(edge_dict, cameras, edge_maps_u8, detector, resolution=SAMPLE_RESOLUTION, tolerances_px=TOLERANCES_PX,
                  keep_tolerance_px=KEEP_TOLERANCE_PX, min_visible=MIN_VISIBLE, min_near=MIN_NEAR,
                  frames_ratio=EDGE_VISIBILITY_FRAMES_RATIO, edge_threshold=EDGE_MAX_THRESHOLD, backend="gpu", device=None,
-                 budget_bytes=None):
+                 budget_bytes=None, thin=False):
     """edge_dict: {"curves_ctl_pts", "lines_end_pts"} (a ``parametric_edges.json``).  cameras: ``NovelViewCamera`` s;
     edge_maps_u8: one uint8 [H,W] map per camera, the stored bytes of the detector's maps, as ``score_edges`` takes them.
     ``resolution``: the sampling step (default: ``reprojection.SAMPLE_RESOLUTION``, the novel views' Replica value); ``keep_tolerance_px``: the one of
@@ -245,7 +247,10 @@ def edge_support(edge_dict, cameras, edge_maps_u8, detector, resolution=SAMPLE_R
     goes through ``edt_squared``.  Views of one size are processed together, ``budget_bytes`` (default BYTE_BUDGET) of masks
     and transforms at a time (7 bytes per pixel) and at least one view; every (edge, view) cell depends on its view alone,
     so the chunking cannot change a bit.  THE DEFAULTS ARE UNTUNED (one run on the drawn test scan, no real scan), there is
-    no depth and a thick detector response inflates support: see the module docstring.
+    no depth and a thick detector response inflates support: see the module docstring.  ``thin``: every chunk's detected
+    masks go through ``edge_thin.thin_masks`` on the same back end before the transform (2 bytes per pixel, released before
+    the transform is allocated; untuned, limits in ops/edge_thin.py); "settings" then holds "thin": True, and nothing
+    otherwise.
 
     Returns {"counts": int32 [E,V,1+T] CPU tensor, "n_points": int64 [E], "curves": Nc, "lines": Nl, the arrays of
     ``support_verdict`` ("seeing_views", "supporting_views", "share", "kept"), "settings"}; edges are ordered
@@ -270,7 +275,11 @@ def edge_support(edge_dict, cameras, edge_maps_u8, detector, resolution=SAMPLE_R
         pts_b = pts
     counts = np.zeros((E, V, 1 + T), np.int32)
     for _, _, sel, intr, w2c in view_chunks(cameras, BYTES_PER_PIXEL, budget):
-        d2 = ES.edt_squared(detected_masks(lut, maps, sel), backend=backend, device=device)
+        det = detected_masks(lut, maps, sel)
+        if thin:
+            det = thin_masks(det, backend=backend, device=device)
+        d2 = ES.edt_squared(det, backend=backend, device=device)
+        del det
         counts[:, sel, :] = support_counts(pts_b, off, intr, w2c, d2, tolerances_px, backend=backend).cpu().numpy()
         del d2
     n_points = np.diff(off.astype(np.int64))
@@ -280,4 +289,6 @@ def edge_support(edge_dict, cameras, edge_maps_u8, detector, resolution=SAMPLE_R
                        "keep_tolerance_px": float(keep_tolerance_px), "min_visible": float(min_visible),
                        "min_near": float(min_near), "frames_ratio": float(frames_ratio),
                        "edge_threshold": float(edge_threshold), "backend": backend, "views": V, "points": int(pts.shape[0])}
+    if thin:
+        out["settings"]["thin"] = True
     return out

@@ -4,6 +4,7 @@
     python -m curve_gaussian_amd.train -s SCAN -m OUT [--iterations N] [--backend graphed|direct|autograd|torch]
                                        [--draw_snapshots] [--topology_backend host|gpu] [--report_dir DIR] [--undistort]
                                        [--init reference|edge_votes] [--init_directions] [--init_exclusive]
+                                       [--thin_edge_maps]
 
 The loop keeps the reference's order.  Per iteration: learning rate, SH degree every 1000 iterations, a random view without
 replacement, render + losses + every regulariser + backward (one ``TrainStep`` call), densification statistics before
@@ -377,6 +378,10 @@ def build_parser():
                    help="support check: share of an edge's samples that a view must see")
     p.add_argument("--support_frames_ratio", type=float, default=None,
                    help="support check: an edge is kept when more than ceil(ratio * views) views support it")
+    p.add_argument("--thin_edge_maps", action="store_true",
+                   help="thin every view's detected mask (Guo-Hall) before --support_check, --reprojection_score and --init "
+                        "edge_votes compare it with projected geometry: for a detector whose response is several pixels wide "
+                        "(untuned; a binary thinning, not non-maximum suppression)")
     return p
 
 
@@ -387,6 +392,8 @@ def support_options(args):
     if args.support_tol_px is not None:
         opts["tolerances_px"] = (args.support_tol_px,)
         opts["keep_tolerance_px"] = args.support_tol_px
+    if args.thin_edge_maps:
+        opts["thin"] = True
     return opts
 
 
@@ -408,6 +415,8 @@ def parse_args(argv):
         init_options["directions"] = True
     if args.init_exclusive:
         init_options["exclusive"] = True
+    if args.thin_edge_maps:
+        init_options["thin"] = True
     if args.init_bounds is not None:
         init_options["bounds"] = (args.init_bounds[:3], args.init_bounds[3:])
     dataset = ModelParams(source_path, args.model_path, args.sh_degree, args.n_gaussians, args.detector, args.resolution,
@@ -429,7 +438,8 @@ def main(argv=None):
                    topology_backend=args.topology_backend, report_writer=writer)
     if args.reprojection_score:
         from .edge_extraction.reprojection import scan_line, score_scene
-        scores = score_scene(dataset.model_path, out["scene"], dataset.detector)
+        scores = score_scene(dataset.model_path, out["scene"], dataset.detector,
+                             **({"thin": True} if args.thin_edge_maps else {}))
         for split, res in scores.items():
             if res is not None:
                 print(scan_line(split, res["aggregate"]))

@@ -1000,6 +1000,43 @@ int cgs_edge_support(int E, int P, const float* points /*[P,3]*/, const int32_t*
                      const int32_t* d2 /*[V,height,width]*/, int T, const int32_t* tol2 /*[T]*/,
                      int32_t* counts /*[E,V,1+T]*/, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Parallel binary thinning of detected masks: a learned detector's response is several pixels wide, and the 2D checks above
+ * (reprojection score, voxel vote, per-edge support) were designed on one-pixel lines.  The reference has no counterpart.
+ *
+ * The rule is Guo-Hall two-subiteration thinning (Guo & Hall, CACM 1989), frozen.  The state is a binary image; pixels
+ * outside the image read as 0.  The neighbours of (y, x): P2 = (y-1, x), P3 = (y-1, x+1), P4 = (y, x+1), P5 = (y+1, x+1),
+ * P6 = (y+1, x), P7 = (y+1, x-1), P8 = (y, x-1), P9 = (y-1, x-1).
+ *   C  = (!P2 & (P3|P4)) + (!P4 & (P5|P6)) + (!P6 & (P7|P8)) + (!P8 & (P9|P2))
+ *   N1 = (P9|P2) + (P3|P4) + (P5|P6) + (P7|P8),  N2 = (P2|P3) + (P4|P5) + (P6|P7) + (P8|P9),  N = min(N1, N2)
+ *   m  = (P6 | P7 | !P9) & P8 in sub-iteration 0,  (P2 | P3 | !P5) & P4 in sub-iteration 1
+ *   a set pixel is cleared iff C == 1 and 2 <= N <= 3 and m == 0
+ * Every pixel of a sub-iteration decides from the state before that sub-iteration; one iteration is sub-iteration 0 followed
+ * by sub-iteration 1; the result is the state after the first iteration that changes nothing in any view.  max_iterations
+ * = n > 0 stops after n iterations, or sooner when the state has settled; 0 runs until it has.
+ *
+ * masks is uint8 [V,height,width], device, in: nonzero = set, out: 0 / 1.  scratch is a second buffer of that size, no
+ * initialisation needed; the result is in masks whichever buffer the last pass wrote.  A PASS is one launch that performs up
+ * to CGS_THIN_PASS_ITERATIONS iterations on tiles of CGS_THIN_TILE_WIDTH x CGS_THIN_TILE_HEIGHT pixels held in LDS with a
+ * halo of two pixels per iteration; integers and booleans only, so the result is exact and does not depend on the tile, the
+ * iterations per pass or the launch geometry.  changed_flag (device, [1], no initialisation needed) receives per pass the
+ * last iteration of that pass in which a pixel changed (an integer atomic maximum, at most one per wave), 0 when none did.
+ * iterations_out (host, may be NULL) receives the number of iterations the rule ran: the one that changed nothing counts,
+ * so a settled input gives 1.  The call returns the number of passes (>= 1 when V > 0).
+ *
+ * The caller's stream, no allocation.  The call SYNCHRONISES the stream once per pass to read the flag, as cgs_edge_trace
+ * does; all views of a call share one size and settle together.  Offsets are 64-bit; more views than one grid dimension
+ * holds go in several launches.  V = 0 is a no-op (returns 0, iterations_out 0).  V < 0, a size outside
+ * [1, CGS_EDT_MAX_SIZE], max_iterations < 0 and NULL pointers are CGS_ERR_INVALID_ARGUMENT, rejected before anything is
+ * launched.
+ * ------------------------------------------------------------------------------------------------ */
+#define CGS_THIN_PASS_ITERATIONS 4
+#define CGS_THIN_TILE_WIDTH 48
+#define CGS_THIN_TILE_HEIGHT 240
+int cgs_thin_masks(int V, int height, int width, uint8_t* masks /*[V,height,width], in: nonzero = set, out: 0/1*/,
+                   uint8_t* scratch /*[V,height,width], no initialisation needed*/, int* changed_flag /*device, [1]*/,
+                   int max_iterations /*0: until stable*/, int* iterations_out /*host, may be NULL*/, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
