@@ -24,6 +24,14 @@ void set_error(const char* fmt, ...) {
     vsnprintf(g_err, sizeof(g_err), fmt, ap);
     va_end(ap);
 }
+// An entry's rejection of its arguments: the thread's error text and the status in one return statement
+__attribute__((format(printf, 1, 2))) static int reject(const char* fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_err, sizeof(g_err), fmt, ap);
+    va_end(ap);
+    return CGS_ERR_INVALID_ARGUMENT;
+}
 
 // ---------------------------------------------------------------- per-kernel timing (bench.py roofline leg)
 static bool g_prof_on = false;
@@ -56,6 +64,10 @@ bool check_launch(const char* what, bool debug, hipStream_t s) {
         return false;
     }
     return true;
+}
+// The tail of an entry whose launches are queued: the launch check on the entry's stream.
+static int finish(const char* what, void* stream_) {
+    return check_launch(what, false, (hipStream_t)stream_) ? CGS_OK : CGS_ERR_HIP;
 }
 
 // Binning capacity hints, one set per workload shape (P, width, height): a process that alternates train and test cameras,
@@ -137,9 +149,12 @@ static void hints_update(int P, int W, int H, int64_t R, uint32_t longest, int64
 static thread_local int64_t g_last_visible = -1;   // radii > 0 count of the last cgs_view_forward_checked
 static thread_local int64_t g_last_stats[3] = {0, 0, 0};  // num_rendered, longest tile list, binning path (0 exact, 1 bucket)
 
-// Device-side zero fill.  hipMemsetAsync is NOT used anywhere in the library: captured into a hipGraph (ROCm 7.0 runtime
-// under PyTorch 2.10) its memset node cleared the buffer on the first replay only -- later replays ran on stale
-// histograms / partial sums.  A plain kernel node replays correctly, and hipMemsetAsync is a fill kernel anyway.
+// Device-side zero fill.  hipMemsetAsync is NOT used by the entries that are captured into graphs (the rasterizer, the view
+// route, the losses, the regularizers and Adam): captured into a hipGraph (ROCm 7.0 runtime under PyTorch 2.10) its memset
+// node cleared the buffer on the first replay only -- later replays ran on stale histograms / partial sums.  A plain kernel
+// node replays correctly, and hipMemsetAsync is a fill kernel anyway.  The edge-map launchers do use it and are not captured:
+// launch_point_mask and launch_edge_score_reduce (edge_score.hip), launch_edge_trace (edge_detect.hip), launch_thin_masks
+// (edge_thin.hip) and launch_ray_claims (edge_seed.hip); so does cgs_segment_merge_labels below for an empty input.
 __global__ void __launch_bounds__(256) k_zero_words(uint32_t* __restrict__ p, size_t words) {
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < words; i += stride) p[i] = 0u;
@@ -161,6 +176,12 @@ static hipError_t zero_async(void* p, size_t bytes, hipStream_t s) {
     const int blocks = (int)std::min<size_t>((words + 255) / 256, 4096);
     hipLaunchKernelGGL(k_zero_words, dim3(blocks), dim3(256), 0, s, reinterpret_cast<uint32_t*>(p), words);
     return hipGetLastError();
+}
+// ... for an entry: a failure leaves `what` as the error text, and the entry returns CGS_ERR_HIP
+static bool zeroed(void* p, size_t bytes, hipStream_t s, const char* what) {
+    if (zero_async(p, bytes, s) == hipSuccess) return true;
+    set_error("%s", what);
+    return false;
 }
 
 // Operator API (cgs_rasterize_forward / _backward): the forward tags its tile lists and lets the scatter raise a device word
@@ -287,6 +308,12 @@ __global__ void __launch_bounds__(256) k_clamp_backward(size_t n, const float* _
         const float x = raw[i];
         g_out[i] = (x >= 0.f && x <= 1.f) ? g_in[i] : 0.f;   // torch.clamp's backward: the gradient passes where min <= x <= max
     }
+}
+
+static void launch_render_epilogue(hipStream_t s, size_t npix, const float* color_raw, const float* all_map, const float* wv,
+                                   int clamp, float* color_out, float* dir_out) {
+    hipLaunchKernelGGL(k_render_epilogue, dim3((unsigned)std::min<size_t>((npix + 255) / 256, 4096)), dim3(256), 0, s, npix,
+                       color_raw, all_map, wv, clamp, color_out, dir_out);
 }
 
 // ---------------------------------------------------------------------------------------------- shared sequencing
@@ -458,10 +485,51 @@ static bool bucket_tail(hipStream_t s, const char* what, const Frame& f, const S
         launch_render_fwd(s, geo, f.tiles, b.img.ranges, b.bin.point_list, f.W, f.H, f.gx, b.geom.rec, b.img.final_T,
                           b.img.n_contrib, background, out_color, out_invdepth, out_all_map, unit, tag);
         if (color_clamped || dir_out)   // (long-list buckets: the non-sorting forward has no epilogue of its own)
-            hipLaunchKernelGGL(k_render_epilogue, dim3((unsigned)std::min<size_t>((f.npix + 255) / 256, 4096)), dim3(256), 0, s,
-                               f.npix, out_color, out_all_map, wv, 1, color_clamped, dir_out);
+            launch_render_epilogue(s, f.npix, out_color, out_all_map, wv, 1, color_clamped, dir_out);
     }
     return check_launch(what, false, s);
+}
+
+// The body of cgs_view_backward and cgs_view_backward_render (clamp_raw: the forward's unclamped image, or NULL)
+static int view_backward_impl(int B, int m, const float* curve_points, const float* width, const uint8_t* is_bezier, const float* coef,
+                      float eps, double* norms, const float* opacity_logit, const float* mask_logit, float mask_thr,
+                      const float* colors_precomp, void* geometry_buffer, const void* binning_buffer, const void* image_buffer, const float* background,
+                      int width_px, int height_px, const float* viewmatrix, const float* projmatrix, const float* cam_pos,
+                      float tan_fovx, float tan_fovy, const int* radii, const float* dL_dout_color,
+                      const float* dL_drotation_extra, float* dL_dmeans2D, float* dL_dcurve_points, float* dL_dwidth,
+                      float* dL_dopacity_logit, float* dL_dmask_logit, float* scratch, int flags, void* stream_,
+                      const float* clamp_raw) {
+    hipStream_t s = (hipStream_t)stream_;
+    if (clamp_raw && colors_precomp)
+        return reject("cgs_view_backward_render: the folded clamp mask is part of the unit-colour path (no colors_precomp)");
+    const int P = B * m;
+    if (B <= 0 || m <= 0 || m > 32 || width_px <= 0 || height_px <= 0 || !curve_points || !width || !coef || !norms ||
+        !opacity_logit || !geometry_buffer || !binning_buffer || !image_buffer || !background || !viewmatrix || !projmatrix ||
+        !cam_pos || !radii || !dL_dout_color || !dL_dmeans2D || !dL_dcurve_points || !dL_dwidth || !dL_dopacity_logit ||
+        !scratch || (mask_logit && !dL_dmask_logit) || !aligned16(curve_points) || !aligned16(coef) ||
+        !aligned16(dL_drotation_extra) || !aligned16(dL_dcurve_points))
+        return reject("cgs_view_backward: invalid argument");
+    const Frame f(width_px, height_px, tan_fovx, tan_fovy);
+    const States b = carve_states(f, P, geometry_buffer, binning_buffer, 1, image_buffer);
+    // scratch: [B,13] per-curve partials of dL/d{curve_points, width} (k_view_bwd -> k_sample_bwd_close; curve_math.h,
+    // sample_backward_tail).  Rounds 2-5 sent 15 floats per SPLAT through here.
+    // training configuration: only dL/dcolour flows in, the colours themselves need no gradient; the forward wrote unit
+    // colours unless it was given colors_precomp (same argument here): closed-form dL/dalpha, no recurrences (render.hip, UNIT)
+    if (colors_precomp == nullptr)
+        launch_render_bwd_unit(s, f.tiles, b.img.ranges, b.bin.point_list, width_px, height_px, f.gx, background, b.geom.rec,
+                               b.img.final_T, b.img.n_contrib, dL_dout_color, b.geom.grad_acc, ACC_STRIDE_VIEW, nullptr, clamp_raw);
+    else   // arbitrary colours: the general training instance (the forward did not tag the lists)
+        launch_render_bwd(s, false, false, false, f.tiles, b.img.ranges, b.bin.point_list, width_px, height_px, f.gx, background,
+                          b.geom.rec, b.img.final_T, b.img.n_contrib, dL_dout_color, nullptr, nullptr, b.geom.grad_acc,
+                          ACC_STRIDE_VIEW);
+    launch_view_backward(s, B, m, curve_points, width, is_bezier, coef, eps, norms, opacity_logit, mask_logit, mask_thr,
+                         cam_pos, viewmatrix, projmatrix, tan_fovx, tan_fovy, f.focal_x, f.focal_y, width_px, height_px, radii,
+                         b.geom.rec, b.geom.grad_acc, dL_drotation_extra, dL_dmeans2D, dL_dopacity_logit, dL_dmask_logit, scratch,
+                         ((flags & CGS_VIEW_ACCUMULATE) ? 1 : 0) | ((flags & CGS_VIEW_SHARED) ? 2 : 0));
+    if (!(flags & CGS_VIEW_SHARED))
+        launch_sample_backward_close(s, B, m, curve_points, width, is_bezier, coef, eps, norms, scratch, dL_dcurve_points,
+                                     dL_dwidth, (flags & CGS_VIEW_ACCUMULATE) ? 1 : 0);
+    return finish("view_backward", s);
 }
 
 extern "C" {
@@ -539,17 +607,14 @@ int64_t cgs_rasterize_forward(cgs_alloc_fn geometry_alloc, void* geometry_user, 
     hipStream_t s = (hipStream_t)stream_;
     g_last_visible = -1;   // (set again by the bucket path, whose status readback carries the count)
     if (P < 0 || width <= 0 || height <= 0 || !out_color || !out_invdepth || !out_all_map || !background ||
-        !viewmatrix || !projmatrix) {
-        set_error("cgs_rasterize_forward: invalid argument (P=%d W=%d H=%d or NULL output/camera pointer)", P, width, height);
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
+        !viewmatrix || !projmatrix)
+        return reject("cgs_rasterize_forward: invalid argument (P=%d W=%d H=%d or NULL output/camera pointer)", P, width,
+                      height);
     const Frame f(width, height, tan_fovx, tan_fovy);
     if (P == 0) {  // rasterize_points.cu:91: outputs stay zero-filled, nothing is rendered (not even background)
-        if (zero_async(out_color, f.npix * 4, s) != hipSuccess || zero_async(out_invdepth, f.npix * 4, s) != hipSuccess ||
-            zero_async(out_all_map, f.npix * 16, s) != hipSuccess) {
-            set_error("zero_async failed");
+        if (!zeroed(out_color, f.npix * 4, s, "zero_async failed") || !zeroed(out_invdepth, f.npix * 4, s, "zero_async failed") ||
+            !zeroed(out_all_map, f.npix * 16, s, "zero_async failed"))
             return CGS_ERR_HIP;
-        }
         return 0;
     }
     if (!splat_inputs_ok("cgs_rasterize_forward", M, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
@@ -609,10 +674,7 @@ int64_t cgs_rasterize_forward(cgs_alloc_fn geometry_alloc, void* geometry_user, 
 
     // ---- path A: exact layout (count -> scan -> scatter -> sort); bit-identical to the reference's binning when
     // tile culling is off.  Used for the first forward, in debug mode, with culling off and after a bucket overflow.
-    if (zero_async(b.img.tile_count, b.clear_bytes, s) != hipSuccess) {
-        set_error("zero_async(tile histogram) failed");
-        return CGS_ERR_HIP;
-    }
+    if (!zeroed(b.img.tile_count, b.clear_bytes, s, "zero_async(tile histogram) failed")) return CGS_ERR_HIP;
     if (!preprocess(b.img.tile_count)) return CGS_ERR_HIP;
     launch_scan_tiles(s, f.tiles, b.img.tile_count, b.img.ranges, b.img.total);
     if (!check_launch("scan_tiles", debug, s)) return CGS_ERR_HIP;
@@ -643,10 +705,8 @@ int64_t cgs_rasterize_forward(cgs_alloc_fn geometry_alloc, void* geometry_user, 
     const uint32_t max_count = h_tot[1];
     hints_update(P, width, height, R, max_count, -1);
     if (!bchunk || R > cap) {  // first call, debug mode, or the speculative buffer was too small: exact-size (re)run
-        if (cap > 0 && zero_async(b.img.tile_cursor, (size_t)f.tiles * sizeof(uint32_t), s) != hipSuccess) {
-            set_error("zero_async(tile cursors) failed");
+        if (cap > 0 && !zeroed(b.img.tile_cursor, (size_t)f.tiles * sizeof(uint32_t), s, "zero_async(tile cursors) failed"))
             return CGS_ERR_HIP;
-        }
         cap = R;
         bchunk = (char*)binning_alloc(binning_user, cgs_binning_bytes(R));
         if (!bchunk) {
@@ -685,10 +745,9 @@ int cgs_rasterize_forward_static(void* geometry_buffer, void* binning_buffer, si
                                  int antialiasing, int render_geo, int* radii, void* stream_) {
     hipStream_t s = (hipStream_t)stream_;
     if (P <= 0 || width <= 0 || height <= 0 || !out_color || !out_invdepth || !out_all_map || !background ||
-        !viewmatrix || !projmatrix || !geometry_buffer || !binning_buffer || !image_buffer || bucket_capacity == 0) {
-        set_error("cgs_rasterize_forward_static: invalid argument (P=%d W=%d H=%d, NULL pointer or zero capacity)", P, width, height);
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
+        !viewmatrix || !projmatrix || !geometry_buffer || !binning_buffer || !image_buffer || bucket_capacity == 0)
+        return reject("cgs_rasterize_forward_static: invalid argument (P=%d W=%d H=%d, NULL pointer or zero capacity)", P,
+                      width, height);
     const Frame f(width, height, tan_fovx, tan_fovy);
     if (!splat_inputs_ok("cgs_rasterize_forward_static", M, means3D, shs, colors_precomp, opacities, scales, rotations,
                          cov3D_precomp, all_map, cam_pos, render_geo, radii) ||
@@ -742,18 +801,12 @@ int cgs_rasterize_backward(int P, int D, int M, int64_t R, const float* backgrou
     if (P < 0 || width <= 0 || height <= 0 || !geometry_buffer || !binning_buffer || !image_buffer || !radii ||
         !dL_dout_color || !dL_dmean2D || !dL_dopacity || (shs && !dL_dcolor) || !dL_dmean3D || !dL_dcov3D ||
         !dL_dall_map || (!dL_dout_invdepth != !dL_dinvdepth) || (scales && (!dL_dscale || !dL_drot)) ||
-        (shs && !dL_dsh)) {
-        set_error("cgs_rasterize_backward: invalid argument");
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
-    if (!dL_dcolor && ((render_geo && dL_dout_all_map) || dL_dout_invdepth)) {
-        set_error("cgs_rasterize_backward: dL_dcolor may only be NULL when no depth / all_map gradients flow in");
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
-    if (!aligned16(rotations) || !aligned16(dL_dconic) || !aligned16(dL_drot) || !aligned16(dL_dall_map)) {
-        set_error("cgs_rasterize_backward: rotations/dL_dconic/dL_drot must be 16-byte aligned");
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
+        (shs && !dL_dsh))
+        return reject("cgs_rasterize_backward: invalid argument");
+    if (!dL_dcolor && ((render_geo && dL_dout_all_map) || dL_dout_invdepth))
+        return reject("cgs_rasterize_backward: dL_dcolor may only be NULL when no depth / all_map gradients flow in");
+    if (!aligned16(rotations) || !aligned16(dL_dconic) || !aligned16(dL_drot) || !aligned16(dL_dall_map))
+        return reject("cgs_rasterize_backward: rotations/dL_dconic/dL_drot must be 16-byte aligned");
     const Frame f(width, height, tan_fovx, tan_fovy);
     const States b = carve_states(f, P, geometry_buffer, binning_buffer, (size_t)(R > 0 ? R : 1), image_buffer);
 
@@ -790,13 +843,9 @@ int cgs_mark_visible(int P, const float* means3D, const float* viewmatrix, const
                      void* stream_) {
     (void)projmatrix;
     if (P == 0) return CGS_OK;
-    if (P < 0 || !means3D || !viewmatrix || !present) {
-        set_error("cgs_mark_visible: invalid argument");
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
+    if (P < 0 || !means3D || !viewmatrix || !present) return reject("cgs_mark_visible: invalid argument");
     launch_mark_visible((hipStream_t)stream_, P, means3D, viewmatrix, present);
-    if (!check_launch("mark_visible", false, (hipStream_t)stream_)) return CGS_ERR_HIP;
-    return CGS_OK;
+    return finish("mark_visible", stream_);
 }
 
 
@@ -806,24 +855,18 @@ int cgs_sample_curves_forward(int B, int m, const float* curve_points, const flo
     hipStream_t s = (hipStream_t)stream_;
     if (B == 0) return CGS_OK;
     if (B < 0 || m <= 0 || m > 32 || !curve_points || !width || !coef || !norms || !xyz || !rotation || !scaling ||
-        !aligned16(curve_points) || !aligned16(rotation) || !aligned16(coef)) {
-        set_error("cgs_sample_curves_forward: invalid argument (NULL or misaligned pointer, B=%d m=%d)", B, m);
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
+        !aligned16(curve_points) || !aligned16(rotation) || !aligned16(coef))
+        return reject("cgs_sample_curves_forward: invalid argument (NULL or misaligned pointer, B=%d m=%d)", B, m);
     // (no zero fill of norms: k_sample_f12 writes the forward sums and clears the backward's, csrc/curve_math.h)
     launch_sample_forward(s, B, m, curve_points, width, is_bezier, coef, eps, norms, xyz, rotation, scaling);
-    if (!check_launch("sample_curves_forward", false, s)) return CGS_ERR_HIP;
-    return CGS_OK;
+    return finish("sample_curves_forward", s);
 }
 
 // ---------------------------------------------------------------------------------------------- fused per-view path
 // One view of the training configuration, curve parameters in, image out (and back): the per-splat chains are fused
 // (view.hip), the rasterizer is the sync-free single-pass bucket pipeline of cgs_rasterize_forward_static.
 static int64_t view_forward_wait(int handle, int64_t* n_visible) {
-    if (!slot_held(handle)) {
-        set_error("cgs_view_forward_wait: handle %d is not an outstanding checked forward", handle);
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
+    if (!slot_held(handle)) return reject("cgs_view_forward_wait: handle %d is not an outstanding checked forward", handle);
     const bool ok = slot_wait(handle, "cgs_view_forward_wait");
     const int64_t longest = (int64_t)g_slots[handle].h[1];
     if (ok && n_visible) *n_visible = g_last_visible;
@@ -840,19 +883,14 @@ static int64_t view_forward_impl(int mode, int B, int m, const float* curve_poin
                      float* scaling, void* stream_, float* out_color_clamped = nullptr, float* out_rend_dir = nullptr) {
     hipStream_t s = (hipStream_t)stream_;
     const int P = B * m;
-    if (out_rend_dir && !out_all_map) {
-        set_error("cgs_view_forward: the direction map needs the all_map output");
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
+    if (out_rend_dir && !out_all_map) return reject("cgs_view_forward: the direction map needs the all_map output");
     if (B <= 0 || m <= 0 || m > 32 || (long long)B * m >= (1ll << 28) || width_px <= 0 || height_px <= 0 || !curve_points ||
         !width || !coef || !norms ||
         !opacity_logit || !geometry_buffer || !binning_buffer || !image_buffer || bucket_capacity == 0 || !background ||
         !viewmatrix || !projmatrix || !cam_pos || !out_color || (!out_invdepth != !out_all_map) ||
-        (!out_all_map && colors_precomp) || !radii || (xyz && (!rotation || !scaling)) || !aligned16(curve_points) || !aligned16(coef) || !aligned16(rotation)) {
-        set_error("cgs_view_forward: invalid argument (B=%d m=%d W=%d H=%d, NULL / misaligned pointer or zero capacity)", B, m,
-                  width_px, height_px);
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
+        (!out_all_map && colors_precomp) || !radii || (xyz && (!rotation || !scaling)) || !aligned16(curve_points) || !aligned16(coef) || !aligned16(rotation))
+        return reject("cgs_view_forward: invalid argument (B=%d m=%d W=%d H=%d, NULL / misaligned pointer or zero capacity)", B,
+                      m, width_px, height_px);
     const Frame f(width_px, height_px, tan_fovx, tan_fovy);
     if (!bucket_cap_ok("cgs_view_forward", bucket_capacity, f.tiles, binning_bytes)) return CGS_ERR_INVALID_ARGUMENT;
     const uint64_t cap = bucket_capacity;
@@ -953,17 +991,14 @@ int cgs_view_forward_shared(int B, int m, const float* curve_points, const float
 }
 int64_t cgs_last_forward_visible(void) { return g_last_visible; }
 int cgs_visible_indices(int P, const int* radii, const void* image_buffer, int width, int height, int64_t* out_indices, void* stream_) {
-    if (P <= 0 || !radii || !image_buffer || width <= 0 || height <= 0 || !out_indices) {
-        set_error("cgs_visible_indices: invalid argument");
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
+    if (P <= 0 || !radii || !image_buffer || width <= 0 || height <= 0 || !out_indices)
+        return reject("cgs_visible_indices: invalid argument");
     const Frame f(width, height);
     char* ichunk = (char*)const_cast<void*>(image_buffer);
     ImageState img = image_from_chunk(ichunk, f.npix, (size_t)f.tiles);
     hipLaunchKernelGGL(k_visible_compact, dim3(STAT_BLOCKS), dim3(256), 0, (hipStream_t)stream_, radii, P, img.work + VIS_COUNT_WORD,
                        (long long*)out_indices);
-    if (!check_launch("visible_indices", false, (hipStream_t)stream_)) return CGS_ERR_HIP;
-    return CGS_OK;
+    return finish("visible_indices", stream_);
 }
 uint32_t cgs_bucket_capacity_hint(int P, int width, int height) {
     const int64_t mx = hints_load(P, width, height).max;
@@ -979,53 +1014,6 @@ int cgs_view_norms_backward_range(int* first, int* count) {
 // 13 floats per curve are used (16 asked for: the size stays a multiple of 64 bytes); rounds 2-5: 15 per splat
 size_t cgs_view_backward_scratch_floats(int B, int m) { (void)m; return (size_t)(B > 0 ? B : 0) * 16; }
 
-}  // extern "C"
-static int view_backward_impl(int B, int m, const float* curve_points, const float* width, const uint8_t* is_bezier, const float* coef,
-                      float eps, double* norms, const float* opacity_logit, const float* mask_logit, float mask_thr,
-                      const float* colors_precomp, void* geometry_buffer, const void* binning_buffer, const void* image_buffer, const float* background,
-                      int width_px, int height_px, const float* viewmatrix, const float* projmatrix, const float* cam_pos,
-                      float tan_fovx, float tan_fovy, const int* radii, const float* dL_dout_color,
-                      const float* dL_drotation_extra, float* dL_dmeans2D, float* dL_dcurve_points, float* dL_dwidth,
-                      float* dL_dopacity_logit, float* dL_dmask_logit, float* scratch, int flags, void* stream_,
-                      const float* clamp_raw) {
-    hipStream_t s = (hipStream_t)stream_;
-    if (clamp_raw && colors_precomp) {
-        set_error("cgs_view_backward_render: the folded clamp mask is part of the unit-colour path (no colors_precomp)");
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
-    const int P = B * m;
-    if (B <= 0 || m <= 0 || m > 32 || width_px <= 0 || height_px <= 0 || !curve_points || !width || !coef || !norms ||
-        !opacity_logit || !geometry_buffer || !binning_buffer || !image_buffer || !background || !viewmatrix || !projmatrix ||
-        !cam_pos || !radii || !dL_dout_color || !dL_dmeans2D || !dL_dcurve_points || !dL_dwidth || !dL_dopacity_logit ||
-        !scratch || (mask_logit && !dL_dmask_logit) || !aligned16(curve_points) || !aligned16(coef) ||
-        !aligned16(dL_drotation_extra) || !aligned16(dL_dcurve_points)) {
-        set_error("cgs_view_backward: invalid argument");
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
-    const Frame f(width_px, height_px, tan_fovx, tan_fovy);
-    const States b = carve_states(f, P, geometry_buffer, binning_buffer, 1, image_buffer);
-    // scratch: [B,13] per-curve partials of dL/d{curve_points, width} (k_view_bwd -> k_sample_bwd_close; curve_math.h,
-    // sample_backward_tail).  Rounds 2-5 sent 15 floats per SPLAT through here.
-    // training configuration: only dL/dcolour flows in, the colours themselves need no gradient; the forward wrote unit
-    // colours unless it was given colors_precomp (same argument here): closed-form dL/dalpha, no recurrences (render.hip, UNIT)
-    if (colors_precomp == nullptr)
-        launch_render_bwd_unit(s, f.tiles, b.img.ranges, b.bin.point_list, width_px, height_px, f.gx, background, b.geom.rec,
-                               b.img.final_T, b.img.n_contrib, dL_dout_color, b.geom.grad_acc, ACC_STRIDE_VIEW, nullptr, clamp_raw);
-    else   // arbitrary colours: the general training instance (the forward did not tag the lists)
-        launch_render_bwd(s, false, false, false, f.tiles, b.img.ranges, b.bin.point_list, width_px, height_px, f.gx, background,
-                          b.geom.rec, b.img.final_T, b.img.n_contrib, dL_dout_color, nullptr, nullptr, b.geom.grad_acc,
-                          ACC_STRIDE_VIEW);
-    launch_view_backward(s, B, m, curve_points, width, is_bezier, coef, eps, norms, opacity_logit, mask_logit, mask_thr,
-                         cam_pos, viewmatrix, projmatrix, tan_fovx, tan_fovy, f.focal_x, f.focal_y, width_px, height_px, radii,
-                         b.geom.rec, b.geom.grad_acc, dL_drotation_extra, dL_dmeans2D, dL_dopacity_logit, dL_dmask_logit, scratch,
-                         ((flags & CGS_VIEW_ACCUMULATE) ? 1 : 0) | ((flags & CGS_VIEW_SHARED) ? 2 : 0));
-    if (!(flags & CGS_VIEW_SHARED))
-        launch_sample_backward_close(s, B, m, curve_points, width, is_bezier, coef, eps, norms, scratch, dL_dcurve_points,
-                                     dL_dwidth, (flags & CGS_VIEW_ACCUMULATE) ? 1 : 0);
-    if (!check_launch("view_backward", false, s)) return CGS_ERR_HIP;
-    return CGS_OK;
-}
-extern "C" {
 int cgs_view_backward(int B, int m, const float* curve_points, const float* width, const uint8_t* is_bezier, const float* coef,
                       float eps, double* norms, const float* opacity_logit, const float* mask_logit, float mask_thr,
                       const float* colors_precomp, void* geometry_buffer, const void* binning_buffer, const void* image_buffer, const float* background,
@@ -1056,31 +1044,22 @@ int cgs_view_backward_render(int B, int m, const float* curve_points, const floa
 int cgs_view_shared_begin(int B, int m, const float* curve_points, const uint8_t* is_bezier, const float* coef, double* norms,
                           float* scratch, void* stream_) {
     hipStream_t s = (hipStream_t)stream_;
-    if (B <= 0 || m <= 0 || m > 32 || !curve_points || !coef || !norms || !scratch || !aligned16(curve_points) || !aligned16(coef)) {
-        set_error("cgs_view_shared_begin: invalid argument");
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
-    if (zero_async(scratch, cgs_view_backward_scratch_floats(B, m) * sizeof(float), s) != hipSuccess) {
-        set_error("zero_async failed");
-        return CGS_ERR_HIP;
-    }
+    if (B <= 0 || m <= 0 || m > 32 || !curve_points || !coef || !norms || !scratch || !aligned16(curve_points) || !aligned16(coef))
+        return reject("cgs_view_shared_begin: invalid argument");
+    if (!zeroed(scratch, cgs_view_backward_scratch_floats(B, m) * sizeof(float), s, "zero_async failed")) return CGS_ERR_HIP;
     launch_sample_norms(s, B, m, curve_points, is_bezier, coef, norms);
-    if (!check_launch("view_shared_begin", false, s)) return CGS_ERR_HIP;
-    return CGS_OK;
+    return finish("view_shared_begin", s);
 }
 int cgs_view_shared_end(int B, int m, const float* curve_points, const float* width, const uint8_t* is_bezier, const float* coef,
                         float eps, double* norms, float* scratch, float* dL_dcurve_points, float* dL_dwidth, int accumulate,
                         void* stream_) {
     hipStream_t s = (hipStream_t)stream_;
     if (B <= 0 || m <= 0 || m > 32 || !curve_points || !width || !coef || !norms || !scratch || !dL_dcurve_points || !dL_dwidth ||
-        !aligned16(curve_points) || !aligned16(coef) || !aligned16(dL_dcurve_points)) {
-        set_error("cgs_view_shared_end: invalid argument");
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
+        !aligned16(curve_points) || !aligned16(coef) || !aligned16(dL_dcurve_points))
+        return reject("cgs_view_shared_end: invalid argument");
     launch_sample_backward_close(s, B, m, curve_points, width, is_bezier, coef, eps, norms, scratch, dL_dcurve_points, dL_dwidth,
                                  accumulate);
-    if (!check_launch("view_shared_end", false, s)) return CGS_ERR_HIP;
-    return CGS_OK;
+    return finish("view_shared_end", s);
 }
 
 int cgs_sample_curves_backward(int B, int m, const float* curve_points, const float* width, const uint8_t* is_bezier,
@@ -1091,19 +1070,15 @@ int cgs_sample_curves_backward(int B, int m, const float* curve_points, const fl
     if (B == 0) return CGS_OK;
     if (B < 0 || m <= 0 || m > 32 || !curve_points || !width || !coef || !norms || !dL_dcurve_points || !dL_dwidth ||
         (dL_drotation && !scratch) ||
-        !aligned16(curve_points) || !aligned16(dL_drotation) || !aligned16(dL_dcurve_points) || !aligned16(coef)) {
-        set_error("cgs_sample_curves_backward: invalid argument");
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
+        !aligned16(curve_points) || !aligned16(dL_drotation) || !aligned16(dL_dcurve_points) || !aligned16(coef))
+        return reject("cgs_sample_curves_backward: invalid argument");
     // (a second backward over the same forward -- retain_graph -- must not see the first one's two sums)
-    if (zero_async(norms + sample_norm_fwd_words(), (size_t)(sample_norm_words() - sample_norm_fwd_words()) * sizeof(double), s) != hipSuccess) {
-        set_error("zero_async(norms) failed");
+    if (!zeroed(norms + sample_norm_fwd_words(), (size_t)(sample_norm_words() - sample_norm_fwd_words()) * sizeof(double), s,
+                "zero_async(norms) failed"))
         return CGS_ERR_HIP;
-    }
     launch_sample_backward(s, B, m, curve_points, width, is_bezier, coef, eps, norms, dL_dxyz, dL_drotation, dL_dscaling,
                            dL_dcurve_points, dL_dwidth, scratch);
-    if (!check_launch("sample_curves_backward", false, s)) return CGS_ERR_HIP;
-    return CGS_OK;
+    return finish("sample_curves_backward", s);
 }
 
 int cgs_splat_attrs_forward(int B, int m, const float* rotation_raw, const float* xyz, const float* opacity_logit,
@@ -1113,14 +1088,11 @@ int cgs_splat_attrs_forward(int B, int m, const float* rotation_raw, const float
     hipStream_t s = (hipStream_t)stream_;
     if (B == 0) return CGS_OK;
     if (B < 0 || m <= 0 || !rotation_raw || !xyz || !opacity_logit || !campos || !viewmatrix || !rotation_n || !opacity ||
-        !all_map || (scaling_out && !scaling) || !aligned16(rotation_raw) || !aligned16(rotation_n) || !aligned16(all_map)) {
-        set_error("cgs_splat_attrs_forward: invalid argument");
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
+        !all_map || (scaling_out && !scaling) || !aligned16(rotation_raw) || !aligned16(rotation_n) || !aligned16(all_map))
+        return reject("cgs_splat_attrs_forward: invalid argument");
     launch_attrs_forward(s, B, m, rotation_raw, xyz, opacity_logit, mask_logit, mask_thr, scaling, campos, viewmatrix,
                          rotation_n, opacity, scaling_out, all_map);
-    if (!check_launch("splat_attrs_forward", false, s)) return CGS_ERR_HIP;
-    return CGS_OK;
+    return finish("splat_attrs_forward", s);
 }
 
 int cgs_splat_attrs_backward(int B, int m, const float* rotation_raw, const float* xyz, const float* opacity_logit,
@@ -1132,15 +1104,12 @@ int cgs_splat_attrs_backward(int B, int m, const float* rotation_raw, const floa
     if (B == 0) return CGS_OK;
     if (B < 0 || m <= 0 || !rotation_raw || !xyz || !opacity_logit || !campos || !viewmatrix || !dL_drotation_raw ||
         !dL_dopacity_logit || !aligned16(rotation_raw) || !aligned16(dL_drotation_n) || !aligned16(dL_dall_map) ||
-        !aligned16(dL_drotation_raw)) {
-        set_error("cgs_splat_attrs_backward: invalid argument");
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
+        !aligned16(dL_drotation_raw))
+        return reject("cgs_splat_attrs_backward: invalid argument");
     launch_attrs_backward(s, B, m, rotation_raw, xyz, opacity_logit, mask_logit, mask_thr, scaling, campos, viewmatrix,
                           dL_drotation_n, dL_dopacity, dL_dscaling_out, dL_dall_map, dL_drotation_raw, dL_dopacity_logit,
                           dL_dmask_logit, dL_dscaling);
-    if (!check_launch("splat_attrs_backward", false, s)) return CGS_ERR_HIP;
-    return CGS_OK;
+    return finish("splat_attrs_backward", s);
 }
 
 
@@ -1149,14 +1118,11 @@ int cgs_ssim_forward(int batch, int channels, int height, int width, float C1, f
                      void* stream_) {
     if (batch * channels == 0 || height == 0 || width == 0) return CGS_OK;
     if (batch < 0 || channels < 0 || height < 0 || width < 0 || !img1 || !img2 || !ssim_map ||
-        (dm_dmu1 && (!dm_dsigma1_sq || !dm_dsigma12)) || (long long)batch * channels > 65535) {
-        set_error("cgs_ssim_forward: invalid argument");
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
+        (dm_dmu1 && (!dm_dsigma1_sq || !dm_dsigma12)) || (long long)batch * channels > 65535)
+        return reject("cgs_ssim_forward: invalid argument");
     launch_ssim_fwd((hipStream_t)stream_, batch * channels, height, width, C1, C2, img1, img2, ssim_map, dm_dmu1,
                     dm_dsigma1_sq, dm_dsigma12);
-    if (!check_launch("ssim_forward", false, (hipStream_t)stream_)) return CGS_ERR_HIP;
-    return CGS_OK;
+    return finish("ssim_forward", stream_);
 }
 
 int cgs_ssim_backward(int batch, int channels, int height, int width, float C1, float C2, const float* img1,
@@ -1166,30 +1132,21 @@ int cgs_ssim_backward(int batch, int channels, int height, int width, float C1, 
     (void)C2;
     if (batch * channels == 0 || height == 0 || width == 0) return CGS_OK;
     if (batch < 0 || channels < 0 || height < 0 || width < 0 || !img1 || !img2 || !dL_dmap || !dm_dmu1 ||
-        !dm_dsigma1_sq || !dm_dsigma12 || !dL_dimg1 || (long long)batch * channels > 65535) {
-        set_error("cgs_ssim_backward: invalid argument");
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
+        !dm_dsigma1_sq || !dm_dsigma12 || !dL_dimg1 || (long long)batch * channels > 65535)
+        return reject("cgs_ssim_backward: invalid argument");
     launch_ssim_bwd((hipStream_t)stream_, batch * channels, height, width, img1, img2, dL_dmap, dm_dmu1, dm_dsigma1_sq,
                     dm_dsigma12, dL_dimg1);
-    if (!check_launch("ssim_backward", false, (hipStream_t)stream_)) return CGS_ERR_HIP;
-    return CGS_OK;
+    return finish("ssim_backward", stream_);
 }
 
 int cgs_edge_aware_loss(int channels, int height, int width, const float* image, const float* gt, float threshold,
                         void* scratch16, float* dL_dimage, void* stream_) {
     hipStream_t s = (hipStream_t)stream_;
-    if (channels <= 0 || height <= 0 || width <= 0 || !image || !gt || !scratch16) {
-        set_error("cgs_edge_aware_loss: invalid argument");
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
-    if (zero_async(scratch16, 16, s) != hipSuccess) {
-        set_error("zero_async failed");
-        return CGS_ERR_HIP;
-    }
+    if (channels <= 0 || height <= 0 || width <= 0 || !image || !gt || !scratch16)
+        return reject("cgs_edge_aware_loss: invalid argument");
+    if (!zeroed(scratch16, 16, s, "zero_async failed")) return CGS_ERR_HIP;
     launch_edge_aware_loss(s, channels, height, width, image, gt, threshold, scratch16, dL_dimage);
-    if (!check_launch("edge_aware_loss", false, s)) return CGS_ERR_HIP;
-    return CGS_OK;
+    return finish("edge_aware_loss", s);
 }
 
 size_t cgs_photometric_workspace_bytes(int height, int width) {
@@ -1197,69 +1154,49 @@ size_t cgs_photometric_workspace_bytes(int height, int width) {
 }
 int cgs_render_epilogue(int height, int width, const float* color_raw, const float* all_map, const float* viewmatrix, int clamp,
                         float* color_out, float* dir_out, void* stream_) {
-    if (height <= 0 || width <= 0 || (color_out && !color_raw) || (dir_out && (!all_map || !viewmatrix))) {
-        set_error("cgs_render_epilogue: invalid argument");
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
+    if (height <= 0 || width <= 0 || (color_out && !color_raw) || (dir_out && (!all_map || !viewmatrix)))
+        return reject("cgs_render_epilogue: invalid argument");
     if (!color_out && !dir_out) return CGS_OK;
-    const size_t npix = (size_t)height * width;
-    hipLaunchKernelGGL(k_render_epilogue, dim3((unsigned)std::min<size_t>((npix + 255) / 256, 4096)), dim3(256), 0, (hipStream_t)stream_,
-                       npix, color_raw, all_map, viewmatrix, clamp, color_out, dir_out);
-    if (!check_launch("render_epilogue", false, (hipStream_t)stream_)) return CGS_ERR_HIP;
-    return CGS_OK;
+    launch_render_epilogue((hipStream_t)stream_, (size_t)height * width, color_raw, all_map, viewmatrix, clamp, color_out, dir_out);
+    return finish("render_epilogue", stream_);
 }
 int cgs_clamp_backward(int64_t n, const float* raw, const float* g_in, float* g_out, void* stream_) {
-    if (n < 0 || (n > 0 && (!raw || !g_in || !g_out))) {
-        set_error("cgs_clamp_backward: invalid argument");
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
+    if (n < 0 || (n > 0 && (!raw || !g_in || !g_out))) return reject("cgs_clamp_backward: invalid argument");
     if (n == 0) return CGS_OK;
     hipLaunchKernelGGL(k_clamp_backward, dim3((unsigned)std::min<size_t>(((size_t)n + 255) / 256, 4096)), dim3(256), 0, (hipStream_t)stream_,
                        (size_t)n, raw, g_in, g_out);
-    if (!check_launch("clamp_backward", false, (hipStream_t)stream_)) return CGS_ERR_HIP;
-    return CGS_OK;
+    return finish("clamp_backward", stream_);
 }
 
 int cgs_edge_count(int channels, int height, int width, const float* gt, float threshold, uint32_t* n_pos, void* stream_) {
-    if (channels <= 0 || height <= 0 || width <= 0 || !gt || !n_pos) {
-        set_error("cgs_edge_count: invalid argument");
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
+    if (channels <= 0 || height <= 0 || width <= 0 || !gt || !n_pos) return reject("cgs_edge_count: invalid argument");
     hipStream_t s = (hipStream_t)stream_;
-    if (zero_async(n_pos, sizeof(uint32_t), s) != hipSuccess) {
-        set_error("cgs_edge_count: zero_async failed");
-        return CGS_ERR_HIP;
-    }
+    if (!zeroed(n_pos, sizeof(uint32_t), s, "cgs_edge_count: zero_async failed")) return CGS_ERR_HIP;
     launch_edge_count(s, channels, height * width, gt, threshold, n_pos);
-    if (!check_launch("edge_count", false, s)) return CGS_ERR_HIP;
-    return CGS_OK;
+    return finish("edge_count", s);
+}
+// cgs_photometric_loss (the view's own target and edge count: no view_index) and cgs_photometric_loss_indexed, as `name`
+static int photometric_loss(const char* name, int height, int width, const float* image, const float* gt, const int* view_index,
+                            float threshold, const uint32_t* n_pos, float lambda_edge, float lambda_ssim, int clamp_input,
+                            void* workspace, float* dL_dimage, float* loss, void* stream_) {
+    if (height <= 0 || width <= 0 || !image || !gt || !n_pos || !workspace || !dL_dimage || !loss)
+        return reject("cgs_%s: invalid argument", name);
+    launch_photometric_loss((hipStream_t)stream_, height, width, image, gt, view_index, threshold, n_pos, lambda_edge, lambda_ssim,
+                            clamp_input, workspace, dL_dimage, loss);
+    return finish(name, stream_);
 }
 int cgs_photometric_loss(int height, int width, const float* image, const float* gt, float threshold,
                          const uint32_t* n_pos, float lambda_edge, float lambda_ssim, int clamp_input, void* workspace,
                          float* dL_dimage, float* loss, void* stream_) {
-    if (height <= 0 || width <= 0 || !image || !gt || !n_pos || !workspace || !dL_dimage || !loss) {
-        set_error("cgs_photometric_loss: invalid argument");
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
-    hipStream_t s = (hipStream_t)stream_;
-    launch_photometric_loss(s, height, width, image, gt, nullptr, threshold, n_pos, lambda_edge, lambda_ssim, clamp_input,
-                            workspace, dL_dimage, loss);
-    if (!check_launch("photometric_loss", false, s)) return CGS_ERR_HIP;
-    return CGS_OK;
+    return photometric_loss("photometric_loss", height, width, image, gt, nullptr, threshold, n_pos, lambda_edge, lambda_ssim,
+                            clamp_input, workspace, dL_dimage, loss, stream_);
 }
 int cgs_photometric_loss_indexed(int height, int width, const float* image, const float* gt_stack, const int* view_index,
                                  float threshold, const uint32_t* n_pos_table, float lambda_edge, float lambda_ssim,
                                  int clamp_input, void* workspace, float* dL_dimage, float* loss, void* stream_) {
-    if (height <= 0 || width <= 0 || !image || !gt_stack || !view_index || !n_pos_table || !workspace || !dL_dimage ||
-        !loss) {
-        set_error("cgs_photometric_loss_indexed: invalid argument");
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
-    hipStream_t s = (hipStream_t)stream_;
-    launch_photometric_loss(s, height, width, image, gt_stack, view_index, threshold, n_pos_table, lambda_edge, lambda_ssim,
-                            clamp_input, workspace, dL_dimage, loss);
-    if (!check_launch("photometric_loss_indexed", false, s)) return CGS_ERR_HIP;
-    return CGS_OK;
+    if (!view_index) return reject("cgs_photometric_loss_indexed: invalid argument");
+    return photometric_loss("photometric_loss_indexed", height, width, image, gt_stack, view_index, threshold, n_pos_table,
+                            lambda_edge, lambda_ssim, clamp_input, workspace, dL_dimage, loss, stream_);
 }
 
 size_t cgs_curve_regularizers_workspace_bytes(void) { return curve_reg_workspace_bytes(); }
@@ -1269,16 +1206,13 @@ int cgs_curve_regularizers(int B, int m, const float* rotation_raw, const float*
                            float* dL_dopacity_logit, float* dL_dwidth_log, void* stream_) {
     if (B <= 0 || m < 2 || m > 32 || 256 / m < 1 || !rotation_raw || !opacity_logit || !width_log || !radii || !workspace ||
         !loss || !dL_drotation_raw || !dL_dopacity_logit || !dL_dwidth_log || !aligned16(rotation_raw) ||
-        !aligned16(dL_drotation_raw)) {
-        set_error("cgs_curve_regularizers: invalid argument (NULL / misaligned pointer, B=%d m=%d)", B, m);
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
+        !aligned16(dL_drotation_raw))
+        return reject("cgs_curve_regularizers: invalid argument (NULL / misaligned pointer, B=%d m=%d)", B, m);
     hipStream_t s = (hipStream_t)stream_;
     launch_curve_regularizers(s, B, m, rotation_raw, opacity_logit, width_log, radii, w_opacity, opacity_gate, w_smooth,
                               w_width, width_threshold, workspace, loss, dL_drotation_raw, dL_dopacity_logit,
                               dL_dwidth_log);
-    if (!check_launch("curve_regularizers", false, s)) return CGS_ERR_HIP;
-    return CGS_OK;
+    return finish("curve_regularizers", s);
 }
 
 int cgs_adam_step_flat(int64_t n, float* params, float* grads, float* exp_avg, float* exp_avg_sq,
@@ -1286,58 +1220,51 @@ int cgs_adam_step_flat(int64_t n, float* params, float* grads, float* exp_avg, f
                        int zero_grads, void* stream_) {
     if (n == 0) return CGS_OK;
     if (n < 0 || !params || !grads || !exp_avg || !exp_avg_sq || !segments || n_segments <= 0 ||
-        n_segments > adam_max_segments() || step <= 0) {
-        set_error("cgs_adam_step_flat: invalid argument");
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
+        n_segments > adam_max_segments() || step <= 0)
+        return reject("cgs_adam_step_flat: invalid argument");
     const double bc1 = 1.0 - pow((double)beta1, (double)step);
     const double bc2 = 1.0 - pow((double)beta2, (double)step);
     launch_adam_flat((hipStream_t)stream_, (long long)n, params, grads, exp_avg, exp_avg_sq, segments, n_segments, beta1,
                      beta2, eps, (float)bc1, (float)sqrt(bc2), zero_grads);
-    if (!check_launch("adam_step_flat", false, (hipStream_t)stream_)) return CGS_ERR_HIP;
-    return CGS_OK;
+    return finish("adam_step_flat", stream_);
 }
 
+// The two device-state Adam entries, as `name` (without a report: NULL, NULL, 0, launch_adam_flat_dev's own defaults)
+static int adam_step_flat_dev(const char* name, int64_t n, float* params, float* grads, float* exp_avg, float* exp_avg_sq,
+                              const void* device_state, int n_segments, float beta1, float beta2, float eps, int zero_grads,
+                              const uint32_t* skip_flag, uint32_t* report_seq, uint32_t* report_ring, int report_len,
+                              void* stream_) {
+    if (n == 0) return CGS_OK;
+    if (n < 0 || !params || !grads || !exp_avg || !exp_avg_sq || !device_state || n_segments <= 0 ||
+        n_segments > adam_max_segments())
+        return reject("cgs_%s: invalid argument", name);
+    launch_adam_flat_dev((hipStream_t)stream_, (long long)n, params, grads, exp_avg, exp_avg_sq, device_state, n_segments,
+                         beta1, beta2, eps, zero_grads, skip_flag, report_seq, report_ring, report_len);
+    return finish(name, stream_);
+}
 int cgs_adam_step_flat_dev(int64_t n, float* params, float* grads, float* exp_avg, float* exp_avg_sq,
                            const void* device_state, int n_segments, float beta1, float beta2, float eps, int zero_grads,
                            const uint32_t* skip_flag, void* stream_) {
-    if (n == 0) return CGS_OK;
-    if (n < 0 || !params || !grads || !exp_avg || !exp_avg_sq || !device_state || n_segments <= 0 ||
-        n_segments > adam_max_segments()) {
-        set_error("cgs_adam_step_flat_dev: invalid argument");
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
-    launch_adam_flat_dev((hipStream_t)stream_, (long long)n, params, grads, exp_avg, exp_avg_sq, device_state, n_segments,
-                         beta1, beta2, eps, zero_grads, skip_flag);
-    if (!check_launch("adam_step_flat_dev", false, (hipStream_t)stream_)) return CGS_ERR_HIP;
-    return CGS_OK;
+    return adam_step_flat_dev("adam_step_flat_dev", n, params, grads, exp_avg, exp_avg_sq, device_state, n_segments, beta1, beta2,
+                              eps, zero_grads, skip_flag, nullptr, nullptr, 0, stream_);
 }
 int cgs_adam_step_flat_dev_report(int64_t n, float* params, float* grads, float* exp_avg, float* exp_avg_sq,
                                   const void* device_state, int n_segments, float beta1, float beta2, float eps, int zero_grads,
                                   const uint32_t* skip_flag, uint32_t* report_seq, uint32_t* report_ring, int report_len,
                                   void* stream_) {
-    if (n == 0) return CGS_OK;
-    if (n < 0 || !params || !grads || !exp_avg || !exp_avg_sq || !device_state || n_segments <= 0 ||
-        n_segments > adam_max_segments() || !report_seq || !report_ring || report_len <= 0) {
-        set_error("cgs_adam_step_flat_dev_report: invalid argument");
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
-    launch_adam_flat_dev((hipStream_t)stream_, (long long)n, params, grads, exp_avg, exp_avg_sq, device_state, n_segments,
-                         beta1, beta2, eps, zero_grads, skip_flag, report_seq, report_ring, report_len);
-    if (!check_launch("adam_step_flat_dev_report", false, (hipStream_t)stream_)) return CGS_ERR_HIP;
-    return CGS_OK;
+    if (n != 0 && (!report_seq || !report_ring || report_len <= 0))   // (an empty step needs no report)
+        return reject("cgs_adam_step_flat_dev_report: invalid argument");
+    return adam_step_flat_dev("adam_step_flat_dev_report", n, params, grads, exp_avg, exp_avg_sq, device_state, n_segments, beta1,
+                              beta2, eps, zero_grads, skip_flag, report_seq, report_ring, report_len, stream_);
 }
 size_t cgs_endpoint_connection_workspace_bytes(int B) { return endpoint_connection_workspace_bytes(B > 0 ? B : 1); }
 int cgs_endpoint_connection_loss(int B, const float* curve_points, float distance_threshold, float weight, void* workspace,
                                  float* loss, float* dL_dcurve_points, int accumulate, void* stream_) {
-    if (B <= 0 || !curve_points || !workspace || !loss || !dL_dcurve_points || !(distance_threshold > 0.f)) {
-        set_error("cgs_endpoint_connection_loss: invalid argument (NULL pointer, B=%d or threshold <= 0)", B);
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
+    if (B <= 0 || !curve_points || !workspace || !loss || !dL_dcurve_points || !(distance_threshold > 0.f))
+        return reject("cgs_endpoint_connection_loss: invalid argument (NULL pointer, B=%d or threshold <= 0)", B);
     hipStream_t s = (hipStream_t)stream_;
     launch_endpoint_connection(s, B, curve_points, distance_threshold, weight, workspace, loss, dL_dcurve_points, accumulate);
-    if (!check_launch("endpoint_connection_loss", false, s)) return CGS_ERR_HIP;
-    return CGS_OK;
+    return finish("endpoint_connection_loss", s);
 }
 
 size_t cgs_adam_state_bytes(void) { return adam_state_bytes(); }
@@ -1346,133 +1273,92 @@ size_t cgs_knn_workspace_bytes(int P) { return knn_workspace_bytes(P); }
 
 int cgs_knn_mean_dist2(int P, const float* points, float* mean_dist2, void* workspace, void* stream_) {
     if (P == 0) return CGS_OK;
-    if (P < 0 || !points || !mean_dist2 || !workspace) {
-        set_error("cgs_knn_mean_dist2: invalid argument");
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
+    if (P < 0 || !points || !mean_dist2 || !workspace) return reject("cgs_knn_mean_dist2: invalid argument");
     launch_knn((hipStream_t)stream_, P, points, mean_dist2, workspace);
-    if (!check_launch("knn_mean_dist2", false, (hipStream_t)stream_)) return CGS_ERR_HIP;
-    return CGS_OK;
+    return finish("knn_mean_dist2", stream_);
 }
 
 size_t cgs_nn1_workspace_bytes(int n_query) { return nn1_workspace_bytes(n_query); }
 
 int cgs_nn1(int n_query, const float* query, int n_ref, const float* ref, float* dist, int* index, void* workspace,
             void* stream_) {
-    if (n_query < 0 || n_ref < 0 || n_query > (1 << 30) || n_ref > (1 << 30)) {
-        set_error("cgs_nn1: invalid argument (n_query=%d, n_ref=%d)", n_query, n_ref);
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
+    if (n_query < 0 || n_ref < 0 || n_query > (1 << 30) || n_ref > (1 << 30))
+        return reject("cgs_nn1: invalid argument (n_query=%d, n_ref=%d)", n_query, n_ref);
     if (n_query == 0) return CGS_OK;
-    if (n_ref == 0 || !query || !ref || !dist || !index || !workspace) {
-        set_error("cgs_nn1: invalid argument (NULL pointer or an empty reference set, n_ref=%d)", n_ref);
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
+    if (n_ref == 0 || !query || !ref || !dist || !index || !workspace)
+        return reject("cgs_nn1: invalid argument (NULL pointer or an empty reference set, n_ref=%d)", n_ref);
     launch_nn1((hipStream_t)stream_, n_query, query, n_ref, ref, dist, index, workspace);
-    if (!check_launch("nn1", false, (hipStream_t)stream_)) return CGS_ERR_HIP;
-    return CGS_OK;
+    return finish("nn1", stream_);
 }
 
 int cgs_edge_visibility(int n_curves, const double* curves, int n_lines, const double* lines, int n_frames,
                         const double* K, const double* w2c, int height, int width, const unsigned char* maps,
                         int invert, int* counts, void* stream_) {
-    if (n_curves < 0 || n_lines < 0 || n_frames < 0 || (long long)n_curves + n_lines > (1 << 30)) {
-        set_error("cgs_edge_visibility: invalid argument (n_curves=%d, n_lines=%d, n_frames=%d)", n_curves, n_lines,
-                  n_frames);
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
+    if (n_curves < 0 || n_lines < 0 || n_frames < 0 || (long long)n_curves + n_lines > (1 << 30))
+        return reject("cgs_edge_visibility: invalid argument (n_curves=%d, n_lines=%d, n_frames=%d)", n_curves, n_lines,
+                      n_frames);
     if (n_curves + n_lines == 0) return CGS_OK;
-    if (n_frames > 0 && (height <= 0 || width <= 0)) {
-        set_error("cgs_edge_visibility: invalid argument (height=%d, width=%d)", height, width);
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
+    if (n_frames > 0 && (height <= 0 || width <= 0))
+        return reject("cgs_edge_visibility: invalid argument (height=%d, width=%d)", height, width);
     if ((n_curves > 0 && !curves) || (n_lines > 0 && !lines) || !counts ||
-        (n_frames > 0 && (!K || !w2c || !maps))) {
-        set_error("cgs_edge_visibility: invalid argument (NULL pointer)");
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
+        (n_frames > 0 && (!K || !w2c || !maps)))
+        return reject("cgs_edge_visibility: invalid argument (NULL pointer)");
     launch_edge_visibility((hipStream_t)stream_, n_curves, curves, n_lines, lines, n_frames, K, w2c, height, width,
                            maps, invert, counts);
-    if (!check_launch("edge_visibility", false, (hipStream_t)stream_)) return CGS_ERR_HIP;
-    return CGS_OK;
+    return finish("edge_visibility", stream_);
 }
 
 int cgs_densification_stats(int64_t P, const int* radii, const float* dL_dmeans2D, int64_t grad_stride, float* max_radii2D,
                             float* xyz_gradient_accum, float* denom, const uint32_t* skip_flag, void* stream_) {
-    if (P < 0 || grad_stride < 2) {
-        set_error("cgs_densification_stats: invalid argument (P=%lld, grad_stride=%lld)", (long long)P, (long long)grad_stride);
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
+    if (P < 0 || grad_stride < 2)
+        return reject("cgs_densification_stats: invalid argument (P=%lld, grad_stride=%lld)", (long long)P,
+                      (long long)grad_stride);
     if (P == 0) return CGS_OK;
-    if (!radii || !dL_dmeans2D || !max_radii2D || !xyz_gradient_accum || !denom) {
-        set_error("cgs_densification_stats: invalid argument (NULL pointer)");
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
+    if (!radii || !dL_dmeans2D || !max_radii2D || !xyz_gradient_accum || !denom)
+        return reject("cgs_densification_stats: invalid argument (NULL pointer)");
     launch_densification_stats((hipStream_t)stream_, (long long)P, radii, dL_dmeans2D, (long long)grad_stride, max_radii2D,
                                xyz_gradient_accum, denom, skip_flag);
-    if (!check_launch("densification_stats", false, (hipStream_t)stream_)) return CGS_ERR_HIP;
-    return CGS_OK;
+    return finish("densification_stats", stream_);
 }
 
 size_t cgs_view_metrics_workspace_bytes(int n_views) { return view_metrics_workspace_bytes(n_views); }
 
 int cgs_view_metrics(int n_views, const cgs_metric_view* views, void* workspace, double* sums, double* means,
                      void* stream_) {
-    if (n_views < 0 || n_views > 65535) {
-        set_error("cgs_view_metrics: invalid argument (n_views=%d)", n_views);
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
+    if (n_views < 0 || n_views > 65535) return reject("cgs_view_metrics: invalid argument (n_views=%d)", n_views);
     if (n_views == 0) return CGS_OK;
-    if (!views || !workspace || !sums) {
-        set_error("cgs_view_metrics: invalid argument (NULL pointer)");
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
+    if (!views || !workspace || !sums) return reject("cgs_view_metrics: invalid argument (NULL pointer)");
     for (int v = 0; v < n_views; v++) {
         const cgs_metric_view& d = views[v];
-        if (!d.image || !d.gt) {
-            set_error("cgs_view_metrics: invalid argument (view %d: NULL pointer)", v);
-            return CGS_ERR_INVALID_ARGUMENT;
-        }
-        if (d.channels <= 0 || d.height <= 0 || d.width <= 0 || d.x0 < 0 || d.x0 >= d.width) {
-            set_error("cgs_view_metrics: invalid argument (view %d: channels=%d, height=%d, width=%d, x0=%d)", v,
-                      d.channels, d.height, d.width, d.x0);
-            return CGS_ERR_INVALID_ARGUMENT;
-        }
+        if (!d.image || !d.gt) return reject("cgs_view_metrics: invalid argument (view %d: NULL pointer)", v);
+        if (d.channels <= 0 || d.height <= 0 || d.width <= 0 || d.x0 < 0 || d.x0 >= d.width)
+            return reject("cgs_view_metrics: invalid argument (view %d: channels=%d, height=%d, width=%d, x0=%d)", v,
+                          d.channels, d.height, d.width, d.x0);
     }
     if (launch_view_metrics((hipStream_t)stream_, n_views, views, workspace, sums, means) != hipSuccess) {
         set_error("cgs_view_metrics: descriptor copy failed");
         return CGS_ERR_HIP;
     }
-    if (!check_launch("view_metrics", false, (hipStream_t)stream_)) return CGS_ERR_HIP;
-    return CGS_OK;
+    return finish("view_metrics", stream_);
 }
 
 size_t cgs_report_panels_workspace_bytes(int n_views) { return report_panels_workspace_bytes(n_views); }
 
 int cgs_report_panels(int n_views, cgs_report_view* views, void* workspace, unsigned char* out, void* stream_) {
-    if (n_views < 0 || n_views > CGS_REPORT_MAX_VIEWS) {
-        set_error("cgs_report_panels: invalid argument (n_views=%d, at most %d per call)", n_views, CGS_REPORT_MAX_VIEWS);
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
+    if (n_views < 0 || n_views > CGS_REPORT_MAX_VIEWS)
+        return reject("cgs_report_panels: invalid argument (n_views=%d, at most %d per call)", n_views, CGS_REPORT_MAX_VIEWS);
     if (n_views == 0) return CGS_OK;
-    if (!views || !workspace || !out) {
-        set_error("cgs_report_panels: invalid argument (NULL pointer)");
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
+    if (!views || !workspace || !out) return reject("cgs_report_panels: invalid argument (NULL pointer)");
     for (int v = 0; v < n_views; v++) {
         const cgs_report_view& d = views[v];
-        if (d.height <= 0 || d.width <= 0 || (d.gt && d.gt_channels != 1 && d.gt_channels != 3)) {
-            set_error("cgs_report_panels: invalid argument (view %d: gt_channels=%d, height=%d, width=%d)", v, d.gt_channels,
-                      d.height, d.width);
-            return CGS_ERR_INVALID_ARGUMENT;
-        }
+        if (d.height <= 0 || d.width <= 0 || (d.gt && d.gt_channels != 1 && d.gt_channels != 3))
+            return reject("cgs_report_panels: invalid argument (view %d: gt_channels=%d, height=%d, width=%d)", v,
+                          d.gt_channels, d.height, d.width);
         const size_t bytes = (size_t)CGS_REPORT_PANELS * 3 * (size_t)d.height * (size_t)d.width;
         for (int u = 0; u < v; u++) {
             const size_t other = (size_t)CGS_REPORT_PANELS * 3 * (size_t)views[u].height * (size_t)views[u].width;
-            if (d.out_offset < views[u].out_offset + other && views[u].out_offset < d.out_offset + bytes) {
-                set_error("cgs_report_panels: invalid argument (the output ranges of views %d and %d overlap)", u, v);
-                return CGS_ERR_INVALID_ARGUMENT;
-            }
+            if (d.out_offset < views[u].out_offset + other && views[u].out_offset < d.out_offset + bytes)
+                return reject("cgs_report_panels: invalid argument (the output ranges of views %d and %d overlap)", u, v);
         }
     }
     for (int v = 0; v < n_views; v++) {
@@ -1481,30 +1367,16 @@ int cgs_report_panels(int n_views, cgs_report_view* views, void* workspace, unsi
                     (d.rend_alpha ? 16u : 0u);
     }
     launch_report_panels((hipStream_t)stream_, n_views, views, workspace, out);
-    if (!check_launch("report_panels", false, (hipStream_t)stream_)) return CGS_ERR_HIP;
-    return CGS_OK;
-}
-
-// The tail of an entry whose launches are queued: the launch check on the entry's stream.
-static int finish(const char* what, void* stream_) {
-    return check_launch(what, false, (hipStream_t)stream_) ? CGS_OK : CGS_ERR_HIP;
+    return finish("report_panels", stream_);
 }
 
 int cgs_project_points(int P, const float* points, int V, const double* intr, const double* w2c, int height, int width,
                        double* uv_out, void* stream_) {
-    if (P < 0 || V < 0 || (long long)P * V > (1LL << 40)) {
-        set_error("cgs_project_points: invalid argument (P=%d, V=%d)", P, V);
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
+    if (P < 0 || V < 0 || (long long)P * V > (1LL << 40))
+        return reject("cgs_project_points: invalid argument (P=%d, V=%d)", P, V);
     if (P == 0 || V == 0) return CGS_OK;
-    if (height <= 0 || width <= 0) {
-        set_error("cgs_project_points: invalid argument (height=%d, width=%d)", height, width);
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
-    if (!points || !intr || !w2c || !uv_out) {
-        set_error("cgs_project_points: invalid argument (NULL pointer)");
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
+    if (height <= 0 || width <= 0) return reject("cgs_project_points: invalid argument (height=%d, width=%d)", height, width);
+    if (!points || !intr || !w2c || !uv_out) return reject("cgs_project_points: invalid argument (NULL pointer)");
     launch_project_points((hipStream_t)stream_, P, points, V, intr, w2c, height, width, uv_out);
     return finish("project_points", stream_);
 }
@@ -1516,25 +1388,17 @@ size_t cgs_render_points_workspace_bytes(int P, int V, int height, int width) {
 int cgs_render_points(int P, const float* points, const float* colors, int V, const double* intr, const double* w2c,
                       int height, int width, double alpha, const double* background, float* out, int* kept,
                       void* workspace, size_t workspace_bytes, void* stream_) {
-    if (P < 0 || V < 0 || height <= 0 || width <= 0 || (long long)height * width > (1LL << 31)) {
-        set_error("cgs_render_points: invalid argument (P=%d, V=%d, height=%d, width=%d)", P, V, height, width);
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
-    if (!(alpha >= 0.0 && alpha <= 1.0)) {
-        set_error("cgs_render_points: invalid argument (alpha=%g, need 0 <= alpha <= 1)", alpha);
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
+    if (P < 0 || V < 0 || height <= 0 || width <= 0 || (long long)height * width > (1LL << 31))
+        return reject("cgs_render_points: invalid argument (P=%d, V=%d, height=%d, width=%d)", P, V, height, width);
+    if (!(alpha >= 0.0 && alpha <= 1.0))
+        return reject("cgs_render_points: invalid argument (alpha=%g, need 0 <= alpha <= 1)", alpha);
     if (V == 0) return CGS_OK;
-    if (!intr || !w2c || !background || !out || !workspace || (P > 0 && (!points || !colors))) {
-        set_error("cgs_render_points: invalid argument (NULL pointer)");
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
+    if (!intr || !w2c || !background || !out || !workspace || (P > 0 && (!points || !colors)))
+        return reject("cgs_render_points: invalid argument (NULL pointer)");
     const int per = render_points_views_per_chunk(P, V, height, width, workspace_bytes);
-    if (per <= 0) {
-        set_error("cgs_render_points: invalid argument (workspace of %zu bytes holds no view; one view needs %zu)",
-                  workspace_bytes, render_points_workspace_bytes(P, 1, height, width));
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
+    if (per <= 0)
+        return reject("cgs_render_points: invalid argument (workspace of %zu bytes holds no view; one view needs %zu)",
+                      workspace_bytes, render_points_workspace_bytes(P, 1, height, width));
     launch_render_points((hipStream_t)stream_, P, points, colors, V, intr, w2c, height, width, alpha, background, out,
                          kept, workspace, per);
     return finish("render_points", stream_);
@@ -1559,62 +1423,39 @@ int64_t cgs_ellipsoid_mesh_body_bytes(int P, int resolution, int64_t* vertex_byt
 
 int cgs_ellipsoid_mesh_vertices(int first, int count, const float* xyz, const float* rot, const float* scale,
                                 const float* rgb, int V0, const double* unit_vertices, void* out, void* stream_) {
-    if (first < 0 || count < 0 || V0 <= 0 || (long long)(first + (long long)count) * V0 > (1LL << 31)) {
-        set_error("cgs_ellipsoid_mesh_vertices: invalid argument (first=%d, count=%d, V0=%d)", first, count, V0);
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
+    if (first < 0 || count < 0 || V0 <= 0 || (long long)(first + (long long)count) * V0 > (1LL << 31))
+        return reject("cgs_ellipsoid_mesh_vertices: invalid argument (first=%d, count=%d, V0=%d)", first, count, V0);
     if (count == 0) return CGS_OK;
-    if (!xyz || !rot || !scale || !rgb || !unit_vertices || !out) {
-        set_error("cgs_ellipsoid_mesh_vertices: invalid argument (NULL pointer)");
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
-    if ((uintptr_t)out % 16) {
-        set_error("cgs_ellipsoid_mesh_vertices: out must be 16-byte aligned");
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
+    if (!xyz || !rot || !scale || !rgb || !unit_vertices || !out)
+        return reject("cgs_ellipsoid_mesh_vertices: invalid argument (NULL pointer)");
+    if ((uintptr_t)out % 16) return reject("cgs_ellipsoid_mesh_vertices: out must be 16-byte aligned");
     launch_ellipsoid_vertices((hipStream_t)stream_, first, count, xyz, rot, scale, rgb, V0, unit_vertices, out);
     return finish("ellipsoid_mesh_vertices", stream_);
 }
 
 int cgs_ellipsoid_mesh_faces(int first, int count, int V0, int F0, const int* template_faces, void* out, void* stream_) {
-    if (first < 0 || count < 0 || V0 <= 0 || F0 <= 0) {
-        set_error("cgs_ellipsoid_mesh_faces: invalid argument (first=%d, count=%d, V0=%d, F0=%d)", first, count, V0, F0);
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
-    if ((long long)(first + (long long)count) * V0 > (1LL << 31)) {
-        set_error("cgs_ellipsoid_mesh_faces: splats [%d, %d) of %d vertices: a vertex index would not fit in an int",
-                  first, first + count, V0);
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
+    if (first < 0 || count < 0 || V0 <= 0 || F0 <= 0)
+        return reject("cgs_ellipsoid_mesh_faces: invalid argument (first=%d, count=%d, V0=%d, F0=%d)", first, count, V0, F0);
+    if ((long long)(first + (long long)count) * V0 > (1LL << 31))
+        return reject("cgs_ellipsoid_mesh_faces: splats [%d, %d) of %d vertices: a vertex index would not fit in an int",
+                      first, first + count, V0);
     if (count == 0) return CGS_OK;
-    if (!template_faces || !out) {
-        set_error("cgs_ellipsoid_mesh_faces: invalid argument (NULL pointer)");
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
-    if ((uintptr_t)out % 16) {
-        set_error("cgs_ellipsoid_mesh_faces: out must be 16-byte aligned");
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
+    if (!template_faces || !out) return reject("cgs_ellipsoid_mesh_faces: invalid argument (NULL pointer)");
+    if ((uintptr_t)out % 16) return reject("cgs_ellipsoid_mesh_faces: out must be 16-byte aligned");
     launch_ellipsoid_faces((hipStream_t)stream_, first, count, V0, F0, template_faces, out);
     return finish("ellipsoid_mesh_faces", stream_);
 }
 
 int cgs_curve_straightness(int B, const float* curve_points, const uint8_t* is_bezier, int sample_num, double threshold,
                            double threshold_max, double* mean_dist, double* max_dist, uint8_t* straight, void* stream_) {
-    if (B < 0 || B > (1 << 24) || sample_num < 2 || sample_num > CGS_CURVE_FIT_MAX_SAMPLES) {
-        set_error("cgs_curve_straightness: invalid argument (B=%d, sample_num=%d, need 2 <= sample_num <= %d)", B, sample_num,
-                  CGS_CURVE_FIT_MAX_SAMPLES);
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
-    if (threshold != threshold || threshold_max != threshold_max) {
-        set_error("cgs_curve_straightness: invalid argument (a threshold is NaN)");
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
+    if (B < 0 || B > (1 << 24) || sample_num < 2 || sample_num > CGS_CURVE_FIT_MAX_SAMPLES)
+        return reject("cgs_curve_straightness: invalid argument (B=%d, sample_num=%d, need 2 <= sample_num <= %d)", B,
+                      sample_num, CGS_CURVE_FIT_MAX_SAMPLES);
+    if (threshold != threshold || threshold_max != threshold_max)
+        return reject("cgs_curve_straightness: invalid argument (a threshold is NaN)");
     if (B == 0) return CGS_OK;
-    if (!curve_points || !is_bezier || !mean_dist || !max_dist || !straight) {
-        set_error("cgs_curve_straightness: invalid argument (NULL pointer)");
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
+    if (!curve_points || !is_bezier || !mean_dist || !max_dist || !straight)
+        return reject("cgs_curve_straightness: invalid argument (NULL pointer)");
     launch_curve_straightness((hipStream_t)stream_, B, curve_points, is_bezier, sample_num, threshold, threshold_max,
                               mean_dist, max_dist, straight);
     return finish("curve_straightness", stream_);
@@ -1624,18 +1465,12 @@ size_t cgs_segment_merge_workspace_bytes(int n) { return segment_merge_workspace
 
 int cgs_segment_merge_labels(int n, const float* seg, double distance_threshold, double similarity_threshold,
                              void* workspace, int* labels, int* n_components, void* stream_) {
-    if (n < 0 || n > CGS_SEGMENT_MERGE_MAX) {
-        set_error("cgs_segment_merge_labels: invalid argument (n=%d, need 0 <= n <= %d)", n, CGS_SEGMENT_MERGE_MAX);
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
-    if (distance_threshold != distance_threshold || similarity_threshold != similarity_threshold) {
-        set_error("cgs_segment_merge_labels: invalid argument (a threshold is NaN)");
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
-    if (!n_components || (n > 0 && (!seg || !workspace || !labels))) {
-        set_error("cgs_segment_merge_labels: invalid argument (NULL pointer)");
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
+    if (n < 0 || n > CGS_SEGMENT_MERGE_MAX)
+        return reject("cgs_segment_merge_labels: invalid argument (n=%d, need 0 <= n <= %d)", n, CGS_SEGMENT_MERGE_MAX);
+    if (distance_threshold != distance_threshold || similarity_threshold != similarity_threshold)
+        return reject("cgs_segment_merge_labels: invalid argument (a threshold is NaN)");
+    if (!n_components || (n > 0 && (!seg || !workspace || !labels)))
+        return reject("cgs_segment_merge_labels: invalid argument (NULL pointer)");
     if (n == 0) {
         if (hipMemsetAsync(n_components, 0, sizeof(int), (hipStream_t)stream_) != hipSuccess) {
             set_error("cgs_segment_merge_labels: hipMemsetAsync failed");
@@ -1650,98 +1485,65 @@ int cgs_segment_merge_labels(int n, const float* seg, double distance_threshold,
 
 int cgs_pair_consensus_fit(int B, const float* curve_points, int K, const int* pairs, int sample_num, double ransac_thresh,
                            double error_threshold, float* ctrl, double* rmse, int* inliers, uint8_t* ok, void* stream_) {
-    if (B < 0 || K < 0 || B > (1 << 24) || K > (1 << 24) || sample_num < 2 || sample_num > CGS_CURVE_FIT_MAX_SAMPLES) {
-        set_error("cgs_pair_consensus_fit: invalid argument (B=%d, K=%d, sample_num=%d, need 2 <= sample_num <= %d)", B, K,
-                  sample_num, CGS_CURVE_FIT_MAX_SAMPLES);
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
-    if (ransac_thresh != ransac_thresh || error_threshold != error_threshold) {
-        set_error("cgs_pair_consensus_fit: invalid argument (a threshold is NaN)");
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
+    if (B < 0 || K < 0 || B > (1 << 24) || K > (1 << 24) || sample_num < 2 || sample_num > CGS_CURVE_FIT_MAX_SAMPLES)
+        return reject("cgs_pair_consensus_fit: invalid argument (B=%d, K=%d, sample_num=%d, need 2 <= sample_num <= %d)", B, K,
+                      sample_num, CGS_CURVE_FIT_MAX_SAMPLES);
+    if (ransac_thresh != ransac_thresh || error_threshold != error_threshold)
+        return reject("cgs_pair_consensus_fit: invalid argument (a threshold is NaN)");
     if (K == 0) return CGS_OK;
-    if (B == 0 || !curve_points || !pairs || !ctrl || !rmse || !inliers || !ok) {
-        set_error("cgs_pair_consensus_fit: invalid argument (NULL pointer or pairs without curves, B=%d)", B);
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
+    if (B == 0 || !curve_points || !pairs || !ctrl || !rmse || !inliers || !ok)
+        return reject("cgs_pair_consensus_fit: invalid argument (NULL pointer or pairs without curves, B=%d)", B);
     launch_pair_consensus_fit((hipStream_t)stream_, K, curve_points, pairs, sample_num, ransac_thresh, error_threshold, ctrl,
                               rmse, inliers, ok);
     return finish("pair_consensus_fit", stream_);
 }
 
 int cgs_undistort_images(int n_views, const cgs_undistort_view* views, float fill, int* blank_counts, void* stream_) {
-    if (n_views < 0 || n_views > CGS_UNDISTORT_MAX_VIEWS) {
-        set_error("cgs_undistort_images: invalid argument (n_views=%d, at most %d per call)", n_views, CGS_UNDISTORT_MAX_VIEWS);
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
+    if (n_views < 0 || n_views > CGS_UNDISTORT_MAX_VIEWS)
+        return reject("cgs_undistort_images: invalid argument (n_views=%d, at most %d per call)", n_views,
+                      CGS_UNDISTORT_MAX_VIEWS);
     if (n_views == 0) return CGS_OK;
-    if (!views || !blank_counts) {
-        set_error("cgs_undistort_images: invalid argument (NULL pointer)");
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
-    if (!std::isfinite(fill)) {
-        set_error("cgs_undistort_images: invalid argument (fill is not finite)");
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
+    if (!views || !blank_counts) return reject("cgs_undistort_images: invalid argument (NULL pointer)");
+    if (!std::isfinite(fill)) return reject("cgs_undistort_images: invalid argument (fill is not finite)");
     for (int v = 0; v < n_views; v++) {
         const cgs_undistort_view& d = views[v];
-        if (!d.src || !d.dst || d.src == d.dst) {
-            set_error("cgs_undistort_images: invalid argument (view %d: NULL pointer or dst == src)", v);
-            return CGS_ERR_INVALID_ARGUMENT;
-        }
-        if (d.channels < 1 || d.channels > CGS_UNDISTORT_MAX_CHANNELS || d.height <= 0 || d.width <= 0) {
-            set_error("cgs_undistort_images: invalid argument (view %d: channels=%d (1..%d), height=%d, width=%d)", v, d.channels,
-                      CGS_UNDISTORT_MAX_CHANNELS, d.height, d.width);
-            return CGS_ERR_INVALID_ARGUMENT;
-        }
-        if (d.model != 0 && d.model != 1 && d.model != 2 && d.model != 3 && d.model != 4 && d.model != 6) {
-            set_error("cgs_undistort_images: invalid argument (view %d: camera model id %d is not supported: SIMPLE_PINHOLE 0, "
-                      "PINHOLE 1, SIMPLE_RADIAL 2, RADIAL 3, OPENCV 4 and FULL_OPENCV 6 are)", v, d.model);
-            return CGS_ERR_INVALID_ARGUMENT;
-        }
+        if (!d.src || !d.dst || d.src == d.dst)
+            return reject("cgs_undistort_images: invalid argument (view %d: NULL pointer or dst == src)", v);
+        if (d.channels < 1 || d.channels > CGS_UNDISTORT_MAX_CHANNELS || d.height <= 0 || d.width <= 0)
+            return reject("cgs_undistort_images: invalid argument (view %d: channels=%d (1..%d), height=%d, width=%d)", v,
+                          d.channels, CGS_UNDISTORT_MAX_CHANNELS, d.height, d.width);
+        if (d.model != 0 && d.model != 1 && d.model != 2 && d.model != 3 && d.model != 4 && d.model != 6)
+            return reject("cgs_undistort_images: invalid argument (view %d: camera model id %d is not supported: SIMPLE_PINHOLE 0, "
+                          "PINHOLE 1, SIMPLE_RADIAL 2, RADIAL 3, OPENCV 4 and FULL_OPENCV 6 are)", v, d.model);
         const double focals[4] = {d.fx, d.fy, d.out_fx, d.out_fy};
         for (double f : focals) {
-            if (!(f > 0.0) || !std::isfinite(f)) {
-                set_error("cgs_undistort_images: invalid argument (view %d: focal lengths fx=%g, fy=%g, out_fx=%g, out_fy=%g must "
-                          "be positive and finite)", v, d.fx, d.fy, d.out_fx, d.out_fy);
-                return CGS_ERR_INVALID_ARGUMENT;
-            }
+            if (!(f > 0.0) || !std::isfinite(f))
+                return reject("cgs_undistort_images: invalid argument (view %d: focal lengths fx=%g, fy=%g, out_fx=%g, out_fy=%g must "
+                              "be positive and finite)", v, d.fx, d.fy, d.out_fx, d.out_fy);
         }
         bool finite = std::isfinite(d.cx) && std::isfinite(d.cy);
         for (double k : d.k) finite = finite && std::isfinite(k);
-        if (!finite) {
-            set_error("cgs_undistort_images: invalid argument (view %d: a principal point or coefficient is not finite)", v);
-            return CGS_ERR_INVALID_ARGUMENT;
-        }
+        if (!finite)
+            return reject("cgs_undistort_images: invalid argument (view %d: a principal point or coefficient is not finite)",
+                          v);
     }
     launch_undistort_images((hipStream_t)stream_, n_views, views, fill, blank_counts);
     return finish("undistort_images", stream_);
 }
 
 int cgs_edge_gradients(int n_views, const cgs_edge_gradient_view* views, const float* taps, int radius, void* stream_) {
-    if (n_views < 1 || n_views > CGS_EDGE_MAX_VIEWS) {
-        set_error("cgs_edge_gradients: invalid argument (n_views=%d, 1..%d per call)", n_views, CGS_EDGE_MAX_VIEWS);
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
-    if (!views || !taps) {
-        set_error("cgs_edge_gradients: invalid argument (NULL pointer)");
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
-    if (radius < 0 || radius > CGS_EDGE_MAX_RADIUS) {
-        set_error("cgs_edge_gradients: invalid argument (radius=%d, 0..%d)", radius, CGS_EDGE_MAX_RADIUS);
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
+    if (n_views < 1 || n_views > CGS_EDGE_MAX_VIEWS)
+        return reject("cgs_edge_gradients: invalid argument (n_views=%d, 1..%d per call)", n_views, CGS_EDGE_MAX_VIEWS);
+    if (!views || !taps) return reject("cgs_edge_gradients: invalid argument (NULL pointer)");
+    if (radius < 0 || radius > CGS_EDGE_MAX_RADIUS)
+        return reject("cgs_edge_gradients: invalid argument (radius=%d, 0..%d)", radius, CGS_EDGE_MAX_RADIUS);
     for (int v = 0; v < n_views; v++) {
         const cgs_edge_gradient_view& d = views[v];
-        if (!d.pixels || !d.gx || !d.gy || !d.m) {
-            set_error("cgs_edge_gradients: invalid argument (view %d: NULL pointer)", v);
-            return CGS_ERR_INVALID_ARGUMENT;
-        }
-        if (d.height <= 0 || d.width <= 0 || (d.channels != 1 && d.channels != 3 && d.channels != 4)) {
-            set_error("cgs_edge_gradients: invalid argument (view %d: height=%d, width=%d, channels=%d (1, 3 or 4))", v, d.height,
-                      d.width, d.channels);
-            return CGS_ERR_INVALID_ARGUMENT;
-        }
+        if (!d.pixels || !d.gx || !d.gy || !d.m)
+            return reject("cgs_edge_gradients: invalid argument (view %d: NULL pointer)", v);
+        if (d.height <= 0 || d.width <= 0 || (d.channels != 1 && d.channels != 3 && d.channels != 4))
+            return reject("cgs_edge_gradients: invalid argument (view %d: height=%d, width=%d, channels=%d (1, 3 or 4))", v,
+                          d.height, d.width, d.channels);
     }
     launch_edge_gradients((hipStream_t)stream_, n_views, views, taps, radius);
     return finish("edge_gradients", stream_);
@@ -1749,28 +1551,17 @@ int cgs_edge_gradients(int n_views, const cgs_edge_gradient_view* views, const f
 
 int cgs_edge_trace(int n_views, const cgs_edge_trace_view* views, float low, float high, int thin, int* changed_flag,
                    void* stream_) {
-    if (n_views < 1 || n_views > CGS_EDGE_MAX_VIEWS) {
-        set_error("cgs_edge_trace: invalid argument (n_views=%d, 1..%d per call)", n_views, CGS_EDGE_MAX_VIEWS);
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
-    if (!views || !changed_flag) {
-        set_error("cgs_edge_trace: invalid argument (NULL pointer)");
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
-    if (!(low > 0.0f) || !(low <= high) || !std::isfinite(high)) {   // (a NaN compares false)
-        set_error("cgs_edge_trace: invalid argument (low=%g, high=%g: need 0 < low <= high, finite)", low, high);
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
+    if (n_views < 1 || n_views > CGS_EDGE_MAX_VIEWS)
+        return reject("cgs_edge_trace: invalid argument (n_views=%d, 1..%d per call)", n_views, CGS_EDGE_MAX_VIEWS);
+    if (!views || !changed_flag) return reject("cgs_edge_trace: invalid argument (NULL pointer)");
+    if (!(low > 0.0f) || !(low <= high) || !std::isfinite(high))   // (a NaN compares false)
+        return reject("cgs_edge_trace: invalid argument (low=%g, high=%g: need 0 < low <= high, finite)", low, high);
     for (int v = 0; v < n_views; v++) {
         const cgs_edge_trace_view& d = views[v];
-        if (!d.gx || !d.gy || !d.m || !d.e || !d.state) {
-            set_error("cgs_edge_trace: invalid argument (view %d: NULL pointer)", v);
-            return CGS_ERR_INVALID_ARGUMENT;
-        }
-        if (d.height <= 0 || d.width <= 0) {
-            set_error("cgs_edge_trace: invalid argument (view %d: height=%d, width=%d)", v, d.height, d.width);
-            return CGS_ERR_INVALID_ARGUMENT;
-        }
+        if (!d.gx || !d.gy || !d.m || !d.e || !d.state)
+            return reject("cgs_edge_trace: invalid argument (view %d: NULL pointer)", v);
+        if (d.height <= 0 || d.width <= 0)
+            return reject("cgs_edge_trace: invalid argument (view %d: height=%d, width=%d)", v, d.height, d.width);
     }
     hipError_t err = hipSuccess;
     const int rounds = launch_edge_trace((hipStream_t)stream_, n_views, views, low, high, thin, changed_flag, &err);
@@ -1784,19 +1575,10 @@ int cgs_edge_trace(int n_views, const cgs_edge_trace_view* views, float low, flo
 
 int cgs_point_mask(int P, const float* points, int V, const double* intr, const double* w2c, int height, int width,
                    uint8_t* mask_out, int* kept, void* stream_) {
-    if (P < 0 || V < 0) {
-        set_error("cgs_point_mask: invalid argument (P=%d, V=%d)", P, V);
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
+    if (P < 0 || V < 0) return reject("cgs_point_mask: invalid argument (P=%d, V=%d)", P, V);
     if (V == 0) return CGS_OK;
-    if (height <= 0 || width <= 0) {
-        set_error("cgs_point_mask: invalid argument (height=%d, width=%d)", height, width);
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
-    if (!intr || !w2c || !mask_out || (P > 0 && !points)) {
-        set_error("cgs_point_mask: invalid argument (NULL pointer)");
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
+    if (height <= 0 || width <= 0) return reject("cgs_point_mask: invalid argument (height=%d, width=%d)", height, width);
+    if (!intr || !w2c || !mask_out || (P > 0 && !points)) return reject("cgs_point_mask: invalid argument (NULL pointer)");
     if (launch_point_mask((hipStream_t)stream_, P, points, V, intr, w2c, height, width, mask_out, kept) != hipSuccess) {
         set_error("cgs_point_mask: clearing the mask failed");
         return CGS_ERR_HIP;
@@ -1814,16 +1596,11 @@ size_t cgs_edt_workspace_bytes(int V, int height, int width) {
 }
 
 int cgs_edt_squared(int V, int height, int width, const uint8_t* mask, void* workspace, int32_t* dist2_out, void* stream_) {
-    if (V < 0 || !edt_size_ok(height, width)) {
-        set_error("cgs_edt_squared: invalid argument (V=%d, height=%d, width=%d; sizes lie in [1, %d])", V, height, width,
-                  CGS_EDT_MAX_SIZE);
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
+    if (V < 0 || !edt_size_ok(height, width))
+        return reject("cgs_edt_squared: invalid argument (V=%d, height=%d, width=%d; sizes lie in [1, %d])", V, height, width,
+                      CGS_EDT_MAX_SIZE);
     if (V == 0) return CGS_OK;
-    if (!mask || !workspace || !dist2_out) {
-        set_error("cgs_edt_squared: invalid argument (NULL pointer)");
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
+    if (!mask || !workspace || !dist2_out) return reject("cgs_edt_squared: invalid argument (NULL pointer)");
     launch_edt_squared((hipStream_t)stream_, V, height, width, mask, workspace, dist2_out);
     return finish("edt_squared", stream_);
 }
@@ -1833,24 +1610,14 @@ size_t cgs_edge_score_workspace_bytes(int V) { return edge_score_workspace_bytes
 int cgs_edge_score_reduce(int V, int height, int width, const uint8_t* pred_mask, const uint8_t* det_mask,
                           const int32_t* pred_dist2, const int32_t* det_dist2, int n_tol, const int* tol2, void* workspace,
                           int64_t* counts, double* sums, uint8_t* both_nonempty, void* stream_) {
-    if (V < 0 || !edt_size_ok(height, width) || n_tol < 0 || n_tol > CGS_EDGE_SCORE_MAX_TOL) {
-        set_error("cgs_edge_score_reduce: invalid argument (V=%d, height=%d, width=%d, n_tol=%d)", V, height, width, n_tol);
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
-    if (n_tol > 0 && !tol2) {
-        set_error("cgs_edge_score_reduce: invalid argument (NULL pointer)");
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
+    if (V < 0 || !edt_size_ok(height, width) || n_tol < 0 || n_tol > CGS_EDGE_SCORE_MAX_TOL)
+        return reject("cgs_edge_score_reduce: invalid argument (V=%d, height=%d, width=%d, n_tol=%d)", V, height, width, n_tol);
+    if (n_tol > 0 && !tol2) return reject("cgs_edge_score_reduce: invalid argument (NULL pointer)");
     for (int t = 0; t < n_tol; t++)
-        if (tol2[t] < 0) {
-            set_error("cgs_edge_score_reduce: invalid argument (tol2[%d]=%d)", t, tol2[t]);
-            return CGS_ERR_INVALID_ARGUMENT;
-        }
+        if (tol2[t] < 0) return reject("cgs_edge_score_reduce: invalid argument (tol2[%d]=%d)", t, tol2[t]);
     if (V == 0) return CGS_OK;
-    if (!pred_mask || !det_mask || !pred_dist2 || !det_dist2 || !workspace || !counts || !sums || !both_nonempty) {
-        set_error("cgs_edge_score_reduce: invalid argument (NULL pointer)");
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
+    if (!pred_mask || !det_mask || !pred_dist2 || !det_dist2 || !workspace || !counts || !sums || !both_nonempty)
+        return reject("cgs_edge_score_reduce: invalid argument (NULL pointer)");
     if (launch_edge_score_reduce((hipStream_t)stream_, V, height, width, pred_mask, det_mask, pred_dist2, det_dist2, n_tol,
                                  tol2, workspace, counts, sums, both_nonempty) != hipSuccess) {
         set_error("cgs_edge_score_reduce: clearing the counters failed");
@@ -1860,16 +1627,11 @@ int cgs_edge_score_reduce(int V, int height, int width, const uint8_t* pred_mask
 }
 
 int cgs_pack_near_bits(int V, int height, int width, const int32_t* dist2, int tol2, uint32_t* bits_out, void* stream_) {
-    if (V < 0 || !edt_size_ok(height, width) || tol2 < 0) {
-        set_error("cgs_pack_near_bits: invalid argument (V=%d, height=%d, width=%d, tol2=%d; sizes lie in [1, %d])", V,
-                  height, width, tol2, CGS_EDT_MAX_SIZE);
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
+    if (V < 0 || !edt_size_ok(height, width) || tol2 < 0)
+        return reject("cgs_pack_near_bits: invalid argument (V=%d, height=%d, width=%d, tol2=%d; sizes lie in [1, %d])", V,
+                      height, width, tol2, CGS_EDT_MAX_SIZE);
     if (V == 0) return CGS_OK;
-    if (!dist2 || !bits_out) {
-        set_error("cgs_pack_near_bits: invalid argument (NULL pointer)");
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
+    if (!dist2 || !bits_out) return reject("cgs_pack_near_bits: invalid argument (NULL pointer)");
     launch_pack_near_bits((hipStream_t)stream_, V, height, width, dist2, tol2, bits_out);
     return finish("pack_near_bits", stream_);
 }
@@ -1911,10 +1673,7 @@ int cgs_voxel_votes(int nx, int ny, int nz, const double* lo, const double* step
     if (!seed_views_ok("cgs_voxel_votes", V, height, width) ||
         !seed_grid_ok("cgs_voxel_votes", nx, ny, nz, ptrs ? lo : nullptr, ptrs ? step : nullptr))
         return CGS_ERR_INVALID_ARGUMENT;
-    if (!ptrs) {
-        set_error("cgs_voxel_votes: invalid argument (NULL pointer)");
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
+    if (!ptrs) return reject("cgs_voxel_votes: invalid argument (NULL pointer)");
     if (V == 0 && accumulate) return CGS_OK;
     launch_voxel_votes((hipStream_t)stream_, SeedGrid{{lo[0], lo[1], lo[2]}, {step[0], step[1], step[2]}, nx, ny, nz},
                        SeedViews{V, height, width, (width + 31) / 32, intr, w2c, bits}, accumulate, seen, hit);
@@ -1923,16 +1682,11 @@ int cgs_voxel_votes(int nx, int ny, int nz, const double* lo, const double* step
 
 int cgs_voxel_moments(int nx, int ny, int nz, const void* keep_bits, int N, const void* centres, int radius, void* moments,
                       void* stream_) {
-    if (N < 0 || radius < 1 || radius > CGS_SEED_MAX_RADIUS) {
-        set_error("cgs_voxel_moments: invalid argument (N=%d, radius=%d; the radius lies in [1, %d])", N, radius,
-                  CGS_SEED_MAX_RADIUS);
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
+    if (N < 0 || radius < 1 || radius > CGS_SEED_MAX_RADIUS)
+        return reject("cgs_voxel_moments: invalid argument (N=%d, radius=%d; the radius lies in [1, %d])", N, radius,
+                      CGS_SEED_MAX_RADIUS);
     if (!seed_grid_ok("cgs_voxel_moments", nx, ny, nz, nullptr, nullptr)) return CGS_ERR_INVALID_ARGUMENT;
-    if (!keep_bits || !centres || !moments) {
-        set_error("cgs_voxel_moments: invalid argument (NULL pointer)");
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
+    if (!keep_bits || !centres || !moments) return reject("cgs_voxel_moments: invalid argument (NULL pointer)");
     if (N == 0) return CGS_OK;
     launch_voxel_moments((hipStream_t)stream_, nx, ny, nz, (const unsigned int*)keep_bits, N, (const int*)centres, radius,
                          (int*)moments);
@@ -1942,16 +1696,11 @@ int cgs_voxel_moments(int nx, int ny, int nz, const void* keep_bits, int N, cons
 int cgs_ray_claims(int nx, int ny, int nz, const double* lo, const double* step, int M, const int32_t* index,
                    const uint16_t* support, int V, const double* intr, const double* w2c, int height, int width,
                    const uint32_t* bits, int clear, uint32_t* best, void* stream_) {
-    if (M < 0) {
-        set_error("cgs_ray_claims: invalid argument (M=%d)", M);
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
+    if (M < 0) return reject("cgs_ray_claims: invalid argument (M=%d)", M);
     if (!seed_views_ok("cgs_ray_claims", V, height, width) || !seed_grid_ok("cgs_ray_claims", nx, ny, nz, lo, step))
         return CGS_ERR_INVALID_ARGUMENT;
-    if (!lo || !step || (V > 0 && !best) || (M > 0 && V > 0 && (!index || !support || !intr || !w2c || !bits))) {
-        set_error("cgs_ray_claims: invalid argument (NULL pointer)");
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
+    if (!lo || !step || (V > 0 && !best) || (M > 0 && V > 0 && (!index || !support || !intr || !w2c || !bits)))
+        return reject("cgs_ray_claims: invalid argument (NULL pointer)");
     const SeedGrid g{{lo[0], lo[1], lo[2]}, {step[0], step[1], step[2]}, nx, ny, nz};
     const SeedViews views{V, height, width, (width + 31) / 32, intr, w2c, bits};
     if (launch_ray_claims((hipStream_t)stream_, g, views, M, index, support, clear, best) != hipSuccess) {
@@ -1966,25 +1715,16 @@ int cgs_ray_wins(int nx, int ny, int nz, const double* lo, const double* step, i
                  const uint16_t* support, int V, const double* intr, const double* w2c, int height, int width,
                  const uint32_t* bits, const uint32_t* best, int window, int margin, int accumulate, uint16_t* wins,
                  void* stream_) {
-    if (M < 0) {
-        set_error("cgs_ray_wins: invalid argument (M=%d)", M);
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
+    if (M < 0) return reject("cgs_ray_wins: invalid argument (M=%d)", M);
     if (!seed_views_ok("cgs_ray_wins", V, height, width) || !seed_grid_ok("cgs_ray_wins", nx, ny, nz, lo, step))
         return CGS_ERR_INVALID_ARGUMENT;
-    if (!lo || !step) {   // before the window and the margin, as it always was
-        set_error("cgs_ray_wins: invalid argument (NULL pointer)");
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
-    if (window < 0 || window > CGS_SEED_MAX_WINDOW || margin < 0 || margin > 65535) {
-        set_error("cgs_ray_wins: invalid argument (window=%d, margin=%d; the window lies in [0, %d], the margin in [0, 65535])",
-                  window, margin, CGS_SEED_MAX_WINDOW);
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
-    if (M > 0 && V > 0 && (!index || !support || !intr || !w2c || !bits || !best || !wins)) {
-        set_error("cgs_ray_wins: invalid argument (NULL pointer)");
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
+    if (!lo || !step)   // before the window and the margin, as it always was
+        return reject("cgs_ray_wins: invalid argument (NULL pointer)");
+    if (window < 0 || window > CGS_SEED_MAX_WINDOW || margin < 0 || margin > 65535)
+        return reject("cgs_ray_wins: invalid argument (window=%d, margin=%d; the window lies in [0, %d], the margin in [0, 65535])",
+                      window, margin, CGS_SEED_MAX_WINDOW);
+    if (M > 0 && V > 0 && (!index || !support || !intr || !w2c || !bits || !best || !wins))
+        return reject("cgs_ray_wins: invalid argument (NULL pointer)");
     if (M == 0 || V == 0) return CGS_OK;
     launch_ray_wins((hipStream_t)stream_, SeedGrid{{lo[0], lo[1], lo[2]}, {step[0], step[1], step[2]}, nx, ny, nz},
                     SeedViews{V, height, width, (width + 31) / 32, intr, w2c, bits}, M, index, support, best, window, margin,
@@ -1995,40 +1735,29 @@ int cgs_ray_wins(int nx, int ny, int nz, const double* lo, const double* step, i
 int cgs_edge_support(int E, int P, const float* points, const int32_t* offsets, int V, const double* intr,
                      const double* w2c, int height, int width, const int32_t* d2, int T, const int32_t* tol2,
                      int32_t* counts, void* stream_) {
-    if (E < 0 || P < 0 || V < 0 || T < 1 || T > CGS_EDGE_SUPPORT_MAX_TOL) {
-        set_error("cgs_edge_support: invalid argument (E=%d, P=%d, V=%d, T=%d; T lies in [1, %d])", E, P, V, T,
-                  CGS_EDGE_SUPPORT_MAX_TOL);
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
+    if (E < 0 || P < 0 || V < 0 || T < 1 || T > CGS_EDGE_SUPPORT_MAX_TOL)
+        return reject("cgs_edge_support: invalid argument (E=%d, P=%d, V=%d, T=%d; T lies in [1, %d])", E, P, V, T,
+                      CGS_EDGE_SUPPORT_MAX_TOL);
     if (E == 0 || V == 0) return CGS_OK;
-    if (!edt_size_ok(height, width)) {   // d2 is a cgs_edt_squared transform
-        set_error("cgs_edge_support: invalid argument (height=%d, width=%d; sizes lie in [1, %d])", height, width,
-                  CGS_EDT_MAX_SIZE);
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
-    if (!offsets || !intr || !w2c || !d2 || !tol2 || !counts || (P > 0 && !points)) {
-        set_error("cgs_edge_support: invalid argument (NULL pointer)");
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
+    if (!edt_size_ok(height, width))   // d2 is a cgs_edt_squared transform
+        return reject("cgs_edge_support: invalid argument (height=%d, width=%d; sizes lie in [1, %d])", height, width,
+                      CGS_EDT_MAX_SIZE);
+    if (!offsets || !intr || !w2c || !d2 || !tol2 || !counts || (P > 0 && !points))
+        return reject("cgs_edge_support: invalid argument (NULL pointer)");
     launch_edge_support((hipStream_t)stream_, E, P, points, offsets, V, intr, w2c, height, width, d2, T, tol2, counts);
     return finish("edge_support", stream_);
 }
 
 int cgs_thin_masks(int V, int height, int width, uint8_t* masks, uint8_t* scratch, int* changed_flag, int max_iterations,
                    int* iterations_out, void* stream_) {
-    if (V < 0 || !edt_size_ok(height, width) || max_iterations < 0) {
-        set_error("cgs_thin_masks: invalid argument (V=%d, height=%d, width=%d, max_iterations=%d; sizes lie in [1, %d])", V,
-                  height, width, max_iterations, CGS_EDT_MAX_SIZE);
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
+    if (V < 0 || !edt_size_ok(height, width) || max_iterations < 0)
+        return reject("cgs_thin_masks: invalid argument (V=%d, height=%d, width=%d, max_iterations=%d; sizes lie in [1, %d])",
+                      V, height, width, max_iterations, CGS_EDT_MAX_SIZE);
     if (V == 0) {
         if (iterations_out) *iterations_out = 0;
         return CGS_OK;
     }
-    if (!masks || !scratch || !changed_flag) {
-        set_error("cgs_thin_masks: invalid argument (NULL pointer)");
-        return CGS_ERR_INVALID_ARGUMENT;
-    }
+    if (!masks || !scratch || !changed_flag) return reject("cgs_thin_masks: invalid argument (NULL pointer)");
     hipError_t err = hipSuccess;
     int iterations = 0;
     const int passes = launch_thin_masks((hipStream_t)stream_, V, height, width, masks, scratch, changed_flag, max_iterations,

@@ -483,7 +483,7 @@ __device__ __forceinline__ int lane_id() { return __builtin_amdgcn_mbcnt_hi(~0u,
 #endif  // __HIPCC__
 
 // ---------------------------------------------------------------- host-side launch bookkeeping
-void set_error(const char* fmt, ...);
+void set_error(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
 struct ProfScope {  // brackets one kernel launch with events when profiling is enabled
     ProfScope(const char* name, hipStream_t s);
     ~ProfScope();
