@@ -117,6 +117,7 @@ SIGNATURES = {
     "cgs_ray_claims": (_i, [_i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _i, _vp, _vp]),
     "cgs_ray_wins": (_i, [_i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "cgs_edge_support": (_i, [_i, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp]),
+    "cgs_sample_support": (_i, [_i, _vp, _i, _vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp]),
     "cgs_thin_masks": (_i, [_i, _i, _i, _vp, _vp, _vp, _i, C.POINTER(_i), _vp]),
 }
 

@@ -1748,6 +1748,21 @@ int cgs_edge_support(int E, int P, const float* points, const int32_t* offsets, 
     return finish("edge_support", stream_);
 }
 
+int cgs_sample_support(int P, const float* points, int V, const double* intr, const double* w2c, int height, int width,
+                       const int32_t* d2, int T, const int32_t* tol2, int32_t* tally, void* stream_) {
+    if (P < 0 || V < 0 || T < 1 || T > CGS_EDGE_SUPPORT_MAX_TOL)
+        return reject("cgs_sample_support: invalid argument (P=%d, V=%d, T=%d; T lies in [1, %d])", P, V, T,
+                      CGS_EDGE_SUPPORT_MAX_TOL);
+    if (!edt_size_ok(height, width))   // d2 is a cgs_edt_squared transform
+        return reject("cgs_sample_support: invalid argument (height=%d, width=%d; sizes lie in [1, %d])", height, width,
+                      CGS_EDT_MAX_SIZE);
+    if (!intr || !w2c || !d2 || !tol2 || (P > 0 && (!points || !tally)))
+        return reject("cgs_sample_support: invalid argument (NULL pointer; P=%d, V=%d)", P, V);
+    if (P == 0 || V == 0) return CGS_OK;   // nothing to add
+    launch_sample_support((hipStream_t)stream_, P, points, V, intr, w2c, height, width, d2, T, tol2, tally);
+    return finish("sample_support", stream_);
+}
+
 int cgs_thin_masks(int V, int height, int width, uint8_t* masks, uint8_t* scratch, int* changed_flag, int max_iterations,
                    int* iterations_out, void* stream_) {
     if (V < 0 || !edt_size_ok(height, width) || max_iterations < 0)

@@ -241,6 +241,10 @@ void launch_ray_wins(hipStream_t s, SeedGrid g, SeedViews views, int M, const in
 void launch_edge_support(hipStream_t s, int E, int P, const float* points, const int* offsets, int V, const double* intr,
                          const double* w2c, int height, int width, const int* d2, int T, const int* tol2, int* counts);
 
+// edge_trim.hip
+void launch_sample_support(hipStream_t s, int P, const float* points, int V, const double* intr, const double* w2c,
+                           int height, int width, const int* d2, int T, const int* tol2, int* tally);
+
 // edge_thin.hip
 int launch_thin_masks(hipStream_t s, int V, int height, int width, uint8_t* masks, uint8_t* scratch, int* changed_flag,
                       int max_iterations, int* iterations, hipError_t* err);

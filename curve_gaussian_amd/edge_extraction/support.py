@@ -9,7 +9,11 @@ rule counts supporting frames and does not pool; a thick detector response infla
 
 ``python -m curve_gaussian_amd.edge_extraction.support --base_dir <predictions> --dataset_dir <scans>`` checks every scan,
 writes ``<base_dir>/<scan>/edge_support.json`` -- one record per edge -- and, with ``--write_filtered``,
-``parametric_edges_supported.json`` with the kept edges.  ``parametric_edges.json`` is never written."""
+``parametric_edges_supported.json`` with the kept edges.  With ``--trim`` every edge of ``parametric_edges.json`` -- not only
+the kept ones: the verdict drops an over-long true edge whole -- is also cut down to the spans of its length that the images
+show (``ops.edge_trim``; its docstring freezes the rule and states the limits: no depth, duplicates are not merged, UNTUNED
+defaults): ``parametric_edges_trimmed.json`` and ``edge_trim.json``, one record per edge.  ``parametric_edges.json`` is never
+written."""
 import argparse
 import json
 import logging
@@ -19,6 +23,7 @@ import sys
 import numpy as np
 
 from ..ops import edge_support as SP
+from ..ops import edge_trim as ET
 from .para_edge import EDGE_MAX_THRESHOLD, EDGE_VISIBILITY_FRAMES_RATIO
 from .reprojection import (LAYOUTS, SAMPLE_RESOLUTION, _json_number, colmap_scan_cameras, dataset_scans, emap_cameras,
                            scene_cameras, write_score)
@@ -27,6 +32,8 @@ log = logging.getLogger(__name__)
 
 SUPPORT_FILE = "edge_support.json"
 FILTERED_FILE = "parametric_edges_supported.json"
+TRIM_FILE = "edge_trim.json"
+TRIMMED_FILE = "parametric_edges_trimmed.json"
 
 
 def filter_edge_dict(edge_dict, kept):
@@ -65,13 +72,42 @@ def write_support(model_dir, edge_dict, result, write_filtered=False, extra=None
     return out
 
 
+def trim_records(result, curves):
+    """One record per edge of a ``trim_edges`` result (``curves``: how many of the edges are curves): kind, index within its
+    kind, samples, spans as [a, b] pairs, and the kept share of its samples (None for an edge without samples)."""
+    n = np.diff(result["offsets"].astype(np.int64))
+    rows = []
+    for e, spans in enumerate(result["spans"]):
+        kept = sum(b - a + 1 for a, b in spans)
+        rows.append({"kind": "curve" if e < curves else "line", "index": int(e if e < curves else e - curves),
+                     "samples": int(n[e]), "spans": [[int(a), int(b)] for a, b in spans],
+                     "kept_share": kept / int(n[e]) if n[e] > 0 else None})
+    return rows
+
+
+def write_trim(model_dir, edge_dict, result, extra=None):
+    """``<model_dir>/edge_trim.json`` = {"edges": trim_records, "total", "pieces", "samples", "kept_samples", "settings",
+    **extra} and ``<model_dir>/parametric_edges_trimmed.json``, the pieces.  Returns the first dict."""
+    rows = trim_records(result, len(edge_dict["curves_ctl_pts"]))
+    out = {**(extra or {}), "edges": rows, "total": len(rows), "pieces": int(len(result["source"])),
+           "samples": int(sum(r["samples"] for r in rows)),
+           "kept_samples": int(sum(b - a + 1 for r in rows for a, b in r["spans"])), "settings": dict(result["settings"])}
+    write_score(os.path.join(model_dir, TRIM_FILE), out)
+    with open(os.path.join(model_dir, TRIMMED_FILE), "w") as f:
+        json.dump(result["edge_dict"], f)
+    return out
+
+
 def score_scan(base_dir, dataset_dir, scan, layout="emap", detector="DexiNed", undistort=False, write_filtered=False,
-               device=None, backend="gpu", resolution=-1, **options):
+               device=None, backend="gpu", resolution=-1, trim_options=None, **options):
     """Checks ``<base_dir>/<scan>/parametric_edges.json`` against the ``detector`` edge maps of ``<dataset_dir>/<scan>`` and
     writes ``<base_dir>/<scan>/edge_support.json`` (``write_support``).  ``layout``, ``undistort`` and ``resolution`` (of the
     images) as ``reprojection.score_scan``, the same camera loaders; ``options`` go to ``ops.edge_support.edge_support``
-    (sampling ``resolution`` as ``sample_resolution``).  Returns the dict written, or None -- after reporting it -- for a
-    scan without a prediction."""
+    (sampling ``resolution`` as ``sample_resolution``).  ``trim_options`` (a dict, possibly empty; None: no trimming) go to
+    ``ops.edge_trim.trim_edges`` on the same cameras and maps, after the check and with its sampling resolution, edge
+    threshold and ``thin`` unless they name their own: ``write_trim`` then adds its two files.  Returns the dict of
+    ``write_support``, with the one of ``write_trim`` under "trim" when there is one, or None -- after reporting it -- for
+    a scan without a prediction."""
     SP._check_backend(backend)
     if layout not in LAYOUTS:
         raise ValueError(f"unknown layout {layout!r}: expected one of {LAYOUTS}")
@@ -92,7 +128,13 @@ def score_scan(base_dir, dataset_dir, scan, layout="emap", detector="DexiNed", u
         options["resolution"] = options.pop("sample_resolution")
     res = SP.edge_support(edge_dict, cams, maps, detector, device=device, backend=backend, **options)
     res["settings"].update({"layout": layout, "undistort": bool(undistort)})
-    return write_support(os.path.join(base_dir, scan), edge_dict, res, write_filtered, extra={"scan": scan})
+    out = write_support(os.path.join(base_dir, scan), edge_dict, res, write_filtered, extra={"scan": scan})
+    if trim_options is not None:
+        shared = {k: options[k] for k in ("resolution", "edge_threshold", "thin") if k in options}
+        trim = ET.trim_edges(edge_dict, cams, maps, detector, device=device, backend=backend, **{**shared, **trim_options})
+        trim["settings"].update({"layout": layout, "undistort": bool(undistort)})
+        out["trim"] = write_trim(os.path.join(base_dir, scan), edge_dict, trim, extra={"scan": scan})
+    return out
 
 
 def support_scene(model_path, edge_dict, cameras, edge_maps, detector, **options):
@@ -109,9 +151,25 @@ def support_scene(model_path, edge_dict, cameras, edge_maps, detector, **options
     return filter_edge_dict(edge_dict, res["kept"]), res
 
 
+def trim_scene(model_path, edge_dict, cameras, edge_maps, detector, **options):
+    """The export's ``trim``: every edge of ``edge_dict`` cut down to its supported spans in the given cameras (as
+    ``support_scene`` takes them).  Writes ``edge_trim.json`` and ``parametric_edges_trimmed.json`` into ``model_path``, prints
+    the counts before and after, and returns (the trimmed dict, the ``trim_edges`` result)."""
+    if edge_maps is None:
+        cameras, edge_maps = scene_cameras(cameras)
+    res = ET.trim_edges(edge_dict, cameras, edge_maps, detector, **options)
+    os.makedirs(model_path, exist_ok=True)
+    out = write_trim(model_path, edge_dict, res)
+    print("before trimming: ", out["total"], "edges, after trimming: ", out["pieces"], "pieces")
+    return res["edge_dict"], res
+
+
 # ------------------------------------------------------------------------------------------------ command line
 def scan_line(scan, out):
-    return f"{scan}: views {out['settings']['views']}, edges {out['total']}, kept {out['kept']}"
+    line = f"{scan}: views {out['settings']['views']}, edges {out['total']}, kept {out['kept']}"
+    if "trim" in out:
+        line += f"; trimmed to {out['trim']['pieces']} pieces, {out['trim']['kept_samples']} of {out['trim']['samples']} samples"
+    return line
 
 
 def parser():
@@ -135,17 +193,27 @@ def parser():
     ap.add_argument("--write_filtered", action="store_true", help=f"also write {FILTERED_FILE} with the kept edges")
     ap.add_argument("--backend", choices=SP.SUPPORT_BACKENDS, default="gpu")
     ap.add_argument("--thin", action="store_true", help="thin the detected masks first (a thick detector response; untuned)")
+    ap.add_argument("--trim", action="store_true",
+                    help=f"also cut EVERY edge down to its supported spans: {TRIMMED_FILE} and {TRIM_FILE} (untuned; no depth)")
+    ap.add_argument("--trim_tolerance", type=float, default=ET.TOLERANCE_PX,
+                    help="trimming: pixel distance to a detected edge within which a sample counts as near (untuned)")
+    ap.add_argument("--trim_max_gap", type=int, default=ET.MAX_GAP,
+                    help="trimming: two supported runs at most this many samples apart are merged (untuned)")
+    ap.add_argument("--trim_min_span", type=int, default=ET.MIN_SPAN,
+                    help="trimming: a supported run of fewer samples is dropped (untuned)")
     return ap
 
 
 def main(argv=None):
     args = parser().parse_args(argv)
+    trim = {"tolerance_px": args.trim_tolerance, "max_gap": args.trim_max_gap, "min_span": args.trim_min_span,
+            "frames_ratio": args.frames_ratio} if args.trim else None
     for scan in dataset_scans(args.dataset_dir, args.layout, args.scans):
         out = score_scan(args.base_dir, args.dataset_dir, scan, args.layout, args.detector, args.undistort,
                          args.write_filtered, backend=args.backend, tolerances_px=args.tolerances,
                          keep_tolerance_px=args.keep_tolerance, min_visible=args.min_visible, min_near=args.min_near,
                          frames_ratio=args.frames_ratio, sample_resolution=args.sample_resolution,
-                         edge_threshold=args.edge_threshold, **({"thin": True} if args.thin else {}))
+                         edge_threshold=args.edge_threshold, trim_options=trim, **({"thin": True} if args.thin else {}))
         if out is None:
             print(f"Invalid prediction at {scan}")
             continue

@@ -273,7 +273,7 @@ def extract_curves(gaussians, merge_endpoints=False, distance_threshold=0.015):
 
 def write_parametric_edges(gaussians, model_path, merge_endpoints=False, distance_threshold=0.015,
                            visible_checking=False, scan_dir=None, detector="DexiNed", support_checking=False,
-                           support_options=None, cameras=None, edge_maps=None):
+                           support_options=None, cameras=None, edge_maps=None, trim=False, trim_options=None):
     """Writes parametric_edges.json (the evaluation input, train.py:287-293) and edge_points.ply (ASCII, :277-285).
     merge_endpoints / distance_threshold: see extract_curves (the reference's default is merge_endpoints=True).
     visible_checking=True keeps only the edges that `detector`'s edge maps of the scan at `scan_dir` show
@@ -282,12 +282,18 @@ def write_parametric_edges(gaussians, model_path, merge_endpoints=False, distanc
     length against `cameras` -- the training cameras of a Scene, or NovelViewCamera s with their uint8 `edge_maps` --
     and writes edge_support.json and parametric_edges_supported.json next to the two files, which stay as they are
     (edge_extraction.support.support_scene; `support_options` go to ops.edge_support.edge_support, whose defaults are
-    untuned)."""
+    untuned).
+    trim=True (off by default; the reference has no counterpart) cuts every written edge -- not only those the support
+    check keeps -- down to the spans of its length that the same `cameras` show and writes edge_trim.json and
+    parametric_edges_trimmed.json, again next to files that stay as they are (edge_extraction.support.trim_scene;
+    `trim_options` go to ops.edge_trim.trim_edges, whose defaults are untuned)."""
     if visible_checking and scan_dir is None:
         raise ValueError("write_parametric_edges(visible_checking=True) needs scan_dir, the scan holding "
                          "meta_data.json and the edge maps")
     if support_checking and cameras is None:
         raise ValueError("write_parametric_edges(support_checking=True) needs cameras, the views to check the edges in")
+    if trim and cameras is None:
+        raise ValueError("write_parametric_edges(trim=True) needs cameras, the views to trim the edges in")
     from ..edge_extraction.para_edge import get_parametric_edge
     merged = extract_curves(gaussians, merge_endpoints, distance_threshold)
     pts, edge_dict = get_parametric_edge(visible_checking, merged, scan_dir, detector)
@@ -295,6 +301,9 @@ def write_parametric_edges(gaussians, model_path, merge_endpoints=False, distanc
     if support_checking:
         from ..edge_extraction.support import support_scene
         support_scene(model_path, edge_dict, cameras, edge_maps, detector, **(support_options or {}))
+    if trim:
+        from ..edge_extraction.support import trim_scene
+        trim_scene(model_path, edge_dict, cameras, edge_maps, detector, **(trim_options or {}))
     return edge_dict, pts
 
 

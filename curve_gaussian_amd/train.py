@@ -378,9 +378,18 @@ def build_parser():
                    help="support check: share of an edge's samples that a view must see")
     p.add_argument("--support_frames_ratio", type=float, default=None,
                    help="support check: an edge is kept when more than ceil(ratio * views) views support it")
+    p.add_argument("--trim_edges", action="store_true",
+                   help="after the export, cut every edge of parametric_edges.json down to the spans of its length that the "
+                        "edge maps of the train cameras show: edge_trim.json and parametric_edges_trimmed.json in the model "
+                        "directory; parametric_edges.json stays as it is (untuned defaults; no depth)")
+    p.add_argument("--trim_tol_px", type=float, default=None,
+                   help="trimming: pixel distance to a detected edge within which a sample counts as near")
+    p.add_argument("--trim_max_gap", type=int, default=None,
+                   help="trimming: two supported runs at most this many samples apart are merged")
+    p.add_argument("--trim_min_span", type=int, default=None, help="trimming: a supported run of fewer samples is dropped")
     p.add_argument("--thin_edge_maps", action="store_true",
-                   help="thin every view's detected mask (Guo-Hall) before --support_check, --reprojection_score and --init "
-                        "edge_votes compare it with projected geometry: for a detector whose response is several pixels wide "
+                   help="thin every view's detected mask (Guo-Hall) before --support_check, --trim_edges, "
+                        "--reprojection_score and --init edge_votes compare it with projected geometry: for a detector whose response is several pixels wide "
                         "(untuned; a binary thinning, not non-maximum suppression)")
     return p
 
@@ -392,6 +401,15 @@ def support_options(args):
     if args.support_tol_px is not None:
         opts["tolerances_px"] = (args.support_tol_px,)
         opts["keep_tolerance_px"] = args.support_tol_px
+    if args.thin_edge_maps:
+        opts["thin"] = True
+    return opts
+
+
+def trim_options(args):
+    """The options of ops.edge_trim.trim_edges that the command line sets; the rest keep their defaults."""
+    opts = {k: v for k, v in (("tolerance_px", args.trim_tol_px), ("max_gap", args.trim_max_gap),
+                              ("min_span", args.trim_min_span)) if v is not None}
     if args.thin_edge_maps:
         opts["thin"] = True
     return opts
@@ -443,13 +461,17 @@ def main(argv=None):
         for split, res in scores.items():
             if res is not None:
                 print(scan_line(split, res["aggregate"]))
-    if args.support_check:
+    if args.support_check or args.trim_edges:
         import json
-        from .edge_extraction.support import support_scene
+        from .edge_extraction.support import support_scene, trim_scene
         with open(os.path.join(dataset.model_path, "parametric_edges.json")) as f:
             edge_dict = json.load(f)
-        support_scene(dataset.model_path, edge_dict, out["scene"].getTrainCameras(), None, dataset.detector,
-                      **support_options(args))
+        if args.support_check:
+            support_scene(dataset.model_path, edge_dict, out["scene"].getTrainCameras(), None, dataset.detector,
+                          **support_options(args))
+        if args.trim_edges:
+            trim_scene(dataset.model_path, edge_dict, out["scene"].getTrainCameras(), None, dataset.detector,
+                       **trim_options(args))
     print("\nTraining complete.")
 
 

@@ -1001,6 +1001,28 @@ int cgs_edge_support(int E, int P, const float* points /*[P,3]*/, const int32_t*
                      int32_t* counts /*[E,V,1+T]*/, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Per-sample 2D support: the tally of cgs_edge_support the other way round -- per SAMPLE over the views -- so that an edge
+ * can be trimmed to the spans of its length that the images show (ops/edge_trim.py).  The reference has no counterpart.
+ *
+ * points, intr, w2c, d2 and tol2 as for cgs_edge_support (no offsets: a sample does not know its edge); SEEN is the same
+ * device function, so no two entries disagree on a boundary point.  tally is int32 [P,1+T], device:
+ *   tally[i][0]     += the number of the V views that see sample i
+ *   tally[i][1 + t] += the number of those with d2[v][floor(v)][floor(u)] <= tol2[t]
+ * The entry ADDS: the caller hands in a zeroed tally and calls once per chunk of views (all views of a call share one
+ * size).  One thread per sample with the view loop inside it (any number of views in one launch), the sums in registers
+ * and one read-modify-write of the thread's own row: integers only, no atomics, no LDS, no barrier, so the result does not
+ * depend on the launch geometry or on how the views are cut into calls.  Offsets are 64-bit.  The caller's stream, no
+ * allocation, no clearing, no host synchronisation.
+ *
+ * Every argument is checked, whether or not there is work: P or V < 0, T outside [1, CGS_EDGE_SUPPORT_MAX_TOL], a size
+ * outside [1, CGS_EDT_MAX_SIZE] and NULL pointers (points and tally only when P > 0) are CGS_ERR_INVALID_ARGUMENT, rejected
+ * before anything is launched.  Then P = 0 or V = 0 is a no-op (nothing to add).
+ * ------------------------------------------------------------------------------------------------ */
+int cgs_sample_support(int P, const float* points /*[P,3]*/, int V, const double* intr /*[V,4]*/,
+                       const double* w2c /*[V,12]*/, int height, int width, const int32_t* d2 /*[V,height,width]*/, int T,
+                       const int32_t* tol2 /*[T]*/, int32_t* tally /*[P,1+T]*/, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Parallel binary thinning of detected masks: a learned detector's response is several pixels wide, and the 2D checks above
  * (reprojection score, voxel vote, per-edge support) were designed on one-pixel lines.  The reference has no counterpart.
  *
