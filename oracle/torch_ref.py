@@ -32,9 +32,11 @@ def _quat_to_R(q):
     return R
 
 
-def dense_render(means3D, opacities, scales, rotations, colors, all_map, viewmatrix, projmatrix, tan_fovx, tan_fovy,
-                 H, W, bg, scale_modifier=1.0, means2D_ndc_offset=None, antialiasing=False):
-    """Returns (color[1,H,W], radii[P], invdepth[1,H,W], out_all_map[4,H,W]).  All float inputs share one dtype."""
+def preprocess_2d(means3D, opacities, scales, rotations, viewmatrix, projmatrix, tan_fovx, tan_fovy, H, W,
+                  scale_modifier=1.0, means2D_ndc_offset=None, antialiasing=False, cov3D=None):
+    """The per-splat 2D state of dense_render, differentiable on its own: (px [P], py [P], conic [P,3], opac [P], tz [P],
+    cov2d [P,3]) -- pixel-space centre, inverse of the dilated 2D covariance, (antialiased) opacity, view-space depth and
+    the dilated covariance itself (a, b, c).  `cov3D` [P,3,3] replaces R S^2 R^T (scales and rotations are then unused)."""
     dt = means3D.dtype
     P = means3D.shape[0]
     vm = viewmatrix.to(dt).reshape(16)
@@ -51,9 +53,12 @@ def dense_render(means3D, opacities, scales, rotations, colors, all_map, viewmat
         p_proj = torch.cat([p_proj[:, :2] + means2D_ndc_offset, p_proj[:, 2:]], 1)
     fx = W / (2.0 * tan_fovx)
     fy = H / (2.0 * tan_fovy)
-    Rq = _quat_to_R(rotations)
-    S2 = (scale_modifier * scales) ** 2
-    Sigma = Rq @ torch.diag_embed(S2) @ Rq.transpose(1, 2)
+    if cov3D is None:
+        Rq = _quat_to_R(rotations)
+        S2 = (scale_modifier * scales) ** 2
+        Sigma = Rq @ torch.diag_embed(S2) @ Rq.transpose(1, 2)
+    else:
+        Sigma = cov3D
     tz = p_view[:, 2]
     limx, limy = 1.3 * tan_fovx, 1.3 * tan_fovy
     tx = torch.clamp(p_view[:, 0] / tz, -limx, limx) * tz
@@ -70,12 +75,31 @@ def dense_render(means3D, opacities, scales, rotations, colors, all_map, viewmat
     opac = opacities.reshape(-1)
     if antialiasing:
         opac = opac * torch.sqrt(torch.clamp((a0 * c0 - b0 * b0) / det, min=0.000025))
+    px = ((p_proj[:, 0] + 1.0) * W - 1.0) * 0.5
+    py = ((p_proj[:, 1] + 1.0) * H - 1.0) * 0.5
+    return px, py, conic, opac, tz, torch.stack([a, b, c], 1)
+
+
+def dense_render(means3D, opacities, scales, rotations, colors, all_map, viewmatrix, projmatrix, tan_fovx, tan_fovy,
+                 H, W, bg, scale_modifier=1.0, means2D_ndc_offset=None, antialiasing=False, trace=None):
+    """Returns (color[1,H,W], radii[P], invdepth[1,H,W], out_all_map[4,H,W]).  All float inputs share one dtype.
+
+    `trace`: an optional dict the walk fills with what a per-pair error analysis needs (tests/raster_ref64.py): "order" (the
+    visible splats in depth order), the 2D state ("px", "py", "conic", "opac", "tz", "radius", "rect") and, per splat of
+    "order" as lists of [npix] tensors, "alpha" (the UNCLAMPED opacity * G, part of the graph with its gradient retained:
+    after backward() its .grad is dL/dalpha where the pair was blended and 0 elsewhere), "dx", "dy", "w" (= alpha T), "T"
+    (the transmittance in front of the pair) and the decision masks "member", "visible_alpha" (member, power <= 0 and
+    alpha >= 1/255, whatever the pixel's state), "stopped" (this pair's T (1 - alpha) < 1e-4 test ended the pixel) and
+    "blended"."""
+    dt = means3D.dtype
+    px, py, conic, opac, tz, cov2d = preprocess_2d(means3D, opacities, scales, rotations, viewmatrix, projmatrix, tan_fovx,
+                                                   tan_fovy, H, W, scale_modifier, means2D_ndc_offset, antialiasing)
+    a, b, c = cov2d[:, 0], cov2d[:, 1], cov2d[:, 2]
+    det = a * c - b * b
     with torch.no_grad():
         mid = 0.5 * (a + c)
         lam = mid + torch.sqrt(torch.clamp(mid * mid - det, min=0.1))
         radius = torch.ceil(3.0 * torch.sqrt(lam))
-    px = ((p_proj[:, 0] + 1.0) * W - 1.0) * 0.5
-    py = ((p_proj[:, 1] + 1.0) * H - 1.0) * 0.5
     gx, gy = (W + 15) // 16, (H + 15) // 16
     with torch.no_grad():
         rminx = torch.clamp(((px - radius) / 16).to(torch.int64), 0, gx)   # trunc toward zero == C (int) cast
@@ -98,20 +122,38 @@ def dense_render(means3D, opacities, scales, rotations, colors, all_map, viewmat
     C = torch.zeros(npix, dtype=dt)
     D = torch.zeros(npix, dtype=dt)
     A = torch.zeros(4, npix, dtype=dt)
+    if trace is not None:
+        trace.update(order=order, px=px.detach(), py=py.detach(), conic=conic.detach(), opac=opac.detach(), tz=tz.detach(),
+                     radius=radius, lam=lam, rect=torch.stack([rminx, rminy, rmaxx, rmaxy], 1), alpha=[], dx=[], dy=[], w=[], T=[],
+                     member=[], visible_alpha=[], stopped=[], blended=[])
     for s in order.tolist():
         member = (tix >= rminx[s]) & (tix < rmaxx[s]) & (tiy >= rminy[s]) & (tiy < rmaxy[s])
         dx = px[s] - pixx
         dy = py[s] - pixy
         power = -0.5 * (conic[s, 0] * dx * dx + conic[s, 2] * dy * dy) - conic[s, 1] * dx * dy
-        alpha = torch.clamp(opac[s] * torch.exp(power), max=0.99)
+        alpha_u = opac[s] * torch.exp(power)
+        if trace is not None and alpha_u.requires_grad:
+            alpha_u.retain_grad()
+        alpha = torch.clamp(alpha_u, max=0.99)
         with torch.no_grad():
-            ok = member & ~done & (power <= 0) & (alpha >= 1.0 / 255.0)
+            seen = member & (power <= 0) & (alpha >= 1.0 / 255.0)
+            ok = seen & ~done
             test_T = T * (1 - alpha)
             stop = ok & (test_T < 0.0001)
             done = done | stop
             ok = ok & ~stop
         alpha = torch.where(ok, alpha, torch.zeros_like(alpha))
         w = alpha * T
+        if trace is not None:
+            trace["alpha"].append(alpha_u)
+            trace["dx"].append(dx.detach())
+            trace["dy"].append(dy.detach())
+            trace["w"].append(w.detach())
+            trace["T"].append(T.detach())
+            trace["member"].append(member)
+            trace["visible_alpha"].append(seen)
+            trace["stopped"].append(stop)
+            trace["blended"].append(ok)
         C = C + colors[s, 0] * w
         D = D + (1.0 / tz[s]) * w
         A = A + all_map[s][:, None] * w[None, :]

@@ -1,0 +1,113 @@
+"""CPU: the float64 truth of the tile compositors (tests/raster_ref64.py) and its constructed scenes.
+
+For every scene of the table: every decision of the float64 forward keeps its margin, the per-quadrant lists are determinate
+and have exactly the lengths the table names, the truth's pair sums reproduce its own autograd, and the C oracle (the
+reference's float32 arithmetic) stays within the bounds element by element -- the run that fixes K (printed: pytest -s)."""
+import numpy as np
+import pytest
+import torch
+
+import raster_ref64 as R64
+from util import ORA, oracle_forward
+
+ALL = (True, True, True)
+
+
+def ratios(got, ref, bound_k1):
+    """worst |got - ref| / bound (bound taken at K = 1); an element with bound 0 must be exact."""
+    got, ref, b = np.asarray(got, np.float64), np.asarray(ref, np.float64), np.asarray(bound_k1, np.float64)
+    err = np.abs(got - ref)
+    zero = b == 0
+    assert (err[zero] == 0).all(), "an element without pairs is not an exact zero"
+    return float((err[~zero] / b[~zero]).max()) if (~zero).any() else 0.0
+
+
+def _stop_position(t):
+    """[H, W] 1-based position (in depth order) of the entry whose T test ended the pixel; 0 where none did."""
+    pos = np.arange(1, len(t.order) + 1)[:, None]
+    return (t.stopped * pos).sum(0).reshape(t.scene.H, t.scene.W)
+
+
+def _check_purpose(name, t):
+    """The scene reaches the edge its table entry is there for."""
+    term, stop = t.terminated(), _stop_position(t)
+    nb = t.n_blended.reshape(term.shape)
+    if name == "term_front":
+        assert term.any() and not term.all()     # (the rim, where the splats are faint, takes longer or runs to the end)
+        assert set(np.unique(nb[6:10, 6:10])) <= {4, 5, 6} and term[6:10, 6:10].all() and (len(t.order) - stop[6:10, 6:10] >= 39).all()
+    elif name == "term_quadrant":
+        assert term[:8, :8].all() and term[8:, 8:].sum() <= 16 and not term[12:, 12:].any()
+    elif name == "term_second_batch":
+        assert term.any() and (stop[term] > 258).all() and (stop[term] <= 266).all()
+    elif name in ("term_group_16", "term_group_17"):
+        assert term.all() and (stop == int(name[-2:])).all()
+    elif name == "ties":
+        z = t.tz[t.order].astype(np.float32)
+        assert (z[6:14] == z[6]).all() and len(np.unique(z)) == len(z) - 7 and (np.diff(t.order[6:14]) > 0).all()
+    elif name == "centres":
+        assert t.m[t.blended].max() > 100.0
+
+
+@pytest.mark.parametrize("name", list(R64.SCENES))
+def test_scene_keeps_its_margins_lists_and_the_oracle_stays_within_bounds(name):
+    sc = R64.Scene(name)
+    grads = R64.scene_grads(sc, ALL)
+    t = R64.truth(sc, grads)
+    # the decisions
+    mg = R64.margins(sc, t)
+    R64.check_margins(mg)
+    _check_purpose(name, t)
+    lists = R64.quadrant_lists(sc, t)
+    lens = {tile: tuple(len(q) for q in d["quadrants"]) for tile, d in lists.items()}
+    if sc.expect is not None:
+        assert lens == sc.expect, (lens, sc.expect)
+    if name.startswith(("stack16_", "ragged_")):   # the staged count (the tile's list after culling) is N as well
+        assert all(len(d["list"]) == sc.P for d in lists.values())
+    if name.startswith("pooled_31_"):   # the run of the 11th splat starts on the last slot of the first chunk of 32 pairs
+        d = lists[0]
+        assert sum(sum(s in q for q in d["quadrants"]) for s in d["list"][:10]) == 31
+        assert sum(d["list"][10] in q for q in d["quadrants"]) == int(name[-1])
+    if name == "pooled_last_1":
+        assert sum(len(q) for q in lists[0]["quadrants"]) % 32 == 1
+    # the truth's pair sums are its autograd gradients (float64: 1e-9 of the bound's own scale)
+    img_b, _ = R64.bounds(t, K=1.0)
+    Bd, Gd = t.grad_bounds(K=1.0)
+    for k, v in t.g.items():
+        assert np.abs(Gd[k] - v).max() <= 1e-3 * Bd[k].max() + 1e-300, (k, np.abs(Gd[k] - v).max(), Bd[k].max())
+    # the C oracle within the bounds
+    fw = oracle_forward(sc.sp, sc.cam, sc.bg)
+    assert (fw.radii == t.radii).all()
+    worst = {"color": ratios(fw.color, t.out["color"], img_b["color"]),
+             "invdepth": ratios(fw.invdepth, t.out["invdepth"], img_b["invdepth"]),
+             "all_map": ratios(fw.out_all_map, t.out["all_map"], img_b["all_map"])}
+    term = t.terminated()
+    want = R64.expected_n_contrib(sc, t, lists)
+    # (the oracle's lists are the reference's: no tile culling -- positions agree when nothing was culled)
+    if all(len(d["list"]) == int((fw.ranges[tile, 1] - fw.ranges[tile, 0])) for tile, d in lists.items()):
+        assert (fw.n_contrib[term] == want[term]).all()
+    n = lambda d: None if d is None else d.numpy()
+    gr = ORA.backward(fw, n(grads[0]), n(grads[1]), n(grads[2]))
+    for k in t.g:
+        worst[k] = ratios(gr[k], t.g[k], Bd[k])
+    fw.free()
+    print(f"\n{name}: P {sc.P} lists {lens} margins " + " ".join(f"{k} {v:.3g}" for k, v in mg.items()))
+    print("   oracle ratios |oracle - truth| / (eps scale): " + " ".join(f"{k} {v:.2f}" for k, v in worst.items()))
+    for k, v in worst.items():
+        assert v <= R64.K / 4.0, f"{k}: the oracle needs {v:.2f} of the bound's unit: K = {R64.K} is below 4 x that"
+
+
+def test_k_is_four_times_the_oracles_worst_ratio_rounded_up_to_a_power_of_two():
+    worst = max(R64.K_MEASURED.values())
+    assert R64.K == max(16.0, 2.0 ** np.ceil(np.log2(4.0 * worst)))
+
+
+def test_trace_and_preprocess_leave_dense_render_unchanged():
+    """The trace is an observer: same outputs with and without it, and preprocess_2d is what dense_render renders from."""
+    sc = R64.Scene("stack16_17")
+    a = R64.Truth(sc, sc.sp)
+    from oracle import torch_ref as TR
+    d = lambda v: v.to(torch.float64)
+    col, radii, invd, amap = TR.dense_render(
+        d(sc.sp["means3D"]), d(sc.sp["opacities"]), d(sc.sp["scales"]), d(sc.sp["rotations"]), d(sc.sp["colors"]),
+        d(sc.sp["all_map"]), d(sc.cam.world_view_transform), d(sc.cam.full_proj_transform), sc.tfx, sc.tfy, sc.H, sc.W, d(sc.bg))
+    assert (col.numpy() == a.out["color"]).all() and (amap.numpy() == a.out["all_map"]).all() and (radii.numpy() == a.radii).all()
