@@ -1763,6 +1763,21 @@ int cgs_sample_support(int P, const float* points, int V, const double* intr, co
     return finish("sample_support", stream_);
 }
 
+size_t cgs_sample_cover_workspace_bytes(int P) { return sample_cover_workspace_bytes(P); }
+
+int cgs_sample_cover(int P, const float* points, int E, const int32_t* offsets, const int32_t* rank, float tol2, float cos2,
+                     int32_t* cover, void* workspace, void* stream_) {
+    if (P < 0 || E < 0) return reject("cgs_sample_cover: invalid argument (P=%d, E=%d)", P, E);
+    if (!(tol2 >= 0.f) || !(cos2 >= 0.f && cos2 <= 1.f))   // a NaN fails either comparison
+        return reject("cgs_sample_cover: invalid argument (tol2=%g, cos2=%g; tol2 >= 0 and cos2 lies in [0, 1])",
+                      (double)tol2, (double)cos2);
+    if (!offsets || !rank || !workspace || (P > 0 && (!points || !cover)))
+        return reject("cgs_sample_cover: invalid argument (NULL pointer; P=%d, E=%d)", P, E);
+    if (P == 0 || E == 0) return CGS_OK;   // nothing to cover
+    launch_sample_cover((hipStream_t)stream_, P, points, E, offsets, rank, tol2, cos2, cover, workspace);
+    return finish("sample_cover", stream_);
+}
+
 int cgs_thin_masks(int V, int height, int width, uint8_t* masks, uint8_t* scratch, int* changed_flag, int max_iterations,
                    int* iterations_out, void* stream_) {
     if (V < 0 || !edt_size_ok(height, width) || max_iterations < 0)

@@ -245,6 +245,11 @@ void launch_edge_support(hipStream_t s, int E, int P, const float* points, const
 void launch_sample_support(hipStream_t s, int P, const float* points, int V, const double* intr, const double* w2c,
                            int height, int width, const int* d2, int T, const int* tol2, int* tally);
 
+// edge_dedupe.hip
+size_t sample_cover_workspace_bytes(int P);
+void launch_sample_cover(hipStream_t s, int P, const float* points, int E, const int* offsets, const int* rank, float tol2,
+                         float cos2, int* cover, void* workspace);
+
 // edge_thin.hip
 int launch_thin_masks(hipStream_t s, int V, int height, int width, uint8_t* masks, uint8_t* scratch, int* changed_flag,
                       int max_iterations, int* iterations, hipError_t* err);

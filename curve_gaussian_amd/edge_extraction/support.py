@@ -11,9 +11,13 @@ rule counts supporting frames and does not pool; a thick detector response infla
 writes ``<base_dir>/<scan>/edge_support.json`` -- one record per edge -- and, with ``--write_filtered``,
 ``parametric_edges_supported.json`` with the kept edges.  With ``--trim`` every edge of ``parametric_edges.json`` -- not only
 the kept ones: the verdict drops an over-long true edge whole -- is also cut down to the spans of its length that the images
-show (``ops.edge_trim``; its docstring freezes the rule and states the limits: no depth, duplicates are not merged, UNTUNED
-defaults): ``parametric_edges_trimmed.json`` and ``edge_trim.json``, one record per edge.  ``parametric_edges.json`` is never
-written."""
+show (``ops.edge_trim``; its docstring freezes the rule and states the limits: no depth, UNTUNED defaults; the duplicates it
+leaves are what ``--dedupe`` is for): ``parametric_edges_trimmed.json`` and ``edge_trim.json``, one record per edge.  With
+``--dedupe`` the parts of the edges that a longer edge already covers in 3D are dropped (``ops.edge_dedupe``; its docstring
+freezes the rule and states the limits: the longer edge always wins, one pass, no image evidence, UNTUNED defaults) -- of
+the trimmed pieces with ``--trim``, of the edges of ``parametric_edges.json`` without: ``parametric_edges_deduped.json`` and
+``edge_dedupe.json``, one record per input edge.  ``parametric_edges.json`` is never written, and no option rewrites
+another option's files."""
 import argparse
 import json
 import logging
@@ -22,6 +26,7 @@ import sys
 
 import numpy as np
 
+from ..ops import edge_dedupe as ED
 from ..ops import edge_support as SP
 from ..ops import edge_trim as ET
 from .para_edge import EDGE_MAX_THRESHOLD, EDGE_VISIBILITY_FRAMES_RATIO
@@ -34,6 +39,8 @@ SUPPORT_FILE = "edge_support.json"
 FILTERED_FILE = "parametric_edges_supported.json"
 TRIM_FILE = "edge_trim.json"
 TRIMMED_FILE = "parametric_edges_trimmed.json"
+DEDUPE_FILE = "edge_dedupe.json"
+DEDUPED_FILE = "parametric_edges_deduped.json"
 
 
 def filter_edge_dict(edge_dict, kept):
@@ -98,16 +105,46 @@ def write_trim(model_dir, edge_dict, result, extra=None):
     return out
 
 
+def dedupe_records(result, curves):
+    """One record per input edge of a ``dedupe_edges`` result (``curves``: how many of the edges are curves): kind, index
+    within its kind, samples, redundant samples, ``covered_by`` -- the best-ranked coverer of each of them, as sorted edge
+    indices over curves first, then lines; a second, lower-ranked coverer of a sample is not listed -- and the spans that
+    are left, as [a, b] pairs."""
+    off = result["offsets"].astype(np.int64)
+    rows = []
+    for e, spans in enumerate(result["spans"]):
+        rows.append({"kind": "curve" if e < curves else "line", "index": int(e if e < curves else e - curves),
+                     "samples": int(off[e + 1] - off[e]),
+                     "redundant_samples": int(np.count_nonzero(result["redundant"][off[e]:off[e + 1]])),
+                     "covered_by": [int(b) for b in result["covered_by"][e]], "spans": [[int(a), int(b)] for a, b in spans]})
+    return rows
+
+
+def write_dedupe(model_dir, edge_dict, result, extra=None):
+    """``<model_dir>/edge_dedupe.json`` = {"edges": dedupe_records, "total", "pieces", "samples", "redundant_samples",
+    "settings", **extra} and ``<model_dir>/parametric_edges_deduped.json``, the pieces.  Returns the first dict."""
+    rows = dedupe_records(result, len(edge_dict["curves_ctl_pts"]))
+    out = {**(extra or {}), "edges": rows, "total": len(rows), "pieces": int(len(result["source"])),
+           "samples": int(sum(r["samples"] for r in rows)),
+           "redundant_samples": int(sum(r["redundant_samples"] for r in rows)), "settings": dict(result["settings"])}
+    write_score(os.path.join(model_dir, DEDUPE_FILE), out)
+    with open(os.path.join(model_dir, DEDUPED_FILE), "w") as f:
+        json.dump(result["edge_dict"], f)
+    return out
+
+
 def score_scan(base_dir, dataset_dir, scan, layout="emap", detector="DexiNed", undistort=False, write_filtered=False,
-               device=None, backend="gpu", resolution=-1, trim_options=None, **options):
+               device=None, backend="gpu", resolution=-1, trim_options=None, dedupe_options=None, **options):
     """Checks ``<base_dir>/<scan>/parametric_edges.json`` against the ``detector`` edge maps of ``<dataset_dir>/<scan>`` and
     writes ``<base_dir>/<scan>/edge_support.json`` (``write_support``).  ``layout``, ``undistort`` and ``resolution`` (of the
     images) as ``reprojection.score_scan``, the same camera loaders; ``options`` go to ``ops.edge_support.edge_support``
     (sampling ``resolution`` as ``sample_resolution``).  ``trim_options`` (a dict, possibly empty; None: no trimming) go to
     ``ops.edge_trim.trim_edges`` on the same cameras and maps, after the check and with its sampling resolution, edge
-    threshold and ``thin`` unless they name their own: ``write_trim`` then adds its two files.  Returns the dict of
-    ``write_support``, with the one of ``write_trim`` under "trim" when there is one, or None -- after reporting it -- for
-    a scan without a prediction."""
+    threshold and ``thin`` unless they name their own: ``write_trim`` then adds its two files.  ``dedupe_options`` (a dict,
+    possibly empty; None: no deduping) go to ``ops.edge_dedupe.dedupe_edges`` on the trimmed pieces when there are any and
+    on the edges of the prediction otherwise, with the check's sampling resolution unless they name their own:
+    ``write_dedupe`` then adds its two files, and "input" there names the file whose edges went in.  Returns the dict of ``write_support``, with the ones of ``write_trim`` and ``write_dedupe`` under "trim" and "dedupe"
+    when there are any, or None -- after reporting it -- for a scan without a prediction."""
     SP._check_backend(backend)
     if layout not in LAYOUTS:
         raise ValueError(f"unknown layout {layout!r}: expected one of {LAYOUTS}")
@@ -134,6 +171,11 @@ def score_scan(base_dir, dataset_dir, scan, layout="emap", detector="DexiNed", u
         trim = ET.trim_edges(edge_dict, cams, maps, detector, device=device, backend=backend, **{**shared, **trim_options})
         trim["settings"].update({"layout": layout, "undistort": bool(undistort)})
         out["trim"] = write_trim(os.path.join(base_dir, scan), edge_dict, trim, extra={"scan": scan})
+    if dedupe_options is not None:
+        given, name = (trim["edge_dict"], TRIMMED_FILE) if trim_options is not None else (edge_dict, "parametric_edges.json")
+        shared = {k: options[k] for k in ("resolution",) if k in options}
+        res = ED.dedupe_edges(given, device=device, backend=backend, **{**shared, **dedupe_options})
+        out["dedupe"] = write_dedupe(os.path.join(base_dir, scan), given, res, extra={"scan": scan, "input": name})
     return out
 
 
@@ -164,11 +206,26 @@ def trim_scene(model_path, edge_dict, cameras, edge_maps, detector, **options):
     return res["edge_dict"], res
 
 
+def dedupe_scene(model_path, edge_dict, input_file="parametric_edges.json", **options):
+    """The export's ``dedupe``: every edge of ``edge_dict`` cut down to what no longer edge covers (``dedupe_edges``; no
+    cameras: this is 3D only).  ``input_file``: the file the edges came from, recorded as "input".  Writes
+    ``edge_dedupe.json`` and ``parametric_edges_deduped.json`` into ``model_path``, prints the counts before and after, and
+    returns (the deduped dict, the ``dedupe_edges`` result)."""
+    res = ED.dedupe_edges(edge_dict, **options)
+    os.makedirs(model_path, exist_ok=True)
+    out = write_dedupe(model_path, edge_dict, res, extra={"input": input_file})
+    print("before deduping: ", out["total"], "edges, after deduping: ", out["pieces"], "pieces")
+    return res["edge_dict"], res
+
+
 # ------------------------------------------------------------------------------------------------ command line
 def scan_line(scan, out):
     line = f"{scan}: views {out['settings']['views']}, edges {out['total']}, kept {out['kept']}"
     if "trim" in out:
         line += f"; trimmed to {out['trim']['pieces']} pieces, {out['trim']['kept_samples']} of {out['trim']['samples']} samples"
+    if "dedupe" in out:
+        line += (f"; deduped to {out['dedupe']['pieces']} pieces, {out['dedupe']['redundant_samples']} of "
+                 f"{out['dedupe']['samples']} samples redundant")
     return line
 
 
@@ -201,6 +258,18 @@ def parser():
                     help="trimming: two supported runs at most this many samples apart are merged (untuned)")
     ap.add_argument("--trim_min_span", type=int, default=ET.MIN_SPAN,
                     help="trimming: a supported run of fewer samples is dropped (untuned)")
+    ap.add_argument("--dedupe", action="store_true",
+                    help=f"also drop what a longer edge already covers in 3D -- of the trimmed pieces with --trim, of the "
+                         f"edges otherwise: {DEDUPED_FILE} and {DEDUPE_FILE} (untuned; the longer edge always wins)")
+    ap.add_argument("--dedupe_tolerance", type=float, default=None,
+                    help=f"deduping: 3D distance within which a sample of a longer edge covers one (default: "
+                         f"{ED.TOLERANCE_RESOLUTIONS:g} x --sample_resolution; untuned)")
+    ap.add_argument("--dedupe_cos_min", type=float, default=ED.COS_MIN,
+                    help="deduping: least |cosine| between the two edges' directions for a cover (untuned)")
+    ap.add_argument("--dedupe_min_run", type=int, default=ED.MIN_RUN,
+                    help="deduping: a run of fewer covered samples is not redundant (untuned)")
+    ap.add_argument("--dedupe_min_span", type=int, default=ED.MIN_SPAN,
+                    help="deduping: a free run of fewer samples is dropped (untuned)")
     return ap
 
 
@@ -208,12 +277,15 @@ def main(argv=None):
     args = parser().parse_args(argv)
     trim = {"tolerance_px": args.trim_tolerance, "max_gap": args.trim_max_gap, "min_span": args.trim_min_span,
             "frames_ratio": args.frames_ratio} if args.trim else None
+    dedupe = {"tolerance": args.dedupe_tolerance, "cos_min": args.dedupe_cos_min, "min_run": args.dedupe_min_run,
+              "min_span": args.dedupe_min_span} if args.dedupe else None
     for scan in dataset_scans(args.dataset_dir, args.layout, args.scans):
         out = score_scan(args.base_dir, args.dataset_dir, scan, args.layout, args.detector, args.undistort,
                          args.write_filtered, backend=args.backend, tolerances_px=args.tolerances,
                          keep_tolerance_px=args.keep_tolerance, min_visible=args.min_visible, min_near=args.min_near,
                          frames_ratio=args.frames_ratio, sample_resolution=args.sample_resolution,
-                         edge_threshold=args.edge_threshold, trim_options=trim, **({"thin": True} if args.thin else {}))
+                         edge_threshold=args.edge_threshold, trim_options=trim, dedupe_options=dedupe,
+                         **({"thin": True} if args.thin else {}))
         if out is None:
             print(f"Invalid prediction at {scan}")
             continue

@@ -23,11 +23,12 @@ Definitions, frozen; n = the samples of edge e, ``sample_edges`
                                B(ta,ta,ta), B(ta,ta,tb), B(ta,tb,tb), B(tb,tb,tb) of its blossom B, for a line
                                p0 + t (p1 - p0) at ta and tb; a span (0, n - 1) is the edge itself, bit for bit
 
-KNOWN LIMITS.  There is no depth, as in ops/edge_support.py: a stretch hidden behind a surface in most views is cut away.
-The pieces of a chord that runs along a real edge duplicate that edge; nothing merges them.  The cut lands up to the
-tolerance plus a pixel diagonal beyond the true end, because a sample just past the end still falls on a pixel near the
-drawn one.  THE DEFAULTS OF ``trim_edges`` ARE UNTUNED: only the drawn test scan (tests/edge_trim_cases.py) has been
-checked, no real scan.
+KNOWN LIMITS.  There is no depth, as in ops/edge_support.py: a stretch hidden behind a surface in most views is cut
+away.  The pieces of a chord that runs along a real edge duplicate that edge; this module does not merge them
+(ops/edge_dedupe.py, opt-in, drops what a longer edge already covers).  The cut lands up to the tolerance plus a pixel
+diagonal beyond the true end, because a sample just past the end still falls on a pixel near the drawn one.  THE
+DEFAULTS OF ``trim_edges`` ARE UNTUNED: only the drawn test scan (tests/edge_trim_cases.py) has been checked, no real
+scan.
 
 Two back ends: ``"gpu"``, HIP, and ``"host"``, numpy -- the same rules in integers, so the tallies agree exactly; the
 spans and the pieces are host arithmetic for both."""

@@ -273,7 +273,8 @@ def extract_curves(gaussians, merge_endpoints=False, distance_threshold=0.015):
 
 def write_parametric_edges(gaussians, model_path, merge_endpoints=False, distance_threshold=0.015,
                            visible_checking=False, scan_dir=None, detector="DexiNed", support_checking=False,
-                           support_options=None, cameras=None, edge_maps=None, trim=False, trim_options=None):
+                           support_options=None, cameras=None, edge_maps=None, trim=False, trim_options=None,
+                           dedupe=False, dedupe_options=None):
     """Writes parametric_edges.json (the evaluation input, train.py:287-293) and edge_points.ply (ASCII, :277-285).
     merge_endpoints / distance_threshold: see extract_curves (the reference's default is merge_endpoints=True).
     visible_checking=True keeps only the edges that `detector`'s edge maps of the scan at `scan_dir` show
@@ -286,7 +287,11 @@ def write_parametric_edges(gaussians, model_path, merge_endpoints=False, distanc
     trim=True (off by default; the reference has no counterpart) cuts every written edge -- not only those the support
     check keeps -- down to the spans of its length that the same `cameras` show and writes edge_trim.json and
     parametric_edges_trimmed.json, again next to files that stay as they are (edge_extraction.support.trim_scene;
-    `trim_options` go to ops.edge_trim.trim_edges, whose defaults are untuned)."""
+    `trim_options` go to ops.edge_trim.trim_edges, whose defaults are untuned).
+    dedupe=True (off by default; the reference has no counterpart) drops the parts of the edges that a longer edge already
+    covers in 3D -- of the trimmed pieces after trim=True, of the written edges otherwise -- and writes edge_dedupe.json and
+    parametric_edges_deduped.json, again next to files that stay as they are (edge_extraction.support.dedupe_scene;
+    `dedupe_options` go to ops.edge_dedupe.dedupe_edges, whose defaults are untuned).  It needs no cameras on its own."""
     if visible_checking and scan_dir is None:
         raise ValueError("write_parametric_edges(visible_checking=True) needs scan_dir, the scan holding "
                          "meta_data.json and the edge maps")
@@ -303,7 +308,11 @@ def write_parametric_edges(gaussians, model_path, merge_endpoints=False, distanc
         support_scene(model_path, edge_dict, cameras, edge_maps, detector, **(support_options or {}))
     if trim:
         from ..edge_extraction.support import trim_scene
-        trim_scene(model_path, edge_dict, cameras, edge_maps, detector, **(trim_options or {}))
+        trimmed, _ = trim_scene(model_path, edge_dict, cameras, edge_maps, detector, **(trim_options or {}))
+    if dedupe:
+        from ..edge_extraction.support import TRIMMED_FILE, dedupe_scene
+        dedupe_scene(model_path, trimmed if trim else edge_dict, input_file=TRIMMED_FILE if trim else "parametric_edges.json",
+                     **(dedupe_options or {}))
     return edge_dict, pts
 
 

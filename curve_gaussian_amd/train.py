@@ -387,6 +387,18 @@ def build_parser():
     p.add_argument("--trim_max_gap", type=int, default=None,
                    help="trimming: two supported runs at most this many samples apart are merged")
     p.add_argument("--trim_min_span", type=int, default=None, help="trimming: a supported run of fewer samples is dropped")
+    p.add_argument("--dedupe_edges", action="store_true",
+                   help="after the export, drop the parts of the edges that a longer edge already covers in 3D -- of the "
+                        "trimmed pieces with --trim_edges, of parametric_edges.json otherwise: edge_dedupe.json and "
+                        "parametric_edges_deduped.json in the model directory; the other files stay as they are (untuned "
+                        "defaults; the longer edge always wins)")
+    p.add_argument("--dedupe_tolerance", type=float, default=None,
+                   help="deduping: 3D distance within which a sample of a longer edge covers one (default: 2 x the sampling "
+                        "resolution)")
+    p.add_argument("--dedupe_cos_min", type=float, default=None,
+                   help="deduping: least |cosine| between the two edges' directions for a cover")
+    p.add_argument("--dedupe_min_run", type=int, default=None, help="deduping: a run of fewer covered samples is not redundant")
+    p.add_argument("--dedupe_min_span", type=int, default=None, help="deduping: a free run of fewer samples is dropped")
     p.add_argument("--thin_edge_maps", action="store_true",
                    help="thin every view's detected mask (Guo-Hall) before --support_check, --trim_edges, "
                         "--reprojection_score and --init edge_votes compare it with projected geometry: for a detector whose response is several pixels wide "
@@ -413,6 +425,12 @@ def trim_options(args):
     if args.thin_edge_maps:
         opts["thin"] = True
     return opts
+
+
+def dedupe_options(args):
+    """The options of ops.edge_dedupe.dedupe_edges that the command line sets; the rest keep their defaults."""
+    return {k: v for k, v in (("tolerance", args.dedupe_tolerance), ("cos_min", args.dedupe_cos_min),
+                              ("min_run", args.dedupe_min_run), ("min_span", args.dedupe_min_span)) if v is not None}
 
 
 def parse_args(argv):
@@ -461,17 +479,20 @@ def main(argv=None):
         for split, res in scores.items():
             if res is not None:
                 print(scan_line(split, res["aggregate"]))
-    if args.support_check or args.trim_edges:
+    if args.support_check or args.trim_edges or args.dedupe_edges:
         import json
-        from .edge_extraction.support import support_scene, trim_scene
+        from .edge_extraction.support import TRIMMED_FILE, dedupe_scene, support_scene, trim_scene
         with open(os.path.join(dataset.model_path, "parametric_edges.json")) as f:
             edge_dict = json.load(f)
         if args.support_check:
             support_scene(dataset.model_path, edge_dict, out["scene"].getTrainCameras(), None, dataset.detector,
                           **support_options(args))
         if args.trim_edges:
-            trim_scene(dataset.model_path, edge_dict, out["scene"].getTrainCameras(), None, dataset.detector,
-                       **trim_options(args))
+            trimmed, _ = trim_scene(dataset.model_path, edge_dict, out["scene"].getTrainCameras(), None, dataset.detector,
+                                    **trim_options(args))
+        if args.dedupe_edges:
+            dedupe_scene(dataset.model_path, trimmed if args.trim_edges else edge_dict,
+                         input_file=TRIMMED_FILE if args.trim_edges else "parametric_edges.json", **dedupe_options(args))
     print("\nTraining complete.")
 
 

@@ -1023,6 +1023,43 @@ int cgs_sample_support(int P, const float* points /*[P,3]*/, int V, const double
                        const int32_t* tol2 /*[T]*/, int32_t* tally /*[P,1+T]*/, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Which samples of the extracted edges a longer edge already covers: the pieces of a chord that runs along a real edge
+ * duplicate that edge, and ops/edge_dedupe.py drops them.  An all-pairs, sample-against-sample test in 3D; the reference has
+ * no counterpart.
+ *
+ * points is float32 [P,3], device, finite, as ``sample_edges`` gives it: edge e owns points[offsets[e]:offsets[e+1]];
+ * offsets is int32 [E+1], device, non-decreasing from 0 to P (NOT checked here: it lives on the device; the ops layer
+ * checks it); rank is int32 [E], device, a permutation of 0..E-1, rank 0 the edge that outranks all others.
+ *
+ * The rule, frozen.  Every operation is one IEEE fp32 operation in the written order, nothing is contracted into an FMA,
+ * so numpy float32 arrays reproduce it bit for bit.  Sample i is sample k of the n samples of edge a; sample j lies on
+ * edge b:
+ *   t_i = points[offsets[a] + min(k + 1, n - 1)] - points[offsets[a] + max(k - 1, 0)]      (0 on an edge of one sample)
+ *   q_i = (t.x*t.x + t.y*t.y) + t.z*t.z
+ *   j COVERS i iff  rank[b] < rank[a]                                                      (strict: never its own edge)
+ *              and  (dx*dx + dy*dy) + dz*dz <= tol2,      dx = p_i.x - p_j.x, ...
+ *              and  dot*dot >= (cos2 * q_i) * q_j,        dot = (t_i.x*t_j.x + t_i.y*t_j.y) + t_i.z*t_j.z
+ *   cover[i] = the minimum of rank[b] over the samples j that cover i, INT32_MAX when there is none
+ * A zero tangent makes the direction test 0 >= 0, which passes.  tol2 and cos2 are the squares, formed once by the caller.
+ *
+ * cover is int32 [P], device; the call writes every word (no initialisation needed).  workspace is
+ * cgs_sample_cover_workspace_bytes(P) bytes of device scratch, no initialisation needed.  A first kernel writes per sample
+ * its tangent and rank and per tile of 256 samples the bounding box and the rank range; the second tests 256 queries per
+ * workgroup against tiles of 256 candidates staged through LDS, skips a tile whose ranks cannot outrank a query or whose
+ * box lies further than the tolerance from the queries' box (a conservative test: csrc/edge_dedupe.hip), splits the
+ * candidates over grid.y and merges with an integer atomic minimum -- the result does not depend on the launch geometry.
+ * Offsets are 64-bit.  The caller's stream, no allocation, no host synchronisation.
+ *
+ * Every argument is checked, whether or not there is work: P or E < 0, tol2 negative or NaN, cos2 outside [0, 1] or NaN
+ * and NULL pointers (points and cover only when P > 0) are CGS_ERR_INVALID_ARGUMENT, rejected before anything is launched.
+ * Then P = 0 or E = 0 is a no-op (nothing is written).
+ * ------------------------------------------------------------------------------------------------ */
+size_t cgs_sample_cover_workspace_bytes(int P);
+int cgs_sample_cover(int P, const float* points /*[P,3]*/, int E, const int32_t* offsets /*[E+1]*/,
+                     const int32_t* rank /*[E]*/, float tol2, float cos2, int32_t* cover /*[P]*/, void* workspace,
+                     void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Parallel binary thinning of detected masks: a learned detector's response is several pixels wide, and the 2D checks above
  * (reprojection score, voxel vote, per-edge support) were designed on one-pixel lines.  The reference has no counterpart.
  *
