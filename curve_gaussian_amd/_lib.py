@@ -121,6 +121,8 @@ SIGNATURES = {
     "cgs_thin_masks": (_i, [_i, _i, _i, _vp, _vp, _vp, _i, C.POINTER(_i), _vp]),
     "cgs_sample_cover_workspace_bytes": (C.c_size_t, [_i]),
     "cgs_sample_cover": (_i, [_i, _vp, _i, _vp, _vp, _f, _f, _vp, _vp, _vp]),
+    "cgs_end_attach_workspace_bytes": (C.c_size_t, [_i, _i]),
+    "cgs_end_attach": (_i, [_i, _vp, _i, _vp, _f, _f, _vp, _vp, _vp]),
 }
 
 

@@ -1778,6 +1778,21 @@ int cgs_sample_cover(int P, const float* points, int E, const int32_t* offsets, 
     return finish("sample_cover", stream_);
 }
 
+size_t cgs_end_attach_workspace_bytes(int P, int E) { return end_attach_workspace_bytes(P, E); }
+
+int cgs_end_attach(int P, const float* points, int E, const int32_t* offsets, float tol2, float reach2, uint64_t* keys,
+                   void* workspace, void* stream_) {
+    if (P < 0 || E < 0) return reject("cgs_end_attach: invalid argument (P=%d, E=%d)", P, E);
+    if (!(tol2 >= 0.f) || !(reach2 >= 0.f))   // a NaN fails either comparison
+        return reject("cgs_end_attach: invalid argument (tol2=%g, reach2=%g; neither may be negative or NaN)", (double)tol2,
+                      (double)reach2);
+    if (!offsets || !workspace || (P > 0 && !points) || (E > 0 && !keys))
+        return reject("cgs_end_attach: invalid argument (NULL pointer; P=%d, E=%d)", P, E);
+    if (E == 0) return CGS_OK;   // no end: nothing is written
+    launch_end_attach((hipStream_t)stream_, P, points, E, offsets, tol2, reach2, (unsigned long long*)keys, workspace);
+    return finish("end_attach", stream_);
+}
+
 int cgs_thin_masks(int V, int height, int width, uint8_t* masks, uint8_t* scratch, int* changed_flag, int max_iterations,
                    int* iterations_out, void* stream_) {
     if (V < 0 || !edt_size_ok(height, width) || max_iterations < 0)

@@ -250,6 +250,11 @@ size_t sample_cover_workspace_bytes(int P);
 void launch_sample_cover(hipStream_t s, int P, const float* points, int E, const int* offsets, const int* rank, float tol2,
                          float cos2, int* cover, void* workspace);
 
+// edge_join.hip
+size_t end_attach_workspace_bytes(int P, int E);
+void launch_end_attach(hipStream_t s, int P, const float* points, int E, const int* offsets, float tol2, float reach2,
+                       unsigned long long* keys, void* workspace);
+
 // edge_thin.hip
 int launch_thin_masks(hipStream_t s, int V, int height, int width, uint8_t* masks, uint8_t* scratch, int* changed_flag,
                       int max_iterations, int* iterations, hipError_t* err);

@@ -16,8 +16,12 @@ leaves are what ``--dedupe`` is for): ``parametric_edges_trimmed.json`` and ``ed
 ``--dedupe`` the parts of the edges that a longer edge already covers in 3D are dropped (``ops.edge_dedupe``; its docstring
 freezes the rule and states the limits: the longer edge always wins, one pass, no image evidence, UNTUNED defaults) -- of
 the trimmed pieces with ``--trim``, of the edges of ``parametric_edges.json`` without: ``parametric_edges_deduped.json`` and
-``edge_dedupe.json``, one record per input edge.  ``parametric_edges.json`` is never written, and no option rewrites
-another option's files."""
+``edge_dedupe.json``, one record per input edge.  With ``--join`` the ends that the cuts left a few samples short of one
+another are rejoined at their junctions (``ops.edge_join``; its docstring freezes the rule and states the limits: 3D only,
+hosts of T-junctions are not split, an end joins at most one thing, UNTUNED defaults) -- of the last product of the chain:
+the deduped edges with ``--dedupe``, else the trimmed pieces with ``--trim``, else the edges of ``parametric_edges.json``:
+``parametric_edges_joined.json`` and ``edge_graph.json``.  ``parametric_edges.json`` is never written, and no option
+rewrites another option's files."""
 import argparse
 import json
 import logging
@@ -27,6 +31,7 @@ import sys
 import numpy as np
 
 from ..ops import edge_dedupe as ED
+from ..ops import edge_join as EJ
 from ..ops import edge_support as SP
 from ..ops import edge_trim as ET
 from .para_edge import EDGE_MAX_THRESHOLD, EDGE_VISIBILITY_FRAMES_RATIO
@@ -41,6 +46,8 @@ TRIM_FILE = "edge_trim.json"
 TRIMMED_FILE = "parametric_edges_trimmed.json"
 DEDUPE_FILE = "edge_dedupe.json"
 DEDUPED_FILE = "parametric_edges_deduped.json"
+GRAPH_FILE = "edge_graph.json"
+JOINED_FILE = "parametric_edges_joined.json"
 
 
 def filter_edge_dict(edge_dict, kept):
@@ -133,8 +140,37 @@ def write_dedupe(model_dir, edge_dict, result, extra=None):
     return out
 
 
+def join_graph(result, curves):
+    """The wireframe of a ``join_edges`` result (``curves``: how many of the edges are curves) as plain lists: "vertices"
+    [Nv,3]; "edges", per edge its kind, index within its kind and the vertex ids of its first and last end (-1: the edge has
+    no sample); "t_junctions", per T-attachment the end, its edge, the host edge, the sample and the parameter on the host,
+    the distance, the vertex and whether the host itself moved; "moved", the displacement per end [2E]; "collapsed" and
+    "released", as ``join_edges`` reports them; "counts"."""
+    ev = result["edge_vertices"]
+    edges = [{"kind": "curve" if e < curves else "line", "index": int(e if e < curves else e - curves),
+              "vertices": [int(ev[e, 0]), int(ev[e, 1])]} for e in range(len(ev))]
+    kind = result["attach"]["kind"]
+    counts = {"edges": len(edges), "vertices": int(len(result["vertices"])), "t_junctions": len(result["t_junctions"]),
+              "attached_ends": int(np.count_nonzero(kind != EJ.KIND_NONE)), "moved_ends": int(np.count_nonzero(result["moved"] > 0)),
+              "collapsed": len(result["collapsed"]), "released": len(result["released"])}
+    return {"vertices": result["vertices"].tolist(), "edges": edges, "t_junctions": [dict(t) for t in result["t_junctions"]],
+            "moved": [float(m) for m in result["moved"]], "collapsed": list(result["collapsed"]),
+            "released": list(result["released"]), "counts": counts}
+
+
+def write_join(model_dir, edge_dict, result, extra=None):
+    """``<model_dir>/edge_graph.json`` = {**join_graph, "settings", **extra} and ``<model_dir>/parametric_edges_joined.json``,
+    the joined edges.  Returns the first dict."""
+    out = {**(extra or {}), **join_graph(result, len(edge_dict["curves_ctl_pts"])), "settings": dict(result["settings"])}
+    write_score(os.path.join(model_dir, GRAPH_FILE), out)
+    with open(os.path.join(model_dir, JOINED_FILE), "w") as f:
+        json.dump(result["edge_dict"], f)
+    return out
+
+
 def score_scan(base_dir, dataset_dir, scan, layout="emap", detector="DexiNed", undistort=False, write_filtered=False,
-               device=None, backend="gpu", resolution=-1, trim_options=None, dedupe_options=None, **options):
+               device=None, backend="gpu", resolution=-1, trim_options=None, dedupe_options=None, join_options=None,
+               **options):
     """Checks ``<base_dir>/<scan>/parametric_edges.json`` against the ``detector`` edge maps of ``<dataset_dir>/<scan>`` and
     writes ``<base_dir>/<scan>/edge_support.json`` (``write_support``).  ``layout``, ``undistort`` and ``resolution`` (of the
     images) as ``reprojection.score_scan``, the same camera loaders; ``options`` go to ``ops.edge_support.edge_support``
@@ -143,7 +179,10 @@ def score_scan(base_dir, dataset_dir, scan, layout="emap", detector="DexiNed", u
     threshold and ``thin`` unless they name their own: ``write_trim`` then adds its two files.  ``dedupe_options`` (a dict,
     possibly empty; None: no deduping) go to ``ops.edge_dedupe.dedupe_edges`` on the trimmed pieces when there are any and
     on the edges of the prediction otherwise, with the check's sampling resolution unless they name their own:
-    ``write_dedupe`` then adds its two files, and "input" there names the file whose edges went in.  Returns the dict of ``write_support``, with the ones of ``write_trim`` and ``write_dedupe`` under "trim" and "dedupe"
+    ``write_dedupe`` then adds its two files, and "input" there names the file whose edges went in.  ``join_options`` (a
+    dict, possibly empty; None: no joining) go to ``ops.edge_join.join_edges`` on the last product of the chain -- the
+    deduped edges, else the trimmed pieces, else the edges of the prediction -- with the check's sampling resolution unless
+    they name their own: ``write_join`` then adds its two files, "input" again the file whose edges went in.  Returns the dict of ``write_support``, with the ones of ``write_trim``, ``write_dedupe`` and ``write_join`` under "trim", "dedupe" and "join"
     when there are any, or None -- after reporting it -- for a scan without a prediction."""
     SP._check_backend(backend)
     if layout not in LAYOUTS:
@@ -176,6 +215,12 @@ def score_scan(base_dir, dataset_dir, scan, layout="emap", detector="DexiNed", u
         shared = {k: options[k] for k in ("resolution",) if k in options}
         res = ED.dedupe_edges(given, device=device, backend=backend, **{**shared, **dedupe_options})
         out["dedupe"] = write_dedupe(os.path.join(base_dir, scan), given, res, extra={"scan": scan, "input": name})
+    if join_options is not None:
+        given, name = ((res["edge_dict"], DEDUPED_FILE) if dedupe_options is not None else
+                       (trim["edge_dict"], TRIMMED_FILE) if trim_options is not None else (edge_dict, "parametric_edges.json"))
+        shared = {k: options[k] for k in ("resolution",) if k in options}
+        joined = EJ.join_edges(given, device=device, backend=backend, **{**shared, **join_options})
+        out["join"] = write_join(os.path.join(base_dir, scan), given, joined, extra={"scan": scan, "input": name})
     return out
 
 
@@ -218,6 +263,19 @@ def dedupe_scene(model_path, edge_dict, input_file="parametric_edges.json", **op
     return res["edge_dict"], res
 
 
+def join_scene(model_path, edge_dict, input_file="parametric_edges.json", **options):
+    """The export's ``join``: the edges of ``edge_dict`` rejoined at their junctions (``join_edges``; no cameras: this is 3D
+    only).  ``input_file``: the file the edges came from, recorded as "input".  Writes ``edge_graph.json`` and
+    ``parametric_edges_joined.json`` into ``model_path``, prints the counts, and returns (the joined dict, the ``join_edges``
+    result)."""
+    res = EJ.join_edges(edge_dict, **options)
+    os.makedirs(model_path, exist_ok=True)
+    out = write_join(model_path, edge_dict, res, extra={"input": input_file})
+    print("joined: ", out["counts"]["edges"], "edges, ", out["counts"]["vertices"], "vertices, ", out["counts"]["t_junctions"],
+          "T-junctions, ", out["counts"]["moved_ends"], "ends moved")
+    return res["edge_dict"], res
+
+
 # ------------------------------------------------------------------------------------------------ command line
 def scan_line(scan, out):
     line = f"{scan}: views {out['settings']['views']}, edges {out['total']}, kept {out['kept']}"
@@ -226,6 +284,10 @@ def scan_line(scan, out):
     if "dedupe" in out:
         line += (f"; deduped to {out['dedupe']['pieces']} pieces, {out['dedupe']['redundant_samples']} of "
                  f"{out['dedupe']['samples']} samples redundant")
+    if "join" in out:
+        counts = out["join"]["counts"]
+        line += (f"; joined {counts['edges']} edges at {counts['vertices']} vertices, {counts['t_junctions']} T-junctions, "
+                 f"{counts['moved_ends']} ends moved")
     return line
 
 
@@ -270,6 +332,16 @@ def parser():
                     help="deduping: a run of fewer covered samples is not redundant (untuned)")
     ap.add_argument("--dedupe_min_span", type=int, default=ED.MIN_SPAN,
                     help="deduping: a free run of fewer samples is dropped (untuned)")
+    ap.add_argument("--join", action="store_true",
+                    help=f"also rejoin the ends at their junctions in 3D -- of the deduped edges with --dedupe, else of the "
+                         f"trimmed pieces with --trim, else of the edges: {JOINED_FILE} and {GRAPH_FILE} (untuned; hosts of "
+                         f"T-junctions are not split, an end joins at most one thing)")
+    ap.add_argument("--join_tolerance", type=float, default=None,
+                    help=f"joining: 3D distance within which an end attaches in any direction, and the half width of the "
+                         f"tube ahead of it (default: {EJ.TOLERANCE_RESOLUTIONS:g} x --sample_resolution; untuned)")
+    ap.add_argument("--join_reach", type=float, default=None,
+                    help=f"joining: how far ahead along its tangent an end looks (default: {EJ.REACH_RESOLUTIONS:g} x "
+                         f"--sample_resolution; untuned)")
     return ap
 
 
@@ -279,12 +351,14 @@ def main(argv=None):
             "frames_ratio": args.frames_ratio} if args.trim else None
     dedupe = {"tolerance": args.dedupe_tolerance, "cos_min": args.dedupe_cos_min, "min_run": args.dedupe_min_run,
               "min_span": args.dedupe_min_span} if args.dedupe else None
+    join = {"tolerance": args.join_tolerance, "reach": args.join_reach} if args.join else None
     for scan in dataset_scans(args.dataset_dir, args.layout, args.scans):
         out = score_scan(args.base_dir, args.dataset_dir, scan, args.layout, args.detector, args.undistort,
                          args.write_filtered, backend=args.backend, tolerances_px=args.tolerances,
                          keep_tolerance_px=args.keep_tolerance, min_visible=args.min_visible, min_near=args.min_near,
                          frames_ratio=args.frames_ratio, sample_resolution=args.sample_resolution,
                          edge_threshold=args.edge_threshold, trim_options=trim, dedupe_options=dedupe,
+                         join_options=join,
                          **({"thin": True} if args.thin else {}))
         if out is None:
             print(f"Invalid prediction at {scan}")

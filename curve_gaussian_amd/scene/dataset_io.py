@@ -274,7 +274,7 @@ def extract_curves(gaussians, merge_endpoints=False, distance_threshold=0.015):
 def write_parametric_edges(gaussians, model_path, merge_endpoints=False, distance_threshold=0.015,
                            visible_checking=False, scan_dir=None, detector="DexiNed", support_checking=False,
                            support_options=None, cameras=None, edge_maps=None, trim=False, trim_options=None,
-                           dedupe=False, dedupe_options=None):
+                           dedupe=False, dedupe_options=None, join=False, join_options=None):
     """Writes parametric_edges.json (the evaluation input, train.py:287-293) and edge_points.ply (ASCII, :277-285).
     merge_endpoints / distance_threshold: see extract_curves (the reference's default is merge_endpoints=True).
     visible_checking=True keeps only the edges that `detector`'s edge maps of the scan at `scan_dir` show
@@ -291,7 +291,12 @@ def write_parametric_edges(gaussians, model_path, merge_endpoints=False, distanc
     dedupe=True (off by default; the reference has no counterpart) drops the parts of the edges that a longer edge already
     covers in 3D -- of the trimmed pieces after trim=True, of the written edges otherwise -- and writes edge_dedupe.json and
     parametric_edges_deduped.json, again next to files that stay as they are (edge_extraction.support.dedupe_scene;
-    `dedupe_options` go to ops.edge_dedupe.dedupe_edges, whose defaults are untuned).  It needs no cameras on its own."""
+    `dedupe_options` go to ops.edge_dedupe.dedupe_edges, whose defaults are untuned).  It needs no cameras on its own.
+    join=True (off by default; the reference's merge_endpoints joins end points only, and before any cut) rejoins the ends
+    at their junctions in 3D -- of the deduped edges after dedupe=True, else of the trimmed pieces after trim=True, else of
+    the written edges -- and writes edge_graph.json and parametric_edges_joined.json, again next to files that stay as they
+    are (edge_extraction.support.join_scene; `join_options` go to ops.edge_join.join_edges, whose defaults are untuned).
+    It needs no cameras on its own."""
     if visible_checking and scan_dir is None:
         raise ValueError("write_parametric_edges(visible_checking=True) needs scan_dir, the scan holding "
                          "meta_data.json and the edge maps")
@@ -311,8 +316,13 @@ def write_parametric_edges(gaussians, model_path, merge_endpoints=False, distanc
         trimmed, _ = trim_scene(model_path, edge_dict, cameras, edge_maps, detector, **(trim_options or {}))
     if dedupe:
         from ..edge_extraction.support import TRIMMED_FILE, dedupe_scene
-        dedupe_scene(model_path, trimmed if trim else edge_dict, input_file=TRIMMED_FILE if trim else "parametric_edges.json",
-                     **(dedupe_options or {}))
+        deduped, _ = dedupe_scene(model_path, trimmed if trim else edge_dict,
+                                  input_file=TRIMMED_FILE if trim else "parametric_edges.json", **(dedupe_options or {}))
+    if join:
+        from ..edge_extraction.support import DEDUPED_FILE, TRIMMED_FILE, join_scene
+        given, name = ((deduped, DEDUPED_FILE) if dedupe else (trimmed, TRIMMED_FILE) if trim else
+                       (edge_dict, "parametric_edges.json"))
+        join_scene(model_path, given, input_file=name, **(join_options or {}))
     return edge_dict, pts
 
 

@@ -399,6 +399,16 @@ def build_parser():
                    help="deduping: least |cosine| between the two edges' directions for a cover")
     p.add_argument("--dedupe_min_run", type=int, default=None, help="deduping: a run of fewer covered samples is not redundant")
     p.add_argument("--dedupe_min_span", type=int, default=None, help="deduping: a free run of fewer samples is dropped")
+    p.add_argument("--join_edges", action="store_true",
+                   help="after the export, rejoin the ends of the edges at their junctions in 3D -- of the deduped edges with "
+                        "--dedupe_edges, else of the trimmed pieces with --trim_edges, else of parametric_edges.json: "
+                        "edge_graph.json and parametric_edges_joined.json in the model directory; the other files stay as "
+                        "they are (untuned defaults; hosts of T-junctions are not split, an end joins at most one thing)")
+    p.add_argument("--join_tolerance", type=float, default=None,
+                   help="joining: 3D distance within which an end attaches in any direction, and the half width of the tube "
+                        "ahead of it (default: 2 x the sampling resolution; untuned)")
+    p.add_argument("--join_reach", type=float, default=None,
+                   help="joining: how far ahead along its tangent an end looks (default: 8 x the sampling resolution; untuned)")
     p.add_argument("--thin_edge_maps", action="store_true",
                    help="thin every view's detected mask (Guo-Hall) before --support_check, --trim_edges, "
                         "--reprojection_score and --init edge_votes compare it with projected geometry: for a detector whose response is several pixels wide "
@@ -431,6 +441,11 @@ def dedupe_options(args):
     """The options of ops.edge_dedupe.dedupe_edges that the command line sets; the rest keep their defaults."""
     return {k: v for k, v in (("tolerance", args.dedupe_tolerance), ("cos_min", args.dedupe_cos_min),
                               ("min_run", args.dedupe_min_run), ("min_span", args.dedupe_min_span)) if v is not None}
+
+
+def join_options(args):
+    """The options of ops.edge_join.join_edges that the command line sets; the rest keep their defaults."""
+    return {k: v for k, v in (("tolerance", args.join_tolerance), ("reach", args.join_reach)) if v is not None}
 
 
 def parse_args(argv):
@@ -479,9 +494,9 @@ def main(argv=None):
         for split, res in scores.items():
             if res is not None:
                 print(scan_line(split, res["aggregate"]))
-    if args.support_check or args.trim_edges or args.dedupe_edges:
+    if args.support_check or args.trim_edges or args.dedupe_edges or args.join_edges:
         import json
-        from .edge_extraction.support import TRIMMED_FILE, dedupe_scene, support_scene, trim_scene
+        from .edge_extraction.support import DEDUPED_FILE, TRIMMED_FILE, dedupe_scene, join_scene, support_scene, trim_scene
         with open(os.path.join(dataset.model_path, "parametric_edges.json")) as f:
             edge_dict = json.load(f)
         if args.support_check:
@@ -491,8 +506,13 @@ def main(argv=None):
             trimmed, _ = trim_scene(dataset.model_path, edge_dict, out["scene"].getTrainCameras(), None, dataset.detector,
                                     **trim_options(args))
         if args.dedupe_edges:
-            dedupe_scene(dataset.model_path, trimmed if args.trim_edges else edge_dict,
-                         input_file=TRIMMED_FILE if args.trim_edges else "parametric_edges.json", **dedupe_options(args))
+            deduped, _ = dedupe_scene(dataset.model_path, trimmed if args.trim_edges else edge_dict,
+                                      input_file=TRIMMED_FILE if args.trim_edges else "parametric_edges.json",
+                                      **dedupe_options(args))
+        if args.join_edges:
+            given, name = ((deduped, DEDUPED_FILE) if args.dedupe_edges else (trimmed, TRIMMED_FILE) if args.trim_edges else
+                           (edge_dict, "parametric_edges.json"))
+            join_scene(dataset.model_path, given, input_file=name, **join_options(args))
     print("\nTraining complete.")
 
 

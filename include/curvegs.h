@@ -1060,6 +1060,42 @@ int cgs_sample_cover(int P, const float* points /*[P,3]*/, int E, const int32_t*
                      void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Where the ends of the extracted edges land on other edges: trimming and deduping cut edges short of their junctions, and
+ * ops/edge_join.py rejoins them.  A test of all ends against all samples in 3D, with a direction; the reference's
+ * merge_endpoints knows only end point against end point inside one ball.
+ *
+ * points is float32 [P,3], device, finite, as ``sample_edges`` gives it: edge e owns points[offsets[e]:offsets[e+1]];
+ * offsets is int32 [E+1], device, non-decreasing from 0 to P (NOT checked here: it lives on the device; the ops layer
+ * checks it).
+ *
+ * The rule, frozen.  Every operation is one IEEE fp32 operation in the written order, nothing is contracted into an FMA,
+ * so numpy float32 arrays reproduce it bit for bit.  Edge e with n >= 1 samples has end 2e at its first sample and end
+ * 2e+1 at its last; an edge without samples has no end.  For an end of edge a at sample i with point p:
+ *   t = points[i] - points[inner],  inner = i + min(1, n-1) for the first end, i - min(1, n-1) for the last   (outward)
+ *   q = (t.x*t.x + t.y*t.y) + t.z*t.z,  rq = reach2*q,  tq = tol2*q                   (an edge of one sample: t = 0, q = 0)
+ * Sample j of edge b, with w = points[j] - p, w2 = (w.x*w.x + w.y*w.y) + w.z*w.z and s = (w.x*t.x + w.y*t.y) + w.z*t.z,
+ * is ACCEPTED iff b != a and one of
+ *   NEAR  w2 <= tol2                                            (the ball of merge_endpoints, any direction)
+ *   TUBE  s > 0 and s*s <= rq and (w2*q) - (s*s) <= tq          (ahead, at most reach along the tangent, tolerance beside)
+ *   ENDS  j is the first or the last sample of b, s > 0 and w2 <= reach2    (another edge's end ahead within reach)
+ *   keys[end] = the minimum over the accepted samples of (uint64(bits(w2)) << 32) | uint32(j); 2^64 - 1 when there is none
+ * and for the two ends of an edge without samples.  tol2 and reach2 are the squares, formed once by the caller.
+ *
+ * keys is uint64 [2E], device; the call writes every word (no initialisation needed).  workspace is
+ * cgs_end_attach_workspace_bytes(P, E) bytes of device scratch, no initialisation needed.  A first kernel writes per
+ * sample (x, y, z, edge and end flag) and per end its record; the second tests 256 ends per workgroup against tiles of 256
+ * samples staged through LDS, splits the samples over grid.y and merges with a 64-bit atomic minimum -- the result does
+ * not depend on the launch geometry.  Offsets are 64-bit.  The caller's stream, no allocation, no host synchronisation.
+ *
+ * Every argument is checked, whether or not there is work: P or E < 0, tol2 or reach2 negative or NaN and NULL pointers
+ * (points only when P > 0, keys only when E > 0) are CGS_ERR_INVALID_ARGUMENT, rejected before anything is launched.
+ * Then E = 0 is a no-op (nothing is written); with P = 0 every key is written as 2^64 - 1.
+ * ------------------------------------------------------------------------------------------------ */
+size_t cgs_end_attach_workspace_bytes(int P, int E);
+int cgs_end_attach(int P, const float* points /*[P,3]*/, int E, const int32_t* offsets /*[E+1]*/, float tol2, float reach2,
+                   uint64_t* keys /*[2E]*/, void* workspace, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Parallel binary thinning of detected masks: a learned detector's response is several pixels wide, and the 2D checks above
  * (reprojection score, voxel vote, per-edge support) were designed on one-pixel lines.  The reference has no counterpart.
  *
