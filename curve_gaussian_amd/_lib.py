@@ -123,6 +123,9 @@ SIGNATURES = {
     "cgs_sample_cover": (_i, [_i, _vp, _i, _vp, _vp, _f, _f, _vp, _vp, _vp]),
     "cgs_end_attach_workspace_bytes": (C.c_size_t, [_i, _i]),
     "cgs_end_attach": (_i, [_i, _vp, _i, _vp, _f, _f, _vp, _vp, _vp]),
+    "cgs_mask_orientation": (_i, [_i, _i, _i, _vp, _vp, _vp]),
+    "cgs_oriented_near": (_i, [_i, _i, _i, _vp, _i, _vp, _vp]),
+    "cgs_sample_support_oriented": (_i, [_i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _i, _vp, _vp]),
 }
 
 
@@ -170,6 +173,11 @@ EDGE_SUPPORT_MAX_TOL = 4   # CGS_EDGE_SUPPORT_MAX_TOL
 THIN_PASS_ITERATIONS = 4   # CGS_THIN_PASS_ITERATIONS
 THIN_TILE_WIDTH = 48   # CGS_THIN_TILE_WIDTH
 THIN_TILE_HEIGHT = 240   # CGS_THIN_TILE_HEIGHT
+ORIENT_RADIUS = 3   # CGS_ORIENT_RADIUS
+ORIENT_MAX_TOL2 = 16   # CGS_ORIENT_MAX_TOL2
+ORIENT_MAX_SPREAD = 4   # CGS_ORIENT_MAX_SPREAD
+ORIENT_TILE_WIDTH = 64   # CGS_ORIENT_TILE_WIDTH
+ORIENT_TILE_HEIGHT = 32   # CGS_ORIENT_TILE_HEIGHT
 REPORT_PANELS = ("render", "ground_truth", "depth", "rend_dir", "rend_alpha")   # panel order of cgs_report_panels
 
 _lib = None

@@ -1816,4 +1816,46 @@ int cgs_thin_masks(int V, int height, int width, uint8_t* masks, uint8_t* scratc
     return passes;
 }
 
+int cgs_mask_orientation(int V, int height, int width, const uint8_t* mask, uint8_t* code, void* stream_) {
+    if (V < 0 || !edt_size_ok(height, width))
+        return reject("cgs_mask_orientation: invalid argument (V=%d, height=%d, width=%d; sizes lie in [1, %d])", V, height,
+                      width, CGS_EDT_MAX_SIZE);
+    if (!mask || !code) return reject("cgs_mask_orientation: invalid argument (NULL pointer)");
+    if (V == 0) return CGS_OK;   // nothing to write
+    launch_mask_orientation((hipStream_t)stream_, V, height, width, mask, code);
+    return finish("mask_orientation", stream_);
+}
+
+int cgs_oriented_near(int V, int height, int width, const uint8_t* code, int tol2, uint8_t* near, void* stream_) {
+    if (V < 0 || !edt_size_ok(height, width))
+        return reject("cgs_oriented_near: invalid argument (V=%d, height=%d, width=%d; sizes lie in [1, %d])", V, height,
+                      width, CGS_EDT_MAX_SIZE);
+    if (tol2 < 0 || tol2 > CGS_ORIENT_MAX_TOL2)
+        return reject("cgs_oriented_near: invalid argument (tol2=%d; tol2 lies in [0, %d])", tol2, CGS_ORIENT_MAX_TOL2);
+    if (!code || !near) return reject("cgs_oriented_near: invalid argument (NULL pointer)");
+    const size_t bytes = (size_t)V * (size_t)height * (size_t)width;   // at most 2^31 * 2^28
+    const uintptr_t c0 = reinterpret_cast<uintptr_t>(code), n0 = reinterpret_cast<uintptr_t>(near);
+    if (c0 < n0 + bytes && n0 < c0 + bytes)   // a tile reads its halo from code while its neighbours write near
+        return reject("cgs_oriented_near: invalid argument (code and near overlap)");
+    if (V == 0) return CGS_OK;   // nothing to write
+    launch_oriented_near((hipStream_t)stream_, V, height, width, code, tol2, near);
+    return finish("oriented_near", stream_);
+}
+
+int cgs_sample_support_oriented(int P, const float* points, const int32_t* partner, int V, const double* intr,
+                                const double* w2c, int height, int width, const uint8_t* near, int spread, int32_t* tally,
+                                void* stream_) {
+    if (P < 0 || V < 0 || spread < 0 || spread > CGS_ORIENT_MAX_SPREAD)
+        return reject("cgs_sample_support_oriented: invalid argument (P=%d, V=%d, spread=%d; the spread lies in [0, %d])", P, V,
+                      spread, CGS_ORIENT_MAX_SPREAD);
+    if (!edt_size_ok(height, width))
+        return reject("cgs_sample_support_oriented: invalid argument (height=%d, width=%d; sizes lie in [1, %d])", height,
+                      width, CGS_EDT_MAX_SIZE);
+    if (!intr || !w2c || !near || (P > 0 && (!points || !partner || !tally)))
+        return reject("cgs_sample_support_oriented: invalid argument (NULL pointer; P=%d, V=%d)", P, V);
+    if (P == 0 || V == 0) return CGS_OK;   // nothing to add
+    launch_sample_support_oriented((hipStream_t)stream_, P, points, partner, V, intr, w2c, height, width, near, spread, tally);
+    return finish("sample_support_oriented", stream_);
+}
+
 }  // extern "C"

@@ -259,4 +259,10 @@ void launch_end_attach(hipStream_t s, int P, const float* points, int E, const i
 int launch_thin_masks(hipStream_t s, int V, int height, int width, uint8_t* masks, uint8_t* scratch, int* changed_flag,
                       int max_iterations, int* iterations, hipError_t* err);
 
+// edge_orient.hip
+void launch_mask_orientation(hipStream_t s, int V, int height, int width, const uint8_t* mask, uint8_t* code);
+void launch_oriented_near(hipStream_t s, int V, int height, int width, const uint8_t* code, int tol2, uint8_t* near);
+void launch_sample_support_oriented(hipStream_t s, int P, const float* points, const int* partner, int V, const double* intr,
+                                    const double* w2c, int height, int width, const uint8_t* near, int spread, int* tally);
+
 }  // namespace cgs

@@ -12,7 +12,9 @@ writes ``<base_dir>/<scan>/edge_support.json`` -- one record per edge -- and, wi
 ``parametric_edges_supported.json`` with the kept edges.  With ``--trim`` every edge of ``parametric_edges.json`` -- not only
 the kept ones: the verdict drops an over-long true edge whole -- is also cut down to the spans of its length that the images
 show (``ops.edge_trim``; its docstring freezes the rule and states the limits: no depth, UNTUNED defaults; the duplicates it
-leaves are what ``--dedupe`` is for): ``parametric_edges_trimmed.json`` and ``edge_trim.json``, one record per edge.  With
+leaves are what ``--dedupe`` is for): ``parametric_edges_trimmed.json`` and ``edge_trim.json``, one record per edge.  ``--trim
+--oriented`` counts a sample as near only where a detected pixel within the tolerance runs the way the sample's edge does
+(``ops.edge_orient``: the rule and its limits; the same two files, fewer stubs where a chord crosses a real edge).  With
 ``--dedupe`` the parts of the edges that a longer edge already covers in 3D are dropped (``ops.edge_dedupe``; its docstring
 freezes the rule and states the limits: the longer edge always wins, one pass, no image evidence, UNTUNED defaults) -- of
 the trimmed pieces with ``--trim``, of the edges of ``parametric_edges.json`` without: ``parametric_edges_deduped.json`` and
@@ -32,6 +34,7 @@ import numpy as np
 
 from ..ops import edge_dedupe as ED
 from ..ops import edge_join as EJ
+from ..ops import edge_orient as OR
 from ..ops import edge_support as SP
 from ..ops import edge_trim as ET
 from .para_edge import EDGE_MAX_THRESHOLD, EDGE_VISIBILITY_FRAMES_RATIO
@@ -320,6 +323,12 @@ def parser():
                     help="trimming: two supported runs at most this many samples apart are merged (untuned)")
     ap.add_argument("--trim_min_span", type=int, default=ET.MIN_SPAN,
                     help="trimming: a supported run of fewer samples is dropped (untuned)")
+    ap.add_argument("--oriented", action="store_true",
+                    help="trimming (needs --trim): a sample counts as near only where a detected pixel within the tolerance runs "
+                         "the way its edge does (ops.edge_orient; untuned; thick strokes fall back to the distance test)")
+    ap.add_argument("--orient_spread", type=int, default=OR.SPREAD,
+                    help=f"oriented trimming: the octants of 22.5 degrees to either side that still agree, 0 to "
+                         f"{OR.MAX_SPREAD} (untuned)")
     ap.add_argument("--dedupe", action="store_true",
                     help=f"also drop what a longer edge already covers in 3D -- of the trimmed pieces with --trim, of the "
                          f"edges otherwise: {DEDUPED_FILE} and {DEDUPE_FILE} (untuned; the longer edge always wins)")
@@ -346,9 +355,14 @@ def parser():
 
 
 def main(argv=None):
-    args = parser().parse_args(argv)
+    ap = parser()
+    args = ap.parse_args(argv)
+    if args.oriented and not args.trim:
+        ap.error("--oriented needs --trim: it changes how trimming tallies")
     trim = {"tolerance_px": args.trim_tolerance, "max_gap": args.trim_max_gap, "min_span": args.trim_min_span,
             "frames_ratio": args.frames_ratio} if args.trim else None
+    if args.oriented:
+        trim.update({"oriented": True, "spread": args.orient_spread})
     dedupe = {"tolerance": args.dedupe_tolerance, "cos_min": args.dedupe_cos_min, "min_run": args.dedupe_min_run,
               "min_span": args.dedupe_min_span} if args.dedupe else None
     join = {"tolerance": args.join_tolerance, "reach": args.join_reach} if args.join else None

@@ -25,7 +25,9 @@ Definitions, frozen; n = the samples of edge e, ``sample_edges`
 
 KNOWN LIMITS.  There is no depth, as in ops/edge_support.py: a stretch hidden behind a surface in most views is cut
 away.  The pieces of a chord that runs along a real edge duplicate that edge; this module does not merge them
-(ops/edge_dedupe.py, opt-in, drops what a longer edge already covers).  The cut lands up to the tolerance plus a pixel
+(ops/edge_dedupe.py, opt-in, drops what a longer edge already covers).  The tally asks how near a detected pixel is, not
+which way the detected edge runs there, so a chord collects support where it crosses a real edge (``oriented=True``,
+ops/edge_orient.py, opt-in, holds the edge's direction against the pixels' orientations).  The cut lands up to the tolerance plus a pixel
 diagonal beyond the true end, because a sample just past the end still falls on a pixel near the drawn one.  THE
 DEFAULTS OF ``trim_edges`` ARE UNTUNED: only the drawn test scan (tests/edge_trim_cases.py) has been checked, no real
 scan.
@@ -40,6 +42,7 @@ import torch
 from .. import _lib as L
 from ..edge_extraction.para_edge import EDGE_MAX_THRESHOLD, EDGE_VISIBILITY_FRAMES_RATIO
 from ..edge_extraction.reprojection import SAMPLE_RESOLUTION
+from . import edge_orient as OR
 from . import edge_score as ES
 from . import edge_support as SP
 from .edge_thin import thin_masks
@@ -202,13 +205,20 @@ def trim_geometry(curves, lines, offsets, spans):
 # ------------------------------------------------------------------------------------------------ a scan
 def trim_edges(edge_dict, cameras, edge_maps_u8, detector, resolution=SAMPLE_RESOLUTION, tolerance_px=TOLERANCE_PX,
                frames_ratio=EDGE_VISIBILITY_FRAMES_RATIO, max_gap=MAX_GAP, min_span=MIN_SPAN,
-               edge_threshold=EDGE_MAX_THRESHOLD, backend="gpu", device=None, budget_bytes=None, thin=False):
+               edge_threshold=EDGE_MAX_THRESHOLD, backend="gpu", device=None, budget_bytes=None, thin=False, oriented=False,
+               spread=OR.SPREAD):
     """edge_dict, cameras, edge_maps_u8, detector, resolution, edge_threshold, budget_bytes and thin as ``edge_support``
     takes them, and the same walk over the views: ``view_chunks``, ``detected_masks``, the optional ``thin_masks``,
     ``edt_squared``, then one ``sample_tally`` call per chunk into one tally -- integers, so the chunking cannot change a bit.
     EVERY edge of edge_dict is trimmed, whatever ``edge_support`` says of it: the verdict drops over-long true edges whole,
     and those are the ones trimming exists for.  ``tolerance_px``: the one pixel tolerance; the frame rule counts all
     cameras.  THE DEFAULTS ARE UNTUNED (the drawn test scan only) and there is no depth: see the module docstring.
+
+    ``oriented=True`` (off by default; ops/edge_orient.py freezes the rule and states its limits) counts a sample as near
+    only where a detected pixel within the tolerance runs the way the sample's edge does, to within ``spread`` octants of
+    22.5 degrees: the walk is ``detected_masks``, the optional ``thin_masks``, ``mask_orientation``, ``oriented_near`` (a
+    tolerance of at most 4 pixels) and one ``oriented_tally`` call per chunk -- no distance transform, three bytes per pixel.
+    "settings" then records "oriented" and "spread".  With oriented=False nothing changes by a byte.
 
     Returns {"tally": int32 [P,2] CPU tensor, "offsets": int32 [E+1], "spans": per edge its list of (a, b), "edge_dict": the
     pieces in the layout of ``get_parametric_edge`` (curves [k,4,3], lines [m,6], as lists), "source": int64 [k+m], the
@@ -229,10 +239,22 @@ def trim_edges(edge_dict, cameras, edge_maps_u8, detector, resolution=SAMPLE_RES
     else:
         pts_b = pts
     tally = torch.zeros((pts.shape[0], 2), dtype=torch.int32, device=device if backend == "gpu" else None)
-    for _, _, sel, intr, w2c in view_chunks(cameras, BYTES_PER_PIXEL, budget):
+    if oriented:
+        spread = OR._spread(spread)
+        OR._tol2(tolerance_px)
+        partner = OR.sample_partners(off)
+        partner_b = torch.from_numpy(partner).to(device) if backend == "gpu" else partner
+    for _, _, sel, intr, w2c in view_chunks(cameras, OR.BYTES_PER_PIXEL if oriented else BYTES_PER_PIXEL, budget):
         det = detected_masks(lut, maps, sel)
         if thin:
             det = thin_masks(det, backend=backend, device=device)
+        if oriented:
+            near = OR.oriented_near(OR.mask_orientation(det, backend=backend, device=device), tolerance_px, backend=backend,
+                                    device=device)
+            del det
+            OR.oriented_tally(pts_b, partner_b, intr, w2c, near, spread, backend=backend, out=tally)
+            del near
+            continue
         d2 = ES.edt_squared(det, backend=backend, device=device)
         del det
         sample_tally(pts_b, intr, w2c, d2, [tolerance_px], backend=backend, out=tally)
@@ -245,6 +267,8 @@ def trim_edges(edge_dict, cameras, edge_maps_u8, detector, resolution=SAMPLE_RES
                 "views": V, "points": int(pts.shape[0])}
     if thin:
         settings["thin"] = True
+    if oriented:
+        settings.update({"oriented": True, "spread": spread})
     return {"tally": tally, "offsets": off, "spans": spans,
             "edge_dict": {"curves_ctl_pts": out_c.tolist(), "lines_end_pts": out_l.reshape(-1, 6).tolist()},
             "source": source, "settings": settings}

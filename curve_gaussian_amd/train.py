@@ -387,6 +387,11 @@ def build_parser():
     p.add_argument("--trim_max_gap", type=int, default=None,
                    help="trimming: two supported runs at most this many samples apart are merged")
     p.add_argument("--trim_min_span", type=int, default=None, help="trimming: a supported run of fewer samples is dropped")
+    p.add_argument("--trim_oriented", action="store_true",
+                   help="trimming: a sample counts as near only where a detected pixel within the tolerance runs the way its "
+                        "edge does (ops.edge_orient; untuned; thick strokes fall back to the distance test)")
+    p.add_argument("--trim_orient_spread", type=int, default=None,
+                   help="oriented trimming: the octants of 22.5 degrees to either side that still agree, 0 to 4")
     p.add_argument("--dedupe_edges", action="store_true",
                    help="after the export, drop the parts of the edges that a longer edge already covers in 3D -- of the "
                         "trimmed pieces with --trim_edges, of parametric_edges.json otherwise: edge_dedupe.json and "
@@ -434,6 +439,10 @@ def trim_options(args):
                               ("min_span", args.trim_min_span)) if v is not None}
     if args.thin_edge_maps:
         opts["thin"] = True
+    if args.trim_oriented:
+        opts["oriented"] = True
+        if args.trim_orient_spread is not None:
+            opts["spread"] = args.trim_orient_spread
     return opts
 
 

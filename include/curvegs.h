@@ -1132,6 +1132,68 @@ int cgs_thin_masks(int V, int height, int width, uint8_t* masks /*[V,height,widt
                    uint8_t* scratch /*[V,height,width], no initialisation needed*/, int* changed_flag /*device, [1]*/,
                    int max_iterations /*0: until stable*/, int* iterations_out /*host, may be NULL*/, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Orientation-aware 2D support: cgs_sample_support asks whether a projected sample lies near a detected pixel, not whether
+ * the edge runs the way the detected edge runs, so a chord that crosses a real edge collects support at the crossing.  These
+ * three entries give every detected pixel an orientation, gather the orientations over the tolerance disk, and tally per
+ * sample with the direction of the sample's own edge held against them (ops/edge_orient.py; opt-in: trim_edges
+ * (oriented=True)).  The reference has no counterpart.  The rule, frozen -- integers, and float64 one rounded operation at
+ * a time, so the numpy back end agrees on every bit:
+ *
+ * octant(a, b) for (a, b) != (0, 0): the half-open octant of the doubled angle, by signs and one comparison of magnitudes
+ *   a >  0, b >= 0:  0 if |b| < |a| else 1          a <  0, b <= 0:  4 if |b| < |a| else 5
+ *   a <= 0, b >  0:  2 if |b| > |a| else 3          a >= 0, b <  0:  6 if |b| > |a| else 7
+ * Bin k is a line orientation in [22.5 k, 22.5 (k + 1)) degrees, x to the right and y down: a horizontal line gives 0, the
+ * line y = x gives 2, a vertical line 4, the line y = -x gives 6.
+ *
+ * cgs_mask_orientation: code[v][y][x], uint8, from view v's mask (nonzero = set; pixels outside the image are unset).  An
+ * unset pixel gets 0.  For a set pixel, over the set pixels of its window (dx, dy) in [-R, R]^2, R = CGS_ORIENT_RADIUS = 3:
+ *   N = sum 1, Sx = sum dx, Sy = sum dy, Sxx = sum dx dx, Syy = sum dy dy, Sxy = sum dx dy
+ *   A = N Sxx - Sx Sx,  B = N Sxy - Sx Sy,  C = N Syy - Sy Sy,  a = A - C,  b = 2 B
+ *   ORIENTED iff N >= 3 and (a, b) != (0, 0) and 4 (a a + b b) >= (A + C)(A + C)          (a coherence of at least 0.5)
+ *   code = 1 << octant(a, b) when oriented, else 0xFF: it accepts every direction (lone pixels, junctions, blobs, strokes
+ *   wider than about 3 pixels).  A + C <= 49 * 392 and a a + b b <= (A + C)^2, so 4 (a a + b b) < 2^31.
+ * One workgroup per tile of CGS_ORIENT_TILE_WIDTH x CGS_ORIENT_TILE_HEIGHT pixels, the tile and its halo staged in LDS once,
+ * separable sums, every output byte written by its one owner (no initialisation needed), no atomics.
+ *
+ * cgs_oriented_near: near[v][y][x] = the OR of code[v][y + dy][x + dx] over dx dx + dy dy <= tol2 (inside the image),
+ * 0 <= tol2 <= CGS_ORIENT_MAX_TOL2 = CGS_EDGE_SUPPORT_MAX_TOL^2.  near != 0 iff the cgs_edt_squared transform of the mask is
+ * <= tol2: the oriented path needs no distance transform.  Same tiles; every output byte written.  code and near must not
+ * overlap: a tile reads its halo from code while its neighbours write near, so overlapping ranges are rejected.
+ *
+ * cgs_sample_support_oriented: points, intr, w2c and SEEN as for cgs_sample_support.  partner is int32 [P], device: the
+ * neighbour on its edge that gives sample i a direction (ops.edge_orient.sample_partners: i + 1, i - 1 for the last sample
+ * of an edge, i for an edge of one sample).  For a sample seen in view v at (u, v), the accepted orientations are
+ *   acc = 0xFF                       if partner[i] == i, or partner[i] lies outside [0, P), or the partner is not seen in v
+ *   else with dx = u_p - u, dy = v_p - v, a = dx dx - dy dy, b = 2 (dx dy)    (float64, each operation rounded, this order)
+ *   acc = 0xFF                       if (a, b) == (0, 0)
+ *   acc = the bits (octant(a, b) + s) mod 8 for s = -spread .. spread,  0 <= spread <= CGS_ORIENT_MAX_SPREAD = 4 (all bits)
+ *   tally[i][0] += the number of the V views that see sample i
+ *   tally[i][1] += the number of those with (near[v][floor(v)][floor(u)] & acc) != 0
+ * spread = 1 accepts every pair of orientations nearer than 22.5 degrees and refuses every pair further than 45.  tally is
+ * int32 [P,2], device; the entry ADDS, like cgs_sample_support.  One thread per sample with the view loop inside it, the
+ * partner's point read once, one read-modify-write of the thread's own row: no atomics, no LDS, no barrier, 64-bit offsets.
+ *
+ * All three run on the caller's stream with no allocation and no host synchronisation, and their results do not depend on
+ * the launch geometry or on how the views are cut into calls.  Every argument is checked, whether or not there is work: V or
+ * P < 0, a size outside [1, CGS_EDT_MAX_SIZE], tol2 outside [0, CGS_ORIENT_MAX_TOL2], spread outside
+ * [0, CGS_ORIENT_MAX_SPREAD], NULL pointers (points, partner and tally only when P > 0) and overlapping code and near are
+ * CGS_ERR_INVALID_ARGUMENT, rejected before anything is launched.  Then V = 0 (or P = 0) is a no-op.
+ * ------------------------------------------------------------------------------------------------ */
+#define CGS_ORIENT_RADIUS 3
+#define CGS_ORIENT_MAX_TOL2 16
+#define CGS_ORIENT_MAX_SPREAD 4
+#define CGS_ORIENT_TILE_WIDTH 64
+#define CGS_ORIENT_TILE_HEIGHT 32
+int cgs_mask_orientation(int V, int height, int width, const uint8_t* mask /*[V,height,width]*/,
+                         uint8_t* code /*[V,height,width]*/, void* stream);
+int cgs_oriented_near(int V, int height, int width, const uint8_t* code /*[V,height,width]*/, int tol2,
+                      uint8_t* near /*[V,height,width]*/, void* stream);
+int cgs_sample_support_oriented(int P, const float* points /*[P,3]*/, const int32_t* partner /*[P]*/, int V,
+                                const double* intr /*[V,4]*/, const double* w2c /*[V,12]*/, int height, int width,
+                                const uint8_t* near /*[V,height,width]*/, int spread, int32_t* tally /*[P,2]*/,
+                                void* stream);
+
 #ifdef __cplusplus
 }
 #endif
