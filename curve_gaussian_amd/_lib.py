@@ -126,6 +126,7 @@ SIGNATURES = {
     "cgs_mask_orientation": (_i, [_i, _i, _i, _vp, _vp, _vp]),
     "cgs_oriented_near": (_i, [_i, _i, _i, _vp, _i, _vp, _vp]),
     "cgs_sample_support_oriented": (_i, [_i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _i, _vp, _vp]),
+    "cgs_sample_snap_terms": (_i, [_i, _vp, _i, _vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
 }
 
 
@@ -178,6 +179,8 @@ ORIENT_MAX_TOL2 = 16   # CGS_ORIENT_MAX_TOL2
 ORIENT_MAX_SPREAD = 4   # CGS_ORIENT_MAX_SPREAD
 ORIENT_TILE_WIDTH = 64   # CGS_ORIENT_TILE_WIDTH
 ORIENT_TILE_HEIGHT = 32   # CGS_ORIENT_TILE_HEIGHT
+SNAP_MAX_CAP2 = 64   # CGS_SNAP_MAX_CAP2
+SNAP_TERMS = 10   # CGS_SNAP_TERMS
 REPORT_PANELS = ("render", "ground_truth", "depth", "rend_dir", "rend_alpha")   # panel order of cgs_report_panels
 
 _lib = None

@@ -1858,4 +1858,20 @@ int cgs_sample_support_oriented(int P, const float* points, const int32_t* partn
     return finish("sample_support_oriented", stream_);
 }
 
+int cgs_sample_snap_terms(int P, const float* points, int V, const double* intr, const double* w2c, int height, int width,
+                          const int32_t* d2, int cap2, const double* dist_lut, double* terms, int32_t* views,
+                          void* stream_) {
+    if (P < 0 || V < 0 || cap2 < 1 || cap2 > CGS_SNAP_MAX_CAP2)   // the kernel stages cap2 + 1 table entries in LDS
+        return reject("cgs_sample_snap_terms: invalid argument (P=%d, V=%d, cap2=%d; cap2 lies in [1, %d])", P, V, cap2,
+                      CGS_SNAP_MAX_CAP2);
+    if (!edt_size_ok(height, width))   // d2 is a cgs_edt_squared transform
+        return reject("cgs_sample_snap_terms: invalid argument (height=%d, width=%d; sizes lie in [1, %d])", height, width,
+                      CGS_EDT_MAX_SIZE);
+    if (!intr || !w2c || !d2 || !dist_lut || (P > 0 && (!points || !terms || !views)))
+        return reject("cgs_sample_snap_terms: invalid argument (NULL pointer; P=%d, V=%d)", P, V);
+    if (P == 0 || V == 0) return CGS_OK;   // nothing to add
+    launch_sample_snap_terms((hipStream_t)stream_, P, points, V, intr, w2c, height, width, d2, cap2, dist_lut, terms, views);
+    return finish("sample_snap_terms", stream_);
+}
+
 }  // extern "C"

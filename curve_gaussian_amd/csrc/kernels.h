@@ -265,4 +265,9 @@ void launch_oriented_near(hipStream_t s, int V, int height, int width, const uin
 void launch_sample_support_oriented(hipStream_t s, int P, const float* points, const int* partner, int V, const double* intr,
                                     const double* w2c, int height, int width, const uint8_t* near, int spread, int* tally);
 
+// edge_snap.hip
+void launch_sample_snap_terms(hipStream_t s, int P, const float* points, int V, const double* intr, const double* w2c,
+                              int height, int width, const int* d2, int cap2, const double* dist_lut, double* terms,
+                              int* views);
+
 }  // namespace cgs

@@ -1,7 +1,8 @@
 // The pinhole projection of a world point into a camera, shared by every kernel that must agree on which points a view
 // keeps (novel_view.hip: cgs_project_points / cgs_render_points; edge_score.hip: cgs_point_mask; edge_seed.hip:
 // cgs_voxel_votes, cgs_ray_claims and cgs_ray_wins -- k_voxel_votes, k_ray_claims, k_ray_wins through seed_walk;
-// edge_support.hip: cgs_edge_support; edge_trim.hip: cgs_sample_support; edge_orient.hip: cgs_sample_support_oriented).
+// edge_support.hip: cgs_edge_support; edge_trim.hip: cgs_sample_support; edge_orient.hip: cgs_sample_support_oriented;
+// edge_snap.hip: cgs_sample_snap_terms).
 //
 // Exact, the reference's operation order (eval_ABC.py project_points_to_camera :66-81): X float32 widened to float64,
 // c = R X + T with every row ((r0*X + r1*Y) + r2*Z) + t, dropped if c2 <= 0 (a NaN depth is dropped too: it fails the

@@ -22,8 +22,12 @@ the trimmed pieces with ``--trim``, of the edges of ``parametric_edges.json`` wi
 another are rejoined at their junctions (``ops.edge_join``; its docstring freezes the rule and states the limits: 3D only,
 hosts of T-junctions are not split, an end joins at most one thing, UNTUNED defaults) -- of the last product of the chain:
 the deduped edges with ``--dedupe``, else the trimmed pieces with ``--trim``, else the edges of ``parametric_edges.json``:
-``parametric_edges_joined.json`` and ``edge_graph.json``.  ``parametric_edges.json`` is never written, and no option
-rewrites another option's files."""
+``parametric_edges_joined.json`` and ``edge_graph.json``.  With ``--snap`` the edges are first MOVED onto the detected edges
+(``ops.edge_snap``; its docstring freezes the rule and states the limits: no depth, a sample within the capture radius of
+the wrong edge is pulled to it, not a filter, UNTUNED defaults): ``parametric_edges_snapped.json`` and ``edge_snap.json``, one
+record per edge -- and the check and every later step then start from the snapped edges, their files naming
+``parametric_edges_snapped.json`` as "input".  ``parametric_edges.json`` is never written, and no option rewrites another
+option's files."""
 import argparse
 import json
 import logging
@@ -35,6 +39,7 @@ import numpy as np
 from ..ops import edge_dedupe as ED
 from ..ops import edge_join as EJ
 from ..ops import edge_orient as OR
+from ..ops import edge_snap as SN
 from ..ops import edge_support as SP
 from ..ops import edge_trim as ET
 from .para_edge import EDGE_MAX_THRESHOLD, EDGE_VISIBILITY_FRAMES_RATIO
@@ -51,6 +56,9 @@ DEDUPE_FILE = "edge_dedupe.json"
 DEDUPED_FILE = "parametric_edges_deduped.json"
 GRAPH_FILE = "edge_graph.json"
 JOINED_FILE = "parametric_edges_joined.json"
+SNAP_FILE = "edge_snap.json"
+SNAPPED_FILE = "parametric_edges_snapped.json"
+EDGES_FILE = "parametric_edges.json"
 
 
 def filter_edge_dict(edge_dict, kept):
@@ -171,9 +179,21 @@ def write_join(model_dir, edge_dict, result, extra=None):
     return out
 
 
+def write_snap(model_dir, result, extra=None):
+    """``<model_dir>/edge_snap.json`` = {"input": "parametric_edges.json", "edges": the records of ``snap_edges``, "total",
+    "moved", "settings", **extra} and ``<model_dir>/parametric_edges_snapped.json``, the snapped edges.  Returns the first
+    dict."""
+    out = {**(extra or {}), "input": EDGES_FILE, "edges": [dict(r) for r in result["edges"]], "total": len(result["edges"]),
+           "moved": int(np.count_nonzero(result["moved"])), "settings": dict(result["settings"])}
+    write_score(os.path.join(model_dir, SNAP_FILE), out)
+    with open(os.path.join(model_dir, SNAPPED_FILE), "w") as f:
+        json.dump(result["edge_dict"], f)
+    return out
+
+
 def score_scan(base_dir, dataset_dir, scan, layout="emap", detector="DexiNed", undistort=False, write_filtered=False,
                device=None, backend="gpu", resolution=-1, trim_options=None, dedupe_options=None, join_options=None,
-               **options):
+               snap_options=None, **options):
     """Checks ``<base_dir>/<scan>/parametric_edges.json`` against the ``detector`` edge maps of ``<dataset_dir>/<scan>`` and
     writes ``<base_dir>/<scan>/edge_support.json`` (``write_support``).  ``layout``, ``undistort`` and ``resolution`` (of the
     images) as ``reprojection.score_scan``, the same camera loaders; ``options`` go to ``ops.edge_support.edge_support``
@@ -185,12 +205,17 @@ def score_scan(base_dir, dataset_dir, scan, layout="emap", detector="DexiNed", u
     ``write_dedupe`` then adds its two files, and "input" there names the file whose edges went in.  ``join_options`` (a
     dict, possibly empty; None: no joining) go to ``ops.edge_join.join_edges`` on the last product of the chain -- the
     deduped edges, else the trimmed pieces, else the edges of the prediction -- with the check's sampling resolution unless
-    they name their own: ``write_join`` then adds its two files, "input" again the file whose edges went in.  Returns the dict of ``write_support``, with the ones of ``write_trim``, ``write_dedupe`` and ``write_join`` under "trim", "dedupe" and "join"
-    when there are any, or None -- after reporting it -- for a scan without a prediction."""
+    they name their own: ``write_join`` then adds its two files, "input" again the file whose edges went in.
+    ``snap_options`` (a dict, possibly empty; None: no snapping) go to ``ops.edge_snap.snap_edges`` on the same cameras and
+    maps, FIRST, with the check's sampling resolution, edge threshold and ``thin`` unless they name their own: ``write_snap``
+    adds its two files, and the check and every later step start from the snapped edges -- ``edge_support.json`` and
+    ``edge_trim.json`` then record "input": ``parametric_edges_snapped.json``, and so do the later files where they would have
+    named ``parametric_edges.json``.  Returns the dict of ``write_support``, with the ones of ``write_trim``, ``write_dedupe`` and ``write_join`` under "trim", "dedupe" and "join"
+    when there are any (and the one of ``write_snap`` under "snap"), or None -- after reporting it -- for a scan without a prediction."""
     SP._check_backend(backend)
     if layout not in LAYOUTS:
         raise ValueError(f"unknown layout {layout!r}: expected one of {LAYOUTS}")
-    path = os.path.join(base_dir, scan, "parametric_edges.json")
+    path = os.path.join(base_dir, scan, EDGES_FILE)
     if not os.path.exists(path):
         log.info(f"Invalid prediction at {scan}")
         return None
@@ -205,51 +230,76 @@ def score_scan(base_dir, dataset_dir, scan, layout="emap", detector="DexiNed", u
         cams, maps = colmap_scan_cameras(scan_dir, detector, undistort, backend, resolution)
     if "sample_resolution" in options:
         options["resolution"] = options.pop("sample_resolution")
+    source, extra = EDGES_FILE, {"scan": scan}
+    if snap_options is not None:   # first: everything below starts from the snapped edges
+        shared = {k: options[k] for k in ("resolution", "edge_threshold", "thin") if k in options}
+        snap = SN.snap_edges(edge_dict, cams, maps, detector, device=device, backend=backend, **{**shared, **snap_options})
+        snap["settings"].update({"layout": layout, "undistort": bool(undistort)})
+        snapped = write_snap(os.path.join(base_dir, scan), snap, extra={"scan": scan})
+        edge_dict, source, extra = snap["edge_dict"], SNAPPED_FILE, {"scan": scan, "input": SNAPPED_FILE}
     res = SP.edge_support(edge_dict, cams, maps, detector, device=device, backend=backend, **options)
     res["settings"].update({"layout": layout, "undistort": bool(undistort)})
-    out = write_support(os.path.join(base_dir, scan), edge_dict, res, write_filtered, extra={"scan": scan})
+    out = write_support(os.path.join(base_dir, scan), edge_dict, res, write_filtered, extra=extra)
+    if snap_options is not None:
+        out["snap"] = snapped
     if trim_options is not None:
         shared = {k: options[k] for k in ("resolution", "edge_threshold", "thin") if k in options}
         trim = ET.trim_edges(edge_dict, cams, maps, detector, device=device, backend=backend, **{**shared, **trim_options})
         trim["settings"].update({"layout": layout, "undistort": bool(undistort)})
-        out["trim"] = write_trim(os.path.join(base_dir, scan), edge_dict, trim, extra={"scan": scan})
+        out["trim"] = write_trim(os.path.join(base_dir, scan), edge_dict, trim, extra=extra)
     if dedupe_options is not None:
-        given, name = (trim["edge_dict"], TRIMMED_FILE) if trim_options is not None else (edge_dict, "parametric_edges.json")
+        given, name = (trim["edge_dict"], TRIMMED_FILE) if trim_options is not None else (edge_dict, source)
         shared = {k: options[k] for k in ("resolution",) if k in options}
         res = ED.dedupe_edges(given, device=device, backend=backend, **{**shared, **dedupe_options})
         out["dedupe"] = write_dedupe(os.path.join(base_dir, scan), given, res, extra={"scan": scan, "input": name})
     if join_options is not None:
         given, name = ((res["edge_dict"], DEDUPED_FILE) if dedupe_options is not None else
-                       (trim["edge_dict"], TRIMMED_FILE) if trim_options is not None else (edge_dict, "parametric_edges.json"))
+                       (trim["edge_dict"], TRIMMED_FILE) if trim_options is not None else (edge_dict, source))
         shared = {k: options[k] for k in ("resolution",) if k in options}
         joined = EJ.join_edges(given, device=device, backend=backend, **{**shared, **join_options})
         out["join"] = write_join(os.path.join(base_dir, scan), given, joined, extra={"scan": scan, "input": name})
     return out
 
 
-def support_scene(model_path, edge_dict, cameras, edge_maps, detector, **options):
+def snap_scene(model_path, edge_dict, cameras, edge_maps, detector, **options):
+    """The export's ``snap``: every edge of ``edge_dict`` moved onto the detected edges of the given cameras (as
+    ``support_scene`` takes them; ``ops.edge_snap.snap_edges``).  Writes ``edge_snap.json`` and
+    ``parametric_edges_snapped.json`` into ``model_path``, prints how many edges moved, and returns (the snapped dict, the
+    ``snap_edges`` result)."""
+    if edge_maps is None:
+        cameras, edge_maps = scene_cameras(cameras)
+    res = SN.snap_edges(edge_dict, cameras, edge_maps, detector, **options)
+    os.makedirs(model_path, exist_ok=True)
+    out = write_snap(model_path, res)
+    print("snapped: ", out["moved"], "of", out["total"], "edges moved")
+    return res["edge_dict"], res
+
+
+def support_scene(model_path, edge_dict, cameras, edge_maps, detector, input_file=None, **options):
     """The export's ``support_checking``: ``edge_dict`` against the given cameras (``NovelViewCamera`` s and uint8 maps, or a
     Scene's ``EdgeCamera`` s when ``edge_maps`` is None: ``reprojection.scene_cameras``).  Writes ``edge_support.json`` and
     ``parametric_edges_supported.json`` into ``model_path``, prints the counts before and after, and returns
-    (the filtered dict, the ``edge_support`` result)."""
+    (the filtered dict, the ``edge_support`` result).  ``input_file``: when the edges did not come from
+    ``parametric_edges.json``, the file they came from, recorded as "input"."""
     if edge_maps is None:
         cameras, edge_maps = scene_cameras(cameras)
     res = SP.edge_support(edge_dict, cameras, edge_maps, detector, **options)
     os.makedirs(model_path, exist_ok=True)
-    out = write_support(model_path, edge_dict, res, write_filtered=True)
+    out = write_support(model_path, edge_dict, res, write_filtered=True, extra={"input": input_file} if input_file else None)
     print("before support checking: ", out["total"], "after support checking: ", out["kept"])
     return filter_edge_dict(edge_dict, res["kept"]), res
 
 
-def trim_scene(model_path, edge_dict, cameras, edge_maps, detector, **options):
+def trim_scene(model_path, edge_dict, cameras, edge_maps, detector, input_file=None, **options):
     """The export's ``trim``: every edge of ``edge_dict`` cut down to its supported spans in the given cameras (as
     ``support_scene`` takes them).  Writes ``edge_trim.json`` and ``parametric_edges_trimmed.json`` into ``model_path``, prints
-    the counts before and after, and returns (the trimmed dict, the ``trim_edges`` result)."""
+    the counts before and after, and returns (the trimmed dict, the ``trim_edges`` result).  ``input_file`` as
+    ``support_scene`` takes it."""
     if edge_maps is None:
         cameras, edge_maps = scene_cameras(cameras)
     res = ET.trim_edges(edge_dict, cameras, edge_maps, detector, **options)
     os.makedirs(model_path, exist_ok=True)
-    out = write_trim(model_path, edge_dict, res)
+    out = write_trim(model_path, edge_dict, res, extra={"input": input_file} if input_file else None)
     print("before trimming: ", out["total"], "edges, after trimming: ", out["pieces"], "pieces")
     return res["edge_dict"], res
 
@@ -282,6 +332,8 @@ def join_scene(model_path, edge_dict, input_file="parametric_edges.json", **opti
 # ------------------------------------------------------------------------------------------------ command line
 def scan_line(scan, out):
     line = f"{scan}: views {out['settings']['views']}, edges {out['total']}, kept {out['kept']}"
+    if "snap" in out:
+        line += f"; snapped {out['snap']['moved']} of {out['snap']['total']} edges first"
     if "trim" in out:
         line += f"; trimmed to {out['trim']['pieces']} pieces, {out['trim']['kept_samples']} of {out['trim']['samples']} samples"
     if "dedupe" in out:
@@ -315,6 +367,14 @@ def parser():
     ap.add_argument("--write_filtered", action="store_true", help=f"also write {FILTERED_FILE} with the kept edges")
     ap.add_argument("--backend", choices=SP.SUPPORT_BACKENDS, default="gpu")
     ap.add_argument("--thin", action="store_true", help="thin the detected masks first (a thick detector response; untuned)")
+    ap.add_argument("--snap", action="store_true",
+                    help=f"FIRST move every edge onto the detected edges: {SNAPPED_FILE} and {SNAP_FILE}; the check and every "
+                         f"later step start from the snapped edges (untuned; no depth; not a filter)")
+    ap.add_argument("--snap_capture", type=float, default=SN.CAPTURE_PX,
+                    help="snapping: pixel distance to a detected edge within which a view pulls a sample, 1 to 8 (untuned)")
+    ap.add_argument("--snap_iterations", type=int, default=SN.ITERATIONS, help="snapping: steps and refits (untuned)")
+    ap.add_argument("--snap_min_constrained", type=float, default=SN.MIN_CONSTRAINED,
+                    help="snapping: share of an edge's samples that must be constrained for it to take part (untuned)")
     ap.add_argument("--trim", action="store_true",
                     help=f"also cut EVERY edge down to its supported spans: {TRIMMED_FILE} and {TRIM_FILE} (untuned; no depth)")
     ap.add_argument("--trim_tolerance", type=float, default=ET.TOLERANCE_PX,
@@ -366,13 +426,15 @@ def main(argv=None):
     dedupe = {"tolerance": args.dedupe_tolerance, "cos_min": args.dedupe_cos_min, "min_run": args.dedupe_min_run,
               "min_span": args.dedupe_min_span} if args.dedupe else None
     join = {"tolerance": args.join_tolerance, "reach": args.join_reach} if args.join else None
+    snap = {"capture_px": args.snap_capture, "iterations": args.snap_iterations, "min_constrained": args.snap_min_constrained,
+            "frames_ratio": args.frames_ratio} if args.snap else None
     for scan in dataset_scans(args.dataset_dir, args.layout, args.scans):
         out = score_scan(args.base_dir, args.dataset_dir, scan, args.layout, args.detector, args.undistort,
                          args.write_filtered, backend=args.backend, tolerances_px=args.tolerances,
                          keep_tolerance_px=args.keep_tolerance, min_visible=args.min_visible, min_near=args.min_near,
                          frames_ratio=args.frames_ratio, sample_resolution=args.sample_resolution,
                          edge_threshold=args.edge_threshold, trim_options=trim, dedupe_options=dedupe,
-                         join_options=join,
+                         join_options=join, **({"snap_options": snap} if snap is not None else {}),
                          **({"thin": True} if args.thin else {}))
         if out is None:
             print(f"Invalid prediction at {scan}")

@@ -274,7 +274,8 @@ def extract_curves(gaussians, merge_endpoints=False, distance_threshold=0.015):
 def write_parametric_edges(gaussians, model_path, merge_endpoints=False, distance_threshold=0.015,
                            visible_checking=False, scan_dir=None, detector="DexiNed", support_checking=False,
                            support_options=None, cameras=None, edge_maps=None, trim=False, trim_options=None,
-                           dedupe=False, dedupe_options=None, join=False, join_options=None):
+                           dedupe=False, dedupe_options=None, join=False, join_options=None, snap=False,
+                           snap_options=None):
     """Writes parametric_edges.json (the evaluation input, train.py:287-293) and edge_points.ply (ASCII, :277-285).
     merge_endpoints / distance_threshold: see extract_curves (the reference's default is merge_endpoints=True).
     visible_checking=True keeps only the edges that `detector`'s edge maps of the scan at `scan_dir` show
@@ -296,7 +297,13 @@ def write_parametric_edges(gaussians, model_path, merge_endpoints=False, distanc
     at their junctions in 3D -- of the deduped edges after dedupe=True, else of the trimmed pieces after trim=True, else of
     the written edges -- and writes edge_graph.json and parametric_edges_joined.json, again next to files that stay as they
     are (edge_extraction.support.join_scene; `join_options` go to ops.edge_join.join_edges, whose defaults are untuned).
-    It needs no cameras on its own."""
+    It needs no cameras on its own.
+    snap=True (off by default; the reference has no counterpart) FIRST moves every written edge onto the detected edges of
+    the same `cameras` and writes edge_snap.json and parametric_edges_snapped.json next to files that stay as they are
+    (edge_extraction.support.snap_scene; `snap_options` go to ops.edge_snap.snap_edges, whose defaults are untuned); the
+    support check, the trimming, the deduping and the joining then start from the snapped edges, and their files record
+    "input": parametric_edges_snapped.json where they would have named parametric_edges.json.  The returned dict is the
+    written one, not the snapped one."""
     if visible_checking and scan_dir is None:
         raise ValueError("write_parametric_edges(visible_checking=True) needs scan_dir, the scan holding "
                          "meta_data.json and the edge maps")
@@ -304,26 +311,32 @@ def write_parametric_edges(gaussians, model_path, merge_endpoints=False, distanc
         raise ValueError("write_parametric_edges(support_checking=True) needs cameras, the views to check the edges in")
     if trim and cameras is None:
         raise ValueError("write_parametric_edges(trim=True) needs cameras, the views to trim the edges in")
+    if snap and cameras is None:
+        raise ValueError("write_parametric_edges(snap=True) needs cameras, the views to snap the edges in")
     from ..edge_extraction.para_edge import get_parametric_edge
     merged = extract_curves(gaussians, merge_endpoints, distance_threshold)
     pts, edge_dict = get_parametric_edge(visible_checking, merged, scan_dir, detector)
     write_edge_files(model_path, edge_dict, pts)
+    written, source, named = edge_dict, "parametric_edges.json", {}
+    if snap:
+        from ..edge_extraction.support import SNAPPED_FILE, snap_scene
+        edge_dict, _ = snap_scene(model_path, edge_dict, cameras, edge_maps, detector, **(snap_options or {}))
+        source, named = SNAPPED_FILE, {"input_file": SNAPPED_FILE}
     if support_checking:
         from ..edge_extraction.support import support_scene
-        support_scene(model_path, edge_dict, cameras, edge_maps, detector, **(support_options or {}))
+        support_scene(model_path, edge_dict, cameras, edge_maps, detector, **named, **(support_options or {}))
     if trim:
         from ..edge_extraction.support import trim_scene
-        trimmed, _ = trim_scene(model_path, edge_dict, cameras, edge_maps, detector, **(trim_options or {}))
+        trimmed, _ = trim_scene(model_path, edge_dict, cameras, edge_maps, detector, **named, **(trim_options or {}))
     if dedupe:
         from ..edge_extraction.support import TRIMMED_FILE, dedupe_scene
         deduped, _ = dedupe_scene(model_path, trimmed if trim else edge_dict,
-                                  input_file=TRIMMED_FILE if trim else "parametric_edges.json", **(dedupe_options or {}))
+                                  input_file=TRIMMED_FILE if trim else source, **(dedupe_options or {}))
     if join:
         from ..edge_extraction.support import DEDUPED_FILE, TRIMMED_FILE, join_scene
-        given, name = ((deduped, DEDUPED_FILE) if dedupe else (trimmed, TRIMMED_FILE) if trim else
-                       (edge_dict, "parametric_edges.json"))
+        given, name = ((deduped, DEDUPED_FILE) if dedupe else (trimmed, TRIMMED_FILE) if trim else (edge_dict, source))
         join_scene(model_path, given, input_file=name, **(join_options or {}))
-    return edge_dict, pts
+    return written, pts
 
 
 def write_edge_files(model_path, edge_dict, pts):

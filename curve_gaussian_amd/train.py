@@ -366,6 +366,16 @@ def build_parser():
                    help="after the export, score parametric_edges.json in 2D against the edge maps of the train cameras and, "
                         "separately, of the test cameras (the held-out ones under --eval): reprojection_score.json in the "
                         "model directory")
+    p.add_argument("--snap_edges", action="store_true",
+                   help="after the export, FIRST move every edge of parametric_edges.json onto the detected edges of the "
+                        "train cameras' edge maps: edge_snap.json and parametric_edges_snapped.json in the model directory; "
+                        "--support_check, --trim_edges, --dedupe_edges and --join_edges then start from the snapped edges; "
+                        "parametric_edges.json stays as it is (untuned defaults; no depth; not a filter)")
+    p.add_argument("--snap_capture", type=float, default=None,
+                   help="snapping: pixel distance to a detected edge within which a view pulls a sample, 1 to 8")
+    p.add_argument("--snap_iterations", type=int, default=None, help="snapping: steps and refits")
+    p.add_argument("--snap_min_constrained", type=float, default=None,
+                   help="snapping: share of an edge's samples that must be constrained for it to take part")
     p.add_argument("--support_check", action="store_true",
                    help="after the export, check every edge of parametric_edges.json along its length against the edge "
                         "maps of the train cameras: edge_support.json and parametric_edges_supported.json in the model "
@@ -428,6 +438,15 @@ def support_options(args):
     if args.support_tol_px is not None:
         opts["tolerances_px"] = (args.support_tol_px,)
         opts["keep_tolerance_px"] = args.support_tol_px
+    if args.thin_edge_maps:
+        opts["thin"] = True
+    return opts
+
+
+def snap_options(args):
+    """The options of ops.edge_snap.snap_edges that the command line sets; the rest keep their defaults."""
+    opts = {k: v for k, v in (("capture_px", args.snap_capture), ("iterations", args.snap_iterations),
+                              ("min_constrained", args.snap_min_constrained)) if v is not None}
     if args.thin_edge_maps:
         opts["thin"] = True
     return opts
@@ -503,26 +522,35 @@ def main(argv=None):
         for split, res in scores.items():
             if res is not None:
                 print(scan_line(split, res["aggregate"]))
-    if args.support_check or args.trim_edges or args.dedupe_edges or args.join_edges:
-        import json
-        from .edge_extraction.support import DEDUPED_FILE, TRIMMED_FILE, dedupe_scene, join_scene, support_scene, trim_scene
-        with open(os.path.join(dataset.model_path, "parametric_edges.json")) as f:
-            edge_dict = json.load(f)
-        if args.support_check:
-            support_scene(dataset.model_path, edge_dict, out["scene"].getTrainCameras(), None, dataset.detector,
-                          **support_options(args))
-        if args.trim_edges:
-            trimmed, _ = trim_scene(dataset.model_path, edge_dict, out["scene"].getTrainCameras(), None, dataset.detector,
-                                    **trim_options(args))
-        if args.dedupe_edges:
-            deduped, _ = dedupe_scene(dataset.model_path, trimmed if args.trim_edges else edge_dict,
-                                      input_file=TRIMMED_FILE if args.trim_edges else "parametric_edges.json",
-                                      **dedupe_options(args))
-        if args.join_edges:
-            given, name = ((deduped, DEDUPED_FILE) if args.dedupe_edges else (trimmed, TRIMMED_FILE) if args.trim_edges else
-                           (edge_dict, "parametric_edges.json"))
-            join_scene(dataset.model_path, given, input_file=name, **join_options(args))
+    if args.snap_edges or args.support_check or args.trim_edges or args.dedupe_edges or args.join_edges:
+        export_checks(args, dataset.model_path, out["scene"].getTrainCameras(), dataset.detector)
     print("\nTraining complete.")
+
+
+def export_checks(args, model_path, cameras, detector, edge_maps=None):
+    """The opt-in steps after the export, on ``<model_path>/parametric_edges.json`` and the train cameras (``edge_maps``
+    None: a Scene's cameras carry their maps): --snap_edges first, then --support_check, --trim_edges, --dedupe_edges and
+    --join_edges, each from the last product of the chain."""
+    import json
+    from .edge_extraction.support import (DEDUPED_FILE, SNAPPED_FILE, TRIMMED_FILE, dedupe_scene, join_scene, snap_scene,
+                                          support_scene, trim_scene)
+    with open(os.path.join(model_path, "parametric_edges.json")) as f:
+        edge_dict = json.load(f)
+    source, named = "parametric_edges.json", {}
+    if args.snap_edges:
+        edge_dict, _ = snap_scene(model_path, edge_dict, cameras, edge_maps, detector, **snap_options(args))
+        source, named = SNAPPED_FILE, {"input_file": SNAPPED_FILE}
+    if args.support_check:
+        support_scene(model_path, edge_dict, cameras, edge_maps, detector, **named, **support_options(args))
+    if args.trim_edges:
+        trimmed, _ = trim_scene(model_path, edge_dict, cameras, edge_maps, detector, **named, **trim_options(args))
+    if args.dedupe_edges:
+        deduped, _ = dedupe_scene(model_path, trimmed if args.trim_edges else edge_dict,
+                                  input_file=TRIMMED_FILE if args.trim_edges else source, **dedupe_options(args))
+    if args.join_edges:
+        given, name = ((deduped, DEDUPED_FILE) if args.dedupe_edges else (trimmed, TRIMMED_FILE) if args.trim_edges else
+                       (edge_dict, source))
+        join_scene(model_path, given, input_file=name, **join_options(args))
 
 
 if __name__ == "__main__":

@@ -1194,6 +1194,46 @@ int cgs_sample_support_oriented(int P, const float* points /*[P,3]*/, const int3
                                 const uint8_t* near /*[V,height,width]*/, int spread, int32_t* tally /*[P,2]*/,
                                 void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Snapping extracted edges onto the detected edges: per SAMPLE, over the views, the 3x3 normal equations of "move me onto
+ * the nearest detected edge in every image" (ops/edge_snap.py solves them per sample on the host and refits each edge's
+ * own control points).  The reference has no counterpart.
+ *
+ * points, intr, w2c and d2 as for cgs_sample_support, SEEN the same device function.  cap2 = floor(capture_px^2) lies in
+ * [1, CGS_SNAP_MAX_CAP2]; dist_lut is float64 [cap2 + 1], device, dist_lut[k] = sqrt(k) computed ON THE HOST: the kernel
+ * takes no square root.  terms is float64 [P, CGS_SNAP_TERMS], device, a row = (Axx, Axy, Axz, Ayy, Ayz, Azz, bx, by, bz,
+ * rr); views is int32 [P], device.  The rule, frozen -- float64, one rounded operation at a time in the written order,
+ * nothing contracted into an FMA, IEEE division; R = w2c's rotation (R_jk = w2c[4 j + k]), and for a view that sees the
+ * sample (c0, c1, c2), x = c0 / c2, y = c1 / c2, u and v are the values of the projection:
+ *   a = u - 0.5, b = v - 0.5, j0 = floor(a), i0 = floor(b)
+ *   the view is SKIPPED unless 0 <= j0, j0 + 1 <= width - 1, 0 <= i0, i0 + 1 <= height - 1   (a plane under 2 x 2: never)
+ *   k00, k01, k10, k11 = d2[v][i0][j0], d2[v][i0][j0 + 1], d2[v][i0 + 1][j0], d2[v][i0 + 1][j0 + 1]
+ *   the view is SKIPPED unless 0 <= k <= cap2 for all four    (CGS_EDT_INF included; compared BEFORE dist_lut is indexed)
+ *   d00 .. d11 = dist_lut[k00] .. dist_lut[k11],  fa = a - j0, fb = b - i0, ga = 1 - fa, gb = 1 - fb
+ *   r  = gb * (ga * d00 + fa * d01) + fb * (ga * d10 + fa * d11)
+ *   gu = gb * (d01 - d00) + fb * (d11 - d10),  gv = ga * (d10 - d00) + fa * (d11 - d01)
+ *   su = (gu * fx) / c2,  sv = (gv * fy) / c2,  gc = -(su * x + sv * y)
+ *   g_k = (R_0k * su + R_1k * sv) + R_2k * gc                                         for k = x, y, z
+ *   Axx += gx * gx, Axy += gx * gy, Axz += gx * gz, Ayy += gy * gy, Ayz += gy * gz, Azz += gz * gz
+ *   bx += gx * r, by += gy * r, bz += gz * r, rr += r * r, views += 1
+ * r is the bilinear distance to the nearest detected pixel at the sample's image point, in pixels, g its gradient with
+ * respect to the world point.  The entry ADDS: one thread per sample loads its own row and view count first, adds view by
+ * view in view order and stores them -- one owner per row, no atomics -- so a row is the same floating-point sequence
+ * however the views are cut into calls, and so on every launch geometry.  The table is staged in LDS behind the kernel's
+ * one barrier, which every thread reaches.  Offsets are 64-bit.  The caller's stream, no allocation, no clearing, no host
+ * synchronisation.
+ *
+ * Every argument is checked, whether or not there is work: P or V < 0, cap2 outside [1, CGS_SNAP_MAX_CAP2], a size outside
+ * [1, CGS_EDT_MAX_SIZE] and NULL pointers (points, terms and views only when P > 0) are CGS_ERR_INVALID_ARGUMENT, rejected
+ * before anything is launched.  Then P = 0 or V = 0 is a no-op (nothing to add).
+ * ------------------------------------------------------------------------------------------------ */
+#define CGS_SNAP_MAX_CAP2 64
+#define CGS_SNAP_TERMS 10
+int cgs_sample_snap_terms(int P, const float* points /*[P,3]*/, int V, const double* intr /*[V,4]*/,
+                          const double* w2c /*[V,12]*/, int height, int width, const int32_t* d2 /*[V,height,width]*/,
+                          int cap2, const double* dist_lut /*[cap2+1]*/, double* terms /*[P,CGS_SNAP_TERMS]*/,
+                          int32_t* views /*[P]*/, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
