@@ -127,6 +127,9 @@ SIGNATURES = {
     "cgs_oriented_near": (_i, [_i, _i, _i, _vp, _i, _vp, _vp]),
     "cgs_sample_support_oriented": (_i, [_i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _i, _vp, _vp]),
     "cgs_sample_snap_terms": (_i, [_i, _vp, _i, _vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
+    "cgs_mesh_depth": (_i, [_i, _vp, _i, _vp, _vp, _i, _i, _vp, _vp]),
+    "cgs_depth_window_max": (_i, [_i, _i, _i, _i, _vp, _vp, _vp]),
+    "cgs_point_mask_depth": (_i, [_i, _vp, _i, _vp, _vp, _i, _i, _vp, C.c_double, _vp, _vp, _vp, _vp]),
 }
 
 
@@ -181,6 +184,7 @@ ORIENT_TILE_WIDTH = 64   # CGS_ORIENT_TILE_WIDTH
 ORIENT_TILE_HEIGHT = 32   # CGS_ORIENT_TILE_HEIGHT
 SNAP_MAX_CAP2 = 64   # CGS_SNAP_MAX_CAP2
 SNAP_TERMS = 10   # CGS_SNAP_TERMS
+DEPTH_MAX_WINDOW = 4   # CGS_DEPTH_MAX_WINDOW
 REPORT_PANELS = ("render", "ground_truth", "depth", "rend_dir", "rend_alpha")   # panel order of cgs_report_panels
 
 _lib = None

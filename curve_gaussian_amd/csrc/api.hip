@@ -154,7 +154,7 @@ static thread_local int64_t g_last_stats[3] = {0, 0, 0};  // num_rendered, longe
 // node cleared the buffer on the first replay only -- later replays ran on stale histograms / partial sums.  A plain kernel
 // node replays correctly, and hipMemsetAsync is a fill kernel anyway.  The edge-map launchers do use it and are not captured:
 // launch_point_mask and launch_edge_score_reduce (edge_score.hip), launch_edge_trace (edge_detect.hip), launch_thin_masks
-// (edge_thin.hip) and launch_ray_claims (edge_seed.hip); so does cgs_segment_merge_labels below for an empty input.
+// (edge_thin.hip), launch_ray_claims (edge_seed.hip), launch_mesh_depth and launch_point_mask_depth (edge_occlusion.hip); so does cgs_segment_merge_labels below for an empty input.
 __global__ void __launch_bounds__(256) k_zero_words(uint32_t* __restrict__ p, size_t words) {
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < words; i += stride) p[i] = 0u;
@@ -1872,6 +1872,57 @@ int cgs_sample_snap_terms(int P, const float* points, int V, const double* intr,
     if (P == 0 || V == 0) return CGS_OK;   // nothing to add
     launch_sample_snap_terms((hipStream_t)stream_, P, points, V, intr, w2c, height, width, d2, cap2, dist_lut, terms, views);
     return finish("sample_snap_terms", stream_);
+}
+
+int cgs_mesh_depth(int F, const float* tris, int V, const double* intr, const double* w2c, int height, int width,
+                   float* depth, void* stream_) {
+    if (F < 0 || V < 0) return reject("cgs_mesh_depth: invalid argument (F=%d, V=%d)", F, V);
+    if (!edt_size_ok(height, width))
+        return reject("cgs_mesh_depth: invalid argument (height=%d, width=%d; sizes lie in [1, %d])", height, width,
+                      CGS_EDT_MAX_SIZE);
+    if (!intr || !w2c || !depth || (F > 0 && !tris)) return reject("cgs_mesh_depth: invalid argument (NULL pointer; F=%d)", F);
+    if (V == 0) return CGS_OK;   // nothing to write
+    if (launch_mesh_depth((hipStream_t)stream_, F, tris, V, intr, w2c, height, width, depth) != hipSuccess) {
+        set_error("cgs_mesh_depth: filling the depth planes failed");
+        return CGS_ERR_HIP;
+    }
+    return finish("mesh_depth", stream_);
+}
+
+int cgs_depth_window_max(int V, int height, int width, int radius, const float* depth, float* out, void* stream_) {
+    if (V < 0 || !edt_size_ok(height, width))
+        return reject("cgs_depth_window_max: invalid argument (V=%d, height=%d, width=%d; sizes lie in [1, %d])", V, height,
+                      width, CGS_EDT_MAX_SIZE);
+    if (radius < 0 || radius > CGS_DEPTH_MAX_WINDOW)   // the tile's LDS halo
+        return reject("cgs_depth_window_max: invalid argument (radius=%d; the radius lies in [0, %d])", radius,
+                      CGS_DEPTH_MAX_WINDOW);
+    if (!depth || !out) return reject("cgs_depth_window_max: invalid argument (NULL pointer)");
+    const size_t bytes = (size_t)V * (size_t)height * (size_t)width * sizeof(float);
+    const uintptr_t d0 = reinterpret_cast<uintptr_t>(depth), o0 = reinterpret_cast<uintptr_t>(out);
+    if (d0 < o0 + bytes && o0 < d0 + bytes)   // a tile reads its halo from depth while its neighbours write out
+        return reject("cgs_depth_window_max: invalid argument (depth and out overlap)");
+    if (V == 0) return CGS_OK;   // nothing to write
+    launch_depth_window_max((hipStream_t)stream_, V, height, width, radius, depth, out);
+    return finish("depth_window_max", stream_);
+}
+
+int cgs_point_mask_depth(int P, const float* points, int V, const double* intr, const double* w2c, int height, int width,
+                         const float* depth, double slack, uint8_t* mask_out, int* kept, int* hidden, void* stream_) {
+    if (P < 0 || V < 0) return reject("cgs_point_mask_depth: invalid argument (P=%d, V=%d)", P, V);
+    if (!edt_size_ok(height, width))
+        return reject("cgs_point_mask_depth: invalid argument (height=%d, width=%d; sizes lie in [1, %d])", height, width,
+                      CGS_EDT_MAX_SIZE);
+    if (!(slack >= 0.0) || std::isinf(slack))
+        return reject("cgs_point_mask_depth: invalid argument (slack=%g; the slack is finite and >= 0)", slack);
+    if (!intr || !w2c || !depth || !mask_out || (P > 0 && !points))
+        return reject("cgs_point_mask_depth: invalid argument (NULL pointer; P=%d)", P);
+    if (V == 0) return CGS_OK;   // nothing to write
+    if (launch_point_mask_depth((hipStream_t)stream_, P, points, V, intr, w2c, height, width, depth, slack, mask_out, kept,
+                                hidden) != hipSuccess) {
+        set_error("cgs_point_mask_depth: clearing the mask failed");
+        return CGS_ERR_HIP;
+    }
+    return finish("point_mask_depth", stream_);
 }
 
 }  // extern "C"

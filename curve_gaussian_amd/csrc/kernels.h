@@ -270,4 +270,12 @@ void launch_sample_snap_terms(hipStream_t s, int P, const float* points, int V, 
                               int height, int width, const int* d2, int cap2, const double* dist_lut, double* terms,
                               int* views);
 
+// edge_occlusion.hip
+hipError_t launch_mesh_depth(hipStream_t s, int F, const float* tris, int V, const double* intr, const double* w2c,
+                             int height, int width, float* depth);
+void launch_depth_window_max(hipStream_t s, int V, int height, int width, int radius, const float* depth, float* out);
+hipError_t launch_point_mask_depth(hipStream_t s, int P, const float* points, int V, const double* intr, const double* w2c,
+                                   int height, int width, const float* depth, double slack, uint8_t* mask, int* kept,
+                                   int* hidden);
+
 }  // namespace cgs

@@ -10,7 +10,9 @@ when e > edge_threshold with e = 1 - u/255 (DexiNed) or u/255 (PidiNet) -- the c
 ``ops.edge_score.score_masks`` compares the two masks; its docstring freezes the aggregate.
 
 KNOWN LIMIT: there is no depth.  An edge hidden behind a surface still projects into the view, finds no detected pixel
-there and counts against precision and accuracy.
+there and counts against precision and accuracy -- unless the caller has a depth source: with ``occluder`` (a triangle
+mesh) or ``depth_maps`` (``--occluder`` / ``--depth_dir``) the hidden samples are left out (``ops.edge_occlusion``, whose
+docstring freezes the rule and states its limits; UNTUNED defaults).
 
 ``python -m curve_gaussian_amd.edge_extraction.reprojection --base_dir <predictions> --dataset_dir <scans>`` scores every
 scan, writes ``<base_dir>/<scan>/reprojection_score.json`` and prints one line per scan and their mean."""
@@ -24,6 +26,7 @@ import sys
 import numpy as np
 import torch
 
+from ..ops import edge_occlusion as EO
 from ..ops import edge_score as ES
 from ..ops.edge_thin import thin_masks
 from ..ops.view_chunks import check_edge_maps, detected_lut, detected_masks, view_chunks
@@ -49,7 +52,8 @@ def _json_number(x):
 
 
 def score_edges(pred, cameras, edge_maps_u8, detector, tolerances_px=(1, 2, 4), edge_threshold=EDGE_MAX_THRESHOLD,
-                sample_resolution=SAMPLE_RESOLUTION, device=None, backend="gpu", budget_bytes=None, thin=False):
+                sample_resolution=SAMPLE_RESOLUTION, device=None, backend="gpu", budget_bytes=None, thin=False,
+                occluder=None, depth_maps=None, depth_slack=EO.DEPTH_SLACK, depth_window=EO.DEPTH_WINDOW):
     """pred: a ``parametric_edges.json`` path or its dict.  cameras: ``NovelViewCamera`` s (R, T world -> camera; fx, fy, cx,
     cy; size).  edge_maps_u8: one uint8 [H,W] map per camera (a list, or an [V,H,W] array), the stored bytes of the
     detector's maps, each of its camera's size.  Returns {"aggregate": ops.edge_score's aggregate over all views,
@@ -58,16 +62,38 @@ def score_edges(pred, cameras, edge_maps_u8, detector, tolerances_px=(1, 2, 4), 
     (default ops.edge_score.BYTE_BUDGET) of masks and distance transforms at a time.  ``backend``: "gpu" (HIP; ``device``)
     or "host" (numpy).  ``thin``: every chunk's detected masks go through ``ops.edge_thin.thin_masks`` on the same back end
     first (a detector's response several pixels wide makes the recall measure its line width; untuned, limits in
-    ops/edge_thin.py); "settings" then holds "thin": true, and nothing otherwise."""
+    ops/edge_thin.py); "settings" then holds "thin": true, and nothing otherwise.
+
+    Occlusion (``ops.edge_occlusion``; at most one of the two): ``occluder`` -- float32 [F,3,3] triangles or the path of an
+    .obj / .ply mesh -- is rendered into every chunk's depth planes (``mesh_depth``); ``depth_maps`` -- one float [H,W]
+    array of camera z per camera, NaN or <= 0 where there is no measurement (``check_depth_maps``) -- are taken as they
+    are.  Either way the planes go through the window maximum of radius ``depth_window`` and the prediction masks come
+    from ``point_masks_depth`` with ``depth_slack``: a hidden sample marks no pixel.  Every row of "views" then holds
+    "hidden_points" (kept_points counts the seen samples that are not hidden), "settings" holds "occluder" (the path, or
+    true) or "depth_maps": true, and "depth_slack" and "depth_window"; a chunk's working set grows by
+    ``ops.edge_score.DEPTH_BYTES_PER_PIXEL``.  With neither, nothing changes: no key is added."""
     ES._check_backend(backend)
+    if occluder is not None and depth_maps is not None:
+        raise ValueError("score_edges: give an occluder or depth_maps, not both")
+    gated = occluder is not None or depth_maps is not None
     tolerances_px = [float(t) for t in tolerances_px]
     ES.tolerances_squared(tolerances_px)
     lut = detected_lut(detector, edge_threshold)
     cameras, maps = check_edge_maps("score_edges", cameras, edge_maps_u8)
+    if gated:
+        depth_slack = EO._check_slack("score_edges", depth_slack)
+        depth_window = EO._check_window("score_edges", depth_window)
+    if occluder is not None:
+        tris = EO.read_triangle_mesh(occluder) if isinstance(occluder, (str, os.PathLike)) else occluder
+        tris = EO._as_tris(tris)
+    if depth_maps is not None:
+        depth_maps = EO.check_depth_maps(cameras, depth_maps)
     pts = _pred_points(pred, sample_resolution)
     if backend == "gpu":
         device = ES._device_for([], "score_edges", device)
         pts_b = torch.from_numpy(pts).to(device)
+        if occluder is not None:
+            tris = tris.to(device)
     else:
         pts_b = pts
     budget = ES.BYTE_BUDGET if budget_bytes is None else int(budget_bytes)
@@ -75,9 +101,20 @@ def score_edges(pred, cameras, edge_maps_u8, detector, tolerances_px=(1, 2, 4), 
     per_view = {"n_pred": np.zeros(V, np.int64), "n_det": np.zeros(V, np.int64), "pred_hits": np.zeros((V, n_tol), np.int64),
                 "det_hits": np.zeros((V, n_tol), np.int64), "sum_pred_to_det": np.zeros(V, np.float64),
                 "sum_det_to_pred": np.zeros(V, np.float64), "both_nonempty": np.zeros(V, bool)}
-    kept = np.zeros(V, np.int64)
-    for H, W, sel, intr, w2c in view_chunks(cameras, ES.BYTES_PER_PIXEL, budget):
-        pm, k = ES.point_masks(pts_b, intr, w2c, H, W, backend=backend, device=device, return_kept=True)
+    kept, hidden = np.zeros(V, np.int64), np.zeros(V, np.int64)
+    for H, W, sel, intr, w2c in view_chunks(cameras, ES.BYTES_PER_PIXEL + (ES.DEPTH_BYTES_PER_PIXEL if gated else 0), budget):
+        if gated:
+            if occluder is not None:
+                depth = EO.mesh_depth(tris, intr, w2c, H, W, depth_window, backend=backend, device=device)
+            else:
+                depth = EO.depth_window_max(np.stack([depth_maps[v] for v in sel]), depth_window, backend=backend,
+                                            device=device)
+            pm, k, hid = EO.point_masks_depth(pts_b, intr, w2c, depth, depth_slack, backend=backend, device=device,
+                                              return_counts=True)
+            hidden[sel] = hid.cpu().numpy()
+            del depth
+        else:
+            pm, k = ES.point_masks(pts_b, intr, w2c, H, W, backend=backend, device=device, return_kept=True)
         det = detected_masks(lut, maps, sel)
         if thin:
             det = thin_masks(det, backend=backend, device=device)
@@ -96,10 +133,18 @@ def score_edges(pred, cameras, edge_maps_u8, detector, tolerances_px=(1, 2, 4), 
                      "accuracy_px": float(per_view["sum_pred_to_det"][v] / per_view["n_pred"][v]) if both else float("nan"),
                      "completeness_px": float(per_view["sum_det_to_pred"][v] / per_view["n_det"][v]) if both else float("nan"),
                      "both_nonempty": both})
+        if gated:
+            rows[-1]["hidden_points"] = int(hidden[v])
     settings = {"detector": detector, "tolerances_px": tolerances_px, "edge_threshold": float(edge_threshold),
                 "sample_resolution": float(sample_resolution), "backend": backend, "points": int(pts.shape[0])}
     if thin:
         settings["thin"] = True
+    if gated:
+        if occluder is not None:
+            settings["occluder"] = os.fspath(occluder) if isinstance(occluder, (str, os.PathLike)) else True
+        else:
+            settings["depth_maps"] = True
+        settings.update({"depth_slack": depth_slack, "depth_window": depth_window})
     return {"aggregate": agg, "views": rows, "settings": settings}
 
 
@@ -141,6 +186,18 @@ def colmap_scan_cameras(scan_dir, detector, undistort=False, backend="gpu", reso
     return scene_cameras(train)
 
 
+def scan_depth_maps(depth_dir, cams):
+    """One array per camera from ``<depth_dir>/<stem of the camera's name>.npy`` (camera z; ``check_depth_maps`` states what
+    an entry may hold).  FileNotFoundError, naming the path, for a missing map."""
+    out = []
+    for c in cams:
+        path = os.path.join(depth_dir, os.path.splitext(os.path.basename(c.name))[0] + ".npy")
+        if not os.path.isfile(path):
+            raise FileNotFoundError(f"no depth map for {c.name}: {path}")
+        out.append(np.load(path))
+    return out
+
+
 def write_score(path, result):
     """The result of score_edges (or a dict of them) as JSON; NaN is written as null."""
     def clean(x):
@@ -158,11 +215,14 @@ def write_score(path, result):
 
 def score_scan(base_dir, dataset_dir, scan, layout="emap", detector="DexiNed", undistort=False, tolerances_px=(1, 2, 4),
                edge_threshold=EDGE_MAX_THRESHOLD, sample_resolution=SAMPLE_RESOLUTION, device=None, backend="gpu",
-               resolution=-1, thin=False):
+               resolution=-1, thin=False, occluder=None, depth_dir=None, depth_slack=EO.DEPTH_SLACK,
+               depth_window=EO.DEPTH_WINDOW):
     """Scores ``<base_dir>/<scan>/parametric_edges.json`` against the ``detector`` edge maps of ``<dataset_dir>/<scan>`` and
     writes ``<base_dir>/<scan>/reprojection_score.json`` = {"scan", "aggregate", "views", "settings"}.  ``layout``: "emap"
     (meta_data.json; cameras and maps through get_edge_maps) or "colmap" (sparse/0, also Replica; through read_colmap, with
-    ``undistort`` and ``resolution`` as there); ``thin`` as ``score_edges``.  Returns the dict, or None -- after reporting it -- for a scan without a
+    ``undistort`` and ``resolution`` as there); ``thin`` as ``score_edges``.  ``occluder``: the name of a mesh file inside the scan directory
+    (``mesh.ply``); ``depth_dir``: the name of a directory inside it that holds one ``<image stem>.npy`` depth map per
+    camera (``scan_depth_maps``); with either, ``depth_slack`` and ``depth_window`` as ``score_edges``.  Returns the dict, or None -- after reporting it -- for a scan without a
     prediction, as the reference's tools skip one."""
     ES._check_backend(backend)
     if layout not in LAYOUTS:
@@ -178,22 +238,37 @@ def score_scan(base_dir, dataset_dir, scan, layout="emap", detector="DexiNed", u
         cams, maps = emap_cameras(scan_dir, detector)
     else:
         cams, maps = colmap_scan_cameras(scan_dir, detector, undistort, backend, resolution)
+    if occluder is not None and depth_dir is not None:
+        raise ValueError("score_scan: give an occluder or a depth_dir, not both")
+    gate = {}
+    if occluder is not None:
+        gate = dict(occluder=os.path.join(scan_dir, occluder), depth_slack=depth_slack, depth_window=depth_window)
+    elif depth_dir is not None:
+        gate = dict(depth_maps=scan_depth_maps(os.path.join(scan_dir, depth_dir), cams), depth_slack=depth_slack,
+                    depth_window=depth_window)
     res = score_edges(path, cams, maps, detector, tolerances_px, edge_threshold, sample_resolution, device, backend,
-                      thin=thin)
+                      thin=thin, **gate)
     res["settings"].update({"layout": layout, "undistort": bool(undistort)})
     out = {"scan": scan, **res}
     write_score(os.path.join(base_dir, scan, SCORE_FILE), out)
     return out
 
 
-def score_scene(model_path, scene, detector, **kw):
+def score_scene(model_path, scene, detector, depth_dir=None, **kw):
     """The driver's ``--reprojection_score``: ``<model_path>/parametric_edges.json`` against the cameras the scene trained
     on and, separately, its test cameras (the held-out ones under ``--eval``; "test" is null when there are none).
-    Writes ``<model_path>/reprojection_score.json`` = {"train": ..., "test": ...} and returns it."""
+    Writes ``<model_path>/reprojection_score.json`` = {"train": ..., "test": ...} and returns it.  ``kw`` go to
+    ``score_edges`` (``occluder``: a mesh's path); ``depth_dir``: a directory of ``<image name>.npy`` depth maps
+    (``scan_depth_maps``) for the cameras of both splits."""
     pred = os.path.join(model_path, "parametric_edges.json")
     out = {}
     for split, cams in (("train", scene.getTrainCameras()), ("test", scene.getTestCameras())):
-        out[split] = score_edges(pred, *scene_cameras(cams), detector, **kw) if len(cams) else None
+        if not len(cams):
+            out[split] = None
+            continue
+        nv_cams, maps = scene_cameras(cams)
+        gate = {} if depth_dir is None else {"depth_maps": scan_depth_maps(depth_dir, nv_cams)}
+        out[split] = score_edges(pred, nv_cams, maps, detector, **gate, **kw)
     write_score(os.path.join(model_path, SCORE_FILE), out)
     return out
 
@@ -243,7 +318,19 @@ def parser():
     ap.add_argument("--undistort", action="store_true", help="colmap layout: resample the edge maps through the lens model")
     ap.add_argument("--backend", choices=ES.SCORE_BACKENDS, default="gpu")
     ap.add_argument("--thin", action="store_true", help="thin the detected masks first (a thick detector response; untuned)")
+    add_depth_arguments(ap)
     return ap
+
+
+def add_depth_arguments(ap):
+    """The depth source of the score (shared with train.py --reprojection_score); without them nothing changes."""
+    ap.add_argument("--occluder", default=None, metavar="FILE",
+                    help="a mesh file inside each scan directory (mesh.ply, .obj): samples hidden behind it are left out")
+    ap.add_argument("--depth_dir", default=None, metavar="DIR",
+                    help="a directory inside each scan holding <image stem>.npy depth maps (camera z) instead of a mesh")
+    ap.add_argument("--depth_slack", type=float, default=EO.DEPTH_SLACK, help="world units behind the surface (untuned)")
+    ap.add_argument("--depth_window", type=int, default=EO.DEPTH_WINDOW,
+                    help="radius of the window maximum over the depth planes (untuned)")
 
 
 def main(argv=None):
@@ -251,7 +338,8 @@ def main(argv=None):
     aggregates = []
     for scan in dataset_scans(args.dataset_dir, args.layout, args.scans):
         res = score_scan(args.base_dir, args.dataset_dir, scan, args.layout, args.detector, args.undistort, args.tolerances,
-                         args.edge_threshold, backend=args.backend, thin=args.thin)
+                         args.edge_threshold, backend=args.backend, thin=args.thin, occluder=args.occluder,
+                         depth_dir=args.depth_dir, depth_slack=args.depth_slack, depth_window=args.depth_window)
         if res is None:
             print(f"Invalid prediction at {scan}")
             continue

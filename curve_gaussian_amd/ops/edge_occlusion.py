@@ -1,0 +1,416 @@
+"""Occlusion for the 2D operators: depth planes from a triangle mesh or from the user, and the prediction mask gated by
+them (cgs_mesh_depth / cgs_depth_window_max / cgs_point_mask_depth, include/curvegs.h; csrc/edge_occlusion.hip).  The
+reference has no counterpart.
+
+  mesh_depth          the mesh rendered into one camera-z plane per view -- a z-buffer, +inf where no triangle covers the
+                      pixel centre -- followed by the window maximum
+  depth_window_max    the maximum over a (2r+1)^2 window clipped to the image: +inf (no surface) wins
+  point_masks_depth   ``ops.edge_score.point_masks`` with the gate: a sample the projection keeps is HIDDEN iff
+                          c2 > float64(depth[v][floor(v_px)][floor(u_px)]) + slack
+                      with c2 its camera-space depth; a hidden sample marks no pixel and counts in ``hidden``
+  check_depth_maps    the user's own depth maps (camera z, one float [H,W] array per camera) made ready: NaN and <= 0
+                      become +inf
+  read_triangle_mesh  float32 [F,3,3] from an .obj or .ply file, without trimesh or open3d
+
+The rules are frozen in include/curvegs.h -- float64, one rounded operation at a time -- and the one occlusion rule is the
+device function ``nv_hidden`` of csrc/point_projection.h.  Two back ends: ``"gpu"``, HIP, and ``"host"``, numpy written
+operation for operation (numpy evaluates one rounded operation per ufunc call), so the two agree BIT FOR BIT, and so do the
+brute-force restatements of tests/edge_occlusion_cases.py.
+
+Why the window: a sample on a visible edge lies somewhere inside its pixel while the plane holds the surface's depth at the
+pixel CENTRE, which on a slanted face differs by far more than any sensible slack.  On a convex solid the depth is a convex
+function of the image point and the sample lies inside the hull of the nine centres around it, so the maximum over them is
+at least the sample's own depth; at a silhouette one of the nine has no surface and the sample is never hidden.
+
+WHAT THIS IS NOT.  No clipping: a triangle with a vertex at or behind the camera plane is dropped whole.  The gate is the
+first consumer of the rule and the only one: the support check, trimming, oriented trimming, snapping and the edge vote do
+NOT take it yet.  Along a CONCAVE edge the surface's depth is a local maximum, so samples of a visible concave edge can be
+hidden by their own faces where the faces are steep; a larger slack trades that against hiding less behind thin parts.
+``DEPTH_WINDOW`` AND ``DEPTH_SLACK`` ARE UNTUNED: only the drawn solids of scene/solid_scan.py have been checked, no real
+scan."""
+import os
+
+import numpy as np
+import torch
+
+from .. import _lib as L
+from . import edge_score as ES
+
+MAX_WINDOW = L.DEPTH_MAX_WINDOW
+DEPTH_WINDOW = 1                 # UNTUNED
+DEPTH_SLACK = 2 * 0.0005         # UNTUNED: 2 x edge_extraction.reprojection.SAMPLE_RESOLUTION, in world units
+
+
+def _check_window(what, window):
+    window = int(window)
+    if not 0 <= window <= MAX_WINDOW:
+        raise ValueError(f"{what}: the window radius must lie in [0, {MAX_WINDOW}] (got {window})")
+    return window
+
+
+def _check_slack(what, slack):
+    slack = float(slack)
+    if not (slack >= 0.0 and np.isfinite(slack)):
+        raise ValueError(f"{what}: the slack must be finite and >= 0 (got {slack})")
+    return slack
+
+
+def _as_tris(tris):
+    """float32 [F,3,3] as a contiguous float32 tensor (on the device it is on)."""
+    t = tris if torch.is_tensor(tris) else torch.from_numpy(np.ascontiguousarray(tris, np.float32))
+    if t.dim() != 3 or tuple(t.shape[1:]) != (3, 3):
+        raise ValueError(f"tris must be [F,3,3] (got {tuple(t.shape)})")
+    return t.detach().to(torch.float32).contiguous()
+
+
+def _as_depth(depth, V, height, width, what):
+    d = depth if torch.is_tensor(depth) else torch.from_numpy(np.ascontiguousarray(depth))
+    if d.dtype != torch.float32 or tuple(d.shape) != (V, height, width):
+        raise ValueError(f"{what}: depth must be float32 [{V},{height},{width}] (got {d.dtype} {tuple(d.shape)})")
+    return d.detach().contiguous()
+
+
+# ------------------------------------------------------------------------------------------------ z-buffer
+def _camera_points_host(P, K, M):
+    """(c2, u, v) of float64 points P [...,3] in one camera (K [4], M [12]): the operation order of cgs_project_points."""
+    X, Y, Z = P[..., 0], P[..., 1], P[..., 2]
+    with np.errstate(all="ignore"):
+        c0 = ((M[0] * X + M[1] * Y) + M[2] * Z) + M[3]
+        c1 = ((M[4] * X + M[5] * Y) + M[6] * Z) + M[7]
+        c2 = ((M[8] * X + M[9] * Y) + M[10] * Z) + M[11]
+        u = K[0] * (c0 / c2) + K[2]
+        v = K[1] * (c1 / c2) + K[3]
+    return c2, u, v
+
+
+def _zbuffer_host(T, K, M, height, width):
+    """One view of cgs_mesh_depth in numpy: T float64 [F,3,3] (widened float32), float32 [height,width]."""
+    plane = np.full((height, width), np.inf, np.float32)
+    if T.shape[0] == 0:
+        return plane
+    z, u, v = _camera_points_host(T, K, M)   # [F,3] each
+    with np.errstate(all="ignore"):
+        ok = (z > 0.0).all(1) & ~np.isnan(u).any(1) & ~np.isnan(v).any(1)
+        area = (u[:, 1] - u[:, 0]) * (v[:, 2] - v[:, 0]) - (v[:, 1] - v[:, 0]) * (u[:, 2] - u[:, 0])
+        ok &= (area != 0.0) & ~np.isnan(area)
+        wd, hd = float(width), float(height)
+        umin, umax = np.minimum(np.minimum(u[:, 0], u[:, 1]), u[:, 2]), np.maximum(np.maximum(u[:, 0], u[:, 1]), u[:, 2])
+        vmin, vmax = np.minimum(np.minimum(v[:, 0], v[:, 1]), v[:, 2]), np.maximum(np.maximum(v[:, 0], v[:, 1]), v[:, 2])
+        jlo = np.minimum(np.maximum(np.ceil(umin - 0.5), 0.0), wd)
+        jhi = np.maximum(np.minimum(np.floor(umax - 0.5), wd - 1.0), -1.0)
+        ilo = np.minimum(np.maximum(np.ceil(vmin - 0.5), 0.0), hd)
+        ihi = np.maximum(np.minimum(np.floor(vmax - 0.5), hd - 1.0), -1.0)
+        ok &= (jlo <= jhi) & (ilo <= ihi)
+    for t in np.nonzero(ok)[0]:
+        j0, j1, i0, i1 = int(jlo[t]), int(jhi[t]), int(ilo[t]), int(ihi[t])
+        px = (np.arange(j0, j1 + 1, dtype=np.float64) + 0.5)[None, :]
+        py = (np.arange(i0, i1 + 1, dtype=np.float64) + 0.5)[:, None]
+        (u0, u1, u2), (v0, v1, v2), (z0, z1, z2), a = u[t], v[t], z[t], area[t]
+        with np.errstate(all="ignore"):
+            e0 = (u2 - u1) * (py - v1) - (v2 - v1) * (px - u1)
+            e1 = (u0 - u2) * (py - v2) - (v0 - v2) * (px - u2)
+            e2 = (u1 - u0) * (py - v0) - (v1 - v0) * (px - u0)
+            covered = ((e0 >= 0.0) & (e1 >= 0.0) & (e2 >= 0.0)) | ((e0 <= 0.0) & (e1 <= 0.0) & (e2 <= 0.0))
+            invz = ((e0 / a) / z0 + (e1 / a) / z1) + (e2 / a) / z2
+            zf = (1.0 / invz).astype(np.float32)
+            store = covered & (zf > 0.0) & np.isfinite(zf)
+        sub = plane[i0:i1 + 1, j0:j1 + 1]
+        np.minimum(sub, np.where(store, zf, np.float32(np.inf)), out=sub)
+    return plane
+
+
+def _window_max_host(depth, radius):
+    """cgs_depth_window_max in numpy on float32 [V,H,W]: a NaN never wins."""
+    d = np.asarray(depth, np.float32)
+    if radius == 0 or d.size == 0:
+        return np.where(d > -np.inf, d, np.float32(-np.inf)).astype(np.float32)
+    for axis in (2, 1):
+        pad = [(0, 0)] * 3
+        pad[axis] = (radius, radius)
+        p = np.pad(d, pad, constant_values=-np.inf)
+        n = d.shape[axis]
+        m = np.full(d.shape, -np.inf, np.float32)
+        for k in range(2 * radius + 1):
+            a = np.take(p, range(k, k + n), axis=axis)
+            m = np.where(a > m, a, m)
+        d = m
+    return d
+
+
+def depth_window_max(depth, radius, backend="gpu", device=None):
+    """float32 [V,H,W] -> float32 [V,H,W]: the maximum over the (2 radius + 1)^2 window clipped to the image, 0 <= radius <=
+    MAX_WINDOW.  ``backend="gpu"``: ``cgs_depth_window_max``, the result stays on the device; ``"host"``: numpy."""
+    ES._check_backend(backend)
+    radius = _check_window("depth_window_max", radius)
+    d = depth if torch.is_tensor(depth) else torch.from_numpy(np.array(depth, order="C"))   # (a copy: may be read-only)
+    if d.dtype != torch.float32 or d.dim() != 3:
+        raise ValueError(f"depth_window_max: depth must be float32 [V,H,W] (got {d.dtype} {tuple(d.shape)})")
+    V, H, W = (int(s) for s in d.shape)
+    if V > 0:
+        ES._check_size("depth_window_max", H, W)
+    if backend == "host":
+        return torch.from_numpy(_window_max_host(ES._host(d), radius))
+    dev = ES._device_for([d], "depth_window_max", device)
+    with L.device_guard(dev):
+        d = d.detach().to(dev).contiguous()
+        out = torch.empty_like(d)
+        if V > 0:
+            rc = L.load().cgs_depth_window_max(V, H, W, radius, L.ptr(d), L.ptr(out), L.raw_stream(dev))
+            L.check(rc, "cgs_depth_window_max")
+    return out
+
+
+def mesh_depth(tris, intrinsics, w2c, height, width, window=DEPTH_WINDOW, backend="gpu", device=None):
+    """float32 [V,height,width]: the camera-z of the nearest triangle at every pixel centre (+inf where there is none), then
+    the window maximum of radius ``window`` (0: the plain z-buffer).  tris float32 [F,3,3] (tensor or array); intrinsics
+    [V,4] and w2c [V,3,4] as ``point_masks``.  ``backend="gpu"``: ``cgs_mesh_depth`` and ``cgs_depth_window_max``, the
+    triangles are uploaded when they are not on a GPU, the result stays on the device; ``"host"``: numpy, a CPU tensor."""
+    ES._check_backend(backend)
+    height, width = ES._check_size("mesh_depth", height, width)
+    window = _check_window("mesh_depth", window)
+    V, K, M = ES._cameras(intrinsics, w2c)
+    t = _as_tris(tris)
+    if backend == "host":
+        T = t.cpu().numpy().astype(np.float64)
+        raw = np.empty((V, height, width), np.float32)
+        for i in range(V):
+            raw[i] = _zbuffer_host(T, K[i], M[i], height, width)
+        return torch.from_numpy(_window_max_host(raw, window) if window else raw)
+    dev = ES._device_for([t], "mesh_depth", device)
+    with L.device_guard(dev):
+        t = t.to(dev)
+        raw = torch.empty((V, height, width), dtype=torch.float32, device=dev)
+        if V > 0:
+            Kd, Md = ES.cameras_on(dev, K, M)
+            rc = L.load().cgs_mesh_depth(int(t.shape[0]), L.ptr(t), V, L.ptr(Kd), L.ptr(Md), height, width, L.ptr(raw),
+                                         L.raw_stream(dev))
+            L.check(rc, "cgs_mesh_depth")
+    return depth_window_max(raw, window, "gpu", dev) if window else raw
+
+
+# ------------------------------------------------------------------------------------------------ the gated mask
+def point_masks_depth(points, intrinsics, w2c, depth, slack=DEPTH_SLACK, backend="gpu", device=None, return_counts=False):
+    """uint8 [V,H,W]: ``point_masks`` of the samples that are not hidden behind ``depth`` (float32 [V,H,W], camera z, +inf =
+    no surface; its size is the views' size).  With return_counts, also (kept, hidden) int32 [V]: the seen samples that are
+    not hidden and those that are; kept + hidden is ``point_masks``'s kept.  ``backend="gpu"``: ``cgs_point_mask_depth``,
+    points and planes are uploaded when they are not on a GPU, the results stay on the device; ``"host"``: numpy."""
+    ES._check_backend(backend)
+    slack = _check_slack("point_masks_depth", slack)
+    V, K, M = ES._cameras(intrinsics, w2c)
+    d = depth if torch.is_tensor(depth) else torch.from_numpy(np.array(depth, order="C"))   # (a copy: may be read-only)
+    if d.dim() != 3:
+        raise ValueError(f"point_masks_depth: depth must be float32 [V,H,W] (got {tuple(d.shape)})")
+    height, width = ES._check_size("point_masks_depth", d.shape[1], d.shape[2])
+    d = _as_depth(d, V, height, width, "point_masks_depth")
+    pts = points if torch.is_tensor(points) else torch.from_numpy(np.ascontiguousarray(points, np.float32).reshape(-1, 3))
+    if pts.dim() != 2 or pts.shape[1] != 3:
+        raise ValueError(f"points must be [P,3] (got {tuple(pts.shape)})")
+    pts = pts.detach().to(torch.float32)
+    if backend == "host":
+        mask = np.zeros((V, height, width), np.uint8)
+        kept, hidden = np.zeros((V,), np.int32), np.zeros((V,), np.int32)
+        P64 = pts.cpu().numpy().astype(np.float64)
+        planes = ES._host(d)
+        for i in range(V):
+            c2, u, v = _camera_points_host(P64, K[i], M[i])
+            with np.errstate(all="ignore"):
+                seen = ~(c2 <= 0.0) & (u >= 0.0) & (u < float(width)) & (v >= 0.0) & (v < float(height))
+            c2, u, v = c2[seen], u[seen], v[seen]
+            row, col = np.floor(v).astype(np.int64), np.floor(u).astype(np.int64)
+            with np.errstate(all="ignore"):
+                hid = c2 > planes[i][row, col].astype(np.float64) + slack
+            mask[i, row[~hid], col[~hid]] = 1
+            kept[i], hidden[i] = np.count_nonzero(~hid), np.count_nonzero(hid)
+        mask = torch.from_numpy(mask)
+        return (mask, torch.from_numpy(kept), torch.from_numpy(hidden)) if return_counts else mask
+    dev = ES._device_for([pts, d], "point_masks_depth", device)
+    with L.device_guard(dev):
+        pts, d = pts.to(dev).contiguous(), d.to(dev)
+        mask = torch.empty((V, height, width), dtype=torch.uint8, device=dev)
+        kept = torch.empty((V,), dtype=torch.int32, device=dev)
+        hidden = torch.empty((V,), dtype=torch.int32, device=dev)
+        if V > 0:
+            Kd, Md = ES.cameras_on(dev, K, M)
+            rc = L.load().cgs_point_mask_depth(int(pts.shape[0]), L.ptr(pts), V, L.ptr(Kd), L.ptr(Md), height, width,
+                                               L.ptr(d), slack, L.ptr(mask), L.ptr(kept), L.ptr(hidden), L.raw_stream(dev))
+            L.check(rc, "cgs_point_mask_depth")
+    return (mask, kept, hidden) if return_counts else mask
+
+
+# ------------------------------------------------------------------------------------------------ the user's depth
+def check_depth_maps(cameras, depth_maps):
+    """One depth map per camera -- a floating-point [H,W] array of camera z, of its camera's size -- as a list of float32
+    arrays in which every entry that is NaN or <= 0 (no measurement) is +inf (no surface: it hides nothing).  ValueError
+    for a wrong count, type or size."""
+    cameras, maps = list(cameras), list(depth_maps)
+    if len(maps) != len(cameras):
+        raise ValueError(f"check_depth_maps: {len(cameras)} cameras and {len(maps)} depth maps")
+    out = []
+    for c, m in zip(cameras, maps):
+        m = ES._host(m)
+        if m.dtype.kind != "f" or m.shape != (c.height, c.width):
+            raise ValueError(f"check_depth_maps: the depth map of {c.name} must be a float [{c.height},{c.width}] array "
+                             f"(got {m.dtype} {m.shape})")
+        m = m.astype(np.float32)
+        with np.errstate(invalid="ignore"):
+            m[~(m > 0.0)] = np.inf
+        out.append(m)
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ mesh files
+def _fan(faces):
+    """Index lists of polygons -> int64 [F,3]: polygon (a, b, c, d, ...) as the fan (a, b, c), (a, c, d), ..."""
+    tris = [(f[0], f[k], f[k + 1]) for f in faces for k in range(1, len(f) - 1)]
+    return np.asarray(tris, np.int64).reshape(-1, 3)
+
+
+def _gather(path, xyz, tri_idx):
+    xyz = np.asarray(xyz, np.float64).reshape(-1, 3)
+    if tri_idx.size and (tri_idx.min() < 0 or tri_idx.max() >= xyz.shape[0]):
+        raise ValueError(f"{path}: a face refers to vertex {int(tri_idx.max() if tri_idx.max() >= xyz.shape[0] else tri_idx.min())}"
+                         f" of {xyz.shape[0]}")
+    return np.ascontiguousarray(xyz[tri_idx].astype(np.float32)).reshape(-1, 3, 3)
+
+
+def _read_obj(path):
+    xyz, faces = [], []
+    with open(path, "r") as f:
+        for n, ln in enumerate(f, 1):
+            tok = ln.split("#", 1)[0].split()
+            if not tok:
+                continue
+            try:
+                if tok[0] == "v":
+                    if len(tok) < 4:
+                        raise ValueError("a vertex needs x y z")
+                    xyz.append([float(t) for t in tok[1:4]])
+                elif tok[0] == "f":
+                    if len(tok) < 4:
+                        raise ValueError("a face needs at least three vertices")
+                    idx = [int(t.split("/")[0]) for t in tok[1:]]   # a, a/b, a/b/c, a//c
+                    if any(i == 0 for i in idx):
+                        raise ValueError("vertex index 0")
+                    # a negative index counts back from the vertices read so far
+                    faces.append([i - 1 if i > 0 else len(xyz) + i for i in idx])
+            except ValueError as e:
+                raise ValueError(f"{path}:{n}: {e}") from None
+    return _gather(path, xyz, _fan(faces))
+
+
+def _read_ply(path):
+    from ..scene.dataset_io import _PLY_TYPES
+    with open(path, "rb") as f:
+        blob = f.read()
+    if b"end_header" not in blob:
+        raise ValueError(f"{path}: not a PLY file (no end_header)")
+    head, body = blob.split(b"end_header", 1)
+    body = body[body.index(b"\n") + 1:] if b"\n" in body else b""
+    lines = head.decode("ascii", "replace").splitlines()
+    if not lines or lines[0].strip() != "ply":
+        raise ValueError(f"{path}: not a PLY file")
+    fmt, elements = None, []   # (name, count, [(property, type, list count type or None)])
+    for ln in lines[1:]:
+        tok = ln.split()
+        if not tok:
+            continue
+        try:
+            if tok[0] == "format":
+                fmt = tok[1]
+            elif tok[0] == "element":
+                elements.append((tok[1], int(tok[2]), []))
+            elif tok[0] == "property":
+                if tok[1] == "list":
+                    elements[-1][2].append((tok[4], _PLY_TYPES[tok[3]], _PLY_TYPES[tok[2]]))
+                else:
+                    elements[-1][2].append((tok[2], _PLY_TYPES[tok[1]], None))
+        except (IndexError, KeyError, ValueError):
+            raise ValueError(f"{path}: bad header line {ln!r}") from None
+    if fmt not in ("ascii", "binary_little_endian"):
+        raise ValueError(f"{path}: unsupported PLY format {fmt} (ascii and binary_little_endian are read)")
+    xyz, faces = None, None
+    text = body.decode("ascii", "replace").split() if fmt == "ascii" else None
+    at = 0   # token index (ascii) or byte offset (binary)
+    try:
+        for name, count, props in elements:
+            rows = []
+            scalar_only = all(lt is None for _, _, lt in props)
+            if fmt != "ascii" and scalar_only:   # a table: one frombuffer
+                dt = np.dtype([(p, "<" + t) for p, t, _ in props])
+                tab = np.frombuffer(body, dtype=dt, count=count, offset=at)
+                at += dt.itemsize * count
+                rows = {p: tab[p] for p, _, _ in props}
+            else:
+                cols = {p: [] for p, _, _ in props}
+                for _ in range(count):
+                    for p, t, lt in props:
+                        if fmt == "ascii":
+                            if lt is None:
+                                cols[p].append(float(text[at]))
+                                at += 1
+                            else:
+                                n = int(text[at])
+                                cols[p].append([int(x) for x in text[at + 1:at + 1 + n]])
+                                if len(cols[p][-1]) != n:
+                                    raise IndexError
+                                at += 1 + n
+                        elif lt is None:
+                            cols[p].append(np.frombuffer(body, "<" + t, 1, at)[0])
+                            at += np.dtype(t).itemsize
+                        else:
+                            n = int(np.frombuffer(body, "<" + lt, 1, at)[0])
+                            at += np.dtype(lt).itemsize
+                            cols[p].append(np.frombuffer(body, "<" + t, n, at).astype(np.int64).tolist())
+                            at += n * np.dtype(t).itemsize
+                rows = cols
+            if name == "vertex":
+                if not all(k in rows for k in "xyz"):
+                    raise ValueError(f"{path}: the vertex element has no x, y, z")
+                for k in "xyz":
+                    if dict((p, t) for p, t, _ in props)[k] not in ("f4", "f8"):
+                        raise ValueError(f"{path}: x, y, z must be float or double")
+                xyz = np.stack([np.asarray(rows[k], np.float64) for k in "xyz"], 1)
+            elif name == "face":
+                key = next((k for k in ("vertex_indices", "vertex_index") if k in rows), None)
+                lt = {p: (t, l) for p, t, l in props}.get(key)
+                if key is None or lt[1] is None or lt[0][0] not in "iu":
+                    raise ValueError(f"{path}: the face element has no integer list vertex_indices / vertex_index")
+                faces = rows[key]
+    except (IndexError, ValueError) as e:
+        if isinstance(e, ValueError) and str(e).startswith(str(path)):
+            raise
+        raise ValueError(f"{path}: the body is shorter than the header says") from None
+    if xyz is None or faces is None:
+        raise ValueError(f"{path}: needs a vertex and a face element")
+    if any(len(f) < 3 for f in faces):
+        raise ValueError(f"{path}: a face needs at least three vertices")
+    return _gather(path, xyz, _fan(faces))
+
+
+def read_triangle_mesh(path):
+    """float32 [F,3,3] of a mesh file.  ``.obj``: ``v`` and ``f`` records (``a``, ``a/b``, ``a/b/c``, ``a//c``; negative
+    indices count back from the last vertex read); ``.ply``: ascii or binary_little_endian, float or double ``x y z``, a
+    face list property ``vertex_indices`` or ``vertex_index`` of any integer types.  Polygons are fan-triangulated.
+    Anything else is a ValueError."""
+    ext = os.path.splitext(str(path))[1].lower()
+    if ext == ".obj":
+        return _read_obj(path)
+    if ext == ".ply":
+        return _read_ply(path)
+    raise ValueError(f"{path}: unknown mesh format {ext!r} (.obj and .ply are read)")
+
+
+def write_triangle_ply(path, tris):
+    """tris [F,3,3] as a binary little-endian PLY of 3 F float vertices and F ``vertex_indices`` faces (no vertex is
+    shared); ``read_triangle_mesh`` returns the same float32 triangles."""
+    t = np.ascontiguousarray(ES._host(tris), "<f4").reshape(-1, 3, 3)
+    F = t.shape[0]
+    head = (f"ply\nformat binary_little_endian 1.0\nelement vertex {3 * F}\nproperty float x\nproperty float y\n"
+            f"property float z\nelement face {F}\nproperty list uchar int vertex_indices\nend_header\n")
+    faces = np.zeros(F, np.dtype([("n", "u1"), ("i", "<i4", (3,))]))
+    faces["n"] = 3
+    faces["i"] = np.arange(3 * F, dtype=np.int32).reshape(F, 3)
+    with open(path, "wb") as f:
+        f.write(head.encode("ascii"))
+        f.write(t.tobytes())
+        f.write(faces.tobytes())

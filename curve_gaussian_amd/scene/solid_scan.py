@@ -1,0 +1,160 @@
+"""Solid synthetic scans with ground truth: a closed triangle mesh, its feature edges as a ``parametric_edges.json`` dict,
+cameras around it and edge maps with the HIDDEN LINES REMOVED -- the first scans of this project in which occlusion exists
+(every drawn scan of tests/*_cases.py is a wireframe with nothing to hide behind).
+
+The maps are drawn by the operators that the score uses: the ground-truth edges sampled as the score samples them
+(``abc.pred_points_and_directions`` at ``reprojection.SAMPLE_RESOLUTION``), gated by ``ops.edge_occlusion.point_masks_depth``
+against ``mesh_depth`` of the solid with the defaults of the score.  Scoring the ground truth with the solid as the
+occluder therefore reproduces the maps exactly, and scoring it without shows what the missing depth costs.  The cameras
+are ``synthetic.fibonacci_cameras`` as a scan in the EMAP layout stores and reads them back (camtoworld = inv(w2c) in the
+file, w2c = inv(camtoworld) on reading), so a scan written by ``write_solid_scan`` scores the same from disk.
+
+Shapes (inside the unit cube, around its centre):
+  box         12 lines
+  l_bracket   an L-shaped prism: concave, 18 lines, one solid hiding part of itself
+  cylinder    a 64-gon side with two caps; the ground truth is its two rims, four cubic quarter arcs each with the usual
+              handle 0.5523 r.  Such an arc leaves the circle by at most 2.7e-4 r, below the sampling resolution; the
+              64-gon's sides lie up to 1.2e-3 r inside the circle, so a rim sample is never behind its own cap.
+
+LIMITS.  The maps hold feature edges only: no silhouette lines of curved surfaces (the cylinder's side draws nothing), no
+detector noise, no line width beyond the pixel a sample falls into.  Along a concave edge (the bracket's inner corner) the
+gate can hide samples of a visible edge behind their own faces (ops/edge_occlusion.py says why); the maps then miss them,
+consistently with the score."""
+import json
+import math
+import os
+from typing import NamedTuple
+
+import numpy as np
+import torch
+
+from .. import synthetic
+from ..ops import edge_occlusion as EO
+from ..ops.view_chunks import camera_arrays
+from .dataset_io import fov2focal
+
+SHAPES = ("box", "l_bracket", "cylinder")
+CYLINDER_SIDES = 64
+ARC_HANDLE = 0.5523
+SAMPLE_RESOLUTION = 0.0005   # edge_extraction.reprojection.SAMPLE_RESOLUTION (that module imports the ops; not imported here)
+
+
+class SolidScan(NamedTuple):
+    tris: np.ndarray        # float32 [F,3,3]
+    edges: dict             # the ground truth: {"lines_end_pts": [[6]], "curves_ctl_pts": [[12]]}
+    synth_cameras: list     # synthetic.SynthCamera s, what dataset_io.write_emap takes
+    cameras: list           # NovelViewCamera s, what score_edges takes
+    maps: np.ndarray        # uint8 [V,H,W], 255 on an edge: PidiNet bytes
+    depth: np.ndarray       # float32 [V,H,W], the plain z-buffer (+inf: no surface)
+    hidden: np.ndarray      # int32 [V]: the ground-truth samples each view hides
+
+
+def _prism(poly, z0, z1):
+    """A polygon [(x, y)] that is star-shaped from its first vertex, extruded from z0 to z1: (triangles, lines).  The caps
+    are fans over the polygon's own vertices, so no side of a triangle ends inside another's (no T-junction)."""
+    n = len(poly)
+    lo = [(x, y, z0) for x, y in poly]
+    hi = [(x, y, z1) for x, y in poly]
+    tris, lines = [], []
+    for k in range(1, n - 1):
+        tris += [(lo[0], lo[k + 1], lo[k]), (hi[0], hi[k], hi[k + 1])]
+    for k in range(n):
+        j = (k + 1) % n
+        tris += [(lo[k], lo[j], hi[j]), (lo[k], hi[j], hi[k])]
+        lines += [lo[k] + lo[j], hi[k] + hi[j], lo[k] + hi[k]]
+    return tris, lines
+
+
+def _ring(cx, cy, r, z):
+    """The circle of radius r around (cx, cy) at height z as four cubic quarter arcs, 12 numbers each."""
+    h = ARC_HANDLE * r
+    out = []
+    for q in range(4):
+        a, b = q * math.pi / 2.0, (q + 1) * math.pi / 2.0
+        p0 = (cx + r * math.cos(a), cy + r * math.sin(a))
+        p3 = (cx + r * math.cos(b), cy + r * math.sin(b))
+        p1 = (p0[0] - h * math.sin(a), p0[1] + h * math.cos(a))
+        p2 = (p3[0] + h * math.sin(b), p3[1] - h * math.cos(b))
+        out.append([c for p in (p0, p1, p2, p3) for c in (p[0], p[1], z)])
+    return out
+
+
+def solid_geometry(shape):
+    """(tris float32 [F,3,3], edge dict) of a shape."""
+    curves = []
+    if shape == "box":
+        tris, lines = _prism([(0.2, 0.25), (0.8, 0.25), (0.8, 0.75), (0.2, 0.75)], 0.3, 0.7)
+    elif shape == "l_bracket":
+        tris, lines = _prism([(0.2, 0.2), (0.8, 0.2), (0.8, 0.45), (0.45, 0.45), (0.45, 0.8), (0.2, 0.8)], 0.3, 0.7)
+    elif shape == "cylinder":
+        r, n = 0.3, CYLINDER_SIDES
+        poly = [(0.5 + r * math.cos(2.0 * math.pi * k / n), 0.5 + r * math.sin(2.0 * math.pi * k / n)) for k in range(n)]
+        tris, lines = _prism(poly, 0.25, 0.75)
+        lines, curves = [], _ring(0.5, 0.5, r, 0.25) + _ring(0.5, 0.5, r, 0.75)
+    else:
+        raise ValueError(f"unknown solid {shape!r}: expected one of {SHAPES}")
+    return (np.asarray(tris, np.float32).reshape(-1, 3, 3),
+            {"lines_end_pts": [list(map(float, ln)) for ln in lines], "curves_ctl_pts": curves})
+
+
+def emap_cameras_of(synth_cams):
+    """NovelViewCamera s of synthetic cameras, formed as ``write_emap`` stores and ``reprojection.emap_cameras`` reads them."""
+    from ..edge_extraction.novel_view import NovelViewCamera
+    out = []
+    for i, c in enumerate(synth_cams):
+        H, W = int(c.image_height), int(c.image_width)
+        stored = np.linalg.inv(c.world_view_transform.detach().cpu().double().numpy().T)   # camtoworld, as written
+        w2c = np.linalg.inv(np.asarray(stored, np.float64))
+        out.append(NovelViewCamera(f"{i}_colors.png", np.ascontiguousarray(w2c[:3, :3]), w2c[:3, 3].copy(),
+                                   float(fov2focal(c.FoVx, W)), float(fov2focal(c.FoVy, H)), W / 2.0, H / 2.0, W, H))
+    return out
+
+
+def solid_scan(shape, n_views, H, W, backend="gpu", device=None, slack=EO.DEPTH_SLACK, window=EO.DEPTH_WINDOW,
+               sample_resolution=SAMPLE_RESOLUTION):
+    """A ``SolidScan`` of ``shape`` seen from ``n_views`` ``synthetic.fibonacci_cameras`` of H x W pixels; ``backend`` as the
+    ops (both give the same bytes)."""
+    from ..edge_extraction.abc import pred_points_and_directions
+    tris, edges = solid_geometry(shape)
+    synth = synthetic.fibonacci_cameras(int(n_views), int(H), int(W))
+    cams = emap_cameras_of(synth)
+    intr, w2c = camera_arrays(cams)
+    pts = np.ascontiguousarray(pred_points_and_directions(edges, sample_resolution).points, np.float32).reshape(-1, 3)
+    raw = EO.mesh_depth(tris, intr, w2c, H, W, window=0, backend=backend, device=device)
+    mask, _, hidden = EO.point_masks_depth(pts, intr, w2c, EO.depth_window_max(raw, window, backend=backend, device=device),
+                                           slack, backend=backend, device=device, return_counts=True)
+    return SolidScan(tris, edges, synth, cams, mask.cpu().numpy() * np.uint8(255), raw.cpu().numpy(), hidden.cpu().numpy())
+
+
+def write_solid_scan(path, scan, depth=False):
+    """The scan in the EMAP layout (``dataset_io.write_emap``, PidiNet maps) plus ``mesh.ply``, ``gt_edges.json`` and, with
+    ``depth``, ``depth/<image stem>.npy`` (the plain z-buffer, float32 camera z, +inf where there is no surface)."""
+    from .dataset_io import write_emap
+    write_emap(path, scan.synth_cameras, [torch.from_numpy(m.astype(np.float32) / 255.0) for m in scan.maps], detector="PidiNet")
+    EO.write_triangle_ply(os.path.join(path, "mesh.ply"), scan.tris)
+    with open(os.path.join(path, "gt_edges.json"), "w") as f:
+        json.dump(scan.edges, f)
+    if depth:
+        os.makedirs(os.path.join(path, "depth"), exist_ok=True)
+        for c, d in zip(scan.cameras, scan.depth):
+            np.save(os.path.join(path, "depth", os.path.splitext(c.name)[0] + ".npy"), d)
+
+
+def main(argv=None):
+    import argparse
+    ap = argparse.ArgumentParser(prog="python -m curve_gaussian_amd.solid_scan",
+                                 description="Write a solid synthetic scan with ground truth and hidden lines removed.")
+    ap.add_argument("shape", choices=SHAPES)
+    ap.add_argument("out_dir", help="the scan directory to write (EMAP layout)")
+    ap.add_argument("--views", type=int, default=24)
+    ap.add_argument("--height", type=int, default=240)
+    ap.add_argument("--width", type=int, default=320)
+    ap.add_argument("--depth", action="store_true", help="also write depth/<image stem>.npy")
+    ap.add_argument("--backend", choices=("gpu", "host"), default="gpu")
+    args = ap.parse_args(argv)
+    scan = solid_scan(args.shape, args.views, args.height, args.width, backend=args.backend)
+    write_solid_scan(args.out_dir, scan, depth=args.depth)
+    print(f"{args.shape}: {len(scan.cameras)} views of {args.width}x{args.height}, {scan.tris.shape[0]} triangles, "
+          f"{len(scan.edges['lines_end_pts'])} lines, {len(scan.edges['curves_ctl_pts'])} curves, "
+          f"{int(scan.hidden.sum())} hidden samples -> {args.out_dir}")
+    return 0

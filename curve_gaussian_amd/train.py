@@ -366,6 +366,8 @@ def build_parser():
                    help="after the export, score parametric_edges.json in 2D against the edge maps of the train cameras and, "
                         "separately, of the test cameras (the held-out ones under --eval): reprojection_score.json in the "
                         "model directory")
+    from .edge_extraction.reprojection import add_depth_arguments
+    add_depth_arguments(p)   # --occluder / --depth_dir (inside --source_path), --depth_slack, --depth_window: for the score
     p.add_argument("--snap_edges", action="store_true",
                    help="after the export, FIRST move every edge of parametric_edges.json onto the detected edges of the "
                         "train cameras' edge maps: edge_snap.json and parametric_edges_snapped.json in the model directory; "
@@ -517,8 +519,15 @@ def main(argv=None):
                    topology_backend=args.topology_backend, report_writer=writer)
     if args.reprojection_score:
         from .edge_extraction.reprojection import scan_line, score_scene
+        gate = {}
+        if args.occluder is not None or args.depth_dir is not None:
+            gate = dict(depth_slack=args.depth_slack, depth_window=args.depth_window)
+            if args.occluder is not None:
+                gate["occluder"] = os.path.join(dataset.source_path, args.occluder)
+            if args.depth_dir is not None:
+                gate["depth_dir"] = os.path.join(dataset.source_path, args.depth_dir)
         scores = score_scene(dataset.model_path, out["scene"], dataset.detector,
-                             **({"thin": True} if args.thin_edge_maps else {}))
+                             **({"thin": True} if args.thin_edge_maps else {}), **gate)
         for split, res in scores.items():
             if res is not None:
                 print(scan_line(split, res["aggregate"]))

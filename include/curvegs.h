@@ -1234,6 +1234,66 @@ int cgs_sample_snap_terms(int P, const float* points /*[P,3]*/, int V, const dou
                           int cap2, const double* dist_lut /*[cap2+1]*/, double* terms /*[P,CGS_SNAP_TERMS]*/,
                           int32_t* views /*[P]*/, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Occlusion for the 2D operators: a triangle mesh rendered into one camera-z plane per view (a z-buffer), the plane widened
+ * by a window maximum, and the prediction mask of cgs_point_mask gated by it (ops/edge_occlusion.py).  The reference has no
+ * counterpart.  intr, w2c as for cgs_point_mask.  Every rule is frozen -- float64, one rounded operation at a time in the
+ * written order, nothing contracted into an FMA, IEEE division -- so that the numpy back end agrees on every bit.
+ *
+ * cgs_mesh_depth: tris is float32 [F,3,3], device (triangle, vertex, xyz); depth is float32 [V,height,width], device.  The
+ * entry fills depth with +inf and then, for every (triangle, view):
+ *   the vertices widened to float64, c = R X + T in the operation order of cgs_project_points; z_k = c2 of vertex k
+ *   the triangle is SKIPPED in the view unless z_k > 0 for all three (NaN included): there is no clipping
+ *   u_k = fx * (c0 / c2) + cx, v_k = fy * (c1 / c2) + cy, the projection's values, with no in-frame test
+ *   the triangle is SKIPPED if any u_k or v_k is NaN
+ *   area = (u1 - u0) * (v2 - v0) - (v1 - v0) * (u2 - u0); the triangle is SKIPPED if area is 0 or NaN
+ *   pixel (j, i) has its centre at (px, py) = (j + 0.5, i + 0.5); the CANDIDATES are jlo <= j <= jhi, ilo <= i <= ihi with
+ *     jlo = min(max(ceil(min(u0, u1, u2) - 0.5), 0), width)        jhi = max(min(floor(max(u0, u1, u2) - 0.5), width - 1), -1)
+ *     ilo = min(max(ceil(min(v0, v1, v2) - 0.5), 0), height)       ihi = max(min(floor(max(v0, v1, v2) - 0.5), height - 1), -1)
+ *     all in float64 (min and max of three taken left to right), converted to int after the clamp: the pixel centres inside
+ *     the vertices' bounding box, its border included, inside the image
+ *   e0 = (u2 - u1) * (py - v1) - (v2 - v1) * (px - u1)       (the directed side opposite vertex 0, at the pixel centre)
+ *   e1 = (u0 - u2) * (py - v2) - (v0 - v2) * (px - u2)
+ *   e2 = (u1 - u0) * (py - v0) - (v1 - v0) * (px - u0)       (area is e2 at vertex 2)
+ *   the pixel is COVERED iff e0, e1, e2 are all >= 0 or all <= 0: both windings, borders inclusive, no fill rule
+ *   w_k = e_k / area,  invz = (w0 / z0 + w1 / z1) + w2 / z2,  z = (float)(1 / invz)           (perspective correct)
+ *   depth[v][i][j] = min(depth[v][i][j], z) if z is a positive finite float; otherwise nothing is stored
+ * The minimum is an integer atomic minimum on the float's bit pattern (non-negative floats order like their bits).  A pixel
+ * on a side shared by two triangles is covered by both, which is harmless under a minimum.  The result does not depend on
+ * the launch geometry or on the order of the triangles.  Limits: a triangle with a vertex at or behind the camera plane is
+ * dropped whole, not clipped; each (triangle, view) costs its bounding box.
+ *
+ * cgs_depth_window_max: out[v][i][j] = the maximum of depth[v][i + di][j + dj] over |di|, |dj| <= radius inside the image,
+ * 0 <= radius <= CGS_DEPTH_MAX_WINDOW.  +inf (no surface) wins: after it a sample is hidden only if EVERY pixel around its
+ * own has a surface in front, which keeps the samples of a silhouette edge.  A NaN never wins (the planes of cgs_mesh_depth
+ * hold none).  Every output word is written.  depth and out must not overlap: a tile reads its halo from depth while its
+ * neighbours write out, so overlapping ranges are rejected.
+ *
+ * cgs_point_mask_depth: cgs_point_mask with the gate.  points, mask_out, kept as there; depth is float32 [V,height,width],
+ * device, camera z, +inf where there is no surface; hidden is int32 [V], device, or NULL.  mask_out, kept and hidden are
+ * cleared first.  A sample is SEEN in a view by the rule of cgs_project_points (the same device function, which here also
+ * returns c2).  A seen sample is HIDDEN iff
+ *   c2 > (double)depth[v][floor(v_px)][floor(u_px)] + slack                      (one float64 addition; slack finite, >= 0)
+ * -- the one occlusion rule, the device function nv_hidden of csrc/point_projection.h.  A seen sample that is not hidden
+ * stores the byte 1 at its pixel and counts in kept[v]; a hidden one stores nothing and counts in hidden[v].  With an
+ * all-+inf plane the outputs are those of cgs_point_mask.
+ *
+ * All three run on the caller's stream with no allocation and no host synchronisation.  Every argument is checked, whether
+ * or not there is work: F, P or V < 0, a size outside [1, CGS_EDT_MAX_SIZE], a radius outside [0, CGS_DEPTH_MAX_WINDOW], a
+ * slack that is negative, NaN or infinite, NULL pointers (tris only when F > 0, points only when P > 0; kept and hidden may
+ * be NULL) and overlapping depth and out are CGS_ERR_INVALID_ARGUMENT, rejected before anything is launched.  Then V = 0 is
+ * a no-op.
+ * ------------------------------------------------------------------------------------------------ */
+#define CGS_DEPTH_MAX_WINDOW 4
+int cgs_mesh_depth(int F, const float* tris /*[F,3,3]*/, int V, const double* intr /*[V,4]*/, const double* w2c /*[V,12]*/,
+                   int height, int width, float* depth /*[V,height,width]*/, void* stream);
+int cgs_depth_window_max(int V, int height, int width, int radius, const float* depth /*[V,height,width]*/,
+                         float* out /*[V,height,width]*/, void* stream);
+int cgs_point_mask_depth(int P, const float* points /*[P,3]*/, int V, const double* intr /*[V,4]*/,
+                         const double* w2c /*[V,12]*/, int height, int width, const float* depth /*[V,height,width]*/,
+                         double slack, uint8_t* mask_out /*[V,height,width]*/, int32_t* kept /*[V]*/,
+                         int32_t* hidden /*[V]*/, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
