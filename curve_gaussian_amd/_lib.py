@@ -130,6 +130,11 @@ SIGNATURES = {
     "cgs_mesh_depth": (_i, [_i, _vp, _i, _vp, _vp, _i, _i, _vp, _vp]),
     "cgs_depth_window_max": (_i, [_i, _i, _i, _i, _vp, _vp, _vp]),
     "cgs_point_mask_depth": (_i, [_i, _vp, _i, _vp, _vp, _i, _i, _vp, C.c_double, _vp, _vp, _vp, _vp]),
+    # the siblings' arguments up to their outputs, then depth, slack, the outputs, hidden, stream
+    "cgs_edge_support_depth": (_i, [_i, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _i, _vp, _vp, C.c_double, _vp, _vp, _vp]),
+    "cgs_sample_support_depth": (_i, [_i, _vp, _i, _vp, _vp, _i, _i, _vp, _i, _vp, _vp, C.c_double, _vp, _vp, _vp]),
+    "cgs_sample_support_oriented_depth": (_i, [_i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _i, _vp, C.c_double, _vp, _vp, _vp]),
+    "cgs_sample_snap_terms_depth": (_i, [_i, _vp, _i, _vp, _vp, _i, _i, _vp, _i, _vp, _vp, C.c_double, _vp, _vp, _vp, _vp]),
 }
 
 

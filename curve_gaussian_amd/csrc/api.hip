@@ -1925,4 +1925,84 @@ int cgs_point_mask_depth(int P, const float* points, int V, const double* intr, 
     return finish("point_mask_depth", stream_);
 }
 
+// ---- the depth-gated siblings of the four per-sample 2D operators (include/curvegs.h).  Each checks what its sibling checks,
+// in its order, plus the gate's arguments as cgs_point_mask_depth checks them: a finite slack >= 0 and a depth pointer.
+static bool slack_ok(double slack) { return slack >= 0.0 && !std::isinf(slack); }   // a NaN fails the comparison
+
+int cgs_edge_support_depth(int E, int P, const float* points, const int32_t* offsets, int V, const double* intr,
+                           const double* w2c, int height, int width, const int32_t* d2, int T, const int32_t* tol2,
+                           const float* depth, double slack, int32_t* counts, int32_t* hidden, void* stream_) {
+    if (E < 0 || P < 0 || V < 0 || T < 1 || T > CGS_EDGE_SUPPORT_MAX_TOL)
+        return reject("cgs_edge_support_depth: invalid argument (E=%d, P=%d, V=%d, T=%d; T lies in [1, %d])", E, P, V, T,
+                      CGS_EDGE_SUPPORT_MAX_TOL);
+    if (!slack_ok(slack))
+        return reject("cgs_edge_support_depth: invalid argument (slack=%g; the slack is finite and >= 0)", slack);
+    if (E == 0 || V == 0) return CGS_OK;
+    if (!edt_size_ok(height, width))   // d2 is a cgs_edt_squared transform, depth has its size
+        return reject("cgs_edge_support_depth: invalid argument (height=%d, width=%d; sizes lie in [1, %d])", height, width,
+                      CGS_EDT_MAX_SIZE);
+    if (!offsets || !intr || !w2c || !d2 || !tol2 || !depth || !counts || (P > 0 && !points))
+        return reject("cgs_edge_support_depth: invalid argument (NULL pointer)");
+    launch_edge_support_depth((hipStream_t)stream_, E, P, points, offsets, V, intr, w2c, height, width, d2, T, tol2, depth,
+                              slack, counts, hidden);
+    return finish("edge_support_depth", stream_);
+}
+
+int cgs_sample_support_depth(int P, const float* points, int V, const double* intr, const double* w2c, int height, int width,
+                             const int32_t* d2, int T, const int32_t* tol2, const float* depth, double slack, int32_t* tally,
+                             int32_t* hidden, void* stream_) {
+    if (P < 0 || V < 0 || T < 1 || T > CGS_EDGE_SUPPORT_MAX_TOL)
+        return reject("cgs_sample_support_depth: invalid argument (P=%d, V=%d, T=%d; T lies in [1, %d])", P, V, T,
+                      CGS_EDGE_SUPPORT_MAX_TOL);
+    if (!edt_size_ok(height, width))   // d2 is a cgs_edt_squared transform, depth has its size
+        return reject("cgs_sample_support_depth: invalid argument (height=%d, width=%d; sizes lie in [1, %d])", height, width,
+                      CGS_EDT_MAX_SIZE);
+    if (!slack_ok(slack))
+        return reject("cgs_sample_support_depth: invalid argument (slack=%g; the slack is finite and >= 0)", slack);
+    if (!intr || !w2c || !d2 || !tol2 || !depth || (P > 0 && (!points || !tally)))
+        return reject("cgs_sample_support_depth: invalid argument (NULL pointer; P=%d, V=%d)", P, V);
+    if (P == 0 || V == 0) return CGS_OK;   // nothing to add
+    launch_sample_support_depth((hipStream_t)stream_, P, points, V, intr, w2c, height, width, d2, T, tol2, depth, slack, tally,
+                                hidden);
+    return finish("sample_support_depth", stream_);
+}
+
+int cgs_sample_support_oriented_depth(int P, const float* points, const int32_t* partner, int V, const double* intr,
+                                      const double* w2c, int height, int width, const uint8_t* near, int spread,
+                                      const float* depth, double slack, int32_t* tally, int32_t* hidden, void* stream_) {
+    if (P < 0 || V < 0 || spread < 0 || spread > CGS_ORIENT_MAX_SPREAD)
+        return reject("cgs_sample_support_oriented_depth: invalid argument (P=%d, V=%d, spread=%d; the spread lies in [0, %d])",
+                      P, V, spread, CGS_ORIENT_MAX_SPREAD);
+    if (!edt_size_ok(height, width))
+        return reject("cgs_sample_support_oriented_depth: invalid argument (height=%d, width=%d; sizes lie in [1, %d])", height,
+                      width, CGS_EDT_MAX_SIZE);
+    if (!slack_ok(slack))
+        return reject("cgs_sample_support_oriented_depth: invalid argument (slack=%g; the slack is finite and >= 0)", slack);
+    if (!intr || !w2c || !near || !depth || (P > 0 && (!points || !partner || !tally)))
+        return reject("cgs_sample_support_oriented_depth: invalid argument (NULL pointer; P=%d, V=%d)", P, V);
+    if (P == 0 || V == 0) return CGS_OK;   // nothing to add
+    launch_sample_support_oriented_depth((hipStream_t)stream_, P, points, partner, V, intr, w2c, height, width, near, spread,
+                                         depth, slack, tally, hidden);
+    return finish("sample_support_oriented_depth", stream_);
+}
+
+int cgs_sample_snap_terms_depth(int P, const float* points, int V, const double* intr, const double* w2c, int height,
+                                int width, const int32_t* d2, int cap2, const double* dist_lut, const float* depth,
+                                double slack, double* terms, int32_t* views, int32_t* hidden, void* stream_) {
+    if (P < 0 || V < 0 || cap2 < 1 || cap2 > CGS_SNAP_MAX_CAP2)   // the kernel stages cap2 + 1 table entries in LDS
+        return reject("cgs_sample_snap_terms_depth: invalid argument (P=%d, V=%d, cap2=%d; cap2 lies in [1, %d])", P, V, cap2,
+                      CGS_SNAP_MAX_CAP2);
+    if (!edt_size_ok(height, width))   // d2 is a cgs_edt_squared transform, depth has its size
+        return reject("cgs_sample_snap_terms_depth: invalid argument (height=%d, width=%d; sizes lie in [1, %d])", height,
+                      width, CGS_EDT_MAX_SIZE);
+    if (!slack_ok(slack))
+        return reject("cgs_sample_snap_terms_depth: invalid argument (slack=%g; the slack is finite and >= 0)", slack);
+    if (!intr || !w2c || !d2 || !dist_lut || !depth || (P > 0 && (!points || !terms || !views)))
+        return reject("cgs_sample_snap_terms_depth: invalid argument (NULL pointer; P=%d, V=%d)", P, V);
+    if (P == 0 || V == 0) return CGS_OK;   // nothing to add
+    launch_sample_snap_terms_depth((hipStream_t)stream_, P, points, V, intr, w2c, height, width, d2, cap2, dist_lut, depth,
+                                   slack, terms, views, hidden);
+    return finish("sample_snap_terms_depth", stream_);
+}
+
 }  // extern "C"

@@ -20,6 +20,9 @@
 //                        so the 16 doubles of a camera are wave-uniform loads.  The sample's and its partner's points are
 //                        read once before the loop; both are projected with nv_project_xyz in every view.  Two sums in
 //                        registers, one read-modify-write of the thread's own row: no atomics, no LDS, no barrier.
+//                        A template over GATED: false is cgs_sample_support_oriented as it always was; true is
+//                        cgs_sample_support_oriented_depth -- nv_verdict (point_projection.h) gates the SAMPLE; the partner
+//                        gives a direction only and is projected with nv_project_xyz, never held against the depth.
 // Nothing here depends on the launch geometry: one owner per output byte or row, integer sums, no order of arrival.
 #include <algorithm>
 
@@ -197,10 +200,12 @@ void launch_oriented_near(hipStream_t s, int V, int height, int width, const uin
 
 constexpr int ORIENT_TALLY_THREADS = 256;
 
+template <bool GATED>
 __global__ void __launch_bounds__(ORIENT_TALLY_THREADS)
 k_sample_support_oriented(int P, const float* __restrict__ pts, const int* __restrict__ partner, int V,
                           const double* __restrict__ intr, const double* __restrict__ w2c, int height, int width,
-                          const uint8_t* __restrict__ near, int spread, int* __restrict__ tally) {
+                          const uint8_t* __restrict__ near, int spread, int* __restrict__ tally,
+                          const float* __restrict__ depth, double slack, int* __restrict__ hidden) {
     const long long i = (long long)blockIdx.x * ORIENT_TALLY_THREADS + threadIdx.x;
     if (i >= P) return;   // the kernel has no barrier
     const double X = (double)pts[3 * i + 0], Y = (double)pts[3 * i + 1], Z = (double)pts[3 * i + 2];
@@ -212,12 +217,18 @@ k_sample_support_oriented(int P, const float* __restrict__ pts, const int* __res
     const unsigned band = spread >= 4 ? 0xFFu : (1u << (2 * spread + 1)) - 1u;
     const double wd = (double)width, hd = (double)height;
     const size_t plane = (size_t)height * (size_t)width;
-    int seen = 0, hit = 0;
+    int seen = 0, hit = 0, hid = 0;
     for (int view = 0; view < V; view++) {   // wave-uniform
         NvCam c;
         nv_load_cam(c, intr, w2c, view);
         double u, v, up, vp;
-        if (!nv_project_xyz(c, X, Y, Z, wd, hd, u, v)) continue;
+        const NvVerdict verdict = nv_verdict<GATED>(c, X, Y, Z, wd, hd, GATED ? depth + (size_t)view * plane : nullptr, width,
+                                                    slack, u, v);
+        if (verdict == NV_OUT) continue;
+        if (GATED && verdict == NV_HIDDEN) {
+            hid++;
+            continue;
+        }
         seen++;
         unsigned acc = 0xFFu;
         if (paired && nv_project_xyz(c, Xp, Yp, Zp, wd, hd, up, vp)) {
@@ -237,14 +248,30 @@ k_sample_support_oriented(int P, const float* __restrict__ pts, const int* __res
     int* __restrict__ out = tally + 2 * (size_t)i;   // the thread's own row: a plain read-modify-write
     out[0] += seen;
     out[1] += hit;
+    if (GATED && hidden) hidden[i] += hid;   // added, like the tally: the thread's own word
+}
+
+template <bool GATED>
+static void sample_support_oriented_launch(hipStream_t s, int P, const float* points, const int* partner, int V,
+                                           const double* intr, const double* w2c, int height, int width, const uint8_t* near,
+                                           int spread, int* tally, const float* depth, double slack, int* hidden) {
+    const unsigned blocks = (unsigned)(((long long)P + ORIENT_TALLY_THREADS - 1) / ORIENT_TALLY_THREADS);   // at most 2^23
+    ProfScope p(GATED ? "sample_support_oriented_depth" : "sample_support_oriented", s);
+    hipLaunchKernelGGL(k_sample_support_oriented<GATED>, dim3(blocks), dim3(ORIENT_TALLY_THREADS), 0, s, P, points, partner, V,
+                       intr, w2c, height, width, near, spread, tally, depth, slack, hidden);
 }
 
 void launch_sample_support_oriented(hipStream_t s, int P, const float* points, const int* partner, int V, const double* intr,
                                     const double* w2c, int height, int width, const uint8_t* near, int spread, int* tally) {
-    const unsigned blocks = (unsigned)(((long long)P + ORIENT_TALLY_THREADS - 1) / ORIENT_TALLY_THREADS);   // at most 2^23
-    ProfScope p("sample_support_oriented", s);
-    hipLaunchKernelGGL(k_sample_support_oriented, dim3(blocks), dim3(ORIENT_TALLY_THREADS), 0, s, P, points, partner, V, intr,
-                       w2c, height, width, near, spread, tally);
+    sample_support_oriented_launch<false>(s, P, points, partner, V, intr, w2c, height, width, near, spread, tally, nullptr, 0.0,
+                                          nullptr);
+}
+
+void launch_sample_support_oriented_depth(hipStream_t s, int P, const float* points, const int* partner, int V,
+                                          const double* intr, const double* w2c, int height, int width, const uint8_t* near,
+                                          int spread, const float* depth, double slack, int* tally, int* hidden) {
+    sample_support_oriented_launch<true>(s, P, points, partner, V, intr, w2c, height, width, near, spread, tally, depth, slack,
+                                         hidden);
 }
 
 }  // namespace cgs

@@ -14,6 +14,10 @@
 //                         order and stores them: one owner per row, no atomics, and the same floating-point sequence however
 //                         the views are cut into calls.  Everything is float64, one rounded operation at a time (contraction
 //                         off, IEEE division), in the order frozen in the header.
+//                         A template over GATED: false is cgs_sample_snap_terms as it always was; true is
+//                         cgs_sample_snap_terms_depth -- nv_verdict (point_projection.h) drops a view whose depth plane hides
+//                         the sample right after the projection's verdict, before the footprint test: no term, no view, and
+//                         for every other view the floating-point sequence of the ungated kernel.
 #include "kernels.h"
 #include "point_projection.h"
 
@@ -22,12 +26,15 @@ namespace cgs {
 constexpr int SNAP_THREADS = 256;
 static_assert(CGS_SNAP_TERMS == 10, "Axx Axy Axz Ayy Ayz Azz bx by bz rr");
 
+template <bool GATED>
 __global__ void __launch_bounds__(SNAP_THREADS) k_sample_snap_terms(int P, const float* __restrict__ pts, int V,
                                                                     const double* __restrict__ intr,
                                                                     const double* __restrict__ w2c, int height, int width,
                                                                     const int* __restrict__ d2, int cap2,
                                                                     const double* __restrict__ dist_lut,
-                                                                    double* __restrict__ terms, int* __restrict__ views) {
+                                                                    double* __restrict__ terms, int* __restrict__ views,
+                                                                    const float* __restrict__ depth, double slack,
+                                                                    int* __restrict__ hidden) {
 #pragma clang fp contract(off)
     __shared__ double lut[CGS_SNAP_MAX_CAP2 + 1];
     for (int k = threadIdx.x; k <= cap2; k += SNAP_THREADS) lut[k] = dist_lut[k];   // cap2 <= CGS_SNAP_MAX_CAP2 (the entry)
@@ -37,7 +44,7 @@ __global__ void __launch_bounds__(SNAP_THREADS) k_sample_snap_terms(int P, const
     double* __restrict__ row = terms + (size_t)i * CGS_SNAP_TERMS;   // the thread's own row: a plain read-modify-write
     double Axx = row[0], Axy = row[1], Axz = row[2], Ayy = row[3], Ayz = row[4], Azz = row[5];
     double bx = row[6], by = row[7], bz = row[8], rr = row[9];
-    int n = views[i];
+    int n = views[i], hid = 0;
     const double X = (double)pts[3 * i + 0], Y = (double)pts[3 * i + 1], Z = (double)pts[3 * i + 2];
     const double wd = (double)width, hd = (double)height;
     const size_t plane = (size_t)height * (size_t)width;
@@ -51,7 +58,13 @@ __global__ void __launch_bounds__(SNAP_THREADS) k_sample_snap_terms(int P, const
         const double c2 = ((c.m[8] * X + c.m[9] * Y) + c.m[10] * Z) + c.m[11];
         const double x = c0 / c2, y = c1 / c2;
         double u, v;
-        if (!nv_project_xyz(c, X, Y, Z, wd, hd, u, v)) continue;
+        const NvVerdict verdict = nv_verdict<GATED>(c, X, Y, Z, wd, hd, GATED ? depth + (size_t)view * plane : nullptr, width,
+                                                    slack, u, v);
+        if (verdict == NV_OUT) continue;
+        if (GATED && verdict == NV_HIDDEN) {   // no term, no view
+            hid++;
+            continue;
+        }
         // the footprint: the four pixel centres around (u, v); 0 <= u < W <= 16384, so the floors fit an int
         const double a = u - 0.5, b = v - 0.5;
         const double fj = floor(a), fi = floor(b);
@@ -87,15 +100,31 @@ __global__ void __launch_bounds__(SNAP_THREADS) k_sample_snap_terms(int P, const
     row[0] = Axx, row[1] = Axy, row[2] = Axz, row[3] = Ayy, row[4] = Ayz, row[5] = Azz;
     row[6] = bx, row[7] = by, row[8] = bz, row[9] = rr;
     views[i] = n;
+    if (GATED && hidden) hidden[i] += hid;   // added, like the sums: the thread's own word
+}
+
+template <bool GATED>
+static void sample_snap_terms_launch(hipStream_t s, int P, const float* points, int V, const double* intr, const double* w2c,
+                                     int height, int width, const int* d2, int cap2, const double* dist_lut, double* terms,
+                                     int* views, const float* depth, double slack, int* hidden) {
+    const unsigned blocks = (unsigned)(((long long)P + SNAP_THREADS - 1) / SNAP_THREADS);   // at most 2^23: one grid dimension
+    ProfScope p(GATED ? "sample_snap_terms_depth" : "sample_snap_terms", s);
+    hipLaunchKernelGGL(k_sample_snap_terms<GATED>, dim3(blocks), dim3(SNAP_THREADS), 0, s, P, points, V, intr, w2c, height,
+                       width, d2, cap2, dist_lut, terms, views, depth, slack, hidden);
 }
 
 void launch_sample_snap_terms(hipStream_t s, int P, const float* points, int V, const double* intr, const double* w2c,
                               int height, int width, const int* d2, int cap2, const double* dist_lut, double* terms,
                               int* views) {
-    const unsigned blocks = (unsigned)(((long long)P + SNAP_THREADS - 1) / SNAP_THREADS);   // at most 2^23: one grid dimension
-    ProfScope p("sample_snap_terms", s);
-    hipLaunchKernelGGL(k_sample_snap_terms, dim3(blocks), dim3(SNAP_THREADS), 0, s, P, points, V, intr, w2c, height, width, d2,
-                       cap2, dist_lut, terms, views);
+    sample_snap_terms_launch<false>(s, P, points, V, intr, w2c, height, width, d2, cap2, dist_lut, terms, views, nullptr, 0.0,
+                                    nullptr);
+}
+
+void launch_sample_snap_terms_depth(hipStream_t s, int P, const float* points, int V, const double* intr, const double* w2c,
+                                    int height, int width, const int* d2, int cap2, const double* dist_lut, const float* depth,
+                                    double slack, double* terms, int* views, int* hidden) {
+    sample_snap_terms_launch<true>(s, P, points, V, intr, w2c, height, width, d2, cap2, dist_lut, terms, views, depth, slack,
+                                   hidden);
 }
 
 }  // namespace cgs

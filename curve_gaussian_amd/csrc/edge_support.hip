@@ -8,6 +8,9 @@
 //                      transform per seen point.  1 + T counts stay in registers; one __shfl_xor reduction per wave; lane 0
 //                      stores the 1 + T integers.  No atomics, no LDS, no barrier: integers only, so the result does not
 //                      depend on the launch geometry.  Every output word is written (an edge without points stores zeros).
+//                      A template over GATED: false is cgs_edge_support as it always was (depth, slack and hidden are not
+//                      read); true is cgs_edge_support_depth -- nv_verdict (point_projection.h) sends a sample that the view's
+//                      depth plane hides to a sixth counter instead of `seen`, one float32 gather more per seen sample.
 #include <algorithm>
 
 #include "kernels.h"
@@ -20,12 +23,15 @@ constexpr int SUPPORT_WAVES = SUPPORT_THREADS / 64;   // edges per workgroup
 constexpr int SUPPORT_MAX_VIEWS = 65535;              // views per launch: grid.y
 static_assert(CGS_EDGE_SUPPORT_MAX_TOL == 4, "the kernel keeps 1 + 4 counts in registers");
 
+template <bool GATED>
 __global__ void __launch_bounds__(SUPPORT_THREADS) k_edge_support(int E, int P, const float* __restrict__ pts,
                                                                  const int* __restrict__ offsets, int V, int v0,
                                                                  const double* __restrict__ intr,
                                                                  const double* __restrict__ w2c, int height, int width,
                                                                  const int* __restrict__ d2, int T,
-                                                                 const int* __restrict__ tol2, int* __restrict__ counts) {
+                                                                 const int* __restrict__ tol2, int* __restrict__ counts,
+                                                                 const float* __restrict__ depth, double slack,
+                                                                 int* __restrict__ hidden) {
     constexpr int MT = CGS_EDGE_SUPPORT_MAX_TOL;
     const int lane = threadIdx.x & 63;
     const long long e = (long long)blockIdx.x * SUPPORT_WAVES + (threadIdx.x >> 6);
@@ -41,12 +47,19 @@ __global__ void __launch_bounds__(SUPPORT_THREADS) k_edge_support(int E, int P, 
     const long long end = std::min<long long>(std::max<long long>(offsets[e + 1], 0), P);
     const double wd = (double)width, hd = (double)height;
     const int* __restrict__ plane = d2 + (size_t)view * (size_t)height * (size_t)width;
-    int seen = 0, near[MT];
+    const float* __restrict__ dplane = GATED ? depth + (size_t)view * (size_t)height * (size_t)width : nullptr;
+    int seen = 0, hid = 0, near[MT];
 #pragma unroll
     for (int t = 0; t < MT; t++) near[t] = 0;
     for (long long i = begin + lane; i < end; i += 64) {   // at most 2^31 / 64 points per lane: int counts
         double u, v;
-        if (!nv_project(c, pts, i, wd, hd, u, v)) continue;
+        const NvVerdict verdict = nv_verdict<GATED>(c, (double)pts[3 * i + 0], (double)pts[3 * i + 1], (double)pts[3 * i + 2],
+                                                    wd, hd, dplane, width, slack, u, v);
+        if (verdict == NV_OUT) continue;
+        if (GATED && verdict == NV_HIDDEN) {
+            hid++;
+            continue;
+        }
         // 0 <= u < W, so 0 <= floor(u) <= W - 1 (likewise v): the pixel is inside the view's plane
         const int d = plane[(size_t)floor(v) * (size_t)width + (size_t)floor(u)];
         seen++;
@@ -56,6 +69,7 @@ __global__ void __launch_bounds__(SUPPORT_THREADS) k_edge_support(int E, int P, 
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) {
         seen += __shfl_xor(seen, off, 64);
+        if (GATED) hid += __shfl_xor(hid, off, 64);
 #pragma unroll
         for (int t = 0; t < MT; t++) near[t] += __shfl_xor(near[t], off, 64);
     }
@@ -65,19 +79,35 @@ __global__ void __launch_bounds__(SUPPORT_THREADS) k_edge_support(int E, int P, 
 #pragma unroll
     for (int t = 0; t < MT; t++)
         if (t < T) out[1 + t] = near[t];
+    if (GATED && hidden) hidden[(size_t)e * (size_t)V + (size_t)(v0 + view)] = hid;   // written, like counts
+}
+
+template <bool GATED>
+static void edge_support_launches(hipStream_t s, int E, int P, const float* points, const int* offsets, int V,
+                                  const double* intr, const double* w2c, int height, int width, const int* d2, int T,
+                                  const int* tol2, int* counts, const float* depth, double slack, int* hidden) {
+    const size_t plane = (size_t)height * (size_t)width;
+    const unsigned blocks = (unsigned)(((long long)E + SUPPORT_WAVES - 1) / SUPPORT_WAVES);
+    ProfScope p(GATED ? "edge_support_depth" : "edge_support", s);
+    for (int v0 = 0; v0 < V; v0 += SUPPORT_MAX_VIEWS) {
+        const int nv = std::min(SUPPORT_MAX_VIEWS, V - v0);
+        hipLaunchKernelGGL(k_edge_support<GATED>, dim3(blocks, nv), dim3(SUPPORT_THREADS), 0, s, E, P, points, offsets, V, v0,
+                           intr + 4 * (size_t)v0, w2c + 12 * (size_t)v0, height, width, d2 + (size_t)v0 * plane, T, tol2,
+                           counts, GATED ? depth + (size_t)v0 * plane : nullptr, slack, hidden);
+    }
 }
 
 void launch_edge_support(hipStream_t s, int E, int P, const float* points, const int* offsets, int V, const double* intr,
                          const double* w2c, int height, int width, const int* d2, int T, const int* tol2, int* counts) {
-    const size_t plane = (size_t)height * (size_t)width;
-    const unsigned blocks = (unsigned)(((long long)E + SUPPORT_WAVES - 1) / SUPPORT_WAVES);
-    ProfScope p("edge_support", s);
-    for (int v0 = 0; v0 < V; v0 += SUPPORT_MAX_VIEWS) {
-        const int nv = std::min(SUPPORT_MAX_VIEWS, V - v0);
-        hipLaunchKernelGGL(k_edge_support, dim3(blocks, nv), dim3(SUPPORT_THREADS), 0, s, E, P, points, offsets, V, v0,
-                           intr + 4 * (size_t)v0, w2c + 12 * (size_t)v0, height, width, d2 + (size_t)v0 * plane, T, tol2,
-                           counts);
-    }
+    edge_support_launches<false>(s, E, P, points, offsets, V, intr, w2c, height, width, d2, T, tol2, counts, nullptr, 0.0,
+                                 nullptr);
+}
+
+void launch_edge_support_depth(hipStream_t s, int E, int P, const float* points, const int* offsets, int V,
+                               const double* intr, const double* w2c, int height, int width, const int* d2, int T,
+                               const int* tol2, const float* depth, double slack, int* counts, int* hidden) {
+    edge_support_launches<true>(s, E, P, points, offsets, V, intr, w2c, height, width, d2, T, tol2, counts, depth, slack,
+                                hidden);
 }
 
 }  // namespace cgs

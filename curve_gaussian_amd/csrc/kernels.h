@@ -240,10 +240,16 @@ void launch_ray_wins(hipStream_t s, SeedGrid g, SeedViews views, int M, const in
 // edge_support.hip
 void launch_edge_support(hipStream_t s, int E, int P, const float* points, const int* offsets, int V, const double* intr,
                          const double* w2c, int height, int width, const int* d2, int T, const int* tol2, int* counts);
+void launch_edge_support_depth(hipStream_t s, int E, int P, const float* points, const int* offsets, int V,
+                               const double* intr, const double* w2c, int height, int width, const int* d2, int T,
+                               const int* tol2, const float* depth, double slack, int* counts, int* hidden);
 
 // edge_trim.hip
 void launch_sample_support(hipStream_t s, int P, const float* points, int V, const double* intr, const double* w2c,
                            int height, int width, const int* d2, int T, const int* tol2, int* tally);
+void launch_sample_support_depth(hipStream_t s, int P, const float* points, int V, const double* intr, const double* w2c,
+                                 int height, int width, const int* d2, int T, const int* tol2, const float* depth, double slack,
+                                 int* tally, int* hidden);
 
 // edge_dedupe.hip
 size_t sample_cover_workspace_bytes(int P);
@@ -264,11 +270,17 @@ void launch_mask_orientation(hipStream_t s, int V, int height, int width, const 
 void launch_oriented_near(hipStream_t s, int V, int height, int width, const uint8_t* code, int tol2, uint8_t* near);
 void launch_sample_support_oriented(hipStream_t s, int P, const float* points, const int* partner, int V, const double* intr,
                                     const double* w2c, int height, int width, const uint8_t* near, int spread, int* tally);
+void launch_sample_support_oriented_depth(hipStream_t s, int P, const float* points, const int* partner, int V,
+                                          const double* intr, const double* w2c, int height, int width, const uint8_t* near,
+                                          int spread, const float* depth, double slack, int* tally, int* hidden);
 
 // edge_snap.hip
 void launch_sample_snap_terms(hipStream_t s, int P, const float* points, int V, const double* intr, const double* w2c,
                               int height, int width, const int* d2, int cap2, const double* dist_lut, double* terms,
                               int* views);
+void launch_sample_snap_terms_depth(hipStream_t s, int P, const float* points, int V, const double* intr, const double* w2c,
+                                    int height, int width, const int* d2, int cap2, const double* dist_lut, const float* depth,
+                                    double slack, double* terms, int* views, int* hidden);
 
 // edge_occlusion.hip
 hipError_t launch_mesh_depth(hipStream_t s, int F, const float* tris, int V, const double* intr, const double* w2c,

@@ -2,7 +2,8 @@
 // keeps (novel_view.hip: cgs_project_points / cgs_render_points; edge_score.hip: cgs_point_mask; edge_seed.hip:
 // cgs_voxel_votes, cgs_ray_claims and cgs_ray_wins -- k_voxel_votes, k_ray_claims, k_ray_wins through seed_walk;
 // edge_support.hip: cgs_edge_support; edge_trim.hip: cgs_sample_support; edge_orient.hip: cgs_sample_support_oriented;
-// edge_snap.hip: cgs_sample_snap_terms; edge_occlusion.hip: cgs_point_mask_depth through nv_project_xyz_depth, and
+// edge_snap.hip: cgs_sample_snap_terms -- those four and their _depth siblings through nv_verdict at the end of this file;
+// edge_occlusion.hip: cgs_point_mask_depth through nv_project_xyz_depth, and
 // cgs_mesh_depth, which projects a triangle's vertices in the same operation order through nv_camera_xyz / nv_image_uv).
 //
 // Exact, the reference's operation order (eval_ABC.py project_points_to_camera :66-81): X float32 widened to float64,
@@ -85,6 +86,26 @@ __device__ inline bool nv_hidden(const float* __restrict__ depth_plane, int widt
 #pragma clang fp contract(off)
     const double d = (double)depth_plane[(size_t)floor(v) * (size_t)width + (size_t)floor(u)];
     return c2 > d + slack;
+}
+
+// ---- the gate as a template parameter (edge_support.hip, edge_trim.hip, edge_orient.hip, edge_snap.hip; include/curvegs.h,
+// cgs_edge_support_depth and the three after it).  What one view says of one sample: not kept, kept and visible, or kept and
+// hidden.  GATED = false is nv_project_xyz and nothing else -- depth_plane and slack are not touched, no sample is hidden;
+// GATED = true is nv_project_xyz_depth followed by nv_hidden.  The two projections are the same operations in the same
+// order, so NV_VISIBLE + NV_HIDDEN of the gated form is NV_VISIBLE of the ungated one, with the same (u, v).
+enum NvVerdict { NV_OUT = 0, NV_VISIBLE = 1, NV_HIDDEN = 2 };
+
+template <bool GATED>
+__device__ __forceinline__ NvVerdict nv_verdict(const NvCam& c, double X, double Y, double Z, double wd, double hd,
+                                                const float* __restrict__ depth_plane, int width, double slack, double& u,
+                                                double& v) {
+    if constexpr (GATED) {
+        double c2;
+        if (!nv_project_xyz_depth(c, X, Y, Z, wd, hd, u, v, c2)) return NV_OUT;
+        return nv_hidden(depth_plane, width, u, v, c2, slack) ? NV_HIDDEN : NV_VISIBLE;
+    } else {
+        return nv_project_xyz(c, X, Y, Z, wd, hd, u, v) ? NV_VISIBLE : NV_OUT;
+    }
 }
 
 }  // namespace cgs

@@ -73,43 +73,30 @@ def score_edges(pred, cameras, edge_maps_u8, detector, tolerances_px=(1, 2, 4), 
     true) or "depth_maps": true, and "depth_slack" and "depth_window"; a chunk's working set grows by
     ``ops.edge_score.DEPTH_BYTES_PER_PIXEL``.  With neither, nothing changes: no key is added."""
     ES._check_backend(backend)
-    if occluder is not None and depth_maps is not None:
-        raise ValueError("score_edges: give an occluder or depth_maps, not both")
+    EO.check_one_depth_source("score_edges", occluder, depth_maps)
     gated = occluder is not None or depth_maps is not None
     tolerances_px = [float(t) for t in tolerances_px]
     ES.tolerances_squared(tolerances_px)
     lut = detected_lut(detector, edge_threshold)
     cameras, maps = check_edge_maps("score_edges", cameras, edge_maps_u8)
-    if gated:
-        depth_slack = EO._check_slack("score_edges", depth_slack)
-        depth_window = EO._check_window("score_edges", depth_window)
-    if occluder is not None:
-        tris = EO.read_triangle_mesh(occluder) if isinstance(occluder, (str, os.PathLike)) else occluder
-        tris = EO._as_tris(tris)
-    if depth_maps is not None:
-        depth_maps = EO.check_depth_maps(cameras, depth_maps)
+    gate = EO.ChunkDepth("score_edges", cameras, occluder, depth_maps, depth_slack, depth_window)
     pts = _pred_points(pred, sample_resolution)
     if backend == "gpu":
         device = ES._device_for([], "score_edges", device)
         pts_b = torch.from_numpy(pts).to(device)
-        if occluder is not None:
-            tris = tris.to(device)
     else:
         pts_b = pts
+    gate.to(backend, device)
     budget = ES.BYTE_BUDGET if budget_bytes is None else int(budget_bytes)
     V, n_tol = len(cameras), len(tolerances_px)
     per_view = {"n_pred": np.zeros(V, np.int64), "n_det": np.zeros(V, np.int64), "pred_hits": np.zeros((V, n_tol), np.int64),
                 "det_hits": np.zeros((V, n_tol), np.int64), "sum_pred_to_det": np.zeros(V, np.float64),
                 "sum_det_to_pred": np.zeros(V, np.float64), "both_nonempty": np.zeros(V, bool)}
     kept, hidden = np.zeros(V, np.int64), np.zeros(V, np.int64)
-    for H, W, sel, intr, w2c in view_chunks(cameras, ES.BYTES_PER_PIXEL + (ES.DEPTH_BYTES_PER_PIXEL if gated else 0), budget):
+    for H, W, sel, intr, w2c in view_chunks(cameras, ES.BYTES_PER_PIXEL + gate.bytes_per_pixel, budget):
         if gated:
-            if occluder is not None:
-                depth = EO.mesh_depth(tris, intr, w2c, H, W, depth_window, backend=backend, device=device)
-            else:
-                depth = EO.depth_window_max(np.stack([depth_maps[v] for v in sel]), depth_window, backend=backend,
-                                            device=device)
-            pm, k, hid = EO.point_masks_depth(pts_b, intr, w2c, depth, depth_slack, backend=backend, device=device,
+            depth = gate.planes(H, W, sel, intr, w2c)
+            pm, k, hid = EO.point_masks_depth(pts_b, intr, w2c, depth, gate.slack, backend=backend, device=device,
                                               return_counts=True)
             hidden[sel] = hid.cpu().numpy()
             del depth
@@ -139,12 +126,7 @@ def score_edges(pred, cameras, edge_maps_u8, detector, tolerances_px=(1, 2, 4), 
                 "sample_resolution": float(sample_resolution), "backend": backend, "points": int(pts.shape[0])}
     if thin:
         settings["thin"] = True
-    if gated:
-        if occluder is not None:
-            settings["occluder"] = os.fspath(occluder) if isinstance(occluder, (str, os.PathLike)) else True
-        else:
-            settings["depth_maps"] = True
-        settings.update({"depth_slack": depth_slack, "depth_window": depth_window})
+    settings.update(gate.settings())
     return {"aggregate": agg, "views": rows, "settings": settings}
 
 

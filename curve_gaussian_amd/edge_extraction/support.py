@@ -4,8 +4,13 @@ freezes the verdict).  Unlike the reference's visibility check, which looks at a
 two end points, this says WHICH edge the images do not show along its length; unlike the reprojection score it is one
 record per edge.  The reference has no counterpart.
 
-KNOWN LIMITS: there is no depth -- an edge hidden behind a surface in most views loses its support there, which is why the
-rule counts supporting frames and does not pool; a thick detector response inflates support; THE DEFAULTS ARE UNTUNED.
+KNOWN LIMITS: without a depth source an edge hidden behind a surface in most views loses its support there, which is why
+the rule counts supporting frames and does not pool; a thick detector response inflates support; THE DEFAULTS ARE UNTUNED.
+With ``--occluder`` (a mesh inside every scan directory) or ``--depth_dir`` (one ``<image stem>.npy`` per camera), and
+``--depth_slack`` / ``--depth_window``, every 2D step run here -- the check, ``--snap`` and ``--trim`` (``--oriented``) --
+counts a (sample, view) pair that the depth hides as not seen (``ops.edge_occlusion``: the one rule and its limits --
+untuned, drawn solids only, concave edges, no near-plane clipping); the files then record the depth settings and one
+hidden total per edge.  Without the flags no file changes by a byte.
 
 ``python -m curve_gaussian_amd.edge_extraction.support --base_dir <predictions> --dataset_dir <scans>`` checks every scan,
 writes ``<base_dir>/<scan>/edge_support.json`` -- one record per edge -- and, with ``--write_filtered``,
@@ -43,8 +48,8 @@ from ..ops import edge_snap as SN
 from ..ops import edge_support as SP
 from ..ops import edge_trim as ET
 from .para_edge import EDGE_MAX_THRESHOLD, EDGE_VISIBILITY_FRAMES_RATIO
-from .reprojection import (LAYOUTS, SAMPLE_RESOLUTION, _json_number, colmap_scan_cameras, dataset_scans, emap_cameras,
-                           scene_cameras, write_score)
+from .reprojection import (LAYOUTS, SAMPLE_RESOLUTION, _json_number, add_depth_arguments, colmap_scan_cameras, dataset_scans,
+                           emap_cameras, scan_depth_maps, scene_cameras, write_score)
 
 log = logging.getLogger(__name__)
 
@@ -74,7 +79,8 @@ def filter_edge_dict(edge_dict, kept):
 
 def edge_records(result):
     """One record per edge of an ``edge_support`` result: kind ("curve" / "line"), index within its kind, samples, seeing
-    views, supporting views and pooled share per tolerance (NaN as None), kept."""
+    views, supporting views and pooled share per tolerance (NaN as None), kept -- and, for a depth-gated result only,
+    "hidden_samples": the (sample, view) pairs of the edge that the depth hides, summed over the views."""
     nc = result["curves"]
     rows = []
     for e in range(len(result["n_points"])):
@@ -82,6 +88,8 @@ def edge_records(result):
                      "samples": int(result["n_points"][e]), "seeing_views": int(result["seeing_views"][e]),
                      "supporting_views": [int(s) for s in result["supporting_views"][e]],
                      "share": [_json_number(s) for s in result["share"][e]], "kept": bool(result["kept"][e])})
+        if "hidden" in result:
+            rows[-1]["hidden_samples"] = int(np.asarray(result["hidden"][e]).sum())
     return rows
 
 
@@ -99,14 +107,19 @@ def write_support(model_dir, edge_dict, result, write_filtered=False, extra=None
 
 def trim_records(result, curves):
     """One record per edge of a ``trim_edges`` result (``curves``: how many of the edges are curves): kind, index within its
-    kind, samples, spans as [a, b] pairs, and the kept share of its samples (None for an edge without samples)."""
-    n = np.diff(result["offsets"].astype(np.int64))
+    kind, samples, spans as [a, b] pairs, and the kept share of its samples (None for an edge without samples) -- and, for a
+    depth-gated result only, "hidden_views": the (sample, view) pairs of the edge that the depth hides, summed over its
+    samples."""
+    off = result["offsets"].astype(np.int64)
+    n = np.diff(off)
     rows = []
     for e, spans in enumerate(result["spans"]):
         kept = sum(b - a + 1 for a, b in spans)
         rows.append({"kind": "curve" if e < curves else "line", "index": int(e if e < curves else e - curves),
                      "samples": int(n[e]), "spans": [[int(a), int(b)] for a, b in spans],
                      "kept_share": kept / int(n[e]) if n[e] > 0 else None})
+        if "hidden" in result:
+            rows[-1]["hidden_views"] = int(np.asarray(result["hidden"][off[e]:off[e + 1]]).sum())
     return rows
 
 
@@ -193,7 +206,7 @@ def write_snap(model_dir, result, extra=None):
 
 def score_scan(base_dir, dataset_dir, scan, layout="emap", detector="DexiNed", undistort=False, write_filtered=False,
                device=None, backend="gpu", resolution=-1, trim_options=None, dedupe_options=None, join_options=None,
-               snap_options=None, **options):
+               snap_options=None, occluder=None, depth_dir=None, depth_slack=None, depth_window=None, **options):
     """Checks ``<base_dir>/<scan>/parametric_edges.json`` against the ``detector`` edge maps of ``<dataset_dir>/<scan>`` and
     writes ``<base_dir>/<scan>/edge_support.json`` (``write_support``).  ``layout``, ``undistort`` and ``resolution`` (of the
     images) as ``reprojection.score_scan``, the same camera loaders; ``options`` go to ``ops.edge_support.edge_support``
@@ -210,7 +223,10 @@ def score_scan(base_dir, dataset_dir, scan, layout="emap", detector="DexiNed", u
     maps, FIRST, with the check's sampling resolution, edge threshold and ``thin`` unless they name their own: ``write_snap``
     adds its two files, and the check and every later step start from the snapped edges -- ``edge_support.json`` and
     ``edge_trim.json`` then record "input": ``parametric_edges_snapped.json``, and so do the later files where they would have
-    named ``parametric_edges.json``.  Returns the dict of ``write_support``, with the ones of ``write_trim``, ``write_dedupe`` and ``write_join`` under "trim", "dedupe" and "join"
+    named ``parametric_edges.json``.  ``occluder`` (the name of a mesh file inside the scan directory) or ``depth_dir`` (the
+    name of a directory inside it with one ``<image stem>.npy`` depth map per camera), at most one, with ``depth_slack`` and
+    ``depth_window`` (None: the defaults of ``ops.edge_occlusion``), as ``reprojection.score_scan`` takes them: the depth
+    source of the snapping, the check and the trimming alike.  Returns the dict of ``write_support``, with the ones of ``write_trim``, ``write_dedupe`` and ``write_join`` under "trim", "dedupe" and "join"
     when there are any (and the one of ``write_snap`` under "snap"), or None -- after reporting it -- for a scan without a prediction."""
     SP._check_backend(backend)
     if layout not in LAYOUTS:
@@ -230,9 +246,18 @@ def score_scan(base_dir, dataset_dir, scan, layout="emap", detector="DexiNed", u
         cams, maps = colmap_scan_cameras(scan_dir, detector, undistort, backend, resolution)
     if "sample_resolution" in options:
         options["resolution"] = options.pop("sample_resolution")
+    if occluder is not None and depth_dir is not None:
+        raise ValueError("score_scan: give an occluder or a depth_dir, not both")
+    if occluder is not None or depth_dir is not None:   # into options: the snapping and the trimming share them below
+        if occluder is not None:
+            options["occluder"] = os.path.join(scan_dir, occluder)
+        else:
+            options["depth_maps"] = scan_depth_maps(os.path.join(scan_dir, depth_dir), cams)
+        options.update({k: v for k, v in (("depth_slack", depth_slack), ("depth_window", depth_window)) if v is not None})
+    gate_keys = ("occluder", "depth_maps", "depth_slack", "depth_window")
     source, extra = EDGES_FILE, {"scan": scan}
     if snap_options is not None:   # first: everything below starts from the snapped edges
-        shared = {k: options[k] for k in ("resolution", "edge_threshold", "thin") if k in options}
+        shared = {k: options[k] for k in ("resolution", "edge_threshold", "thin") + gate_keys if k in options}
         snap = SN.snap_edges(edge_dict, cams, maps, detector, device=device, backend=backend, **{**shared, **snap_options})
         snap["settings"].update({"layout": layout, "undistort": bool(undistort)})
         snapped = write_snap(os.path.join(base_dir, scan), snap, extra={"scan": scan})
@@ -243,7 +268,7 @@ def score_scan(base_dir, dataset_dir, scan, layout="emap", detector="DexiNed", u
     if snap_options is not None:
         out["snap"] = snapped
     if trim_options is not None:
-        shared = {k: options[k] for k in ("resolution", "edge_threshold", "thin") if k in options}
+        shared = {k: options[k] for k in ("resolution", "edge_threshold", "thin") + gate_keys if k in options}
         trim = ET.trim_edges(edge_dict, cams, maps, detector, device=device, backend=backend, **{**shared, **trim_options})
         trim["settings"].update({"layout": layout, "undistort": bool(undistort)})
         out["trim"] = write_trim(os.path.join(base_dir, scan), edge_dict, trim, extra=extra)
@@ -411,6 +436,7 @@ def parser():
     ap.add_argument("--join_reach", type=float, default=None,
                     help=f"joining: how far ahead along its tangent an end looks (default: {EJ.REACH_RESOLUTIONS:g} x "
                          f"--sample_resolution; untuned)")
+    add_depth_arguments(ap)   # --occluder / --depth_dir, --depth_slack, --depth_window: gate the check, --snap and --trim
     return ap
 
 
@@ -435,7 +461,10 @@ def main(argv=None):
                          frames_ratio=args.frames_ratio, sample_resolution=args.sample_resolution,
                          edge_threshold=args.edge_threshold, trim_options=trim, dedupe_options=dedupe,
                          join_options=join, **({"snap_options": snap} if snap is not None else {}),
-                         **({"thin": True} if args.thin else {}))
+                         **({"thin": True} if args.thin else {}),
+                         **({"occluder": args.occluder, "depth_dir": args.depth_dir, "depth_slack": args.depth_slack,
+                             "depth_window": args.depth_window}
+                            if args.occluder is not None or args.depth_dir is not None else {}))
         if out is None:
             print(f"Invalid prediction at {scan}")
             continue

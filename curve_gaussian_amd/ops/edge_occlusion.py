@@ -11,6 +11,10 @@ reference has no counterpart.
   check_depth_maps    the user's own depth maps (camera z, one float [H,W] array per camera) made ready: NaN and <= 0
                       become +inf
   read_triangle_mesh  float32 [F,3,3] from an .obj or .ply file, without trimesh or open3d
+  hidden_host         the rule for one view in numpy, the host back ends' one statement of it; gate_view_host: the
+                      projection and the rule together, what the gated 2D operators' host back ends call per view
+  ChunkDepth          a scan's depth source -- an occluder or the user's maps -- asked per chunk of views, with the
+                      settings a result records and the bytes per pixel it adds
 
 The rules are frozen in include/curvegs.h -- float64, one rounded operation at a time -- and the one occlusion rule is the
 device function ``nv_hidden`` of csrc/point_projection.h.  Two back ends: ``"gpu"``, HIP, and ``"host"``, numpy written
@@ -22,9 +26,11 @@ pixel CENTRE, which on a slanted face differs by far more than any sensible slac
 function of the image point and the sample lies inside the hull of the nine centres around it, so the maximum over them is
 at least the sample's own depth; at a silhouette one of the nine has no surface and the sample is never hidden.
 
-WHAT THIS IS NOT.  No clipping: a triangle with a vertex at or behind the camera plane is dropped whole.  The gate is the
-first consumer of the rule and the only one: the support check, trimming, oriented trimming, snapping and the edge vote do
-NOT take it yet.  Along a CONCAVE edge the surface's depth is a local maximum, so samples of a visible concave edge can be
+WHAT THIS IS NOT.  No clipping: a triangle with a vertex at or behind the camera plane is dropped whole.  The rule has
+five consumers: the score's prediction mask (``point_masks_depth``) and, opt-in, the support check, trimming, oriented
+trimming and snapping (``support_counts``, ``sample_tally``, ``oriented_tally`` and ``snap_terms`` with ``depth=``; DESIGN.md
+4.8u), which share ``hidden_host`` / ``gate_view_host`` on the host and ``ChunkDepth`` for a scan's planes.  The edge vote
+(ops/edge_seed.py) and the control-point visibility check do NOT take it.  Along a CONCAVE edge the surface's depth is a local maximum, so samples of a visible concave edge can be
 hidden by their own faces where the faces are steep; a larger slack trades that against hiding less behind thin parts.
 ``DEPTH_WINDOW`` AND ``DEPTH_SLACK`` ARE UNTUNED: only the drawn solids of scene/solid_scan.py have been checked, no real
 scan."""
@@ -64,7 +70,10 @@ def _as_tris(tris):
 
 
 def _as_depth(depth, V, height, width, what):
-    d = depth if torch.is_tensor(depth) else torch.from_numpy(np.ascontiguousarray(depth))
+    if not torch.is_tensor(depth):
+        a = np.ascontiguousarray(depth)
+        depth = torch.from_numpy(a if a.flags.writeable else a.copy())   # (a tensor cannot share a read-only array)
+    d = depth
     if d.dtype != torch.float32 or tuple(d.shape) != (V, height, width):
         raise ValueError(f"{what}: depth must be float32 [{V},{height},{width}] (got {d.dtype} {tuple(d.shape)})")
     return d.detach().contiguous()
@@ -188,6 +197,56 @@ def mesh_depth(tris, intrinsics, w2c, height, width, window=DEPTH_WINDOW, backen
     return depth_window_max(raw, window, "gpu", dev) if window else raw
 
 
+# ------------------------------------------------------------------------------------------------ the rule on the host
+def hidden_host(c2, u, v, keep, plane, slack):
+    """``nv_hidden`` in numpy for one view, the host back ends' one statement of the rule: bool [P], True where a sample that
+    the projection keeps (``keep`` bool [P]; only those are looked up) has c2 > float64(plane[floor(v)][floor(u)]) + slack.
+    c2, u, v float64 [P] as the projection forms them; plane float32 [H,W].  A NaN depth hides nothing."""
+    hid = np.zeros(keep.shape, bool)
+    idx = np.flatnonzero(keep)
+    row, col = np.floor(v[idx]).astype(np.int64), np.floor(u[idx]).astype(np.int64)
+    with np.errstate(all="ignore"):
+        hid[idx] = c2[idx] > plane[row, col].astype(np.float64) + slack
+    return hid
+
+
+def gate_view_host(points, K, M, plane, slack):
+    """One view of a gated operator on the host: (u, v, seen, hidden), float64 [P] and bool [P].  points float32 [P,3]; K [4],
+    M [12]; plane float32 [H,W].  The projection is ``cgs_project_points`` operation for operation; ``seen`` are the samples
+    it keeps that ``hidden_host`` does not hide, ``hidden`` those it does: seen | hidden is the ungated operators' keep."""
+    H, W = plane.shape
+    c2, u, v = _camera_points_host(np.asarray(points, np.float32).reshape(-1, 3).astype(np.float64), K, M)
+    with np.errstate(all="ignore"):
+        keep = ~(c2 <= 0.0) & (u >= 0.0) & (u < float(W)) & (v >= 0.0) & (v < float(H))   # NaN fails the image test
+    hid = hidden_host(c2, u, v, keep, plane, slack)
+    return u, v, keep & ~hid, hid
+
+
+def operator_depth(what, depth, slack, V, height, width, backend, dev=None):
+    """The ``depth`` and ``slack`` arguments of a gated operator, checked: (float32 [V,height,width] -- a numpy array for
+    ``backend="host"``, a tensor on ``dev`` otherwise --, the slack as a float)."""
+    slack = _check_slack(what, slack)
+    d = _as_depth(depth, V, height, width, what)
+    if backend == "host":
+        if d.is_cuda:
+            raise ValueError(f"{what}: backend='host' takes host arrays and CPU tensors")
+        return d.numpy(), slack
+    if d.is_cuda and d.device != dev:
+        raise L.CurveGSError(f"{what}: depth is on {d.device}, the other tensors on {dev}: all tensors must be on one device")
+    return d.to(dev), slack
+
+
+def check_hidden_out(what, hidden_out, depth, P):
+    """The ``hidden_out`` argument of a per-sample gated operator: None, or a contiguous int32 [P] tensor (needs ``depth``)."""
+    if hidden_out is None:
+        return
+    if depth is None:
+        raise ValueError(f"{what}: hidden_out needs depth")
+    if (not torch.is_tensor(hidden_out) or hidden_out.dtype != torch.int32 or tuple(hidden_out.shape) != (P,)
+            or not hidden_out.is_contiguous()):
+        raise ValueError(f"{what}: hidden_out must be a contiguous int32 [{P}] tensor")
+
+
 # ------------------------------------------------------------------------------------------------ the gated mask
 def point_masks_depth(points, intrinsics, w2c, depth, slack=DEPTH_SLACK, backend="gpu", device=None, return_counts=False):
     """uint8 [V,H,W]: ``point_masks`` of the samples that are not hidden behind ``depth`` (float32 [V,H,W], camera z, +inf =
@@ -215,12 +274,10 @@ def point_masks_depth(points, intrinsics, w2c, depth, slack=DEPTH_SLACK, backend
             c2, u, v = _camera_points_host(P64, K[i], M[i])
             with np.errstate(all="ignore"):
                 seen = ~(c2 <= 0.0) & (u >= 0.0) & (u < float(width)) & (v >= 0.0) & (v < float(height))
-            c2, u, v = c2[seen], u[seen], v[seen]
-            row, col = np.floor(v).astype(np.int64), np.floor(u).astype(np.int64)
-            with np.errstate(all="ignore"):
-                hid = c2 > planes[i][row, col].astype(np.float64) + slack
-            mask[i, row[~hid], col[~hid]] = 1
-            kept[i], hidden[i] = np.count_nonzero(~hid), np.count_nonzero(hid)
+            hid = hidden_host(c2, u, v, seen, planes[i], slack)
+            vis = seen & ~hid
+            mask[i, np.floor(v[vis]).astype(np.int64), np.floor(u[vis]).astype(np.int64)] = 1
+            kept[i], hidden[i] = np.count_nonzero(vis), np.count_nonzero(hid)
         mask = torch.from_numpy(mask)
         return (mask, torch.from_numpy(kept), torch.from_numpy(hidden)) if return_counts else mask
     dev = ES._device_for([pts, d], "point_masks_depth", device)
@@ -256,6 +313,67 @@ def check_depth_maps(cameras, depth_maps):
             m[~(m > 0.0)] = np.inf
         out.append(m)
     return out
+
+
+# ------------------------------------------------------------------------------------------------ a scan's depth source
+def check_one_depth_source(what, occluder, depth_maps):
+    if occluder is not None and depth_maps is not None:
+        raise ValueError(f"{what}: give an occluder or depth_maps, not both")
+
+
+class ChunkDepth:
+    """The depth source of a scan-level operator (``score_edges``, ``edge_support``, ``trim_edges``, ``snap_edges``), built
+    once and asked per chunk of views.  ``occluder``: float32 [F,3,3] triangles or the path of an .obj / .ply mesh, rendered
+    into every chunk's planes by ``mesh_depth``; ``depth_maps``: one float [H,W] array of camera z per camera
+    (``check_depth_maps``).  At most one of the two; with neither ``gated`` is False and nothing else may be asked.  Either
+    way a chunk's planes go through the window maximum of radius ``depth_window``; ``depth_slack`` is what the operators
+    then hold a sample's depth against.  Nothing is kept between chunks: ``planes`` builds what one chunk needs.
+
+      gated             whether there is a depth source
+      bytes_per_pixel   what a chunk's working set grows by: ``edge_score.DEPTH_BYTES_PER_PIXEL`` (the float32 plane and
+                        its window maximum), 0 when not gated
+      slack, window     the checked settings
+      to(backend, dev)  where the planes are built; uploads the triangles once
+      planes(...)       float32 [len(sel),H,W] of a chunk of ``view_chunks``, on the back end's device
+      settings()        the keys a result records: "occluder" (the path, or true) or "depth_maps": true, "depth_slack",
+                        "depth_window"; {} when not gated"""
+
+    def __init__(self, what, cameras, occluder=None, depth_maps=None, depth_slack=DEPTH_SLACK, depth_window=DEPTH_WINDOW):
+        check_one_depth_source(what, occluder, depth_maps)
+        self.what = what
+        self.gated = occluder is not None or depth_maps is not None
+        self.bytes_per_pixel = ES.DEPTH_BYTES_PER_PIXEL if self.gated else 0
+        self.slack, self.window = depth_slack, depth_window
+        self.occluder, self.tris, self.maps = occluder, None, None
+        self.backend, self.device = "host", None
+        if self.gated:
+            self.slack = _check_slack(what, depth_slack)
+            self.window = _check_window(what, depth_window)
+        if occluder is not None:
+            self.tris = _as_tris(read_triangle_mesh(occluder) if isinstance(occluder, (str, os.PathLike)) else occluder)
+        if depth_maps is not None:
+            self.maps = check_depth_maps(cameras, depth_maps)
+
+    def to(self, backend, device=None):
+        self.backend, self.device = backend, device
+        if self.tris is not None and backend == "gpu":
+            self.tris = self.tris.to(device)
+        return self
+
+    def planes(self, H, W, sel, intr, w2c):
+        if self.tris is not None:
+            return mesh_depth(self.tris, intr, w2c, H, W, self.window, backend=self.backend, device=self.device)
+        return depth_window_max(np.stack([self.maps[v] for v in sel]), self.window, backend=self.backend, device=self.device)
+
+    def settings(self):
+        if not self.gated:
+            return {}
+        if self.occluder is not None:
+            out = {"occluder": os.fspath(self.occluder) if isinstance(self.occluder, (str, os.PathLike)) else True}
+        else:
+            out = {"depth_maps": True}
+        out.update({"depth_slack": self.slack, "depth_window": self.window})
+        return out
 
 
 # ------------------------------------------------------------------------------------------------ mesh files

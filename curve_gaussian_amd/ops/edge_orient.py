@@ -45,7 +45,9 @@ orientations nearer than 22.5 degrees and refuses every pair further than 45.
 KNOWN LIMITS.  The orientation comes from a BINARY MASK in a 7 x 7 window: a stroke wider than about 3 pixels is isotropic
 there, its pixels get 0xFF and the test falls back to the plain distance test -- thin such maps first (``thin=True``,
 ops/edge_thin.py).  Corners and junctions accept everything, so a chord still collects support where it crosses one.  There
-is no depth, as in ops/edge_trim.py.  THE DEFAULTS (R = 3, coherence 0.5, spread 1) ARE UNTUNED: drawn fixtures only
+is no depth unless the caller gives one: ``oriented_tally(depth=...)`` (``trim_edges(oriented=True, occluder=...)``) gates THE
+SAMPLE by the one rule of ops/edge_occlusion.py -- a view that hides it does not see it -- while its partner gives a
+direction only and is never held against the depth (``cgs_sample_support_oriented_depth``).  THE DEFAULTS (R = 3, coherence 0.5, spread 1) ARE UNTUNED: drawn fixtures only
 (tests/edge_orient_cases.py), unmeasured on ABC or any real detector output.
 
 Two back ends: ``"gpu"``, HIP, and ``"host"``, numpy -- the same rule, so they agree on every bit."""
@@ -53,6 +55,7 @@ import numpy as np
 import torch
 
 from .. import _lib as L
+from . import edge_occlusion as EO
 from . import edge_score as ES
 from . import edge_support as SP
 
@@ -138,7 +141,8 @@ def oriented_near_host(code, tol2):
     return out
 
 
-def _tally_host(pts, partner, K, M, near, spread, out):
+def _tally_host(pts, partner, K, M, near, spread, out, depth=None, slack=0.0, hidden=None):
+    """``depth`` float32 [V,H,W] or None; ``hidden`` int32 [P] or None, added to when there is a depth."""
     P = pts.shape[0]
     H, W = near.shape[1], near.shape[2]
     i = np.arange(P, dtype=np.int64)
@@ -146,7 +150,12 @@ def _tally_host(pts, partner, K, M, near, spread, out):
     paired = (j != i) & (j >= 0) & (j < P)
     other = pts[np.where(paired, j, i)]
     for v in range(K.shape[0]):   # one view at a time: [P] temporaries
-        u, w, keep = (x[0] for x in ES.project_points_host(pts, K[v:v + 1], M[v:v + 1], H, W))
+        if depth is None:
+            u, w, keep = (x[0] for x in ES.project_points_host(pts, K[v:v + 1], M[v:v + 1], H, W))
+        else:   # the sample is gated; the partner below is not
+            u, w, keep, hid = EO.gate_view_host(pts, K[v], M[v], depth[v], slack)
+            if hidden is not None:
+                hidden += hid
         up, wp, keep_p = (x[0] for x in ES.project_points_host(other, K[v:v + 1], M[v:v + 1], H, W))
         with np.errstate(all="ignore"):   # a sample or a partner that is not seen may project to anything
             dx, dy = up - u, wp - w
@@ -242,7 +251,8 @@ def _near(near, V):
     return t.contiguous()
 
 
-def oriented_tally(points, partner, intrinsics, w2c, near, spread=SPREAD, backend="gpu", device=None, out=None):
+def oriented_tally(points, partner, intrinsics, w2c, near, spread=SPREAD, backend="gpu", device=None, out=None, depth=None,
+                   slack=EO.DEPTH_SLACK, hidden_out=None):
     """int32 [P,2].  points float32 [P,3]; partner int32 [P] (``sample_partners``; a value outside [0, P) or equal to its
     index means no partner); intrinsics [V,4] = (fx, fy, cx, cy) and w2c [V,3,4] float64 host arrays or tensors; near uint8
     [V,H,W], ``oriented_near`` of every view; ``spread`` in [0, 4].  tally[i,0] = the views in which ``cgs_project_points``
@@ -254,7 +264,12 @@ def oriented_tally(points, partner, intrinsics, w2c, near, spread=SPREAD, backen
 
     ``backend="gpu"``: ``cgs_sample_support_oriented``.  near must be on a GPU (CurveGSError otherwise), ``device``, when
     given, must be that GPU, and so must the device of ``out`` and of points and partner that are on a GPU; those on the host
-    are uploaded.  The result stays on the device.  ``backend="host"``: numpy, CPU tensors."""
+    are uploaded.  The result stays on the device.  ``backend="host"``: numpy, CPU tensors.
+
+    ``depth`` (None: no gate, the call above and nothing else), ``slack`` and ``hidden_out`` as ``edge_trim.sample_tally``
+    takes them (``cgs_sample_support_oriented_depth``): a view that keeps sample i and whose depth plane hides it counts in
+    neither column and is ADDED to hidden_out[i].  ONLY THE SAMPLE IS GATED: its partner is projected by the projection rule
+    alone and gives its direction whether or not a surface lies in front of it."""
     _check_backend(backend)
     spread = _spread(spread)
     pts = SP._points(points)
@@ -265,12 +280,19 @@ def oriented_tally(points, partner, intrinsics, w2c, near, spread=SPREAD, backen
     if out is not None:
         if not torch.is_tensor(out) or out.dtype != torch.int32 or tuple(out.shape) != (P, 2) or not out.is_contiguous():
             raise ValueError(f"oriented_tally: out must be a contiguous int32 [{P},2] tensor")
+    EO.check_hidden_out("oriented_tally", hidden_out, depth, P)
     if backend == "host":
-        if near.is_cuda or pts.is_cuda or partner.is_cuda or (out is not None and out.is_cuda):
+        if (near.is_cuda or pts.is_cuda or partner.is_cuda or (out is not None and out.is_cuda)
+                or (hidden_out is not None and hidden_out.is_cuda)):
             raise ValueError("oriented_tally: backend='host' takes host arrays and CPU tensors")
         if out is None:
             out = torch.zeros((P, 2), dtype=torch.int32)
-        _tally_host(pts.numpy(), partner.numpy(), K, M, near.numpy(), spread, out.numpy())
+        if depth is None:
+            _tally_host(pts.numpy(), partner.numpy(), K, M, near.numpy(), spread, out.numpy())
+            return out
+        depth, slack = EO.operator_depth("oriented_tally", depth, slack, V, int(near.shape[1]), int(near.shape[2]), "host")
+        _tally_host(pts.numpy(), partner.numpy(), K, M, near.numpy(), spread, out.numpy(), depth, slack,
+                    None if hidden_out is None else hidden_out.numpy())
         return out
     L.require_gpu_tensor(near, "oriented_tally: near")
     dev = near.device
@@ -281,14 +303,27 @@ def oriented_tally(points, partner, intrinsics, w2c, near, spread=SPREAD, backen
             raise L.CurveGSError(f"oriented_tally: {name} are on {t.device}, near on {dev}: all tensors must be on one device")
     if out is not None and out.device != dev:
         raise L.CurveGSError(f"oriented_tally: out is on {out.device}, near on {dev}: all tensors must be on one device")
+    if hidden_out is not None and hidden_out.device != dev:
+        raise L.CurveGSError(f"oriented_tally: hidden_out is on {hidden_out.device}, near on {dev}: all tensors must be on one "
+                             "device")
     with L.device_guard(dev):
         pts, partner = pts.to(dev).contiguous(), partner.to(dev).contiguous()
         if out is None:
             out = torch.zeros((P, 2), dtype=torch.int32, device=dev)
+        if depth is not None:
+            depth, slack = EO.operator_depth("oriented_tally", depth, slack, V, int(near.shape[1]), int(near.shape[2]), "gpu",
+                                             dev)
         if P > 0 and V > 0:
             Kd, Md = ES.cameras_on(dev, K, M)
-            rc = L.load().cgs_sample_support_oriented(P, L.ptr(pts), L.ptr(partner), V, L.ptr(Kd), L.ptr(Md),
-                                                      int(near.shape[1]), int(near.shape[2]), L.ptr(near), spread, L.ptr(out),
-                                                      L.raw_stream(dev))
-            L.check(rc, "cgs_sample_support_oriented")
+            if depth is None:
+                rc = L.load().cgs_sample_support_oriented(P, L.ptr(pts), L.ptr(partner), V, L.ptr(Kd), L.ptr(Md),
+                                                          int(near.shape[1]), int(near.shape[2]), L.ptr(near), spread,
+                                                          L.ptr(out), L.raw_stream(dev))
+                L.check(rc, "cgs_sample_support_oriented")
+            else:
+                rc = L.load().cgs_sample_support_oriented_depth(P, L.ptr(pts), L.ptr(partner), V, L.ptr(Kd), L.ptr(Md),
+                                                                int(near.shape[1]), int(near.shape[2]), L.ptr(near), spread,
+                                                                L.ptr(depth), slack, L.ptr(out), L.ptr(hidden_out),
+                                                                L.raw_stream(dev))
+                L.check(rc, "cgs_sample_support_oriented_depth")
     return out

@@ -28,7 +28,14 @@ edge's length -- that is trimming's job.  The refit is a linear least-squares fi
 targets B(t) P + delta at the fixed parameters np.linspace(0, 1, n) of ``sample_edges`` (Bernstein basis for a curve,
 (1 - t, t) for a line: a line stays a line).
 
-KNOWN LIMITS.  There is no depth, as in ops/edge_support.py.  A sample inside the capture radius of the WRONG edge is pulled
+DEPTH (opt-in).  Without a depth source a sample hidden behind a surface is pulled onto whatever front
+edge it projects within ``capture_px`` of.  With ``depth`` (``snap_terms``) or ``occluder`` / ``depth_maps``
+(``snap_edges``) a view whose depth plane hides the sample -- the one rule of ops/edge_occlusion.py -- contributes no term
+and no view: it is left right after the projection's verdict, before the footprint test, and for every other view the
+floating-point sequence is unchanged.  Limits as ops/edge_occlusion.py states them: untuned, drawn solids only, concave
+edges, no near-plane clipping.
+
+KNOWN LIMITS.  A sample inside the capture radius of the WRONG edge is pulled
 to it: at crossings, and along a parallel edge closer than ``capture_px``.  Snapping is not a filter: a bogus chord that
 passes the gate is moved too (the gate asks that 0.8 of an edge's samples be constrained; see DESIGN.md 4.8s for what the
 drawn scan's chords read).  A shared end with a member that came back unchanged stays at the old point, off the moved
@@ -45,6 +52,7 @@ import torch
 from .. import _lib as L
 from ..edge_extraction.para_edge import EDGE_MAX_THRESHOLD, EDGE_VISIBILITY_FRAMES_RATIO
 from ..edge_extraction.reprojection import SAMPLE_RESOLUTION
+from . import edge_occlusion as EO
 from . import edge_score as ES
 from . import edge_support as SP
 from .edge_thin import thin_masks
@@ -78,7 +86,8 @@ def distance_table(cap2):
     return np.sqrt(np.arange(cap2 + 1, dtype=np.float64))
 
 
-def _terms_host(pts, K, M, d2, cap2, lut, terms, views):
+def _terms_host(pts, K, M, d2, cap2, lut, terms, views, depth=None, slack=0.0, hidden=None):
+    """``depth`` float32 [V,H,W] or None; ``hidden`` int32 [P] or None, added to when there is a depth."""
     H, W = d2.shape[1], d2.shape[2]
     P64 = pts.astype(np.float64)
     X, Y, Z = P64[:, 0], P64[:, 1], P64[:, 2]
@@ -91,6 +100,11 @@ def _terms_host(pts, K, M, d2, cap2, lut, terms, views):
             x, y = c0 / c2, c1 / c2
             u, w = fx * x + cx, fy * y + cy
             keep = ~(c2 <= 0.0) & (u >= 0.0) & (u < float(W)) & (w >= 0.0) & (w < float(H))   # NaN fails the image test
+            if depth is not None:   # right after the projection's verdict: a hidden pair gives no term and no view
+                hid = EO.hidden_host(c2, u, w, keep, depth[v], slack)
+                keep &= ~hid
+                if hidden is not None:
+                    hidden += hid
             a, b = u - 0.5, w - 0.5
             fj, fi = np.floor(a), np.floor(b)
             keep &= (fj >= 0.0) & (fj + 1.0 <= W - 1.0) & (fi >= 0.0) & (fi + 1.0 <= H - 1.0)
@@ -124,7 +138,8 @@ def _check_out(out, P):
     return out[0], out[1]
 
 
-def snap_terms(points, intrinsics, w2c, d2, capture_px, backend="gpu", device=None, out=None):
+def snap_terms(points, intrinsics, w2c, d2, capture_px, backend="gpu", device=None, out=None, depth=None,
+               slack=EO.DEPTH_SLACK, hidden_out=None):
     """(terms float64 [P,10], views int32 [P]).  points float32 [P,3]; intrinsics [V,4] = (fx, fy, cx, cy) and w2c [V,3,4]
     float64 host arrays or tensors; d2 int32 [V,H,W], ``edt_squared`` of every view's detected mask -- the arguments of
     ``sample_tally`` -- and ``capture_px``, whose square, rounded down, lies in [1, 64].  A row of terms is (Axx, Axy, Axz,
@@ -136,7 +151,12 @@ def snap_terms(points, intrinsics, w2c, d2, capture_px, backend="gpu", device=No
 
     ``backend="gpu"``: ``cgs_sample_snap_terms``.  d2 must be on a GPU (CurveGSError otherwise), ``device``, when given, must
     be that GPU, and so must the device of ``out`` and of points that are on a GPU; points on the host are uploaded.  The
-    result stays on the device.  ``backend="host"``: numpy, CPU tensors."""
+    result stays on the device.  ``backend="host"``: numpy, CPU tensors.
+
+    ``depth`` (None: no gate, the call above and nothing else), ``slack`` and ``hidden_out`` as ``edge_trim.sample_tally``
+    takes them (``cgs_sample_snap_terms_depth``): a view that keeps sample i and whose depth plane hides it adds no term and
+    no view and is ADDED to hidden_out[i], whether or not its footprint would have captured the sample; the sums of the other
+    views are bit for bit what they are without the gate."""
     SP._check_backend(backend)
     cap2 = capture_squared(capture_px)
     pts = SP._points(points)
@@ -146,12 +166,19 @@ def snap_terms(points, intrinsics, w2c, d2, capture_px, backend="gpu", device=No
     if out is not None:
         terms, views = _check_out(out, P)
     lut = distance_table(cap2)
+    EO.check_hidden_out("snap_terms", hidden_out, depth, P)
     if backend == "host":
-        if d2.is_cuda or pts.is_cuda or (out is not None and (terms.is_cuda or views.is_cuda)):
+        if (d2.is_cuda or pts.is_cuda or (out is not None and (terms.is_cuda or views.is_cuda))
+                or (hidden_out is not None and hidden_out.is_cuda)):
             raise ValueError("snap_terms: backend='host' takes host arrays and CPU tensors")
         if out is None:
             terms, views = torch.zeros((P, TERMS), dtype=torch.float64), torch.zeros((P,), dtype=torch.int32)
-        _terms_host(pts.numpy(), K, M, d2.numpy(), cap2, lut, terms.numpy(), views.numpy())
+        if depth is None:
+            _terms_host(pts.numpy(), K, M, d2.numpy(), cap2, lut, terms.numpy(), views.numpy())
+            return terms, views
+        depth, slack = EO.operator_depth("snap_terms", depth, slack, V, int(d2.shape[1]), int(d2.shape[2]), "host")
+        _terms_host(pts.numpy(), K, M, d2.numpy(), cap2, lut, terms.numpy(), views.numpy(), depth, slack,
+                    None if hidden_out is None else hidden_out.numpy())
         return terms, views
     L.require_gpu_tensor(d2, "snap_terms: d2")
     dev = d2.device
@@ -162,17 +189,29 @@ def snap_terms(points, intrinsics, w2c, d2, capture_px, backend="gpu", device=No
     if out is not None and (terms.device != dev or views.device != dev):
         raise L.CurveGSError(f"snap_terms: out is on {terms.device} and {views.device}, d2 on {dev}: all tensors must be on "
                              "one device")
+    if hidden_out is not None and hidden_out.device != dev:
+        raise L.CurveGSError(f"snap_terms: hidden_out is on {hidden_out.device}, d2 on {dev}: all tensors must be on one "
+                             "device")
     with L.device_guard(dev):
         pts = pts.to(dev).contiguous()
         if out is None:
             terms = torch.zeros((P, TERMS), dtype=torch.float64, device=dev)
             views = torch.zeros((P,), dtype=torch.int32, device=dev)
+        if depth is not None:
+            depth, slack = EO.operator_depth("snap_terms", depth, slack, V, int(d2.shape[1]), int(d2.shape[2]), "gpu", dev)
         if P > 0 and V > 0:
             lut_d = torch.from_numpy(lut).to(dev)
             Kd, Md = ES.cameras_on(dev, K, M)
-            rc = L.load().cgs_sample_snap_terms(P, L.ptr(pts), V, L.ptr(Kd), L.ptr(Md), int(d2.shape[1]), int(d2.shape[2]),
-                                                L.ptr(d2), cap2, L.ptr(lut_d), L.ptr(terms), L.ptr(views), L.raw_stream(dev))
-            L.check(rc, "cgs_sample_snap_terms")
+            if depth is None:
+                rc = L.load().cgs_sample_snap_terms(P, L.ptr(pts), V, L.ptr(Kd), L.ptr(Md), int(d2.shape[1]),
+                                                    int(d2.shape[2]), L.ptr(d2), cap2, L.ptr(lut_d), L.ptr(terms),
+                                                    L.ptr(views), L.raw_stream(dev))
+                L.check(rc, "cgs_sample_snap_terms")
+            else:
+                rc = L.load().cgs_sample_snap_terms_depth(P, L.ptr(pts), V, L.ptr(Kd), L.ptr(Md), int(d2.shape[1]),
+                                                          int(d2.shape[2]), L.ptr(d2), cap2, L.ptr(lut_d), L.ptr(depth), slack,
+                                                          L.ptr(terms), L.ptr(views), L.ptr(hidden_out), L.raw_stream(dev))
+                L.check(rc, "cgs_sample_snap_terms_depth")
     return terms, views
 
 
@@ -314,7 +353,8 @@ def _number(x):
 def snap_edges(edge_dict, cameras, edge_maps_u8, detector, resolution=SAMPLE_RESOLUTION, capture_px=CAPTURE_PX,
                iterations=ITERATIONS, frames_ratio=EDGE_VISIBILITY_FRAMES_RATIO, min_constrained=MIN_CONSTRAINED,
                damping=DAMPING, step_cap=None, edge_threshold=EDGE_MAX_THRESHOLD, backend="gpu", device=None,
-               budget_bytes=None, thin=False):
+               budget_bytes=None, thin=False, occluder=None, depth_maps=None, depth_slack=EO.DEPTH_SLACK,
+               depth_window=EO.DEPTH_WINDOW):
     """edge_dict, cameras, edge_maps_u8, detector, resolution, edge_threshold, budget_bytes and thin as ``trim_edges`` takes
     them, and the same walk over the views: ``view_chunks``, ``detected_masks``, the optional ``thin_masks``, ``edt_squared``
     (the same seven bytes per pixel), then one ``snap_terms`` call per chunk into one pair of sums.  When all views fit one
@@ -330,8 +370,18 @@ def snap_edges(edge_dict, cameras, edge_maps_u8, detector, resolution=SAMPLE_RES
              in pixels -- is lower in the last pass than in the first; one that fails is returned bit for bit.
       SHARED ENDS  end control points that were bitwise equal before are bitwise equal after: the mean of their members'
              snapped ends, or the old point if any member's edge came back unchanged.
-    THE DEFAULTS ARE UNTUNED (the drawn test scan only), there is no depth, a sample within ``capture_px`` of the wrong
-    edge is pulled to it, and this is not a filter: see the module docstring.
+    THE DEFAULTS ARE UNTUNED (the drawn test scan only), a sample within ``capture_px`` of the wrong edge is pulled to it,
+    and this is not a filter: see the module docstring.
+
+    Depth (opt-in; ``occluder``, ``depth_maps``, ``depth_slack`` and ``depth_window`` with the meaning and the checks of
+    ``score_edges`` and ``edge_support``, at most one of the first two): a view whose depth plane hides a sample gives it
+    no term and no view (``snap_terms(depth=...)``).  The planes are built PER CHUNK inside the walk over the views, like
+    the transform, in every pass (``edge_occlusion.ChunkDepth``, 8 bytes per pixel more); only when all views fit one chunk
+    are they, like the transform, built once and kept.  The result then also holds "hidden": int32 [P] numpy array, the
+    views that hide every sample of the edges AS THEY CAME IN (the first pass), every record of "edges" holds
+    "hidden_views", their sum over the edge's samples, and "settings" the keys ``score_edges`` records.  With neither,
+    nothing changes: no key is added.  Untuned, drawn solids only, concave edges can be hidden by their own faces, no
+    near-plane clipping (ops/edge_occlusion.py).
 
     Returns {"edge_dict": the edges in the layout of ``get_parametric_edge`` (curves [Nc,4,3], lines [Nl,6], as lists; an
     unmoved edge holds the floats it came with), "edges": one record per edge -- kind, index within its kind, samples,
@@ -348,6 +398,7 @@ def snap_edges(edge_dict, cameras, edge_maps_u8, detector, resolution=SAMPLE_RES
     lut = detected_lut(detector, edge_threshold)
     cameras, maps = check_edge_maps("snap_edges", cameras, edge_maps_u8)
     budget = check_budget("snap_edges", budget_bytes, BYTE_BUDGET)
+    source = EO.ChunkDepth("snap_edges", cameras, occluder, depth_maps, depth_slack, depth_window)
     old_c, old_l = SP._edge_arrays(edge_dict["curves_ctl_pts"], edge_dict["lines_end_pts"])
     pts0, off = SP.sample_edges(old_c, old_l, resolution)
     off = off.astype(np.int64)
@@ -355,7 +406,8 @@ def snap_edges(edge_dict, cameras, edge_maps_u8, detector, resolution=SAMPLE_RES
     E, Nc, P, V = len(sizes), len(old_c), int(off[-1]), len(cameras)
     if backend == "gpu":
         device = ES._device_for([], "snap_edges", device)
-    chunks = list(view_chunks(cameras, BYTES_PER_PIXEL, budget))
+    source.to(backend, device)
+    chunks = list(view_chunks(cameras, BYTES_PER_PIXEL + source.bytes_per_pixel, budget))
 
     def transform(sel):
         det = detected_masks(lut, maps, sel)
@@ -364,15 +416,26 @@ def snap_edges(edge_dict, cameras, edge_maps_u8, detector, resolution=SAMPLE_RES
         return ES.edt_squared(det, backend=backend, device=device)
 
     kept = transform(chunks[0][2]) if len(chunks) == 1 else None   # one chunk: the transform is computed once
+    kept_depth = source.planes(*chunks[0]) if source.gated and len(chunks) == 1 else None   # and so are the depth planes
+    hidden_first = []   # the hidden counts of the first pass
 
     def measure(pts32):
         pts_b = torch.from_numpy(pts32).to(device) if backend == "gpu" else pts32
         out = (torch.zeros((P, TERMS), dtype=torch.float64, device=device if backend == "gpu" else None),
                torch.zeros((P,), dtype=torch.int32, device=device if backend == "gpu" else None))
-        for _, _, sel, intr, w2c in chunks:
+        hid = torch.zeros((P,), dtype=torch.int32, device=out[1].device) if source.gated and not hidden_first else None
+        for H, W, sel, intr, w2c in chunks:
             d2 = kept if kept is not None else transform(sel)
-            snap_terms(pts_b, intr, w2c, d2, capture_px, backend=backend, out=out)
+            if source.gated:   # the planes of this chunk, built inside the walk like the transform
+                depth = kept_depth if kept_depth is not None else source.planes(H, W, sel, intr, w2c)
+                snap_terms(pts_b, intr, w2c, d2, capture_px, backend=backend, out=out, depth=depth, slack=source.slack,
+                           hidden_out=hid)
+                del depth
+            else:
+                snap_terms(pts_b, intr, w2c, d2, capture_px, backend=backend, out=out)
             del d2
+        if hid is not None:
+            hidden_first.append(hid.cpu().numpy())
         return out[0].cpu().numpy(), out[1].cpu().numpy()
 
     cur_c, cur_l = old_c.copy(), old_l.copy()
@@ -418,11 +481,17 @@ def snap_edges(edge_dict, cameras, edge_maps_u8, detector, resolution=SAMPLE_RES
                         "rms_before": _number(rms_before[e]), "rms_after": _number(rms_after[e]) if gate[e] else None,
                         "mean_displacement": float(seg.mean()) if seg.size else 0.0,
                         "max_displacement": float(seg.max()) if seg.size else 0.0})
+        if source.gated:
+            records[-1]["hidden_views"] = int(hidden_first[0][off[e]:off[e + 1]].sum())
     settings = {"detector": detector, "resolution": resolution, "capture_px": float(capture_px), "iterations": iterations,
                 "frames_ratio": frames_ratio, "min_constrained": min_constrained, "damping": damping, "step_cap": step_cap,
                 "edge_threshold": float(edge_threshold), "backend": backend, "views": V, "points": P,
                 "chunks": len(chunks)}
     if thin:
         settings["thin"] = True
-    return {"edge_dict": {"curves_ctl_pts": new_c.tolist(), "lines_end_pts": new_l.reshape(-1, 6).tolist()},
-            "edges": records, "moved": moved, "settings": settings}
+    settings.update(source.settings())
+    out = {"edge_dict": {"curves_ctl_pts": new_c.tolist(), "lines_end_pts": new_l.reshape(-1, 6).tolist()},
+           "edges": records, "moved": moved, "settings": settings}
+    if source.gated:
+        out["hidden"] = hidden_first[0]
+    return out

@@ -21,8 +21,16 @@ The verdict, frozen; n = the number of samples of edge e, seen 
   share[e][t]                 = sum_v near / sum_v seen over all views, NaN when nothing is seen (reported, not used)
 The thresholds are built in float64 on the host, as ``edge_seed.need_table`` builds them.
 
-KNOWN LIMITS.  There is no depth: an edge hidden behind a surface in most views loses its support there, which is why the
-rule counts supporting FRAMES and does not pool the samples of all views.  A thick detector response inflates support: a
+DEPTH (opt-in).  Without a depth source an edge hidden behind a surface in most views loses its support
+there, which is why the rule counts supporting FRAMES and does not pool the samples of all views -- and a hidden edge
+collects support it cannot have from the front edges it projects behind.  With ``depth`` (``support_counts``) or
+``occluder`` / ``depth_maps`` (``edge_support``) a (sample, view) pair that the view's depth plane hides -- the one rule of
+ops/edge_occlusion.py, ``nv_hidden`` -- counts as NOT SEEN and is tallied in "hidden" instead.  The verdict's formulas do
+not change, only their inputs: a view whose VISIBLE samples number fewer than ceil(min_visible * n) does not see the edge.
+The gate's limits are those of ops/edge_occlusion.py: untuned window and slack, checked on the drawn solids of
+scene/solid_scan.py only; a concave edge can be hidden by its own faces; no near-plane clipping.
+
+KNOWN LIMITS.  A thick detector response inflates support: a
 chord across a wide response lies "on" it (``thin=True`` thins the detected masks first: ops/edge_thin.py, DESIGN.md 4.8n;
 untuned, checked on dilated drawn maps only).  THE DEFAULTS OF ``edge_support`` ARE UNTUNED: one run on the drawn test scan
 (tests/edge_support_cases.py), no real scan.
@@ -37,6 +45,7 @@ from .. import _lib as L
 from ..edge_extraction.para_edge import EDGE_MAX_THRESHOLD, EDGE_VISIBILITY_FRAMES_RATIO
 from ..edge_extraction.reprojection import SAMPLE_RESOLUTION
 from ..scene.dataset_io import bezier_curve_length
+from . import edge_occlusion as EO
 from . import edge_score as ES
 from .edge_thin import thin_masks
 from .view_chunks import check_budget, check_edge_maps, detected_lut, detected_masks, view_chunks
@@ -134,7 +143,8 @@ def _d2(d2, V):
     return t.contiguous()
 
 
-def _counts_host(pts, off, K, M, d2, tol2):
+def _counts_host(pts, off, K, M, d2, tol2, depth=None, slack=0.0, hidden=None):
+    """``depth`` float32 [V,H,W] or None; ``hidden`` int32 [E,V] or None, written when there is a depth."""
     E, V, T = off.size - 1, K.shape[0], len(tol2)
     H, W = d2.shape[1], d2.shape[2]
     lo, hi = off[:-1].astype(np.int64), off[1:].astype(np.int64)
@@ -142,10 +152,15 @@ def _counts_host(pts, off, K, M, d2, tol2):
     flags = np.empty((1 + T, pts.shape[0]), np.int64)
     run = np.zeros((1 + T, pts.shape[0] + 1), np.int64)
     for v in range(V):   # one view at a time: [P] temporaries
-        u, w, keep = ES.project_points_host(pts, K[v:v + 1], M[v:v + 1], H, W)
-        keep = keep[0]
+        if depth is None:
+            u, w, keep = (x[0] for x in ES.project_points_host(pts, K[v:v + 1], M[v:v + 1], H, W))
+        else:   # a hidden sample counts as not seen
+            u, w, keep, hid = EO.gate_view_host(pts, K[v], M[v], depth[v], slack)
+            if hidden is not None:
+                hrun = np.concatenate([[0], np.cumsum(hid, dtype=np.int64)])
+                hidden[:, v] = hrun[hi] - hrun[lo]
         d = np.full(pts.shape[0], ES.EDT_INF, np.int64)
-        d[keep] = d2[v][np.floor(w[0][keep]).astype(np.int64), np.floor(u[0][keep]).astype(np.int64)]
+        d[keep] = d2[v][np.floor(w[keep]).astype(np.int64), np.floor(u[keep]).astype(np.int64)]
         flags[0] = keep
         for t, t2 in enumerate(tol2):
             flags[1 + t] = keep & (d <= t2)
@@ -154,7 +169,8 @@ def _counts_host(pts, off, K, M, d2, tol2):
     return out
 
 
-def support_counts(points, offsets, intrinsics, w2c, d2, tolerances_px, backend="gpu", device=None):
+def support_counts(points, offsets, intrinsics, w2c, d2, tolerances_px, backend="gpu", device=None, depth=None,
+                   slack=EO.DEPTH_SLACK, return_hidden=False):
     """int32 [E,V,1+T].  points float32 [P,3] and offsets int32 [E+1] as ``sample_edges`` gives them; intrinsics [V,4] =
     (fx, fy, cx, cy) and w2c [V,3,4] float64 host arrays or tensors; d2 int32 [V,H,W], ``edt_squared`` of every view's detected
     mask; 1 to 4 pixel tolerances, squared by ``edge_score.tolerances_squared``.  counts[e,v,0] = the points of edge e that
@@ -162,8 +178,16 @@ def support_counts(points, offsets, intrinsics, w2c, d2, tolerances_px, backend=
 
     ``backend="gpu"``: ``cgs_edge_support``.  d2 must be on a GPU (``edt_squared`` leaves it there; CurveGSError
     otherwise), ``device``, when given, must be that GPU, and so must the device of points that are on a GPU; points and
-    offsets on the host are uploaded.  The result stays on the device.  ``backend="host"``: numpy, a CPU tensor."""
+    offsets on the host are uploaded.  The result stays on the device.  ``backend="host"``: numpy, a CPU tensor.
+
+    ``depth`` (None: no gate, the call above and nothing else): float32 [V,H,W] of d2's size, camera z, +inf where there is
+    no surface.  A sample that view v keeps is HIDDEN there iff c2 > float64(depth[v][floor(v)][floor(u)]) + ``slack``
+    (finite, >= 0; ``cgs_edge_support_depth``): it counts as not seen -- in counts[e,v,0] no more than in the near columns.
+    ``return_hidden`` (needs ``depth``): also int32 [E,V], the hidden samples of every (edge, view); counts[e,v,0] + hidden[e,v]
+    is the ungated counts[e,v,0].  depth on the host is uploaded for ``backend="gpu"``."""
     _check_backend(backend)
+    if return_hidden and depth is None:
+        raise ValueError("support_counts: return_hidden needs depth")
     tol2 = _tolerances(tolerances_px)
     pts = _points(points)
     off = _offsets(offsets, int(pts.shape[0]))
@@ -173,7 +197,12 @@ def support_counts(points, offsets, intrinsics, w2c, d2, tolerances_px, backend=
     if backend == "host":
         if d2.is_cuda or pts.is_cuda:
             raise ValueError("support_counts: backend='host' takes host arrays and CPU tensors")
-        return torch.from_numpy(_counts_host(pts.numpy(), off, K, M, d2.numpy(), tol2))
+        if depth is None:
+            return torch.from_numpy(_counts_host(pts.numpy(), off, K, M, d2.numpy(), tol2))
+        depth, slack = EO.operator_depth("support_counts", depth, slack, V, int(d2.shape[1]), int(d2.shape[2]), "host")
+        hidden = np.zeros((E, V), np.int32)
+        counts = torch.from_numpy(_counts_host(pts.numpy(), off, K, M, d2.numpy(), tol2, depth, slack, hidden))
+        return (counts, torch.from_numpy(hidden)) if return_hidden else counts
     L.require_gpu_tensor(d2, "support_counts: d2")
     dev = d2.device
     if device is not None and torch.device(device) != dev and torch.device(device) != torch.device(dev.type):
@@ -185,15 +214,24 @@ def support_counts(points, offsets, intrinsics, w2c, d2, tolerances_px, backend=
     with L.device_guard(dev):
         pts = pts.to(dev).contiguous()
         out = torch.empty((E, V, 1 + T), dtype=torch.int32, device=dev)
+        if depth is not None:
+            depth, slack = EO.operator_depth("support_counts", depth, slack, V, int(d2.shape[1]), int(d2.shape[2]), "gpu", dev)
+            hidden = torch.empty((E, V), dtype=torch.int32, device=dev) if return_hidden else None
         if E > 0 and V > 0:
             off_d = torch.from_numpy(off).to(dev)
             tol_d = torch.tensor(tol2, dtype=torch.int32).to(dev)
             Kd, Md = ES.cameras_on(dev, K, M)
-            rc = L.load().cgs_edge_support(E, int(pts.shape[0]), L.ptr(pts), L.ptr(off_d), V, L.ptr(Kd), L.ptr(Md),
-                                           int(d2.shape[1]), int(d2.shape[2]), L.ptr(d2), T, L.ptr(tol_d), L.ptr(out),
-                                           L.raw_stream(dev))
-            L.check(rc, "cgs_edge_support")
-    return out
+            if depth is None:
+                rc = L.load().cgs_edge_support(E, int(pts.shape[0]), L.ptr(pts), L.ptr(off_d), V, L.ptr(Kd), L.ptr(Md),
+                                               int(d2.shape[1]), int(d2.shape[2]), L.ptr(d2), T, L.ptr(tol_d), L.ptr(out),
+                                               L.raw_stream(dev))
+                L.check(rc, "cgs_edge_support")
+            else:
+                rc = L.load().cgs_edge_support_depth(E, int(pts.shape[0]), L.ptr(pts), L.ptr(off_d), V, L.ptr(Kd), L.ptr(Md),
+                                                     int(d2.shape[1]), int(d2.shape[2]), L.ptr(d2), T, L.ptr(tol_d),
+                                                     L.ptr(depth), slack, L.ptr(out), L.ptr(hidden), L.raw_stream(dev))
+                L.check(rc, "cgs_edge_support_depth")
+    return (out, hidden) if return_hidden else out
 
 
 # ------------------------------------------------------------------------------------------------ verdict
@@ -237,7 +275,8 @@ def support_verdict(counts, n_points, frames, min_visible=MIN_VISIBLE, min_near=
 def edge_support(edge_dict, cameras, edge_maps_u8, detector, resolution=SAMPLE_RESOLUTION, tolerances_px=TOLERANCES_PX,
                  keep_tolerance_px=KEEP_TOLERANCE_PX, min_visible=MIN_VISIBLE, min_near=MIN_NEAR,
                  frames_ratio=EDGE_VISIBILITY_FRAMES_RATIO, edge_threshold=EDGE_MAX_THRESHOLD, backend="gpu", device=None,
-                 budget_bytes=None, thin=False):
+                 budget_bytes=None, thin=False, occluder=None, depth_maps=None, depth_slack=EO.DEPTH_SLACK,
+                 depth_window=EO.DEPTH_WINDOW):
     """edge_dict: {"curves_ctl_pts", "lines_end_pts"} (a ``parametric_edges.json``).  cameras: ``NovelViewCamera`` s;
     edge_maps_u8: one uint8 [H,W] map per camera, the stored bytes of the detector's maps, as ``score_edges`` takes them.
     ``resolution``: the sampling step (default: ``reprojection.SAMPLE_RESOLUTION``, the novel views' Replica value); ``keep_tolerance_px``: the one of
@@ -252,6 +291,16 @@ def edge_support(edge_dict, cameras, edge_maps_u8, detector, resolution=SAMPLE_R
     the transform is allocated; untuned, limits in ops/edge_thin.py); "settings" then holds "thin": True, and nothing
     otherwise.
 
+    Depth (opt-in; at most one of the two, with the meaning and the checks of ``score_edges``): ``occluder`` -- float32
+    [F,3,3] triangles or the path of an .obj / .ply mesh -- or ``depth_maps`` -- one float [H,W] array of camera z per
+    camera -- give every chunk its depth planes (``edge_occlusion.ChunkDepth``: the window maximum of radius
+    ``depth_window``, 8 bytes per pixel more), and ``support_counts`` holds every sample against them with ``depth_slack``: a
+    hidden (sample, view) pair counts as not seen.  The verdict's formulas are the frozen ones; only their inputs change, so
+    a view whose VISIBLE samples number fewer than ceil(min_visible * n) does not see the edge.  The result then also holds
+    "hidden": int32 [E,V] CPU tensor, and "settings" the keys ``score_edges`` records ("occluder" or "depth_maps",
+    "depth_slack", "depth_window").  With neither, nothing changes: no key is added.  The window and the slack are untuned and
+    checked on the drawn solids only; concave edges can be hidden by their own faces; there is no near-plane clipping.
+
     Returns {"counts": int32 [E,V,1+T] CPU tensor, "n_points": int64 [E], "curves": Nc, "lines": Nl, the arrays of
     ``support_verdict`` ("seeing_views", "supporting_views", "share", "kept"), "settings"}; edges are ordered
     curves first, then lines."""
@@ -265,6 +314,7 @@ def edge_support(edge_dict, cameras, edge_maps_u8, detector, resolution=SAMPLE_R
     lut = detected_lut(detector, edge_threshold)
     cameras, maps = check_edge_maps("edge_support", cameras, edge_maps_u8)
     budget = check_budget("edge_support", budget_bytes, BYTE_BUDGET)
+    gate = EO.ChunkDepth("edge_support", cameras, occluder, depth_maps, depth_slack, depth_window)
     curves, lines = _edge_arrays(edge_dict["curves_ctl_pts"], edge_dict["lines_end_pts"])
     pts, off = sample_edges(curves, lines, resolution)
     E, V, T = off.size - 1, len(cameras), len(tol2)
@@ -273,17 +323,26 @@ def edge_support(edge_dict, cameras, edge_maps_u8, detector, resolution=SAMPLE_R
         pts_b = torch.from_numpy(pts).to(device)
     else:
         pts_b = pts
+    gate.to(backend, device)
     counts = np.zeros((E, V, 1 + T), np.int32)
-    for _, _, sel, intr, w2c in view_chunks(cameras, BYTES_PER_PIXEL, budget):
+    hidden = np.zeros((E, V), np.int32)
+    for H, W, sel, intr, w2c in view_chunks(cameras, BYTES_PER_PIXEL + gate.bytes_per_pixel, budget):
         det = detected_masks(lut, maps, sel)
         if thin:
             det = thin_masks(det, backend=backend, device=device)
         d2 = ES.edt_squared(det, backend=backend, device=device)
         del det
-        counts[:, sel, :] = support_counts(pts_b, off, intr, w2c, d2, tolerances_px, backend=backend).cpu().numpy()
+        if gate.gated:
+            c, h = support_counts(pts_b, off, intr, w2c, d2, tolerances_px, backend=backend,
+                                  depth=gate.planes(H, W, sel, intr, w2c), slack=gate.slack, return_hidden=True)
+            counts[:, sel, :], hidden[:, sel] = c.cpu().numpy(), h.cpu().numpy()
+        else:
+            counts[:, sel, :] = support_counts(pts_b, off, intr, w2c, d2, tolerances_px, backend=backend).cpu().numpy()
         del d2
     n_points = np.diff(off.astype(np.int64))
     out = {"counts": torch.from_numpy(counts), "n_points": n_points, "curves": int(len(curves)), "lines": int(len(lines))}
+    if gate.gated:
+        out["hidden"] = torch.from_numpy(hidden)
     out.update(support_verdict(counts, n_points, V, min_visible, min_near, frames_ratio, keep_index))
     out["settings"] = {"detector": detector, "resolution": resolution, "tolerances_px": tolerances_px,
                        "keep_tolerance_px": float(keep_tolerance_px), "min_visible": float(min_visible),
@@ -291,4 +350,5 @@ def edge_support(edge_dict, cameras, edge_maps_u8, detector, resolution=SAMPLE_R
                        "edge_threshold": float(edge_threshold), "backend": backend, "views": V, "points": int(pts.shape[0])}
     if thin:
         out["settings"]["thin"] = True
+    out["settings"].update(gate.settings())
     return out

@@ -23,8 +23,13 @@ Definitions, frozen; n = the samples of edge e, ``sample_edges`
                                B(ta,ta,ta), B(ta,ta,tb), B(ta,tb,tb), B(tb,tb,tb) of its blossom B, for a line
                                p0 + t (p1 - p0) at ta and tb; a span (0, n - 1) is the edge itself, bit for bit
 
-KNOWN LIMITS.  There is no depth, as in ops/edge_support.py: a stretch hidden behind a surface in most views is cut
-away.  The pieces of a chord that runs along a real edge duplicate that edge; this module does not merge them
+DEPTH (opt-in).  Without a depth source a stretch hidden behind a surface in most views is cut away,
+and a hidden stretch collects hits it cannot have from the front edges it projects behind.  With ``depth``
+(``sample_tally``) or ``occluder`` / ``depth_maps`` (``trim_edges``) a view whose depth plane hides the sample -- the one
+rule of ops/edge_occlusion.py -- counts as not seeing it and is tallied in "hidden" instead; the frame rule itself does not
+change.  Limits as ops/edge_occlusion.py states them: untuned, drawn solids only, concave edges, no near-plane clipping.
+
+KNOWN LIMITS.  The pieces of a chord that runs along a real edge duplicate that edge; this module does not merge them
 (ops/edge_dedupe.py, opt-in, drops what a longer edge already covers).  The tally asks how near a detected pixel is, not
 which way the detected edge runs there, so a chord collects support where it crosses a real edge (``oriented=True``,
 ops/edge_orient.py, opt-in, holds the edge's direction against the pixels' orientations).  The cut lands up to the tolerance plus a pixel
@@ -42,6 +47,7 @@ import torch
 from .. import _lib as L
 from ..edge_extraction.para_edge import EDGE_MAX_THRESHOLD, EDGE_VISIBILITY_FRAMES_RATIO
 from ..edge_extraction.reprojection import SAMPLE_RESOLUTION
+from . import edge_occlusion as EO
 from . import edge_orient as OR
 from . import edge_score as ES
 from . import edge_support as SP
@@ -58,20 +64,26 @@ MIN_SPAN = 10
 
 
 # ------------------------------------------------------------------------------------------------ tally
-def _tally_host(pts, K, M, d2, tol2, out):
+def _tally_host(pts, K, M, d2, tol2, out, depth=None, slack=0.0, hidden=None):
+    """``depth`` float32 [V,H,W] or None; ``hidden`` int32 [P] or None, added to when there is a depth."""
     H, W = d2.shape[1], d2.shape[2]
     for v in range(K.shape[0]):   # one view at a time: [P] temporaries
-        u, w, keep = ES.project_points_host(pts, K[v:v + 1], M[v:v + 1], H, W)
-        keep = keep[0]
+        if depth is None:
+            u, w, keep = (x[0] for x in ES.project_points_host(pts, K[v:v + 1], M[v:v + 1], H, W))
+        else:   # a view that hides the sample does not see it
+            u, w, keep, hid = EO.gate_view_host(pts, K[v], M[v], depth[v], slack)
+            if hidden is not None:
+                hidden += hid
         d = np.full(pts.shape[0], ES.EDT_INF, np.int64)
-        d[keep] = d2[v][np.floor(w[0][keep]).astype(np.int64), np.floor(u[0][keep]).astype(np.int64)]
+        d[keep] = d2[v][np.floor(w[keep]).astype(np.int64), np.floor(u[keep]).astype(np.int64)]
         out[:, 0] += keep
         for t, t2 in enumerate(tol2):
             out[:, 1 + t] += keep & (d <= t2)
     return out
 
 
-def sample_tally(points, intrinsics, w2c, d2, tolerances_px, backend="gpu", device=None, out=None):
+def sample_tally(points, intrinsics, w2c, d2, tolerances_px, backend="gpu", device=None, out=None, depth=None,
+                 slack=EO.DEPTH_SLACK, hidden_out=None):
     """int32 [P,1+T].  points float32 [P,3]; intrinsics [V,4] = (fx, fy, cx, cy) and w2c [V,3,4] float64 host arrays or
     tensors; d2 int32 [V,H,W], ``edt_squared`` of every view's detected mask; 1 to 4 pixel tolerances, squared by
     ``edge_score.tolerances_squared`` -- the arguments of ``support_counts`` without the offsets.  tally[i,0] = the views in
@@ -82,7 +94,13 @@ def sample_tally(points, intrinsics, w2c, d2, tolerances_px, backend="gpu", devi
 
     ``backend="gpu"``: ``cgs_sample_support``.  d2 must be on a GPU (CurveGSError otherwise), ``device``, when given, must
     be that GPU, and so must the device of ``out`` and of points that are on a GPU; points on the host are uploaded.  The
-    result stays on the device.  ``backend="host"``: numpy, CPU tensors."""
+    result stays on the device.  ``backend="host"``: numpy, CPU tensors.
+
+    ``depth`` (None: no gate, the call above and nothing else): float32 [V,H,W] of d2's size, camera z, +inf where there is
+    no surface.  A view that keeps sample i HIDES it iff c2 > float64(depth[v][floor(v)][floor(u)]) + ``slack`` (finite,
+    >= 0; ``cgs_sample_support_depth``): it counts in no column of the tally.  ``hidden_out`` (needs ``depth``): a contiguous
+    int32 [P] tensor, on ``out``'s device, that the hiding views of every sample are ADDED to, as the tally is; tally[i,0] +
+    hidden is the ungated tally[i,0].  depth on the host is uploaded for ``backend="gpu"``."""
     SP._check_backend(backend)
     tol2 = SP._tolerances(tolerances_px)
     pts = SP._points(points)
@@ -92,12 +110,18 @@ def sample_tally(points, intrinsics, w2c, d2, tolerances_px, backend="gpu", devi
     if out is not None:
         if not torch.is_tensor(out) or out.dtype != torch.int32 or tuple(out.shape) != (P, 1 + T) or not out.is_contiguous():
             raise ValueError(f"sample_tally: out must be a contiguous int32 [{P},{1 + T}] tensor")
+    EO.check_hidden_out("sample_tally", hidden_out, depth, P)
     if backend == "host":
-        if d2.is_cuda or pts.is_cuda or (out is not None and out.is_cuda):
+        if d2.is_cuda or pts.is_cuda or (out is not None and out.is_cuda) or (hidden_out is not None and hidden_out.is_cuda):
             raise ValueError("sample_tally: backend='host' takes host arrays and CPU tensors")
         if out is None:
             out = torch.zeros((P, 1 + T), dtype=torch.int32)
-        _tally_host(pts.numpy(), K, M, d2.numpy(), tol2, out.numpy())
+        if depth is None:
+            _tally_host(pts.numpy(), K, M, d2.numpy(), tol2, out.numpy())
+            return out
+        depth, slack = EO.operator_depth("sample_tally", depth, slack, V, int(d2.shape[1]), int(d2.shape[2]), "host")
+        _tally_host(pts.numpy(), K, M, d2.numpy(), tol2, out.numpy(), depth, slack,
+                    None if hidden_out is None else hidden_out.numpy())
         return out
     L.require_gpu_tensor(d2, "sample_tally: d2")
     dev = d2.device
@@ -107,16 +131,27 @@ def sample_tally(points, intrinsics, w2c, d2, tolerances_px, backend="gpu", devi
         raise L.CurveGSError(f"sample_tally: points are on {pts.device}, d2 on {dev}: all tensors must be on one device")
     if out is not None and out.device != dev:
         raise L.CurveGSError(f"sample_tally: out is on {out.device}, d2 on {dev}: all tensors must be on one device")
+    if hidden_out is not None and hidden_out.device != dev:
+        raise L.CurveGSError(f"sample_tally: hidden_out is on {hidden_out.device}, d2 on {dev}: all tensors must be on one "
+                             "device")
     with L.device_guard(dev):
         pts = pts.to(dev).contiguous()
         if out is None:
             out = torch.zeros((P, 1 + T), dtype=torch.int32, device=dev)
+        if depth is not None:
+            depth, slack = EO.operator_depth("sample_tally", depth, slack, V, int(d2.shape[1]), int(d2.shape[2]), "gpu", dev)
         if P > 0 and V > 0:
             tol_d = torch.tensor(tol2, dtype=torch.int32).to(dev)
             Kd, Md = ES.cameras_on(dev, K, M)
-            rc = L.load().cgs_sample_support(P, L.ptr(pts), V, L.ptr(Kd), L.ptr(Md), int(d2.shape[1]), int(d2.shape[2]),
-                                             L.ptr(d2), T, L.ptr(tol_d), L.ptr(out), L.raw_stream(dev))
-            L.check(rc, "cgs_sample_support")
+            if depth is None:
+                rc = L.load().cgs_sample_support(P, L.ptr(pts), V, L.ptr(Kd), L.ptr(Md), int(d2.shape[1]), int(d2.shape[2]),
+                                                 L.ptr(d2), T, L.ptr(tol_d), L.ptr(out), L.raw_stream(dev))
+                L.check(rc, "cgs_sample_support")
+            else:
+                rc = L.load().cgs_sample_support_depth(P, L.ptr(pts), V, L.ptr(Kd), L.ptr(Md), int(d2.shape[1]),
+                                                       int(d2.shape[2]), L.ptr(d2), T, L.ptr(tol_d), L.ptr(depth), slack,
+                                                       L.ptr(out), L.ptr(hidden_out), L.raw_stream(dev))
+                L.check(rc, "cgs_sample_support_depth")
     return out
 
 
@@ -206,13 +241,22 @@ def trim_geometry(curves, lines, offsets, spans):
 def trim_edges(edge_dict, cameras, edge_maps_u8, detector, resolution=SAMPLE_RESOLUTION, tolerance_px=TOLERANCE_PX,
                frames_ratio=EDGE_VISIBILITY_FRAMES_RATIO, max_gap=MAX_GAP, min_span=MIN_SPAN,
                edge_threshold=EDGE_MAX_THRESHOLD, backend="gpu", device=None, budget_bytes=None, thin=False, oriented=False,
-               spread=OR.SPREAD):
+               spread=OR.SPREAD, occluder=None, depth_maps=None, depth_slack=EO.DEPTH_SLACK, depth_window=EO.DEPTH_WINDOW):
     """edge_dict, cameras, edge_maps_u8, detector, resolution, edge_threshold, budget_bytes and thin as ``edge_support``
     takes them, and the same walk over the views: ``view_chunks``, ``detected_masks``, the optional ``thin_masks``,
     ``edt_squared``, then one ``sample_tally`` call per chunk into one tally -- integers, so the chunking cannot change a bit.
     EVERY edge of edge_dict is trimmed, whatever ``edge_support`` says of it: the verdict drops over-long true edges whole,
     and those are the ones trimming exists for.  ``tolerance_px``: the one pixel tolerance; the frame rule counts all
-    cameras.  THE DEFAULTS ARE UNTUNED (the drawn test scan only) and there is no depth: see the module docstring.
+    cameras.  THE DEFAULTS ARE UNTUNED (the drawn test scan only): see the module docstring.
+
+    Depth (opt-in; ``occluder``, ``depth_maps``, ``depth_slack`` and ``depth_window`` with the meaning and the checks of
+    ``score_edges`` and ``edge_support``, at most one of the first two): every chunk gets its depth planes
+    (``edge_occlusion.ChunkDepth``, 8 bytes per pixel more) and ``sample_tally`` / ``oriented_tally`` hold every sample
+    against them: a view that hides a sample does not see it -- with ``oriented`` the sample alone is gated, its partner
+    gives a direction only.  The frame rule is the frozen one; only the tally changes.  The result then also holds "hidden":
+    int32 [P] CPU tensor, the hiding views of every sample, and "settings" the keys ``score_edges`` records.  With neither,
+    nothing changes: no key is added.  Untuned, drawn solids only, concave edges can be hidden by their own faces, no
+    near-plane clipping (ops/edge_occlusion.py).
 
     ``oriented=True`` (off by default; ops/edge_orient.py freezes the rule and states its limits) counts a sample as near
     only where a detected pixel within the tolerance runs the way the sample's edge does, to within ``spread`` octants of
@@ -230,6 +274,7 @@ def trim_edges(edge_dict, cameras, edge_maps_u8, detector, resolution=SAMPLE_RES
     lut = detected_lut(detector, edge_threshold)
     cameras, maps = check_edge_maps("trim_edges", cameras, edge_maps_u8)
     budget = check_budget("trim_edges", budget_bytes, BYTE_BUDGET)
+    gate = EO.ChunkDepth("trim_edges", cameras, occluder, depth_maps, depth_slack, depth_window)
     curves, lines = SP._edge_arrays(edge_dict["curves_ctl_pts"], edge_dict["lines_end_pts"])
     pts, off = SP.sample_edges(curves, lines, resolution)
     V = len(cameras)
@@ -238,13 +283,17 @@ def trim_edges(edge_dict, cameras, edge_maps_u8, detector, resolution=SAMPLE_RES
         pts_b = torch.from_numpy(pts).to(device)
     else:
         pts_b = pts
+    gate.to(backend, device)
     tally = torch.zeros((pts.shape[0], 2), dtype=torch.int32, device=device if backend == "gpu" else None)
+    hidden = torch.zeros((pts.shape[0],), dtype=torch.int32, device=tally.device) if gate.gated else None
     if oriented:
         spread = OR._spread(spread)
         OR._tol2(tolerance_px)
         partner = OR.sample_partners(off)
         partner_b = torch.from_numpy(partner).to(device) if backend == "gpu" else partner
-    for _, _, sel, intr, w2c in view_chunks(cameras, OR.BYTES_PER_PIXEL if oriented else BYTES_PER_PIXEL, budget):
+    per_pixel = (OR.BYTES_PER_PIXEL if oriented else BYTES_PER_PIXEL) + gate.bytes_per_pixel
+    for H, W, sel, intr, w2c in view_chunks(cameras, per_pixel, budget):
+        gated = dict(depth=gate.planes(H, W, sel, intr, w2c), slack=gate.slack, hidden_out=hidden) if gate.gated else {}
         det = detected_masks(lut, maps, sel)
         if thin:
             det = thin_masks(det, backend=backend, device=device)
@@ -252,13 +301,13 @@ def trim_edges(edge_dict, cameras, edge_maps_u8, detector, resolution=SAMPLE_RES
             near = OR.oriented_near(OR.mask_orientation(det, backend=backend, device=device), tolerance_px, backend=backend,
                                     device=device)
             del det
-            OR.oriented_tally(pts_b, partner_b, intr, w2c, near, spread, backend=backend, out=tally)
-            del near
+            OR.oriented_tally(pts_b, partner_b, intr, w2c, near, spread, backend=backend, out=tally, **gated)
+            del near, gated
             continue
         d2 = ES.edt_squared(det, backend=backend, device=device)
         del det
-        sample_tally(pts_b, intr, w2c, d2, [tolerance_px], backend=backend, out=tally)
-        del d2
+        sample_tally(pts_b, intr, w2c, d2, [tolerance_px], backend=backend, out=tally, **gated)
+        del d2, gated
     tally = tally.cpu()
     spans = supported_spans(supported_samples(tally, V, frames_ratio)[:, 0], off, max_gap, min_span)
     out_c, out_l, source = trim_geometry(curves, lines, off, spans)
@@ -269,6 +318,10 @@ def trim_edges(edge_dict, cameras, edge_maps_u8, detector, resolution=SAMPLE_RES
         settings["thin"] = True
     if oriented:
         settings.update({"oriented": True, "spread": spread})
-    return {"tally": tally, "offsets": off, "spans": spans,
-            "edge_dict": {"curves_ctl_pts": out_c.tolist(), "lines_end_pts": out_l.reshape(-1, 6).tolist()},
-            "source": source, "settings": settings}
+    settings.update(gate.settings())
+    out = {"tally": tally, "offsets": off, "spans": spans,
+           "edge_dict": {"curves_ctl_pts": out_c.tolist(), "lines_end_pts": out_l.reshape(-1, 6).tolist()},
+           "source": source, "settings": settings}
+    if gate.gated:
+        out["hidden"] = hidden.cpu()
+    return out

@@ -275,7 +275,7 @@ def write_parametric_edges(gaussians, model_path, merge_endpoints=False, distanc
                            visible_checking=False, scan_dir=None, detector="DexiNed", support_checking=False,
                            support_options=None, cameras=None, edge_maps=None, trim=False, trim_options=None,
                            dedupe=False, dedupe_options=None, join=False, join_options=None, snap=False,
-                           snap_options=None):
+                           snap_options=None, depth_options=None):
     """Writes parametric_edges.json (the evaluation input, train.py:287-293) and edge_points.ply (ASCII, :277-285).
     merge_endpoints / distance_threshold: see extract_curves (the reference's default is merge_endpoints=True).
     visible_checking=True keeps only the edges that `detector`'s edge maps of the scan at `scan_dir` show
@@ -303,7 +303,12 @@ def write_parametric_edges(gaussians, model_path, merge_endpoints=False, distanc
     (edge_extraction.support.snap_scene; `snap_options` go to ops.edge_snap.snap_edges, whose defaults are untuned); the
     support check, the trimming, the deduping and the joining then start from the snapped edges, and their files record
     "input": parametric_edges_snapped.json where they would have named parametric_edges.json.  The returned dict is the
-    written one, not the snapped one."""
+    written one, not the snapped one.
+    depth_options (None: no depth, nothing changes) is a dict of `occluder` or `depth_maps` (one per camera, in the cameras'
+    order) with `depth_slack` and `depth_window`, as reprojection.score_edges takes them: it goes to the snapping, the
+    support check and the trimming alike, each of which then counts a (sample, view) pair that the depth hides as not seen
+    (ops.edge_occlusion; untuned, drawn solids only).  An option of the same name in snap_options, support_options or
+    trim_options wins for its step."""
     if visible_checking and scan_dir is None:
         raise ValueError("write_parametric_edges(visible_checking=True) needs scan_dir, the scan holding "
                          "meta_data.json and the edge maps")
@@ -320,14 +325,17 @@ def write_parametric_edges(gaussians, model_path, merge_endpoints=False, distanc
     written, source, named = edge_dict, "parametric_edges.json", {}
     if snap:
         from ..edge_extraction.support import SNAPPED_FILE, snap_scene
-        edge_dict, _ = snap_scene(model_path, edge_dict, cameras, edge_maps, detector, **(snap_options or {}))
+        edge_dict, _ = snap_scene(model_path, edge_dict, cameras, edge_maps, detector,
+                                  **{**(depth_options or {}), **(snap_options or {})})
         source, named = SNAPPED_FILE, {"input_file": SNAPPED_FILE}
     if support_checking:
         from ..edge_extraction.support import support_scene
-        support_scene(model_path, edge_dict, cameras, edge_maps, detector, **named, **(support_options or {}))
+        support_scene(model_path, edge_dict, cameras, edge_maps, detector, **named,
+                      **{**(depth_options or {}), **(support_options or {})})
     if trim:
         from ..edge_extraction.support import trim_scene
-        trimmed, _ = trim_scene(model_path, edge_dict, cameras, edge_maps, detector, **named, **(trim_options or {}))
+        trimmed, _ = trim_scene(model_path, edge_dict, cameras, edge_maps, detector, **named,
+                                **{**(depth_options or {}), **(trim_options or {})})
     if dedupe:
         from ..edge_extraction.support import TRIMMED_FILE, dedupe_scene
         deduped, _ = dedupe_scene(model_path, trimmed if trim else edge_dict,

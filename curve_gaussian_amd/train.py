@@ -368,6 +368,10 @@ def build_parser():
                         "model directory")
     from .edge_extraction.reprojection import add_depth_arguments
     add_depth_arguments(p)   # --occluder / --depth_dir (inside --source_path), --depth_slack, --depth_window: for the score
+    p.add_argument("--gate_edge_checks", action="store_true",
+                   help="--snap_edges, --support_check and --trim_edges also take the depth source that --occluder or "
+                        "--depth_dir names: a (sample, view) pair the depth hides counts as not seen (needs one of the two; "
+                        "untuned, checked on drawn solids only)")
     p.add_argument("--snap_edges", action="store_true",
                    help="after the export, FIRST move every edge of parametric_edges.json onto the detected edges of the "
                         "train cameras' edge maps: edge_snap.json and parametric_edges_snapped.json in the model directory; "
@@ -480,7 +484,12 @@ def join_options(args):
 
 def parse_args(argv):
     """(ModelParams, OptimizationParams, args) of a command line, as :378-404 derives them."""
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if args.gate_edge_checks and args.occluder is None and args.depth_dir is None:
+        parser.error("--gate_edge_checks needs a depth source: --occluder or --depth_dir")
+    if args.gate_edge_checks and args.occluder is not None and args.depth_dir is not None:
+        parser.error("--gate_edge_checks takes one depth source: --occluder or --depth_dir, not both")
     source_path = os.path.abspath(args.source_path)                                 # ModelParams.extract (:63-66)
     opt = select_options(source_path, args.detector)()
     if args.iterations is not None:
@@ -532,27 +541,52 @@ def main(argv=None):
             if res is not None:
                 print(scan_line(split, res["aggregate"]))
     if args.snap_edges or args.support_check or args.trim_edges or args.dedupe_edges or args.join_edges:
-        export_checks(args, dataset.model_path, out["scene"].getTrainCameras(), dataset.detector)
+        export_checks(args, dataset.model_path, out["scene"].getTrainCameras(), dataset.detector,
+                      source_path=dataset.source_path)
     print("\nTraining complete.")
 
 
-def export_checks(args, model_path, cameras, detector, edge_maps=None):
+def gate_options(args, source_path, cameras):
+    """The depth keywords of the chain's 2D steps under --gate_edge_checks: ``occluder`` (the mesh inside ``source_path``) or
+    ``depth_maps`` (``<source_path>/<depth_dir>/<image stem>.npy`` of ``cameras``, NovelViewCamera s), and the slack and the
+    window; {} without the flag."""
+    if not getattr(args, "gate_edge_checks", False):
+        return {}
+    if args.occluder is not None and args.depth_dir is not None:
+        raise ValueError("--gate_edge_checks: give --occluder or --depth_dir, not both")
+    gate = dict(depth_slack=args.depth_slack, depth_window=args.depth_window)
+    if args.occluder is not None:
+        gate["occluder"] = os.path.join(source_path, args.occluder)
+    else:
+        from .edge_extraction.reprojection import scan_depth_maps
+        gate["depth_maps"] = scan_depth_maps(os.path.join(source_path, args.depth_dir), cameras)
+    return gate
+
+
+def export_checks(args, model_path, cameras, detector, edge_maps=None, source_path=None):
     """The opt-in steps after the export, on ``<model_path>/parametric_edges.json`` and the train cameras (``edge_maps``
     None: a Scene's cameras carry their maps): --snap_edges first, then --support_check, --trim_edges, --dedupe_edges and
-    --join_edges, each from the last product of the chain."""
+    --join_edges, each from the last product of the chain.  With --gate_edge_checks the first three take the depth source
+    of --occluder / --depth_dir inside ``source_path`` (``gate_options``)."""
     import json
     from .edge_extraction.support import (DEDUPED_FILE, SNAPPED_FILE, TRIMMED_FILE, dedupe_scene, join_scene, snap_scene,
                                           support_scene, trim_scene)
     with open(os.path.join(model_path, "parametric_edges.json")) as f:
         edge_dict = json.load(f)
     source, named = "parametric_edges.json", {}
+    gate = {}
+    if getattr(args, "gate_edge_checks", False):
+        if edge_maps is None:   # the depth maps are found by the cameras' names
+            from .edge_extraction.reprojection import scene_cameras
+            cameras, edge_maps = scene_cameras(cameras)
+        gate = gate_options(args, source_path, cameras)
     if args.snap_edges:
-        edge_dict, _ = snap_scene(model_path, edge_dict, cameras, edge_maps, detector, **snap_options(args))
+        edge_dict, _ = snap_scene(model_path, edge_dict, cameras, edge_maps, detector, **snap_options(args), **gate)
         source, named = SNAPPED_FILE, {"input_file": SNAPPED_FILE}
     if args.support_check:
-        support_scene(model_path, edge_dict, cameras, edge_maps, detector, **named, **support_options(args))
+        support_scene(model_path, edge_dict, cameras, edge_maps, detector, **named, **support_options(args), **gate)
     if args.trim_edges:
-        trimmed, _ = trim_scene(model_path, edge_dict, cameras, edge_maps, detector, **named, **trim_options(args))
+        trimmed, _ = trim_scene(model_path, edge_dict, cameras, edge_maps, detector, **named, **trim_options(args), **gate)
     if args.dedupe_edges:
         deduped, _ = dedupe_scene(model_path, trimmed if args.trim_edges else edge_dict,
                                   input_file=TRIMMED_FILE if args.trim_edges else source, **dedupe_options(args))

@@ -1294,6 +1294,70 @@ int cgs_point_mask_depth(int P, const float* points /*[P,3]*/, int V, const doub
                          double slack, uint8_t* mask_out /*[V,height,width]*/, int32_t* kept /*[V]*/,
                          int32_t* hidden /*[V]*/, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * The depth gate on the four per-sample 2D operators of the extraction chain: cgs_edge_support, cgs_sample_support,
+ * cgs_sample_support_oriented and cgs_sample_snap_terms, each with the occlusion rule of cgs_point_mask_depth.  Opt-in; the
+ * ungated entries above are unchanged to the bit.  Each entry takes the arguments of its sibling, with their meaning, plus
+ *   depth   float32 [V,height,width], device: camera z per view, +inf where there is no surface (cgs_mesh_depth followed by
+ *           cgs_depth_window_max, or the caller's own maps); height and width are those of d2 / near
+ *   slack   float64, finite and >= 0, in the units of depth
+ * THE RULE, the same in all four: a (sample, view) pair that the projection rule of cgs_project_points keeps -- the same
+ * device function, which here also returns the camera-space depth c2 -- is HIDDEN iff
+ *   c2 > (double)depth[v][floor(v_px)][floor(u_px)] + slack                      (one float64 addition, one comparison)
+ * -- the device function nv_hidden of csrc/point_projection.h, the one statement of the rule.  A hidden pair counts as NOT
+ * SEEN: everything the sibling does for a seen pair is skipped, and the pair counts in the entry's hidden counter instead.
+ * A NaN depth hides nothing.  Seen and hidden of a gated entry always add up to seen of its sibling; with an all-+inf depth
+ * the outputs are the sibling's, and hidden is zero.
+ *
+ * cgs_edge_support_depth: counts int32 [E,V,1+T] is WRITTEN, every word, like the sibling's: counts[e][v][0] = the samples of
+ * edge e that view v sees and does not hide, counts[e][v][1+t] = those of them within tolerance t.  hidden is int32 [E,V],
+ * device, or NULL: hidden[e][v] = the samples of edge e that view v sees and hides, WRITTEN (not added to), every word.
+ *
+ * cgs_sample_support_depth: tally int32 [P,1+T]; the entry ADDS, like its sibling: tally[i][0] += the views that see sample
+ * i and do not hide it, tally[i][1+t] += those of them within tolerance t.  hidden is int32 [P], device, or NULL:
+ * hidden[i] += the views that see sample i and hide it -- ADDED to, like the tally, so that one call per chunk of views
+ * accumulates both.
+ *
+ * cgs_sample_support_oriented_depth: tally int32 [P,2] and hidden int32 [P] or NULL, both ADDED to as above.  ONLY THE
+ * SAMPLE ITSELF IS GATED.  The partner gives a direction and nothing else: it is projected by the projection rule alone
+ * and is NEVER tested against depth -- a partner behind a surface still gives its direction, exactly as a partner that
+ * the sibling would use.  (A partner the projection does not keep gives no direction, as in the sibling.)
+ *
+ * cgs_sample_snap_terms_depth: terms float64 [P,10], views int32 [P] and hidden int32 [P] or NULL, all ADDED to.  A hidden
+ * pair contributes NO TERM AND NO VIEW: the view is left right after the projection's verdict, before the footprint test,
+ * and counts in hidden[i] whether or not its footprint would have captured the sample.  For every other view the
+ * floating-point sequence is exactly the sibling's, view by view in view order into the sample's own row, so the sums do
+ * not depend on how the views are cut into calls and both back ends agree on every bit.
+ *
+ * Geometry as the siblings': one wave per (edge, view) for cgs_edge_support_depth, one thread per sample with the view loop
+ * inside for the other three -- each kernel is the sibling's own body instantiated with the gate; integers or uncontracted
+ * float64, no atomics, one owner per output row, so no result depends on the launch geometry.  The gate costs one float32
+ * gather per seen pair.  All four run on the caller's stream with no allocation and no host synchronisation.  Every
+ * argument is checked as the sibling checks it, and in addition a slack that is negative, NaN or infinite and a NULL
+ * depth are CGS_ERR_INVALID_ARGUMENT, rejected before anything is launched (hidden may be NULL).
+ * LIMITS, those of the rule: no near-plane clipping in the z-buffer that usually draws depth; along a concave edge samples of
+ * a visible edge can be hidden by their own faces; the window and the slack that make depth are the caller's, and untuned.
+ * ------------------------------------------------------------------------------------------------ */
+int cgs_edge_support_depth(int E, int P, const float* points /*[P,3]*/, const int32_t* offsets /*[E+1]*/, int V,
+                           const double* intr /*[V,4]*/, const double* w2c /*[V,12]*/, int height, int width,
+                           const int32_t* d2 /*[V,height,width]*/, int T, const int32_t* tol2 /*[T]*/,
+                           const float* depth /*[V,height,width]*/, double slack, int32_t* counts /*[E,V,1+T]*/,
+                           int32_t* hidden /*[E,V]*/, void* stream);
+int cgs_sample_support_depth(int P, const float* points /*[P,3]*/, int V, const double* intr /*[V,4]*/,
+                             const double* w2c /*[V,12]*/, int height, int width, const int32_t* d2 /*[V,height,width]*/,
+                             int T, const int32_t* tol2 /*[T]*/, const float* depth /*[V,height,width]*/, double slack,
+                             int32_t* tally /*[P,1+T]*/, int32_t* hidden /*[P]*/, void* stream);
+int cgs_sample_support_oriented_depth(int P, const float* points /*[P,3]*/, const int32_t* partner /*[P]*/, int V,
+                                      const double* intr /*[V,4]*/, const double* w2c /*[V,12]*/, int height, int width,
+                                      const uint8_t* near /*[V,height,width]*/, int spread,
+                                      const float* depth /*[V,height,width]*/, double slack, int32_t* tally /*[P,2]*/,
+                                      int32_t* hidden /*[P]*/, void* stream);
+int cgs_sample_snap_terms_depth(int P, const float* points /*[P,3]*/, int V, const double* intr /*[V,4]*/,
+                                const double* w2c /*[V,12]*/, int height, int width, const int32_t* d2 /*[V,height,width]*/,
+                                int cap2, const double* dist_lut /*[cap2+1]*/, const float* depth /*[V,height,width]*/,
+                                double slack, double* terms /*[P,10]*/, int32_t* views /*[P]*/, int32_t* hidden /*[P]*/,
+                                void* stream);
+
 #ifdef __cplusplus
 }
 #endif
