@@ -135,6 +135,7 @@ SIGNATURES = {
     "cgs_sample_support_depth": (_i, [_i, _vp, _i, _vp, _vp, _i, _i, _vp, _i, _vp, _vp, C.c_double, _vp, _vp, _vp]),
     "cgs_sample_support_oriented_depth": (_i, [_i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _i, _vp, C.c_double, _vp, _vp, _vp]),
     "cgs_sample_snap_terms_depth": (_i, [_i, _vp, _i, _vp, _vp, _i, _i, _vp, _i, _vp, _vp, C.c_double, _vp, _vp, _vp, _vp]),
+    "cgs_mesh_contours": (_i, [_i, _vp, _i, _vp, _vp, _i, _i, _vp, C.c_double, _vp, _vp]),
 }
 
 

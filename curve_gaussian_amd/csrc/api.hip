@@ -154,7 +154,7 @@ static thread_local int64_t g_last_stats[3] = {0, 0, 0};  // num_rendered, longe
 // node cleared the buffer on the first replay only -- later replays ran on stale histograms / partial sums.  A plain kernel
 // node replays correctly, and hipMemsetAsync is a fill kernel anyway.  The edge-map launchers do use it and are not captured:
 // launch_point_mask and launch_edge_score_reduce (edge_score.hip), launch_edge_trace (edge_detect.hip), launch_thin_masks
-// (edge_thin.hip), launch_ray_claims (edge_seed.hip), launch_mesh_depth and launch_point_mask_depth (edge_occlusion.hip); so does cgs_segment_merge_labels below for an empty input.
+// (edge_thin.hip), launch_ray_claims (edge_seed.hip), launch_mesh_depth and launch_point_mask_depth (edge_occlusion.hip), launch_mesh_contours (mesh_contours.hip); so does cgs_segment_merge_labels below for an empty input.
 __global__ void __launch_bounds__(256) k_zero_words(uint32_t* __restrict__ p, size_t words) {
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < words; i += stride) p[i] = 0u;
@@ -2003,6 +2003,25 @@ int cgs_sample_snap_terms_depth(int P, const float* points, int V, const double*
     launch_sample_snap_terms_depth((hipStream_t)stream_, P, points, V, intr, w2c, height, width, d2, cap2, dist_lut, depth,
                                    slack, terms, views, hidden);
     return finish("sample_snap_terms_depth", stream_);
+}
+
+// ---- occluding contours of a mesh (include/curvegs.h).  The slack is checked only with a plane: without one it is not read.
+int cgs_mesh_contours(int E, const float* edges, int V, const double* intr, const double* w2c, int height, int width,
+                      const float* depth, double slack, uint8_t* mask_out, void* stream_) {
+    if (E < 0 || V < 0) return reject("cgs_mesh_contours: invalid argument (E=%d, V=%d)", E, V);
+    if (!edt_size_ok(height, width))
+        return reject("cgs_mesh_contours: invalid argument (height=%d, width=%d; sizes lie in [1, %d])", height, width,
+                      CGS_EDT_MAX_SIZE);
+    if (depth && !slack_ok(slack))
+        return reject("cgs_mesh_contours: invalid argument (slack=%g; with a depth plane the slack is finite and >= 0)", slack);
+    if (!intr || !w2c || !mask_out || (E > 0 && !edges))
+        return reject("cgs_mesh_contours: invalid argument (NULL pointer; E=%d)", E);
+    if (V == 0) return CGS_OK;   // nothing to clear
+    if (launch_mesh_contours((hipStream_t)stream_, E, edges, V, intr, w2c, height, width, depth, slack, mask_out) != hipSuccess) {
+        set_error("cgs_mesh_contours: clearing the mask failed");
+        return CGS_ERR_HIP;
+    }
+    return finish("mesh_contours", stream_);
 }
 
 }  // extern "C"

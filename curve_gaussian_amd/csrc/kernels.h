@@ -290,4 +290,8 @@ hipError_t launch_point_mask_depth(hipStream_t s, int P, const float* points, in
                                    int height, int width, const float* depth, double slack, uint8_t* mask, int* kept,
                                    int* hidden);
 
+// mesh_contours.hip
+hipError_t launch_mesh_contours(hipStream_t s, int E, const float* rows, int V, const double* intr, const double* w2c,
+                                int height, int width, const float* depth, double slack, uint8_t* mask);
+
 }  // namespace cgs

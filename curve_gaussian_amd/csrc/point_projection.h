@@ -4,7 +4,8 @@
 // edge_support.hip: cgs_edge_support; edge_trim.hip: cgs_sample_support; edge_orient.hip: cgs_sample_support_oriented;
 // edge_snap.hip: cgs_sample_snap_terms -- those four and their _depth siblings through nv_verdict at the end of this file;
 // edge_occlusion.hip: cgs_point_mask_depth through nv_project_xyz_depth, and
-// cgs_mesh_depth, which projects a triangle's vertices in the same operation order through nv_camera_xyz / nv_image_uv).
+// cgs_mesh_depth, which projects a triangle's vertices in the same operation order through nv_camera_xyz / nv_image_uv;
+// mesh_contours.hip: cgs_mesh_contours, an edge row's four vertices through the same two and nv_hidden).
 //
 // Exact, the reference's operation order (eval_ABC.py project_points_to_camera :66-81): X float32 widened to float64,
 // c = R X + T with every row ((r0*X + r1*Y) + r2*Z) + t, dropped if c2 <= 0 (a NaN depth is dropped too: it fails the

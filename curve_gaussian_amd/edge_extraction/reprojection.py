@@ -12,7 +12,10 @@ when e > edge_threshold with e = 1 - u/255 (DexiNed) or u/255 (PidiNet) -- the c
 KNOWN LIMIT: there is no depth.  An edge hidden behind a surface still projects into the view, finds no detected pixel
 there and counts against precision and accuracy -- unless the caller has a depth source: with ``occluder`` (a triangle
 mesh) or ``depth_maps`` (``--occluder`` / ``--depth_dir``) the hidden samples are left out (``ops.edge_occlusion``, whose
-docstring freezes the rule and states its limits; UNTUNED defaults).
+docstring freezes the rule and states its limits; UNTUNED defaults).  The reverse limit: an occluding contour of a curved
+surface is a detected edge that no 3D edge explains and counts against recall -- unless ``ignore_contours``
+(``--ignore_contours``, with an occluder) takes a zone around the mesh's predicted contours out of both masks
+(``ops.mesh_contours``; UNTUNED defaults).
 
 ``python -m curve_gaussian_amd.edge_extraction.reprojection --base_dir <predictions> --dataset_dir <scans>`` scores every
 scan, writes ``<base_dir>/<scan>/reprojection_score.json`` and prints one line per scan and their mean."""
@@ -28,6 +31,7 @@ import torch
 
 from ..ops import edge_occlusion as EO
 from ..ops import edge_score as ES
+from ..ops import mesh_contours as MC
 from ..ops.edge_thin import thin_masks
 from ..ops.view_chunks import check_edge_maps, detected_lut, detected_masks, view_chunks
 from ..scene.dataset_io import fov2focal
@@ -53,7 +57,8 @@ def _json_number(x):
 
 def score_edges(pred, cameras, edge_maps_u8, detector, tolerances_px=(1, 2, 4), edge_threshold=EDGE_MAX_THRESHOLD,
                 sample_resolution=SAMPLE_RESOLUTION, device=None, backend="gpu", budget_bytes=None, thin=False,
-                occluder=None, depth_maps=None, depth_slack=EO.DEPTH_SLACK, depth_window=EO.DEPTH_WINDOW):
+                occluder=None, depth_maps=None, depth_slack=EO.DEPTH_SLACK, depth_window=EO.DEPTH_WINDOW,
+                ignore_contours=False, contour_radius_px=MC.CONTOUR_RADIUS_PX, crease_deg=MC.CREASE_DEG):
     """pred: a ``parametric_edges.json`` path or its dict.  cameras: ``NovelViewCamera`` s (R, T world -> camera; fx, fy, cx,
     cy; size).  edge_maps_u8: one uint8 [H,W] map per camera (a list, or an [V,H,W] array), the stored bytes of the
     detector's maps, each of its camera's size.  Returns {"aggregate": ops.edge_score's aggregate over all views,
@@ -71,10 +76,22 @@ def score_edges(pred, cameras, edge_maps_u8, detector, tolerances_px=(1, 2, 4), 
     from ``point_masks_depth`` with ``depth_slack``: a hidden sample marks no pixel.  Every row of "views" then holds
     "hidden_points" (kept_points counts the seen samples that are not hidden), "settings" holds "occluder" (the path, or
     true) or "depth_maps": true, and "depth_slack" and "depth_window"; a chunk's working set grows by
-    ``ops.edge_score.DEPTH_BYTES_PER_PIXEL``.  With neither, nothing changes: no key is added."""
+    ``ops.edge_score.DEPTH_BYTES_PER_PIXEL``.  With neither, nothing changes: no key is added.
+
+    A don't-care zone around occluding contours (``ops.mesh_contours``; needs ``occluder``, the mesh whose edges are
+    tested): with ``ignore_contours`` every chunk predicts the smooth contours of the occluder -- folds up to ``crease_deg``,
+    gated by the chunk's planes -- widens them to ``contour_radius_px`` with the score's distance transform and removes the
+    zone from BOTH the prediction masks and the detected masks before they are compared: a pixel beside a contour is
+    evidence neither way.  Every row of "views" then holds "contour_pixels" (the drawn contour pixels, before widening),
+    "settings" holds "ignore_contours": true, "contour_radius_px" and "crease_deg"; a chunk's working set grows by
+    ``ops.edge_score.CONTOUR_BYTES_PER_PIXEL``.  Both defaults are UNTUNED.  Without the flag no key is added and no
+    output changes; with it and no occluder (``depth_maps`` have no mesh edges) it is a ValueError."""
     ES._check_backend(backend)
     EO.check_one_depth_source("score_edges", occluder, depth_maps)
     gated = occluder is not None or depth_maps is not None
+    if ignore_contours and occluder is None:
+        raise ValueError("score_edges: ignore_contours needs an occluder, the mesh whose contours are predicted"
+                         + (" (depth_maps have no mesh edges)" if depth_maps is not None else ""))
     tolerances_px = [float(t) for t in tolerances_px]
     ES.tolerances_squared(tolerances_px)
     lut = detected_lut(detector, edge_threshold)
@@ -87,24 +104,38 @@ def score_edges(pred, cameras, edge_maps_u8, detector, tolerances_px=(1, 2, 4), 
     else:
         pts_b = pts
     gate.to(backend, device)
+    if ignore_contours:
+        contour_radius_px = MC._check_radius("score_edges", contour_radius_px)
+        contour_rows = MC.edge_rows(gate.tris, "smooth", crease_deg)   # once: the selection is the host's
+        if backend == "gpu":
+            contour_rows = torch.from_numpy(contour_rows).to(device)
     budget = ES.BYTE_BUDGET if budget_bytes is None else int(budget_bytes)
     V, n_tol = len(cameras), len(tolerances_px)
     per_view = {"n_pred": np.zeros(V, np.int64), "n_det": np.zeros(V, np.int64), "pred_hits": np.zeros((V, n_tol), np.int64),
                 "det_hits": np.zeros((V, n_tol), np.int64), "sum_pred_to_det": np.zeros(V, np.float64),
                 "sum_det_to_pred": np.zeros(V, np.float64), "both_nonempty": np.zeros(V, bool)}
-    kept, hidden = np.zeros(V, np.int64), np.zeros(V, np.int64)
-    for H, W, sel, intr, w2c in view_chunks(cameras, ES.BYTES_PER_PIXEL + gate.bytes_per_pixel, budget):
+    kept, hidden, contour_px = np.zeros(V, np.int64), np.zeros(V, np.int64), np.zeros(V, np.int64)
+    bytes_per_pixel = ES.BYTES_PER_PIXEL + gate.bytes_per_pixel + (ES.CONTOUR_BYTES_PER_PIXEL if ignore_contours else 0)
+    for H, W, sel, intr, w2c in view_chunks(cameras, bytes_per_pixel, budget):
+        zone = None
         if gated:
             depth = gate.planes(H, W, sel, intr, w2c)
             pm, k, hid = EO.point_masks_depth(pts_b, intr, w2c, depth, gate.slack, backend=backend, device=device,
                                               return_counts=True)
             hidden[sel] = hid.cpu().numpy()
+            if ignore_contours:
+                drawn = MC.row_masks(contour_rows, intr, w2c, H, W, depth, gate.slack, backend=backend, device=device)
+                contour_px[sel] = drawn.sum((1, 2), dtype=torch.int64).cpu().numpy()
+                zone = MC.ignore_zone(drawn, contour_radius_px, backend=backend, device=device)
+                del drawn
             del depth
         else:
             pm, k = ES.point_masks(pts_b, intr, w2c, H, W, backend=backend, device=device, return_kept=True)
         det = detected_masks(lut, maps, sel)
         if thin:
             det = thin_masks(det, backend=backend, device=device)
+        if zone is not None:   # a pixel beside a contour is evidence neither way: out of both masks
+            pm, det = pm * ~zone, det.to(zone.device) * ~zone
         res = ES.score_masks(pm, det, tolerances_px, backend=backend, device=device, budget_bytes=budget)
         kept[sel] = k.cpu().numpy()
         for name, a in per_view.items():
@@ -122,11 +153,15 @@ def score_edges(pred, cameras, edge_maps_u8, detector, tolerances_px=(1, 2, 4), 
                      "both_nonempty": both})
         if gated:
             rows[-1]["hidden_points"] = int(hidden[v])
+        if ignore_contours:
+            rows[-1]["contour_pixels"] = int(contour_px[v])
     settings = {"detector": detector, "tolerances_px": tolerances_px, "edge_threshold": float(edge_threshold),
                 "sample_resolution": float(sample_resolution), "backend": backend, "points": int(pts.shape[0])}
     if thin:
         settings["thin"] = True
     settings.update(gate.settings())
+    if ignore_contours:
+        settings.update({"ignore_contours": True, "contour_radius_px": contour_radius_px, "crease_deg": float(crease_deg)})
     return {"aggregate": agg, "views": rows, "settings": settings}
 
 
@@ -198,13 +233,15 @@ def write_score(path, result):
 def score_scan(base_dir, dataset_dir, scan, layout="emap", detector="DexiNed", undistort=False, tolerances_px=(1, 2, 4),
                edge_threshold=EDGE_MAX_THRESHOLD, sample_resolution=SAMPLE_RESOLUTION, device=None, backend="gpu",
                resolution=-1, thin=False, occluder=None, depth_dir=None, depth_slack=EO.DEPTH_SLACK,
-               depth_window=EO.DEPTH_WINDOW):
+               depth_window=EO.DEPTH_WINDOW, ignore_contours=False, contour_radius_px=MC.CONTOUR_RADIUS_PX,
+               crease_deg=MC.CREASE_DEG):
     """Scores ``<base_dir>/<scan>/parametric_edges.json`` against the ``detector`` edge maps of ``<dataset_dir>/<scan>`` and
     writes ``<base_dir>/<scan>/reprojection_score.json`` = {"scan", "aggregate", "views", "settings"}.  ``layout``: "emap"
     (meta_data.json; cameras and maps through get_edge_maps) or "colmap" (sparse/0, also Replica; through read_colmap, with
     ``undistort`` and ``resolution`` as there); ``thin`` as ``score_edges``.  ``occluder``: the name of a mesh file inside the scan directory
     (``mesh.ply``); ``depth_dir``: the name of a directory inside it that holds one ``<image stem>.npy`` depth map per
-    camera (``scan_depth_maps``); with either, ``depth_slack`` and ``depth_window`` as ``score_edges``.  Returns the dict, or None -- after reporting it -- for a scan without a
+    camera (``scan_depth_maps``); with either, ``depth_slack`` and ``depth_window`` as ``score_edges``; ``ignore_contours``,
+    ``contour_radius_px`` and ``crease_deg`` as there (they need ``occluder``).  Returns the dict, or None -- after reporting it -- for a scan without a
     prediction, as the reference's tools skip one."""
     ES._check_backend(backend)
     if layout not in LAYOUTS:
@@ -229,7 +266,7 @@ def score_scan(base_dir, dataset_dir, scan, layout="emap", detector="DexiNed", u
         gate = dict(depth_maps=scan_depth_maps(os.path.join(scan_dir, depth_dir), cams), depth_slack=depth_slack,
                     depth_window=depth_window)
     res = score_edges(path, cams, maps, detector, tolerances_px, edge_threshold, sample_resolution, device, backend,
-                      thin=thin, **gate)
+                      thin=thin, **gate, **contour_options(ignore_contours, contour_radius_px, crease_deg))
     res["settings"].update({"layout": layout, "undistort": bool(undistort)})
     out = {"scan": scan, **res}
     write_score(os.path.join(base_dir, scan, SCORE_FILE), out)
@@ -304,6 +341,13 @@ def parser():
     return ap
 
 
+def contour_options(ignore_contours, contour_radius_px=MC.CONTOUR_RADIUS_PX, crease_deg=MC.CREASE_DEG):
+    """The keyword arguments of ``score_edges`` for the don't-care zone: none without the flag."""
+    if not ignore_contours:
+        return {}
+    return {"ignore_contours": True, "contour_radius_px": contour_radius_px, "crease_deg": crease_deg}
+
+
 def add_depth_arguments(ap):
     """The depth source of the score (shared with train.py --reprojection_score); without them nothing changes."""
     ap.add_argument("--occluder", default=None, metavar="FILE",
@@ -313,6 +357,11 @@ def add_depth_arguments(ap):
     ap.add_argument("--depth_slack", type=float, default=EO.DEPTH_SLACK, help="world units behind the surface (untuned)")
     ap.add_argument("--depth_window", type=int, default=EO.DEPTH_WINDOW,
                     help="radius of the window maximum over the depth planes (untuned)")
+    ap.add_argument("--ignore_contours", action="store_true",
+                    help="with --occluder: leave a zone around the mesh's predicted occluding contours out of the score")
+    ap.add_argument("--contour_radius_px", type=float, default=MC.CONTOUR_RADIUS_PX, help="radius of that zone (untuned)")
+    ap.add_argument("--crease_deg", type=float, default=MC.CREASE_DEG,
+                    help="mesh edges folded by up to this angle are smooth: candidates for a contour (untuned)")
 
 
 def main(argv=None):
@@ -321,7 +370,9 @@ def main(argv=None):
     for scan in dataset_scans(args.dataset_dir, args.layout, args.scans):
         res = score_scan(args.base_dir, args.dataset_dir, scan, args.layout, args.detector, args.undistort, args.tolerances,
                          args.edge_threshold, backend=args.backend, thin=args.thin, occluder=args.occluder,
-                         depth_dir=args.depth_dir, depth_slack=args.depth_slack, depth_window=args.depth_window)
+                         depth_dir=args.depth_dir, depth_slack=args.depth_slack, depth_window=args.depth_window,
+                         ignore_contours=args.ignore_contours, contour_radius_px=args.contour_radius_px,
+                         crease_deg=args.crease_deg)
         if res is None:
             print(f"Invalid prediction at {scan}")
             continue

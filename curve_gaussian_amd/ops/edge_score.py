@@ -39,6 +39,8 @@ EDT_INF = L.EDT_INF
 BYTE_BUDGET = 1 << 30    # bytes of masks, transforms and scratch per chunk of views in score_masks
 BYTES_PER_PIXEL = 12     # two uint8 masks, two int32 transforms, one uint16 column pass
 DEPTH_BYTES_PER_PIXEL = 8   # score_edges with a depth source, per pixel more: the float32 depth plane and its window maximum
+CONTOUR_BYTES_PER_PIXEL = 8   # score_edges with ignore_contours, per pixel more: the uint8 contour mask, its int32 transform
+                              # with the uint16 column pass, and the bool zone
 
 
 def _check_backend(backend):

@@ -16,8 +16,11 @@ Shapes (inside the unit cube, around its centre):
               handle 0.5523 r.  Such an arc leaves the circle by at most 2.7e-4 r, below the sampling resolution; the
               64-gon's sides lie up to 1.2e-3 r inside the circle, so a rim sample is never behind its own cap.
 
-LIMITS.  The maps hold feature edges only: no silhouette lines of curved surfaces (the cylinder's side draws nothing), no
-detector noise, no line width beyond the pixel a sample falls into.  Along a concave edge (the bracket's inner corner) the
+LIMITS.  By default the maps hold feature edges only (the cylinder's side draws nothing).  With ``contours=True`` they also
+hold the occluding contours of the curved surfaces -- the smooth mesh edges along which a view sees the surface turn away
+(``ops.mesh_contours.contour_masks``, gated by the same planes and slack) -- as a detector would: edges of the image that
+no 3D edge explains.  They are the contours of the MESH (the 64-gon's side edges), one pixel wide.  No detector noise, no
+line width beyond the pixel a sample falls into.  Along a concave edge (the bracket's inner corner) the
 gate can hide samples of a visible edge behind their own faces (ops/edge_occlusion.py says why); the maps then miss them,
 consistently with the score."""
 import json
@@ -30,6 +33,7 @@ import torch
 
 from .. import synthetic
 from ..ops import edge_occlusion as EO
+from ..ops import mesh_contours as MC
 from ..ops.view_chunks import camera_arrays
 from .dataset_io import fov2focal
 
@@ -47,6 +51,7 @@ class SolidScan(NamedTuple):
     maps: np.ndarray        # uint8 [V,H,W], 255 on an edge: PidiNet bytes
     depth: np.ndarray       # float32 [V,H,W], the plain z-buffer (+inf: no surface)
     hidden: np.ndarray      # int32 [V]: the ground-truth samples each view hides
+    contours: np.ndarray = None   # uint8 [V,H,W], 1 on a drawn contour (already OR-ed into maps); None without contours=True
 
 
 def _prism(poly, z0, z1):
@@ -111,9 +116,11 @@ def emap_cameras_of(synth_cams):
 
 
 def solid_scan(shape, n_views, H, W, backend="gpu", device=None, slack=EO.DEPTH_SLACK, window=EO.DEPTH_WINDOW,
-               sample_resolution=SAMPLE_RESOLUTION):
+               sample_resolution=SAMPLE_RESOLUTION, contours=False, crease_deg=MC.CREASE_DEG):
     """A ``SolidScan`` of ``shape`` seen from ``n_views`` ``synthetic.fibonacci_cameras`` of H x W pixels; ``backend`` as the
-    ops (both give the same bytes)."""
+    ops (both give the same bytes).  ``contours``: the smooth contours of the mesh (folds up to ``crease_deg``, UNTUNED) are
+    OR-ed into the maps as 255, gated by the planes and the slack that gate the feature edges, and kept in ``.contours``;
+    without it every byte is what it was."""
     from ..edge_extraction.abc import pred_points_and_directions
     tris, edges = solid_geometry(shape)
     synth = synthetic.fibonacci_cameras(int(n_views), int(H), int(W))
@@ -121,9 +128,14 @@ def solid_scan(shape, n_views, H, W, backend="gpu", device=None, slack=EO.DEPTH_
     intr, w2c = camera_arrays(cams)
     pts = np.ascontiguousarray(pred_points_and_directions(edges, sample_resolution).points, np.float32).reshape(-1, 3)
     raw = EO.mesh_depth(tris, intr, w2c, H, W, window=0, backend=backend, device=device)
-    mask, _, hidden = EO.point_masks_depth(pts, intr, w2c, EO.depth_window_max(raw, window, backend=backend, device=device),
-                                           slack, backend=backend, device=device, return_counts=True)
-    return SolidScan(tris, edges, synth, cams, mask.cpu().numpy() * np.uint8(255), raw.cpu().numpy(), hidden.cpu().numpy())
+    planes = EO.depth_window_max(raw, window, backend=backend, device=device)
+    mask, _, hidden = EO.point_masks_depth(pts, intr, w2c, planes, slack, backend=backend, device=device, return_counts=True)
+    maps, drawn = mask.cpu().numpy() * np.uint8(255), None
+    if contours:
+        drawn = MC.contour_masks(tris, intr, w2c, H, W, planes, slack, "smooth", crease_deg, backend=backend,
+                                 device=device).cpu().numpy()
+        maps |= drawn * np.uint8(255)
+    return SolidScan(tris, edges, synth, cams, maps, raw.cpu().numpy(), hidden.cpu().numpy(), drawn)
 
 
 def write_solid_scan(path, scan, depth=False):
@@ -150,11 +162,14 @@ def main(argv=None):
     ap.add_argument("--height", type=int, default=240)
     ap.add_argument("--width", type=int, default=320)
     ap.add_argument("--depth", action="store_true", help="also write depth/<image stem>.npy")
+    ap.add_argument("--contours", action="store_true",
+                    help="also draw the occluding contours of the curved surfaces into the maps (no 3D edge explains them)")
     ap.add_argument("--backend", choices=("gpu", "host"), default="gpu")
     args = ap.parse_args(argv)
-    scan = solid_scan(args.shape, args.views, args.height, args.width, backend=args.backend)
+    scan = solid_scan(args.shape, args.views, args.height, args.width, backend=args.backend, contours=args.contours)
     write_solid_scan(args.out_dir, scan, depth=args.depth)
     print(f"{args.shape}: {len(scan.cameras)} views of {args.width}x{args.height}, {scan.tris.shape[0]} triangles, "
           f"{len(scan.edges['lines_end_pts'])} lines, {len(scan.edges['curves_ctl_pts'])} curves, "
-          f"{int(scan.hidden.sum())} hidden samples -> {args.out_dir}")
+          f"{int(scan.hidden.sum())} hidden samples"
+          + (f", {int(scan.contours.sum())} contour pixels" if scan.contours is not None else "") + f" -> {args.out_dir}")
     return 0

@@ -490,6 +490,8 @@ def parse_args(argv):
         parser.error("--gate_edge_checks needs a depth source: --occluder or --depth_dir")
     if args.gate_edge_checks and args.occluder is not None and args.depth_dir is not None:
         parser.error("--gate_edge_checks takes one depth source: --occluder or --depth_dir, not both")
+    if args.ignore_contours and args.occluder is None:
+        parser.error("--ignore_contours needs --occluder: the mesh whose contours are predicted")
     source_path = os.path.abspath(args.source_path)                                 # ModelParams.extract (:63-66)
     opt = select_options(source_path, args.detector)()
     if args.iterations is not None:
@@ -535,8 +537,10 @@ def main(argv=None):
                 gate["occluder"] = os.path.join(dataset.source_path, args.occluder)
             if args.depth_dir is not None:
                 gate["depth_dir"] = os.path.join(dataset.source_path, args.depth_dir)
+        from .edge_extraction.reprojection import contour_options
         scores = score_scene(dataset.model_path, out["scene"], dataset.detector,
-                             **({"thin": True} if args.thin_edge_maps else {}), **gate)
+                             **({"thin": True} if args.thin_edge_maps else {}), **gate,
+                             **contour_options(args.ignore_contours, args.contour_radius_px, args.crease_deg))
         for split, res in scores.items():
             if res is not None:
                 print(scan_line(split, res["aggregate"]))

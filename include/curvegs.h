@@ -1358,6 +1358,59 @@ int cgs_sample_snap_terms_depth(int P, const float* points /*[P,3]*/, int V, con
                                 double slack, double* terms /*[P,10]*/, int32_t* views /*[P]*/, int32_t* hidden /*[P]*/,
                                 void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Occluding contours of a triangle mesh: the edges along which a view sees a smooth surface turn away, drawn into one uint8
+ * mask per view (ops/mesh_contours.py).  A contour is an edge in every image and an edge nowhere in 3D; this entry predicts
+ * where a view has one.  The reference has no counterpart.  intr, w2c as for cgs_point_mask.
+ *
+ * edges is float32 [E,4,3], device: rows (a, b, c, d), (a, b) a mesh edge shared by exactly two triangles and c, d those
+ * triangles' third vertices.  WHICH edges are candidates (the smooth ones, or all) is the caller's choice: the entry sees
+ * only the selected rows.  depth is float32 [V,height,width], device, camera z, +inf where there is no surface (usually
+ * cgs_mesh_depth followed by cgs_depth_window_max), or NULL: no gate, and slack is not read.  mask_out is uint8
+ * [V,height,width], device; the entry clears it first.  E = 0 only clears.
+ *
+ * THE RULE, frozen -- float64, one rounded operation at a time in the written order, nothing contracted into an FMA, IEEE
+ * division -- for every (row, view):
+ *   the twelve floats widened to float64; A, B, C, D = R X + T of a, b, c, d in the operation order of cgs_project_points
+ *   (the device function nv_camera_xyz of csrc/point_projection.h)
+ *   the row is SKIPPED in the view unless A2 > 0 and B2 > 0 (NaN included): there is no clipping at the camera plane
+ *   m = A x B:  m0 = A1 * B2 - A2 * B1,  m1 = A2 * B0 - A0 * B2,  m2 = A0 * B1 - A1 * B0
+ *   sc = (m0 * C0 + m1 * C1) + m2 * C2,  sd = (m0 * D0 + m1 * D1) + m2 * D2
+ *   the row is a CONTOUR iff sc * sd > 0: both triangles lie on the same side of the plane through the eye and the edge.
+ *     The test does not depend on the triangles' winding or on the order of c and d; an edge-on triangle (a zero) and a NaN
+ *     are no contour
+ *   (ua, va), (ub, vb) = fx * (X0 / X2) + cx, fy * (X1 / X2) + cy of A and B (nv_image_uv), with no in-frame test
+ *   du = ub - ua,  dv = vb - va
+ *   THE CLIP of the segment (ua, va) + t (du, dv), t in [t0, t1], to 0 <= u <= width, 0 <= v <= height: t0 = 0, t1 = 1, then
+ *   for (p, q) = (-du, ua), (du, width - ua), (-dv, va), (dv, height - va) in this order:
+ *     p == 0:  the row draws nothing if q < 0
+ *     p <  0:  r = q / p;  the row draws nothing if r > t1;  t0 = r if r > t0
+ *     p >  0:  r = q / p;  the row draws nothing if r < t0;  t1 = r if r < t1
+ *   (a NaN p or q fails every comparison and changes nothing)
+ *   dt = t1 - t0,  len = max(|dt * du|, |dt * dv|);  the row draws nothing unless len <= width + height (a NaN fails)
+ *   n = (int)ceil(2 * len): THE STEPS are k = 0 .. n, at most half a pixel apart on either axis, so two consecutive steps
+ *   never lie in pixels that are not 8-neighbours
+ *   step k:  f = k / n (0 when n = 0),  t = t0 + dt * f,  u = ua + t * du,  v = va + t * dv
+ *     dropped unless 0 <= u < width and 0 <= v < height (the projection's in-frame test; this test, not the clip, keeps
+ *     the store inside the plane -- the clip bounds n)
+ *     with depth:  z = 1 / ((1 - t) / A2 + t / B2)   (1/z is linear along the image segment, as in cgs_mesh_depth);
+ *       dropped if z > (double)depth[v][floor(v)][floor(u)] + slack -- the one occlusion rule, nv_hidden
+ *     a kept step stores the byte 1 at mask_out[view][floor(v)][floor(u)]
+ * A byte store of a constant is idempotent: no atomics, and the result does not depend on the order of the rows or on the
+ * launch geometry (one lane classifies one row of a view; a wave ballot gives the contours among 64 rows and the whole wave
+ * draws each of them, its lanes striding over the steps).
+ *
+ * Runs on the caller's stream with no allocation and no host synchronisation.  Every argument is checked, whether or not
+ * there is work: E or V < 0, a size outside [1, CGS_EDT_MAX_SIZE], with a depth plane a slack that is negative, NaN or
+ * infinite, and NULL pointers (edges only when E > 0; depth may be NULL) are CGS_ERR_INVALID_ARGUMENT, rejected before
+ * anything is launched.  Then V = 0 is a no-op.
+ * LIMITS: no near-plane clipping (a row with an end at or behind the camera plane is skipped whole); boundary edges of an
+ * open mesh have one triangle and are never rows; the silhouette edges of a general triangulation zigzag across its facets.
+ * ------------------------------------------------------------------------------------------------ */
+int cgs_mesh_contours(int E, const float* edges /*[E,4,3]*/, int V, const double* intr /*[V,4]*/,
+                      const double* w2c /*[V,12]*/, int height, int width, const float* depth /*[V,height,width] or NULL*/,
+                      double slack, uint8_t* mask_out /*[V,height,width]*/, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
