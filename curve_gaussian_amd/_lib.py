@@ -135,6 +135,13 @@ SIGNATURES = {
     "cgs_sample_support_depth": (_i, [_i, _vp, _i, _vp, _vp, _i, _i, _vp, _i, _vp, _vp, C.c_double, _vp, _vp, _vp]),
     "cgs_sample_support_oriented_depth": (_i, [_i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _i, _vp, C.c_double, _vp, _vp, _vp]),
     "cgs_sample_snap_terms_depth": (_i, [_i, _vp, _i, _vp, _vp, _i, _i, _vp, _i, _vp, _vp, C.c_double, _vp, _vp, _vp, _vp]),
+    # the seed siblings' arguments, with depth and slack after the last per-view input (bits; best for the wins) and the
+    # vote's hidden after hit
+    "cgs_voxel_votes_depth": (_i, [_i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, C.c_double, _i, _vp, _vp, _vp, _vp]),
+    "cgs_ray_claims_depth": (_i, [_i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, C.c_double, _i, _vp,
+                                  _vp]),
+    "cgs_ray_wins_depth": (_i, [_i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, C.c_double, _i, _i,
+                                _i, _vp, _vp]),
     "cgs_mesh_contours": (_i, [_i, _vp, _i, _vp, _vp, _i, _i, _vp, C.c_double, _vp, _vp]),
 }
 

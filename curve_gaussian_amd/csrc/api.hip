@@ -2005,6 +2005,70 @@ int cgs_sample_snap_terms_depth(int P, const float* points, int V, const double*
     return finish("sample_snap_terms_depth", stream_);
 }
 
+// ---- the depth-gated siblings of the three seed entries that walk the views (include/curvegs.h).  Each checks what its
+// sibling checks, in its order, with the slack right after the grid and the depth pointer among the pointers of the views.
+int cgs_voxel_votes_depth(int nx, int ny, int nz, const double* lo, const double* step, int V, const double* intr,
+                          const double* w2c, int height, int width, const uint32_t* bits, const float* depth, double slack,
+                          int accumulate, uint16_t* seen, uint16_t* hit, uint16_t* hidden, void* stream_) {
+    const bool ptrs = lo && step && seen && hit && (V == 0 || (intr && w2c && bits && depth));
+    if (!seed_views_ok("cgs_voxel_votes_depth", V, height, width) ||
+        !seed_grid_ok("cgs_voxel_votes_depth", nx, ny, nz, ptrs ? lo : nullptr, ptrs ? step : nullptr))
+        return CGS_ERR_INVALID_ARGUMENT;
+    if (!slack_ok(slack))
+        return reject("cgs_voxel_votes_depth: invalid argument (slack=%g; the slack is finite and >= 0)", slack);
+    if (!ptrs) return reject("cgs_voxel_votes_depth: invalid argument (NULL pointer)");
+    if (V == 0 && accumulate) return CGS_OK;
+    launch_voxel_votes_depth((hipStream_t)stream_, SeedGrid{{lo[0], lo[1], lo[2]}, {step[0], step[1], step[2]}, nx, ny, nz},
+                             SeedViews{V, height, width, (width + 31) / 32, intr, w2c, bits}, SeedGate{depth, slack},
+                             accumulate, seen, hit, hidden);
+    return finish("voxel_votes_depth", stream_);
+}
+
+int cgs_ray_claims_depth(int nx, int ny, int nz, const double* lo, const double* step, int M, const int32_t* index,
+                         const uint16_t* support, int V, const double* intr, const double* w2c, int height, int width,
+                         const uint32_t* bits, const float* depth, double slack, int clear, uint32_t* best, void* stream_) {
+    if (M < 0) return reject("cgs_ray_claims_depth: invalid argument (M=%d)", M);
+    if (!seed_views_ok("cgs_ray_claims_depth", V, height, width) ||
+        !seed_grid_ok("cgs_ray_claims_depth", nx, ny, nz, lo, step))
+        return CGS_ERR_INVALID_ARGUMENT;
+    if (!slack_ok(slack))
+        return reject("cgs_ray_claims_depth: invalid argument (slack=%g; the slack is finite and >= 0)", slack);
+    if (!lo || !step || (V > 0 && !best) || (M > 0 && V > 0 && (!index || !support || !intr || !w2c || !bits || !depth)))
+        return reject("cgs_ray_claims_depth: invalid argument (NULL pointer)");
+    const SeedGrid g{{lo[0], lo[1], lo[2]}, {step[0], step[1], step[2]}, nx, ny, nz};
+    const SeedViews views{V, height, width, (width + 31) / 32, intr, w2c, bits};
+    if (launch_ray_claims_depth((hipStream_t)stream_, g, views, SeedGate{depth, slack}, M, index, support, clear, best) !=
+        hipSuccess) {
+        set_error("cgs_ray_claims_depth: clearing the claims failed");
+        return CGS_ERR_HIP;
+    }
+    if (M == 0 || V == 0) return CGS_OK;
+    return finish("ray_claims_depth", stream_);
+}
+
+int cgs_ray_wins_depth(int nx, int ny, int nz, const double* lo, const double* step, int M, const int32_t* index,
+                       const uint16_t* support, int V, const double* intr, const double* w2c, int height, int width,
+                       const uint32_t* bits, const uint32_t* best, const float* depth, double slack, int window, int margin,
+                       int accumulate, uint16_t* wins, void* stream_) {
+    if (M < 0) return reject("cgs_ray_wins_depth: invalid argument (M=%d)", M);
+    if (!seed_views_ok("cgs_ray_wins_depth", V, height, width) || !seed_grid_ok("cgs_ray_wins_depth", nx, ny, nz, lo, step))
+        return CGS_ERR_INVALID_ARGUMENT;
+    if (!lo || !step)   // before the slack, the window and the margin, as in the sibling
+        return reject("cgs_ray_wins_depth: invalid argument (NULL pointer)");
+    if (!slack_ok(slack))
+        return reject("cgs_ray_wins_depth: invalid argument (slack=%g; the slack is finite and >= 0)", slack);
+    if (window < 0 || window > CGS_SEED_MAX_WINDOW || margin < 0 || margin > 65535)
+        return reject("cgs_ray_wins_depth: invalid argument (window=%d, margin=%d; the window lies in [0, %d], the margin in "
+                      "[0, 65535])", window, margin, CGS_SEED_MAX_WINDOW);
+    if (M > 0 && V > 0 && (!index || !support || !intr || !w2c || !bits || !best || !depth || !wins))
+        return reject("cgs_ray_wins_depth: invalid argument (NULL pointer)");
+    if (M == 0 || V == 0) return CGS_OK;
+    launch_ray_wins_depth((hipStream_t)stream_, SeedGrid{{lo[0], lo[1], lo[2]}, {step[0], step[1], step[2]}, nx, ny, nz},
+                          SeedViews{V, height, width, (width + 31) / 32, intr, w2c, bits}, SeedGate{depth, slack}, M, index,
+                          support, best, window, margin, accumulate, wins);
+    return finish("ray_wins_depth", stream_);
+}
+
 // ---- occluding contours of a mesh (include/curvegs.h).  The slack is checked only with a plane: without one it is not read.
 int cgs_mesh_contours(int E, const float* edges, int V, const double* intr, const double* w2c, int height, int width,
                       const float* depth, double slack, uint8_t* mask_out, void* stream_) {

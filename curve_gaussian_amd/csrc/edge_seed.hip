@@ -1,6 +1,6 @@
 // Multi-view voxel vote: where do the edge maps of a scan say the edges are?  (include/curvegs.h, cgs_pack_near_bits /
-// cgs_voxel_votes / cgs_voxel_moments / cgs_ray_claims / cgs_ray_wins.)  Every voxel centre of a regular grid is projected
-// into every view and counts the views that see it and the views in which it lands within a tolerance of a detected edge
+// cgs_voxel_votes / cgs_voxel_moments / cgs_ray_claims / cgs_ray_wins and the three _depth siblings.)  Every voxel centre
+// of a regular grid is projected into every view and counts the views that see it and the views in which it lands within a tolerance of a detected edge
 // pixel; the kept voxels around a seed then give the seed's direction through their integer second moments; on request the
 // kept voxels first claim the pixels they land on and only those that win their claims stay.  Five kernels:
 //   k_pack_near_bits   one thread per pixel of the PADDED row (32 * stride pixels, stride = ceil(W / 32) words): the bit is
@@ -14,7 +14,12 @@
 //                      wave-uniform, so the 16 doubles of a camera are scalar loads, as in visibility.hip.  For every view
 //                      that keeps the centre, seed_pixel gives its pixel and the pixel's near bit, and the kernel's own
 //                      lambda gets (v, px, py, near).  A pixel that differed between the vote and the claim would be a bug
-//                      that no tolerance hides: there is one walk for it to differ in.
+//                      that no tolerance hides: there is one walk for it to differ in.  A template over GATED: false is the
+//                      walk as it always was (nv_verdict<false> is nv_project_xyz and nothing else; the gate is not read);
+//                      true is the walk of the _depth entries -- nv_verdict<true> holds the centre's camera depth against
+//                      the view's float32 depth plane (nv_hidden, the one occlusion rule), a view that hides the centre is
+//                      not seen by the lambda and its near bit is not gathered: one float32 gather more per kept pair, one
+//                      gather of a word less per hidden pair.  The walk returns the number of views that hid the centre.
 //   k_voxel_votes      one thread per voxel, linear index with x fastest, so the lanes of a wave are neighbours along x and
 //                      gather neighbouring pixels.  The walk counts the views that keep the centre and those whose bit is
 //                      set.  Both counts stay in registers; one plain 16-bit store each at the end (a read-add-store of the
@@ -37,7 +42,10 @@
 //                      support + margin (32 bits) reaches it.  The count stays in a register; one plain 16-bit store at the
 //                      end (a read-add-store of the thread's own word with `accumulate`).  No atomics, no LDS, no barrier.
 //                      An index outside the grid (the caller's error) reads nothing, claims nothing and wins nothing.
-// Voxel, map, keep-bit and pixel offsets are 64-bit.
+//   The three kernels are templates over the same GATED; the gated k_voxel_votes stores the walk's hidden count as a third
+//   uint16 per voxel when asked (NULL allowed), under the rule of `accumulate`: seen + hidden of the gated vote is seen of
+//   the ungated one, voxel for voxel.  No atomic is added: the atomicMax of k_ray_claims stays the only one.
+// Voxel, map, keep-bit, depth and pixel offsets are 64-bit.
 #include <algorithm>
 
 #include "kernels.h"
@@ -79,13 +87,19 @@ __device__ inline void seed_centre(const SeedGrid& g, long long id, double& X, d
     Z = (double)(float)(g.lo[2] + ((double)k + 0.5) * g.step[2]);
 }
 
-// True if view `c` keeps the centre; then (px, py) is its pixel and `near` the pixel's bit in the view's packed mask.
+// True if view `c` keeps the centre and, when GATED, does not hide it (nv_verdict, point_projection.h); then (px, py) is its
+// pixel and `near` the pixel's bit in the view's packed mask.  `hid`, written only when GATED: the view keeps the centre and
+// hides it -- no word of the mask is gathered for it.
+template <bool GATED>
 __device__ inline bool seed_pixel(const NvCam& c, double X, double Y, double Z, double wd, double hd,
-                                  const unsigned int* __restrict__ view_bits, int stride, unsigned int& px, unsigned int& py,
-                                  bool& near) {
+                                  const unsigned int* __restrict__ view_bits, int stride,
+                                  const float* __restrict__ depth_plane, int width, double slack, unsigned int& px,
+                                  unsigned int& py, bool& near, bool& hid) {
 #pragma clang fp contract(off)
     double pu, pv;
-    if (!nv_project_xyz(c, X, Y, Z, wd, hd, pu, pv)) return false;
+    const NvVerdict verdict = nv_verdict<GATED>(c, X, Y, Z, wd, hd, depth_plane, width, slack, pu, pv);
+    if (GATED) hid = verdict == NV_HIDDEN;
+    if (verdict != NV_VISIBLE) return false;
     // 0 <= pu < W and 0 <= pv < H: the pixel is inside the view, its word inside the view's plane
     px = (unsigned int)floor(pu);
     py = (unsigned int)floor(pv);
@@ -94,31 +108,41 @@ __device__ inline bool seed_pixel(const NvCam& c, double X, double Y, double Z, 
     return true;
 }
 
-// The walk of the file header: f(v, px, py, near) for every view v that keeps the centre of the voxel with linear index `id`.
-template <class F>
-__device__ inline void seed_walk(const SeedGrid& g, const SeedViews& s, long long id, F&& f) {
+// The walk of the file header: f(v, px, py, near) for every view v that keeps the centre of the voxel with linear index `id`
+// and, when GATED, does not hide it.  Returns the number of views that keep the centre and hide it (0 when not GATED).
+template <bool GATED, class F>
+__device__ inline int seed_walk(const SeedGrid& g, const SeedViews& s, const SeedGate& gate, long long id, F&& f) {
 #pragma clang fp contract(off)
     double X, Y, Z;
     seed_centre(g, id, X, Y, Z);
     const double wd = (double)s.width, hd = (double)s.height;
     const size_t plane = (size_t)s.height * (size_t)s.stride;
+    const size_t image = (size_t)s.height * (size_t)s.width;
+    int n_hidden = 0;
     for (int v = 0; v < s.V; v++) {   // v is uniform: scalar loads of the camera
         NvCam c;
         nv_load_cam(c, s.intr, s.w2c, v);
         unsigned int px, py;
-        bool near;
-        if (seed_pixel(c, X, Y, Z, wd, hd, s.bits + (size_t)v * plane, s.stride, px, py, near)) f(v, px, py, near);
+        bool near, hid = false;
+        const float* __restrict__ dplane = GATED ? gate.depth + (size_t)v * image : nullptr;
+        if (seed_pixel<GATED>(c, X, Y, Z, wd, hd, s.bits + (size_t)v * plane, s.stride, dplane, s.width, gate.slack, px, py, near,
+                              hid))
+            f(v, px, py, near);
+        if (GATED) n_hidden += (int)hid;
     }
+    return n_hidden;
 }
 
+template <bool GATED>
 __global__ void __launch_bounds__(SEED_THREADS) k_voxel_votes(const SeedGrid g, const SeedViews s, int accumulate,
                                                              unsigned short* __restrict__ seen,
-                                                             unsigned short* __restrict__ hit) {
+                                                             unsigned short* __restrict__ hit, const SeedGate gate,
+                                                             unsigned short* __restrict__ hidden) {
     const long long n = (long long)g.nx * g.ny * g.nz;   // <= 2^31 - 1
     const long long id = (long long)blockIdx.x * SEED_THREADS + threadIdx.x;
     if (id >= n) return;
     int n_seen = 0, n_hit = 0;
-    seed_walk(g, s, id, [&](int, unsigned int, unsigned int, bool near) {
+    int n_hidden = seed_walk<GATED>(g, s, gate, id, [&](int, unsigned int, unsigned int, bool near) {
         n_seen++;
         n_hit += (int)near;
     });
@@ -128,6 +152,10 @@ __global__ void __launch_bounds__(SEED_THREADS) k_voxel_votes(const SeedGrid g, 
     }
     seen[id] = (unsigned short)n_seen;
     hit[id] = (unsigned short)n_hit;
+    if (GATED && hidden) {   // the third count, under the same rule
+        if (accumulate) n_hidden += hidden[id];
+        hidden[id] = (unsigned short)n_hidden;
+    }
 }
 
 __global__ void __launch_bounds__(SEED_THREADS) k_voxel_moments(int nx, int ny, int nz, int stride,
@@ -177,10 +205,11 @@ __global__ void __launch_bounds__(SEED_THREADS) k_voxel_moments(int nx, int ny, 
     }
 }
 
+template <bool GATED>
 __global__ void __launch_bounds__(SEED_THREADS) k_ray_claims(const SeedGrid g, const SeedViews s, int M,
                                                             const int* __restrict__ index,
                                                             const unsigned short* __restrict__ support,
-                                                            unsigned int* __restrict__ best) {
+                                                            unsigned int* __restrict__ best, const SeedGate gate) {
     const long long n = (long long)g.nx * g.ny * g.nz;   // <= 2^31 - 1
     const long long m = (long long)blockIdx.x * SEED_THREADS + threadIdx.x;
     if (m >= M) return;
@@ -188,7 +217,7 @@ __global__ void __launch_bounds__(SEED_THREADS) k_ray_claims(const SeedGrid g, c
     if (id < 0 || id >= n) return;   // the caller's error: claims nothing
     const unsigned int sup = support[m];
     const size_t image = (size_t)s.height * (size_t)s.width;
-    seed_walk(g, s, id, [&](int v, unsigned int px, unsigned int py, bool near) {
+    seed_walk<GATED>(g, s, gate, id, [&](int v, unsigned int px, unsigned int py, bool near) {
         if (!near) return;
         unsigned int* p = best + (size_t)v * image + (size_t)py * (size_t)s.width + (size_t)px;
         // no look before the atomic: a plain load that skips it where best already holds as much measured slower
@@ -197,11 +226,13 @@ __global__ void __launch_bounds__(SEED_THREADS) k_ray_claims(const SeedGrid g, c
     });
 }
 
+template <bool GATED>
 __global__ void __launch_bounds__(SEED_THREADS) k_ray_wins(const SeedGrid g, const SeedViews s, int M,
                                                           const int* __restrict__ index,
                                                           const unsigned short* __restrict__ support,
                                                           const unsigned int* __restrict__ best, int window, int margin,
-                                                          int accumulate, unsigned short* __restrict__ wins) {
+                                                          int accumulate, unsigned short* __restrict__ wins,
+                                                          const SeedGate gate) {
     const long long n = (long long)g.nx * g.ny * g.nz;   // <= 2^31 - 1
     const long long m = (long long)blockIdx.x * SEED_THREADS + threadIdx.x;
     if (m >= M) return;
@@ -210,7 +241,7 @@ __global__ void __launch_bounds__(SEED_THREADS) k_ray_wins(const SeedGrid g, con
     if (id >= 0 && id < n) {   // an index outside the grid is the caller's error: it wins nothing
         const unsigned int sup = (unsigned int)support[m] + (unsigned int)margin;   // <= 131070: 32 bits do not wrap
         const size_t image = (size_t)s.height * (size_t)s.width;
-        seed_walk(g, s, id, [&](int v, unsigned int px, unsigned int py, bool near) {
+        seed_walk<GATED>(g, s, gate, id, [&](int v, unsigned int px, unsigned int py, bool near) {
             if (!near) return;
             const int x0 = max((int)px - window, 0), x1 = min((int)px + window, s.width - 1);
             const int y0 = max((int)py - window, 0), y1 = min((int)py + window, s.height - 1);
@@ -238,12 +269,24 @@ void launch_pack_near_bits(hipStream_t s, int V, int height, int width, const in
     }
 }
 
-void launch_voxel_votes(hipStream_t s, SeedGrid g, SeedViews views, int accumulate, unsigned short* seen,
-                        unsigned short* hit) {
+template <bool GATED>
+static void voxel_votes_launch(hipStream_t s, SeedGrid g, SeedViews views, SeedGate gate, int accumulate, unsigned short* seen,
+                               unsigned short* hit, unsigned short* hidden) {
     const long long n = (long long)g.nx * g.ny * g.nz;
     const unsigned blocks = (unsigned)((n + SEED_THREADS - 1) / SEED_THREADS);   // <= 2^23
-    ProfScope p("voxel_votes", s);
-    hipLaunchKernelGGL(k_voxel_votes, dim3(blocks), dim3(SEED_THREADS), 0, s, g, views, accumulate, seen, hit);
+    ProfScope p(GATED ? "voxel_votes_depth" : "voxel_votes", s);
+    hipLaunchKernelGGL(k_voxel_votes<GATED>, dim3(blocks), dim3(SEED_THREADS), 0, s, g, views, accumulate, seen, hit, gate,
+                       hidden);
+}
+
+void launch_voxel_votes(hipStream_t s, SeedGrid g, SeedViews views, int accumulate, unsigned short* seen,
+                        unsigned short* hit) {
+    voxel_votes_launch<false>(s, g, views, SeedGate{nullptr, 0.0}, accumulate, seen, hit, nullptr);
+}
+
+void launch_voxel_votes_depth(hipStream_t s, SeedGrid g, SeedViews views, SeedGate gate, int accumulate, unsigned short* seen,
+                              unsigned short* hit, unsigned short* hidden) {
+    voxel_votes_launch<true>(s, g, views, gate, accumulate, seen, hit, hidden);
 }
 
 void launch_voxel_moments(hipStream_t s, int nx, int ny, int nz, const unsigned int* keep, int N, const int* centres,
@@ -254,8 +297,9 @@ void launch_voxel_moments(hipStream_t s, int nx, int ny, int nz, const unsigned 
                        radius, moments);
 }
 
-hipError_t launch_ray_claims(hipStream_t s, SeedGrid g, SeedViews views, int M, const int* index,
-                             const unsigned short* support, int clear, unsigned int* best) {
+template <bool GATED>
+static hipError_t ray_claims_launch(hipStream_t s, SeedGrid g, SeedViews views, SeedGate gate, int M, const int* index,
+                                    const unsigned short* support, int clear, unsigned int* best) {
     if (clear && views.V > 0) {
         const size_t bytes = (size_t)views.V * (size_t)views.height * (size_t)views.width * sizeof(unsigned int);
         const hipError_t e = hipMemsetAsync(best, 0, bytes, s);
@@ -263,17 +307,40 @@ hipError_t launch_ray_claims(hipStream_t s, SeedGrid g, SeedViews views, int M, 
     }
     if (M == 0 || views.V == 0) return hipSuccess;
     const unsigned blocks = (unsigned)(((long long)M + SEED_THREADS - 1) / SEED_THREADS);   // <= 2^23
-    ProfScope p("ray_claims", s);
-    hipLaunchKernelGGL(k_ray_claims, dim3(blocks), dim3(SEED_THREADS), 0, s, g, views, M, index, support, best);
+    ProfScope p(GATED ? "ray_claims_depth" : "ray_claims", s);
+    hipLaunchKernelGGL(k_ray_claims<GATED>, dim3(blocks), dim3(SEED_THREADS), 0, s, g, views, M, index, support, best, gate);
     return hipSuccess;
+}
+
+hipError_t launch_ray_claims(hipStream_t s, SeedGrid g, SeedViews views, int M, const int* index,
+                             const unsigned short* support, int clear, unsigned int* best) {
+    return ray_claims_launch<false>(s, g, views, SeedGate{nullptr, 0.0}, M, index, support, clear, best);
+}
+
+hipError_t launch_ray_claims_depth(hipStream_t s, SeedGrid g, SeedViews views, SeedGate gate, int M, const int* index,
+                                   const unsigned short* support, int clear, unsigned int* best) {
+    return ray_claims_launch<true>(s, g, views, gate, M, index, support, clear, best);
+}
+
+template <bool GATED>
+static void ray_wins_launch(hipStream_t s, SeedGrid g, SeedViews views, SeedGate gate, int M, const int* index,
+                            const unsigned short* support, const unsigned int* best, int window, int margin, int accumulate,
+                            unsigned short* wins) {
+    const unsigned blocks = (unsigned)(((long long)M + SEED_THREADS - 1) / SEED_THREADS);   // <= 2^23
+    ProfScope p(GATED ? "ray_wins_depth" : "ray_wins", s);
+    hipLaunchKernelGGL(k_ray_wins<GATED>, dim3(blocks), dim3(SEED_THREADS), 0, s, g, views, M, index, support, best, window,
+                       margin, accumulate, wins, gate);
 }
 
 void launch_ray_wins(hipStream_t s, SeedGrid g, SeedViews views, int M, const int* index, const unsigned short* support,
                      const unsigned int* best, int window, int margin, int accumulate, unsigned short* wins) {
-    const unsigned blocks = (unsigned)(((long long)M + SEED_THREADS - 1) / SEED_THREADS);   // <= 2^23
-    ProfScope p("ray_wins", s);
-    hipLaunchKernelGGL(k_ray_wins, dim3(blocks), dim3(SEED_THREADS), 0, s, g, views, M, index, support, best, window, margin,
-                       accumulate, wins);
+    ray_wins_launch<false>(s, g, views, SeedGate{nullptr, 0.0}, M, index, support, best, window, margin, accumulate, wins);
+}
+
+void launch_ray_wins_depth(hipStream_t s, SeedGrid g, SeedViews views, SeedGate gate, int M, const int* index,
+                           const unsigned short* support, const unsigned int* best, int window, int margin, int accumulate,
+                           unsigned short* wins) {
+    ray_wins_launch<true>(s, g, views, gate, M, index, support, best, window, margin, accumulate, wins);
 }
 
 }  // namespace cgs

@@ -236,6 +236,17 @@ hipError_t launch_ray_claims(hipStream_t s, SeedGrid g, SeedViews views, int M, 
                              const unsigned short* support, int clear, unsigned int* best);
 void launch_ray_wins(hipStream_t s, SeedGrid g, SeedViews views, int M, const int* index, const unsigned short* support,
                      const unsigned int* best, int window, int margin, int accumulate, unsigned short* wins);
+struct SeedGate {   // the depth gate of the _depth entries: one float32 [height, width] plane per view; passed by value
+    const float* depth;
+    double slack;
+};
+void launch_voxel_votes_depth(hipStream_t s, SeedGrid g, SeedViews views, SeedGate gate, int accumulate, unsigned short* seen,
+                              unsigned short* hit, unsigned short* hidden);
+hipError_t launch_ray_claims_depth(hipStream_t s, SeedGrid g, SeedViews views, SeedGate gate, int M, const int* index,
+                                   const unsigned short* support, int clear, unsigned int* best);
+void launch_ray_wins_depth(hipStream_t s, SeedGrid g, SeedViews views, SeedGate gate, int M, const int* index,
+                           const unsigned short* support, const unsigned int* best, int window, int margin, int accumulate,
+                           unsigned short* wins);
 
 // edge_support.hip
 void launch_edge_support(hipStream_t s, int E, int P, const float* points, const int* offsets, int V, const double* intr,

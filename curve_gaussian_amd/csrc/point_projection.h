@@ -2,7 +2,7 @@
 // keeps (novel_view.hip: cgs_project_points / cgs_render_points; edge_score.hip: cgs_point_mask; edge_seed.hip:
 // cgs_voxel_votes, cgs_ray_claims and cgs_ray_wins -- k_voxel_votes, k_ray_claims, k_ray_wins through seed_walk;
 // edge_support.hip: cgs_edge_support; edge_trim.hip: cgs_sample_support; edge_orient.hip: cgs_sample_support_oriented;
-// edge_snap.hip: cgs_sample_snap_terms -- those four and their _depth siblings through nv_verdict at the end of this file;
+// edge_snap.hip: cgs_sample_snap_terms -- those seven and their _depth siblings through nv_verdict at the end of this file;
 // edge_occlusion.hip: cgs_point_mask_depth through nv_project_xyz_depth, and
 // cgs_mesh_depth, which projects a triangle's vertices in the same operation order through nv_camera_xyz / nv_image_uv;
 // mesh_contours.hip: cgs_mesh_contours, an edge row's four vertices through the same two and nv_hidden).
@@ -89,8 +89,8 @@ __device__ inline bool nv_hidden(const float* __restrict__ depth_plane, int widt
     return c2 > d + slack;
 }
 
-// ---- the gate as a template parameter (edge_support.hip, edge_trim.hip, edge_orient.hip, edge_snap.hip; include/curvegs.h,
-// cgs_edge_support_depth and the three after it).  What one view says of one sample: not kept, kept and visible, or kept and
+// ---- the gate as a template parameter (edge_support.hip, edge_trim.hip, edge_orient.hip, edge_snap.hip, edge_seed.hip;
+// include/curvegs.h, cgs_edge_support_depth and the three after it, cgs_voxel_votes_depth and the two after it).  What one view says of one sample: not kept, kept and visible, or kept and
 // hidden.  GATED = false is nv_project_xyz and nothing else -- depth_plane and slack are not touched, no sample is hidden;
 // GATED = true is nv_project_xyz_depth followed by nv_hidden.  The two projections are the same operations in the same
 // order, so NV_VISIBLE + NV_HIDDEN of the gated form is NV_VISIBLE of the ungated one, with the same (u, v).

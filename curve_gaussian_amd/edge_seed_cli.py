@@ -1,16 +1,24 @@
 """Seed points of a scan from its edge maps, without training: the multi-view voxel vote of ``ops.edge_seed`` as a tool.
 
     python -m curve_gaussian_amd.edge_seed_cli --scan DIR [--layout emap|colmap] [--backend gpu|host] [--directions]
-                                               [--exclusive] --out seeds.ply
+                                               [--exclusive] [--occluder FILE | --depth_dir DIR] [--depth_slack S]
+                                               [--depth_window R] --out seeds.ply
 
 The cameras and maps are those ``edge_extraction.reprojection`` scores against: ``emap_cameras`` (meta_data.json) or
 ``read_colmap`` (sparse/0; ``--undistort`` as there).  The box is ``--bounds``, or ``scene.default_seed_bounds``.  The seeds
 are written as the ASCII PLY of ``edge_points.ply``; the counts are printed.  ``--directions`` also seeds the curves'
 directions: they are written as the PLY's normals (zero for an undirected seed) and the directed count is printed.
 ``--exclusive`` keeps only the voted voxels that win the pixels they claim (``--excl_window``, ``--excl_margin``,
-``--excl_win_ratio``), which suppresses the ghosts of a scan with few views; the voxels that remain are printed.  The
-defaults are untuned and there is no occlusion reasoning, with or without ``--exclusive`` (ops/edge_seed.py)."""
+``--excl_win_ratio``), which suppresses the ghosts of a scan with few views; the voxels that remain are printed.
+``--occluder`` (a mesh file inside the scan directory) or ``--depth_dir`` (a directory inside it with one
+``<image stem>.npy`` depth map per camera), at most one, gate the vote and the claims: a view whose depth plane has a surface
+more than ``--depth_slack`` (default: half the voxel diagonal) in front of a voxel's centre does not see the voxel
+(``--depth_window``: the window maximum over the planes); the hidden (voxel, view) pairs are printed.  On a scan of a solid
+the ungated vote keeps next to nothing at the default ``--min_ratio``.  The defaults are untuned, and without a depth source
+there is no occlusion reasoning, with or without ``--exclusive`` (ops/edge_seed.py); the gate's own limits -- no near-plane
+clipping, drawn solids only -- are those of ops/edge_occlusion.py."""
 import argparse
+import os
 import sys
 
 import numpy as np
@@ -45,6 +53,8 @@ def parser():
     ap.add_argument("--excl_margin", type=int, default=SD.EXCL_MARGIN)
     ap.add_argument("--excl_win_ratio", type=float, default=SD.EXCL_WIN_RATIO)
     ap.add_argument("--thin", action="store_true", help="thin the detected masks first (a thick detector response; untuned)")
+    RP.add_depth_arguments(ap)   # --occluder / --depth_dir, --depth_slack, --depth_window: gate the vote and the claims
+    ap.set_defaults(depth_slack=None)   # None: half the voxel diagonal (ops.edge_seed.default_slack), not a sample's slack
     return ap
 
 
@@ -57,11 +67,18 @@ def seed_options(args):
                 excl_win_ratio=args.excl_win_ratio)
     if args.thin:
         opts["thin"] = True
+    if args.occluder is not None or args.depth_dir is not None:
+        opts.update(occluder=args.occluder, depth_dir=args.depth_dir, depth_slack=args.depth_slack,
+                    depth_window=args.depth_window)
     return opts
 
 
-def seed_scan(scan_dir, layout="emap", detector="DexiNed", undistort=False, bounds=None, backend="gpu", **options):
-    """(seeds float64 [N,3], info) of the scan at ``scan_dir``; ``options``: seed_points' keywords."""
+def seed_scan(scan_dir, layout="emap", detector="DexiNed", undistort=False, bounds=None, backend="gpu", occluder=None,
+              depth_dir=None, **options):
+    """(seeds float64 [N,3], info) of the scan at ``scan_dir``; ``options``: seed_points' keywords.  ``occluder``: the name of
+    a mesh file inside the scan directory; ``depth_dir``: the name of a directory inside it with one ``<image stem>.npy``
+    depth map per camera (``reprojection.scan_depth_maps``); at most one, with ``depth_slack`` / ``depth_window`` among the
+    options."""
     if layout not in RP.LAYOUTS:
         raise ValueError(f"unknown layout {layout!r}: expected one of {RP.LAYOUTS}")
     points = None
@@ -76,6 +93,12 @@ def seed_scan(scan_dir, layout="emap", detector="DexiNed", undistort=False, boun
         points = pcd.points
     if bounds is None:
         bounds = IO.default_seed_bounds(layout, points)
+    if occluder is not None and depth_dir is not None:
+        raise ValueError("seed_scan: give an occluder or a depth_dir, not both")
+    if occluder is not None:
+        options["occluder"] = os.path.join(scan_dir, occluder)
+    elif depth_dir is not None:
+        options["depth_maps"] = RP.scan_depth_maps(os.path.join(scan_dir, depth_dir), cams)
     seeds, info = SD.seed_points(cams, maps, detector, bounds, backend=backend, **options)
     info["bounds"] = [np.asarray(b, np.float64).tolist() for b in bounds]
     return seeds, info
@@ -89,7 +112,9 @@ def main(argv=None):
     print(f"views {info['views']}, grid {info['dims'][0]}x{info['dims'][1]}x{info['dims'][2]}, kept voxels "
           f"{info['kept_voxels']}, cells {info['cells']}, seeds {info['seeds']}{' (capped)' if info['capped'] else ''}, "
           f"bounds {info['bounds']}" + (f", after the claims {info['exclusive_voxels']} voxels" if args.exclusive else "")
-          + (f", directed {info['directed']}" if args.directions else "") + (", detected masks thinned" if args.thin else ""))
+          + (f", directed {info['directed']}" if args.directions else "") + (", detected masks thinned" if args.thin else "")
+          + (f", depth gate hid {info['hidden_pairs']} (voxel, view) pairs at slack {info['depth_slack']:g}"
+             if "hidden_pairs" in info else ""))
     print(f"Wrote {args.out}")
     return 0
 

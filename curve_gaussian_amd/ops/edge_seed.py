@@ -52,8 +52,19 @@ Ray-exclusive claims (``exclusive=True``; frozen), the same on b
   selection  voxel m stays iff wins[m] >= need_table(excl_win_ratio)[hit[m]]; the surviving mask is what the thinning,
              the keep bits and the moments then see
 
-There is NO occlusion reasoning in the vote: a voxel behind a surface is seen by the views that look at it through the
-surface, and with few views the back-projections of unrelated edge pixels intersect in empty space ("ghosts");
+Depth gate (opt-in: ``depth=`` of ``voxel_votes`` / ``ray_claims`` / ``ray_wins``, ``occluder`` / ``depth_maps`` of
+``seed_points``; frozen), the same on both back ends bit for bit:
+  hidden     view v HIDES voxel g iff the projection keeps its centre and c2 > float64(depth[v][floor(v)][floor(u)]) + slack
+             -- the one rule of ops/edge_occlusion.py (``nv_hidden``; ``gate_view_host`` on the host), c2 the centre's
+             camera-space depth, depth float32 [V,H,W] camera z with +inf for no surface; a NaN depth hides nothing
+  votes      a hiding view counts in neither seen nor hit but in hidden[g] (uint16): seen + hidden is the ungated seen
+  claims     a listed voxel claims nothing and wins nothing in a view that hides it
+  slack      the caller's; None is ``default_slack``, half the voxel diagonal (the centre of a voxel that holds an edge can lie
+             that far behind the surface that carries the edge).  UNTUNED, drawn solids only (``seed_points``)
+
+WITHOUT a depth source there is no occlusion reasoning in the vote: a voxel behind a surface is seen by the views that look
+at it through the surface -- on a scan whose hidden lines are removed hit / seen then never reaches ``min_ratio`` on a rim
+and nothing is kept --, and with few views the back-projections of unrelated edge pixels intersect in empty space ("ghosts");
 min_views / min_ratio are its only defence.  ``exclusive=True`` adds a winner-take-all pass without depth: a voxel stays
 only if, in enough of the views in which it hits, no listed voxel near the same ray is better supported.  That removes
 most ghosts of a scan with few views (each of their pixels is explained better by a true voxel) and thins a true tube to
@@ -72,6 +83,7 @@ import torch
 
 from .. import _lib as L
 from ..edge_extraction.para_edge import EDGE_MAX_THRESHOLD
+from . import edge_occlusion as EO
 from . import edge_score as ES
 from .edge_thin import thin_masks
 from .view_chunks import check_budget, check_edge_maps, detected_lut, detected_masks, view_chunks
@@ -206,34 +218,70 @@ def voxel_centres(bounds, dims, start=0, stop=None):
     return _centres(lo, dims, step, start, dims[0] * dims[1] * dims[2] if stop is None else stop)
 
 
-def _pixels_host(pts, K, M, words, H, W, v):
+def _pixels_host(pts, K, M, words, H, W, v, gate=None, hidden_at=None):
     """(at, px, py, bit): the positions among the centres ``pts`` that view v keeps, their pixels and the pixels' near bits
-    in the packed uint32 ``words``."""
-    pu, pv, keep = ES.project_points_host(pts, K[v:v + 1], M[v:v + 1], H, W)
-    at = np.nonzero(keep[0])[0]
-    px, py = np.floor(pu[0][at]).astype(np.int64), np.floor(pv[0][at]).astype(np.int64)
+    in the packed uint32 ``words``.  ``gate``: None, or (depth float32 [V,H,W], slack) -- then ``at`` are the positions view v
+    keeps and does not hide, by ``edge_occlusion.gate_view_host``, the host's one statement of the rule; ``hidden_at``: a
+    list that receives the positions it keeps and hides."""
+    if gate is None:
+        pu, pv, keep = (x[0] for x in ES.project_points_host(pts, K[v:v + 1], M[v:v + 1], H, W))
+    else:
+        pu, pv, keep, hid = EO.gate_view_host(pts, K[v], M[v], gate[0][v], gate[1])
+        if hidden_at is not None:
+            hidden_at.append(np.nonzero(hid)[0])
+    at = np.nonzero(keep)[0]
+    px, py = np.floor(pu[at]).astype(np.int64), np.floor(pv[at]).astype(np.int64)
     return at, px, py, (words[v, py, px >> 5] >> (px & 31).astype(np.uint32)) & np.uint32(1)
 
 
-def _votes_host(lo, dims, step, K, M, words, H, W, seen, hit):
+def _votes_host(lo, dims, step, K, M, words, H, W, seen, hit, gate=None, hidden=None):
     n = dims[0] * dims[1] * dims[2]
     words = words.view(np.uint32)
     for s0 in range(0, n, HOST_SLAB):
         pts = _centres(lo, dims, step, s0, min(n, s0 + HOST_SLAB))
         for v in range(K.shape[0]):   # one view at a time: [slab] temporaries
-            at, _, _, bit = _pixels_host(pts, K, M, words, H, W, v)
+            hidden_at = [] if hidden is not None else None
+            at, _, _, bit = _pixels_host(pts, K, M, words, H, W, v, gate, hidden_at)
             seen[s0 + at] += np.uint16(1)
             hit[s0 + at] += bit.astype(np.uint16)
+            if hidden_at:
+                hidden[s0 + hidden_at[0]] += np.uint16(1)
 
 
-def voxel_votes(bounds, dims, intrinsics, w2c, bits, height, width, counts=None, backend="gpu", device=None):
+def default_slack(bounds, dims):
+    """Half the diagonal of a voxel of the grid, in world units: the default slack of the gated vote.  The point held against
+    the depth plane is a voxel's centre, and the centre of a voxel that holds an edge can lie that far behind the surface
+    that carries the edge.  UNTUNED (``seed_points``)."""
+    _, _, _, step = _grid(bounds, dims)
+    return 0.5 * float(np.sqrt((step * step).sum()))
+
+
+def _gate_args(name, depth, slack, bounds, dims, V, height, width, backend, dev=None):
+    """None without ``depth``; otherwise (depth, slack) checked by ``edge_occlusion.operator_depth`` -- a numpy array for
+    ``backend="host"``, a tensor on ``dev`` otherwise; slack None is ``default_slack``."""
+    if depth is None:
+        return None
+    return EO.operator_depth(name, depth, default_slack(bounds, dims) if slack is None else slack, V, height, width, backend, dev)
+
+
+def voxel_votes(bounds, dims, intrinsics, w2c, bits, height, width, counts=None, backend="gpu", device=None, depth=None,
+                slack=None, return_hidden=False):
     """(seen, hit): uint16 [nx ny nz] tensors, the votes of the module docstring over the views of this call.
     intrinsics [V,4] = (fx, fy, cx, cy) and w2c [V,3,4] float64 (arrays or tensors); ``bits``: ``near_bits`` of the same
     views, int32 [V,height,ceil(width/32)].  ``counts``: a (seen, hit) pair of an earlier call over the same grid -- the
     votes are added to it in place and it is returned; the views of all accumulating calls number at most 65535 (the
     caller's to keep: ``seed_points`` checks it).  ``backend="gpu"``: ``cgs_voxel_votes``, device tensors;
-    ``backend="host"``: numpy, CPU tensors."""
+    ``backend="host"``: numpy, CPU tensors.
+
+    ``depth`` (None: no gate, the call above and nothing else): float32 [V,height,width], camera z, +inf where there is no
+    surface.  A view that keeps a centre HIDES it iff c2 > float64(depth[v][floor(v)][floor(u)]) + ``slack`` (finite, >= 0;
+    None: ``default_slack``, half the voxel diagonal; ``cgs_voxel_votes_depth``): it counts in neither seen nor hit.
+    ``return_hidden`` (needs ``depth``): (seen, hit, hidden), hidden uint16 [nx ny nz] the views that keep the centre and
+    hide it -- seen + hidden is the ungated seen; ``counts`` is then a (seen, hit, hidden) triple.  depth on the host is
+    uploaded for ``backend="gpu"``."""
     _check_backend(backend)
+    if return_hidden and depth is None:
+        raise ValueError("voxel_votes: return_hidden needs depth")
     lo, _, dims, step = _grid(bounds, dims)
     height, width = ES._check_size("voxel_votes", height, width)
     V, K, M = ES._cameras(intrinsics, w2c)
@@ -241,31 +289,44 @@ def voxel_votes(bounds, dims, intrinsics, w2c, bits, height, width, counts=None,
         raise ValueError(f"voxel_votes: at most {MAX_VIEWS} views (got {V})")
     bits = _check_bits("voxel_votes", bits, V, height, width)
     n = dims[0] * dims[1] * dims[2]
+    arity = 3 if return_hidden else 2
     if counts is not None:
+        counts = tuple(counts)
+        if len(counts) != arity:
+            raise ValueError(f"voxel_votes: counts must hold {arity} tensors (got {len(counts)})")
         for c in counts:
             if not torch.is_tensor(c) or c.dtype != torch.uint16 or tuple(c.shape) != (n,) or not c.is_contiguous():
-                raise ValueError(f"voxel_votes: counts must be a pair of contiguous uint16 [{n}] tensors")
+                raise ValueError(f"voxel_votes: counts must be a pair of contiguous uint16 [{n}] tensors")   # (or a triple)
     if backend == "host":
-        seen, hit = counts if counts is not None else (torch.zeros(n, dtype=torch.uint16), torch.zeros(n, dtype=torch.uint16))
-        if seen.is_cuda or hit.is_cuda:
+        gate = _gate_args("voxel_votes", depth, slack, bounds, dims, V, height, width, "host")
+        out = counts if counts is not None else tuple(torch.zeros(n, dtype=torch.uint16) for _ in range(arity))
+        if any(c.is_cuda for c in out):
             raise ValueError("voxel_votes: backend='host' accumulates into CPU tensors")
-        _votes_host(lo, dims, step, K, M, bits.detach().cpu().numpy(), height, width, seen.numpy(), hit.numpy())
-        return seen, hit
+        _votes_host(lo, dims, step, K, M, bits.detach().cpu().numpy(), height, width, out[0].numpy(), out[1].numpy(), gate,
+                    out[2].numpy() if return_hidden else None)
+        return out
     dev = ES._device_for([bits] + list(counts or []), "voxel_votes", device)
     with L.device_guard(dev):
         if counts is not None:
-            seen, hit = counts
-            if seen.device != dev or hit.device != dev:
+            out = counts
+            if any(c.device != dev for c in out):
                 raise ValueError(f"voxel_votes: counts must be on {dev}")
         else:
-            seen = torch.empty(n, dtype=torch.uint16, device=dev)
-            hit = torch.empty(n, dtype=torch.uint16, device=dev)
+            out = tuple(torch.empty(n, dtype=torch.uint16, device=dev) for _ in range(arity))
+        gate = _gate_args("voxel_votes", depth, slack, bounds, dims, V, height, width, "gpu", dev)
         bits = bits.to(dev).contiguous()
         (Kd, Md), (lo_c, step_c) = ES.cameras_on(dev, K, M), _grid_c(lo, step)
-        rc = L.load().cgs_voxel_votes(*dims, lo_c, step_c, V, L.ptr(Kd), L.ptr(Md), height, width, L.ptr(bits),
-                                      1 if counts is not None else 0, L.ptr(seen), L.ptr(hit), L.raw_stream(dev))
-        L.check(rc, "cgs_voxel_votes")
-    return seen, hit
+        accumulate = 1 if counts is not None else 0
+        if gate is None:
+            rc = L.load().cgs_voxel_votes(*dims, lo_c, step_c, V, L.ptr(Kd), L.ptr(Md), height, width, L.ptr(bits),
+                                          accumulate, L.ptr(out[0]), L.ptr(out[1]), L.raw_stream(dev))
+            L.check(rc, "cgs_voxel_votes")
+        else:
+            rc = L.load().cgs_voxel_votes_depth(*dims, lo_c, step_c, V, L.ptr(Kd), L.ptr(Md), height, width, L.ptr(bits),
+                                                L.ptr(gate[0]), gate[1], accumulate, L.ptr(out[0]), L.ptr(out[1]),
+                                                L.ptr(out[2]) if return_hidden else None, L.raw_stream(dev))
+            L.check(rc, "cgs_voxel_votes_depth")
+    return out
 
 
 # ------------------------------------------------------------------------------------------------ selection and thinning
@@ -373,20 +434,23 @@ def _ray_args(name, bounds, dims, index, support, intrinsics, w2c, bits, height,
     return lo, dims, step, height, width, V, K, M, bits, idx, np.ascontiguousarray(sup.astype(np.uint16))
 
 
-def _hits_host(pts, K, M, words, H, W, v):
-    """(the positions among the centres ``pts`` that hit in view v, their px, their py): the rule of ``_votes_host``."""
-    at, px, py, bit = _pixels_host(pts, K, M, words, H, W, v)
+def _hits_host(pts, K, M, words, H, W, v, gate=None):
+    """(the positions among the centres ``pts`` that hit in view v, their px, their py): the rule of ``_votes_host``, with
+    its gate."""
+    at, px, py, bit = _pixels_host(pts, K, M, words, H, W, v, gate)
     near = bit != 0
     return at[near], px[near], py[near]
 
 
-def ray_claims(bounds, dims, index, support, intrinsics, w2c, bits, height, width, best=None, backend="gpu", device=None):
+def ray_claims(bounds, dims, index, support, intrinsics, w2c, bits, height, width, best=None, backend="gpu", device=None,
+               depth=None, slack=None):
     """best: int32 [V,height,width] tensor holding the uint32 claims of the module docstring (values <= 65535) over the
     views of this call.  index: integer [M] linear indices inside the grid; support: integer [M] in [0, 65535]
     (``voxel_support``); cameras and ``bits`` as for ``voxel_votes``.  ``best``: the claims of an earlier call over the
     same views -- this list's claims are raised into it in place (a list claimed piece by piece) and it is returned;
     without it the claims start from 0.  ``backend="gpu"``: ``cgs_ray_claims``, a device tensor; ``backend="host"``:
-    ``np.maximum.at``, a CPU tensor."""
+    ``np.maximum.at``, a CPU tensor.  ``depth``, ``slack``: the gate of ``voxel_votes`` (``cgs_ray_claims_depth``) -- a listed
+    voxel that a view hides claims nothing there."""
     _check_backend(backend)
     lo, dims, step, height, width, V, K, M, bits, idx, sup = _ray_args("ray_claims", bounds, dims, index, support,
                                                                        intrinsics, w2c, bits, height, width)
@@ -398,11 +462,12 @@ def ray_claims(bounds, dims, index, support, intrinsics, w2c, bits, height, widt
             best = torch.zeros((V, height, width), dtype=torch.int32)
         if best.is_cuda:
             raise ValueError("ray_claims: backend='host' claims into a CPU tensor")
+        gate = _gate_args("ray_claims", depth, slack, bounds, dims, V, height, width, "host")
         out, words = best.numpy(), bits.detach().cpu().numpy().view(np.uint32)
         for s0 in range(0, idx.size, HOST_SLAB):
             pts = _centres_of(lo, dims, step, idx[s0:s0 + HOST_SLAB].astype(np.int64))
             for v in range(V):   # one view at a time: [slab] temporaries
-                at, px, py = _hits_host(pts, K, M, words, height, width, v)
+                at, px, py = _hits_host(pts, K, M, words, height, width, v, gate)
                 np.maximum.at(out[v], (py, px), sup[s0 + at].astype(np.int32))
         return best
     dev = ES._device_for([bits] + ([best] if best is not None else []), "ray_claims", device)
@@ -415,19 +480,28 @@ def ray_claims(bounds, dims, index, support, intrinsics, w2c, bits, height, widt
         bits = bits.to(dev).contiguous()
         (Kd, Md), (lo_c, step_c) = ES.cameras_on(dev, K, M), _grid_c(lo, step)
         idx_d, sup_d = torch.from_numpy(idx).to(dev), torch.from_numpy(sup).to(dev)
-        rc = L.load().cgs_ray_claims(*dims, lo_c, step_c, idx.size, L.ptr(idx_d), L.ptr(sup_d), V, L.ptr(Kd), L.ptr(Md),
-                                     height, width, L.ptr(bits), 1 if clear else 0, L.ptr(best), L.raw_stream(dev))
-        L.check(rc, "cgs_ray_claims")
+        gate = _gate_args("ray_claims", depth, slack, bounds, dims, V, height, width, "gpu", dev)
+        if gate is None:
+            rc = L.load().cgs_ray_claims(*dims, lo_c, step_c, idx.size, L.ptr(idx_d), L.ptr(sup_d), V, L.ptr(Kd), L.ptr(Md),
+                                         height, width, L.ptr(bits), 1 if clear else 0, L.ptr(best), L.raw_stream(dev))
+            L.check(rc, "cgs_ray_claims")
+        else:
+            rc = L.load().cgs_ray_claims_depth(*dims, lo_c, step_c, idx.size, L.ptr(idx_d), L.ptr(sup_d), V, L.ptr(Kd),
+                                               L.ptr(Md), height, width, L.ptr(bits), L.ptr(gate[0]), gate[1],
+                                               1 if clear else 0, L.ptr(best), L.raw_stream(dev))
+            L.check(rc, "cgs_ray_claims_depth")
     return best
 
 
 def ray_wins(bounds, dims, index, support, intrinsics, w2c, bits, best, height, width, window=EXCL_WINDOW,
-             margin=EXCL_MARGIN, counts=None, backend="gpu", device=None):
+             margin=EXCL_MARGIN, counts=None, backend="gpu", device=None, depth=None, slack=None):
     """wins: uint16 [M] tensor, the wins of the module docstring over the views of this call.  ``best``: ``ray_claims`` of
     ALL listed voxels over the same views, int32 [V,height,width]; ``window`` an integer in [0, SEED_MAX_WINDOW],
     ``margin`` an integer in [0, 65535].  ``counts``: the wins of an earlier call over the same list -- this call's are
     added to it in place and it is returned (the views of all accumulating calls number at most 65535).
-    ``backend="gpu"``: ``cgs_ray_wins``, a device tensor; ``backend="host"``: numpy, a CPU tensor."""
+    ``backend="gpu"``: ``cgs_ray_wins``, a device tensor; ``backend="host"``: numpy, a CPU tensor.  ``depth``, ``slack``: the
+    gate of ``voxel_votes`` (``cgs_ray_wins_depth``) -- a listed voxel that a view hides wins nothing there; ``best`` must
+    then be the claims under the same gate."""
     _check_backend(backend)
     lo, dims, step, height, width, V, K, M, bits, idx, sup = _ray_args("ray_wins", bounds, dims, index, support, intrinsics,
                                                                        w2c, bits, height, width)
@@ -445,10 +519,11 @@ def ray_wins(bounds, dims, index, support, intrinsics, w2c, bits, best, height, 
             raise ValueError("ray_wins: backend='host' accumulates into a CPU tensor")
         out, words = wins.numpy(), bits.detach().cpu().numpy().view(np.uint32)
         claims = best.detach().cpu().numpy().view(np.uint32)
+        gate = _gate_args("ray_wins", depth, slack, bounds, dims, V, height, width, "host")
         for s0 in range(0, idx.size, HOST_SLAB):
             pts = _centres_of(lo, dims, step, idx[s0:s0 + HOST_SLAB].astype(np.int64))
             for v in range(V):   # one view at a time: [slab] temporaries
-                at, px, py = _hits_host(pts, K, M, words, height, width, v)
+                at, px, py = _hits_host(pts, K, M, words, height, width, v, gate)
                 x0, x1 = np.maximum(px - window, 0), np.minimum(px + window, width - 1)
                 y0, y1 = np.maximum(py - window, 0), np.minimum(py + window, height - 1)
                 top = np.zeros(at.size, np.int64)
@@ -470,10 +545,17 @@ def ray_wins(bounds, dims, index, support, intrinsics, w2c, bits, best, height, 
         bits, best = bits.to(dev).contiguous(), best.to(dev).contiguous()
         (Kd, Md), (lo_c, step_c) = ES.cameras_on(dev, K, M), _grid_c(lo, step)
         idx_d, sup_d = torch.from_numpy(idx).to(dev), torch.from_numpy(sup).to(dev)
-        rc = L.load().cgs_ray_wins(*dims, lo_c, step_c, idx.size, L.ptr(idx_d), L.ptr(sup_d), V, L.ptr(Kd), L.ptr(Md),
-                                   height, width, L.ptr(bits), L.ptr(best), window, margin, 1 if counts is not None else 0,
-                                   L.ptr(wins), L.raw_stream(dev))
-        L.check(rc, "cgs_ray_wins")
+        gate = _gate_args("ray_wins", depth, slack, bounds, dims, V, height, width, "gpu", dev)
+        if gate is None:
+            rc = L.load().cgs_ray_wins(*dims, lo_c, step_c, idx.size, L.ptr(idx_d), L.ptr(sup_d), V, L.ptr(Kd), L.ptr(Md),
+                                       height, width, L.ptr(bits), L.ptr(best), window, margin,
+                                       1 if counts is not None else 0, L.ptr(wins), L.raw_stream(dev))
+            L.check(rc, "cgs_ray_wins")
+        else:
+            rc = L.load().cgs_ray_wins_depth(*dims, lo_c, step_c, idx.size, L.ptr(idx_d), L.ptr(sup_d), V, L.ptr(Kd), L.ptr(Md),
+                                             height, width, L.ptr(bits), L.ptr(best), L.ptr(gate[0]), gate[1], window, margin,
+                                             1 if counts is not None else 0, L.ptr(wins), L.raw_stream(dev))
+            L.check(rc, "cgs_ray_wins_depth")
     return wins
 
 
@@ -619,7 +701,8 @@ def seed_points(cameras, edge_maps_u8, detector, bounds, grid=128, tol_px=2, min
                 max_seeds=20000, edge_threshold=EDGE_MAX_THRESHOLD, backend="gpu", device=None, budget_bytes=None,
                 directions=False, dir_radius=DIR_RADIUS, dir_min_support=DIR_MIN_SUPPORT,
                 dir_min_linearity=DIR_MIN_LINEARITY, exclusive=False, excl_window=EXCL_WINDOW, excl_margin=EXCL_MARGIN,
-                excl_win_ratio=EXCL_WIN_RATIO, thin=False):
+                excl_win_ratio=EXCL_WIN_RATIO, thin=False, occluder=None, depth_maps=None, depth_slack=None,
+                depth_window=EO.DEPTH_WINDOW):
     """cameras: ``NovelViewCamera`` s; edge_maps_u8: one uint8 [H,W] map per camera (a list or an [V,H,W] array), the
     stored bytes of the detector's maps, as ``score_edges`` takes them.  bounds = (lo, hi) of the box to search.
 
@@ -630,9 +713,35 @@ def seed_points(cameras, edge_maps_u8, detector, bounds, grid=128, tol_px=2, min
     at a time; the votes accumulate across the chunks, so the result does not depend on the chunking.
 
     Returns (seeds float64 [N,3], info) with info = {"dims", "voxels", "views", "kept_voxels", "cells", "seeds", "capped",
-    "backend"}.  THE DEFAULTS ARE UNTUNED (no scan has been measured against them), the vote has no occlusion reasoning
-    (``exclusive=True`` suppresses ghosts without depth, see below), and the curve direction is not seeded unless
-    ``directions=True``.  ``backend``: "gpu" (HIP; ``device``) or "host" (numpy).
+    "backend"}.  THE DEFAULTS ARE UNTUNED (no scan has been measured against them), the vote reasons about occlusion only
+    when it is given a depth source (below; ``exclusive=True`` suppresses ghosts without depth), and the curve direction is
+    not seeded unless ``directions=True``.  ``backend``: "gpu" (HIP; ``device``) or "host" (numpy).
+
+    Depth (opt-in; at most one of the two, with the meaning and the checks of ``edge_support``): ``occluder`` -- float32
+    [F,3,3] triangles or the path of an .obj / .ply mesh -- or ``depth_maps`` -- one float [H,W] array of camera z per
+    camera -- give every chunk of views its depth planes (``edge_occlusion.ChunkDepth``: the window maximum of radius
+    ``depth_window``, 8 bytes per pixel more, in both sweeps), and a view whose plane has a surface more than
+    ``depth_slack`` in front of a voxel's centre does not see the voxel: it counts in neither seen nor hit, claims nothing
+    and wins nothing (``voxel_votes``, ``ray_claims``, ``ray_wins`` with ``depth=``).  On a scan whose hidden lines are
+    removed -- every real scan of a solid -- the ungated vote counts the views that look at a rim through the solid in seen,
+    hit / seen stays below ``min_ratio`` and nothing is kept; the gate is the way out that lets no ghosts in.
+    ``depth_slack=None`` is HALF THE VOXEL DIAGONAL (``default_slack``): the centre of a voxel that holds an edge can lie
+    that far behind the surface that carries the edge, and ``edge_occlusion.DEPTH_SLACK``, made for samples, is far too
+    tight for a voxel.  UNTUNED: one host prototype on the drawn solids of scene/solid_scan.py, no real scan -- unit-cube
+    bounds, grid 64 (voxel diagonal 0.0271), 24 views of 240x320, tol_px 2, min_views 3, min_ratio 0.8, window 1, the scan's
+    own z-buffer as depth maps, ground truth sampled at 0.005; "uncovered" = ground-truth samples with no kept centre
+    within two diagonals, "far" = kept centres farther than 0.02 from the ground truth:
+
+        solid      kept, ungated  uncovered, ungated  kept, gated  uncovered, gated  worst sample->kept, gated  far, gated
+        box                   22         961 of 1192          903                 0                      0.012           0
+        l_bracket             41         974 of 1430          960                 0                     0.0102           1
+        cylinder               0          all of 752          541                 0                      0.017           0
+
+    A slack of 1 or 2 diagonals still covers every sample and lets 15 far voxels through on l_bracket; ungated at
+    min_ratio 0.5 every sample is covered too, with 38 far voxels on the box.  info then also holds the keys of
+    ``ChunkDepth.settings()`` ("occluder" or "depth_maps", "depth_slack", "depth_window") and "hidden_pairs", the
+    (voxel, view) pairs the gate hid, summed over the grid.  With neither source nothing changes: no key is added.  The
+    gate's limits are those of ops/edge_occlusion.py: no near-plane clipping, concave edges can be hidden by their own faces.
 
     ``directions=True``: the kept voxels within ``dir_radius`` voxels of every seed's centre voxel give its direction
     (``keep_bits``, ``voxel_moments`` on ``backend``, ``seed_directions(dir_min_support, dir_min_linearity)``; module
@@ -646,7 +755,7 @@ def seed_points(cameras, edge_maps_u8, detector, bounds, grid=128, tol_px=2, min
     EXCL_BYTES_PER_PIXEL bytes per pixel of ``budget_bytes``, and the wins accumulate across the chunks, so the result
     does not depend on the chunking.  The thinning, the keep bits and the moments see the surviving mask; info
     additionally holds "exclusive_voxels", the voxels that remain ("kept_voxels" keeps its meaning).  These three
-    defaults are untuned too; there is still no depth.
+    defaults are untuned too; the pass itself uses no depth beyond the gate above, when that is given.
 
     ``thin=True``: every chunk's detected masks go through ``edge_thin.thin_masks`` on the same back end before the
     transform (a detector's response several pixels wide widens the near band by half its width; 2 bytes per pixel,
@@ -668,12 +777,19 @@ def seed_points(cameras, edge_maps_u8, detector, bounds, grid=128, tol_px=2, min
     _grid(bounds, dims)
     need_table(min_ratio, 0)
     budget = check_budget("seed_points", budget_bytes, BYTE_BUDGET)
+    gate = EO.ChunkDepth("seed_points", cameras, occluder, depth_maps,
+                         default_slack(bounds, dims) if depth_slack is None else depth_slack, depth_window)
     if backend == "gpu":
         device = ES._device_for([], "seed_points", device)
+    gate.to(backend, device)
     n = dims[0] * dims[1] * dims[2]
     on = {"backend": backend, "device": device}
+
+    def gated(H, W, sel, intr, w2c):   # the gate's arguments of one chunk of views: its planes are built here, per chunk
+        return {"depth": gate.planes(H, W, sel, intr, w2c), "slack": gate.slack} if gate.gated else {}
+
     counts, near = None, {}   # near: every view's near bits of the first sweep, for the second
-    for H, W, sel, intr, w2c in view_chunks(cameras, BYTES_PER_PIXEL, budget):
+    for H, W, sel, intr, w2c in view_chunks(cameras, BYTES_PER_PIXEL + gate.bytes_per_pixel, budget):
         det = detected_masks(lut, maps, sel)
         if thin:
             det = thin_masks(det, **on)
@@ -681,23 +797,25 @@ def seed_points(cameras, edge_maps_u8, detector, bounds, grid=128, tol_px=2, min
         del det
         bits = near_bits(d2, tol_px, **on)
         del d2
-        counts = voxel_votes(bounds, dims, intr, w2c, bits, H, W, counts=counts, **on)
+        counts = voxel_votes(bounds, dims, intr, w2c, bits, H, W, counts=counts, return_hidden=gate.gated,
+                             **gated(H, W, sel, intr, w2c), **on)
         if exclusive:
             near.update(zip(sel, bits))
     if counts is None:   # no view: nothing is seen
-        counts = (torch.zeros(n, dtype=torch.uint16), torch.zeros(n, dtype=torch.uint16))
-    seen, hit = (c.cpu().numpy() for c in counts)
+        counts = tuple(torch.zeros(n, dtype=torch.uint16) for _ in range(3 if gate.gated else 2))
+    seen, hit = (c.cpu().numpy() for c in counts[:2])
     keep = select_voxels(seen, hit, min_views, min_ratio)
     kept_voxels = int(np.count_nonzero(keep))
     if exclusive:   # the second sweep: the kept voxels claim their pixels, chunk of views by chunk of views
         index = np.nonzero(keep)[0].astype(np.int32)
         support = voxel_support(seen, hit, index)
         wins = None
-        for H, W, sel, intr, w2c in view_chunks(cameras, EXCL_BYTES_PER_PIXEL, budget):
+        for H, W, sel, intr, w2c in view_chunks(cameras, EXCL_BYTES_PER_PIXEL + gate.bytes_per_pixel, budget):
             args = (bounds, dims, index, support, intr, w2c, torch.stack([near[v] for v in sel]))
-            best = ray_claims(*args, H, W, **on)
-            wins = ray_wins(*args, best, H, W, window=excl_window, margin=excl_margin, counts=wins, **on)
-            del best
+            planes = gated(H, W, sel, intr, w2c)
+            best = ray_claims(*args, H, W, **planes, **on)
+            wins = ray_wins(*args, best, H, W, window=excl_window, margin=excl_margin, counts=wins, **planes, **on)
+            del best, planes
         del near
         if wins is None:   # no view
             wins = torch.zeros(index.size, dtype=torch.uint16)
@@ -708,6 +826,9 @@ def seed_points(cameras, edge_maps_u8, detector, bounds, grid=128, tol_px=2, min
             "cells": cells["cells"], "seeds": int(seeds.shape[0]), "capped": cells["capped"], "backend": backend}
     if thin:
         info["thin"] = True
+    if gate.gated:
+        info.update(gate.settings())
+        info["hidden_pairs"] = int(counts[2].cpu().numpy().astype(np.int64).sum())
     if exclusive:
         info["exclusive_voxels"] = int(np.count_nonzero(keep))
     if directions:

@@ -180,7 +180,8 @@ def edge_vote_point_cloud(cameras, detector, bounds, rng=None, **options) -> Bas
     ``ops.edge_seed.seed_points`` over ``bounds`` = (lo, hi), every view voting with the camera it is trained with
     (``reprojection.scene_cameras``).  ``options``: seed_points' keywords (grid, tol_px, min_views, min_ratio, cell,
     max_seeds, edge_threshold, backend, device, budget_bytes, directions, dir_radius, dir_min_support,
-    dir_min_linearity, exclusive, excl_window, excl_margin, excl_win_ratio, thin).  Colours as grid_point_cloud's.  The normals are zeros, or with ``directions=True`` the seeded
+    dir_min_linearity, exclusive, excl_window, excl_margin, excl_win_ratio, thin, occluder, depth_maps, depth_slack,
+    depth_window).  Colours as grid_point_cloud's.  The normals are zeros, or with ``directions=True`` the seeded
     directions (unit rows, zero rows for undirected seeds).  No seed is a ValueError that names the bounds and the
     counts: there is no fallback to another cloud."""
     from ..edge_extraction.reprojection import scene_cameras

@@ -499,8 +499,12 @@ class Scene:
     the SfM cloud for COLMAP); the vote runs on the GPU when `device` is one, on the host otherwise, unless ``backend``
     says so.  With ``"directions": True`` among them the vote also seeds the curves' directions: the cloud's normals hold
     them and are handed to ``create_from_pcd``.  With ``"exclusive": True`` only the voted voxels that win the pixels they
-    claim give seeds (fewer ghosts from few views; still no depth).  No seed, or an unknown ``init``, is a ValueError:
-    there is no fallback."""
+    claim give seeds (fewer ghosts from few views; no depth of its own).  With ``"occluder"`` -- triangles, or the name of a
+    mesh file inside ``source_path`` -- or ``"depth_dir"`` -- the name of a directory inside it with one
+    ``<image stem>.npy`` depth map per training camera (``reprojection.scan_depth_maps``) --, at most one, and optionally
+    ``"depth_slack"`` / ``"depth_window"``, the vote and the claims are depth-gated (``seed_points``: without a depth source
+    the vote keeps next to nothing on a scan of a solid; untuned, no near-plane clipping).  No seed, or an unknown ``init``,
+    is a ValueError: there is no fallback."""
 
     def __init__(self, source_path, gaussians, detector="DexiNed", num_pts_per_axis=15, cameras_extent=None, rng=None,
                  device=None, eval=False, llffhold=8, images=None, resolution=-1, undistort=False, init="reference",
@@ -538,6 +542,14 @@ class Scene:
             if opts["backend"] == "gpu" and on_gpu:
                 opts.setdefault("device", device)
             directed = bool(opts.get("directions", False))
+            if isinstance(opts.get("occluder"), (str, os.PathLike)):
+                opts["occluder"] = os.path.join(source_path, opts["occluder"])
+            depth_dir = opts.pop("depth_dir", None)
+            if depth_dir is not None:
+                if opts.get("occluder") is not None or opts.get("depth_maps") is not None:
+                    raise ValueError("Scene: init_options take one depth source: occluder, depth_dir or depth_maps")
+                from ..edge_extraction.reprojection import scan_depth_maps, scene_cameras
+                opts["depth_maps"] = scan_depth_maps(os.path.join(source_path, depth_dir), scene_cameras(self.train_cameras)[0])
             self.point_cloud = dataset_io.edge_vote_point_cloud(self.train_cameras, detector, bounds, rng, **opts)
         if device is not None:
             moved = {id(c): c.to(device) for c in self.train_cameras + self.test_cameras}

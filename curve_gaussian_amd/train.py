@@ -4,7 +4,7 @@
     python -m curve_gaussian_amd.train -s SCAN -m OUT [--iterations N] [--backend graphed|direct|autograd|torch]
                                        [--draw_snapshots] [--topology_backend host|gpu] [--report_dir DIR] [--undistort]
                                        [--init reference|edge_votes] [--init_directions] [--init_exclusive]
-                                       [--thin_edge_maps]
+                                       [--init_occluder FILE | --init_depth_dir DIR] [--thin_edge_maps]
 
 The loop keeps the reference's order.  Per iteration: learning rate, SH degree every 1000 iterations, a random view without
 replacement, render + losses + every regulariser + backward (one ``TrainStep`` call), densification statistics before
@@ -321,8 +321,8 @@ def build_parser():
                         "SIMPLE_RADIAL, RADIAL and FULL_OPENCV cameras too); without it distortion is ignored, as in the reference")
     p.add_argument("--init", choices=("reference", "edge_votes"), default="reference",
                    help="the seed of the curves: the reference's (the 15^3 grid, or the SfM cloud of a COLMAP scan) or a "
-                        "multi-view voxel vote of the training views' edge maps (untuned defaults; no occlusion reasoning, "
-                        "see --init_exclusive)")
+                        "multi-view voxel vote of the training views' edge maps (untuned defaults; occlusion reasoning only "
+                        "with --init_occluder / --init_depth_dir; see also --init_exclusive)")
     p.add_argument("--init_grid", type=int, default=None, help="edge_votes: voxels along the longest side of the box")
     p.add_argument("--init_tol_px", type=float, default=None, help="edge_votes: pixel distance to a detected edge that votes")
     p.add_argument("--init_min_views", type=int, default=None, help="edge_votes: views that must see a voxel")
@@ -338,13 +338,24 @@ def build_parser():
                    help="edge_votes: (l2 - l1) / l2 of the voxels' scatter a seed needs to be given a direction")
     p.add_argument("--init_exclusive", action="store_true",
                    help="edge_votes: keep only the voted voxels that win the pixels they claim -- suppresses the ghosts of a "
-                        "scan with few views (untuned defaults; still no depth)")
+                        "scan with few views (untuned defaults; no depth of its own: see --init_occluder)")
     p.add_argument("--init_excl_window", type=int, default=None,
                    help="edge_votes: pixels around a voxel's pixel in which a better supported voxel beats it")
     p.add_argument("--init_excl_margin", type=int, default=None,
                    help="edge_votes: support (of 65535) by which a voxel may fall short of the best claim and still win")
     p.add_argument("--init_excl_win_ratio", type=float, default=None,
                    help="edge_votes: share of the views a voxel hits in that it must win")
+    p.add_argument("--init_occluder", default=None, metavar="FILE",
+                   help="edge_votes: a mesh file inside the scan directory (mesh.ply, .obj); a view that sees a voxel's centre "
+                        "behind it does not count the voxel as seen -- without a depth source the vote keeps next to nothing "
+                        "on a scan of a solid (untuned; no near-plane clipping)")
+    p.add_argument("--init_depth_dir", default=None, metavar="DIR",
+                   help="edge_votes: a directory inside the scan holding <image stem>.npy depth maps (camera z) instead of a mesh")
+    p.add_argument("--init_depth_slack", type=float, default=None,
+                   help="edge_votes: world units a voxel's centre may lie behind the surface (default: half the voxel diagonal; "
+                        "untuned)")
+    p.add_argument("--init_depth_window", type=int, default=None,
+                   help="edge_votes: radius of the window maximum over the depth planes (untuned)")
     p.add_argument("--init_bounds", nargs=6, type=float, default=None, metavar=("X0", "Y0", "Z0", "X1", "Y1", "Z1"),
                    help="edge_votes: the box to search (default: the reference's box, or the trimmed extent of the SfM cloud)")
     p.add_argument("--iterations", type=int, default=None)
@@ -490,6 +501,8 @@ def parse_args(argv):
         parser.error("--gate_edge_checks needs a depth source: --occluder or --depth_dir")
     if args.gate_edge_checks and args.occluder is not None and args.depth_dir is not None:
         parser.error("--gate_edge_checks takes one depth source: --occluder or --depth_dir, not both")
+    if args.init_occluder is not None and args.init_depth_dir is not None:
+        parser.error("--init edge_votes takes one depth source: --init_occluder or --init_depth_dir, not both")
     if args.ignore_contours and args.occluder is None:
         parser.error("--ignore_contours needs --occluder: the mesh whose contours are predicted")
     source_path = os.path.abspath(args.source_path)                                 # ModelParams.extract (:63-66)
@@ -502,7 +515,9 @@ def parse_args(argv):
                                       ("dir_radius", args.init_dir_radius), ("dir_min_support", args.init_dir_min_support),
                                       ("dir_min_linearity", args.init_dir_min_linearity),
                                       ("excl_window", args.init_excl_window), ("excl_margin", args.init_excl_margin),
-                                      ("excl_win_ratio", args.init_excl_win_ratio)) if v is not None}
+                                      ("excl_win_ratio", args.init_excl_win_ratio), ("occluder", args.init_occluder),
+                                      ("depth_dir", args.init_depth_dir), ("depth_slack", args.init_depth_slack),
+                                      ("depth_window", args.init_depth_window)) if v is not None}
     if args.init_directions:
         init_options["directions"] = True
     if args.init_exclusive:

@@ -881,8 +881,9 @@ int cgs_edge_score_reduce(int V, int height, int width, const uint8_t* pred_mask
  * Multi-view voxel vote: a seed for the curves from the scan's own edge maps.  Every voxel centre of a regular grid is
  * projected into every view; a voxel records in how many views it lies inside the image and in how many of those it lands
  * within a tolerance of a detected edge pixel.  The reference has no counterpart (it seeds a fixed 15^3 grid, or the SfM
- * cloud).  There is no occlusion reasoning in the vote (cgs_ray_claims / cgs_ray_wins below refine its selection without
- * depth).  Both entry points: caller's stream, no allocation, no host synchronisation, no atomics, results independent of
+ * cloud).  There is no occlusion reasoning in these entries (cgs_ray_claims / cgs_ray_wins below refine the selection without
+ * depth); cgs_voxel_votes_depth, cgs_ray_claims_depth and cgs_ray_wins_depth, documented after cgs_sample_snap_terms_depth
+ * further down, are the same three held against a depth plane per view.  Both entry points: caller's stream, no allocation, no host synchronisation, no atomics, results independent of
  * the launch geometry.
  *
  * Grid: lo, step (host, float64 [3]; step = (hi - lo) / dims, formed by the caller) and dims (nx, ny, nz), each >= 1.
@@ -1357,6 +1358,62 @@ int cgs_sample_snap_terms_depth(int P, const float* points /*[P,3]*/, int V, con
                                 int cap2, const double* dist_lut /*[cap2+1]*/, const float* depth /*[V,height,width]*/,
                                 double slack, double* terms /*[P,10]*/, int32_t* views /*[P]*/, int32_t* hidden /*[P]*/,
                                 void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The depth gate on the edge vote: cgs_voxel_votes, cgs_ray_claims and cgs_ray_wins (above, beside cgs_pack_near_bits), each
+ * with the occlusion rule of cgs_point_mask_depth.  Opt-in; the ungated entries are unchanged to the bit.  Why: a voxel on a
+ * rim projects into every view and is detected only where the rim is visible, so on a scan with its hidden lines removed the
+ * views that look at it through the solid count in seen and hit / seen never reaches a sensible ratio.  Each entry takes the
+ * arguments of its sibling, with their meaning, plus -- after the last per-view input --
+ *   depth   float32 [V,height,width], device: camera z per view, +inf where there is no surface (cgs_mesh_depth followed by
+ *           cgs_depth_window_max, or the caller's own maps); height and width are those of bits
+ *   slack   float64, finite and >= 0, in the units of depth.  The point that is held against depth is the voxel's CENTRE,
+ *           which can lie half a voxel diagonal behind the surface that carries the edge: the slack is the caller's, and a
+ *           sample's slack (2 x the sampling step) is far too tight for a voxel
+ * THE RULE is the one of the four entries above: a (centre, view) pair that the projection keeps -- the float32 centre of
+ * cgs_voxel_votes, the same device function, the same operation order -- is HIDDEN iff
+ *   c2 > (double)depth[v][floor(v_px)][floor(u_px)] + slack                      (one float64 addition, one comparison)
+ * (nv_hidden, csrc/point_projection.h).  A hidden pair counts as NOT SEEN: its near bit is not read.  A NaN depth hides
+ * nothing; with an all-+inf depth the outputs are the sibling's.
+ *
+ * cgs_voxel_votes_depth: seen[g] = the views that keep the centre and do not hide it, hit[g] = those of them whose near bit
+ * is set, hidden[g] = the views that keep the centre and hide it: uint16 [nx ny nz], device, or NULL.  All three follow
+ * `accumulate` (stored, or added to what they hold).  seen + hidden is the sibling's seen, voxel for voxel.  V = 0 as in the
+ * sibling: with accumulate == 0 the counts (hidden too, when given) are zeroed and intr, w2c, bits and depth may be NULL; with
+ * accumulate != 0 it is a no-op.
+ *
+ * cgs_ray_claims_depth / cgs_ray_wins_depth: a listed voxel HITS in a view only if the view does not hide it -- hidden, it
+ * claims nothing there and wins nothing there.  A voxel hidden in every view leaves best untouched and has 0 wins.  best of
+ * cgs_ray_wins_depth must be the gated claims of all listed voxels for the same depth and slack.  clear, accumulate, M = 0
+ * and V = 0 as in the siblings.
+ *
+ * The three kernels are the siblings' own bodies -- one walk over the views, shared by the three and instantiated with the
+ * gate, so a vote, a claim and a win cannot disagree on a pixel or a verdict; integers on uncontracted float64, no atomics
+ * beyond the sibling's integer maximum, no result depends on the launch geometry.  The gate costs one float32 gather per kept
+ * pair and saves a hidden pair its gather from the masks.  Caller's stream, no allocation, no host synchronisation.  Every
+ * argument is checked as the sibling checks it; in addition a slack that is negative, NaN or infinite and -- where the
+ * sibling needs bits -- a NULL depth are CGS_ERR_INVALID_ARGUMENT, rejected before anything is launched or cleared.
+ * LIMITS, those of the rule: no near-plane clipping in the z-buffer that usually draws depth; a voxel on a concave edge lies
+ * behind both of its faces in the views that see it at a grazing angle; the window and the slack are untuned, checked on the
+ * drawn solids of scene/solid_scan.py only.  cgs_voxel_moments and cgs_pack_near_bits have no gate (neither walks the views
+ * of a voxel), and cgs_edge_visibility, the control-point check, is still ungated.
+ * ------------------------------------------------------------------------------------------------ */
+int cgs_voxel_votes_depth(int nx, int ny, int nz, const double* lo /*host, [3]*/, const double* step /*host, [3]*/, int V,
+                          const double* intr /*[V,4]*/, const double* w2c /*[V,12]*/, int height, int width,
+                          const uint32_t* bits /*[V,height,ceil(width/32)]*/, const float* depth /*[V,height,width]*/,
+                          double slack, int accumulate, uint16_t* seen /*[nx ny nz]*/, uint16_t* hit /*[nx ny nz]*/,
+                          uint16_t* hidden /*[nx ny nz] or NULL*/, void* stream);
+int cgs_ray_claims_depth(int nx, int ny, int nz, const double* lo /*host, [3]*/, const double* step /*host, [3]*/, int M,
+                         const int32_t* index /*[M]*/, const uint16_t* support /*[M]*/, int V, const double* intr /*[V,4]*/,
+                         const double* w2c /*[V,12]*/, int height, int width,
+                         const uint32_t* bits /*[V,height,ceil(width/32)]*/, const float* depth /*[V,height,width]*/,
+                         double slack, int clear, uint32_t* best /*[V,height,width]*/, void* stream);
+int cgs_ray_wins_depth(int nx, int ny, int nz, const double* lo /*host, [3]*/, const double* step /*host, [3]*/, int M,
+                       const int32_t* index /*[M]*/, const uint16_t* support /*[M]*/, int V, const double* intr /*[V,4]*/,
+                       const double* w2c /*[V,12]*/, int height, int width,
+                       const uint32_t* bits /*[V,height,ceil(width/32)]*/, const uint32_t* best /*[V,height,width]*/,
+                       const float* depth /*[V,height,width]*/, double slack, int window, int margin, int accumulate,
+                       uint16_t* wins /*[M]*/, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Occluding contours of a triangle mesh: the edges along which a view sees a smooth surface turn away, drawn into one uint8
