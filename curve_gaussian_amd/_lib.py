@@ -143,6 +143,9 @@ SIGNATURES = {
     "cgs_ray_wins_depth": (_i, [_i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, C.c_double, _i, _i,
                                 _i, _vp, _vp]),
     "cgs_mesh_contours": (_i, [_i, _vp, _i, _vp, _vp, _i, _i, _vp, C.c_double, _vp, _vp]),
+    # the siblings with near before the output
+    "cgs_mesh_depth_clipped": (_i, [_i, _vp, _i, _vp, _vp, _i, _i, C.c_double, _vp, _vp]),
+    "cgs_mesh_contours_clipped": (_i, [_i, _vp, _i, _vp, _vp, _i, _i, _vp, C.c_double, C.c_double, _vp, _vp]),
 }
 
 

@@ -2088,4 +2088,45 @@ int cgs_mesh_contours(int E, const float* edges, int V, const double* intr, cons
     return finish("mesh_contours", stream_);
 }
 
+// ---- near-plane clipping (include/curvegs.h): the siblings' checks in their order, plus the plane itself.
+static bool near_ok(double near) { return near > 0.0 && !std::isinf(near); }   // a NaN fails the comparison
+
+int cgs_mesh_depth_clipped(int F, const float* tris, int V, const double* intr, const double* w2c, int height, int width,
+                           double near, float* depth, void* stream_) {
+    if (F < 0 || V < 0) return reject("cgs_mesh_depth_clipped: invalid argument (F=%d, V=%d)", F, V);
+    if (!edt_size_ok(height, width))
+        return reject("cgs_mesh_depth_clipped: invalid argument (height=%d, width=%d; sizes lie in [1, %d])", height, width,
+                      CGS_EDT_MAX_SIZE);
+    if (!near_ok(near)) return reject("cgs_mesh_depth_clipped: invalid argument (near=%g; the plane is finite and > 0)", near);
+    if (!intr || !w2c || !depth || (F > 0 && !tris))
+        return reject("cgs_mesh_depth_clipped: invalid argument (NULL pointer; F=%d)", F);
+    if (V == 0) return CGS_OK;   // nothing to write
+    if (launch_mesh_depth_clipped((hipStream_t)stream_, F, tris, V, intr, w2c, height, width, near, depth) != hipSuccess) {
+        set_error("cgs_mesh_depth_clipped: filling the depth planes failed");
+        return CGS_ERR_HIP;
+    }
+    return finish("mesh_depth_clipped", stream_);
+}
+
+int cgs_mesh_contours_clipped(int E, const float* edges, int V, const double* intr, const double* w2c, int height, int width,
+                              const float* depth, double slack, double near, uint8_t* mask_out, void* stream_) {
+    if (E < 0 || V < 0) return reject("cgs_mesh_contours_clipped: invalid argument (E=%d, V=%d)", E, V);
+    if (!edt_size_ok(height, width))
+        return reject("cgs_mesh_contours_clipped: invalid argument (height=%d, width=%d; sizes lie in [1, %d])", height, width,
+                      CGS_EDT_MAX_SIZE);
+    if (depth && !slack_ok(slack))
+        return reject("cgs_mesh_contours_clipped: invalid argument (slack=%g; with a depth plane the slack is finite and >= 0)",
+                      slack);
+    if (!near_ok(near)) return reject("cgs_mesh_contours_clipped: invalid argument (near=%g; the plane is finite and > 0)", near);
+    if (!intr || !w2c || !mask_out || (E > 0 && !edges))
+        return reject("cgs_mesh_contours_clipped: invalid argument (NULL pointer; E=%d)", E);
+    if (V == 0) return CGS_OK;   // nothing to clear
+    if (launch_mesh_contours_clipped((hipStream_t)stream_, E, edges, V, intr, w2c, height, width, depth, slack, near, mask_out) !=
+        hipSuccess) {
+        set_error("cgs_mesh_contours_clipped: clearing the mask failed");
+        return CGS_ERR_HIP;
+    }
+    return finish("mesh_contours_clipped", stream_);
+}
+
 }  // extern "C"

@@ -9,7 +9,9 @@
 //                       operands: the plane is the same for every launch geometry and every order of the triangles.  The
 //                       other geometry, one THREAD per (triangle, view), is kept as a probe: on a mesh of triangles of a few
 //                       pixels it takes 5.5 ms where this one takes 7.4, on 12 triangles that fill the image 1.26 s
-//                       against 21 ms (profiles/edge_occlusion.md) -- this one has no bad case.
+//                       against 21 ms (profiles/edge_occlusion.md) -- this one has no bad case.  k_mesh_depth<true> is
+//                       cgs_mesh_depth_clipped: the same wave rasterises the one or two pieces that the plane c2 == near
+//                       leaves of its triangle, one after the other (profiles/edge_clip.md).
 //   k_depth_window_max  grid (tiles of 64 x 16, 1, views), one pass: the tile and its halo staged in LDS (pixels outside the
 //                       image as -inf: they never win, which is the clipping), the row maximum into a second LDS array, the
 //                       column maximum out.  A maximum is exact, so the separable form is the window's maximum to the bit.
@@ -31,22 +33,44 @@ constexpr int OCC_TILE_W = 64, OCC_TILE_H = 16;
 constexpr int OCC_HALO = CGS_DEPTH_MAX_WINDOW;
 
 // ------------------------------------------------------------------------------------------------ z-buffer
-__global__ void __launch_bounds__(OCC_THREADS) k_mesh_depth(int F, const float* __restrict__ tris,
-                                                           const double* __restrict__ intr,
-                                                           const double* __restrict__ w2c, int height, int width,
-                                                           unsigned int* __restrict__ depth) {
-    const long long f = (long long)blockIdx.x * OCC_WAVES + (threadIdx.x >> 6);
-    if (f >= F) return;   // (uniform over the wave; no barrier in this kernel)
-    NvCam c;
-    nv_load_cam(c, intr, w2c, blockIdx.y);
-    MeshTri t;
-    if (!mesh_tri_setup(c, tris + 9 * f, height, width, t)) return;   // (uniform)
+// The wave's 64 lanes over the candidate pixels of one set-up triangle (or clipped piece), row-major, 64 at a time.
+__device__ inline void mesh_tri_raster(const MeshTri& t, int height, int width, unsigned int* __restrict__ depth) {
     const unsigned int bw = (unsigned int)(t.jhi - t.jlo + 1);
     const unsigned int n = bw * (unsigned int)(t.ihi - t.ilo + 1);   // at most 2^28
     unsigned int* __restrict__ plane = depth + (size_t)blockIdx.y * (size_t)height * (size_t)width;
     for (unsigned int idx = threadIdx.x & 63; idx < n; idx += 64) {
         const unsigned int r = idx / bw;
         mesh_tri_pixel(t, t.ilo + (int)r, t.jlo + (int)(idx - r * bw), plane, width);
+    }
+}
+
+// CLIP = false is cgs_mesh_depth and reads no `near`; CLIP = true is cgs_mesh_depth_clipped: the triangle's one or two
+// pieces in front of the plane c2 == near (mesh_depth.h), rasterised one after the other.  The classification is uniform
+// over the wave -- every lane holds the same nine floats -- so nothing diverges, and there is still no barrier.
+template <bool CLIP>
+__global__ void __launch_bounds__(OCC_THREADS) k_mesh_depth(int F, const float* __restrict__ tris,
+                                                           const double* __restrict__ intr,
+                                                           const double* __restrict__ w2c, int height, int width,
+                                                           double near, unsigned int* __restrict__ depth) {
+    const long long f = (long long)blockIdx.x * OCC_WAVES + (threadIdx.x >> 6);
+    if (f >= F) return;   // (uniform over the wave; no barrier in this kernel)
+    NvCam c;
+    nv_load_cam(c, intr, w2c, blockIdx.y);
+    MeshTri t;
+    if constexpr (!CLIP) {
+        if (!mesh_tri_setup(c, tris + 9 * f, height, width, t)) return;   // (uniform)
+        mesh_tri_raster(t, height, width, depth);
+    } else {
+        const float* __restrict__ p = tris + 9 * f;
+        CamPt v[3], q[4];
+#pragma unroll
+        for (int k = 0; k < 3; k++)
+            nv_camera_xyz(c, (double)p[3 * k + 0], (double)p[3 * k + 1], (double)p[3 * k + 2], v[k].x, v[k].y, v[k].z);
+        const int pieces = mesh_tri_clip(v[0], v[1], v[2], near, q);   // (uniform)
+        for (int k = 0; k < pieces; k++) {   // piece 0 is (q0, q1, q2), piece 1 (q0, q2, q3): selects, one rasteriser body
+            const CamPt b = k == 0 ? q[1] : q[2], d = k == 0 ? q[2] : q[3];
+            if (mesh_tri_setup_cam(c, q[0], b, d, height, width, t)) mesh_tri_raster(t, height, width, depth);
+        }
     }
 }
 
@@ -128,19 +152,31 @@ __global__ void __launch_bounds__(OCC_THREADS) k_point_mask_depth(int P, const f
 }
 
 // ------------------------------------------------------------------------------------------------ launchers
-hipError_t launch_mesh_depth(hipStream_t s, int F, const float* tris, int V, const double* intr, const double* w2c,
-                             int height, int width, float* depth) {
+template <bool CLIP>
+static hipError_t launch_mesh_depth_t(hipStream_t s, const char* name, int F, const float* tris, int V, const double* intr,
+                                      const double* w2c, int height, int width, double near, float* depth) {
     const size_t plane = (size_t)height * (size_t)width;
     hipError_t e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(depth), (int)DEPTH_INF_BITS, (size_t)V * plane, s);
     if (e != hipSuccess || F == 0) return e;
     const unsigned blocks = (unsigned)(((long long)F + OCC_WAVES - 1) / OCC_WAVES);
-    ProfScope p("mesh_depth", s);
+    ProfScope p(name, s);
     for (int v0 = 0; v0 < V; v0 += OCC_MAX_VIEWS) {
         const int nv = std::min(OCC_MAX_VIEWS, V - v0);
-        hipLaunchKernelGGL(k_mesh_depth, dim3(blocks, nv), dim3(OCC_THREADS), 0, s, F, tris, intr + 4 * (size_t)v0,
-                           w2c + 12 * (size_t)v0, height, width, reinterpret_cast<unsigned int*>(depth) + (size_t)v0 * plane);
+        hipLaunchKernelGGL(k_mesh_depth<CLIP>, dim3(blocks, nv), dim3(OCC_THREADS), 0, s, F, tris, intr + 4 * (size_t)v0,
+                           w2c + 12 * (size_t)v0, height, width, near,
+                           reinterpret_cast<unsigned int*>(depth) + (size_t)v0 * plane);
     }
     return hipSuccess;
+}
+
+hipError_t launch_mesh_depth(hipStream_t s, int F, const float* tris, int V, const double* intr, const double* w2c,
+                             int height, int width, float* depth) {
+    return launch_mesh_depth_t<false>(s, "mesh_depth", F, tris, V, intr, w2c, height, width, 0.0, depth);
+}
+
+hipError_t launch_mesh_depth_clipped(hipStream_t s, int F, const float* tris, int V, const double* intr, const double* w2c,
+                                     int height, int width, double near, float* depth) {
+    return launch_mesh_depth_t<true>(s, "mesh_depth_clipped", F, tris, V, intr, w2c, height, width, near, depth);
 }
 
 void launch_depth_window_max(hipStream_t s, int V, int height, int width, int radius, const float* depth, float* out) {

@@ -305,4 +305,10 @@ hipError_t launch_point_mask_depth(hipStream_t s, int P, const float* points, in
 hipError_t launch_mesh_contours(hipStream_t s, int E, const float* rows, int V, const double* intr, const double* w2c,
                                 int height, int width, const float* depth, double slack, uint8_t* mask);
 
+// near-plane clipping: edge_occlusion.hip, mesh_contours.hip (the cut is mesh_depth.h's)
+hipError_t launch_mesh_depth_clipped(hipStream_t s, int F, const float* tris, int V, const double* intr, const double* w2c,
+                                     int height, int width, double near, float* depth);
+hipError_t launch_mesh_contours_clipped(hipStream_t s, int E, const float* rows, int V, const double* intr, const double* w2c,
+                                        int height, int width, const float* depth, double slack, double near, uint8_t* mask);
+
 }  // namespace cgs

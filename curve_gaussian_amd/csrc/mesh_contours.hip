@@ -11,9 +11,12 @@
 //                     64 lanes stride over its steps.  No lane leaves before the loop, so every lane read holds live values.
 //                     A kept step stores the byte 1: a constant, so neither the order nor a second writer matters, and the
 //                     mask is the same for every launch geometry.  No atomics, no LDS, no scratch, 64-bit offsets.
+//                     k_mesh_contours<., true> is cgs_mesh_contours_clipped: the lane that classifies a row also cuts its
+//                     OUT end at the plane c2 == near (near_cut of mesh_depth.h, the z-buffer's); the drawing is the same.
 #include <algorithm>
 
 #include "kernels.h"
+#include "mesh_depth.h"
 #include "point_projection.h"
 
 namespace cgs {
@@ -44,19 +47,39 @@ __device__ inline bool contour_clip_side(double p, double q, double& t0, double&
 }
 
 // True iff the row (a, b, c, d) -- twelve floats -- is a contour of the view AND has something to draw; then s is filled.
-__device__ inline bool contour_classify(const NvCam& c, const float* __restrict__ row, int height, int width, ContourSeg& s) {
+// CLIP = false is cgs_mesh_contours and reads no `near`.  CLIP = true is cgs_mesh_contours_clipped: an end is IN iff its
+// c2 >= near, a row with no end IN is skipped, the contour test is the same (on the unclipped points), and an OUT end is
+// then replaced by near_cut (mesh_depth.h) from the IN end toward it, before the image points and the depths are taken.
+template <bool CLIP>
+__device__ inline bool contour_classify(const NvCam& c, const float* __restrict__ row, int height, int width, double near,
+                                        ContourSeg& s) {
 #pragma clang fp contract(off)
     double p[4][3];
 #pragma unroll
     for (int k = 0; k < 4; k++)
         nv_camera_xyz(c, (double)row[3 * k + 0], (double)row[3 * k + 1], (double)row[3 * k + 2], p[k][0], p[k][1], p[k][2]);
-    if (!(p[0][2] > 0.0) || !(p[1][2] > 0.0)) return false;   // an end at or behind the camera plane, or NaN: no clipping
+    bool in_a = true, in_b = true;
+    if constexpr (CLIP) {
+        in_a = p[0][2] >= near, in_b = p[1][2] >= near;   // (a NaN is OUT)
+        if (!in_a && !in_b) return false;
+    } else {
+        if (!(p[0][2] > 0.0) || !(p[1][2] > 0.0)) return false;   // an end at or behind the camera plane, or NaN: no clipping
+    }
     const double m0 = p[0][1] * p[1][2] - p[0][2] * p[1][1];   // m = a x b: the normal of the plane through the eye and the edge
     const double m1 = p[0][2] * p[1][0] - p[0][0] * p[1][2];
     const double m2 = p[0][0] * p[1][1] - p[0][1] * p[1][0];
     const double sc = (m0 * p[2][0] + m1 * p[2][1]) + m2 * p[2][2];
     const double sd = (m0 * p[3][0] + m1 * p[3][1]) + m2 * p[3][2];
     if (!(sc * sd > 0.0)) return false;   // opposite sides, edge-on (a zero) or NaN
+    if constexpr (CLIP) {
+        if (!in_a || !in_b) {
+            const CamPt A = {p[0][0], p[0][1], p[0][2]}, B = {p[1][0], p[1][1], p[1][2]};
+            const CamPt cut = in_a ? near_cut(A, B, near) : near_cut(B, A, near);
+            // the OUT end becomes the cut (selects, not an indexed store: the array stays in registers)
+            p[0][0] = in_a ? p[0][0] : cut.x, p[0][1] = in_a ? p[0][1] : cut.y, p[0][2] = in_a ? p[0][2] : cut.z;
+            p[1][0] = in_a ? cut.x : p[1][0], p[1][1] = in_a ? cut.y : p[1][1], p[1][2] = in_a ? cut.z : p[1][2];
+        }
+    }
     double ub, vb;
     nv_image_uv(c, p[0][0], p[0][1], p[0][2], s.ua, s.va);
     nv_image_uv(c, p[1][0], p[1][1], p[1][2], ub, vb);
@@ -104,17 +127,17 @@ __device__ inline double wave_read(double x, int src) {
     return __hiloint2double(wave_read(__double2hiint(x), src), wave_read(__double2loint(x), src));
 }
 
-template <bool GATED>
+template <bool GATED, bool CLIP>
 __global__ void __launch_bounds__(CONTOUR_THREADS) k_mesh_contours(int E, const float* __restrict__ rows,
                                                                   const double* __restrict__ intr,
                                                                   const double* __restrict__ w2c, int height, int width,
                                                                   const float* __restrict__ depth, double slack,
-                                                                  uint8_t* __restrict__ mask) {
+                                                                  double near, uint8_t* __restrict__ mask) {
     NvCam c;
     nv_load_cam(c, intr, w2c, blockIdx.y);
     const long long e = (long long)blockIdx.x * CONTOUR_THREADS + threadIdx.x;
     ContourSeg mine = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 1.0, 1.0, 0};
-    const bool is_contour = e < E && contour_classify(c, rows + 12 * (size_t)e, height, width, mine);
+    const bool is_contour = e < E && contour_classify<CLIP>(c, rows + 12 * (size_t)e, height, width, near, mine);
     unsigned long long todo = __ballot(is_contour);   // every lane of the wave is here: none has returned
     const size_t off = (size_t)blockIdx.y * (size_t)height * (size_t)width;
     uint8_t* __restrict__ plane = mask + off;
@@ -137,13 +160,15 @@ __global__ void __launch_bounds__(CONTOUR_THREADS) k_mesh_contours(int E, const 
     }
 }
 
-hipError_t launch_mesh_contours(hipStream_t s, int E, const float* rows, int V, const double* intr, const double* w2c,
-                                int height, int width, const float* depth, double slack, uint8_t* mask) {
+template <bool CLIP>
+static hipError_t launch_mesh_contours_t(hipStream_t s, const char* name, int E, const float* rows, int V, const double* intr,
+                                         const double* w2c, int height, int width, const float* depth, double slack,
+                                         double near, uint8_t* mask) {
     const size_t plane = (size_t)height * (size_t)width;
     hipError_t err = hipMemsetAsync(mask, 0, (size_t)V * plane, s);
     if (err != hipSuccess || E == 0) return err;
     const unsigned blocks = (unsigned)(((long long)E + CONTOUR_THREADS - 1) / CONTOUR_THREADS);
-    ProfScope p("mesh_contours", s);
+    ProfScope p(name, s);
     for (int v0 = 0; v0 < V; v0 += CONTOUR_MAX_VIEWS) {
         const int nv = std::min(CONTOUR_MAX_VIEWS, V - v0);
         const dim3 grid(blocks, nv);
@@ -151,13 +176,24 @@ hipError_t launch_mesh_contours(hipStream_t s, int E, const float* rows, int V, 
         const double* M = w2c + 12 * (size_t)v0;
         uint8_t* out = mask + (size_t)v0 * plane;
         if (depth)
-            hipLaunchKernelGGL(k_mesh_contours<true>, grid, dim3(CONTOUR_THREADS), 0, s, E, rows, K, M, height, width,
-                               depth + (size_t)v0 * plane, slack, out);
+            hipLaunchKernelGGL((k_mesh_contours<true, CLIP>), grid, dim3(CONTOUR_THREADS), 0, s, E, rows, K, M, height, width,
+                               depth + (size_t)v0 * plane, slack, near, out);
         else
-            hipLaunchKernelGGL(k_mesh_contours<false>, grid, dim3(CONTOUR_THREADS), 0, s, E, rows, K, M, height, width,
-                               (const float*)nullptr, 0.0, out);
+            hipLaunchKernelGGL((k_mesh_contours<false, CLIP>), grid, dim3(CONTOUR_THREADS), 0, s, E, rows, K, M, height, width,
+                               (const float*)nullptr, 0.0, near, out);
     }
     return hipSuccess;
+}
+
+hipError_t launch_mesh_contours(hipStream_t s, int E, const float* rows, int V, const double* intr, const double* w2c,
+                                int height, int width, const float* depth, double slack, uint8_t* mask) {
+    return launch_mesh_contours_t<false>(s, "mesh_contours", E, rows, V, intr, w2c, height, width, depth, slack, 0.0, mask);
+}
+
+hipError_t launch_mesh_contours_clipped(hipStream_t s, int E, const float* rows, int V, const double* intr, const double* w2c,
+                                        int height, int width, const float* depth, double slack, double near, uint8_t* mask) {
+    return launch_mesh_contours_t<true>(s, "mesh_contours_clipped", E, rows, V, intr, w2c, height, width, depth, slack, near,
+                                        mask);
 }
 
 }  // namespace cgs

@@ -58,7 +58,7 @@ def _json_number(x):
 def score_edges(pred, cameras, edge_maps_u8, detector, tolerances_px=(1, 2, 4), edge_threshold=EDGE_MAX_THRESHOLD,
                 sample_resolution=SAMPLE_RESOLUTION, device=None, backend="gpu", budget_bytes=None, thin=False,
                 occluder=None, depth_maps=None, depth_slack=EO.DEPTH_SLACK, depth_window=EO.DEPTH_WINDOW,
-                ignore_contours=False, contour_radius_px=MC.CONTOUR_RADIUS_PX, crease_deg=MC.CREASE_DEG):
+                ignore_contours=False, contour_radius_px=MC.CONTOUR_RADIUS_PX, crease_deg=MC.CREASE_DEG, near_clip=None):
     """pred: a ``parametric_edges.json`` path or its dict.  cameras: ``NovelViewCamera`` s (R, T world -> camera; fx, fy, cx,
     cy; size).  edge_maps_u8: one uint8 [H,W] map per camera (a list, or an [V,H,W] array), the stored bytes of the
     detector's maps, each of its camera's size.  Returns {"aggregate": ops.edge_score's aggregate over all views,
@@ -85,7 +85,13 @@ def score_edges(pred, cameras, edge_maps_u8, detector, tolerances_px=(1, 2, 4), 
     evidence neither way.  Every row of "views" then holds "contour_pixels" (the drawn contour pixels, before widening),
     "settings" holds "ignore_contours": true, "contour_radius_px" and "crease_deg"; a chunk's working set grows by
     ``ops.edge_score.CONTOUR_BYTES_PER_PIXEL``.  Both defaults are UNTUNED.  Without the flag no key is added and no
-    output changes; with it and no occluder (``depth_maps`` have no mesh edges) it is a ValueError."""
+    output changes; with it and no occluder (``depth_maps`` have no mesh edges) it is a ValueError.
+
+    ``near_clip`` (opt-in, with ``occluder`` only; ``edge_support``, ``trim_edges``, ``snap_edges`` and ``seed_points`` take it
+    the same way): the near plane at which the occluder's triangles and contour rows are clipped instead of being dropped
+    (``ops.edge_occlusion.mesh_depth``; ``EO.NEAR_CLIP``, UNTUNED), for cameras that stand INSIDE the occluder.  "settings"
+    records "near_clip" only when it is given; with ``depth_maps`` or no depth source it is a ValueError (the caller's maps
+    need no clipping)."""
     ES._check_backend(backend)
     EO.check_one_depth_source("score_edges", occluder, depth_maps)
     gated = occluder is not None or depth_maps is not None
@@ -96,7 +102,7 @@ def score_edges(pred, cameras, edge_maps_u8, detector, tolerances_px=(1, 2, 4), 
     ES.tolerances_squared(tolerances_px)
     lut = detected_lut(detector, edge_threshold)
     cameras, maps = check_edge_maps("score_edges", cameras, edge_maps_u8)
-    gate = EO.ChunkDepth("score_edges", cameras, occluder, depth_maps, depth_slack, depth_window)
+    gate = EO.ChunkDepth("score_edges", cameras, occluder, depth_maps, depth_slack, depth_window, near_clip)
     pts = _pred_points(pred, sample_resolution)
     if backend == "gpu":
         device = ES._device_for([], "score_edges", device)
@@ -124,7 +130,8 @@ def score_edges(pred, cameras, edge_maps_u8, detector, tolerances_px=(1, 2, 4), 
                                               return_counts=True)
             hidden[sel] = hid.cpu().numpy()
             if ignore_contours:
-                drawn = MC.row_masks(contour_rows, intr, w2c, H, W, depth, gate.slack, backend=backend, device=device)
+                drawn = MC.row_masks(contour_rows, intr, w2c, H, W, depth, gate.slack, backend=backend, device=device,
+                                     near_clip=gate.near)
                 contour_px[sel] = drawn.sum((1, 2), dtype=torch.int64).cpu().numpy()
                 zone = MC.ignore_zone(drawn, contour_radius_px, backend=backend, device=device)
                 del drawn
@@ -234,14 +241,15 @@ def score_scan(base_dir, dataset_dir, scan, layout="emap", detector="DexiNed", u
                edge_threshold=EDGE_MAX_THRESHOLD, sample_resolution=SAMPLE_RESOLUTION, device=None, backend="gpu",
                resolution=-1, thin=False, occluder=None, depth_dir=None, depth_slack=EO.DEPTH_SLACK,
                depth_window=EO.DEPTH_WINDOW, ignore_contours=False, contour_radius_px=MC.CONTOUR_RADIUS_PX,
-               crease_deg=MC.CREASE_DEG):
+               crease_deg=MC.CREASE_DEG, near_clip=None):
     """Scores ``<base_dir>/<scan>/parametric_edges.json`` against the ``detector`` edge maps of ``<dataset_dir>/<scan>`` and
     writes ``<base_dir>/<scan>/reprojection_score.json`` = {"scan", "aggregate", "views", "settings"}.  ``layout``: "emap"
     (meta_data.json; cameras and maps through get_edge_maps) or "colmap" (sparse/0, also Replica; through read_colmap, with
     ``undistort`` and ``resolution`` as there); ``thin`` as ``score_edges``.  ``occluder``: the name of a mesh file inside the scan directory
     (``mesh.ply``); ``depth_dir``: the name of a directory inside it that holds one ``<image stem>.npy`` depth map per
     camera (``scan_depth_maps``); with either, ``depth_slack`` and ``depth_window`` as ``score_edges``; ``ignore_contours``,
-    ``contour_radius_px`` and ``crease_deg`` as there (they need ``occluder``).  Returns the dict, or None -- after reporting it -- for a scan without a
+    ``contour_radius_px`` and ``crease_deg`` as there (they need ``occluder``), and so does ``near_clip`` (the near plane for
+    cameras inside the occluder; None: no clipping).  Returns the dict, or None -- after reporting it -- for a scan without a
     prediction, as the reference's tools skip one."""
     ES._check_backend(backend)
     if layout not in LAYOUTS:
@@ -259,9 +267,9 @@ def score_scan(base_dir, dataset_dir, scan, layout="emap", detector="DexiNed", u
         cams, maps = colmap_scan_cameras(scan_dir, detector, undistort, backend, resolution)
     if occluder is not None and depth_dir is not None:
         raise ValueError("score_scan: give an occluder or a depth_dir, not both")
-    gate = {}
+    gate = near_clip_options("score_scan", near_clip, occluder)
     if occluder is not None:
-        gate = dict(occluder=os.path.join(scan_dir, occluder), depth_slack=depth_slack, depth_window=depth_window)
+        gate.update(occluder=os.path.join(scan_dir, occluder), depth_slack=depth_slack, depth_window=depth_window)
     elif depth_dir is not None:
         gate = dict(depth_maps=scan_depth_maps(os.path.join(scan_dir, depth_dir), cams), depth_slack=depth_slack,
                     depth_window=depth_window)
@@ -348,10 +356,22 @@ def contour_options(ignore_contours, contour_radius_px=MC.CONTOUR_RADIUS_PX, cre
     return {"ignore_contours": True, "contour_radius_px": contour_radius_px, "crease_deg": crease_deg}
 
 
+def near_clip_options(what, near_clip, occluder):
+    """The keyword arguments of a scan-level operator for the near plane: none without it; a ValueError without an occluder."""
+    if near_clip is None:
+        return {}
+    if occluder is None:
+        raise ValueError(f"{what}: near_clip needs an occluder (depth maps need no clipping)")
+    return {"near_clip": near_clip}
+
+
 def add_depth_arguments(ap):
     """The depth source of the score (shared with train.py --reprojection_score); without them nothing changes."""
     ap.add_argument("--occluder", default=None, metavar="FILE",
                     help="a mesh file inside each scan directory (mesh.ply, .obj): samples hidden behind it are left out")
+    ap.add_argument("--near_clip", nargs="?", type=float, const=EO.NEAR_CLIP, default=None, metavar="VALUE",
+                    help="with --occluder: clip the mesh at this camera depth instead of dropping a triangle that reaches "
+                         f"behind the camera, for cameras INSIDE the mesh (bare flag: {EO.NEAR_CLIP}, world units; untuned)")
     ap.add_argument("--depth_dir", default=None, metavar="DIR",
                     help="a directory inside each scan holding <image stem>.npy depth maps (camera z) instead of a mesh")
     ap.add_argument("--depth_slack", type=float, default=EO.DEPTH_SLACK, help="world units behind the surface (untuned)")
@@ -372,7 +392,7 @@ def main(argv=None):
                          args.edge_threshold, backend=args.backend, thin=args.thin, occluder=args.occluder,
                          depth_dir=args.depth_dir, depth_slack=args.depth_slack, depth_window=args.depth_window,
                          ignore_contours=args.ignore_contours, contour_radius_px=args.contour_radius_px,
-                         crease_deg=args.crease_deg)
+                         crease_deg=args.crease_deg, near_clip=args.near_clip)
         if res is None:
             print(f"Invalid prediction at {scan}")
             continue

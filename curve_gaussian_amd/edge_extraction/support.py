@@ -9,7 +9,7 @@ the rule counts supporting frames and does not pool; a thick detector response i
 With ``--occluder`` (a mesh inside every scan directory) or ``--depth_dir`` (one ``<image stem>.npy`` per camera), and
 ``--depth_slack`` / ``--depth_window``, every 2D step run here -- the check, ``--snap`` and ``--trim`` (``--oriented``) --
 counts a (sample, view) pair that the depth hides as not seen (``ops.edge_occlusion``: the one rule and its limits --
-untuned, drawn solids only, concave edges, no near-plane clipping); the files then record the depth settings and one
+untuned, drawn solids only, concave edges, no near-plane clipping without ``--near_clip``); the files then record the depth settings and one
 hidden total per edge.  Without the flags no file changes by a byte.
 
 ``python -m curve_gaussian_amd.edge_extraction.support --base_dir <predictions> --dataset_dir <scans>`` checks every scan,
@@ -226,7 +226,8 @@ def score_scan(base_dir, dataset_dir, scan, layout="emap", detector="DexiNed", u
     named ``parametric_edges.json``.  ``occluder`` (the name of a mesh file inside the scan directory) or ``depth_dir`` (the
     name of a directory inside it with one ``<image stem>.npy`` depth map per camera), at most one, with ``depth_slack`` and
     ``depth_window`` (None: the defaults of ``ops.edge_occlusion``), as ``reprojection.score_scan`` takes them: the depth
-    source of the snapping, the check and the trimming alike.  Returns the dict of ``write_support``, with the ones of ``write_trim``, ``write_dedupe`` and ``write_join`` under "trim", "dedupe" and "join"
+    source of the snapping, the check and the trimming alike; ``near_clip`` among the options (the near plane for cameras
+    inside the occluder, ``ops.edge_occlusion``) goes to all three as well.  Returns the dict of ``write_support``, with the ones of ``write_trim``, ``write_dedupe`` and ``write_join`` under "trim", "dedupe" and "join"
     when there are any (and the one of ``write_snap`` under "snap"), or None -- after reporting it -- for a scan without a prediction."""
     SP._check_backend(backend)
     if layout not in LAYOUTS:
@@ -254,7 +255,7 @@ def score_scan(base_dir, dataset_dir, scan, layout="emap", detector="DexiNed", u
         else:
             options["depth_maps"] = scan_depth_maps(os.path.join(scan_dir, depth_dir), cams)
         options.update({k: v for k, v in (("depth_slack", depth_slack), ("depth_window", depth_window)) if v is not None})
-    gate_keys = ("occluder", "depth_maps", "depth_slack", "depth_window")
+    gate_keys = ("occluder", "depth_maps", "depth_slack", "depth_window", "near_clip")
     source, extra = EDGES_FILE, {"scan": scan}
     if snap_options is not None:   # first: everything below starts from the snapped edges
         shared = {k: options[k] for k in ("resolution", "edge_threshold", "thin") + gate_keys if k in options}
@@ -464,7 +465,8 @@ def main(argv=None):
                          **({"thin": True} if args.thin else {}),
                          **({"occluder": args.occluder, "depth_dir": args.depth_dir, "depth_slack": args.depth_slack,
                              "depth_window": args.depth_window}
-                            if args.occluder is not None or args.depth_dir is not None else {}))
+                            if args.occluder is not None or args.depth_dir is not None else {}),
+                         **({"near_clip": args.near_clip} if args.near_clip is not None else {}))
         if out is None:
             print(f"Invalid prediction at {scan}")
             continue

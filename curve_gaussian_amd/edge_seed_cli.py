@@ -2,7 +2,7 @@
 
     python -m curve_gaussian_amd.edge_seed_cli --scan DIR [--layout emap|colmap] [--backend gpu|host] [--directions]
                                                [--exclusive] [--occluder FILE | --depth_dir DIR] [--depth_slack S]
-                                               [--depth_window R] --out seeds.ply
+                                               [--depth_window R] [--near_clip [VALUE]] --out seeds.ply
 
 The cameras and maps are those ``edge_extraction.reprojection`` scores against: ``emap_cameras`` (meta_data.json) or
 ``read_colmap`` (sparse/0; ``--undistort`` as there).  The box is ``--bounds``, or ``scene.default_seed_bounds``.  The seeds
@@ -16,7 +16,8 @@ more than ``--depth_slack`` (default: half the voxel diagonal) in front of a vox
 (``--depth_window``: the window maximum over the planes); the hidden (voxel, view) pairs are printed.  On a scan of a solid
 the ungated vote keeps next to nothing at the default ``--min_ratio``.  The defaults are untuned, and without a depth source
 there is no occlusion reasoning, with or without ``--exclusive`` (ops/edge_seed.py); the gate's own limits -- no near-plane
-clipping, drawn solids only -- are those of ops/edge_occlusion.py."""
+clipping unless ``--near_clip`` (with ``--occluder``, for cameras inside the mesh) asks for it, drawn solids only -- are
+those of ops/edge_occlusion.py."""
 import argparse
 import os
 import sys
@@ -70,6 +71,8 @@ def seed_options(args):
     if args.occluder is not None or args.depth_dir is not None:
         opts.update(occluder=args.occluder, depth_dir=args.depth_dir, depth_slack=args.depth_slack,
                     depth_window=args.depth_window)
+    if args.near_clip is not None:   # (seed_points rejects it without an occluder)
+        opts["near_clip"] = args.near_clip
     return opts
 
 

@@ -26,7 +26,12 @@ pixel CENTRE, which on a slanted face differs by far more than any sensible slac
 function of the image point and the sample lies inside the hull of the nine centres around it, so the maximum over them is
 at least the sample's own depth; at a silhouette one of the nine has no surface and the sample is never hidden.
 
-WHAT THIS IS NOT.  No clipping: a triangle with a vertex at or behind the camera plane is dropped whole.  The rule has
+WHAT THIS IS NOT.  By default no clipping: a triangle with a vertex at or behind the camera plane is dropped whole, which
+is right for a solid seen from outside and wrong for a camera INSIDE its occluder (a room, a coarse proxy mesh): there
+``near_clip=`` (``mesh_depth``, ``ChunkDepth``; ``cgs_mesh_depth_clipped``) cuts such a triangle at the plane c2 == near_clip
+and keeps what is in front.  It stays off unless asked for; ``NEAR_CLIP`` IS UNTUNED and only the drawn room of
+scene/solid_scan.py has been checked.  A sample nearer than the plane is still seen and can only be hidden by a surface at
+or beyond it.  The rule has
 five consumers: the score's prediction mask (``point_masks_depth``) and, opt-in, the support check, trimming, oriented
 trimming and snapping (``support_counts``, ``sample_tally``, ``oriented_tally`` and ``snap_terms`` with ``depth=``; DESIGN.md
 4.8u), which share ``hidden_host`` / ``gate_view_host`` on the host and ``ChunkDepth`` for a scan's planes.  The edge vote
@@ -46,6 +51,8 @@ from . import edge_score as ES
 MAX_WINDOW = L.DEPTH_MAX_WINDOW
 DEPTH_WINDOW = 1                 # UNTUNED
 DEPTH_SLACK = 2 * 0.0005         # UNTUNED: 2 x edge_extraction.reprojection.SAMPLE_RESOLUTION, in world units
+NEAR_CLIP = 0.01                 # UNTUNED: the near plane of the clipped z-buffer, in world units, for scenes in the unit cube;
+                                 # synthetic.make_camera's znear
 
 
 def _check_window(what, window):
@@ -60,6 +67,16 @@ def _check_slack(what, slack):
     if not (slack >= 0.0 and np.isfinite(slack)):
         raise ValueError(f"{what}: the slack must be finite and >= 0 (got {slack})")
     return slack
+
+
+def _check_near(what, near_clip):
+    """None (no clipping), or the near plane as a float: finite and > 0."""
+    if near_clip is None:
+        return None
+    near = float(near_clip)
+    if not (near > 0.0 and np.isfinite(near)):
+        raise ValueError(f"{what}: near_clip must be finite and > 0 (got {near_clip})")
+    return near
 
 
 def _as_tris(tris):
@@ -93,12 +110,58 @@ def _camera_points_host(P, K, M):
     return c2, u, v
 
 
-def _zbuffer_host(T, K, M, height, width):
-    """One view of cgs_mesh_depth in numpy: T float64 [F,3,3] (widened float32), float32 [height,width]."""
+def near_cut_host(a, b, near):
+    """THE cut of cgs_mesh_depth_clipped in numpy, from the IN ends a toward the OUT ends b: (c0, c1, c2) float64 [N] each of
+    a, b -> the cut points, c2 assigned.  The host back ends' one statement of it (the contours share it)."""
+    with np.errstate(all="ignore"):
+        t = (a[2] - near) / (a[2] - b[2])
+        return a[0] + t * (b[0] - a[0]), a[1] + t * (b[1] - a[1]), np.full_like(t, near)
+
+
+def _clip_host(T, M, near):
+    """The pieces of cgs_mesh_depth_clipped in one view: camera-space (c0, c1, c2), float64 [G,3] each.  T float64 [F,3,3]."""
+    X, Y, Z = T[..., 0], T[..., 1], T[..., 2]
+    with np.errstate(all="ignore"):
+        c = np.stack([((M[0] * X + M[1] * Y) + M[2] * Z) + M[3], ((M[4] * X + M[5] * Y) + M[6] * Z) + M[7],
+                      ((M[8] * X + M[9] * Y) + M[10] * Z) + M[11]])          # [3 (coordinate), F, 3 (vertex)]
+        c = c[:, ~np.isnan(c).any(axis=(0, 2))]
+        inn = c[2] >= near
+    nin = inn.sum(1)
+    pieces = [c[:, nin == 3]]
+    for count in (1, 2):
+        sel = nin == count
+        if not sel.any():
+            continue
+        cs, ins = c[:, sel], inn[sel]
+        i = np.argmax(ins, 1) if count == 1 else np.argmin(ins, 1)   # the one IN, or the one OUT
+        rows = np.arange(cs.shape[1])
+        r0, r1, r2 = (tuple(cs[k][rows, (i + d) % 3] for k in range(3)) for d in range(3))
+        if count == 1:       # a = r0, b = r1, c = r2: (a, cut(a,b), cut(a,c))
+            tri = [(r0, near_cut_host(r0, r1, near), near_cut_host(r0, r2, near))]
+        else:                # c = r0, a = r1, b = r2: (a, b, cut(b,c)), (a, cut(b,c), cut(a,c))
+            qb, qa = near_cut_host(r2, r0, near), near_cut_host(r1, r0, near)
+            tri = [(r1, r2, qb), (r1, qb, qa)]
+        for verts in tri:
+            pieces.append(np.stack([np.stack([vtx[k] for vtx in verts], 1) for k in range(3)]))
+    c = np.concatenate(pieces, 1)
+    return c[0], c[1], c[2]
+
+
+def _zbuffer_host(T, K, M, height, width, near=None):
+    """One view of cgs_mesh_depth (near None) or cgs_mesh_depth_clipped in numpy: T float64 [F,3,3] (widened float32),
+    float32 [height,width]."""
     plane = np.full((height, width), np.inf, np.float32)
     if T.shape[0] == 0:
         return plane
-    z, u, v = _camera_points_host(T, K, M)   # [F,3] each
+    if near is None:
+        z, u, v = _camera_points_host(T, K, M)   # [F,3] each
+    else:
+        c0, c1, z = _clip_host(T, M, near)       # [G,3] each: the pieces' camera-space vertices
+        if z.shape[0] == 0:
+            return plane
+        with np.errstate(all="ignore"):
+            u = K[0] * (c0 / z) + K[2]
+            v = K[1] * (c1 / z) + K[3]
     with np.errstate(all="ignore"):
         ok = (z > 0.0).all(1) & ~np.isnan(u).any(1) & ~np.isnan(v).any(1)
         area = (u[:, 1] - u[:, 0]) * (v[:, 2] - v[:, 0]) - (v[:, 1] - v[:, 0]) * (u[:, 2] - u[:, 0])
@@ -170,21 +233,25 @@ def depth_window_max(depth, radius, backend="gpu", device=None):
     return out
 
 
-def mesh_depth(tris, intrinsics, w2c, height, width, window=DEPTH_WINDOW, backend="gpu", device=None):
+def mesh_depth(tris, intrinsics, w2c, height, width, window=DEPTH_WINDOW, backend="gpu", device=None, near_clip=None):
     """float32 [V,height,width]: the camera-z of the nearest triangle at every pixel centre (+inf where there is none), then
     the window maximum of radius ``window`` (0: the plain z-buffer).  tris float32 [F,3,3] (tensor or array); intrinsics
     [V,4] and w2c [V,3,4] as ``point_masks``.  ``backend="gpu"``: ``cgs_mesh_depth`` and ``cgs_depth_window_max``, the
-    triangles are uploaded when they are not on a GPU, the result stays on the device; ``"host"``: numpy, a CPU tensor."""
+    triangles are uploaded when they are not on a GPU, the result stays on the device; ``"host"``: numpy, a CPU tensor.
+    ``near_clip``: None -- a triangle with a vertex at or behind the camera plane is dropped whole --, or the near plane
+    (world units, finite, > 0; ``NEAR_CLIP``): such a triangle is clipped at c2 == near_clip (``cgs_mesh_depth_clipped``),
+    which a camera INSIDE its occluder needs; with every vertex in front of the plane the bits are the same."""
     ES._check_backend(backend)
     height, width = ES._check_size("mesh_depth", height, width)
     window = _check_window("mesh_depth", window)
+    near = _check_near("mesh_depth", near_clip)
     V, K, M = ES._cameras(intrinsics, w2c)
     t = _as_tris(tris)
     if backend == "host":
         T = t.cpu().numpy().astype(np.float64)
         raw = np.empty((V, height, width), np.float32)
         for i in range(V):
-            raw[i] = _zbuffer_host(T, K[i], M[i], height, width)
+            raw[i] = _zbuffer_host(T, K[i], M[i], height, width, near)
         return torch.from_numpy(_window_max_host(raw, window) if window else raw)
     dev = ES._device_for([t], "mesh_depth", device)
     with L.device_guard(dev):
@@ -192,9 +259,14 @@ def mesh_depth(tris, intrinsics, w2c, height, width, window=DEPTH_WINDOW, backen
         raw = torch.empty((V, height, width), dtype=torch.float32, device=dev)
         if V > 0:
             Kd, Md = ES.cameras_on(dev, K, M)
-            rc = L.load().cgs_mesh_depth(int(t.shape[0]), L.ptr(t), V, L.ptr(Kd), L.ptr(Md), height, width, L.ptr(raw),
-                                         L.raw_stream(dev))
-            L.check(rc, "cgs_mesh_depth")
+            if near is None:
+                rc = L.load().cgs_mesh_depth(int(t.shape[0]), L.ptr(t), V, L.ptr(Kd), L.ptr(Md), height, width, L.ptr(raw),
+                                             L.raw_stream(dev))
+                L.check(rc, "cgs_mesh_depth")
+            else:
+                rc = L.load().cgs_mesh_depth_clipped(int(t.shape[0]), L.ptr(t), V, L.ptr(Kd), L.ptr(Md), height, width, near,
+                                                     L.ptr(raw), L.raw_stream(dev))
+                L.check(rc, "cgs_mesh_depth_clipped")
     return depth_window_max(raw, window, "gpu", dev) if window else raw
 
 
@@ -337,10 +409,17 @@ class ChunkDepth:
       to(backend, dev)  where the planes are built; uploads the triangles once
       planes(...)       float32 [len(sel),H,W] of a chunk of ``view_chunks``, on the back end's device
       settings()        the keys a result records: "occluder" (the path, or true) or "depth_maps": true, "depth_slack",
-                        "depth_window"; {} when not gated"""
+                        "depth_window", and "near_clip" only when it was given; {} when not gated
 
-    def __init__(self, what, cameras, occluder=None, depth_maps=None, depth_slack=DEPTH_SLACK, depth_window=DEPTH_WINDOW):
+    ``near_clip``: the near plane of ``mesh_depth`` for an occluder the cameras stand INSIDE (None: no clipping, the
+    default); rejected without an occluder."""
+
+    def __init__(self, what, cameras, occluder=None, depth_maps=None, depth_slack=DEPTH_SLACK, depth_window=DEPTH_WINDOW,
+                 near_clip=None):
         check_one_depth_source(what, occluder, depth_maps)
+        if near_clip is not None and occluder is None:
+            raise ValueError(f"{what}: near_clip needs an occluder (the caller's depth maps need no clipping)")
+        self.near = _check_near(what, near_clip)
         self.what = what
         self.gated = occluder is not None or depth_maps is not None
         self.bytes_per_pixel = ES.DEPTH_BYTES_PER_PIXEL if self.gated else 0
@@ -363,7 +442,8 @@ class ChunkDepth:
 
     def planes(self, H, W, sel, intr, w2c):
         if self.tris is not None:
-            return mesh_depth(self.tris, intr, w2c, H, W, self.window, backend=self.backend, device=self.device)
+            return mesh_depth(self.tris, intr, w2c, H, W, self.window, backend=self.backend, device=self.device,
+                              near_clip=self.near)
         return depth_window_max(np.stack([self.maps[v] for v in sel]), self.window, backend=self.backend, device=self.device)
 
     def settings(self):
@@ -374,6 +454,8 @@ class ChunkDepth:
         else:
             out = {"depth_maps": True}
         out.update({"depth_slack": self.slack, "depth_window": self.window})
+        if self.near is not None:
+            out["near_clip"] = self.near
         return out
 
 

@@ -702,7 +702,7 @@ def seed_points(cameras, edge_maps_u8, detector, bounds, grid=128, tol_px=2, min
                 directions=False, dir_radius=DIR_RADIUS, dir_min_support=DIR_MIN_SUPPORT,
                 dir_min_linearity=DIR_MIN_LINEARITY, exclusive=False, excl_window=EXCL_WINDOW, excl_margin=EXCL_MARGIN,
                 excl_win_ratio=EXCL_WIN_RATIO, thin=False, occluder=None, depth_maps=None, depth_slack=None,
-                depth_window=EO.DEPTH_WINDOW):
+                depth_window=EO.DEPTH_WINDOW, near_clip=None):
     """cameras: ``NovelViewCamera`` s; edge_maps_u8: one uint8 [H,W] map per camera (a list or an [V,H,W] array), the
     stored bytes of the detector's maps, as ``score_edges`` takes them.  bounds = (lo, hi) of the box to search.
 
@@ -741,7 +741,7 @@ def seed_points(cameras, edge_maps_u8, detector, bounds, grid=128, tol_px=2, min
     min_ratio 0.5 every sample is covered too, with 38 far voxels on the box.  info then also holds the keys of
     ``ChunkDepth.settings()`` ("occluder" or "depth_maps", "depth_slack", "depth_window") and "hidden_pairs", the
     (voxel, view) pairs the gate hid, summed over the grid.  With neither source nothing changes: no key is added.  The
-    gate's limits are those of ops/edge_occlusion.py: no near-plane clipping, concave edges can be hidden by their own faces.
+    gate's limits are those of ops/edge_occlusion.py: no near-plane clipping unless ``near_clip`` is given, concave edges can be hidden by their own faces.
 
     ``directions=True``: the kept voxels within ``dir_radius`` voxels of every seed's centre voxel give its direction
     (``keep_bits``, ``voxel_moments`` on ``backend``, ``seed_directions(dir_min_support, dir_min_linearity)``; module
@@ -778,7 +778,7 @@ def seed_points(cameras, edge_maps_u8, detector, bounds, grid=128, tol_px=2, min
     need_table(min_ratio, 0)
     budget = check_budget("seed_points", budget_bytes, BYTE_BUDGET)
     gate = EO.ChunkDepth("seed_points", cameras, occluder, depth_maps,
-                         default_slack(bounds, dims) if depth_slack is None else depth_slack, depth_window)
+                         default_slack(bounds, dims) if depth_slack is None else depth_slack, depth_window, near_clip)
     if backend == "gpu":
         device = ES._device_for([], "seed_points", device)
     gate.to(backend, device)

@@ -33,7 +33,7 @@ edge it projects within ``capture_px`` of.  With ``depth`` (``snap_terms``) or `
 (``snap_edges``) a view whose depth plane hides the sample -- the one rule of ops/edge_occlusion.py -- contributes no term
 and no view: it is left right after the projection's verdict, before the footprint test, and for every other view the
 floating-point sequence is unchanged.  Limits as ops/edge_occlusion.py states them: untuned, drawn solids only, concave
-edges, no near-plane clipping.
+edges, no near-plane clipping unless ``near_clip`` is given.
 
 KNOWN LIMITS.  A sample inside the capture radius of the WRONG edge is pulled
 to it: at crossings, and along a parallel edge closer than ``capture_px``.  Snapping is not a filter: a bogus chord that
@@ -354,7 +354,7 @@ def snap_edges(edge_dict, cameras, edge_maps_u8, detector, resolution=SAMPLE_RES
                iterations=ITERATIONS, frames_ratio=EDGE_VISIBILITY_FRAMES_RATIO, min_constrained=MIN_CONSTRAINED,
                damping=DAMPING, step_cap=None, edge_threshold=EDGE_MAX_THRESHOLD, backend="gpu", device=None,
                budget_bytes=None, thin=False, occluder=None, depth_maps=None, depth_slack=EO.DEPTH_SLACK,
-               depth_window=EO.DEPTH_WINDOW):
+               depth_window=EO.DEPTH_WINDOW, near_clip=None):
     """edge_dict, cameras, edge_maps_u8, detector, resolution, edge_threshold, budget_bytes and thin as ``trim_edges`` takes
     them, and the same walk over the views: ``view_chunks``, ``detected_masks``, the optional ``thin_masks``, ``edt_squared``
     (the same seven bytes per pixel), then one ``snap_terms`` call per chunk into one pair of sums.  When all views fit one
@@ -381,7 +381,7 @@ def snap_edges(edge_dict, cameras, edge_maps_u8, detector, resolution=SAMPLE_RES
     views that hide every sample of the edges AS THEY CAME IN (the first pass), every record of "edges" holds
     "hidden_views", their sum over the edge's samples, and "settings" the keys ``score_edges`` records.  With neither,
     nothing changes: no key is added.  Untuned, drawn solids only, concave edges can be hidden by their own faces, no
-    near-plane clipping (ops/edge_occlusion.py).
+    near-plane clipping unless ``near_clip`` is given (ops/edge_occlusion.py).
 
     Returns {"edge_dict": the edges in the layout of ``get_parametric_edge`` (curves [Nc,4,3], lines [Nl,6], as lists; an
     unmoved edge holds the floats it came with), "edges": one record per edge -- kind, index within its kind, samples,
@@ -398,7 +398,7 @@ def snap_edges(edge_dict, cameras, edge_maps_u8, detector, resolution=SAMPLE_RES
     lut = detected_lut(detector, edge_threshold)
     cameras, maps = check_edge_maps("snap_edges", cameras, edge_maps_u8)
     budget = check_budget("snap_edges", budget_bytes, BYTE_BUDGET)
-    source = EO.ChunkDepth("snap_edges", cameras, occluder, depth_maps, depth_slack, depth_window)
+    source = EO.ChunkDepth("snap_edges", cameras, occluder, depth_maps, depth_slack, depth_window, near_clip)
     old_c, old_l = SP._edge_arrays(edge_dict["curves_ctl_pts"], edge_dict["lines_end_pts"])
     pts0, off = SP.sample_edges(old_c, old_l, resolution)
     off = off.astype(np.int64)

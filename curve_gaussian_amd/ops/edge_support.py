@@ -28,7 +28,7 @@ collects support it cannot have from the front edges it projects behind.  With `
 ops/edge_occlusion.py, ``nv_hidden`` -- counts as NOT SEEN and is tallied in "hidden" instead.  The verdict's formulas do
 not change, only their inputs: a view whose VISIBLE samples number fewer than ceil(min_visible * n) does not see the edge.
 The gate's limits are those of ops/edge_occlusion.py: untuned window and slack, checked on the drawn solids of
-scene/solid_scan.py only; a concave edge can be hidden by its own faces; no near-plane clipping.
+scene/solid_scan.py only; a concave edge can be hidden by its own faces; no near-plane clipping unless ``near_clip`` is given.
 
 KNOWN LIMITS.  A thick detector response inflates support: a
 chord across a wide response lies "on" it (``thin=True`` thins the detected masks first: ops/edge_thin.py, DESIGN.md 4.8n;
@@ -276,7 +276,7 @@ def edge_support(edge_dict, cameras, edge_maps_u8, detector, resolution=SAMPLE_R
                  keep_tolerance_px=KEEP_TOLERANCE_PX, min_visible=MIN_VISIBLE, min_near=MIN_NEAR,
                  frames_ratio=EDGE_VISIBILITY_FRAMES_RATIO, edge_threshold=EDGE_MAX_THRESHOLD, backend="gpu", device=None,
                  budget_bytes=None, thin=False, occluder=None, depth_maps=None, depth_slack=EO.DEPTH_SLACK,
-                 depth_window=EO.DEPTH_WINDOW):
+                 depth_window=EO.DEPTH_WINDOW, near_clip=None):
     """edge_dict: {"curves_ctl_pts", "lines_end_pts"} (a ``parametric_edges.json``).  cameras: ``NovelViewCamera`` s;
     edge_maps_u8: one uint8 [H,W] map per camera, the stored bytes of the detector's maps, as ``score_edges`` takes them.
     ``resolution``: the sampling step (default: ``reprojection.SAMPLE_RESOLUTION``, the novel views' Replica value); ``keep_tolerance_px``: the one of
@@ -299,7 +299,7 @@ def edge_support(edge_dict, cameras, edge_maps_u8, detector, resolution=SAMPLE_R
     a view whose VISIBLE samples number fewer than ceil(min_visible * n) does not see the edge.  The result then also holds
     "hidden": int32 [E,V] CPU tensor, and "settings" the keys ``score_edges`` records ("occluder" or "depth_maps",
     "depth_slack", "depth_window").  With neither, nothing changes: no key is added.  The window and the slack are untuned and
-    checked on the drawn solids only; concave edges can be hidden by their own faces; there is no near-plane clipping.
+    checked on the drawn solids only; concave edges can be hidden by their own faces; there is no near-plane clipping unless ``near_clip`` is given (``score_edges``).
 
     Returns {"counts": int32 [E,V,1+T] CPU tensor, "n_points": int64 [E], "curves": Nc, "lines": Nl, the arrays of
     ``support_verdict`` ("seeing_views", "supporting_views", "share", "kept"), "settings"}; edges are ordered
@@ -314,7 +314,7 @@ def edge_support(edge_dict, cameras, edge_maps_u8, detector, resolution=SAMPLE_R
     lut = detected_lut(detector, edge_threshold)
     cameras, maps = check_edge_maps("edge_support", cameras, edge_maps_u8)
     budget = check_budget("edge_support", budget_bytes, BYTE_BUDGET)
-    gate = EO.ChunkDepth("edge_support", cameras, occluder, depth_maps, depth_slack, depth_window)
+    gate = EO.ChunkDepth("edge_support", cameras, occluder, depth_maps, depth_slack, depth_window, near_clip)
     curves, lines = _edge_arrays(edge_dict["curves_ctl_pts"], edge_dict["lines_end_pts"])
     pts, off = sample_edges(curves, lines, resolution)
     E, V, T = off.size - 1, len(cameras), len(tol2)

@@ -27,7 +27,7 @@ DEPTH (opt-in).  Without a depth source a stretch hidden behind 
 and a hidden stretch collects hits it cannot have from the front edges it projects behind.  With ``depth``
 (``sample_tally``) or ``occluder`` / ``depth_maps`` (``trim_edges``) a view whose depth plane hides the sample -- the one
 rule of ops/edge_occlusion.py -- counts as not seeing it and is tallied in "hidden" instead; the frame rule itself does not
-change.  Limits as ops/edge_occlusion.py states them: untuned, drawn solids only, concave edges, no near-plane clipping.
+change.  Limits as ops/edge_occlusion.py states them: untuned, drawn solids only, concave edges, no near-plane clipping unless ``near_clip`` is given.
 
 KNOWN LIMITS.  The pieces of a chord that runs along a real edge duplicate that edge; this module does not merge them
 (ops/edge_dedupe.py, opt-in, drops what a longer edge already covers).  The tally asks how near a detected pixel is, not
@@ -241,7 +241,8 @@ def trim_geometry(curves, lines, offsets, spans):
 def trim_edges(edge_dict, cameras, edge_maps_u8, detector, resolution=SAMPLE_RESOLUTION, tolerance_px=TOLERANCE_PX,
                frames_ratio=EDGE_VISIBILITY_FRAMES_RATIO, max_gap=MAX_GAP, min_span=MIN_SPAN,
                edge_threshold=EDGE_MAX_THRESHOLD, backend="gpu", device=None, budget_bytes=None, thin=False, oriented=False,
-               spread=OR.SPREAD, occluder=None, depth_maps=None, depth_slack=EO.DEPTH_SLACK, depth_window=EO.DEPTH_WINDOW):
+               spread=OR.SPREAD, occluder=None, depth_maps=None, depth_slack=EO.DEPTH_SLACK, depth_window=EO.DEPTH_WINDOW,
+               near_clip=None):
     """edge_dict, cameras, edge_maps_u8, detector, resolution, edge_threshold, budget_bytes and thin as ``edge_support``
     takes them, and the same walk over the views: ``view_chunks``, ``detected_masks``, the optional ``thin_masks``,
     ``edt_squared``, then one ``sample_tally`` call per chunk into one tally -- integers, so the chunking cannot change a bit.
@@ -256,7 +257,7 @@ def trim_edges(edge_dict, cameras, edge_maps_u8, detector, resolution=SAMPLE_RES
     gives a direction only.  The frame rule is the frozen one; only the tally changes.  The result then also holds "hidden":
     int32 [P] CPU tensor, the hiding views of every sample, and "settings" the keys ``score_edges`` records.  With neither,
     nothing changes: no key is added.  Untuned, drawn solids only, concave edges can be hidden by their own faces, no
-    near-plane clipping (ops/edge_occlusion.py).
+    near-plane clipping unless ``near_clip`` is given (ops/edge_occlusion.py).
 
     ``oriented=True`` (off by default; ops/edge_orient.py freezes the rule and states its limits) counts a sample as near
     only where a detected pixel within the tolerance runs the way the sample's edge does, to within ``spread`` octants of
@@ -274,7 +275,7 @@ def trim_edges(edge_dict, cameras, edge_maps_u8, detector, resolution=SAMPLE_RES
     lut = detected_lut(detector, edge_threshold)
     cameras, maps = check_edge_maps("trim_edges", cameras, edge_maps_u8)
     budget = check_budget("trim_edges", budget_bytes, BYTE_BUDGET)
-    gate = EO.ChunkDepth("trim_edges", cameras, occluder, depth_maps, depth_slack, depth_window)
+    gate = EO.ChunkDepth("trim_edges", cameras, occluder, depth_maps, depth_slack, depth_window, near_clip)
     curves, lines = SP._edge_arrays(edge_dict["curves_ctl_pts"], edge_dict["lines_end_pts"])
     pts, off = SP.sample_edges(curves, lines, resolution)
     V = len(cameras)

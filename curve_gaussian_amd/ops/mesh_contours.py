@@ -20,8 +20,9 @@ the clip and the stepping are frozen in include/curvegs.h -- float64, one rounde
 brute-force restatement of tests/mesh_contours_cases.py.  The selection of the rows happens on the host either way: the
 kernel sees only the selected rows.
 
-WHAT THIS IS NOT.  Boundary edges of an open mesh (one triangle) are never rows.  No near-plane clipping: a row with an
-end at or behind the camera plane is skipped whole.  The silhouette edges of a general, noisy triangulation zigzag across
+WHAT THIS IS NOT.  Boundary edges of an open mesh (one triangle) are never rows.  By default no near-plane clipping: a row
+with an end at or behind the camera plane is skipped whole; ``near_clip=`` (``cgs_mesh_contours_clipped``) cuts it at the
+plane instead, for cameras inside the mesh -- off unless asked for.  The silhouette edges of a general, noisy triangulation zigzag across
 its facets; the radius of ``ignore_zone`` is meant to absorb that and this is UNMEASURED -- only the drawn solids of
 scene/solid_scan.py have been checked.  The zone is known to the 2D score only: the support check, trimming, snapping and
 the edge vote do not take it (their per-sample tallies would need a third verdict).  ``CREASE_DEG`` AND ``CONTOUR_RADIUS_PX``
@@ -112,8 +113,9 @@ def _clip_side(p, q, t0, t1, alive):
         return np.where(neg & (r > t0), r, t0), np.where(pos & (r < t1), r, t1), alive
 
 
-def _classify_host(rows64, M):
-    """The contour test of one view for all rows at once: (bool [E], c0, c1, c2 [E,4] -- the camera-space vertices)."""
+def _classify_host(rows64, M, near=None):
+    """The contour test of one view for all rows at once: (bool [E], c0, c1, c2 [E,4] -- the camera-space vertices).  With
+    ``near`` (cgs_mesh_contours_clipped) a row needs one end with c2 >= near instead of both ends in front of the camera."""
     X, Y, Z = rows64[..., 0], rows64[..., 1], rows64[..., 2]   # [E,4] each
     with np.errstate(all="ignore"):
         c0 = ((M[0] * X + M[1] * Y) + M[2] * Z) + M[3]
@@ -125,7 +127,8 @@ def _classify_host(rows64, M):
         m2 = A0 * B1 - A1 * B0
         sc = (m0 * c0[:, 2] + m1 * c1[:, 2]) + m2 * z[:, 2]
         sd = (m0 * c0[:, 3] + m1 * c1[:, 3]) + m2 * z[:, 3]
-        return (A2 > 0.0) & (B2 > 0.0) & (sc * sd > 0.0), c0, c1, z
+        ends = (A2 > 0.0) & (B2 > 0.0) if near is None else (A2 >= near) | (B2 >= near)
+        return ends & (sc * sd > 0.0), c0, c1, z
 
 
 def contour_flags(rows, intrinsics, w2c):
@@ -136,13 +139,21 @@ def contour_flags(rows, intrinsics, w2c):
     return np.stack([_classify_host(rows64, M[i])[0] for i in range(V)]) if V else np.zeros((0, rows64.shape[0]), bool)
 
 
-def _contours_view_host(rows64, K, M, height, width, plane, slack, out):
-    """One view of cgs_mesh_contours in numpy: rows64 float64 [E,4,3] (widened float32); plane float32 [H,W] or None; out
-    uint8 [H,W], cleared.  The classification and the clip for all rows at once, then one contour at a time."""
+def _contours_view_host(rows64, K, M, height, width, plane, slack, out, near=None):
+    """One view of cgs_mesh_contours (near None) or cgs_mesh_contours_clipped in numpy: rows64 float64 [E,4,3] (widened
+    float32); plane float32 [H,W] or None; out uint8 [H,W], cleared.  The classification and the clip for all rows at once,
+    then one contour at a time."""
     if rows64.shape[0] == 0:
         return
-    alive, c0, c1, z = _classify_host(rows64, M)
+    alive, c0, c1, z = _classify_host(rows64, M, near)
     A0, A1, A2, B0, B1, B2 = c0[:, 0], c1[:, 0], z[:, 0], c0[:, 1], c1[:, 1], z[:, 1]
+    if near is not None:   # an OUT end becomes the cut from the IN end toward it (EO.near_cut_host, the z-buffer's)
+        with np.errstate(all="ignore"):
+            in_a, in_b = A2 >= near, B2 >= near
+        A, B = (A0, A1, A2), (B0, B1, B2)
+        cut_b, cut_a = EO.near_cut_host(A, B, near), EO.near_cut_host(B, A, near)
+        A0, A1, A2 = (np.where(in_a, x, q) for x, q in zip(A, cut_a))
+        B0, B1, B2 = (np.where(in_b, x, q) for x, q in zip(B, cut_b))
     with np.errstate(all="ignore"):
         ua, va = K[0] * (A0 / A2) + K[2], K[1] * (A1 / A2) + K[3]
         ub, vb = K[0] * (B0 / B2) + K[2], K[1] * (B1 / B2) + K[3]
@@ -179,14 +190,18 @@ def _as_rows(rows):
     return r.detach().to(torch.float32).contiguous()
 
 
-def row_masks(rows, intrinsics, w2c, height, width, depth=None, slack=EO.DEPTH_SLACK, backend="gpu", device=None):
+def row_masks(rows, intrinsics, w2c, height, width, depth=None, slack=EO.DEPTH_SLACK, backend="gpu", device=None,
+              near_clip=None):
     """uint8 [V,height,width]: 1 on every step of every row (float32 [E,4,3], ``edge_rows``) that is a contour of the view.
     ``depth``: float32 [V,height,width] planes (camera z, +inf = no surface; usually ``mesh_depth`` of the same mesh) --
     a step behind them by more than ``slack`` is dropped --, or None: nothing is hidden and the slack is not read.
     ``backend="gpu"``: ``cgs_mesh_contours``, rows and planes are uploaded when they are not on a GPU, the result stays on the
-    device; ``"host"``: numpy, a CPU tensor."""
+    device; ``"host"``: numpy, a CPU tensor.  ``near_clip``: None -- a row with an end at or behind the camera plane is
+    skipped whole --, or the near plane (finite, > 0): such a row is cut at c2 == near_clip
+    (``cgs_mesh_contours_clipped``), as ``mesh_depth`` cuts the triangles."""
     ES._check_backend(backend)
     height, width = ES._check_size("row_masks", height, width)
+    near = EO._check_near("row_masks", near_clip)
     V, K, M = ES._cameras(intrinsics, w2c)
     r = _as_rows(rows)
     if backend == "host":
@@ -196,7 +211,8 @@ def row_masks(rows, intrinsics, w2c, height, width, depth=None, slack=EO.DEPTH_S
         rows64 = r.cpu().numpy().astype(np.float64)
         mask = np.zeros((V, height, width), np.uint8)
         for i in range(V):
-            _contours_view_host(rows64, K[i], M[i], height, width, None if planes is None else planes[i], slack, mask[i])
+            _contours_view_host(rows64, K[i], M[i], height, width, None if planes is None else planes[i], slack, mask[i],
+                                near)
         return torch.from_numpy(mask)
     dev = ES._device_for([r] + ([depth] if torch.is_tensor(depth) else []), "row_masks", device)
     with L.device_guard(dev):
@@ -207,18 +223,25 @@ def row_masks(rows, intrinsics, w2c, height, width, depth=None, slack=EO.DEPTH_S
         mask = torch.empty((V, height, width), dtype=torch.uint8, device=dev)
         if V > 0:
             Kd, Md = ES.cameras_on(dev, K, M)
-            rc = L.load().cgs_mesh_contours(int(r.shape[0]), L.ptr(r), V, L.ptr(Kd), L.ptr(Md), height, width, L.ptr(d),
-                                            float(slack) if d is not None else 0.0, L.ptr(mask), L.raw_stream(dev))
-            L.check(rc, "cgs_mesh_contours")
+            sl = float(slack) if d is not None else 0.0
+            if near is None:
+                rc = L.load().cgs_mesh_contours(int(r.shape[0]), L.ptr(r), V, L.ptr(Kd), L.ptr(Md), height, width, L.ptr(d),
+                                                sl, L.ptr(mask), L.raw_stream(dev))
+                L.check(rc, "cgs_mesh_contours")
+            else:
+                rc = L.load().cgs_mesh_contours_clipped(int(r.shape[0]), L.ptr(r), V, L.ptr(Kd), L.ptr(Md), height, width,
+                                                        L.ptr(d), sl, near, L.ptr(mask), L.raw_stream(dev))
+                L.check(rc, "cgs_mesh_contours_clipped")
     return mask
 
 
 def contour_masks(tris, intrinsics, w2c, height, width, depth=None, slack=EO.DEPTH_SLACK, kind="smooth",
-                  crease_deg=CREASE_DEG, backend="gpu", device=None):
+                  crease_deg=CREASE_DEG, backend="gpu", device=None, near_clip=None):
     """uint8 [V,height,width]: the contours of the mesh (float32 [F,3,3] triangles) in every view -- ``row_masks`` of
     ``edge_rows(tris, kind, crease_deg)``.  ``kind="smooth"``: the view-dependent contours of curved surfaces;
     ``"all"``: the outline of every two-triangle edge, with ``depth`` the hidden-line-removed outline."""
-    return row_masks(edge_rows(tris, kind, crease_deg), intrinsics, w2c, height, width, depth, slack, backend, device)
+    return row_masks(edge_rows(tris, kind, crease_deg), intrinsics, w2c, height, width, depth, slack, backend, device,
+                     near_clip)
 
 
 def _check_radius(what, radius_px):

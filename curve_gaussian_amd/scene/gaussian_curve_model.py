@@ -503,7 +503,7 @@ class Scene:
     mesh file inside ``source_path`` -- or ``"depth_dir"`` -- the name of a directory inside it with one
     ``<image stem>.npy`` depth map per training camera (``reprojection.scan_depth_maps``) --, at most one, and optionally
     ``"depth_slack"`` / ``"depth_window"``, the vote and the claims are depth-gated (``seed_points``: without a depth source
-    the vote keeps next to nothing on a scan of a solid; untuned, no near-plane clipping).  No seed, or an unknown ``init``,
+    the vote keeps next to nothing on a scan of a solid; untuned, no near-plane clipping unless ``"near_clip"`` is among them).  No seed, or an unknown ``init``,
     is a ValueError: there is no fallback."""
 
     def __init__(self, source_path, gaussians, detector="DexiNed", num_pts_per_axis=15, cameras_extent=None, rng=None,

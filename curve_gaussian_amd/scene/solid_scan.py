@@ -16,6 +16,14 @@ Shapes (inside the unit cube, around its centre):
               handle 0.5523 r.  Such an arc leaves the circle by at most 2.7e-4 r, below the sampling resolution; the
               64-gon's sides lie up to 1.2e-3 r inside the circle, so a rim sample is never behind its own cap.
 
+One shape is seen from INSIDE (``INDOOR_SHAPES``; it is not among ``SHAPES``, whose scans stay byte for byte what they were):
+  room        an inward box of 12 large triangles (walls, floor, ceiling) with one free-standing box pillar on its floor,
+              12 triangles; the ground truth is the 12 lines of the room and the 12 of the pillar.  The cameras are
+              ``synthetic.make_camera`` s on a ring inside the room, each looking across it at the far side of the ring --
+              every eye at least 0.1 from every surface.  Every wall reaches behind the camera plane of most views, so the
+              planes are drawn with near-plane clipping (``near_clip = EO.NEAR_CLIP``, ``cgs_mesh_depth_clipped``); without
+              it most of the room's triangles are dropped and the gate sees through the walls.
+
 LIMITS.  By default the maps hold feature edges only (the cylinder's side draws nothing).  With ``contours=True`` they also
 hold the occluding contours of the curved surfaces -- the smooth mesh edges along which a view sees the surface turn away
 (``ops.mesh_contours.contour_masks``, gated by the same planes and slack) -- as a detector would: edges of the image that
@@ -38,6 +46,11 @@ from ..ops.view_chunks import camera_arrays
 from .dataset_io import fov2focal
 
 SHAPES = ("box", "l_bracket", "cylinder")
+INDOOR_SHAPES = ("room",)    # seen from inside: their own cameras, planes drawn with near-plane clipping
+ROOM_BOX = ((0.05, 0.05), (0.95, 0.95), 0.25, 0.75)       # (x0, y0), (x1, y1), floor, ceiling
+ROOM_PILLAR = ((0.50, 0.40), (0.62, 0.52), 0.25, 0.60)    # stands on the floor, ends below the ceiling
+ROOM_RING = (0.5, 0.5, 0.5, 0.3)                          # the eyes: centre x, y, height, radius
+ROOM_LOOK_DOWN = 0.08                                     # the target lies this far below the eyes' height
 CYLINDER_SIDES = 64
 ARC_HANDLE = 0.5523
 SAMPLE_RESOLUTION = 0.0005   # edge_extraction.reprojection.SAMPLE_RESOLUTION (that module imports the ops; not imported here)
@@ -96,8 +109,14 @@ def solid_geometry(shape):
         poly = [(0.5 + r * math.cos(2.0 * math.pi * k / n), 0.5 + r * math.sin(2.0 * math.pi * k / n)) for k in range(n)]
         tris, lines = _prism(poly, 0.25, 0.75)
         lines, curves = [], _ring(0.5, 0.5, r, 0.25) + _ring(0.5, 0.5, r, 0.75)
+    elif shape == "room":
+        tris, lines = [], []
+        for k, ((x0, y0), (x1, y1), z0, z1) in enumerate((ROOM_BOX, ROOM_PILLAR)):
+            t, ln = _prism([(x0, y0), (x1, y0), (x1, y1), (x0, y1)], z0, z1)
+            tris += [tri[::-1] for tri in t] if k == 0 else t   # the room faces inward
+            lines += ln
     else:
-        raise ValueError(f"unknown solid {shape!r}: expected one of {SHAPES}")
+        raise ValueError(f"unknown solid {shape!r}: expected one of {SHAPES + INDOOR_SHAPES}")
     return (np.asarray(tris, np.float32).reshape(-1, 3, 3),
             {"lines_end_pts": [list(map(float, ln)) for ln in lines], "curves_ctl_pts": curves})
 
@@ -115,25 +134,48 @@ def emap_cameras_of(synth_cams):
     return out
 
 
+def room_cameras(n_views, H, W):
+    """``n_views`` ``synthetic.make_camera`` s on the ring ``ROOM_RING`` inside the room, each looking at the opposite point
+    of the ring, ``ROOM_LOOK_DOWN`` lower; z is up."""
+    cx, cy, cz, r = ROOM_RING
+    cams = []
+    for k in range(int(n_views)):
+        a = 2.0 * math.pi * k / max(int(n_views), 1)
+        eye = (cx + r * math.cos(a), cy + r * math.sin(a), cz)
+        target = (cx - r * math.cos(a), cy - r * math.sin(a), cz - ROOM_LOOK_DOWN)
+        cams.append(synthetic.make_camera(eye, target, (0.0, 0.0, 1.0), int(H), int(W)))
+    return cams
+
+
 def solid_scan(shape, n_views, H, W, backend="gpu", device=None, slack=EO.DEPTH_SLACK, window=EO.DEPTH_WINDOW,
-               sample_resolution=SAMPLE_RESOLUTION, contours=False, crease_deg=MC.CREASE_DEG):
+               sample_resolution=SAMPLE_RESOLUTION, contours=False, crease_deg=MC.CREASE_DEG, near_clip=None, clip=True):
     """A ``SolidScan`` of ``shape`` seen from ``n_views`` ``synthetic.fibonacci_cameras`` of H x W pixels; ``backend`` as the
     ops (both give the same bytes).  ``contours``: the smooth contours of the mesh (folds up to ``crease_deg``, UNTUNED) are
     OR-ed into the maps as 255, gated by the planes and the slack that gate the feature edges, and kept in ``.contours``;
-    without it every byte is what it was."""
+    without it every byte is what it was.  ``near_clip``: the near plane of the planes and contours, as
+    ``mesh_depth`` takes it (None: no clipping for ``SHAPES``, whose cameras stand outside; ``EO.NEAR_CLIP`` for
+    ``INDOOR_SHAPES``, whose cameras stand inside).  ``clip=False`` draws an indoor scan WITHOUT clipping, to see what that
+    costs; it is an error with a ``near_clip``."""
     from ..edge_extraction.abc import pred_points_and_directions
     tris, edges = solid_geometry(shape)
-    synth = synthetic.fibonacci_cameras(int(n_views), int(H), int(W))
+    if shape in INDOOR_SHAPES:
+        synth = room_cameras(n_views, H, W)
+        if not clip and near_clip is not None:
+            raise ValueError("solid_scan: clip=False takes no near_clip")
+        if clip and near_clip is None:
+            near_clip = EO.NEAR_CLIP
+    else:
+        synth = synthetic.fibonacci_cameras(int(n_views), int(H), int(W))
     cams = emap_cameras_of(synth)
     intr, w2c = camera_arrays(cams)
     pts = np.ascontiguousarray(pred_points_and_directions(edges, sample_resolution).points, np.float32).reshape(-1, 3)
-    raw = EO.mesh_depth(tris, intr, w2c, H, W, window=0, backend=backend, device=device)
+    raw = EO.mesh_depth(tris, intr, w2c, H, W, window=0, backend=backend, device=device, near_clip=near_clip)
     planes = EO.depth_window_max(raw, window, backend=backend, device=device)
     mask, _, hidden = EO.point_masks_depth(pts, intr, w2c, planes, slack, backend=backend, device=device, return_counts=True)
     maps, drawn = mask.cpu().numpy() * np.uint8(255), None
     if contours:
         drawn = MC.contour_masks(tris, intr, w2c, H, W, planes, slack, "smooth", crease_deg, backend=backend,
-                                 device=device).cpu().numpy()
+                                 device=device, near_clip=near_clip).cpu().numpy()
         maps |= drawn * np.uint8(255)
     return SolidScan(tris, edges, synth, cams, maps, raw.cpu().numpy(), hidden.cpu().numpy(), drawn)
 
@@ -156,7 +198,7 @@ def main(argv=None):
     import argparse
     ap = argparse.ArgumentParser(prog="python -m curve_gaussian_amd.solid_scan",
                                  description="Write a solid synthetic scan with ground truth and hidden lines removed.")
-    ap.add_argument("shape", choices=SHAPES)
+    ap.add_argument("shape", choices=SHAPES + INDOOR_SHAPES)
     ap.add_argument("out_dir", help="the scan directory to write (EMAP layout)")
     ap.add_argument("--views", type=int, default=24)
     ap.add_argument("--height", type=int, default=240)

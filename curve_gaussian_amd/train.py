@@ -4,7 +4,8 @@
     python -m curve_gaussian_amd.train -s SCAN -m OUT [--iterations N] [--backend graphed|direct|autograd|torch]
                                        [--draw_snapshots] [--topology_backend host|gpu] [--report_dir DIR] [--undistort]
                                        [--init reference|edge_votes] [--init_directions] [--init_exclusive]
-                                       [--init_occluder FILE | --init_depth_dir DIR] [--thin_edge_maps]
+                                       [--init_occluder FILE | --init_depth_dir DIR] [--init_near_clip [VALUE]]
+                                       [--thin_edge_maps]
 
 The loop keeps the reference's order.  Per iteration: learning rate, SH degree every 1000 iterations, a random view without
 replacement, render + losses + every regulariser + backward (one ``TrainStep`` call), densification statistics before
@@ -348,7 +349,11 @@ def build_parser():
     p.add_argument("--init_occluder", default=None, metavar="FILE",
                    help="edge_votes: a mesh file inside the scan directory (mesh.ply, .obj); a view that sees a voxel's centre "
                         "behind it does not count the voxel as seen -- without a depth source the vote keeps next to nothing "
-                        "on a scan of a solid (untuned; no near-plane clipping)")
+                        "on a scan of a solid (untuned; no near-plane clipping unless --init_near_clip)")
+    from .ops.edge_occlusion import NEAR_CLIP
+    p.add_argument("--init_near_clip", nargs="?", type=float, const=NEAR_CLIP, default=None, metavar="VALUE",
+                   help="edge_votes, with --init_occluder: clip the mesh at this camera depth instead of dropping a triangle "
+                        f"that reaches behind the camera, for cameras INSIDE the mesh (bare flag: {NEAR_CLIP}; untuned)")
     p.add_argument("--init_depth_dir", default=None, metavar="DIR",
                    help="edge_votes: a directory inside the scan holding <image stem>.npy depth maps (camera z) instead of a mesh")
     p.add_argument("--init_depth_slack", type=float, default=None,
@@ -501,6 +506,10 @@ def parse_args(argv):
         parser.error("--gate_edge_checks needs a depth source: --occluder or --depth_dir")
     if args.gate_edge_checks and args.occluder is not None and args.depth_dir is not None:
         parser.error("--gate_edge_checks takes one depth source: --occluder or --depth_dir, not both")
+    if args.near_clip is not None and args.occluder is None:
+        parser.error("--near_clip needs --occluder: the mesh that is clipped")
+    if args.init_near_clip is not None and args.init_occluder is None:
+        parser.error("--init_near_clip needs --init_occluder: the mesh that is clipped")
     if args.init_occluder is not None and args.init_depth_dir is not None:
         parser.error("--init edge_votes takes one depth source: --init_occluder or --init_depth_dir, not both")
     if args.ignore_contours and args.occluder is None:
@@ -517,7 +526,8 @@ def parse_args(argv):
                                       ("excl_window", args.init_excl_window), ("excl_margin", args.init_excl_margin),
                                       ("excl_win_ratio", args.init_excl_win_ratio), ("occluder", args.init_occluder),
                                       ("depth_dir", args.init_depth_dir), ("depth_slack", args.init_depth_slack),
-                                      ("depth_window", args.init_depth_window)) if v is not None}
+                                      ("depth_window", args.init_depth_window),
+                                      ("near_clip", args.init_near_clip)) if v is not None}
     if args.init_directions:
         init_options["directions"] = True
     if args.init_exclusive:
@@ -552,6 +562,8 @@ def main(argv=None):
                 gate["occluder"] = os.path.join(dataset.source_path, args.occluder)
             if args.depth_dir is not None:
                 gate["depth_dir"] = os.path.join(dataset.source_path, args.depth_dir)
+        if args.near_clip is not None:   # (score_edges rejects it without an occluder)
+            gate["near_clip"] = args.near_clip
         from .edge_extraction.reprojection import contour_options
         scores = score_scene(dataset.model_path, out["scene"], dataset.detector,
                              **({"thin": True} if args.thin_edge_maps else {}), **gate,
@@ -579,6 +591,8 @@ def gate_options(args, source_path, cameras):
     else:
         from .edge_extraction.reprojection import scan_depth_maps
         gate["depth_maps"] = scan_depth_maps(os.path.join(source_path, args.depth_dir), cameras)
+    if getattr(args, "near_clip", None) is not None:   # (the operators reject it without an occluder)
+        gate["near_clip"] = args.near_clip
     return gate
 
 

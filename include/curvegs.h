@@ -1262,7 +1262,7 @@ int cgs_sample_snap_terms(int P, const float* points /*[P,3]*/, int V, const dou
  * The minimum is an integer atomic minimum on the float's bit pattern (non-negative floats order like their bits).  A pixel
  * on a side shared by two triangles is covered by both, which is harmless under a minimum.  The result does not depend on
  * the launch geometry or on the order of the triangles.  Limits: a triangle with a vertex at or behind the camera plane is
- * dropped whole, not clipped; each (triangle, view) costs its bounding box.
+ * dropped whole, not clipped (cgs_mesh_depth_clipped below clips it); each (triangle, view) costs its bounding box.
  *
  * cgs_depth_window_max: out[v][i][j] = the maximum of depth[v][i + di][j + dj] over |di|, |dj| <= radius inside the image,
  * 0 <= radius <= CGS_DEPTH_MAX_WINDOW.  +inf (no surface) wins: after it a sample is hidden only if EVERY pixel around its
@@ -1461,12 +1461,64 @@ int cgs_ray_wins_depth(int nx, int ny, int nz, const double* lo /*host, [3]*/, c
  * there is work: E or V < 0, a size outside [1, CGS_EDT_MAX_SIZE], with a depth plane a slack that is negative, NaN or
  * infinite, and NULL pointers (edges only when E > 0; depth may be NULL) are CGS_ERR_INVALID_ARGUMENT, rejected before
  * anything is launched.  Then V = 0 is a no-op.
- * LIMITS: no near-plane clipping (a row with an end at or behind the camera plane is skipped whole); boundary edges of an
+ * LIMITS: no near-plane clipping (a row with an end at or behind the camera plane is skipped whole;
+ * cgs_mesh_contours_clipped below clips it); boundary edges of an
  * open mesh have one triangle and are never rows; the silhouette edges of a general triangulation zigzag across its facets.
  * ------------------------------------------------------------------------------------------------ */
 int cgs_mesh_contours(int E, const float* edges /*[E,4,3]*/, int V, const double* intr /*[V,4]*/,
                       const double* w2c /*[V,12]*/, int height, int width, const float* depth /*[V,height,width] or NULL*/,
                       double slack, uint8_t* mask_out /*[V,height,width]*/, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Near-plane clipping for the two mesh entries: occluders seen from INSIDE (a room, a coarse proxy mesh whose large
+ * triangles reach behind the camera plane while most of them fills the image).  Opt-in siblings: cgs_mesh_depth and
+ * cgs_mesh_contours are untouched.  near is in the camera's units (world units), finite and > 0.  A camera-space point is
+ * IN iff its c2 >= near; a NaN c2 is OUT.
+ *
+ * THE CUT, frozen -- float64, one rounded operation at a time in the written order, nothing contracted into an FMA, IEEE
+ * division -- of an edge is ALWAYS taken from its IN end a toward its OUT end b:
+ *   t = (a2 - near) / (a2 - b2)
+ *   p0 = a0 + t * (b0 - a0),  p1 = a1 + t * (b1 - a1),  p2 = near            (p2 is assigned, not computed)
+ * so two triangles that share a straddling edge compute the same point to the bit and no crack opens between them.  (One
+ * device function, near_cut of csrc/mesh_depth.h, serves both entries.)
+ *
+ * cgs_mesh_depth_clipped: cgs_mesh_depth with one step between the camera transform and the projection.  For every
+ * (triangle, view):
+ *   C_k = R X_k + T of the three vertices (nv_camera_xyz); a NaN in any coordinate of any C_k SKIPS the triangle
+ *   three IN:  the triangle goes on unchanged -- exactly the bits of cgs_mesh_depth
+ *   none IN:   the triangle is SKIPPED
+ *   one IN, at index i:       a = i, b = (i+1)%3, c = (i+2)%3;  the piece is (a, cut(a,b), cut(a,c))
+ *   two IN, the OUT one at i: c = i, a = (i+1)%3, b = (i+2)%3;  the pieces are (a, b, cut(b,c)) and (a, cut(b,c), cut(a,c))
+ *   every piece then runs through the set-up and the pixel rule of cgs_mesh_depth unchanged, with its three camera-space
+ *   vertices: z_k = c2 (> 0 or skipped), u_k, v_k, the NaN and area tests, the candidate box (clamped in float64 before the
+ *   conversion: a clipped piece often has image coordinates of 1e4 and more), coverage, the perspective-correct depth and
+ *   the integer atomic minimum
+ * The minimum still makes the plane independent of the launch geometry and of the order of the triangles and pieces.
+ *
+ * cgs_mesh_contours_clipped: cgs_mesh_contours with the ends A, B of a row clipped.  For every (row, view):
+ *   A, B, C, D as there; the row is SKIPPED when neither A nor B is IN
+ *   the contour test sc * sd > 0 is unchanged and uses the UNCLIPPED A, B, C, D
+ *   a row with one end OUT has that end replaced by the cut from the IN end toward it, before nv_image_uv
+ *   the clip to the image, the steps, and the per-step depth z = 1 / ((1 - t) / A2 + t / B2) use the clipped ends
+ *   a row with both ends IN produces the bytes of cgs_mesh_contours
+ *
+ * CONSEQUENCE.  The projection rule and nv_hidden are not touched: a sample with 0 < c2 < near is still SEEN by
+ * cgs_project_points and can only be hidden by a surface at c2 >= near -- the part of the mesh nearer than the plane is cut
+ * away and hides nothing.  With every vertex of every triangle IN (any camera outside the mesh, farther than near from it)
+ * both entries equal their siblings bit for bit.
+ *
+ * The arguments are checked as the siblings check theirs, plus one: near that is NaN, infinite or <= 0 is
+ * CGS_ERR_INVALID_ARGUMENT.  Every check happens before anything is launched; then V = 0 is a no-op.  Same stream rules: no
+ * allocation, no host synchronisation.  Limits: only the near plane -- the side planes of the frustum need no clip (the
+ * candidate box clamps them); each piece costs its bounding box, which for a clipped piece is usually the whole image.
+ * ------------------------------------------------------------------------------------------------ */
+int cgs_mesh_depth_clipped(int F, const float* tris /*[F,3,3]*/, int V, const double* intr /*[V,4]*/,
+                           const double* w2c /*[V,12]*/, int height, int width, double near,
+                           float* depth /*[V,height,width]*/, void* stream);
+int cgs_mesh_contours_clipped(int E, const float* edges /*[E,4,3]*/, int V, const double* intr /*[V,4]*/,
+                              const double* w2c /*[V,12]*/, int height, int width,
+                              const float* depth /*[V,height,width] or NULL*/, double slack, double near,
+                              uint8_t* mask_out /*[V,height,width]*/, void* stream);
 
 #ifdef __cplusplus
 }

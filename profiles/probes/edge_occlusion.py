@@ -1,5 +1,6 @@
 """python profiles/probes/edge_occlusion.py [--views 100] [--width 1600] [--height 1200] [--grid 224] [--edges 4000]
                                              [--samples 100] [--reps 20] [--thread_lib FILE] [--check_faces 4000] [--out FILE]
+                                             [--clip] [--only_clip] [--parent_lib FILE]
 
 Times the three occlusion kernels (profiles/edge_occlusion.md), everything resident, raw calls between device events after
 a warm-up, three rounds, the variants alternating within a round:
@@ -12,6 +13,12 @@ a warm-up, three rounds, the variants alternating within a round:
   cgs_depth_window_max at radius 1 and 4.
   cgs_point_mask_depth beside cgs_point_mask on the samples of profiles/probes/edge_dedupe.py (400 708 at the defaults),
       gated by the fine mesh's planes.
+
+``--clip`` (profiles/edge_clip.md): cgs_mesh_depth_clipped beside cgs_mesh_depth on the two meshes above -- seen from
+      outside, every vertex in front of the plane, so nothing is clipped and the planes must be equal bit for bit -- and, with
+      ``--parent_lib`` (a ``libcurvegs.so`` built from the commit before the clipping), beside that library's cgs_mesh_depth
+      in the same rounds; then the INDOOR case: the 24 coarse triangles of ``solid_scan``'s room with ``--views`` cameras
+      inside it, clipped (first view compared with the host back end) and unclipped.  ``--only_clip`` skips the rest.
 
 Before anything is timed the planes of the first ``--check_faces`` triangles of the fine mesh and of the coarse mesh in the
 first view, and the gated masks of the first two views, are compared with the host back end bit for bit."""
@@ -60,6 +67,9 @@ def main():
     p.add_argument("--thread_lib", default=None)
     p.add_argument("--check_faces", type=int, default=4000)
     p.add_argument("--out", default=None)
+    p.add_argument("--clip", action="store_true")
+    p.add_argument("--only_clip", action="store_true")
+    p.add_argument("--parent_lib", default=None)
     a = p.parse_args()
     import torch
     from curve_gaussian_amd import _lib as L
@@ -111,6 +121,69 @@ def main():
             print(f"  {name}: {[round(x, 3) for x in t]} ms per call", flush=True)
         result["ms"].update(ms)
 
+    def finish():
+        line = json.dumps(result)
+        print(line)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                f.write(line + "\n")
+
+    if a.clip or a.only_clip:
+        near = EO.NEAR_CLIP
+        parent = None
+        if a.parent_lib:
+            parent = ctypes.CDLL(os.path.abspath(a.parent_lib))
+            parent.cgs_mesh_depth.restype, parent.cgs_mesh_depth.argtypes = L.SIGNATURES["cgs_mesh_depth"]
+        for name, tris in meshes.items():
+            F = len(tris)
+            t_d = torch.from_numpy(tris).to(dev)
+            calls = {f"clip_{name}_unclipped": lambda: L.check(lib.cgs_mesh_depth(
+                         F, L.ptr(t_d), V, L.ptr(Kd), L.ptr(Md), H, W, L.ptr(depth), stream), "cgs_mesh_depth"),
+                     f"clip_{name}_clipped": lambda: L.check(lib.cgs_mesh_depth_clipped(
+                         F, L.ptr(t_d), V, L.ptr(Kd), L.ptr(Md), H, W, near, L.ptr(other), stream), "cgs_mesh_depth_clipped")}
+            if parent is not None:
+                calls[f"clip_{name}_parent"] = lambda: L.check(parent.cgs_mesh_depth(
+                    F, L.ptr(t_d), V, L.ptr(Kd), L.ptr(Md), H, W, L.ptr(depth), stream), "cgs_mesh_depth [parent]")
+                calls[f"clip_{name}_parent"]()
+                torch.cuda.synchronize()
+                kept = depth.clone()
+            calls[f"clip_{name}_unclipped"]()
+            calls[f"clip_{name}_clipped"]()
+            torch.cuda.synchronize()
+            assert same(depth, other), f"{name}: the clipped entry's planes differ from the unclipped one's"
+            if parent is not None:
+                assert same(depth, kept), f"{name}: this build and the parent write different bits"
+                del kept
+            print(f"clipping, {name}: {F} triangles seen from outside, clipped == unclipped"
+                  + (" == the parent build's" if parent is not None else "") + " bit for bit", flush=True)
+            rounds(calls, a.reps)
+        from curve_gaussian_amd.ops.view_chunks import camera_arrays
+        from curve_gaussian_amd.scene import solid_scan as SS
+        room, _ = SS.solid_geometry("room")
+        Kr, Mr = camera_arrays(SS.emap_cameras_of(SS.room_cameras(V, H, W)))
+        want = EO.mesh_depth(room, Kr[:1], Mr[:1], H, W, window=0, backend="host", near_clip=near)
+        assert same(EO.mesh_depth(room, Kr[:1], Mr[:1], H, W, window=0, near_clip=near), want), "room: disagrees with the host"
+        Krd, Mrd = ES.cameras_on(dev, Kr, np.ascontiguousarray(np.asarray(Mr).reshape(V, 12)))
+        r_d = torch.from_numpy(room).to(dev)
+        calls = {"clip_room_clipped": lambda: L.check(lib.cgs_mesh_depth_clipped(
+                     len(room), L.ptr(r_d), V, L.ptr(Krd), L.ptr(Mrd), H, W, near, L.ptr(other), stream), "cgs_mesh_depth_clipped"),
+                 "clip_room_unclipped": lambda: L.check(lib.cgs_mesh_depth(
+                     len(room), L.ptr(r_d), V, L.ptr(Krd), L.ptr(Mrd), H, W, L.ptr(depth), stream), "cgs_mesh_depth")}
+        calls["clip_room_clipped"]()
+        calls["clip_room_unclipped"]()
+        torch.cuda.synchronize()
+        result["room"] = {"faces": len(room), "inf_pixels_clipped": int(torch.isinf(other).sum()),
+                          "inf_pixels_unclipped": int(torch.isinf(depth).sum()), "pixels": V * H * W, "near": near}
+        print(f"clipping, room: {len(room)} triangles, cameras inside, first view equal to the host; +inf pixels "
+              f"{result['room']['inf_pixels_clipped']} clipped, {result['room']['inf_pixels_unclipped']} unclipped of {V * H * W}",
+              flush=True)
+        rounds(calls, a.reps)
+        result.update({"faces": {k: len(v) for k, v in meshes.items()}, "reps": a.reps, "parent": bool(a.parent_lib)})
+        if a.only_clip:
+            finish()
+            return
+
     print("a +inf fill of the planes alone (torch's fill kernel):", flush=True)
     rounds({"fill": lambda: depth.fill_(float("inf"))}, a.reps)
     for name, tris in meshes.items():
@@ -150,12 +223,7 @@ def main():
                                                              L.ptr(kept), stream), "cgs_point_mask")}, a.reps)
     result.update({"points": P, "faces": {k: len(v) for k, v in meshes.items()}, "reps": a.reps,
                    "hidden_sample_views": int(hidden.sum())})
-    line = json.dumps(result)
-    print(line)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    finish()
 
 
 if __name__ == "__main__":
