@@ -57,11 +57,14 @@ K is fixed by test_raster_ref64_cpu.py from the C oracle (oracle/raster_ref.c: t
 in double): 4 x the largest ratio |oracle - truth| / (eps * scale) over all scenes and tensors, rounded up to a power of two, at
 least 16.  It is never taken from a HIP run.  Measured (worst over the scenes of SCENES, all upstream gradients flowing; the
 scene it was measured on in brackets; the CPU test prints them again per scene):
-    color 1.28, invdepth 4.19, all_map 6.33 [centres: a pixel under one turned, elongated splat -- the float32 pixel-space centre
-    and conic move the exponent by about eps m, the first term of the image bound, which counts it once];
-    dL_dmeans3D 0.42, dL_dmeans2D 0.43, dL_dopacity 0.18, dL_dcolors 1.18, dL_dscales 0.46, dL_drotations 0.23,
-    dL_dall_map 1.27 [uneven_17_0_1_104].
-4 x 6.33 = 25.3  ->  K = 32.
+    color 2.88 [turned_0], invdepth 6.07, all_map 10.66, dL_dcolors 5.00 [turned_2: a 61 x 77 image under a turned camera,
+    pixels under thin (0.7 .. 0.9 px) splats at axis ratio 20 -- the float32 per-splat state moves the exponent by more than
+    eps m there: the pixel-space centre is rounded at eps |px| (px up to 77, not 16) and the conic of a thin turned splat
+    loses the digits that a c - b^2 cancels; K absorbs both, as it did at 6.33 for the `centres` scene at 48 x 48];
+    dL_dmeans3D 0.79, dL_dmeans2D 0.82, dL_dopacity 1.89, dL_dscales 0.99, dL_dall_map 5.14 [turned_1],
+    dL_drotations 0.65 [long_9000].
+4 x 10.66 = 42.6  ->  K = 64.  (Before the long and turned scenes: all_map 6.33 [centres], K = 32; the longest list, 9000
+entries, stays at dL_dall_map 2.64: the accumulation terms of the bounds hold their form.)
 
 Scenes
 ------
@@ -69,6 +72,23 @@ SCENES names, per scene, the per-quadrant list lengths it must produce (quadrant
 seed whose scene fails a margin is replaced in the table.  One departure from a naive reading of "far centres": the reference
 clamps x/z at 1.3 tan(fov) in the projection's Jacobian and its backward is not the derivative beyond, so a centre can lie at
 most 0.3 * W/2 px outside the image (7 px at 48 x 48) -- m still runs into the thousands under the turned, elongated splats.
+
+Decisions: cleared per splat, masked per pixel
+----------------------------------------------
+A float32 forward may legitimately decide the other way wherever the float64 forward decides within a few bounds of an edge,
+and nothing of such an element can be compared.  Two kinds:
+- per splat (radius ceil, tile rect edge, near cull, the 1.3 tan(fov) clamp, depth keys under 4 ulp apart or tied between
+  different 3D centres, opacity in the slack of the 1/255 cut): splat_failures.  Builder.clear re-draws such a splat from the
+  scene's own rng when the scene is built (random_scene drops it), so no scene has one.
+- per pair (alpha >= 1/255, T < 1e-4, the 0.99 clamp): with tens of thousands of pairs one always lands inside its margin.
+  undecided_pixels masks the PIXEL of such a pair: its three upstream gradients are zero (scene_grads), so each of its pairs
+  contributes g = alpha * sum_ch d_ch (...) = 0 to every gradient exactly, in any arithmetic and whichever way a kernel
+  decides; the truth and the bounds need no new term, and the pixel is left out of the image, `terminated` and n_contrib
+  comparisons.  A kernel that turns a zero upstream gradient into a contribution fails the bound == 0 => exact zero rule.
+  check_mask: at most 5 % of a scene's pixels and 16 of the 64 of any quadrant of any tile; the scenes of OLD_SCENES (lists of
+  at most 286 entries, built until every pair clears its margin) must have none.
+The long_* scenes (one tile, 1024 .. 9000 entries: every sort and every batch carry of the compositors), the turned_* scenes
+(20 tiles under the three turned cameras, depth ties) and the random scenes (RANDOM_SCENES) rest on the mask.
 """
 import math
 
@@ -80,9 +100,9 @@ from oracle import torch_ref as TR
 
 EPS = 2.0 ** -24
 # worst |oracle - truth| / (eps * scale) per tensor over SCENES, as printed by test_raster_ref64_cpu.py
-K_MEASURED = {"color": 1.28, "invdepth": 4.19, "all_map": 6.33, "dL_dmeans3D": 0.42, "dL_dmeans2D": 0.43, "dL_dopacity": 0.18,
-              "dL_dcolors": 1.18, "dL_dscales": 0.46, "dL_drotations": 0.23, "dL_dall_map": 1.27}
-K = 32.0   # 4 x max(K_MEASURED) = 25.3, rounded up to a power of two
+K_MEASURED = {"color": 2.88, "invdepth": 6.07, "all_map": 10.66, "dL_dmeans3D": 0.79, "dL_dmeans2D": 0.82, "dL_dopacity": 1.89,
+              "dL_dcolors": 5.00, "dL_dscales": 0.99, "dL_drotations": 0.65, "dL_dall_map": 5.14}
+K = 64.0   # 4 x max(K_MEASURED) = 42.6, rounded up to a power of two
 
 DT = torch.float64
 
@@ -93,34 +113,85 @@ def _camera(H, W):
     return S.make_camera((0.0, 0.0, 0.0), (0.0, 0.0, 1.0), (0.0, -1.0, 0.0), H, W)
 
 
+def _mat_to_quat(R):
+    """(w, x, y, z) of a rotation matrix (Shepperd's branch on the largest of w, x, y, z)."""
+    t = (R[0, 0] + R[1, 1] + R[2, 2], R[0, 0], R[1, 1], R[2, 2])
+    k = int(np.argmax(t))
+    if k == 0:
+        q = np.array([1 + t[0], R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
+    elif k == 1:
+        q = np.array([R[2, 1] - R[1, 2], 1 + 2 * R[0, 0] - t[0], R[0, 1] + R[1, 0], R[0, 2] + R[2, 0]])
+    elif k == 2:
+        q = np.array([R[0, 2] - R[2, 0], R[0, 1] + R[1, 0], 1 + 2 * R[1, 1] - t[0], R[1, 2] + R[2, 1]])
+    else:
+        q = np.array([R[1, 0] - R[0, 1], R[0, 2] + R[2, 0], R[1, 2] + R[2, 1], 1 + 2 * R[2, 2] - t[0]])
+    return q / np.linalg.norm(q)
+
+
 class Builder:
     """Collects 3D splats whose projections land where wanted: centre on the camera ray through pixel (u, v) at depth z, pixel
-    standard deviations (su, sv) along axes turned by `angle` in the image plane."""
+    standard deviations (su, sv) along axes turned by `angle` in the image plane.  `cam`: a general camera (None: the one at
+    the origin with the world's axes); rows that name the same `tie` share one bit-identical 3D centre."""
 
-    def __init__(self, H, W, seed):
+    def __init__(self, H, W, seed, cam=None):
         self.H, self.W = H, W
-        self.cam = _camera(H, W)
+        self.cam = _camera(H, W) if cam is None else cam
+        self.turned = cam is not None
+        V = self.cam.world_view_transform.double().numpy().T          # p_view = V p_world
+        self.Rwc, self.twc = V[:3, :3], V[:3, 3]
         self.tfx, self.tfy = math.tan(self.cam.FoVx * 0.5), math.tan(self.cam.FoVy * 0.5)
         self.fx, self.fy = W / (2 * self.tfx), H / (2 * self.tfy)
         self.rng = np.random.default_rng(seed)
         self.rows = []
 
-    def add(self, u, v, z, su, sv, op, angle=0.0):
+    def _place(self, u, v, z, su, sv, angle):
         x = z * self.tfx * ((2 * u + 1) / self.W - 1)
         y = z * self.tfy * ((2 * v + 1) / self.H - 1)
         # pixel variance = (f s / z)^2 + 0.3 (the dilation): solve for s on the optical axis (off axis the projection shears
         # it a little: the lists are computed from the real projection, not from these numbers)
         s1 = math.sqrt(max(su * su - 0.3, 1e-4)) * z / self.fx
         s2 = math.sqrt(max(sv * sv - 0.3, 1e-4)) * z / self.fy
+        mean, rot = (x, y, z), (math.cos(angle / 2), 0.0, 0.0, math.sin(angle / 2))
+        if self.turned:   # the same splat in the camera's frame, carried to the world
+            c, s = math.cos(angle), math.sin(angle)
+            mean = tuple(self.Rwc.T @ (np.array(mean) - self.twc))
+            rot = tuple(_mat_to_quat(self.Rwc.T @ np.array([[c, -s, 0.0], [s, c, 0.0], [0.0, 0.0, 1.0]])))
+        return dict(mean=mean, scale=(s1, s2, 0.05 * min(s1, s2)), rot=rot)
+
+    def add(self, u, v, z, su, sv, op, angle=0.0, tie=None):
         r = self.rng
-        self.rows.append(dict(mean=(x, y, z), scale=(s1, s2, 0.05 * min(s1, s2)),
-                              rot=(math.cos(angle / 2), 0.0, 0.0, math.sin(angle / 2)), op=op,
-                              color=r.uniform(0.2, 1.0), amap=tuple(r.normal(size=3)) + (1.0,)))
+        self.rows.append(dict(self._place(u, v, z, su, sv, angle), op=op,
+                              color=r.uniform(0.2, 1.0), amap=tuple(r.normal(size=3)) + (1.0,),
+                              spec=[u, v, z, su, sv, angle], tie=tie))
 
     def splats(self):
         f = lambda k: torch.tensor([r[k] for r in self.rows], dtype=torch.float32)
         return dict(means3D=f("mean"), scales=f("scale"), rotations=f("rot"), opacities=f("op").reshape(-1, 1),
                     all_map=f("amap"), colors=f("color").reshape(-1, 1))
+
+    def clear(self, max_rounds=64):
+        """Re-draws, from the scene's own rng, every splat one of whose per-splat decisions (splat_failures) sits inside
+        its margin -- a nudge of its centre (of all rows of its tie, together), depth, size and opacity -- until none
+        does.  Returns the number of re-draws; a scene whose splats all pass is left as it was built, rng included."""
+        n = 0
+        for _ in range(max_rounds):
+            fail = np.nonzero(splat_failures(self.splats(), self.cam, self.H, self.W).any(1))[0]
+            if not len(fail):
+                return n
+            r = self.rng
+            for i in fail:
+                row = self.rows[i]
+                du, dv, fz = r.uniform(-0.3, 0.3), r.uniform(-0.3, 0.3), 1.0 + r.uniform(-2e-5, 2e-5)
+                fs, fo = r.uniform(0.97, 1.03, 2), r.uniform(0.97, 1.03)
+                for j, other in enumerate(self.rows):
+                    if j == i or (row["tie"] is not None and other["tie"] == row["tie"]):
+                        sp = other["spec"]
+                        sp[0], sp[1], sp[2] = sp[0] + du, sp[1] + dv, sp[2] * fz
+                        if j == i:
+                            sp[3], sp[4], other["op"] = sp[3] * fs[0], sp[4] * fs[1], other["op"] * fo
+                        other.update(self._place(*sp))
+                n += 1
+        raise AssertionError(f"Builder.clear: per-splat margins still fail after {max_rounds} rounds")
 
 
 def _stack(H, W, n, seed, centre, sigma, jitter=0.7):
@@ -280,6 +351,74 @@ def _scene_pooled(k, seed):
     return b
 
 
+def _faint(b, n, z0, dz, op_scale=1.0, tie_groups=0, sigma=1.5):
+    """n small faint splats (sigma .. 1.25 sigma px, opacity 0.02 .. 0.04 times op_scale but at least 0.011: above 2/255 at
+    the pixel next to the centre) whose centres lie inside the single tile, at depths z0 + dz * (a permutation of 0 .. n-1);
+    with tie_groups, row i takes the centre of group i % tie_groups."""
+    r = b.rng
+    k = tie_groups or n
+    depth = r.permutation(k)
+    cu, cv = r.uniform(0.5, 14.5, k), r.uniform(0.5, 14.5, k)
+    for i in range(n):
+        j = i % k
+        b.add(cu[j], cv[j], z0 + dz * depth[j], sigma * r.uniform(1.0, 1.25), sigma * r.uniform(1.0, 1.25),
+              max(0.011, op_scale * r.uniform(0.02, 0.04)), r.uniform(0, math.pi), tie=j if tie_groups else None)
+
+
+def _scene_long(n, seed):
+    """One 16 x 16 tile whose list is exactly n entries long: every centre inside the tile, so faint that no pixel
+    terminates: beyond 2500 entries the opacities shrink with 1 / n, beyond 5000 the splats as well (sigma 1 px), which keeps
+    sum alpha of a pixel near 5 and the pairs on the alpha >= 1/255 edge few."""
+    b = Builder(16, 16, seed)
+    _faint(b, n, 2.0, 0.0005, min(1.0, 2500.0 / n), sigma=1.5 if n <= 5000 else 1.0)
+    return b
+
+
+def _scene_long_term(seed):
+    """1100 faint entries that leave T well above 1e-4, then 8 opaque splats that terminate the centre pixels inside the
+    forward's fifth batch of 256 (the backward's ninth of 128) while the rim runs on, then 200 more faint entries."""
+    b = Builder(16, 16, seed)
+    _faint(b, 1100, 2.0, 0.0005)
+    _opaque(b, 8, (7.5, 7.5), 3.2, 3.0)
+    _faint(b, 200, 3.5, 0.0005)
+    return b
+
+
+def _scene_long_ties(seed):
+    """1700 entries in one tile on 300 distinct centres: depth ties of 5 or 6 rows each, ordered by index."""
+    b = Builder(16, 16, seed)
+    _faint(b, 1700, 2.0, 0.001, tie_groups=300)
+    return b
+
+
+# the turned cameras of test_raster_gpu.CAMS (eye, target, up); the last one sits inside that module's random cloud
+TURNED_CAMS = [((0.5, -1.6, 0.7), (0.5, 0.5, 0.5), (0, 0, 1)), ((2.0, 1.4, 1.1), (0.4, 0.5, 0.6), (0, 0, 1)),
+               ((0.5, 0.5, 0.5), (0.9, 0.2, 0.5), (0, 0, 1))]
+TURNED_HW = (61, 77)   # the 4 x 5 tiles of a 64 x 80 image, cut so that the last row and the last column of tiles are ragged
+
+
+def _scene_turned(cam_i, seed):
+    """About 300 splats in front of a turned camera: two screen-filling ones, 40 thin elongated ones (axis ratio 20), 8
+    centres that three rows each share (depth ties, ordered by index) and small ones."""
+    H, W = TURNED_HW
+    b = Builder(H, W, seed, cam=S.make_camera(*TURNED_CAMS[cam_i], H, W))
+    r = b.rng
+    uv = lambda: (r.uniform(1.0, W - 2.0), r.uniform(1.0, H - 2.0))
+    for z in (1.5, 2.5):
+        b.add(W / 2 + r.uniform(-6, 6), H / 2 + r.uniform(-6, 6), z, 60.0 * r.uniform(1.0, 1.2), 60.0 * r.uniform(1.0, 1.2),
+              r.uniform(0.15, 0.25), r.uniform(0, math.pi))
+    for _ in range(40):
+        sv = r.uniform(0.7, 0.9)
+        b.add(*uv(), r.uniform(1.0, 4.0), 20.0 * sv, sv, r.uniform(0.3, 0.6), r.uniform(0, math.pi))
+    for g in range(8):
+        (u, v), z = uv(), r.uniform(1.0, 4.0)
+        for _ in range(3):
+            b.add(u, v, z, r.uniform(1.5, 4.0), r.uniform(1.5, 4.0), r.uniform(0.1, 0.5), r.uniform(0, math.pi), tie=g)
+    for _ in range(234):
+        b.add(*uv(), r.uniform(1.0, 4.0), r.uniform(0.8, 3.0), r.uniform(0.8, 3.0), r.uniform(0.1, 0.7), r.uniform(0, math.pi))
+    return b
+
+
 def _all4(n):
     return {0: (n, n, n, n)}
 
@@ -295,8 +434,9 @@ SCENES = {}
 # gradients: 95 96 97) and CGS_BWD3_CAP_GEO = 64 (all_map gradients: 63 64 65); BWD_BATCH 127 128 129; BATCH / UB 255 256 257;
 # a third backward batch 260
 for _n in (1, 7, 8, 9, 15, 16, 17, 31, 32, 33, 63, 64, 65, 95, 96, 97, 103, 104, 105, 127, 128, 129, 255, 256, 257, 260):
-    # (seeds replaced in the table because a decision sat inside its margin: 1095 -> 11095, 1097 -> 11097)
-    SCENES[f"stack16_{_n}"] = (_scene_stack16, (_n,), {95: 11095, 97: 11097}.get(_n, 1000 + _n), _all4(_n))
+    # (seeds replaced in the table because a decision sat inside its margin: 1095 -> 11095, 1097 -> 11097; at K = 64, whose
+    # margins are twice as wide, 1096 -> 21096)
+    SCENES[f"stack16_{_n}"] = (_scene_stack16, (_n,), {95: 11095, 96: 21096, 97: 11097}.get(_n, 1000 + _n), _all4(_n))
     SCENES[f"ragged_{_n}"] = (_scene_stack_ragged, (_n,), 2000 + _n, _all4_ragged(_n))
 SCENES["uneven_17_0_1_104"] = (_scene_uneven, ((17, 0, 1, 104),), 3001, {0: (17, 0, 1, 104)})
 SCENES["uneven_0_0_0_33"] = (_scene_uneven, ((0, 0, 0, 33),), 3002, {0: (0, 0, 0, 33)})
@@ -312,24 +452,75 @@ SCENES["term_group_16"] = (_scene_term_group, (11,), 4004, _all4(22))
 SCENES["term_group_17"] = (_scene_term_group, (12,), 14005, _all4(23))
 SCENES["ties"] = (_scene_ties, (), 5001, _all4(20))
 SCENES["centres"] = (_scene_centres, (), 6001, None)
+OLD_SCENES = tuple(SCENES)   # every pair decision of these clears its margin: their masks (undecided_pixels) are empty
+
+# Scenes whose undecided pixels are masked, with a fifth table entry: `list` = the exact length of tile 0's list (None: the
+# lists are reported), `layout` = the binning layout the operator's SECOND call must report (1: single-pass buckets, whose
+# capacity is 5/4 of the longest list + 64, rounded up to 64 -- 0: exact, once that passes bucket_cap_limit() = 4096 entries,
+# which lists from 3226 entries on do), `instances` = "long": four instances only (three truths; the float64 walk dominates).
+# long_N: the rank sort's first and last length (1025, 2048), the LDS network's (2049, 4096), the global-memory network (4097,
+# 9000); the forward carries T through 4 .. 36 batches of 256, the backward through twice as many of 128.
+for _n in (1024, 1025, 2048, 2049, 4096, 4097, 9000):
+    SCENES[f"long_{_n}"] = (_scene_long, (_n,), 8000 + _n, None, dict(list=_n, layout=int(_n <= 3225), instances="long"))
+SCENES["long_term_1100"] = (_scene_long_term, (), 8101, None, dict(list=1308, layout=1, instances="long"))
+SCENES["long_ties"] = (_scene_long_ties, (), 8102, None, dict(list=1700, layout=1, instances="long"))
+for _k in range(3):
+    SCENES[f"turned_{_k}"] = (_scene_turned, (_k,), 8200 + _k, None, dict(list=None, layout=1, instances="all"))
 
 
 class Scene:
-    def __init__(self, name):
-        fn, args, seed, expect = SCENES[name]
-        b = fn(*args, seed)
+    def __init__(self, name, built=None):
+        if built is None:
+            fn, args, seed, expect = SCENES[name][:4]
+            opts = SCENES[name][4] if len(SCENES[name]) > 4 else None
+            b = fn(*args, seed)
+            self.redrawn = b.clear()
+            sp, cam, H, W = b.splats(), b.cam, b.H, b.W
+        else:   # (splats, camera, H, W, seed): a scene from elsewhere (the random ones), cleared by its maker
+            sp, cam, H, W, seed = built
+            expect, opts, self.redrawn = None, dict(list=None, layout=None, instances="all"), 0
         self.name, self.seed, self.expect = name, seed, expect
-        self.sp, self.cam, self.H, self.W = b.splats(), b.cam, b.H, b.W
-        self.tfx, self.tfy = b.tfx, b.tfy
+        self.masked = opts is not None          # undecided pixels are masked instead of forbidden
+        self.list_len, self.layout, self.instances = ((opts["list"], opts["layout"], opts["instances"]) if opts else (None, 1, "all"))
+        self.sp, self.cam, self.H, self.W = sp, cam, H, W
+        self.tfx, self.tfy = math.tan(cam.FoVx * 0.5), math.tan(cam.FoVy * 0.5)
         self.P = self.sp["means3D"].shape[0]
         self.bg = torch.tensor([0.3, 0.0, 0.0])
 
 
-def scene_grads(scene, which=(True, True, True)):
-    """Seeded upstream gradients (dL/dcolour, dL/dinvdepth, dL/dall_map); None where `which` is False."""
+# Random scenes from the generator of test_raster_gpu's bucket-against-exact fuzz test (synthetic.random_splats under its three
+# cameras, every third with the depth-tie trick), sized to the pair budget P * H * W <= 4e6:
+# (seed, H, W, P, smallest scale, largest / smallest, camera, depth ties).  A row whose scene misses a mask condition
+# (check_mask) is replaced, as in SCENES.
+RANDOM_SCENES = [(2001, 33, 47, 500, 0.01, 10, 0, True), (2002, 64, 64, 500, 0.002, 40, 1, False), (2003, 16, 47, 3000, 0.01, 2, 2, False),
+                 (2004, 100, 128, 300, 0.05, 2, 0, True), (2005, 33, 64, 1500, 0.002, 10, 1, False), (2006, 64, 47, 64, 0.05, 10, 2, False),
+                 (2007, 16, 16, 3000, 0.01, 10, 0, True), (2008, 100, 47, 500, 0.01, 40, 1, False)]
+
+
+def random_scene(row):
+    """The Scene of a RANDOM_SCENES row: splats one of whose per-splat decisions sits inside its margin (splat_failures, off-
+    screen ones included) are dropped before anything runs."""
+    seed, H, W, P, lo, mult, cam_i, ties = row
+    sp = S.random_splats(P, seed, scale_range=(lo, lo * mult))
+    if ties:
+        sp["means3D"] = sp["means3D"][torch.arange(P) % max(1, P // 20)]
+    cam = S.make_camera(*TURNED_CAMS[cam_i], H, W)
+    keep = torch.from_numpy(~splat_failures(sp, cam, H, W, outside=True).any(1))
+    sp = {k: v[keep].contiguous() for k, v in sp.items()}
+    assert not splat_failures(sp, cam, H, W, outside=True).any()
+    return Scene(f"random_{seed}", built=(sp, cam, H, W, seed))
+
+
+def scene_grads(scene, which=(True, True, True), mask=None):
+    """Seeded upstream gradients (dL/dcolour, dL/dinvdepth, dL/dall_map); None where `which` is False.  `mask` [H, W]: the
+    undecided pixels, where all three are zero -- every pair of such a pixel then contributes alpha * sum_ch d_ch (...) = 0 to
+    every gradient, exactly and in any arithmetic, whichever way a kernel decides there."""
     g = torch.Generator().manual_seed(scene.seed + 7)
     H, W = scene.H, scene.W
     d = (torch.randn(1, H, W, generator=g), torch.randn(1, H, W, generator=g), torch.randn(4, H, W, generator=g))
+    if mask is not None and mask.any():
+        keep = torch.from_numpy(~mask)
+        d = tuple(t * keep for t in d)
     return tuple(t if w else None for t, w in zip(d, which))
 
 
@@ -551,21 +742,19 @@ def bounds(t, K=None, J=None):
 
 
 # ----------------------------------------------------------------------------------------------------------------- margins
-def margins(scene, t=None, K=None):
+def margins(scene, t=None, K=None, mask=None):
     """Distance of every decision of the float64 forward from its edge; the first two as multiples of the pair's own bound.
-    Returns a dict of the smallest margins (each must be >= its entry of MARGIN_MIN)."""
-    K = globals()["K"] if K is None else K
+    Returns a dict of the smallest margins (check_margins holds each to its minimum).  `mask`: the scene's undecided pixels,
+    whose pairs are left out of the per-pair margins (alpha, T, alpha_max)."""
     t = Truth(scene, variant(scene, "base")) if t is None else t
     out = {}
-    reached = t.member & ~_done_before(t)
-    a_err = K * EPS * (1 + t.m)
-    r = np.abs(255.0 * t.alpha_u - 1.0) / a_err
-    out["alpha"] = float(r[reached].min()) if reached.any() else np.inf
-    tested = t.blended | t.stopped
-    Tn = t.Tb * (1 - np.minimum(t.alpha_u, 0.99))
-    t_err = K * EPS * (t.n_front + 1 + (1 + t.m) * t.alpha_u / (1 - np.minimum(t.alpha_u, 0.99)) + t.X[None, :])
-    r = np.abs(1e4 * Tn - 1.0) / t_err
-    out["T"] = float(r[tested].min()) if tested.any() else np.inf
+    reached, r_alpha, tested, r_T = _pair_margins(t, K)
+    member = t.member
+    if mask is not None and mask.any():   # the undecided pixels carry no loss and are not compared: their pairs do not count
+        keep = ~mask.reshape(-1)[None, :]
+        reached, tested, member = reached & keep, tested & keep, member & keep
+    out["alpha"] = float(r_alpha[reached].min()) if reached.any() else np.inf
+    out["T"] = float(r_T[tested].min()) if tested.any() else np.inf
     vis = t.radii > 0
     rad = 3.0 * np.sqrt(t.lam[vis])
     out["radius"] = float((np.minimum(np.ceil(rad) - rad, rad - np.floor(rad)) / rad).min()) if vis.any() else 1.0
@@ -583,21 +772,123 @@ def margins(scene, t=None, K=None):
     zs = np.sort(z32)
     gaps = np.diff(zs.view(np.int32).astype(np.int64))
     out["depth_ulps"] = int(gaps[gaps > 0].min()) if (gaps > 0).any() else 1 << 30
-    if (gaps == 0).any():   # ties must be bit-identical in every arithmetic: identical 3D centres' z and a camera on the axes
-        zin = scene.sp["means3D"][:, 2].numpy()[vis]
+    if (gaps == 0).any():   # ties must be bit-identical in every arithmetic: rows with bit-identical means3D (_tie_rows)
+        min3 = _tie_rows(scene.sp["means3D"], scene.cam)[vis]
         for zv in np.unique(zs[1:][gaps == 0]):
-            assert len(np.unique(zin[z32 == zv])) == 1, "depth tie between different inputs"
-    out["alpha_max"] = float(t.alpha_u[t.member].max()) if t.member.any() else 0.0
-    m = scene.sp["means3D"].double().numpy()
-    out["clamp"] = float(min((1.3 * scene.tfx - np.abs(m[:, 0] / m[:, 2])).min() / scene.tfx,
-                             (1.3 * scene.tfy - np.abs(m[:, 1] / m[:, 2])).min() / scene.tfy))
-    out["near"] = float((t.tz / 0.2 - 1.0).min())
+            assert len(np.unique(min3[z32 == zv], axis=0)) == 1, "depth tie between different inputs"
+    out["alpha_max"] = float(t.alpha_u[member].max()) if member.any() else 0.0
+    m = _view_space(scene.sp["means3D"], scene.cam)
+    front = t.tz > 0.2     # (a splat behind the near plane is culled whatever its x / z)
+    out["clamp"] = float(min((1.3 * scene.tfx - np.abs(m[front, 0] / m[front, 2])).min() / scene.tfx,
+                             (1.3 * scene.tfy - np.abs(m[front, 1] / m[front, 2])).min() / scene.tfy)) if front.any() else 1.0
+    out["near"] = float(np.abs(t.tz / 0.2 - 1.0).min())
     return out
+
+
+def _view_space(means3D, cam):
+    """[P, 3] float64 view-space centres (for the camera at the origin with the world's axes: means3D itself, exactly)."""
+    V = cam.world_view_transform.double().numpy().T
+    return means3D.double().numpy() @ V[:3, :3].T + V[:3, 3]
+
+
+def _tie_rows(means3D, cam):
+    """What two rows must share bit for bit for their depth keys to tie in every arithmetic: means3D -- of which a camera
+    whose view depth IS the world's z (the one at the origin with the world's axes) reads the z alone."""
+    m = means3D.numpy()
+    V = cam.world_view_transform.numpy().T
+    return m[:, 2:3] if (V[2] == np.array([0.0, 0.0, 1.0, 0.0], np.float32)).all() else m
 
 
 def _done_before(t):
     s = np.cumsum(t.stopped, 0)
     return (s - t.stopped) > 0
+
+
+def _pair_margins(t, K=None):
+    """(reached, r_alpha, tested, r_T), all [N, npix]: the pairs whose alpha >= 1/255 decision the float64 forward reached
+    and that decision's distance from its edge in bounds of the pair's own alpha; the pairs whose T (1 - alpha) < 1e-4 test it
+    ran and that test's distance in bounds of the pair's own T."""
+    K = globals()["K"] if K is None else K
+    reached = t.member & ~_done_before(t)
+    a_err = K * EPS * (1 + t.m)
+    r_alpha = np.abs(255.0 * t.alpha_u - 1.0) / a_err
+    tested = t.blended | t.stopped
+    Tn = t.Tb * (1 - np.minimum(t.alpha_u, 0.99))
+    t_err = K * EPS * (t.n_front + 1 + (1 + t.m) * t.alpha_u / (1 - np.minimum(t.alpha_u, 0.99)) + t.X[None, :])
+    r_T = np.abs(1e4 * Tn - 1.0) / t_err
+    return reached, r_alpha, tested, r_T
+
+
+def undecided_pixels(scene, t, K=None):
+    """[H, W] bool: the pixels at which a pair the float64 forward reached sits within 4 bounds of a per-pair decision
+    (alpha >= 1/255, T < 1e-4) or above the 0.97 that keeps the 0.99 clamp out of reach: there a float32 forward may
+    legitimately decide the other way.  Such pixels carry no loss (scene_grads) and are left out of the image, `terminated`
+    and n_contrib comparisons; check_mask limits how many a scene may have."""
+    reached, r_alpha, tested, r_T = _pair_margins(t, K)
+    und = (reached & (r_alpha < 4.0)) | (tested & (r_T < 4.0)) | (reached & (t.alpha_u > 0.97))
+    return und.any(0).reshape(scene.H, scene.W) if len(t.order) else np.zeros((scene.H, scene.W), bool)
+
+
+def check_mask(scene, mask):
+    """At most 5 % of the scene's pixels and at most 16 of the 64 pixels of any quadrant of any tile are undecided; a scene
+    that is not in the masked part of the table has none."""
+    if not scene.masked:
+        assert not mask.any(), f"{scene.name}: {int(mask.sum())} undecided pixels in a scene that must have none"
+    assert mask.sum() <= 0.05 * mask.size, f"{scene.name}: {int(mask.sum())} of {mask.size} pixels undecided"
+    H8, W8 = -(-scene.H // 8), -(-scene.W // 8)
+    pad = np.zeros((H8 * 8, W8 * 8), bool)
+    pad[:scene.H, :scene.W] = mask
+    worst = int(pad.reshape(H8, 8, W8, 8).sum((1, 3)).max())
+    assert worst <= 16, f"{scene.name}: {worst} undecided pixels in one quadrant"
+
+
+def splat_failures(sp, cam, H, W, outside=False):
+    """[P, 6] bool, per splat, in float64: a per-splat decision inside the margin check_margins asks for -- radius ceil, tile
+    rect edge, near cull, the 1.3 tan(fov) clamp, a depth key under 4 ulp from (or tied with) that of a different 3D centre,
+    opacity in the slack of the 1/255 cut.  These are cleared where the scene is built (Builder.clear), never masked.
+    `outside`: also flag what margins() has no word on because the constructed scenes do not have it -- a rect edge within
+    1e-4 of the grid's far side from beyond, and any decision of a splat the float64 forward culls off-screen."""
+    tfx, tfy = math.tan(cam.FoVx * 0.5), math.tan(cam.FoVy * 0.5)
+    d = lambda v: v.to(DT)
+    px, py, _, opac, tz, cov = (v.numpy() for v in TR.preprocess_2d(
+        d(sp["means3D"]), d(sp["opacities"]), d(sp["scales"]), d(sp["rotations"]), d(cam.world_view_transform),
+        d(cam.full_proj_transform), tfx, tfy, H, W))
+    P = len(tz)
+    a, b, c = cov.T
+    mid = 0.5 * (a + c)
+    rad = 3.0 * np.sqrt(mid + np.sqrt(np.maximum(mid * mid - (a * c - b * b), 0.1)))
+    R = np.ceil(rad)
+    gx, gy = (W + 15) // 16, (H + 15) // 16
+    front = tz > 0.2
+    rect = np.stack([np.clip(np.trunc(q), 0, g) for q, g in (((px - R) / 16, gx), ((py - R) / 16, gy), ((px + R + 15) / 16, gx),
+                                                              ((py + R + 15) / 16, gy))], 1)
+    vis = front & ((rect[:, 2] - rect[:, 0]) * (rect[:, 3] - rect[:, 1]) > 0)
+    judged = front if outside else vis
+    fail = np.zeros((P, 6), bool)
+    fail[:, 0] = judged & (np.minimum(np.ceil(rad) - rad, rad - np.floor(rad)) / rad < 1e-5)
+    for cc, gmax in ((px, gx), (py, gy)):
+        for q in ((cc - R) / 16, (cc + R + 15) / 16):
+            inside = (q > 0) & (q < gmax + (1e-3 if outside else 0.0))
+            fail[:, 1] |= judged & inside & (np.abs(q - np.round(q)) < 1e-4)
+    fail[:, 2] = np.abs(tz / 0.2 - 1.0) < 0.01
+    m = _view_space(sp["means3D"], cam)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        fail[:, 3] = front & ~((1.3 * tfx - np.abs(m[:, 0] / m[:, 2]) >= 0.01 * tfx) & (1.3 * tfy - np.abs(m[:, 1] / m[:, 2]) >= 0.01 * tfy))
+    ids = np.nonzero(judged)[0]
+    z32 = tz[ids].astype(np.float32)
+    o = np.argsort(z32, kind="stable")
+    key = z32[o].view(np.int32).astype(np.int64)
+    m3 = _tie_rows(sp["means3D"], cam)[ids[o]]
+    for k in np.nonzero(np.diff(key) < 4)[0]:   # the later row of a close pair (a run of ties flags every row after its first)
+        first = k
+        while first > 0 and key[first - 1] == key[k]:
+            first -= 1
+        if key[k + 1] != key[k] or (m3[k + 1] != m3[first]).any():
+            fail[ids[o[k + 1]], 4] = True
+    with np.errstate(divide="ignore"):   # (quadrant_lists' two assertions on the opacity)
+        fail[:, 5] = judged & (((opac < 1.0 / 255.0) & (opac >= 0.5 / 255.0)) |
+                               ((opac >= 1.0 / 255.0) & (2.0 * np.log(255.0 * opac) <= 0.05)))
+    return fail
 
 
 def check_margins(mg):
@@ -631,7 +922,9 @@ def quadrant_lists(scene, t=None, strict=None):
     per-quadrant lists the compositors will walk.  Determinate or an AssertionError: every (splat, quadrant) either reaches
     alpha >= 2/255 at one of the quadrant's 64 pixel positions or has its quadratic form at or above 2 tau2 over the quadrant's
     box (quadrant_mask accepts up to 1.001 tau2 + 1e-3 + 8e-6 mag); a splat in no quadrant list must clear the whole tile's box
-    the same way (common.h::tile_reach_det drops it)."""
+    the same way (common.h::tile_reach_det drops it).  Where the table names no quadrant lengths the undetermined entries are
+    counted instead: `slack` per (splat, quadrant), `tile_slack` per splat that neither reaches a quadrant nor clears the tile
+    -- only the latter leave the tile's LIST undetermined."""
     t = Truth(scene, variant(scene, "base")) if t is None else t
     # a scene whose table entry names no lengths (broad splats over many tiles: something always sits between the two cuts)
     # only COUNTS its undetermined entries ("slack"); positions in such a tile's list are then not compared
@@ -641,7 +934,7 @@ def quadrant_lists(scene, t=None, strict=None):
     yy, xx = np.mgrid[0:8, 0:8]
     for tile in range(gx * gy):
         ty, tx = divmod(tile, gx)
-        ids, quads, slack = [], [[], [], [], []], 0
+        ids, quads, slack, tile_slack = [], [[], [], [], []], 0, 0
         for s in t.order:
             x0, y0, x1, y1 = t.rect[s]
             if not (x0 <= tx < x1 and y0 <= ty < y1):
@@ -673,7 +966,8 @@ def quadrant_lists(scene, t=None, strict=None):
                 l, b = tx * 16 - t.px[s], ty * 16 - t.py[s]
                 v = _quad_min_box(A, B, C, l, l + 15, b, b + 15)
                 assert v >= 2.0 * tau2 or not strict, f"{scene.name}: splat {s} sits in the slack of tile {tile}"
-        out[tile] = dict(list=ids, quadrants=quads, slack=int(slack))
+                tile_slack += v < 2.0 * tau2
+        out[tile] = dict(list=ids, quadrants=quads, slack=int(slack), tile_slack=int(tile_slack))
     return out
 
 
@@ -686,7 +980,9 @@ def expected_n_contrib(scene, t, lists):
     tile_of = (np.arange(H)[:, None] // 16 * gx + np.arange(W)[None, :] // 16).reshape(-1)
     for tile, d in lists.items():
         pix = np.nonzero(tile_of == tile)[0]
-        if d["slack"]:
+        # (a masked scene's tile list is determinate wherever every splat either reaches a quadrant or clears the whole tile:
+        # the list positions do not depend on which quadrant lists a splat in a quadrant's slack joins)
+        if d["tile_slack"] if scene.masked else d["slack"]:
             out[pix] = -1   # undetermined list: no position to compare
             continue
         for pos, s in enumerate(d["list"], 1):
