@@ -129,6 +129,11 @@ SIGNATURES = {
     "cgs_sample_snap_terms": (_i, [_i, _vp, _i, _vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
     "cgs_mesh_depth": (_i, [_i, _vp, _i, _vp, _vp, _i, _i, _vp, _vp]),
     "cgs_depth_window_max": (_i, [_i, _i, _i, _i, _vp, _vp, _vp]),
+    # the siblings' arguments up to their outputs, then depth, slack, the outputs (the gate's own counter last), stream
+    "cgs_edge_visibility_depth": (_i, [_i, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _vp, _i, _vp, C.c_double, _vp, _vp]),
+    "cgs_project_points_depth": (_i, [_i, _vp, _i, _vp, _vp, _i, _i, _vp, C.c_double, _vp, _vp, _vp]),
+    "cgs_render_points_depth": (_i, [_i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, C.c_double, C.c_double, _vp, _vp, _vp, _vp, _vp,
+                                     C.c_size_t, _vp]),
     "cgs_point_mask_depth": (_i, [_i, _vp, _i, _vp, _vp, _i, _i, _vp, C.c_double, _vp, _vp, _vp, _vp]),
     # the siblings' arguments up to their outputs, then depth, slack, the outputs, hidden, stream
     "cgs_edge_support_depth": (_i, [_i, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _i, _vp, _vp, C.c_double, _vp, _vp, _vp]),

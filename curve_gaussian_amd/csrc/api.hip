@@ -2069,6 +2069,64 @@ int cgs_ray_wins_depth(int nx, int ny, int nz, const double* lo, const double* s
     return finish("ray_wins_depth", stream_);
 }
 
+// ---- the depth gate on the control-point visibility check and on the drawn views (include/curvegs.h).  Each checks what its
+// sibling checks, in its order, with the slack right after the sizes and the depth pointer among the pointers of the views.
+int cgs_edge_visibility_depth(int n_curves, const double* curves, int n_lines, const double* lines, int n_frames,
+                              const double* K, const double* w2c, int height, int width, const unsigned char* maps,
+                              int invert, const float* depth, double slack, int32_t* counts_out, void* stream_) {
+    if (n_curves < 0 || n_lines < 0 || n_frames < 0 || (long long)n_curves + n_lines > (1 << 30))
+        return reject("cgs_edge_visibility_depth: invalid argument (n_curves=%d, n_lines=%d, n_frames=%d)", n_curves, n_lines,
+                      n_frames);
+    if (!slack_ok(slack))
+        return reject("cgs_edge_visibility_depth: invalid argument (slack=%g; the slack is finite and >= 0)", slack);
+    if (n_curves + n_lines == 0) return CGS_OK;
+    if (n_frames > 0 && (height <= 0 || width <= 0))
+        return reject("cgs_edge_visibility_depth: invalid argument (height=%d, width=%d)", height, width);
+    if ((n_curves > 0 && !curves) || (n_lines > 0 && !lines) || !counts_out ||
+        (n_frames > 0 && (!K || !w2c || !maps || !depth)))
+        return reject("cgs_edge_visibility_depth: invalid argument (NULL pointer)");
+    launch_edge_visibility_depth((hipStream_t)stream_, n_curves, curves, n_lines, lines, n_frames, K, w2c, height, width,
+                                 maps, invert, depth, slack, counts_out);
+    return finish("edge_visibility_depth", stream_);
+}
+
+int cgs_project_points_depth(int P, const float* points, int V, const double* intr, const double* w2c, int height, int width,
+                             const float* depth, double slack, double* uv_out, uint8_t* hidden_out, void* stream_) {
+    if (P < 0 || V < 0 || (long long)P * V > (1LL << 40))
+        return reject("cgs_project_points_depth: invalid argument (P=%d, V=%d)", P, V);
+    if (!slack_ok(slack))
+        return reject("cgs_project_points_depth: invalid argument (slack=%g; the slack is finite and >= 0)", slack);
+    if (P == 0 || V == 0) return CGS_OK;
+    if (height <= 0 || width <= 0)
+        return reject("cgs_project_points_depth: invalid argument (height=%d, width=%d)", height, width);
+    if (!points || !intr || !w2c || !depth || !uv_out)
+        return reject("cgs_project_points_depth: invalid argument (NULL pointer)");
+    launch_project_points_depth((hipStream_t)stream_, P, points, V, intr, w2c, height, width, depth, slack, uv_out,
+                                hidden_out);
+    return finish("project_points_depth", stream_);
+}
+
+int cgs_render_points_depth(int P, const float* points, const float* colors, int V, const double* intr, const double* w2c,
+                            int height, int width, const float* depth, double slack, double alpha, const double* background,
+                            float* out, int* kept, int* hidden, void* workspace, size_t workspace_bytes, void* stream_) {
+    if (P < 0 || V < 0 || height <= 0 || width <= 0 || (long long)height * width > (1LL << 31))
+        return reject("cgs_render_points_depth: invalid argument (P=%d, V=%d, height=%d, width=%d)", P, V, height, width);
+    if (!slack_ok(slack))
+        return reject("cgs_render_points_depth: invalid argument (slack=%g; the slack is finite and >= 0)", slack);
+    if (!(alpha >= 0.0 && alpha <= 1.0))
+        return reject("cgs_render_points_depth: invalid argument (alpha=%g, need 0 <= alpha <= 1)", alpha);
+    if (V == 0) return CGS_OK;
+    if (!intr || !w2c || !depth || !background || !out || !workspace || (P > 0 && (!points || !colors)))
+        return reject("cgs_render_points_depth: invalid argument (NULL pointer)");
+    const int per = render_points_views_per_chunk(P, V, height, width, workspace_bytes);
+    if (per <= 0)
+        return reject("cgs_render_points_depth: invalid argument (workspace of %zu bytes holds no view; one view needs %zu)",
+                      workspace_bytes, render_points_workspace_bytes(P, 1, height, width));
+    launch_render_points_depth((hipStream_t)stream_, P, points, colors, V, intr, w2c, height, width, depth, slack, alpha,
+                               background, out, kept, hidden, workspace, per);
+    return finish("render_points_depth", stream_);
+}
+
 // ---- occluding contours of a mesh (include/curvegs.h).  The slack is checked only with a plane: without one it is not read.
 int cgs_mesh_contours(int E, const float* edges, int V, const double* intr, const double* w2c, int height, int width,
                       const float* depth, double slack, uint8_t* mask_out, void* stream_) {

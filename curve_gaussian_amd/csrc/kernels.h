@@ -155,6 +155,9 @@ void launch_nn1(hipStream_t s, int n_query, const float* query, int n_ref, const
 void launch_edge_visibility(hipStream_t s, int n_curves, const double* curves, int n_lines, const double* lines,
                             int n_frames, const double* K, const double* w2c, int height, int width,
                             const unsigned char* maps, int invert, int* counts);
+void launch_edge_visibility_depth(hipStream_t s, int n_curves, const double* curves, int n_lines, const double* lines,
+                                  int n_frames, const double* K, const double* w2c, int height, int width,
+                                  const unsigned char* maps, int invert, const float* depth, double slack, int* counts);
 
 // metrics.hip
 size_t view_metrics_workspace_bytes(int n_views);
@@ -175,6 +178,11 @@ int render_points_keep(double alpha);
 void launch_render_points(hipStream_t s, int P, const float* points, const float* colors, int V, const double* intr,
                           const double* w2c, int height, int width, double alpha, const double* bg, float* out,
                           int* kept, void* ws, int views_per_chunk);
+void launch_project_points_depth(hipStream_t s, int P, const float* points, int V, const double* intr, const double* w2c,
+                                 int height, int width, const float* depth, double slack, double* uv, uint8_t* hidden_out);
+void launch_render_points_depth(hipStream_t s, int P, const float* points, const float* colors, int V, const double* intr,
+                                const double* w2c, int height, int width, const float* depth, double slack, double alpha,
+                                const double* bg, float* out, int* kept, int* hidden, void* ws, int views_per_chunk);
 
 // mesh.hip
 void launch_ellipsoid_vertices(hipStream_t s, int first, int count, const float* xyz, const float* rot, const float* scale,

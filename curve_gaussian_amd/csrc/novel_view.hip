@@ -39,20 +39,34 @@ constexpr int NV_MAX_VIEWS = 65535;            // views per launch: grid.y
 
 // NvCam, nv_load_cam, nv_project: point_projection.h (shared with edge_score.hip)
 
-// uv[v][i] = (u, v) of a kept point, (NaN, NaN) for a dropped one.
+// The depth gate (include/curvegs.h, cgs_project_points_depth / cgs_render_points_depth): k_nv_project and k_nv_bin are
+// templates over GATED and take what a view says of a point from nv_verdict<GATED> (point_projection.h).  false is the
+// projection as it always was: depth, slack and the hidden outputs are not touched.  true drops a point that the view's
+// depth plane hides, as a point outside the image is dropped; the count pass and the fill pass call the same function on
+// the same data, so they reach the same verdict and the lists are exactly as long as their counts.
+
+// uv[v][i] = (u, v) of a kept point, (NaN, NaN) for a dropped one.  GATED: a hidden point is dropped too, and
+// hidden_out[v][i] (optional) = 1 iff the projection kept the point and the gate hid it.
+template <bool GATED>
 __global__ void __launch_bounds__(NV_BLOCK) k_nv_project(int P, const float* __restrict__ pts,
                                                         const double* __restrict__ intr, const double* __restrict__ w2c,
-                                                        int height, int width, double* __restrict__ uv) {
+                                                        int height, int width, double* __restrict__ uv,
+                                                        const float* __restrict__ depth, double slack,
+                                                        uint8_t* __restrict__ hidden_out) {
     const int view = blockIdx.y;
     NvCam c;
     nv_load_cam(c, intr, w2c, view);
     const double wd = (double)width, hd = (double)height;
+    const float* __restrict__ dplane = GATED ? depth + (size_t)view * (size_t)height * (size_t)width : nullptr;
     for (long long i = (long long)blockIdx.x * NV_BLOCK + threadIdx.x; i < P; i += (long long)gridDim.x * NV_BLOCK) {
         double u, v;
-        const bool keep = nv_project(c, pts, i, wd, hd, u, v);
+        const NvVerdict verdict = nv_verdict<GATED>(c, (double)pts[3 * i + 0], (double)pts[3 * i + 1], (double)pts[3 * i + 2],
+                                                    wd, hd, dplane, width, slack, u, v);
+        const bool keep = verdict == NV_VISIBLE;
         double* o = uv + 2 * ((size_t)view * (size_t)P + (size_t)i);
         o[0] = keep ? u : (double)NAN;
         o[1] = keep ? v : (double)NAN;
+        if (GATED && hidden_out) hidden_out[(size_t)view * (size_t)P + (size_t)i] = verdict == NV_HIDDEN ? 1 : 0;
     }
 }
 
@@ -62,21 +76,42 @@ __global__ void __launch_bounds__(NV_BLOCK) k_nv_zero(long long n, unsigned int*
 
 // Pass 1 (fill = 0): counts[pixel] += 1 per kept point.  Pass 3 (fill = 1): list[ends[pixel]++] = i.
 // grid.y = views of the chunk (view v0 + blockIdx.y), pixel index (size_t)blockIdx.y * H * W + y * W + x.
+// GATED: depth [V,H,W] and hidden [V] (optional) belong to ALL views and are indexed by the absolute view v0 + blockIdx.y; a
+// hidden point is in neither pass, and the count pass alone tallies it: a register count per thread, one shuffle
+// reduction per wave (every lane leaves the loop and reaches it) and one integer atomicAdd per wave that has any, as
+// k_point_mask_depth does.
+template <bool GATED>
 __global__ void __launch_bounds__(NV_BLOCK) k_nv_bin(int P, const float* __restrict__ pts, const double* __restrict__ intr,
                                                     const double* __restrict__ w2c, int v0, int height, int width,
                                                     unsigned int* __restrict__ cells, unsigned int* __restrict__ list,
-                                                    int fill) {
+                                                    int fill, const float* __restrict__ depth, double slack,
+                                                    int* __restrict__ hidden) {
+    const int view = v0 + (int)blockIdx.y;
     NvCam c;
-    nv_load_cam(c, intr, w2c, v0 + (int)blockIdx.y);
+    nv_load_cam(c, intr, w2c, view);
     const double wd = (double)width, hd = (double)height;
     const size_t base = (size_t)blockIdx.y * (size_t)height * (size_t)width;
+    const float* __restrict__ dplane = GATED ? depth + (size_t)view * (size_t)height * (size_t)width : nullptr;
+    int h = 0;   // GATED only
     for (long long i = (long long)blockIdx.x * NV_BLOCK + threadIdx.x; i < P; i += (long long)gridDim.x * NV_BLOCK) {
         double u, v;
-        if (!nv_project(c, pts, i, wd, hd, u, v)) continue;
+        const NvVerdict verdict = nv_verdict<GATED>(c, (double)pts[3 * i + 0], (double)pts[3 * i + 1], (double)pts[3 * i + 2],
+                                                    wd, hd, dplane, width, slack, u, v);
+        if (verdict == NV_OUT) continue;
+        if (GATED && verdict == NV_HIDDEN) {
+            h++;
+            continue;
+        }
         // 0 <= u < W, so 0 <= floor(u) <= W - 1 (likewise v): the pixel is inside the view's plane
         const size_t pix = base + (size_t)floor(v) * (size_t)width + (size_t)floor(u);
         const unsigned int slot = atomicAdd(&cells[pix], 1u);
         if (fill) list[slot] = (unsigned int)i;
+    }
+    if constexpr (GATED) {
+        if (fill || !hidden) return;   // (uniform over the grid)
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) h += __shfl_xor(h, off, 64);
+        if ((threadIdx.x & 63) == 0 && h) atomicAdd(&hidden[view], h);
     }
 }
 
@@ -238,21 +273,40 @@ int render_points_keep(double alpha) {
 
 static int nv_point_blocks(int P) { return std::max(1, std::min(NV_POINT_BLOCKS_MAX, (P + NV_BLOCK - 1) / NV_BLOCK)); }
 
-void launch_project_points(hipStream_t s, int P, const float* points, int V, const double* intr, const double* w2c,
-                           int height, int width, double* uv) {
-    ProfScope p("project_points", s);
+template <bool GATED>
+static void project_points_launches(hipStream_t s, int P, const float* points, int V, const double* intr, const double* w2c,
+                                    int height, int width, double* uv, const float* depth, double slack,
+                                    uint8_t* hidden_out) {
+    const size_t plane = (size_t)height * (size_t)width;
+    ProfScope p(GATED ? "project_points_depth" : "project_points", s);
     for (int v0 = 0; v0 < V; v0 += NV_MAX_VIEWS) {
         const int nv = std::min(NV_MAX_VIEWS, V - v0);
-        hipLaunchKernelGGL(k_nv_project, dim3(nv_point_blocks(P), nv), dim3(NV_BLOCK), 0, s, P, points, intr + 4 * (size_t)v0,
-                           w2c + 12 * (size_t)v0, height, width, uv + 2 * (size_t)v0 * (size_t)P);
+        hipLaunchKernelGGL(k_nv_project<GATED>, dim3(nv_point_blocks(P), nv), dim3(NV_BLOCK), 0, s, P, points,
+                           intr + 4 * (size_t)v0, w2c + 12 * (size_t)v0, height, width, uv + 2 * (size_t)v0 * (size_t)P,
+                           GATED ? depth + (size_t)v0 * plane : nullptr, slack,
+                           GATED && hidden_out ? hidden_out + (size_t)v0 * (size_t)P : nullptr);
     }
 }
 
-void launch_render_points(hipStream_t s, int P, const float* points, const float* colors, int V, const double* intr,
-                          const double* w2c, int height, int width, double alpha, const double* bg, float* out,
-                          int* kept, void* ws, int views_per_chunk) {
+void launch_project_points(hipStream_t s, int P, const float* points, int V, const double* intr, const double* w2c,
+                           int height, int width, double* uv) {
+    project_points_launches<false>(s, P, points, V, intr, w2c, height, width, uv, nullptr, 0.0, nullptr);
+}
+
+void launch_project_points_depth(hipStream_t s, int P, const float* points, int V, const double* intr, const double* w2c,
+                                 int height, int width, const float* depth, double slack, double* uv, uint8_t* hidden_out) {
+    project_points_launches<true>(s, P, points, V, intr, w2c, height, width, uv, depth, slack, hidden_out);
+}
+
+template <bool GATED>
+static void render_points_launches(hipStream_t s, int P, const float* points, const float* colors, int V, const double* intr,
+                                   const double* w2c, int height, int width, double alpha, const double* bg, float* out,
+                                   int* kept, void* ws, int views_per_chunk, const float* depth, double slack, int* hidden) {
     const long long plane = (long long)height * width;
     const int keep_max = render_points_keep(alpha);
+    if (GATED && hidden)   // cleared by a kernel: a captured memset node clears once (zero_async in api.hip)
+        hipLaunchKernelGGL(k_nv_zero, dim3((V + NV_BLOCK - 1) / NV_BLOCK), dim3(NV_BLOCK), 0, s, (long long)V,
+                           reinterpret_cast<unsigned int*>(hidden));
     for (int v0 = 0; v0 < V; v0 += views_per_chunk) {
         const int nv = std::min(views_per_chunk, V - v0);
         const long long n = (long long)nv * plane;
@@ -271,8 +325,8 @@ void launch_render_points(hipStream_t s, int P, const float* points, const float
             ProfScope p("render_points_count", s);
             hipLaunchKernelGGL(k_nv_zero, dim3(zblocks), dim3(NV_BLOCK), 0, s, n, counts);
             if (P > 0)
-                hipLaunchKernelGGL(k_nv_bin, dim3(nv_point_blocks(P), nv), dim3(NV_BLOCK), 0, s, P, points, intr, w2c,
-                                   v0, height, width, counts, (unsigned int*)nullptr, 0);
+                hipLaunchKernelGGL(k_nv_bin<GATED>, dim3(nv_point_blocks(P), nv), dim3(NV_BLOCK), 0, s, P, points, intr, w2c,
+                                   v0, height, width, counts, (unsigned int*)nullptr, 0, depth, slack, hidden);
         }
         {
             ProfScope p("render_points_scan", s);
@@ -285,8 +339,8 @@ void launch_render_points(hipStream_t s, int P, const float* points, const float
         }
         if (P > 0) {
             ProfScope p("render_points_fill", s);
-            hipLaunchKernelGGL(k_nv_bin, dim3(nv_point_blocks(P), nv), dim3(NV_BLOCK), 0, s, P, points, intr, w2c, v0,
-                               height, width, offsets, list, 1);
+            hipLaunchKernelGGL(k_nv_bin<GATED>, dim3(nv_point_blocks(P), nv), dim3(NV_BLOCK), 0, s, P, points, intr, w2c, v0,
+                               height, width, offsets, list, 1, depth, slack, hidden);
         }
         {
             ProfScope p("render_points_composite", s);
@@ -294,6 +348,21 @@ void launch_render_points(hipStream_t s, int P, const float* points, const float
                                alpha, keep_max, bg[0], bg[1], bg[2], out + 3 * (size_t)v0 * (size_t)plane);
         }
     }
+}
+
+void launch_render_points(hipStream_t s, int P, const float* points, const float* colors, int V, const double* intr,
+                          const double* w2c, int height, int width, double alpha, const double* bg, float* out,
+                          int* kept, void* ws, int views_per_chunk) {
+    render_points_launches<false>(s, P, points, colors, V, intr, w2c, height, width, alpha, bg, out, kept, ws,
+                                  views_per_chunk, nullptr, 0.0, nullptr);
+}
+
+// The lists of the gated form can only be shorter: the workspace of cgs_render_points holds them.
+void launch_render_points_depth(hipStream_t s, int P, const float* points, const float* colors, int V, const double* intr,
+                                const double* w2c, int height, int width, const float* depth, double slack, double alpha,
+                                const double* bg, float* out, int* kept, int* hidden, void* ws, int views_per_chunk) {
+    render_points_launches<true>(s, P, points, colors, V, intr, w2c, height, width, alpha, bg, out, kept, ws,
+                                 views_per_chunk, depth, slack, hidden);
 }
 
 }  // namespace cgs

@@ -6,7 +6,14 @@ projected into every camera of a scan and drawn one pixel per point, one image p
 no CPU path: CPU tensors raise).  The camera loaders and the per-edge colours are host-side float64 numpy, computed as
 the reference computes them.  Deviations: the output is the camera's pixel grid (a kept point covers pixel
 (floor(u), floor(v)), alpha-composited in point order) rather than a matplotlib figure; the colour permutation is seeded;
-SIMPLE_PINHOLE cameras are read as (f, f, cx, cy)."""
+SIMPLE_PINHOLE cameras are read as (f, f, cx, cy).
+
+The depth gate (opt-in; ``ops.edge_occlusion``): ``project_points_depth`` and ``render_points_depth`` drop a
+point that its view's depth plane hides (``cgs_project_points_depth`` / ``cgs_render_points_depth``, the occlusion rule
+``nv_hidden`` of the 2D score), ``render_views(depth=)`` takes a scan's ``ChunkDepth``, and the two scan drivers take
+``occluder`` / ``depth_dir`` and then write to ``novel_view_visible/`` beside ``novel_view/``: the picture a user looks at is
+the one the depth-gated score was computed on.  Hidden means dropped -- nothing is drawn dashed or dimmed.  UNTUNED: only the
+drawn solids of scene/solid_scan.py have been checked, no real scan."""
 import colorsys
 import json
 import logging
@@ -20,6 +27,8 @@ import numpy as np
 import torch
 
 from .. import _lib as L
+from ..ops import edge_occlusion as EO
+from ..ops import edge_score as ES
 from ..ops.edge_score import _cameras, cameras_on
 from ..ops.view_chunks import camera_arrays, view_chunks
 from ..scene import colmap_io
@@ -34,6 +43,7 @@ REPLICA_SAMPLE_RESOLUTION = 0.0005  # eval_replica.py:113
 WORKSPACE_BUDGET = 1 << 30          # bytes of kernel scratch per render_points call (views are chunked to fit)
 OUTPUT_BUDGET = 1 << 30             # bytes of float32 images per driver batch
 MAX_WRITERS = 16                    # image-encoding threads
+VISIBLE_DIR = "novel_view_visible"  # where the scan drivers write with a depth source (novel_view/ is never touched)
 
 
 class NovelViewCamera(NamedTuple):
@@ -204,6 +214,96 @@ def render_points(points, colors, intrinsics, w2c, height, width, alpha=ALPHA, b
     return (out, kept) if return_kept else out
 
 
+def _depth_planes(what, depth, V):
+    """``depth`` as a float32 [V,H,W] tensor (where it is) and its (H, W)."""
+    d = depth if torch.is_tensor(depth) else torch.from_numpy(np.array(depth, order="C"))   # (a copy: may be read-only)
+    if d.dim() != 3:
+        raise ValueError(f"{what}: depth must be float32 [V,H,W] (got {tuple(d.shape)})")
+    H, W = int(d.shape[1]), int(d.shape[2])
+    return EO._as_depth(d, V, H, W, what), H, W
+
+
+def project_points_depth(points, intrinsics, w2c, depth, slack=EO.DEPTH_SLACK, return_hidden=False, backend="gpu",
+                         device=None):
+    """``project_points`` with the depth gate: float64 [V,P,2], NaN for a dropped point -- behind the camera, outside the
+    image (``depth``'s size), or HIDDEN: c2 > float64(depth[v][floor(v_px)][floor(u_px)]) + slack (``nv_hidden``).  depth:
+    float32 [V,H,W], camera z, +inf where there is no surface.  With return_hidden, also uint8 [V,P]: 1 iff the projection
+    kept the point and the gate hid it.  ``backend="gpu"``: ``cgs_project_points_depth``; points and planes are uploaded when
+    they are not on a GPU, the results stay on the device.  ``"host"``: ``ops.edge_occlusion.gate_view_host`` per view, CPU
+    tensors; the two agree bit for bit."""
+    ES._check_backend(backend)
+    what = "project_points_depth"
+    slack = EO._check_slack(what, slack)
+    V, K, M = _cameras(intrinsics, w2c)
+    d, H, W = _depth_planes(what, depth, V)
+    pts = points if torch.is_tensor(points) else torch.from_numpy(np.ascontiguousarray(points, np.float32).reshape(-1, 3))
+    if pts.dim() != 2 or pts.shape[1] != 3:
+        raise ValueError(f"points must be [P,3] (got {tuple(pts.shape)})")
+    pts = pts.detach().to(torch.float32)
+    P = int(pts.shape[0])
+    if backend == "host":
+        uv = np.full((V, P, 2), np.nan, np.float64)
+        hidden = np.zeros((V, P), np.uint8)
+        host_pts, planes = ES._host(pts), ES._host(d)
+        for i in range(V):
+            u, v, seen, hid = EO.gate_view_host(host_pts, K[i], M[i], planes[i], slack)
+            uv[i, seen, 0], uv[i, seen, 1] = u[seen], v[seen]
+            hidden[i] = hid
+        uv, hidden = torch.from_numpy(uv), torch.from_numpy(hidden)
+        return (uv, hidden) if return_hidden else uv
+    dev = ES._device_for([pts, d], what, device)
+    with L.device_guard(dev):
+        pts, d = pts.to(dev).contiguous(), d.to(dev)
+        Kd, Md = cameras_on(dev, K, M)
+        uv = torch.empty((V, P, 2), dtype=torch.float64, device=dev)
+        hidden = torch.empty((V, P), dtype=torch.uint8, device=dev) if return_hidden else None
+        if V > 0 and P > 0:
+            rc = L.load().cgs_project_points_depth(P, L.ptr(pts), V, L.ptr(Kd), L.ptr(Md), H, W, L.ptr(d), slack, L.ptr(uv),
+                                                   L.ptr(hidden) if return_hidden else None, L.raw_stream(dev))
+            L.check(rc, "cgs_project_points_depth")
+    return (uv, hidden) if return_hidden else uv
+
+
+def render_points_depth(points, colors, intrinsics, w2c, depth, slack=EO.DEPTH_SLACK, alpha=ALPHA, background=BACKGROUND,
+                        workspace_bytes=None, return_counts=False):
+    """``render_points`` with the depth gate (``cgs_render_points_depth``; GPU only, like ``render_points``): float32
+    [V,H,W,3] images, (H, W) the size of ``depth`` (float32 [V,H,W], camera z, +inf where there is no surface; uploaded when
+    it is not on the points' device).  A point that its view hides -- ``project_points_depth``'s rule -- is dropped: it is in
+    no pixel.  With return_counts, also (kept, hidden) int32 [V]: the drawn points and the hidden ones; kept + hidden is
+    ``render_points``'s kept.  The result does not depend on ``workspace_bytes``."""
+    what = "render_points_depth"
+    pts = _points(points)
+    col = _points(colors, "colors")
+    dev = pts.device
+    if col.device != dev or col.shape[0] != pts.shape[0]:
+        raise L.CurveGSError(f"colors must be [P,3] on {dev} (got {tuple(col.shape)} on {col.device})")
+    slack = EO._check_slack(what, slack)
+    bg = np.ascontiguousarray(np.asarray(background, np.float64).reshape(3))
+    lib = L.load()
+    V, K, M = _cameras(intrinsics, w2c, L.CurveGSError)
+    d, H, W = _depth_planes(what, depth, V)
+    if d.is_cuda and d.device != dev:
+        raise L.CurveGSError(f"{what}: depth is on {d.device}, the points on {dev}: all tensors must be on one device")
+    with L.device_guard(dev):
+        K, M = cameras_on(dev, K, M)
+        d = d.to(dev)
+        P = pts.shape[0]
+        out = torch.empty((V, H, W, 3), dtype=torch.float32, device=dev)
+        kept = torch.zeros((V,), dtype=torch.int32, device=dev)
+        hidden = torch.zeros((V,), dtype=torch.int32, device=dev)
+        if V > 0:
+            need = lib.cgs_render_points_workspace_bytes(P, V, H, W)
+            one = lib.cgs_render_points_workspace_bytes(P, 1, H, W)
+            budget = WORKSPACE_BUDGET if workspace_bytes is None else int(workspace_bytes)
+            nbytes = max(min(need, budget), one)
+            ws = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=dev)
+            rc = lib.cgs_render_points_depth(P, L.ptr(pts), L.ptr(col), V, L.ptr(K), L.ptr(M), H, W, L.ptr(d), slack,
+                                             float(alpha), bg.ctypes.data_as(L.C.c_void_p), L.ptr(out), L.ptr(kept),
+                                             L.ptr(hidden), L.ptr(ws), nbytes, L.raw_stream(dev))
+            L.check(rc, "cgs_render_points_depth")
+    return (out, kept, hidden) if return_counts else out
+
+
 # ------------------------------------------------------------------------------------------------ drivers
 def _write_images(jobs, pool):
     """jobs: (path, uint8 [H,W,3]); PIL picks the format from the extension, as savefig does."""
@@ -215,20 +315,33 @@ def _write_images(jobs, pool):
     list(pool.map(one, jobs))
 
 
-def render_views(points, colors, cams, out_dir, file_names, device=None, alpha=ALPHA, background=BACKGROUND):
+def render_views(points, colors, cams, out_dir, file_names, device=None, alpha=ALPHA, background=BACKGROUND, depth=None):
     """Renders `points` into every camera and writes <out_dir>/<file_names[v]> for each view with at least one kept
     point (the reference saves nothing for an empty view): round(255 * image) as uint8 RGB.  Views of one size are
     rendered together, OUTPUT_BUDGET bytes of images at a time.  Returns {"views", "written", "gpu_s", "write_s"}: the
-    GPU time (render, conversion and copy to the host, synchronised) and the encoding time, in seconds."""
+    GPU time (render, conversion and copy to the host, synchronised) and the encoding time, in seconds.  ``depth``: None, or
+    the scan's ``ops.edge_occlusion.ChunkDepth`` (built for `cams`): every chunk's planes are built on the GPU, a point its
+    view hides is not drawn (``render_points_depth``), the budget of a chunk counts the planes' bytes per pixel beside the
+    image's, and the stats gain "hidden", the hidden (point, view) pairs."""
     dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
     pts = torch.from_numpy(np.ascontiguousarray(points, np.float32).reshape(-1, 3)).to(dev)
     col = torch.from_numpy(np.ascontiguousarray(colors, np.float32).reshape(-1, 3)).to(dev)
     stats = {"views": len(cams), "written": 0, "gpu_s": 0.0, "write_s": 0.0}
+    gated = depth is not None and depth.gated
+    if gated:
+        depth.to("gpu", dev)
+        stats["hidden"] = 0
     os.makedirs(out_dir, exist_ok=True)
     with ThreadPoolExecutor(max_workers=MAX_WRITERS) as pool:
-        for H, W, sel, intr, w2c in view_chunks(cams, 12, OUTPUT_BUDGET):   # 12 bytes: a float32 RGB pixel
+        # 12 bytes: a float32 RGB pixel
+        for H, W, sel, intr, w2c in view_chunks(cams, 12 + (depth.bytes_per_pixel if gated else 0), OUTPUT_BUDGET):
             t0 = time.perf_counter()
-            img, kept = render_points(pts, col, intr, w2c, H, W, alpha, background, return_kept=True)
+            if gated:
+                img, kept, hid = render_points_depth(pts, col, intr, w2c, depth.planes(H, W, sel, intr, w2c), depth.slack,
+                                                     alpha, background, return_counts=True)
+                stats["hidden"] += int(hid.sum().item())
+            else:
+                img, kept = render_points(pts, col, intr, w2c, H, W, alpha, background, return_kept=True)
             u8 = torch.round(img * 255.0).clamp_(0, 255).to(torch.uint8).cpu().numpy()
             kept = kept.cpu().numpy()
             t1 = time.perf_counter()
@@ -253,11 +366,33 @@ def _scan_points(base_dir, scan, sample_resolution, seed):
     return pts, edge_point_colors(pred, seed)
 
 
-def render_abc_novel_views(base_dir, dataset_dir, detector="DexiNed", seed=0, device=None):
+def scan_depth(what, scan_dir, cams, occluder=None, depth_dir=None, depth_slack=EO.DEPTH_SLACK,
+               depth_window=EO.DEPTH_WINDOW, near_clip=None):
+    """The ``ChunkDepth`` of one scan for the scan drivers, or None without a depth source.  ``occluder``: the name of a mesh
+    file inside the scan directory (``mesh.ply``); ``depth_dir``: the name of a directory inside it holding one
+    ``<image stem>.npy`` depth map per camera (``reprojection.scan_depth_maps``), as the score takes them.  Both together, and
+    ``near_clip`` without an occluder, are ValueErrors."""
+    if occluder is not None and depth_dir is not None:
+        raise ValueError(f"{what}: give an occluder or a depth_dir, not both")
+    if near_clip is not None and occluder is None:
+        raise ValueError(f"{what}: near_clip needs an occluder (depth maps need no clipping)")
+    if occluder is not None:
+        return EO.ChunkDepth(what, cams, os.path.join(scan_dir, occluder), None, depth_slack, depth_window, near_clip)
+    if depth_dir is not None:
+        from .reprojection import scan_depth_maps   # (reprojection imports this module)
+        return EO.ChunkDepth(what, cams, None, scan_depth_maps(os.path.join(scan_dir, depth_dir), cams), depth_slack,
+                             depth_window)
+    return None
+
+
+def render_abc_novel_views(base_dir, dataset_dir, detector="DexiNed", seed=0, device=None, occluder=None, depth_dir=None,
+                           depth_slack=EO.DEPTH_SLACK, depth_window=EO.DEPTH_WINDOW, near_clip=None):
     """eval_ABC.py main with --render_mv (:180-185): for every scan directory of `dataset_dir` (sorted) with a
     <base_dir>/<scan>/parametric_edges.json, the edges sampled every 0.005 are drawn into every camera of
     <dataset_dir>/<scan>/transforms_video.json and written to <base_dir>/<scan>/novel_view/<frame stem>.png.
-    Returns {scan: stats of render_views}."""
+    Returns {scan: stats of render_views}.  With ``occluder`` or ``depth_dir`` (``scan_depth``; ``depth_slack``,
+    ``depth_window``, ``near_clip`` as ``score_edges``) the hidden samples are not drawn and the images go to
+    <base_dir>/<scan>/novel_view_visible/ instead: novel_view/ is never touched, so the two sit side by side."""
     out = {}
     for scan in sorted(f.name for f in os.scandir(dataset_dir) if f.is_dir()):
         log.info(f"Processing: {scan}")
@@ -265,8 +400,10 @@ def render_abc_novel_views(base_dir, dataset_dir, detector="DexiNed", seed=0, de
         if got is None:
             continue
         cams = transforms_video_cameras(os.path.join(dataset_dir, scan), detector)
-        out[scan] = render_views(*got, cams, os.path.join(base_dir, scan, "novel_view"),
-                                 [c.name + ".png" for c in cams], device)
+        depth = scan_depth("render_abc_novel_views", os.path.join(dataset_dir, scan), cams, occluder, depth_dir, depth_slack,
+                           depth_window, near_clip)
+        out[scan] = render_views(*got, cams, os.path.join(base_dir, scan, "novel_view" if depth is None else VISIBLE_DIR),
+                                 [c.name + ".png" for c in cams], device, depth=depth)
     return out
 
 
@@ -280,11 +417,13 @@ def replica_scans(dataset_dir, scans_file=None):
                   if f.is_dir() and os.path.isdir(os.path.join(f.path, "sparse", "0")))
 
 
-def render_replica_novel_views(base_dir, dataset_dir, scans=None, seed=0, device=None):
+def render_replica_novel_views(base_dir, dataset_dir, scans=None, seed=0, device=None, occluder=None, depth_dir=None,
+                               depth_slack=EO.DEPTH_SLACK, depth_window=EO.DEPTH_WINDOW, near_clip=None):
     """eval_replica.py process_scan (:100-212) for every scan in `scans` (default: replica_scans(dataset_dir)): the edges
     sampled every 0.0005 are drawn into every COLMAP camera of <dataset_dir>/<scan>/sparse/0 and written to
     <base_dir>/<scan>/novel_view/<image name> (format from the extension).  The comparison video is not made.
-    Returns {scan: stats of render_views}."""
+    Returns {scan: stats of render_views}.  The depth arguments as ``render_abc_novel_views``: with a depth source the
+    images go to <base_dir>/<scan>/novel_view_visible/."""
     out = {}
     for scan in (replica_scans(dataset_dir) if scans is None else scans):
         print(f"Processing: {scan}")
@@ -292,5 +431,8 @@ def render_replica_novel_views(base_dir, dataset_dir, scans=None, seed=0, device
         if got is None:
             continue
         cams = colmap_cameras(os.path.join(dataset_dir, scan))
-        out[scan] = render_views(*got, cams, os.path.join(base_dir, scan, "novel_view"), [c.name for c in cams], device)
+        depth = scan_depth("render_replica_novel_views", os.path.join(dataset_dir, scan), cams, occluder, depth_dir,
+                           depth_slack, depth_window, near_clip)
+        out[scan] = render_views(*got, cams, os.path.join(base_dir, scan, "novel_view" if depth is None else VISIBLE_DIR),
+                                 [c.name for c in cams], device, depth=depth)
     return out

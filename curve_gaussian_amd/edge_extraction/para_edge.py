@@ -3,7 +3,14 @@ reference): which fitted curves and lines the 2D edge detector actually saw.
 
 ``get_edge_maps`` reads a scan's edge maps on the host as raw 8-bit values; ``compute_visibility`` counts, in the HIP
 kernel ``cgs_edge_visibility``, the frames in which every edge is seen and applies the reference's thresholds;
-``get_parametric_edge`` is the reference's entry point of the same name, with its signature and return value."""
+``get_parametric_edge`` is the reference's entry point of the same name, with its signature and return value.
+
+The depth gate (opt-in; ``ops.edge_occlusion``): ``edge_visibility_counts_depth`` / ``compute_visibility_depth``
+drop a control or end point that a frame's depth plane hides before the frame's cell is formed (``cgs_edge_visibility_depth``,
+or numpy written operation for operation with ``backend="host"``: the two agree bit for bit), ``scan_visibility_counts_depth``
+builds a scan's planes a chunk of frames at a time, and ``get_parametric_edge`` takes ``occluder`` / ``depth_maps``.  Without
+them nothing changes.  ``DEPTH_WINDOW`` AND ``DEPTH_SLACK`` ARE UNTUNED: only the drawn solids of scene/solid_scan.py have
+been checked, no real scan."""
 import json
 import math
 import os
@@ -12,12 +19,17 @@ import numpy as np
 import torch
 
 from .. import _lib as L
+from ..ops import edge_occlusion as EO
+from ..ops import edge_score as ES
+from ..ops.view_chunks import check_budget, view_chunks
 from ..scene.dataset_io import DETECTOR_DIRS, sample_edge_points
 
 # The reference's hard-coded thresholds (extract_para_edge.py:189-192, 212-214)
 EDGE_VISIBILITY_THRESHOLD = 0.1      # mean of the edge-map values at the projected points
 EDGE_MAX_THRESHOLD = 0.5             # max of the same values
 EDGE_VISIBILITY_FRAMES_RATIO = 0.05  # an edge is kept if seen in more than ceil(0.05 * frames) frames
+
+VISIBILITY_BYTE_BUDGET = 1 << 30     # bytes of maps and depth planes per chunk of frames of the gated check
 
 # Image modes converted to 8-bit grayscale when a map is not already one (see get_edge_maps)
 _CONVERTIBLE_MODES = ("1", "P", "LA", "RGB", "RGBA")
@@ -140,23 +152,207 @@ def compute_visibility(curves, lines, maps_u8, intrinsics, camtoworld, detector)
     return keep[:nc], keep[nc:]
 
 
+# ------------------------------------------------------------------------------------------------ the depth gate
+def _invert_of(detector):
+    if detector == "DexiNed":
+        return 1
+    if detector == "PidiNet":
+        return 0
+    raise ValueError(f"Unknown detector: {detector}")
+
+
+def _frame_cells_host(pts, valid, K, M, emap, invert, plane, slack):
+    """One frame of ``cgs_edge_visibility_depth`` in numpy, operation for operation: (visible bool [E], touched bool [E]).
+    pts float64 [E,4,3] (a line's slots 2 and 3 are not ``valid``); K [3,3], M [3,4]; emap uint8 [H,W]; plane float32 [H,W]."""
+    H, W = emap.shape
+    X, Y, Z = pts[..., 0], pts[..., 1], pts[..., 2]
+    with np.errstate(all="ignore"):
+        c0 = ((M[0, 0] * X + M[0, 1] * Y) + M[0, 2] * Z) + M[0, 3]
+        c1 = ((M[1, 0] * X + M[1, 1] * Y) + M[1, 2] * Z) + M[1, 3]
+        c2 = ((M[2, 0] * X + M[2, 1] * Y) + M[2, 2] * Z) + M[2, 3]
+        x0 = (K[0, 0] * c0 + K[0, 1] * c1) + K[0, 2] * c2
+        x1 = (K[1, 0] * c0 + K[1, 1] * c1) + K[1, 2] * c2
+        x2 = (K[2, 0] * c0 + K[2, 1] * c1) + K[2, 2] * c2
+        ur, vr = x0 / x2, x1 / x2
+        u, v = np.rint(ur), np.rint(vr)
+        keep = valid & (u >= 0.0) & (u < float(W)) & (v >= 0.0) & (v < float(H))   # NaN and +-inf fail
+        gate = keep & (ur >= 0.0) & (vr >= 0.0)   # a point kept by rounding from [-0.5, 0) has no plane pixel
+    hid = EO.hidden_host(c2.ravel(), ur.ravel(), vr.ravel(), gate.ravel(), plane, slack).reshape(keep.shape)
+    vis = keep & ~hid
+    raw = np.zeros(keep.shape, np.float64)
+    raw[vis] = emap[v[vis].astype(np.int64), u[vis].astype(np.int64)] / 255.0
+    val = np.where(vis, 1.0 - raw if invert else raw, 0.0)   # x + 0.0 == x: a dropped point adds nothing
+    total = ((val[:, 0] + val[:, 1]) + val[:, 2]) + val[:, 3]
+    nv = vis.sum(1)
+    mx = np.where(vis, val, -np.inf).max(1)
+    with np.errstate(all="ignore"):
+        cell = (nv > 0) & (total / nv > EDGE_VISIBILITY_THRESHOLD) & (mx > EDGE_MAX_THRESHOLD)
+    return cell, hid.any(1)
+
+
+def edge_visibility_counts_depth(curves, lines, maps_u8, intrinsics, camtoworld, detector, depth, slack=EO.DEPTH_SLACK,
+                                 backend="gpu", device=None):
+    """``edge_visibility_counts`` with the depth gate: int32 [Nc + Nl, 2] -- [:, 0] the frames in which the edge is seen,
+    [:, 1] the frames in which the gate dropped at least one of its points.  ``depth``: float32 [F,H,W], camera z per frame,
+    +inf where there is no surface; a control or end point that the check keeps (its ROUNDED pixel is in the image) is dropped,
+    exactly as an out-of-image point is, iff its raw coordinates (u, v) = (x0 / x2, x1 / x2) are >= 0 and its camera depth c2
+    (the third row of w2c X) has c2 > float64(depth[f][floor(v)][floor(u)]) + slack (``nv_hidden``).  The edge map is still
+    read at the rounded pixel.  With an all-+inf depth [:, 0] is ``edge_visibility_counts`` and [:, 1] is 0.
+    ``backend="gpu"``: ``cgs_edge_visibility_depth``; arrays and CPU tensors are uploaded, the result stays on the device.
+    ``"host"``: numpy written operation for operation, a CPU tensor; the two agree bit for bit."""
+    ES._check_backend(backend)
+    invert = _invert_of(detector)
+    maps = maps_u8 if torch.is_tensor(maps_u8) else torch.from_numpy(np.ascontiguousarray(maps_u8))
+    if maps.dtype != torch.uint8 or maps.dim() != 3:
+        raise ValueError(f"maps_u8 must be uint8 [F,H,W] (got {maps.dtype} {tuple(maps.shape)})")
+    F, H, W = (int(s) for s in maps.shape)
+    K = _host64(intrinsics)
+    c2w = _host64(camtoworld)
+    if K.ndim != 3 or c2w.ndim != 3 or K.shape[0] != F or c2w.shape[0] != F or K.shape[1] < 3 or K.shape[2] < 3 \
+            or c2w.shape[1:] != (4, 4):
+        raise ValueError(f"intrinsics / camtoworld must be [F,3+,3+] / [F,4,4] with F = {F} (got {K.shape}, {c2w.shape})")
+    K = np.ascontiguousarray(K[:, :3, :3])
+    w2c = np.stack([np.linalg.inv(c2w[f])[:3, :4] for f in range(F)]) if F else np.zeros((0, 3, 4))
+    c = torch.as_tensor(curves).detach().to(torch.float64).reshape(-1, 12)
+    ln = torch.as_tensor(lines).detach().to(torch.float64).reshape(-1, 6)
+    nc, nl = int(c.shape[0]), int(ln.shape[0])
+    what = "edge_visibility_counts_depth"
+    if backend == "host":
+        d, slack = EO.operator_depth(what, depth, slack, F, H, W, "host")
+        pts = np.zeros((nc + nl, 4, 3), np.float64)
+        pts[:nc] = ES._host(c).reshape(nc, 4, 3)
+        pts[nc:, :2] = ES._host(ln).reshape(nl, 2, 3)
+        valid = np.ones((nc + nl, 4), bool)
+        valid[nc:, 2:] = False
+        emaps = ES._host(maps)
+        counts = np.zeros((nc + nl, 2), np.int32)
+        for f in range(F):
+            cell, touched = _frame_cells_host(pts, valid, K[f], w2c[f], emaps[f], invert, d[f], slack)
+            counts[:, 0] += cell
+            counts[:, 1] += touched
+        return torch.from_numpy(counts)
+    dev = ES._device_for([maps, c, ln] + ([depth] if torch.is_tensor(depth) else []), what, device)
+    d, slack = EO.operator_depth(what, depth, slack, F, H, W, "gpu", dev)
+    with L.device_guard(dev):
+        c, ln, maps = c.to(dev).contiguous(), ln.to(dev).contiguous(), maps.to(dev).contiguous()
+        counts = torch.zeros((nc + nl, 2), dtype=torch.int32, device=dev)
+        if nc + nl > 0:
+            Kd = torch.from_numpy(K).to(dev)
+            Md = torch.from_numpy(np.ascontiguousarray(w2c)).to(dev)
+            rc = L.load().cgs_edge_visibility_depth(nc, L.ptr(c), nl, L.ptr(ln), F, L.ptr(Kd), L.ptr(Md), H, W, L.ptr(maps),
+                                                    invert, L.ptr(d), slack, L.ptr(counts), L.raw_stream(dev))
+            L.check(rc, "cgs_edge_visibility_depth")
+    return counts
+
+
+def compute_visibility_depth(curves, lines, maps_u8, intrinsics, camtoworld, detector, depth, slack=EO.DEPTH_SLACK,
+                             backend="gpu", device=None, return_counts=False):
+    """``compute_visibility`` with the depth gate, the reference's thresholds unchanged: an edge is kept if it is visible in
+    more than ceil(0.05 * F) frames, a frame's cell being formed from the points that ``depth`` does not hide.  Arguments as
+    ``edge_visibility_counts_depth``.  Returns (curve_mask bool [Nc], line_mask bool [Nl]) and, with return_counts, the
+    int32 [Nc + Nl, 2] counts."""
+    counts = edge_visibility_counts_depth(curves, lines, maps_u8, intrinsics, camtoworld, detector, depth, slack, backend,
+                                          device)
+    keep = counts[:, 0] > edge_visibility_frames(int(maps_u8.shape[0]))
+    nc = int(torch.as_tensor(curves).reshape(-1, 12).shape[0])
+    return (keep[:nc], keep[nc:], counts) if return_counts else (keep[:nc], keep[nc:])
+
+
+def check_pinhole_intrinsics(what, intrinsics):
+    """The planes of an occluder are drawn by a pinhole camera (fx, fy, cx, cy) = (K00, K11, K02, K12): ValueError for a K
+    with K01, K10, K20 or K21 nonzero, or K22 != 1, whose image those planes are not in."""
+    for f, K in enumerate(np.asarray(intrinsics, np.float64)):
+        if K[0, 1] != 0.0 or K[1, 0] != 0.0 or K[2, 0] != 0.0 or K[2, 1] != 0.0 or K[2, 2] != 1.0:
+            raise ValueError(f"{what}: the intrinsics of frame {f} are not a pinhole camera's (K01, K10, K20, K21 must be 0 "
+                             f"and K22 1; got {K[:3, :3].tolist()}): an occluder's depth planes are drawn for "
+                             "(fx, fy, cx, cy) only; give depth_maps in this K's image instead")
+
+
+def scan_visibility_counts_depth(curves, lines, scan_dir, detector, occluder=None, depth_maps=None,
+                                 depth_slack=EO.DEPTH_SLACK, depth_window=EO.DEPTH_WINDOW, near_clip=None, backend="gpu",
+                                 device=None, budget_bytes=None):
+    """The gated counts of a whole EMAP scan: (int32 [Nc + Nl, 2] numpy array, the number of frames).  The cameras and maps
+    come from ``reprojection.emap_cameras``, the planes from ``ops.edge_occlusion.ChunkDepth`` over ``view_chunks`` -- a chunk
+    of frames at a time, ``budget_bytes`` (default VISIBILITY_BYTE_BUDGET) of maps and planes -- and the chunks' integer
+    counts are added, so the result does not depend on the chunking.  One of ``occluder`` (triangles or a mesh file's path;
+    the intrinsics must then be a pinhole camera's, ``check_pinhole_intrinsics``) and ``depth_maps`` (one float [H,W] array
+    per frame, in K's image; K is not restricted) is required; ``near_clip`` needs the occluder."""
+    from .reprojection import emap_cameras   # (reprojection imports this module)
+    what = "get_parametric_edge"
+    ES._check_backend(backend)
+    EO.check_one_depth_source(what, occluder, depth_maps)
+    if occluder is None and depth_maps is None:
+        raise ValueError(f"{what}: the gated check needs an occluder or depth_maps")
+    if near_clip is not None and occluder is None:
+        raise ValueError(f"{what}: near_clip needs an occluder (the caller's depth maps need no clipping)")
+    budget = check_budget(what, budget_bytes, VISIBILITY_BYTE_BUDGET)
+    cams, maps = emap_cameras(scan_dir, detector)   # (a scan without frames raises here)
+    meta, _ = edge_map_paths(scan_dir, detector)
+    intrinsics = np.stack([np.array(fr["intrinsics"], np.float64) for fr in meta["frames"]])
+    camtoworld = np.stack([np.array(fr["camtoworld"], np.float64)[:4, :4] for fr in meta["frames"]])
+    if occluder is not None:
+        check_pinhole_intrinsics(what, intrinsics)
+    gate = EO.ChunkDepth(what, cams, occluder, depth_maps, depth_slack, depth_window, near_clip)
+    if backend == "gpu":
+        device = ES._device_for([], what, device)
+    gate.to(backend, device)
+    c = np.asarray(curves, np.float64).reshape(-1, 12)
+    ln = np.asarray(lines, np.float64).reshape(-1, 6)
+    if backend == "gpu":
+        c, ln = torch.from_numpy(c).to(device), torch.from_numpy(ln).to(device)
+    counts = np.zeros((c.shape[0] + ln.shape[0], 2), np.int32)
+    for H, W, sel, intr, w2c in view_chunks(cams, gate.bytes_per_pixel + 1, budget):   # + 1: the map's byte
+        planes = gate.planes(H, W, sel, intr, w2c)
+        counts += edge_visibility_counts_depth(c, ln, maps[sel], intrinsics[sel], camtoworld[sel], detector, planes,
+                                               gate.slack, backend, device).cpu().numpy()
+    return counts, len(cams)
+
+
 def _edge_arrays(edge_dict):
     curves = np.array(edge_dict["curves_ctl_pts"]).reshape(-1, 12).reshape(-1, 4, 3)
     lines = np.array(edge_dict["lines_end_pts"]).reshape(-1, 6)
     return curves, lines
 
 
-def get_parametric_edge(visible_checking, merged_edge_dict, meta_data_dir=None, detector=None):
+def get_parametric_edge(visible_checking, merged_edge_dict, meta_data_dir=None, detector=None, *, occluder=None,
+                        depth_maps=None, depth_slack=EO.DEPTH_SLACK, depth_window=EO.DEPTH_WINDOW, near_clip=None,
+                        backend="gpu"):
     """extract_para_edge.py:200-257: (pred_points float32 [N,3], return_edge_dict) with return_edge_dict =
     {"curves_ctl_pts": [n,4,3], "lines_end_pts": [n,6]} and the points sampled every 5 mm along its edges.  With
     visible_checking=True only the edges that compute_visibility keeps are returned (maps of `detector` read from
     `meta_data_dir`, the check on the current GPU) and the reference's "before / after visible checking" counts are
-    printed; meta_data_dir is then required (the reference's train.py never passes it)."""
+    printed; meta_data_dir is then required (the reference's train.py never passes it).
+
+    The depth gate (keyword arguments only; opt-in, UNTUNED, drawn solids only): with ``occluder`` -- float32 [F,3,3]
+    triangles or the path of an .obj / .ply mesh -- or ``depth_maps`` -- one float [H,W] array of camera z per frame -- the
+    check is ``scan_visibility_counts_depth``: a control or end point hidden behind the frame's depth plane (window maximum
+    of radius ``depth_window``, ``depth_slack`` world units behind the surface) is dropped before the frame's cell is formed,
+    so an edge inside a solid no longer reads whatever detected pixel it lands on.  ``near_clip`` as ``mesh_depth`` (with an
+    occluder only).  A line more is printed: the (edge, frame) cells in which the gate dropped a point.  ``backend="host"``
+    runs the gated check in numpy (the same counts to the bit).  Without a depth source nothing changes: the ungated check
+    has no host back end and nothing to clip, so ``backend="host"`` and ``near_clip`` are then ValueErrors."""
     curves, lines = _edge_arrays(merged_edge_dict)
-    if visible_checking:
-        if meta_data_dir is None:
-            raise ValueError("get_parametric_edge(visible_checking=True) needs meta_data_dir, the scan directory "
-                             "holding meta_data.json and the edge maps")
+    EO.check_one_depth_source("get_parametric_edge", occluder, depth_maps)
+    gated = occluder is not None or depth_maps is not None
+    if near_clip is not None and occluder is None:
+        raise ValueError("get_parametric_edge: near_clip needs an occluder (the caller's depth maps need no clipping)")
+    if not gated and backend != "gpu":
+        raise ValueError("get_parametric_edge: without a depth source the check runs on the GPU only (backend='gpu')")
+    if gated and not visible_checking:
+        raise ValueError("get_parametric_edge: a depth source gates the visibility check; it needs visible_checking=True")
+    if visible_checking and meta_data_dir is None:
+        raise ValueError("get_parametric_edge(visible_checking=True) needs meta_data_dir, the scan directory "
+                         "holding meta_data.json and the edge maps")
+    if visible_checking and gated:
+        counts, n_frames = scan_visibility_counts_depth(curves, lines, meta_data_dir, detector, occluder, depth_maps,
+                                                        depth_slack, depth_window, near_clip, backend)
+        keep = counts[:, 0] > edge_visibility_frames(n_frames)
+        cm, lm = keep[:len(curves)], keep[len(curves):]
+        print("before visible checking: ", len(curves) + len(lines), "after visible checking: ",
+              int(cm.sum()) + int(lm.sum()))
+        print("depth gate: dropped a point in", int(counts[:, 1].sum()), "of", len(keep) * n_frames, "(edge, frame) cells")
+        curves, lines = curves[cm], lines[lm]
+    elif visible_checking:
         maps, intrinsics, camtoworld, _, _ = get_edge_maps(meta_data_dir, detector)
         dev = torch.device("cuda", torch.cuda.current_device())
         cm, lm = compute_visibility(torch.from_numpy(curves).to(dev), torch.from_numpy(lines).to(dev),

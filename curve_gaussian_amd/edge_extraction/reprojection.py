@@ -365,8 +365,9 @@ def near_clip_options(what, near_clip, occluder):
     return {"near_clip": near_clip}
 
 
-def add_depth_arguments(ap):
-    """The depth source of the score (shared with train.py --reprojection_score); without them nothing changes."""
+def add_gate_arguments(ap):
+    """The depth source alone -- --occluder, --near_clip, --depth_dir, --depth_slack, --depth_window --, for the tools that
+    have no contour options (the visibility filter and the drawn views); ``check_gate_arguments`` after parsing."""
     ap.add_argument("--occluder", default=None, metavar="FILE",
                     help="a mesh file inside each scan directory (mesh.ply, .obj): samples hidden behind it are left out")
     ap.add_argument("--near_clip", nargs="?", type=float, const=EO.NEAR_CLIP, default=None, metavar="VALUE",
@@ -377,6 +378,27 @@ def add_depth_arguments(ap):
     ap.add_argument("--depth_slack", type=float, default=EO.DEPTH_SLACK, help="world units behind the surface (untuned)")
     ap.add_argument("--depth_window", type=int, default=EO.DEPTH_WINDOW,
                     help="radius of the window maximum over the depth planes (untuned)")
+
+
+def check_gate_arguments(ap, args):
+    """The parser errors of ``add_gate_arguments``: both depth sources, and --near_clip without --occluder."""
+    if args.occluder is not None and args.depth_dir is not None:
+        ap.error("give one depth source: --occluder or --depth_dir, not both")
+    if args.near_clip is not None and args.occluder is None:
+        ap.error("--near_clip needs --occluder: the mesh that is clipped")
+
+
+def gate_arguments(args):
+    """The depth keywords of a scan driver from parsed ``add_gate_arguments``: {} without a depth source."""
+    if args.occluder is None and args.depth_dir is None:
+        return {}
+    return dict(occluder=args.occluder, depth_dir=args.depth_dir, depth_slack=args.depth_slack,
+                depth_window=args.depth_window, near_clip=args.near_clip)
+
+
+def add_depth_arguments(ap):
+    """The depth source of the score (shared with train.py --reprojection_score); without them nothing changes."""
+    add_gate_arguments(ap)
     ap.add_argument("--ignore_contours", action="store_true",
                     help="with --occluder: leave a zone around the mesh's predicted occluding contours out of the score")
     ap.add_argument("--contour_radius_px", type=float, default=MC.CONTOUR_RADIUS_PX, help="radius of that zone (untuned)")

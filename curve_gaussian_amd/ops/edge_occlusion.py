@@ -36,7 +36,8 @@ five consumers: the score's prediction mask (``point_masks_depth``) and, opt-in,
 trimming and snapping (``support_counts``, ``sample_tally``, ``oriented_tally`` and ``snap_terms`` with ``depth=``; DESIGN.md
 4.8u), which share ``hidden_host`` / ``gate_view_host`` on the host and ``ChunkDepth`` for a scan's planes.  The edge vote
 (ops/edge_seed.py) takes it the same way, opt-in, for a voxel's centre; the control-point visibility check
-does NOT take it.  Along a CONCAVE edge the surface's depth is a local maximum, so samples of a visible concave edge can be
+(``edge_extraction.para_edge``) is ungated unless ``get_parametric_edge`` is given ``occluder=`` / ``depth_maps=``, and the
+drawn views (``edge_extraction.novel_view``) unless their drivers are (opt-in, like the others).  Along a CONCAVE edge the surface's depth is a local maximum, so samples of a visible concave edge can be
 hidden by their own faces where the faces are steep; a larger slack trades that against hiding less behind thin parts.
 ``DEPTH_WINDOW`` AND ``DEPTH_SLACK`` ARE UNTUNED: only the drawn solids of scene/solid_scan.py have been checked, no real
 scan."""

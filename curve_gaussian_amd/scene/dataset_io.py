@@ -276,7 +276,7 @@ def write_parametric_edges(gaussians, model_path, merge_endpoints=False, distanc
                            visible_checking=False, scan_dir=None, detector="DexiNed", support_checking=False,
                            support_options=None, cameras=None, edge_maps=None, trim=False, trim_options=None,
                            dedupe=False, dedupe_options=None, join=False, join_options=None, snap=False,
-                           snap_options=None, depth_options=None):
+                           snap_options=None, depth_options=None, visibility_options=None):
     """Writes parametric_edges.json (the evaluation input, train.py:287-293) and edge_points.ply (ASCII, :277-285).
     merge_endpoints / distance_threshold: see extract_curves (the reference's default is merge_endpoints=True).
     visible_checking=True keeps only the edges that `detector`'s edge maps of the scan at `scan_dir` show
@@ -309,7 +309,12 @@ def write_parametric_edges(gaussians, model_path, merge_endpoints=False, distanc
     order) with `depth_slack` and `depth_window`, as reprojection.score_edges takes them: it goes to the snapping, the
     support check and the trimming alike, each of which then counts a (sample, view) pair that the depth hides as not seen
     (ops.edge_occlusion; untuned, drawn solids only).  An option of the same name in snap_options, support_options or
-    trim_options wins for its step."""
+    trim_options wins for its step.
+    visibility_options (None: the check stays ungated) is a dict of the depth keywords of get_parametric_edge -- `occluder` or
+    `depth_maps` (one per FRAME of the scan), `depth_slack`, `depth_window`, `near_clip`, `backend` -- and gates the
+    visibility check itself, the one step that decides what goes into parametric_edges.json (needs visible_checking=True;
+    untuned, drawn solids only).  depth_options is deliberately NOT read for it: a run that passes depth_options alone
+    writes the parametric_edges.json it always wrote."""
     if visible_checking and scan_dir is None:
         raise ValueError("write_parametric_edges(visible_checking=True) needs scan_dir, the scan holding "
                          "meta_data.json and the edge maps")
@@ -321,7 +326,7 @@ def write_parametric_edges(gaussians, model_path, merge_endpoints=False, distanc
         raise ValueError("write_parametric_edges(snap=True) needs cameras, the views to snap the edges in")
     from ..edge_extraction.para_edge import get_parametric_edge
     merged = extract_curves(gaussians, merge_endpoints, distance_threshold)
-    pts, edge_dict = get_parametric_edge(visible_checking, merged, scan_dir, detector)
+    pts, edge_dict = get_parametric_edge(visible_checking, merged, scan_dir, detector, **(visibility_options or {}))
     write_edge_files(model_path, edge_dict, pts)
     written, source, named = edge_dict, "parametric_edges.json", {}
     if snap:

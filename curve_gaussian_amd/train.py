@@ -179,12 +179,13 @@ def _save_ply(gaussians, model_path, iteration):
     save_ply(gaussians, os.path.join(model_path, "point_cloud", f"iteration_{iteration}", "point_cloud.ply"))
 
 
-def _export(gaussians, dataset, opt):
-    """train.py:250-293 (extract_curves)."""
+def _export(gaussians, dataset, opt, visibility_options=None):
+    """train.py:250-293 (extract_curves).  ``visibility_options``: the depth gate of the visibility check (--gate_visibility)."""
     from .scene.dataset_io import write_parametric_edges
     return write_parametric_edges(gaussians, dataset.model_path, merge_endpoints=opt.merge_endpoints_flag,
                                   distance_threshold=0.015, visible_checking=opt.visible_checking,   # :264
-                                  scan_dir=dataset.source_path, detector=dataset.detector)
+                                  scan_dir=dataset.source_path, detector=dataset.detector,
+                                  **({"visibility_options": visibility_options} if visibility_options else {}))
 
 
 def training(dataset, opt, testing_iterations, saving_iterations, checkpoint_iterations, checkpoint=None, backend="graphed",
@@ -388,6 +389,14 @@ def build_parser():
                    help="--snap_edges, --support_check and --trim_edges also take the depth source that --occluder or "
                         "--depth_dir names: a (sample, view) pair the depth hides counts as not seen (needs one of the two; "
                         "untuned, checked on drawn solids only)")
+    p.add_argument("--visible_checking", action="store_true",
+                   help="the export keeps only the edges that the scan's edge maps show (the reference's OptimizationParams "
+                        "field of the same name, off in every option set; the check of get_parametric_edge, on the GPU)")
+    p.add_argument("--gate_visibility", action="store_true",
+                   help="the export's edge-map visibility check, which decides what goes into parametric_edges.json, also takes "
+                        "the depth source that --occluder or --depth_dir names (with --near_clip): a control or end point the "
+                        "depth hides is dropped before its frame is judged (needs one of the two, and the check itself: "
+                        "--visible_checking; untuned, checked on drawn solids only)")
     p.add_argument("--snap_edges", action="store_true",
                    help="after the export, FIRST move every edge of parametric_edges.json onto the detected edges of the "
                         "train cameras' edge maps: edge_snap.json and parametric_edges_snapped.json in the model directory; "
@@ -506,6 +515,10 @@ def parse_args(argv):
         parser.error("--gate_edge_checks needs a depth source: --occluder or --depth_dir")
     if args.gate_edge_checks and args.occluder is not None and args.depth_dir is not None:
         parser.error("--gate_edge_checks takes one depth source: --occluder or --depth_dir, not both")
+    if args.gate_visibility and args.occluder is None and args.depth_dir is None:
+        parser.error("--gate_visibility needs a depth source: --occluder or --depth_dir")
+    if args.gate_visibility and args.occluder is not None and args.depth_dir is not None:
+        parser.error("--gate_visibility takes one depth source: --occluder or --depth_dir, not both")
     if args.near_clip is not None and args.occluder is None:
         parser.error("--near_clip needs --occluder: the mesh that is clipped")
     if args.init_near_clip is not None and args.init_occluder is None:
@@ -516,6 +529,11 @@ def parse_args(argv):
         parser.error("--ignore_contours needs --occluder: the mesh whose contours are predicted")
     source_path = os.path.abspath(args.source_path)                                 # ModelParams.extract (:63-66)
     opt = select_options(source_path, args.detector)()
+    if args.visible_checking:
+        opt.visible_checking = True
+    if args.gate_visibility and not opt.visible_checking:
+        parser.error("--gate_visibility gates the export's visibility check, which this run leaves off: give "
+                     "--visible_checking too")
     if args.iterations is not None:
         opt.iterations = args.iterations
     args.save_iterations.append(opt.iterations)                                     # :404
@@ -550,9 +568,17 @@ def main(argv=None):
     if args.report_dir:
         from .evaluation import ReportDirWriter
         writer = ReportDirWriter(args.report_dir)
+    export = None
+    if args.gate_visibility:   # the depth maps are one per frame of the scan, found by the frames' names
+        cams = None
+        if args.depth_dir is not None:
+            from .edge_extraction.reprojection import emap_cameras
+            cams = emap_cameras(dataset.source_path, dataset.detector)[0]
+        vis = gate_options(args, dataset.source_path, cams, flag="gate_visibility")
+        export = lambda g, d, o: _export(g, d, o, vis)
     out = training(dataset, opt, args.test_iterations, args.save_iterations, args.checkpoint_iterations, args.start_checkpoint,
                    backend=args.backend, seed=args.seed, quiet=args.quiet, draw=args.draw_snapshots,
-                   topology_backend=args.topology_backend, report_writer=writer)
+                   topology_backend=args.topology_backend, report_writer=writer, export=export)
     if args.reprojection_score:
         from .edge_extraction.reprojection import scan_line, score_scene
         gate = {}
@@ -577,11 +603,12 @@ def main(argv=None):
     print("\nTraining complete.")
 
 
-def gate_options(args, source_path, cameras):
+def gate_options(args, source_path, cameras, flag="gate_edge_checks"):
     """The depth keywords of the chain's 2D steps under --gate_edge_checks: ``occluder`` (the mesh inside ``source_path``) or
     ``depth_maps`` (``<source_path>/<depth_dir>/<image stem>.npy`` of ``cameras``, NovelViewCamera s), and the slack and the
-    window; {} without the flag."""
-    if not getattr(args, "gate_edge_checks", False):
+    window; {} without the flag.  ``flag="gate_visibility"``: the same keywords for the export's visibility check
+    (``write_parametric_edges(visibility_options=)``; ``cameras`` are then the scan's frames)."""
+    if not getattr(args, flag, False):
         return {}
     if args.occluder is not None and args.depth_dir is not None:
         raise ValueError("--gate_edge_checks: give --occluder or --depth_dir, not both")

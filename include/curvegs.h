@@ -1396,7 +1396,8 @@ int cgs_sample_snap_terms_depth(int P, const float* points /*[P,3]*/, int V, con
  * LIMITS, those of the rule: no near-plane clipping in the z-buffer that usually draws depth; a voxel on a concave edge lies
  * behind both of its faces in the views that see it at a grazing angle; the window and the slack are untuned, checked on the
  * drawn solids of scene/solid_scan.py only.  cgs_voxel_moments and cgs_pack_near_bits have no gate (neither walks the views
- * of a voxel), and cgs_edge_visibility, the control-point check, is still ungated.
+ * of a voxel), and cgs_edge_visibility, the control-point check, is ungated unless its sibling cgs_edge_visibility_depth
+ * (below) is called instead.
  * ------------------------------------------------------------------------------------------------ */
 int cgs_voxel_votes_depth(int nx, int ny, int nz, const double* lo /*host, [3]*/, const double* step /*host, [3]*/, int V,
                           const double* intr /*[V,4]*/, const double* w2c /*[V,12]*/, int height, int width,
@@ -1414,6 +1415,63 @@ int cgs_ray_wins_depth(int nx, int ny, int nz, const double* lo /*host, [3]*/, c
                        const uint32_t* bits /*[V,height,ceil(width/32)]*/, const uint32_t* best /*[V,height,width]*/,
                        const float* depth /*[V,height,width]*/, double slack, int window, int margin, int accumulate,
                        uint16_t* wins /*[M]*/, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The depth gate on the control-point visibility check and on the drawn views: cgs_edge_visibility, cgs_project_points and
+ * cgs_render_points, each with the occlusion rule of cgs_point_mask_depth (nv_hidden, csrc/point_projection.h).  Opt-in,
+ * UNTUNED, checked on the drawn solids of scene/solid_scan.py only; the ungated entries are unchanged to the bit.  Each entry
+ * takes the arguments of its sibling, with their meaning, plus
+ *   depth   float32 [F or V,height,width], device: camera z per frame, +inf where there is no surface
+ *   slack   float64, finite and >= 0, in the units of depth
+ *
+ * cgs_edge_visibility_depth.  THE RULE, frozen -- float64, one rounded operation at a time, nothing contracted into an FMA:
+ *   c = w2c X with every row ((m0*X + m1*Y) + m2*Z) + t and x = K c with every row (k0*c0 + k1*c1) + k2*c2, as the sibling;
+ *   the raw coordinates are ur = x0 / x2, vr = x1 / x2; the camera depth is c2, the third row of w2c X, NOT x2
+ *   the sibling keeps a point when its ROUNDED pixel (rint(ur), rint(vr)) is in the image: that test stays as it is, and the
+ *   edge map is still read at the rounded pixel
+ *   a kept point is HIDDEN iff  ur >= 0 && vr >= 0 && c2 > (double)depth[f][floor(vr)][floor(ur)] + slack
+ * The plane is read at the FLOORED pixel, the convention the planes are drawn in (a pixel's centre is (j + 0.5, i + 0.5)): the
+ * two conventions differ by up to one pixel, which the window maximum that usually follows cgs_mesh_depth covers.  A point
+ * kept by rounding with ur or vr in [-0.5, 0) has no plane pixel and is never hidden; rint(ur) <= width - 1 implies
+ * floor(ur) <= width - 1, so there is no upper test.  A point behind the camera (c2 <= 0; the sibling keeps it, mirrored: the
+ * reference's quirk) is never hidden by a positive plane.  A NaN plane entry hides nothing.  A hidden point is dropped exactly
+ * as an out-of-image point is: it enters neither the sum, the maximum nor the number of points of its (edge, frame) cell, and a
+ * cell whose points are all hidden is 0.  counts_out is int32 [E,2], device, E = n_curves + n_lines, zeroed by a kernel and
+ * then WRITTEN: counts_out[e][0] = the frames in which edge e is visible, counts_out[e][1] = the frames in which the gate
+ * dropped at least one of its points.  On 0 / 255 maps counts_out[e][0] never exceeds the sibling's count (a cell is visible
+ * iff some kept point reads 255; dropping points cannot create one); with an all-+inf depth it is the sibling's count and
+ * counts_out[e][1] is 0.  The kernel is the sibling's body instantiated with the gate: two register counters, at most two
+ * integer atomicAdds per (edge, slice of frames), deterministic.  With K a pinhole matrix (no skew, K22 == 1), (ur, vr) is the
+ * image point the planes of cgs_mesh_depth are drawn for; for any other K the caller's planes must be in K's image.
+ *
+ * cgs_project_points_depth: uv_out as the sibling's, and (NaN, NaN) also for a point the view hides.  hidden_out is uint8
+ * [V,P], device, or NULL: 1 iff the projection kept the point and the gate hid it, WRITTEN, every byte.
+ *
+ * cgs_render_points_depth: a hidden point is dropped -- it is in no pixel's list, in neither the count pass nor the fill pass
+ * (both take the verdict from the same device function on the same data).  Hidden means dropped: nothing is drawn dashed or
+ * dimmed.  kept[v] stays "points in the image" that are drawn; hidden is int32 [V], device, or NULL: the points view v keeps
+ * and hides, cleared by a kernel and tallied in the count pass; kept[v] + hidden[v] is the sibling's kept[v].  The workspace
+ * is the sibling's (cgs_render_points_workspace_bytes): the lists can only get shorter.  The result does not depend on how the
+ * workspace cuts the views into chunks; with an all-+inf depth it is the sibling's image to the bit.
+ *
+ * Every argument is checked as the sibling checks it, and in addition a slack that is negative, NaN or infinite and a NULL
+ * depth are CGS_ERR_INVALID_ARGUMENT, rejected before anything is launched.  Caller's stream, no allocation, no host
+ * synchronisation.  LIMITS, those of the rule (see cgs_point_mask_depth): the window and the slack are the caller's.
+ * ------------------------------------------------------------------------------------------------ */
+int cgs_edge_visibility_depth(int n_curves, const double* curves /*[n_curves,4,3]*/, int n_lines,
+                              const double* lines /*[n_lines,2,3]*/, int n_frames, const double* K /*[n_frames,3,3]*/,
+                              const double* w2c /*[n_frames,3,4]*/, int height, int width,
+                              const unsigned char* maps /*[n_frames,height,width]*/, int invert,
+                              const float* depth /*[n_frames,height,width]*/, double slack, int32_t* counts_out /*[E,2]*/,
+                              void* stream);
+int cgs_project_points_depth(int P, const float* points /*[P,3]*/, int V, const double* intr /*[V,4]*/,
+                             const double* w2c /*[V,12]*/, int height, int width, const float* depth /*[V,height,width]*/,
+                             double slack, double* uv_out /*[V,P,2]*/, uint8_t* hidden_out /*[V,P] or NULL*/, void* stream);
+int cgs_render_points_depth(int P, const float* points /*[P,3]*/, const float* colors /*[P,3]*/, int V,
+                            const double* intr /*[V,4]*/, const double* w2c /*[V,12]*/, int height, int width,
+                            const float* depth /*[V,height,width]*/, double slack, double alpha,
+                            const double* background /*host, [3]*/, float* out /*[V,height,width,3]*/, int* kept /*[V] or NULL*/,
+                            int* hidden /*[V] or NULL*/, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Occluding contours of a triangle mesh: the edges along which a view sees a smooth surface turn away, drawn into one uint8
