@@ -32,11 +32,98 @@ def _quat_to_R(q):
     return R
 
 
+# Spherical-harmonic colour: constants of auxiliary.h:21-38 (as oracle/raster_ref.c and csrc/kernels.h restate them)
+SH_C0 = 0.28209479177387814
+SH_C1 = 0.4886025119029199
+SH_C2 = (1.0925484305920792, -1.0925484305920792, 0.31539156525252005, -1.0925484305920792, 0.5462742152960396)
+SH_C3 = (-0.5900435899266435, 2.890611442640554, -0.4570457994644658, 0.3731763325901154, -0.4570457994644658,
+         1.445305721320277, -0.5900435899266435)
+
+
+def sh_basis(x, y, z, degree, mag=False):
+    """[c_k basis_k(x, y, z)] for k < (degree + 1)^2 (forward.cu:34-70), on tensors or arrays.  `mag`: every function as the
+    sum of the MAGNITUDES of its monomials (what a float32 evaluation's rounding is proportional to)."""
+    n = -1.0
+    c0, c1, c2, c3 = SH_C0, SH_C1, SH_C2, SH_C3
+    if mag:
+        x, y, z, n = abs(x), abs(y), abs(z), 1.0
+        c1, c2, c3 = abs(c1), [abs(c) for c in c2], [abs(c) for c in c3]
+    b = [c0 + 0.0 * x]
+    if degree > 0:
+        b += [n * c1 * y, c1 * z, n * c1 * x]
+    if degree > 1:
+        xx, yy, zz, xy, yz, xz = x * x, y * y, z * z, x * y, y * z, x * z
+        b += [c2[0] * xy, c2[1] * yz, c2[2] * (2.0 * zz + n * xx + n * yy), c2[3] * xz, c2[4] * (xx + n * yy)]
+    if degree > 2:
+        b += [c3[0] * y * (3.0 * xx + n * yy), c3[1] * xy * z, c3[2] * y * (4.0 * zz + n * xx + n * yy),
+              c3[3] * z * (2.0 * zz + n * 3.0 * xx + n * 3.0 * yy), c3[4] * x * (4.0 * zz + n * xx + n * yy),
+              c3[5] * z * (xx + n * yy), c3[6] * x * (xx + n * 3.0 * yy)]
+    return b
+
+
+def sh_direction(means3D, campos):
+    d = means3D - campos.to(means3D.dtype).reshape(1, 3)
+    return d / torch.sqrt((d * d).sum(1, keepdim=True))
+
+
+def sh_colour(sh, means3D, campos, degree):
+    """forward.cu:20-75, single channel: colour [P, 1] = max(0, sum_k c_k basis_k(dir) sh_k + 0.5) with dir
+    the unit vector from the camera to the splat.  `sh` [P, M] or [P, M, 1]; M may be sized for a higher degree: the
+    coefficients from (degree + 1)^2 on are not read."""
+    P = means3D.shape[0]
+    sh = sh.reshape(P, -1)
+    assert sh.shape[1] >= (degree + 1) ** 2
+    d = sh_direction(means3D, campos)
+    b = sh_basis(d[:, 0], d[:, 1], d[:, 2], degree)
+    res = sum(bk * sh[:, k] for k, bk in enumerate(b)) + 0.5
+    return torch.clamp(res, min=0.0).reshape(P, 1)
+
+
+class _AntialiasingScaleRef(torch.autograd.Function):
+    """h = sqrt(max(0.000025, (a0 c0 - b0^2) / ((a0 + 0.3)(c0 + 0.3) - b0^2))) with the REFERENCE's backward, which is not
+    the derivative: backward.cu:234-241 evaluates d[(xy - z^2) / ((x + w)(y + w) - z^2)] with the
+    already dilated entries x = a0 + w, y = c0 + w (backward.cu:212-213); :219 zeroes it at or below the floor."""
+
+    @staticmethod
+    def forward(ctx, a0, b0, c0):
+        w = 0.3
+        ratio = (a0 * c0 - b0 * b0) / ((a0 + w) * (c0 + w) - b0 * b0)
+        h = torch.sqrt(torch.clamp(ratio, min=0.000025))
+        ctx.save_for_backward(a0, b0, c0, ratio, h)
+        return h
+
+    @staticmethod
+    def backward(ctx, dh):
+        a0, b0, c0, ratio, h = ctx.saved_tensors
+        w = 0.3
+        x, y, z = a0 + w, c0 + w, b0
+        d_inside_root = torch.where(ratio <= 0.000025, torch.zeros_like(dh), dh / (2.0 * h))
+        sqv = w * w + w * (x + y) + x * y - z * z
+        f = d_inside_root / (sqv * sqv)
+        return w * (w * y + y * y + z * z) * f, -2.0 * w * z * (w + x + y) * f, w * (w * x + x * x + z * z) * f
+
+
+class _ScaleModifierRef(torch.autograd.Function):
+    """Identity on the scales whose backward divides by `mod`: the reference's dL_dscale lacks the factor mod of
+    s = mod * scale (backward.cu:346,374-376)."""
+
+    @staticmethod
+    def forward(ctx, scales, mod):
+        ctx.mod = mod
+        return scales.clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        return g / ctx.mod, None
+
+
 def preprocess_2d(means3D, opacities, scales, rotations, viewmatrix, projmatrix, tan_fovx, tan_fovy, H, W,
-                  scale_modifier=1.0, means2D_ndc_offset=None, antialiasing=False, cov3D=None):
+                  scale_modifier=1.0, means2D_ndc_offset=None, antialiasing=False, cov3D=None, reference_backward=False):
     """The per-splat 2D state of dense_render, differentiable on its own: (px [P], py [P], conic [P,3], opac [P], tz [P],
     cov2d [P,3]) -- pixel-space centre, inverse of the dilated 2D covariance, (antialiased) opacity, view-space depth and
-    the dilated covariance itself (a, b, c).  `cov3D` [P,3,3] replaces R S^2 R^T (scales and rotations are then unused)."""
+    the dilated covariance itself (a, b, c).  `cov3D` [P,3,3] replaces R S^2 R^T (scales and rotations are then unused).
+    `reference_backward`: autograd with the reference's two departures from the derivative (_AntialiasingScaleRef,
+    _ScaleModifierRef) -- what its kernels return; the forward values are the same."""
     dt = means3D.dtype
     P = means3D.shape[0]
     vm = viewmatrix.to(dt).reshape(16)
@@ -55,6 +142,8 @@ def preprocess_2d(means3D, opacities, scales, rotations, viewmatrix, projmatrix,
     fy = H / (2.0 * tan_fovy)
     if cov3D is None:
         Rq = _quat_to_R(rotations)
+        if reference_backward and scale_modifier != 1.0:
+            scales = _ScaleModifierRef.apply(scales, scale_modifier)
         S2 = (scale_modifier * scales) ** 2
         Sigma = Rq @ torch.diag_embed(S2) @ Rq.transpose(1, 2)
     else:
@@ -73,7 +162,9 @@ def preprocess_2d(means3D, opacities, scales, rotations, viewmatrix, projmatrix,
     det = a * c - b * b
     conic = torch.stack([c / det, -b / det, a / det], 1)
     opac = opacities.reshape(-1)
-    if antialiasing:
+    if antialiasing and reference_backward:
+        opac = opac * _AntialiasingScaleRef.apply(a0, b0, c0)
+    elif antialiasing:
         opac = opac * torch.sqrt(torch.clamp((a0 * c0 - b0 * b0) / det, min=0.000025))
     px = ((p_proj[:, 0] + 1.0) * W - 1.0) * 0.5
     py = ((p_proj[:, 1] + 1.0) * H - 1.0) * 0.5
@@ -81,8 +172,13 @@ def preprocess_2d(means3D, opacities, scales, rotations, viewmatrix, projmatrix,
 
 
 def dense_render(means3D, opacities, scales, rotations, colors, all_map, viewmatrix, projmatrix, tan_fovx, tan_fovy,
-                 H, W, bg, scale_modifier=1.0, means2D_ndc_offset=None, antialiasing=False, trace=None):
+                 H, W, bg, scale_modifier=1.0, means2D_ndc_offset=None, antialiasing=False, trace=None, cov3D=None, sh=None,
+                 sh_degree=0, campos=None, reference_backward=False):
     """Returns (color[1,H,W], radii[P], invdepth[1,H,W], out_all_map[4,H,W]).  All float inputs share one dtype.
+
+    `cov3D` [P,3,3]: the 3D covariances (scales and rotations are then unused).  `sh` [P,M]: the colours are sh_colour(sh,
+    means3D, campos, sh_degree), computed inside the graph (`colors` is then unused): a colour depends on means3D through the
+    view direction.  `reference_backward`: see preprocess_2d.
 
     `trace`: an optional dict the walk fills with what a per-pair error analysis needs (tests/raster_ref64.py): "order" (the
     visible splats in depth order), the 2D state ("px", "py", "conic", "opac", "tz", "radius", "rect") and, per splat of
@@ -93,7 +189,12 @@ def dense_render(means3D, opacities, scales, rotations, colors, all_map, viewmat
     "blended"."""
     dt = means3D.dtype
     px, py, conic, opac, tz, cov2d = preprocess_2d(means3D, opacities, scales, rotations, viewmatrix, projmatrix, tan_fovx,
-                                                   tan_fovy, H, W, scale_modifier, means2D_ndc_offset, antialiasing)
+                                                   tan_fovy, H, W, scale_modifier, means2D_ndc_offset, antialiasing, cov3D,
+                                                   reference_backward)
+    if sh is not None:
+        colors = sh_colour(sh, means3D, campos, sh_degree)
+        if trace is not None:
+            trace["colors"] = colors.detach()
     a, b, c = cov2d[:, 0], cov2d[:, 1], cov2d[:, 2]
     det = a * c - b * b
     with torch.no_grad():

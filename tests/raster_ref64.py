@@ -89,6 +89,35 @@ and nothing of such an element can be compared.  Two kinds:
   at most 286 entries, built until every pair clears its margin) must have none.
 The long_* scenes (one tile, 1024 .. 9000 entries: every sort and every batch carry of the compositors), the turned_* scenes
 (20 tiles under the three turned cameras, depth ties) and the random scenes (RANDOM_SCENES) rest on the mask.
+
+Options
+-------
+The per-splat kernels' options (Options: spherical-harmonic colours, antialiasing, scale_modifier, cov3D_precomp; the scenes
+of OPTION_SETS; test_splat_options_ref64_cpu.py / _gpu.py).  The truth is dense_render with reference_backward=True: float64
+autograd but for the reference's two departures from the derivative, each a torch.autograd.Function evaluating the reference's
+own formula in float64 (torch_ref._AntialiasingScaleRef, backward.cu:234-241; _ScaleModifierRef, backward.cu:346,374-376;
+SURVEY quirks 23, 24).  The 2D state reaching the per-splat backward is (px, py, A, B, C, tz, effective opacity, colour); the
+bounds keep the construction above (first order in eps, sums of the magnitudes of an element's own terms, bound 0 = exact zero):
+- SH colour: the stage has its own constant, K_SH eps colmag, colmag = |C0 sh_0| + sum over the active k of |c_k basis_k|_mag
+  |sh_k| + 0.5 (|.|_mag: the sum of the magnitudes of the basis function's monomials), 0 for a clamped colour; measured on the
+  per-splat colour alone.  It is ADDED to the compositor's part (which stays at K with |v_s|): K_SH eps sum_s colmag_s w_s in
+  the colour image, (K_SH / K) colmag in place of |v_s| as a further term of gmag.
+  dL_dsh[k]: |c_k basis_k|_mag ((K_DL_DSH / K) bound of dL_dcolour + K_SH eps |dL_dcolour|), then quirk 16's layout (quirk16)
+  applied to truth and bound alike; the view-direction path into dL_dmeans3D: sum_k |sh_k| |d (c_k basis_k) / d dir| times
+  |d dir / d mean|.
+- two terms the option scenes' sub-0.04 px splats drawn on a pixel centre made necessary (the C oracle was outside without
+  them; option path only, so no compositor scene's bound changes): |d conic / d cov2D| from the magnitudes of the terms of
+  the kernels' formula, whose (denom - c_xx c_yy) cancels, and 16 eps |px| for the rounding of the pixel-space centre in the
+  moments of g (see grad_bounds, jacobian_opt).
+- antialiasing: h = sqrt(max(0.000025, det0 / det)) has the relative error eps hrel, hrel = 1/2 ((|a0 c0| + b0^2) / |det0| +
+  (a c + b^2) / det) -- det0 = a0 c0 - b0^2 cancels for thin splats --, which joins m in every pair's alpha error (m_rel) and the
+  effective opacity's gradient; the reference-formula gradient of h goes through |d h / d cov2D| |d cov2D / d Sigma| and the
+  stage magnitudes of section 5.
+- cov3D_precomp: Jmag ends at |d conic / d Sigma|; the off-diagonal entries of dL_dcov3D sum both symmetric entries (factor 2).
+- scale_modifier: |d Sigma / d S| carries mod^2, divided by mod for the departure; |d Sigma / d R| carries mod^2 s^2.
+Truth.jacobian_opt builds these; with every option at its default the numbers are those of the path above
+(test_default_options_return_the_same_float64_numbers).  K stays 64; K_MEASURED_OPTIONS holds the oracle's worst ratios on the
+option sets, and dL_dsh alone has its own constant K_DL_DSH.
 """
 import math
 
@@ -103,6 +132,23 @@ EPS = 2.0 ** -24
 K_MEASURED = {"color": 2.88, "invdepth": 6.07, "all_map": 10.66, "dL_dmeans3D": 0.79, "dL_dmeans2D": 0.82, "dL_dopacity": 1.89,
               "dL_dcolors": 5.00, "dL_dscales": 0.99, "dL_drotations": 0.65, "dL_dall_map": 5.14}
 K = 64.0   # 4 x max(K_MEASURED) = 42.6, rounded up to a power of two
+# The option sets (OPTION_SETS; test_splat_options_ref64_cpu.py measures and prints all of this from the C oracle).
+# K_SH: the spherical-harmonic stage's own constant -- the per-splat colour against eps colmag, measured on the colour alone
+# (the oracle's rgb buffer): worst 4.67 [sh3_aa_mod17, an isolated degree-3 coefficient]; 4 x 4.67 = 18.7 -> 32.  It bounds
+# the colour's rounding wherever the colour enters (images, gmag, the basis factor of dL_dsh); the compositor's part of every
+# bound stays at K.
+K_SH = 32.0
+# K_DL_DSH: the constant of the part of dL_dsh's bound inherited from the compositor's dL_dcolour (dL_dsh[k] = c_k basis_k
+# dL_dcolour): on these random clouds dL_dcolour's own error reaches a third of K (as on test_raster_ref64_cpu's random scenes),
+# 20.84 in dL_dsh[0] = C0 dL_dcolour on sh0: 4 x 20.84 = 83.4 -> 128.
+K_DL_DSH_MEASURED = 20.84
+K_DL_DSH = 128.0
+# worst |oracle - truth| / bound per tensor whose bound an option's own stage enters (tensor: (worst, option set)); the K rule
+# asks 4 x worst <= 1 of each
+K_MEASURED_OPTIONS = {"color": (0.170, "sh0"), "invdepth": (0.111, "sh3_aa_mod17"), "all_map": (0.145, "sh3_aa_mod17"),
+                      "dL_dmeans3D": (0.204, "aa"), "dL_dsh": (0.131, "sh2"), "dL_dopacity": (0.024, "cov_aa_sh2"),
+                      "dL_dscales": (0.089, "aa"), "dL_drotations": (0.082, "sh3_aa_mod17"), "dL_dcov3D": (0.043, "cov_aa_sh2"),
+                      "sh_colour": (0.146, "sh3_aa_mod17")}
 
 DT = torch.float64
 
@@ -511,6 +557,145 @@ def random_scene(row):
     return Scene(f"random_{seed}", built=(sp, cam, H, W, seed))
 
 
+# Option sets (module docstring: "Options"): name -> (seed, camera, sh degree or None, M, antialiasing, scale_modifier,
+# cov3D_precomp, render_geo).  A seed whose scene misses a mask condition or an edge count (option_edges) is replaced.
+OPTION_SETS = {
+    "sh0": (3100, 0, 0, 1, False, 1.0, False, True), "sh1": (3101, 1, 1, 4, False, 1.0, False, True),
+    "sh2": (3102, 2, 2, 9, False, 1.0, False, True), "sh3": (3103, 0, 3, 16, False, 1.0, False, True),
+    "sh1_m16": (3104, 1, 1, 16, False, 1.0, False, True), "aa": (3105, 2, None, 0, True, 1.0, False, True),
+    "cov": (3106, 0, None, 0, False, 1.0, True, True), "mod05": (3107, 1, None, 0, False, 0.5, False, True),
+    "mod17": (3108, 2, None, 0, False, 1.7, False, True), "sh3_aa_mod17": (3109, 0, 3, 16, True, 1.7, False, True),
+    "cov_aa_sh2": (3110, 1, 2, 9, True, 1.0, True, True), "nogeo_sh3": (3111, 2, 3, 16, False, 1.0, False, False)}
+OPTION_HW = (45, 64)     # 3 x 4 tiles, the last row ragged
+TAGS = ("random", "thin", "below_floor", "faint", "near", "offscreen", "below_floor_drawn")
+
+
+def option_scene(name):
+    """The Scene of an OPTION_SETS row, with .opt (Options), .render_geo and .tag ([P] index into TAGS): 330 random splats
+    (900 under the third camera; synthetic.random_splats, scales 0.01 .. 0.08) under a turned camera plus placed ones -- under antialiasing 12 thin ones at
+    axis ratio 20 turned in the image plane; 8 far ones of 0.02 .. 0.03 px (antialiasing ratio below its floor 0.000025), 8 of 0.1 px at
+    opacity 0.05 (above the floor; antialiased opacity under 0.5 / 255: visible, never blended), 6 inside the near plane and 6
+    whose tile rectangle is empty beyond the right edge.  Splats with a per-splat decision inside its margin (splat_failures
+    with the options, off-screen ones included) are dropped, then random ones from the tail until P is no multiple of 64."""
+    seed, cam_i, degree, M, aa, mod, use_cov, render_geo = OPTION_SETS[name]
+    H, W = OPTION_HW
+    cam = S.make_camera(*TURNED_CAMS[cam_i], H, W)
+    n_random = 330 if cam_i < 2 else 900     # (the third camera sits inside the cloud: it sees one splat in seven)
+    sp = S.random_splats(n_random, seed, scale_range=(0.01, 0.08))
+    b = Builder(H, W, seed + 50, cam=cam)
+    r = b.rng
+    uv = lambda: (r.uniform(2.0, W - 3.0), r.uniform(2.0, H - 3.0))
+    tags = [0] * n_random
+    # (thin ones under antialiasing only, where the issue is their cancelling det0: without it the float32 conic of a thin
+    # turned splat is the compositor scenes' subject, turned_*, and costs the images of these small scenes up to 65 of K = 64)
+    for _ in range(12 if aa else 0):
+        sv = r.uniform(0.7, 0.9)
+        b.add(*uv(), r.uniform(1.0, 3.0), 20.0 * sv, sv, r.uniform(0.3, 0.6), r.uniform(0, math.pi))
+    for _ in range(8):
+        s = math.sqrt(0.3 + r.uniform(0.02, 0.03) ** 2)
+        b.add(*uv(), r.uniform(3.0, 4.0), s, s, r.uniform(0.2, 0.35), 0.0)   # (times h = 0.005: under 0.5 / 255)
+    for _ in range(8):
+        s = math.sqrt(0.3 + 0.1 ** 2)
+        b.add(*uv(), r.uniform(1.5, 3.0), s, s, 0.05, 0.0)
+    for _ in range(6):
+        b.add(*uv(), 0.1, 2.0, 2.0, 0.5, 0.0)
+    for _ in range(6):
+        b.add(W + 6.0, r.uniform(2.0, H - 3.0), r.uniform(1.5, 3.0), 0.8, 0.8, 0.5, 0.0)
+    for _ in range(6):   # below the floor and DRAWN: opacity 0.93 .. 0.95 times h = 0.005 is 1.2 / 255, and the centre lies within
+        # 0.08 px of a pixel centre, where G >= 0.98: the floored h reaches the image and its zeroed gradient meets a dL_dopacity
+        s = math.sqrt(0.3 + r.uniform(0.02, 0.03) ** 2)
+        b.add(int(r.uniform(2.0, W - 3.0)) + r.uniform(-0.08, 0.08), int(r.uniform(2.0, H - 3.0)) + r.uniform(-0.08, 0.08),
+              r.uniform(3.0, 4.0), s, s, r.uniform(0.93, 0.95), 0.0)
+    tags += [1] * (12 if aa else 0) + [2] * 8 + [3] * 8 + [4] * 6 + [5] * 6 + [6] * 6
+    placed = b.splats()
+    # the sizes above are the ones the rasterizer sees: the inputs are those divided by scale_modifier (the option under test is
+    # the factor, not a cloud of sub-pixel splats at 0.5)
+    placed["scales"], sp["scales"] = placed["scales"] / mod, sp["scales"] / mod
+    sp = {k: torch.cat([sp[k], placed[k]]).contiguous() for k in sp}
+    P = len(tags)
+    g = torch.Generator().manual_seed(seed + 99)
+    # (coefficient spread per degree: wide enough at the low degrees for a few per cent of the results to fall below 0)
+    sh = torch.randn(P, M, generator=g) * (1.2, 0.8, 0.5, 0.5)[degree] if degree is not None else None
+    isolated = np.full(P, -1)
+    if degree:
+        # isolated coefficients: random splats whose only coefficient is one active k >= 1, at 40 with the sign that makes its
+        # term positive -- the colour (and dL_dsh[k]) IS that term: an error of one constant or one basis function is not
+        # averaged away by fifteen other terms.
+        nb = (degree + 1) ** 2
+        d = TR.sh_direction(sp["means3D"].to(DT), cam.camera_center.to(DT))
+        basis = torch.stack(TR.sh_basis(d[:, 0], d[:, 1], d[:, 2], degree), 1)
+        f64 = lambda v: v.to(DT)
+        cpx, cpy, _, _, ctz, _ = TR.preprocess_2d(f64(sp["means3D"]), f64(sp["opacities"]), f64(sp["scales"]), f64(sp["rotations"]),
+                                                  f64(cam.world_view_transform), f64(cam.full_proj_transform),
+                                                  math.tan(cam.FoVx * 0.5), math.tan(cam.FoVy * 0.5), H, W)
+        on_screen = torch.nonzero((ctz[:n_random] > 0.2) & (cpx[:n_random] > 1) & (cpx[:n_random] < W - 2) & (cpy[:n_random] > 1)
+                                  & (cpy[:n_random] < H - 2))[:, 0].tolist()
+        for j, i in enumerate(on_screen[:3 * (nb - 1)]):   # three on-screen random splats per k
+            k = 1 + j % (nb - 1)
+            sh[i], isolated[i] = 0.0, k
+            sh[i, k] = 40.0 * (1.0 if basis[i, k] >= 0 else -1.0)
+    cov = None
+    if use_cov:
+        # R S^2 R^T of the scene's splats, but 40 symmetric positive-definite matrices A A^T that are not of that form, one
+        # of them flat (a zero z row and column)
+        Sg = TR._quat_to_R(sp["rotations"]) @ torch.diag_embed(sp["scales"] ** 2) @ TR._quat_to_R(sp["rotations"]).transpose(1, 2)
+        A = torch.randn(40, 3, 3, generator=g) * 0.02
+        Sg[:40] = A @ A.transpose(1, 2)
+        Sg[7, 2, :] = 0.0
+        Sg[7, :, 2] = 0.0
+        cov = torch.stack([Sg[:, 0, 0], Sg[:, 0, 1], Sg[:, 0, 2], Sg[:, 1, 1], Sg[:, 1, 2], Sg[:, 2, 2]], 1).contiguous()
+    opt = Options(sh, degree or 0, aa, mod, cov)
+    keep = ~splat_failures(sp, cam, H, W, outside=True, opt=opt).any(1)
+    tag = np.array(tags)
+    while int(keep.sum()) % 64 == 0:
+        keep[np.nonzero(keep & (tag == 0))[0][-1]] = False
+    kt = torch.from_numpy(keep)
+    sp, opt = {k: v[kt].contiguous() for k, v in sp.items()}, opt.subset(kt)
+    assert not splat_failures(sp, cam, H, W, outside=True, opt=opt).any()
+    sc = Scene(f"option_{name}", built=(sp, cam, H, W, seed))
+    sc.opt, sc.render_geo, sc.tag, sc.isolated = opt, render_geo, tag[keep], isolated[keep]
+    sc.custom = (np.arange(P) < 40)[keep] & use_cov                      # the rows whose covariance is an A A^T
+    sc.flat = int(np.nonzero(keep)[0].tolist().index(7)) if use_cov and keep[7] else None
+    assert sc.P > 256 and sc.P % 64 != 0, sc.P
+    return sc
+
+
+def option_edges(sc, t):
+    """Asserts that the scene holds the edges its option set is there for (t: a Truth of it) and returns their counts."""
+    o, tag = sc.opt, sc.tag
+    vis = t.radii > 0
+    drawn = np.zeros(sc.P, bool)
+    drawn[t.order[t.blended.any(1)]] = True
+    n = dict(P=sc.P, visible=int(vis.sum()), blended=int(drawn.sum()), culled=int((~vis).sum()),
+             near=int((~vis & (tag == 4)).sum()), empty_rect=int((~vis & (t.tz > 0.2)).sum()))
+    assert n["near"] >= 5 and n["empty_rect"] >= 5 and n["culled"] >= 10, n
+    if o.sh is not None:
+        n.update(clamped=int((vis & t.clampd).sum()), unclamped=int((vis & ~t.clampd).sum()))
+        assert n["clamped"] >= 5 and n["unclamped"] >= 20, n
+        assert o.sh.shape[1] == OPTION_SETS[sc.name[7:]][3] >= (o.degree + 1) ** 2
+        n["isolated"] = int((drawn & (sc.isolated > 0)).sum())     # every active k >= 1 alone in a drawn, unclamped splat
+        assert set(sc.isolated[drawn & ~t.clampd]) >= set(range(1, (o.degree + 1) ** 2)), sorted(set(sc.isolated[drawn]))
+    if o.antialiasing:
+        below, above = vis & (t.aa_ratio <= 0.000025), vis & (t.aa_ratio > 0.000025)
+        faint = vis & (t.opac < 1.0 / 255.0)
+        n.update(below_floor=int(below.sum()), above_floor=int(above.sum()), antialiased_away=int(faint.sum()),
+                 thin=int((drawn & (tag == 1)).sum()))
+        assert n["below_floor"] >= 4 and n["above_floor"] >= 40 and n["antialiased_away"] >= 4 and n["thin"] >= 6, n
+        assert (faint & (tag == 3)).any() and not drawn[faint].any()
+        # the floor meets a gradient: below-floor splats that are blended, with a non-zero dL_dopacity (t with gradients)
+        lit = below & drawn
+        n["below_floor_drawn"] = int(lit.sum())
+        assert n["below_floor_drawn"] >= 3 and (tag[lit] == 6).all(), n
+        if t.g is not None:
+            assert (t.g["dL_dopacity"][lit, 0] != 0).all()
+    if o.cov3D is not None:
+        n.update(not_RSSR=int((vis & sc.custom).sum()), flat=sc.flat)
+        assert n["not_RSSR"] >= 20 and sc.flat is not None and vis[sc.flat], n
+        c = o.cov3D[sc.flat]
+        assert c[2] == 0 and c[4] == 0 and c[5] == 0 and c[0] > 0 and c[3] > 0
+    return n
+
+
 def scene_grads(scene, which=(True, True, True), mask=None):
     """Seeded upstream gradients (dL/dcolour, dL/dinvdepth, dL/dall_map); None where `which` is False.  `mask` [H, W]: the
     undecided pixels, where all three are zero -- every pair of such a pixel then contributes alpha * sum_ch d_ch (...) = 0 to
@@ -543,20 +728,97 @@ def _pre_args(scene, ins, off):
             cam.full_proj_transform.to(DT), scene.tfx, scene.tfy, scene.H, scene.W, 1.0, off)
 
 
+COV6 = torch.tensor([[0, 1, 2], [1, 3, 4], [2, 4, 5]])    # cov3D_precomp [P, 6] -> the symmetric [P, 3, 3]: cov6[:, COV6]
+
+
+class Options:
+    """The per-splat options of GaussianRasterizer that the compositor scenes leave at their defaults: `sh` [P, M] float32
+    spherical-harmonic coefficients evaluated at `degree` (None: colors_precomp), `antialiasing`, `scale_modifier`, `cov3D`
+    [P, 6] float32 (None: scales and rotations)."""
+
+    def __init__(self, sh=None, degree=0, antialiasing=False, scale_modifier=1.0, cov3D=None):
+        self.sh, self.degree, self.antialiasing, self.scale_modifier, self.cov3D = sh, degree, antialiasing, scale_modifier, cov3D
+
+    def subset(self, keep):
+        f = lambda t: None if t is None else t[keep].contiguous()
+        return Options(f(self.sh), self.degree, self.antialiasing, self.scale_modifier, f(self.cov3D))
+
+
+def quirk16(g):
+    """A per-coefficient gradient [P, M] as the operator returns it: the kernel writes P * M floats into the
+    head of a [P, M, 3] buffer, which autograd sums onto the [P, M, 1] input."""
+    P, M = g.shape
+    flat = np.zeros(P * M * 3)
+    flat[:P * M] = g.reshape(-1)
+    return flat.reshape(P, M, 3).sum(-1)
+
+
+def rows_of(splats, g, name):
+    """The elements of gradient tensor `g` that only the splats of the [P] mask `splats` write: their rows -- for dL_dsh,
+    whose layout quirk 16 scrambles, the elements no other splat's coefficient is summed into."""
+    if name != "dL_dsh":
+        return np.broadcast_to(splats.reshape((-1,) + (1,) * (g.ndim - 1)), g.shape)
+    return quirk16(np.broadcast_to((~splats)[:, None], g.shape).astype(np.float64)) == 0
+
+
+def sh_terms(sh, means3D, campos, degree):
+    """(result [P], magnitude [P]) in float64: the spherical-harmonic sum + 0.5 before its clamp at 0, and the sum of the
+    magnitudes of its terms, |C0 sh_0| + sum_k |c_k basis_k|_mag |sh_k| + 0.5."""
+    d = TR.sh_direction(means3D.to(DT), campos.to(DT)).numpy()
+    s = sh.to(DT).numpy().reshape(len(d), -1)
+    b = TR.sh_basis(d[:, 0], d[:, 1], d[:, 2], degree)
+    bm = TR.sh_basis(d[:, 0], d[:, 1], d[:, 2], degree, mag=True)
+    res = sum(bk * s[:, k] for k, bk in enumerate(b)) + 0.5
+    mag = sum(bk * np.abs(s[:, k]) for k, bk in enumerate(bm)) + 0.5
+    return res, mag
+
+
+def aa_terms(cov2d):
+    """(ratio [P], hrel [P]) of the antialiasing factor h = sqrt(max(0.000025, ratio)), ratio = det0 / det with det0 =
+    a0 c0 - b0^2 of the undilated and det = a c - b^2 of the dilated 2D covariance: hrel = the relative rounding error of h
+    in units of eps, 1/2 ((|a0 c0| + b0^2) / |det0| + (a c + b^2) / det) -- det0 cancels for thin splats."""
+    a, b, c = np.asarray(cov2d, np.float64).T
+    a0, c0 = a - 0.3, c - 0.3
+    det0, det = a0 * c0 - b * b, a * c - b * b
+    with np.errstate(divide="ignore", invalid="ignore"):
+        hrel = 0.5 * ((np.abs(a0 * c0) + b * b) / np.abs(det0) + (a * c + b * b) / det)
+    return det0 / det, hrel
+
+
+def _jac(P, outs, xs):
+    """[P, len(outs), sum of the xs' row sizes]: per-splat Jacobian of per-splat outputs (rows are independent)."""
+    rows = []
+    for o in outs:
+        gs = torch.autograd.grad(o.sum(), xs, retain_graph=True, allow_unused=True)
+        rows.append(np.concatenate([(np.zeros(tuple(x.shape)) if g is None else g.numpy()).reshape(P, -1) for g, x in zip(gs, xs)], 1))
+    return np.stack(rows, 1)
+
+
 class Truth:
     """One float64 forward + backward of dense_render on a scene variant with one set of upstream gradients."""
 
-    def __init__(self, scene, sp, grads=None, render_geo=True):
-        self.scene, self.render_geo = scene, render_geo
+    def __init__(self, scene, sp, grads=None, render_geo=True, opt=None):
+        """`opt`: an Options (spherical-harmonic colours, antialiasing, scale_modifier, cov3D_precomp); None = none of them,
+        through the call dense_render always had."""
+        self.scene, self.render_geo, self.opt = scene, render_geo, opt
         H, W, P = scene.H, scene.W, scene.P
         ins = {k: v.to(DT).requires_grad_(grads is not None) for k, v in sp.items()}
         off = torch.zeros(P, 2, dtype=DT, requires_grad=grads is not None)
         cam = scene.cam
         tr = {}
+        kw = {}
+        if opt is not None:
+            kw = dict(scale_modifier=opt.scale_modifier, antialiasing=opt.antialiasing, reference_backward=True)
+            if opt.sh is not None:
+                ins["sh"] = opt.sh.to(DT).requires_grad_(grads is not None)
+                kw.update(sh=ins["sh"], sh_degree=opt.degree, campos=cam.camera_center.to(DT))
+            if opt.cov3D is not None:
+                ins["cov3D"] = opt.cov3D.to(DT).requires_grad_(grads is not None)
+                kw.update(cov3D=ins["cov3D"][:, COV6])
         col, radii, invd, amap = TR.dense_render(
             ins["means3D"], ins["opacities"], ins["scales"], ins["rotations"], ins["colors"], ins["all_map"],
             cam.world_view_transform.to(DT), cam.full_proj_transform.to(DT), scene.tfx, scene.tfy, H, W, scene.bg.to(DT),
-            means2D_ndc_offset=off, trace=tr)
+            means2D_ndc_offset=off, trace=tr, **kw)
         if not render_geo:
             amap = torch.zeros_like(amap)
         self.out = dict(color=col.detach().numpy(), invdepth=invd.detach().numpy(), all_map=amap.detach().numpy())
@@ -570,6 +832,11 @@ class Truth:
         self.px, self.py, self.conic, self.opac, self.tz = (tr[k].numpy() for k in ("px", "py", "conic", "opac", "tz"))
         self.lam, self.rect = tr["lam"].numpy(), tr["rect"].numpy()
         self.colors, self.all_map = sp["colors"].double().numpy()[:, 0], sp["all_map"].double().numpy()
+        # what the options add: to a pair's relative alpha error (the antialiasing factor's own rounding, hrel) and, for
+        # spherical-harmonic colours (sh_stage), the sum of the magnitudes of a colour's terms (colmag)
+        self.hrel, self.colmag, self.sh_stage = np.zeros(P), np.zeros(P), False
+        if opt is not None:
+            self._option_state(tr)
         self.grads = grads
         self.g = None
         if grads is not None:
@@ -583,6 +850,10 @@ class Truth:
             self.g = dict(dL_dmeans3D=z(ins["means3D"]), dL_dmeans2D=m2, dL_dopacity=z(ins["opacities"]),
                           dL_dcolors=z(ins["colors"]), dL_dscales=z(ins["scales"]), dL_drotations=z(ins["rotations"]),
                           dL_dall_map=z(ins["all_map"]) if render_geo else np.zeros((P, 4)))
+            if "sh" in ins:
+                self.g["dL_dsh"] = quirk16(z(ins["sh"]))
+            if "cov3D" in ins:
+                self.g["dL_dcov3D"] = z(ins["cov3D"])
             self.dalpha = (np.stack([(t.grad if t.grad is not None else torch.zeros_like(t)).numpy() for t in tr["alpha"]])
                            if N else np.zeros((0, H * W)))
         self._pairs()
@@ -597,33 +868,38 @@ class Truth:
         self.al = np.where(bl, self.alpha_u, 0.0)
         self.w = self.al * self.Tb
         self.n_front = np.cumsum(bl, 0) - bl
-        self.X = (bl * self.al / (1 - self.al) * self.m).sum(0)
-        self.omega = 1 + self.m + self.X[None, :] + self.n_front
+        # (with antialiasing the opacity carries the relative error eps hrel of its factor h into every alpha of the splat)
+        self.m_rel = self.m + self.hrel[o][:, None]
+        self.X = (bl * self.al / (1 - self.al) * self.m_rel).sum(0)
+        self.omega = 1 + self.m_rel + self.X[None, :] + self.n_front
         self.T_final = (self.Tb[-1] * (1 - self.al[-1])) if len(o) else np.ones(self.scene.H * self.scene.W)
         self.n_blended = bl.sum(0)
 
     def _channels(self):
-        """[(name, v [N], |bg|)] of the channels the forward accumulates."""
+        """[(name, v [N], |v| [N], |bg|)] of the channels the forward accumulates."""
         o = self.order
-        ch = [("color", self.colors[o], float(self.scene.bg[0])), ("invdepth", 1.0 / self.tz[o], 0.0)]
+        ch = [("color", self.colors[o], np.abs(self.colors[o]), float(self.scene.bg[0])),
+              ("invdepth", 1.0 / self.tz[o], np.abs(1.0 / self.tz[o]), 0.0)]
         if self.render_geo:
-            ch += [(f"all_map{k}", self.all_map[o, k], 0.0) for k in range(4)]
+            ch += [(f"all_map{k}", self.all_map[o, k], np.abs(self.all_map[o, k]), 0.0) for k in range(4)]
         return ch
 
-    def _chanmag(self, v, bg):
+    def _chanmag(self, vmag, bg):
         """T |v_s| + (sum_{t behind} |v_t| w_t + |bg| T_final) / (1 - alpha_s): the magnitudes of d out / d alpha_s's terms."""
-        t = np.abs(v)[:, None] * self.w
+        t = vmag[:, None] * self.w
         behind = np.cumsum(t[::-1], 0)[::-1] - t + abs(bg) * self.T_final[None, :]
-        return self.Tb * np.abs(v)[:, None] + behind / (1 - self.al)
+        return self.Tb * vmag[:, None] + behind / (1 - self.al)
 
     def image_bounds(self, K=None):
         K = globals()["K"] if K is None else K
         H, W = self.scene.H, self.scene.W
         out = {}
-        for name, v, bg in self._channels():
-            sens = (self.al * self._chanmag(v, bg) * (1 + self.m)).sum(0)
-            mag = (np.abs(v)[:, None] * self.w).sum(0) + abs(bg) * self.T_final
+        for name, v, vmag, bg in self._channels():
+            sens = (self.al * self._chanmag(vmag, bg) * (1 + self.m_rel)).sum(0)
+            mag = (vmag[:, None] * self.w).sum(0) + abs(bg) * self.T_final
             out[name] = (K * EPS * (sens + (self.n_blended + 2) * mag)).reshape(H, W)
+        if self.sh_stage:   # the spherical-harmonic colours' own rounding, K_SH eps colmag per splat, weighted like the colours
+            out["color"] = out["color"] + ((K * K_SH / globals()["K"]) * EPS * (self.colmag[self.order][:, None] * self.w).sum(0)).reshape(H, W)
         am = np.stack([out.get(f"all_map{k}", np.zeros((H, W))) for k in range(4)])
         return dict(color=out["color"][None], invdepth=out["invdepth"][None], all_map=am)
 
@@ -679,9 +955,11 @@ class Truth:
         for k in range(4):
             ups[f"all_map{k}"] = None if damap is None or not self.render_geo else damap[k]
         gmag = np.zeros_like(self.al)
-        for name, v, bg in self._channels():
+        for name, v, vmag, bg in self._channels():
             if ups[name] is not None:
-                gmag += np.abs(ups[name])[None, :] * self._chanmag(v, bg)
+                gmag += np.abs(ups[name])[None, :] * self._chanmag(vmag, bg)
+        if self.sh_stage and ups["color"] is not None:   # the colours' own rounding (K_SH eps colmag) in dL/dalpha's two halves
+            gmag += (K_SH / globals()["K"]) * np.abs(ups["color"])[None, :] * self._chanmag(self.colmag[o], 0.0)
         gmag *= self.al
         g = self.al * self.dalpha
         self.gmag, self.gpair = gmag, g
@@ -707,17 +985,178 @@ class Truth:
                                  (gmag * (np.abs(C * dy) + np.abs(B * dx)) * om).sum(1), 0.5 * (gmag * dx * dx * om).sum(1),
                                  (gmag * np.abs(dx * dy) * om).sum(1), 0.5 * (gmag * dy * dy * om).sum(1),
                                  Binv / (K * EPS) / self.tz[o] ** 2], 1)
+        if self.opt is not None:
+            # the float32 pixel-space centre is rounded at eps |px| (not eps |dx|): in the moments of g that is eps |px| times the
+            # derivative of the moment's weight by dx.  Sections 4 and 5 leave it to K, which holds while |dx| is not small
+            # against eps |px| / eps; the option scenes place drawn splats within 0.08 px of a pixel centre (the C oracle's
+            # dL_dmeans2D 44 x outside the bound without this term).
+            # px passes four roundings at its own magnitude after the projection (p_hom.x p_w, + 1, W, - 1): 4 eps |px|, taken
+            # 4 x as the K rule takes a measured error: 16 eps |px| = K / 4, not K eps |px|
+            apx, apy = np.abs(self.px[o])[:, None], np.abs(self.py[o])[:, None]
+            B2 = B2 + (K / globals()["K"]) * 16.0 * EPS * np.stack([(gmag * (np.abs(A) * apx + np.abs(B) * apy)).sum(1), (gmag * (np.abs(C) * apy + np.abs(B) * apx)).sum(1),
+                                          (gmag * np.abs(dx) * apx).sum(1), (gmag * (np.abs(dx) * apy + np.abs(dy) * apx)).sum(1),
+                                          (gmag * np.abs(dy) * apy).sum(1), np.zeros(len(o))], 1)
         G2f, B2f = full(G2, (P, 6)), full(B2, (P, 6))
         half = np.array([0.5 * W, 0.5 * H])
         Gd["dL_dmeans2D"] = np.concatenate([G2f[:, :2] * half, np.zeros((P, 1))], 1)
         Bd["dL_dmeans2D"] = np.concatenate([B2f[:, :2] * half, np.zeros((P, 1))], 1)
+        self.G2, self.B2 = G2f, B2f
+        if self.opt is not None:
+            self._option_bounds(K, Bd, Gd, G2f, B2f, J)
+            return Bd, Gd
         J, Jmag = self.jacobian() if J is None else J
         G3 = np.einsum("pij,pi->pj", J, G2f)
         B3 = np.einsum("pij,pi->pj", Jmag, B2f) + K * EPS * np.einsum("pij,pi->pj", Jmag, np.abs(G2f))
         for name, sl in (("dL_dmeans3D", slice(0, 3)), ("dL_dscales", slice(3, 6)), ("dL_drotations", slice(6, 10))):
             Gd[name], Bd[name] = G3[:, sl], B3[:, sl]
-        self.G2, self.B2 = G2f, B2f
         return Bd, Gd
+
+    # ---- the per-splat options (module docstring: "Options")
+    def _opt_pre(self, m, op, s, q, cov):
+        sc, o = self.scene, self.opt
+        return TR.preprocess_2d(m, op, s, q, sc.cam.world_view_transform.to(DT), sc.cam.full_proj_transform.to(DT), sc.tfx, sc.tfy,
+                                sc.H, sc.W, o.scale_modifier, None, o.antialiasing, cov, True)
+
+    def _option_state(self, tr):
+        """hrel, colmag and the decisions the options add (clampd: the spherical-harmonic result is negative)."""
+        sc, o = self.scene, self.opt
+        P = sc.P
+        self.clampd = np.zeros(P, bool)
+        if o.sh is not None:
+            res, mag = sh_terms(o.sh, sc.sp["means3D"], sc.cam.camera_center, o.degree)
+            self.clampd = res < 0
+            self.colors = tr["colors"].numpy()[:, 0]
+            self.colmag, self.sh_stage = np.where(self.clampd, 0.0, mag), True
+        if o.antialiasing:
+            cov = None if o.cov3D is None else o.cov3D.to(DT)[:, COV6]
+            d = lambda k: sc.sp[k].to(DT)
+            cov2d = self._opt_pre(d("means3D"), d("opacities"), d("scales"), d("rotations"), cov)[5].numpy()
+            ratio, hrel = aa_terms(cov2d)
+            self.aa_ratio = ratio
+            self.hrel = np.where(ratio > 0.000025, hrel, 0.0)
+
+    def jacobian_opt(self):
+        """(J, Jmag), both [P, 8, 17 + M]: d (px, py, A, B, C, tz, effective opacity, colour) / d (means3D 3, scales 3,
+        rotations 4, cov3D 6, opacity 1, sh M) per splat -- J by float64 autograd with the reference's two departures
+        (torch_ref.preprocess_2d(reference_backward=True)), Jmag with the magnitudes of the stages multiplied as in jacobian():
+            Jmag[A B C, .]           = |d conic / d Sigma| |d Sigma / d .|
+            Jmag[op_eff, .]          = opacity |d h / d cov2D| |d cov2D / d Sigma| |d Sigma / d .|   (h by the reference formula)
+            |d Sigma / d scales|     = |d (R (mod S)^2 R^T) / d S| / mod                             (the departure's division)
+            |d Sigma / d rotations|  = |d (R (mod S)^2 R^T) / d R| |d R / d q|
+            |d Sigma / d cov3D|      = 1 on the diagonal entries, 2 on the others (both symmetric entries read the input)
+            Jmag[colour, means3D]    = sum_k |sh_k| |d (c_k basis_k) / d dir| |d dir / d means3D|
+            Jmag[colour, sh_k]       = |c_k basis_k| (the sum of the magnitudes of its monomials)
+        A clamped colour's row is zero; columns of an input the option set does not have are zero."""
+        sc, o = self.scene, self.opt
+        P = sc.P
+        M = 0 if o.sh is None else o.sh.shape[1]
+        has_cov = o.cov3D is not None
+        leaf = lambda t: t.detach().to(DT).clone().requires_grad_(True)
+        m, op, s, q = (leaf(sc.sp[k]) for k in ("means3D", "opacities", "scales", "rotations"))
+        cov6 = leaf(o.cov3D) if has_cov else None
+        campos = sc.cam.camera_center.to(DT)
+        px, py, conic, opac, tz, cov2d_m = self._opt_pre(m, op, s, q, cov6[:, COV6] if has_cov else None)
+        outs = [px, py, conic[:, 0], conic[:, 1], conic[:, 2], tz, opac]
+        xs, cols = [m], [slice(0, 3)]
+        if has_cov:
+            xs, cols = xs + [cov6], cols + [slice(10, 16)]
+        else:
+            xs, cols = xs + [s, q], cols + [slice(3, 6), slice(6, 10)]
+        xs, cols = xs + [op], cols + [slice(16, 17)]
+        if M:
+            sh = leaf(o.sh)
+            outs.append(TR.sh_colour(sh, m, campos, o.degree)[:, 0])
+            xs, cols = xs + [sh], cols + [slice(17, 17 + M)]
+        Jc = _jac(P, outs, xs)
+        J = np.zeros((P, 8, 17 + M))
+        at = 0
+        for x, c in zip(xs, cols):
+            J[:, :len(outs), c] = Jc[:, :, at:at + (c.stop - c.start)]
+            at += c.stop - c.start
+        a = np.abs
+        Jmag = a(J)
+        # the covariance path, stage by stage
+        if has_cov:
+            Sl = leaf(cov6[:, COV6])
+        else:
+            ql = leaf(q)
+            R = TR._quat_to_R(ql)
+            J_Rq = _jac(P, [R[:, i, j] for i in range(3) for j in range(3)], [ql])                   # [P, 9, 4]
+            Rl, sl = leaf(R), leaf(s)
+            Sig = Rl @ torch.diag_embed((o.scale_modifier * sl) ** 2) @ Rl.transpose(1, 2)
+            J_SRs = _jac(P, [Sig[:, i, j] for i in range(3) for j in range(3)], [Rl, sl])            # [P, 9, 9 + 3]
+            Sl = leaf(Sig)
+        pre = self._opt_pre(m.detach(), op.detach(), None, None, Sl)
+        con, cov2 = pre[2], pre[5]
+        stage = np.zeros((P, 4, 9))                                                                  # rows A, B, C, op_eff
+        J_vS = _jac(P, [cov2[:, 0], cov2[:, 1], cov2[:, 2]], [Sl])                                   # [P, 3, 9]
+        # |d conic / d cov2D| as the magnitudes of the terms of the formula the kernels evaluate (backward.cu:247-260): its
+        # (denom - c_xx c_yy) cancels to -c_xy^2, which leaves eps (denom + c_xx c_yy) |dL_dconic.z| in dL_dc_xx whatever the
+        # true derivative is (found on the drawn below-floor splats, 0.025 px: the C oracle 81 x outside |d conic / d Sigma|)
+        cx, cxy, cy = (cov2.detach().numpy()[:, i] for i in range(3))
+        den = cx * cy - cxy * cxy
+        Mv = np.stack([np.stack([cy * cy, 2 * a(cxy) * cy, den + cx * cy], 1),
+                       np.stack([2 * a(cxy) * cy, 2 * (den + 2 * cxy * cxy), 2 * cx * a(cxy)], 1),
+                       np.stack([den + cx * cy, 2 * cx * a(cxy), cx * cx], 1)], 1) / (den * den)[:, None, None]   # [P, cov2D, conic]
+        stage[:, :3] = np.maximum(a(_jac(P, [con[:, 0], con[:, 1], con[:, 2]], [Sl])), np.einsum("pvc,pvk->pck", Mv, a(J_vS)))
+        J_vm = _jac(P, [cov2d_m[:, 0], cov2d_m[:, 1], cov2d_m[:, 2]], [m])                           # [P, 3, 3]
+        Jmag[:, 2:5, 0:3] = np.maximum(Jmag[:, 2:5, 0:3], np.einsum("pvc,pvk->pck", Mv, a(J_vm)))
+        if o.antialiasing:
+            c0 = leaf(cov2 - torch.tensor([0.3, 0.0, 0.3], dtype=DT))
+            h = TR._AntialiasingScaleRef.apply(c0[:, 0], c0[:, 1], c0[:, 2])
+            J_hv = _jac(P, [h], [c0])                                                                # [P, 1, 3]
+            stage[:, 3:] = a(op.detach().numpy()).reshape(P, 1, 1) * np.einsum("pij,pjk->pik", a(J_hv), a(J_vS))
+        rows = [2, 3, 4, 6]
+        if has_cov:
+            F = np.zeros((9, 6))
+            for i in range(3):
+                for j in range(3):
+                    F[3 * i + j, int(COV6[i, j])] = 1.0
+            Jmag[:, rows, 10:16] = stage @ F
+        else:
+            Jmag[:, rows, 3:6] = np.einsum("pij,pjk->pik", stage, a(J_SRs[:, :, 9:])) / o.scale_modifier
+            Jmag[:, rows, 6:10] = np.einsum("pij,pjk,pkl->pil", stage, a(J_SRs[:, :, :9]), a(J_Rq))
+        if M:
+            live = (~self.clampd).astype(np.float64)
+            ml = leaf(m)
+            d = TR.sh_direction(ml, campos)
+            J_dm = _jac(P, [d[:, 0], d[:, 1], d[:, 2]], [ml])                                        # [P, 3, 3]
+            dl, shd = leaf(d), o.sh.to(DT)
+            dcd = np.zeros((P, 3))
+            for k, bk in enumerate(TR.sh_basis(dl[:, 0], dl[:, 1], dl[:, 2], o.degree)):
+                if k:
+                    dcd += a(torch.autograd.grad((bk * shd[:, k]).sum(), dl, retain_graph=True)[0].numpy())
+            Jmag[:, 7, 0:3] = live[:, None] * np.einsum("pj,pji->pi", dcd, a(J_dm))
+            dn = d.detach().numpy()
+            bm = np.stack(TR.sh_basis(dn[:, 0], dn[:, 1], dn[:, 2], o.degree, mag=True), 1)
+            Jmag[:, 7, 17:17 + bm.shape[1]] = live[:, None] * bm
+        assert (Jmag >= a(J) * (1 - 1e-9)).all()
+        return J, Jmag
+
+    def _option_bounds(self, K, Bd, Gd, G2f, B2f, J=None):
+        """The per-splat backward with options: the 2D state is (px, py, A, B, C, tz, effective opacity, colour), whose last two
+        gradients and bounds are the compositor's dL_dopacity and dL_dcolors (bounds of section 4); each input's gradient is
+        J^T G_state with bound |J|^T B_state + K eps |J|^T |G_state| (section 5), the antialiasing factor's own rounding
+        (eps hrel of h) added to the effective opacity's row."""
+        o = self.opt
+        J, Jmag = self.jacobian_opt() if J is None else J
+        Gop, Bop = Gd["dL_dopacity"][:, 0], Bd["dL_dopacity"][:, 0]
+        G8 = np.concatenate([G2f, Gop[:, None], Gd["dL_dcolors"]], 1)
+        B8 = np.concatenate([B2f, (Bop + K * EPS * self.hrel * np.abs(Gop))[:, None], Bd["dL_dcolors"]], 1)
+        G = np.einsum("pij,pi->pj", J, G8)
+        B = np.einsum("pij,pi->pj", Jmag, B8) + K * EPS * np.einsum("pij,pi->pj", Jmag, np.abs(G8))
+        for name, sl in (("dL_dmeans3D", slice(0, 3)), ("dL_dscales", slice(3, 6)), ("dL_drotations", slice(6, 10))):
+            Gd[name], Bd[name] = G[:, sl], B[:, sl]
+        if o.antialiasing:   # (without it the effective opacity IS the input: the compositor's own gradient and bound)
+            Gd["dL_dopacity"], Bd["dL_dopacity"] = G[:, 16:17], B[:, 16:17]
+        if o.cov3D is not None:
+            Gd["dL_dcov3D"], Bd["dL_dcov3D"] = G[:, 10:16], B[:, 10:16]
+        if o.sh is not None:
+            # dL_dsh[k] = c_k basis_k dL_dcolour: the compositor's bound of dL_dcolour (at K_DL_DSH) and the basis function's
+            # own rounding (the spherical-harmonic stage, K_SH eps), both times |c_k basis_k|_mag
+            k0 = globals()["K"]
+            per = (K_DL_DSH / k0) * Bd["dL_dcolors"] + (K * K_SH / k0) * EPS * np.abs(Gd["dL_dcolors"])
+            Gd["dL_dsh"], Bd["dL_dsh"] = quirk16(G[:, 17:]), quirk16(Jmag[:, 7, 17:] * per)
 
     # ---- decisions
     def terminated(self):
@@ -810,11 +1249,11 @@ def _pair_margins(t, K=None):
     ran and that test's distance in bounds of the pair's own T."""
     K = globals()["K"] if K is None else K
     reached = t.member & ~_done_before(t)
-    a_err = K * EPS * (1 + t.m)
+    a_err = K * EPS * (1 + t.m_rel)
     r_alpha = np.abs(255.0 * t.alpha_u - 1.0) / a_err
     tested = t.blended | t.stopped
     Tn = t.Tb * (1 - np.minimum(t.alpha_u, 0.99))
-    t_err = K * EPS * (t.n_front + 1 + (1 + t.m) * t.alpha_u / (1 - np.minimum(t.alpha_u, 0.99)) + t.X[None, :])
+    t_err = K * EPS * (t.n_front + 1 + (1 + t.m_rel) * t.alpha_u / (1 - np.minimum(t.alpha_u, 0.99)) + t.X[None, :])
     r_T = np.abs(1e4 * Tn - 1.0) / t_err
     return reached, r_alpha, tested, r_T
 
@@ -842,17 +1281,22 @@ def check_mask(scene, mask):
     assert worst <= 16, f"{scene.name}: {worst} undecided pixels in one quadrant"
 
 
-def splat_failures(sp, cam, H, W, outside=False):
-    """[P, 6] bool, per splat, in float64: a per-splat decision inside the margin check_margins asks for -- radius ceil, tile
+def splat_failures(sp, cam, H, W, outside=False, opt=None):
+    """[P, 6] bool ([P, 8] with `opt`, an Options), per splat, in float64: a per-splat decision inside the margin check_margins asks for -- radius ceil, tile
     rect edge, near cull, the 1.3 tan(fov) clamp, a depth key under 4 ulp from (or tied with) that of a different 3D centre,
     opacity in the slack of the 1/255 cut.  These are cleared where the scene is built (Builder.clear), never masked.
     `outside`: also flag what margins() has no word on because the constructed scenes do not have it -- a rect edge within
-    1e-4 of the grid's far side from beyond, and any decision of a splat the float64 forward culls off-screen."""
+    1e-4 of the grid's far side from beyond, and any decision of a splat the float64 forward culls off-screen.
+    With `opt` the 2D state is the options' (the opacity of the 1/255 cut is the antialiased one) and two columns follow: the
+    spherical-harmonic result within 8 bounds of 0 (the `clamped` flag), the antialiasing ratio within 8 bounds (at least
+    1e-3 relative) of its floor 0.000025."""
     tfx, tfy = math.tan(cam.FoVx * 0.5), math.tan(cam.FoVy * 0.5)
     d = lambda v: v.to(DT)
+    kw = {} if opt is None else dict(scale_modifier=opt.scale_modifier, antialiasing=opt.antialiasing,
+                                     cov3D=None if opt.cov3D is None else d(opt.cov3D)[:, COV6])
     px, py, _, opac, tz, cov = (v.numpy() for v in TR.preprocess_2d(
         d(sp["means3D"]), d(sp["opacities"]), d(sp["scales"]), d(sp["rotations"]), d(cam.world_view_transform),
-        d(cam.full_proj_transform), tfx, tfy, H, W))
+        d(cam.full_proj_transform), tfx, tfy, H, W, **kw))
     P = len(tz)
     a, b, c = cov.T
     mid = 0.5 * (a + c)
@@ -864,7 +1308,14 @@ def splat_failures(sp, cam, H, W, outside=False):
                                                               ((py + R + 15) / 16, gy))], 1)
     vis = front & ((rect[:, 2] - rect[:, 0]) * (rect[:, 3] - rect[:, 1]) > 0)
     judged = front if outside else vis
-    fail = np.zeros((P, 6), bool)
+    fail = np.zeros((P, 6 if opt is None else 8), bool)
+    if opt is not None and opt.sh is not None:
+        res, mag = sh_terms(opt.sh, sp["means3D"], cam.camera_center, opt.degree)
+        fail[:, 6] = judged & (np.abs(res) <= 8.0 * K * EPS * mag)
+    if opt is not None and opt.antialiasing:
+        ratio, hrel = aa_terms(cov)
+        with np.errstate(invalid="ignore"):
+            fail[:, 7] = judged & ~(np.abs(ratio - 0.000025) > np.maximum(16.0 * K * EPS * hrel * np.abs(ratio), 0.000025 * 1e-3))
     fail[:, 0] = judged & (np.minimum(np.ceil(rad) - rad, rad - np.floor(rad)) / rad < 1e-5)
     for cc, gmax in ((px, gx), (py, gy)):
         for q in ((cc - R) / 16, (cc + R + 15) / 16):
