@@ -72,11 +72,17 @@ struct ViewEpilogue {
 // (the kernel is bound by exactly those two: VALU issue and LDS return traffic).  Each wave compacts the staged entries
 // its quadrant accepted into a private list and walks it in groups of 16.
 constexpr int GROUP = 16;
-// 6 waves per SIMD (80 VGPRs, a dozen spills): 136 us at the natural 104 VGPRs / 4 waves, 124 at 5, 122 at 6, 128 at 7
+// 7 waves per SIMD: 71 VGPRs without a spill and 22.3 KB of LDS (seven workgroups per CU need <= 72 VGPRs and <= 23,405
+// bytes each).  History: 136 us at the natural 104 VGPRs / 4 waves, 124 at 5, 122 at 6 (80 VGPRs, a dozen spills).  An
+// earlier "128 at 7" point never ran seven waves: with 25.3 KB of LDS per workgroup the CU held six workgroups whatever the
+// register cap, and the compiler, seeing that, dropped the cap altogether (104 VGPRs, four waves).  What made room: the
+// pixel-side matrix operand lives in LDS (s_pix), the wave index is scalar, and the sort's scratch arrays share storage
+// (s_si, s_fmask below).  Measurements: profiles/compositor_occupancy.md.
 #ifndef CGS_FWD3_WAVES
-#define CGS_FWD3_WAVES 6
+#define CGS_FWD3_WAVES 7
 #endif
-// the general (arbitrary colours) instances carry two more accumulators and the last-contributor tracking
+// the general (arbitrary colours) instances carry two more accumulators and the last-contributor tracking; they fit the
+// same budget (71 VGPRs, no spill)
 #ifndef CGS_FWD3_WAVES_GENERAL
 #define CGS_FWD3_WAVES_GENERAL CGS_FWD3_WAVES
 #endif
@@ -84,7 +90,7 @@ constexpr int GROUP = 16;
 #ifndef CGS_FWD_FAST
 #define CGS_FWD_FAST 1
 #endif
-// backward, training configuration: 6 waves per SIMD like the forward (80 VGPRs, 5 spills; 26.2 KB of LDS with the first 104
+// backward, training configuration: 6 waves per SIMD, as the forward had then (80 VGPRs, 5 spills; 26.2 KB of LDS with the first 104
 // list positions of each quadrant parked).  Alone it runs as fast with 5 waves, 95 VGPRs and all 128 positions parked
 // (176 us); with three views in flight the matching footprints let forward and backward workgroups of neighbouring views
 // share CUs evenly: 567 -> 597 Msplats/s.  (A branch-free walk -- eight pairs' exp2 / rcp / colour reads in flight before
@@ -126,8 +132,26 @@ __global__ void __launch_bounds__(256, UNIT ? CGS_FWD3_WAVES : CGS_FWD3_WAVES_GE
     __shared__ __attribute__((aligned(16))) uint32_t s_list[4][BATCH + GROUP];   // per wave: 16 * (staged index + 1); dwords: a
                                                                                  // broadcast read hands the walk ready LDS addresses
     __shared__ __attribute__((aligned(16))) uint32_t s_ord[SORT ? RANK_MAX + RANK_U : 1];
-    __shared__ uint32_t s_si[SORT ? RANK_MAX : 1];
     __shared__ uint32_t s_hist[SORT ? RANK_NB : 1], s_start[SORT ? RANK_NB + 1 : 1], s_mm[8];
+    // Two arrays of the sort live inside others (seven workgroups per CU need <= 23,405 bytes each):
+    //  * s_si, tile_rank_sort's index array (RANK_MAX dwords), is s_list (4 * 272 dwords).  Last read of s_si: inside
+    //    tile_rank_sort, in front of its closing barriers (common.h: the claim pass, or the tie pass's final barrier).
+    //    First write of s_list: the first list build, behind the staging barrier of round 0.  The sort runs once, before
+    //    round 0, so the two lifetimes never meet.
+    //  * s_fmask, the fused path's claim / quadrant-mask array (BATCH dwords), is the upper half of s_ord: the fused path
+    //    keeps its depths in s_ord[0 .. n + RANK_U), n <= BATCH, and touches nothing above.  s_fmask is cleared before
+    //    the path's first barrier, claimed between that barrier and __syncthreads_or, and read by the list build of
+    //    the (only) round of a prestaged tile, which never reads or writes s_ord again.  A tile that falls back to
+    //    tile_rank_sort overwrites all of s_ord behind __syncthreads_or -- and never reads s_fmask.
+    static_assert(!SORT || sizeof(s_list) >= RANK_MAX * sizeof(uint32_t), "s_si lives in s_list");
+    static_assert(RANK_MAX / 2 >= BATCH + RANK_U && RANK_MAX / 2 + BATCH <= RANK_MAX, "s_fmask lives in the upper half of s_ord");
+    uint32_t* const s_si = &s_list[0][0];
+    uint32_t* const s_fmask = s_ord + (SORT ? RANK_MAX / 2 : 0);
+    // the pixel-side matrix operand (p2_mfma.h), one 16-byte row per lane, the same for all four waves: read back at the
+    // head of every group of 16 instead of being held in registers through the walk.  Written here, read behind at least
+    // one workgroup barrier (every path to the walk passes the staging barrier or the fused path's).
+    __shared__ __attribute__((aligned(16))) u32x4 s_pix[64];
+    if (threadIdx.x < 64) s_pix[threadIdx.x] = p2_pixel_operand((int)threadIdx.x).k0;
     if (threadIdx.x == 0) {
         s_geo[BATCH + 1] = make_float4(0.f, 0.f, 0.f, 0.f);
         s_at[BATCH + 1] = make_float4(0.f, 0.f, 0.f, L2_NEVER);
@@ -181,7 +205,7 @@ __global__ void __launch_bounds__(256, UNIT ? CGS_FWD3_WAVES : CGS_FWD3_WAVES_GE
             }
             if (has) s_ord[tid] = depth;
             if (tid < 4u) s_ord[n + tid] = 0x7f800000u;   // +inf padding of the broadcast loop
-            s_si[tid] = 0u;                           // per list position: 0x100 | quadrant mask once claimed
+            s_fmask[tid] = 0u;                        // per list position: 0x100 | quadrant mask once claimed
             __syncthreads();
             uint32_t lost = 0u;
             if (((uint32_t)__builtin_amdgcn_readfirstlane((int)tid) & ~63u) < n) {   // wave-uniform
@@ -195,7 +219,7 @@ __global__ void __launch_bounds__(256, UNIT ? CGS_FWD3_WAVES : CGS_FWD3_WAVES_GE
                     s_at[slot] = make_float4(sb.z, sb.w, sb.x, __builtin_amdgcn_logf(sb.y));
                     if (GEO) s_c[GEO ? slot : 0] = UNIT ? make_float4(rc.x, rc.y, rc.z, sb.w) : rc;
                     const uint32_t qm = quadrant_mask(ra, rb, tau2, X0, Y0);
-                    lost = atomicExch(&s_si[rk[0]], 0x100u | qm);
+                    lost = atomicExch(&s_fmask[rk[0]], 0x100u | qm);
                     bs.point_list[base + rk[0]] = TAG ? (id | (qm << LIST_TAG_SHIFT)) : id;
                 }
             }
@@ -230,12 +254,12 @@ __global__ void __launch_bounds__(256, UNIT ? CGS_FWD3_WAVES : CGS_FWD3_WAVES_GE
     float C = 0.f, Dacc = 0.f;
     float A0 = 0.f, A1 = 0.f, A2 = 0.f, A3 = 0.f;
     bool wave_done = ballot64(cA > -0x1p120f) == 0ull;
-    // matrix-core operands: this lane's pixel monomials (loop invariant), and what its splat-side row stands for
-    const P2Frag pix = p2_pixel_operand(lane);
+    const int wave = __builtin_amdgcn_readfirstlane(g.wave);   // (wave-uniform: what hangs on it stays in scalar registers)
+    // matrix-core operands: what this lane's splat-side row stands for (its pixel monomials, loop invariant, are in s_pix)
     const int row_splat = p2_row_splat(lane);
-    const float hx = X0 + (float)((g.wave & 1) << 3) + 3.5f;
-    const float hy = Y0 + (float)((g.wave >> 1) << 3) + 4.f * (float)p2_row_half(lane) + 1.5f;
-    uint32_t* const list = s_list[g.wave];
+    const float hx = X0 + (float)((wave & 1) << 3) + 3.5f;
+    const float hy = Y0 + (float)((wave >> 1) << 3) + 4.f * (float)p2_row_half(lane) + 1.5f;
+    uint32_t* const list = s_list[wave];
     const char* const geo_bytes = reinterpret_cast<const char*>(s_geo);
     const char* const at_bytes = reinterpret_cast<const char*>(s_at);
     const char* const c_bytes = reinterpret_cast<const char*>(s_c);
@@ -264,7 +288,7 @@ __global__ void __launch_bounds__(256, UNIT ? CGS_FWD3_WAVES : CGS_FWD3_WAVES_GE
 #pragma unroll
             for (int q = 0; q < 4; q++) {
                 const uint64_t bal = ballot64((qm >> q) & 1u);
-                if (lane == 0) s_qmask[q][g.wave] = bal;
+                if (lane == 0) s_qmask[q][wave] = bal;
             }
             __syncthreads();
         }
@@ -273,7 +297,7 @@ __global__ void __launch_bounds__(256, UNIT ? CGS_FWD3_WAVES : CGS_FWD3_WAVES_GE
         int n = 0;
 #pragma unroll
         for (int c = 0; c < 4; c++) {
-            const uint64_t m = prestaged ? ballot64((s_si[SORT ? c * 64 + lane : 0] >> g.wave) & 1u) : uniform64(s_qmask[g.wave][c]);
+            const uint64_t m = prestaged ? ballot64((s_fmask[SORT ? c * 64 + lane : 0] >> wave) & 1u) : uniform64(s_qmask[wave][c]);
             if ((m >> lane) & 1ull) {
                 const int pos = n + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
                 list[pos] = (uint32_t)((c * 64 + lane + 1) * 16);
@@ -293,6 +317,11 @@ __global__ void __launch_bounds__(256, UNIT ? CGS_FWD3_WAVES : CGS_FWD3_WAVES_GE
                 const uint32_t joff = list[g0 + row_splat];
                 const float4 ge = *reinterpret_cast<const float4*>(geo_bytes + joff);
                 const float2 cl = *reinterpret_cast<const float2*>(at_bytes + joff + 8);
+                uint32_t pix_off = (uint32_t)lane * 16u;
+                asm volatile("" : "+v"(pix_off));   // (opaque: the read stays inside the loop)
+                P2Frag pix;
+                pix.k0 = *reinterpret_cast<const u32x4*>(reinterpret_cast<const char*>(s_pix) + pix_off);
+                pix.k1 = u32x4{pix.k0.w >> 16, 0u, 0u, 0u};   // (p2_pixel_operand: k0.w = the third monomial twice)
                 P = p2_mfma(p2_splat_operand(lane, ge.x, ge.y, ge.z, ge.w, cl.x, cl.y, hx, hy), pix);
             }
             const int cnt = min(GROUP, n - g0);

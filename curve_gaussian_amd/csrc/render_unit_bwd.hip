@@ -28,8 +28,9 @@
 
 namespace cgs {
 
+// 7 waves per SIMD: 72 VGPRs without a spill, 19.5 KB of LDS (s_pix: the loop-invariant pixel operands live in LDS)
 #ifndef CGS_UBWD_WAVES
-#define CGS_UBWD_WAVES 6
+#define CGS_UBWD_WAVES 7
 #endif
 constexpr int UB = 256;                 // splats staged per batch (one per thread)
 constexpr int CH = 32;                  // pairs per chunk = columns of one MFMA
@@ -187,6 +188,10 @@ __global__ void __launch_bounds__(256, CGS_UBWD_WAVES) k_render_bwd_unit(
     __shared__ uint32_t s_wcount[4];
     __shared__ uint32_t s_qlast[8];      // [q]: deepest cut of the quadrant, [4 + q]: shallowest
     __shared__ __attribute__((aligned(16))) float s_out[4][CH][8];      // per wave: sums of the chunk's instances
+    // the pixel-side matrix operands of the two 8x4 blocks, one 16-byte row per lane and block, the same for all four waves:
+    // read back per chunk and block instead of being held in twelve registers through the walk.  Written here, read behind
+    // the barrier that follows the per-pixel constants.
+    __shared__ __attribute__((aligned(16))) u32x4 s_pix[2][64];
 
     const TileGeom g = tile_geom(W, H, grid_x);
     const int lane = g.lane;
@@ -225,6 +230,10 @@ __global__ void __launch_bounds__(256, CGS_UBWD_WAVES) k_render_bwd_unit(
             s_qlast[g.wave] = mx;
             s_qlast[4 + g.wave] = mn;
         }
+        if (threadIdx.x < 64) {
+            s_pix[0][threadIdx.x] = ub_pixel_operand((int)threadIdx.x, 0).k0;
+            s_pix[1][threadIdx.x] = ub_pixel_operand((int)threadIdx.x, 1).k0;
+        }
         if (threadIdx.x == 0) {
             s_geo[UB] = make_float4(0.f, 0.f, 0.f, 0.f);
             s_at[UB] = make_float4(0.f, L2_NEVER, 0.f, 0.f);
@@ -240,8 +249,6 @@ __global__ void __launch_bounds__(256, CGS_UBWD_WAVES) k_render_bwd_unit(
     const int nb = min(total, (int)max(max(qmax[0], qmax[1]), max(qmax[2], qmax[3])));   // nothing behind the deepest cut
     const int rounds = (nb + UB - 1) / UB;
 
-    // loop-invariant matrix-core operands (pixel side)
-    const P2Frag pix0 = ub_pixel_operand(lane, 0), pix1 = ub_pixel_operand(lane, 1);
     const int n = lane & 31, hh = lane >> 5;
     const WalkConsts wk = walk_consts();
     float* const outw = &s_out[g.wave][0][0];
@@ -330,9 +337,12 @@ __global__ void __launch_bounds__(256, CGS_UBWD_WAVES) k_render_bwd_unit(
 #pragma unroll
             for (int b = 0; b < 2; b++) {
                 f32x16 P = {};
-                const P2Frag& px = b ? pix1 : pix0;
-                P = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, px.k0), __builtin_bit_cast(bf16x8, bf.k0), P, 0, 0, 0);
-                P = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, pix0.k1), __builtin_bit_cast(bf16x8, bf.k1), P, 0, 0, 0);
+                uint32_t pix_off = (uint32_t)lane * 16u;
+                asm volatile("" : "+v"(pix_off));   // (opaque: the read stays inside the loop)
+                const u32x4 pk0 = *reinterpret_cast<const u32x4*>(reinterpret_cast<const char*>(s_pix[b]) + pix_off);
+                const u32x4 pk1 = u32x4{pk0.x >> 16, 0u, 0u, 0u};   // (ub_pixel_operand: k0.x = the first monomial twice, any block)
+                P = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, pk0), __builtin_bit_cast(bf16x8, bf.k0), P, 0, 0, 0);
+                P = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, pk1), __builtin_bit_cast(bf16x8, bf.k1), P, 0, 0, 0);
                 float r0, r1, r2;
                 const int variant = (slow ? 2 : 0) + (lean ? 1 : 0);   // wave-uniform
 #define CGS_UB_ROW(R)                                                                                        \

@@ -1,5 +1,6 @@
-"""Per-kernel resources (LDS bytes, SGPRs, VGPRs, spills) from the ISA listing hipcc --save-temps leaves behind:
-    cd /tmp/rt && hipcc --offload-arch=gfx950 <Makefile flags> -c <file>.hip --save-temps && python kernel_resources.py *.s [filter]"""
+"""Per-kernel resources (LDS bytes, SGPRs, VGPRs, spills) from the device ISA listing of one source file.  No
+--save-temps litter: compile for the device only, straight to assembly (the Makefile's HIPFLAGS plus -S --cuda-device-only):
+    hipcc $HIPFLAGS -S --cuda-device-only csrc/render.hip -o /tmp/render.s && python kernel_resources.py /tmp/render.s [filter]"""
 import re
 import subprocess
 import sys
