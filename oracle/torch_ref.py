@@ -404,6 +404,17 @@ def edge_aware_loss(image, gt_image, threshold=0.1):
 def knn_mean_dist2(points):
     """Brute-force oracle for simple_knn distCUDA2 (simple_knn.cu:148-184): mean of the 3 smallest squared
     distances to OTHER points (index-distinct; duplicates at distance 0 count)."""
+    return knn_mean_dist2_f64(points).float()
+
+
+def knn_mean_dist2_f64(points):
+    """knn_mean_dist2 before its rounding to float32.  Its accuracy is torch.cdist's: above about 25 points cdist MAY
+    expand |a|^2 + |b|^2 - 2 a.b (compute_mode, by torch version and device) and always takes a square root; the
+    expansion leaves an absolute error of about |x|^2 * 2^-53 in d^2 -- harmless on the unit cube, 1e-3 relative or worse
+    on a tight cluster far from the origin (the cancellation csrc/nn.hip's header warns against).  The torch this was
+    written with keeps float64 on the direct path (4e-16 relative on such a cluster, tests/test_knn_ref64_cpu.py prints
+    it), but nothing promises that.  The version that is float64-accurate by construction (explicit differences, no
+    cdist, no sqrt) is tests/knn_ref64.py::mean_dist2_ref64; the hard clouds are held to that one."""
     P = points.shape[0]
     d2 = torch.cdist(points.double(), points.double()) ** 2
     d2[torch.arange(P), torch.arange(P)] = float("inf")
@@ -412,7 +423,7 @@ def knn_mean_dist2(points):
     if k < 3:
         fmax = torch.full((P, 3 - k), 3.4028234663852886e38, dtype=torch.float64)
         best = torch.cat([best, fmax], 1)
-    return (best.sum(1) / 3.0).float()
+    return best.sum(1) / 3.0
 
 
 # ----------------------------------------------------------------------------- model initialisation
