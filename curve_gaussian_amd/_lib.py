@@ -151,6 +151,7 @@ SIGNATURES = {
     # the siblings with near before the output
     "cgs_mesh_depth_clipped": (_i, [_i, _vp, _i, _vp, _vp, _i, _i, C.c_double, _vp, _vp]),
     "cgs_mesh_contours_clipped": (_i, [_i, _vp, _i, _vp, _vp, _i, _i, _vp, C.c_double, C.c_double, _vp, _vp]),
+    "cgs_surfel_depth": (_i, [_i, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp]),
 }
 
 

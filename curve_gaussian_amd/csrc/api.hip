@@ -154,7 +154,7 @@ static thread_local int64_t g_last_stats[3] = {0, 0, 0};  // num_rendered, longe
 // node cleared the buffer on the first replay only -- later replays ran on stale histograms / partial sums.  A plain kernel
 // node replays correctly, and hipMemsetAsync is a fill kernel anyway.  The edge-map launchers do use it and are not captured:
 // launch_point_mask and launch_edge_score_reduce (edge_score.hip), launch_edge_trace (edge_detect.hip), launch_thin_masks
-// (edge_thin.hip), launch_ray_claims (edge_seed.hip), launch_mesh_depth and launch_point_mask_depth (edge_occlusion.hip), launch_mesh_contours (mesh_contours.hip); so does cgs_segment_merge_labels below for an empty input.
+// (edge_thin.hip), launch_ray_claims (edge_seed.hip), launch_mesh_depth and launch_point_mask_depth (edge_occlusion.hip), launch_mesh_contours (mesh_contours.hip), launch_surfel_depth (surfel_depth.hip); so does cgs_segment_merge_labels below for an empty input.
 __global__ void __launch_bounds__(256) k_zero_words(uint32_t* __restrict__ p, size_t words) {
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < words; i += stride) p[i] = 0u;
@@ -2185,6 +2185,23 @@ int cgs_mesh_contours_clipped(int E, const float* edges, int V, const double* in
         return CGS_ERR_HIP;
     }
     return finish("mesh_contours_clipped", stream_);
+}
+
+// ---- the surfel z-buffer (include/curvegs.h): cgs_mesh_depth's checks in their order; normals may always be NULL.
+int cgs_surfel_depth(int P, const float* points, const float* normals, const float* radii, int V, const double* intr,
+                     const double* w2c, int height, int width, float* depth, void* stream_) {
+    if (P < 0 || V < 0) return reject("cgs_surfel_depth: invalid argument (P=%d, V=%d)", P, V);
+    if (!edt_size_ok(height, width))
+        return reject("cgs_surfel_depth: invalid argument (height=%d, width=%d; sizes lie in [1, %d])", height, width,
+                      CGS_EDT_MAX_SIZE);
+    if (!intr || !w2c || !depth || (P > 0 && (!points || !radii)))
+        return reject("cgs_surfel_depth: invalid argument (NULL pointer; P=%d)", P);
+    if (V == 0) return CGS_OK;   // nothing to write
+    if (launch_surfel_depth((hipStream_t)stream_, P, points, normals, radii, V, intr, w2c, height, width, depth) != hipSuccess) {
+        set_error("cgs_surfel_depth: filling the depth planes failed");
+        return CGS_ERR_HIP;
+    }
+    return finish("surfel_depth", stream_);
 }
 
 }  // extern "C"

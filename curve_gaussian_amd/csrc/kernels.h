@@ -319,4 +319,8 @@ hipError_t launch_mesh_depth_clipped(hipStream_t s, int F, const float* tris, in
 hipError_t launch_mesh_contours_clipped(hipStream_t s, int E, const float* rows, int V, const double* intr, const double* w2c,
                                         int height, int width, const float* depth, double slack, double near, uint8_t* mask);
 
+// surfel_depth.hip (the rule is surfel_depth.h's)
+hipError_t launch_surfel_depth(hipStream_t s, int P, const float* points, const float* normals, const float* radii, int V,
+                               const double* intr, const double* w2c, int height, int width, float* depth);
+
 }  // namespace cgs

@@ -110,6 +110,8 @@ def score_edges(pred, cameras, edge_maps_u8, detector, tolerances_px=(1, 2, 4), 
     else:
         pts_b = pts
     gate.to(backend, device)
+    if ignore_contours and gate.surfels is not None:
+        raise ValueError("score_edges: ignore_contours takes a mesh (a point cloud has no mesh edges to predict contours from)")
     if ignore_contours:
         contour_radius_px = MC._check_radius("score_edges", contour_radius_px)
         contour_rows = MC.edge_rows(gate.tris, "smooth", crease_deg)   # once: the selection is the host's
@@ -369,10 +371,12 @@ def add_gate_arguments(ap):
     """The depth source alone -- --occluder, --near_clip, --depth_dir, --depth_slack, --depth_window --, for the tools that
     have no contour options (the visibility filter and the drawn views); ``check_gate_arguments`` after parsing."""
     ap.add_argument("--occluder", default=None, metavar="FILE",
-                    help="a mesh file inside each scan directory (mesh.ply, .obj): samples hidden behind it are left out")
+                    help="a mesh or point cloud file inside each scan directory (mesh.ply, .obj; a .ply without faces, such as "
+                         "COLMAP's fused.ply, is drawn as disks): samples hidden behind it are left out")
     ap.add_argument("--near_clip", nargs="?", type=float, const=EO.NEAR_CLIP, default=None, metavar="VALUE",
-                    help="with --occluder: clip the mesh at this camera depth instead of dropping a triangle that reaches "
-                         f"behind the camera, for cameras INSIDE the mesh (bare flag: {EO.NEAR_CLIP}, world units; untuned)")
+                    help="with a mesh --occluder: clip the mesh at this camera depth instead of dropping a triangle that reaches "
+                         f"behind the camera, for cameras INSIDE the mesh (bare flag: {EO.NEAR_CLIP}, world units; untuned; "
+                         "an error with a point cloud)")
     ap.add_argument("--depth_dir", default=None, metavar="DIR",
                     help="a directory inside each scan holding <image stem>.npy depth maps (camera z) instead of a mesh")
     ap.add_argument("--depth_slack", type=float, default=EO.DEPTH_SLACK, help="world units behind the surface (untuned)")
@@ -400,7 +404,8 @@ def add_depth_arguments(ap):
     """The depth source of the score (shared with train.py --reprojection_score); without them nothing changes."""
     add_gate_arguments(ap)
     ap.add_argument("--ignore_contours", action="store_true",
-                    help="with --occluder: leave a zone around the mesh's predicted occluding contours out of the score")
+                    help="with a mesh --occluder: leave a zone around the mesh's predicted occluding contours out of the score "
+                         "(an error with a point cloud)")
     ap.add_argument("--contour_radius_px", type=float, default=MC.CONTOUR_RADIUS_PX, help="radius of that zone (untuned)")
     ap.add_argument("--crease_deg", type=float, default=MC.CREASE_DEG,
                     help="mesh edges folded by up to this angle are smooth: candidates for a contour (untuned)")

@@ -4,6 +4,14 @@ reference has no counterpart.
 
   mesh_depth          the mesh rendered into one camera-z plane per view -- a z-buffer, +inf where no triangle covers the
                       pixel centre -- followed by the window maximum
+  surfel_depth        the same planes from an ORIENTED POINT CLOUD, a ``Surfels(points, normals, radii)``: every point a
+                      disk around it, normal to its normal (cgs_surfel_depth; csrc/surfel_depth.hip) -- for a scan made
+                      from photographs, which has COLMAP's fused.ply and neither a mesh nor depth maps.  A disk overhangs
+                      a silhouette by up to its radius, so a cloud hides slightly MORE than the surface it samples
+  surfel_radii        a cloud's radii from its 3 nearest neighbours (cgs_knn_mean_dist2): ``SURFEL_RADIUS_FACTOR`` x the
+                      root of their mean squared distance, capped at ``SURFEL_RADIUS_CAP`` median radii; BOTH UNTUNED
+  read_occluder       what an occluder file holds: triangles (``read_triangle_mesh``), or the ``Surfels`` of a PLY that
+                      has vertices and no faces; write_surfel_ply writes one
   depth_window_max    the maximum over a (2r+1)^2 window clipped to the image: +inf (no surface) wins
   point_masks_depth   ``ops.edge_score.point_masks`` with the gate: a sample the projection keeps is HIDDEN iff
                           c2 > float64(depth[v][floor(v_px)][floor(u_px)]) + slack
@@ -42,6 +50,7 @@ hidden by their own faces where the faces are steep; a larger slack trades that 
 ``DEPTH_WINDOW`` AND ``DEPTH_SLACK`` ARE UNTUNED: only the drawn solids of scene/solid_scan.py have been checked, no real
 scan."""
 import os
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -49,6 +58,10 @@ import torch
 from .. import _lib as L
 from . import edge_score as ES
 
+SURFEL_RADIUS_FACTOR = 1.0       # UNTUNED: a disk's radius over the root of its point's mean squared 3-NN distance; the
+                                 # smallest of (0.6, 0.8, 1.0, 1.2) that leaves no hole in the sampled box and cylinder of
+                                 # tests/test_surfel_depth_cpu.py (profiles/surfel_depth.md)
+SURFEL_RADIUS_CAP = 4.0          # UNTUNED: no radius above this many median radii (a lone outlier has far neighbours)
 MAX_WINDOW = L.DEPTH_MAX_WINDOW
 DEPTH_WINDOW = 1                 # UNTUNED
 DEPTH_SLACK = 2 * 0.0005         # UNTUNED: 2 x edge_extraction.reprojection.SAMPLE_RESOLUTION, in world units
@@ -271,6 +284,186 @@ def mesh_depth(tris, intrinsics, w2c, height, width, window=DEPTH_WINDOW, backen
     return depth_window_max(raw, window, "gpu", dev) if window else raw
 
 
+# ------------------------------------------------------------------------------------------------ surfel z-buffer
+class Surfels(NamedTuple):
+    """An oriented point cloud as an occluder: every point a disk of its own radius around it, normal to its normal."""
+    points: object            # float32 [P,3]
+    normals: object           # float32 [P,3], or None: every disk faces the camera plane of the view that draws it
+    radii: object             # float32 [P], world units
+
+
+def _as_surfels(surfels):
+    """A ``Surfels`` as contiguous float32 tensors (each on the device it is on): (points [P,3], normals [P,3] or None,
+    radii [P])."""
+    def tensor(x):
+        t = x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x, np.float32))
+        return t.detach().to(torch.float32).contiguous()
+    if not isinstance(surfels, Surfels):
+        raise ValueError(f"surfels must be a Surfels(points, normals, radii) (got {type(surfels).__name__})")
+    pts, rad = tensor(surfels.points), tensor(surfels.radii)
+    nrm = None if surfels.normals is None else tensor(surfels.normals)
+    if pts.dim() != 2 or pts.shape[1] != 3:
+        raise ValueError(f"surfels: points must be [P,3] (got {tuple(pts.shape)})")
+    P = int(pts.shape[0])
+    if tuple(rad.shape) != (P,) or (nrm is not None and tuple(nrm.shape) != (P, 3)):
+        raise ValueError(f"surfels: normals must be [{P},3] or None and radii [{P}] (got "
+                         f"{None if nrm is None else tuple(nrm.shape)}, {tuple(rad.shape)})")
+    return pts, nrm, rad
+
+
+SURFEL_HOST_PAIRS = 1 << 21      # (surfel, candidate pixel) pairs the host back end holds at a time
+
+
+def _surfel_zbuffer_host(X, N, R, K, M, height, width):
+    """One view of cgs_surfel_depth in numpy: X float64 [P,3], N float64 [P,3] or None, R float64 [P] (all widened float32);
+    float32 [height,width].  The set-up is vectorised over the surfels and the pixel rule over the (surfel, candidate pixel)
+    pairs of a run of surfels; every operation is elementwise, so the grouping does not show in the bits."""
+    plane = np.full((height, width), np.inf, np.float32)
+    if X.shape[0] == 0:
+        return plane
+    with np.errstate(all="ignore"):
+        c0 = ((M[0] * X[:, 0] + M[1] * X[:, 1]) + M[2] * X[:, 2]) + M[3]
+        c1 = ((M[4] * X[:, 0] + M[5] * X[:, 1]) + M[6] * X[:, 2]) + M[7]
+        c2 = ((M[8] * X[:, 0] + M[9] * X[:, 1]) + M[10] * X[:, 2]) + M[11]
+        if N is None:
+            n0, n1, n2 = np.zeros_like(c0), np.zeros_like(c0), np.ones_like(c0)
+        else:
+            n0 = (M[0] * N[:, 0] + M[1] * N[:, 1]) + M[2] * N[:, 2]
+            n1 = (M[4] * N[:, 0] + M[5] * N[:, 1]) + M[6] * N[:, 2]
+            n2 = (M[8] * N[:, 0] + M[9] * N[:, 1]) + M[10] * N[:, 2]
+        zlo, zhi = c2 - R, c2 + R
+        ok = (R > 0.0) & (zlo > 0.0)
+        a0, b0, a1, b1 = c0 - R, c0 + R, c1 - R, c1 + R
+        ulo = K[0] * np.fmin(a0 / zlo, a0 / zhi) + K[2]      # fmin / fmax: a NaN operand loses, as the device's
+        uhi = K[0] * np.fmax(b0 / zlo, b0 / zhi) + K[2]
+        vlo = K[1] * np.fmin(a1 / zlo, a1 / zhi) + K[3]
+        vhi = K[1] * np.fmax(b1 / zlo, b1 / zhi) + K[3]
+        ok &= ~(np.isnan(ulo) | np.isnan(uhi) | np.isnan(vlo) | np.isnan(vhi))
+        wd, hd = float(width), float(height)
+        jlo = np.fmin(np.fmax(np.ceil(ulo - 0.5), 0.0), wd)
+        jhi = np.fmax(np.fmin(np.floor(uhi - 0.5), wd - 1.0), -1.0)
+        ilo = np.fmin(np.fmax(np.ceil(vlo - 0.5), 0.0), hd)
+        ihi = np.fmax(np.fmin(np.floor(vhi - 0.5), hd - 1.0), -1.0)
+        ok &= (jlo <= jhi) & (ilo <= ihi)
+        num = (n0 * c0 + n1 * c1) + n2 * c2
+        r2 = R * R
+    live = np.flatnonzero(ok)
+    if live.size == 0:
+        return plane
+    j0, i0 = jlo[live].astype(np.int64), ilo[live].astype(np.int64)
+    bw = jhi[live].astype(np.int64) - j0 + 1
+    count = bw * (ihi[live].astype(np.int64) - i0 + 1)
+    flat = plane.reshape(-1)
+    ends = np.cumsum(count)
+    at = 0
+    while at < live.size:
+        # a run of surfels whose boxes hold about SURFEL_HOST_PAIRS pixels together (one surfel at least)
+        stop = max(at + 1, int(np.searchsorted(ends, (ends[at - 1] if at else 0) + SURFEL_HOST_PAIRS, side="right")))
+        n = count[at:stop]
+        rep = np.repeat(np.arange(at, stop), n)
+        local = np.arange(int(n.sum()), dtype=np.int64) - np.repeat(np.cumsum(n) - n, n)
+        row = local // bw[rep]
+        i, j = i0[rep] + row, j0[rep] + (local - row * bw[rep])
+        s_ = live[rep]
+        with np.errstate(all="ignore"):
+            px, py = j.astype(np.float64) + 0.5, i.astype(np.float64) + 0.5
+            dx, dy = (px - K[2]) / K[0], (py - K[3]) / K[1]
+            den = (n0[s_] * dx + n1[s_] * dy) + n2[s_]
+            s = num[s_] / den
+            qx, qy, qz = s * dx - c0[s_], s * dy - c1[s_], s - c2[s_]
+            d2 = (qx * qx + qy * qy) + qz * qz
+            zf = s.astype(np.float32)
+            store = (d2 <= r2[s_]) & (zf > 0.0) & np.isfinite(zf)
+        pix, zf = (i * width + j)[store], zf[store]
+        if pix.size:
+            order = np.argsort(pix, kind="stable")
+            pix, zf = pix[order], zf[order]
+            first = np.flatnonzero(np.r_[True, pix[1:] != pix[:-1]])
+            flat[pix[first]] = np.minimum(flat[pix[first]], np.minimum.reduceat(zf, first))
+        at = stop
+    return plane
+
+
+def surfel_depth(surfels, intrinsics, w2c, height, width, window=DEPTH_WINDOW, backend="gpu", device=None):
+    """``mesh_depth`` for an oriented point cloud: float32 [V,height,width], the camera-z of the nearest disk at every pixel
+    centre (+inf where there is none), then the window maximum of radius ``window`` (0: the plain z-buffer).  ``surfels``: a
+    ``Surfels`` (tensors or arrays); intrinsics [V,4] and w2c [V,3,4] as ``point_masks``.  ``backend="gpu"``:
+    ``cgs_surfel_depth`` and ``cgs_depth_window_max``, the cloud is uploaded when it is not on a GPU, the result stays on the
+    device; ``"host"``: numpy, a CPU tensor, the same bits.  A disk that could reach the camera plane (c2 - r <= 0) is
+    dropped whole: there is no near-plane clipping of disks."""
+    ES._check_backend(backend)
+    height, width = ES._check_size("surfel_depth", height, width)
+    window = _check_window("surfel_depth", window)
+    V, K, M = ES._cameras(intrinsics, w2c)
+    pts, nrm, rad = _as_surfels(surfels)
+    if backend == "host":
+        X = pts.cpu().numpy().astype(np.float64)
+        N = None if nrm is None else nrm.cpu().numpy().astype(np.float64)
+        R = rad.cpu().numpy().astype(np.float64)
+        raw = np.empty((V, height, width), np.float32)
+        for i in range(V):
+            raw[i] = _surfel_zbuffer_host(X, N, R, K[i], M[i], height, width)
+        return torch.from_numpy(_window_max_host(raw, window) if window else raw)
+    dev = ES._device_for([pts, nrm, rad], "surfel_depth", device)
+    with L.device_guard(dev):
+        pts, rad = pts.to(dev), rad.to(dev)
+        nrm = None if nrm is None else nrm.to(dev)
+        raw = torch.empty((V, height, width), dtype=torch.float32, device=dev)
+        if V > 0:
+            Kd, Md = ES.cameras_on(dev, K, M)
+            rc = L.load().cgs_surfel_depth(int(pts.shape[0]), L.ptr(pts), L.ptr(nrm), L.ptr(rad), V, L.ptr(Kd), L.ptr(Md),
+                                           height, width, L.ptr(raw), L.raw_stream(dev))
+            L.check(rc, "cgs_surfel_depth")
+    return depth_window_max(raw, window, "gpu", dev) if window else raw
+
+
+def _knn_mean_dist2_host(pts):
+    """The mean squared distance to the 3 nearest other points, float64 from float32 points, as float32 [P]; +inf with
+    fewer than 4 points, as ``cgs_knn_mean_dist2``.  scipy's k-d tree where there is one, else brute force."""
+    X = np.asarray(pts, np.float32).reshape(-1, 3).astype(np.float64)
+    P = X.shape[0]
+    if P < 4:
+        return np.full((P,), np.inf, np.float32)
+    try:
+        from scipy.spatial import cKDTree
+        d = cKDTree(X).query(X, k=4)[0][:, 1:]             # (itself first, at 0; with exact copies a copy stands in for it)
+        return (d * d).mean(1).astype(np.float32)
+    except ImportError:
+        out = np.empty((P,), np.float32)
+        for a in range(0, P, 1024):
+            d2 = ((X[a:a + 1024, None, :] - X[None, :, :]) ** 2).sum(2)
+            d2[np.arange(d2.shape[0]), np.arange(a, a + d2.shape[0])] = np.inf
+            out[a:a + 1024] = np.sort(d2, 1)[:, :3].mean(1).astype(np.float32)
+        return out
+
+
+def surfel_radii(points, factor=SURFEL_RADIUS_FACTOR, backend="gpu", device=None):
+    """float32 [P] (a host array): ``factor * sqrt(mean_dist2)`` of every point, with mean_dist2 the mean squared distance to
+    its 3 nearest neighbours -- ``cgs_knn_mean_dist2``, the initialiser's kernel, for ``backend="gpu"``; an exact host 3-NN
+    for ``"host"`` --, capped at ``SURFEL_RADIUS_CAP`` x the cloud's median radius: a lone outlier has far neighbours and
+    would otherwise get a giant disk.  The two back ends agree to float32 rounding of mean_dist2, not to the bit.  Fewer than
+    4 points have no 3 neighbours: their radii are +inf, which ``surfel_depth`` skips."""
+    ES._check_backend(backend)
+    factor = float(factor)
+    if not (factor > 0.0 and np.isfinite(factor)):
+        raise ValueError(f"surfel_radii: the factor must be finite and > 0 (got {factor})")
+    pts = points if torch.is_tensor(points) else torch.from_numpy(np.ascontiguousarray(points, np.float32).reshape(-1, 3))
+    if pts.dim() != 2 or pts.shape[1] != 3:
+        raise ValueError(f"points must be [P,3] (got {tuple(pts.shape)})")
+    pts = pts.detach().to(torch.float32)
+    if backend == "host":
+        md2 = _knn_mean_dist2_host(pts.cpu().numpy())
+    else:
+        from ..simple_knn import distCUDA2
+        md2 = distCUDA2(pts.to(ES._device_for([pts], "surfel_radii", device))).cpu().numpy()
+    with np.errstate(all="ignore"):
+        r = factor * np.sqrt(md2.astype(np.float64))
+    finite = r[np.isfinite(r)]
+    if finite.size:
+        r = np.minimum(r, SURFEL_RADIUS_CAP * float(np.median(finite)))
+    return r.astype(np.float32)
+
+
 # ------------------------------------------------------------------------------------------------ the rule on the host
 def hidden_host(c2, u, v, keep, plane, slack):
     """``nv_hidden`` in numpy for one view, the host back ends' one statement of the rule: bool [P], True where a sample that
@@ -413,7 +606,13 @@ class ChunkDepth:
                         "depth_window", and "near_clip" only when it was given; {} when not gated
 
     ``near_clip``: the near plane of ``mesh_depth`` for an occluder the cameras stand INSIDE (None: no clipping, the
-    default); rejected without an occluder."""
+    default); rejected without an occluder.
+
+    The occluder may also be a point cloud: a ``Surfels``, or the path of a PLY with vertices and no faces
+    (``read_occluder``), rendered by ``surfel_depth``.  ``to`` then uploads its three arrays once; radii that the file does
+    not hold are derived once by ``surfel_radii`` on the back end the planes are built on; ``settings()`` also records
+    "occluder_kind": "surfels", "surfels" (the count) and, when the radii were derived, "surfel_radius_factor" -- for a
+    mesh the keys are what they were.  ``near_clip`` with a cloud is a ValueError: a disk is dropped, not cut."""
 
     def __init__(self, what, cameras, occluder=None, depth_maps=None, depth_slack=DEPTH_SLACK, depth_window=DEPTH_WINDOW,
                  near_clip=None):
@@ -426,12 +625,25 @@ class ChunkDepth:
         self.bytes_per_pixel = ES.DEPTH_BYTES_PER_PIXEL if self.gated else 0
         self.slack, self.window = depth_slack, depth_window
         self.occluder, self.tris, self.maps = occluder, None, None
+        self.surfels, self.radius_factor = None, None   # a point-cloud occluder: (points, normals or None, radii) tensors
         self.backend, self.device = "host", None
         if self.gated:
             self.slack = _check_slack(what, depth_slack)
             self.window = _check_window(what, depth_window)
         if occluder is not None:
-            self.tris = _as_tris(read_triangle_mesh(occluder) if isinstance(occluder, (str, os.PathLike)) else occluder)
+            geometry = occluder
+            if isinstance(occluder, (str, os.PathLike)):
+                geometry = read_occluder(occluder, derive_radii=False)   # (radii the file lacks: on the back end of to())
+            if isinstance(geometry, Surfels):
+                if self.near is not None:
+                    raise ValueError(f"{what}: near_clip takes a mesh (a disk that reaches the camera plane is dropped, not cut)")
+                if geometry.radii is None:
+                    self.radius_factor = SURFEL_RADIUS_FACTOR
+                    geometry = geometry._replace(radii=np.zeros((len(geometry.points),), np.float32))
+                self.surfels = _as_surfels(geometry)
+                self._radii_ready = self.radius_factor is None
+            else:
+                self.tris = _as_tris(geometry)
         if depth_maps is not None:
             self.maps = check_depth_maps(cameras, depth_maps)
 
@@ -439,12 +651,20 @@ class ChunkDepth:
         self.backend, self.device = backend, device
         if self.tris is not None and backend == "gpu":
             self.tris = self.tris.to(device)
+        if self.surfels is not None and backend == "gpu":
+            self.surfels = tuple(None if t is None else t.to(device) for t in self.surfels)
         return self
 
     def planes(self, H, W, sel, intr, w2c):
         if self.tris is not None:
             return mesh_depth(self.tris, intr, w2c, H, W, self.window, backend=self.backend, device=self.device,
                               near_clip=self.near)
+        if self.surfels is not None:
+            if not self._radii_ready:   # a cloud file without radii: derived once, on the back end the planes are built on
+                pts, nrm, _ = self.surfels
+                rad = torch.from_numpy(surfel_radii(pts, self.radius_factor, backend=self.backend, device=self.device))
+                self.surfels, self._radii_ready = (pts, nrm, rad.to(pts.device)), True
+            return surfel_depth(Surfels(*self.surfels), intr, w2c, H, W, self.window, backend=self.backend, device=self.device)
         return depth_window_max(np.stack([self.maps[v] for v in sel]), self.window, backend=self.backend, device=self.device)
 
     def settings(self):
@@ -457,6 +677,10 @@ class ChunkDepth:
         out.update({"depth_slack": self.slack, "depth_window": self.window})
         if self.near is not None:
             out["near_clip"] = self.near
+        if self.surfels is not None:
+            out.update({"occluder_kind": "surfels", "surfels": int(self.surfels[0].shape[0])})
+            if self.radius_factor is not None:
+                out["surfel_radius_factor"] = self.radius_factor
         return out
 
 
@@ -600,6 +824,63 @@ def read_triangle_mesh(path):
     if ext == ".ply":
         return _read_ply(path)
     raise ValueError(f"{path}: unknown mesh format {ext!r} (.obj and .ply are read)")
+
+
+def _ply_element_counts(path):
+    """{element name: count} of a PLY file's header."""
+    counts = {}
+    with open(path, "rb") as f:
+        if f.readline().strip() != b"ply":
+            raise ValueError(f"{path}: not a PLY file")
+        for raw in f:
+            tok = raw.decode("ascii", "replace").split()
+            if tok[:1] == ["end_header"]:
+                return counts
+            if tok[:1] == ["element"]:
+                try:
+                    counts[tok[1]] = int(tok[2])
+                except (IndexError, ValueError):
+                    raise ValueError(f"{path}: bad header line {raw!r}") from None
+    raise ValueError(f"{path}: not a PLY file (no end_header)")
+
+
+def read_occluder(path, factor=SURFEL_RADIUS_FACTOR, backend="host", device=None, derive_radii=True):
+    """An occluder file as what ``ChunkDepth`` takes: float32 [F,3,3] triangles of an ``.obj`` or of a ``.ply`` that has
+    faces (``read_triangle_mesh``), or the ``Surfels`` of a ``.ply`` with a vertex element and no face (none, or ``element
+    face 0``) -- a point cloud such as COLMAP's fused.ply: positions from ``x y z``, normals from ``nx ny nz`` when all three
+    are there (else None), radii from a scalar ``radius`` property when there is one, else ``surfel_radii(points, factor,
+    backend, device)`` -- or None with ``derive_radii=False``, for a caller that derives them later."""
+    ext = os.path.splitext(str(path))[1].lower()
+    if ext != ".ply":
+        return read_triangle_mesh(path)
+    counts = _ply_element_counts(path)
+    if "vertex" not in counts or counts.get("face", 0) > 0:
+        return read_triangle_mesh(path)
+    from ..scene.dataset_io import read_ply_table
+    tab = read_ply_table(path)
+    if not all(k in tab and tab[k].dtype.kind == "f" for k in "xyz"):
+        raise ValueError(f"{path}: the vertex element needs float or double x, y, z")
+    column = lambda names: np.ascontiguousarray(np.stack([np.asarray(tab[k], np.float32) for k in names], 1))
+    pts = column("xyz")
+    nrm = column(("nx", "ny", "nz")) if all(k in tab for k in ("nx", "ny", "nz")) else None
+    if "radius" in tab:
+        rad = np.ascontiguousarray(tab["radius"], np.float32)
+    else:
+        rad = surfel_radii(pts, factor, backend=backend, device=device) if derive_radii else None
+    return Surfels(pts, nrm, rad)
+
+
+def write_surfel_ply(path, surfels):
+    """A ``Surfels`` as a binary little-endian PLY of P float vertices -- ``x y z``, ``nx ny nz`` when there are normals,
+    ``radius`` -- and no face element; ``read_occluder`` returns the same float32 bits."""
+    pts, nrm, rad = _as_surfels(surfels)
+    cols = [pts.cpu().numpy()] + ([] if nrm is None else [nrm.cpu().numpy()]) + [rad.cpu().numpy()[:, None]]
+    names = ["x", "y", "z"] + ([] if nrm is None else ["nx", "ny", "nz"]) + ["radius"]
+    head = (f"ply\nformat binary_little_endian 1.0\nelement vertex {pts.shape[0]}\n"
+            + "".join(f"property float {n}\n" for n in names) + "end_header\n")
+    with open(path, "wb") as f:
+        f.write(head.encode("ascii"))
+        f.write(np.ascontiguousarray(np.concatenate(cols, 1), "<f4").tobytes())
 
 
 def write_triangle_ply(path, tris):

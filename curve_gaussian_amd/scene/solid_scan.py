@@ -24,6 +24,9 @@ One shape is seen from INSIDE (``INDOOR_SHAPES``; it is not among ``SHAPES``, wh
               planes are drawn with near-plane clipping (``near_clip = EO.NEAR_CLIP``, ``cgs_mesh_depth_clipped``); without
               it most of the room's triangles are dropped and the gate sees through the walls.
 
+``surfel_cloud`` samples a solid's surface as an oriented point cloud, and ``write_solid_scan(..., cloud=SPACING)`` writes it
+as ``cloud.ply`` beside ``mesh.ply``: the occluder of a scan that has no mesh (``ops.edge_occlusion.read_occluder``).
+
 LIMITS.  By default the maps hold feature edges only (the cylinder's side draws nothing).  With ``contours=True`` they also
 hold the occluding contours of the curved surfaces -- the smooth mesh edges along which a view sees the surface turn away
 (``ops.mesh_contours.contour_masks``, gated by the same planes and slack) -- as a detector would: edges of the image that
@@ -53,6 +56,8 @@ ROOM_RING = (0.5, 0.5, 0.5, 0.3)                          # the eyes: centre x, 
 ROOM_LOOK_DOWN = 0.08                                     # the target lies this far below the eyes' height
 CYLINDER_SIDES = 64
 ARC_HANDLE = 0.5523
+CLOUD_SPACING = 0.01         # the --cloud flag's spacing: the density the surfel gate is checked at (profiles/surfel_depth.md)
+CLOUD_MIN_GAP = 0.75         # surfel_cloud: no two samples nearer than this many spacings
 SAMPLE_RESOLUTION = 0.0005   # edge_extraction.reprojection.SAMPLE_RESOLUTION (that module imports the ops; not imported here)
 
 
@@ -180,12 +185,76 @@ def solid_scan(shape, n_views, H, W, backend="gpu", device=None, slack=EO.DEPTH_
     return SolidScan(tris, edges, synth, cams, maps, raw.cpu().numpy(), hidden.cpu().numpy(), drawn)
 
 
-def write_solid_scan(path, scan, depth=False):
+def surfel_cloud(tris, spacing):
+    """A mesh's surface as an oriented point cloud, what a dense reconstruction would give: (points float32 [P,3], normals
+    float32 [P,3]).  Deterministic, no randomness, in two steps.  CANDIDATES: a grid in barycentric coordinates per
+    triangle -- with a the vertex between the longest side ab and the shortest side ac, the points a + u (b - a) + v (c - a) for
+    u = (i + 0.5) / n1, v = (j + 0.5) / n2, u + v < 1, n1 and n2 the sides' lengths over a third of the spacing, rounded up --
+    each with the face's unit normal (b - a) x (c - a); none lies on a side.  THINNING: the candidates are taken in their
+    order (triangle by triangle, row by row) and one is kept unless a kept one lies nearer than ``CLOUD_MIN_GAP * spacing``.
+    A grid alone is as skewed as its triangle: on the thin triangles of a cylinder's caps and sides it leaves lines of
+    points many times as dense along one direction as along the other, and disks sized by the nearest neighbours
+    (``EO.surfel_radii``) then leave gaps between the lines.  After the thinning no two samples are nearer than that
+    distance and no point of the surface is farther than it, plus a candidate cell, from a sample, whatever the
+    triangulation.  A triangle without area gives nothing."""
+    T = np.asarray(tris, np.float64).reshape(-1, 3, 3)
+    spacing = float(spacing)
+    if not (spacing > 0.0 and math.isfinite(spacing)):
+        raise ValueError(f"surfel_cloud: the spacing must be finite and > 0 (got {spacing})")
+    pts, nrm = [], []
+    for tri in T:
+        normal = np.cross(tri[1] - tri[0], tri[2] - tri[0])
+        length = float(np.linalg.norm(normal))
+        if not length > 0.0:
+            continue
+        sides = [float(np.linalg.norm(tri[(s + 1) % 3] - tri[s])) for s in range(3)]   # side s: vertex s -> vertex s + 1
+        lo, hi = int(np.argmin(sides)), int(np.argmax(sides))
+        if lo == hi:
+            lo = (hi + 2) % 3
+        # a: the vertex the longest and the shortest side share, so that the grid's cells are about as long as wide
+        a = tri[hi] if (hi + 2) % 3 == lo else tri[(hi + 1) % 3]
+        b = tri[(hi + 1) % 3] if (hi + 2) % 3 == lo else tri[hi]
+        c = tri[lo] if (hi + 2) % 3 == lo else tri[(lo + 1) % 3]
+        n1 = max(1, int(math.ceil(3.0 * np.linalg.norm(b - a) / spacing)))
+        n2 = max(1, int(math.ceil(3.0 * np.linalg.norm(c - a) / spacing)))
+        u, v = np.meshgrid((np.arange(n1) + 0.5) / n1, (np.arange(n2) + 0.5) / n2, indexing="ij")
+        inside = (u + v) < 1.0
+        pts.append(a + u[inside][:, None] * (b - a) + v[inside][:, None] * (c - a))
+        nrm.append(np.broadcast_to(normal / length, (pts[-1].shape[0], 3)))
+    if not pts:
+        return np.zeros((0, 3), np.float32), np.zeros((0, 3), np.float32)
+    pts, nrm = np.concatenate(pts), np.concatenate(nrm)
+    gap = CLOUD_MIN_GAP * spacing
+    cell = np.floor(pts / gap).astype(np.int64)
+    kept, grid = [], {}
+    around = [(i, j, k) for i in (-1, 0, 1) for j in (-1, 0, 1) for k in (-1, 0, 1)]
+    rows, cells, gap2 = pts.tolist(), cell.tolist(), gap * gap
+    for n, ((x, y, z), (ci, cj, ck)) in enumerate(zip(rows, cells)):
+        for di, dj, dk in around:
+            for (qx, qy, qz) in grid.get((ci + di, cj + dj, ck + dk), ()):
+                if (x - qx) * (x - qx) + (y - qy) * (y - qy) + (z - qz) * (z - qz) < gap2:
+                    break
+            else:
+                continue
+            break
+        else:
+            grid.setdefault((ci, cj, ck), []).append((x, y, z))
+            kept.append(n)
+    return np.ascontiguousarray(pts[kept], np.float32), np.ascontiguousarray(nrm[kept], np.float32)
+
+
+def write_solid_scan(path, scan, depth=False, cloud=None):
     """The scan in the EMAP layout (``dataset_io.write_emap``, PidiNet maps) plus ``mesh.ply``, ``gt_edges.json`` and, with
-    ``depth``, ``depth/<image stem>.npy`` (the plain z-buffer, float32 camera z, +inf where there is no surface)."""
+    ``depth``, ``depth/<image stem>.npy`` (the plain z-buffer, float32 camera z, +inf where there is no surface).  ``cloud``:
+    a spacing in world units; ``cloud.ply`` is then written beside ``mesh.ply`` -- ``surfel_cloud`` of the mesh at that
+    spacing, with normals and the radii ``EO.surfel_radii`` derives (host back end) --, the occluder a scan without a mesh
+    has.  None (the default) writes no such file, and every other file is the same either way."""
     from .dataset_io import write_emap
     write_emap(path, scan.synth_cameras, [torch.from_numpy(m.astype(np.float32) / 255.0) for m in scan.maps], detector="PidiNet")
     EO.write_triangle_ply(os.path.join(path, "mesh.ply"), scan.tris)
+    if cloud is not None:
+        pts, nrm = surfel_cloud(scan.tris, cloud)
+        EO.write_surfel_ply(os.path.join(path, "cloud.ply"), EO.Surfels(pts, nrm, EO.surfel_radii(pts, backend="host")))
     with open(os.path.join(path, "gt_edges.json"), "w") as f:
         json.dump(scan.edges, f)
     if depth:
@@ -206,10 +275,13 @@ def main(argv=None):
     ap.add_argument("--depth", action="store_true", help="also write depth/<image stem>.npy")
     ap.add_argument("--contours", action="store_true",
                     help="also draw the occluding contours of the curved surfaces into the maps (no 3D edge explains them)")
+    ap.add_argument("--cloud", nargs="?", type=float, const=CLOUD_SPACING, default=None, metavar="SPACING",
+                    help="also write cloud.ply, the solid's surface sampled as an oriented point cloud with radii: the "
+                         f"occluder of a scan that has no mesh (bare flag: a spacing of {CLOUD_SPACING}, world units)")
     ap.add_argument("--backend", choices=("gpu", "host"), default="gpu")
     args = ap.parse_args(argv)
     scan = solid_scan(args.shape, args.views, args.height, args.width, backend=args.backend, contours=args.contours)
-    write_solid_scan(args.out_dir, scan, depth=args.depth)
+    write_solid_scan(args.out_dir, scan, depth=args.depth, cloud=args.cloud)
     print(f"{args.shape}: {len(scan.cameras)} views of {args.width}x{args.height}, {scan.tris.shape[0]} triangles, "
           f"{len(scan.edges['lines_end_pts'])} lines, {len(scan.edges['curves_ctl_pts'])} curves, "
           f"{int(scan.hidden.sum())} hidden samples"

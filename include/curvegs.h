@@ -1578,6 +1578,55 @@ int cgs_mesh_contours_clipped(int E, const float* edges /*[E,4,3]*/, int V, cons
                               const float* depth /*[V,height,width] or NULL*/, double slack, double near,
                               uint8_t* mask_out /*[V,height,width]*/, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Occlusion from an oriented point cloud: every point drawn as a disk (a "surfel") into the camera-z planes that
+ * cgs_mesh_depth draws a mesh into, for scans that have a dense cloud (COLMAP's fused.ply) and no mesh.  The planes then go
+ * through cgs_depth_window_max and gate every operator exactly as a mesh's do.  The reference has no counterpart.  intr, w2c
+ * as for cgs_point_mask.  The rule is frozen -- float64, one rounded operation at a time in the written order, nothing
+ * contracted into an FMA, IEEE division -- so that the numpy back end agrees on every bit.
+ *
+ * cgs_surfel_depth: points is float32 [P,3], device; normals is float32 [P,3], device, or NULL; radii is float32 [P], device
+ * (world units); depth is float32 [V,height,width], device.  The entry fills depth with +inf and then, for every
+ * (surfel, view):
+ *   the point widened to float64, c = R X + T in the operation order of cgs_project_points
+ *   the normal widened to float64, n = R N: per row (r0 * Nx + r1 * Ny) + r2 * Nz, no translation
+ *   with normals == NULL, n = (0, 0, 1): the disk faces the camera plane (for clouds without normals)
+ *   r = (double)radii[p]; the surfel is SKIPPED in the view unless r > 0 and c2 - r > 0 (a NaN fails the test, and so does
+ *     r = +inf): there is no clipping, a disk that could reach the camera plane is dropped whole
+ *   zlo = c2 - r, zhi = c2 + r;  a = c0 - r, b = c0 + r
+ *   ulo = fx * min(a / zlo, a / zhi) + cx,  uhi = fx * max(b / zlo, b / zhi) + cx      (min, max: a NaN operand loses)
+ *   vlo, vhi likewise from c1 - r, c1 + r and fy, cy: the image box of the bounding box of the disk's sphere
+ *   the surfel is SKIPPED if ulo, uhi, vlo or vhi is NaN (that takes a NaN or infinite c0 / c1 or a NaN camera, with which
+ *     no pixel below is covered: the skip changes no output)
+ *   the CANDIDATES are jlo <= j <= jhi, ilo <= i <= ihi, formed as cgs_mesh_depth forms its own:
+ *     jlo = min(max(ceil(ulo - 0.5), 0), width)        jhi = max(min(floor(uhi - 0.5), width - 1), -1)
+ *     ilo = min(max(ceil(vlo - 0.5), 0), height)       ihi = max(min(floor(vhi - 0.5), height - 1), -1)
+ *     all in float64, converted to int after the clamp.  The box is part of the rule, as the triangle's is of the mesh's
+ *   num = (n0 * c0 + n1 * c1) + n2 * c2, once per (surfel, view)
+ *   at the pixel centre (px, py) = (j + 0.5, i + 0.5):
+ *     dx = (px - cx) / fx,  dy = (py - cy) / fy                  (the ray through the centre is (dx, dy, 1) * s)
+ *     den = (n0 * dx + n1 * dy) + n2,  s = num / den             (where the ray meets the disk's plane: its camera z)
+ *     qx = s * dx - c0,  qy = s * dy - c1,  qz = s - c2
+ *     d2 = (qx * qx + qy * qy) + qz * qz;  the pixel is COVERED iff d2 <= r * r
+ *     z = (float)s;  depth[v][i][j] = min(depth[v][i][j], z) if z is a positive finite float; otherwise nothing is stored
+ * The minimum is cgs_mesh_depth's: the integer atomic minimum on the float's bit pattern, behind a plain read.
+ *
+ * CONSEQUENCES.  The disk is two-sided.  The normal need not have unit length: s does not change with its scale (to the
+ * bit for a power of two; in the last bits otherwise, as num and den round on their own).  A zero normal (0 / 0), a grazing
+ * ray (den == 0: s is infinite) and a NaN anywhere store nothing.  The result does not depend on the launch geometry or
+ * on the order of the points.  Limits: no near-plane clipping; a disk overhangs a silhouette by up to its radius and pokes
+ * through the other face at a concave corner, so a cloud hides slightly MORE than the surface it samples; isotropic disks
+ * only; each (surfel, view) costs its candidate box.
+ *
+ * Runs on the caller's stream with no allocation and no host synchronisation.  Every argument is checked, whether or not
+ * there is work: P or V < 0, a size outside [1, CGS_EDT_MAX_SIZE] and NULL pointers (points and radii only when P > 0;
+ * normals may always be NULL) are CGS_ERR_INVALID_ARGUMENT, rejected before anything is launched.  Then V = 0 is a no-op;
+ * P = 0 still fills the planes with +inf.
+ * ------------------------------------------------------------------------------------------------ */
+int cgs_surfel_depth(int P, const float* points /*[P,3]*/, const float* normals /*[P,3] or NULL*/,
+                     const float* radii /*[P]*/, int V, const double* intr /*[V,4]*/, const double* w2c /*[V,12]*/,
+                     int height, int width, float* depth /*[V,height,width]*/, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
