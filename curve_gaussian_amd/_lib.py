@@ -152,6 +152,8 @@ SIGNATURES = {
     "cgs_mesh_depth_clipped": (_i, [_i, _vp, _i, _vp, _vp, _i, _i, C.c_double, _vp, _vp]),
     "cgs_mesh_contours_clipped": (_i, [_i, _vp, _i, _vp, _vp, _i, _i, _vp, C.c_double, C.c_double, _vp, _vp]),
     "cgs_surfel_depth": (_i, [_i, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp]),
+    "cgs_stereo_sweep": (_i, [_i, _i, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, C.c_double, C.c_double, _i, _vp, _vp]),
+    "cgs_stereo_consistency": (_i, [_i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp]),
 }
 
 
@@ -207,6 +209,7 @@ ORIENT_TILE_HEIGHT = 32   # CGS_ORIENT_TILE_HEIGHT
 SNAP_MAX_CAP2 = 64   # CGS_SNAP_MAX_CAP2
 SNAP_TERMS = 10   # CGS_SNAP_TERMS
 DEPTH_MAX_WINDOW = 4   # CGS_DEPTH_MAX_WINDOW
+STEREO_MAX_RADIUS = 8   # CGS_STEREO_MAX_RADIUS
 REPORT_PANELS = ("render", "ground_truth", "depth", "rend_dir", "rend_alpha")   # panel order of cgs_report_panels
 
 _lib = None

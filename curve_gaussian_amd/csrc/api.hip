@@ -2204,4 +2204,44 @@ int cgs_surfel_depth(int P, const float* points, const float* normals, const flo
     return finish("surfel_depth", stream_);
 }
 
+// ---- plane-sweep stereo (include/curvegs.h).  The arrays are the device's: an entry of src outside [0, V) is no source.
+int cgs_stereo_sweep(int V, int height, int width, const uint8_t* gray, const double* intr, int D, const double* inv, int S,
+                     const int* src, const double* rel, int radius, double min_var, double max_cost, int min_sources,
+                     float* depth, void* stream_) {
+    if (V < 0 || !edt_size_ok(height, width))
+        return reject("cgs_stereo_sweep: invalid argument (V=%d, height=%d, width=%d; sizes lie in [1, %d])", V, height, width,
+                      CGS_EDT_MAX_SIZE);
+    if (D < 1 || S < 1 || min_sources < 1)
+        return reject("cgs_stereo_sweep: invalid argument (D=%d, S=%d, min_sources=%d; each is at least 1)", D, S, min_sources);
+    if (radius < 0 || radius > CGS_STEREO_MAX_RADIUS)   // the tile's LDS halo
+        return reject("cgs_stereo_sweep: invalid argument (radius=%d; the radius lies in [0, %d])", radius,
+                      CGS_STEREO_MAX_RADIUS);
+    if (!(min_var >= 0.0) || max_cost != max_cost)
+        return reject("cgs_stereo_sweep: invalid argument (min_var=%g, max_cost=%g; min_var is >= 0, neither is NaN)", min_var,
+                      max_cost);
+    if (!gray || !intr || !inv || !src || !rel || !depth) return reject("cgs_stereo_sweep: invalid argument (NULL pointer)");
+    if (V == 0) return CGS_OK;   // nothing to write
+    launch_stereo_sweep((hipStream_t)stream_, V, height, width, gray, intr, D, inv, S, src, rel, radius, min_var, max_cost,
+                        min_sources, depth);
+    return finish("stereo_sweep", stream_);
+}
+
+int cgs_stereo_consistency(int V, int height, int width, const float* depth, const double* intr, int S, const int* src,
+                           const double* rel, const double* tol, int min_consistent, float* out, void* stream_) {
+    if (V < 0 || !edt_size_ok(height, width))
+        return reject("cgs_stereo_consistency: invalid argument (V=%d, height=%d, width=%d; sizes lie in [1, %d])", V, height,
+                      width, CGS_EDT_MAX_SIZE);
+    if (S < 1 || min_consistent < 0)
+        return reject("cgs_stereo_consistency: invalid argument (S=%d, min_consistent=%d; S is at least 1, min_consistent "
+                      "at least 0)", S, min_consistent);
+    if (!depth || !intr || !src || !rel || !tol || !out) return reject("cgs_stereo_consistency: invalid argument (NULL pointer)");
+    const size_t bytes = (size_t)V * (size_t)height * (size_t)width * sizeof(float);
+    const uintptr_t d0 = reinterpret_cast<uintptr_t>(depth), o0 = reinterpret_cast<uintptr_t>(out);
+    if (d0 < o0 + bytes && o0 < d0 + bytes)   // a pixel reads its sources' planes while their pixels are written
+        return reject("cgs_stereo_consistency: invalid argument (depth and out overlap)");
+    if (V == 0) return CGS_OK;   // nothing to write
+    launch_stereo_consistency((hipStream_t)stream_, V, height, width, depth, intr, S, src, rel, tol, min_consistent, out);
+    return finish("stereo_consistency", stream_);
+}
+
 }  // extern "C"

@@ -323,4 +323,11 @@ hipError_t launch_mesh_contours_clipped(hipStream_t s, int E, const float* rows,
 hipError_t launch_surfel_depth(hipStream_t s, int P, const float* points, const float* normals, const float* radii, int V,
                                const double* intr, const double* w2c, int height, int width, float* depth);
 
+// stereo_depth.hip (the rule is stereo_depth.h's)
+void launch_stereo_sweep(hipStream_t s, int V, int height, int width, const uint8_t* gray, const double* intr, int D,
+                         const double* inv, int S, const int* src, const double* rel, int radius, double min_var,
+                         double max_cost, int min_sources, float* depth);
+void launch_stereo_consistency(hipStream_t s, int V, int height, int width, const float* depth, const double* intr, int S,
+                               const int* src, const double* rel, const double* tol, int min_consistent, float* out);
+
 }  // namespace cgs

@@ -27,6 +27,10 @@ One shape is seen from INSIDE (``INDOOR_SHAPES``; it is not among ``SHAPES``, wh
 ``surfel_cloud`` samples a solid's surface as an oriented point cloud, and ``write_solid_scan(..., cloud=SPACING)`` writes it
 as ``cloud.ply`` beside ``mesh.ply``: the occluder of a scan that has no mesh (``ops.edge_occlusion.read_occluder``).
 
+``photographs`` shades every view from the depth planes with a fixed 3D value-noise texture, and
+``write_solid_scan(..., photos=True)`` writes them as ``color/<rgb_path>``: the input of a scan that has photographs and
+poses only (``edge_detect``, ``stereo_depth``).
+
 LIMITS.  By default the maps hold feature edges only (the cylinder's side draws nothing).  With ``contours=True`` they also
 hold the occluding contours of the curved surfaces -- the smooth mesh edges along which a view sees the surface turn away
 (``ops.mesh_contours.contour_masks``, gated by the same planes and slack) -- as a detector would: edges of the image that
@@ -58,6 +62,8 @@ CYLINDER_SIDES = 64
 ARC_HANDLE = 0.5523
 CLOUD_SPACING = 0.01         # the --cloud flag's spacing: the density the surfel gate is checked at (profiles/surfel_depth.md)
 CLOUD_MIN_GAP = 0.75         # surfel_cloud: no two samples nearer than this many spacings
+PHOTO_BACKGROUND = 128       # photographs: the grey value where a view sees no surface
+PHOTO_OCTAVES = ((12, 4.0), (29, 2.0), (67, 1.0))   # photographs: (lattice cells per world unit, weight) of the value noise
 SAMPLE_RESOLUTION = 0.0005   # edge_extraction.reprojection.SAMPLE_RESOLUTION (that module imports the ops; not imported here)
 
 
@@ -153,17 +159,23 @@ def room_cameras(n_views, H, W):
 
 
 def solid_scan(shape, n_views, H, W, backend="gpu", device=None, slack=EO.DEPTH_SLACK, window=EO.DEPTH_WINDOW,
-               sample_resolution=SAMPLE_RESOLUTION, contours=False, crease_deg=MC.CREASE_DEG, near_clip=None, clip=True):
+               sample_resolution=SAMPLE_RESOLUTION, contours=False, crease_deg=MC.CREASE_DEG, near_clip=None, clip=True,
+               synth_cameras=None):
     """A ``SolidScan`` of ``shape`` seen from ``n_views`` ``synthetic.fibonacci_cameras`` of H x W pixels; ``backend`` as the
     ops (both give the same bytes).  ``contours``: the smooth contours of the mesh (folds up to ``crease_deg``, UNTUNED) are
     OR-ed into the maps as 255, gated by the planes and the slack that gate the feature edges, and kept in ``.contours``;
     without it every byte is what it was.  ``near_clip``: the near plane of the planes and contours, as
     ``mesh_depth`` takes it (None: no clipping for ``SHAPES``, whose cameras stand outside; ``EO.NEAR_CLIP`` for
     ``INDOOR_SHAPES``, whose cameras stand inside).  ``clip=False`` draws an indoor scan WITHOUT clipping, to see what that
-    costs; it is an error with a ``near_clip``."""
+    costs; it is an error with a ``near_clip``.  ``synth_cameras``: ``synthetic.make_camera`` s of H x W pixels to use instead
+    (``n_views`` is then ignored): neighbouring views a few degrees apart, which the default cameras are not."""
     from ..edge_extraction.abc import pred_points_and_directions
     tris, edges = solid_geometry(shape)
-    if shape in INDOOR_SHAPES:
+    if synth_cameras is not None:
+        synth = list(synth_cameras)
+        if shape in INDOOR_SHAPES and clip and near_clip is None:
+            near_clip = EO.NEAR_CLIP
+    elif shape in INDOOR_SHAPES:
         synth = room_cameras(n_views, H, W)
         if not clip and near_clip is not None:
             raise ValueError("solid_scan: clip=False takes no near_clip")
@@ -243,12 +255,73 @@ def surfel_cloud(tris, spacing):
     return np.ascontiguousarray(pts[kept], np.float32), np.ascontiguousarray(nrm[kept], np.float32)
 
 
-def write_solid_scan(path, scan, depth=False, cloud=None):
+def arc_cameras(n_views, H, W, step_deg=8.0, radius=1.8, elevation_deg=25.0, centre=(0.5, 0.5, 0.5)):
+    """``n_views`` ``synthetic.make_camera`` s on an arc around ``centre``, ``step_deg`` apart in azimuth at one elevation, all
+    looking at the centre; z is up.  Neighbours a few degrees apart: what stereo needs and ``fibonacci_cameras`` do not give."""
+    c, el = np.asarray(centre, np.float64), math.radians(float(elevation_deg))
+    cams = []
+    for k in range(int(n_views)):
+        az = math.radians(float(step_deg)) * (k - 0.5 * (int(n_views) - 1)) + math.radians(30.0)
+        eye = c + float(radius) * np.array([math.cos(el) * math.cos(az), math.cos(el) * math.sin(az), math.sin(el)])
+        cams.append(synthetic.make_camera(eye, c, (0.0, 0.0, 1.0), int(H), int(W)))
+    return cams
+
+
+def value_noise(points):
+    """A fixed 3D value-noise texture at float64 world points [...,3], in [0, 1]: per octave of ``PHOTO_OCTAVES`` an integer
+    lattice whose nodes carry a hashed value, interpolated trilinearly; the octaves' weighted mean.  Not periodic within
+    any scene, which sines are: a periodic texture gives plane-sweep stereo false matches."""
+    P = np.asarray(points, np.float64)
+    total, weight = np.zeros(P.shape[:-1]), 0.0
+    for cells, wgt in PHOTO_OCTAVES:
+        q = P * float(cells)
+        q0 = np.floor(q)
+        t = q - q0
+        q0 = q0.astype(np.int64)
+        acc = np.zeros(P.shape[:-1])
+        for dx in (0, 1):
+            for dy in (0, 1):
+                for dz in (0, 1):
+                    h = ((q0[..., 0] + dx) * 73856093) ^ ((q0[..., 1] + dy) * 19349663) ^ ((q0[..., 2] + dz) * 83492791)
+                    h = (h ^ (cells * 2654435761)) & 0xFFFFFFFF
+                    h = ((h ^ (h >> 16)) * 0x45D9F3B) & 0xFFFFFFFF
+                    h = ((h ^ (h >> 16)) * 0x45D9F3B) & 0xFFFFFFFF
+                    h = h ^ (h >> 16)
+                    wx = t[..., 0] if dx else 1.0 - t[..., 0]
+                    wy = t[..., 1] if dy else 1.0 - t[..., 1]
+                    wz = t[..., 2] if dz else 1.0 - t[..., 2]
+                    acc += (h & 0xFFFF).astype(np.float64) / 65535.0 * wx * wy * wz
+        total += wgt * acc
+        weight += wgt
+    return total / weight
+
+
+def photographs(scan):
+    """uint8 [V,H,W]: what a camera would photograph of the textured solid.  A pixel whose depth plane holds a surface is
+    un-projected at its centre to its world point and takes round(255 * ``value_noise``) there; every other pixel is
+    ``PHOTO_BACKGROUND``.  No lighting: a surface point has the same grey value in every view.  Host numpy."""
+    depth = np.asarray(scan.depth, np.float32)
+    V, H, W = depth.shape
+    out = np.full((V, H, W), PHOTO_BACKGROUND, np.uint8)
+    for v, c in enumerate(scan.cameras):
+        z = depth[v].astype(np.float64)
+        hit = np.isfinite(z) & (z > 0.0)
+        i, j = np.nonzero(hit)
+        zc = z[i, j]
+        cam = np.stack([((j + 0.5) - c.cx) / c.fx * zc, ((i + 0.5) - c.cy) / c.fy * zc, zc], 1)
+        world = (cam - np.asarray(c.T, np.float64)) @ np.asarray(c.R, np.float64)   # R^T (c - T), row vectors
+        out[v, i, j] = np.rint(255.0 * np.clip(value_noise(world), 0.0, 1.0)).astype(np.uint8)
+    return out
+
+
+def write_solid_scan(path, scan, depth=False, cloud=None, photos=False):
     """The scan in the EMAP layout (``dataset_io.write_emap``, PidiNet maps) plus ``mesh.ply``, ``gt_edges.json`` and, with
     ``depth``, ``depth/<image stem>.npy`` (the plain z-buffer, float32 camera z, +inf where there is no surface).  ``cloud``:
     a spacing in world units; ``cloud.ply`` is then written beside ``mesh.ply`` -- ``surfel_cloud`` of the mesh at that
     spacing, with normals and the radii ``EO.surfel_radii`` derives (host back end) --, the occluder a scan without a mesh
-    has.  None (the default) writes no such file, and every other file is the same either way."""
+    has.  None (the default) writes no such file, and every other file is the same either way.  ``photos``: also
+    ``color/<rgb_path>``, the view's ``photographs`` as an 8-bit grey PNG; without it no such folder is written and every
+    other file is the same either way."""
     from .dataset_io import write_emap
     write_emap(path, scan.synth_cameras, [torch.from_numpy(m.astype(np.float32) / 255.0) for m in scan.maps], detector="PidiNet")
     EO.write_triangle_ply(os.path.join(path, "mesh.ply"), scan.tris)
@@ -257,6 +330,11 @@ def write_solid_scan(path, scan, depth=False, cloud=None):
         EO.write_surfel_ply(os.path.join(path, "cloud.ply"), EO.Surfels(pts, nrm, EO.surfel_radii(pts, backend="host")))
     with open(os.path.join(path, "gt_edges.json"), "w") as f:
         json.dump(scan.edges, f)
+    if photos:
+        from PIL import Image
+        os.makedirs(os.path.join(path, "color"), exist_ok=True)
+        for c, p in zip(scan.cameras, photographs(scan)):
+            Image.fromarray(p, mode="L").save(os.path.join(path, "color", c.name))
     if depth:
         os.makedirs(os.path.join(path, "depth"), exist_ok=True)
         for c, d in zip(scan.cameras, scan.depth):
@@ -278,10 +356,17 @@ def main(argv=None):
     ap.add_argument("--cloud", nargs="?", type=float, const=CLOUD_SPACING, default=None, metavar="SPACING",
                     help="also write cloud.ply, the solid's surface sampled as an oriented point cloud with radii: the "
                          f"occluder of a scan that has no mesh (bare flag: a spacing of {CLOUD_SPACING}, world units)")
+    ap.add_argument("--photos", action="store_true",
+                    help="also write color/<rgb_path>: photographs of the solid under a fixed value-noise texture")
+    ap.add_argument("--arc", nargs="?", type=float, const=8.0, default=None, metavar="DEGREES",
+                    help="cameras on an arc this many degrees apart instead of spread over the sphere (bare flag: 8): "
+                         "neighbouring views close enough for stereo")
     ap.add_argument("--backend", choices=("gpu", "host"), default="gpu")
     args = ap.parse_args(argv)
-    scan = solid_scan(args.shape, args.views, args.height, args.width, backend=args.backend, contours=args.contours)
-    write_solid_scan(args.out_dir, scan, depth=args.depth, cloud=args.cloud)
+    arc = None if args.arc is None else arc_cameras(args.views, args.height, args.width, args.arc)
+    scan = solid_scan(args.shape, args.views, args.height, args.width, backend=args.backend, contours=args.contours,
+                      synth_cameras=arc)
+    write_solid_scan(args.out_dir, scan, depth=args.depth, cloud=args.cloud, photos=args.photos)
     print(f"{args.shape}: {len(scan.cameras)} views of {args.width}x{args.height}, {scan.tris.shape[0]} triangles, "
           f"{len(scan.edges['lines_end_pts'])} lines, {len(scan.edges['curves_ctl_pts'])} curves, "
           f"{int(scan.hidden.sum())} hidden samples"

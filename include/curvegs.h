@@ -1627,6 +1627,72 @@ int cgs_surfel_depth(int P, const float* points /*[P,3]*/, const float* normals 
                      const float* radii /*[P]*/, int V, const double* intr /*[V,4]*/, const double* w2c /*[V,12]*/,
                      int height, int width, float* depth /*[V,height,width]*/, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Depth maps from a scan's own photographs: plane-sweep stereo, for scans that have photographs and poses and neither a
+ * mesh, a dense cloud nor depth maps.  One camera-z map per view, 0 where stereo gives nothing -- the format the caller's
+ * depth maps have (ops.edge_occlusion.check_depth_maps turns <= 0 into +inf: the gate fails open).  The reference has no
+ * counterpart.  The rule is frozen -- float64, one rounded operation at a time in the written order, nothing contracted
+ * into an FMA, IEEE division, NO square root, every sum a running sum from 0.0 in the stated order -- so that the numpy
+ * back end (ops/stereo_depth.py) agrees on every bit.  It is stated once for the kernels, in csrc/stereo_depth.h.
+ *
+ * Inputs, all device arrays.  gray: uint8 [V,height,width] luminance.  intr: [V,4] doubles fx, fy, cx, cy.  inv: [V,D]
+ * doubles, the inverse depths of view v's hypotheses.  src: int32 [V,S], the source views of reference view v; an entry
+ * outside [0, V) (-1 by convention) is no source.  rel: [V,S,12] doubles, row-major [R | T] taking reference-camera
+ * coordinates to the source's camera coordinates.  inv, src and rel are made by the host, so both back ends read the same
+ * bits.  Scalars: the patch radius R, min_var, max_cost, min_sources.  n = (2R+1)^2 as a double; thr = (min_var * n) * n.
+ *
+ * cgs_stereo_sweep, reference pixel (i, j) of view v; depth[v][i][j] is written exactly once, by a plain store:
+ *   0 unless the whole patch lies inside the image: i - R >= 0, i + R <= height - 1, j - R >= 0, j + R <= width - 1
+ *   taps k in row-major order (di = -R..R outer, dj = -R..R inner); r_k = (double)gray[v][i+di][j+dj]
+ *   sr = sum r_k, srr = sum r_k * r_k, var_r = n * srr - sr * sr;  0 unless var_r > thr
+ *   hypothesis d = 0..D-1: z = 1.0 / inv[v][d].  Source s = 0..S-1 in order, skipped when src[v][s] is no source; with
+ *   w = src[v][s], M = rel[v][s] and (fx', fy', cx', cy') = intr[w], per tap:
+ *     px = (j + dj) + 0.5, py = (i + di) + 0.5;  X = ((px - cx) / fx) * z,  Y = ((py - cy) / fy) * z    (intr[v])
+ *     c = M (X, Y, z): per row ((m0 * X + m1 * Y) + m2 * z) + m3, the operation order of cgs_project_points
+ *     the tap is INVALID if !(c2 > 0);  u = fx' * (c0 / c2) + cx',  v = fy' * (c1 / c2) + cy'
+ *     x = u - 0.5, y = v - 0.5, x0 = floor(x), y0 = floor(y); INVALID unless 0 <= x0, x0 + 1 <= width - 1, 0 <= y0,
+ *       y0 + 1 <= height - 1, compared in float64 (a NaN or an infinity is invalid)
+ *     a = x - x0, b = y - y0;  g00 = gray[w][y0][x0], g01 = gray[w][y0][x0+1], g10 = gray[w][y0+1][x0], g11 likewise
+ *     top = g00 * (1 - a) + g01 * a,  bot = g10 * (1 - a) + g11 * a,  val = top * (1 - b) + bot * b
+ *     ss += val, sss += val * val, srs += r_k * val
+ *   the source COUNTS for d iff every tap is valid and var_s = n * sss - ss * ss > thr; then
+ *     cov = n * srs - sr * ss;  score = (cov * fabs(cov)) / (var_r * var_s);  cost_s = 1 - score
+ *     (score is the signed square of the normalised cross-correlation, in [-1, 1] up to rounding)
+ *   cost[d] = (sum of cost_s over the counting sources, in source order) / (double)count; +inf when count < min_sources
+ *   WINNER: best = the d of the smallest cost, a strict < keeping the lowest d on a tie; cb = cost[best];
+ *     0 unless cb is finite and cb <= max_cost
+ *   REFINEMENT: o = 0 unless 0 < best < D - 1, cm = cost[best-1] and cp = cost[best+1] are finite and
+ *     den = (cm - 2 * cb) + cp > 0; then o = (0.5 * (cm - cp)) / den, clamped to [-0.5, 0.5]
+ *     q = inv[v][best] + o * (o >= 0 ? inv[v][best+1] - inv[v][best] : inv[v][best] - inv[v][best-1]), and q = inv[v][best]
+ *     itself when o == 0 (an end has no neighbour to read);  depth[v][i][j] = (float)(1.0 / q)
+ * CONSEQUENCES.  D = 1: the one hypothesis wins when its cost is finite and <= max_cost, unrefined.  D = 2: the cheaper of
+ * the two (d = 0 on a tie), unrefined: both are ends.  R = 0: one tap has no variance (var_r = r * r - r * r = 0), so every
+ * pixel stores 0; matching starts at R = 1.  den = (cm - cb) + (cp - cb) is > 0 for finite costs around a strict minimum;
+ * the test guards the division, and at its edge (cp == cb) o is 0.5, the clamp's end.  A source whose pose or depth holds
+ * a NaN never counts.  The cost volume is never stored.
+ *
+ * cgs_stereo_consistency, pixel (i, j) of view v with z = (double)depth[v][i][j]; out[v][i][j] is written exactly once:
+ *   0 unless z > 0 (a NaN fails).  Otherwise X = (((j + 0.5) - cx) / fx) * z, Y = (((i + 0.5) - cy) / fy) * z and, per
+ *   source as above, c = M (X, Y, z); the source AGREES iff c2 > 0, (u, v) formed as above lies in the image
+ *   (0 <= u < width, 0 <= v < height: cgs_point_mask_depth's test), ds = (double)depth[w][floor(v)][floor(u)] > 0 and
+ *   fabs(1.0 / ds - 1.0 / c2) <= tol[v], tol a double per view.  out[v][i][j] = depth[v][i][j], the same bits, when at
+ *   least min_consistent sources agree, and 0 otherwise.  depth and out must not overlap: a pixel reads other views.
+ *
+ * Both run on the caller's stream with no allocation, no atomics and no host synchronisation; the result does not depend
+ * on the launch geometry.  Every argument is checked whether or not there is work: V < 0, a size outside
+ * [1, CGS_EDT_MAX_SIZE], D < 1, S < 1, a radius outside [0, CGS_STEREO_MAX_RADIUS], min_var negative or NaN, a NaN
+ * max_cost, min_sources < 1, min_consistent < 0, NULL pointers and overlapping depth / out are
+ * CGS_ERR_INVALID_ARGUMENT, rejected before anything is launched.  Then V = 0 is a no-op.
+ * ------------------------------------------------------------------------------------------------ */
+#define CGS_STEREO_MAX_RADIUS 8
+int cgs_stereo_sweep(int V, int height, int width, const uint8_t* gray /*[V,height,width]*/, const double* intr /*[V,4]*/,
+                     int D, const double* inv /*[V,D]*/, int S, const int* src /*[V,S]*/, const double* rel /*[V,S,12]*/,
+                     int radius, double min_var, double max_cost, int min_sources,
+                     float* depth /*[V,height,width]*/, void* stream);
+int cgs_stereo_consistency(int V, int height, int width, const float* depth /*[V,height,width]*/,
+                           const double* intr /*[V,4]*/, int S, const int* src /*[V,S]*/, const double* rel /*[V,S,12]*/,
+                           const double* tol /*[V]*/, int min_consistent, float* out /*[V,height,width]*/, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
