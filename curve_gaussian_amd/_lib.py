@@ -154,6 +154,10 @@ SIGNATURES = {
     "cgs_surfel_depth": (_i, [_i, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp]),
     "cgs_stereo_sweep": (_i, [_i, _i, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, C.c_double, C.c_double, _i, _vp, _vp]),
     "cgs_stereo_consistency": (_i, [_i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp]),
+    # (V, height, width, depth, intr, F, fsrc, into, v0, nv, warped, stream)
+    "cgs_stereo_warp": (_i, [_i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp]),
+    # (V, height, width, depth, F, warped, tol, min_support, v0, nv, out, support, stream)
+    "cgs_stereo_fuse": (_i, [_i, _i, _i, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
 }
 
 
@@ -210,6 +214,7 @@ SNAP_MAX_CAP2 = 64   # CGS_SNAP_MAX_CAP2
 SNAP_TERMS = 10   # CGS_SNAP_TERMS
 DEPTH_MAX_WINDOW = 4   # CGS_DEPTH_MAX_WINDOW
 STEREO_MAX_RADIUS = 8   # CGS_STEREO_MAX_RADIUS
+STEREO_MAX_FUSE = 16   # CGS_STEREO_MAX_FUSE
 REPORT_PANELS = ("render", "ground_truth", "depth", "rend_dir", "rend_alpha")   # panel order of cgs_report_panels
 
 _lib = None

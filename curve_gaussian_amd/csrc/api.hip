@@ -2244,4 +2244,50 @@ int cgs_stereo_consistency(int V, int height, int width, const float* depth, con
     return finish("stereo_consistency", stream_);
 }
 
+// ---- fusing the stereo maps (include/curvegs.h).  The checks the two entries share: the sizes, the range, F.
+static bool fuse_shape_ok(int V, int height, int width, int F, int v0, int nv) {
+    return V >= 0 && edt_size_ok(height, width) && F >= 1 && F <= CGS_STEREO_MAX_FUSE && v0 >= 0 && nv >= 0 && v0 <= V &&
+           nv <= V - v0;
+}
+static bool ranges_overlap(const void* a, size_t abytes, const void* b, size_t bbytes) {
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+    return abytes > 0 && bbytes > 0 && a0 < b0 + bbytes && b0 < a0 + abytes;
+}
+
+int cgs_stereo_warp(int V, int height, int width, const float* depth, const double* intr, int F, const int* fsrc,
+                    const double* into, int v0, int nv, float* warped, void* stream_) {
+    if (!fuse_shape_ok(V, height, width, F, v0, nv))
+        return reject("cgs_stereo_warp: invalid argument (V=%d, height=%d, width=%d, F=%d, v0=%d, nv=%d; sizes lie in [1, %d], "
+                      "F in [1, %d], the range in [0, V])", V, height, width, F, v0, nv, CGS_EDT_MAX_SIZE, CGS_STEREO_MAX_FUSE);
+    if (!depth || !intr || !fsrc || !into || !warped) return reject("cgs_stereo_warp: invalid argument (NULL pointer)");
+    const size_t plane = (size_t)height * (size_t)width * sizeof(float);
+    if (ranges_overlap(depth, (size_t)V * plane, warped, (size_t)nv * (size_t)F * plane))
+        return reject("cgs_stereo_warp: invalid argument (depth and warped overlap)");
+    if (nv == 0) return CGS_OK;   // nothing to write
+    if (launch_stereo_warp((hipStream_t)stream_, V, height, width, depth, intr, F, fsrc, into, v0, nv, warped) != hipSuccess) {
+        set_error("cgs_stereo_warp: filling the warped planes failed");
+        return CGS_ERR_HIP;
+    }
+    return finish("stereo_warp", stream_);
+}
+
+int cgs_stereo_fuse(int V, int height, int width, const float* depth, int F, const float* warped, const double* tol,
+                    int min_support, int v0, int nv, float* out, uint8_t* support, void* stream_) {
+    if (!fuse_shape_ok(V, height, width, F, v0, nv))
+        return reject("cgs_stereo_fuse: invalid argument (V=%d, height=%d, width=%d, F=%d, v0=%d, nv=%d; sizes lie in [1, %d], "
+                      "F in [1, %d], the range in [0, V])", V, height, width, F, v0, nv, CGS_EDT_MAX_SIZE, CGS_STEREO_MAX_FUSE);
+    if (min_support < 1) return reject("cgs_stereo_fuse: invalid argument (min_support=%d; it is at least 1)", min_support);
+    if (!depth || !warped || !tol || !out) return reject("cgs_stereo_fuse: invalid argument (NULL pointer)");
+    const size_t pixels = (size_t)height * (size_t)width, plane = pixels * sizeof(float);
+    const size_t dbytes = (size_t)V * plane, wbytes = (size_t)nv * (size_t)F * plane, obytes = (size_t)nv * plane;
+    if (ranges_overlap(out, obytes, depth, dbytes) || ranges_overlap(out, obytes, warped, wbytes) ||
+        (support && (ranges_overlap(support, (size_t)nv * pixels, depth, dbytes) ||
+                     ranges_overlap(support, (size_t)nv * pixels, warped, wbytes) ||
+                     ranges_overlap(support, (size_t)nv * pixels, out, obytes))))
+        return reject("cgs_stereo_fuse: invalid argument (the outputs overlap an input or each other)");
+    if (nv == 0) return CGS_OK;   // nothing to write
+    launch_stereo_fuse((hipStream_t)stream_, height, width, depth, F, warped, tol, min_support, v0, nv, out, support);
+    return finish("stereo_fuse", stream_);
+}
+
 }  // extern "C"

@@ -330,4 +330,10 @@ void launch_stereo_sweep(hipStream_t s, int V, int height, int width, const uint
 void launch_stereo_consistency(hipStream_t s, int V, int height, int width, const float* depth, const double* intr, int S,
                                const int* src, const double* rel, const double* tol, int min_consistent, float* out);
 
+// stereo_fuse.hip (the rule is stereo_fuse.h's)
+hipError_t launch_stereo_warp(hipStream_t s, int V, int height, int width, const float* depth, const double* intr, int F,
+                              const int* fsrc, const double* into, int v0, int nv, float* warped);
+void launch_stereo_fuse(hipStream_t s, int height, int width, const float* depth, int F, const float* warped,
+                        const double* tol, int min_support, int v0, int nv, float* out, uint8_t* support);
+
 }  // namespace cgs

@@ -10,15 +10,21 @@ hides nothing, so the gate fails open wherever stereo is unsure.
   sweep            the winner-take-all sweep of a planned group: float32 [V,H,W]
   consistency      the cross-view filter of a swept group
   stereo_depth     photographs and cameras in, one map per view out
+  plan_fusion      the host's decisions for fusing a group's maps: each target's fusion sources, the poses that take a
+                   source's camera coordinates INTO the target's, and plan_views' tolerance
+  warp, fuse       cgs_stereo_warp / cgs_stereo_fuse on a range of targets of a planned group
+  fuse_depth       maps and cameras in, one fused map per view out (``stereo_depth(..., fuse=True)`` chains the two)
 
 The rule is frozen in include/curvegs.h -- float64, one rounded operation at a time, no square root, running sums -- and
-stated once for the kernels in csrc/stereo_depth.h.  Two back ends: ``"gpu"``, HIP, and ``"host"``, numpy written operation
-for operation (numpy evaluates one rounded operation per ufunc call), so the two agree BIT FOR BIT, and so does the brute
+stated once for the kernels in csrc/stereo_depth.h and csrc/stereo_fuse.h.  Two back ends: ``"gpu"``, HIP, and ``"host"``,
+numpy written operation for operation (numpy evaluates one rounded operation per ufunc call), so the two agree BIT FOR BIT, and so does the brute
 force of tests/stereo_cases.py.
 
 WHAT THIS IS NOT.  Fronto-parallel patches on one scale of grey values: no patch-match propagation, no slanted planes, no
-colour, no fusion of the maps.  EVERY DEFAULT BELOW IS UNTUNED: only the drawn solids of scene/solid_scan.py with their
-value-noise photographs have been checked -- no real photograph, no lighting change, no specular or textureless surface."""
+colour.  The fusion (OFF BY DEFAULT) works in map space: per pixel the largest cluster of agreeing inverse depths among the
+own depth and the sources' warped ones, stored as its mean -- no fused point cloud, no second sweep.  EVERY DEFAULT BELOW
+IS UNTUNED: only the drawn solids of scene/solid_scan.py with their value-noise photographs have been checked -- no real
+photograph, no lighting change, no specular or textureless surface."""
 import math
 from typing import NamedTuple
 
@@ -40,6 +46,10 @@ MIN_SOURCES = 1             # UNTUNED
 CONSISTENCY_STEPS = 1.5     # UNTUNED: sources agree within this many hypothesis steps of inverse depth
 MIN_CONSISTENT = 2          # UNTUNED
 BOUNDS = ((0.0, 0.0, 0.0), (1.0, 1.0, 1.0))
+MAX_FUSE = L.STEREO_MAX_FUSE
+FUSE_SOURCES = 7            # UNTUNED: what the numpy prototype of the fusion used
+FUSE_SUPPORT = 3            # UNTUNED: likewise; the own depth counts
+FUSE_CHUNK_BYTES = 1 << 30  # the warped planes of the targets fused at once stay under this (at least one target)
 
 
 def luminance(image):
@@ -73,6 +83,13 @@ def relative_pose(R_ref, T_ref, R_src, T_src):
     Rel = Rs @ Rr.T
     t = np.asarray(T_src, np.float64) - Rel @ np.asarray(T_ref, np.float64)
     return np.concatenate([Rel, t[:, None]], 1).reshape(12)
+
+
+def _nearest_views(v, centres, axes, cos_max, count):
+    """The ``count`` nearest camera centres among the other views whose optical axes lie within the angle of view v's."""
+    d2 = ((centres - centres[v]) ** 2).sum(1)
+    cand = [w for w in range(len(centres)) if w != v and float(axes[w] @ axes[v]) >= cos_max]
+    return sorted(cand, key=lambda w: d2[w])[:count]   # (sorted is stable: ties stay in index order)
 
 
 class Plan(NamedTuple):
@@ -116,9 +133,7 @@ def plan_views(cameras, bounds=BOUNDS, hypotheses=HYPOTHESES, sources=SOURCES, m
             continue
         inv[v] = np.linspace(1.0 / z_near[v], 1.0 / z_far[v], D) if D > 1 else 1.0 / z_near[v]
         tol[v] = float(consistency_steps) * abs(inv[v][1] - inv[v][0]) if D > 1 else 0.0
-        d2 = ((centres - centres[v]) ** 2).sum(1)
-        cand = [w for w in range(V) if w != v and float(axes[w] @ axes[v]) >= cos_max]
-        cand = sorted(cand, key=lambda w: d2[w])[:S]   # (sorted is stable: ties stay in index order)
+        cand = _nearest_views(v, centres, axes, cos_max, S)
         if len(cand) < max(int(min_sources), int(min_consistent), 1):
             continue
         usable[v] = True
@@ -126,6 +141,37 @@ def plan_views(cameras, bounds=BOUNDS, hypotheses=HYPOTHESES, sources=SOURCES, m
             src[v, s] = w
             rel[v, s] = relative_pose(Rm[v], Tm[v], Rm[w], Tm[w])
     return Plan(K, inv, src, rel, tol, z_near, z_far, usable)
+
+
+def _check_fuse_params(what, fuse_sources, min_support):
+    F, N = int(fuse_sources), int(min_support)
+    if not 1 <= F <= MAX_FUSE or N < 1:
+        raise ValueError(f"{what}: fuse_sources must lie in [1, {MAX_FUSE}] and min_support be at least 1 (got {F}, {N})")
+    return F, N
+
+
+def plan_fusion(cameras, bounds=BOUNDS, hypotheses=HYPOTHESES, fuse_sources=FUSE_SOURCES, max_angle_deg=MAX_ANGLE_DEG,
+                consistency_steps=CONSISTENCY_STEPS):
+    """(K [V,4], fsrc int32 [V,F], into [V,F,12], tol [V]) of same-size ``NovelViewCamera`` s, as cgs_stereo_warp and
+    cgs_stereo_fuse take them.  fsrc: target v's ``fuse_sources`` nearest camera centres within ``max_angle_deg``, chosen as
+    ``plan_views`` chooses (ties to the lower index, -1 pads) -- however few there are.  into[v][s] takes the SOURCE's camera
+    coordinates to the TARGET's: ``relative_pose(R_w, T_w, R_v, T_v)``, the other direction than the sweep's ``rel``.  K and tol
+    are those of ``plan_views`` for the same bounds, hypotheses and consistency_steps."""
+    cams = list(cameras)
+    F, _ = _check_fuse_params("plan_fusion", fuse_sources, 1)
+    plan = plan_views(cams, bounds, hypotheses, 1, max_angle_deg, consistency_steps, 1, 0)
+    V = len(cams)
+    Rm = [np.asarray(c.R, np.float64).reshape(3, 3) for c in cams]
+    Tm = [np.asarray(c.T, np.float64).reshape(3) for c in cams]
+    centres = np.array([-(R.T @ T) for R, T in zip(Rm, Tm)], np.float64).reshape(V, 3)
+    axes = np.array([R[2] / np.linalg.norm(R[2]) for R in Rm], np.float64).reshape(V, 3)
+    cos_max = math.cos(math.radians(float(max_angle_deg)))
+    fsrc, into = np.full((V, F), -1, np.int32), np.zeros((V, F, 12), np.float64)
+    for v in range(V):
+        for s, w in enumerate(_nearest_views(v, centres, axes, cos_max, F)):
+            fsrc[v, s] = w
+            into[v, s] = relative_pose(Rm[w], Tm[w], Rm[v], Tm[v])
+    return plan.K, fsrc, into, plan.tol
 
 
 # ------------------------------------------------------------------------------------------------ the host back end
@@ -322,11 +368,200 @@ def consistency(depth, intrinsics, src, rel, tol, min_consistent=MIN_CONSISTENT,
     return out
 
 
+# ------------------------------------------------------------------------------------------------ fusion: the host back end
+def _is_depth(a):
+    """A positive finite float32: what the fusion takes for a depth."""
+    with np.errstate(invalid="ignore"):
+        return (a > 0.0) & np.isfinite(a)
+
+
+def _warp_slot_host(src_map, Kw, Kv, M, plane):
+    """One source's map into one slot's plane (float32 [H,W], +inf where nothing has landed), in place."""
+    H, W = src_map.shape
+    with np.errstate(all="ignore"):
+        ok = _is_depth(src_map)
+        z = src_map.astype(np.float64)
+        X = (((np.arange(W, dtype=np.float64) + 0.5) - Kw[2]) / Kw[0])[None, :] * z
+        Y = (((np.arange(H, dtype=np.float64) + 0.5) - Kw[3]) / Kw[1])[:, None] * z
+        c0 = ((M[0] * X + M[1] * Y) + M[2] * z) + M[3]
+        c1 = ((M[4] * X + M[5] * Y) + M[6] * z) + M[7]
+        c2 = ((M[8] * X + M[9] * Y) + M[10] * z) + M[11]
+        u = Kv[0] * (c0 / c2) + Kv[2]
+        vv = Kv[1] * (c1 / c2) + Kv[3]
+        ok &= ~(c2 <= 0.0) & (u >= 0.0) & (u < float(W)) & (vv >= 0.0) & (vv < float(H))
+        zf = c2.astype(np.float32)
+        ok &= _is_depth(zf)
+        at = np.floor(vv[ok]).astype(np.int64) * W + np.floor(u[ok]).astype(np.int64)
+    np.minimum.at(plane.reshape(-1), at, zf[ok])   # (positive floats order as their bit patterns do)
+
+
+def _fuse_view_host(own, warped, tol, min_support):
+    """(out float32 [H,W], support uint8 [H,W]) of one target: own [H,W], warped [F,H,W]."""
+    F = warped.shape[0]
+    with np.errstate(all="ignore"):
+        vals = np.concatenate([own[None], warped], 0)
+        q = np.where(_is_depth(vals), 1.0 / vals.astype(np.float64), np.nan)    # an absent candidate fails every comparison
+        sb, qb = np.full(own.shape, -1, np.int64), np.full(own.shape, np.nan)
+        for k in range(F + 1):
+            cnt = np.zeros(own.shape, np.int64)
+            for m in range(F + 1):
+                cnt += np.abs(q[m] - q[k]) <= tol
+            better = ~np.isnan(q[k]) & ((cnt > sb) | ((cnt == sb) & (q[k] < qb)))
+            sb, qb = np.where(better, cnt, sb), np.where(better, q[k], qb)
+        total, count = np.zeros(own.shape), np.zeros(own.shape, np.int64)
+        for m in range(F + 1):
+            member = np.abs(q[m] - qb) <= tol
+            total = np.where(member, total + q[m], total)
+            count += member
+        keep = sb >= min_support
+        out = np.where(keep, (1.0 / (total / count)).astype(np.float32), np.float32(0.0)).astype(np.float32)
+    return out, np.where(keep, count, 0).astype(np.uint8)
+
+
+# ------------------------------------------------------------------------------------------------ fusion: the two entries
+def _as_maps(what, depth):
+    d = depth if torch.is_tensor(depth) else torch.from_numpy(np.ascontiguousarray(depth))
+    if d.dtype != torch.float32 or d.dim() != 3:
+        raise ValueError(f"{what}: depth must be float32 [V,H,W] (got {d.dtype} {tuple(d.shape)})")
+    return d.detach().contiguous()
+
+
+def _check_range(what, V, v0, nv):
+    v0, nv = int(v0), int(nv)
+    if not (0 <= v0 <= V and 0 <= nv <= V - v0):
+        raise ValueError(f"{what}: the targets v0 .. v0 + nv must lie in [0, {V}] (got v0={v0}, nv={nv})")
+    return v0, nv
+
+
+def warp(depth, intrinsics, fsrc, into, v0=0, nv=None, backend="gpu", device=None):
+    """cgs_stereo_warp on the targets v0 .. v0 + nv - 1 (all from v0 on when ``nv`` is None) of a group: depth float32
+    [V,H,W], intrinsics [V,4], fsrc int32 [V,F], into [V,F,12] (``plan_fusion``) -> float32 [nv,F,H,W]: per slot the source's
+    depths where they land in the target, the nearest of those that share a pixel, +inf where none lands."""
+    ES._check_backend(backend)
+    d = _as_maps("stereo warp", depth)
+    V = int(d.shape[0])
+    K = np.ascontiguousarray(np.asarray(intrinsics, np.float64).reshape(-1, 4))
+    fsrc = np.ascontiguousarray(np.asarray(fsrc, np.int32))
+    if K.shape != (V, 4) or fsrc.ndim != 2 or fsrc.shape[0] != V or not 1 <= fsrc.shape[1] <= MAX_FUSE:
+        raise ValueError(f"stereo warp: intrinsics must be [{V},4] and fsrc int32 [{V},F], 1 <= F <= {MAX_FUSE} (got {K.shape}, "
+                         f"{fsrc.shape})")
+    F = int(fsrc.shape[1])
+    into = np.ascontiguousarray(np.asarray(into, np.float64).reshape(V, F, 12))
+    v0, nv = _check_range("stereo warp", V, v0, V - int(v0) if nv is None else nv)
+    H, W = ES._check_size("stereo warp", d.shape[1], d.shape[2])
+    if backend == "host":
+        a = d.cpu().numpy()
+        out = np.full((nv, F, H, W), np.inf, np.float32)
+        for t in range(nv):
+            for s in range(F):
+                w = int(fsrc[v0 + t, s])
+                if 0 <= w < V:
+                    _warp_slot_host(a[w], K[w], K[v0 + t], into[v0 + t, s], out[t, s])
+        return torch.from_numpy(out)
+    dev = ES._device_for([d], "stereo warp", device)
+    with L.device_guard(dev):
+        d = d.to(dev)
+        out = torch.empty((nv, F, H, W), dtype=torch.float32, device=dev)
+        if nv > 0:
+            Kd, srcd, intod = (torch.from_numpy(a).to(dev) for a in (K, fsrc, into))
+            rc = L.load().cgs_stereo_warp(V, H, W, L.ptr(d), L.ptr(Kd), F, L.ptr(srcd), L.ptr(intod), v0, nv, L.ptr(out),
+                                          L.raw_stream(dev))
+            L.check(rc, "cgs_stereo_warp")
+    return out
+
+
+def fuse(depth, warped, tol, min_support=FUSE_SUPPORT, v0=0, backend="gpu", device=None, return_support=False):
+    """cgs_stereo_fuse on the targets v0 .. v0 + nv - 1 of a group: depth float32 [V,H,W], warped float32 [nv,F,H,W]
+    (``warp`` of the same range), tol [V] -> float32 [nv,H,W]: per pixel the mean inverse depth of the largest cluster among
+    the own depth and the warped ones, as a depth; 0 where the cluster has fewer than ``min_support`` members.
+    ``return_support``: also uint8 [nv,H,W], the cluster's size (0 where the map is 0)."""
+    ES._check_backend(backend)
+    d = _as_maps("stereo fuse", depth)
+    w = warped if torch.is_tensor(warped) else torch.from_numpy(np.ascontiguousarray(warped))
+    V = int(d.shape[0])
+    if w.dtype != torch.float32 or w.dim() != 4 or tuple(w.shape[2:]) != tuple(d.shape[1:]) or not 1 <= w.shape[1] <= MAX_FUSE:
+        raise ValueError(f"stereo fuse: warped must be float32 [nv,F,{d.shape[1]},{d.shape[2]}], 1 <= F <= {MAX_FUSE} (got "
+                         f"{w.dtype} {tuple(w.shape)})")
+    w = w.detach().contiguous()
+    F, min_support = _check_fuse_params("stereo fuse", w.shape[1], min_support)
+    tol = np.ascontiguousarray(np.asarray(tol, np.float64).reshape(-1))
+    if tol.shape != (V,):
+        raise ValueError(f"stereo fuse: tol must be [{V}] (got {tol.shape})")
+    v0, nv = _check_range("stereo fuse", V, v0, w.shape[0])
+    H, W = ES._check_size("stereo fuse", d.shape[1], d.shape[2])
+    if backend == "host":
+        a, b = d.cpu().numpy(), w.cpu().numpy()
+        out, sup = np.zeros((nv, H, W), np.float32), np.zeros((nv, H, W), np.uint8)
+        for t in range(nv):
+            out[t], sup[t] = _fuse_view_host(a[v0 + t], b[t], tol[v0 + t], min_support)
+        return (torch.from_numpy(out), torch.from_numpy(sup)) if return_support else torch.from_numpy(out)
+    dev = ES._device_for([d, w], "stereo fuse", device)
+    with L.device_guard(dev):
+        d, w = d.to(dev), w.to(dev)
+        out = torch.empty((nv, H, W), dtype=torch.float32, device=dev)
+        sup = torch.empty((nv, H, W), dtype=torch.uint8, device=dev) if return_support else None
+        if nv > 0:
+            told = torch.from_numpy(tol).to(dev)
+            rc = L.load().cgs_stereo_fuse(V, H, W, L.ptr(d), F, L.ptr(w), L.ptr(told), min_support, v0, nv, L.ptr(out),
+                                          L.ptr(sup) if return_support else None, L.raw_stream(dev))
+            L.check(rc, "cgs_stereo_fuse")
+    return (out, sup) if return_support else out
+
+
+def fuse_depth(maps, cameras, bounds=BOUNDS, hypotheses=HYPOTHESES, max_angle_deg=MAX_ANGLE_DEG,
+               consistency_steps=CONSISTENCY_STEPS, fuse_sources=FUSE_SOURCES, min_support=FUSE_SUPPORT, backend="gpu",
+               device=None, return_info=False):
+    """One fused float32 [H,W] numpy map of camera z per camera, 0 where there is none.  maps: one float [H,W] array per
+    camera, of its camera's size, in which only a positive finite entry is a depth (``stereo_depth``'s maps, or the
+    caller's own).  Views are grouped by size as ``stereo_depth`` groups them, a group is planned by ``plan_fusion`` and its
+    targets are walked in chunks whose warped planes stay under ``FUSE_CHUNK_BYTES``; the result does not depend on the
+    chunks.  A pixel's cluster counts its own depth, so a view without sources keeps nothing at ``min_support`` > 1.
+    OFF BY DEFAULT in ``stereo_depth``; ``fuse_sources`` and ``min_support`` are UNTUNED.
+
+    ``return_info``: also a dict with "coverage_before" and "coverage" (per view, the share of pixels that hold a depth
+    before and after), "support_histogram" (entry n: the pixels whose cluster has n members, n = 0 .. fuse_sources + 1),
+    "filled" (pixels without a depth that got one) and "dropped" (pixels that lost theirs)."""
+    ES._check_backend(backend)
+    cams, own = list(cameras), [ES._host(m) for m in maps]
+    if len(cams) != len(own):
+        raise ValueError(f"fuse_depth: {len(cams)} cameras and {len(own)} depth maps")
+    F, min_support = _check_fuse_params("fuse_depth", fuse_sources, min_support)
+    for c, m in zip(cams, own):
+        if m.dtype.kind != "f" or m.shape != (c.height, c.width):
+            raise ValueError(f"fuse_depth: the depth map of {c.name} must be a float [{c.height},{c.width}] array "
+                             f"(got {m.dtype} {m.shape})")
+    groups = {}
+    for v, c in enumerate(cams):
+        groups.setdefault((int(c.height), int(c.width)), []).append(v)
+    fused, hist = [None] * len(cams), np.zeros(F + 2, np.int64)
+    for (H, W), idx in groups.items():
+        K, fsrc, into, tol = plan_fusion([cams[v] for v in idx], bounds, hypotheses, F, max_angle_deg, consistency_steps)
+        depth = torch.from_numpy(np.stack([own[v].astype(np.float32) for v in idx]))
+        if backend == "gpu":
+            depth = depth.to(ES._device_for([depth], "fuse_depth", device))
+        step = max(1, int(FUSE_CHUNK_BYTES) // (F * H * W * 4))
+        for v0 in range(0, len(idx), step):
+            nv = min(step, len(idx) - v0)
+            warped = warp(depth, K, fsrc, into, v0, nv, backend, device)
+            out, sup = fuse(depth, warped, tol, min_support, v0, backend, device, return_support=True)
+            out, sup = out.cpu().numpy(), sup.cpu().numpy()
+            hist += np.bincount(sup.reshape(-1), minlength=F + 2)[:F + 2]
+            for k in range(nv):
+                fused[idx[v0 + k]] = out[k]
+    if not return_info:
+        return fused
+    had = [_is_depth(m.astype(np.float32)) for m in own]
+    return fused, {"coverage_before": [float(h.mean()) for h in had], "coverage": [float((m > 0).mean()) for m in fused],
+                   "support_histogram": [int(n) for n in hist],
+                   "filled": int(sum((~h & (m > 0)).sum() for h, m in zip(had, fused))),
+                   "dropped": int(sum((h & ~(m > 0)).sum() for h, m in zip(had, fused)))}
+
+
 # ------------------------------------------------------------------------------------------------ photographs in, maps out
 def stereo_depth(gray_u8, cameras, bounds=BOUNDS, hypotheses=HYPOTHESES, patch_radius=PATCH_RADIUS, sources=SOURCES,
                  max_angle_deg=MAX_ANGLE_DEG, min_var=MIN_VAR, max_cost=MAX_COST, min_sources=MIN_SOURCES,
                  consistency_steps=CONSISTENCY_STEPS, min_consistent=MIN_CONSISTENT, backend="gpu", device=None,
-                 return_info=False):
+                 return_info=False, fuse=False, fuse_sources=FUSE_SOURCES, min_support=FUSE_SUPPORT):
     """One float32 [H,W] numpy map of camera z per camera, 0 where there is none.  gray_u8: one uint8 [H,W] luminance image
     per camera (``luminance``), each of its camera's size; cameras: ``NovelViewCamera`` s.  Views are grouped by size and a
     group is planned by ``plan_views`` (sources are views of the same size), swept and filtered; a view that is not swept
@@ -336,13 +571,19 @@ def stereo_depth(gray_u8, cameras, bounds=BOUNDS, hypotheses=HYPOTHESES, patch_r
     ``return_info``: also a dict with "coverage" (per view, the share of pixels given a depth), "swept" (per view),
     "depth_step_max" -- the largest z^2 * |inv[1] - inv[0]| over the swept views at their far ends, what one hypothesis step
     is in depth -- and "recommended_slack" = 2 * depth_step_max: the gate's default slack (0.001) is far below what stereo
-    resolves, so a gate fed these maps wants this slack instead."""
+    resolves, so a gate fed these maps wants this slack instead.
+
+    ``fuse`` (OFF BY DEFAULT): the filtered maps go through ``fuse_depth`` with ``fuse_sources`` and ``min_support`` (both
+    UNTUNED) before they are returned; "coverage" is then the fused maps' and "fusion" holds ``fuse_depth``'s dict.
+    "recommended_slack" is what it is without."""
     ES._check_backend(backend)
     cams, imgs = list(cameras), [ES._host(g) for g in gray_u8]
     if len(cams) != len(imgs):
         raise ValueError(f"stereo_depth: {len(cams)} cameras and {len(imgs)} photographs")
     D, R, S, min_var, max_cost, min_sources, min_consistent = _check_params(
         "stereo_depth", hypotheses, patch_radius, sources, min_var, max_cost, min_sources, min_consistent)
+    if fuse:
+        _check_fuse_params("stereo_depth", fuse_sources, min_support)
     for c, g in zip(cams, imgs):
         if g.dtype != np.uint8 or g.shape != (c.height, c.width):
             raise ValueError(f"stereo_depth: the photograph of {c.name} must be uint8 [{c.height},{c.width}] "
@@ -365,7 +606,14 @@ def stereo_depth(gray_u8, cameras, bounds=BOUNDS, hypotheses=HYPOTHESES, patch_r
             maps[v], swept[v] = z[k], bool(plan.usable[k])
             if plan.usable[k] and D > 1:
                 step_max = max(step_max, float(plan.z_far[k] ** 2 * abs(plan.inv[k][1] - plan.inv[k][0])))
+    fusion = None
+    if fuse:
+        maps, fusion = fuse_depth(maps, cams, bounds, D, max_angle_deg, consistency_steps, fuse_sources, min_support, backend,
+                                  device, return_info=True)
     if not return_info:
         return maps
-    return maps, {"coverage": [float((m > 0).mean()) for m in maps], "swept": [bool(s) for s in swept],
-                  "depth_step_max": step_max, "recommended_slack": 2.0 * step_max}
+    info = {"coverage": [float((m > 0).mean()) for m in maps], "swept": [bool(s) for s in swept],
+            "depth_step_max": step_max, "recommended_slack": 2.0 * step_max}
+    if fuse:
+        info["fusion"] = fusion
+    return maps, info

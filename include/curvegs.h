@@ -1693,6 +1693,66 @@ int cgs_stereo_consistency(int V, int height, int width, const float* depth /*[V
                            const double* intr /*[V,4]*/, int S, const int* src /*[V,S]*/, const double* rel /*[V,S,12]*/,
                            const double* tol /*[V]*/, int min_consistent, float* out /*[V,height,width]*/, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Fusing the stereo depth maps across views.  cgs_stereo_consistency uses the other views only to DELETE depths; a pixel
+ * that its own view failed to match stays empty although every other view that saw the same surface holds its depth.
+ * cgs_stereo_warp carries every source's map into the target view, cgs_stereo_fuse keeps, per pixel, the largest cluster
+ * of agreeing inverse depths (the own depth included) and stores the cluster's mean.  The output is again one camera-z
+ * map per view, 0 where there is none.  The reference has no counterpart.  The rule is frozen with the conventions of the
+ * sweep above -- float64, one rounded operation at a time in the written order, nothing contracted, IEEE division, no
+ * square root, running sums from 0.0 in the stated order -- and stated once for the kernels, in csrc/stereo_fuse.h.
+ *
+ * Inputs, all device arrays, made by the host so that both back ends read the same bits.  depth: float32
+ * [V,height,width].  intr: [V,4] doubles.  fsrc: int32 [V,F], the fusion sources of TARGET view v; an entry outside [0, V)
+ * is no source.  into: [V,F,12] doubles, row-major [R | T] taking the SOURCE's camera coordinates to the TARGET's (the
+ * sweep's rel goes the other way).  tol: [V] doubles, the consistency tolerance in inverse depth.  Both entries take a
+ * range of targets v0 <= v < v0 + nv with 0 <= v0 and v0 + nv <= V, so that the intermediate stays bounded; a DEPTH below
+ * is a positive finite float (a NaN, an infinity, zero and negative values are none).
+ *
+ * cgs_stereo_warp, output warped float32 [nv,F,height,width].  The entry first fills warped with +inf.  Then for every
+ * target v of the range, every slot s with a source w = fsrc[v][s], and every source pixel (i, j):
+ *   skip unless depth[w][i][j] is a depth; z = (double)depth[w][i][j]
+ *   X = (((j + 0.5) - cx_w) / fx_w) * z,  Y = (((i + 0.5) - cy_w) / fy_w) * z                            (intr[w])
+ *   c = M (X, Y, z), M = into[v][s]: per row ((m0 * X + m1 * Y) + m2 * z) + m3, the operation order of cgs_project_points
+ *   skip unless c2 > 0;  u = fx_v * (c0 / c2) + cx_v,  v' = fy_v * (c1 / c2) + cy_v                        (intr[v])
+ *   skip unless 0 <= u < width and 0 <= v' < height (cgs_point_mask_depth's test; a NaN fails)
+ *   zf = (float)c2; if zf is a depth: warped[v-v0][s][floor(v')][floor(u)] = min(what it holds, zf)
+ *   (the integer atomic minimum on the float's bit pattern behind a plain read, as cgs_mesh_depth stores)
+ * The result does not depend on the launch geometry or the order.  depth and warped must not overlap.
+ *
+ * cgs_stereo_fuse, outputs out float32 [nv,height,width] and support uint8 [nv,height,width] (may be NULL); each pixel is
+ * written exactly once, by plain stores, no atomics.  Pixel (i, j) of target v:
+ *   candidates k = 0..F: k = 0 is present iff depth[v][i][j] is a depth, k = s + 1 iff warped[v-v0][s][i][j] is one;
+ *     q_k = 1.0 / (double)value
+ *   support_k = the number of present m (k itself included) with fabs(q_m - q_k) <= tol[v]
+ *   WINNER: there is no best at first; scanning k upward, a present k replaces the best iff there is none yet, or
+ *     support_k > support_best, or support_k == support_best and q_k < q_best -- the FARTHER candidate wins a tie, the
+ *     side on which a gate errs safely; the lowest k stays on a full tie
+ *   0 (and support 0) when no candidate is present or support_best < min_support
+ *   otherwise sum = the running sum of q_m over the present m = 0..F in order with fabs(q_m - q_best) <= tol[v], count
+ *     their number; mean = sum / (double)count; out = (float)(1.0 / mean); support = (uint8_t)count
+ * CONSEQUENCES.  The fused map holds NEW values: every cluster of two or more stores a mean, and even where only the own
+ * depth supports itself the stored number is (float)(1 / (1 / z)), not a copy (its two float64 roundings lie far inside
+ * half a float32 step, so it has z's bits again).  A NaN tol stores 0 everywhere (no candidate supports even itself), and so does a negative one; tol = 0 clusters
+ * equal inverse depths only; tol = +inf makes every present candidate a member.  min_support > F + 1 stores 0
+ * everywhere.  Two source pixels landing on one target pixel keep the nearer.  A point that is visible in the source and
+ * hidden in the target lands BEHIND the target's surface: it loses to the cluster, or alone it yields a far depth; both
+ * fail open.  support never saturates: F + 1 <= 17.
+ *
+ * Both run on the caller's stream with no allocation and no host synchronisation.  Every argument is checked whether or
+ * not there is work: V < 0, a size outside [1, CGS_EDT_MAX_SIZE], a range outside [0, V], F outside
+ * [1, CGS_STEREO_MAX_FUSE], min_support < 1, NULL pointers (support excepted) and overlapping buffers (warped with depth;
+ * out or support with depth, warped or each other) are CGS_ERR_INVALID_ARGUMENT, rejected before anything is launched.
+ * Then nv = 0 is a no-op.
+ * ------------------------------------------------------------------------------------------------ */
+#define CGS_STEREO_MAX_FUSE 16
+int cgs_stereo_warp(int V, int height, int width, const float* depth /*[V,height,width]*/, const double* intr /*[V,4]*/,
+                    int F, const int* fsrc /*[V,F]*/, const double* into /*[V,F,12]*/, int v0, int nv,
+                    float* warped /*[nv,F,height,width]*/, void* stream);
+int cgs_stereo_fuse(int V, int height, int width, const float* depth /*[V,height,width]*/, int F,
+                    const float* warped /*[nv,F,height,width]*/, const double* tol /*[V]*/, int min_support, int v0, int nv,
+                    float* out /*[nv,height,width]*/, uint8_t* support /*[nv,height,width] or NULL*/, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
