@@ -70,6 +70,17 @@ static int finish(const char* what, void* stream_) {
     return check_launch(what, false, (hipStream_t)stream_) ? CGS_OK : CGS_ERR_HIP;
 }
 
+// ---- the entries with a depth-gated (_depth) or near-clipped (_clipped) sibling (include/curvegs.h).  Each pair has one
+// <op>_entry that holds the checks once: `name` is the entry that was called, `gate` is NULL for the ungated entry and `near`
+// is NULL for the unclipped one.  The gate's own checks are cgs_point_mask_depth's: a finite slack >= 0 and a depth pointer.
+static bool slack_ok(double slack) { return slack >= 0.0 && !std::isinf(slack); }   // a NaN fails the comparison
+static bool near_ok(double near) { return near > 0.0 && !std::isinf(near); }        // a NaN fails the comparison
+static bool slack_bad(const DepthGate* gate) { return gate && !slack_ok(gate->slack); }
+static bool depth_missing(const DepthGate* gate) { return gate && !gate->depth; }
+static int reject_slack(const char* name, const DepthGate* gate) {
+    return reject("%s: invalid argument (slack=%g; the slack is finite and >= 0)", name, gate->slack);
+}
+
 // Binning capacity hints, one set per workload shape (P, width, height): a process that alternates train and test cameras,
 // two resolutions or two models keeps a separate history for each instead of thrashing one (each mismatch used to cost a
 // bucket overflow and an exact-path redo).  Small LRU table behind a mutex; the three numbers of an entry:
@@ -1291,21 +1302,37 @@ int cgs_nn1(int n_query, const float* query, int n_ref, const float* ref, float*
     return finish("nn1", stream_);
 }
 
+// The slack comes right after the counts, the depth pointer among the pointers of the frames.
+static int edge_visibility_entry(const char* name, int n_curves, const double* curves, int n_lines, const double* lines,
+                                 int n_frames, const double* K, const double* w2c, int height, int width,
+                                 const unsigned char* maps, int invert, const DepthGate* gate, int* counts, void* stream_) {
+    if (n_curves < 0 || n_lines < 0 || n_frames < 0 || (long long)n_curves + n_lines > (1 << 30))
+        return reject("%s: invalid argument (n_curves=%d, n_lines=%d, n_frames=%d)", name, n_curves, n_lines, n_frames);
+    if (slack_bad(gate)) return reject_slack(name, gate);
+    if (n_curves + n_lines == 0) return CGS_OK;
+    if (n_frames > 0 && (height <= 0 || width <= 0))
+        return reject("%s: invalid argument (height=%d, width=%d)", name, height, width);
+    if ((n_curves > 0 && !curves) || (n_lines > 0 && !lines) || !counts ||
+        (n_frames > 0 && (!K || !w2c || !maps || depth_missing(gate))))
+        return reject("%s: invalid argument (NULL pointer)", name);
+    launch_edge_visibility((hipStream_t)stream_, n_curves, curves, n_lines, lines, n_frames, K, w2c, height, width, maps,
+                           invert, gate, counts);
+    return finish(name + 4, stream_);   // the label is the entry's name without its cgs_
+}
+
 int cgs_edge_visibility(int n_curves, const double* curves, int n_lines, const double* lines, int n_frames,
                         const double* K, const double* w2c, int height, int width, const unsigned char* maps,
                         int invert, int* counts, void* stream_) {
-    if (n_curves < 0 || n_lines < 0 || n_frames < 0 || (long long)n_curves + n_lines > (1 << 30))
-        return reject("cgs_edge_visibility: invalid argument (n_curves=%d, n_lines=%d, n_frames=%d)", n_curves, n_lines,
-                      n_frames);
-    if (n_curves + n_lines == 0) return CGS_OK;
-    if (n_frames > 0 && (height <= 0 || width <= 0))
-        return reject("cgs_edge_visibility: invalid argument (height=%d, width=%d)", height, width);
-    if ((n_curves > 0 && !curves) || (n_lines > 0 && !lines) || !counts ||
-        (n_frames > 0 && (!K || !w2c || !maps)))
-        return reject("cgs_edge_visibility: invalid argument (NULL pointer)");
-    launch_edge_visibility((hipStream_t)stream_, n_curves, curves, n_lines, lines, n_frames, K, w2c, height, width,
-                           maps, invert, counts);
-    return finish("edge_visibility", stream_);
+    return edge_visibility_entry("cgs_edge_visibility", n_curves, curves, n_lines, lines, n_frames, K, w2c, height, width,
+                                 maps, invert, nullptr, counts, stream_);
+}
+
+int cgs_edge_visibility_depth(int n_curves, const double* curves, int n_lines, const double* lines, int n_frames,
+                              const double* K, const double* w2c, int height, int width, const unsigned char* maps,
+                              int invert, const float* depth, double slack, int32_t* counts_out, void* stream_) {
+    const DepthGate gate{depth, slack};
+    return edge_visibility_entry("cgs_edge_visibility_depth", n_curves, curves, n_lines, lines, n_frames, K, w2c, height,
+                                 width, maps, invert, &gate, counts_out, stream_);
 }
 
 int cgs_densification_stats(int64_t P, const int* radii, const float* dL_dmeans2D, int64_t grad_stride, float* max_radii2D,
@@ -1370,38 +1397,69 @@ int cgs_report_panels(int n_views, cgs_report_view* views, void* workspace, unsi
     return finish("report_panels", stream_);
 }
 
+// The drawn views: the slack comes right after the counts (and the sizes, where they are checked with the counts).
+static int project_points_entry(const char* name, int P, const float* points, int V, const double* intr, const double* w2c,
+                                int height, int width, const DepthGate* gate, double* uv_out, uint8_t* hidden_out,
+                                void* stream_) {
+    if (P < 0 || V < 0 || (long long)P * V > (1LL << 40)) return reject("%s: invalid argument (P=%d, V=%d)", name, P, V);
+    if (slack_bad(gate)) return reject_slack(name, gate);
+    if (P == 0 || V == 0) return CGS_OK;
+    if (height <= 0 || width <= 0) return reject("%s: invalid argument (height=%d, width=%d)", name, height, width);
+    if (!points || !intr || !w2c || depth_missing(gate) || !uv_out) return reject("%s: invalid argument (NULL pointer)", name);
+    launch_project_points((hipStream_t)stream_, P, points, V, intr, w2c, height, width, gate, uv_out, hidden_out);
+    return finish(name + 4, stream_);
+}
+
 int cgs_project_points(int P, const float* points, int V, const double* intr, const double* w2c, int height, int width,
                        double* uv_out, void* stream_) {
-    if (P < 0 || V < 0 || (long long)P * V > (1LL << 40))
-        return reject("cgs_project_points: invalid argument (P=%d, V=%d)", P, V);
-    if (P == 0 || V == 0) return CGS_OK;
-    if (height <= 0 || width <= 0) return reject("cgs_project_points: invalid argument (height=%d, width=%d)", height, width);
-    if (!points || !intr || !w2c || !uv_out) return reject("cgs_project_points: invalid argument (NULL pointer)");
-    launch_project_points((hipStream_t)stream_, P, points, V, intr, w2c, height, width, uv_out);
-    return finish("project_points", stream_);
+    return project_points_entry("cgs_project_points", P, points, V, intr, w2c, height, width, nullptr, uv_out, nullptr,
+                                stream_);
+}
+
+int cgs_project_points_depth(int P, const float* points, int V, const double* intr, const double* w2c, int height, int width,
+                             const float* depth, double slack, double* uv_out, uint8_t* hidden_out, void* stream_) {
+    const DepthGate gate{depth, slack};
+    return project_points_entry("cgs_project_points_depth", P, points, V, intr, w2c, height, width, &gate, uv_out, hidden_out,
+                                stream_);
 }
 
 size_t cgs_render_points_workspace_bytes(int P, int V, int height, int width) {
     return render_points_workspace_bytes(P, V, height, width);
 }
 
+static int render_points_entry(const char* name, int P, const float* points, const float* colors, int V, const double* intr,
+                               const double* w2c, int height, int width, const DepthGate* gate, double alpha,
+                               const double* background, float* out, int* kept, int* hidden, void* workspace,
+                               size_t workspace_bytes, void* stream_) {
+    if (P < 0 || V < 0 || height <= 0 || width <= 0 || (long long)height * width > (1LL << 31))
+        return reject("%s: invalid argument (P=%d, V=%d, height=%d, width=%d)", name, P, V, height, width);
+    if (slack_bad(gate)) return reject_slack(name, gate);
+    if (!(alpha >= 0.0 && alpha <= 1.0)) return reject("%s: invalid argument (alpha=%g, need 0 <= alpha <= 1)", name, alpha);
+    if (V == 0) return CGS_OK;
+    if (!intr || !w2c || depth_missing(gate) || !background || !out || !workspace || (P > 0 && (!points || !colors)))
+        return reject("%s: invalid argument (NULL pointer)", name);
+    const int per = render_points_views_per_chunk(P, V, height, width, workspace_bytes);
+    if (per <= 0)
+        return reject("%s: invalid argument (workspace of %zu bytes holds no view; one view needs %zu)", name, workspace_bytes,
+                      render_points_workspace_bytes(P, 1, height, width));
+    launch_render_points((hipStream_t)stream_, P, points, colors, V, intr, w2c, height, width, gate, alpha, background, out,
+                         kept, hidden, workspace, per);
+    return finish(name + 4, stream_);
+}
+
 int cgs_render_points(int P, const float* points, const float* colors, int V, const double* intr, const double* w2c,
                       int height, int width, double alpha, const double* background, float* out, int* kept,
                       void* workspace, size_t workspace_bytes, void* stream_) {
-    if (P < 0 || V < 0 || height <= 0 || width <= 0 || (long long)height * width > (1LL << 31))
-        return reject("cgs_render_points: invalid argument (P=%d, V=%d, height=%d, width=%d)", P, V, height, width);
-    if (!(alpha >= 0.0 && alpha <= 1.0))
-        return reject("cgs_render_points: invalid argument (alpha=%g, need 0 <= alpha <= 1)", alpha);
-    if (V == 0) return CGS_OK;
-    if (!intr || !w2c || !background || !out || !workspace || (P > 0 && (!points || !colors)))
-        return reject("cgs_render_points: invalid argument (NULL pointer)");
-    const int per = render_points_views_per_chunk(P, V, height, width, workspace_bytes);
-    if (per <= 0)
-        return reject("cgs_render_points: invalid argument (workspace of %zu bytes holds no view; one view needs %zu)",
-                      workspace_bytes, render_points_workspace_bytes(P, 1, height, width));
-    launch_render_points((hipStream_t)stream_, P, points, colors, V, intr, w2c, height, width, alpha, background, out,
-                         kept, workspace, per);
-    return finish("render_points", stream_);
+    return render_points_entry("cgs_render_points", P, points, colors, V, intr, w2c, height, width, nullptr, alpha, background,
+                               out, kept, nullptr, workspace, workspace_bytes, stream_);
+}
+
+int cgs_render_points_depth(int P, const float* points, const float* colors, int V, const double* intr, const double* w2c,
+                            int height, int width, const float* depth, double slack, double alpha, const double* background,
+                            float* out, int* kept, int* hidden, void* workspace, size_t workspace_bytes, void* stream_) {
+    const DepthGate gate{depth, slack};
+    return render_points_entry("cgs_render_points_depth", P, points, colors, V, intr, w2c, height, width, &gate, alpha,
+                               background, out, kept, hidden, workspace, workspace_bytes, stream_);
 }
 
 int64_t cgs_ellipsoid_mesh_body_bytes(int P, int resolution, int64_t* vertex_bytes, int64_t* face_bytes) {
@@ -1665,19 +1723,37 @@ static bool seed_views_ok(const char* name, int V, int height, int width) {
     return true;
 }
 
+// The three seed entries that walk the views: the slack comes right after the grid, the depth pointer among the pointers of
+// the views.
+static int voxel_votes_entry(const char* name, int nx, int ny, int nz, const double* lo, const double* step, int V,
+                             const double* intr, const double* w2c, int height, int width, const uint32_t* bits,
+                             const DepthGate* gate, int accumulate, uint16_t* seen, uint16_t* hit, uint16_t* hidden,
+                             void* stream_) {
+    // a NULL pointer is reported after the dims and before a bad lo or step, as it always was
+    const bool ptrs = lo && step && seen && hit && (V == 0 || (intr && w2c && bits && !depth_missing(gate)));
+    if (!seed_views_ok(name, V, height, width) || !seed_grid_ok(name, nx, ny, nz, ptrs ? lo : nullptr, ptrs ? step : nullptr))
+        return CGS_ERR_INVALID_ARGUMENT;
+    if (slack_bad(gate)) return reject_slack(name, gate);
+    if (!ptrs) return reject("%s: invalid argument (NULL pointer)", name);
+    if (V == 0 && accumulate) return CGS_OK;
+    launch_voxel_votes((hipStream_t)stream_, SeedGrid{{lo[0], lo[1], lo[2]}, {step[0], step[1], step[2]}, nx, ny, nz},
+                       SeedViews{V, height, width, (width + 31) / 32, intr, w2c, bits}, gate, accumulate, seen, hit, hidden);
+    return finish(name + 4, stream_);
+}
+
 int cgs_voxel_votes(int nx, int ny, int nz, const double* lo, const double* step, int V, const double* intr,
                     const double* w2c, int height, int width, const uint32_t* bits, int accumulate, uint16_t* seen,
                     uint16_t* hit, void* stream_) {
-    // a NULL pointer is reported after the dims and before a bad lo or step, as it always was
-    const bool ptrs = lo && step && seen && hit && (V == 0 || (intr && w2c && bits));
-    if (!seed_views_ok("cgs_voxel_votes", V, height, width) ||
-        !seed_grid_ok("cgs_voxel_votes", nx, ny, nz, ptrs ? lo : nullptr, ptrs ? step : nullptr))
-        return CGS_ERR_INVALID_ARGUMENT;
-    if (!ptrs) return reject("cgs_voxel_votes: invalid argument (NULL pointer)");
-    if (V == 0 && accumulate) return CGS_OK;
-    launch_voxel_votes((hipStream_t)stream_, SeedGrid{{lo[0], lo[1], lo[2]}, {step[0], step[1], step[2]}, nx, ny, nz},
-                       SeedViews{V, height, width, (width + 31) / 32, intr, w2c, bits}, accumulate, seen, hit);
-    return finish("voxel_votes", stream_);
+    return voxel_votes_entry("cgs_voxel_votes", nx, ny, nz, lo, step, V, intr, w2c, height, width, bits, nullptr, accumulate,
+                             seen, hit, nullptr, stream_);
+}
+
+int cgs_voxel_votes_depth(int nx, int ny, int nz, const double* lo, const double* step, int V, const double* intr,
+                          const double* w2c, int height, int width, const uint32_t* bits, const float* depth, double slack,
+                          int accumulate, uint16_t* seen, uint16_t* hit, uint16_t* hidden, void* stream_) {
+    const DepthGate gate{depth, slack};
+    return voxel_votes_entry("cgs_voxel_votes_depth", nx, ny, nz, lo, step, V, intr, w2c, height, width, bits, &gate,
+                             accumulate, seen, hit, hidden, stream_);
 }
 
 int cgs_voxel_moments(int nx, int ny, int nz, const void* keep_bits, int N, const void* centres, int radius, void* moments,
@@ -1693,74 +1769,143 @@ int cgs_voxel_moments(int nx, int ny, int nz, const void* keep_bits, int N, cons
     return finish("voxel_moments", stream_);
 }
 
-int cgs_ray_claims(int nx, int ny, int nz, const double* lo, const double* step, int M, const int32_t* index,
-                   const uint16_t* support, int V, const double* intr, const double* w2c, int height, int width,
-                   const uint32_t* bits, int clear, uint32_t* best, void* stream_) {
-    if (M < 0) return reject("cgs_ray_claims: invalid argument (M=%d)", M);
-    if (!seed_views_ok("cgs_ray_claims", V, height, width) || !seed_grid_ok("cgs_ray_claims", nx, ny, nz, lo, step))
-        return CGS_ERR_INVALID_ARGUMENT;
-    if (!lo || !step || (V > 0 && !best) || (M > 0 && V > 0 && (!index || !support || !intr || !w2c || !bits)))
-        return reject("cgs_ray_claims: invalid argument (NULL pointer)");
+static int ray_claims_entry(const char* name, int nx, int ny, int nz, const double* lo, const double* step, int M,
+                            const int32_t* index, const uint16_t* support, int V, const double* intr, const double* w2c,
+                            int height, int width, const uint32_t* bits, const DepthGate* gate, int clear, uint32_t* best,
+                            void* stream_) {
+    if (M < 0) return reject("%s: invalid argument (M=%d)", name, M);
+    if (!seed_views_ok(name, V, height, width) || !seed_grid_ok(name, nx, ny, nz, lo, step)) return CGS_ERR_INVALID_ARGUMENT;
+    if (slack_bad(gate)) return reject_slack(name, gate);
+    if (!lo || !step || (V > 0 && !best) ||
+        (M > 0 && V > 0 && (!index || !support || !intr || !w2c || !bits || depth_missing(gate))))
+        return reject("%s: invalid argument (NULL pointer)", name);
     const SeedGrid g{{lo[0], lo[1], lo[2]}, {step[0], step[1], step[2]}, nx, ny, nz};
     const SeedViews views{V, height, width, (width + 31) / 32, intr, w2c, bits};
-    if (launch_ray_claims((hipStream_t)stream_, g, views, M, index, support, clear, best) != hipSuccess) {
-        set_error("cgs_ray_claims: clearing the claims failed");
+    if (launch_ray_claims((hipStream_t)stream_, g, views, gate, M, index, support, clear, best) != hipSuccess) {
+        set_error("%s: clearing the claims failed", name);
         return CGS_ERR_HIP;
     }
     if (M == 0 || V == 0) return CGS_OK;
-    return finish("ray_claims", stream_);
+    return finish(name + 4, stream_);
+}
+
+int cgs_ray_claims(int nx, int ny, int nz, const double* lo, const double* step, int M, const int32_t* index,
+                   const uint16_t* support, int V, const double* intr, const double* w2c, int height, int width,
+                   const uint32_t* bits, int clear, uint32_t* best, void* stream_) {
+    return ray_claims_entry("cgs_ray_claims", nx, ny, nz, lo, step, M, index, support, V, intr, w2c, height, width, bits,
+                            nullptr, clear, best, stream_);
+}
+
+int cgs_ray_claims_depth(int nx, int ny, int nz, const double* lo, const double* step, int M, const int32_t* index,
+                         const uint16_t* support, int V, const double* intr, const double* w2c, int height, int width,
+                         const uint32_t* bits, const float* depth, double slack, int clear, uint32_t* best, void* stream_) {
+    const DepthGate gate{depth, slack};
+    return ray_claims_entry("cgs_ray_claims_depth", nx, ny, nz, lo, step, M, index, support, V, intr, w2c, height, width, bits,
+                            &gate, clear, best, stream_);
+}
+
+// Here the slack comes after lo and step and before the window.
+static int ray_wins_entry(const char* name, int nx, int ny, int nz, const double* lo, const double* step, int M,
+                          const int32_t* index, const uint16_t* support, int V, const double* intr, const double* w2c,
+                          int height, int width, const uint32_t* bits, const uint32_t* best, const DepthGate* gate, int window,
+                          int margin, int accumulate, uint16_t* wins, void* stream_) {
+    if (M < 0) return reject("%s: invalid argument (M=%d)", name, M);
+    if (!seed_views_ok(name, V, height, width) || !seed_grid_ok(name, nx, ny, nz, lo, step)) return CGS_ERR_INVALID_ARGUMENT;
+    if (!lo || !step)   // before the slack, the window and the margin, as it always was
+        return reject("%s: invalid argument (NULL pointer)", name);
+    if (slack_bad(gate)) return reject_slack(name, gate);
+    if (window < 0 || window > CGS_SEED_MAX_WINDOW || margin < 0 || margin > 65535)
+        return reject("%s: invalid argument (window=%d, margin=%d; the window lies in [0, %d], the margin in [0, 65535])", name,
+                      window, margin, CGS_SEED_MAX_WINDOW);
+    if (M > 0 && V > 0 && (!index || !support || !intr || !w2c || !bits || !best || depth_missing(gate) || !wins))
+        return reject("%s: invalid argument (NULL pointer)", name);
+    if (M == 0 || V == 0) return CGS_OK;
+    launch_ray_wins((hipStream_t)stream_, SeedGrid{{lo[0], lo[1], lo[2]}, {step[0], step[1], step[2]}, nx, ny, nz},
+                    SeedViews{V, height, width, (width + 31) / 32, intr, w2c, bits}, gate, M, index, support, best, window,
+                    margin, accumulate, wins);
+    return finish(name + 4, stream_);
 }
 
 int cgs_ray_wins(int nx, int ny, int nz, const double* lo, const double* step, int M, const int32_t* index,
                  const uint16_t* support, int V, const double* intr, const double* w2c, int height, int width,
                  const uint32_t* bits, const uint32_t* best, int window, int margin, int accumulate, uint16_t* wins,
                  void* stream_) {
-    if (M < 0) return reject("cgs_ray_wins: invalid argument (M=%d)", M);
-    if (!seed_views_ok("cgs_ray_wins", V, height, width) || !seed_grid_ok("cgs_ray_wins", nx, ny, nz, lo, step))
-        return CGS_ERR_INVALID_ARGUMENT;
-    if (!lo || !step)   // before the window and the margin, as it always was
-        return reject("cgs_ray_wins: invalid argument (NULL pointer)");
-    if (window < 0 || window > CGS_SEED_MAX_WINDOW || margin < 0 || margin > 65535)
-        return reject("cgs_ray_wins: invalid argument (window=%d, margin=%d; the window lies in [0, %d], the margin in [0, 65535])",
-                      window, margin, CGS_SEED_MAX_WINDOW);
-    if (M > 0 && V > 0 && (!index || !support || !intr || !w2c || !bits || !best || !wins))
-        return reject("cgs_ray_wins: invalid argument (NULL pointer)");
-    if (M == 0 || V == 0) return CGS_OK;
-    launch_ray_wins((hipStream_t)stream_, SeedGrid{{lo[0], lo[1], lo[2]}, {step[0], step[1], step[2]}, nx, ny, nz},
-                    SeedViews{V, height, width, (width + 31) / 32, intr, w2c, bits}, M, index, support, best, window, margin,
-                    accumulate, wins);
-    return finish("ray_wins", stream_);
+    return ray_wins_entry("cgs_ray_wins", nx, ny, nz, lo, step, M, index, support, V, intr, w2c, height, width, bits, best,
+                          nullptr, window, margin, accumulate, wins, stream_);
+}
+
+int cgs_ray_wins_depth(int nx, int ny, int nz, const double* lo, const double* step, int M, const int32_t* index,
+                       const uint16_t* support, int V, const double* intr, const double* w2c, int height, int width,
+                       const uint32_t* bits, const uint32_t* best, const float* depth, double slack, int window, int margin,
+                       int accumulate, uint16_t* wins, void* stream_) {
+    const DepthGate gate{depth, slack};
+    return ray_wins_entry("cgs_ray_wins_depth", nx, ny, nz, lo, step, M, index, support, V, intr, w2c, height, width, bits,
+                          best, &gate, window, margin, accumulate, wins, stream_);
+}
+
+// The slack comes before the no-op return.
+static int edge_support_entry(const char* name, int E, int P, const float* points, const int32_t* offsets, int V,
+                              const double* intr, const double* w2c, int height, int width, const int32_t* d2, int T,
+                              const int32_t* tol2, const DepthGate* gate, int32_t* counts, int32_t* hidden, void* stream_) {
+    if (E < 0 || P < 0 || V < 0 || T < 1 || T > CGS_EDGE_SUPPORT_MAX_TOL)
+        return reject("%s: invalid argument (E=%d, P=%d, V=%d, T=%d; T lies in [1, %d])", name, E, P, V, T,
+                      CGS_EDGE_SUPPORT_MAX_TOL);
+    if (slack_bad(gate)) return reject_slack(name, gate);
+    if (E == 0 || V == 0) return CGS_OK;
+    if (!edt_size_ok(height, width))   // d2 is a cgs_edt_squared transform, depth has its size
+        return reject("%s: invalid argument (height=%d, width=%d; sizes lie in [1, %d])", name, height, width,
+                      CGS_EDT_MAX_SIZE);
+    if (!offsets || !intr || !w2c || !d2 || !tol2 || depth_missing(gate) || !counts || (P > 0 && !points))
+        return reject("%s: invalid argument (NULL pointer)", name);
+    launch_edge_support((hipStream_t)stream_, E, P, points, offsets, V, intr, w2c, height, width, d2, T, tol2, gate, counts,
+                        hidden);
+    return finish(name + 4, stream_);
 }
 
 int cgs_edge_support(int E, int P, const float* points, const int32_t* offsets, int V, const double* intr,
                      const double* w2c, int height, int width, const int32_t* d2, int T, const int32_t* tol2,
                      int32_t* counts, void* stream_) {
-    if (E < 0 || P < 0 || V < 0 || T < 1 || T > CGS_EDGE_SUPPORT_MAX_TOL)
-        return reject("cgs_edge_support: invalid argument (E=%d, P=%d, V=%d, T=%d; T lies in [1, %d])", E, P, V, T,
-                      CGS_EDGE_SUPPORT_MAX_TOL);
-    if (E == 0 || V == 0) return CGS_OK;
-    if (!edt_size_ok(height, width))   // d2 is a cgs_edt_squared transform
-        return reject("cgs_edge_support: invalid argument (height=%d, width=%d; sizes lie in [1, %d])", height, width,
+    return edge_support_entry("cgs_edge_support", E, P, points, offsets, V, intr, w2c, height, width, d2, T, tol2, nullptr,
+                              counts, nullptr, stream_);
+}
+
+int cgs_edge_support_depth(int E, int P, const float* points, const int32_t* offsets, int V, const double* intr,
+                           const double* w2c, int height, int width, const int32_t* d2, int T, const int32_t* tol2,
+                           const float* depth, double slack, int32_t* counts, int32_t* hidden, void* stream_) {
+    const DepthGate gate{depth, slack};
+    return edge_support_entry("cgs_edge_support_depth", E, P, points, offsets, V, intr, w2c, height, width, d2, T, tol2, &gate,
+                              counts, hidden, stream_);
+}
+
+// The three per-sample operators: the slack comes right after the sizes.
+static int sample_support_entry(const char* name, int P, const float* points, int V, const double* intr, const double* w2c,
+                                int height, int width, const int32_t* d2, int T, const int32_t* tol2, const DepthGate* gate,
+                                int32_t* tally, int32_t* hidden, void* stream_) {
+    if (P < 0 || V < 0 || T < 1 || T > CGS_EDGE_SUPPORT_MAX_TOL)
+        return reject("%s: invalid argument (P=%d, V=%d, T=%d; T lies in [1, %d])", name, P, V, T, CGS_EDGE_SUPPORT_MAX_TOL);
+    if (!edt_size_ok(height, width))   // d2 is a cgs_edt_squared transform, depth has its size
+        return reject("%s: invalid argument (height=%d, width=%d; sizes lie in [1, %d])", name, height, width,
                       CGS_EDT_MAX_SIZE);
-    if (!offsets || !intr || !w2c || !d2 || !tol2 || !counts || (P > 0 && !points))
-        return reject("cgs_edge_support: invalid argument (NULL pointer)");
-    launch_edge_support((hipStream_t)stream_, E, P, points, offsets, V, intr, w2c, height, width, d2, T, tol2, counts);
-    return finish("edge_support", stream_);
+    if (slack_bad(gate)) return reject_slack(name, gate);
+    if (!intr || !w2c || !d2 || !tol2 || depth_missing(gate) || (P > 0 && (!points || !tally)))
+        return reject("%s: invalid argument (NULL pointer; P=%d, V=%d)", name, P, V);
+    if (P == 0 || V == 0) return CGS_OK;   // nothing to add
+    launch_sample_support((hipStream_t)stream_, P, points, V, intr, w2c, height, width, d2, T, tol2, gate, tally, hidden);
+    return finish(name + 4, stream_);
 }
 
 int cgs_sample_support(int P, const float* points, int V, const double* intr, const double* w2c, int height, int width,
                        const int32_t* d2, int T, const int32_t* tol2, int32_t* tally, void* stream_) {
-    if (P < 0 || V < 0 || T < 1 || T > CGS_EDGE_SUPPORT_MAX_TOL)
-        return reject("cgs_sample_support: invalid argument (P=%d, V=%d, T=%d; T lies in [1, %d])", P, V, T,
-                      CGS_EDGE_SUPPORT_MAX_TOL);
-    if (!edt_size_ok(height, width))   // d2 is a cgs_edt_squared transform
-        return reject("cgs_sample_support: invalid argument (height=%d, width=%d; sizes lie in [1, %d])", height, width,
-                      CGS_EDT_MAX_SIZE);
-    if (!intr || !w2c || !d2 || !tol2 || (P > 0 && (!points || !tally)))
-        return reject("cgs_sample_support: invalid argument (NULL pointer; P=%d, V=%d)", P, V);
-    if (P == 0 || V == 0) return CGS_OK;   // nothing to add
-    launch_sample_support((hipStream_t)stream_, P, points, V, intr, w2c, height, width, d2, T, tol2, tally);
-    return finish("sample_support", stream_);
+    return sample_support_entry("cgs_sample_support", P, points, V, intr, w2c, height, width, d2, T, tol2, nullptr, tally,
+                                nullptr, stream_);
+}
+
+int cgs_sample_support_depth(int P, const float* points, int V, const double* intr, const double* w2c, int height, int width,
+                             const int32_t* d2, int T, const int32_t* tol2, const float* depth, double slack, int32_t* tally,
+                             int32_t* hidden, void* stream_) {
+    const DepthGate gate{depth, slack};
+    return sample_support_entry("cgs_sample_support_depth", P, points, V, intr, w2c, height, width, d2, T, tol2, &gate, tally,
+                                hidden, stream_);
 }
 
 size_t cgs_sample_cover_workspace_bytes(int P) { return sample_cover_workspace_bytes(P); }
@@ -1842,51 +1987,96 @@ int cgs_oriented_near(int V, int height, int width, const uint8_t* code, int tol
     return finish("oriented_near", stream_);
 }
 
+static int sample_support_oriented_entry(const char* name, int P, const float* points, const int32_t* partner, int V,
+                                         const double* intr, const double* w2c, int height, int width, const uint8_t* near,
+                                         int spread, const DepthGate* gate, int32_t* tally, int32_t* hidden, void* stream_) {
+    if (P < 0 || V < 0 || spread < 0 || spread > CGS_ORIENT_MAX_SPREAD)
+        return reject("%s: invalid argument (P=%d, V=%d, spread=%d; the spread lies in [0, %d])", name, P, V, spread,
+                      CGS_ORIENT_MAX_SPREAD);
+    if (!edt_size_ok(height, width))
+        return reject("%s: invalid argument (height=%d, width=%d; sizes lie in [1, %d])", name, height, width,
+                      CGS_EDT_MAX_SIZE);
+    if (slack_bad(gate)) return reject_slack(name, gate);
+    if (!intr || !w2c || !near || depth_missing(gate) || (P > 0 && (!points || !partner || !tally)))
+        return reject("%s: invalid argument (NULL pointer; P=%d, V=%d)", name, P, V);
+    if (P == 0 || V == 0) return CGS_OK;   // nothing to add
+    launch_sample_support_oriented((hipStream_t)stream_, P, points, partner, V, intr, w2c, height, width, near, spread, gate,
+                                   tally, hidden);
+    return finish(name + 4, stream_);
+}
+
 int cgs_sample_support_oriented(int P, const float* points, const int32_t* partner, int V, const double* intr,
                                 const double* w2c, int height, int width, const uint8_t* near, int spread, int32_t* tally,
                                 void* stream_) {
-    if (P < 0 || V < 0 || spread < 0 || spread > CGS_ORIENT_MAX_SPREAD)
-        return reject("cgs_sample_support_oriented: invalid argument (P=%d, V=%d, spread=%d; the spread lies in [0, %d])", P, V,
-                      spread, CGS_ORIENT_MAX_SPREAD);
-    if (!edt_size_ok(height, width))
-        return reject("cgs_sample_support_oriented: invalid argument (height=%d, width=%d; sizes lie in [1, %d])", height,
-                      width, CGS_EDT_MAX_SIZE);
-    if (!intr || !w2c || !near || (P > 0 && (!points || !partner || !tally)))
-        return reject("cgs_sample_support_oriented: invalid argument (NULL pointer; P=%d, V=%d)", P, V);
+    return sample_support_oriented_entry("cgs_sample_support_oriented", P, points, partner, V, intr, w2c, height, width, near,
+                                         spread, nullptr, tally, nullptr, stream_);
+}
+
+int cgs_sample_support_oriented_depth(int P, const float* points, const int32_t* partner, int V, const double* intr,
+                                      const double* w2c, int height, int width, const uint8_t* near, int spread,
+                                      const float* depth, double slack, int32_t* tally, int32_t* hidden, void* stream_) {
+    const DepthGate gate{depth, slack};
+    return sample_support_oriented_entry("cgs_sample_support_oriented_depth", P, points, partner, V, intr, w2c, height, width,
+                                         near, spread, &gate, tally, hidden, stream_);
+}
+
+static int sample_snap_terms_entry(const char* name, int P, const float* points, int V, const double* intr, const double* w2c,
+                                   int height, int width, const int32_t* d2, int cap2, const double* dist_lut,
+                                   const DepthGate* gate, double* terms, int32_t* views, int32_t* hidden, void* stream_) {
+    if (P < 0 || V < 0 || cap2 < 1 || cap2 > CGS_SNAP_MAX_CAP2)   // the kernel stages cap2 + 1 table entries in LDS
+        return reject("%s: invalid argument (P=%d, V=%d, cap2=%d; cap2 lies in [1, %d])", name, P, V, cap2, CGS_SNAP_MAX_CAP2);
+    if (!edt_size_ok(height, width))   // d2 is a cgs_edt_squared transform, depth has its size
+        return reject("%s: invalid argument (height=%d, width=%d; sizes lie in [1, %d])", name, height, width,
+                      CGS_EDT_MAX_SIZE);
+    if (slack_bad(gate)) return reject_slack(name, gate);
+    if (!intr || !w2c || !d2 || !dist_lut || depth_missing(gate) || (P > 0 && (!points || !terms || !views)))
+        return reject("%s: invalid argument (NULL pointer; P=%d, V=%d)", name, P, V);
     if (P == 0 || V == 0) return CGS_OK;   // nothing to add
-    launch_sample_support_oriented((hipStream_t)stream_, P, points, partner, V, intr, w2c, height, width, near, spread, tally);
-    return finish("sample_support_oriented", stream_);
+    launch_sample_snap_terms((hipStream_t)stream_, P, points, V, intr, w2c, height, width, d2, cap2, dist_lut, gate, terms,
+                             views, hidden);
+    return finish(name + 4, stream_);
 }
 
 int cgs_sample_snap_terms(int P, const float* points, int V, const double* intr, const double* w2c, int height, int width,
                           const int32_t* d2, int cap2, const double* dist_lut, double* terms, int32_t* views,
                           void* stream_) {
-    if (P < 0 || V < 0 || cap2 < 1 || cap2 > CGS_SNAP_MAX_CAP2)   // the kernel stages cap2 + 1 table entries in LDS
-        return reject("cgs_sample_snap_terms: invalid argument (P=%d, V=%d, cap2=%d; cap2 lies in [1, %d])", P, V, cap2,
-                      CGS_SNAP_MAX_CAP2);
-    if (!edt_size_ok(height, width))   // d2 is a cgs_edt_squared transform
-        return reject("cgs_sample_snap_terms: invalid argument (height=%d, width=%d; sizes lie in [1, %d])", height, width,
+    return sample_snap_terms_entry("cgs_sample_snap_terms", P, points, V, intr, w2c, height, width, d2, cap2, dist_lut, nullptr,
+                                   terms, views, nullptr, stream_);
+}
+
+int cgs_sample_snap_terms_depth(int P, const float* points, int V, const double* intr, const double* w2c, int height,
+                                int width, const int32_t* d2, int cap2, const double* dist_lut, const float* depth,
+                                double slack, double* terms, int32_t* views, int32_t* hidden, void* stream_) {
+    const DepthGate gate{depth, slack};
+    return sample_snap_terms_entry("cgs_sample_snap_terms_depth", P, points, V, intr, w2c, height, width, d2, cap2, dist_lut,
+                                   &gate, terms, views, hidden, stream_);
+}
+
+// Near-plane clipping: the plane is checked right after the sizes (and the slack, where there is one).
+static int mesh_depth_entry(const char* name, int F, const float* tris, int V, const double* intr, const double* w2c,
+                            int height, int width, const double* near, float* depth, void* stream_) {
+    if (F < 0 || V < 0) return reject("%s: invalid argument (F=%d, V=%d)", name, F, V);
+    if (!edt_size_ok(height, width))
+        return reject("%s: invalid argument (height=%d, width=%d; sizes lie in [1, %d])", name, height, width,
                       CGS_EDT_MAX_SIZE);
-    if (!intr || !w2c || !d2 || !dist_lut || (P > 0 && (!points || !terms || !views)))
-        return reject("cgs_sample_snap_terms: invalid argument (NULL pointer; P=%d, V=%d)", P, V);
-    if (P == 0 || V == 0) return CGS_OK;   // nothing to add
-    launch_sample_snap_terms((hipStream_t)stream_, P, points, V, intr, w2c, height, width, d2, cap2, dist_lut, terms, views);
-    return finish("sample_snap_terms", stream_);
+    if (near && !near_ok(*near)) return reject("%s: invalid argument (near=%g; the plane is finite and > 0)", name, *near);
+    if (!intr || !w2c || !depth || (F > 0 && !tris)) return reject("%s: invalid argument (NULL pointer; F=%d)", name, F);
+    if (V == 0) return CGS_OK;   // nothing to write
+    if (launch_mesh_depth((hipStream_t)stream_, F, tris, V, intr, w2c, height, width, near, depth) != hipSuccess) {
+        set_error("%s: filling the depth planes failed", name);
+        return CGS_ERR_HIP;
+    }
+    return finish(name + 4, stream_);
 }
 
 int cgs_mesh_depth(int F, const float* tris, int V, const double* intr, const double* w2c, int height, int width,
                    float* depth, void* stream_) {
-    if (F < 0 || V < 0) return reject("cgs_mesh_depth: invalid argument (F=%d, V=%d)", F, V);
-    if (!edt_size_ok(height, width))
-        return reject("cgs_mesh_depth: invalid argument (height=%d, width=%d; sizes lie in [1, %d])", height, width,
-                      CGS_EDT_MAX_SIZE);
-    if (!intr || !w2c || !depth || (F > 0 && !tris)) return reject("cgs_mesh_depth: invalid argument (NULL pointer; F=%d)", F);
-    if (V == 0) return CGS_OK;   // nothing to write
-    if (launch_mesh_depth((hipStream_t)stream_, F, tris, V, intr, w2c, height, width, depth) != hipSuccess) {
-        set_error("cgs_mesh_depth: filling the depth planes failed");
-        return CGS_ERR_HIP;
-    }
-    return finish("mesh_depth", stream_);
+    return mesh_depth_entry("cgs_mesh_depth", F, tris, V, intr, w2c, height, width, nullptr, depth, stream_);
+}
+
+int cgs_mesh_depth_clipped(int F, const float* tris, int V, const double* intr, const double* w2c, int height, int width,
+                           double near, float* depth, void* stream_) {
+    return mesh_depth_entry("cgs_mesh_depth_clipped", F, tris, V, intr, w2c, height, width, &near, depth, stream_);
 }
 
 int cgs_depth_window_max(int V, int height, int width, int radius, const float* depth, float* out, void* stream_) {
@@ -1925,266 +2115,38 @@ int cgs_point_mask_depth(int P, const float* points, int V, const double* intr, 
     return finish("point_mask_depth", stream_);
 }
 
-// ---- the depth-gated siblings of the four per-sample 2D operators (include/curvegs.h).  Each checks what its sibling checks,
-// in its order, plus the gate's arguments as cgs_point_mask_depth checks them: a finite slack >= 0 and a depth pointer.
-static bool slack_ok(double slack) { return slack >= 0.0 && !std::isinf(slack); }   // a NaN fails the comparison
-
-int cgs_edge_support_depth(int E, int P, const float* points, const int32_t* offsets, int V, const double* intr,
-                           const double* w2c, int height, int width, const int32_t* d2, int T, const int32_t* tol2,
-                           const float* depth, double slack, int32_t* counts, int32_t* hidden, void* stream_) {
-    if (E < 0 || P < 0 || V < 0 || T < 1 || T > CGS_EDGE_SUPPORT_MAX_TOL)
-        return reject("cgs_edge_support_depth: invalid argument (E=%d, P=%d, V=%d, T=%d; T lies in [1, %d])", E, P, V, T,
-                      CGS_EDGE_SUPPORT_MAX_TOL);
-    if (!slack_ok(slack))
-        return reject("cgs_edge_support_depth: invalid argument (slack=%g; the slack is finite and >= 0)", slack);
-    if (E == 0 || V == 0) return CGS_OK;
-    if (!edt_size_ok(height, width))   // d2 is a cgs_edt_squared transform, depth has its size
-        return reject("cgs_edge_support_depth: invalid argument (height=%d, width=%d; sizes lie in [1, %d])", height, width,
-                      CGS_EDT_MAX_SIZE);
-    if (!offsets || !intr || !w2c || !d2 || !tol2 || !depth || !counts || (P > 0 && !points))
-        return reject("cgs_edge_support_depth: invalid argument (NULL pointer)");
-    launch_edge_support_depth((hipStream_t)stream_, E, P, points, offsets, V, intr, w2c, height, width, d2, T, tol2, depth,
-                              slack, counts, hidden);
-    return finish("edge_support_depth", stream_);
-}
-
-int cgs_sample_support_depth(int P, const float* points, int V, const double* intr, const double* w2c, int height, int width,
-                             const int32_t* d2, int T, const int32_t* tol2, const float* depth, double slack, int32_t* tally,
-                             int32_t* hidden, void* stream_) {
-    if (P < 0 || V < 0 || T < 1 || T > CGS_EDGE_SUPPORT_MAX_TOL)
-        return reject("cgs_sample_support_depth: invalid argument (P=%d, V=%d, T=%d; T lies in [1, %d])", P, V, T,
-                      CGS_EDGE_SUPPORT_MAX_TOL);
-    if (!edt_size_ok(height, width))   // d2 is a cgs_edt_squared transform, depth has its size
-        return reject("cgs_sample_support_depth: invalid argument (height=%d, width=%d; sizes lie in [1, %d])", height, width,
-                      CGS_EDT_MAX_SIZE);
-    if (!slack_ok(slack))
-        return reject("cgs_sample_support_depth: invalid argument (slack=%g; the slack is finite and >= 0)", slack);
-    if (!intr || !w2c || !d2 || !tol2 || !depth || (P > 0 && (!points || !tally)))
-        return reject("cgs_sample_support_depth: invalid argument (NULL pointer; P=%d, V=%d)", P, V);
-    if (P == 0 || V == 0) return CGS_OK;   // nothing to add
-    launch_sample_support_depth((hipStream_t)stream_, P, points, V, intr, w2c, height, width, d2, T, tol2, depth, slack, tally,
-                                hidden);
-    return finish("sample_support_depth", stream_);
-}
-
-int cgs_sample_support_oriented_depth(int P, const float* points, const int32_t* partner, int V, const double* intr,
-                                      const double* w2c, int height, int width, const uint8_t* near, int spread,
-                                      const float* depth, double slack, int32_t* tally, int32_t* hidden, void* stream_) {
-    if (P < 0 || V < 0 || spread < 0 || spread > CGS_ORIENT_MAX_SPREAD)
-        return reject("cgs_sample_support_oriented_depth: invalid argument (P=%d, V=%d, spread=%d; the spread lies in [0, %d])",
-                      P, V, spread, CGS_ORIENT_MAX_SPREAD);
-    if (!edt_size_ok(height, width))
-        return reject("cgs_sample_support_oriented_depth: invalid argument (height=%d, width=%d; sizes lie in [1, %d])", height,
-                      width, CGS_EDT_MAX_SIZE);
-    if (!slack_ok(slack))
-        return reject("cgs_sample_support_oriented_depth: invalid argument (slack=%g; the slack is finite and >= 0)", slack);
-    if (!intr || !w2c || !near || !depth || (P > 0 && (!points || !partner || !tally)))
-        return reject("cgs_sample_support_oriented_depth: invalid argument (NULL pointer; P=%d, V=%d)", P, V);
-    if (P == 0 || V == 0) return CGS_OK;   // nothing to add
-    launch_sample_support_oriented_depth((hipStream_t)stream_, P, points, partner, V, intr, w2c, height, width, near, spread,
-                                         depth, slack, tally, hidden);
-    return finish("sample_support_oriented_depth", stream_);
-}
-
-int cgs_sample_snap_terms_depth(int P, const float* points, int V, const double* intr, const double* w2c, int height,
-                                int width, const int32_t* d2, int cap2, const double* dist_lut, const float* depth,
-                                double slack, double* terms, int32_t* views, int32_t* hidden, void* stream_) {
-    if (P < 0 || V < 0 || cap2 < 1 || cap2 > CGS_SNAP_MAX_CAP2)   // the kernel stages cap2 + 1 table entries in LDS
-        return reject("cgs_sample_snap_terms_depth: invalid argument (P=%d, V=%d, cap2=%d; cap2 lies in [1, %d])", P, V, cap2,
-                      CGS_SNAP_MAX_CAP2);
-    if (!edt_size_ok(height, width))   // d2 is a cgs_edt_squared transform, depth has its size
-        return reject("cgs_sample_snap_terms_depth: invalid argument (height=%d, width=%d; sizes lie in [1, %d])", height,
-                      width, CGS_EDT_MAX_SIZE);
-    if (!slack_ok(slack))
-        return reject("cgs_sample_snap_terms_depth: invalid argument (slack=%g; the slack is finite and >= 0)", slack);
-    if (!intr || !w2c || !d2 || !dist_lut || !depth || (P > 0 && (!points || !terms || !views)))
-        return reject("cgs_sample_snap_terms_depth: invalid argument (NULL pointer; P=%d, V=%d)", P, V);
-    if (P == 0 || V == 0) return CGS_OK;   // nothing to add
-    launch_sample_snap_terms_depth((hipStream_t)stream_, P, points, V, intr, w2c, height, width, d2, cap2, dist_lut, depth,
-                                   slack, terms, views, hidden);
-    return finish("sample_snap_terms_depth", stream_);
-}
-
-// ---- the depth-gated siblings of the three seed entries that walk the views (include/curvegs.h).  Each checks what its
-// sibling checks, in its order, with the slack right after the grid and the depth pointer among the pointers of the views.
-int cgs_voxel_votes_depth(int nx, int ny, int nz, const double* lo, const double* step, int V, const double* intr,
-                          const double* w2c, int height, int width, const uint32_t* bits, const float* depth, double slack,
-                          int accumulate, uint16_t* seen, uint16_t* hit, uint16_t* hidden, void* stream_) {
-    const bool ptrs = lo && step && seen && hit && (V == 0 || (intr && w2c && bits && depth));
-    if (!seed_views_ok("cgs_voxel_votes_depth", V, height, width) ||
-        !seed_grid_ok("cgs_voxel_votes_depth", nx, ny, nz, ptrs ? lo : nullptr, ptrs ? step : nullptr))
-        return CGS_ERR_INVALID_ARGUMENT;
-    if (!slack_ok(slack))
-        return reject("cgs_voxel_votes_depth: invalid argument (slack=%g; the slack is finite and >= 0)", slack);
-    if (!ptrs) return reject("cgs_voxel_votes_depth: invalid argument (NULL pointer)");
-    if (V == 0 && accumulate) return CGS_OK;
-    launch_voxel_votes_depth((hipStream_t)stream_, SeedGrid{{lo[0], lo[1], lo[2]}, {step[0], step[1], step[2]}, nx, ny, nz},
-                             SeedViews{V, height, width, (width + 31) / 32, intr, w2c, bits}, SeedGate{depth, slack},
-                             accumulate, seen, hit, hidden);
-    return finish("voxel_votes_depth", stream_);
-}
-
-int cgs_ray_claims_depth(int nx, int ny, int nz, const double* lo, const double* step, int M, const int32_t* index,
-                         const uint16_t* support, int V, const double* intr, const double* w2c, int height, int width,
-                         const uint32_t* bits, const float* depth, double slack, int clear, uint32_t* best, void* stream_) {
-    if (M < 0) return reject("cgs_ray_claims_depth: invalid argument (M=%d)", M);
-    if (!seed_views_ok("cgs_ray_claims_depth", V, height, width) ||
-        !seed_grid_ok("cgs_ray_claims_depth", nx, ny, nz, lo, step))
-        return CGS_ERR_INVALID_ARGUMENT;
-    if (!slack_ok(slack))
-        return reject("cgs_ray_claims_depth: invalid argument (slack=%g; the slack is finite and >= 0)", slack);
-    if (!lo || !step || (V > 0 && !best) || (M > 0 && V > 0 && (!index || !support || !intr || !w2c || !bits || !depth)))
-        return reject("cgs_ray_claims_depth: invalid argument (NULL pointer)");
-    const SeedGrid g{{lo[0], lo[1], lo[2]}, {step[0], step[1], step[2]}, nx, ny, nz};
-    const SeedViews views{V, height, width, (width + 31) / 32, intr, w2c, bits};
-    if (launch_ray_claims_depth((hipStream_t)stream_, g, views, SeedGate{depth, slack}, M, index, support, clear, best) !=
-        hipSuccess) {
-        set_error("cgs_ray_claims_depth: clearing the claims failed");
-        return CGS_ERR_HIP;
-    }
-    if (M == 0 || V == 0) return CGS_OK;
-    return finish("ray_claims_depth", stream_);
-}
-
-int cgs_ray_wins_depth(int nx, int ny, int nz, const double* lo, const double* step, int M, const int32_t* index,
-                       const uint16_t* support, int V, const double* intr, const double* w2c, int height, int width,
-                       const uint32_t* bits, const uint32_t* best, const float* depth, double slack, int window, int margin,
-                       int accumulate, uint16_t* wins, void* stream_) {
-    if (M < 0) return reject("cgs_ray_wins_depth: invalid argument (M=%d)", M);
-    if (!seed_views_ok("cgs_ray_wins_depth", V, height, width) || !seed_grid_ok("cgs_ray_wins_depth", nx, ny, nz, lo, step))
-        return CGS_ERR_INVALID_ARGUMENT;
-    if (!lo || !step)   // before the slack, the window and the margin, as in the sibling
-        return reject("cgs_ray_wins_depth: invalid argument (NULL pointer)");
-    if (!slack_ok(slack))
-        return reject("cgs_ray_wins_depth: invalid argument (slack=%g; the slack is finite and >= 0)", slack);
-    if (window < 0 || window > CGS_SEED_MAX_WINDOW || margin < 0 || margin > 65535)
-        return reject("cgs_ray_wins_depth: invalid argument (window=%d, margin=%d; the window lies in [0, %d], the margin in "
-                      "[0, 65535])", window, margin, CGS_SEED_MAX_WINDOW);
-    if (M > 0 && V > 0 && (!index || !support || !intr || !w2c || !bits || !best || !depth || !wins))
-        return reject("cgs_ray_wins_depth: invalid argument (NULL pointer)");
-    if (M == 0 || V == 0) return CGS_OK;
-    launch_ray_wins_depth((hipStream_t)stream_, SeedGrid{{lo[0], lo[1], lo[2]}, {step[0], step[1], step[2]}, nx, ny, nz},
-                          SeedViews{V, height, width, (width + 31) / 32, intr, w2c, bits}, SeedGate{depth, slack}, M, index,
-                          support, best, window, margin, accumulate, wins);
-    return finish("ray_wins_depth", stream_);
-}
-
-// ---- the depth gate on the control-point visibility check and on the drawn views (include/curvegs.h).  Each checks what its
-// sibling checks, in its order, with the slack right after the sizes and the depth pointer among the pointers of the views.
-int cgs_edge_visibility_depth(int n_curves, const double* curves, int n_lines, const double* lines, int n_frames,
-                              const double* K, const double* w2c, int height, int width, const unsigned char* maps,
-                              int invert, const float* depth, double slack, int32_t* counts_out, void* stream_) {
-    if (n_curves < 0 || n_lines < 0 || n_frames < 0 || (long long)n_curves + n_lines > (1 << 30))
-        return reject("cgs_edge_visibility_depth: invalid argument (n_curves=%d, n_lines=%d, n_frames=%d)", n_curves, n_lines,
-                      n_frames);
-    if (!slack_ok(slack))
-        return reject("cgs_edge_visibility_depth: invalid argument (slack=%g; the slack is finite and >= 0)", slack);
-    if (n_curves + n_lines == 0) return CGS_OK;
-    if (n_frames > 0 && (height <= 0 || width <= 0))
-        return reject("cgs_edge_visibility_depth: invalid argument (height=%d, width=%d)", height, width);
-    if ((n_curves > 0 && !curves) || (n_lines > 0 && !lines) || !counts_out ||
-        (n_frames > 0 && (!K || !w2c || !maps || !depth)))
-        return reject("cgs_edge_visibility_depth: invalid argument (NULL pointer)");
-    launch_edge_visibility_depth((hipStream_t)stream_, n_curves, curves, n_lines, lines, n_frames, K, w2c, height, width,
-                                 maps, invert, depth, slack, counts_out);
-    return finish("edge_visibility_depth", stream_);
-}
-
-int cgs_project_points_depth(int P, const float* points, int V, const double* intr, const double* w2c, int height, int width,
-                             const float* depth, double slack, double* uv_out, uint8_t* hidden_out, void* stream_) {
-    if (P < 0 || V < 0 || (long long)P * V > (1LL << 40))
-        return reject("cgs_project_points_depth: invalid argument (P=%d, V=%d)", P, V);
-    if (!slack_ok(slack))
-        return reject("cgs_project_points_depth: invalid argument (slack=%g; the slack is finite and >= 0)", slack);
-    if (P == 0 || V == 0) return CGS_OK;
-    if (height <= 0 || width <= 0)
-        return reject("cgs_project_points_depth: invalid argument (height=%d, width=%d)", height, width);
-    if (!points || !intr || !w2c || !depth || !uv_out)
-        return reject("cgs_project_points_depth: invalid argument (NULL pointer)");
-    launch_project_points_depth((hipStream_t)stream_, P, points, V, intr, w2c, height, width, depth, slack, uv_out,
-                                hidden_out);
-    return finish("project_points_depth", stream_);
-}
-
-int cgs_render_points_depth(int P, const float* points, const float* colors, int V, const double* intr, const double* w2c,
-                            int height, int width, const float* depth, double slack, double alpha, const double* background,
-                            float* out, int* kept, int* hidden, void* workspace, size_t workspace_bytes, void* stream_) {
-    if (P < 0 || V < 0 || height <= 0 || width <= 0 || (long long)height * width > (1LL << 31))
-        return reject("cgs_render_points_depth: invalid argument (P=%d, V=%d, height=%d, width=%d)", P, V, height, width);
-    if (!slack_ok(slack))
-        return reject("cgs_render_points_depth: invalid argument (slack=%g; the slack is finite and >= 0)", slack);
-    if (!(alpha >= 0.0 && alpha <= 1.0))
-        return reject("cgs_render_points_depth: invalid argument (alpha=%g, need 0 <= alpha <= 1)", alpha);
-    if (V == 0) return CGS_OK;
-    if (!intr || !w2c || !depth || !background || !out || !workspace || (P > 0 && (!points || !colors)))
-        return reject("cgs_render_points_depth: invalid argument (NULL pointer)");
-    const int per = render_points_views_per_chunk(P, V, height, width, workspace_bytes);
-    if (per <= 0)
-        return reject("cgs_render_points_depth: invalid argument (workspace of %zu bytes holds no view; one view needs %zu)",
-                      workspace_bytes, render_points_workspace_bytes(P, 1, height, width));
-    launch_render_points_depth((hipStream_t)stream_, P, points, colors, V, intr, w2c, height, width, depth, slack, alpha,
-                               background, out, kept, hidden, workspace, per);
-    return finish("render_points_depth", stream_);
-}
-
 // ---- occluding contours of a mesh (include/curvegs.h).  The slack is checked only with a plane: without one it is not read.
-int cgs_mesh_contours(int E, const float* edges, int V, const double* intr, const double* w2c, int height, int width,
-                      const float* depth, double slack, uint8_t* mask_out, void* stream_) {
-    if (E < 0 || V < 0) return reject("cgs_mesh_contours: invalid argument (E=%d, V=%d)", E, V);
+static int mesh_contours_entry(const char* name, int E, const float* edges, int V, const double* intr, const double* w2c,
+                               int height, int width, const float* depth, double slack, const double* near, uint8_t* mask_out,
+                               void* stream_) {
+    if (E < 0 || V < 0) return reject("%s: invalid argument (E=%d, V=%d)", name, E, V);
     if (!edt_size_ok(height, width))
-        return reject("cgs_mesh_contours: invalid argument (height=%d, width=%d; sizes lie in [1, %d])", height, width,
+        return reject("%s: invalid argument (height=%d, width=%d; sizes lie in [1, %d])", name, height, width,
                       CGS_EDT_MAX_SIZE);
     if (depth && !slack_ok(slack))
-        return reject("cgs_mesh_contours: invalid argument (slack=%g; with a depth plane the slack is finite and >= 0)", slack);
-    if (!intr || !w2c || !mask_out || (E > 0 && !edges))
-        return reject("cgs_mesh_contours: invalid argument (NULL pointer; E=%d)", E);
+        return reject("%s: invalid argument (slack=%g; with a depth plane the slack is finite and >= 0)", name, slack);
+    if (near && !near_ok(*near)) return reject("%s: invalid argument (near=%g; the plane is finite and > 0)", name, *near);
+    if (!intr || !w2c || !mask_out || (E > 0 && !edges)) return reject("%s: invalid argument (NULL pointer; E=%d)", name, E);
     if (V == 0) return CGS_OK;   // nothing to clear
-    if (launch_mesh_contours((hipStream_t)stream_, E, edges, V, intr, w2c, height, width, depth, slack, mask_out) != hipSuccess) {
-        set_error("cgs_mesh_contours: clearing the mask failed");
+    const DepthGate gate{depth, slack};
+    if (launch_mesh_contours((hipStream_t)stream_, E, edges, V, intr, w2c, height, width, depth ? &gate : nullptr, near,
+                             mask_out) != hipSuccess) {
+        set_error("%s: clearing the mask failed", name);
         return CGS_ERR_HIP;
     }
-    return finish("mesh_contours", stream_);
+    return finish(name + 4, stream_);
 }
 
-// ---- near-plane clipping (include/curvegs.h): the siblings' checks in their order, plus the plane itself.
-static bool near_ok(double near) { return near > 0.0 && !std::isinf(near); }   // a NaN fails the comparison
-
-int cgs_mesh_depth_clipped(int F, const float* tris, int V, const double* intr, const double* w2c, int height, int width,
-                           double near, float* depth, void* stream_) {
-    if (F < 0 || V < 0) return reject("cgs_mesh_depth_clipped: invalid argument (F=%d, V=%d)", F, V);
-    if (!edt_size_ok(height, width))
-        return reject("cgs_mesh_depth_clipped: invalid argument (height=%d, width=%d; sizes lie in [1, %d])", height, width,
-                      CGS_EDT_MAX_SIZE);
-    if (!near_ok(near)) return reject("cgs_mesh_depth_clipped: invalid argument (near=%g; the plane is finite and > 0)", near);
-    if (!intr || !w2c || !depth || (F > 0 && !tris))
-        return reject("cgs_mesh_depth_clipped: invalid argument (NULL pointer; F=%d)", F);
-    if (V == 0) return CGS_OK;   // nothing to write
-    if (launch_mesh_depth_clipped((hipStream_t)stream_, F, tris, V, intr, w2c, height, width, near, depth) != hipSuccess) {
-        set_error("cgs_mesh_depth_clipped: filling the depth planes failed");
-        return CGS_ERR_HIP;
-    }
-    return finish("mesh_depth_clipped", stream_);
+int cgs_mesh_contours(int E, const float* edges, int V, const double* intr, const double* w2c, int height, int width,
+                      const float* depth, double slack, uint8_t* mask_out, void* stream_) {
+    return mesh_contours_entry("cgs_mesh_contours", E, edges, V, intr, w2c, height, width, depth, slack, nullptr, mask_out,
+                               stream_);
 }
 
 int cgs_mesh_contours_clipped(int E, const float* edges, int V, const double* intr, const double* w2c, int height, int width,
                               const float* depth, double slack, double near, uint8_t* mask_out, void* stream_) {
-    if (E < 0 || V < 0) return reject("cgs_mesh_contours_clipped: invalid argument (E=%d, V=%d)", E, V);
-    if (!edt_size_ok(height, width))
-        return reject("cgs_mesh_contours_clipped: invalid argument (height=%d, width=%d; sizes lie in [1, %d])", height, width,
-                      CGS_EDT_MAX_SIZE);
-    if (depth && !slack_ok(slack))
-        return reject("cgs_mesh_contours_clipped: invalid argument (slack=%g; with a depth plane the slack is finite and >= 0)",
-                      slack);
-    if (!near_ok(near)) return reject("cgs_mesh_contours_clipped: invalid argument (near=%g; the plane is finite and > 0)", near);
-    if (!intr || !w2c || !mask_out || (E > 0 && !edges))
-        return reject("cgs_mesh_contours_clipped: invalid argument (NULL pointer; E=%d)", E);
-    if (V == 0) return CGS_OK;   // nothing to clear
-    if (launch_mesh_contours_clipped((hipStream_t)stream_, E, edges, V, intr, w2c, height, width, depth, slack, near, mask_out) !=
-        hipSuccess) {
-        set_error("cgs_mesh_contours_clipped: clearing the mask failed");
-        return CGS_ERR_HIP;
-    }
-    return finish("mesh_contours_clipped", stream_);
+    return mesh_contours_entry("cgs_mesh_contours_clipped", E, edges, V, intr, w2c, height, width, depth, slack, &near,
+                               mask_out, stream_);
 }
 
 // ---- the surfel z-buffer (include/curvegs.h): cgs_mesh_depth's checks in their order; normals may always be NULL.

@@ -153,13 +153,13 @@ __global__ void __launch_bounds__(OCC_THREADS) k_point_mask_depth(int P, const f
 
 // ------------------------------------------------------------------------------------------------ launchers
 template <bool CLIP>
-static hipError_t launch_mesh_depth_t(hipStream_t s, const char* name, int F, const float* tris, int V, const double* intr,
-                                      const double* w2c, int height, int width, double near, float* depth) {
+static hipError_t mesh_depth_launches(hipStream_t s, int F, const float* tris, int V, const double* intr, const double* w2c,
+                                      int height, int width, double near, float* depth) {
     const size_t plane = (size_t)height * (size_t)width;
     hipError_t e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(depth), (int)DEPTH_INF_BITS, (size_t)V * plane, s);
     if (e != hipSuccess || F == 0) return e;
     const unsigned blocks = (unsigned)(((long long)F + OCC_WAVES - 1) / OCC_WAVES);
-    ProfScope p(name, s);
+    ProfScope p(CLIP ? "mesh_depth_clipped" : "mesh_depth", s);
     for (int v0 = 0; v0 < V; v0 += OCC_MAX_VIEWS) {
         const int nv = std::min(OCC_MAX_VIEWS, V - v0);
         hipLaunchKernelGGL(k_mesh_depth<CLIP>, dim3(blocks, nv), dim3(OCC_THREADS), 0, s, F, tris, intr + 4 * (size_t)v0,
@@ -170,13 +170,9 @@ static hipError_t launch_mesh_depth_t(hipStream_t s, const char* name, int F, co
 }
 
 hipError_t launch_mesh_depth(hipStream_t s, int F, const float* tris, int V, const double* intr, const double* w2c,
-                             int height, int width, float* depth) {
-    return launch_mesh_depth_t<false>(s, "mesh_depth", F, tris, V, intr, w2c, height, width, 0.0, depth);
-}
-
-hipError_t launch_mesh_depth_clipped(hipStream_t s, int F, const float* tris, int V, const double* intr, const double* w2c,
-                                     int height, int width, double near, float* depth) {
-    return launch_mesh_depth_t<true>(s, "mesh_depth_clipped", F, tris, V, intr, w2c, height, width, near, depth);
+                             int height, int width, const double* near, float* depth) {
+    return near ? mesh_depth_launches<true>(s, F, tris, V, intr, w2c, height, width, *near, depth)
+                : mesh_depth_launches<false>(s, F, tris, V, intr, w2c, height, width, 0.0, depth);
 }
 
 void launch_depth_window_max(hipStream_t s, int V, int height, int width, int radius, const float* depth, float* out) {

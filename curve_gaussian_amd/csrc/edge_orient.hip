@@ -254,24 +254,22 @@ k_sample_support_oriented(int P, const float* __restrict__ pts, const int* __res
 template <bool GATED>
 static void sample_support_oriented_launch(hipStream_t s, int P, const float* points, const int* partner, int V,
                                            const double* intr, const double* w2c, int height, int width, const uint8_t* near,
-                                           int spread, int* tally, const float* depth, double slack, int* hidden) {
+                                           int spread, int* tally, DepthGate gate, int* hidden) {
     const unsigned blocks = (unsigned)(((long long)P + ORIENT_TALLY_THREADS - 1) / ORIENT_TALLY_THREADS);   // at most 2^23
     ProfScope p(GATED ? "sample_support_oriented_depth" : "sample_support_oriented", s);
     hipLaunchKernelGGL(k_sample_support_oriented<GATED>, dim3(blocks), dim3(ORIENT_TALLY_THREADS), 0, s, P, points, partner, V,
-                       intr, w2c, height, width, near, spread, tally, depth, slack, hidden);
+                       intr, w2c, height, width, near, spread, tally, gate.depth, gate.slack, hidden);
 }
 
 void launch_sample_support_oriented(hipStream_t s, int P, const float* points, const int* partner, int V, const double* intr,
-                                    const double* w2c, int height, int width, const uint8_t* near, int spread, int* tally) {
-    sample_support_oriented_launch<false>(s, P, points, partner, V, intr, w2c, height, width, near, spread, tally, nullptr, 0.0,
-                                          nullptr);
-}
-
-void launch_sample_support_oriented_depth(hipStream_t s, int P, const float* points, const int* partner, int V,
-                                          const double* intr, const double* w2c, int height, int width, const uint8_t* near,
-                                          int spread, const float* depth, double slack, int* tally, int* hidden) {
-    sample_support_oriented_launch<true>(s, P, points, partner, V, intr, w2c, height, width, near, spread, tally, depth, slack,
-                                         hidden);
+                                    const double* w2c, int height, int width, const uint8_t* near, int spread,
+                                    const DepthGate* gate, int* tally, int* hidden) {
+    if (gate)
+        sample_support_oriented_launch<true>(s, P, points, partner, V, intr, w2c, height, width, near, spread, tally, *gate,
+                                             hidden);
+    else
+        sample_support_oriented_launch<false>(s, P, points, partner, V, intr, w2c, height, width, near, spread, tally,
+                                              DepthGate{nullptr, 0.0}, nullptr);
 }
 
 }  // namespace cgs

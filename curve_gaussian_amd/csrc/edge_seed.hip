@@ -270,7 +270,7 @@ void launch_pack_near_bits(hipStream_t s, int V, int height, int width, const in
 }
 
 template <bool GATED>
-static void voxel_votes_launch(hipStream_t s, SeedGrid g, SeedViews views, SeedGate gate, int accumulate, unsigned short* seen,
+static void voxel_votes_launch(hipStream_t s, SeedGrid g, SeedViews views, DepthGate gate, int accumulate, unsigned short* seen,
                                unsigned short* hit, unsigned short* hidden) {
     const long long n = (long long)g.nx * g.ny * g.nz;
     const unsigned blocks = (unsigned)((n + SEED_THREADS - 1) / SEED_THREADS);   // <= 2^23
@@ -279,14 +279,10 @@ static void voxel_votes_launch(hipStream_t s, SeedGrid g, SeedViews views, SeedG
                        hidden);
 }
 
-void launch_voxel_votes(hipStream_t s, SeedGrid g, SeedViews views, int accumulate, unsigned short* seen,
-                        unsigned short* hit) {
-    voxel_votes_launch<false>(s, g, views, SeedGate{nullptr, 0.0}, accumulate, seen, hit, nullptr);
-}
-
-void launch_voxel_votes_depth(hipStream_t s, SeedGrid g, SeedViews views, SeedGate gate, int accumulate, unsigned short* seen,
-                              unsigned short* hit, unsigned short* hidden) {
-    voxel_votes_launch<true>(s, g, views, gate, accumulate, seen, hit, hidden);
+void launch_voxel_votes(hipStream_t s, SeedGrid g, SeedViews views, const DepthGate* gate, int accumulate,
+                        unsigned short* seen, unsigned short* hit, unsigned short* hidden) {
+    if (gate) voxel_votes_launch<true>(s, g, views, *gate, accumulate, seen, hit, hidden);
+    else voxel_votes_launch<false>(s, g, views, DepthGate{nullptr, 0.0}, accumulate, seen, hit, nullptr);
 }
 
 void launch_voxel_moments(hipStream_t s, int nx, int ny, int nz, const unsigned int* keep, int N, const int* centres,
@@ -298,7 +294,7 @@ void launch_voxel_moments(hipStream_t s, int nx, int ny, int nz, const unsigned 
 }
 
 template <bool GATED>
-static hipError_t ray_claims_launch(hipStream_t s, SeedGrid g, SeedViews views, SeedGate gate, int M, const int* index,
+static hipError_t ray_claims_launch(hipStream_t s, SeedGrid g, SeedViews views, DepthGate gate, int M, const int* index,
                                     const unsigned short* support, int clear, unsigned int* best) {
     if (clear && views.V > 0) {
         const size_t bytes = (size_t)views.V * (size_t)views.height * (size_t)views.width * sizeof(unsigned int);
@@ -312,18 +308,14 @@ static hipError_t ray_claims_launch(hipStream_t s, SeedGrid g, SeedViews views, 
     return hipSuccess;
 }
 
-hipError_t launch_ray_claims(hipStream_t s, SeedGrid g, SeedViews views, int M, const int* index,
+hipError_t launch_ray_claims(hipStream_t s, SeedGrid g, SeedViews views, const DepthGate* gate, int M, const int* index,
                              const unsigned short* support, int clear, unsigned int* best) {
-    return ray_claims_launch<false>(s, g, views, SeedGate{nullptr, 0.0}, M, index, support, clear, best);
-}
-
-hipError_t launch_ray_claims_depth(hipStream_t s, SeedGrid g, SeedViews views, SeedGate gate, int M, const int* index,
-                                   const unsigned short* support, int clear, unsigned int* best) {
-    return ray_claims_launch<true>(s, g, views, gate, M, index, support, clear, best);
+    return gate ? ray_claims_launch<true>(s, g, views, *gate, M, index, support, clear, best)
+                : ray_claims_launch<false>(s, g, views, DepthGate{nullptr, 0.0}, M, index, support, clear, best);
 }
 
 template <bool GATED>
-static void ray_wins_launch(hipStream_t s, SeedGrid g, SeedViews views, SeedGate gate, int M, const int* index,
+static void ray_wins_launch(hipStream_t s, SeedGrid g, SeedViews views, DepthGate gate, int M, const int* index,
                             const unsigned short* support, const unsigned int* best, int window, int margin, int accumulate,
                             unsigned short* wins) {
     const unsigned blocks = (unsigned)(((long long)M + SEED_THREADS - 1) / SEED_THREADS);   // <= 2^23
@@ -332,15 +324,14 @@ static void ray_wins_launch(hipStream_t s, SeedGrid g, SeedViews views, SeedGate
                        margin, accumulate, wins, gate);
 }
 
-void launch_ray_wins(hipStream_t s, SeedGrid g, SeedViews views, int M, const int* index, const unsigned short* support,
-                     const unsigned int* best, int window, int margin, int accumulate, unsigned short* wins) {
-    ray_wins_launch<false>(s, g, views, SeedGate{nullptr, 0.0}, M, index, support, best, window, margin, accumulate, wins);
-}
-
-void launch_ray_wins_depth(hipStream_t s, SeedGrid g, SeedViews views, SeedGate gate, int M, const int* index,
-                           const unsigned short* support, const unsigned int* best, int window, int margin, int accumulate,
-                           unsigned short* wins) {
-    ray_wins_launch<true>(s, g, views, gate, M, index, support, best, window, margin, accumulate, wins);
+void launch_ray_wins(hipStream_t s, SeedGrid g, SeedViews views, const DepthGate* gate, int M, const int* index,
+                     const unsigned short* support, const unsigned int* best, int window, int margin, int accumulate,
+                     unsigned short* wins) {
+    if (gate)
+        ray_wins_launch<true>(s, g, views, *gate, M, index, support, best, window, margin, accumulate, wins);
+    else
+        ray_wins_launch<false>(s, g, views, DepthGate{nullptr, 0.0}, M, index, support, best, window, margin, accumulate,
+                               wins);
 }
 
 }  // namespace cgs

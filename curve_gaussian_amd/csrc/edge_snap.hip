@@ -106,25 +106,22 @@ __global__ void __launch_bounds__(SNAP_THREADS) k_sample_snap_terms(int P, const
 template <bool GATED>
 static void sample_snap_terms_launch(hipStream_t s, int P, const float* points, int V, const double* intr, const double* w2c,
                                      int height, int width, const int* d2, int cap2, const double* dist_lut, double* terms,
-                                     int* views, const float* depth, double slack, int* hidden) {
+                                     int* views, DepthGate gate, int* hidden) {
     const unsigned blocks = (unsigned)(((long long)P + SNAP_THREADS - 1) / SNAP_THREADS);   // at most 2^23: one grid dimension
     ProfScope p(GATED ? "sample_snap_terms_depth" : "sample_snap_terms", s);
     hipLaunchKernelGGL(k_sample_snap_terms<GATED>, dim3(blocks), dim3(SNAP_THREADS), 0, s, P, points, V, intr, w2c, height,
-                       width, d2, cap2, dist_lut, terms, views, depth, slack, hidden);
+                       width, d2, cap2, dist_lut, terms, views, gate.depth, gate.slack, hidden);
 }
 
 void launch_sample_snap_terms(hipStream_t s, int P, const float* points, int V, const double* intr, const double* w2c,
-                              int height, int width, const int* d2, int cap2, const double* dist_lut, double* terms,
-                              int* views) {
-    sample_snap_terms_launch<false>(s, P, points, V, intr, w2c, height, width, d2, cap2, dist_lut, terms, views, nullptr, 0.0,
-                                    nullptr);
-}
-
-void launch_sample_snap_terms_depth(hipStream_t s, int P, const float* points, int V, const double* intr, const double* w2c,
-                                    int height, int width, const int* d2, int cap2, const double* dist_lut, const float* depth,
-                                    double slack, double* terms, int* views, int* hidden) {
-    sample_snap_terms_launch<true>(s, P, points, V, intr, w2c, height, width, d2, cap2, dist_lut, terms, views, depth, slack,
-                                   hidden);
+                              int height, int width, const int* d2, int cap2, const double* dist_lut, const DepthGate* gate,
+                              double* terms, int* views, int* hidden) {
+    if (gate)
+        sample_snap_terms_launch<true>(s, P, points, V, intr, w2c, height, width, d2, cap2, dist_lut, terms, views, *gate,
+                                       hidden);
+    else
+        sample_snap_terms_launch<false>(s, P, points, V, intr, w2c, height, width, d2, cap2, dist_lut, terms, views,
+                                        DepthGate{nullptr, 0.0}, nullptr);
 }
 
 }  // namespace cgs

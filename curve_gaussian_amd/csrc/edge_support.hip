@@ -85,7 +85,7 @@ __global__ void __launch_bounds__(SUPPORT_THREADS) k_edge_support(int E, int P, 
 template <bool GATED>
 static void edge_support_launches(hipStream_t s, int E, int P, const float* points, const int* offsets, int V,
                                   const double* intr, const double* w2c, int height, int width, const int* d2, int T,
-                                  const int* tol2, int* counts, const float* depth, double slack, int* hidden) {
+                                  const int* tol2, int* counts, DepthGate gate, int* hidden) {
     const size_t plane = (size_t)height * (size_t)width;
     const unsigned blocks = (unsigned)(((long long)E + SUPPORT_WAVES - 1) / SUPPORT_WAVES);
     ProfScope p(GATED ? "edge_support_depth" : "edge_support", s);
@@ -93,21 +93,18 @@ static void edge_support_launches(hipStream_t s, int E, int P, const float* poin
         const int nv = std::min(SUPPORT_MAX_VIEWS, V - v0);
         hipLaunchKernelGGL(k_edge_support<GATED>, dim3(blocks, nv), dim3(SUPPORT_THREADS), 0, s, E, P, points, offsets, V, v0,
                            intr + 4 * (size_t)v0, w2c + 12 * (size_t)v0, height, width, d2 + (size_t)v0 * plane, T, tol2,
-                           counts, GATED ? depth + (size_t)v0 * plane : nullptr, slack, hidden);
+                           counts, GATED ? gate.depth + (size_t)v0 * plane : nullptr, gate.slack, hidden);
     }
 }
 
 void launch_edge_support(hipStream_t s, int E, int P, const float* points, const int* offsets, int V, const double* intr,
-                         const double* w2c, int height, int width, const int* d2, int T, const int* tol2, int* counts) {
-    edge_support_launches<false>(s, E, P, points, offsets, V, intr, w2c, height, width, d2, T, tol2, counts, nullptr, 0.0,
-                                 nullptr);
-}
-
-void launch_edge_support_depth(hipStream_t s, int E, int P, const float* points, const int* offsets, int V,
-                               const double* intr, const double* w2c, int height, int width, const int* d2, int T,
-                               const int* tol2, const float* depth, double slack, int* counts, int* hidden) {
-    edge_support_launches<true>(s, E, P, points, offsets, V, intr, w2c, height, width, d2, T, tol2, counts, depth, slack,
-                                hidden);
+                         const double* w2c, int height, int width, const int* d2, int T, const int* tol2,
+                         const DepthGate* gate, int* counts, int* hidden) {
+    if (gate)
+        edge_support_launches<true>(s, E, P, points, offsets, V, intr, w2c, height, width, d2, T, tol2, counts, *gate, hidden);
+    else
+        edge_support_launches<false>(s, E, P, points, offsets, V, intr, w2c, height, width, d2, T, tol2, counts,
+                                     DepthGate{nullptr, 0.0}, nullptr);
 }
 
 }  // namespace cgs

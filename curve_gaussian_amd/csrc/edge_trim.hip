@@ -66,23 +66,22 @@ __global__ void __launch_bounds__(TRIM_THREADS) k_sample_support(int P, const fl
 
 template <bool GATED>
 static void sample_support_launch(hipStream_t s, int P, const float* points, int V, const double* intr, const double* w2c,
-                                  int height, int width, const int* d2, int T, const int* tol2, int* tally,
-                                  const float* depth, double slack, int* hidden) {
+                                  int height, int width, const int* d2, int T, const int* tol2, int* tally, DepthGate gate,
+                                  int* hidden) {
     const unsigned blocks = (unsigned)(((long long)P + TRIM_THREADS - 1) / TRIM_THREADS);   // at most 2^23: one grid dimension
     ProfScope p(GATED ? "sample_support_depth" : "sample_support", s);
     hipLaunchKernelGGL(k_sample_support<GATED>, dim3(blocks), dim3(TRIM_THREADS), 0, s, P, points, V, intr, w2c, height, width,
-                       d2, T, tol2, tally, depth, slack, hidden);
+                       d2, T, tol2, tally, gate.depth, gate.slack, hidden);
 }
 
 void launch_sample_support(hipStream_t s, int P, const float* points, int V, const double* intr, const double* w2c,
-                           int height, int width, const int* d2, int T, const int* tol2, int* tally) {
-    sample_support_launch<false>(s, P, points, V, intr, w2c, height, width, d2, T, tol2, tally, nullptr, 0.0, nullptr);
-}
-
-void launch_sample_support_depth(hipStream_t s, int P, const float* points, int V, const double* intr, const double* w2c,
-                                 int height, int width, const int* d2, int T, const int* tol2, const float* depth, double slack,
-                                 int* tally, int* hidden) {
-    sample_support_launch<true>(s, P, points, V, intr, w2c, height, width, d2, T, tol2, tally, depth, slack, hidden);
+                           int height, int width, const int* d2, int T, const int* tol2, const DepthGate* gate, int* tally,
+                           int* hidden) {
+    if (gate)
+        sample_support_launch<true>(s, P, points, V, intr, w2c, height, width, d2, T, tol2, tally, *gate, hidden);
+    else
+        sample_support_launch<false>(s, P, points, V, intr, w2c, height, width, d2, T, tol2, tally, DepthGate{nullptr, 0.0},
+                                     nullptr);
 }
 
 }  // namespace cgs

@@ -5,6 +5,15 @@
 
 namespace cgs {
 
+// The depth gate of the _depth entries (include/curvegs.h): one float32 [height, width] plane per view and the slack of
+// nv_hidden (point_projection.h).  A launcher with a gated form takes `const DepthGate* gate`: nullptr is the entry as it
+// always was (the GATED = false instantiation, no plane read, no hidden output written), a gate is its _depth sibling, with
+// the hidden output beside it.  The near plane of the _clipped entries is a nullable `const double* near` in the same way.
+struct DepthGate {
+    const float* depth;
+    double slack;
+};
+
 // preprocess.hip
 void launch_preprocess_fwd(hipStream_t s, int P, int D, int M, const float* means3D, const float* scales,
                            float scale_modifier, const float* rotations, const float* opacities, const float* shs,
@@ -154,10 +163,7 @@ void launch_nn1(hipStream_t s, int n_query, const float* query, int n_ref, const
 // visibility.hip
 void launch_edge_visibility(hipStream_t s, int n_curves, const double* curves, int n_lines, const double* lines,
                             int n_frames, const double* K, const double* w2c, int height, int width,
-                            const unsigned char* maps, int invert, int* counts);
-void launch_edge_visibility_depth(hipStream_t s, int n_curves, const double* curves, int n_lines, const double* lines,
-                                  int n_frames, const double* K, const double* w2c, int height, int width,
-                                  const unsigned char* maps, int invert, const float* depth, double slack, int* counts);
+                            const unsigned char* maps, int invert, const DepthGate* gate, int* counts);
 
 // metrics.hip
 size_t view_metrics_workspace_bytes(int n_views);
@@ -171,18 +177,13 @@ void launch_report_panels(hipStream_t s, int n_views, const cgs_report_view* vie
 
 // novel_view.hip
 void launch_project_points(hipStream_t s, int P, const float* points, int V, const double* intr, const double* w2c,
-                           int height, int width, double* uv);
+                           int height, int width, const DepthGate* gate, double* uv, uint8_t* hidden_out);
 size_t render_points_workspace_bytes(int P, int V, int H, int W);
 int render_points_views_per_chunk(int P, int V, int H, int W, size_t ws_bytes);
 int render_points_keep(double alpha);
 void launch_render_points(hipStream_t s, int P, const float* points, const float* colors, int V, const double* intr,
-                          const double* w2c, int height, int width, double alpha, const double* bg, float* out,
-                          int* kept, void* ws, int views_per_chunk);
-void launch_project_points_depth(hipStream_t s, int P, const float* points, int V, const double* intr, const double* w2c,
-                                 int height, int width, const float* depth, double slack, double* uv, uint8_t* hidden_out);
-void launch_render_points_depth(hipStream_t s, int P, const float* points, const float* colors, int V, const double* intr,
-                                const double* w2c, int height, int width, const float* depth, double slack, double alpha,
-                                const double* bg, float* out, int* kept, int* hidden, void* ws, int views_per_chunk);
+                          const double* w2c, int height, int width, const DepthGate* gate, double alpha, const double* bg,
+                          float* out, int* kept, int* hidden, void* ws, int views_per_chunk);
 
 // mesh.hip
 void launch_ellipsoid_vertices(hipStream_t s, int first, int count, const float* xyz, const float* rot, const float* scale,
@@ -236,39 +237,26 @@ struct SeedViews {  // the views of one call: cameras and packed near masks, str
     const double* w2c;
     const unsigned int* bits;
 };
-void launch_voxel_votes(hipStream_t s, SeedGrid g, SeedViews views, int accumulate, unsigned short* seen,
-                        unsigned short* hit);
+using SeedGate = DepthGate;   // the name the seed kernels know it by; passed to them by value
+void launch_voxel_votes(hipStream_t s, SeedGrid g, SeedViews views, const DepthGate* gate, int accumulate,
+                        unsigned short* seen, unsigned short* hit, unsigned short* hidden);
 void launch_voxel_moments(hipStream_t s, int nx, int ny, int nz, const unsigned int* keep, int N, const int* centres,
                           int radius, int* moments);
-hipError_t launch_ray_claims(hipStream_t s, SeedGrid g, SeedViews views, int M, const int* index,
+hipError_t launch_ray_claims(hipStream_t s, SeedGrid g, SeedViews views, const DepthGate* gate, int M, const int* index,
                              const unsigned short* support, int clear, unsigned int* best);
-void launch_ray_wins(hipStream_t s, SeedGrid g, SeedViews views, int M, const int* index, const unsigned short* support,
-                     const unsigned int* best, int window, int margin, int accumulate, unsigned short* wins);
-struct SeedGate {   // the depth gate of the _depth entries: one float32 [height, width] plane per view; passed by value
-    const float* depth;
-    double slack;
-};
-void launch_voxel_votes_depth(hipStream_t s, SeedGrid g, SeedViews views, SeedGate gate, int accumulate, unsigned short* seen,
-                              unsigned short* hit, unsigned short* hidden);
-hipError_t launch_ray_claims_depth(hipStream_t s, SeedGrid g, SeedViews views, SeedGate gate, int M, const int* index,
-                                   const unsigned short* support, int clear, unsigned int* best);
-void launch_ray_wins_depth(hipStream_t s, SeedGrid g, SeedViews views, SeedGate gate, int M, const int* index,
-                           const unsigned short* support, const unsigned int* best, int window, int margin, int accumulate,
-                           unsigned short* wins);
+void launch_ray_wins(hipStream_t s, SeedGrid g, SeedViews views, const DepthGate* gate, int M, const int* index,
+                     const unsigned short* support, const unsigned int* best, int window, int margin, int accumulate,
+                     unsigned short* wins);
 
 // edge_support.hip
 void launch_edge_support(hipStream_t s, int E, int P, const float* points, const int* offsets, int V, const double* intr,
-                         const double* w2c, int height, int width, const int* d2, int T, const int* tol2, int* counts);
-void launch_edge_support_depth(hipStream_t s, int E, int P, const float* points, const int* offsets, int V,
-                               const double* intr, const double* w2c, int height, int width, const int* d2, int T,
-                               const int* tol2, const float* depth, double slack, int* counts, int* hidden);
+                         const double* w2c, int height, int width, const int* d2, int T, const int* tol2,
+                         const DepthGate* gate, int* counts, int* hidden);
 
 // edge_trim.hip
 void launch_sample_support(hipStream_t s, int P, const float* points, int V, const double* intr, const double* w2c,
-                           int height, int width, const int* d2, int T, const int* tol2, int* tally);
-void launch_sample_support_depth(hipStream_t s, int P, const float* points, int V, const double* intr, const double* w2c,
-                                 int height, int width, const int* d2, int T, const int* tol2, const float* depth, double slack,
-                                 int* tally, int* hidden);
+                           int height, int width, const int* d2, int T, const int* tol2, const DepthGate* gate, int* tally,
+                           int* hidden);
 
 // edge_dedupe.hip
 size_t sample_cover_workspace_bytes(int P);
@@ -288,36 +276,25 @@ int launch_thin_masks(hipStream_t s, int V, int height, int width, uint8_t* mask
 void launch_mask_orientation(hipStream_t s, int V, int height, int width, const uint8_t* mask, uint8_t* code);
 void launch_oriented_near(hipStream_t s, int V, int height, int width, const uint8_t* code, int tol2, uint8_t* near);
 void launch_sample_support_oriented(hipStream_t s, int P, const float* points, const int* partner, int V, const double* intr,
-                                    const double* w2c, int height, int width, const uint8_t* near, int spread, int* tally);
-void launch_sample_support_oriented_depth(hipStream_t s, int P, const float* points, const int* partner, int V,
-                                          const double* intr, const double* w2c, int height, int width, const uint8_t* near,
-                                          int spread, const float* depth, double slack, int* tally, int* hidden);
+                                    const double* w2c, int height, int width, const uint8_t* near, int spread,
+                                    const DepthGate* gate, int* tally, int* hidden);
 
 // edge_snap.hip
 void launch_sample_snap_terms(hipStream_t s, int P, const float* points, int V, const double* intr, const double* w2c,
-                              int height, int width, const int* d2, int cap2, const double* dist_lut, double* terms,
-                              int* views);
-void launch_sample_snap_terms_depth(hipStream_t s, int P, const float* points, int V, const double* intr, const double* w2c,
-                                    int height, int width, const int* d2, int cap2, const double* dist_lut, const float* depth,
-                                    double slack, double* terms, int* views, int* hidden);
+                              int height, int width, const int* d2, int cap2, const double* dist_lut, const DepthGate* gate,
+                              double* terms, int* views, int* hidden);
 
 // edge_occlusion.hip
 hipError_t launch_mesh_depth(hipStream_t s, int F, const float* tris, int V, const double* intr, const double* w2c,
-                             int height, int width, float* depth);
+                             int height, int width, const double* near, float* depth);   // the cut is mesh_depth.h's
 void launch_depth_window_max(hipStream_t s, int V, int height, int width, int radius, const float* depth, float* out);
 hipError_t launch_point_mask_depth(hipStream_t s, int P, const float* points, int V, const double* intr, const double* w2c,
                                    int height, int width, const float* depth, double slack, uint8_t* mask, int* kept,
                                    int* hidden);
 
-// mesh_contours.hip
+// mesh_contours.hip (a NULL gate is no depth plane; the cut is mesh_depth.h's)
 hipError_t launch_mesh_contours(hipStream_t s, int E, const float* rows, int V, const double* intr, const double* w2c,
-                                int height, int width, const float* depth, double slack, uint8_t* mask);
-
-// near-plane clipping: edge_occlusion.hip, mesh_contours.hip (the cut is mesh_depth.h's)
-hipError_t launch_mesh_depth_clipped(hipStream_t s, int F, const float* tris, int V, const double* intr, const double* w2c,
-                                     int height, int width, double near, float* depth);
-hipError_t launch_mesh_contours_clipped(hipStream_t s, int E, const float* rows, int V, const double* intr, const double* w2c,
-                                        int height, int width, const float* depth, double slack, double near, uint8_t* mask);
+                                int height, int width, const DepthGate* gate, const double* near, uint8_t* mask);
 
 // surfel_depth.hip (the rule is surfel_depth.h's)
 hipError_t launch_surfel_depth(hipStream_t s, int P, const float* points, const float* normals, const float* radii, int V,

@@ -161,23 +161,22 @@ __global__ void __launch_bounds__(CONTOUR_THREADS) k_mesh_contours(int E, const 
 }
 
 template <bool CLIP>
-static hipError_t launch_mesh_contours_t(hipStream_t s, const char* name, int E, const float* rows, int V, const double* intr,
-                                         const double* w2c, int height, int width, const float* depth, double slack,
-                                         double near, uint8_t* mask) {
+static hipError_t mesh_contours_launches(hipStream_t s, int E, const float* rows, int V, const double* intr, const double* w2c,
+                                         int height, int width, const DepthGate* gate, double near, uint8_t* mask) {
     const size_t plane = (size_t)height * (size_t)width;
     hipError_t err = hipMemsetAsync(mask, 0, (size_t)V * plane, s);
     if (err != hipSuccess || E == 0) return err;
     const unsigned blocks = (unsigned)(((long long)E + CONTOUR_THREADS - 1) / CONTOUR_THREADS);
-    ProfScope p(name, s);
+    ProfScope p(CLIP ? "mesh_contours_clipped" : "mesh_contours", s);
     for (int v0 = 0; v0 < V; v0 += CONTOUR_MAX_VIEWS) {
         const int nv = std::min(CONTOUR_MAX_VIEWS, V - v0);
         const dim3 grid(blocks, nv);
         const double* K = intr + 4 * (size_t)v0;
         const double* M = w2c + 12 * (size_t)v0;
         uint8_t* out = mask + (size_t)v0 * plane;
-        if (depth)
+        if (gate)
             hipLaunchKernelGGL((k_mesh_contours<true, CLIP>), grid, dim3(CONTOUR_THREADS), 0, s, E, rows, K, M, height, width,
-                               depth + (size_t)v0 * plane, slack, near, out);
+                               gate->depth + (size_t)v0 * plane, gate->slack, near, out);
         else
             hipLaunchKernelGGL((k_mesh_contours<false, CLIP>), grid, dim3(CONTOUR_THREADS), 0, s, E, rows, K, M, height, width,
                                (const float*)nullptr, 0.0, near, out);
@@ -186,14 +185,9 @@ static hipError_t launch_mesh_contours_t(hipStream_t s, const char* name, int E,
 }
 
 hipError_t launch_mesh_contours(hipStream_t s, int E, const float* rows, int V, const double* intr, const double* w2c,
-                                int height, int width, const float* depth, double slack, uint8_t* mask) {
-    return launch_mesh_contours_t<false>(s, "mesh_contours", E, rows, V, intr, w2c, height, width, depth, slack, 0.0, mask);
-}
-
-hipError_t launch_mesh_contours_clipped(hipStream_t s, int E, const float* rows, int V, const double* intr, const double* w2c,
-                                        int height, int width, const float* depth, double slack, double near, uint8_t* mask) {
-    return launch_mesh_contours_t<true>(s, "mesh_contours_clipped", E, rows, V, intr, w2c, height, width, depth, slack, near,
-                                        mask);
+                                int height, int width, const DepthGate* gate, const double* near, uint8_t* mask) {
+    return near ? mesh_contours_launches<true>(s, E, rows, V, intr, w2c, height, width, gate, *near, mask)
+                : mesh_contours_launches<false>(s, E, rows, V, intr, w2c, height, width, gate, 0.0, mask);
 }
 
 }  // namespace cgs

@@ -275,33 +275,28 @@ static int nv_point_blocks(int P) { return std::max(1, std::min(NV_POINT_BLOCKS_
 
 template <bool GATED>
 static void project_points_launches(hipStream_t s, int P, const float* points, int V, const double* intr, const double* w2c,
-                                    int height, int width, double* uv, const float* depth, double slack,
-                                    uint8_t* hidden_out) {
+                                    int height, int width, double* uv, DepthGate gate, uint8_t* hidden_out) {
     const size_t plane = (size_t)height * (size_t)width;
     ProfScope p(GATED ? "project_points_depth" : "project_points", s);
     for (int v0 = 0; v0 < V; v0 += NV_MAX_VIEWS) {
         const int nv = std::min(NV_MAX_VIEWS, V - v0);
         hipLaunchKernelGGL(k_nv_project<GATED>, dim3(nv_point_blocks(P), nv), dim3(NV_BLOCK), 0, s, P, points,
                            intr + 4 * (size_t)v0, w2c + 12 * (size_t)v0, height, width, uv + 2 * (size_t)v0 * (size_t)P,
-                           GATED ? depth + (size_t)v0 * plane : nullptr, slack,
+                           GATED ? gate.depth + (size_t)v0 * plane : nullptr, gate.slack,
                            GATED && hidden_out ? hidden_out + (size_t)v0 * (size_t)P : nullptr);
     }
 }
 
 void launch_project_points(hipStream_t s, int P, const float* points, int V, const double* intr, const double* w2c,
-                           int height, int width, double* uv) {
-    project_points_launches<false>(s, P, points, V, intr, w2c, height, width, uv, nullptr, 0.0, nullptr);
-}
-
-void launch_project_points_depth(hipStream_t s, int P, const float* points, int V, const double* intr, const double* w2c,
-                                 int height, int width, const float* depth, double slack, double* uv, uint8_t* hidden_out) {
-    project_points_launches<true>(s, P, points, V, intr, w2c, height, width, uv, depth, slack, hidden_out);
+                           int height, int width, const DepthGate* gate, double* uv, uint8_t* hidden_out) {
+    if (gate) project_points_launches<true>(s, P, points, V, intr, w2c, height, width, uv, *gate, hidden_out);
+    else project_points_launches<false>(s, P, points, V, intr, w2c, height, width, uv, DepthGate{nullptr, 0.0}, nullptr);
 }
 
 template <bool GATED>
 static void render_points_launches(hipStream_t s, int P, const float* points, const float* colors, int V, const double* intr,
                                    const double* w2c, int height, int width, double alpha, const double* bg, float* out,
-                                   int* kept, void* ws, int views_per_chunk, const float* depth, double slack, int* hidden) {
+                                   int* kept, void* ws, int views_per_chunk, DepthGate gate, int* hidden) {
     const long long plane = (long long)height * width;
     const int keep_max = render_points_keep(alpha);
     if (GATED && hidden)   // cleared by a kernel: a captured memset node clears once (zero_async in api.hip)
@@ -326,7 +321,7 @@ static void render_points_launches(hipStream_t s, int P, const float* points, co
             hipLaunchKernelGGL(k_nv_zero, dim3(zblocks), dim3(NV_BLOCK), 0, s, n, counts);
             if (P > 0)
                 hipLaunchKernelGGL(k_nv_bin<GATED>, dim3(nv_point_blocks(P), nv), dim3(NV_BLOCK), 0, s, P, points, intr, w2c,
-                                   v0, height, width, counts, (unsigned int*)nullptr, 0, depth, slack, hidden);
+                                   v0, height, width, counts, (unsigned int*)nullptr, 0, gate.depth, gate.slack, hidden);
         }
         {
             ProfScope p("render_points_scan", s);
@@ -340,7 +335,7 @@ static void render_points_launches(hipStream_t s, int P, const float* points, co
         if (P > 0) {
             ProfScope p("render_points_fill", s);
             hipLaunchKernelGGL(k_nv_bin<GATED>, dim3(nv_point_blocks(P), nv), dim3(NV_BLOCK), 0, s, P, points, intr, w2c, v0,
-                               height, width, offsets, list, 1, depth, slack, hidden);
+                               height, width, offsets, list, 1, gate.depth, gate.slack, hidden);
         }
         {
             ProfScope p("render_points_composite", s);
@@ -350,19 +345,16 @@ static void render_points_launches(hipStream_t s, int P, const float* points, co
     }
 }
 
-void launch_render_points(hipStream_t s, int P, const float* points, const float* colors, int V, const double* intr,
-                          const double* w2c, int height, int width, double alpha, const double* bg, float* out,
-                          int* kept, void* ws, int views_per_chunk) {
-    render_points_launches<false>(s, P, points, colors, V, intr, w2c, height, width, alpha, bg, out, kept, ws,
-                                  views_per_chunk, nullptr, 0.0, nullptr);
-}
-
 // The lists of the gated form can only be shorter: the workspace of cgs_render_points holds them.
-void launch_render_points_depth(hipStream_t s, int P, const float* points, const float* colors, int V, const double* intr,
-                                const double* w2c, int height, int width, const float* depth, double slack, double alpha,
-                                const double* bg, float* out, int* kept, int* hidden, void* ws, int views_per_chunk) {
-    render_points_launches<true>(s, P, points, colors, V, intr, w2c, height, width, alpha, bg, out, kept, ws,
-                                 views_per_chunk, depth, slack, hidden);
+void launch_render_points(hipStream_t s, int P, const float* points, const float* colors, int V, const double* intr,
+                          const double* w2c, int height, int width, const DepthGate* gate, double alpha, const double* bg,
+                          float* out, int* kept, int* hidden, void* ws, int views_per_chunk) {
+    if (gate)
+        render_points_launches<true>(s, P, points, colors, V, intr, w2c, height, width, alpha, bg, out, kept, ws,
+                                     views_per_chunk, *gate, hidden);
+    else
+        render_points_launches<false>(s, P, points, colors, V, intr, w2c, height, width, alpha, bg, out, kept, ws,
+                                      views_per_chunk, DepthGate{nullptr, 0.0}, nullptr);
 }
 
 }  // namespace cgs

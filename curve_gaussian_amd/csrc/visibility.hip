@@ -132,7 +132,7 @@ static int visibility_per_slice(int n_edges, int n_frames) {
 template <bool GATED>
 static void edge_visibility_launches(hipStream_t s, int n_curves, const double* curves, int n_lines, const double* lines,
                                      int n_frames, const double* K, const double* w2c, int height, int width,
-                                     const unsigned char* maps, int invert, int* counts, const float* depth, double slack) {
+                                     const unsigned char* maps, int invert, int* counts, DepthGate gate) {
     const int n_edges = n_curves + n_lines;
     const int eblocks = (n_edges + VIS_BLOCK - 1) / VIS_BLOCK;
     const int n_out = GATED ? 2 * n_edges : n_edges;   // n_edges <= 2^30: 2 n_edges - 1 + VIS_BLOCK fits an int
@@ -142,21 +142,18 @@ static void edge_visibility_launches(hipStream_t s, int n_curves, const double* 
     const int slices = (n_frames + per - 1) / per;
     ProfScope p(GATED ? "edge_visibility_depth" : "edge_visibility", s);
     hipLaunchKernelGGL(k_edge_visibility<GATED>, dim3(eblocks, slices), dim3(VIS_BLOCK), 0, s, n_curves, curves, n_lines,
-                       lines, n_frames, per, K, w2c, height, width, maps, invert, counts, depth, slack);
+                       lines, n_frames, per, K, w2c, height, width, maps, invert, counts, gate.depth, gate.slack);
 }
 
 void launch_edge_visibility(hipStream_t s, int n_curves, const double* curves, int n_lines, const double* lines,
                             int n_frames, const double* K, const double* w2c, int height, int width,
-                            const unsigned char* maps, int invert, int* counts) {
-    edge_visibility_launches<false>(s, n_curves, curves, n_lines, lines, n_frames, K, w2c, height, width, maps, invert,
-                                    counts, nullptr, 0.0);
-}
-
-void launch_edge_visibility_depth(hipStream_t s, int n_curves, const double* curves, int n_lines, const double* lines,
-                                  int n_frames, const double* K, const double* w2c, int height, int width,
-                                  const unsigned char* maps, int invert, const float* depth, double slack, int* counts) {
-    edge_visibility_launches<true>(s, n_curves, curves, n_lines, lines, n_frames, K, w2c, height, width, maps, invert,
-                                   counts, depth, slack);
+                            const unsigned char* maps, int invert, const DepthGate* gate, int* counts) {
+    if (gate)
+        edge_visibility_launches<true>(s, n_curves, curves, n_lines, lines, n_frames, K, w2c, height, width, maps, invert,
+                                       counts, *gate);
+    else
+        edge_visibility_launches<false>(s, n_curves, curves, n_lines, lines, n_frames, K, w2c, height, width, maps, invert,
+                                        counts, DepthGate{nullptr, 0.0});
 }
 
 }  // namespace cgs

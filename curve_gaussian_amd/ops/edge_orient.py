@@ -282,30 +282,16 @@ def oriented_tally(points, partner, intrinsics, w2c, near, spread=SPREAD, backen
             raise ValueError(f"oriented_tally: out must be a contiguous int32 [{P},2] tensor")
     EO.check_hidden_out("oriented_tally", hidden_out, depth, P)
     if backend == "host":
-        if (near.is_cuda or pts.is_cuda or partner.is_cuda or (out is not None and out.is_cuda)
-                or (hidden_out is not None and hidden_out.is_cuda)):
-            raise ValueError("oriented_tally: backend='host' takes host arrays and CPU tensors")
+        SP._host_only("oriented_tally", near, pts, partner, out, hidden_out)
         if out is None:
             out = torch.zeros((P, 2), dtype=torch.int32)
-        if depth is None:
-            _tally_host(pts.numpy(), partner.numpy(), K, M, near.numpy(), spread, out.numpy())
-            return out
-        depth, slack = EO.operator_depth("oriented_tally", depth, slack, V, int(near.shape[1]), int(near.shape[2]), "host")
+        if depth is not None:
+            depth, slack = EO.operator_depth("oriented_tally", depth, slack, V, int(near.shape[1]), int(near.shape[2]), "host")
         _tally_host(pts.numpy(), partner.numpy(), K, M, near.numpy(), spread, out.numpy(), depth, slack,
                     None if hidden_out is None else hidden_out.numpy())
         return out
-    L.require_gpu_tensor(near, "oriented_tally: near")
-    dev = near.device
-    if device is not None and torch.device(device) != dev and torch.device(device) != torch.device(dev.type):
-        raise L.CurveGSError(f"oriented_tally: near is on {dev}, device={device}: all tensors must be on one device")
-    for name, t in (("points", pts), ("partner", partner)):
-        if t.is_cuda and t.device != dev:
-            raise L.CurveGSError(f"oriented_tally: {name} are on {t.device}, near on {dev}: all tensors must be on one device")
-    if out is not None and out.device != dev:
-        raise L.CurveGSError(f"oriented_tally: out is on {out.device}, near on {dev}: all tensors must be on one device")
-    if hidden_out is not None and hidden_out.device != dev:
-        raise L.CurveGSError(f"oriented_tally: hidden_out is on {hidden_out.device}, near on {dev}: all tensors must be on one "
-                             "device")
+    dev = SP._one_device("oriented_tally", "near", near, device, uploaded=[("points", pts), ("partner", partner)],
+                         resident=[("out", [out]), ("hidden_out", [hidden_out])])
     with L.device_guard(dev):
         pts, partner = pts.to(dev).contiguous(), partner.to(dev).contiguous()
         if out is None:
@@ -315,15 +301,12 @@ def oriented_tally(points, partner, intrinsics, w2c, near, spread=SPREAD, backen
                                              dev)
         if P > 0 and V > 0:
             Kd, Md = ES.cameras_on(dev, K, M)
+            args = [P, L.ptr(pts), L.ptr(partner), V, L.ptr(Kd), L.ptr(Md), int(near.shape[1]), int(near.shape[2]),
+                    L.ptr(near), spread]
             if depth is None:
-                rc = L.load().cgs_sample_support_oriented(P, L.ptr(pts), L.ptr(partner), V, L.ptr(Kd), L.ptr(Md),
-                                                          int(near.shape[1]), int(near.shape[2]), L.ptr(near), spread,
-                                                          L.ptr(out), L.raw_stream(dev))
-                L.check(rc, "cgs_sample_support_oriented")
+                L.check(L.load().cgs_sample_support_oriented(*args, L.ptr(out), L.raw_stream(dev)),
+                        "cgs_sample_support_oriented")
             else:
-                rc = L.load().cgs_sample_support_oriented_depth(P, L.ptr(pts), L.ptr(partner), V, L.ptr(Kd), L.ptr(Md),
-                                                                int(near.shape[1]), int(near.shape[2]), L.ptr(near), spread,
-                                                                L.ptr(depth), slack, L.ptr(out), L.ptr(hidden_out),
-                                                                L.raw_stream(dev))
-                L.check(rc, "cgs_sample_support_oriented_depth")
+                L.check(L.load().cgs_sample_support_oriented_depth(*args, L.ptr(depth), slack, L.ptr(out), L.ptr(hidden_out),
+                                                                   L.raw_stream(dev)), "cgs_sample_support_oriented_depth")
     return out

@@ -168,30 +168,16 @@ def snap_terms(points, intrinsics, w2c, d2, capture_px, backend="gpu", device=No
     lut = distance_table(cap2)
     EO.check_hidden_out("snap_terms", hidden_out, depth, P)
     if backend == "host":
-        if (d2.is_cuda or pts.is_cuda or (out is not None and (terms.is_cuda or views.is_cuda))
-                or (hidden_out is not None and hidden_out.is_cuda)):
-            raise ValueError("snap_terms: backend='host' takes host arrays and CPU tensors")
+        SP._host_only("snap_terms", d2, pts, *(out or ()), hidden_out)
         if out is None:
             terms, views = torch.zeros((P, TERMS), dtype=torch.float64), torch.zeros((P,), dtype=torch.int32)
-        if depth is None:
-            _terms_host(pts.numpy(), K, M, d2.numpy(), cap2, lut, terms.numpy(), views.numpy())
-            return terms, views
-        depth, slack = EO.operator_depth("snap_terms", depth, slack, V, int(d2.shape[1]), int(d2.shape[2]), "host")
+        if depth is not None:
+            depth, slack = EO.operator_depth("snap_terms", depth, slack, V, int(d2.shape[1]), int(d2.shape[2]), "host")
         _terms_host(pts.numpy(), K, M, d2.numpy(), cap2, lut, terms.numpy(), views.numpy(), depth, slack,
                     None if hidden_out is None else hidden_out.numpy())
         return terms, views
-    L.require_gpu_tensor(d2, "snap_terms: d2")
-    dev = d2.device
-    if device is not None and torch.device(device) != dev and torch.device(device) != torch.device(dev.type):
-        raise L.CurveGSError(f"snap_terms: d2 is on {dev}, device={device}: all tensors must be on one device")
-    if pts.is_cuda and pts.device != dev:
-        raise L.CurveGSError(f"snap_terms: points are on {pts.device}, d2 on {dev}: all tensors must be on one device")
-    if out is not None and (terms.device != dev or views.device != dev):
-        raise L.CurveGSError(f"snap_terms: out is on {terms.device} and {views.device}, d2 on {dev}: all tensors must be on "
-                             "one device")
-    if hidden_out is not None and hidden_out.device != dev:
-        raise L.CurveGSError(f"snap_terms: hidden_out is on {hidden_out.device}, d2 on {dev}: all tensors must be on one "
-                             "device")
+    dev = SP._one_device("snap_terms", "d2", d2, device, uploaded=[("points", pts)],
+                         resident=[("out", out or ()), ("hidden_out", [hidden_out])])
     with L.device_guard(dev):
         pts = pts.to(dev).contiguous()
         if out is None:
@@ -202,16 +188,14 @@ def snap_terms(points, intrinsics, w2c, d2, capture_px, backend="gpu", device=No
         if P > 0 and V > 0:
             lut_d = torch.from_numpy(lut).to(dev)
             Kd, Md = ES.cameras_on(dev, K, M)
+            args = [P, L.ptr(pts), V, L.ptr(Kd), L.ptr(Md), int(d2.shape[1]), int(d2.shape[2]), L.ptr(d2), cap2, L.ptr(lut_d)]
             if depth is None:
-                rc = L.load().cgs_sample_snap_terms(P, L.ptr(pts), V, L.ptr(Kd), L.ptr(Md), int(d2.shape[1]),
-                                                    int(d2.shape[2]), L.ptr(d2), cap2, L.ptr(lut_d), L.ptr(terms),
-                                                    L.ptr(views), L.raw_stream(dev))
-                L.check(rc, "cgs_sample_snap_terms")
+                L.check(L.load().cgs_sample_snap_terms(*args, L.ptr(terms), L.ptr(views), L.raw_stream(dev)),
+                        "cgs_sample_snap_terms")
             else:
-                rc = L.load().cgs_sample_snap_terms_depth(P, L.ptr(pts), V, L.ptr(Kd), L.ptr(Md), int(d2.shape[1]),
-                                                          int(d2.shape[2]), L.ptr(d2), cap2, L.ptr(lut_d), L.ptr(depth), slack,
-                                                          L.ptr(terms), L.ptr(views), L.ptr(hidden_out), L.raw_stream(dev))
-                L.check(rc, "cgs_sample_snap_terms_depth")
+                L.check(L.load().cgs_sample_snap_terms_depth(*args, L.ptr(depth), slack, L.ptr(terms), L.ptr(views),
+                                                             L.ptr(hidden_out), L.raw_stream(dev)),
+                        "cgs_sample_snap_terms_depth")
     return terms, views
 
 

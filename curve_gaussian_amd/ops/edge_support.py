@@ -143,6 +143,31 @@ def _d2(d2, V):
     return t.contiguous()
 
 
+def _host_only(who, *tensors):
+    """``backend="host"``: none of the tensors (None: not given) may be on a GPU."""
+    if any(t is not None and t.is_cuda for t in tensors):
+        raise ValueError(f"{who}: backend='host' takes host arrays and CPU tensors")
+
+
+def _one_device(who, anchor_name, anchor, device, uploaded=(), resident=()):
+    """``backend="gpu"``: the device of the call, which is the anchor's (d2 or near; CurveGSError unless it is on a GPU).
+    ``device``, when given, must be it.  So must the device of every (name, tensor) of ``uploaded`` that is on a GPU -- one
+    on the host is the caller's to upload -- and of every (name, tensors) of ``resident``, the outputs (None: not given)."""
+    L.require_gpu_tensor(anchor, f"{who}: {anchor_name}")
+    dev = anchor.device
+    if device is not None and torch.device(device) != dev and torch.device(device) != torch.device(dev.type):
+        raise L.CurveGSError(f"{who}: {anchor_name} is on {dev}, device={device}: all tensors must be on one device")
+    for name, t in uploaded:
+        if t.is_cuda and t.device != dev:
+            raise L.CurveGSError(f"{who}: {name} are on {t.device}, {anchor_name} on {dev}: all tensors must be on one device")
+    for name, tensors in resident:
+        devices = [t.device for t in tensors if t is not None]
+        if any(d != dev for d in devices):
+            raise L.CurveGSError(f"{who}: {name} is on {' and '.join(map(str, devices))}, {anchor_name} on {dev}: all tensors "
+                                 "must be on one device")
+    return dev
+
+
 def _counts_host(pts, off, K, M, d2, tol2, depth=None, slack=0.0, hidden=None):
     """``depth`` float32 [V,H,W] or None; ``hidden`` int32 [E,V] or None, written when there is a depth."""
     E, V, T = off.size - 1, K.shape[0], len(tol2)
@@ -195,20 +220,14 @@ def support_counts(points, offsets, intrinsics, w2c, d2, tolerances_px, backend=
     d2 = _d2(d2, V)
     E, T = off.size - 1, len(tol2)
     if backend == "host":
-        if d2.is_cuda or pts.is_cuda:
-            raise ValueError("support_counts: backend='host' takes host arrays and CPU tensors")
-        if depth is None:
-            return torch.from_numpy(_counts_host(pts.numpy(), off, K, M, d2.numpy(), tol2))
-        depth, slack = EO.operator_depth("support_counts", depth, slack, V, int(d2.shape[1]), int(d2.shape[2]), "host")
-        hidden = np.zeros((E, V), np.int32)
+        _host_only("support_counts", d2, pts)
+        hidden = None
+        if depth is not None:
+            depth, slack = EO.operator_depth("support_counts", depth, slack, V, int(d2.shape[1]), int(d2.shape[2]), "host")
+            hidden = np.zeros((E, V), np.int32)
         counts = torch.from_numpy(_counts_host(pts.numpy(), off, K, M, d2.numpy(), tol2, depth, slack, hidden))
         return (counts, torch.from_numpy(hidden)) if return_hidden else counts
-    L.require_gpu_tensor(d2, "support_counts: d2")
-    dev = d2.device
-    if device is not None and torch.device(device) != dev and torch.device(device) != torch.device(dev.type):
-        raise L.CurveGSError(f"support_counts: d2 is on {dev}, device={device}: all tensors must be on one device")
-    if pts.is_cuda and pts.device != dev:
-        raise L.CurveGSError(f"support_counts: points are on {pts.device}, d2 on {dev}: all tensors must be on one device")
+    dev = _one_device("support_counts", "d2", d2, device, uploaded=[("points", pts)])
     if E * V * (1 + T) > np.iinfo(np.int64).max // 4:
         raise ValueError("support_counts: the counts do not fit")
     with L.device_guard(dev):
@@ -221,16 +240,13 @@ def support_counts(points, offsets, intrinsics, w2c, d2, tolerances_px, backend=
             off_d = torch.from_numpy(off).to(dev)
             tol_d = torch.tensor(tol2, dtype=torch.int32).to(dev)
             Kd, Md = ES.cameras_on(dev, K, M)
+            args = [E, int(pts.shape[0]), L.ptr(pts), L.ptr(off_d), V, L.ptr(Kd), L.ptr(Md), int(d2.shape[1]),
+                    int(d2.shape[2]), L.ptr(d2), T, L.ptr(tol_d)]
             if depth is None:
-                rc = L.load().cgs_edge_support(E, int(pts.shape[0]), L.ptr(pts), L.ptr(off_d), V, L.ptr(Kd), L.ptr(Md),
-                                               int(d2.shape[1]), int(d2.shape[2]), L.ptr(d2), T, L.ptr(tol_d), L.ptr(out),
-                                               L.raw_stream(dev))
-                L.check(rc, "cgs_edge_support")
+                L.check(L.load().cgs_edge_support(*args, L.ptr(out), L.raw_stream(dev)), "cgs_edge_support")
             else:
-                rc = L.load().cgs_edge_support_depth(E, int(pts.shape[0]), L.ptr(pts), L.ptr(off_d), V, L.ptr(Kd), L.ptr(Md),
-                                                     int(d2.shape[1]), int(d2.shape[2]), L.ptr(d2), T, L.ptr(tol_d),
-                                                     L.ptr(depth), slack, L.ptr(out), L.ptr(hidden), L.raw_stream(dev))
-                L.check(rc, "cgs_edge_support_depth")
+                L.check(L.load().cgs_edge_support_depth(*args, L.ptr(depth), slack, L.ptr(out), L.ptr(hidden),
+                                                        L.raw_stream(dev)), "cgs_edge_support_depth")
     return (out, hidden) if return_hidden else out
 
 

@@ -112,28 +112,16 @@ def sample_tally(points, intrinsics, w2c, d2, tolerances_px, backend="gpu", devi
             raise ValueError(f"sample_tally: out must be a contiguous int32 [{P},{1 + T}] tensor")
     EO.check_hidden_out("sample_tally", hidden_out, depth, P)
     if backend == "host":
-        if d2.is_cuda or pts.is_cuda or (out is not None and out.is_cuda) or (hidden_out is not None and hidden_out.is_cuda):
-            raise ValueError("sample_tally: backend='host' takes host arrays and CPU tensors")
+        SP._host_only("sample_tally", d2, pts, out, hidden_out)
         if out is None:
             out = torch.zeros((P, 1 + T), dtype=torch.int32)
-        if depth is None:
-            _tally_host(pts.numpy(), K, M, d2.numpy(), tol2, out.numpy())
-            return out
-        depth, slack = EO.operator_depth("sample_tally", depth, slack, V, int(d2.shape[1]), int(d2.shape[2]), "host")
+        if depth is not None:
+            depth, slack = EO.operator_depth("sample_tally", depth, slack, V, int(d2.shape[1]), int(d2.shape[2]), "host")
         _tally_host(pts.numpy(), K, M, d2.numpy(), tol2, out.numpy(), depth, slack,
                     None if hidden_out is None else hidden_out.numpy())
         return out
-    L.require_gpu_tensor(d2, "sample_tally: d2")
-    dev = d2.device
-    if device is not None and torch.device(device) != dev and torch.device(device) != torch.device(dev.type):
-        raise L.CurveGSError(f"sample_tally: d2 is on {dev}, device={device}: all tensors must be on one device")
-    if pts.is_cuda and pts.device != dev:
-        raise L.CurveGSError(f"sample_tally: points are on {pts.device}, d2 on {dev}: all tensors must be on one device")
-    if out is not None and out.device != dev:
-        raise L.CurveGSError(f"sample_tally: out is on {out.device}, d2 on {dev}: all tensors must be on one device")
-    if hidden_out is not None and hidden_out.device != dev:
-        raise L.CurveGSError(f"sample_tally: hidden_out is on {hidden_out.device}, d2 on {dev}: all tensors must be on one "
-                             "device")
+    dev = SP._one_device("sample_tally", "d2", d2, device, uploaded=[("points", pts)],
+                         resident=[("out", [out]), ("hidden_out", [hidden_out])])
     with L.device_guard(dev):
         pts = pts.to(dev).contiguous()
         if out is None:
@@ -143,15 +131,12 @@ def sample_tally(points, intrinsics, w2c, d2, tolerances_px, backend="gpu", devi
         if P > 0 and V > 0:
             tol_d = torch.tensor(tol2, dtype=torch.int32).to(dev)
             Kd, Md = ES.cameras_on(dev, K, M)
+            args = [P, L.ptr(pts), V, L.ptr(Kd), L.ptr(Md), int(d2.shape[1]), int(d2.shape[2]), L.ptr(d2), T, L.ptr(tol_d)]
             if depth is None:
-                rc = L.load().cgs_sample_support(P, L.ptr(pts), V, L.ptr(Kd), L.ptr(Md), int(d2.shape[1]), int(d2.shape[2]),
-                                                 L.ptr(d2), T, L.ptr(tol_d), L.ptr(out), L.raw_stream(dev))
-                L.check(rc, "cgs_sample_support")
+                L.check(L.load().cgs_sample_support(*args, L.ptr(out), L.raw_stream(dev)), "cgs_sample_support")
             else:
-                rc = L.load().cgs_sample_support_depth(P, L.ptr(pts), V, L.ptr(Kd), L.ptr(Md), int(d2.shape[1]),
-                                                       int(d2.shape[2]), L.ptr(d2), T, L.ptr(tol_d), L.ptr(depth), slack,
-                                                       L.ptr(out), L.ptr(hidden_out), L.raw_stream(dev))
-                L.check(rc, "cgs_sample_support_depth")
+                L.check(L.load().cgs_sample_support_depth(*args, L.ptr(depth), slack, L.ptr(out), L.ptr(hidden_out),
+                                                          L.raw_stream(dev)), "cgs_sample_support_depth")
     return out
 
 

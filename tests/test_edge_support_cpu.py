@@ -117,6 +117,45 @@ def test_argument_errors():
             call(backend="gpu")
 
 
+class _OnGpu(torch.Tensor):
+    """A CPU tensor that says it is on a GPU: what the placement checks ask, without a GPU."""
+    is_cuda = property(lambda self: True)
+
+
+def test_the_host_back_end_refuses_gpu_tensors_in_the_four_per_sample_operators():
+    from curve_gaussian_amd.ops import edge_orient as OR
+    from curve_gaussian_amd.ops import edge_snap as SN
+    from curve_gaussian_amd.ops import edge_trim as ET
+    K, M = XC.identity_camera()
+    d2, near = np.zeros((1, 3, 4), np.int32), np.zeros((1, 3, 4), np.uint8)
+    depth = np.full((1, 3, 4), np.inf, np.float32)
+    pts, off, partner = np.zeros((2, 3), np.float32), np.array([0, 2], np.int32), np.array([1, 0], np.int32)
+    gpu = lambda *shape, dtype=torch.int32: torch.zeros(shape, dtype=dtype).as_subclass(_OnGpu)
+    cpu = lambda *shape, dtype=torch.int32: torch.zeros(shape, dtype=dtype)
+    calls = {
+        "support_counts": [lambda: SP.support_counts(gpu(2, 3, dtype=torch.float32), off, K, M, d2, (1,), backend="host"),
+                           lambda: SP.support_counts(pts, off, K, M, gpu(1, 3, 4), (1,), backend="host", depth=depth)],
+        "sample_tally": [lambda: ET.sample_tally(pts, K, M, d2, (1,), backend="host", out=gpu(2, 2)),
+                         lambda: ET.sample_tally(pts, K, M, d2, (1,), backend="host", depth=depth, hidden_out=gpu(2)),
+                         lambda: ET.sample_tally(gpu(2, 3, dtype=torch.float32), K, M, d2, (1,), backend="host")],
+        "oriented_tally": [lambda: OR.oriented_tally(pts, partner, K, M, near, backend="host", out=gpu(2, 2)),
+                           lambda: OR.oriented_tally(pts, partner, K, M, near, backend="host", depth=depth,
+                                                     out=cpu(2, 2), hidden_out=gpu(2)),
+                           lambda: OR.oriented_tally(pts, gpu(2), K, M, near, backend="host")],
+        "snap_terms": [lambda: SN.snap_terms(pts, K, M, d2, 3, backend="host", out=(gpu(2, 10, dtype=torch.float64), cpu(2))),
+                       lambda: SN.snap_terms(pts, K, M, d2, 3, backend="host", out=(cpu(2, 10, dtype=torch.float64), gpu(2))),
+                       lambda: SN.snap_terms(pts, K, M, d2, 3, backend="host", depth=depth, hidden_out=gpu(2))],
+    }
+    for who, rows in calls.items():
+        for row in rows:
+            with pytest.raises(ValueError) as err:
+                row()
+            assert str(err.value) == f"{who}: backend='host' takes host arrays and CPU tensors"
+    # the same calls with CPU tensors are taken
+    assert ET.sample_tally(pts, K, M, d2, (1,), backend="host", out=cpu(2, 2)).shape == (2, 2)
+    assert SN.snap_terms(pts, K, M, d2, 3, backend="host", out=(cpu(2, 10, dtype=torch.float64), cpu(2)))[1].shape == (2,)
+
+
 # ------------------------------------------------------------------------------------------------ the verdict
 def test_the_verdict_thresholds_at_their_boundaries():
     # one edge per row, V = 4 views, T = 1; n = 10 samples: sees iff seen >= ceil(0.5 * 10) = 5
