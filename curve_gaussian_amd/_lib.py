@@ -158,6 +158,12 @@ SIGNATURES = {
     "cgs_stereo_warp": (_i, [_i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp]),
     # (V, height, width, depth, F, warped, tol, min_support, v0, nv, out, support, stream)
     "cgs_stereo_fuse": (_i, [_i, _i, _i, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    # (nx, ny, nz, lo, step, V, intr, w2c, height, width, depth, trunc, accumulate, sum, weight, stream)
+    "cgs_tsdf_integrate": (_i, [_i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, C.c_double, _i, _vp, _vp, _vp]),
+    # (nx, ny, nz, sum, weight, min_weight, counts, stream)
+    "cgs_tsdf_mesh_count": (_i, [_i, _i, _i, _vp, _vp, _i, _vp, _vp]),
+    # (nx, ny, nz, lo, step, sum, weight, min_weight, offsets, T, tris, stream)
+    "cgs_tsdf_mesh_emit": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _i64, _vp, _vp]),
 }
 
 
@@ -215,6 +221,7 @@ SNAP_TERMS = 10   # CGS_SNAP_TERMS
 DEPTH_MAX_WINDOW = 4   # CGS_DEPTH_MAX_WINDOW
 STEREO_MAX_RADIUS = 8   # CGS_STEREO_MAX_RADIUS
 STEREO_MAX_FUSE = 16   # CGS_STEREO_MAX_FUSE
+TSDF_MAX_WEIGHT = 65535   # CGS_TSDF_MAX_WEIGHT
 REPORT_PANELS = ("render", "ground_truth", "depth", "rend_dir", "rend_alpha")   # panel order of cgs_report_panels
 
 _lib = None

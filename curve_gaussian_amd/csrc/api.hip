@@ -2252,4 +2252,53 @@ int cgs_stereo_fuse(int V, int height, int width, const float* depth, int F, con
     return finish("stereo_fuse", stream_);
 }
 
+// ---- the distance field and its surface (include/curvegs.h).  The grid and the views are checked as the seed entries
+// check theirs.
+static bool tsdf_weight_ok(int min_weight) { return min_weight >= 1 && min_weight <= CGS_TSDF_MAX_WEIGHT; }
+
+int cgs_tsdf_integrate(int nx, int ny, int nz, const double* lo, const double* step, int V, const double* intr,
+                       const double* w2c, int height, int width, const float* depth, double trunc, int accumulate, double* sum,
+                       uint16_t* weight, void* stream_) {
+    const char* name = "cgs_tsdf_integrate";
+    const bool ptrs = lo && step && sum && weight && (V == 0 || (intr && w2c && depth));
+    if (!seed_views_ok(name, V, height, width) || !seed_grid_ok(name, nx, ny, nz, ptrs ? lo : nullptr, ptrs ? step : nullptr))
+        return CGS_ERR_INVALID_ARGUMENT;
+    if (!(trunc > 0.0) || std::isinf(trunc))   // a NaN fails the comparison
+        return reject("%s: invalid argument (trunc=%g; the truncation distance is finite and > 0)", name, trunc);
+    if (!ptrs) return reject("%s: invalid argument (NULL pointer)", name);
+    if (V == 0 && accumulate) return CGS_OK;   // nothing to add
+    launch_tsdf_integrate((hipStream_t)stream_, SeedGrid{{lo[0], lo[1], lo[2]}, {step[0], step[1], step[2]}, nx, ny, nz},
+                          TsdfViews{V, height, width, intr, w2c, depth}, trunc, accumulate, sum, weight);
+    return finish("tsdf_integrate", stream_);
+}
+
+int cgs_tsdf_mesh_count(int nx, int ny, int nz, const double* sum, const uint16_t* weight, int min_weight, uint8_t* counts,
+                        void* stream_) {
+    const char* name = "cgs_tsdf_mesh_count";
+    if (!seed_grid_ok(name, nx, ny, nz, nullptr, nullptr)) return CGS_ERR_INVALID_ARGUMENT;
+    if (!tsdf_weight_ok(min_weight))
+        return reject("%s: invalid argument (min_weight=%d; it lies in [1, %d])", name, min_weight, CGS_TSDF_MAX_WEIGHT);
+    if (!sum || !weight) return reject("%s: invalid argument (NULL pointer)", name);
+    if (nx == 1 || ny == 1 || nz == 1) return CGS_OK;   // no cells: nothing to write
+    if (!counts) return reject("%s: invalid argument (NULL pointer)", name);
+    launch_tsdf_count((hipStream_t)stream_, SeedGrid{{0.0, 0.0, 0.0}, {1.0, 1.0, 1.0}, nx, ny, nz}, sum, weight, min_weight, counts);
+    return finish("tsdf_mesh_count", stream_);
+}
+
+int cgs_tsdf_mesh_emit(int nx, int ny, int nz, const double* lo, const double* step, const double* sum, const uint16_t* weight,
+                       int min_weight, const int64_t* offsets, int64_t T, float* tris, void* stream_) {
+    const char* name = "cgs_tsdf_mesh_emit";
+    const bool cells = nx > 1 && ny > 1 && nz > 1;
+    const bool ptrs = lo && step && sum && weight && (!cells || T == 0 || (offsets && tris));
+    if (!seed_grid_ok(name, nx, ny, nz, ptrs ? lo : nullptr, ptrs ? step : nullptr)) return CGS_ERR_INVALID_ARGUMENT;
+    if (!tsdf_weight_ok(min_weight))
+        return reject("%s: invalid argument (min_weight=%d; it lies in [1, %d])", name, min_weight, CGS_TSDF_MAX_WEIGHT);
+    if (T < 0) return reject("%s: invalid argument (T=%lld; it is at least 0)", name, (long long)T);
+    if (!ptrs) return reject("%s: invalid argument (NULL pointer)", name);
+    if (!cells || T == 0) return CGS_OK;   // nothing to write
+    launch_tsdf_emit((hipStream_t)stream_, SeedGrid{{lo[0], lo[1], lo[2]}, {step[0], step[1], step[2]}, nx, ny, nz}, sum, weight,
+                     min_weight, (const long long*)offsets, (long long)T, tris);
+    return finish("tsdf_mesh_emit", stream_);
+}
+
 }  // extern "C"

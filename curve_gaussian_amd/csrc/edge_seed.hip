@@ -50,6 +50,7 @@
 
 #include "kernels.h"
 #include "point_projection.h"
+#include "seed_centre.h"   // seed_centre: the lattice, shared with tsdf.hip
 
 namespace cgs {
 
@@ -73,18 +74,6 @@ __global__ void __launch_bounds__(SEED_THREADS) k_pack_near_bits(int height, int
     const int lane = threadIdx.x & 63;
     if ((lane & 31) == 0 && p < padded)            // p is a multiple of 32 here: p / 32 is this half wave's word
         bits[(size_t)view * (size_t)height * (size_t)stride + (size_t)(p >> 5)] = (unsigned int)(lane ? b >> 32 : b);
-}
-
-// The centre of the voxel with linear index `id` (x fastest): float64, then the float32 point that the projection contract
-// is written for, widened again.
-__device__ inline void seed_centre(const SeedGrid& g, long long id, double& X, double& Y, double& Z) {
-#pragma clang fp contract(off)
-    const int i = (int)(id % g.nx);
-    const long long r = id / g.nx;
-    const int j = (int)(r % g.ny), k = (int)(r / g.ny);
-    X = (double)(float)(g.lo[0] + ((double)i + 0.5) * g.step[0]);
-    Y = (double)(float)(g.lo[1] + ((double)j + 0.5) * g.step[1]);
-    Z = (double)(float)(g.lo[2] + ((double)k + 0.5) * g.step[2]);
 }
 
 // True if view `c` keeps the centre and, when GATED, does not hide it (nv_verdict, point_projection.h); then (px, py) is its

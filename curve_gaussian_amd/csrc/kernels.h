@@ -313,4 +313,18 @@ hipError_t launch_stereo_warp(hipStream_t s, int V, int height, int width, const
 void launch_stereo_fuse(hipStream_t s, int height, int width, const float* depth, int F, const float* warped,
                         const double* tol, int min_support, int v0, int nv, float* out, uint8_t* support);
 
+// tsdf.hip (the rule is tsdf.h's; the lattice is a SeedGrid's voxel centres)
+struct TsdfViews {  // the views of one call: cameras and float32 [V,height,width] depth planes; passed by value
+    int V, height, width;
+    const double* intr;
+    const double* w2c;
+    const float* depth;
+};
+void launch_tsdf_integrate(hipStream_t s, SeedGrid g, TsdfViews views, double trunc, int accumulate, double* sum,
+                           unsigned short* weight);
+void launch_tsdf_count(hipStream_t s, SeedGrid g, const double* sum, const unsigned short* weight, int min_weight,
+                       uint8_t* counts);
+void launch_tsdf_emit(hipStream_t s, SeedGrid g, const double* sum, const unsigned short* weight, int min_weight,
+                      const long long* offsets, long long T, float* tris);
+
 }  // namespace cgs

@@ -5,7 +5,8 @@
 // edge_snap.hip: cgs_sample_snap_terms -- those seven and their _depth siblings through nv_verdict at the end of this file;
 // edge_occlusion.hip: cgs_point_mask_depth through nv_project_xyz_depth, and
 // cgs_mesh_depth, which projects a triangle's vertices in the same operation order through nv_camera_xyz / nv_image_uv;
-// mesh_contours.hip: cgs_mesh_contours, an edge row's four vertices through the same two and nv_hidden).
+// mesh_contours.hip: cgs_mesh_contours, an edge row's four vertices through the same two and nv_hidden;
+// tsdf.hip: cgs_tsdf_integrate through nv_project_xyz_depth, reading the pixel nv_hidden reads).
 //
 // Exact, the reference's operation order (eval_ABC.py project_points_to_camera :66-81): X float32 widened to float64,
 // c = R X + T with every row ((r0*X + r1*Y) + r2*Z) + t, dropped if c2 <= 0 (a NaN depth is dropped too: it fails the

@@ -1753,6 +1753,80 @@ int cgs_stereo_fuse(int V, int height, int width, const float* depth /*[V,height
                     const float* warped /*[nv,F,height,width]*/, const double* tol /*[V]*/, int min_support, int v0, int nv,
                     float* out /*[nv,height,width]*/, uint8_t* support /*[nv,height,width] or NULL*/, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * A truncated signed distance field (TSDF) from per-view depth maps, and its surface as a triangle soup by marching
+ * tetrahedra.  The maps of a scan -- the stereo maps above, a z-buffer's planes, a sensor's -- are separate estimates of
+ * one surface; the field AVERAGES the signed distances that the views report at a point of space (it takes no minimum, so
+ * noise on either side of the surface cancels), and its zero set is one surface that all views share, in the float32
+ * [T,3,3] layout that cgs_mesh_depth and cgs_mesh_contours take.  The reference has no counterpart.  The rule is frozen
+ * with the conventions of this header -- float64, one rounded operation at a time in the written order, nothing
+ * contracted, IEEE division, running sums in view order, 64-bit offsets -- and stated once for the kernels, in csrc/tsdf.h.
+ *
+ * LATTICE.  The lattice points are the voxel centres of the grid of cgs_voxel_votes (nx, ny, nz, lo, step; the same
+ * checks): point g = i + nx (j + ny k) is float64 lo + (i + 0.5) * step per axis, rounded to float32 and widened again.  A
+ * CELL is the cube between 8 neighbouring points: cell (i, j, k) with 0 <= i < nx - 1, 0 <= j < ny - 1, 0 <= k < nz - 1 has
+ * the linear index i + (nx - 1) (j + (ny - 1) k), and its corner c = dx + 2 dy + 4 dz is the point (i + dx, j + dy, k + dz).
+ * A grid with a dimension of 1 has no cells.
+ *
+ * cgs_tsdf_integrate.  State: sum float64 [nx ny nz], weight uint16 [nx ny nz].  Without `accumulate` a point starts
+ * from (0.0, 0); with it, from its own stored pair.  Then the views v = 0 .. V-1 in order (cameras and planes as
+ * cgs_voxel_votes_depth takes them: intr [V,4], w2c [V,3,4], depth float32 [V,height,width], one size per call):
+ *   the point is projected as cgs_point_mask_depth projects (c2 > 0, 0 <= u < width, 0 <= v' < height); a view that does
+ *     not keep it contributes nothing
+ *   d = (double)depth[v][floor(v')][floor(u)], the pixel the occlusion rule reads
+ *   the view OBSERVES the point iff d > 0 && d < +inf: a NaN, 0, a negative depth and +inf all fail (0 is the stereo
+ *     maps' "unsure", +inf the z-buffers' "no surface"; neither carves)
+ *   sdf = d - c2; if sdf < -trunc the view does not observe the point (it lies too far behind the surface to know of)
+ *   if weight == 65535 the view contributes nothing: the weight SATURATES, and the pair stays a sum over `weight` views
+ *   t = sdf / trunc; if t > 1.0, t = 1.0; sum += t; weight += 1
+ * Because a thread continues its own running sum, integrating V views at once and integrating them in chunks with
+ * `accumulate` give the same bits, as cgs_sample_snap_terms guarantees for its sums.  V = 0 without `accumulate` writes
+ * (0.0, 0) everywhere; with it, nothing.
+ *
+ * EXTRACTION, two entries with the caller's exclusive scan between them.  A cell is LIVE iff all 8 corners have
+ * weight >= min_weight (1 <= min_weight <= 65535).  A corner's value is f = sum / (double)weight; the corner is INSIDE iff
+ * f < 0 (0.0, -0.0 and a NaN are outside).  The cube is cut into the 6 Kuhn tetrahedra around the diagonal from corner 0 to
+ * corner 7, the same cut in every cell, so neighbouring cells agree on their shared faces: tetrahedron t = 0..5 belongs to
+ * the t-th order (a, b, c) of the axes 0, 1, 2 in lexicographic order and has the corners (q0, q1, q2, q3) =
+ * (0, 1 << a, (1 << a) | (1 << b), 7), in ascending corner number; its PARITY is the order's (t = 0, 3, 4 even; 1, 2, 5
+ * odd).  E(x, y) is the vertex on the lattice edge from q_x to q_y.  Per tetrahedron, by its inside corners:
+ *   none or all four: no triangle
+ *   one, x, the others p < q < r:   (E(x,p), E(x,q), E(x,r)), TURNED iff x is odd
+ *   three, all but x, p < q < r:    the same triangle, turned iff x is even
+ *   two, i < j, outside k < l:      the quad E(i,k) E(i,l) E(j,l) E(j,k), split along the diagonal E(i,k) -- E(j,l):
+ *                                   (E(i,k), E(i,l), E(j,l)) then (E(i,k), E(j,l), E(j,k)), both turned iff (i, j, k, l) is an
+ *                                   odd permutation of (0, 1, 2, 3)
+ * Turning swaps a triangle's second and third vertex; a tetrahedron of odd parity turns every triangle once more.
+ * WINDING: with that, (v1 - v0) x (v2 - v0) points from inside to outside (in tetrahedron 0 with corner 0 alone inside,
+ * the triangle on the three axes has the normal (1, 1, 1); every other case is this one with the corners relabelled, and
+ * an odd relabelling mirrors the tetrahedron).  At most 2 triangles per tetrahedron, 12 per cell.
+ * A VERTEX lies on a lattice edge whose ends differ in sign.  With the ends in ascending linear lattice index (a, b),
+ * whichever of them is inside: p = Pa + (fa / (fa - fb)) * (Pb - Pa) per component in float64, rounded to float32.  The end
+ * order is canonical, so two cells that share an edge produce the same bits and a weld by bits sees no crack.  An outside
+ * end of exactly 0.0 puts the vertex ON the lattice point; triangles with two equal vertices are emitted like any other
+ * (the Python layer drops them).
+ *   cgs_tsdf_mesh_count: counts uint8 [(nx-1)(ny-1)(nz-1)], the triangles of every cell (0 for a cell that is not live).
+ *   cgs_tsdf_mesh_emit:  offsets int64 [cells], the exclusive prefix sums of counts; tris float32 [T,3,3].  Cell e writes
+ *     its triangles at tris[offsets[e]] .. in the order tetrahedron, then triangle, so the soup is ordered by cell and does
+ *     not depend on the launch geometry.  A cell whose range does not lie in [0, T] writes nothing (the caller's error).
+ *
+ * All three run on the caller's stream with no allocation, no atomics and no host synchronisation.  Every argument is
+ * checked whether or not there is work: the grid and the views as cgs_voxel_votes_depth checks them, a trunc that is not
+ * finite and > 0, a min_weight outside [1, CGS_TSDF_MAX_WEIGHT], T < 0 and NULL pointers are CGS_ERR_INVALID_ARGUMENT,
+ * rejected before anything is launched, so every buffer is untouched.  intr, w2c and depth may be NULL when V = 0; counts,
+ * offsets and tris when the grid has no cells; offsets and tris when T = 0.
+ * ------------------------------------------------------------------------------------------------ */
+#define CGS_TSDF_MAX_WEIGHT 65535
+int cgs_tsdf_integrate(int nx, int ny, int nz, const double* lo /*host, [3]*/, const double* step /*host, [3]*/, int V,
+                       const double* intr /*[V,4]*/, const double* w2c /*[V,3,4]*/, int height, int width,
+                       const float* depth /*[V,height,width]*/, double trunc, int accumulate, double* sum /*[nx ny nz]*/,
+                       uint16_t* weight /*[nx ny nz]*/, void* stream);
+int cgs_tsdf_mesh_count(int nx, int ny, int nz, const double* sum /*[nx ny nz]*/, const uint16_t* weight /*[nx ny nz]*/,
+                        int min_weight, uint8_t* counts /*[cells]*/, void* stream);
+int cgs_tsdf_mesh_emit(int nx, int ny, int nz, const double* lo /*host, [3]*/, const double* step /*host, [3]*/,
+                       const double* sum /*[nx ny nz]*/, const uint16_t* weight /*[nx ny nz]*/, int min_weight,
+                       const int64_t* offsets /*[cells]*/, int64_t T, float* tris /*[T,3,3]*/, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
