@@ -33,6 +33,11 @@ SIGNATURES = {
                                      C.c_uint32, _vp, _i, _i, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "cgs_view_forward_render": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _f, _vp, _vp, C.c_size_t, _vp, C.c_uint32,
                                      _vp, _i, _i, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # the siblings' arguments with the cgs_view_gate pointer before the stream
+    "cgs_view_forward_depth": (_i, [_i, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _f, _vp, _vp, _vp, C.c_size_t, _vp, C.c_uint32,
+                                    _vp, _i, _i, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cgs_view_forward_render_depth": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _f, _vp, _vp, C.c_size_t, _vp,
+                                           C.c_uint32, _vp, _i, _i, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "cgs_view_backward_render": (_i, [_i, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp,
                                       _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
     "cgs_view_forward_wait": (_i64, [_i, C.POINTER(_i64)]),
@@ -176,6 +181,12 @@ class ReportView(C.Structure):
     """cgs_report_view (include/curvegs.h)."""
     _fields_ = [("render", _vp), ("gt", _vp), ("depth", _vp), ("rend_dir", _vp), ("rend_alpha", _vp), ("gt_channels", _i),
                 ("height", _i), ("width", _i), ("written", C.c_uint), ("out_offset", C.c_size_t)]
+
+
+class ViewGate(C.Structure):
+    """cgs_view_gate (include/curvegs.h)."""
+    _fields_ = [("planes", _vp), ("intr", _vp), ("w2c", _vp), ("view_index", _vp), ("slack", C.c_double), ("V", C.c_int32),
+                ("view", C.c_int32), ("height", C.c_int32), ("width", C.c_int32)]
 
 
 class UndistortView(C.Structure):

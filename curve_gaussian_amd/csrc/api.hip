@@ -885,13 +885,33 @@ static int64_t view_forward_wait(int handle, int64_t* n_visible) {
     return ok ? longest : CGS_ERR_HIP;
 }
 
+// The gate of the two _depth forwards, checked after the sibling's own arguments and before the bucket capacity, under the
+// name of the entry that was called: a gate, its three pointers, V >= 1, a host view inside [0, V) (a device view index is
+// the kernel's to read), a slack >= 0 (+inf is allowed: it hides nothing; NaN fails the comparison) and planes of the
+// image's size.  Nothing is launched before all of it holds.
+static int view_gate_check(const char* name, const cgs_view_gate* gate, int width_px, int height_px, ViewGate& out) {
+    if (!gate) return reject("%s: invalid argument (NULL gate)", name);
+    if (!gate->planes || !gate->intr || !gate->w2c) return reject("%s: invalid argument (NULL plane or camera pointer)", name);
+    if (gate->V < 1) return reject("%s: invalid argument (V=%d; the stack holds at least one view)", name, gate->V);
+    if (!gate->view_index && (gate->view < 0 || gate->view >= gate->V))
+        return reject("%s: invalid argument (view=%d outside [0, %d))", name, gate->view, gate->V);
+    if (!(gate->slack >= 0.0)) return reject("%s: invalid argument (slack=%g; the slack is >= 0)", name, gate->slack);
+    if (gate->height != height_px || gate->width != width_px)
+        return reject("%s: invalid argument (planes %dx%d, image %dx%d; the planes have the image's size)", name, gate->width,
+                      gate->height, width_px, height_px);
+    out = ViewGate{gate->planes, gate->intr, gate->w2c, gate->view_index, gate->slack, gate->V, gate->view};
+    return 0;
+}
+
 static int64_t view_forward_impl(int mode, int B, int m, const float* curve_points, const float* width, const uint8_t* is_bezier, const float* coef,
                      float eps, double* norms, const float* opacity_logit, const float* mask_logit, float mask_thr,
                      const float* colors_precomp, void* geometry_buffer, void* binning_buffer, size_t binning_bytes,
                      void* image_buffer, uint32_t bucket_capacity, const float* background, int width_px, int height_px,
                      const float* viewmatrix, const float* projmatrix, const float* cam_pos, float tan_fovx, float tan_fovy,
                      float* out_color, float* out_invdepth, float* out_all_map, int* radii, float* xyz, float* rotation,
-                     float* scaling, void* stream_, float* out_color_clamped = nullptr, float* out_rend_dir = nullptr) {
+                     float* scaling, void* stream_, float* out_color_clamped = nullptr, float* out_rend_dir = nullptr,
+                     const char* gated_name = nullptr, const cgs_view_gate* gate = nullptr) {
+    // gated_name: the _depth entry that was called (NULL: one of the five forwards as they always were, `gate` is not looked at)
     hipStream_t s = (hipStream_t)stream_;
     const int P = B * m;
     if (out_rend_dir && !out_all_map) return reject("cgs_view_forward: the direction map needs the all_map output");
@@ -902,6 +922,10 @@ static int64_t view_forward_impl(int mode, int B, int m, const float* curve_poin
         (!out_all_map && colors_precomp) || !radii || (xyz && (!rotation || !scaling)) || !aligned16(curve_points) || !aligned16(coef) || !aligned16(rotation))
         return reject("cgs_view_forward: invalid argument (B=%d m=%d W=%d H=%d, NULL / misaligned pointer or zero capacity)", B,
                       m, width_px, height_px);
+    ViewGate vg{};
+    if (gated_name) {
+        if (const int rc = view_gate_check(gated_name, gate, width_px, height_px, vg)) return rc;
+    }
     const Frame f(width_px, height_px, tan_fovx, tan_fovy);
     if (!bucket_cap_ok("cgs_view_forward", bucket_capacity, f.tiles, binning_bytes)) return CGS_ERR_INVALID_ARGUMENT;
     const uint64_t cap = bucket_capacity;
@@ -918,7 +942,7 @@ static int64_t view_forward_impl(int mode, int B, int m, const float* curve_poin
     launch_view_forward(s, B, m, curve_points, width, is_bezier, coef, eps, norms, opacity_logit, mask_logit, mask_thr,
                         colors_precomp, cam_pos, viewmatrix, projmatrix, tan_fovx, tan_fovy, f.focal_x, f.focal_y, width_px,
                         height_px, f.gx, f.gy, xyz, rotation, scaling, radii, b.geom.rec, b.geom.grad_acc, b.img.tile_count,
-                        b.clear_bytes / sizeof(uint32_t));
+                        b.clear_bytes / sizeof(uint32_t), gated_name ? &vg : nullptr);
     // k_view_fwd writes unit colours (no colors_precomp) and all_map[3] = 1 itself: the compositor derives both sums from T.
     // Image-only forward (unit colours required) when the caller passes neither map.
     const bool unit = colors_precomp == nullptr;
@@ -983,6 +1007,35 @@ int cgs_view_forward_render(int checked, int B, int m, const float* curve_points
                                   background, width_px, height_px, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, out_color,
                                   out_invdepth, out_all_map, radii, nullptr, nullptr, nullptr, stream_, out_color_clamped,
                                   out_rend_dir);
+}
+// The two forwards every training route calls, behind the depth gate (include/curvegs.h): the sibling's arguments and checks,
+// then the gate's; the launcher picks k_view_fwd<true>, everything behind it is the sibling's.
+int cgs_view_forward_depth(int B, int m, const float* curve_points, const float* width, const uint8_t* is_bezier, const float* coef,
+                           float eps, double* norms, const float* opacity_logit, const float* mask_logit, float mask_thr,
+                           const float* colors_precomp, void* geometry_buffer, void* binning_buffer, size_t binning_bytes,
+                           void* image_buffer, uint32_t bucket_capacity, const float* background, int width_px, int height_px,
+                           const float* viewmatrix, const float* projmatrix, const float* cam_pos, float tan_fovx, float tan_fovy,
+                           float* out_color, float* out_invdepth, float* out_all_map, int* radii, float* xyz, float* rotation,
+                           float* scaling, const cgs_view_gate* gate, void* stream_) {
+    return (int)view_forward_impl(0, B, m, curve_points, width, is_bezier, coef, eps, norms, opacity_logit, mask_logit,
+                                  mask_thr, colors_precomp, geometry_buffer, binning_buffer, binning_bytes, image_buffer,
+                                  bucket_capacity, background, width_px, height_px, viewmatrix, projmatrix, cam_pos, tan_fovx,
+                                  tan_fovy, out_color, out_invdepth, out_all_map, radii, xyz, rotation, scaling, stream_, nullptr,
+                                  nullptr, "cgs_view_forward_depth", gate);
+}
+int cgs_view_forward_render_depth(int checked, int B, int m, const float* curve_points, const float* width,
+                                  const uint8_t* is_bezier, const float* coef, float eps, double* norms,
+                                  const float* opacity_logit, const float* mask_logit, float mask_thr, void* geometry_buffer,
+                                  void* binning_buffer, size_t binning_bytes, void* image_buffer, uint32_t bucket_capacity,
+                                  const float* background, int width_px, int height_px, const float* viewmatrix,
+                                  const float* projmatrix, const float* cam_pos, float tan_fovx, float tan_fovy, float* out_color,
+                                  float* out_invdepth, float* out_all_map, int* radii, float* out_color_clamped,
+                                  float* out_rend_dir, const cgs_view_gate* gate, void* stream_) {
+    return (int)view_forward_impl(checked ? 2 : 0, B, m, curve_points, width, is_bezier, coef, eps, norms, opacity_logit, mask_logit,
+                                  mask_thr, nullptr, geometry_buffer, binning_buffer, binning_bytes, image_buffer, bucket_capacity,
+                                  background, width_px, height_px, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, out_color,
+                                  out_invdepth, out_all_map, radii, nullptr, nullptr, nullptr, stream_, out_color_clamped,
+                                  out_rend_dir, "cgs_view_forward_render_depth", gate);
 }
 int64_t cgs_view_forward_wait(int handle, int64_t* n_visible) { return view_forward_wait(handle, n_visible); }
 void cgs_view_forward_abandon(int handle) {

@@ -14,6 +14,20 @@ struct DepthGate {
     double slack;
 };
 
+// The gate of the training render (cgs_view_forward_depth / cgs_view_forward_render_depth; view.hip, k_view_fwd<true>): it
+// needs more than a DepthGate holds, because the kernel projects a splat's centre itself -- the resident stack of planes,
+// float32 [V,H,W] with H x W the image of the forward, the float64 cameras the planes were drawn with, and which view this
+// forward is: `view` on the host, or *view_index on the device when that pointer is set.  launch_view_forward takes
+// `const ViewGate* gate` by the convention above: nullptr is the forward as it always was.  Passed to the kernel by value.
+struct ViewGate {
+    const float* planes;
+    const double* intr;
+    const double* w2c;
+    const int* view_index;
+    double slack;
+    int V, view;
+};
+
 // preprocess.hip
 void launch_preprocess_fwd(hipStream_t s, int P, int D, int M, const float* means3D, const float* scales,
                            float scale_modifier, const float* rotations, const float* opacities, const float* shs,
@@ -99,7 +113,7 @@ void launch_view_forward(hipStream_t s, int B, int m, const float* cp, const flo
                          const float* mask_logit, float mask_thr, const float* colors_precomp, const float* campos,
                          const float* viewmatrix, const float* projmatrix, float tan_fovx, float tan_fovy, float focal_x,
                          float focal_y, int W, int H, int grid_x, int grid_y, float* xyz, float* rot, float* scl, int* radii,
-                         SplatRec* rec, float* grad_acc, uint32_t* clear_words, size_t n_clear);
+                         SplatRec* rec, float* grad_acc, uint32_t* clear_words, size_t n_clear, const ViewGate* gate = nullptr);
 void launch_view_backward(hipStream_t s, int B, int m, const float* cp, const float* width, const uint8_t* is_bezier,
                           const void* coef, float eps, double* norms, const float* opacity_logit, const float* mask_logit,
                           float mask_thr, const float* campos, const float* viewmatrix, const float* projmatrix,

@@ -209,11 +209,40 @@ struct ViewFwd {
     Tensor cp, w, ol, mk, geom, binb, img, norms, bgc, view, proj, cpos;                   // what the backward needs (mk: undefined = no mask)
     int handle = -1;
 };
+// cgs_view_gate of a TrainGate's tensors (view_forward_core says what they are); `like`: a tensor of the forward's device
+cgs_view_gate view_gate_of(const std::vector<Tensor>& gate, double slack, int64_t view, const Tensor& like) {
+    if (gate.size() != 3 && gate.size() != 4) raise_cgs("depth_gate: expected planes, intr, w2c and optionally a device view index");
+    const Tensor &planes = gate[0], &intr = gate[1], &w2c = gate[2];
+    for (const Tensor& t : gate)
+        if (!t.is_cuda() || t.device() != like.device() || !t.is_contiguous())
+            raise_cgs("depth_gate: the gate's tensors must be contiguous and on the model's device");
+    if (planes.scalar_type() != at::kFloat || planes.dim() != 3 || intr.scalar_type() != at::kDouble || w2c.scalar_type() != at::kDouble ||
+        intr.numel() != 4 * planes.size(0) || w2c.numel() != 12 * planes.size(0))
+        raise_cgs("depth_gate: planes must be float32 [V,H,W], intr float64 [V,4], w2c float64 [V,12]");
+    cgs_view_gate g;
+    g.planes = planes.data_ptr<float>();
+    g.intr = intr.data_ptr<double>();
+    g.w2c = w2c.data_ptr<double>();
+    g.view_index = nullptr;
+    if (gate.size() == 4) {
+        if (gate[3].scalar_type() != at::kInt || gate[3].numel() != 1) raise_cgs("depth_gate: the device view index is one int32");
+        g.view_index = gate[3].data_ptr<int32_t>();
+    }
+    g.slack = slack;
+    g.V = (int32_t)planes.size(0);
+    g.view = (int32_t)view;
+    g.height = (int32_t)planes.size(1);
+    g.width = (int32_t)planes.size(2);
+    return g;
+}
 ViewFwd view_forward_core(const Tensor& curve_points, const Tensor& width, const Tensor& opacity_logit,
                           const c10::optional<Tensor>& mask_logit, const c10::optional<Tensor>& is_bezier_u8, const Tensor& coef,
                           int64_t m, double mask_thr, const Tensor& bg, const Tensor& viewmatrix, const Tensor& projmatrix,
                           const Tensor& campos, double tanx, double tany, int64_t H, int64_t W, int64_t cap, bool sync_free, bool clamp,
-                          bool want_dir, double eps) {
+                          bool want_dir, double eps, const std::vector<Tensor>& gate = {}, double gate_slack = 0.0,
+                          int64_t gate_view = 0) {
+    // gate: empty, or the tensors of an ops/train_gate.py::TrainGate -- planes [V,H,W] f32, intr [V,4] f64, w2c [V,12] f64 and,
+    // optionally, a one-element int32 view index -- for cgs_view_forward_render_depth (gate_slack, gate_view: its other fields)
     require_gpu(curve_points, "curve_points");
     require_gpu(bg, "bg_color");   // "Background tensor (bg_color) must be on GPU!" (gaussian_renderer/__init__.py:23)
     require_gpu(viewmatrix, "viewpoint_camera.world_view_transform");
@@ -239,14 +268,27 @@ ViewFwd view_forward_core(const Tensor& curve_points, const Tensor& width, const
     Tensor color_out = color, rend_dir = at::empty({0}, fopt);
     if (clamp) color_out = at::empty({1, H, W}, fopt);
     if (want_dir) rend_dir = at::empty({3, H, W}, fopt);
-    const int handle = check(cgs_view_forward_render(sync_free ? 0 : 1, B, (int)m, fp(cp), fp(w), isb, fp(coef), (float)eps,
+    int handle;
+    if (gate.empty()) {
+        handle = check(cgs_view_forward_render(sync_free ? 0 : 1, B, (int)m, fp(cp), fp(w), isb, fp(coef), (float)eps,
+                                               norms.data_ptr<double>(), fp(ol), fp(mk), (float)mask_thr, geom.data_ptr(),
+                                               binb.data_ptr(), nbin, img.data_ptr(), (uint32_t)cap, fp(bgc), (int)W, (int)H,
+                                               fp(view), fp(proj), fp(cpos), (float)tanx, (float)tany, color.data_ptr<float>(),
+                                               invd.data_ptr<float>(), amap.data_ptr<float>(), radii.data_ptr<int>(),
+                                               clamp ? color_out.data_ptr<float>() : nullptr,
+                                               want_dir ? rend_dir.data_ptr<float>() : nullptr, st),
+                       "cgs_view_forward_render");
+    } else {
+        const cgs_view_gate vg = view_gate_of(gate, gate_slack, gate_view, cp);
+        handle = check(cgs_view_forward_render_depth(sync_free ? 0 : 1, B, (int)m, fp(cp), fp(w), isb, fp(coef), (float)eps,
                                                      norms.data_ptr<double>(), fp(ol), fp(mk), (float)mask_thr, geom.data_ptr(),
                                                      binb.data_ptr(), nbin, img.data_ptr(), (uint32_t)cap, fp(bgc), (int)W, (int)H,
                                                      fp(view), fp(proj), fp(cpos), (float)tanx, (float)tany, color.data_ptr<float>(),
                                                      invd.data_ptr<float>(), amap.data_ptr<float>(), radii.data_ptr<int>(),
                                                      clamp ? color_out.data_ptr<float>() : nullptr,
-                                                     want_dir ? rend_dir.data_ptr<float>() : nullptr, st),
-                             "cgs_view_forward_render");
+                                                     want_dir ? rend_dir.data_ptr<float>() : nullptr, &vg, st),
+                       "cgs_view_forward_render_depth");
+    }
     ViewFwd f;
     f.color_out = color_out; f.invd = invd; f.amap = amap; f.radii = radii; f.rend_dir = rend_dir;
     if (clamp) f.color_raw = color;
@@ -259,9 +301,11 @@ py::tuple view_forward(const Tensor& curve_points, const Tensor& width, const Te
                        const c10::optional<Tensor>& mask_logit, const c10::optional<Tensor>& is_bezier_u8, const Tensor& coef,
                        int64_t m, double mask_thr, const Tensor& bg, const Tensor& viewmatrix, const Tensor& projmatrix,
                        const Tensor& campos, double tanx, double tany, int64_t H, int64_t W, int64_t cap, bool sync_free, bool clamp,
-                       bool want_dir, double eps) {
+                       bool want_dir, double eps, const c10::optional<std::vector<Tensor>>& gate, double gate_slack,
+                       int64_t gate_view) {
     const ViewFwd f = view_forward_core(curve_points, width, opacity_logit, mask_logit, is_bezier_u8, coef, m, mask_thr, bg, viewmatrix,
-                                        projmatrix, campos, tanx, tany, H, W, cap, sync_free, clamp, want_dir, eps);
+                                        projmatrix, campos, tanx, tany, H, W, cap, sync_free, clamp, want_dir, eps,
+                                        gate.value_or(std::vector<Tensor>()), gate_slack, gate_view);
     return py::make_tuple(f.color_out, f.invd, f.amap, f.radii, f.rend_dir, f.color_raw.defined() ? py::cast(f.color_raw) : py::none(),
                           py::make_tuple(f.cp, f.w, f.ol, f.mk.defined() ? py::cast(f.mk) : py::none(), f.geom, f.binb, f.img, f.radii,
                                          f.norms, f.bgc, f.view, f.proj, f.cpos),
@@ -399,10 +443,11 @@ struct ViewRenderFn : public torch::autograd::Function<ViewRenderFn> {
                                  const c10::optional<Tensor>& mask_logit, const Tensor& means2D,
                                  const c10::optional<Tensor>& is_bezier_u8, const c10::optional<Tensor>& is_bezier, const Tensor& coef, int64_t m, double mask_thr, const Tensor& bg, const Tensor& viewmatrix,
                                  const Tensor& projmatrix, const Tensor& campos, double tanx, double tany, int64_t H, int64_t W, int64_t cap,
-                                 bool sync_free, bool clamp, bool want_dir, double eps, const std::vector<Tensor>& sinks) {
+                                 bool sync_free, bool clamp, bool want_dir, double eps, const std::vector<Tensor>& sinks,
+                                 const std::vector<Tensor>& gate, double gate_slack, int64_t gate_view) {
         (void)means2D;
         ViewFwd f = view_forward_core(curve_points, width, opacity_logit, mask_logit, is_bezier_u8, coef, m, mask_thr, bg, viewmatrix, projmatrix,
-                                      campos, tanx, tany, H, W, cap, sync_free, clamp, want_dir, eps);
+                                      campos, tanx, tany, H, W, cap, sync_free, clamp, want_dir, eps, gate, gate_slack, gate_view);
         t_handle = f.handle;
         t_img = f.img;
         ctx->save_for_backward({f.cp, f.w, f.ol, f.mk, f.geom, f.binb, f.img, f.radii, f.norms, f.bgc, f.view, f.proj, f.cpos, coef,
@@ -431,7 +476,7 @@ struct ViewRenderFn : public torch::autograd::Function<ViewRenderFn> {
         const int64_t m = ctx->saved_data["m"].toInt(), H = ctx->saved_data["H"].toInt(), W = ctx->saved_data["W"].toInt();
         const double mask_thr = ctx->saved_data["mask_thr"].toDouble(), tanx = ctx->saved_data["tanx"].toDouble(),
                      tany = ctx->saved_data["tany"].toDouble(), eps = ctx->saved_data["eps"].toDouble();
-        variable_list out(24);   // one slot per forward argument; only the first five can carry a gradient
+        variable_list out(27);   // one slot per forward argument; only the first five can carry a gradient
         const Tensor &g_color = go[0], &g_invd = go[1], &g_amap = go[2], &g_dir = go[4];
         if (g_invd.defined() || g_amap.defined() || g_dir.defined()) {
             // a loss on inverse depth / all_map / the direction map: re-render through the differentiable general route (Python)
@@ -481,10 +526,12 @@ py::tuple view_render(const Tensor& curve_points, const Tensor& width, const Ten
                       const Tensor& means2D, const c10::optional<Tensor>& is_bezier_u8, const c10::optional<Tensor>& is_bezier,
                       const Tensor& coef, int64_t m, double mask_thr, const Tensor& bg, const Tensor& viewmatrix, const Tensor& projmatrix,
                       const Tensor& campos, double tanx, double tany, int64_t H, int64_t W, int64_t cap, bool sync_free, bool clamp,
-                      bool want_dir, double eps, const c10::optional<std::vector<Tensor>>& sinks) {
+                      bool want_dir, double eps, const c10::optional<std::vector<Tensor>>& sinks,
+                      const c10::optional<std::vector<Tensor>>& gate, double gate_slack, int64_t gate_view) {
     const variable_list o = ViewRenderFn::apply(curve_points, width, opacity_logit, mask_logit, means2D, is_bezier_u8, is_bezier, coef, m, mask_thr, bg,
                                                 viewmatrix, projmatrix, campos, tanx, tany, H, W, cap, sync_free, clamp, want_dir, eps,
-                                                sinks.value_or(std::vector<Tensor>()));
+                                                sinks.value_or(std::vector<Tensor>()), gate.value_or(std::vector<Tensor>()), gate_slack,
+                                                gate_view);
     const int handle = ViewRenderFn::t_handle;
     Tensor img = ViewRenderFn::t_img;
     ViewRenderFn::t_img = Tensor();
@@ -543,10 +590,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
             py::arg("binningBuffer"), py::arg("imageBuffer"), py::arg("antialiasing"), py::arg("render_geo"), py::arg("debug"),
             py::arg("need_color_grad") = true);
     mod.def("mark_visible", &mark_visible);
-    mod.def("view_forward", &view_forward);
+    mod.def("view_forward", &view_forward, py::arg("curve_points"), py::arg("width"), py::arg("opacity_logit"), py::arg("mask_logit"),
+            py::arg("is_bezier_u8"), py::arg("coef"), py::arg("m"), py::arg("mask_thr"), py::arg("bg"), py::arg("viewmatrix"),
+            py::arg("projmatrix"), py::arg("campos"), py::arg("tanx"), py::arg("tany"), py::arg("H"), py::arg("W"), py::arg("cap"),
+            py::arg("sync_free"), py::arg("clamp"), py::arg("want_dir"), py::arg("eps"), py::arg("gate") = py::none(),
+            py::arg("gate_slack") = 0.0, py::arg("gate_view") = 0);
     mod.def("view_wait", &view_wait);
     mod.def("view_abandon", &view_abandon);
-    mod.def("view_render", &view_render);
+    mod.def("view_render", &view_render, py::arg("curve_points"), py::arg("width"), py::arg("opacity_logit"), py::arg("mask_logit"),
+            py::arg("means2D"), py::arg("is_bezier_u8"), py::arg("is_bezier"), py::arg("coef"), py::arg("m"), py::arg("mask_thr"),
+            py::arg("bg"), py::arg("viewmatrix"), py::arg("projmatrix"), py::arg("campos"), py::arg("tanx"), py::arg("tany"),
+            py::arg("H"), py::arg("W"), py::arg("cap"), py::arg("sync_free"), py::arg("clamp"), py::arg("want_dir"), py::arg("eps"),
+            py::arg("sinks"), py::arg("gate") = py::none(), py::arg("gate_slack") = 0.0, py::arg("gate_view") = 0);
     mod.def("set_general_backward", &set_general_backward);
     mod.def("photometric_loss", &photometric_loss);
     mod.def("view_backward", &view_backward, py::arg("cp"), py::arg("w"), py::arg("ol"), py::arg("mk"), py::arg("is_bezier_u8"),

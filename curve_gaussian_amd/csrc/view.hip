@@ -11,17 +11,42 @@
 // (k_sample_bwd_close).  Training configuration only: scales + rotations (no precomputed covariance), precomputed colours
 // (no SH), no antialiasing -- everything else goes through the general kernels.
 #include "curve_math.h"
+#include "point_projection.h"
 #include "splat_math.h"
 
 namespace cgs {
 
+// Does the gate's view hide the splat centre `xyz`?  (k_view_fwd<true>, below, says what is asked and when.)
+__device__ __forceinline__ bool view_gate_hides(const ViewGate& gate, int W, int H, const V3& xyz) {
+    int v = gate.view;
+    if (gate.view_index) {
+        v = *gate.view_index;
+        if (v < 0 || v >= gate.V) return false;
+    }
+    NvCam cam;
+    nv_load_cam(cam, gate.intr, gate.w2c, v);
+    double u, w, c2;
+    if (!nv_project_xyz_depth(cam, (double)xyz.x, (double)xyz.y, (double)xyz.z, (double)W, (double)H, u, w, c2)) return false;
+    return nv_hidden(gate.planes + (size_t)v * (size_t)H * (size_t)W, W, u, w, c2, gate.slack);
+}
+
+// GATED = false is the kernel as it always was: the parameter pack is empty, so it takes no plane pointer and no argument
+// of the gate exists.  GATED = true takes ONE more argument, the ViewGate (kernels.h), and applies the rule of
+// cgs_view_forward_depth (include/curvegs.h) after splat_geometry has accepted the splat: the float32 centre s.xyz widened
+// to float64 through nv_project_xyz_depth with the view's NvCam, then nv_hidden against the view's plane -- the device
+// functions of point_projection.h as they are.  A centre the projection does not keep (behind the camera, off the image)
+// reads no plane and stays visible.  The view is gate.view, or *gate.view_index when that pointer is set (a captured graph
+// picks the step's plane on the device); a device index outside [0, V) reads nothing and hides nothing.
+template <bool GATED, typename... Gate>
 __global__ void __launch_bounds__(256) k_view_fwd(
     int B, int m, const float* __restrict__ cp, const float* __restrict__ width, const uint8_t* __restrict__ is_bezier,
     const SampleCoef* __restrict__ coef, float eps, const double* __restrict__ norms,
     const float* __restrict__ opacity_logit, const float* __restrict__ mask_logit, float mask_thr,
     const float* __restrict__ colors_precomp, const float* __restrict__ campos, ViewParams vp,
     float* __restrict__ xyz_out, float* __restrict__ rot_out, float* __restrict__ scl_out, int* __restrict__ radii,
-    SplatRec* __restrict__ rec, float* __restrict__ grad_acc, uint32_t* __restrict__ clear_words, uint32_t n_clear) {
+    SplatRec* __restrict__ rec, float* __restrict__ grad_acc, uint32_t* __restrict__ clear_words, uint32_t n_clear,
+    Gate... gate) {
+    static_assert(sizeof...(Gate) == (GATED ? 1 : 0), "the gate is an argument of the gated kernel only");
     __shared__ SampleCoef s_coef[MAX_M];
     __shared__ BlockConst s_bc;
     stage_consts(coef, m, norms, s_coef, &s_bc);
@@ -57,8 +82,12 @@ __global__ void __launch_bounds__(256) k_view_fwd(
     SplatGeom g;
     int out_radius = 0;
     if (splat_geometry(make_float3(s.xyz.x, s.xyz.y, s.xyz.z), cov3D, vp, 0, g)) {
-        rec[p] = splat_record(g, a.opac, colors_precomp ? colors_precomp[p] : 1.0f, a.all_map);
-        out_radius = (int)g.radius;
+        bool hidden = false;
+        if constexpr (GATED) hidden = view_gate_hides(gate..., vp.W, vp.H, s.xyz);
+        if (!hidden) {
+            rec[p] = splat_record(g, a.opac, colors_precomp ? colors_precomp[p] : 1.0f, a.all_map);
+            out_radius = (int)g.radius;
+        }
     }
     radii[p] = out_radius;
 }
@@ -186,12 +215,19 @@ void launch_view_forward(hipStream_t s, int B, int m, const float* cp, const flo
                          const float* mask_logit, float mask_thr, const float* colors_precomp, const float* campos,
                          const float* viewmatrix, const float* projmatrix, float tan_fovx, float tan_fovy, float focal_x,
                          float focal_y, int W, int H, int grid_x, int grid_y, float* xyz, float* rot, float* scl, int* radii,
-                         SplatRec* rec, float* grad_acc, uint32_t* clear_words, size_t n_clear) {
-    ProfScope p("view_fwd", s);
+                         SplatRec* rec, float* grad_acc, uint32_t* clear_words, size_t n_clear, const ViewGate* gate) {
+    ProfScope p(gate ? "view_fwd_depth" : "view_fwd", s);
     const ViewParams vp{viewmatrix, projmatrix, tan_fovx, tan_fovy, focal_x, focal_y, W, H, grid_x, grid_y};
-    hipLaunchKernelGGL(k_view_fwd, dim3((B * m + 255) / 256), dim3(256), 0, s, B, m, cp, width, is_bezier,
-                       reinterpret_cast<const SampleCoef*>(coef), eps, norms, opacity_logit, mask_logit, mask_thr,
-                       colors_precomp, campos, vp, xyz, rot, scl, radii, rec, grad_acc, clear_words, (uint32_t)n_clear);
+    const dim3 grid((B * m + 255) / 256), block(256);
+    const SampleCoef* cf = reinterpret_cast<const SampleCoef*>(coef);
+    if (gate)
+        hipLaunchKernelGGL((k_view_fwd<true, ViewGate>), grid, block, 0, s, B, m, cp, width, is_bezier, cf, eps, norms,
+                           opacity_logit, mask_logit, mask_thr, colors_precomp, campos, vp, xyz, rot, scl, radii, rec, grad_acc,
+                           clear_words, (uint32_t)n_clear, *gate);
+    else
+        hipLaunchKernelGGL(k_view_fwd<false>, grid, block, 0, s, B, m, cp, width, is_bezier, cf, eps, norms, opacity_logit,
+                           mask_logit, mask_thr, colors_precomp, campos, vp, xyz, rot, scl, radii, rec, grad_acc, clear_words,
+                           (uint32_t)n_clear);
 }
 void launch_view_backward(hipStream_t s, int B, int m, const float* cp, const float* width, const uint8_t* is_bezier,
                           const void* coef, float eps, double* norms, const float* opacity_logit, const float* mask_logit,

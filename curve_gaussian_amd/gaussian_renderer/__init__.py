@@ -68,7 +68,7 @@ def _grad_sinks(pc, use_mask):
 
 def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, separate_sh=False, override_color=None,
            use_trained_exp=False, use_mask=False, mask_thr=0.01, compute_visibility=True, clamp=True,
-           compute_rend_dir=True, static_bucket_cap=0, status_sink=None, fused=None, grad_sinks=False):
+           compute_rend_dir=True, static_bucket_cap=0, status_sink=None, fused=None, grad_sinks=False, depth_gate=None):
     """Render the scene.  Background tensor (bg_color) must be on the GPU.  Returns the reference's dict
     {render, viewspace_points, visibility_filter, radii, depth, rend_dir, rend_alpha} (:147-155).
 
@@ -83,7 +83,11 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, separate_
     ``grad_sinks=True`` (fused route, training loops that own their ``.grad`` buffers): the backward kernels add the gradients
     of curve points / width / opacity / mask straight into the parameters' existing ``.grad`` tensors -- the same values
     autograd's AccumulateGrad would have added, three to four kernel launches fewer per iteration; gradient hooks on those
-    parameters do not see this contribution."""
+    parameters do not see this contribution.
+    ``depth_gate=(gate, view)`` (fused route only; ``ops.train_gate.TrainGate`` and the camera's index in it, an int or a
+    one-element int32 device tensor): splats whose centre the view's depth plane hides get radius 0, exactly like
+    frustum-culled ones -- not drawn, no gradient, out of ``visibility_filter`` (``cgs_view_forward_render_depth``).  The
+    retry after a bucket overflow is gated too.  The general route has no gate: ValueError.  OFF BY DEFAULT, UNTUNED."""
     if separate_sh:   # (:108-119) GaussianRasterizer.forward() got an unexpected keyword argument 'dc'
         raise TypeError("GaussianRasterizer.forward() got an unexpected keyword argument 'dc' (render(separate_sh=True): the "
                         "reference's rasterizer has no separate-SH entry point, gaussian_renderer/__init__.py:108-119)")
@@ -101,6 +105,8 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, separate_
     if fused and not _fused_route_ok(pc, pipe, scaling_modifier, override_color):
         raise ValueError("render(fused=True): the fused view path needs a GaussianCurveModel whose derived tensors are current "
                          "and the reference's default pipeline flags")
+    if depth_gate is not None and not use_fused:
+        raise ValueError("render(depth_gate=...): the depth gate lives in the fused view forward; the general route has none")
     if use_fused:
         from ..ops import view_render as VR
         pend = []
@@ -112,7 +118,7 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, separate_
             rendered_image, depth_image, out_all_map, radii, rend_dir = VR.view_render(
                 pc._curve_points, pc._width, pc._opacity, pc._mask if use_mask else None, screenspace_points, pc.is_bezier,
                 pc.n_gaussians, mask_thr, bg_color, viewpoint_camera, tanfovx, tanfovy, static_bucket_cap, status_sink,
-                clamp and fold, compute_rend_dir and fold, pend, getattr(pc, "_derived_eps", 1e-8), sinks)
+                clamp and fold, compute_rend_dir and fold, pend, getattr(pc, "_derived_eps", 1e-8), sinks, depth_gate)
             try:
                 pkg = _package(viewpoint_camera, pc, rendered_image, radii, depth_image, out_all_map, screenspace_points,
                                use_trained_exp, clamp and not fold, compute_rend_dir and not fold, False)

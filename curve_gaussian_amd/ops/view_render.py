@@ -65,7 +65,7 @@ class _ViewRender(torch.autograd.Function):
     """The fused node over the ctypes bindings (CGS_TORCH_SHIM=0, or a CGS_LIB experiment build): the twin of
     csrc/torch_shim.cpp::ViewRenderFn, with its arguments, its outputs (color [1,H,W], invdepth [1,H,W], all_map [4,H,W],
     radii [P] int32, rend_dir, handle, image buffer) and its two library calls, cgs_view_forward_render /
-    cgs_view_backward_render.  The fast backward handles d/dcolor -- the loss of train.py:98-107 reads `render` alone.  A
+    cgs_view_backward_render -- with ``depth_gate`` the forward is cgs_view_forward_render_depth, the backward is the same.  The fast backward handles d/dcolor -- the loss of train.py:98-107 reads `render` alone.  A
     gradient arriving at inverse depth, all_map or the direction map (a depth / normal loss: the reference's rasterizer backward
     takes grad_out_depth and grad_out_all_map, diff_cur_rasterization/__init__.py:117-151) is served too: the backward then
     re-renders the view through the general operator route under autograd and pulls all upstream gradients through it
@@ -78,7 +78,7 @@ class _ViewRender(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, curve_points, width, opacity_logit, mask_logit, means2D, isb, is_bezier, coef, m, mask_thr, bg, viewmatrix,
-                projmatrix, campos, tanx, tany, H, W, cap, sync_free, clamp, want_dir, eps):
+                projmatrix, campos, tanx, tany, H, W, cap, sync_free, clamp, want_dir, eps, depth_gate=None):
         L.require_gpu_tensor(bg, "bg_color")                       # "Background tensor (bg_color) must be on GPU!" (:23)
         L.require_gpu_tensor(viewmatrix, "viewpoint_camera.world_view_transform")
         lib = L.load()
@@ -98,11 +98,17 @@ class _ViewRender(torch.autograd.Function):
             # render()'s epilogue (gaussian_renderer/__init__.py:138-145) is written by the forward compositor itself
             color_out = f32(1, H, W) if clamp else color
             rend_dir = f32(3, H, W) if want_dir else torch.empty(0, device=dev)
-            handle = L.check(lib.cgs_view_forward_render(
+            fwd_args = (
                 0 if sync_free else 1, B, m, L.ptr(cp), L.ptr(w), L.ptr(isb), L.ptr(coef), _f(eps), L.ptr(norms), L.ptr(ol),
                 L.ptr(mk), _f(mask_thr), L.ptr(geom), L.ptr(binb), nbin, L.ptr(img), cap, L.ptr(bgc), W, H, L.ptr(view),
                 L.ptr(proj), L.ptr(cpos), _f(tanx), _f(tany), L.ptr(color), L.ptr(invd), L.ptr(amap), L.ptr(radii),
-                L.ptr(color_out) if clamp else None, L.ptr(rend_dir), L.raw_stream(dev)), "cgs_view_forward_render")
+                L.ptr(color_out) if clamp else None, L.ptr(rend_dir))
+            if depth_gate is None:
+                handle = L.check(lib.cgs_view_forward_render(*fwd_args, L.raw_stream(dev)), "cgs_view_forward_render")
+            else:
+                vg = depth_gate[0].struct(depth_gate[1])
+                handle = L.check(lib.cgs_view_forward_render_depth(*fwd_args, C.byref(vg), L.raw_stream(dev)),
+                                 "cgs_view_forward_render_depth")
         ctx.save_for_backward(cp, w, ol, mk, geom, binb, img, radii, norms, bgc, view, proj, cpos, isb, coef)
         ctx.raw = color if clamp else None          # the clamp's gradient mask needs the unclamped image
         ctx.is_bezier, ctx.ran_backward = is_bezier, False
@@ -117,7 +123,7 @@ class _ViewRender(torch.autograd.Function):
         B, m, H, W, mask_thr, tanx, tany, eps = ctx.dims
         if g_invd is not None or g_amap is not None or g_dir is not None:
             return _general_backward(cp, w, ol, mk, bgc, view, proj, cpos, ctx.is_bezier, m, H, W, mask_thr, tanx, tany, eps,
-                                     ctx.raw is not None, g_color, g_invd, g_amap, g_dir) + (None,) * 18
+                                     ctx.raw is not None, g_color, g_invd, g_amap, g_dir) + (None,) * 19
         if ctx.ran_backward:
             # a second backward over this forward (retain_graph): the two grid-wide sums of the sampling backward were cleared
             # by the forward's norm pass once (include/curvegs.h: one view backward per view forward) -- clear them again,
@@ -140,7 +146,7 @@ class _ViewRender(torch.autograd.Function):
                     L.ptr(geom), L.ptr(binb), L.ptr(img), L.ptr(bgc), W, H, L.ptr(view), L.ptr(proj), L.ptr(cpos), _f(tanx),
                     _f(tany), L.ptr(radii), L.ptr(g_color), L.ptr(ctx.raw), L.ptr(g_m2d), L.ptr(g_cp), L.ptr(g_w), L.ptr(g_ol),
                     L.ptr(g_mk), L.ptr(scratch), 0, L.raw_stream(dev)), "cgs_view_backward_render")
-        return (g_cp, g_w, g_ol, g_mk, g_m2d) + (None,) * 18
+        return (g_cp, g_w, g_ol, g_mk, g_m2d) + (None,) * 19
 
 
 def _general_backward(cp, w, ol, mk, bgc, view, proj, campos, is_bezier, m, H, W, mask_thr, tanx, tany, eps, clamped, g_color,
@@ -193,7 +199,8 @@ _cpp_ready = []
 
 
 def view_render(curve_points, width, opacity_logit, mask_logit, means2D, is_bezier, m, mask_thr, bg, cam, tanx, tany,
-                static_cap=0, status_sink=None, clamp=False, want_dir=False, pending_out=None, eps=1e-8, grad_sinks=None):
+                static_cap=0, status_sink=None, clamp=False, want_dir=False, pending_out=None, eps=1e-8, grad_sinks=None,
+                depth_gate=None):
     """-> (image [1,H,W] (clamped to [0,1] when `clamp`), inverse depth [1,H,W], all_map [4,H,W], radii [P], world-space
     direction map [3,H,W] or an empty tensor).  Eager callers (static_cap == 0) pass a list as `pending_out`: it receives the
     forward's `Pending`, to be handed to finish() once the caller has queued whatever else it has; without it the call waits
@@ -202,7 +209,12 @@ def view_render(curve_points, width, opacity_logit, mask_logit, means2D, is_bezi
     `grad_sinks` (compiled shim only; ignored otherwise): float32 tensors shaped like (curve_points, width, opacity_logit[,
     mask_logit]) -- normally the parameters' `.grad` -- that the backward kernels ADD their gradients to; the node then hands
     autograd no gradient for those inputs (no AccumulateGrad kernels).  A loss that reaches depth / all_map / the direction
-    map takes the general backward, which returns its gradients the ordinary way."""
+    map takes the general backward, which returns its gradients the ordinary way.
+
+    `depth_gate` (both bindings): ``(TrainGate, view)`` -- the forward is cgs_view_forward_render_depth, which gives every splat
+    whose centre the view's depth plane hides radius 0 (include/curvegs.h); `view` is the camera's index in the gate's stack,
+    an int or a one-element int32 device tensor.  The backward is unchanged: it skips radii == 0.  (A loss that reaches depth /
+    all_map / the direction map re-renders through the general route, which has no gate.)"""
     L.require_gpu_tensor(curve_points, "curve_points")
     lib = L.load()
     dev = curve_points.device
@@ -210,6 +222,8 @@ def view_render(curve_points, width, opacity_logit, mask_logit, means2D, is_bezi
     P = curve_points.shape[0] * m
     isb, coef = _bezier_mask(is_bezier, dev), sample_coefficients(m, dev)
     cap = int(static_cap) if static_cap else _capacity(lib, dev, P, W, H)
+    if depth_gate is not None:
+        depth_gate[0].check(H, W, dev)
     args = (curve_points, width, opacity_logit, mask_logit, means2D, isb, is_bezier, coef, m, mask_thr, bg, cam.world_view_transform,
             cam.full_proj_transform, cam.camera_center, tanx, tany, H, W, cap, bool(static_cap), bool(clamp), bool(want_dir), eps)
     if L.use_shim():
@@ -219,9 +233,14 @@ def view_render(curve_points, width, opacity_logit, mask_logit, means2D, is_bezi
         if not _cpp_ready:
             shim.set_general_backward(_general_backward)
             _cpp_ready.append(True)
-        color, invd, amap, radii, rend_dir, handle, img = shim.view_render(*args, grad_sinks)
+        if depth_gate is None:
+            color, invd, amap, radii, rend_dir, handle, img = shim.view_render(*args, grad_sinks)
+        else:
+            planes, intr, w2c, slack, v, idx = depth_gate[0].tensors(depth_gate[1])
+            color, invd, amap, radii, rend_dir, handle, img = shim.view_render(
+                *args, grad_sinks, [planes, intr, w2c] + ([idx] if idx is not None else []), slack, v)
     else:
-        color, invd, amap, radii, rend_dir, handle, img = _ViewRender.apply(*args)
+        color, invd, amap, radii, rend_dir, handle, img = _ViewRender.apply(*args, depth_gate)
     if static_cap:
         # sync-free (stream-ordered / graph-captured callers): nothing is read back, the caller checks the status words it is
         # handed through status_sink

@@ -150,8 +150,9 @@ def make_scene(dataset, opt, device):
     return scene, gaussians
 
 
-def make_step(backend, gaussians, cameras, opt, seed=0):
-    """The per-iteration object of `backend` with train.py's loss weights, every regulariser and the statistics on."""
+def make_step(backend, gaussians, cameras, opt, seed=0, depth_gate=None, gate_from_iter=0):
+    """The per-iteration object of `backend` with train.py's loss weights, every regulariser and the statistics on;
+    ``depth_gate`` (an ``ops.train_gate.TrainGate`` over ``cameras``) gates the training render from ``gate_from_iter`` on."""
     from .train_step import GraphedTrainStep, TrainStep
     if backend not in BACKENDS:
         raise ValueError(f"training: unknown backend {backend!r} (one of {BACKENDS})")
@@ -161,6 +162,8 @@ def make_step(backend, gaussians, cameras, opt, seed=0):
               opacity_loss_weight=opt.opacity_loss_weight, lambda_curve_smo=opt.lambda_curve_smo,
               lambda_width=opt.lambda_width, lambda_points_conn=opt.lambda_points_conn, conn_from_iter=opt.conn_from_iter,
               densification_stats=True)
+    if depth_gate is not None:
+        kw.update(depth_gate=depth_gate, gate_from_iter=gate_from_iter)
     if backend == "graphed":
         return GraphedTrainStep(gaussians, cameras, gts, **kw)
     return TrainStep(gaussians, cameras, gts, fused=backend != "torch", direct=backend == "direct", **kw)
@@ -190,7 +193,7 @@ def _export(gaussians, dataset, opt, visibility_options=None):
 
 def training(dataset, opt, testing_iterations, saving_iterations, checkpoint_iterations, checkpoint=None, backend="graphed",
              seed=0, device="cuda", quiet=False, scene=None, step=None, report=None, save_ply=None, save_checkpoint=None,
-             export=None, draw=False, topology_backend="host", report_writer=None):
+             export=None, draw=False, topology_backend="host", report_writer=None, train_gate=None, gate_from_iter=0):
     """train.py:38-248.  Returns {"events": [(iteration, event, n_curves_after)] for every edit, report, save, checkpoint and
     the export, "losses": {iteration: loss} (the first iteration and every iteration run with a deferred update),
     "first_iter", "scene", "gaussians"}.
@@ -204,7 +207,11 @@ def training(dataset, opt, testing_iterations, saving_iterations, checkpoint_ite
     and merge_curves in numpy like the reference, "gpu" in the kernels of ops/curve_fit.py (scene/topology.py); the schedule and
     the event log are the same.  ``report_writer``: a summary writer (``evaluation.ReportDirWriter``, a tensorboard
     ``SummaryWriter``) handed to the default ``report``, which then writes the reference's scalar and image summaries at the
-    test iterations; None writes nothing.  An injected ``report`` is called as before and never sees it."""
+    test iterations; None writes nothing.  An injected ``report`` is called as before and never sees it.
+    ``train_gate`` (--gate_training; OFF BY DEFAULT, UNTUNED): ``cameras -> keywords of ops.train_gate.TrainGate``, called with
+    the train cameras; the gate built from them culls, from iteration ``gate_from_iter`` on, every splat of the training render
+    whose centre its view's depth plane hides, and ``<model_path>/train_gate.json`` is written after the export
+    (``write_train_gate_report``).  Not with an injected ``step`` or ``backend="torch"``."""
     from .scene.topology import _check_backend
     _check_backend(topology_backend)
     topo = {} if topology_backend == "host" else {"backend": topology_backend}
@@ -215,7 +222,17 @@ def training(dataset, opt, testing_iterations, saving_iterations, checkpoint_ite
     if checkpoint:                                                                  # :49-51
         model_params, first_iter = torch.load(checkpoint, weights_only=False)
         gaussians.restore(model_params, opt)
-    step = step if step is not None else make_step(backend, gaussians, scene.getTrainCameras(), opt, seed)
+    gate = None
+    if train_gate is not None:
+        if step is not None or backend == "torch":
+            raise ValueError("training(train_gate=...): the depth gate lives in the fused view forward of this package's own "
+                             "steps (not backend='torch', not an injected step)")
+        from .ops.train_gate import TrainGate
+        cams = scene.getTrainCameras()
+        gate = TrainGate(cams, device=gaussians._curve_points.device, **train_gate(cams))
+        say(f"Training gate: {gate.V} planes of {gate.width}x{gate.height}, {gate.planes_bytes} bytes, slack {gate.slack:g}, "
+            f"from iteration {int(gate_from_iter)}")
+    step = step if step is not None else make_step(backend, gaussians, scene.getTrainCameras(), opt, seed, gate, gate_from_iter)
     step.start_at(first_iter)
     bg = torch.tensor([1, 1, 1] if dataset.white_background else [0, 0, 0], dtype=torch.float32,
                       device=gaussians._curve_points.device)                        # :53-54
@@ -293,7 +310,32 @@ def training(dataset, opt, testing_iterations, saving_iterations, checkpoint_ite
     finish()
     export(gaussians, dataset, opt)                                                 # :248
     log(opt.iterations, "export")
+    if gate is not None:
+        write_train_gate_report(os.path.join(dataset.model_path, "train_gate.json"), gaussians, gate, gate_from_iter)
     return {"events": events, "losses": losses, "first_iter": first_iter, "scene": scene, "gaussians": gaussians}
+
+
+def write_train_gate_report(path, gaussians, gate, gate_from_iter=0, backend="gpu"):
+    """``train_gate.json`` of a gated run, from the FINAL splat centres and existing operators only: per view what
+    ``point_masks_depth`` counts (the centres the view keeps and does not hide, and those it hides), and per splat, from the
+    same rule on the host (``ops.train_gate.splat_visibility``), how many views see it, how many of those hide it, and whether
+    it is "dead": hidden in EVERY view that sees it, so that no gradient of a gated run can reach it.  ``backend``: where
+    ``point_masks_depth`` runs ("host" for a gate built on the host).  Returns the dict."""
+    import json
+    from .ops.edge_occlusion import point_masks_depth
+    from .ops.train_gate import splat_visibility
+    xyz = gaussians.get_xyz.detach().float().contiguous()
+    _mask, kept, hidden_v = point_masks_depth(xyz, gate.intr, gate.w2c, gate.planes, gate.slack, backend=backend,
+                                              return_counts=True)
+    seen, hidden, dead = splat_visibility(xyz, gate)
+    out = {"settings": dict(gate.settings(), gate_from_iter=int(gate_from_iter)), "splats": int(xyz.shape[0]),
+           "views": [{"kept": int(k), "hidden": int(h)} for k, h in zip(kept.cpu().tolist(), hidden_v.cpu().tolist())],
+           "never_seen": int((seen == 0).sum()), "hidden_somewhere": int((hidden > 0).sum()), "dead": int(dead.sum()),
+           "seen_views": [int(x) for x in seen], "hidden_views": [int(x) for x in hidden],
+           "dead_splats": [int(i) for i in dead.nonzero()[0]]}
+    with open(path, "w") as f:
+        json.dump(out, f)
+    return out
 
 
 def select_options(source_path, detector):
@@ -397,6 +439,17 @@ def build_parser():
                         "the depth source that --occluder or --depth_dir names (with --near_clip): a control or end point the "
                         "depth hides is dropped before its frame is judged (needs one of the two, and the check itself: "
                         "--visible_checking; untuned, checked on drawn solids only)")
+    p.add_argument("--gate_training", action="store_true",
+                   help="the TRAINING render also takes the depth source that --occluder or --depth_dir names (with "
+                        "--depth_window and --near_clip): in every view, a splat whose centre the view's depth plane hides is "
+                        "culled like a frustum-culled one -- not drawn, no gradient; train_gate.json in the model directory "
+                        "tallies the final splats (needs exactly one of the two sources; not with --backend torch; OFF BY "
+                        "DEFAULT, untuned, checked on drawn solids only)")
+    p.add_argument("--train_gate_slack", type=float, default=None, metavar="S",
+                   help="--gate_training: how far behind the plane a centre may lie, in world units (default: the chain's "
+                        "depth slack, untuned)")
+    p.add_argument("--gate_from_iter", type=int, default=0, metavar="N",
+                   help="--gate_training: the gate applies from iteration N on (default 0: from the start)")
     p.add_argument("--snap_edges", action="store_true",
                    help="after the export, FIRST move every edge of parametric_edges.json onto the detected edges of the "
                         "train cameras' edge maps: edge_snap.json and parametric_edges_snapped.json in the model directory; "
@@ -519,6 +572,14 @@ def parse_args(argv):
         parser.error("--gate_visibility needs a depth source: --occluder or --depth_dir")
     if args.gate_visibility and args.occluder is not None and args.depth_dir is not None:
         parser.error("--gate_visibility takes one depth source: --occluder or --depth_dir, not both")
+    if args.gate_training and (args.occluder is None) == (args.depth_dir is None):
+        parser.error("--gate_training needs exactly one depth source: --occluder or --depth_dir")
+    if args.gate_training and args.backend == "torch":
+        parser.error("--gate_training gates the fused view forward: not with --backend torch")
+    if not args.gate_training and (args.train_gate_slack is not None or args.gate_from_iter != 0):
+        parser.error("--train_gate_slack and --gate_from_iter belong to --gate_training")
+    if args.gate_training and ((args.train_gate_slack is not None and not args.train_gate_slack >= 0) or args.gate_from_iter < 0):
+        parser.error("--train_gate_slack and --gate_from_iter are >= 0")
     if args.near_clip is not None and args.occluder is None:
         parser.error("--near_clip needs --occluder: the mesh that is clipped")
     if args.init_near_clip is not None and args.init_occluder is None:
@@ -576,9 +637,13 @@ def main(argv=None):
             cams = emap_cameras(dataset.source_path, dataset.detector)[0]
         vis = gate_options(args, dataset.source_path, cams, flag="gate_visibility")
         export = lambda g, d, o: _export(g, d, o, vis)
+    train_gate = {}
+    if args.gate_training:
+        train_gate = dict(train_gate=lambda cams: train_gate_options(args, dataset.source_path, cams),
+                          gate_from_iter=args.gate_from_iter)
     out = training(dataset, opt, args.test_iterations, args.save_iterations, args.checkpoint_iterations, args.start_checkpoint,
                    backend=args.backend, seed=args.seed, quiet=args.quiet, draw=args.draw_snapshots,
-                   topology_backend=args.topology_backend, report_writer=writer, export=export)
+                   topology_backend=args.topology_backend, report_writer=writer, export=export, **train_gate)
     if args.reprojection_score:
         from .edge_extraction.reprojection import scan_line, score_scene
         gate = {}
@@ -620,6 +685,16 @@ def gate_options(args, source_path, cameras, flag="gate_edge_checks"):
         gate["depth_maps"] = scan_depth_maps(os.path.join(source_path, args.depth_dir), cameras)
     if getattr(args, "near_clip", None) is not None:   # (the operators reject it without an occluder)
         gate["near_clip"] = args.near_clip
+    return gate
+
+
+def train_gate_options(args, source_path, cameras):
+    """The keywords of ``ops.train_gate.TrainGate`` under --gate_training: ``gate_options`` of the train cameras (a Scene's;
+    the depth maps of --depth_dir are found by their names), with --train_gate_slack in place of the slack when it is given."""
+    from .edge_extraction.reprojection import scene_cameras
+    gate = gate_options(args, source_path, scene_cameras(cameras)[0], flag="gate_training")
+    if args.train_gate_slack is not None:
+        gate["depth_slack"] = args.train_gate_slack
     return gate
 
 

@@ -27,8 +27,21 @@ class TrainStep:
     def __init__(self, gaussians, cameras, gt_images, lambda_mse=10.0, lambda_dssim=0.1, lambda_mask=0.0005,
                  densify_until_iter=7000, mask_threshold=0.01, seed=0, rank=0, world=1, fused=True,
                  regularisers=False, opacity_loss_weight=0.01, lambda_curve_smo=0.1, lambda_width=0.01,
-                 lambda_points_conn=0.1, conn_from_iter=7000, direct=False, densification_stats=False):
+                 lambda_points_conn=0.1, conn_from_iter=7000, direct=False, densification_stats=False, depth_gate=None,
+                 gate_from_iter=0):
         self.g = gaussians
+        # depth_gate (an ops.train_gate.TrainGate over `cameras`, in their order; OFF BY DEFAULT, UNTUNED): from iteration
+        # gate_from_iter on, every render of the loop -- the redo after a bucket overflow included -- goes through the gated
+        # forward: a splat whose centre the view's depth plane hides is treated like a frustum-culled one (no gradient, out
+        # of the statistics and the regularisers' visible set).  Fused route only; not exercised with world > 1.
+        if depth_gate is not None:
+            if world > 1:
+                raise ValueError("TrainStep(depth_gate=...): the depth gate has not been exercised view-parallel (world > 1)")
+            if not fused:
+                raise ValueError("TrainStep(depth_gate=...): the depth gate lives in the fused view forward (fused=True)")
+            if depth_gate.V != len(cameras):
+                raise ValueError(f"TrainStep(depth_gate=...): the gate holds {depth_gate.V} planes, the loop {len(cameras)} cameras")
+        self.depth_gate, self.gate_from_iter = depth_gate, int(gate_from_iter)
         # densification_stats=True: every iteration before densify_until_iter adds the view's statistics (train.py:184-187:
         # max_radii2D, xyz_gradient_accum, denom) after the backward, in one launch without a host sync
         # (GaussianCurveModel.accumulate_densification_stats, csrc/densify.hip)
@@ -120,6 +133,10 @@ class TrainStep:
         """Continue a resumed run: the next step() is iteration + 1 (train.py:49-51, 73)."""
         self.iteration = int(iteration)
 
+    def _gate_active(self, iteration):
+        """The depth gate applies from iteration gate_from_iter on."""
+        return self.depth_gate is not None and iteration >= self.gate_from_iter
+
     def _stats_active(self, iteration):
         """train.py:184: the statistics are gathered while `iteration < opt.densify_until_iter`."""
         return self.densification_stats and iteration < self.densify_until_iter
@@ -148,12 +165,14 @@ class TrainStep:
         cam, gt = self.cams[vi], self.gts[vi]
         use_mask = it >= self.densify_until_iter
         gate = 1.0 if self.reset_timestep > 0 else 0.0
+        depth_gate = (self.depth_gate, vi) if self._gate_active(it) else None
         if direct:
-            loss, pkg = self._step_direct(cam, gt, gate, use_mask, self._conn_active(it), self._stats_active(it))
+            loss, pkg = self._step_direct(cam, gt, gate, use_mask, self._conn_active(it), self._stats_active(it), depth_gate)
         else:
             pkg = render(cam, g, self.pipe, self.bg, use_mask=use_mask, mask_thr=self.mask_threshold,
                          compute_visibility=not self.fused, clamp=not self.fused, compute_rend_dir=not self.fused,
-                         grad_sinks=self.fused)   # (fused: the backward kernels add into the flat gradient buffer themselves)
+                         grad_sinks=self.fused,   # (fused: the backward kernels add into the flat gradient buffer themselves)
+                         depth_gate=depth_gate)
             loss = self._autograd_loss(pkg, gt[:1], None, gate, use_mask, self._conn_active(it), self._stats_active(it))
         self.flat.all_reduce()
         self._finish(update)
@@ -283,10 +302,11 @@ class TrainStep:
         self.g.prepare_scaling_rot()
 
 
-    def _step_direct(self, cam, gt, gate, use_mask, use_conn, use_stats):
+    def _step_direct(self, cam, gt, gate, use_mask, use_conn, use_stats, depth_gate=None):
         """TrainStep.step() from the render to the statistics, without autograd (TrainStep(direct=True)): train.py:95-146,
         :184-187 as library calls.  The forward is the checked one (exact binning: a bucket overflow re-renders with the
-        raised capacity before anything reached the gradient buffer)."""
+        raised capacity before anything reached the gradient buffer); with depth_gate = (TrainGate, view) it is the gated one,
+        re-renders included."""
         g = self.g
         lib = L.load()
         if not L.use_shim():
@@ -309,6 +329,11 @@ class TrainStep:
         gt1 = gt[:1].detach().float().contiguous()
         n_pos = edge_pixel_count(gt1)
         a, bb = photometric_weights(self.lambda_mse, self.lambda_dssim)
+        gate_args = ()
+        if depth_gate is not None:
+            depth_gate[0].check(H, W, dev)
+            planes, intr, w2c, slack, gv, gidx = depth_gate[0].tensors(depth_gate[1])
+            gate_args = ([planes, intr, w2c] + ([gidx] if gidx is not None else []), slack, gv)
         with L.device_guard(dev):
             st = L.raw_stream(dev)
             ws = photometric_workspace(dev, H, W, st)
@@ -316,7 +341,7 @@ class TrainStep:
                 cap = VR._capacity(lib, dev, P, W, H)
                 color, invd, amap, radii, _dir, _raw, saved, handle = L.shim().view_forward(
                     cp, wl, ol, mask, isb, coef, m, self.mask_threshold, self.bg, cam.world_view_transform, cam.full_proj_transform,
-                    cam.camera_center, tanx, tany, H, W, cap, False, False, False, eps)
+                    cam.camera_center, tanx, tany, H, W, cap, False, False, False, eps, *gate_args)
                 pend = VR.Pending(handle, (dev.index, P, W, H), cap, saved[6])
                 # value and d loss / d image behind the compositor (render()'s clamp inside the loss kernels), then the wait for
                 # the forward's 16-byte status readback -- the compositor and the loss are already queued behind it
@@ -436,6 +461,11 @@ class GraphedTrainStep(TrainStep):
         self._use_mask = False
         self._use_conn = False      # graph constant like _use_mask: the switch at conn_from_iter re-captures
         self._use_stats = False     # likewise: the statistics stop at densify_until_iter
+        self._use_gate = False      # likewise: the depth gate starts at gate_from_iter (another forward entry: re-capture)
+        if self.depth_gate is not None:
+            if self.direct and not self.fused_view:
+                raise ValueError("GraphedTrainStep(depth_gate=...): the gate needs the fused per-view entry points (fused_view=True)")
+            self.depth_gate.check(H, W, dev)
         self._stats_ptrs = None     # the statistics buffers the graph writes (restore() replaces them: re-capture)
         self._flag_host = torch.zeros(64, dtype=torch.int32).pin_memory()
         # single-GPU replays: the captured Adam kernel reports "this iteration was skipped" straight into that pinned ring
@@ -458,7 +488,9 @@ class GraphedTrainStep(TrainStep):
         g.prepare_scaling_rot()
         pkg = render(self._cam, g, self.pipe, self.bg, use_mask=self._use_mask, mask_thr=self.mask_threshold,
                      compute_visibility=False, clamp=False, compute_rend_dir=False,
-                     static_bucket_cap=self._cap, status_sink=sink)
+                     static_bucket_cap=self._cap, status_sink=sink,
+                     # (the step's view is read on the device from the staging slot, like the ground-truth map's)
+                     depth_gate=(self.depth_gate, self._view_idx) if self._use_gate else None)
         status = sink[0]
         # sync-free: the phase switches are graph constants (a switch re-captures), the opacity term is gated by a device
         # scalar refreshed per step, and the statistics are gated like the Adam step (an overflowed replay adds nothing)
@@ -539,12 +571,17 @@ class GraphedTrainStep(TrainStep):
         aux = self.aux_outputs or not self.fused_view
         # ---- forward: curves -> splats -> per-view attributes -> rasterizer (sync-free) -> loss
         if self.fused_view:     # the fused per-view entry points: 8 launches for render + its backward instead of 13
-            chk(lib.cgs_view_forward(
+            fwd_args = (
                 B, m, p(cp), p(wl), p(b["isb"]), p(b["coef"]), cf(1e-8), p(b["norms"]), p(ol), p(mask), cf(self.mask_threshold),
                 None, p(b["geom"]), p(b["bin"]), b["nbin"], p(b["img"]), self._cap, p(b["bg"]), W, H,
                 p(cam.world_view_transform), p(cam.full_proj_transform), p(cam.camera_center), tanx, tany, p(b["color"]),
                 p(b["invd"]) if aux else None, p(b["omap"]) if aux else None, p(b["radii"]),
-                p(b["xyz"]), p(b["rot"]), p(b["scl"]), s), "view_forward")
+                p(b["xyz"]), p(b["rot"]), p(b["scl"]))
+            if self._use_gate:   # the step's plane and camera are picked on the device: the view index of the staging slot
+                vg = self.depth_gate.struct(self._view_idx)
+                chk(lib.cgs_view_forward_depth(*fwd_args, C.byref(vg), s), "view_forward_depth")
+            else:
+                chk(lib.cgs_view_forward(*fwd_args, s), "view_forward")
         else:
             chk(lib.cgs_sample_curves_forward(B, m, p(cp), p(wl), p(b["isb"]), p(b["coef"]), cf(1e-8), p(b["norms"]),
                                               p(b["xyz"]), p(b["rot"]), p(b["scl"]), s), "sample_curves_forward")
@@ -740,10 +777,12 @@ class GraphedTrainStep(TrainStep):
         use_mask = self.iteration + 1 >= self.densify_until_iter
         use_conn = self._conn_active(self.iteration + 1)
         use_stats = self._stats_active(self.iteration + 1)
+        use_gate = self._gate_active(self.iteration + 1)
         if (use_mask != self._use_mask or use_conn != self._use_conn or use_stats != self._use_stats
+                or use_gate != self._use_gate
                 or self._stats_moved()):   # a phase of train.py starts (or the captured buffers moved): re-capture
             self.finish()
-            self._use_mask, self._use_conn, self._use_stats = use_mask, use_conn, use_stats
+            self._use_mask, self._use_conn, self._use_stats, self._use_gate = use_mask, use_conn, use_stats, use_gate
             self._graph = None
         self._check_overflow()
         self.iteration += 1

@@ -203,6 +203,69 @@ int cgs_view_forward_render(int checked, int B, int m, const float* curve_points
                             void* stream);
 int64_t cgs_view_forward_wait(int handle, int64_t* n_visible);
 void cgs_view_forward_abandon(int handle);
+/* ------------------------------------------------------------------------------------------------
+ * The depth gate on the TRAINING render: cgs_view_forward and cgs_view_forward_render -- the two forwards every training
+ * route calls -- with the occlusion rule of cgs_point_mask_depth (nv_hidden, csrc/point_projection.h) applied per splat
+ * inside the fused per-splat kernel (k_view_fwd<true>, csrc/view.hip).  The edge map of a real scan of a solid has its
+ * hidden lines removed; without the gate a curve on a far rim is drawn into every view that looks at it through the solid
+ * and the photometric loss of those views pushes against it.  Opt-in, OFF BY DEFAULT, UNTUNED; the five ungated forwards are
+ * unchanged to the bit.  cgs_view_forward_shared, cgs_view_forward_checked and cgs_view_forward_begin get NO gated sibling:
+ * shared-sampling view batches are out of the gate's scope, and the checked / two-halves forms are reached through
+ * cgs_view_forward_render_depth(checked != 0), which returns the handle cgs_view_forward_wait takes.
+ *
+ * Each entry takes the arguments of its sibling, with their meaning and their checks, plus `gate` before the stream:
+ *   planes      float32 [V,height,width], device: camera z per training view, +inf where there is no surface (the planes of
+ *               cgs_mesh_depth / cgs_surfel_depth / the caller's maps, usually after cgs_depth_window_max), ALL views resident
+ *   intr, w2c   float64 [V,4] = (fx, fy, cx, cy) and [V,12] = [R | T] row-major, device: the cameras the planes were drawn with
+ *   view_index  int32 [1], device, or NULL.  When set the kernel reads the view from it (a captured graph picks the step's
+ *               plane and camera the way cgs_photometric_loss_indexed picks its ground-truth map) and `view` is ignored; a
+ *               value outside [0, V) reads nothing and hides nothing
+ *   slack       float64 >= 0 in the units of the planes; +inf is allowed and hides nothing
+ *   V, view     the number of views in the stack and, without view_index, this forward's view in [0, V)
+ *   height, width   the planes' size: it must be the image's (height_px, width_px)
+ *
+ * THE RULE, frozen, for splat p and the gate's view v:
+ *   1. splat_geometry decides first, as in the sibling: a splat it rejects (behind the near plane, outside the frustum,
+ *      degenerate) gets radius 0 and the plane is not read.
+ *   2. Otherwise X = the splat's centre, the float32 sample position of the kernel (the bits of the xyz output), widened to
+ *      float64, goes through the projection of cgs_point_mask_depth with view v's camera: c = R X + T with every row
+ *      ((r0*X + r1*Y) + r2*Z) + t, u = fx * (c0 / c2) + cx, v = fy * (c1 / c2) + cy, float64, one rounded operation at a time.
+ *   3. If c2 <= 0 or (u, v) is outside [0, width) x [0, height) the splat is visible exactly as without the gate and the plane
+ *      is not read: a large splat whose centre is off the image keeps drawing.
+ *   4. Otherwise the splat is HIDDEN iff c2 > (double)planes[v][floor(v)][floor(u)] + slack (a NaN entry hides nothing):
+ *      radii[p] = 0 and no splat record is written; else nothing changes.
+ * A hidden splat is never binned; cgs_view_backward skips radii == 0, so it receives no gradient from this view and stays out of
+ * the densification statistics and the regularisers' visible set -- exactly how a frustum-culled splat is treated.  The gate
+ * is piecewise constant and has no derivative of its own.  It judges the splat's CENTRE, not its footprint.  The stack is
+ * indexed in size_t.  With planes that hide nothing (all +inf, or slack = +inf) every output equals the sibling's to the bit.
+ *
+ * CGS_ERR_INVALID_ARGUMENT, before anything is launched and with a message naming the entry that was called: a NULL gate; a NULL
+ * planes / intr / w2c; V < 1; without view_index a view outside [0, V); a slack that is negative or NaN; planes whose size
+ * is not the image's.  Checked after the sibling's own arguments and before the bucket capacity.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct cgs_view_gate {
+    const float* planes;
+    const double* intr;
+    const double* w2c;
+    const int32_t* view_index;
+    double slack;
+    int32_t V, view, height, width;
+} cgs_view_gate;
+int cgs_view_forward_depth(int B, int m, const float* curve_points, const float* width, const uint8_t* is_bezier, const float* coef,
+                           float eps, double* norms, const float* opacity_logit, const float* mask_logit, float mask_thr,
+                           const float* colors_precomp, void* geometry_buffer, void* binning_buffer, size_t binning_bytes,
+                           void* image_buffer, uint32_t bucket_capacity, const float* background, int width_px, int height_px,
+                           const float* viewmatrix, const float* projmatrix, const float* cam_pos, float tan_fovx, float tan_fovy,
+                           float* out_color, float* out_invdepth, float* out_all_map, int* radii, float* xyz, float* rotation,
+                           float* scaling, const cgs_view_gate* gate, void* stream);
+int cgs_view_forward_render_depth(int checked, int B, int m, const float* curve_points, const float* width,
+                                  const uint8_t* is_bezier, const float* coef, float eps, double* norms,
+                                  const float* opacity_logit, const float* mask_logit, float mask_thr, void* geometry_buffer,
+                                  void* binning_buffer, size_t binning_bytes, void* image_buffer, uint32_t bucket_capacity,
+                                  const float* background, int width_px, int height_px, const float* viewmatrix,
+                                  const float* projmatrix, const float* cam_pos, float tan_fovx, float tan_fovy, float* out_color,
+                                  float* out_invdepth, float* out_all_map, int* radii, float* out_color_clamped,
+                                  float* out_rend_dir, const cgs_view_gate* gate, void* stream);
 /* Epilogue of render() on the fused route, /root/reference/gaussian_renderer/__init__.py:138-145 in one launch: color_out [H,W] =
  * clamp ? clamp(color_raw, 0, 1) : color_raw (NULL: skipped); dir_out [3,H,W] = all_map[0:3] taken from view to world space,
  * out_i = sum_k all_map[k] * viewmatrix[4 i + k] (viewmatrix = world_view_transform, row-major 4x4; NULL: skipped).
